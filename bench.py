@@ -330,6 +330,24 @@ def compact_line(full):
     return out
 
 
+DUMP_MAX_SCORES = 4 << 20      # 16 MB of float32 scores; a larger batch is dumped as a fixed sample (+ its float64 indices)
+
+
+def dump_outputs(out_dir, lcp, best_lcp, best_gid):
+    """--dump-outputs: what a caller of the timed path receives from its last step -- every candidate's LCP score and the
+    arg-max key unpacked (score, global candidate id) -- as .npy files.  The inputs are seeded (synth), so two builds run
+    with the same arguments can be compared file for file."""
+    os.makedirs(out_dir, exist_ok=True)
+    scores = np.ascontiguousarray(lcp, np.float32)
+    if len(scores) > DUMP_MAX_SCORES:
+        idx = np.sort(np.random.Generator(np.random.PCG64(0x5EED00D0)).choice(len(scores), DUMP_MAX_SCORES, replace=False))
+        np.save(os.path.join(out_dir, "lcp_scores_sample_index.npy"), idx.astype(np.float64))
+        scores = scores[idx]
+    np.save(os.path.join(out_dir, "lcp_scores.npy"), scores)
+    np.save(os.path.join(out_dir, "best_lcp.npy"), np.array([best_lcp], np.float32))
+    np.save(os.path.join(out_dir, "best_candidate_id.npy"), np.array([best_gid], np.float64))
+
+
 def cpu_pipeline_baseline(model, scene, device, threads, cm_attempts=8):
     """The reference's CPU path over the WHOLE path, beside the GPU's whole-path numbers: the oracle's restated run_stocs_estimation
     (oracle/stocs_oracle.cpp orc_run_mode, one thread like the reference) reports the same three spans the reference's driver prints --
@@ -406,7 +424,11 @@ def main():
     ap.add_argument("--no-cpu-pipeline", action="store_true", help="skip the CPU whole-path baseline (oracle run_stocs_estimation at Cm and on the ycb frame)")
     ap.add_argument("--details", default="", help="where the full record goes (default: bench_details.json next to this script, and gpurun_out/ when it exists)")
     ap.add_argument("--pmc-groups", default="", help="comma-separated counter groups of tools/pmc.py for the live passes (default: all)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed (rank 0's scores, the arg-max over all ranks) to DIR/<name>.npy, to compare two builds")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # --gpus N > 1 without a launcher around it: this process becomes the launcher of N rank children (before torch or the
     # GPU runtime is loaded) and relays rank 0's JSON line; it never runs one rank under an N-GPU label
@@ -530,6 +552,8 @@ def main():
     if world == 1:
         i_chk = int(np.argmax(lcp))
         assert final_gid == i_chk and final_lcp == float(lcp[i_chk]), (final_gid, i_chk)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, lcp, final_lcp, final_gid)
     b_pose = 68 + 52 * est.nM                      # algorithmic bytes per pose
     best_i = int(np.argmax(lcp))
     run_pmc = rank == 0 and world == 1 and not args.no_pmc

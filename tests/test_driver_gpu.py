@@ -244,6 +244,36 @@ def test_bench_gpus_2_without_a_launcher_runs_two_ranks():
 
 
 @pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_steps_scores(tmp_path, oracle_lib):
+    """`bench.py --dump-outputs DIR` writes what the timed path computed in its last step -- every candidate's score and the
+    arg-max -- as .npy files: the same files from run to run (seeded inputs), the oracle's scores on the same batch.  The line
+    reports the --steps it was given and ms_per_step."""
+    import json
+    from model_matching_amd import synth
+    dumps = []
+    for run in range(2):
+        d = tmp_path / ("dump%d" % run)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--no-pmc", "--no-cpu-baseline",
+                            "--no-pipeline", "--no-c5", "--workload", "small", "--details", str(tmp_path / "details.json"), "--dump-outputs", str(d)],
+                           capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0
+        dumps.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert sorted(a) == ["best_candidate_id.npy", "best_lcp.npy", "lcp_scores.npy"]
+    for f in a:
+        assert a[f].dtype in (np.float32, np.float64) and a[f].dtype == b[f].dtype and np.array_equal(a[f], b[f]), f
+    got = a["lcp_scores.npy"]
+    assert got.shape == (2048,) and int(a["best_candidate_id.npy"][0]) == int(np.argmax(got)) and a["best_lcp.npy"][0] == got.max() > 0
+    m, s, k = synth.workload("small")
+    orc = oracle_lib.Oracle(s.pos, s.nrm, s.prob, s.pixel, m.pos, m.nrm, build_index=False)
+    cs, cm = orc.centroids()
+    T = synth.make_candidates(synth.centred_gt(s.T_gt, cs.astype(np.float64), cm.astype(np.float64)), k, seed=synth.SEED_CAND)
+    assert np.abs(orc.lcp_batch(T, nthreads=4) - got).max() <= 1e-5
+
+
+@pytest.mark.gpu
 def test_stocs_single_instance_mode_on_packed_dove(tmp_path):
     """edge map present -> the driver takes the sample_instance_base path (stocs_match_one_object.cpp:90)."""
     from model_matching_amd import cloudio
