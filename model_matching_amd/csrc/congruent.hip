@@ -1333,7 +1333,7 @@ static int count_pass(stocs_ctx* c, CongruentState* S, const PlanDev& plan, bool
     int rc;
     if ((rc = d_pk_raw.alloc(totP0)) || (rc = d_pv_raw.alloc(totP0)) || (rc = d_qk_raw.alloc(totQ0)) || (rc = d_qv_raw.alloc(totQ0))) return rc;
     S->d_jobs.p = plan.jobs;
-    if (S->deferred && !S->reduce) { const int rd = S->deferred(); S->deferred = nullptr; if (rd) return rd; }   // (no survivors pass to hide it behind)
+    if (S->deferred && !S->reduce) { const int rd = S->deferred(); S->deferred = nullptr; if (rd) return rd; c->timing[0].lap("host: cone records of the bases (no survivors pass to hide them behind)"); }
     const Segment* d_psegs = plan.psegs;
     const Segment* d_qsegs = plan.qsegs;
     S->d_qoff.p = plan.q_off;
@@ -1836,6 +1836,7 @@ int stocs_internal_find_congruent(stocs_ctx* c, int64_t* total_quads, size_t max
         std::vector<Segment> psegs, qsegs;
         std::vector<std::pair<uint32_t, uint32_t> > pr, qr;
         std::vector<int> keys8((size_t)nB * 8);
+        uint32_t* p_off = (uint32_t*)(h + o_poff);   // P's per-base offsets: the segments of P's sort in the unreduced form (the reduced form rewrites them)
         for (int b = 0; b < nB; ++b) {   // the keys first, touching the bucket table ahead of the planning loop
             const BaseRec& B = c->bases[b];
             int* K1 = &keys8[(size_t)b * 8];
@@ -1860,11 +1861,11 @@ int stocs_internal_find_congruent(stocs_ctx* c, int64_t* total_quads, size_t max
             for (size_t r = 0; r < pr.size(); ++r) { Segment sg = {pr[r].first, pr[r].second - pr[r].first, d, (uint32_t)b}; psegs.push_back(sg); d += sg.len; }
             d = (uint32_t)totQ;
             for (size_t r = 0; r < qr.size(); ++r) { Segment sg = {qr[r].first, qr[r].second - qr[r].first, d, (uint32_t)b}; qsegs.push_back(sg); d += sg.len; }
-            q_off[b] = (uint32_t)totQ;
+            p_off[b] = (uint32_t)totP; q_off[b] = (uint32_t)totQ;
             totP += np; totQ += nq;
             if (totP >= 0xFFFF0000ull || totQ >= 0xFFFF0000ull) { if (too_big) { *too_big = 1; return STOCS_OK; } set_error("pair lists exceed 2^32 entries"); return STOCS_ERR_CAPACITY; }
         }
-        q_off[nB] = (uint32_t)totQ;
+        p_off[nB] = (uint32_t)totP; q_off[nB] = (uint32_t)totQ;
         if (psegs.size() > nb * 128 || qsegs.size() > nb * 128) { set_error("internal: more than 128 ranges per lookup"); return STOCS_ERR_STATE; }
         memcpy(h + o_jobs, jobs.data(), sizeof(BaseJob) * nb);
         memcpy(h + o_pseg, psegs.data(), sizeof(Segment) * psegs.size());
@@ -1873,6 +1874,7 @@ int stocs_internal_find_congruent(stocs_ctx* c, int64_t* total_quads, size_t max
         STOCS_HIP_CHECK(hipMemcpyAsync(dpl, h, up_bytes, hipMemcpyHostToDevice, c->stream));
         STOCS_HIP_CHECK(hipMemcpyAsync(dpl + o_pseg, h + o_pseg, sizeof(Segment) * psegs.size(), hipMemcpyHostToDevice, c->stream));
         STOCS_HIP_CHECK(hipMemcpyAsync(dpl + o_qseg, h + o_qseg, sizeof(Segment) * qsegs.size(), hipMemcpyHostToDevice, c->stream));
+        STOCS_HIP_CHECK(hipMemcpyAsync(dpl + o_poff, h + o_poff, 4 * (nb + 1), hipMemcpyHostToDevice, c->stream));
         STOCS_HIP_CHECK(hipMemcpyAsync(dpl + o_qoff, h + o_qoff, 4 * (nb + 1), hipMemcpyHostToDevice, c->stream));
         plan.n_pseg = (int)psegs.size(); plan.n_qseg = (int)qsegs.size();
         c->timing[0].lap("plan on the host + upload");
@@ -1901,7 +1903,7 @@ int stocs_internal_find_congruent(stocs_ctx* c, int64_t* total_quads, size_t max
         if (rc0) return rc0;
         if (over) { if (too_big) *too_big = 1; return STOCS_OK; }   // the caller splits its base set
     }
-    c->timing[0].lap("arena reserve");
+    c->timing[0].lap(!use_table ? "arena reserve (no run table, 64-bit keys)" : (wide ? "arena reserve (64-bit keys)" : "arena reserve"));   // (names the form)
     S->nB = nB; S->totP = (uint32_t)totP; S->totQ = (uint32_t)totQ; S->nepsilon = nepsilon;
     S->half_inv_neps = (float)(0.5 / (double)nepsilon);
     S->NC = NC; S->use_table = use_table; S->wide = wide; S->reduce = reduce;

@@ -427,7 +427,8 @@ def test_two_stream_sections_pass_the_happens_before_audit(setup, monkeypatch):
     n0 = est.find_congruent_all(); c0 = est.make_transforms(40, 9)
     monkeypatch.setenv("STOCS_DEBUG_STREAMS", "1")
     for extra in ({}, {"STOCS_CONGRUENT_EXACT_SIZES": "1"}, {"STOCS_CONGRUENT_KEEP_ALL": "1"}, {"STOCS_CONGRUENT_CAPACITY": "0.05"},
-                  {"STOCS_CONGRUENT_TWO_STREAMS": "1"}, {"STOCS_CONGRUENT_TWO_STREAMS": "1", "STOCS_CONGRUENT_CAPACITY": "0.05"}):
+                  {"STOCS_CONGRUENT_TWO_STREAMS": "1"}, {"STOCS_CONGRUENT_TWO_STREAMS": "1", "STOCS_CONGRUENT_CAPACITY": "0.05"},
+                  {"STOCS_CONGRUENT_HOST_PLAN": "1", "STOCS_CONGRUENT_KEEP_ALL": "1"}):
         for k, v in extra.items():
             monkeypatch.setenv(k, v)
         assert est.find_congruent_all() == n0 and est.make_transforms(40, 9) == c0, extra
