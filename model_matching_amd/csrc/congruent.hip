@@ -9,9 +9,9 @@
 // The reference builds, per base, a pointer grid (egSize^3 position cells, each a lazily allocated
 // array of 343 std::vectors) over the "intersection" points of the P pairs and queries it once per
 // Q pair along a sampled cone of directions.  Here all bases are processed together:
-//   1. host: the two PPF keys of the base, the source buckets of each lookup (CSR ranges of the index, in ascending
-//      index position), the cone sample table (<= 56 unit vectors from libm's acosf/atanf/sinf/cosf -- per-base
-//      scalars, exactly the reference's values);
+//   1. plan_*_kernel: the two PPF keys of the base, the source buckets of each lookup (CSR ranges of the index, in
+//      ascending index position); host: the cone sample table (<= 56 unit vectors from libm's acosf/atanf/sinf/cosf --
+//      per-base scalars, exactly the reference's values);
 //   2. gather_key_kernel: the P and Q pair lists of all bases straight out of the device index, each entry with its
 //      32-bit key (base, position cell of its intersection point);
 //   3. ONE stable rocPRIM radix sort per list replaces the pointer grid: the Q entries by (base, position cell) in three
@@ -140,7 +140,6 @@ __device__ __forceinline__ void block_scan_1024(uint32_t* __restrict__ a, uint32
 // stocs.cpp:788), the segment arrays the gather walks, the list offsets patched into the base jobs, the totals for the host.
 // Four in-place scans over arrays of nB + 1 words in device memory (any number of bases: a trial batch brings thousands), then
 // everything else in parallel over the bases.
-#define PLAN_MAX_BASES (1 << 20)
 __global__ __launch_bounds__(1024) void plan_offsets_kernel(int nB, const uint2* __restrict__ ranges, const uint32_t* __restrict__ n_ranges, const uint32_t* __restrict__ totals,
                                                             BaseJob* __restrict__ jobs, Segment* __restrict__ psegs, Segment* __restrict__ qsegs,
                                                             uint32_t* __restrict__ p_off, uint32_t* __restrict__ q_off, uint32_t* __restrict__ sp_off, uint32_t* __restrict__ sq_off,
@@ -1302,12 +1301,200 @@ struct PlanDev {
     int n_pseg, n_qseg;
 };
 
+// The planning buffer of a call with nB bases: jobs | base ids | error words | ranges | range counts | totals | P segments | Q segments |
+// p_off | q_off | segment offsets | result.  A lookup is at most 128 ranges, so every region has a bound that depends on nB alone.  The
+// host stages the upload (jobs | base ids | error words, at the same offsets) in its pinned block, and the deferred cone records behind it.
+struct PlanLayout {
+    size_t jobs, bids, err, rng, nr, tot, pseg, qseg, poff, qoff, spo, sqo, out, bytes;   // device
+    size_t up, cone, stage;                                                                // pinned staging
+    explicit PlanLayout(int nB) {
+        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+        const size_t nb = (size_t)nB;
+        jobs = 0; bids = jobs + al(sizeof(BaseJob) * nb); err = bids + al(16 * nb); rng = err + 256; nr = rng + al(2 * nb * 128 * 8);
+        tot = nr + al(2 * nb * 4); pseg = tot + al(2 * nb * 4); qseg = pseg + al(nb * 128 * sizeof(Segment));
+        poff = qseg + al(nb * 128 * sizeof(Segment)); qoff = poff + al((nb + 1) * 4); spo = qoff + al((nb + 2) * 4); sqo = spo + al((nb + 1) * 4);
+        out = sqo + al((nb + 1) * 4); bytes = out + 256;
+        up = err + 256; cone = up; stage = cone + al(sizeof(float4) * nb);
+    }
+};
+
+// the layout kernel of the plan: list offsets into the base jobs, segment offsets, totals (launched again by the capacity redo)
+static void launch_plan_offsets(hipStream_t st, int nB, char* dpl, const PlanLayout& L, const PlanDev& plan) {
+    hipLaunchKernelGGL(plan_offsets_kernel, dim3(1), dim3(1024), 0, st, nB, (const uint2*)(dpl + L.rng), (const uint32_t*)(dpl + L.nr), (const uint32_t*)(dpl + L.tot),
+                       plan.jobs, plan.psegs, plan.qsegs, plan.p_off, plan.q_off, (uint32_t*)(dpl + L.spo), (uint32_t*)(dpl + L.sqo), (PlanOut*)(dpl + L.out), plan.err);
+}
+
+// The per-call switches of this file (tests and A/B), read once at the top of each call: together with the sizes they decide the form
+// the call takes.  (STOCS_SORT and STOCS_GATHER_WGS are read once per process: cong_sort_own, gather_max_wgs.)
+struct CongruentSwitches {
+    int min_id_bits = 0;                        // STOCS_CONGRUENT_ID_BITS: keeps the wide-id form of the quad keys testable on small models
+    int force_streams = 0;                      // 2: STOCS_CONGRUENT_TWO_STREAMS, 1: STOCS_CONGRUENT_ONE_STREAM
+    double capacity = 1.6, slack = 1048576.0;   // STOCS_CONGRUENT_CAPACITY: the factor, without slack (below 1 it forces the redo with exact sizes)
+    bool wide_keys, keep_all, exact_sizes, distance_gate, no_lds_bits, p_fullsort;   // STOCS_CONGRUENT_<NAME>
+    bool debug_streams, debug_timing;           // STOCS_DEBUG_STREAMS (the stream audit), STOCS_DEBUG_TIMING (synchronised steps on stderr)
+    static CongruentSwitches read() {
+        auto on = [](const char* name) { return getenv(name) != NULL; };
+        CongruentSwitches w;
+        if (const char* e = getenv("STOCS_CONGRUENT_ID_BITS")) w.min_id_bits = std::min(16, atoi(e));
+        w.force_streams = on("STOCS_CONGRUENT_TWO_STREAMS") ? 2 : (on("STOCS_CONGRUENT_ONE_STREAM") ? 1 : 0);
+        if (const char* e = getenv("STOCS_CONGRUENT_CAPACITY")) { w.capacity = atof(e); w.slack = 1.0; }
+        w.wide_keys = on("STOCS_CONGRUENT_WIDE_KEYS"); w.keep_all = on("STOCS_CONGRUENT_KEEP_ALL"); w.exact_sizes = on("STOCS_CONGRUENT_EXACT_SIZES");
+        w.distance_gate = on("STOCS_CONGRUENT_DISTANCE_GATE"); w.no_lds_bits = on("STOCS_CONGRUENT_NO_LDS_BITS"); w.p_fullsort = on("STOCS_CONGRUENT_P_FULLSORT");
+        w.debug_streams = on("STOCS_DEBUG_STREAMS"); w.debug_timing = on("STOCS_DEBUG_TIMING");
+        return w;
+    }
+};
+
+// the pair lists of one count pass as gathered and, when they are reduced, their survivors (one buffer for both lists in the one-stream form)
+template <class KeyT>
+struct PassLists { DevBuf<KeyT> pk_raw, qk_raw, pk_c, qk_c; DevBuf<uint32_t> pv_raw, qv_raw, pv_c, qv_c, comb_off; };
+
+// The reduced form's first stage: gather -> occupancy -> survivor counts -> tile scan -> compaction of both lists, and the read-back of
+// the survivors' offsets and totals (S->totP, S->totQ, S->h_qoff).  S->no_quads when no cell is shared; *outgrown when the plan turned
+// out larger than the capacities (d_po != NULL): the streams are idle then.
+template <class KeyT>
+static int reduce_lists(stocs_ctx* c, CongruentState* S, const PlanDev& plan, PassLists<KeyT>& L, hipStream_t sq, bool one_stream, uint32_t lds_words, bool dbg,
+                        const PlanOut* d_po, const PlanOut* po_pin, bool* outgrown) {
+    const int nB = S->nB;
+    const size_t totP0 = S->totP, totQ0 = S->totQ;
+    hipStream_t st = c->stream;
+    const int s0 = 0, s1 = sq != st ? 1 : 0;
+    const bool dev_clock = c->device_clock != 0;
+    const long long cell_limit = S->use_table ? S->NC : ((long long)1 << 31);
+    const PpfIndex& ix = c->index;
+    StreamAudit& AU = c->audit;
+    int rc;
+    // one zeroed block: occupancy of P | occupancy of Q | P tile counts (+ total) | Q tile counts (+ total)
+    const size_t W = (size_t)((((unsigned long long)nB << S->cell_bits) + 31) >> 5) + 1;   // words of one occupancy table: one bit per (base, cell) value
+    const uint32_t ntp = (uint32_t)((totP0 + SURV_TILE - 1) / SURV_TILE), ntq = (uint32_t)((totQ0 + SURV_TILE - 1) / SURV_TILE);
+    const size_t o_tp = 2 * W, o_tq = o_tp + ntp + 1, n_words = o_tq + ntq + 1;
+    DevBuf<uint32_t> d_surv;
+    if ((rc = d_surv.alloc(n_words))) return rc;
+    DevBuf<unsigned long long> d_bits_p, d_bits_q;   // one bit per gathered entry: survives (written by the count pass, read by the compaction)
+    if ((rc = d_bits_p.alloc((size_t)std::max(ntp, 1u) * (SURV_TILE / 64))) || (rc = d_bits_q.alloc((size_t)std::max(ntq, 1u) * (SURV_TILE / 64)))) return rc;
+    uint32_t* occ_p = d_surv.p;
+    uint32_t* occ_q = d_surv.p + W;
+    hipLaunchKernelGGL(zero_u32_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, st, d_surv.p, n_words, (uint32_t*)NULL);
+    const uint32_t* tiles_p = d_surv.p + o_tp; const uint32_t* tiles_q = d_surv.p + o_tq;
+    AU.use(s0, occ_p, true, "occupancy of P", "zero fill"); AU.use(s0, occ_q, true, "occupancy of Q", "zero fill");
+    AU.use(s0, tiles_p, true, "tile counts of P", "zero fill"); AU.use(s0, tiles_q, true, "tile counts of Q", "zero fill");
+    AU.use(s0, plan.jobs, true, "base jobs", "plan kernels"); AU.use(s0, plan.psegs, true, "P segments", "plan kernels"); AU.use(s0, plan.qsegs, true, "Q segments", "plan kernels");
+    AU.use(s0, plan.q_off, true, "Q offsets per base", "plan kernels");
+    if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[6], st));
+    if (sq != st) {
+        STOCS_HIP_CHECK(hipEventRecord(c->ev_fork, st));          // the plan upload and the zero fill are on st
+        STOCS_HIP_CHECK(hipStreamWaitEvent(sq, c->ev_fork, 0));
+        AU.record(c->ev_fork, s0); AU.wait(s1, c->ev_fork);
+    }
+    if (one_stream) {
+        const GatherSide<KeyT> gp = {plan.psegs, plan.n_pseg, (uint32_t)totP0, L.pk_raw.p, L.pv_raw.p, occ_p}, gq = {plan.qsegs, plan.n_qseg, (uint32_t)totQ0, L.qk_raw.p, L.qv_raw.p, occ_q};
+        hipLaunchKernelGGL(gather_key_dual_kernel<KeyT>, dim3(std::max(gather_grid(totP0), gather_grid(totQ0)), 2), dim3(256), lds_words * 4, st, ix.d_pairs, gp, gq,
+                           (const BaseJob*)S->d_jobs.p, (const float4*)c->d_munit, S->cell_bits, cell_limit, d_po, lds_words, (uint32_t)nB);
+    } else
+    hipLaunchKernelGGL(gather_key_kernel<KeyT>, dim3(gather_grid(totQ0)), dim3(256), lds_words * 4, sq, ix.d_pairs, plan.qsegs, plan.n_qseg, (uint32_t)totQ0,
+                       S->d_jobs.p, c->d_munit, 1, S->cell_bits, cell_limit, L.qk_raw.p, L.qv_raw.p, occ_q, d_po, lds_words, (uint32_t)nB);
+    AU.use(s1, plan.qsegs, false, "Q segments", "gather Q"); AU.use(s1, plan.jobs, false, "base jobs", "gather Q");
+    AU.use(s1, L.qk_raw.p, true, "gathered Q keys", "gather Q"); AU.use(s1, L.qv_raw.p, true, "gathered Q pairs", "gather Q"); AU.use(s1, occ_q, true, "occupancy of Q", "gather Q");
+    if (sq != st || dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[8], sq));             // Q's cells are marked
+    AU.record(c->ev_t[8], s1);
+    if (!one_stream)
+    hipLaunchKernelGGL(gather_key_kernel<KeyT>, dim3(gather_grid(totP0)), dim3(256), lds_words * 4, st, ix.d_pairs, plan.psegs, plan.n_pseg, (uint32_t)totP0,
+                       S->d_jobs.p, c->d_munit, 0, S->cell_bits, cell_limit, L.pk_raw.p, L.pv_raw.p, occ_p, d_po, lds_words, (uint32_t)nB);
+    AU.use(s0, plan.psegs, false, "P segments", "gather P"); AU.use(s0, plan.jobs, false, "base jobs", "gather P");
+    AU.use(s0, L.pk_raw.p, true, "gathered P keys", "gather P"); AU.use(s0, L.pv_raw.p, true, "gathered P pairs", "gather P"); AU.use(s0, occ_p, true, "occupancy of P", "gather P");
+    if (sq != st || dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[9], st));             // P's cells are marked
+    AU.record(c->ev_t[9], s0);
+    if (sq != st) { STOCS_HIP_CHECK(hipStreamWaitEvent(sq, c->ev_t[9], 0)); STOCS_HIP_CHECK(hipStreamWaitEvent(st, c->ev_t[8], 0)); AU.wait(s1, c->ev_t[9]); AU.wait(s0, c->ev_t[8]); }
+    // (one stream: the compacted lists are ONE buffer, allocated here so that the launch below can name it)
+    if (one_stream) { if ((rc = L.pk_c.alloc(totP0 + totQ0)) || (rc = L.pv_c.alloc(totP0 + totQ0)) || (rc = L.comb_off.alloc(2 * (size_t)nB + 1))) return rc; }
+    const SurvSide<KeyT> sp = {(const KeyT*)L.pk_raw.p, (const uint32_t*)L.pv_raw.p, (uint32_t)totP0, (const uint32_t*)occ_q, d_surv.p + o_tp, d_bits_p.p, L.pk_c.p, L.pv_c.p},
+                         sqd = {(const KeyT*)L.qk_raw.p, (const uint32_t*)L.qv_raw.p, (uint32_t)totQ0, (const uint32_t*)occ_p, d_surv.p + o_tq, d_bits_q.p, L.pk_c.p, L.pv_c.p};
+    if (one_stream)
+        hipLaunchKernelGGL(survivors_count_dual_kernel<KeyT>, dim3(std::max(1u, std::min((std::max(ntp, ntq) + 3u) / 4u, GATHER_MAX_WGS)), 2), dim3(256), lds_words * 4, st, sp, sqd, d_po,
+                           lds_words, S->cell_bits);
+    else
+    hipLaunchKernelGGL(survivors_count_kernel<KeyT>, dim3(std::max(1u, std::min((ntq + 3u) / 4u, GATHER_MAX_WGS))), dim3(256), lds_words * 4, sq, (const KeyT*)L.qk_raw.p, (uint32_t)totQ0, (const uint32_t*)occ_p, d_surv.p + o_tq, d_po, 1, d_bits_q.p, lds_words, S->cell_bits);
+    AU.use(s1, L.qk_raw.p, false, "gathered Q keys", "survivors count Q"); AU.use(s1, occ_p, false, "occupancy of P", "survivors count Q"); AU.use(s1, tiles_q, true, "tile counts of Q", "survivors count Q"); AU.use(s1, d_bits_q.p, true, "alive bits of Q", "survivors count Q");
+    if (sq != st) { STOCS_HIP_CHECK(hipEventRecord(c->ev_join, sq)); AU.record(c->ev_join, s1); }
+    if (!one_stream)
+    hipLaunchKernelGGL(survivors_count_kernel<KeyT>, dim3(std::max(1u, std::min((ntp + 3u) / 4u, GATHER_MAX_WGS))), dim3(256), lds_words * 4, st, (const KeyT*)L.pk_raw.p, (uint32_t)totP0, (const uint32_t*)occ_q, d_surv.p + o_tp, d_po, 0, d_bits_p.p, lds_words, S->cell_bits);
+    AU.use(s0, L.pk_raw.p, false, "gathered P keys", "survivors count P"); AU.use(s0, occ_q, false, "occupancy of Q", "survivors count P"); AU.use(s0, tiles_p, true, "tile counts of P", "survivors count P"); AU.use(s0, d_bits_p.p, true, "alive bits of P", "survivors count P");
+    if (sq != st) { STOCS_HIP_CHECK(hipStreamWaitEvent(st, c->ev_join, 0)); AU.wait(s0, c->ev_join); }
+    AU.use(s0, tiles_p, true, "tile counts of P", "tile scan"); AU.use(s0, tiles_q, true, "tile counts of Q", "tile scan");
+    AU.use(s0, L.qk_raw.p, false, "gathered Q keys", "base offsets"); AU.use(s0, occ_p, false, "occupancy of P", "base offsets"); AU.use(s0, plan.jobs, true, "base jobs", "base offsets");
+    AU.use(s0, plan.q_off, true, "Q offsets per base", "base offsets");
+    if (std::max(ntp, ntq) + 1u <= 2u * TSCAN) {
+        hipLaunchKernelGGL(survivors_scan_kernel, dim3(2), dim3(1024), 0, st, d_surv.p + o_tp, ntp, d_surv.p + o_tq, ntq);
+    } else {      // long lists (trial batches): the scan on many workgroups
+        const uint32_t pp = (ntp + 1u + TSCAN - 1u) / TSCAN, pq = (ntq + 1u + TSCAN - 1u) / TSCAN;
+        DevBuf<uint32_t> d_part;
+        if ((rc = d_part.alloc((size_t)pp + pq))) return rc;
+        hipLaunchKernelGGL(tile_scan_local_kernel, dim3(std::max(pp, pq), 2), dim3(256), 0, st, d_surv.p + o_tp, ntp + 1u, d_surv.p + o_tq, ntq + 1u, d_part.p, pp);
+        hipLaunchKernelGGL(tile_scan_add_kernel, dim3(std::max(pp, pq), 2), dim3(256), 0, st, d_surv.p + o_tp, ntp + 1u, d_surv.p + o_tq, ntq + 1u, (const uint32_t*)d_part.p, pp);
+    }
+    hipLaunchKernelGGL(survivors_base_offsets_kernel<KeyT>, dim3((unsigned)nB, 2), dim3(256), 0, st, (const KeyT*)L.pk_raw.p, (uint32_t)totP0, (const uint32_t*)occ_q,
+                       (const uint32_t*)(d_surv.p + o_tp), (const KeyT*)L.qk_raw.p, (uint32_t)totQ0, (const uint32_t*)occ_p, (const uint32_t*)(d_surv.p + o_tq), nB,
+                       S->d_jobs.p, plan.p_off, plan.q_off, d_po);
+    STOCS_HIP_CHECK(hipGetLastError());
+    // the host sizes the sorts and the join with the survivors' totals and lays the materialise blocks out with their Q offsets
+    uint32_t* qoff_pin = (uint32_t*)((char*)c->h_pin + PIN_VAR + 8 * ((size_t)nB + 1));
+    STOCS_HIP_CHECK(hipMemcpyAsync(qoff_pin, plan.q_off, 4 * ((size_t)nB + 2), hipMemcpyDeviceToHost, st));   // Q offsets, Q total, P total
+    STOCS_HIP_CHECK(hipEventRecord(c->ev_t[7], st));
+    AU.record(c->ev_t[7], s0);
+    // the survivors move behind their tiles' offsets while the host waits for the totals: the compacted lists are sized by
+    // the gathered ones here (the totals are what the wait is for)
+    if (!one_stream) { if ((rc = L.pk_c.alloc(totP0)) || (rc = L.pv_c.alloc(totP0)) || (rc = L.qk_c.alloc(totQ0)) || (rc = L.qv_c.alloc(totQ0))) return rc; }
+    if (sq != st) {
+        STOCS_HIP_CHECK(hipEventRecord(c->ev_fork, st));          // tile offsets are scanned on st
+        STOCS_HIP_CHECK(hipStreamWaitEvent(sq, c->ev_fork, 0));
+        AU.record(c->ev_fork, s0); AU.wait(s1, c->ev_fork);
+    }
+    AU.use(s1, L.qk_raw.p, false, "gathered Q keys", "compact Q"); AU.use(s1, L.qv_raw.p, false, "gathered Q pairs", "compact Q"); AU.use(s1, d_bits_q.p, false, "alive bits of Q", "compact Q");
+    AU.use(s1, tiles_q, false, "tile counts of Q", "compact Q"); AU.use(s1, L.qk_c.p, true, "surviving Q keys", "compact Q"); AU.use(s1, L.qv_c.p, true, "surviving Q pairs", "compact Q");
+    AU.use(s0, L.pk_raw.p, false, "gathered P keys", "compact P"); AU.use(s0, L.pv_raw.p, false, "gathered P pairs", "compact P"); AU.use(s0, d_bits_p.p, false, "alive bits of P", "compact P");
+    AU.use(s0, tiles_p, false, "tile counts of P", "compact P"); AU.use(s0, L.pk_c.p, true, "surviving P keys", "compact P"); AU.use(s0, L.pv_c.p, true, "surviving P pairs", "compact P");
+    if (one_stream)
+        hipLaunchKernelGGL(survivors_compact_dual_kernel<KeyT>, dim3(std::max(1u, (std::max(ntp, ntq) + 3u) / 4u), 3), dim3(256), 0, st, sp, sqd, d_po, (const uint32_t*)plan.p_off,
+                           (const uint32_t*)plan.q_off, nB, L.comb_off.p);
+    else {
+    hipLaunchKernelGGL(survivors_compact_kernel<KeyT>, dim3((ntq + 3u) / 4u), dim3(256), 0, sq, (const KeyT*)L.qk_raw.p, (const uint32_t*)L.qv_raw.p, (uint32_t)totQ0,
+                       (const unsigned long long*)d_bits_q.p, (const uint32_t*)(d_surv.p + o_tq), L.qk_c.p, L.qv_c.p, d_po, 1);
+    hipLaunchKernelGGL(survivors_compact_kernel<KeyT>, dim3((ntp + 3u) / 4u), dim3(256), 0, st, (const KeyT*)L.pk_raw.p, (const uint32_t*)L.pv_raw.p, (uint32_t)totP0,
+                       (const unsigned long long*)d_bits_p.p, (const uint32_t*)(d_surv.p + o_tp), L.pk_c.p, L.pv_c.p, d_po, 0);
+    }
+    STOCS_HIP_CHECK(hipGetLastError());
+    c->timing[0].lap("enqueue gather + occupancy + survivor counts");
+    if (S->deferred) { const int rd = S->deferred(); S->deferred = nullptr; if (rd) return rd; c->timing[0].lap("host: cone records of the bases (while the device gathers)"); }
+    STOCS_HIP_CHECK(hipEventSynchronize(c->ev_t[7]));   // the read-back, not the compaction behind it
+    AU.host_sync_event(c->ev_t[7]);
+    c->timing[0].lap("wait for the device (survivors)");
+    if (po_pin) {   // the plan's own totals came with this read-back: were the capacities enough?
+        if (po_pin->overflow || po_pin->totP > (unsigned long long)totP0 || po_pin->totQ > (unsigned long long)totQ0) {
+            STOCS_HIP_CHECK(hipStreamSynchronize(st));            // the compaction behind the read-back: nothing may still touch the arena
+            if (sq != st) STOCS_HIP_CHECK(hipStreamSynchronize(sq));
+            AU.host_sync(s0); AU.host_sync(s1);
+            *outgrown = true;
+            return STOCS_OK;
+        }
+    }
+    const size_t totP = qoff_pin[nB + 1], totQ = qoff_pin[nB];
+    memcpy(S->h_qoff.data(), qoff_pin, 4 * ((size_t)nB + 1));
+    if (dbg) fprintf(stderr, "[stocs congruent] survivors: P %zu of %zu, Q %zu of %zu\n", totP, totP0, totQ, totQ0);
+    S->totP = (uint32_t)totP; S->totQ = (uint32_t)totQ;
+    if (totP == 0 || totQ == 0) S->no_quads = true;   // no cell is shared: no quads (quad_off is all zero already)
+    return STOCS_OK;
+}
+
+// The count pass over the planned lists: (reduce_lists,) sorts, P records and run table, join count, scan, per-base quad offsets.
 // d_po != NULL ("optimistic"): the host has NOT read the plan -- S->totP / S->totQ are capacities the buffers and launches are
 // sized by, the kernels read the planned totals from *d_po, and the plan's totals arrive with the survivors' in ONE read-back
-// (po_pin).  Returns 1 (not an error) when the plan turned out larger than the capacities: the caller redoes the pass with the
+// (po_pin).  *outgrown (not an error) when the plan turned out larger than the capacities: the caller redoes the pass with the
 // exact sizes it now knows.
 template <class KeyT>
-static int count_pass(stocs_ctx* c, CongruentState* S, const PlanDev& plan, bool dbg, double& tprev, const PlanOut* d_po = NULL, const PlanOut* po_pin = NULL) {
+static int count_pass(stocs_ctx* c, CongruentState* S, const PlanDev& plan, const CongruentSwitches& sw, double& tprev, const PlanOut* d_po, const PlanOut* po_pin,
+                      bool* outgrown) {
+    *outgrown = false;
+    const bool dbg = sw.debug_timing;
     const int nB = S->nB;
     const size_t totP0 = S->totP, totQ0 = S->totQ;   // the gathered lists as planned (d_po: their capacities)
     size_t totP = totP0, totQ = totQ0;               // the lists that are sorted and joined (the survivors, when the lists are reduced)
@@ -1323,157 +1510,33 @@ static int count_pass(stocs_ctx* c, CongruentState* S, const PlanDev& plan, bool
     // it stays for 64-bit keys, unreduced lists and rocPRIM's sort, and under STOCS_CONGRUENT_TWO_STREAMS for A/B.
     // Lists beyond 10^8 entries -- the pieces of a trial batch at the metric size -- keep the two streams: there the edges are nothing and the
     // overlap of unlike kernels (P's records next to Q's sort) is worth 2 % (64 Cm trials: 2 040 against 1 985 trials/s).
-    const int force_streams = getenv("STOCS_CONGRUENT_TWO_STREAMS") ? 2 : (getenv("STOCS_CONGRUENT_ONE_STREAM") ? 1 : 0);
-    const bool one_stream = S->reduce && sizeof(KeyT) == 4 && cong_sort_own() && (totP0 + totQ0) < ((size_t)1 << 30) && nB < (1 << 22) && force_streams != 2 &&
-                            (force_streams == 1 || totP0 + totQ0 < (size_t)100000000);
+    const bool one_stream = S->reduce && sizeof(KeyT) == 4 && cong_sort_own() && (totP0 + totQ0) < ((size_t)1 << 30) && nB < (1 << 22) && sw.force_streams != 2 &&
+                            (sw.force_streams == 1 || totP0 + totQ0 < (size_t)100000000);
     hipStream_t sq = (c->aux_stream && !one_stream) ? c->aux_stream : st;
-    DevBuf<KeyT> d_pk_raw, d_qk_raw;
-    DevBuf<uint32_t> d_pv_raw, d_qv_raw;
+    PassLists<KeyT> L;
     DevBuf<char> d_tmp;
     int rc;
-    if ((rc = d_pk_raw.alloc(totP0)) || (rc = d_pv_raw.alloc(totP0)) || (rc = d_qk_raw.alloc(totQ0)) || (rc = d_qv_raw.alloc(totQ0))) return rc;
+    if ((rc = L.pk_raw.alloc(totP0)) || (rc = L.pv_raw.alloc(totP0)) || (rc = L.qk_raw.alloc(totQ0)) || (rc = L.qv_raw.alloc(totQ0))) return rc;
     S->d_jobs.p = plan.jobs;
     if (S->deferred && !S->reduce) { const int rd = S->deferred(); S->deferred = nullptr; if (rd) return rd; c->timing[0].lap("host: cone records of the bases (no survivors pass to hide them behind)"); }
-    const Segment* d_psegs = plan.psegs;
-    const Segment* d_qsegs = plan.qsegs;
     S->d_qoff.p = plan.q_off;
     S->d_bids.p = plan.bids;
     S->d_err.p = plan.err;
-    const int n_pseg = plan.n_pseg, n_qseg = plan.n_qseg;
     const PpfIndex& ix = c->index;
     StreamAudit& AU = c->audit;                       // STOCS_DEBUG_STREAMS: every two-stream step below says what it reads and writes
     const int s0 = 0, s1 = sq != st ? 1 : 0;
     const long long cell_limit = S->use_table ? S->NC : ((long long)1 << 31);
     const unsigned end_bit = (unsigned)(S->cell_bits + S->base_bits);
-    const unsigned long long occ_bits = (unsigned long long)nB << S->cell_bits;   // (base, cell) values = BITS of an occupancy table
     // one base's bits in LDS (gather: collected there; count: the other list's, tested there) while they fit 32 KB
-    const uint32_t lds_words = (S->cell_bits >= 5 && S->cell_bits <= 18 && !getenv("STOCS_CONGRUENT_NO_LDS_BITS")) ? (1u << (S->cell_bits - 5)) : 0u;
+    const uint32_t lds_words = (S->cell_bits >= 5 && S->cell_bits <= 18 && !sw.no_lds_bits) ? (1u << (S->cell_bits - 5)) : 0u;
     const bool reduce = S->reduce;
-    const KeyT* pk_in = d_pk_raw.p; const uint32_t* pv_in = d_pv_raw.p;   // what the sorts read
-    const KeyT* qk_in = d_qk_raw.p; const uint32_t* qv_in = d_qv_raw.p;
-    DevBuf<KeyT> d_pk_c, d_qk_c;
-    DevBuf<uint32_t> d_pv_c, d_qv_c, d_surv, d_comb_off;
-    bool have_surv_clock = false;
+    const KeyT* pk_in = L.pk_raw.p; const uint32_t* pv_in = L.pv_raw.p;   // what the sorts read
+    const KeyT* qk_in = L.qk_raw.p; const uint32_t* qv_in = L.qv_raw.p;
     if (reduce) {
-        // one zeroed block: occupancy of P | occupancy of Q | P tile counts (+ total) | Q tile counts (+ total)
-        const size_t W = (size_t)((occ_bits + 31) >> 5) + 1;   // words of one occupancy table
-        const uint32_t ntp = (uint32_t)((totP0 + SURV_TILE - 1) / SURV_TILE), ntq = (uint32_t)((totQ0 + SURV_TILE - 1) / SURV_TILE);
-        const size_t o_tp = 2 * W, o_tq = o_tp + ntp + 1, n_words = o_tq + ntq + 1;
-        if ((rc = d_surv.alloc(n_words))) return rc;
-        DevBuf<unsigned long long> d_bits_p, d_bits_q;   // one bit per gathered entry: survives (written by the count pass, read by the compaction)
-        if ((rc = d_bits_p.alloc((size_t)std::max(ntp, 1u) * (SURV_TILE / 64))) || (rc = d_bits_q.alloc((size_t)std::max(ntq, 1u) * (SURV_TILE / 64)))) return rc;
-        uint32_t* occ_p = d_surv.p;
-        uint32_t* occ_q = d_surv.p + W;
-        hipLaunchKernelGGL(zero_u32_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, st, d_surv.p, n_words, (uint32_t*)NULL);
-        const uint32_t* tiles_p = d_surv.p + o_tp; const uint32_t* tiles_q = d_surv.p + o_tq;
-        AU.use(s0, occ_p, true, "occupancy of P", "zero fill"); AU.use(s0, occ_q, true, "occupancy of Q", "zero fill");
-        AU.use(s0, tiles_p, true, "tile counts of P", "zero fill"); AU.use(s0, tiles_q, true, "tile counts of Q", "zero fill");
-        AU.use(s0, plan.jobs, true, "base jobs", "plan kernels"); AU.use(s0, plan.psegs, true, "P segments", "plan kernels"); AU.use(s0, plan.qsegs, true, "Q segments", "plan kernels");
-        AU.use(s0, plan.q_off, true, "Q offsets per base", "plan kernels");
-        if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[6], st));
-        if (sq != st) {
-            STOCS_HIP_CHECK(hipEventRecord(c->ev_fork, st));          // the plan upload and the zero fill are on st
-            STOCS_HIP_CHECK(hipStreamWaitEvent(sq, c->ev_fork, 0));
-            AU.record(c->ev_fork, s0); AU.wait(s1, c->ev_fork);
-        }
-        if (one_stream) {
-            const GatherSide<KeyT> gp = {d_psegs, n_pseg, (uint32_t)totP0, d_pk_raw.p, d_pv_raw.p, occ_p}, gq = {d_qsegs, n_qseg, (uint32_t)totQ0, d_qk_raw.p, d_qv_raw.p, occ_q};
-            hipLaunchKernelGGL(gather_key_dual_kernel<KeyT>, dim3(std::max(gather_grid(totP0), gather_grid(totQ0)), 2), dim3(256), lds_words * 4, st, ix.d_pairs, gp, gq,
-                               (const BaseJob*)S->d_jobs.p, (const float4*)c->d_munit, S->cell_bits, cell_limit, d_po, lds_words, (uint32_t)nB);
-        } else
-        hipLaunchKernelGGL(gather_key_kernel<KeyT>, dim3(gather_grid(totQ0)), dim3(256), lds_words * 4, sq, ix.d_pairs, d_qsegs, n_qseg, (uint32_t)totQ0,
-                           S->d_jobs.p, c->d_munit, 1, S->cell_bits, cell_limit, d_qk_raw.p, d_qv_raw.p, occ_q, d_po, lds_words, (uint32_t)nB);
-        AU.use(s1, plan.qsegs, false, "Q segments", "gather Q"); AU.use(s1, plan.jobs, false, "base jobs", "gather Q");
-        AU.use(s1, d_qk_raw.p, true, "gathered Q keys", "gather Q"); AU.use(s1, d_qv_raw.p, true, "gathered Q pairs", "gather Q"); AU.use(s1, occ_q, true, "occupancy of Q", "gather Q");
-        if (sq != st || dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[8], sq));             // Q's cells are marked
-        AU.record(c->ev_t[8], s1);
-        if (!one_stream)
-        hipLaunchKernelGGL(gather_key_kernel<KeyT>, dim3(gather_grid(totP0)), dim3(256), lds_words * 4, st, ix.d_pairs, d_psegs, n_pseg, (uint32_t)totP0,
-                           S->d_jobs.p, c->d_munit, 0, S->cell_bits, cell_limit, d_pk_raw.p, d_pv_raw.p, occ_p, d_po, lds_words, (uint32_t)nB);
-        AU.use(s0, plan.psegs, false, "P segments", "gather P"); AU.use(s0, plan.jobs, false, "base jobs", "gather P");
-        AU.use(s0, d_pk_raw.p, true, "gathered P keys", "gather P"); AU.use(s0, d_pv_raw.p, true, "gathered P pairs", "gather P"); AU.use(s0, occ_p, true, "occupancy of P", "gather P");
-        if (sq != st || dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[9], st));             // P's cells are marked
-        AU.record(c->ev_t[9], s0);
-        if (sq != st) { STOCS_HIP_CHECK(hipStreamWaitEvent(sq, c->ev_t[9], 0)); STOCS_HIP_CHECK(hipStreamWaitEvent(st, c->ev_t[8], 0)); AU.wait(s1, c->ev_t[9]); AU.wait(s0, c->ev_t[8]); }
-        // (one stream: the compacted lists are ONE buffer, allocated here so that the launch below can name it)
-        if (one_stream) { if ((rc = d_pk_c.alloc(totP0 + totQ0)) || (rc = d_pv_c.alloc(totP0 + totQ0)) || (rc = d_comb_off.alloc(2 * (size_t)nB + 1))) return rc; }
-        const SurvSide<KeyT> sp = {(const KeyT*)d_pk_raw.p, (const uint32_t*)d_pv_raw.p, (uint32_t)totP0, (const uint32_t*)occ_q, d_surv.p + o_tp, d_bits_p.p, d_pk_c.p, d_pv_c.p},
-                             sqd = {(const KeyT*)d_qk_raw.p, (const uint32_t*)d_qv_raw.p, (uint32_t)totQ0, (const uint32_t*)occ_p, d_surv.p + o_tq, d_bits_q.p, d_pk_c.p, d_pv_c.p};
-        if (one_stream)
-            hipLaunchKernelGGL(survivors_count_dual_kernel<KeyT>, dim3(std::max(1u, std::min((std::max(ntp, ntq) + 3u) / 4u, GATHER_MAX_WGS)), 2), dim3(256), lds_words * 4, st, sp, sqd, d_po,
-                               lds_words, S->cell_bits);
-        else
-        hipLaunchKernelGGL(survivors_count_kernel<KeyT>, dim3(std::max(1u, std::min((ntq + 3u) / 4u, GATHER_MAX_WGS))), dim3(256), lds_words * 4, sq, (const KeyT*)d_qk_raw.p, (uint32_t)totQ0, (const uint32_t*)occ_p, d_surv.p + o_tq, d_po, 1, d_bits_q.p, lds_words, S->cell_bits);
-        AU.use(s1, d_qk_raw.p, false, "gathered Q keys", "survivors count Q"); AU.use(s1, occ_p, false, "occupancy of P", "survivors count Q"); AU.use(s1, tiles_q, true, "tile counts of Q", "survivors count Q"); AU.use(s1, d_bits_q.p, true, "alive bits of Q", "survivors count Q");
-        if (sq != st) { STOCS_HIP_CHECK(hipEventRecord(c->ev_join, sq)); AU.record(c->ev_join, s1); }
-        if (!one_stream)
-        hipLaunchKernelGGL(survivors_count_kernel<KeyT>, dim3(std::max(1u, std::min((ntp + 3u) / 4u, GATHER_MAX_WGS))), dim3(256), lds_words * 4, st, (const KeyT*)d_pk_raw.p, (uint32_t)totP0, (const uint32_t*)occ_q, d_surv.p + o_tp, d_po, 0, d_bits_p.p, lds_words, S->cell_bits);
-        AU.use(s0, d_pk_raw.p, false, "gathered P keys", "survivors count P"); AU.use(s0, occ_q, false, "occupancy of Q", "survivors count P"); AU.use(s0, tiles_p, true, "tile counts of P", "survivors count P"); AU.use(s0, d_bits_p.p, true, "alive bits of P", "survivors count P");
-        if (sq != st) { STOCS_HIP_CHECK(hipStreamWaitEvent(st, c->ev_join, 0)); AU.wait(s0, c->ev_join); }
-        AU.use(s0, tiles_p, true, "tile counts of P", "tile scan"); AU.use(s0, tiles_q, true, "tile counts of Q", "tile scan");
-        AU.use(s0, d_qk_raw.p, false, "gathered Q keys", "base offsets"); AU.use(s0, occ_p, false, "occupancy of P", "base offsets"); AU.use(s0, plan.jobs, true, "base jobs", "base offsets");
-        AU.use(s0, plan.q_off, true, "Q offsets per base", "base offsets");
-        if (std::max(ntp, ntq) + 1u <= 2u * TSCAN) {
-            hipLaunchKernelGGL(survivors_scan_kernel, dim3(2), dim3(1024), 0, st, d_surv.p + o_tp, ntp, d_surv.p + o_tq, ntq);
-        } else {      // long lists (trial batches): the scan on many workgroups
-            const uint32_t pp = (ntp + 1u + TSCAN - 1u) / TSCAN, pq = (ntq + 1u + TSCAN - 1u) / TSCAN;
-            DevBuf<uint32_t> d_part;
-            if ((rc = d_part.alloc((size_t)pp + pq))) return rc;
-            hipLaunchKernelGGL(tile_scan_local_kernel, dim3(std::max(pp, pq), 2), dim3(256), 0, st, d_surv.p + o_tp, ntp + 1u, d_surv.p + o_tq, ntq + 1u, d_part.p, pp);
-            hipLaunchKernelGGL(tile_scan_add_kernel, dim3(std::max(pp, pq), 2), dim3(256), 0, st, d_surv.p + o_tp, ntp + 1u, d_surv.p + o_tq, ntq + 1u, (const uint32_t*)d_part.p, pp);
-        }
-        hipLaunchKernelGGL(survivors_base_offsets_kernel<KeyT>, dim3((unsigned)nB, 2), dim3(256), 0, st, (const KeyT*)d_pk_raw.p, (uint32_t)totP0, (const uint32_t*)occ_q,
-                           (const uint32_t*)(d_surv.p + o_tp), (const KeyT*)d_qk_raw.p, (uint32_t)totQ0, (const uint32_t*)occ_p, (const uint32_t*)(d_surv.p + o_tq), nB,
-                           S->d_jobs.p, plan.p_off, plan.q_off, d_po);
-        STOCS_HIP_CHECK(hipGetLastError());
-        // the host sizes the sorts and the join with the survivors' totals and lays the materialise blocks out with their Q offsets
-        uint32_t* qoff_pin = (uint32_t*)((char*)c->h_pin + PIN_VAR + 8 * ((size_t)nB + 1));
-        STOCS_HIP_CHECK(hipMemcpyAsync(qoff_pin, plan.q_off, 4 * ((size_t)nB + 2), hipMemcpyDeviceToHost, st));   // Q offsets, Q total, P total
-        STOCS_HIP_CHECK(hipEventRecord(c->ev_t[7], st));
-        AU.record(c->ev_t[7], s0);
-        // the survivors move behind their tiles' offsets while the host waits for the totals: the compacted lists are sized by
-        // the gathered ones here (the totals are what the wait is for)
-        if (!one_stream) { if ((rc = d_pk_c.alloc(totP0)) || (rc = d_pv_c.alloc(totP0)) || (rc = d_qk_c.alloc(totQ0)) || (rc = d_qv_c.alloc(totQ0))) return rc; }
-        if (sq != st) {
-            STOCS_HIP_CHECK(hipEventRecord(c->ev_fork, st));          // tile offsets are scanned on st
-            STOCS_HIP_CHECK(hipStreamWaitEvent(sq, c->ev_fork, 0));
-            AU.record(c->ev_fork, s0); AU.wait(s1, c->ev_fork);
-        }
-        AU.use(s1, d_qk_raw.p, false, "gathered Q keys", "compact Q"); AU.use(s1, d_qv_raw.p, false, "gathered Q pairs", "compact Q"); AU.use(s1, d_bits_q.p, false, "alive bits of Q", "compact Q");
-        AU.use(s1, tiles_q, false, "tile counts of Q", "compact Q"); AU.use(s1, d_qk_c.p, true, "surviving Q keys", "compact Q"); AU.use(s1, d_qv_c.p, true, "surviving Q pairs", "compact Q");
-        AU.use(s0, d_pk_raw.p, false, "gathered P keys", "compact P"); AU.use(s0, d_pv_raw.p, false, "gathered P pairs", "compact P"); AU.use(s0, d_bits_p.p, false, "alive bits of P", "compact P");
-        AU.use(s0, tiles_p, false, "tile counts of P", "compact P"); AU.use(s0, d_pk_c.p, true, "surviving P keys", "compact P"); AU.use(s0, d_pv_c.p, true, "surviving P pairs", "compact P");
-        if (one_stream)
-            hipLaunchKernelGGL(survivors_compact_dual_kernel<KeyT>, dim3(std::max(1u, (std::max(ntp, ntq) + 3u) / 4u), 3), dim3(256), 0, st, sp, sqd, d_po, (const uint32_t*)plan.p_off,
-                               (const uint32_t*)plan.q_off, nB, d_comb_off.p);
-        else {
-        hipLaunchKernelGGL(survivors_compact_kernel<KeyT>, dim3((ntq + 3u) / 4u), dim3(256), 0, sq, (const KeyT*)d_qk_raw.p, (const uint32_t*)d_qv_raw.p, (uint32_t)totQ0,
-                           (const unsigned long long*)d_bits_q.p, (const uint32_t*)(d_surv.p + o_tq), d_qk_c.p, d_qv_c.p, d_po, 1);
-        hipLaunchKernelGGL(survivors_compact_kernel<KeyT>, dim3((ntp + 3u) / 4u), dim3(256), 0, st, (const KeyT*)d_pk_raw.p, (const uint32_t*)d_pv_raw.p, (uint32_t)totP0,
-                           (const unsigned long long*)d_bits_p.p, (const uint32_t*)(d_surv.p + o_tp), d_pk_c.p, d_pv_c.p, d_po, 0);
-        }
-        STOCS_HIP_CHECK(hipGetLastError());
-        c->timing[0].lap("enqueue gather + occupancy + survivor counts");
-        if (S->deferred) { const int rd = S->deferred(); S->deferred = nullptr; if (rd) return rd; c->timing[0].lap("host: cone records of the bases (while the device gathers)"); }
-        STOCS_HIP_CHECK(hipEventSynchronize(c->ev_t[7]));   // the read-back, not the compaction behind it
-        AU.host_sync_event(c->ev_t[7]);
-        c->timing[0].lap("wait for the device (survivors)");
-        have_surv_clock = true;
-        if (po_pin) {   // the plan's own totals came with this read-back: were the capacities enough?
-            if (po_pin->overflow || po_pin->totP > (unsigned long long)totP0 || po_pin->totQ > (unsigned long long)totQ0) {
-                STOCS_HIP_CHECK(hipStreamSynchronize(st));            // the compaction behind the read-back: nothing may still touch the arena
-                if (sq != st) STOCS_HIP_CHECK(hipStreamSynchronize(sq));
-                AU.host_sync(s0); AU.host_sync(s1);
-                return 1;
-            }
-        }
-        totP = qoff_pin[nB + 1]; totQ = qoff_pin[nB];
-        memcpy(S->h_qoff.data(), qoff_pin, 4 * ((size_t)nB + 1));
-        if (dbg) fprintf(stderr, "[stocs congruent] survivors: P %zu of %zu, Q %zu of %zu\n", totP, totP0, totQ, totQ0);
-        S->totP = (uint32_t)totP; S->totQ = (uint32_t)totQ;
-        if (totP == 0 || totQ == 0) { S->no_quads = true; return STOCS_OK; }   // no cell is shared: no quads (quad_off is all zero already)
-        pk_in = d_pk_c.p; pv_in = d_pv_c.p; qk_in = d_qk_c.p; qv_in = d_qv_c.p;
-        if (one_stream) { qk_in = d_pk_c.p + totP; qv_in = d_pv_c.p + totP; }   // (Q's survivors sit behind P's)
+        if ((rc = reduce_lists<KeyT>(c, S, plan, L, sq, one_stream, lds_words, dbg, d_po, po_pin, outgrown)) || *outgrown || S->no_quads) return rc;
+        totP = S->totP; totQ = S->totQ;
+        pk_in = L.pk_c.p; pv_in = L.pv_c.p; qk_in = L.qk_c.p; qv_in = L.qv_c.p;
+        if (one_stream) { qk_in = L.pk_c.p + totP; qv_in = L.pv_c.p + totP; }   // (Q's survivors sit behind P's)
     }
     if (one_stream) {   // one sorted list: P's part, then Q's
         if ((rc = S->d_pkeys.alloc((totP + totQ) * sizeof(KeyT))) || (rc = S->d_pvals.alloc(totP + totQ))) return rc;
@@ -1488,9 +1551,9 @@ static int count_pass(stocs_ctx* c, CongruentState* S, const PlanDev& plan, bool
     // P side with the run table: sorted by position cell ALONE.  The gather emits base after base and the sort is stable, so
     // inside a cell the entries stay grouped by base, in index order inside a base: the runs of (base, cell) are contiguous
     // all the same, the table finds them wherever they are, and 15 bits are two radix passes where 22 are three.
-    const unsigned end_bit_p = (S->use_table && !getenv("STOCS_CONGRUENT_P_FULLSORT")) ? (unsigned)S->cell_bits : end_bit;
+    const unsigned end_bit_p = (S->use_table && !sw.p_fullsort) ? (unsigned)S->cell_bits : end_bit;
     bool own_p = false, own_q = false;      // (decided per list: by its length per base)
-    if (one_stream) STOCS_HIP_CHECK(cong_sort(NULL, tb1, pk_in, (KeyT*)S->d_pkeys.p, pv_in, S->d_pvals.p, totP + totQ, (unsigned)S->cell_bits, end_bit_p, d_comb_off.p, 2 * nB, st, &own_p));
+    if (one_stream) STOCS_HIP_CHECK(cong_sort(NULL, tb1, pk_in, (KeyT*)S->d_pkeys.p, pv_in, S->d_pvals.p, totP + totQ, (unsigned)S->cell_bits, end_bit_p, L.comb_off.p, 2 * nB, st, &own_p));
     else {
     STOCS_HIP_CHECK(cong_sort(NULL, tb1, pk_in, (KeyT*)S->d_pkeys.p, pv_in, S->d_pvals.p, totP, (unsigned)S->cell_bits, end_bit_p, plan.p_off, nB, st, &own_p));
     STOCS_HIP_CHECK(cong_sort(NULL, tb2, qk_in, (KeyT*)S->d_qkeys.p, qv_in, S->d_qvals.p, totQ, (unsigned)S->cell_bits, end_bit, plan.q_off, nB, st, &own_q));
@@ -1508,11 +1571,11 @@ static int count_pass(stocs_ctx* c, CongruentState* S, const PlanDev& plan, bool
     // The P side first: it is the longer chain (sort + records: ~100 us at Cm against ~70 us of the Q sort), and whichever side is enqueued second
     // starts ~25 us later -- the host needs that long for the first side's five launches (kernel trace of a trial, round 5)
     if (!reduce)
-        hipLaunchKernelGGL(gather_key_kernel<KeyT>, dim3(gather_grid(totP)), dim3(256), 0, st, ix.d_pairs, d_psegs, n_pseg, (uint32_t)totP,
-                           S->d_jobs.p, c->d_munit, 0, S->cell_bits, cell_limit, d_pk_raw.p, d_pv_raw.p, (uint32_t*)NULL, (const PlanOut*)NULL, 0u, (uint32_t)nB);
+        hipLaunchKernelGGL(gather_key_kernel<KeyT>, dim3(gather_grid(totP)), dim3(256), 0, st, ix.d_pairs, plan.psegs, plan.n_pseg, (uint32_t)totP,
+                           S->d_jobs.p, c->d_munit, 0, S->cell_bits, cell_limit, L.pk_raw.p, L.pv_raw.p, (uint32_t*)NULL, (const PlanOut*)NULL, 0u, (uint32_t)nB);
     STOCS_HIP_CHECK(hipGetLastError());
     // one stable sort per list: (base, position cell); inside a cell the entries keep the index order of the gather
-    if (one_stream) STOCS_HIP_CHECK(cong_sort(d_tmp.p, tb1, pk_in, (KeyT*)S->d_pkeys.p, pv_in, S->d_pvals.p, totP + totQ, (unsigned)S->cell_bits, end_bit_p, d_comb_off.p, 2 * nB, st, &own_p));
+    if (one_stream) STOCS_HIP_CHECK(cong_sort(d_tmp.p, tb1, pk_in, (KeyT*)S->d_pkeys.p, pv_in, S->d_pvals.p, totP + totQ, (unsigned)S->cell_bits, end_bit_p, L.comb_off.p, 2 * nB, st, &own_p));
     else
     STOCS_HIP_CHECK(cong_sort(d_tmp.p, tb1, pk_in, (KeyT*)S->d_pkeys.p, pv_in, S->d_pvals.p, totP, (unsigned)S->cell_bits, end_bit_p, plan.p_off, nB, st, &own_p));
     if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[2], st));
@@ -1531,8 +1594,8 @@ static int count_pass(stocs_ctx* c, CongruentState* S, const PlanDev& plan, bool
     AU.use(s0, pk_in, false, "P keys to sort", "sort P"); AU.use(s0, pv_in, false, "P pairs to sort", "sort P");
     AU.use(s0, S->d_pkeys.p, true, "sorted P keys", "sort P + records"); AU.use(s0, S->d_pvals.p, true, "sorted P pairs", "sort P + records"); AU.use(s0, plan.jobs, false, "base jobs", "P records");
     if (!reduce)
-        hipLaunchKernelGGL(gather_key_kernel<KeyT>, dim3(gather_grid(totQ)), dim3(256), 0, sq, ix.d_pairs, d_qsegs, n_qseg, (uint32_t)totQ,
-                           S->d_jobs.p, c->d_munit, 1, S->cell_bits, cell_limit, d_qk_raw.p, d_qv_raw.p, (uint32_t*)NULL, (const PlanOut*)NULL, 0u, (uint32_t)nB);
+        hipLaunchKernelGGL(gather_key_kernel<KeyT>, dim3(gather_grid(totQ)), dim3(256), 0, sq, ix.d_pairs, plan.qsegs, plan.n_qseg, (uint32_t)totQ,
+                           S->d_jobs.p, c->d_munit, 1, S->cell_bits, cell_limit, L.qk_raw.p, L.qv_raw.p, (uint32_t*)NULL, (const PlanOut*)NULL, 0u, (uint32_t)nB);
     if (!one_stream)
     STOCS_HIP_CHECK(cong_sort(d_tmp2.p, tb2, qk_in, (KeyT*)S->d_qkeys.p, qv_in, S->d_qvals.p, totQ, (unsigned)S->cell_bits, end_bit, plan.q_off, nB, sq, &own_q));
     AU.use(s1, plan.q_off, false, "Q offsets per base", "sort Q");
@@ -1572,26 +1635,268 @@ static int count_pass(stocs_ctx* c, CongruentState* S, const PlanDev& plan, bool
     STOCS_HIP_CHECK(hipStreamSynchronize(st));
     AU.host_sync(s0);
     c->timing[0].lap("wait for the device (counts)");
-    {   // the device's own account of that wait (every event has completed: the stream is idle, the Q side was joined into it)
-        static const char* const what_all[5] = {"device: Q gather + sort (aux stream, from the fork)", "device: P gather + sort", "device: P records + wait for Q",
-                                                "device: join count", "device: scan + offsets + read-back"};
-        static const char* const what_red[6] = {"device: gathers + occupancy + survivor counts (both lists)", "device: Q sort (aux stream, from the fork; its compaction ran during the wait)",
-                                                "device: P sort", "device: P records + wait for Q", "device: join count", "device: scan + offsets + read-back"};
-        const int from[6] = {6, 0, 0, 2, 3, 4}, to[6] = {7, 1, 2, 3, 4, 5};
-        static const char* const what_one[6] = {"device: gathers + occupancy + survivor counts (both lists in every launch)", "", "device: sort (P and Q as one list of 2 nB segments)",
-                                                "device: P records", "device: join count", "device: scan + offsets + read-back"};
-        for (int k = have_surv_clock ? 0 : 1; k < 6 && dev_clock; ++k) {
-            if (one_stream && k == 1) continue;
-            float ms = -1.0f;
-            if (hipEventElapsedTime(&ms, c->ev_t[from[k]], c->ev_t[to[k]]) != hipSuccess) ms = -1.0f;
-            CallTiming& T = c->timing[0];
-            if (T.n < CallTiming::MAX_STEPS) { T.label[T.n] = one_stream ? what_one[k] : (have_surv_clock ? what_red[k] : what_all[k - 1]); T.ms[T.n] = (double)ms; ++T.n; }
-        }
-        c->timing[0].t_last = CallTiming::now_s();
+    // the device's own account of that wait (every event has completed: the stream is idle, the Q side was joined into it): a group
+    // between two events per row, named per form (NULL: not a group of that form)
+    static const struct { int from, to; const char *all, *red, *one; } groups[] = {
+        {6, 7, NULL, "device: gathers + occupancy + survivor counts (both lists)", "device: gathers + occupancy + survivor counts (both lists in every launch)"},
+        {0, 1, "device: Q gather + sort (aux stream, from the fork)", "device: Q sort (aux stream, from the fork; its compaction ran during the wait)", NULL},
+        {0, 2, "device: P gather + sort", "device: P sort", "device: sort (P and Q as one list of 2 nB segments)"},
+        {2, 3, "device: P records + wait for Q", "device: P records + wait for Q", "device: P records"},
+        {3, 4, "device: join count", "device: join count", "device: join count"},
+        {4, 5, "device: scan + offsets + read-back", "device: scan + offsets + read-back", "device: scan + offsets + read-back"}};
+    CallTiming& T = c->timing[0];
+    for (const auto& g : groups) {
+        const char* what = one_stream ? g.one : (reduce ? g.red : g.all);
+        if (!dev_clock || !what || T.n >= CallTiming::MAX_STEPS) continue;
+        float ms = -1.0f;
+        if (hipEventElapsedTime(&ms, c->ev_t[g.from], c->ev_t[g.to]) != hipSuccess) ms = -1.0f;
+        T.label[T.n] = what; T.ms[T.n] = (double)ms; ++T.n;
     }
+    T.t_last = CallTiming::now_s();
     STOCS_TICK("join count+scan")
     if (sort_err_pin[0] || sort_err_pin[1]) { set_error("stocs_find_congruent_all: the pair-list sort gave up waiting for a tile (sort32.hip)"); return STOCS_ERR_HIP; }
     for (int b = 0; b <= nB; ++b) c->quad_off[b] = qoff_at[b];
+    return STOCS_OK;
+}
+
+// the pair lists are too long for this call: a piece of a trial batch (too_big != NULL) hears it and splits its base set, any other caller gets an error
+static int lists_too_long(int* too_big, const char* why) { if (too_big) *too_big = 1; else set_error("%s", why); return too_big ? STOCS_OK : STOCS_ERR_CAPACITY; }
+
+// stocs_internal_find_congruent without its exit (below): every return of this body, error or not, goes through there
+static int find_congruent(stocs_ctx* c, const CongruentSwitches& sw, int64_t* total_quads, size_t max_bytes, int* too_big) {
+    const bool dbg = sw.debug_timing;
+    double tprev = now_s();
+    c->timing[0].begin();
+    if (!c->index.built) { set_error("stocs_find_congruent_all: PPF index not built"); return STOCS_ERR_STATE; }
+    const int nB = (int)c->bases.size();
+    if (!c->cong) c->cong = new CongruentState();
+    CongruentState* S = (CongruentState*)c->cong;
+    S->valid = false;
+    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));   // the previous trial's buffers are about to be reused
+    if (c->aux_stream) STOCS_HIP_CHECK(hipStreamSynchronize(c->aux_stream));   // (idle unless an earlier call failed half way)
+    c->audit.on = sw.debug_streams;
+    c->audit.host_sync(0); if (c->aux_stream) c->audit.host_sync(1);
+    c->audit.retire_all("stocs_find_congruent_all: the arena is recycled");
+    c->timing[0].lap("entry synchronisation");
+    { int rc0 = S->arena_state.reset(); if (rc0) return rc0; }
+    tl_arena = &S->arena_state;
+    if (!S->d_trig) {   // once per context (synchronous copy from static host memory)
+        STOCS_HIP_CHECK(dev_malloc((void**)&S->d_trig, sizeof(float2) * (STOCS_MAX_CONE + 1) * STOCS_MAX_CONE));
+        STOCS_HIP_CHECK(hipMemcpy(S->d_trig, cone_trig(), sizeof(float2) * (STOCS_MAX_CONE + 1) * STOCS_MAX_CONE, hipMemcpyHostToDevice));
+    }
+    // pinned block for everything this call reads back: plan totals, Q offsets (4 B per base), per-base quad offsets (8 B)
+    { int rc0 = ensure_pinned(c, (size_t)PIN_VAR + 12 * ((size_t)nB + 1) + 256); if (rc0) return rc0; }
+    c->timing[0].lap("arena reset + pinned block");
+    if (dbg) { const double t_ = now_s(); fprintf(stderr, "[stocs congruent] %-18s %8.3f ms\n", "sync+reset", (t_ - tprev) * 1e3); tprev = t_; }
+    c->quad_off.assign(nB + 1, 0);
+    c->quad_id_bits = 16;
+    if (total_quads) *total_quads = 0;
+    if (nB == 0) return STOCS_OK;
+    if (nB >= (1 << 20)) { set_error("too many bases"); return STOCS_ERR_INVALID; }
+    const PpfIndex& ix = c->index;
+
+    // ---- per base: the job record (invariants, cone table), then the plan of its two lookups ----
+    std::vector<BaseJob> jobs(nB);
+    const float eps_unit = c->prm.distance_threshold / c->ratio;  // getNormalizedEpsilon, pairCreationFunctor.h:141-143
+    const int gridDepth = (int)(-log2f(eps_unit));                // normalset.h:117
+    const int egSize = (int)pow(2.0, (double)gridDepth);          // :118
+    const float cell = 1.f / egSize;                               // :119
+    const float nepsilon = (float)((double)(1.0f / 7.0f) + 0.00001);  // normalset.h:86
+    // ---- key layout ----
+    const long long NC = (long long)egSize * egSize * egSize;
+    // (8 bytes of run table + 2 of occupancy per (base, cell): up to 2.7 GB -- a trial batch brings thousands of bases, and 288 GB are there for it)
+    const bool use_table = NC > 0 && NC * (long long)nB <= (long long)256 * 1024 * 1024;
+    int base_bits = 1, id_bits = 1, cell_bits = 1;
+    while ((1 << base_bits) < nB) base_bits++;
+    while ((1 << id_bits) < c->nM) id_bits++;
+    id_bits = std::max(id_bits, sw.min_id_bits);
+    {   // cells 0 .. limit-1 plus the all-ones "no cell" value
+        const unsigned long long lim = use_table ? (unsigned long long)NC : ((unsigned long long)1 << 31);
+        while (cell_bits < 40 && (((unsigned long long)1 << cell_bits) - 1ull) < lim) cell_bits++;
+    }
+    const bool wide = base_bits + cell_bits > 32 || sw.wide_keys;
+    // both pair lists are reduced to the entries with a partner cell when one byte per (base, cell) is a small table (count_pass)
+    const bool reduce = use_table && ((unsigned long long)nB << cell_bits) <= (1ull << 29) && !sw.keep_all;
+    // a batch's bases: the cone records wait until the device is busy (S->deferred, below)
+    const bool defer_cone = nB >= 512;
+    for (int b = 0; b < nB; ++b) {
+        const BaseRec& B = c->bases[b];
+        BaseJob& J = jobs[b];
+        memset(&J, 0, sizeof(J));
+        J.inv1 = B.inv1; J.inv2 = B.inv2;
+        J.cell = cell; J.egSize = egSize;
+        if (defer_cone) continue;
+        J.cos_alpha = dot3(normalized3(c->h_spos[B.ids[1]] - c->h_spos[B.ids[0]]), normalized3(c->h_spos[B.ids[3]] - c->h_spos[B.ids[2]]));  // stocs.cpp:801-803
+        fill_cone_table(&J);
+    }
+    const PlanLayout L(nB);
+    if (S->plan_bytes < L.bytes) {
+        if (S->d_plan) (void)hipFree(S->d_plan);
+        S->d_plan = NULL; S->plan_bytes = 0;
+        STOCS_HIP_CHECK(dev_malloc((void**)&S->d_plan, 2 * L.bytes));
+        S->plan_bytes = 2 * L.bytes;
+    }
+    if (S->stage_bytes < L.stage) {
+        if (S->h_stage) (void)hipHostFree(S->h_stage);
+        S->h_stage = NULL; S->stage_bytes = 0;
+        STOCS_HIP_CHECK(pinned_malloc(&S->h_stage, 2 * L.stage));   // counted: a regrow inside a trial must show up
+        S->stage_bytes = 2 * L.stage;
+    }
+    c->timing[0].lap("host: jobs + cone tables + buffers");
+    char* h = (char*)S->h_stage;
+    char* dpl = S->d_plan;
+    PlanDev plan = {(BaseJob*)(dpl + L.jobs), (Segment*)(dpl + L.pseg), (Segment*)(dpl + L.qseg), (uint32_t*)(dpl + L.qoff), (uint32_t*)(dpl + L.poff),
+                    (int32_t*)(dpl + L.bids), (unsigned int*)(dpl + L.err), 0, 0};
+    uint64_t totP = 0, totQ = 0;
+    std::vector<uint32_t>& q_off = S->h_qoff;
+    q_off.assign(nB + 1, 0);
+    {
+        int32_t* bids = (int32_t*)(h + L.bids);
+        for (int b = 0; b < nB; ++b) for (int k = 0; k < 4; ++k) bids[4 * b + k] = c->bases[b].ids[k];
+        memset(h + L.err, 0, 256);
+    }
+    // the plan, on the device: 2 x nB small workgroups probe the bucket table, one workgroup lays the lists out; the host reads
+    // back four totals and the Q offsets (it sizes the sorts with them) -- 0.2 ms of host work per trial otherwise
+    memcpy(h + L.jobs, jobs.data(), sizeof(BaseJob) * (size_t)nB);
+    STOCS_HIP_CHECK(hipMemcpyAsync(dpl, h, L.up, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(plan_ranges_kernel, dim3((unsigned)nB, 2), dim3(64), 0, c->stream, ix.d_bucket_start, ix.tr, ix.rot, ix.NA, ix.nD, plan.bids,
+                       (const float4*)c->d_spos, (const float4*)c->d_snrmw, nB, (uint2*)(dpl + L.rng), (uint32_t*)(dpl + L.nr), (uint32_t*)(dpl + L.tot));
+    launch_plan_offsets(c->stream, nB, dpl, L, plan);
+    hipLaunchKernelGGL(plan_segments_kernel, dim3((unsigned)((2 * nB + 3) / 4)), dim3(256), 0, c->stream, nB, (const uint2*)(dpl + L.rng), (const uint32_t*)(dpl + L.nr),
+                       (const uint32_t*)(dpl + L.tot), plan.psegs, plan.qsegs, (const uint32_t*)plan.p_off, (const uint32_t*)plan.q_off, (const uint32_t*)(dpl + L.spo),
+                       (const uint32_t*)(dpl + L.sqo));
+    STOCS_HIP_CHECK(hipGetLastError());
+    // read-backs land in the pinned block (a copy into pageable memory -- a stack variable, a std::vector -- takes the
+    // runtime's staging path): totals in the fixed slot, the Q offsets behind the per-base quad offsets of count_pass
+    static_assert(sizeof(PlanOut) <= 256, "PlanOut must fit its pinned slot");
+    PlanOut* po_pin = (PlanOut*)((char*)c->h_pin + PIN_CONGRUENT);
+    uint32_t* qoff_pin = (uint32_t*)((char*)c->h_pin + PIN_VAR + 8 * ((size_t)nB + 1));
+    STOCS_HIP_CHECK(hipMemcpyAsync(po_pin, dpl + L.out, sizeof(PlanOut), hipMemcpyDeviceToHost, c->stream));
+    if (!reduce) STOCS_HIP_CHECK(hipMemcpyAsync(qoff_pin, plan.q_off, 4 * ((size_t)nB + 1), hipMemcpyDeviceToHost, c->stream));   // (reduced lists: their own offsets come later)
+    c->timing[0].lap("enqueue plan upload + kernels + read-back");
+    if (defer_cone) {
+        // staged in the pinned block behind the upload, uploaded and patched into the device's jobs on the context's stream -- behind
+        // the plan kernels, ahead of the join
+        float4* hc = (float4*)(h + L.cone);
+        BaseJob* dj = plan.jobs;
+        S->deferred = [c, hc, dj, nB]() -> int {
+            for (int b = 0; b < nB; ++b) {
+                const BaseRec& B = c->bases[b];
+                BaseJob J;
+                J.cos_alpha = dot3(normalized3(c->h_spos[B.ids[1]] - c->h_spos[B.ids[0]]), normalized3(c->h_spos[B.ids[3]] - c->h_spos[B.ids[2]]));  // stocs.cpp:801-803
+                fill_cone_table(&J);
+                float nb_bits; memcpy(&nb_bits, &J.nb, 4);
+                hc[b] = make_float4(J.cos_alpha, J.sin_alpha, nb_bits, 0.f);
+            }
+            DevBuf<float4> d_cone;
+            int rc1 = d_cone.alloc((size_t)nB);
+            if (rc1) return rc1;
+            STOCS_HIP_CHECK(hipMemcpyAsync(d_cone.p, hc, sizeof(float4) * (size_t)nB, hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(patch_cone_kernel, dim3((unsigned)((nB + 255) / 256)), dim3(256), 0, c->stream, dj, (const float4*)d_cone.p, nB);
+            STOCS_HIP_CHECK(hipGetLastError());
+            return STOCS_OK;
+        };
+    }
+    // ONE sizing synchronisation point instead of two (plan totals, then survivors' totals): when an earlier trial of this scene
+    // has shown how long the lists get, buffers and launches are sized by a capacity (1.6 x that, per base), the kernels read the
+    // planned totals from the device, and the plan's totals come back together with the survivors' (count_pass).  A plan beyond
+    // the capacity is detected there and redone with exact sizes.  Not for a trial batch under a memory ceiling (its caller
+    // needs the totals first) and not for the first trial of a scene.
+    bool optimistic = reduce && S->hist_nB > 0 && !sw.exact_sizes;
+    if (optimistic) {
+        const double scale = sw.capacity * (double)nB / (double)S->hist_nB;
+        totP = (uint64_t)std::min(4.0e9, (double)S->hist_P * scale + sw.slack);
+        totQ = (uint64_t)std::min(4.0e9, (double)S->hist_Q * scale + sw.slack);
+        // a piece of a trial batch (too_big: its caller wants to hear when the lists do not fit the ceiling) goes this way only when the
+        // capacities are far below the ceiling -- small frames, where the plan's round trip is a tenth of the piece; near the ceiling the
+        // totals are read first, as in round 4
+        if (too_big && max_bytes && (double)(totP + totQ) * 64.0 + (use_table ? (double)(NC * nB) * 8.0 : 0.0) + (double)((size_t)nB << cell_bits) / 4.0 > 0.25 * (double)max_bytes) {
+            optimistic = false; totP = 0; totQ = 0;
+        }
+    }
+    if (!optimistic) {
+        STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
+        c->timing[0].lap("wait for the device (plan)");
+        const PlanOut po = *po_pin;
+        if (!reduce) memcpy(q_off.data(), qoff_pin, 4 * ((size_t)nB + 1));
+        if (po.overflow) return lists_too_long(too_big, "pair lists exceed 2^32 entries");
+        totP = po.totP; totQ = po.totQ; plan.n_pseg = (int)po.n_pseg; plan.n_qseg = (int)po.n_qseg;
+        S->hist_P = po.totP; S->hist_Q = po.totQ; S->hist_nB = nB;
+    }
+    STOCS_TICK("plan (device)")
+    if (dbg) fprintf(stderr, "[stocs congruent] %s totP %llu totQ %llu segs %d %d\n", optimistic ? "capacities" : "planned", (unsigned long long)totP, (unsigned long long)totQ, plan.n_pseg, plan.n_qseg);
+    if (totP == 0 || totQ == 0) return STOCS_OK;
+    if (id_bits > 16) { set_error("|M| = %d: model ids beyond 16 bits do not fit the packed pairs and quads", c->nM); return STOCS_ERR_CAPACITY; }
+
+    auto reserve_arena = [&](uint64_t nP, uint64_t nQ, bool* over) -> int {
+        // everything this call allocates, estimated up front: one slab, one hipMalloc in a context's lifetime (if sizes stay put)
+        const size_t kb = wide ? 8 : 4;
+        const size_t tables = use_table ? (size_t)(NC * nB) * 8 : 0;
+        const size_t per_entry = 3 * kb + 8 + 16 + 8 + (reduce ? kb + 4 : 0);   // (the compacted copies of the reduced form)
+        const size_t occ = reduce ? 2 * (((size_t)nB << cell_bits) / 8 + 8) : 0;
+        const size_t need = (size_t)nP * per_entry + (size_t)nQ * per_entry + tables + occ + ((size_t)48 << 20);
+        if (max_bytes && need > max_bytes && nB > 1) { *over = true; return STOCS_OK; }
+        // (under a ceiling -- a piece of a trial batch -- the slab is 1.5 x the need, not twice it: 40 Cm trials need 36 GB)
+        const int rc_r = S->arena_state.reserve(need, (max_bytes && need > ((size_t)4 << 30)) ? 1.5 : 2.0);   // (small pieces: room for the next call's capacities, which follow THIS call's totals)
+        if (rc_r == STOCS_ERR_NOMEM && max_bytes && nB > 1) { *over = true; return STOCS_OK; }   // the device is fuller than the ceiling assumes: the caller halves the piece
+        return rc_r;
+    };
+    {
+        bool over = false;
+        int rc0 = reserve_arena(totP, totQ, &over);
+        if (rc0) return rc0;
+        if (over) return lists_too_long(too_big, "pair lists beyond the memory ceiling");   // the caller splits its base set
+    }
+    c->timing[0].lap(!use_table ? "arena reserve (no run table, 64-bit keys)" : (wide ? "arena reserve (64-bit keys)" : "arena reserve"));   // (names the form)
+    S->nB = nB; S->totP = (uint32_t)totP; S->totQ = (uint32_t)totQ; S->nepsilon = nepsilon;
+    S->half_inv_neps = (float)(0.5 / (double)nepsilon);
+    S->NC = NC; S->use_table = use_table; S->wide = wide; S->reduce = reduce;
+    {   // two points of one position cell are at most a cell diagonal apart (cell edge = ratio / egSize < 2 epsilon); the
+        // float roundings of the two world-space points and of the unit-cube coordinates are far below the 1e-5 m allowed for
+        const double cell_world = (double)c->ratio / (double)egSize, diag2 = 3.0 * (cell_world * 1.001 + 1e-5) * (cell_world * 1.001 + 1e-5);
+        S->close_cells = diag2 < 0.999 * (double)c->prm.distance_threshold && !sw.distance_gate;
+    }
+    S->id_bits = id_bits; S->base_bits = base_bits; S->cell_bits = cell_bits;
+    S->base_in_key = 4 * id_bits + base_bits <= 64;
+    S->no_quads = false;
+    const PlanOut* d_po = optimistic ? (const PlanOut*)(dpl + L.out) : NULL;
+    bool outgrown = false;
+    int rc = wide ? count_pass<uint64_t>(c, S, plan, sw, tprev, d_po, optimistic ? po_pin : NULL, &outgrown)
+                  : count_pass<uint32_t>(c, S, plan, sw, tprev, d_po, optimistic ? po_pin : NULL, &outgrown);
+    if (rc) return rc;   // (on an error the read-back may not have landed: the capacity history stays as it was)
+    if (optimistic) {    // the read-back of count_pass brought the plan's totals
+        const PlanOut po = *po_pin;
+        if (po.overflow) return lists_too_long(too_big, "pair lists exceed 2^32 entries");
+        S->hist_P = po.totP; S->hist_Q = po.totQ; S->hist_nB = nB;
+        if (outgrown) {
+            // the plan outgrew the capacities: once more with the sizes now known.  The base jobs carry the survivors' offsets by now:
+            // the layout kernel writes the planned ones again (its inputs are still in the planning buffer)
+            c->timing[0].lap("plan beyond the capacities: redone with exact sizes");
+            launch_plan_offsets(c->stream, nB, dpl, L, plan);
+            STOCS_HIP_CHECK(hipGetLastError());
+            { int rc0 = S->arena_state.reset(); if (rc0) return rc0; }
+            tl_arena = &S->arena_state;
+            bool over = false;
+            int rc0 = reserve_arena(po.totP, po.totQ, &over);
+            if (rc0) return rc0;
+            if (over) return lists_too_long(too_big, "pair lists beyond the memory ceiling");   // (a batch's piece: the caller splits its base set)
+            plan.n_pseg = (int)po.n_pseg; plan.n_qseg = (int)po.n_qseg;
+            S->totP = (uint32_t)po.totP; S->totQ = (uint32_t)po.totQ;
+            S->no_quads = false;
+            if (po.totP == 0 || po.totQ == 0) return STOCS_OK;
+            rc = wide ? count_pass<uint64_t>(c, S, plan, sw, tprev, NULL, NULL, &outgrown) : count_pass<uint32_t>(c, S, plan, sw, tprev, NULL, NULL, &outgrown);
+            if (rc) return rc;
+        }
+    }
+    if (!c->audit.violations.empty()) {   // STOCS_DEBUG_STREAMS: a use without an event edge between the two streams
+        set_error("stocs_find_congruent_all: %zu stream-ordering violation(s); first: %s", c->audit.violations.size(), c->audit.violations[0].c_str());
+        c->audit.violations.clear();
+        return STOCS_ERR_STATE;
+    }
+    if (S->no_quads) return STOCS_OK;   // as with empty lists: nothing to materialise, every base has zero quads
+    S->valid = true;
+    c->quad_id_bits = id_bits;
+    if (total_quads) *total_quads = (int64_t)c->quad_off[nB];
     return STOCS_OK;
 }
 
@@ -1653,311 +1958,17 @@ int stocs_internal_find_congruent(stocs_ctx* c, int64_t* total_quads, size_t max
     if (!c) return STOCS_ERR_INVALID;
     if (too_big) *too_big = 0;
     DeviceGuard dev_guard(c->device);
-    const bool dbg = getenv("STOCS_DEBUG_TIMING") != NULL;
-    double tprev = now_s();
-    c->timing[0].begin();
-    if (!c->index.built) { set_error("stocs_find_congruent_all: PPF index not built"); return STOCS_ERR_STATE; }
-    const int nB = (int)c->bases.size();
-    if (!c->cong) c->cong = new CongruentState();
-    CongruentState* S = (CongruentState*)c->cong;
-    S->valid = false;
-    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));   // the previous trial's buffers are about to be reused
-    if (c->aux_stream) STOCS_HIP_CHECK(hipStreamSynchronize(c->aux_stream));   // (idle unless an earlier call failed half way)
-    c->audit.on = getenv("STOCS_DEBUG_STREAMS") != NULL;
-    c->audit.host_sync(0); if (c->aux_stream) c->audit.host_sync(1);
-    c->audit.retire_all("stocs_find_congruent_all: the arena is recycled");
-    c->timing[0].lap("entry synchronisation");
-    { int rc0 = S->arena_state.reset(); if (rc0) return rc0; }
-    tl_arena = &S->arena_state;
-    if (!S->d_trig) {   // once per context (synchronous copy from static host memory)
-        STOCS_HIP_CHECK(dev_malloc((void**)&S->d_trig, sizeof(float2) * (STOCS_MAX_CONE + 1) * STOCS_MAX_CONE));
-        STOCS_HIP_CHECK(hipMemcpy(S->d_trig, cone_trig(), sizeof(float2) * (STOCS_MAX_CONE + 1) * STOCS_MAX_CONE, hipMemcpyHostToDevice));
+    const int rc = find_congruent(c, CongruentSwitches::read(), total_quads, max_bytes, too_big);
+    // The one exit.  The deferred host work never outlives the call, and a failed call leaves nothing in flight: no read-back still
+    // landing in the pinned block (ensure_pinned may free it), nothing still running on the auxiliary stream.  The synchronisation's
+    // own status is ignored (the first error message stands); a successful call is synchronised at the next one's entry.
+    if (c->cong) ((CongruentState*)c->cong)->deferred = nullptr;
+    if (rc != STOCS_OK) {
+        (void)hipStreamSynchronize(c->stream);
+        if (c->aux_stream) (void)hipStreamSynchronize(c->aux_stream);
+        c->audit.host_sync(0); if (c->aux_stream) c->audit.host_sync(1);
     }
-    // pinned block for everything this call reads back: plan totals, Q offsets (4 B per base), per-base quad offsets (8 B)
-    { int rc0 = ensure_pinned(c, (size_t)PIN_VAR + 12 * ((size_t)nB + 1) + 256); if (rc0) return rc0; }
-    c->timing[0].lap("arena reset + pinned block");
-    if (dbg) { const double t_ = now_s(); fprintf(stderr, "[stocs congruent] %-18s %8.3f ms\n", "sync+reset", (t_ - tprev) * 1e3); tprev = t_; }
-    c->quad_off.assign(nB + 1, 0);
-    c->quad_id_bits = 16;
-    if (total_quads) *total_quads = 0;
-    if (nB == 0) return STOCS_OK;
-    if (nB >= (1 << 20)) { set_error("too many bases"); return STOCS_ERR_INVALID; }
-    const PpfIndex& ix = c->index;
-
-    // ---- per base: the job record (invariants, cone table), then the plan of its two lookups ----
-    std::vector<BaseJob> jobs(nB);
-    const float eps_unit = c->prm.distance_threshold / c->ratio;  // getNormalizedEpsilon, pairCreationFunctor.h:141-143
-    const int gridDepth = (int)(-log2f(eps_unit));                // normalset.h:117
-    const int egSize = (int)pow(2.0, (double)gridDepth);          // :118
-    const float cell = 1.f / egSize;                               // :119
-    const float nepsilon = (float)((double)(1.0f / 7.0f) + 0.00001);  // normalset.h:86
-    // ---- key layout ----
-    const long long NC = (long long)egSize * egSize * egSize;
-    // (8 bytes of run table + 2 of occupancy per (base, cell): up to 2.7 GB -- a trial batch brings thousands of bases, and 288 GB are there for it)
-    const bool use_table = NC > 0 && NC * (long long)nB <= (long long)256 * 1024 * 1024;
-    int base_bits = 1, id_bits = 1, cell_bits = 1;
-    while ((1 << base_bits) < nB) base_bits++;
-    while ((1 << id_bits) < c->nM) id_bits++;
-    if (const char* e = getenv("STOCS_CONGRUENT_ID_BITS")) id_bits = std::max(id_bits, std::min(16, atoi(e)));   // keeps the wide-id form of the quad keys testable on small models
-    {   // cells 0 .. limit-1 plus the all-ones "no cell" value
-        const unsigned long long lim = use_table ? (unsigned long long)NC : ((unsigned long long)1 << 31);
-        while (cell_bits < 40 && (((unsigned long long)1 << cell_bits) - 1ull) < lim) cell_bits++;
-    }
-    const bool wide = base_bits + cell_bits > 32 || getenv("STOCS_CONGRUENT_WIDE_KEYS") != NULL;   // env: keeps the 64-bit path testable
-    // both pair lists are reduced to the entries with a partner cell when one byte per (base, cell) is a small table (count_pass)
-    const bool reduce = use_table && ((unsigned long long)nB << cell_bits) <= (1ull << 29) && !getenv("STOCS_CONGRUENT_KEEP_ALL");
-    // a batch's bases: the cone records wait until the device is busy (S->deferred, below)
-    const bool defer_cone = nB >= 512 && nB <= PLAN_MAX_BASES && !getenv("STOCS_CONGRUENT_HOST_PLAN");
-    S->deferred = nullptr;
-    for (int b = 0; b < nB; ++b) {
-        const BaseRec& B = c->bases[b];
-        BaseJob& J = jobs[b];
-        memset(&J, 0, sizeof(J));
-        J.inv1 = B.inv1; J.inv2 = B.inv2;
-        J.cell = cell; J.egSize = egSize;
-        if (defer_cone) continue;
-        J.cos_alpha = dot3(normalized3(c->h_spos[B.ids[1]] - c->h_spos[B.ids[0]]), normalized3(c->h_spos[B.ids[3]] - c->h_spos[B.ids[2]]));  // stocs.cpp:801-803
-        fill_cone_table(&J);
-    }
-    // the planning buffer: jobs | base ids | error words | ranges | range counts | totals | P segments | Q segments | p_off | q_off |
-    // segment offsets | result.  A lookup is at most 128 ranges, so every array has a bound that depends on nB alone.
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t nb = (size_t)nB;
-    const size_t o_jobs = 0, o_bids = o_jobs + al(sizeof(BaseJob) * nb), o_err = o_bids + al(16 * nb), o_rng = o_err + 256, o_nr = o_rng + al(2 * nb * 128 * 8),
-                 o_tot = o_nr + al(2 * nb * 4), o_pseg = o_tot + al(2 * nb * 4), o_qseg = o_pseg + al(nb * 128 * sizeof(Segment)),
-                 o_poff = o_qseg + al(nb * 128 * sizeof(Segment)), o_qoff = o_poff + al((nb + 1) * 4), o_spo = o_qoff + al((nb + 2) * 4), o_sqo = o_spo + al((nb + 1) * 4),
-                 o_out = o_sqo + al((nb + 1) * 4), plan_bytes = o_out + 256, up_bytes = o_err + 256;
-    if (S->plan_bytes < plan_bytes) {
-        if (S->d_plan) (void)hipFree(S->d_plan);
-        S->d_plan = NULL; S->plan_bytes = 0;
-        STOCS_HIP_CHECK(dev_malloc((void**)&S->d_plan, 2 * plan_bytes));
-        S->plan_bytes = 2 * plan_bytes;
-    }
-    const size_t host_plan_bytes = o_out;   // the host-planned form stages everything up to the result block
-    if (S->stage_bytes < host_plan_bytes) {
-        if (S->h_stage) (void)hipHostFree(S->h_stage);
-        S->h_stage = NULL; S->stage_bytes = 0;
-        STOCS_HIP_CHECK(pinned_malloc(&S->h_stage, 2 * host_plan_bytes));   // counted: a regrow inside a trial must show up
-        S->stage_bytes = 2 * host_plan_bytes;
-    }
-    c->timing[0].lap("host: jobs + cone tables + buffers");
-    char* h = (char*)S->h_stage;
-    char* dpl = S->d_plan;
-    PlanDev plan;
-    plan.jobs = (BaseJob*)(dpl + o_jobs); plan.bids = (int32_t*)(dpl + o_bids); plan.err = (unsigned int*)(dpl + o_err);
-    plan.psegs = (Segment*)(dpl + o_pseg); plan.qsegs = (Segment*)(dpl + o_qseg); plan.p_off = (uint32_t*)(dpl + o_poff); plan.q_off = (uint32_t*)(dpl + o_qoff);
-    plan.n_pseg = 0; plan.n_qseg = 0;
-    uint64_t totP = 0, totQ = 0;
-    bool optimistic = false;
-    const PlanOut* d_po = NULL; const PlanOut* po_pinned = NULL;
-    std::vector<uint32_t>& q_off = S->h_qoff;
-    q_off.assign(nB + 1, 0);
-    {
-        int32_t* bids = (int32_t*)(h + o_bids);
-        for (int b = 0; b < nB; ++b) for (int k = 0; k < 4; ++k) bids[4 * b + k] = c->bases[b].ids[k];
-        memset(h + o_err, 0, 256);
-    }
-    if (nB <= PLAN_MAX_BASES && !getenv("STOCS_CONGRUENT_HOST_PLAN")) {
-        // on the device: 2 x nB small workgroups probe the bucket table, one workgroup lays the lists out; the host reads
-        // back four totals and the Q offsets (it sizes the sorts with them) -- 0.2 ms of host work per trial otherwise
-        memcpy(h + o_jobs, jobs.data(), sizeof(BaseJob) * nb);
-        STOCS_HIP_CHECK(hipMemcpyAsync(dpl, h, up_bytes, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(plan_ranges_kernel, dim3((unsigned)nB, 2), dim3(64), 0, c->stream, ix.d_bucket_start, ix.tr, ix.rot, ix.NA, ix.nD, plan.bids,
-                           (const float4*)c->d_spos, (const float4*)c->d_snrmw, nB, (uint2*)(dpl + o_rng), (uint32_t*)(dpl + o_nr), (uint32_t*)(dpl + o_tot));
-        hipLaunchKernelGGL(plan_offsets_kernel, dim3(1), dim3(1024), 0, c->stream, nB, (const uint2*)(dpl + o_rng), (const uint32_t*)(dpl + o_nr), (const uint32_t*)(dpl + o_tot),
-                           plan.jobs, plan.psegs, plan.qsegs, plan.p_off, plan.q_off, (uint32_t*)(dpl + o_spo), (uint32_t*)(dpl + o_sqo), (PlanOut*)(dpl + o_out), plan.err);
-        hipLaunchKernelGGL(plan_segments_kernel, dim3((unsigned)((2 * nB + 3) / 4)), dim3(256), 0, c->stream, nB, (const uint2*)(dpl + o_rng), (const uint32_t*)(dpl + o_nr),
-                           (const uint32_t*)(dpl + o_tot), plan.psegs, plan.qsegs, (const uint32_t*)plan.p_off, (const uint32_t*)plan.q_off, (const uint32_t*)(dpl + o_spo),
-                           (const uint32_t*)(dpl + o_sqo));
-        STOCS_HIP_CHECK(hipGetLastError());
-        // read-backs land in the pinned block (a copy into pageable memory -- a stack variable, a std::vector -- takes the
-        // runtime's staging path): totals in the fixed slot, the Q offsets behind the per-base quad offsets of count_pass
-        static_assert(sizeof(PlanOut) <= 256, "PlanOut must fit its pinned slot");
-        PlanOut* po_pin = (PlanOut*)((char*)c->h_pin + PIN_CONGRUENT);
-        uint32_t* qoff_pin = (uint32_t*)((char*)c->h_pin + PIN_VAR + 8 * (nb + 1));
-        STOCS_HIP_CHECK(hipMemcpyAsync(po_pin, dpl + o_out, sizeof(PlanOut), hipMemcpyDeviceToHost, c->stream));
-        if (!reduce) STOCS_HIP_CHECK(hipMemcpyAsync(qoff_pin, plan.q_off, 4 * (nb + 1), hipMemcpyDeviceToHost, c->stream));   // (reduced lists: their own offsets come later)
-        c->timing[0].lap("enqueue plan upload + kernels + read-back");
-        if (defer_cone) {
-            // staged in the part of the pinned block that only the host-planned form uses (ranges), uploaded and patched into the device's
-            // jobs on the context's stream -- behind the plan kernels, ahead of the join
-            float4* hc = (float4*)(h + o_rng);
-            BaseJob* dj = plan.jobs;
-            S->deferred = [c, hc, dj, nB]() -> int {
-                for (int b = 0; b < nB; ++b) {
-                    const BaseRec& B = c->bases[b];
-                    BaseJob J;
-                    J.cos_alpha = dot3(normalized3(c->h_spos[B.ids[1]] - c->h_spos[B.ids[0]]), normalized3(c->h_spos[B.ids[3]] - c->h_spos[B.ids[2]]));  // stocs.cpp:801-803
-                    fill_cone_table(&J);
-                    float nb_bits; memcpy(&nb_bits, &J.nb, 4);
-                    hc[b] = make_float4(J.cos_alpha, J.sin_alpha, nb_bits, 0.f);
-                }
-                DevBuf<float4> d_cone;
-                int rc1 = d_cone.alloc((size_t)nB);
-                if (rc1) return rc1;
-                STOCS_HIP_CHECK(hipMemcpyAsync(d_cone.p, hc, sizeof(float4) * (size_t)nB, hipMemcpyHostToDevice, c->stream));
-                hipLaunchKernelGGL(patch_cone_kernel, dim3((unsigned)((nB + 255) / 256)), dim3(256), 0, c->stream, dj, (const float4*)d_cone.p, nB);
-                STOCS_HIP_CHECK(hipGetLastError());
-                return STOCS_OK;
-            };
-        }
-        // ONE sizing synchronisation point instead of two (plan totals, then survivors' totals): when an earlier trial of this scene
-        // has shown how long the lists get, buffers and launches are sized by a capacity (1.6 x that, per base), the kernels read the
-        // planned totals from the device, and the plan's totals come back together with the survivors' (count_pass).  A plan beyond
-        // the capacity is detected there and redone with exact sizes.  Not for a trial batch under a memory ceiling (its caller
-        // needs the totals first) and not for the first trial of a scene.
-        optimistic = reduce && S->hist_nB > 0 && !getenv("STOCS_CONGRUENT_EXACT_SIZES");
-        if (optimistic) {
-            const char* ce = getenv("STOCS_CONGRUENT_CAPACITY");     // (tests: a factor below 1 forces the redo with exact sizes)
-            const double scale = (ce ? atof(ce) : 1.6) * (double)nB / (double)S->hist_nB, slack = ce ? 1.0 : 1048576.0;
-            totP = (uint64_t)std::min(4.0e9, (double)S->hist_P * scale + slack);
-            totQ = (uint64_t)std::min(4.0e9, (double)S->hist_Q * scale + slack);
-            // a piece of a trial batch (too_big: its caller wants to hear when the lists do not fit the ceiling) goes this way only when the
-            // capacities are far below the ceiling -- small frames, where the plan's round trip is a tenth of the piece; near the ceiling the
-            // totals are read first, as in round 4
-            if (too_big && max_bytes && (double)(totP + totQ) * 64.0 + (use_table ? (double)(NC * nB) * 8.0 : 0.0) + (double)((size_t)nB << cell_bits) / 4.0 > 0.25 * (double)max_bytes) {
-                optimistic = false; totP = 0; totQ = 0;
-            }
-        }
-        if (optimistic) {
-            d_po = (const PlanOut*)(dpl + o_out); po_pinned = po_pin;
-        } else {
-            STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-            c->timing[0].lap("wait for the device (plan)");
-            const PlanOut po = *po_pin;
-            if (!reduce) memcpy(q_off.data(), qoff_pin, 4 * (nb + 1));
-            if (po.overflow) { if (too_big) { *too_big = 1; return STOCS_OK; } set_error("pair lists exceed 2^32 entries"); return STOCS_ERR_CAPACITY; }
-            totP = po.totP; totQ = po.totQ; plan.n_pseg = (int)po.n_pseg; plan.n_qseg = (int)po.n_qseg;
-            S->hist_P = po.totP; S->hist_Q = po.totQ; S->hist_nB = nB;
-        }
-        STOCS_TICK("plan (device)")
-    } else {
-        // on the host (kept for very many bases and for A/B): the same ranges from the host copy of the bucket table
-        std::vector<Segment> psegs, qsegs;
-        std::vector<std::pair<uint32_t, uint32_t> > pr, qr;
-        std::vector<int> keys8((size_t)nB * 8);
-        uint32_t* p_off = (uint32_t*)(h + o_poff);   // P's per-base offsets: the segments of P's sort in the unreduced form (the reduced form rewrites them)
-        for (int b = 0; b < nB; ++b) {   // the keys first, touching the bucket table ahead of the planning loop
-            const BaseRec& B = c->bases[b];
-            int* K1 = &keys8[(size_t)b * 8];
-            int* K2 = K1 + 4;
-            ppf_compute(c->h_spos[B.ids[0]], c->h_snrm[B.ids[0]], c->h_spos[B.ids[1]], c->h_snrm[B.ids[1]], ix.tr, ix.rot, K1);  // stocs.cpp:771
-            ppf_compute(c->h_spos[B.ids[2]], c->h_snrm[B.ids[2]], c->h_spos[B.ids[3]], c->h_snrm[B.ids[3]], ix.tr, ix.rot, K2);  // stocs.cpp:772
-            prefetch_lookup(ix, K1);
-            prefetch_lookup(ix, K2);
-        }
-        for (int b = 0; b < nB; ++b) {
-            BaseJob& J = jobs[b];
-            const int* K1 = &keys8[(size_t)b * 8];
-            const int* K2 = K1 + 4;
-            plan_lookup(ix, K1, &pr);
-            plan_lookup(ix, K2, &qr);
-            uint64_t np = 0, nq = 0;
-            for (size_t r = 0; r < pr.size(); ++r) np += pr[r].second - pr[r].first;
-            for (size_t r = 0; r < qr.size(); ++r) nq += qr[r].second - qr[r].first;
-            if (np == 0 || nq == 0) { np = 0; nq = 0; pr.clear(); qr.clear(); }  // stocs.cpp:788
-            J.p_off = (uint32_t)totP; J.p_len = (uint32_t)np; J.q_off = (uint32_t)totQ; J.q_len = (uint32_t)nq;
-            uint32_t d = (uint32_t)totP;
-            for (size_t r = 0; r < pr.size(); ++r) { Segment sg = {pr[r].first, pr[r].second - pr[r].first, d, (uint32_t)b}; psegs.push_back(sg); d += sg.len; }
-            d = (uint32_t)totQ;
-            for (size_t r = 0; r < qr.size(); ++r) { Segment sg = {qr[r].first, qr[r].second - qr[r].first, d, (uint32_t)b}; qsegs.push_back(sg); d += sg.len; }
-            p_off[b] = (uint32_t)totP; q_off[b] = (uint32_t)totQ;
-            totP += np; totQ += nq;
-            if (totP >= 0xFFFF0000ull || totQ >= 0xFFFF0000ull) { if (too_big) { *too_big = 1; return STOCS_OK; } set_error("pair lists exceed 2^32 entries"); return STOCS_ERR_CAPACITY; }
-        }
-        p_off[nB] = (uint32_t)totP; q_off[nB] = (uint32_t)totQ;
-        if (psegs.size() > nb * 128 || qsegs.size() > nb * 128) { set_error("internal: more than 128 ranges per lookup"); return STOCS_ERR_STATE; }
-        memcpy(h + o_jobs, jobs.data(), sizeof(BaseJob) * nb);
-        memcpy(h + o_pseg, psegs.data(), sizeof(Segment) * psegs.size());
-        memcpy(h + o_qseg, qsegs.data(), sizeof(Segment) * qsegs.size());
-        memcpy(h + o_qoff, q_off.data(), 4 * (nb + 1));
-        STOCS_HIP_CHECK(hipMemcpyAsync(dpl, h, up_bytes, hipMemcpyHostToDevice, c->stream));
-        STOCS_HIP_CHECK(hipMemcpyAsync(dpl + o_pseg, h + o_pseg, sizeof(Segment) * psegs.size(), hipMemcpyHostToDevice, c->stream));
-        STOCS_HIP_CHECK(hipMemcpyAsync(dpl + o_qseg, h + o_qseg, sizeof(Segment) * qsegs.size(), hipMemcpyHostToDevice, c->stream));
-        STOCS_HIP_CHECK(hipMemcpyAsync(dpl + o_poff, h + o_poff, 4 * (nb + 1), hipMemcpyHostToDevice, c->stream));
-        STOCS_HIP_CHECK(hipMemcpyAsync(dpl + o_qoff, h + o_qoff, 4 * (nb + 1), hipMemcpyHostToDevice, c->stream));
-        plan.n_pseg = (int)psegs.size(); plan.n_qseg = (int)qsegs.size();
-        c->timing[0].lap("plan on the host + upload");
-        STOCS_TICK("plan (host)")
-    }
-    if (dbg) fprintf(stderr, "[stocs congruent] %s totP %llu totQ %llu segs %d %d\n", optimistic ? "capacities" : "planned", (unsigned long long)totP, (unsigned long long)totQ, plan.n_pseg, plan.n_qseg);
-    if (totP == 0 || totQ == 0) return STOCS_OK;
-    if (id_bits > 16) { set_error("|M| = %d: model ids beyond 16 bits do not fit the packed pairs and quads", c->nM); return STOCS_ERR_CAPACITY; }
-
-    auto reserve_arena = [&](uint64_t nP, uint64_t nQ, bool* over) -> int {
-        // everything this call allocates, estimated up front: one slab, one hipMalloc in a context's lifetime (if sizes stay put)
-        const size_t kb = wide ? 8 : 4;
-        const size_t tables = use_table ? (size_t)(NC * nB) * 8 : 0;
-        const size_t per_entry = 3 * kb + 8 + 16 + 8 + (reduce ? kb + 4 : 0);   // (the compacted copies of the reduced form)
-        const size_t occ = reduce ? 2 * (((size_t)nB << cell_bits) / 8 + 8) : 0;
-        const size_t need = (size_t)nP * per_entry + (size_t)nQ * per_entry + tables + occ + ((size_t)48 << 20);
-        if (max_bytes && need > max_bytes && nB > 1) { *over = true; return STOCS_OK; }
-        // (under a ceiling -- a piece of a trial batch -- the slab is 1.5 x the need, not twice it: 40 Cm trials need 36 GB)
-        const int rc_r = S->arena_state.reserve(need, (max_bytes && need > ((size_t)4 << 30)) ? 1.5 : 2.0);   // (small pieces: room for the next call's capacities, which follow THIS call's totals)
-        if (rc_r == STOCS_ERR_NOMEM && max_bytes && nB > 1) { *over = true; return STOCS_OK; }   // the device is fuller than the ceiling assumes: the caller halves the piece
-        return rc_r;
-    };
-    {
-        bool over = false;
-        int rc0 = reserve_arena(totP, totQ, &over);
-        if (rc0) return rc0;
-        if (over) { if (too_big) *too_big = 1; return STOCS_OK; }   // the caller splits its base set
-    }
-    c->timing[0].lap(!use_table ? "arena reserve (no run table, 64-bit keys)" : (wide ? "arena reserve (64-bit keys)" : "arena reserve"));   // (names the form)
-    S->nB = nB; S->totP = (uint32_t)totP; S->totQ = (uint32_t)totQ; S->nepsilon = nepsilon;
-    S->half_inv_neps = (float)(0.5 / (double)nepsilon);
-    S->NC = NC; S->use_table = use_table; S->wide = wide; S->reduce = reduce;
-    {   // two points of one position cell are at most a cell diagonal apart (cell edge = ratio / egSize < 2 epsilon); the
-        // float roundings of the two world-space points and of the unit-cube coordinates are far below the 1e-5 m allowed for
-        const double cell_world = (double)c->ratio / (double)egSize, diag2 = 3.0 * (cell_world * 1.001 + 1e-5) * (cell_world * 1.001 + 1e-5);
-        S->close_cells = diag2 < 0.999 * (double)c->prm.distance_threshold && !getenv("STOCS_CONGRUENT_DISTANCE_GATE");
-    }
-    S->id_bits = id_bits; S->base_bits = base_bits; S->cell_bits = cell_bits;
-    S->base_in_key = 4 * id_bits + base_bits <= 64;
-    S->no_quads = false;
-    int rc = wide ? count_pass<uint64_t>(c, S, plan, dbg, tprev, d_po, po_pinned) : count_pass<uint32_t>(c, S, plan, dbg, tprev, d_po, po_pinned);
-    if (optimistic && (rc == STOCS_OK || rc == 1)) {   // (the read-back of count_pass brought the plan's totals; on an error the copy may not have landed: the history stays as it was)
-        const PlanOut po = *po_pinned;
-        if (po.overflow) { if (too_big) { *too_big = 1; return STOCS_OK; } set_error("pair lists exceed 2^32 entries"); return STOCS_ERR_CAPACITY; }
-        S->hist_P = po.totP; S->hist_Q = po.totQ; S->hist_nB = nB;
-        if (rc == 1) {
-            // the plan outgrew the capacities: once more with the sizes now known.  The base jobs carry the survivors' offsets by now:
-            // the layout kernel writes the planned ones again (its inputs are still in the planning buffer)
-            c->timing[0].lap("plan beyond the capacities: redone with exact sizes");
-            const size_t nb2 = (size_t)nB;
-            char* dpl2 = S->d_plan;
-            auto al2 = [](size_t x) { return (x + 255) & ~(size_t)255; };
-            const size_t o_bids2 = al2(sizeof(BaseJob) * nb2), o_err2 = o_bids2 + al2(16 * nb2), o_rng2 = o_err2 + 256, o_nr2 = o_rng2 + al2(2 * nb2 * 128 * 8),
-                         o_tot2 = o_nr2 + al2(2 * nb2 * 4), o_pseg2 = o_tot2 + al2(2 * nb2 * 4), o_qseg2 = o_pseg2 + al2(nb2 * 128 * sizeof(Segment)),
-                         o_poff2 = o_qseg2 + al2(nb2 * 128 * sizeof(Segment)), o_qoff2 = o_poff2 + al2((nb2 + 1) * 4), o_spo2 = o_qoff2 + al2((nb2 + 2) * 4),
-                         o_sqo2 = o_spo2 + al2((nb2 + 1) * 4), o_out2 = o_sqo2 + al2((nb2 + 1) * 4);
-            hipLaunchKernelGGL(plan_offsets_kernel, dim3(1), dim3(1024), 0, c->stream, nB, (const uint2*)(dpl2 + o_rng2), (const uint32_t*)(dpl2 + o_nr2), (const uint32_t*)(dpl2 + o_tot2),
-                               plan.jobs, plan.psegs, plan.qsegs, plan.p_off, plan.q_off, (uint32_t*)(dpl2 + o_spo2), (uint32_t*)(dpl2 + o_sqo2), (PlanOut*)(dpl2 + o_out2), plan.err);
-            STOCS_HIP_CHECK(hipGetLastError());
-            { int rc0 = S->arena_state.reset(); if (rc0) return rc0; }
-            tl_arena = &S->arena_state;
-            bool over = false;
-            int rc0 = reserve_arena(po.totP, po.totQ, &over);
-            if (rc0) return rc0;
-            if (over) { if (too_big) *too_big = 1; return STOCS_OK; }   // (a batch's piece: the caller splits its base set)
-            plan.n_pseg = (int)po.n_pseg; plan.n_qseg = (int)po.n_qseg;
-            S->totP = (uint32_t)po.totP; S->totQ = (uint32_t)po.totQ;
-            S->no_quads = false;
-            if (po.totP == 0 || po.totQ == 0) return STOCS_OK;
-            rc = wide ? count_pass<uint64_t>(c, S, plan, dbg, tprev) : count_pass<uint32_t>(c, S, plan, dbg, tprev);
-        }
-    }
-    if (rc) return rc;
-    if (!c->audit.violations.empty()) {   // STOCS_DEBUG_STREAMS: a use without an event edge between the two streams
-        set_error("stocs_find_congruent_all: %zu stream-ordering violation(s); first: %s", c->audit.violations.size(), c->audit.violations[0].c_str());
-        c->audit.violations.clear();
-        return STOCS_ERR_STATE;
-    }
-    if (S->no_quads) return STOCS_OK;   // as with empty lists: nothing to materialise, every base has zero quads
-    S->valid = true;
-    c->quad_id_bits = id_bits;
-    if (total_quads) *total_quads = (int64_t)c->quad_off[nB];
-    return STOCS_OK;
+    return rc;
 }
 
 int stocs_get_quads(stocs_ctx* c, int slot, int32_t* quads4, int64_t cap, int64_t* n) {

@@ -188,23 +188,6 @@ int plan_lookup(const PpfIndex& ix, const int* K, std::vector<std::pair<uint32_t
     return (int)std::min<int64_t>(total, 0x7fffffff);
 }
 
-// touches the lines of the bucket table that plan_lookup(K) will read (the 4 a3 bins of a probe share a line or two)
-void prefetch_lookup(const PpfIndex& ix, const int* K) {
-    if (K[0] <= 5 || K[1] < 0 || K[2] < 0 || K[3] < 0) return;
-    if (K[0] % ix.tr || K[1] % ix.rot || K[2] % ix.rot || K[3] % ix.rot) return;
-    for (int a = 0; a < 2; ++a)
-        for (int b = 0; b < 4; ++b)
-            for (int cc = 0; cc < 4; ++cc) {
-                const int F0 = K[0] + a * ix.tr, F1 = K[1] + (2 - b) * ix.rot, F2 = K[2] + (2 - cc) * ix.rot, F3 = K[3] - ix.rot;
-                if (F1 < 0 || F2 < 0) continue;
-                const int fd = F0 / ix.tr, f1 = F1 / ix.rot, f2 = F2 / ix.rot, f3 = F3 < 0 ? 0 : F3 / ix.rot;
-                if (fd >= ix.nD || f1 >= ix.NA || f2 >= ix.NA || f3 >= ix.NA) continue;
-                const uint32_t* p = &ix.h_bucket_start[ppf_pack(fd, f1, f2, f3, ix.NA)];
-                __builtin_prefetch(p);
-                __builtin_prefetch(p + 4);
-            }
-}
-
 }  // namespace stocs
 
 using namespace stocs;

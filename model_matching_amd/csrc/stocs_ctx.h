@@ -346,7 +346,6 @@ extern "C" void stocs_internal_free_trials(stocs_ctx* c);
 extern "C" int stocs_internal_find_congruent(stocs_ctx* c, int64_t* total_quads, size_t max_bytes, int* too_big);
 extern "C" void stocs_internal_invalidate_instance(stocs_ctx* c);
 int plan_lookup(const PpfIndex& ix, const int* K, std::vector<std::pair<uint32_t, uint32_t> >* ranges);
-void prefetch_lookup(const PpfIndex& ix, const int* K);
 void compute_thresholds(const stocs_params& prm, Thresholds* t);
 }  // namespace stocs
 

@@ -1,12 +1,12 @@
 """Every form of the congruent-set phase against the CPU oracle (stocs_internal_find_congruent / count_pass, csrc/congruent.hip).
 
-The phase picks its form per call: lookups planned on the device or on the host, pair lists reduced to the entries with a partner cell or
-kept whole, 32- or 64-bit list keys, one stream or two, the library's own sort or rocPRIM's, sizes from a capacity or exact -- and per batch
-size: cone records computed late from 512 bases on, no run table (full lists, 64-bit keys) beyond 8 192 bases on `tiny` (32^3 position
-cells x nB > 2^28).  Here the per-call switches run as a product on ONE context in a shuffled order, each cell on other bases than the one
-before it (state a form forgets to write shows up as a mismatch); the batch sizes run at their edges; the switches read once per process
-run in child processes.  Every result -- per-base quads, walk order, candidates -- is compared with the oracle or, for the candidates,
-bit for bit with the default form on the same bases."""
+The phase picks its form per call: pair lists reduced to the entries with a partner cell or kept whole, 32- or 64-bit list keys, one
+stream or two, the library's own sort or rocPRIM's, sizes from a capacity or exact -- and per batch size: cone records computed late from
+512 bases on, no run table (full lists, 64-bit keys) beyond 8 192 bases on `tiny` (32^3 position cells x nB > 2^28).  Here the per-call
+switches run as a product on ONE context in a shuffled order, each cell on other bases than the one before it (state a form forgets to
+write shows up as a mismatch); the batch sizes run at their edges; the switches read once per process run in child processes.  Every
+result -- per-base quads, walk order, candidates -- is compared with the oracle or, for the candidates, bit for bit with the default form
+on the same bases."""
 import itertools
 import json
 import os
@@ -20,7 +20,7 @@ pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CHILD = os.path.join(HERE, "fresh_process_child.py")
-SWITCHES = ("STOCS_CONGRUENT_HOST_PLAN", "STOCS_CONGRUENT_KEEP_ALL", "STOCS_CONGRUENT_WIDE_KEYS", "STOCS_CONGRUENT_ID_BITS", "STOCS_CONGRUENT_TWO_STREAMS",
+SWITCHES = ("STOCS_CONGRUENT_KEEP_ALL", "STOCS_CONGRUENT_WIDE_KEYS", "STOCS_CONGRUENT_ID_BITS", "STOCS_CONGRUENT_TWO_STREAMS",
             "STOCS_CONGRUENT_ONE_STREAM", "STOCS_CONGRUENT_EXACT_SIZES", "STOCS_CONGRUENT_CAPACITY", "STOCS_CONGRUENT_NO_LDS_BITS",
             "STOCS_CONGRUENT_P_FULLSORT", "STOCS_CONGRUENT_DISTANCE_GATE", "STOCS_TRANSFORMS_HOST_PICKS", "STOCS_DEBUG_STREAMS")
 WALK_ALL = 4096          # walk order: every rank of a base up to this many quads, a seeded sample (first and last rank included) beyond
@@ -113,8 +113,7 @@ def _pick(rng, counts, n_valid, n, n_empty):
 
 
 # ---- the per-call switch matrix ----
-MAIN = {"plan": ({}, {"STOCS_CONGRUENT_HOST_PLAN": "1"}),
-        "lists": ({}, {"STOCS_CONGRUENT_KEEP_ALL": "1"}),
+MAIN = {"lists": ({}, {"STOCS_CONGRUENT_KEEP_ALL": "1"}),
         "keys": ({}, {"STOCS_CONGRUENT_WIDE_KEYS": "1"}, {"STOCS_CONGRUENT_ID_BITS": "16"}),
         "streams": ({}, {"STOCS_CONGRUENT_TWO_STREAMS": "1"}, {"STOCS_CONGRUENT_ONE_STREAM": "1"})}
 PAIRED = {"sizing": ({}, {"STOCS_CONGRUENT_EXACT_SIZES": "1"}, {"STOCS_CONGRUENT_CAPACITY": "0.05"}),
@@ -140,8 +139,8 @@ def _matrix():
     return cells
 
 
-def test_every_combination_of_the_per_call_switches_equals_the_oracle(forms, monkeypatch):
-    """36 cells of plan x lists x keys x streams (sizing, occupancy bits in device memory, P sorted on all bits and the distance gate
+def test_every_combination_of_lists_keys_and_streams_equals_the_oracle(forms, monkeypatch):
+    """18 cells of lists x keys x streams (sizing, occupancy bits in device memory, P sorted on all bits and the distance gate
     paired over them) in a seeded, shuffled order on one context, each on its own subset of the pool (repeats and empty-list bases
     among them).  The host steps of the call name the form that ran; quads and walk order equal the oracle's; the candidates of
     make_transforms equal the default form's on the same bases, bit for bit."""
@@ -168,11 +167,10 @@ def test_every_combination_of_the_per_call_switches_equals_the_oracle(forms, mon
             est.set_bases(bi, bv)
             total = est.find_congruent_all()
             labels = _labels(est)
-            host, reduce, wide = cell["plan"] == 1, cell["lists"] == 0, cell["keys"] == 1
+            reduce, wide = cell["lists"] == 0, cell["keys"] == 1
             one_stream = reduce and not wide and cell["streams"] != 1
-            optimistic = not host and reduce and cell["sizing"] != 1
-            assert ("plan on the host + upload" in labels) == host, (env, labels)
-            assert ("wait for the device (plan)" in labels) == (not host and not optimistic), (env, labels)
+            optimistic = reduce and cell["sizing"] != 1
+            assert ("wait for the device (plan)" in labels) == (not optimistic), (env, labels)
             assert ("enqueue compact/sort/records/join/scan" in labels) == reduce, (env, labels)
             assert ("enqueue gather/sort/records/join/scan" in labels) == (not reduce), (env, labels)
             assert ("arena reserve (64-bit keys)" in labels) == wide and ("arena reserve" in labels) == (not wide), (env, labels)
@@ -228,14 +226,14 @@ def test_a_call_whose_bases_all_have_empty_lists_then_one_with_quads(forms, monk
 
 
 # ---- a trial batch ----
-def test_trial_batch_with_host_planned_full_lists_equals_the_default(forms, monkeypatch):
-    """run_trials (three seeds) with the lookups planned on the host and the lists kept whole: bit for bit the default batch."""
+def test_trial_batch_with_full_lists_equals_the_default(forms, monkeypatch):
+    """run_trials (three seeds) with the lists kept whole: bit for bit the default batch."""
     est, *_ = forms
     _set_switches(monkeypatch, {})
     seeds = [404, 405, 406]
     res0 = est.run_trials(seeds, 24, max_per_base=40, keep_details=True)
     d0 = [(est.trial_quad_counts(t), est.trial_candidates(t)) for t in range(3)]
-    _set_switches(monkeypatch, {"STOCS_CONGRUENT_HOST_PLAN": "1", "STOCS_CONGRUENT_KEEP_ALL": "1"})
+    _set_switches(monkeypatch, {"STOCS_CONGRUENT_KEEP_ALL": "1"})
     res1 = est.run_trials(seeds, 24, max_per_base=40, keep_details=True)
     for t in range(3):
         r0, r1 = res0[t], res1[t]
@@ -248,8 +246,8 @@ def test_trial_batch_with_host_planned_full_lists_equals_the_default(forms, monk
 
 
 # ---- switches read once per process: child processes ----
-def test_switches_cached_per_process_equal_the_oracle(forms, tmp_path):
-    """rocPRIM sorting the 32-bit pair lists (STOCS_SORT=rocprim: default, full lists, host plan) and the gather / survivor count with
+def test_switches_read_once_per_process_equal_the_oracle(forms, tmp_path):
+    """rocPRIM sorting the 32-bit pair lists (STOCS_SORT=rocprim: default, full lists) and the gather / survivor count with
     1, 3 and 7 workgroups (STOCS_GATHER_WGS: every workgroup walks many tiles across base boundaries), 600 bases each (cone records
     deferred): one child process per setting, one after the other, stopping at the first that fails."""
     est, orc, cache, ids, inv, counts, n_valid = forms
@@ -259,7 +257,7 @@ def test_switches_cached_per_process_equal_the_oracle(forms, tmp_path):
     path = str(tmp_path / "bases.npz")
     np.savez(path, ids=bi, inv=bv)
     refs = [cache.get(bi[k], bv[k]) for k in range(len(bi))]
-    cells = [{"STOCS_SORT": "rocprim"}, {"STOCS_SORT": "rocprim", "STOCS_CONGRUENT_KEEP_ALL": "1"}, {"STOCS_SORT": "rocprim", "STOCS_CONGRUENT_HOST_PLAN": "1"},
+    cells = [{"STOCS_SORT": "rocprim"}, {"STOCS_SORT": "rocprim", "STOCS_CONGRUENT_KEEP_ALL": "1"},
              {"STOCS_GATHER_WGS": "1"}, {"STOCS_GATHER_WGS": "3"}, {"STOCS_GATHER_WGS": "7"}]
     for cell in cells:
         env = {k: v for k, v in os.environ.items() if k not in SWITCHES and k not in ("STOCS_SORT", "STOCS_GATHER_WGS")}
@@ -268,10 +266,7 @@ def test_switches_cached_per_process_equal_the_oracle(forms, tmp_path):
         assert p.returncode == 0, (cell, p.returncode, p.stderr[-3000:])
         out = json.loads(p.stdout.strip().splitlines()[-1])
         assert out["total"] == sum(len(q) for q, _ in refs), cell
-        if "STOCS_CONGRUENT_HOST_PLAN" in cell:
-            assert "plan on the host + upload" in out["labels"], (cell, out["labels"])
-        else:
-            assert any(lab.startswith("host: cone records of the bases") for lab in out["labels"]), (cell, out["labels"])
+        assert any(lab.startswith("host: cone records of the bases") for lab in out["labels"]), (cell, out["labels"])
         for k, (qo, so) in enumerate(refs):
             assert np.array_equal(np.array(out["quads"][k], np.int32).reshape(-1, 4), qo), (cell, k)
             assert np.array_equal(np.array(out["walk"][k], np.int32).reshape(-1, 4), so[: len(out["walk"][k]) // 4]), (cell, k)

@@ -245,29 +245,6 @@ def test_quad_keys_of_models_beyond_16384_points(setup, monkeypatch):
     assert len(T0) > 0 and np.array_equal(T0, T1) and np.array_equal(P0, P1) and np.array_equal(b0, b1)
 
 
-def test_host_planned_lookups_equal_device_planned(setup, monkeypatch):
-    """The lookups of a trial (128 buckets per key merged into ranges, list offsets per base) are planned by two small
-    kernels; the host form (plan_lookup over the host copy of the bucket table, kept for very many bases) must lay out the
-    same lists: same counts, same quads in the same orders."""
-    m, s, est, orc = setup
-    est.L.stocs_clear_bases(est.h)
-    valid, ids, inv = est.sample_bases(123, 24)
-    n_dev = est.find_congruent_all()
-    sizes = [len(est.get_quads(k)) for k in range(int(valid.sum()))]
-    monkeypatch.setenv("STOCS_CONGRUENT_HOST_PLAN", "1")
-    assert est.find_congruent_all() == n_dev and n_dev > 0
-    slot = 0
-    for a in range(24):
-        if not valid[a]:
-            continue
-        qo = orc.find_congruent(ids[a], float(inv[a][0]), float(inv[a][1]))
-        assert len(qo) == sizes[slot] and np.array_equal(est.get_quads(slot), qo)
-        if len(qo):
-            so = orc.find_congruent_seq(ids[a], float(inv[a][0]), float(inv[a][1]))
-            assert np.array_equal(est.get_quads_at(slot, np.arange(len(so))), so)
-        slot += 1
-
-
 def test_unreduced_pair_lists_give_the_same_sets(setup, monkeypatch):
     """Before anything is sorted both pair lists are reduced to the entries whose (base, position cell) the other list
     occupies too (an entry without a partner cell can form no set).  The unreduced form -- what a position grid too fine
@@ -427,8 +404,7 @@ def test_two_stream_sections_pass_the_happens_before_audit(setup, monkeypatch):
     n0 = est.find_congruent_all(); c0 = est.make_transforms(40, 9)
     monkeypatch.setenv("STOCS_DEBUG_STREAMS", "1")
     for extra in ({}, {"STOCS_CONGRUENT_EXACT_SIZES": "1"}, {"STOCS_CONGRUENT_KEEP_ALL": "1"}, {"STOCS_CONGRUENT_CAPACITY": "0.05"},
-                  {"STOCS_CONGRUENT_TWO_STREAMS": "1"}, {"STOCS_CONGRUENT_TWO_STREAMS": "1", "STOCS_CONGRUENT_CAPACITY": "0.05"},
-                  {"STOCS_CONGRUENT_HOST_PLAN": "1", "STOCS_CONGRUENT_KEEP_ALL": "1"}):
+                  {"STOCS_CONGRUENT_TWO_STREAMS": "1"}, {"STOCS_CONGRUENT_TWO_STREAMS": "1", "STOCS_CONGRUENT_CAPACITY": "0.05"}):
         for k, v in extra.items():
             monkeypatch.setenv(k, v)
         assert est.find_congruent_all() == n0 and est.make_transforms(40, 9) == c0, extra
