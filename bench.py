@@ -9,6 +9,10 @@ max all-reduce of the packed (score, candidate id) key over xGMI.  Every rank ve
 independent batch (weak scaling: StoCS trials shard one-per-GPU, no data-path collective).
 
 Contract: python bench.py --gpus N --steps K --warmup W ; rank 0 prints ONE JSON line.
+
+A plain run does only what that line's headline needs: set up, warm up, time the K steps, write --dump-outputs, print.  Everything
+else it can measure or check -- the hit census and kernel roofline (live counters, the C5 leg), the untimed whole-path reports, the
+CPU baselines and the oracle comparison of the whole batch -- comes with --full (the --no-* switches then skip parts of it).
 """
 import argparse
 import json
@@ -81,7 +85,7 @@ def add_counters(rec, nested, workload, candidates_arg, groups=None):
         import pmc as pmc_tool
         if shutil.which("rocprofv3"):
             pdir = tempfile.mkdtemp(prefix="stocs_pmc_")
-            child = ["python3", os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline", "--no-pipeline", "--no-pmc", "--no-c5", "--no-hits",
+            child = ["python3", os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "1",     # a plain run: the timed steps alone
                      "--details", os.devnull, "--workload", workload] + (["--candidates", str(candidates_arg)] if candidates_arg else [])
             grp = pmc_tool.GROUPS if not groups else type(pmc_tool.GROUPS)((g, pmc_tool.GROUPS[g]) for g in groups if g in pmc_tool.GROUPS)
             raw = pmc_tool.collect("lcp_coopq_kernel<false", child, pdir, groups=grp)   # the scoring kernel, not its per-point detail form (<true, ...>)
@@ -281,8 +285,9 @@ def compact_line(full):
     di = full.get("distributed")
     if di:
         out["distributed"] = {"world_size": di.get("world_size"), "backend": di.get("backend"), "ranks_reporting": [r.get("rank") for r in di.get("ranks", [])][:8]}
-    rf = full.get("roofline", {})
-    out["roofline"] = {k: rf.get(k) for k in ROOFLINE_KEYS if k in rf}
+    rf = full.get("roofline")
+    if rf:                                                      # (--full only)
+        out["roofline"] = {k: rf.get(k) for k in ROOFLINE_KEYS if k in rf}
     cb = full.get("cpu_baseline")
     if cb:
         out["cpu_baseline"] = {k: cb.get(k) for k in ("value", "unit", "cores", "kind", "sample")}
@@ -414,13 +419,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--workload", default="Cm", choices=["Cm", "C5", "small", "tiny"])
     ap.add_argument("--candidates", type=int, default=0, help="override candidates per step per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check, outside the timed steps, everything beyond the headline: hit census and kernel roofline (live counters, "
+                         "C5 leg), the untimed whole-path reports, the CPU baselines and the oracle comparison of the whole batch")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-pipeline", action="store_true", help="skip the untimed phases 1-4 report")
     ap.add_argument("--cpu-seconds", type=float, default=8.0)
     ap.add_argument("--no-pmc", action="store_true", help="skip the live rocprofv3 counter passes (roofline.traffic / binding become null)")
     ap.add_argument("--no-c5", action="store_true", help="skip the C5 leg of the roofline record (200 000-point scene, 50 000-point model: the HBM-bound configuration)")
     ap.add_argument("--no-prewarm", action="store_true", help="skip the 120 ms of untimed scoring launches that bring an idle chip to its sustained clocks")
-    ap.add_argument("--no-hits", action="store_true", help="skip the hit census behind needed_bytes (the counter child runs: its per-point detail launches must not be profiled)")
+    ap.add_argument("--no-hits", action="store_true", help="skip the hit census behind needed_bytes (its per-point detail launches, ~30 ms of device work in front of the warm-up)")
     ap.add_argument("--no-cpu-pipeline", action="store_true", help="skip the CPU whole-path baseline (oracle run_stocs_estimation at Cm and on the ycb frame)")
     ap.add_argument("--details", default="", help="where the full record goes (default: bench_details.json next to this script, and gpurun_out/ when it exists)")
     ap.add_argument("--pmc-groups", default="", help="comma-separated counter groups of tools/pmc.py for the live passes (default: all)")
@@ -512,7 +520,8 @@ def main():
     # first: it is a measurement of the same batch, and taking it in front leaves the chip at its working clocks for the W warm-up steps
     # and the K timed ones (a 20-step timed region is 24 ms: after 5 warm-up steps from idle it ran 7 % below the 400-step rate in
     # round 3).  The timed region below is unchanged: W untimed steps, then exactly K; the kernel's own clock is taken after it.
-    hits_counted = est.lcp_hit_count(dT, kcand) if not args.no_hits else (0, 0)
+    # (--full only: a plain run has the pre-warm below in front of its warm-up steps)
+    hits_counted = est.lcp_hit_count(dT, kcand) if args.full and not args.no_hits else (0, 0)
     # An idle MI355X needs ~60-100 ms of load to reach its sustained clocks (kernel trace of this command: the same launch takes 1.39, 1.17, 1.13,
     # ... 0.98 ms over the first 25 launches and 0.95 from the 35th on), longer than the driver's whole 5 + 20-step run.  So the chip is brought
     # to its working state first -- the same scoring launch, untimed, for a fixed 120 ms -- and then the contract runs as written: W untimed
@@ -544,25 +553,18 @@ def main():
     poses = float(kcand) * args.steps * world
     value = poses / dt
 
-    # roofline of the dominant kernel: HIP events on the context's stream, resident inputs
-    est.dev_download(dL, lcp)
     key = keys[(state["k"] - 1) & 1]                      # the last step's buffer (torch.cuda.synchronize above covers the side stream)
     final_key = int(key.item())
     final_lcp, final_gid = sdist.unpack_best(final_key) if final_key else (0.0, -1)
-    if world == 1:
-        i_chk = int(np.argmax(lcp))
-        assert final_gid == i_chk and final_lcp == float(lcp[i_chk]), (final_gid, i_chk)
+    if args.full or (rank == 0 and args.dump_outputs):
+        est.dev_download(dL, lcp)                         # every candidate's score of the last step
+        if world == 1:
+            i_chk = int(np.argmax(lcp))
+            assert final_gid == i_chk and final_lcp == float(lcp[i_chk]), (final_gid, i_chk)
     if rank == 0 and args.dump_outputs:
         dump_outputs(args.dump_outputs, lcp, final_lcp, final_gid)
-    b_pose = 68 + 52 * est.nM                      # algorithmic bytes per pose
-    best_i = int(np.argmax(lcp))
-    run_pmc = rank == 0 and world == 1 and not args.no_pmc
+    run_pmc = args.full and rank == 0 and world == 1 and not args.no_pmc
     groups = [g for g in args.pmc_groups.split(",") if g] or None
-    reps = max(5, min(args.steps, 400))
-    krec, knest = kernel_record(est, dT, kcand, dL, reps, args.workload, args.candidates, False, hits_counted=hits_counted)   # (counters: after the pipeline section, below)
-    k_ms = krec["kernel_ms"]
-    achieved = b_pose * kcand / (k_ms * 1e-3) / 1e9   # GB/s
-    peak = PEAK_HBM_GBS
 
     out = {
         "metric": "candidate poses verified/sec",
@@ -585,18 +587,26 @@ def main():
         "pre_warm_ms": pre_warm_ms,
         "final_lcp_percent": float(final_lcp) * 100.0,
         "best_global_candidate_id": int(final_gid),
-        "roofline": dict({"bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s", "frac": achieved / peak,
-                          "frac_is_a_ceiling": False, "traffic": None,
-                          "note": "achieved / frac: the SURVEY 8(d) contract figure -- ALGORITHMIC bytes (68 + 52 |M| per pose) over the kernel time against the "
-                                  "HBM peak; it charges a 28-byte scene record to every model point and the model to every pose, so on a cache-resident "
-                                  "workload it is not bounded by 1.  The physical numbers are the flat keys next to it: needed_* (transform + score + one "
-                                  "28-byte record per model point that has a neighbour; needed_frac <= 1, recomputable from the kernel's average duration), "
-                                  "memory_side_* (FETCH_SIZE x2 + WRITE_SIZE of this run: the L2's memory-side requests, Infinity-Cache hits included), "
-                                  "l2_to_l1_*, the unit utilisations and binding_unit / binding_frac = the busiest unit.  `bound` names that unit once the "
-                                  "counters are in (else the contract's \"hbm\"); c5_* is the same record for the one workload whose lists leave the caches",
-                          "kernel": "lcp_coopq_kernel behind stocs_score_transforms_device (kernel_ms includes the ~50 us candidate ordering in front of it where the library orders: scenes with >= 12 MB of lists, i.e. C5, not Cm)"},
-                         **krec),
     }
+    if args.full:
+        # roofline of the dominant kernel: HIP events on the context's stream, resident inputs
+        b_pose = 68 + 52 * est.nM                      # algorithmic bytes per pose
+        reps = max(5, min(args.steps, 400))
+        krec, knest = kernel_record(est, dT, kcand, dL, reps, args.workload, args.candidates, False, hits_counted=hits_counted)   # (counters: after the pipeline section, below)
+        k_ms = krec["kernel_ms"]
+        achieved = b_pose * kcand / (k_ms * 1e-3) / 1e9   # GB/s
+        peak = PEAK_HBM_GBS
+        out["roofline"] = dict({"bound": "hbm", "achieved": achieved, "peak": peak, "unit": "GB/s", "frac": achieved / peak,
+                                "frac_is_a_ceiling": False, "traffic": None,
+                                "note": "achieved / frac: the SURVEY 8(d) contract figure -- ALGORITHMIC bytes (68 + 52 |M| per pose) over the kernel time against the "
+                                        "HBM peak; it charges a 28-byte scene record to every model point and the model to every pose, so on a cache-resident "
+                                        "workload it is not bounded by 1.  The physical numbers are the flat keys next to it: needed_* (transform + score + one "
+                                        "28-byte record per model point that has a neighbour; needed_frac <= 1, recomputable from the kernel's average duration), "
+                                        "memory_side_* (FETCH_SIZE x2 + WRITE_SIZE of this run: the L2's memory-side requests, Infinity-Cache hits included), "
+                                        "l2_to_l1_*, the unit utilisations and binding_unit / binding_frac = the busiest unit.  `bound` names that unit once the "
+                                        "counters are in (else the contract's \"hbm\"); c5_* is the same record for the one workload whose lists leave the caches",
+                                "kernel": "lcp_coopq_kernel behind stocs_score_transforms_device (kernel_ms includes the ~50 us candidate ordering in front of it where the library orders: scenes with >= 12 MB of lists, i.e. C5, not Cm)"},
+                               **krec)
 
     # what the collective saw: every rank reports itself through the same backend (evidence that RCCL ran with N ranks)
     me = {"rank": rank, "local_rank": local_rank, "device": torch.cuda.get_device_name(local_rank), "candidates_per_step": int(kcand),
@@ -608,7 +618,7 @@ def main():
     out["distributed"] = {"world_size": world, "backend": (dist.get_backend() if world > 1 else None), "ranks": ranks,
                           "collective_per_step": "all_reduce(int64 MAX) of the packed (score, candidate id) key, 8 bytes" if world > 1 else None}
 
-    if rank == 0 and world == 1 and not args.no_pipeline and est.nM <= 8192:
+    if args.full and rank == 0 and world == 1 and not args.no_pipeline and est.nM <= 8192:
         out["pipeline"] = pipeline_report(model, scene, local_rank)
         if args.workload == "Cm":
             # the same sizes with a model WITHOUT symmetry: the metric model is an ellipsoid of revolution with one bump, on
@@ -628,7 +638,7 @@ def main():
         out["roofline"]["binding"] = knest["binding"]
         out["roofline"]["pmc"] = knest["pmc"]
     # the same record on C5 (the configuration where the memory side IS the bound): flat c5_* keys in the same object
-    if rank == 0 and world == 1 and not args.no_c5 and args.workload == "Cm":
+    if args.full and rank == 0 and world == 1 and not args.no_c5 and args.workload == "Cm":
         try:
             c5rec, c5nest = c5_leg(local_rank, run_pmc, groups or ["fetch", "write", "mem"])
             out["roofline"].update(c5rec)
@@ -637,7 +647,7 @@ def main():
         except Exception as e:   # the Cm line must not depend on the second workload
             out["roofline"]["c5_error"] = repr(e)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         # CPU baseline: the oracle (single-threaded restatement of the reference's kd-tree LCP) on a
         # bounded sample of the SAME candidate batch.  Reported, never the target.
         from oracle import pyoracle

@@ -424,3 +424,19 @@ def test_bench_contract_line_is_small_and_parses():
     bare["roofline"] = {k: full["roofline"][k] for k in ("bound", "achieved", "peak", "unit", "frac", "traffic")}
     got = json.loads(json.dumps(bench.compact_line(bare)))
     assert got["roofline"]["frac"] == pytest.approx(full["roofline"]["frac"], rel=1e-5) and "cpu_baseline" not in got
+
+
+def test_bench_plain_run_line_has_no_empty_sections():
+    """A plain bench run (no --full) records the contract keys, the config and the final step's winner, no roofline: its line
+    carries those and no empty roofline object."""
+    import json
+    import bench
+    full = json.load(open(os.path.join(ROOT, "profiles", "r04_bench_driver_command.json")))
+    plain = {k: full[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype",
+                                  "data", "config", "rehearsal", "final_lcp_percent", "distributed")}
+    plain["details_file"] = "bench_details.json"
+    got = json.loads(json.dumps(bench.compact_line(plain)))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "config", "final_lcp_percent", "details"):
+        assert k in got, k
+    assert got["value"] == pytest.approx(full["value"], rel=1e-5) and got["ms_per_step"] == pytest.approx(full["ms_per_step"], rel=1e-5)
+    assert not {"roofline", "cpu_baseline", "oracle_check"} & set(got)

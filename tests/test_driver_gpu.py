@@ -274,6 +274,33 @@ def test_bench_dump_outputs_are_the_last_steps_scores(tmp_path, oracle_lib):
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_is_lean_and_full_adds_the_rest(tmp_path):
+    """A plain `bench.py` run measures its timed steps and nothing else: no roofline, no CPU baseline, no oracle comparison, no
+    whole-path report, in the line or in the details file.  `--full` adds them to the same timed steps."""
+    import json
+    recs = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-pmc", "--no-pipeline", "--cpu-seconds", "0.5"])):
+        details = tmp_path / ("%s.json" % mode)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "small",
+                            "--details", str(details)] + extra, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1, r.stdout[-2000:]
+        recs[mode] = json.loads(lines[0]), json.load(open(details))
+    for line, _ in recs.values():
+        assert line["metric"] == "candidate poses verified/sec" and line["unit"] == "poses/s" and line["higher_is_better"] is True
+        assert line["dtype"] == "f32" and line["steps"] == 3 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["final_lcp_percent"] > 0
+    line, det = recs["plain"]
+    for k in ("roofline", "cpu_baseline", "cpu_baseline_all_cores", "oracle_check", "pipeline", "cpu_baseline_pipeline"):
+        assert k not in line and k not in det, k
+    line, det = recs["full"]
+    assert line["roofline"]["kernel_ms"] > 0 and det["roofline"]["hits_per_pose"] > 0
+    assert line["cpu_baseline"]["value"] > 0 and det["oracle_check"]["candidates_compared"] == 2048 and det["oracle_check"]["within_tolerance"]
+    assert recs["full"][1]["final_lcp_percent"] == recs["plain"][1]["final_lcp_percent"]     # the same batch, the same last step
+
+
+@pytest.mark.gpu
 def test_stocs_single_instance_mode_on_packed_dove(tmp_path):
     """edge map present -> the driver takes the sample_instance_base path (stocs_match_one_object.cpp:90)."""
     from model_matching_amd import cloudio

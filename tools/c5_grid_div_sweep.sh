@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/c5_div; mkdir -p $O
 for d in 1 2 4; do
-  STOCS_GRID_DIV=$d STOCS_DEBUG_TIMING=1 timeout -k 10 400 python3 bench.py --workload C5 --steps 20 --warmup 2 --no-pipeline --no-cpu-baseline > $O/c5_div$d.json 2> $O/c5_div$d.err || exit 1
+  STOCS_GRID_DIV=$d STOCS_DEBUG_TIMING=1 timeout -k 10 400 python3 bench.py --full --workload C5 --steps 20 --warmup 2 --no-pipeline --no-cpu-baseline > $O/c5_div$d.json 2> $O/c5_div$d.err || exit 1
   grep "stocs grid" $O/c5_div$d.err | tail -1
   python - <<PY
 import json

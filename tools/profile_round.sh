@@ -20,11 +20,11 @@ timeout -k 10 500 python3 $R/tools/pmc_all.py $OUT/pmc_pipe -- python3 $R/tools/
 timeout -k 10 500 python3 $R/tools/pmc_all.py $OUT/pmc_trials -- python3 $R/tools/trials.py --example synth:Cm --trials 16 --batch 16 > $OUT/pmc_trials_Cm16.json 2> $OUT/pmc_trials_Cm16.err; echo "pmc_all trials rc $?"
 timeout -k 10 300 python3 $R/tools/pmc.py "lcp_coopq_kernel<false" $OUT/pmc_lcp -- $B --steps 3 --warmup 1 > $OUT/lcp_pmc.json 2> $OUT/lcp_pmc.err; echo "pmc lcp rc $?"
 cd $R
-timeout -k 10 900 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc $?"
+timeout -k 10 900 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err; echo "bench rc $?"
 cp bench_details.json $OUT/bench_details.json 2>/dev/null
-timeout -k 10 900 python3 bench.py --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench2.err; echo "bench (the driver's command) rc $?"
+timeout -k 10 900 python3 bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver_command.json 2> $OUT/bench2.err; echo "bench (the driver's command) rc $?"
 cp bench_details.json $OUT/bench_driver_command_details.json 2>/dev/null
-timeout -k 10 900 python3 bench.py --workload C5 --steps 40 --warmup 3 --no-pipeline --cpu-seconds 6 > $OUT/bench_C5.json 2> $OUT/bench_C5.err; echo "bench C5 rc $?"
+timeout -k 10 900 python3 bench.py --full --workload C5 --steps 40 --warmup 3 --no-pipeline --cpu-seconds 6 > $OUT/bench_C5.json 2> $OUT/bench_C5.err; echo "bench C5 rc $?"
 cp bench_details.json $OUT/bench_C5_details.json 2>/dev/null
 fi
 if [ $PART = A ]; then echo "part A written under $OUT"; exit 0; fi
