@@ -305,6 +305,14 @@ public:
     }
 
     void set_seed(uint64_t seed) { seed_ = seed; attempt_ = 0; la_n_ = 0; la_in_ctx_ = false; }
+    // Extension, no reference counterpart: with `on`, a nearest-neighbour query whose closest scene points lie at exactly the same
+    // float32 distance takes the point the reference's kd-tree returns instead of the one with the largest index (stocs_set_option
+    // "exact_ties", include/stocs_hip.h; divergence Q11).  Every score and pose then follows the reference's integer answers exactly;
+    // it costs a kd-tree build per scene and a slower scoring kernel.  Off by default.
+    void set_exact_ties(bool on) {
+        const int rc = stocs_set_option(ctx_, "exact_ties", on ? 1 : 0);
+        if (rc != STOCS_OK) throw std::runtime_error(std::string("stocs_set_option(exact_ties): ") + stocs_last_error());
+    }
     // not in the reference (one estimator per scene there): the next frame against the same model; the model
     // clouds and the PPF index are kept, everything derived from the old scene is dropped
     void set_scene(const SceneCloud& scene) {

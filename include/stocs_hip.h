@@ -317,8 +317,21 @@ int stocs_icp_point_to_plane(const float* src_pos3, int nsrc, const float* tgt_p
  *   the new scene's field at once, on the context's auxiliary stream (a frame stream on a fixed camera will cross it again).
  * "lcp_group": lanes that verify one queued query together in the queue-fed kernels: 4 (two entries of a 128-byte list line per
  *   lane, sixteen queries per trip).  The only value of the product library (8, one entry per lane, is the form of rounds 1-3a
- *   and lives in the measurement build). ---- */
+ *   and lives in the measurement build).
+ * "exact_ties": 0 (default) = a query whose nearest scene points lie at exactly the same float32 distance takes the one with the
+ *   largest scene index (divergence Q11: every other integer result already equals the reference's).  1 = it takes the point the
+ *   reference's kd-tree (kdtree.h:394-459) returns -- the one its visiting order reaches last -- so that every (candidate, model
+ *   point) query of every scoring entry point (stocs_score_transforms(_device), stocs_score_best_device(_async), stocs_verify_all,
+ *   stocs_lcp_detail, stocs_lcp_hit_count, stocs_run_trials) returns exactly the reference's scene index, and scores and arg-max
+ *   keys follow from those answers.  Costs: a host build of the reference-order tree per scene (at the first exact-mode scoring
+ *   call after a scene change, or in stocs_ctx_set_scene when the option is already on; that call synchronises) and a slower
+ *   scoring kernel (a lane per query, whole cell lists, no patch test; see DESIGN.md 2 for measured figures).  Default-mode
+ *   kernels are untouched.  Other values are STOCS_ERR_INVALID.  This one option changes results (on exact ties only). ---- */
 int stocs_set_option(stocs_ctx* ctx, const char* key, int value);
+/* exact_ties counters of the context's last scoring entry point: *flagged = queries answered by the kd-tree (exact distance ties,
+ * and single answers lying exactly at epsilon^2), *changed = those whose answer differs from the largest-index rule.  Both 0 when that
+ * call ran in default mode.  Synchronises the context's stream. */
+int stocs_last_tie_counts(stocs_ctx* ctx, int64_t* flagged, int64_t* changed);
 /* Diagnostics of that patch test (tests only; no reference counterpart).  patches4: n_patches x (centre x, y, z, radius) in the
  * centred model frame, one per 64 consecutive slots of the sorted model; perm: sorted slot -> model index (|M| entries);
  * geom8: origin x, y, z, cell edge, cap, nx, ny, nz of the scene's distance field; dist: its nx*ny*nz values (x fastest;
@@ -330,6 +343,11 @@ int stocs_get_cull_state(stocs_ctx* ctx, float* patches4, int32_t* perm, int* n_
  * which the scoring kernels walk the model -- perm[slot] = model index, 64 consecutive slots = one compact surface patch --
  * and the bounding sphere of every patch (centre x, y, z in the CENTRED model frame, radius), ceil(nM / 64) of them. */
 int stocs_model_patch_order(const float* model_pos3, int nM, int32_t* perm, float* patches4);
+/* The reference-order kd-tree of the "exact_ties" option on the host, for tests: builds the tree over n points pos3 as the reference
+ * builds it (64 points per leaf, depth 32, widest axis split at the box midpoint, the same in-place partition) and answers nq
+ * radius queries q3 with the query function the device runs: idx[i] = the reference's doQueryRestrictedClosestIndex(q3[i], sqdist),
+ * -1 when no point lies within sqdist. */
+int stocs_kdtree_nn_host(const float* pos3, int n, const float* q3, int nq, float sqdist, int32_t* idx);
 
 /* ---- stream / timing plumbing ---- */
 /* run the context's work on a caller-owned HIP stream (e.g. PyTorch's current stream, so that RCCL

@@ -12,7 +12,7 @@
 //
 //   stocs_single <scene_path> <object_name> [--repo DIR] [--intrinsics fx,cx,fy,cy] [--depth-scale S] [--voxel V] ...
 //   stocs_single --clouds <scene.stcl> <model.stcl> [--edge edge.u8] ...       (flat clouds, e.g. the synthetic workloads)
-// common options: --seed N --bases 100 --max-sets 200 --out FILE --dbg DIR --cluster 1
+// common options: --seed N --bases 100 --max-sets 200 --out FILE --dbg DIR --cluster 1 --exact-ties 1
 // The reference edits its per-data-set constants in the source (README.md:42-66); here they are options with the
 // reference's YCB values as defaults.
 #include <chrono>
@@ -67,7 +67,7 @@ int main(int argc, char** argv) {
     const std::string a1 = argv[clouds ? 2 : 1], a2 = argv[clouds ? 3 : 2];
     if (const char* e = getenv("STOCS_REPO_PATH")) repo_path = e;
     std::string edge_path, out_path, dbg_dir;
-    int do_cluster = 0, n_trials = 0;
+    int do_cluster = 0, n_trials = 0, exact_ties = 0;
     uint64_t seed = 1;
     for (int i = clouds ? 4 : 3; i + 1 < argc; i += 2) {
         const std::string k = argv[i], v = argv[i + 1];
@@ -79,6 +79,7 @@ int main(int argc, char** argv) {
         else if (k == "--dbg") dbg_dir = v;
         else if (k == "--cluster") do_cluster = atoi(v.c_str());
         else if (k == "--trials") n_trials = atoi(v.c_str());   // N independent runs (seeds seed, seed + 1, ...) in one set of GPU launches; the best one is written
+        else if (k == "--exact-ties") exact_ties = atoi(v.c_str());   // 1: the reference kd-tree's answer on exact distance ties (set_exact_ties)
         else if (k == "--repo") repo_path = v;
         else if (k == "--voxel") voxel_size = (float)atof(v.c_str());
         else if (k == "--depth-scale") depth_scale = (float)atof(v.c_str());
@@ -131,6 +132,7 @@ int main(int argc, char** argv) {
     }
     stocs::stocs_estimator& stocs_ptr = *est;
     stocs_ptr.set_seed(seed);
+    if (exact_ties) stocs_ptr.set_exact_ties(true);
 
     if (n_trials > 0) {
         // BASELINE config 4: N independent StoCS trials -- each the whole loop of run_stocs_estimation (:79-165) with its own seed --

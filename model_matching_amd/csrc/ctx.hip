@@ -257,6 +257,7 @@ static int load_scene_impl(stocs_ctx* c, const float* sp, const float* sn, const
     cs = cs / (float)nS;
     for (int i = 0; i < nS; ++i) c->h_spos[i] = c->h_spos[i] - cs;
     c->centroid_scene = cs;
+    c->kd_ready = false;
     free_grid(c);
     lap("host copies + centroid");
     int rc = STOCS_OK;
@@ -295,6 +296,7 @@ static int load_scene_impl(stocs_ctx* c, const float* sp, const float* sn, const
     lap("upload");
     if (!rc) rc = build_grid(c);
     lap("grid");
+    if (!rc && c->exact_ties) { rc = ensure_kdtree(c); lap("kd-tree (exact_ties)"); }
     if (!rc && c->prev_scene_warm && c->lcp_cull == 1 && c->grid.d_dist && c->d_mpatch && c->aux_stream) {
         // (the grid build has synchronised c->stream: the scene arrays the fill reads are in place)
         rc = fill_cull_field(c, c->aux_stream);
@@ -331,6 +333,7 @@ static int load_scene(stocs_ctx* c, const float* sp, const float* sn, const floa
         c->nS = 0;
         c->h_spos.clear(); c->h_snrm.clear(); c->h_sprob.clear(); c->h_sprob0.clear(); c->h_spix.clear();
         c->d_spos = NULL; c->d_snrmw = NULL; c->d_spix = NULL;
+        c->kd_ready = false;
         free_grid(c);
         c->bases.clear(); c->quad_off.clear(); clear_candidates(c);
         c->best_lcp = 0; c->best_index = -1;
@@ -497,6 +500,7 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
     c->lcp_flat = getenv("STOCS_LCP_FLAT") ? atoi(getenv("STOCS_LCP_FLAT")) : 1;
     c->lcp_order = getenv("STOCS_LCP_ORDER") ? atoi(getenv("STOCS_LCP_ORDER")) : 1;
     c->d_order = NULL; c->order_bytes = 0;
+    c->exact_ties = 0; c->kd_ready = false; c->d_kd = NULL; c->kd_bytes = 0; c->d_kd_nodes = NULL; c->d_kd_pts = NULL; c->d_ties = NULL; c->ties_started = false;
     c->d_cdf = NULL; c->cdf_bytes = 0; c->cdf_n = 0; c->prior_epoch = 1; c->cdf_epoch = 0;
     memset(&c->grid, 0, sizeof(c->grid));
     c->d_spos = c->d_snrmw = c->d_mpos = c->d_mnrm = c->d_munit = c->d_mpos_raw = c->d_mpos_s = c->d_mnrm_s = NULL;
@@ -625,7 +629,7 @@ int stocs_ctx_destroy(stocs_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void* ptrs[] = {c->d_scene_mem, c->d_mpos, c->d_mnrm, c->d_munit, c->d_mpos_raw, c->d_mpos_s,
                     c->d_mnrm_s, c->d_mperm, c->d_mpatch, c->index.d_bucket_start,
-                    c->index.d_pairs, c->index.d_exists, c->d_scratch, c->d_best, c->d_cand, c->d_order, c->d_cdf};
+                    c->index.d_pairs, c->index.d_exists, c->d_scratch, c->d_best, c->d_cand, c->d_order, c->d_cdf, c->d_kd};
     stocs_internal_free_congruent(c);
     stocs_internal_free_instance(c);
     stocs_internal_free_trials(c);

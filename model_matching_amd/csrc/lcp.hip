@@ -28,6 +28,7 @@
 
 #include <algorithm>
 
+#include "kdtree.h"
 #include "prims.h"
 #include "stocs_ctx.h"
 
@@ -800,6 +801,91 @@ __global__ __launch_bounds__(64 * WPB, 8) void lcp_coopq_kernel(LcpArgs a, const
     } else if (lane == 0) lcp_store(a, out, cand, acc);
 }
 
+// ---------------------------------------------------------------------------------------------
+// Exact-ties scoring (stocs_set_option "exact_ties" = 1; divergence Q11).  The form of lcp_kernel (a lane per query,
+// one wavefront per candidate, the whole cell list scanned: no sub-cell mask, no early exit, no patch test), which also records
+// whether the query's minimum distance within epsilon^2 is held by two or more listed points.  Such a query -- and one whose only
+// answer lies exactly at epsilon^2, where the reference's strict split-plane pruning (kdtree.h:409) can skip the point -- is answered
+// again by the reference-order kd-tree (kdtree.h), whose answer is the reference's: the point its visiting order reaches last.
+// Every other query has one nearest point, which both structures find.  The lists hold every scene point within epsilon of the cell
+// box except the dominated ones of grid.hip's pruning, which are strictly farther than another listed point from every position of
+// the cell and so can neither win nor tie.  Scores, detail rows, per-trial weights and the arg-max key go through the same helpers as
+// the scan kernels.  ties[0] counts the queries sent to the tree, ties[1] those whose tree answer differs from the largest-index rule.
+// ---------------------------------------------------------------------------------------------
+template <bool DETAIL>
+__global__ __launch_bounds__(256) void lcp_exact_kernel(LcpArgs a, const float* __restrict__ T16, float* __restrict__ out, int n,
+                                                        int32_t* __restrict__ hit_out, uint8_t* __restrict__ cnt_out,
+                                                        const KdNodeP* __restrict__ kd_nodes, const float4* __restrict__ kd_pts,
+                                                        unsigned long long* __restrict__ ties) {
+    const int lane = threadIdx.x & 63;
+    const int cand = lcp_candidate(a, n, threadIdx.x >> 6);
+    if (cand < 0) return;
+    const float* T = T16 + (size_t)cand * 16;
+    const float4* __restrict__ snrmw = lcp_weights_of(a, cand);
+    const float t0 = T[0], t1 = T[1], t2 = T[2], t4 = T[4], t5 = T[5], t6 = T[6], t8 = T[8], t9 = T[9], t10 = T[10],
+                t12 = T[12], t13 = T[13], t14 = T[14];
+    unsigned long long acc = 0ull, n_flag = 0ull, n_changed = 0ull;
+    for (int i = lane; i < a.M; i += 64) {
+        const float4 p = a.mpos[i];
+        const float qx = ((t0 * p.x + t4 * p.y) + t8 * p.z) + t12;
+        const float qy = ((t1 * p.x + t5 * p.y) + t9 * p.z) + t13;
+        const float qz = ((t2 * p.x + t6 * p.y) + t10 * p.z) + t14;
+        const float fx = floorf((qx - a.ox) * a.inv_h);
+        const float fy = floorf((qy - a.oy) * a.inv_h);
+        const float fz = floorf((qz - a.oz) * a.inv_h);
+        int best = -1;
+        bool tie = false;
+        float bd = a.sq_eps;
+        if (fx >= 0.0f && fy >= 0.0f && fz >= 0.0f && fx < (float)a.nx && fy < (float)a.ny && fz < (float)a.nz) {
+            const int cx = (int)fx, cy = (int)fy, cz = (int)fz;
+            const int brick = a.top[((cz >> 3) * a.nby + (cy >> 3)) * a.nbx + (cx >> 3)];
+            if (brick >= 0) {
+                const uint4 cw = a.cells[(size_t)brick * 512 + (((cz & 7) << 6) | ((cy & 7) << 3) | (cx & 7))];
+                for (uint32_t k = 0; k < cw.y; ++k) {
+                    const float4 s = a.list[cw.x + k];
+                    const float dx = qx - s.x, dy = qy - s.y, dz = qz - s.z;
+                    const float d = dx * dx + (dy * dy + dz * dz);
+                    const int ei = __float_as_int(s.w);
+                    // any list order (the dense grid's lists are sorted by distance from the cell centre): the largest index among the
+                    // points at the minimum; a tie only against a point already held, not against the initial bound epsilon^2
+                    if (d < bd) { bd = d; best = ei; tie = false; }
+                    else if (d == bd) { if (best >= 0) { tie = true; best = max(best, ei); } else best = ei; }
+                }
+            }
+        }
+        if (tie || (best >= 0 && bd == a.sq_eps)) {
+            const int kb = kd_query_closest(kd_nodes, kd_pts, qx, qy, qz, a.sq_eps);
+            n_flag++;
+            if (kb != best) n_changed++;
+            best = kb;
+        }
+        bool counted = false;
+        if (best >= 0) {
+            const float4 nm = a.mnrm[i];
+            const float nx = t0 * nm.x + (t4 * nm.y + t8 * nm.z);
+            const float ny = t1 * nm.x + (t5 * nm.y + t9 * nm.z);
+            const float nz = t2 * nm.x + (t6 * nm.y + t10 * nm.z);
+            const float4 sn = snrmw[best];
+            const float d = sn.x * nx + (sn.y * ny + sn.z * nz);
+            counted = (d >= a.dot_lo) && (d <= 1.0f);
+            if (counted) lcp_add(acc, sn.w);
+        }
+        if (DETAIL) {
+            const int orig = a.mperm[i];
+            hit_out[(size_t)cand * a.M + orig] = best;
+            cnt_out[(size_t)cand * a.M + orig] = counted ? 1 : 0;
+        }
+    }
+    acc = lcp_wave_sum(acc);
+    n_flag = lcp_wave_sum(n_flag);
+    n_changed = lcp_wave_sum(n_changed);
+    if (lane == 0) {
+        lcp_store(a, out, cand, acc);
+        if (n_flag) atomicAdd(&ties[0], n_flag);
+        if (n_changed) atomicAdd(&ties[1], n_changed);
+    }
+}
+
 // compute_best_transform (stocs.cpp:982-1004) on the device: max of the packed (score, ~id) keys --
 // larger score wins, lower id wins ties, non-positive scores never win.  Integer max: order independent.
 __global__ __launch_bounds__(256) void best_kernel(const float* __restrict__ lcp, int n, uint32_t id_offset, unsigned long long* __restrict__ best) {
@@ -914,6 +1000,22 @@ int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d
     a.gox = a.goy = a.goz = 0.f; a.g = a.inv_g = a.cap = 0.f; a.gnx = a.gny = a.gnz = 0;
     c->scene_scored++;
     c->scene_work += (double)n * (double)c->nM;
+    if (c->exact_ties) {
+        // the reference-order tie rule (lcp_exact_kernel): every candidate in batch order, the arg-max in the same epilogue
+        int rc = ensure_kdtree(c);
+        if (rc) return rc;
+        if (!c->ties_started) { STOCS_HIP_CHECK(hipMemsetAsync(c->d_ties, 0, 16, c->stream)); c->ties_started = true; }
+        a.order = NULL; a.xcd_blocks = 0;
+#ifdef STOCS_TOOLS_BUILD
+        a.ablate = 0;
+#endif
+        if (d_best8 && !(d_best8 == c->d_best && c->best_is_zero)) STOCS_HIP_CHECK(hipMemsetAsync(d_best8, 0, 8, c->stream));
+        if (d_best8 == c->d_best) c->best_is_zero = false;
+        if (d_hit) hipLaunchKernelGGL((lcp_exact_kernel<true>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted, c->d_kd_nodes, c->d_kd_pts, c->d_ties);
+        else hipLaunchKernelGGL((lcp_exact_kernel<false>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted, c->d_kd_nodes, c->d_kd_pts, c->d_ties);
+        STOCS_HIP_CHECK(hipGetLastError());
+        return STOCS_OK;
+    }
     if (c->lcp_cull && c->grid.d_dist && c->d_mpatch && (c->grid.dist_ready || c->lcp_cull >= 2 || c->scene_work >= c->lcp_cull_after)) {
         int rc = fill_cull_field(c);
         if (rc) return rc;
@@ -1098,12 +1200,14 @@ extern "C" {
 int stocs_score_transforms_device(stocs_ctx* c, const void* d_T16, int n, void* d_lcp) {
     if (!c || n < 0 || (n && (!d_T16 || !d_lcp))) return STOCS_ERR_INVALID;
     DeviceGuard dev_guard(c->device);
+    begin_scoring_call(c);
     return launch_lcp(c, (const float*)d_T16, n, (float*)d_lcp, NULL, NULL, NULL, 0);
 }
 
 int stocs_score_transforms(stocs_ctx* c, const float* T_host, int n, float* lcp_host) {
     if (!c || n < 0 || (n && (!T_host || !lcp_host))) return STOCS_ERR_INVALID;
     DeviceGuard dev_guard(c->device);
+    begin_scoring_call(c);
     if (n == 0) return STOCS_OK;
     const size_t tb = (size_t)n * 64, lb = (size_t)n * 4;
     int rc = ensure_scratch(c, tb + lb + 256);
@@ -1121,6 +1225,7 @@ int stocs_score_transforms(stocs_ctx* c, const float* T_host, int n, float* lcp_
 int stocs_lcp_detail(stocs_ctx* c, const float* T_host, int32_t* hit, uint8_t* counted) {
     if (!c || !T_host || !hit || !counted) return STOCS_ERR_INVALID;
     DeviceGuard dev_guard(c->device);
+    begin_scoring_call(c);
     const size_t M = (size_t)c->nM;
     int rc = ensure_scratch(c, 256 + 256 + M * 4 + 256 + M);
     if (rc) return rc;
@@ -1149,6 +1254,7 @@ __global__ __launch_bounds__(256) void hit_count_kernel(const int32_t* __restric
 int stocs_lcp_hit_count(stocs_ctx* c, const void* d_T16, int n, int64_t* hits, int64_t* counted) {
     if (!c || n < 0 || (n && !d_T16) || !hits) return STOCS_ERR_INVALID;
     DeviceGuard dev_guard(c->device);
+    begin_scoring_call(c);
     *hits = 0;
     if (counted) *counted = 0;
     if (n == 0 || c->nM == 0) return STOCS_OK;
@@ -1220,6 +1326,7 @@ int stocs_best_device_async(stocs_ctx* c, const void* d_lcp, int n, uint32_t id_
 int stocs_score_best_device_async(stocs_ctx* c, const void* d_T16, int n, void* d_lcp, uint32_t id_offset, void* d_key8) {
     if (!c || !d_key8 || n < 0 || (n && (!d_T16 || !d_lcp))) return STOCS_ERR_INVALID;
     DeviceGuard dev_guard(c->device);
+    begin_scoring_call(c);
     return launch_lcp(c, (const float*)d_T16, n, (float*)d_lcp, NULL, NULL, (unsigned long long*)d_key8, id_offset);
 }
 
@@ -1251,6 +1358,12 @@ int stocs_set_option(stocs_ctx* c, const char* key, int value) {
     // 1: stocs_find_congruent_all times its kernel groups with HIP events ("device: ..." steps of stocs_last_call_timing); 0 (default): host steps only
     if (!strcmp(key, "device_clock") && (value == 0 || value == 1)) { c->device_clock = value; return STOCS_OK; }
     if (!strcmp(key, "lcp_flat") && (value == 0 || value == 1)) { c->lcp_flat = value; return STOCS_OK; }
+    // 1: tied nearest-neighbour queries take the reference kd-tree's answer (lcp_exact_kernel, kdtree.h); 0 (default): largest index
+    if (!strcmp(key, "exact_ties")) {
+        if (value != 0 && value != 1) { set_error("stocs_set_option: exact_ties takes 0 or 1, not %d", value); return STOCS_ERR_INVALID; }
+        c->exact_ties = value;
+        return STOCS_OK;
+    }
     // 0: one wavefront per candidate, 1 (default): four wavefronts share a candidate's model points (same scores)
     if (!strcmp(key, "lcp_split") && (value == 0 || value == 1)) { c->lcp_split = value; return STOCS_OK; }
     // 0: every 64-point step is walked; 1 (default): steps whose bounding sphere is out of reach of the scene are skipped once the scene's
@@ -1302,6 +1415,7 @@ int stocs_get_cull_state(stocs_ctx* c, float* patches4, int32_t* perm, int* n_pa
 int stocs_time_score_kernel(stocs_ctx* c, const void* d_T16, int n, void* d_lcp, int reps, float* avg_ms) {
     if (!c || !avg_ms || reps <= 0 || n <= 0) return STOCS_ERR_INVALID;
     DeviceGuard dev_guard(c->device);
+    begin_scoring_call(c);
     STOCS_HIP_CHECK(hipEventRecord(c->ev0, c->stream));
     for (int r = 0; r < reps; ++r) {
         int rc = launch_lcp(c, (const float*)d_T16, n, (float*)d_lcp, NULL, NULL, NULL, 0);

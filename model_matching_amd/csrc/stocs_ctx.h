@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/stocs_hip.h"
+#include "kdtree.h"
 #include "stocs_math.h"
 #include "stream_audit.h"
 
@@ -254,6 +255,17 @@ struct stocs_ctx {
     int lcp_order;     // 0: candidates in batch order; 1: spatially ordered processing of big batches; 2: + XCD-contiguous blocks
     void* d_order;     // keys / permutation / sort scratch of the ordering
     size_t order_bytes;
+    // "exact_ties" (stocs_set_option): tied nearest-neighbour queries answered by the reference-order kd-tree (kdtree.h).  The tree
+    // of the current scene is built at the first exact-mode scoring call after a scene change (at stocs_ctx_set_scene when the
+    // option is already on) and lives in one grow-only device block: tie counters (flagged, changed) | nodes | points in tree order
+    int exact_ties;
+    bool kd_ready;                 // kd_host / d_kd hold the tree of the current scene
+    stocs::KdTreeHost kd_host;
+    char* d_kd; size_t kd_bytes;
+    const stocs::KdNodeP* d_kd_nodes;
+    const float4* d_kd_pts;
+    unsigned long long* d_ties;    // [0] tied queries seen, [1] those whose reference answer differs from the largest-index rule
+    bool ties_started;             // the current entry point has zeroed the counters (stocs_last_tie_counts reads 0 / 0 otherwise)
     // class-mode sampling, lean kernel (sample.hip): exclusive prefix sums of the prior's 2^32 fixed-point weights in scene order (S + 1
     // entries), recomputed when the class probabilities on the device have changed (prior_epoch) or the scene has (cdf_n)
     void* d_cdf; size_t cdf_bytes, cdf_n; unsigned long long prior_epoch, cdf_epoch;
@@ -330,6 +342,9 @@ int ensure_pinned(stocs_ctx* c, size_t bytes);   // c->h_pin of at least `bytes`
 enum { PIN_CONGRUENT = 0, PIN_TRANSFORMS = 256, PIN_VERIFY = 512, PIN_BEST = 768, PIN_VAR = 1024 };   // fixed slots, then the per-call variable part
 // d_best8 != NULL: the kernel's epilogue also takes the arg-max of compute_best_transform over the batch into that word (zeroed in front)
 int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d_hit, uint8_t* d_counted, unsigned long long* d_best8, uint32_t id_offset);
+// every scoring entry point calls this first: the tie counters of stocs_last_tie_counts then cover that call alone (no device work)
+inline void begin_scoring_call(stocs_ctx* c) { c->ties_started = false; }
+int ensure_kdtree(stocs_ctx* c);   // kdtree.hip: the kd-tree of the current scene on the device (exact_ties); synchronises
 int sample_trials(stocs_ctx* c, int mode, int nT, const uint64_t* seeds, int nA, float dispersion, BaseOut* res_host, const float4** snrmw0, size_t* snrmw_stride);   // sample.hip
 int build_ppf_index(stocs_ctx* c);
 int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune);

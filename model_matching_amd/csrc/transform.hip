@@ -471,6 +471,7 @@ int stocs_get_candidates(stocs_ctx* c, float* T16, float* pose16, float* lcp, in
 int stocs_verify_all(stocs_ctx* c, float* best_lcp, int* best_idx, float* best_pose16) {
     if (!c) return STOCS_ERR_INVALID;
     DeviceGuard dev_guard(c->device);
+    begin_scoring_call(c);
     const int n = c->n_cands;
     c->best_lcp = 0; c->best_index = -1;
     float pose[16];

@@ -93,6 +93,7 @@ int stocs_run_trials(stocs_ctx* c, int mode, int n_trials, const uint64_t* seeds
                      stocs_trial_result* out) {
     if (!c || n_trials < 0 || n_attempts < 0 || max_per_base <= 0 || (mode != 0 && mode != 1) || (n_trials && !seeds)) return STOCS_ERR_INVALID;
     DeviceGuard dev_guard(c->device);
+    begin_scoring_call(c);
     const double t_entry = now_ms();
     if (!c->index.built) { set_error("stocs_run_trials: PPF index not built"); return STOCS_ERR_STATE; }
     if (mode == 1 && n_attempts > 254) { set_error("instance mode labels segments with a u8 (<= 254 attempts, Q14)"); return STOCS_ERR_INVALID; }

@@ -338,6 +338,13 @@ class StocsEstimator:
     def set_option(self, key, value):
         capi.check(self.L.stocs_set_option(self.h, key.encode(), int(value)))
 
+    def last_tie_counts(self):
+        """(flagged, changed) of the last scoring call in exact_ties mode: queries the reference-order kd-tree answered, and those
+        whose answer differs from the default largest-index rule.  (0, 0) after a default-mode call."""
+        f = C.c_int64(0); ch = C.c_int64(0)
+        capi.check(self.L.stocs_last_tie_counts(self.h, C.byref(f), C.byref(ch)))
+        return int(f.value), int(ch.value)
+
     def best_device(self, dL, n, id_offset=0):
         """(best_lcp, global id) of n device-resident scores; (0.0, -1) when none is positive."""
         key = C.c_uint64(0)
@@ -383,6 +390,17 @@ class StocsEstimator:
         ms = C.c_float(0)
         capi.check(self.L.stocs_time_score_kernel(self.h, dT, n, dL, reps, C.byref(ms)))
         return ms.value
+
+
+def kdtree_nn_host(pos3, queries3, sqdist):
+    """The reference-order kd-tree of the exact_ties option on the host (stocs_kdtree_nn_host): built over pos3 (n, 3), one radius
+    query per row of queries3 (q, 3); returns the scene indices (-1: nothing within sqdist)."""
+    L = capi.load()
+    p, pp = capi.f32(np.asarray(pos3, np.float32).reshape(-1, 3))
+    q, pq = capi.f32(np.asarray(queries3, np.float32).reshape(-1, 3))
+    out = np.zeros(max(len(q), 1), np.int32)
+    capi.check(L.stocs_kdtree_nn_host(pp, len(p), pq, len(q), float(sqdist), out.ctypes.data_as(capi._ip)))
+    return out[:len(q)]
 
 
 def cluster_poses(poses16, lcp, acceptable_fraction, best_score, maximum_pose_count, min_distance, min_angle, sym):

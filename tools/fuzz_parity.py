@@ -9,7 +9,9 @@ device kernel with the union-find flood fill) against the oracle's literal BFS, 
 the last attempt and the decayed class prior.
 With --batch every workload also runs four trials as ONE batch (stocs_run_trials): trial 0 against the oracle's run, trials 1-3
 against the same seeds run alone through the single-trial calls (bitwise: counts, candidates, scores, winner).
-usage: python tools/fuzz_parity.py [N] [first_seed] [--instance] [--batch]"""
+With --exact-ties every context runs with stocs_set_option("exact_ties", 1): no tie escape is applied, and the summary adds the
+queries the reference-order kd-tree answered (ties_flagged) and those whose answer differs from the default rule (ties_changed).
+usage: python tools/fuzz_parity.py [N] [first_seed] [--instance] [--batch] [--exact-ties]"""
 import json
 import os
 import sys
@@ -89,7 +91,8 @@ def main():
     global n_ties
     instance = "--instance" in sys.argv
     batch = "--batch" in sys.argv
-    argv = [a for a in sys.argv if a not in ("--instance", "--batch")]
+    exact = "--exact-ties" in sys.argv
+    argv = [a for a in sys.argv if a not in ("--instance", "--batch", "--exact-ties")]
     n = int(argv[1]) if len(argv) > 1 else 20
     first = int(argv[2]) if len(argv) > 2 else 1000
     pyoracle.build()
@@ -97,6 +100,7 @@ def main():
     n_inst_bases = 0
     n_batch_trials = 0
     stats = []
+    ties_flagged = ties_changed = 0
     for k in range(n):
         rng = np.random.default_rng(first + k)
         nm = int(rng.integers(120, 420))
@@ -106,6 +110,8 @@ def main():
         args = (s.pos, s.nrm, s.prob, s.pixel, m.pos, m.nrm)
         est = StocsEstimator(*args, build_index=True)
         orc = pyoracle.Oracle(*args, build_index=True)
+        if exact:
+            est.set_option("exact_ties", 1)
         seed = int(rng.integers(1, 1 << 30))
         nb = int(rng.integers(20, 80))
         r = orc.run(seed, nb, 200)
@@ -119,13 +125,16 @@ def main():
         Tg, Pg, lg, bg = est.get_pose_candidates()
         ok &= Tg.shape == To.shape and np.array_equal(To, Tg) and np.array_equal(Po, Pg) and np.array_equal(bo, bg)
         lcp, idx, pose = est.compute_best_transform()
+        if exact:
+            f, ch = est.last_tie_counts()
+            ties_flagged += f; ties_changed += ch
         dl = abs(lcp - r.best_lcp)
         ok &= dl <= 1e-5
         if len(To):
             lo = orc.lcp_batch(To, nthreads=8)
             dd = np.abs(est.get_pose_candidates()[2] - lo)
             over = np.nonzero(dd > 1e-5)[0]
-            if len(over) and all(is_distance_tie(est, orc, m, To[c]) for c in over):
+            if len(over) and not exact and all(is_distance_tie(est, orc, m, To[c]) for c in over):
                 n_ties += len(over)            # (Q11: two scene points at the same f32 distance, the kd-tree's visiting order picks the other one)
                 dd[over] = 0.0
             dmax = float(dd.max())
@@ -164,7 +173,7 @@ def main():
         est.close()
         if (k + 1) % 25 == 0:
             print("... %d workloads, %d mismatches" % (k + 1, bad), file=sys.stderr, flush=True)
-    print(json.dumps({"workloads": n, "batched_trials_checked": n_batch_trials, "instance_mode": instance, "instance_bases": n_inst_bases, "mismatches": bad, "exact_distance_ties_q11": n_ties, "total_quads": int(sum(x[4] for x in stats)), "total_candidates": int(sum(x[5] for x in stats)),
+    print(json.dumps({"workloads": n, "batched_trials_checked": n_batch_trials, "instance_mode": instance, "instance_bases": n_inst_bases, "mismatches": bad, "exact_distance_ties_q11": n_ties, "exact_ties": exact, "ties_flagged": ties_flagged, "ties_changed": ties_changed, "total_quads": int(sum(x[4] for x in stats)), "total_candidates": int(sum(x[5] for x in stats)),
                       "max_abs_lcp_diff": max(x[6] for x in stats)}))
 
 
