@@ -310,6 +310,8 @@ int stocs_icp_point_to_plane(const float* src_pos3, int nsrc, const float* tgt_p
  *   than epsilon from every scene point cannot add to the score and is skipped after one look-up in a distance field of
  *   the scene.  0 = off, 1 (default) = on once the field pays (1e9 candidates x model points scored against the scene so
  *   far: the field costs ~0.25 ms per scene and takes ~6 % off a launch), 2 = from the first call.  Same scores, bitwise.
+ * "lcp_cull_unit": the points per bounding sphere of that test: 16 (default) = every 64-point step is tested as four 16-point
+ *   sub-patches and the wavefront walks only the live ones, four to a step; 64 = whole steps.  Same scores, bitwise.
  * "lcp_cull_after": that threshold of "lcp_cull" = 1 in MILLIONS of point queries (candidates x model points scored against
  *   the current scene); default 1000, 0 = from the first call.  One trial of a 640x480 frame is 1-40 million: a caller that
  *   scores a single trial per frame never fills the field, a trial batch (stocs_run_trials) or a stream of candidate batches
@@ -343,6 +345,10 @@ int stocs_get_cull_state(stocs_ctx* ctx, float* patches4, int32_t* perm, int* n_
  * which the scoring kernels walk the model -- perm[slot] = model index, 64 consecutive slots = one compact surface patch --
  * and the bounding sphere of every patch (centre x, y, z in the CENTRED model frame, radius), ceil(nM / 64) of them. */
 int stocs_model_patch_order(const float* model_pos3, int nM, int32_t* perm, float* patches4);
+/* The unit of that test at "lcp_cull_unit" = 16, on the host likewise: the same perm (every 64-slot patch above is the union of four
+ * 16-slot runs) and the bounding sphere of every run of 16 consecutive slots (centre x, y, z in the centred frame, radius),
+ * ceil(nM / 16) of them. */
+int stocs_model_subpatches(const float* model_pos3, int nM, int32_t* perm, float* spheres4);
 /* The reference-order kd-tree of the "exact_ties" option on the host, for tests: builds the tree over n points pos3 as the reference
  * builds it (64 points per leaf, depth 32, widest axis split at the box midpoint, the same in-place partition) and answers nq
  * radius queries q3 with the query function the device runs: idx[i] = the reference's doQueryRestrictedClosestIndex(q3[i], sqdist),

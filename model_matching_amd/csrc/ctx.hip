@@ -344,32 +344,24 @@ static int load_scene(stocs_ctx* c, const float* sp, const float* sn, const floa
     return rc;
 }
 
-// Order of the centred model for the scan kernels and the bounding sphere of every 64-point step (host only: no device involved;
-// stocs_model_patch_order exposes it to the CPU tests).  mpos: centred positions, munit: unit-cube positions (Morton order only).
-static void model_patch_order(const std::vector<V3>& mpos, const std::vector<V3>& munit, std::vector<int32_t>& perm, std::vector<float4>& patch, float* r_ref) {
+// Order of the centred model for the scan kernels, the bounding sphere of every 64-point step and of every 16-point sub-patch (host
+// only: no device involved; stocs_model_patch_order / stocs_model_subpatches expose them to the CPU tests).  mpos: centred
+// positions, munit: unit-cube positions (Morton order only).
+static void model_patch_order(const std::vector<V3>& mpos, const std::vector<V3>& munit, std::vector<int32_t>& perm, std::vector<float4>& patch,
+                              std::vector<float4>& sub, float* r_ref) {
     const int nM = (int)mpos.size();
     // Order of the centred model for the LCP kernel: 64 consecutive points = one step of a wavefront = one compact surface patch
     // (spatially coherent look-ups, and a small bounding sphere for the patch test).  Median splits along the longest axis with
-    // the left part a multiple of 64 points: every leaf is one step, neighbouring leaves are neighbouring patches.
+    // the left part a multiple of `unit` points: every leaf is one step, neighbouring leaves are neighbouring patches.
     // (Rounds 1-2 used the Morton order of the unit-cube coordinates: patches of 25 mm radius in the median on the 5 000-point
     // model against 19 mm here; STOCS_MODEL_ORDER=morton keeps it selectable for the A/B.)
-    perm.resize(nM);
-    std::iota(perm.begin(), perm.end(), 0);
-    if (getenv("STOCS_MODEL_ORDER") && !strcmp(getenv("STOCS_MODEL_ORDER"), "morton")) {
-        std::vector<uint32_t> code(nM);
-        for (int i = 0; i < nM; ++i) {
-            const V3 u = munit[i];
-            auto q10 = [](float v) { int k = (int)(v * 1024.0f); return (uint32_t)(k < 0 ? 0 : (k > 1023 ? 1023 : k)); };
-            code[i] = (part1by2(q10(u.z)) << 2) | (part1by2(q10(u.y)) << 1) | part1by2(q10(u.x));
-        }
-        std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return code[a] < code[b]; });
-    } else {
+    auto split = [&](int lo, int hi, int unit) {
         struct Range { int lo, hi; };
-        std::vector<Range> todo(1, Range{0, nM});
+        std::vector<Range> todo(1, Range{lo, hi});
         while (!todo.empty()) {
             const Range r = todo.back(); todo.pop_back();
             const int n = r.hi - r.lo;
-            if (n <= 64) continue;
+            if (n <= unit) continue;
             float mn[3] = {1e30f, 1e30f, 1e30f}, mx[3] = {-1e30f, -1e30f, -1e30f};
             for (int k = r.lo; k < r.hi; ++k) {
                 const V3 q = mpos[perm[k]];
@@ -378,52 +370,93 @@ static void model_patch_order(const std::vector<V3>& mpos, const std::vector<V3>
             }
             int ax = 0;
             for (int a = 1; a < 3; ++a) if (mx[a] - mn[a] > mx[ax] - mn[ax]) ax = a;
-            const int leaves = (n + 63) / 64, nl = (leaves / 2) * 64;   // >= 64, < n
+            const int leaves = (n + unit - 1) / unit, nl = (leaves / 2) * unit;   // >= unit, < n
             auto coord = [&](int id) { const V3 q = mpos[id]; return ax == 0 ? q.x : (ax == 1 ? q.y : q.z); };
             std::stable_sort(perm.begin() + r.lo, perm.begin() + r.hi, [&](int a, int b) { return coord(a) < coord(b); });
             todo.push_back(Range{r.lo + nl, r.hi});
             todo.push_back(Range{r.lo, r.lo + nl});
         }
-    }
-    // bounding sphere per 64-point step (double arithmetic; centre = a few steps of Ritter's iteration towards the farthest point,
+    };
+    // bounding sphere of the slots [lo, hi) (double arithmetic; centre = a few steps of Ritter's iteration towards the farthest point,
     // radius = the exact maximum distance from that centre, rounded up)
+    auto sphere = [&](int lo, int hi) {
+        double ctr[3] = {0, 0, 0};
+        for (int k = lo; k < hi; ++k) { const V3 q = mpos[perm[k]]; ctr[0] += q.x; ctr[1] += q.y; ctr[2] += q.z; }
+        for (int a = 0; a < 3; ++a) ctr[a] /= (double)(hi - lo);
+        auto farthest = [&](double* d_out) {
+            int best = lo; double bd = -1;
+            for (int k = lo; k < hi; ++k) {
+                const V3 q = mpos[perm[k]];
+                const double dx = q.x - ctr[0], dy = q.y - ctr[1], dz = q.z - ctr[2], d = dx * dx + dy * dy + dz * dz;
+                if (d > bd) { bd = d; best = k; }
+            }
+            *d_out = sqrt(bd);
+            return best;
+        };
+        double rad = 0;
+        for (int it = 0; it < 64; ++it) {
+            const int f = farthest(&rad);
+            const V3 q = mpos[perm[f]];
+            const double step = 0.5 / (double)(it + 2);
+            ctr[0] += (q.x - ctr[0]) * step; ctr[1] += (q.y - ctr[1]) * step; ctr[2] += (q.z - ctr[2]) * step;
+        }
+        const float cf[3] = {(float)ctr[0], (float)ctr[1], (float)ctr[2]};
+        ctr[0] = cf[0]; ctr[1] = cf[1]; ctr[2] = cf[2];   // the radius belongs to the centre as stored
+        (void)farthest(&rad);
+        return make_float4(cf[0], cf[1], cf[2], (float)(rad * (1.0 + 1e-6) + 1e-7));
+    };
+    perm.resize(nM);
+    std::iota(perm.begin(), perm.end(), 0);
+    const bool morton = getenv("STOCS_MODEL_ORDER") && !strcmp(getenv("STOCS_MODEL_ORDER"), "morton");
+    if (morton) {
+        std::vector<uint32_t> code(nM);
+        for (int i = 0; i < nM; ++i) {
+            const V3 u = munit[i];
+            auto q10 = [](float v) { int k = (int)(v * 1024.0f); return (uint32_t)(k < 0 ? 0 : (k > 1023 ? 1023 : k)); };
+            code[i] = (part1by2(q10(u.z)) << 2) | (part1by2(q10(u.y)) << 1) | part1by2(q10(u.x));
+        }
+        std::stable_sort(perm.begin(), perm.end(), [&](int a, int b) { return code[a] < code[b]; });
+    } else {
+        split(0, nM, 64);
+    }
     const int n_patch = (nM + 63) / 64;
     patch.assign((size_t)std::max(n_patch, 1), make_float4(0.f, 0.f, 0.f, 0.f));
-    {
-        std::vector<float> radii;
-        for (int s = 0; s < n_patch; ++s) {
-            const int lo = 64 * s, hi = std::min(nM, lo + 64);
-            double ctr[3] = {0, 0, 0};
-            for (int k = lo; k < hi; ++k) { const V3 q = mpos[perm[k]]; ctr[0] += q.x; ctr[1] += q.y; ctr[2] += q.z; }
-            for (int a = 0; a < 3; ++a) ctr[a] /= (double)(hi - lo);
-            auto farthest = [&](double* d_out) {
-                int best = lo; double bd = -1;
-                for (int k = lo; k < hi; ++k) {
-                    const V3 q = mpos[perm[k]];
-                    const double dx = q.x - ctr[0], dy = q.y - ctr[1], dz = q.z - ctr[2], d = dx * dx + dy * dy + dz * dz;
-                    if (d > bd) { bd = d; best = k; }
-                }
-                *d_out = sqrt(bd);
-                return best;
-            };
-            double rad = 0;
-            for (int it = 0; it < 64; ++it) {
-                const int f = farthest(&rad);
-                const V3 q = mpos[perm[f]];
-                const double step = 0.5 / (double)(it + 2);
-                ctr[0] += (q.x - ctr[0]) * step; ctr[1] += (q.y - ctr[1]) * step; ctr[2] += (q.z - ctr[2]) * step;
-            }
-            const float cf[3] = {(float)ctr[0], (float)ctr[1], (float)ctr[2]};
-            ctr[0] = cf[0]; ctr[1] = cf[1]; ctr[2] = cf[2];   // the radius belongs to the centre as stored
-            (void)farthest(&rad);
-            const float rf = (float)(rad * (1.0 + 1e-6) + 1e-7);
-            patch[s] = make_float4(cf[0], cf[1], cf[2], rf);
-            radii.push_back(rf);
-        }
-        std::sort(radii.begin(), radii.end());
-        *r_ref = radii.empty() ? 0.0f : radii[(size_t)((radii.size() - 1) * 0.8)];
+    std::vector<float> radii;
+    for (int s = 0; s < n_patch; ++s) {
+        patch[s] = sphere(64 * s, std::min(nM, 64 * s + 64));
+        radii.push_back(patch[s].w);
     }
+    std::sort(radii.begin(), radii.end());
+    *r_ref = radii.empty() ? 0.0f : radii[(size_t)((radii.size() - 1) * 0.8)];
+    // Each 64-point step split once more, down to four 16-point runs (the unit of the kernel's patch test, lcp_cull_unit = 16): the
+    // step keeps its points (and the sphere above), only their order inside it changes.  One sphere per 16 slots; the runs of the
+    // last step that lie wholly beyond the model are padded with NaN spheres, which the test never rules out.
+    if (!morton)
+        for (int s = 0; s < n_patch; ++s) split(64 * s, std::min(nM, 64 * s + 64), 16);
+    sub.assign((size_t)std::max(n_patch, 1) * 4, make_float4(NAN, NAN, NAN, 0.f));
+    for (int q = 0; q < (nM + 15) / 16; ++q) sub[q] = sphere(16 * q, std::min(nM, 16 * q + 16));
+}
 
+// the model order and spheres of a model as stocs_ctx_create computes them, without a context (CPU tests)
+static void model_patch_order_host(const float* model_pos3, int nM, std::vector<int32_t>& perm, std::vector<float4>& patch, std::vector<float4>& sub) {
+    // centroid_shift and the unit cube exactly as stocs_ctx_create does them (stocs.cpp:943-964, pairCreationFunctor.h:96-132)
+    std::vector<V3> mpos(nM), munit(nM);
+    V3 cm = mk3(0, 0, 0);
+    for (int i = 0; i < nM; ++i) { mpos[i] = mk3(model_pos3[3 * i], model_pos3[3 * i + 1], model_pos3[3 * i + 2]); cm = cm + mpos[i]; }
+    cm = cm / (float)nM;
+    const float big = std::numeric_limits<float>::max() / 2;
+    V3 bmn = mk3(big, big, big), bmx = mk3(-big, -big, -big);
+    for (int i = 0; i < nM; ++i) {
+        mpos[i] = mpos[i] - cm;
+        const V3 q = mpos[i];
+        if (q.x < bmn.x) bmn.x = q.x; if (q.y < bmn.y) bmn.y = q.y; if (q.z < bmn.z) bmn.z = q.z;
+        if (q.x > bmx.x) bmx.x = q.x; if (q.y > bmx.y) bmx.y = q.y; if (q.z > bmx.z) bmx.z = q.z;
+    }
+    const V3 gcenter = bmn + ((bmx - bmn) / 2.0f), ext = bmx - bmn;
+    const float ratio = (float)std::max((double)ext.z + 0.001, std::max((double)ext.y + 0.001, (double)ext.x + 0.001));
+    for (int i = 0; i < nM; ++i) munit[i] = (mpos[i] - gcenter) / ratio + mk3(0.5f, 0.5f, 0.5f);
+    float r_ref = 0.0f;
+    model_patch_order(mpos, munit, perm, patch, sub, &r_ref);
 }
 
 }  // namespace stocs
@@ -504,10 +537,11 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
     c->d_cdf = NULL; c->cdf_bytes = 0; c->cdf_n = 0; c->prior_epoch = 1; c->cdf_epoch = 0;
     memset(&c->grid, 0, sizeof(c->grid));
     c->d_spos = c->d_snrmw = c->d_mpos = c->d_mnrm = c->d_munit = c->d_mpos_raw = c->d_mpos_s = c->d_mnrm_s = NULL;
-    c->d_spix = NULL; c->d_mperm = NULL; c->d_mpatch = NULL; c->d_scene_mem = NULL; c->scene_cap = 0;
+    c->d_spix = NULL; c->d_mperm = NULL; c->d_mpatch = NULL; c->d_msub = NULL; c->d_scene_mem = NULL; c->scene_cap = 0;
     c->patch_r_ref = 0.0f; c->scene_scored = 0; c->scene_work = 0.0;
     c->lcp_group = getenv("STOCS_LCP_GROUP") ? atoi(getenv("STOCS_LCP_GROUP")) : 4;
     c->lcp_cull = getenv("STOCS_LCP_CULL") ? atoi(getenv("STOCS_LCP_CULL")) : 1;
+    c->lcp_cull_unit = 16;
     c->lcp_cull_after = 1.0e9; c->prev_scene_warm = false; c->cull_pending = false; c->ev_cull = NULL;
     c->stream = NULL; c->own_stream = NULL; c->aux_stream = NULL;
     if (hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess || hipStreamCreateWithFlags(&c->aux_stream, hipStreamNonBlocking) != hipSuccess ||
@@ -564,8 +598,8 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
         for (int i = 0; i < nM; ++i) c->h_munit[i] = (c->h_mpos[i] - c->gcenter) / c->ratio + half;
     }
 
-    std::vector<float4> patch;
-    model_patch_order(c->h_mpos, c->h_munit, c->h_mperm, patch, &c->patch_r_ref);
+    std::vector<float4> patch, sub;
+    model_patch_order(c->h_mpos, c->h_munit, c->h_mperm, patch, sub, &c->patch_r_ref);
     const int n_patch = (nM + 63) / 64;
 
     int rc = STOCS_OK;
@@ -590,6 +624,7 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
         if (!rc) rc = upload(&c->d_mnrm_s, bs.data(), bs.size());
         if (!rc) rc = upload(&c->d_mperm, c->h_mperm.data(), c->h_mperm.size());
         if (!rc) rc = upload(&c->d_mpatch, patch.data(), patch.size());
+        if (!rc) rc = upload(&c->d_msub, sub.data(), sub.size());
     }
     if (!rc) rc = load_scene(c, sp, sn, sprob, spix, nS);
     if (!rc && build_index) rc = build_ppf_index(c);
@@ -600,26 +635,19 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
 
 int stocs_model_patch_order(const float* model_pos3, int nM, int32_t* perm, float* patches4) {
     if (!model_pos3 || nM <= 0 || !perm || !patches4) return STOCS_ERR_INVALID;
-    // centroid_shift and the unit cube exactly as stocs_ctx_create does them (stocs.cpp:943-964, pairCreationFunctor.h:96-132)
-    std::vector<V3> mpos(nM), munit(nM);
-    V3 cm = mk3(0, 0, 0);
-    for (int i = 0; i < nM; ++i) { mpos[i] = mk3(model_pos3[3 * i], model_pos3[3 * i + 1], model_pos3[3 * i + 2]); cm = cm + mpos[i]; }
-    cm = cm / (float)nM;
-    const float big = std::numeric_limits<float>::max() / 2;
-    V3 bmn = mk3(big, big, big), bmx = mk3(-big, -big, -big);
-    for (int i = 0; i < nM; ++i) {
-        mpos[i] = mpos[i] - cm;
-        const V3 q = mpos[i];
-        if (q.x < bmn.x) bmn.x = q.x; if (q.y < bmn.y) bmn.y = q.y; if (q.z < bmn.z) bmn.z = q.z;
-        if (q.x > bmx.x) bmx.x = q.x; if (q.y > bmx.y) bmx.y = q.y; if (q.z > bmx.z) bmx.z = q.z;
-    }
-    const V3 gcenter = bmn + ((bmx - bmn) / 2.0f), ext = bmx - bmn;
-    const float ratio = (float)std::max((double)ext.z + 0.001, std::max((double)ext.y + 0.001, (double)ext.x + 0.001));
-    for (int i = 0; i < nM; ++i) munit[i] = (mpos[i] - gcenter) / ratio + mk3(0.5f, 0.5f, 0.5f);
-    std::vector<int32_t> pm; std::vector<float4> patch; float r_ref = 0.0f;
-    model_patch_order(mpos, munit, pm, patch, &r_ref);
+    std::vector<int32_t> pm; std::vector<float4> patch, sub;
+    model_patch_order_host(model_pos3, nM, pm, patch, sub);
     for (int i = 0; i < nM; ++i) perm[i] = pm[i];
     for (int s = 0; s < (nM + 63) / 64; ++s) { patches4[4 * s] = patch[s].x; patches4[4 * s + 1] = patch[s].y; patches4[4 * s + 2] = patch[s].z; patches4[4 * s + 3] = patch[s].w; }
+    return STOCS_OK;
+}
+
+int stocs_model_subpatches(const float* model_pos3, int nM, int32_t* perm, float* spheres4) {
+    if (!model_pos3 || nM <= 0 || !perm || !spheres4) return STOCS_ERR_INVALID;
+    std::vector<int32_t> pm; std::vector<float4> patch, sub;
+    model_patch_order_host(model_pos3, nM, pm, patch, sub);
+    for (int i = 0; i < nM; ++i) perm[i] = pm[i];
+    for (int q = 0; q < (nM + 15) / 16; ++q) { spheres4[4 * q] = sub[q].x; spheres4[4 * q + 1] = sub[q].y; spheres4[4 * q + 2] = sub[q].z; spheres4[4 * q + 3] = sub[q].w; }
     return STOCS_OK;
 }
 
@@ -628,7 +656,7 @@ int stocs_ctx_destroy(stocs_ctx* c) {
     DeviceGuard dev_guard(c->device);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void* ptrs[] = {c->d_scene_mem, c->d_mpos, c->d_mnrm, c->d_munit, c->d_mpos_raw, c->d_mpos_s,
-                    c->d_mnrm_s, c->d_mperm, c->d_mpatch, c->index.d_bucket_start,
+                    c->d_mnrm_s, c->d_mperm, c->d_mpatch, c->d_msub, c->index.d_bucket_start,
                     c->index.d_pairs, c->index.d_exists, c->d_scratch, c->d_best, c->d_cand, c->d_order, c->d_cdf, c->d_kd};
     stocs_internal_free_congruent(c);
     stocs_internal_free_instance(c);

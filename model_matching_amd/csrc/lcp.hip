@@ -14,8 +14,9 @@
 // d^2 <= epsilon^2, then the 30-degree normal test as an exact threshold on the dot product, and an
 // integer (2^32 fixed-point) sum of the class-probability weights.  No atomics: results are run-to-run
 // deterministic and do not depend on the batch or on how the points are split over wavefronts.
-// The queue-fed kernel (lcp_coopq_kernel, the automatic choice) first rules out whole 64-point steps whose bounding
-// sphere is out of reach of the scene (patch test, one look-up in a distance field of the scene), collects the
+// The queue-fed kernel (lcp_coopq_kernel, the automatic choice) first rules out the 16-point sub-patches whose bounding
+// sphere is out of reach of the scene (patch test, one look-up in a distance field of the scene) and walks the live ones
+// four to a step, collects the
 // queries that survive the sub-cell mask in a per-wave LDS ring and verifies them 16 at a time, four lanes per query
 // with two entries of a 128-byte list line each.
 //
@@ -61,6 +62,7 @@ struct LcpArgs {
     uint32_t id_offset;         // atomic max on this word (integer max: order independent), id = id_offset + candidate
     // patch test (lcp_coopq_kernel): bounding sphere per 64-point step + the scene's distance field (SceneGrid::d_dist); patch == NULL: off
     const float4* patch;
+    const float4* sub;    // bounding sphere per 16-point sub-patch (ctx.hip), the unit of that test in the CU = 16 kernels
     const float* dist;
     float gox, goy, goz, g, inv_g, cap;
     int gnx, gny, gnz;
@@ -450,7 +452,8 @@ __device__ __forceinline__ bool lcp_patch_dead(const LcpArgs& a, const float4 sp
 // -- the unit this kernel sits on -- takes four lane addresses per clock whatever their width, so a four-entry list read by four lanes x two
 // entries costs twice the addresses it needs.  The pending queries are ordered tiny lists first; a trip is a two-lane trip while 32 tiny
 // queries are left.
-template <bool DETAIL, int UNR, bool SORTQ = false, int PIPE = 4, bool IDX = true, int WPB = 4, int FLAT = 0, bool SPLIT = false, bool TILE = false, bool EARLY = false, int GL = 8, int FIRST = 1, bool NOSENT = false, bool NEAR = false, bool TINY = false>
+// CU (lcp_cull_unit): points per bounding sphere of the patch test -- 64, whole steps; 16, sub-patches, the live ones packed four to a step.
+template <bool DETAIL, int UNR, bool SORTQ = false, int PIPE = 4, bool IDX = true, int WPB = 4, int FLAT = 0, bool SPLIT = false, bool TILE = false, bool EARLY = false, int GL = 8, int FIRST = 1, bool NOSENT = false, bool NEAR = false, bool TINY = false, int CU = 64>
 __global__ __launch_bounds__(64 * WPB, 8) void lcp_coopq_kernel(LcpArgs a, const float* __restrict__ T16, float* __restrict__ out,
                                                         int n, int32_t* __restrict__ hit_out, uint8_t* __restrict__ cnt_out) {
     __shared__ float4 qt[WPB][128];     // qx, qy, qz, bits(list offset)
@@ -745,6 +748,69 @@ __global__ __launch_bounds__(64 * WPB, 8) void lcp_coopq_kernel(LcpArgs a, const
             buf ^= 1;
         }
         if (cand < 0) return;
+    } else if (CU == 16) {
+    // The wavefront's steps as 16-point sub-patches, four per step, 64 at a time: every lane tests the sphere of one sub-patch
+    // (a.sub), and the live ones join a per-wave ring in LDS (ballot + mbcnt compaction, as the query queue).  Each 64-lane step
+    // takes the next four entries of the ring -- lane l walks point l & 15 of the (l >> 4)-th -- and a window is tested only when
+    // fewer than four are left, so only the wavefront's last step can be partial; its empty lanes read the NaN padding behind
+    // the model.  (The selection costs a few vector instructions and one LDS read per step: picking the four with scalar
+    // find-first-set costs more scalar issue slots than the skipped steps save.)  The model point of the next step is requested
+    // one step ahead, as below.
+    __shared__ uint16_t live_q[WPB][128];   // global sub-patch indices, a ring (at most 3 + 64 entries pending)
+    const int nsteps = (a.M + 63) >> 6;
+    const int wfirst = SPLIT ? w : 0, nw = SPLIT ? WPB : 1;
+    // this wavefront's sub-patches: k -> step wfirst + (k >> 2) * nw, quarter k & 3 (wave-uniform: the walk's loops branch on scalars)
+    const int nsub = __builtin_amdgcn_readfirstlane(4 * ((nsteps - wfirst + nw - 1) / nw));
+    const float snorm = a.patch ? lcp_linear_norm_bound(t0, t1, t2, t4, t5, t6, t8, t9, t10) : 0.0f;
+    int qh = 0, qtl = 0;   // ring head and tail
+    for (int s0 = 0;; s0 += 64) {
+        {   // the window s0 .. s0 + 63 (wave-uniform)
+            const int kl = s0 + lane, q = 4 * (wfirst + (kl >> 2) * nw) + (kl & 3);
+            const bool in = kl < nsub && (q << 4) < a.M;   // (the quarters of the last step that lie wholly beyond the model: none)
+            bool live = in;
+            if (a.patch && live && !STOCS_ABLATE(a, 64))
+                live = !lcp_patch_dead(a, a.sub[q], snorm, t0, t1, t2, t4, t5, t6, t8, t9, t10, t12, t13, t14);
+            const unsigned long long mask = __ballot(live);
+            if (live) live_q[w][(qtl + __popcll(mask & ((1ull << lane) - 1ull))) & 127] = (uint16_t)q;
+            qtl += __popcll(mask);
+            if (DETAIL && a.patch) {   // the skipped sub-patches' points: no neighbour, not counted
+                unsigned long long dead = __ballot(in && !live);
+                while (dead) {
+                    const int j = __builtin_ctzll(dead);
+                    dead &= dead - 1ull;
+                    const int id = ((4 * (wfirst + ((s0 + j) >> 2) * nw) + ((s0 + j) & 3)) << 4) + lane;
+                    if (lane < 16 && id < a.M) {
+                        const int orig = a.mperm[id];
+                        hit_out[(size_t)cand * a.M + orig] = -1;
+                        cnt_out[(size_t)cand * a.M + orig] = 0;
+                    }
+                }
+            }
+            __builtin_amdgcn_wave_barrier();
+        }
+        const bool last = s0 + 64 >= nsub;
+        // the steps: four queued sub-patches each, fewer only in the last step of the last window (its other lanes: the NaN padding)
+        const int g = lane >> 4;
+        auto slot = [&](int t) { return g < t ? ((int)live_q[w][(qh + g) & 127] << 4) + (lane & 15) : (nsteps << 6) + lane; };
+        int t = min(qtl - qh, 4);
+        if (t == 4 || (last && t > 0)) {
+            // (the sorted positions are padded to whole steps and one step beyond: no bounds checks on these loads)
+            int i = slot(t);
+            float4 p_next = a.mpos[i];
+            for (;;) {
+                const int ic = i;
+                const float4 p = p_next;
+                qh += t;
+                t = min(qtl - qh, 4);
+                const bool more = t == 4 || (last && t > 0);
+                i = more ? slot(t) : ic;   // behind the last step its own point is requested once more: no branch around the load
+                p_next = a.mpos[i];
+                step(ic, p);
+                if (!more) break;
+            }
+        }
+        if (last) break;
+    }
     } else {
     // The wavefront's steps, 64 at a time: every lane tests the patch of one step (a.patch), the ballot is the list of the
     // steps that have to be walked; the model point of the NEXT such step is requested one step ahead (takes one of the
@@ -996,7 +1062,7 @@ int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d
     // patch test: its distance field costs one pass over the scene points (0.24 ms at Cm) and takes ~6 % off a launch, so it is filled
     // once the scene has seen 1e9 point queries (three steps of the metric batch; ~25 trials of one frame) -- a caller that scores one
     // trial per frame never pays for it.  The scores do not depend on it
-    a.patch = NULL; a.dist = NULL;
+    a.patch = NULL; a.sub = NULL; a.dist = NULL;
     a.gox = a.goy = a.goz = 0.f; a.g = a.inv_g = a.cap = 0.f; a.gnx = a.gny = a.gnz = 0;
     c->scene_scored++;
     c->scene_work += (double)n * (double)c->nM;
@@ -1020,7 +1086,7 @@ int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d
         int rc = fill_cull_field(c);
         if (rc) return rc;
         if (c->cull_pending) { STOCS_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_cull, 0)); c->cull_pending = false; }   // filled at stocs_ctx_set_scene, on the auxiliary stream
-        a.patch = c->d_mpatch; a.dist = c->grid.d_dist;
+        a.patch = c->d_mpatch; a.sub = c->d_msub; a.dist = c->grid.d_dist;
         a.gox = c->grid.cg_ox; a.goy = c->grid.cg_oy; a.goz = c->grid.cg_oz; a.g = c->grid.cg_g; a.inv_g = c->grid.cg_inv_g; a.cap = c->grid.cg_cap;
         a.gnx = c->grid.cg_nx; a.gny = c->grid.cg_ny; a.gnz = c->grid.cg_nz;
     }
@@ -1078,14 +1144,23 @@ int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d
     if (dense && !(variant == 0 || variant == 16 || dense_only)) variant = 39;
     if (!dense && dense_only) variant = 24;
 #define STOCS_LCP_LAUNCH(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(blocks), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted)
+    // the unit of the patch test (lcp_cull_unit); without the test the walk of whole steps (CU = 64) is the one to run
+    const bool cu16 = a.patch && c->lcp_cull_unit == 16;
     if (d_hit) {   // per-point detail (parity tests)
-        if (dense && variant == 39) STOCS_LCP_LAUNCH(lcp_coopq_kernel<true, 1, true, 4, false, 4, 0, false, false, true>);
+        if (dense && variant == 39) {
+            if (cu16) STOCS_LCP_LAUNCH(lcp_coopq_kernel<true, 1, true, 4, false, 4, 0, false, false, true, 8, 1, false, false, false, 16>);
+            else STOCS_LCP_LAUNCH(lcp_coopq_kernel<true, 1, true, 4, false, 4, 0, false, false, true>);
+        }
         else if (dense) STOCS_LCP_LAUNCH(lcp_coop_kernel<true, 2, true, true, false>);
         else if (variant == 0) STOCS_LCP_LAUNCH(lcp_kernel<true, true>);
 #ifdef STOCS_TOOLS_BUILD
         else if (!(variant >= 20 && variant <= 28)) STOCS_LCP_LAUNCH(lcp_coop_kernel<true, 1, true, false, true>);
 #endif
-        else if (a.has_nearest) STOCS_LCP_LAUNCH(lcp_coopq_kernel<true, 1, true, 4, true, 4, 0, false, false, false, 8, 1, false, true>);   // pruned lists on a grid finer than epsilon
+        else if (a.has_nearest) {   // pruned lists on a grid finer than epsilon
+            if (cu16) STOCS_LCP_LAUNCH(lcp_coopq_kernel<true, 1, true, 4, true, 4, 0, false, false, false, 8, 1, false, true, false, 16>);
+            else STOCS_LCP_LAUNCH(lcp_coopq_kernel<true, 1, true, 4, true, 4, 0, false, false, false, 8, 1, false, true>);
+        }
+        else if (cu16) STOCS_LCP_LAUNCH(lcp_coopq_kernel<true, 1, true, 4, true, 4, 0, false, false, false, 8, 1, false, false, false, 16>);
         else STOCS_LCP_LAUNCH(lcp_coopq_kernel<true, 1, true, 4, true>);
     } else if (dense) {
         switch (variant) {
@@ -1105,7 +1180,8 @@ int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d
                 else if (c->lcp_group == 2) hipLaunchKernelGGL((lcp_coopq_kernel<false, 1, true, 1, false, 4, 0, true, false, true, 2>), dim3(n), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted);
                 else
 #endif
-                hipLaunchKernelGGL((lcp_coopq_kernel<false, 1, true, 1, false, 4, 0, true, false, true, 4>), dim3(n), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted);
+                if (cu16) hipLaunchKernelGGL((lcp_coopq_kernel<false, 1, true, 1, false, 4, 0, true, false, true, 4, 1, false, false, false, 16>), dim3(n), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted);
+                else hipLaunchKernelGGL((lcp_coopq_kernel<false, 1, true, 1, false, 4, 0, true, false, true, 4>), dim3(n), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted);
                 break;
 #ifdef STOCS_TOOLS_BUILD
             case 41: hipLaunchKernelGGL((lcp_coopq_kernel<false, 2, true, 4, false, 4, 0, true, false, true>), dim3(n), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted); break;   // 39, two lines per trip after the first
@@ -1178,7 +1254,9 @@ int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d
 #ifdef STOCS_TOOLS_BUILD
                         if (getenv("STOCS_LCP_TINY")) { if (a.has_nearest) STOCS_LCP_Q(true, 1, 4, 1, 2, true, true, true); else STOCS_LCP_Q(true, 1, 4, 1, 2, true, false, true); break; }
 #endif
-                        if (a.has_nearest) STOCS_LCP_Q(true, 1, 4, 1, 2, true, true); else STOCS_LCP_Q(true, 1, 4, 1, 2, true);
+                        if (a.has_nearest) { if (cu16) STOCS_LCP_Q(true, 1, 4, 1, 2, true, true, false, 16); else STOCS_LCP_Q(true, 1, 4, 1, 2, true, true); }
+                        else if (cu16) STOCS_LCP_Q(true, 1, 4, 1, 2, true, false, false, 16);
+                        else STOCS_LCP_Q(true, 1, 4, 1, 2, true);
                         break;
                 }
 #undef STOCS_LCP_Q
@@ -1369,6 +1447,8 @@ int stocs_set_option(stocs_ctx* c, const char* key, int value) {
     // 0: every 64-point step is walked; 1 (default): steps whose bounding sphere is out of reach of the scene are skipped once the scene's
     // distance field pays (1e9 point queries against the scene so far); 2: from the first call (same scores in every case)
     if (!strcmp(key, "lcp_cull") && value >= 0 && value <= 2) { c->lcp_cull = value; return STOCS_OK; }
+    // points per bounding sphere of that test: 16 (default: sub-patches, the live ones packed four to a step) or 64 (whole steps)
+    if (!strcmp(key, "lcp_cull_unit") && (value == 16 || value == 64)) { c->lcp_cull_unit = value; return STOCS_OK; }
     // the threshold of lcp_cull = 1, in MILLIONS of point queries (candidates x model points) scored against the current scene:
     // default 1000 (= 1e9: the field costs ~0.25 ms at 20 000 scene points and takes ~6 % off a launch); 0 = from the first call
     if (!strcmp(key, "lcp_cull_after") && value >= 0) { c->lcp_cull_after = (double)value * 1.0e6; return STOCS_OK; }

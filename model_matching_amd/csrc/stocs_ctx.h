@@ -232,8 +232,10 @@ struct stocs_ctx {
     float4* d_mnrm_s;
     int32_t* d_mperm;
     float4* d_mpatch;  // per 64-point step of the sorted model: bounding sphere (centre xyz, radius) of its points (patch test, lcp.hip)
+    float4* d_msub;    // per 16-point sub-patch (four per step, NaN spheres behind the model): the unit of the patch test at lcp_cull_unit = 16
     float patch_r_ref; // the radius most patches stay below (sizes the cap of the scene's distance field)
     int lcp_cull;      // 1: the scan kernels skip the 64-point steps whose bounding sphere is farther than epsilon from every scene point
+    int lcp_cull_unit; // points per sphere of that test: 16 (default; live sub-patches are packed four to a step) or 64 (whole steps)
     int lcp_group;     // lanes per queued query in the verify trips: 4 (default, two list entries per lane) or 8 (one entry per lane)
     double lcp_cull_after;   // lcp_cull == 1: the distance field is filled once this many point queries were scored against the scene (default 1e9)
     bool prev_scene_warm;    // the scene before this one crossed that threshold: a stream of frames will again, so the field of a new frame

@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Census (CPU only, scipy kd-tree; no library code): which 64-point steps of the sorted model a sphere test against the scene could rule out, for the Morton and the median-split order.  usage: python tools/cull_census.py [Cm|C5] [candidates]"""
+"""Census (CPU only, scipy kd-tree; no library code): which 64-point steps of the sorted model a sphere test against the scene could rule out, for the Morton and the median-split order;
+then, per cull unit (64 / 32 / 16 points, median splits inside the 64-point leaves), the points and the wave-steps a pose still walks under the field bound when the
+live units of each of a candidate's four wavefronts are packed into full 64-lane steps (lcp_cull_unit).  usage: python tools/cull_census.py [Cm|C5] [candidates]"""
 import numpy as np, sys
 sys.path.insert(0, __import__('os').path.dirname(__import__('os').path.dirname(__import__('os').path.abspath(__file__))))
 import os as _os; _os.environ.setdefault("STOCS_PIN_BLAS", "1")   # harness side: one BLAS thread under the cgroup CPU quota; the library import itself has no side effects
@@ -72,3 +74,31 @@ for oname,order in (('morton',morton(mp0)),('kd',kdorder(mp0))):
         dl=np.zeros(npz); dl[ok]=Dlb[ci3[ok,0],ci3[ok,1],ci3[ok,2]]
         tot+=npz; empty+=(per==0).sum(); cull_exact+=(dcen>rad+1.001*eps).sum(); cull_grid+=(dl>rad+1.001*eps).sum()
     print(' steps',tot,'empty',empty/tot,'cull exact-dist',cull_exact/tot,'cull grid',cull_grid/tot)
+
+# per cull unit: the kd order's 64-point leaves split further (median splits), one sphere per run, the field bound above; a candidate's
+# four wavefronts own the 64-point steps w, w + 4, ...; their live runs are packed into full 64-lane steps
+mp=mp0[kdorder(mp0)]; M=len(mp); nst=(M+63)//64
+rng=np.random.default_rng(0)
+sel=rng.choice(k,ncand,replace=False)
+for unit in (64,32,16):
+    order=np.concatenate([j*64+kdorder(mp[j*64:min(M,j*64+64)],unit) for j in range(nst)])
+    mu=mp[order]; nu=(M+unit-1)//unit
+    cen=np.zeros((nu,3)); rad=np.zeros(nu)
+    for j in range(nu):
+        pts=mu[j*unit:(j+1)*unit]; cc=pts.mean(0)
+        for it in range(50):
+            d=np.linalg.norm(pts-cc,axis=1); f=pts[np.argmax(d)]; cc=cc+(f-cc)*0.05
+        cen[j]=cc; rad[j]=np.linalg.norm(pts-cc,axis=1).max()
+    walked=0; wsteps=0
+    per=64//unit; owner=(np.arange(nu)//per)%4
+    for ci in sel:
+        Mx=T[ci].reshape(4,4).T.astype(np.float64)
+        cc=cen@Mx[:3,:3].T+Mx[:3,3]
+        ci3=np.floor((cc-org)/g).astype(int)
+        ok=np.all((ci3>=0)&(ci3<dims),axis=1)
+        dl=np.zeros(nu); dl[ok]=Dlb[ci3[ok,0],ci3[ok,1],ci3[ok,2]]
+        live=~(dl>rad+1.001*eps)
+        walked+=np.minimum(unit,M-np.arange(nu)*unit)[live].sum()
+        wsteps+=sum(int(np.ceil(live[owner==w].sum()/per)) for w in range(4))
+    print(name,'unit',unit,'median radius mm %.1f'%(np.median(rad)*1000),'points walked per pose %.0f'%(walked/len(sel)),
+          'wave-steps per pose %.1f of %d'%(wsteps/len(sel),nst))
