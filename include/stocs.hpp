@@ -512,8 +512,43 @@ public:
     // the winner of the last run_trials (camera frame), NULL when no trial found a pose; owned by the estimator
     PoseCandidate* get_best_trial_pose() const { return trial_best_.get(); }
 
+    // clustering::point_to_plane_icp (reference pose_clustering.cpp:123-140) for every hypothesis at once, on the estimator's own scene
+    // and model (stocs_refine_poses): the camera-frame hypotheses go to the centred frame, are refined against every scene point and
+    // rescored.  Returns new candidates (camera-frame refined transform, rescored lcp, the input's base_index) in input order, owned by
+    // the estimator until the next call; empty on error (the text is on stdout, as compute_best_transform reports errors).
+    std::vector<PoseCandidate*> refine_pose_candidates(const std::vector<PoseCandidate*>& hypotheses, int max_iterations = 5,
+                                                       float max_correspondence_distance = 0.035f) {
+        refined_store_.clear();
+        std::vector<PoseCandidate*> out;
+        const int n = (int)hypotheses.size();
+        float cs[3], cm[3];
+        stocs_get_centroids(ctx_, cs, cm);
+        std::vector<float> T((size_t)n * 16), P((size_t)n * 16), l((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            // camera -> centred: same linear part, t = (t_camera - c_scene) + R c_model (in double, rounded once)
+            const float* src = hypotheses[(size_t)i]->transform.data();
+            float* dst = &T[(size_t)i * 16];
+            std::memcpy(dst, src, 64);
+            for (int r = 0; r < 3; ++r)
+                dst[12 + r] = (float)(((double)src[12 + r] - (double)cs[r]) +
+                                      (((double)src[r] * (double)cm[0] + (double)src[4 + r] * (double)cm[1]) + (double)src[8 + r] * (double)cm[2]));
+        }
+        if (n > 0 && stocs_refine_poses(ctx_, T.data(), n, NULL, 0, max_iterations, max_correspondence_distance, NULL, P.data(), l.data(), NULL, NULL) != STOCS_OK) {
+            std::cout << "refine_pose_candidates failed: " << stocs_last_error() << std::endl;
+            return out;
+        }
+        for (int i = 0; i < n; ++i) {
+            MatrixType m;
+            std::memcpy(m.data(), &P[(size_t)i * 16], 64);
+            refined_store_.emplace_back(new PoseCandidate(m, l[(size_t)i], (float)hypotheses[(size_t)i]->base_index));
+            out.push_back(refined_store_.back().get());
+        }
+        return out;
+    }
+
 protected:
     std::unique_ptr<PoseCandidate> trial_best_;
+    std::vector<std::unique_ptr<PoseCandidate> > refined_store_;   // results of the last refine_pose_candidates
     void reset_members(const std::string& dbg, int w, int h, float dist, int tr, int rot, float edge_thr, float class_thr) {
         ctx_ = NULL; best_lcp = 0; best_index = -1; seed_ = 0; attempt_ = 0; batched_ = false; fetched_ = false; n_batched_ = 0;
         la_n_ = 0; la_first_ = 0; la_seed_ = 0; la_cursor_ = 0; la_in_ctx_ = false; la_congruent_done_ = false; la_mode_ = 0; la_nvalid_ = 0;

@@ -290,6 +290,24 @@ int stocs_icp_point_to_plane(const float* src_pos3, int nsrc, const float* tgt_p
                              int max_iterations, float max_correspondence_distance, int device, float* T16_out,
                              int* n_correspondences);
 
+/* ---- pose refinement on the context: clustering::point_to_plane_icp (pose_clustering.cpp:123-140: PCL ICP with normals, 5
+ * iterations, 3.5 cm; scene segment aligned onto the model) applied to n hypotheses in one call and rescored.  T16_centred_in:
+ * n column-major 4x4 in the centred frame of stocs_score_transforms (centred model -> centred scene).  Source: the context's
+ * centred scene points, restricted to src_idx[0 .. n_src) when src_idx != NULL (e.g. stocs_get_segment's indices in instance
+ * mode; NULL: every scene point); target: the centred model with its unit normals.  Per hypothesis, exactly max_iterations
+ * iterations of: nearest model point within max_correspondence_distance (lowest model index on equal distance), linearised
+ * point-to-plane least squares in double, U <- [Rz Ry Rx | t] U; a hypothesis with < 6 correspondences or a singular system
+ * stops and keeps its U.  Out (any pointer may be NULL): T16_centred_out = T U^-1, pose16_camera_out its camera form (as
+ * stocs_get_candidates forms it), lcp_out = bitwise what stocs_score_transforms returns for T16_centred_out, n_corr_out the
+ * last evaluated iteration's correspondences, iterations_out the updates applied.  Results are bitwise independent of the
+ * batch a hypothesis shares.  n == 0: no-op; max_iterations == 0: inputs returned unchanged and scored; negative sizes or
+ * iterations, a distance <= 0 or not finite, an index outside the scene: STOCS_ERR_INVALID; no scene: STOCS_ERR_STATE.
+ * The model's correspondence grid is built at the first call and kept per distance.  One synchronisation per call.
+ * Parity with PCL unpinned (pinned against oracle/ingest_oracle.py::icp). ---- */
+int stocs_refine_poses(stocs_ctx* ctx, const float* T16_centred_in, int n, const int32_t* src_idx, int n_src, int max_iterations,
+                       float max_correspondence_distance, float* T16_centred_out, float* pose16_camera_out, float* lcp_out,
+                       int32_t* n_corr_out, int32_t* iterations_out);
+
 /* ---- tuning knobs (never change results beyond float summation order).
  * "lcp_variant": 99 = automatic (default): the scan fed from a per-wavefront LDS queue of the queries that have a list -- over
  *   index-ordered lists at cell edge epsilon (24, sparse scenes), over centre-sorted lists with triangle-inequality early exit

@@ -13,6 +13,8 @@
 //   stocs_single <scene_path> <object_name> [--repo DIR] [--intrinsics fx,cx,fy,cy] [--depth-scale S] [--voxel V] ...
 //   stocs_single --clouds <scene.stcl> <model.stcl> [--edge edge.u8] ...       (flat clouds, e.g. the synthetic workloads)
 // common options: --seed N --bases 100 --max-sets 200 --out FILE --dbg DIR --cluster 1 --exact-ties 1
+// --refine N (with --cluster 1): N point-to-plane iterations on every clustered hypothesis (clustering::point_to_plane_icp,
+// pose_clustering.cpp:123-140, batched: stocs_refine_poses); the best refined pose goes to <out>.refined in the same format.
 // The reference edits its per-data-set constants in the source (README.md:42-66); here they are options with the
 // reference's YCB values as defaults.
 #include <chrono>
@@ -67,7 +69,7 @@ int main(int argc, char** argv) {
     const std::string a1 = argv[clouds ? 2 : 1], a2 = argv[clouds ? 3 : 2];
     if (const char* e = getenv("STOCS_REPO_PATH")) repo_path = e;
     std::string edge_path, out_path, dbg_dir;
-    int do_cluster = 0, n_trials = 0, exact_ties = 0;
+    int do_cluster = 0, n_trials = 0, exact_ties = 0, n_refine = 0;
     uint64_t seed = 1;
     for (int i = clouds ? 4 : 3; i + 1 < argc; i += 2) {
         const std::string k = argv[i], v = argv[i + 1];
@@ -78,6 +80,7 @@ int main(int argc, char** argv) {
         else if (k == "--max-sets") maximum_congruent_sets = atoi(v.c_str());
         else if (k == "--dbg") dbg_dir = v;
         else if (k == "--cluster") do_cluster = atoi(v.c_str());
+        else if (k == "--refine") n_refine = atoi(v.c_str());   // iterations of the refinement of the clustered hypotheses (0: off)
         else if (k == "--trials") n_trials = atoi(v.c_str());   // N independent runs (seeds seed, seed + 1, ...) in one set of GPU launches; the best one is written
         else if (k == "--exact-ties") exact_ties = atoi(v.c_str());   // 1: the reference kd-tree's answer on exact distance ties (set_exact_ties)
         else if (k == "--repo") repo_path = v;
@@ -88,6 +91,8 @@ int main(int argc, char** argv) {
             if (sscanf(v.c_str(), "%f,%f,%f,%f", &cam_intrinsics[0], &cam_intrinsics[1], &cam_intrinsics[2], &cam_intrinsics[3]) != 4) { std::cerr << "--intrinsics fx,cx,fy,cy" << std::endl; return -1; }
         } else { std::cerr << "unknown option " << k << std::endl; return -1; }
     }
+
+    if (n_refine < 0 || (n_refine > 0 && (!do_cluster || n_trials > 0))) { std::cerr << "--refine N needs N >= 0, --cluster 1 and no --trials" << std::endl; return -1; }
 
     std::unique_ptr<stocs::stocs_estimator> est;
     try {
@@ -208,6 +213,22 @@ int main(int argc, char** argv) {
             clustering::greedy_clustering(all, 0.8f, stocs_ptr.get_best_score(), 10, 0.02f, 15.0f, VectorType(0, 0, 0), kept);
             std::cout << "clustered hypotheses: " << kept.size() << std::endl;
             for (size_t i = 0; i < kept.size(); ++i) std::cout << "  cluster " << i << ": base " << kept[i]->base_index << " lcp " << kept[i]->lcp << std::endl;
+            if (n_refine > 0) {
+                const std::vector<PoseCandidate*> ref = stocs_ptr.refine_pose_candidates(kept, n_refine);
+                PoseCandidate* rb = NULL;
+                for (size_t i = 0; i < ref.size(); ++i) {
+                    std::cout << "  refined " << i << ": base " << ref[i]->base_index << " lcp " << kept[i]->lcp << " -> " << ref[i]->lcp << std::endl;
+                    if (!rb || ref[i]->lcp > rb->lcp) rb = ref[i];   // first maximum
+                }
+                if (rb) {
+                    std::ofstream rf(out_path + ".refined", std::ofstream::out);
+                    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) rf << rb->transform(r, c) << (r == 2 && c == 3 ? "" : " ");
+                    rf << std::endl;
+                    std::cout << "refined pose:";
+                    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) { char b[32]; snprintf(b, sizeof(b), " %.9g", (double)rb->transform(r, c)); std::cout << b; }
+                    std::cout << std::endl;
+                }
+            }
         }
     } else {
         std::cout << "no pose found" << std::endl;

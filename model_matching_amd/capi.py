@@ -102,6 +102,7 @@ SIGNATURES = {
     "stocs_preprocess_model": (C.c_int, [_fp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, _fp, _fp, C.c_int, _intp]),
     "stocs_trim": (C.c_int, []),
     "stocs_icp_point_to_plane": (C.c_int, [_fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_float, C.c_int, _fp, _intp]),
+    "stocs_refine_poses": (C.c_int, [_vp, _fp, C.c_int, _ip, C.c_int, C.c_int, C.c_float, _fp, _fp, _fp, _ip, _ip]),
     "stocs_device_alloc_count": (C.c_int64, []),
     "stocs_debug_stream_audit_selftest": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     "stocs_debug_streams_overlap": (C.c_int, [_vp]),

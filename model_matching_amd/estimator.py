@@ -224,6 +224,20 @@ class StocsEstimator:
         capi.check(self.L.stocs_score_transforms(self.h, pT, n, out.ctypes.data_as(capi._fp)))
         return out
 
+    def refine_poses(self, T16, max_iterations=5, max_correspondence_distance=0.035, src_idx=None):
+        """Point-to-plane refinement of n centred-frame hypotheses on this context (stocs_refine_poses; the reference's
+        clustering::point_to_plane_icp per hypothesis) -> (T16_refined (n, 16), pose16_camera (n, 16), lcp (n,), n_corr (n,),
+        iterations (n,))."""
+        T, pT = capi.f32(T16)
+        n = T.size // 16
+        idx, pidx = (None, None) if src_idx is None else capi.i32(src_idx)
+        To = np.zeros((n, 16), np.float32); Po = np.zeros((n, 16), np.float32); lcp = np.zeros(n, np.float32)
+        nc = np.zeros(n, np.int32); it = np.zeros(n, np.int32)
+        capi.check(self.L.stocs_refine_poses(self.h, pT, n, pidx, 0 if idx is None else len(idx), max_iterations, max_correspondence_distance,
+                                             To.ctypes.data_as(capi._fp), Po.ctypes.data_as(capi._fp), lcp.ctypes.data_as(capi._fp),
+                                             nc.ctypes.data_as(capi._ip), it.ctypes.data_as(capi._ip)))
+        return To, Po, lcp, nc, it
+
     def lcp_detail(self, T16):
         T, pT = capi.f32(T16)
         hit = np.zeros(self.nM, np.int32); counted = np.zeros(self.nM, np.uint8)
