@@ -279,6 +279,18 @@ public:
         scene_ = scene;
         create_context(device);
     }
+    // not in the reference: one object of a frame ingested for several (load_frame_scenes), with the object's preloaded PPF index.
+    // log: where the estimator's own lines go (std::cout when NULL) -- several estimators on host threads each keep theirs apart.
+    stocs_estimator(const ModelCloud& model, PPFMapType& ppf_map_preloaded, const SceneCloud& scene, std::string debug_location, int image_width,
+                    int image_height, float distance_threshold, int ppf_tr_discretization, int ppf_rot_discretization, float edge_threshold,
+                    float class_threshold, int device = -1, std::ostream* log = NULL) {
+        reset_members(debug_location, image_width, image_height, distance_threshold, ppf_tr_discretization, ppf_rot_discretization, edge_threshold, class_threshold);
+        if (log) log_ = log;
+        model_ = model;
+        ppf_location_ = ppf_map_preloaded.location;
+        scene_ = scene;
+        create_context(device);
+    }
     ~stocs_estimator() { stocs_ctx_destroy(ctx_); }
     stocs_estimator(const stocs_estimator&) = delete;
     stocs_estimator& operator=(const stocs_estimator&) = delete;
@@ -287,7 +299,7 @@ public:
     void load_object_info(std::string model_location, PPFMapType& ppf_map_preloaded) {
         read_ply(model_location, &model_, true);
         ppf_location_ = ppf_map_preloaded.location;
-        std::cout << "|M| = " << model_.size() << ",  |map(M)| = " << ppf_map_preloaded.size() << std::endl;
+        *log_ << "|M| = " << model_.size() << ",  |map(M)| = " << ppf_map_preloaded.size() << std::endl;
     }
     // reference stocs.hpp:69-78 / stocs.cpp:99-131 -> rgbd::load_rgbd_data_sampled (rgbd.cpp:179-281), on the GPU.  The
     // rgb image only colours the reference's debug clouds and is not read.
@@ -398,19 +410,19 @@ public:
     void compute_best_transform() {
         if (batched_) {   // candidates live on the device (make_transforms): score + arg-max there, one round trip
             float pose[16];
-            std::cout << "Transforms to verify: " << n_batched_ << std::endl;   // stocs.cpp:985
+            *log_ << "Transforms to verify: " << n_batched_ << std::endl;   // stocs.cpp:985
             if (stocs_verify_all(ctx_, &best_lcp, &best_index, pose) != STOCS_OK) {
                 // the reference's error convention: text on stdout, "no pose" state, no exception from the hot path
-                std::cout << "compute_best_transform failed: " << stocs_last_error() << std::endl;
+                *log_ << "compute_best_transform failed: " << stocs_last_error() << std::endl;
                 best_lcp = 0;
                 best_index = -1;
             }
-            std::cout << "best index: " << best_index << ", maximum score: " << best_lcp << std::endl;   // :1003
+            *log_ << "best index: " << best_index << ", maximum score: " << best_lcp << std::endl;   // :1003
             fetched_ = false;
             return;
         }
         const int n = (int)all_transforms.size();
-        std::cout << "Transforms to verify: " << n << std::endl;
+        *log_ << "Transforms to verify: " << n << std::endl;
         std::vector<float> T((size_t)n * 16), l((size_t)n);
         for (int i = 0; i < n; ++i) std::memcpy(&T[(size_t)i * 16], all_transforms[(size_t)i].data(), 64);
         Scalar max_score = 0;
@@ -423,7 +435,7 @@ public:
         }
         best_lcp = max_score;
         best_index = index;
-        std::cout << "best index: " << best_index << ", maximum score: " << best_lcp << std::endl;
+        *log_ << "best index: " << best_index << ", maximum score: " << best_lcp << std::endl;
     }
 
     // reference stocs.hpp:109-113: run by the constructor there; here both are part of stocs_ctx_create (sequential f32
@@ -534,7 +546,7 @@ public:
                                       (((double)src[r] * (double)cm[0] + (double)src[4 + r] * (double)cm[1]) + (double)src[8 + r] * (double)cm[2]));
         }
         if (n > 0 && stocs_refine_poses(ctx_, T.data(), n, NULL, 0, max_iterations, max_correspondence_distance, NULL, P.data(), l.data(), NULL, NULL) != STOCS_OK) {
-            std::cout << "refine_pose_candidates failed: " << stocs_last_error() << std::endl;
+            *log_ << "refine_pose_candidates failed: " << stocs_last_error() << std::endl;
             return out;
         }
         for (int i = 0; i < n; ++i) {
@@ -550,7 +562,7 @@ protected:
     std::unique_ptr<PoseCandidate> trial_best_;
     std::vector<std::unique_ptr<PoseCandidate> > refined_store_;   // results of the last refine_pose_candidates
     void reset_members(const std::string& dbg, int w, int h, float dist, int tr, int rot, float edge_thr, float class_thr) {
-        ctx_ = NULL; best_lcp = 0; best_index = -1; seed_ = 0; attempt_ = 0; batched_ = false; fetched_ = false; n_batched_ = 0;
+        ctx_ = NULL; log_ = &std::cout; best_lcp = 0; best_index = -1; seed_ = 0; attempt_ = 0; batched_ = false; fetched_ = false; n_batched_ = 0;
         la_n_ = 0; la_first_ = 0; la_seed_ = 0; la_cursor_ = 0; la_in_ctx_ = false; la_congruent_done_ = false; la_mode_ = 0; la_nvalid_ = 0;
         debug_location = dbg; image_width = w; image_height = h; distance_threshold = dist; ppf_tr_discretization = tr;
         ppf_rot_discretization = rot; edge_threshold = edge_thr; class_threshold = class_thr;
@@ -590,7 +602,7 @@ protected:
             throw std::runtime_error(msg);
         }
         if (!scene_.edge_map.empty()) stocs_set_edge_map(ctx_, scene_.edge_map.data());
-        std::cout << "|S|: " << scene_.size() << std::endl;   // stocs.cpp:970
+        *log_ << "|S|: " << scene_.size() << std::endl;   // stocs.cpp:970
     }
     // One attempt of the reference's one-per-call loop.  Class mode: the attempts do not depend on each other (every base
     // starts from the prior, stocs.cpp:372-381; attempt a is seeded by (seed, a)), so the facade draws a block of them in one
@@ -696,6 +708,7 @@ protected:
     }
 
     stocs_ctx* ctx_;
+    std::ostream* log_;
     stocs_params prm_;
     ModelCloud model_;
     SceneCloud scene_;
@@ -725,6 +738,59 @@ protected:
     int la_first_, la_n_, la_cursor_, la_mode_, la_nvalid_;
     bool la_in_ctx_, la_congruent_done_;
 };
+
+// Not in the reference (its driver runs once per object): every object of one frame from one ingest (stocs_ingest_scene_multi).
+// class_probability_maps holds class_thresholds.size() images of image_height x image_width, object after object; edge (may be NULL)
+// is shared by all of them.  Scene k is what the estimator's own ingest makes of (depth, map k, class_thresholds[k]), bit for bit.
+inline std::vector<SceneCloud> load_frame_scenes(const uint16_t* depth, const uint16_t* class_probability_maps, const std::vector<float>& class_thresholds,
+                                                 const uint8_t* edge, const std::vector<float>& camera_intrinsics, int image_width, int image_height,
+                                                 float read_depth_scale, float voxel_size, int device = -1) {
+    if (camera_intrinsics.size() < 4) throw std::runtime_error("camera_intrinsics must hold {fx, cx, fy, cy}");
+    stocs_camera cam;
+    cam.fx = camera_intrinsics[0]; cam.cx = camera_intrinsics[1]; cam.fy = camera_intrinsics[2]; cam.cy = camera_intrinsics[3];
+    cam.depth_scale = read_depth_scale; cam.width = image_width; cam.height = image_height;
+    cam.normal_method = STOCS_NORMALS_DEPTH_GRADIENT;   // as stocs_estimator::ingest
+    const int n_obj = (int)class_thresholds.size();
+    std::vector<int32_t> off((size_t)n_obj + 1, 0);
+    std::vector<float> pos, nrm, prob;
+    std::vector<int32_t> pix;
+    int cap = image_width * image_height;   // one frame's worth of points; grown once when the objects need more
+    for (int pass = 0; pass < 2; ++pass) {
+        pos.resize((size_t)cap * 3); nrm.resize((size_t)cap * 3); prob.resize((size_t)cap); pix.resize((size_t)cap * 2);
+        const int rc = stocs_ingest_scene_multi(&cam, depth, n_obj, class_probability_maps, class_thresholds.data(), voxel_size, device, pos.data(), nrm.data(),
+                                                prob.data(), pix.data(), cap, off.data());
+        if (rc == STOCS_ERR_CAPACITY && pass == 0) { cap = off[(size_t)n_obj]; continue; }
+        if (rc != STOCS_OK) throw std::runtime_error(std::string("stocs_ingest_scene_multi: ") + stocs_last_error());
+        break;
+    }
+    std::vector<SceneCloud> out((size_t)n_obj);
+    for (int k = 0; k < n_obj; ++k) {
+        SceneCloud& sc = out[(size_t)k];
+        const size_t a = (size_t)off[(size_t)k], b = (size_t)off[(size_t)k + 1];
+        sc.pos.assign(pos.begin() + 3 * a, pos.begin() + 3 * b); sc.nrm.assign(nrm.begin() + 3 * a, nrm.begin() + 3 * b);
+        sc.class_probability.assign(prob.begin() + a, prob.begin() + b); sc.pixel.assign(pix.begin() + 2 * a, pix.begin() + 2 * b);
+        if (edge) sc.edge_map.assign(edge, edge + (size_t)image_width * image_height);
+    }
+    return out;
+}
+// the same from the reference's files: depth.png, one probability map per object, edge.png when it exists (as load_scene_info)
+inline std::vector<SceneCloud> load_frame_scenes(std::string depth_location, const std::vector<std::string>& class_probability_map_locations,
+                                                 const std::vector<float>& class_thresholds, std::string edge_probability_map_location,
+                                                 const std::vector<float>& camera_intrinsics, int image_width, int image_height, float read_depth_scale,
+                                                 float voxel_size, int device = -1) {
+    if (class_probability_map_locations.size() != class_thresholds.size()) throw std::runtime_error("load_frame_scenes: one class threshold per probability map");
+    std::vector<uint16_t> depth, maps, one;
+    std::vector<uint8_t> edge;
+    read_image(depth_location, 1, 16, image_width, image_height, &depth);
+    for (size_t k = 0; k < class_probability_map_locations.size(); ++k) {
+        read_image(class_probability_map_locations[k], 1, 16, image_width, image_height, &one);
+        maps.insert(maps.end(), one.begin(), one.end());
+    }
+    const bool has_edge = file_exists(edge_probability_map_location);
+    if (has_edge) read_image(edge_probability_map_location, 1, 8, image_width, image_height, &edge);
+    return load_frame_scenes(depth.data(), maps.data(), class_thresholds, has_edge ? edge.data() : NULL, camera_intrinsics, image_width, image_height,
+                             read_depth_scale, voxel_size, device);
+}
 
 // reference stocs.hpp:182-191 / stocs.cpp:28-84: raw model PLY -> normals (radius), flipped, voxel grid, scale -> model_search
 // PLY + the PPF index of the sampled cloud, both on the GPU.  The index is built from the cloud as the estimator will read

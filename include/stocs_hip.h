@@ -264,12 +264,25 @@ typedef struct stocs_camera {
 int stocs_ingest_scene(const stocs_camera* cam, const uint16_t* depth, const uint16_t* class_prob, float voxel_size,
                        float class_threshold, int device, float* pos3, float* nrm3, float* prob, int32_t* pixel2,
                        int cap, int* n_out);
+/* Several objects of one frame: one depth image, n_objects class-probability images (n_objects*height*width uint16, object-major)
+ * and n_objects class thresholds -> n_objects scene clouds, concatenated in object order; object k owns points
+ * offsets[k] .. offsets[k+1]-1 (offsets: n_objects+1 entries, offsets[0] = 0).  The stages that never read a class-probability
+ * image (back-projection, normals, voxel grid, outlier removal; rgbd.cpp:227-237) run once for the frame; per object, the cloud is
+ * bitwise what stocs_ingest_scene(cam, depth, class_probs + k*height*width, voxel_size, class_thresholds[k], ...) returns.  An
+ * empty cloud is not an error (offsets[k] == offsets[k+1]).  cap counts points over all objects: when offsets[n_objects] > cap
+ * the call returns STOCS_ERR_CAPACITY with offsets filled and writes no point.  1 <= n_objects <= STOCS_MAX_FRAME_OBJECTS; NULL
+ * images / thresholds / offsets, a non-finite threshold or voxel_size <= 0: STOCS_ERR_INVALID.  Same cached workspace and pinned
+ * block as stocs_ingest_scene (the block grows to (2 + 2*n_objects) bytes per pixel in, 36 bytes per point out). */
+#define STOCS_MAX_FRAME_OBJECTS 64
+int stocs_ingest_scene_multi(const stocs_camera* cam, const uint16_t* depth, int n_objects, const uint16_t* class_probs,
+                             const float* class_thresholds, float voxel_size, int device, float* pos3, float* nrm3, float* prob,
+                             int32_t* pixel2, int cap, int32_t* offsets);
 /* cloud part of stocs::pre_process_model (stocs.cpp:43-60): raw vertices -> radius normals pointing away
  * from the model origin -> voxel grid (positions and normals averaged per leaf) -> scale */
 int stocs_preprocess_model(const float* raw_pos3, int n_raw, float normal_radius, float voxel_size, float model_scale,
                            int device, float* pos3, float* nrm3, int cap, int* n_out);
-/* stocs_ingest_scene / stocs_preprocess_model keep their device workspace cached per calling thread and device
- * (a stream of frames does no hipMalloc / hipFree after the first one), and stocs_ingest_scene a pinned host block per calling thread
+/* stocs_ingest_scene(_multi) / stocs_preprocess_model keep their device workspace cached per calling thread and device
+ * (a stream of frames does no hipMalloc / hipFree after the first one), and stocs_ingest_scene(_multi) a pinned host block per calling thread
  * (40 bytes per pixel: the frame's two images go up and its cloud comes down through it, so the caller's arrays may be ordinary
  * pageable memory at no cost); this gives the calling thread's cache and block back. */
 int stocs_trim(void);

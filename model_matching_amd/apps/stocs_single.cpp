@@ -12,17 +12,23 @@
 //
 //   stocs_single <scene_path> <object_name> [--repo DIR] [--intrinsics fx,cx,fy,cy] [--depth-scale S] [--voxel V] ...
 //   stocs_single --clouds <scene.stcl> <model.stcl> [--edge edge.u8] ...       (flat clouds, e.g. the synthetic workloads)
+//   stocs_single <scene_path> <object_a,object_b,...> [options]   (several objects of the frame: one ingest, one context per object)
 // common options: --seed N --bases 100 --max-sets 200 --out FILE --dbg DIR --cluster 1 --exact-ties 1
 // --refine N (with --cluster 1): N point-to-plane iterations on every clustered hypothesis (clustering::point_to_plane_icp,
 // pose_clustering.cpp:123-140, batched: stocs_refine_poses); the best refined pose goes to <out>.refined in the same format.
 // The reference edits its per-data-set constants in the source (README.md:42-66); here they are options with the
 // reference's YCB values as defaults.
+#include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
 #include <iostream>
+#include <sstream>
 #include <string>
+#include <thread>
+#include <vector>
 
 #include "../../include/pose_clustering.hpp"
 #include "../../include/stocs.hpp"
@@ -59,6 +65,176 @@ static bool read_stcl(const std::string& path, std::vector<float>& pos, std::vec
     return ok;
 }
 
+// everything after the estimator is built (:79-185): one run, or n_trials in one batch; lines to os, the pose to out_path
+static int run_search(stocs::stocs_estimator& stocs_ptr, std::ostream& os, const std::string& out_path, const std::string& dbg_dir, uint64_t seed, int n_trials,
+                      int exact_ties, int do_cluster, int n_refine) {
+    stocs_ptr.set_seed(seed);
+    if (exact_ties) stocs_ptr.set_exact_ties(true);
+
+    if (n_trials > 0) {
+        // BASELINE config 4: N independent StoCS trials -- each the whole loop of run_stocs_estimation (:79-165) with its own seed --
+        // in ONE set of launches (stocs_run_trials); the best pose over the trials is the result
+        std::vector<stocs::stocs_estimator::TrialResult> res;
+        auto t0 = std::chrono::high_resolution_clock::now();
+        const int best = stocs_ptr.run_trials(n_trials, seed, number_of_bases, maximum_congruent_sets, sample_dispersion, &res);
+        auto t1 = std::chrono::high_resolution_clock::now();
+        long long cand = 0;
+        for (size_t t = 0; t < res.size(); ++t) {
+            cand += res[t].n_candidates;
+            os << "trial " << t << ": bases " << res[t].n_bases << " congruent sets " << res[t].n_congruent_sets << " candidates " << res[t].n_candidates
+               << " best lcp " << res[t].best_lcp << std::endl;
+        }
+        const long long us = (long long)std::chrono::duration_cast<micro>(t1 - t0).count();
+        char tl[256];
+        snprintf(tl, sizeof(tl), "trials: n=%d best_trial=%d best_lcp=%.9g candidates=%lld total_microseconds=%lld", n_trials, best,
+                 best >= 0 ? (double)res[(size_t)best].best_lcp : 0.0, cand, us);
+        if (PoseCandidate* bp = stocs_ptr.get_best_trial_pose()) {
+            std::ofstream o(out_path, std::ofstream::out);
+            for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) o << bp->transform(r, c) << (r == 2 && c == 3 ? "" : " ");
+            o << std::endl;
+            os << "pose:";
+            for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) { char b[32]; snprintf(b, sizeof(b), " %.9g", (double)bp->transform(r, c)); os << b; }
+            os << std::endl;
+        } else {
+            os << "no pose found" << std::endl;
+        }
+        os << tl << std::endl;
+        return 0;
+    }
+
+    // Step 1: sample n bases on the scene (:79-105)
+    auto start = std::chrono::high_resolution_clock::now();
+    const int n_bases = stocs_ptr.sample_bases(number_of_bases, sample_dispersion);
+    auto finish = std::chrono::high_resolution_clock::now();
+    os << "Sampled " << n_bases << " bases in " << std::chrono::duration_cast<micro>(finish - start).count() << " microseconds\n";
+    auto total_time = std::chrono::duration_cast<micro>(finish - start).count();
+
+    // Step 2 + 3: congruent sets and rigid transforms (:107-153)
+    start = std::chrono::high_resolution_clock::now();
+    const long long total_congruent_set_found = stocs_ptr.find_congruent_sets_all();
+    const int n_candidates = stocs_ptr.make_transforms(maximum_congruent_sets);
+    finish = std::chrono::high_resolution_clock::now();
+    os << "found " << total_congruent_set_found << " congruent sets in " << std::chrono::duration_cast<micro>(finish - start).count() << " microseconds\n";
+    total_time += std::chrono::duration_cast<micro>(finish - start).count();
+
+    // Step 4: verify all transforms to get the best pose (:155-165)
+    start = std::chrono::high_resolution_clock::now();
+    stocs_ptr.compute_best_transform();
+    finish = std::chrono::high_resolution_clock::now();
+    os << "evaluated transforms in " << std::chrono::duration_cast<micro>(finish - start).count() << " microseconds\n";
+    total_time += std::chrono::duration_cast<micro>(finish - start).count();
+
+    PoseCandidate* best_pose = stocs_ptr.get_best_pose();
+    char line[256];
+    snprintf(line, sizeof(line), "summary: bases=%d congruent_sets=%lld candidates=%d best_lcp=%.9g best_index=%d total_microseconds=%lld", n_bases,
+             total_congruent_set_found, n_candidates, (double)stocs_ptr.get_best_score(), stocs_ptr.get_best_index(), (long long)total_time);
+    if (!dbg_dir.empty()) stocs_ptr.visualize_best_pose();   // :167
+    if (best_pose != NULL) {  // :171-180
+        std::ofstream out_file_ptr;
+        out_file_ptr.open(out_path, std::ofstream::out);
+        out_file_ptr << best_pose->transform(0, 0) << " " << best_pose->transform(0, 1) << " " << best_pose->transform(0, 2) << " " << best_pose->transform(0, 3) << " "
+                     << best_pose->transform(1, 0) << " " << best_pose->transform(1, 1) << " " << best_pose->transform(1, 2) << " " << best_pose->transform(1, 3) << " "
+                     << best_pose->transform(2, 0) << " " << best_pose->transform(2, 1) << " " << best_pose->transform(2, 2) << " " << best_pose->transform(2, 3) << std::endl;
+        out_file_ptr.close();
+        // full-precision copy of the same 12 numbers for tools that compare poses
+        os << "pose:";
+        for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) { char b[32]; snprintf(b, sizeof(b), " %.9g", (double)best_pose->transform(r, c)); os << b; }
+        os << std::endl;
+        if (do_cluster) {  // clustering::greedy_clustering (pose_clustering.cpp:79-121; no caller in the reference): 0.8, best, 10, 2 cm, 15 deg, no symmetry
+            std::vector<PoseCandidate*> all = stocs_ptr.get_pose_candidates(), kept;
+            clustering::greedy_clustering(all, 0.8f, stocs_ptr.get_best_score(), 10, 0.02f, 15.0f, VectorType(0, 0, 0), kept);
+            os << "clustered hypotheses: " << kept.size() << std::endl;
+            for (size_t i = 0; i < kept.size(); ++i) os << "  cluster " << i << ": base " << kept[i]->base_index << " lcp " << kept[i]->lcp << std::endl;
+            if (n_refine > 0) {
+                const std::vector<PoseCandidate*> ref = stocs_ptr.refine_pose_candidates(kept, n_refine);
+                PoseCandidate* rb = NULL;
+                for (size_t i = 0; i < ref.size(); ++i) {
+                    os << "  refined " << i << ": base " << ref[i]->base_index << " lcp " << kept[i]->lcp << " -> " << ref[i]->lcp << std::endl;
+                    if (!rb || ref[i]->lcp > rb->lcp) rb = ref[i];   // first maximum
+                }
+                if (rb) {
+                    std::ofstream rf(out_path + ".refined", std::ofstream::out);
+                    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) rf << rb->transform(r, c) << (r == 2 && c == 3 ? "" : " ");
+                    rf << std::endl;
+                    os << "refined pose:";
+                    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) { char b[32]; snprintf(b, sizeof(b), " %.9g", (double)rb->transform(r, c)); os << b; }
+                    os << std::endl;
+                }
+            }
+        }
+    } else {
+        os << "no pose found" << std::endl;
+    }
+    os << line << std::endl;
+    return 0;
+}
+
+// Several objects of one frame (<object_name> = a,b,c): every model, PPF index and probability map is read before any GPU work (a
+// missing one ends the run, naming the object); the frame is ingested once for all of them (stocs::load_frame_scenes); then each
+// object is searched on its own context, at most kMaxFrameThreads at a time (every context holds its own trial memory).  Each
+// object writes <scene>/best_pose_candidate_<object>.txt and its block of lines, printed in the order given once all are done.
+static const int kMaxFrameThreads = 4;
+
+static int run_frame_objects(const std::string& scene_path, const std::vector<std::string>& objects, uint64_t seed, int n_trials, int exact_ties) {
+    const size_t n = objects.size();
+    std::vector<stocs::ModelCloud> models(n);
+    std::vector<PPFMapType> maps(n);
+    std::vector<std::string> prob_paths(n);
+    std::cout << "############# LOADING OBJECT MAPS ################" << std::endl;
+    for (size_t k = 0; k < n; ++k) {
+        const std::string& obj = objects[k];
+        const std::string model_path = repo_path + "/models/" + obj + "/model_search.ply", map_path = repo_path + "/models/" + obj + "/ppf_map";
+        prob_paths[k] = scene_path + "/probability_maps/" + obj + ".png";
+        if (!stocs::file_exists(prob_paths[k])) { std::cerr << "object " << obj << ": no class probability map " << prob_paths[k] << std::endl; return 1; }
+        if (!stocs::file_exists(model_path)) { std::cerr << "object " << obj << ": no model " << model_path << std::endl; return 1; }
+        rgbd::load_ppf_map(map_path, maps[k]);
+        if (maps[k].location.empty()) { std::cerr << "object " << obj << ": no readable ppf_map " << map_path << std::endl; return 1; }
+        try {
+            stocs::read_ply(model_path, &models[k], true);
+        } catch (const std::exception& e) {
+            std::cerr << "object " << obj << ": " << e.what() << std::endl;
+            return 1;
+        }
+        std::cout << "object " << obj << ": |M| = " << models[k].size() << ",  |map(M)| = " << maps[k].size() << std::endl;
+    }
+    std::cout << "############# LOADING OBJECT COMPLETE ################" << std::endl;
+    std::vector<stocs::SceneCloud> scenes;
+    try {
+        scenes = stocs::load_frame_scenes(scene_path + "/depth.png", prob_paths, std::vector<float>(n, class_threshold), scene_path + "/probability_maps/edge.png",
+                                          cam_intrinsics, image_width, image_height, depth_scale, voxel_size);
+    } catch (const std::exception& e) {
+        std::cerr << e.what() << std::endl;   // no GPU => loud failure, never a CPU fallback
+        return 2;
+    }
+    std::vector<std::ostringstream> blocks(n);
+    std::vector<int> rcs(n, 0);
+    std::atomic<size_t> next(0);
+    auto worker = [&]() {
+        for (size_t k; (k = next.fetch_add(1)) < n;) {
+            std::ostringstream& os = blocks[k];
+            os << "############# RUNNING STOCS for Scene: " << scene_path << ", Object: " << objects[k] << " ##############" << std::endl;
+            try {
+                stocs::stocs_estimator est(models[k], maps[k], scenes[k], std::string(), image_width, image_height, distance_threshold, ppf_tr_discretization,
+                                           ppf_rot_discretization, edge_threshold, class_threshold, -1, &os);
+                rcs[k] = run_search(est, os, scene_path + "/best_pose_candidate_" + objects[k] + ".txt", std::string(), seed, n_trials, exact_ties, 0, 0);
+            } catch (const std::exception& e) {
+                os << "object " << objects[k] << " failed: " << e.what() << std::endl;
+                rcs[k] = 2;
+            }
+        }
+    };
+    std::vector<std::thread> pool;
+    for (size_t t = 0; t < std::min<size_t>(n, kMaxFrameThreads); ++t) pool.emplace_back(worker);
+    for (size_t t = 0; t < pool.size(); ++t) pool[t].join();
+    int rc = 0;
+    for (size_t k = 0; k < n; ++k) {
+        std::cout << blocks[k].str();
+        if (rcs[k] != 0 && rc == 0) rc = rcs[k];
+    }
+    std::cout << std::flush;
+    return rc;
+}
+
 int main(int argc, char** argv) {
     if (argc < 3) {
         std::cout << "Enter scene path and object name as arguments!" << std::endl;   // :190
@@ -93,6 +269,21 @@ int main(int argc, char** argv) {
     }
 
     if (n_refine < 0 || (n_refine > 0 && (!do_cluster || n_trials > 0))) { std::cerr << "--refine N needs N >= 0, --cluster 1 and no --trials" << std::endl; return -1; }
+
+    if (!clouds && a2.find(',') != std::string::npos) {
+        std::vector<std::string> objects;
+        std::stringstream names(a2);
+        for (std::string o; std::getline(names, o, ',');) objects.push_back(o);
+        if (a2.back() == ',') objects.push_back(std::string());
+        for (size_t k = 0; k < objects.size(); ++k) {
+            if (objects[k].empty() || std::count(objects.begin(), objects.end(), objects[k]) > 1) { std::cerr << "object list " << a2 << ": empty or repeated name" << std::endl; return -1; }
+        }
+        if (do_cluster || n_refine || !out_path.empty() || !dbg_dir.empty() || !edge_path.empty()) {
+            std::cerr << "several objects: --cluster, --refine, --out, --dbg and --edge take a single object" << std::endl;
+            return -1;
+        }
+        return run_frame_objects(a1, objects, seed, n_trials, exact_ties);
+    }
 
     std::unique_ptr<stocs::stocs_estimator> est;
     try {
@@ -135,104 +326,5 @@ int main(int argc, char** argv) {
         std::cerr << e.what() << std::endl;  // no GPU => loud failure, never a CPU fallback
         return 2;
     }
-    stocs::stocs_estimator& stocs_ptr = *est;
-    stocs_ptr.set_seed(seed);
-    if (exact_ties) stocs_ptr.set_exact_ties(true);
-
-    if (n_trials > 0) {
-        // BASELINE config 4: N independent StoCS trials -- each the whole loop of run_stocs_estimation (:79-165) with its own seed --
-        // in ONE set of launches (stocs_run_trials); the best pose over the trials is the result
-        std::vector<stocs::stocs_estimator::TrialResult> res;
-        auto t0 = std::chrono::high_resolution_clock::now();
-        const int best = stocs_ptr.run_trials(n_trials, seed, number_of_bases, maximum_congruent_sets, sample_dispersion, &res);
-        auto t1 = std::chrono::high_resolution_clock::now();
-        long long cand = 0;
-        for (size_t t = 0; t < res.size(); ++t) {
-            cand += res[t].n_candidates;
-            std::cout << "trial " << t << ": bases " << res[t].n_bases << " congruent sets " << res[t].n_congruent_sets << " candidates " << res[t].n_candidates
-                      << " best lcp " << res[t].best_lcp << std::endl;
-        }
-        const long long us = (long long)std::chrono::duration_cast<micro>(t1 - t0).count();
-        char tl[256];
-        snprintf(tl, sizeof(tl), "trials: n=%d best_trial=%d best_lcp=%.9g candidates=%lld total_microseconds=%lld", n_trials, best,
-                 best >= 0 ? (double)res[(size_t)best].best_lcp : 0.0, cand, us);
-        if (PoseCandidate* bp = stocs_ptr.get_best_trial_pose()) {
-            std::ofstream o(out_path, std::ofstream::out);
-            for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) o << bp->transform(r, c) << (r == 2 && c == 3 ? "" : " ");
-            o << std::endl;
-            std::cout << "pose:";
-            for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) { char b[32]; snprintf(b, sizeof(b), " %.9g", (double)bp->transform(r, c)); std::cout << b; }
-            std::cout << std::endl;
-        } else {
-            std::cout << "no pose found" << std::endl;
-        }
-        std::cout << tl << std::endl;
-        return 0;
-    }
-
-    // Step 1: sample n bases on the scene (:79-105)
-    auto start = std::chrono::high_resolution_clock::now();
-    const int n_bases = stocs_ptr.sample_bases(number_of_bases, sample_dispersion);
-    auto finish = std::chrono::high_resolution_clock::now();
-    std::cout << "Sampled " << n_bases << " bases in " << std::chrono::duration_cast<micro>(finish - start).count() << " microseconds\n";
-    auto total_time = std::chrono::duration_cast<micro>(finish - start).count();
-
-    // Step 2 + 3: congruent sets and rigid transforms (:107-153)
-    start = std::chrono::high_resolution_clock::now();
-    const long long total_congruent_set_found = stocs_ptr.find_congruent_sets_all();
-    const int n_candidates = stocs_ptr.make_transforms(maximum_congruent_sets);
-    finish = std::chrono::high_resolution_clock::now();
-    std::cout << "found " << total_congruent_set_found << " congruent sets in " << std::chrono::duration_cast<micro>(finish - start).count() << " microseconds\n";
-    total_time += std::chrono::duration_cast<micro>(finish - start).count();
-
-    // Step 4: verify all transforms to get the best pose (:155-165)
-    start = std::chrono::high_resolution_clock::now();
-    stocs_ptr.compute_best_transform();
-    finish = std::chrono::high_resolution_clock::now();
-    std::cout << "evaluated transforms in " << std::chrono::duration_cast<micro>(finish - start).count() << " microseconds\n";
-    total_time += std::chrono::duration_cast<micro>(finish - start).count();
-
-    PoseCandidate* best_pose = stocs_ptr.get_best_pose();
-    char line[256];
-    snprintf(line, sizeof(line), "summary: bases=%d congruent_sets=%lld candidates=%d best_lcp=%.9g best_index=%d total_microseconds=%lld", n_bases,
-             total_congruent_set_found, n_candidates, (double)stocs_ptr.get_best_score(), stocs_ptr.get_best_index(), (long long)total_time);
-    if (!dbg_dir.empty()) stocs_ptr.visualize_best_pose();   // :167
-    if (best_pose != NULL) {  // :171-180
-        std::ofstream out_file_ptr;
-        out_file_ptr.open(out_path, std::ofstream::out);
-        out_file_ptr << best_pose->transform(0, 0) << " " << best_pose->transform(0, 1) << " " << best_pose->transform(0, 2) << " " << best_pose->transform(0, 3) << " "
-                     << best_pose->transform(1, 0) << " " << best_pose->transform(1, 1) << " " << best_pose->transform(1, 2) << " " << best_pose->transform(1, 3) << " "
-                     << best_pose->transform(2, 0) << " " << best_pose->transform(2, 1) << " " << best_pose->transform(2, 2) << " " << best_pose->transform(2, 3) << std::endl;
-        out_file_ptr.close();
-        // full-precision copy of the same 12 numbers for tools that compare poses
-        std::cout << "pose:";
-        for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) { char b[32]; snprintf(b, sizeof(b), " %.9g", (double)best_pose->transform(r, c)); std::cout << b; }
-        std::cout << std::endl;
-        if (do_cluster) {  // clustering::greedy_clustering (pose_clustering.cpp:79-121; no caller in the reference): 0.8, best, 10, 2 cm, 15 deg, no symmetry
-            std::vector<PoseCandidate*> all = stocs_ptr.get_pose_candidates(), kept;
-            clustering::greedy_clustering(all, 0.8f, stocs_ptr.get_best_score(), 10, 0.02f, 15.0f, VectorType(0, 0, 0), kept);
-            std::cout << "clustered hypotheses: " << kept.size() << std::endl;
-            for (size_t i = 0; i < kept.size(); ++i) std::cout << "  cluster " << i << ": base " << kept[i]->base_index << " lcp " << kept[i]->lcp << std::endl;
-            if (n_refine > 0) {
-                const std::vector<PoseCandidate*> ref = stocs_ptr.refine_pose_candidates(kept, n_refine);
-                PoseCandidate* rb = NULL;
-                for (size_t i = 0; i < ref.size(); ++i) {
-                    std::cout << "  refined " << i << ": base " << ref[i]->base_index << " lcp " << kept[i]->lcp << " -> " << ref[i]->lcp << std::endl;
-                    if (!rb || ref[i]->lcp > rb->lcp) rb = ref[i];   // first maximum
-                }
-                if (rb) {
-                    std::ofstream rf(out_path + ".refined", std::ofstream::out);
-                    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) rf << rb->transform(r, c) << (r == 2 && c == 3 ? "" : " ");
-                    rf << std::endl;
-                    std::cout << "refined pose:";
-                    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) { char b[32]; snprintf(b, sizeof(b), " %.9g", (double)rb->transform(r, c)); std::cout << b; }
-                    std::cout << std::endl;
-                }
-            }
-        }
-    } else {
-        std::cout << "no pose found" << std::endl;
-    }
-    std::cout << line << std::endl;
-    return 0;
+    return run_search(*est, std::cout, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine);
 }

@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libstocs_hip.so")
 
 STOCS_OK = 0
+ERR_INVALID, ERR_CAPACITY = -1, -4
 ERR_NAMES = {0: "OK", -1: "INVALID", -2: "NO_DEVICE", -3: "HIP", -4: "CAPACITY", -5: "STATE", -6: "NOMEM"}
 
 
@@ -99,6 +100,8 @@ SIGNATURES = {
     "stocs_allreduce_best": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), _fp, C.c_uint32]),
     "stocs_cluster_poses": (C.c_int, [_fp, _fp, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, _fp, _ip, C.c_int, _intp]),
     "stocs_ingest_scene": (C.c_int, [C.POINTER(Camera), C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.c_float, C.c_float, C.c_int, _fp, _fp, _fp, _ip, C.c_int, _intp]),
+    "stocs_ingest_scene_multi": (C.c_int, [C.POINTER(Camera), C.POINTER(C.c_uint16), C.c_int, C.POINTER(C.c_uint16), _fp, C.c_float, C.c_int, _fp, _fp, _fp, _ip,
+                                           C.c_int, _ip]),
     "stocs_preprocess_model": (C.c_int, [_fp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, _fp, _fp, C.c_int, _intp]),
     "stocs_trim": (C.c_int, []),
     "stocs_icp_point_to_plane": (C.c_int, [_fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_float, C.c_int, _fp, _intp]),

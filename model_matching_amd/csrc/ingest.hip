@@ -15,6 +15,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include <time.h>
+#include <cmath>
 #include <cstring>
 
 
@@ -457,6 +458,71 @@ __global__ __launch_bounds__(256) void scene_pack_kernel(const float4* __restric
     o_px[2 * m] = px[i].x; o_px[2 * m + 1] = px[i].y;
 }
 
+// ---- several objects of one frame (stocs_ingest_scene_multi): the select / compact / pack stages above, over K class images at once
+struct FrameThresholds { float t[STOCS_MAX_FRAME_OBJECTS]; };
+// scene_select_kernel's tests, the geometric ones once per centroid, then the class test per object.  keep holds K segments of
+// n + 1 flags (segment k: object k's flags, then a 0 sentinel -- one exclusive scan over all of them gives the concatenated
+// output positions, and at each sentinel the end of that object's cloud).  Normal and pixel do not depend on the object: stored
+// once per centroid.  One thread per centroid, plus thread n for the sentinels.
+__global__ __launch_bounds__(256) void scene_select_multi_kernel(const float4* __restrict__ cen, const uint32_t* __restrict__ count, int n, uint32_t min_pts,
+                                                                 float fx, float cx, float fy, float cy, int W, int H, const uint16_t* __restrict__ prob, int K,
+                                                                 FrameThresholds thr, const float4* __restrict__ normals, uint32_t* __restrict__ keep,
+                                                                 float4* __restrict__ out_n, int2* __restrict__ out_px) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx > n) return;
+    const size_t seg = (size_t)n + 1, npx = (size_t)W * H;
+    if (idx == n) {
+        for (int k = 0; k < K; ++k) keep[k * seg + n] = 0u;
+        return;
+    }
+    bool ok = false;
+    int pix = 0;
+    const float4 pt = cen[idx];
+    if (count[idx] > min_pts && pt.z == pt.z && pt.z > 0.f && pt.z <= 2.0f) {
+        const int col = (int)((fx * pt.x + cx * pt.z) / pt.z);
+        const int row = (int)((fy * pt.y + cy * pt.z) / pt.z);
+        if (row >= 0 && row < H && col >= 0 && col < W) {
+            pix = row * W + col;
+            const float4 nn = normals[pix];
+            const bool fin = nn.x == nn.x && nn.y == nn.y && nn.z == nn.z;
+            if (fin && !(nn.x == 0 && nn.y == 0 && nn.z == 0)) {
+                ok = true;
+                out_n[idx] = nn; out_px[idx] = make_int2(row, col);
+            }
+        }
+    }
+    for (int k = 0; k < K; ++k) {
+        uint32_t f = 0;
+        if (ok) {
+            const float cp = (float)((double)prob[k * npx + pix] * (1.0 / 10000));
+            f = !(cp < thr.t[k]) ? 1u : 0u;
+        }
+        keep[k * seg + idx] = f;
+    }
+}
+// end of every object's cloud in the concatenated output: offsets[0] = 0, offsets[k + 1] = the scan at object k's sentinel
+__global__ __launch_bounds__(128) void frame_offsets_kernel(const uint32_t* __restrict__ kpos, int n, int K, int32_t* __restrict__ offsets) {
+    const int k = threadIdx.x;
+    if (k > K) return;
+    offsets[k] = k == 0 ? 0 : (int32_t)kpos[(size_t)(k - 1) * ((size_t)n + 1) + n];
+}
+// scene_pack_kernel per object (blockIdx.y = object): the probability is read again from the object's image at the stored pixel,
+// by the same expression as the select
+__global__ __launch_bounds__(256) void scene_pack_multi_kernel(const float4* __restrict__ cen, const float4* __restrict__ nn, const int2* __restrict__ px,
+                                                               const uint16_t* __restrict__ prob, int W, int H, const uint32_t* __restrict__ keep,
+                                                               const uint32_t* __restrict__ pos, int n, float* __restrict__ o_pos, float* __restrict__ o_nrm,
+                                                               float* __restrict__ o_prob, int32_t* __restrict__ o_px) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const size_t s = (size_t)blockIdx.y * ((size_t)n + 1) + i;
+    if (i >= n || !keep[s]) return;
+    const uint32_t m = pos[s];
+    const int2 p = px[i];
+    o_pos[3 * (size_t)m] = cen[i].x; o_pos[3 * (size_t)m + 1] = cen[i].y; o_pos[3 * (size_t)m + 2] = cen[i].z;
+    o_nrm[3 * (size_t)m] = nn[i].x; o_nrm[3 * (size_t)m + 1] = nn[i].y; o_nrm[3 * (size_t)m + 2] = nn[i].z;
+    o_prob[m] = (float)((double)prob[(size_t)blockIdx.y * W * H + (size_t)p.x * W + p.y] * (1.0 / 10000));
+    o_px[2 * (size_t)m] = p.x; o_px[2 * (size_t)m + 1] = p.y;
+}
+
 // voxel grid on device points dP[n] (+ optional extra field); outputs device centroid arrays (workspace memory)
 static int voxel_grid_device(const float4* dP, const float4* dExtra, int n, double leaf, Buf<float4>& cen, Buf<float4>& ext, int* n_out, hipStream_t st,
                              double* box6 = NULL, int* pin_small = NULL) {   // pin_small: 16 pinned words for the call's small read-backs (else pageable stack words)   // box6: a box that holds every centroid (from the leaf bounds, a leaf of slack either side)
@@ -541,6 +607,79 @@ static int voxel_grid_device(const float4* dP, const float4* dExtra, int n, doub
     return STOCS_OK;
 }
 
+// The stages of a frame's ingest that never read a class-probability image (rgbd.cpp:227-237: VoxelGrid and RadiusOutlierRemoval
+// run on the whole cloud, the class threshold comes after them): back-projection, normals, voxel grid, outlier-removal counts.
+// dD: the depth image on the device.  Out: dN the per-pixel normals; *nv centroids in cen with their neighbour counts in count
+// (nothing more when *nv == 0).  pin_small as for voxel_grid_device.
+template <class Tick>
+static int ingest_shared_stages(const stocs_camera* cam, const uint16_t* dD, float voxel_size, hipStream_t st, int* pin_small, Buf<float4>& dN,
+                                Buf<float4>& cen, Buf<uint32_t>& count, int* nv_out, Tick tick) {
+    const int W = cam->width, H = cam->height, npx = W * H;
+    *nv_out = 0;
+    Buf<float4> dP;
+    int rc;
+    if ((rc = dP.alloc(npx)) || (rc = dN.alloc(npx))) return rc;
+    const dim3 g((unsigned)((npx + 255) / 256));
+    hipLaunchKernelGGL(backproject_kernel, g, dim3(256), 0, st, dD, W, H, cam->fx, cam->cx, cam->fy, cam->cy, cam->depth_scale, dP.p);
+    if (cam->normal_method == STOCS_NORMALS_PLANE_FIT) hipLaunchKernelGGL(depth_normals_kernel, g, dim3(256), 0, st, dP.p, W, H, dN.p);
+    else hipLaunchKernelGGL(gradient_normals_kernel, g, dim3(256), 0, st, dD, W, H, cam->fx, cam->cx, cam->fy, cam->cy, dN.p);
+    tick("upload+backproject+normals");
+    Buf<float4> ext;
+    int nv = 0;
+    double box6[6] = {0, 0, 0, 0, 0, 0};
+    if ((rc = voxel_grid_device(dP.p, NULL, npx, (double)voxel_size, cen, ext, &nv, st, box6, pin_small))) return rc;   // rgbd.cpp:228-231
+    tick("voxel grid");
+    if (nv == 0) return STOCS_OK;
+    // radius outlier removal: radius 2*voxel + 5 mm, more than 10 points (itself included)   rgbd.cpp:233-237
+    const double radius = 2.0 * (double)voxel_size + 0.005;
+    // the search grid only has to hold every centroid (the counts do not depend on where its cells fall): its box comes from
+    // the leaf bounds the voxel grid already read back -- no reduction over the centroids, no synchronisation here
+    const double3 mn = make_double3(box6[0], box6[1], box6[2]), mx = make_double3(box6[3], box6[4], box6[5]);
+    const int3 dims = make_int3((int)floor((mx.x - mn.x) / radius) + 1, (int)floor((mx.y - mn.y) / radius) + 1, (int)floor((mx.z - mn.z) / radius) + 1);
+    const size_t ncell = (size_t)dims.x * dims.y * dims.z;
+    if (ncell > ((size_t)1 << 28)) { set_error("scene extent too large for the outlier-removal grid"); return STOCS_ERR_INVALID; }
+    Buf<uint32_t> cell, cell_s, ids, ids_s, cstart, cend; Buf<char> tmp;
+    if ((rc = cell.alloc(nv)) || (rc = cell_s.alloc(nv)) || (rc = ids.alloc(nv)) || (rc = ids_s.alloc(nv)) || (rc = cstart.alloc(ncell)) || (rc = cend.alloc(ncell)) ||
+        (rc = count.alloc(nv))) return rc;
+    const dim3 gv((unsigned)((nv + 255) / 256));
+    hipLaunchKernelGGL(ror_cell_kernel, gv, dim3(256), 0, st, cen.p, nv, mn, 1.0 / radius, dims, cell.p);
+    hipLaunchKernelGGL(iota_kernel, gv, dim3(256), 0, st, ids.p, nv);
+    size_t tb = 0;
+    int cell_bits = 1;
+    while (cell_bits < 32 && ((size_t)1 << cell_bits) < ncell) cell_bits++;
+    STOCS_HIP_CHECK(sort_pairs(NULL, tb, cell.p, cell_s.p, ids.p, ids_s.p, (size_t)nv, 0, (unsigned)cell_bits, st));
+    if ((rc = tmp.alloc(tb))) return rc;
+    STOCS_HIP_CHECK(sort_pairs(tmp.p, tb, cell.p, cell_s.p, ids.p, ids_s.p, (size_t)nv, 0, (unsigned)cell_bits, st));
+    hipLaunchKernelGGL(zero_u32x2_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, st, cstart.p, cend.p, ncell);
+    hipLaunchKernelGGL(cell_start_kernel, gv, dim3(256), 0, st, cell_s.p, nv, cstart.p, cend.p);
+    hipLaunchKernelGGL(ror_count_kernel, gv, dim3(256), 0, st, cen.p, nv, mn, 1.0 / radius, dims, radius, cstart.p, cend.p, ids_s.p, count.p, 10u);
+    STOCS_HIP_CHECK(hipGetLastError());
+    *nv_out = nv;
+    return STOCS_OK;
+}
+
+// STOCS_DEBUG_TIMING: the ingest's stages on stderr (each one synchronised)
+struct IngestTick {
+    const char* who;
+    bool on;
+    struct timespec t0;
+    explicit IngestTick(const char* w) : who(w), on(getenv("STOCS_DEBUG_TIMING") != NULL) { clock_gettime(CLOCK_MONOTONIC, &t0); }
+    void operator()(const char* label) {
+        if (!on) return;
+        (void)hipDeviceSynchronize();
+        struct timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
+        fprintf(stderr, "[%s] %-22s %8.3f ms\n", who, label, (t1.tv_sec - t0.tv_sec) * 1e3 + (t1.tv_nsec - t0.tv_nsec) * 1e-6);
+        t0 = t1;
+    }
+};
+
+static int ingest_check_camera(const stocs_camera* cam, const char* fn) {
+    if (cam->normal_method != STOCS_NORMALS_DEPTH_GRADIENT && cam->normal_method != STOCS_NORMALS_PLANE_FIT) { set_error("%s: unknown normal_method %d", fn, cam->normal_method); return STOCS_ERR_INVALID; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: this library has no CPU fallback"); return STOCS_ERR_NO_DEVICE; }
+    return STOCS_OK;
+}
+
 }  // namespace stocs
 
 using namespace stocs;
@@ -562,68 +701,33 @@ int stocs_trim(void) {
 int stocs_ingest_scene(const stocs_camera* cam, const uint16_t* depth, const uint16_t* class_prob, float voxel_size,
                        float class_threshold, int device, float* pos3, float* nrm3, float* prob, int32_t* pixel2, int cap, int* n_out) {
     if (!cam || !depth || !class_prob || !n_out || cam->width <= 0 || cam->height <= 0 || !(voxel_size > 0)) return STOCS_ERR_INVALID;
-    if (cam->normal_method != STOCS_NORMALS_DEPTH_GRADIENT && cam->normal_method != STOCS_NORMALS_PLANE_FIT) { set_error("stocs_ingest_scene: unknown normal_method %d", cam->normal_method); return STOCS_ERR_INVALID; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: this library has no CPU fallback"); return STOCS_ERR_NO_DEVICE; }
-    if (device >= 0) STOCS_HIP_CHECK(hipSetDevice(device));
-    const bool dbg = getenv("STOCS_DEBUG_TIMING") != NULL;
-    struct timespec ts0; clock_gettime(CLOCK_MONOTONIC, &ts0);
-    auto tick = [&](const char* label) {
-        if (!dbg) return;
-        (void)hipDeviceSynchronize();
-        struct timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
-        fprintf(stderr, "[stocs ingest] %-22s %8.3f ms\n", label, (t1.tv_sec - ts0.tv_sec) * 1e3 + (t1.tv_nsec - ts0.tv_nsec) * 1e-6);
-        ts0 = t1;
-    };
-    int rc = workspace_begin(device);
+    int rc = ingest_check_camera(cam, "stocs_ingest_scene");
     if (rc) return rc;
+    if (device >= 0) STOCS_HIP_CHECK(hipSetDevice(device));
+    IngestTick tick("stocs ingest");
+    if ((rc = workspace_begin(device))) return rc;
     tick("workspace");
     hipStream_t st = NULL;
     const int W = cam->width, H = cam->height, npx = W * H;
-    Buf<uint16_t> dD, dC; Buf<float4> dP, dN;
-    if ((rc = dD.alloc(npx)) || (rc = dC.alloc(npx)) || (rc = dP.alloc(npx)) || (rc = dN.alloc(npx))) return rc;
+    Buf<uint16_t> dD, dC;
+    if ((rc = dD.alloc(npx)) || (rc = dC.alloc(npx))) return rc;
     char* pin = NULL;
     if ((rc = staging((size_t)npx * 40 + 4096, &pin))) return rc;     // in: two u16 images (4 B per pixel); out: at most one point per pixel, 36 B each
     memcpy(pin, depth, 2 * (size_t)npx); memcpy(pin + 2 * (size_t)npx, class_prob, 2 * (size_t)npx);
     STOCS_HIP_CHECK(hipMemcpyAsync(dD.p, pin, 2 * (size_t)npx, hipMemcpyHostToDevice, st));
     STOCS_HIP_CHECK(hipMemcpyAsync(dC.p, pin + 2 * (size_t)npx, 2 * (size_t)npx, hipMemcpyHostToDevice, st));
-    const dim3 g((unsigned)((npx + 255) / 256));
-    hipLaunchKernelGGL(backproject_kernel, g, dim3(256), 0, st, dD.p, W, H, cam->fx, cam->cx, cam->fy, cam->cy, cam->depth_scale, dP.p);
-    if (cam->normal_method == STOCS_NORMALS_PLANE_FIT) hipLaunchKernelGGL(depth_normals_kernel, g, dim3(256), 0, st, dP.p, W, H, dN.p);
-    else hipLaunchKernelGGL(gradient_normals_kernel, g, dim3(256), 0, st, dD.p, W, H, cam->fx, cam->cx, cam->fy, cam->cy, dN.p);
-    tick("upload+backproject+normals");
-    Buf<float4> cen, ext;
-    int nv = 0;
-    double box6[6] = {0, 0, 0, 0, 0, 0};
     int* pin_small = (int*)(pin + (size_t)npx * 40);                 // (the 4 KB behind the cloud's part of the staging block)
-    if ((rc = voxel_grid_device(dP.p, NULL, npx, (double)voxel_size, cen, ext, &nv, st, box6, pin_small))) return rc;   // rgbd.cpp:228-231
+    Buf<float4> dN, cen; Buf<uint32_t> count;
+    int nv = 0;
+    if ((rc = ingest_shared_stages(cam, dD.p, voxel_size, st, pin_small, dN, cen, count, &nv, tick))) return rc;
     *n_out = 0;
-    tick("voxel grid");
     if (nv == 0) { STOCS_HIP_CHECK(hipStreamSynchronize(st)); return STOCS_OK; }
-    // radius outlier removal: radius 2*voxel + 5 mm, more than 10 points (itself included)   rgbd.cpp:233-237
-    const double radius = 2.0 * (double)voxel_size + 0.005;
-    // the search grid only has to hold every centroid (the counts do not depend on where its cells fall): its box comes from
-    // the leaf bounds the voxel grid already read back -- no reduction over the centroids, no synchronisation here
-    const double3 mn = make_double3(box6[0], box6[1], box6[2]), mx = make_double3(box6[3], box6[4], box6[5]);
-    const int3 dims = make_int3((int)floor((mx.x - mn.x) / radius) + 1, (int)floor((mx.y - mn.y) / radius) + 1, (int)floor((mx.z - mn.z) / radius) + 1);
-    const size_t ncell = (size_t)dims.x * dims.y * dims.z;
-    if (ncell > ((size_t)1 << 28)) { set_error("scene extent too large for the outlier-removal grid"); return STOCS_ERR_INVALID; }
-    Buf<uint32_t> cell, cell_s, ids, ids_s, cstart, cend, count, keep, kpos; Buf<char> tmp;
-    if ((rc = cell.alloc(nv)) || (rc = cell_s.alloc(nv)) || (rc = ids.alloc(nv)) || (rc = ids_s.alloc(nv)) || (rc = cstart.alloc(ncell)) || (rc = cend.alloc(ncell)) ||
-        (rc = count.alloc(nv)) || (rc = keep.alloc(nv + 1)) || (rc = kpos.alloc(nv + 1))) return rc;
-    const dim3 gv((unsigned)((nv + 255) / 256));
-    hipLaunchKernelGGL(ror_cell_kernel, gv, dim3(256), 0, st, cen.p, nv, mn, 1.0 / radius, dims, cell.p);
-    hipLaunchKernelGGL(iota_kernel, gv, dim3(256), 0, st, ids.p, nv);
-    size_t tb = 0, tb2 = 0;
-    int cell_bits = 1;
-    while (cell_bits < 32 && ((size_t)1 << cell_bits) < ncell) cell_bits++;
-    STOCS_HIP_CHECK(sort_pairs(NULL, tb, cell.p, cell_s.p, ids.p, ids_s.p, (size_t)nv, 0, (unsigned)cell_bits, st));
+    Buf<uint32_t> keep, kpos; Buf<char> tmp;
+    size_t tb2 = 0;
+    if ((rc = keep.alloc(nv + 1)) || (rc = kpos.alloc(nv + 1))) return rc;
     STOCS_HIP_CHECK(exclusive_scan(NULL, tb2, keep.p, kpos.p, (size_t)nv + 1, st));
-    if ((rc = tmp.alloc(std::max(tb, tb2)))) return rc;
-    STOCS_HIP_CHECK(sort_pairs(tmp.p, tb, cell.p, cell_s.p, ids.p, ids_s.p, (size_t)nv, 0, (unsigned)cell_bits, st));
-    hipLaunchKernelGGL(zero_u32x2_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, st, cstart.p, cend.p, ncell);
-    hipLaunchKernelGGL(cell_start_kernel, gv, dim3(256), 0, st, cell_s.p, nv, cstart.p, cend.p);
-    hipLaunchKernelGGL(ror_count_kernel, gv, dim3(256), 0, st, cen.p, nv, mn, 1.0 / radius, dims, radius, cstart.p, cend.p, ids_s.p, count.p, 10u);
+    if ((rc = tmp.alloc(tb2))) return rc;
+    const dim3 gv((unsigned)((nv + 255) / 256));
     Buf<float4> on; Buf<float> op; Buf<int2> opx;
     if ((rc = on.alloc(nv)) || (rc = op.alloc(nv)) || (rc = opx.alloc(nv))) return rc;
     hipLaunchKernelGGL(scene_select_kernel, gv, dim3(256), 0, st, cen.p, count.p, nv, 10u, cam->fx, cam->cx, cam->fy, cam->cy, W, H, dC.p, class_threshold, dN.p,
@@ -660,6 +764,86 @@ int stocs_ingest_scene(const stocs_camera* cam, const uint16_t* depth, const uin
     tick("download");
     *n_out = (int)m;
     return (int)m > cap ? STOCS_ERR_CAPACITY : STOCS_OK;
+}
+
+int stocs_ingest_scene_multi(const stocs_camera* cam, const uint16_t* depth, int n_objects, const uint16_t* class_probs, const float* class_thresholds,
+                             float voxel_size, int device, float* pos3, float* nrm3, float* prob, int32_t* pixel2, int cap, int32_t* offsets) {
+    if (!cam || !depth || !class_probs || !class_thresholds || !offsets || cam->width <= 0 || cam->height <= 0 || !(voxel_size > 0)) return STOCS_ERR_INVALID;
+    if (n_objects < 1 || n_objects > STOCS_MAX_FRAME_OBJECTS) { set_error("stocs_ingest_scene_multi: n_objects %d outside 1..%d", n_objects, STOCS_MAX_FRAME_OBJECTS); return STOCS_ERR_INVALID; }
+    FrameThresholds thr;
+    memset(&thr, 0, sizeof(thr));
+    for (int k = 0; k < n_objects; ++k) {
+        if (!std::isfinite(class_thresholds[k])) { set_error("stocs_ingest_scene_multi: class threshold %d is not finite", k); return STOCS_ERR_INVALID; }
+        thr.t[k] = class_thresholds[k];
+    }
+    int rc = ingest_check_camera(cam, "stocs_ingest_scene_multi");
+    if (rc) return rc;
+    if (device >= 0) STOCS_HIP_CHECK(hipSetDevice(device));
+    IngestTick tick("stocs ingest multi");
+    if ((rc = workspace_begin(device))) return rc;
+    tick("workspace");
+    hipStream_t st = NULL;
+    const int W = cam->width, H = cam->height, npx = W * H, K = n_objects;
+    Buf<uint16_t> dD, dC;
+    if ((rc = dD.alloc(npx)) || (rc = dC.alloc((size_t)K * npx))) return rc;
+    // staging: 4 KB of small read-backs, then the depth image and the K class images (the cloud comes down through the block later)
+    char* pin = NULL;
+    const size_t in_bytes = (size_t)(2 + 2 * K) * npx;
+    if ((rc = staging(4096 + in_bytes, &pin))) return rc;
+    int* pin_small = (int*)pin;
+    memcpy(pin + 4096, depth, 2 * (size_t)npx); memcpy(pin + 4096 + 2 * (size_t)npx, class_probs, 2 * (size_t)K * npx);
+    STOCS_HIP_CHECK(hipMemcpyAsync(dD.p, pin + 4096, 2 * (size_t)npx, hipMemcpyHostToDevice, st));
+    STOCS_HIP_CHECK(hipMemcpyAsync(dC.p, pin + 4096 + 2 * (size_t)npx, 2 * (size_t)K * npx, hipMemcpyHostToDevice, st));
+    Buf<float4> dN, cen; Buf<uint32_t> count;
+    int nv = 0;
+    if ((rc = ingest_shared_stages(cam, dD.p, voxel_size, st, pin_small, dN, cen, count, &nv, tick))) return rc;
+    if (nv == 0) {
+        STOCS_HIP_CHECK(hipStreamSynchronize(st));
+        for (int k = 0; k <= K; ++k) offsets[k] = 0;
+        return STOCS_OK;
+    }
+    const size_t nflag = (size_t)K * ((size_t)nv + 1);
+    if (nflag > (size_t)INT_MAX) { set_error("stocs_ingest_scene_multi: %d objects x %d centroids exceed the compaction's range", K, nv); return STOCS_ERR_INVALID; }
+    Buf<uint32_t> keep, kpos; Buf<char> tmp; Buf<int32_t> d_off;
+    size_t tb2 = 0;
+    if ((rc = keep.alloc(nflag)) || (rc = kpos.alloc(nflag)) || (rc = d_off.alloc((size_t)K + 1))) return rc;
+    STOCS_HIP_CHECK(exclusive_scan(NULL, tb2, keep.p, kpos.p, nflag, st));
+    if ((rc = tmp.alloc(tb2))) return rc;
+    Buf<float4> on; Buf<int2> opx;
+    if ((rc = on.alloc(nv)) || (rc = opx.alloc(nv))) return rc;
+    hipLaunchKernelGGL(scene_select_multi_kernel, dim3((unsigned)((nv + 1 + 255) / 256)), dim3(256), 0, st, cen.p, count.p, nv, 10u, cam->fx, cam->cx, cam->fy, cam->cy,
+                       W, H, dC.p, K, thr, dN.p, keep.p, on.p, opx.p);
+    // one stable compaction for all objects: the scan runs across the K segments, each closed by its 0 sentinel
+    STOCS_HIP_CHECK(exclusive_scan(tmp.p, tb2, keep.p, kpos.p, nflag, st));
+    hipLaunchKernelGGL(frame_offsets_kernel, dim3(1), dim3(128), 0, st, kpos.p, nv, K, d_off.p);
+    Buf<float> o_pos, o_nrm, o_prob; Buf<int32_t> o_px;
+    const size_t most = (size_t)K * nv;   // every centroid kept for every object
+    if ((rc = o_pos.alloc(most * 3)) || (rc = o_nrm.alloc(most * 3)) || (rc = o_prob.alloc(most)) || (rc = o_px.alloc(most * 2))) return rc;
+    hipLaunchKernelGGL(scene_pack_multi_kernel, dim3((unsigned)((nv + 255) / 256), (unsigned)K), dim3(256), 0, st, cen.p, on.p, opx.p, dC.p, W, H, keep.p, kpos.p, nv,
+                       o_pos.p, o_nrm.p, o_prob.p, o_px.p);
+    STOCS_HIP_CHECK(hipGetLastError());
+    tick("outlier removal+select");
+    int32_t* off_pin = pin_small + 16;   // (words 0-11 are the voxel grid's)
+    STOCS_HIP_CHECK(hipMemcpyAsync(off_pin, d_off.p, 4 * ((size_t)K + 1), hipMemcpyDeviceToHost, st));
+    STOCS_HIP_CHECK(hipStreamSynchronize(st));
+    memcpy(offsets, off_pin, 4 * ((size_t)K + 1));
+    const size_t m = (size_t)offsets[K];
+    if (m > (size_t)std::max(cap, 0)) { set_error("stocs_ingest_scene_multi: %zu points over all objects, cap %d", m, cap); return STOCS_ERR_CAPACITY; }
+    if (m == 0) return STOCS_OK;
+    // (the images in the staging block were consumed before the offsets came back: the block is free for the clouds)
+    if ((rc = staging(36 * m, &pin))) return rc;
+    char* h_pos = pin; char* h_nrm = pin + 12 * m; char* h_prob = pin + 24 * m; char* h_px = pin + 28 * m;
+    if (pos3) STOCS_HIP_CHECK(hipMemcpyAsync(h_pos, o_pos.p, 12 * m, hipMemcpyDeviceToHost, st));
+    if (nrm3) STOCS_HIP_CHECK(hipMemcpyAsync(h_nrm, o_nrm.p, 12 * m, hipMemcpyDeviceToHost, st));
+    if (prob) STOCS_HIP_CHECK(hipMemcpyAsync(h_prob, o_prob.p, 4 * m, hipMemcpyDeviceToHost, st));
+    if (pixel2) STOCS_HIP_CHECK(hipMemcpyAsync(h_px, o_px.p, 8 * m, hipMemcpyDeviceToHost, st));
+    STOCS_HIP_CHECK(hipStreamSynchronize(st));
+    if (pos3) memcpy(pos3, h_pos, 12 * m);
+    if (nrm3) memcpy(nrm3, h_nrm, 12 * m);
+    if (prob) memcpy(prob, h_prob, 4 * m);
+    if (pixel2) memcpy(pixel2, h_px, 8 * m);
+    tick("download");
+    return STOCS_OK;
 }
 
 int stocs_preprocess_model(const float* raw_pos3, int n_raw, float normal_radius, float voxel_size, float model_scale, int device,

@@ -444,6 +444,68 @@ def ingest_scene(depth_u16, prob_u16, K, depth_scale, voxel_size=0.005, class_th
     return pos[:k].copy(), nrm[:k].copy(), pr[:k].copy(), px[:k].copy()
 
 
+def ingest_scene_multi(depth_u16, probs_u16, K, depth_scale, voxel_size=0.005, class_thresholds=0.10, device=-1, normal_method=0):
+    """Every object of one frame from one GPU ingest (stocs_ingest_scene_multi): probs_u16 holds one class-probability image per object
+    (n_objects x H x W, or a list of H x W images), class_thresholds one threshold for all or one per object.  Returns a list of
+    (pos, nrm, prob, pixel), one per object, each bit for bit what ingest_scene(depth_u16, probs_u16[k], ..., class_thresholds[k]) returns."""
+    L = capi.load()
+    d = np.ascontiguousarray(depth_u16, np.uint16)
+    H, W = d.shape
+    p = np.ascontiguousarray(np.stack([np.asarray(x, np.uint16) for x in probs_u16]) if isinstance(probs_u16, (list, tuple)) else probs_u16, np.uint16)
+    n_obj = p.shape[0]
+    if p.shape[1:] != (H, W):
+        raise ValueError("class-probability images are %s, the depth image %s" % (p.shape[1:], (H, W)))
+    thr = np.ascontiguousarray(np.broadcast_to(np.asarray(class_thresholds, np.float32), (n_obj,)), np.float32)
+    cam = capi.Camera(K[0], K[1], K[2], K[3], depth_scale, W, H, normal_method)
+    off = np.zeros(n_obj + 1, np.int32)
+    cap = W * H   # one frame's worth of points; grown once when the objects need more
+    for attempt in range(2):
+        pos = np.zeros((cap, 3), np.float32); nrm = np.zeros((cap, 3), np.float32); pr = np.zeros(cap, np.float32); px = np.zeros((cap, 2), np.int32)
+        rc = L.stocs_ingest_scene_multi(C.byref(cam), d.ctypes.data_as(C.POINTER(C.c_uint16)), n_obj, p.ctypes.data_as(C.POINTER(C.c_uint16)),
+                                        thr.ctypes.data_as(capi._fp), voxel_size, device, pos.ctypes.data_as(capi._fp), nrm.ctypes.data_as(capi._fp),
+                                        pr.ctypes.data_as(capi._fp), px.ctypes.data_as(capi._ip), cap, off.ctypes.data_as(capi._ip))
+        if rc == capi.ERR_CAPACITY and attempt == 0:
+            cap = int(off[-1])
+            continue
+        capi.check(rc)
+        break
+    return [(pos[a:b].copy(), nrm[a:b].copy(), pr[a:b].copy(), px[a:b].copy()) for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
+
+
+def estimate_objects(scenes, models, seeds, n_attempts=100, mode=0, dispersion=0.9, max_per_base=200, edge_map=None, options=None,
+                     params=None, max_workers=4, device=-1):
+    """One estimator per object of a frame, run concurrently on a pool of at most max_workers host threads (each context owns its
+    streams; the library calls release the GIL).  scenes[k] = (pos, nrm, prob, pixel) -- e.g. from ingest_scene_multi --, models[k] =
+    (pos, nrm).  seeds: an int runs one trial (sample_bases, find_congruent_all, make_transforms, compute_best_transform), a sequence
+    runs run_trials over it.  edge_map (instance mode) and options (set_option) apply to every object.  Each context is closed when its
+    object is done, so at most max_workers hold trial memory at a time.  Returns, in object order, (best_lcp, best_index, best_pose)
+    for one trial and run_trials' list of dicts otherwise."""
+    from concurrent.futures import ThreadPoolExecutor
+    if len(scenes) != len(models):
+        raise ValueError("%d scenes for %d models" % (len(scenes), len(models)))
+
+    def one(k):
+        (sp, sn, spr, spx), (mp, mn) = scenes[k], models[k]
+        est = StocsEstimator(sp, sn, spr, spx, mp, mn, params=params, build_index=True, device=device)
+        try:
+            for key, v in (options or {}).items():
+                est.set_option(key, v)
+            if edge_map is not None:
+                est.set_edge_map(edge_map)
+            if np.ndim(seeds) == 0:
+                est.sample_bases(int(seeds), n_attempts, mode=mode, dispersion=dispersion)
+                est.find_congruent_all()
+                est.make_transforms(max_per_base, int(seeds))
+                lcp, idx, pose = est.compute_best_transform()
+                return float(lcp), int(idx), pose
+            return est.run_trials(seeds, n_attempts, mode=mode, dispersion=dispersion, max_per_base=max_per_base)
+        finally:
+            est.close()
+
+    with ThreadPoolExecutor(max(1, min(max_workers, len(scenes)))) as ex:
+        return list(ex.map(one, range(len(scenes))))
+
+
 def preprocess_model(raw_pos, normal_radius, voxel_size, model_scale=1.0, device=-1):
     """GPU model preprocessing (stocs_preprocess_model): returns voxelised pos, unit nrm."""
     L = capi.load()
