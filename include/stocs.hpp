@@ -494,11 +494,56 @@ public:
     // estimator's best pose (get_best_score / get_best_pose); returns the index of that trial, -1 when no trial found a pose.
     struct TrialResult { int n_bases, n_candidates; long long n_congruent_sets; float best_lcp; int best_index; MatrixType best_pose; };
     int run_trials(int n_trials, uint64_t first_seed, int number_of_bases, int maximum_congruent_sets, float dispersion, std::vector<TrialResult>* results = NULL) {
+        return run_trials_impl(n_trials, first_seed, number_of_bases, maximum_congruent_sets, dispersion, NULL, results);
+    }
+    // the same batch with post-processing inside it (stocs_run_trials_post): every trial's candidates clustered on the device
+    // (clustering::greedy_clustering with post's fraction, count, distance, angle and sym_info, best_score = the trial's best lcp) and,
+    // with post.refine_iterations > 0, the kept hypotheses refined (clustering::point_to_plane_icp on the whole scene) and rescored.
+    // hypotheses[t]: trial t's kept candidates (camera-frame transform, lcp, base index) in cluster order; refined[t]: the same
+    // hypotheses refined (refined transform, rescored lcp) -- the candidates themselves without refinement.  Owned by the estimator
+    // until the next run_trials.
+    int run_trials(int n_trials, uint64_t first_seed, int number_of_bases, int maximum_congruent_sets, float dispersion, const stocs_trial_post& post,
+                   std::vector<TrialResult>* results, std::vector<std::vector<PoseCandidate*> >* hypotheses,
+                   std::vector<std::vector<PoseCandidate*> >* refined = NULL) {
+        hyp_store_.clear();
+        if (hypotheses) hypotheses->clear();
+        if (refined) refined->clear();
+        const int best = run_trials_impl(n_trials, first_seed, number_of_bases, maximum_congruent_sets, dispersion, &post, results);
+        if (best == -2) return -1;
+        std::vector<stocs_trial_hypothesis> h;
+        for (int t = 0; t < n_trials; ++t) {
+            int n = 0;
+            if (stocs_trials_get_hypotheses(ctx_, t, NULL, 0, &n) != STOCS_OK) return -1;
+            h.resize((size_t)std::max(n, 1));
+            if (n > 0 && stocs_trials_get_hypotheses(ctx_, t, h.data(), n, &n) != STOCS_OK) return -1;
+            std::vector<PoseCandidate*> a, b;
+            for (int i = 0; i < n; ++i) {
+                MatrixType m, r;
+                memcpy(m.data(), h[(size_t)i].pose16, 64);
+                memcpy(r.data(), h[(size_t)i].refined_pose16, 64);
+                hyp_store_.emplace_back(new PoseCandidate(m, h[(size_t)i].lcp, (float)h[(size_t)i].base_index));
+                a.push_back(hyp_store_.back().get());
+                hyp_store_.emplace_back(new PoseCandidate(r, h[(size_t)i].refined_lcp, (float)h[(size_t)i].base_index));
+                b.push_back(hyp_store_.back().get());
+            }
+            if (hypotheses) hypotheses->push_back(a);
+            if (refined) refined->push_back(b);
+        }
+        return best;
+    }
+
+private:
+    // -2: the library call failed (the public forms return -1 then, as for "no pose")
+    int run_trials_impl(int n_trials, uint64_t first_seed, int number_of_bases, int maximum_congruent_sets, float dispersion, const stocs_trial_post* post,
+                        std::vector<TrialResult>* results) {
         std::vector<uint64_t> seeds((size_t)std::max(n_trials, 0));
         for (int t = 0; t < n_trials; ++t) seeds[(size_t)t] = first_seed + (uint64_t)t;
         std::vector<stocs_trial_result> r((size_t)std::max(n_trials, 1));
         la_n_ = 0; la_in_ctx_ = false; batched_ = false; fetched_ = false; n_batched_ = 0;
-        if (stocs_run_trials(ctx_, has_edge_map() ? 1 : 0, n_trials, seeds.data(), number_of_bases, dispersion, maximum_congruent_sets, 0, r.data()) != STOCS_OK) return -1;
+        const int rc = post ? stocs_run_trials_post(ctx_, has_edge_map() ? 1 : 0, n_trials, seeds.data(), number_of_bases, dispersion, maximum_congruent_sets, 0,
+                                                    post, r.data())
+                            : stocs_run_trials(ctx_, has_edge_map() ? 1 : 0, n_trials, seeds.data(), number_of_bases, dispersion, maximum_congruent_sets, 0, r.data());
+        if (rc != STOCS_OK) return post ? -2 : -1;
         int best = -1;
         if (results) results->clear();
         for (int t = 0; t < n_trials; ++t) {
@@ -521,6 +566,8 @@ public:
         }
         return best;
     }
+
+public:
     // the winner of the last run_trials (camera frame), NULL when no trial found a pose; owned by the estimator
     PoseCandidate* get_best_trial_pose() const { return trial_best_.get(); }
 
@@ -561,6 +608,7 @@ public:
 protected:
     std::unique_ptr<PoseCandidate> trial_best_;
     std::vector<std::unique_ptr<PoseCandidate> > refined_store_;   // results of the last refine_pose_candidates
+    std::vector<std::unique_ptr<PoseCandidate> > hyp_store_;       // hypotheses of the last post-processed run_trials
     void reset_members(const std::string& dbg, int w, int h, float dist, int tr, int rot, float edge_thr, float class_thr) {
         ctx_ = NULL; log_ = &std::cout; best_lcp = 0; best_index = -1; seed_ = 0; attempt_ = 0; batched_ = false; fetched_ = false; n_batched_ = 0;
         la_n_ = 0; la_first_ = 0; la_seed_ = 0; la_cursor_ = 0; la_in_ctx_ = false; la_congruent_done_ = false; la_mode_ = 0; la_nvalid_ = 0;

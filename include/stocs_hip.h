@@ -213,6 +213,34 @@ int stocs_trials_get_quad_counts(stocs_ctx* ctx, int trial, int64_t* counts, int
 /* the trial's candidates as stocs_get_candidates returns them after stocs_verify_all (needs keep_details; base_index counts the
  * trial's own valid bases) */
 int stocs_trials_get_candidates(stocs_ctx* ctx, int trial, float* T16_centred, float* pose16_camera, float* lcp, int32_t* base_index, int cap, int* n);
+/* ---- post-processing inside a trial batch: clustering::greedy_clustering (pose_clustering.cpp:79-121) of every trial's candidates
+ * and clustering::point_to_plane_icp (:123-140) of the kept hypotheses, on the device, per piece of the batch; only the kept
+ * hypotheses come back (with the per-trial results: one read-back, one synchronisation per piece).  Trial t's hypotheses are, bit
+ * for bit, stocs_cluster_poses(its candidates' camera poses, their lcp, n, acceptable_fraction, best_score = its best_lcp, ...) --
+ * candidate_index in that order, i.e. descending lcp -- and, with refine_iterations > 0, stocs_refine_poses(the kept candidates'
+ * centred T16, n, NULL, 0, refine_iterations, max_correspondence_distance) run on the same context right after that trial alone
+ * (instance mode: rescored against the trial's own decayed class probabilities).  stocs_run_trials(...) is
+ * stocs_run_trials_post(..., post = NULL, ...): the batch runs exactly as without post-processing.  A negative count or iteration
+ * number, a NaN fraction, a min_distance / min_angle / max_correspondence_distance that is <= 0 or not finite: STOCS_ERR_INVALID. ---- */
+typedef struct stocs_trial_post {
+    float   acceptable_fraction;          /* candidates with lcp > fraction * best_lcp take part (the driver uses 0.8)            */
+    int32_t maximum_pose_count;           /* >= 0; up to count + 1 hypotheses per trial (the reference's size() > count break)    */
+    float   min_distance, min_angle;      /* metres, degrees: a candidate within both of a kept one is dropped (0.02, 15)        */
+    float   sym3[3];                      /* sym_info: 0 / 90 / 180 / 360 degrees per Euler axis                                 */
+    int32_t refine_iterations;            /* 0: cluster only (refined fields = the candidate's, counts 0)                        */
+    float   max_correspondence_distance;  /* metres (0.035)                                                                      */
+} stocs_trial_post;
+int stocs_run_trials_post(stocs_ctx* ctx, int mode, int n_trials, const uint64_t* seeds, int n_attempts, float dispersion, int max_per_base,
+                          int keep_details, const stocs_trial_post* post /* may be NULL */, stocs_trial_result* out /* n_trials, may be NULL */);
+typedef struct stocs_trial_hypothesis {
+    int32_t candidate_index, base_index;  /* into the trial's own lists, as stocs_trials_get_candidates                          */
+    float   lcp, pose16[16];              /* the candidate as scored (camera frame, column-major)                                */
+    float   refined_lcp, refined_pose16[16];
+    int32_t n_correspondences, iterations;   /* stocs_refine_poses's; == the candidate's lcp / pose and 0, 0 without refinement */
+} stocs_trial_hypothesis;
+/* the hypotheses of one trial of the last batch, in cluster order (descending lcp); a trial without a pose has none.  The batch ran
+ * without post: STOCS_ERR_STATE; out != NULL and cap < the count: STOCS_ERR_CAPACITY (*n is the count either way) */
+int stocs_trials_get_hypotheses(stocs_ctx* ctx, int trial, stocs_trial_hypothesis* out, int cap, int* n);
 
 /* arg-max of n device-resident scores on the device: *key = max over i of
  * stocs_pack_best(lcp[i], id_offset + i), 0 when no score is positive (first maximum wins, as the

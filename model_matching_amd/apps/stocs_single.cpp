@@ -16,6 +16,8 @@
 // common options: --seed N --bases 100 --max-sets 200 --out FILE --dbg DIR --cluster 1 --exact-ties 1
 // --refine N (with --cluster 1): N point-to-plane iterations on every clustered hypothesis (clustering::point_to_plane_icp,
 // pose_clustering.cpp:123-140, batched: stocs_refine_poses); the best refined pose goes to <out>.refined in the same format.
+// --trials N --cluster 1 [--refine K]: the clustering (and refinement) of every trial runs inside the batch, on the device
+// (stocs_run_trials_post); per-trial cluster / refined lines, the best refined pose of the best trial to <out>.refined.
 // The reference edits its per-data-set constants in the source (README.md:42-66); here they are options with the
 // reference's YCB values as defaults.
 #include <algorithm>
@@ -74,15 +76,33 @@ static int run_search(stocs::stocs_estimator& stocs_ptr, std::ostream& os, const
     if (n_trials > 0) {
         // BASELINE config 4: N independent StoCS trials -- each the whole loop of run_stocs_estimation (:79-165) with its own seed --
         // in ONE set of launches (stocs_run_trials); the best pose over the trials is the result
+        // --cluster 1 [--refine K]: every trial's candidates clustered (and the kept ones refined) inside the batch, on the device
+        // (stocs_run_trials_post), with the single-trial block's clustering constants
         std::vector<stocs::stocs_estimator::TrialResult> res;
+        std::vector<std::vector<PoseCandidate*> > hyps, refined;
         auto t0 = std::chrono::high_resolution_clock::now();
-        const int best = stocs_ptr.run_trials(n_trials, seed, number_of_bases, maximum_congruent_sets, sample_dispersion, &res);
+        int best;
+        if (do_cluster) {
+            stocs_trial_post post;
+            post.acceptable_fraction = 0.8f; post.maximum_pose_count = 10; post.min_distance = 0.02f; post.min_angle = 15.0f;
+            post.sym3[0] = post.sym3[1] = post.sym3[2] = 0.0f;
+            post.refine_iterations = n_refine; post.max_correspondence_distance = 0.035f;
+            best = stocs_ptr.run_trials(n_trials, seed, number_of_bases, maximum_congruent_sets, sample_dispersion, post, &res, &hyps, &refined);
+        } else {
+            best = stocs_ptr.run_trials(n_trials, seed, number_of_bases, maximum_congruent_sets, sample_dispersion, &res);
+        }
         auto t1 = std::chrono::high_resolution_clock::now();
         long long cand = 0;
         for (size_t t = 0; t < res.size(); ++t) {
             cand += res[t].n_candidates;
             os << "trial " << t << ": bases " << res[t].n_bases << " congruent sets " << res[t].n_congruent_sets << " candidates " << res[t].n_candidates
                << " best lcp " << res[t].best_lcp << std::endl;
+            if (do_cluster && t < hyps.size()) {
+                os << "trial " << t << " clustered hypotheses: " << hyps[t].size() << std::endl;
+                for (size_t i = 0; i < hyps[t].size(); ++i) os << "  cluster " << i << ": base " << hyps[t][i]->base_index << " lcp " << hyps[t][i]->lcp << std::endl;
+                for (size_t i = 0; n_refine > 0 && i < refined[t].size(); ++i)
+                    os << "  refined " << i << ": base " << refined[t][i]->base_index << " lcp " << hyps[t][i]->lcp << " -> " << refined[t][i]->lcp << std::endl;
+            }
         }
         const long long us = (long long)std::chrono::duration_cast<micro>(t1 - t0).count();
         char tl[256];
@@ -95,6 +115,18 @@ static int run_search(stocs::stocs_estimator& stocs_ptr, std::ostream& os, const
             os << "pose:";
             for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) { char b[32]; snprintf(b, sizeof(b), " %.9g", (double)bp->transform(r, c)); os << b; }
             os << std::endl;
+            // the best refined hypothesis (first maximum of the rescored lcp) of the best trial
+            PoseCandidate* rb = NULL;
+            for (size_t i = 0; n_refine > 0 && best >= 0 && (size_t)best < refined.size() && i < refined[(size_t)best].size(); ++i)
+                if (!rb || refined[(size_t)best][i]->lcp > rb->lcp) rb = refined[(size_t)best][i];
+            if (rb) {
+                std::ofstream rf(out_path + ".refined", std::ofstream::out);
+                for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) rf << rb->transform(r, c) << (r == 2 && c == 3 ? "" : " ");
+                rf << std::endl;
+                os << "refined pose:";
+                for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) { char b[32]; snprintf(b, sizeof(b), " %.9g", (double)rb->transform(r, c)); os << b; }
+                os << std::endl;
+            }
         } else {
             os << "no pose found" << std::endl;
         }
@@ -268,7 +300,7 @@ int main(int argc, char** argv) {
         } else { std::cerr << "unknown option " << k << std::endl; return -1; }
     }
 
-    if (n_refine < 0 || (n_refine > 0 && (!do_cluster || n_trials > 0))) { std::cerr << "--refine N needs N >= 0, --cluster 1 and no --trials" << std::endl; return -1; }
+    if (n_refine < 0 || (n_refine > 0 && !do_cluster)) { std::cerr << "--refine N needs N >= 0 and --cluster 1" << std::endl; return -1; }
 
     if (!clouds && a2.find(',') != std::string::npos) {
         std::vector<std::string> objects;

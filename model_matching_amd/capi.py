@@ -34,6 +34,16 @@ class TrialResult(C.Structure):
                 ("best_pose16", C.c_float * 16)]
 
 
+class TrialPost(C.Structure):
+    _fields_ = [("acceptable_fraction", C.c_float), ("maximum_pose_count", C.c_int32), ("min_distance", C.c_float), ("min_angle", C.c_float),
+                ("sym3", C.c_float * 3), ("refine_iterations", C.c_int32), ("max_correspondence_distance", C.c_float)]
+
+
+class TrialHypothesis(C.Structure):
+    _fields_ = [("candidate_index", C.c_int32), ("base_index", C.c_int32), ("lcp", C.c_float), ("pose16", C.c_float * 16),
+                ("refined_lcp", C.c_float), ("refined_pose16", C.c_float * 16), ("n_correspondences", C.c_int32), ("iterations", C.c_int32)]
+
+
 class Camera(C.Structure):
     _fields_ = [("fx", C.c_float), ("cx", C.c_float), ("fy", C.c_float), ("cy", C.c_float), ("depth_scale", C.c_float),
                 ("width", C.c_int), ("height", C.c_int), ("normal_method", C.c_int)]
@@ -91,6 +101,9 @@ SIGNATURES = {
     "stocs_trials_get_bases": (C.c_int, [_vp, C.c_int, _ip, _fp, _ip, C.c_int, _intp]),
     "stocs_trials_get_quad_counts": (C.c_int, [_vp, C.c_int, _i64p, C.c_int, _intp]),
     "stocs_trials_get_candidates": (C.c_int, [_vp, C.c_int, _fp, _fp, _fp, _ip, C.c_int, _intp]),
+    "stocs_run_trials_post": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int, C.c_float, C.c_int, C.c_int, C.POINTER(TrialPost),
+                                        C.POINTER(TrialResult)]),
+    "stocs_trials_get_hypotheses": (C.c_int, [_vp, C.c_int, C.POINTER(TrialHypothesis), C.c_int, _intp]),
     "stocs_best_device": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.POINTER(C.c_uint64)]),
     "stocs_pack_best": (C.c_uint64, [C.c_float, C.c_uint32]),
     "stocs_unpack_best": (None, [C.c_uint64, _fp, C.POINTER(C.c_uint32)]),

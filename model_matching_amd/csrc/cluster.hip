@@ -1,94 +1,130 @@
-// cluster.hip -- host-side pose clustering.  Replaces clustering::greedy_clustering with
-// get_pose_diff and quaternion_to_euler (reference src/pose_clustering.cpp:79-121, 27-71, 5-25).
-// O(K log K + K*C) on at most 20 000 scored candidates: stays on the host, as in the reference
-// (where it has no caller at all).  std::sort in the reference is unstable; a stable sort by
-// descending score is used so that results are reproducible.
+// cluster.hip -- pose clustering.  Replaces clustering::greedy_clustering with get_pose_diff and quaternion_to_euler
+// (reference src/pose_clustering.cpp:79-121, 27-71, 5-25; pose_diff.h).
+// Host (stocs_cluster_poses): O(K log K + K*C) on at most 20 000 scored candidates of one trial, as in the reference (where it has
+// no caller at all).  std::sort in the reference is unstable; a stable sort by descending score is used so that results are
+// reproducible.
+// Device (trial batches, stocs_run_trials_post): the candidates of a batch already sit on the device, so every trial of a piece is
+// clustered there, one workgroup per trial.  The host loop is greedy non-maximum suppression, so no sort is needed: the arg-max of
+// the survivors by (lcp bits, ~local index) -- highest score first, lowest index on ties, std::stable_sort's order -- is the next
+// kept cluster, and every survivor within the thresholds of it (get_pose_diff(survivor, cluster), the host's argument order) drops
+// out.  Same decisions as the host function, rounds = kept clusters.
 #include <math.h>
 
 #include <algorithm>
 #include <vector>
 
+#include "pose_diff.h"
 #include "stocs_ctx.h"
 
 namespace stocs {
 
-struct HM3 { float m[3][3]; };
-static HM3 hmul(const HM3& A, const HM3& B) {
-    HM3 C;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) C.m[i][j] = A.m[i][0] * B.m[0][j] + (A.m[i][1] * B.m[1][j] + A.m[i][2] * B.m[2][j]);
-    return C;
-}
-static HM3 hinverse(const HM3& a) {  // cofactor inverse, as Eigen does for fixed 3x3
-    HM3 r;
-    const float c00 = a.m[1][1] * a.m[2][2] - a.m[1][2] * a.m[2][1];
-    const float c01 = a.m[1][2] * a.m[2][0] - a.m[1][0] * a.m[2][2];
-    const float c02 = a.m[1][0] * a.m[2][1] - a.m[1][1] * a.m[2][0];
-    const float det = a.m[0][0] * c00 + (a.m[0][1] * c01 + a.m[0][2] * c02);
-    const float inv = 1.0f / det;
-    r.m[0][0] = c00 * inv; r.m[1][0] = c01 * inv; r.m[2][0] = c02 * inv;
-    r.m[0][1] = (a.m[0][2] * a.m[2][1] - a.m[0][1] * a.m[2][2]) * inv;
-    r.m[1][1] = (a.m[0][0] * a.m[2][2] - a.m[0][2] * a.m[2][0]) * inv;
-    r.m[2][1] = (a.m[0][1] * a.m[2][0] - a.m[0][0] * a.m[2][1]) * inv;
-    r.m[0][2] = (a.m[0][1] * a.m[1][2] - a.m[0][2] * a.m[1][1]) * inv;
-    r.m[1][2] = (a.m[0][2] * a.m[1][0] - a.m[0][0] * a.m[1][2]) * inv;
-    r.m[2][2] = (a.m[0][0] * a.m[1][1] - a.m[0][1] * a.m[1][0]) * inv;
-    return r;
-}
-static void mat_to_quat(const HM3& a, float q[4] /*x,y,z,w*/) {  // Eigen Quaternion(Matrix3)
-    float t = a.m[0][0] + a.m[1][1] + a.m[2][2];
-    if (t > 0.0f) {
-        t = sqrtf(t + 1.0f);
-        q[3] = 0.5f * t;
-        t = 0.5f / t;
-        q[0] = (a.m[2][1] - a.m[1][2]) * t;
-        q[1] = (a.m[0][2] - a.m[2][0]) * t;
-        q[2] = (a.m[1][0] - a.m[0][1]) * t;
-    } else {
-        int i = 0;
-        if (a.m[1][1] > a.m[0][0]) i = 1;
-        if (a.m[2][2] > a.m[i][i]) i = 2;
-        const int j = (i + 1) % 3, k = (j + 1) % 3;
-        t = sqrtf(a.m[i][i] - a.m[j][j] - a.m[k][k] + 1.0f);
-        q[i] = 0.5f * t;
-        t = 0.5f / t;
-        q[3] = (a.m[k][j] - a.m[j][k]) * t;
-        q[j] = (a.m[j][i] + a.m[i][j]) * t;
-        q[k] = (a.m[k][i] + a.m[i][k]) * t;
-    }
-}
 static void pose_diff(const float* test, const float* base, const float* sym, float& rot_err, float& tr_err) {
-    HM3 t, b;
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) { t.m[i][j] = test[j * 4 + i]; b.m[i][j] = base[j * 4 + i]; }
-    const HM3 diff = hmul(hinverse(t), b);
-    float q[4], e[3];
-    mat_to_quat(diff, q);
-    // quaternion_to_euler, pose_clustering.cpp:5-25 (float products promoted to double)
-    const double sinr = +2.0 * (double)(q[3] * q[0] + q[1] * q[2]);
-    const double cosr = +1.0 - 2.0 * (double)(q[0] * q[0] + q[1] * q[1]);
-    e[0] = (float)atan2(sinr, cosr);
-    const double sinp = +2.0 * (double)(q[3] * q[1] - q[2] * q[0]);
-    if (fabs(sinp) >= 1) e[1] = (float)copysign(M_PI / 2, sinp);
-    else e[1] = (float)asin(sinp);
-    const double siny = +2.0 * (double)(q[3] * q[2] + q[0] * q[1]);
-    const double cosy = +1.0 - 2.0 * (double)(q[1] * q[1] + q[2] * q[2]);
-    e[2] = (float)atan2(siny, cosy);
-    for (int d = 0; d < 3; ++d) {
-        e[d] = (float)((double)e[d] * 180.0 / M_PI);
-        e[d] = fabsf(e[d]);
-        if (sym[d] == 90) {
-            e[d] = fabsf(e[d] - 90);
-            e[d] = std::min(e[d], 90 - e[d]);
-        } else if (sym[d] == 180) {
-            e[d] = std::min(e[d], 180 - e[d]);
-        } else if (sym[d] == 360) {
-            e[d] = 0;
+    rot_err = pose_rot_err(pose_inverse_rotation(test), base, sym);
+    tr_err = pose_trans_err(test, base);
+}
+
+// One workgroup per trial t of a piece.  Survivors: lcp > fraction * best_t (best_t = key hi of trial_best_kernel, the trial's best_lcp;
+// the float product as the host forms it).  Per round, one pass over the survivors drops those the last kept cluster suppresses and
+// takes the arg-max of the rest; the pass is also the suppression test of the round before.  Rounds stop after count + 1 clusters
+// (the host's `size() > count` break) or when no survivor is left.  The translation test comes first: it is cheap, and a survivor it
+// clears needs no rotation (both must hold to suppress).  The first pass reads every candidate; the survivors -- a few dozen per trial
+// at the driver's fraction 0.8 -- go to LDS with their key and translation, and the later rounds walk that list only.  When more than
+// CLUSTER_LDS survive (small fractions), the rounds walk the trial's candidates with a survivor flag per candidate in `alive`.
+// hyp_idx[hyp_off[t] ..] gets the kept local indices in cluster order, hyp_cnt[t] their number (hyp_off[t + 1] - hyp_off[t] =
+// min(count + 1, candidates of t) bounds it).
+static const int CLUSTER_LDS = 2048;
+__global__ __launch_bounds__(256) void trial_cluster_kernel(const float* __restrict__ P, const float* __restrict__ lcp, const int32_t* __restrict__ cand_off,
+                                                            const float* __restrict__ best18, TrialClusterArgs a, uint8_t* __restrict__ alive,
+                                                            const int32_t* __restrict__ hyp_off, int32_t* __restrict__ hyp_cnt, int32_t* __restrict__ hyp_idx) {
+    __shared__ unsigned long long sh[4];
+    __shared__ float acc[16];                       // the last kept cluster's pose
+    __shared__ unsigned long long skey[CLUSTER_LDS];   // survivors: key (0: dropped) ...
+    __shared__ float strans[CLUSTER_LDS][3];           // ... and translation
+    __shared__ int n_surv;
+    const int t = blockIdx.x;
+    const int i0 = cand_off[t], n = cand_off[t + 1] - i0;
+    const int h0 = hyp_off[t], cap = hyp_off[t + 1] - h0;
+    const float thr = a.fraction * best18[(size_t)t * 18 + 1];
+    if (threadIdx.x == 0) n_surv = 0;
+    __syncthreads();
+    int kept = 0, last = -1;
+    bool in_lds = false;
+    while (kept < cap) {
+        unsigned long long k = 0;
+        if (last < 0) {
+            // the survivors (four loads in flight per lane)
+            for (int b = (int)threadIdx.x; b < n; b += 1024) {
+                float v[4];
+#pragma unroll
+                for (int u = 0; u < 4; ++u) v[u] = b + 256 * u < n ? lcp[(size_t)i0 + (size_t)(b + 256 * u)] : 0.0f;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    const int i = b + 256 * u;
+                    if (i >= n) break;
+                    const size_t g = (size_t)i0 + (size_t)i;
+                    const bool live = v[u] > thr;
+                    alive[g] = live ? 1 : 0;
+                    if (!live) continue;
+                    const unsigned long long key = ((unsigned long long)__float_as_uint(v[u]) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)i);
+                    k = key > k ? key : k;
+                    const int slot = atomicAdd(&n_surv, 1);
+                    if (slot < CLUSTER_LDS) {
+                        skey[slot] = key;
+                        for (int d = 0; d < 3; ++d) strans[slot][d] = P[g * 16 + 12 + d];
+                    }
+                }
+            }
+        } else if (in_lds) {
+            for (int j = (int)threadIdx.x; j < n_surv; j += 256) {
+                const unsigned long long key = skey[j];
+                if (!key) continue;
+                const int i = (int)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull));
+                bool live = i != last;
+                if (live && pose_trans_err3(strans[j], acc + 12) < a.min_distance &&
+                    pose_rot_err(pose_inverse_rotation(P + ((size_t)i0 + (size_t)i) * 16), acc, a.sym) < a.min_angle)
+                    live = false;
+                if (!live) skey[j] = 0;
+                else k = key > k ? key : k;
+            }
+        } else {
+            for (int i = (int)threadIdx.x; i < n; i += 256) {
+                const size_t g = (size_t)i0 + (size_t)i;
+                if (!alive[g]) continue;
+                bool live = i != last;
+                if (live) {
+                    const float* p = P + g * 16;
+                    if (pose_trans_err(p, acc) < a.min_distance && pose_rot_err(pose_inverse_rotation(p), acc, a.sym) < a.min_angle) live = false;
+                }
+                if (!live) alive[g] = 0;
+                else {
+                    const unsigned long long key = ((unsigned long long)__float_as_uint(lcp[g]) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)i);
+                    k = key > k ? key : k;
+                }
+            }
         }
+        for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(k, off, 64); k = o > k ? o : k; }
+        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = k;
+        __syncthreads();   // (also: the survivor list of the first pass is complete)
+        for (int w = 0; w < 4; ++w) k = sh[w] > k ? sh[w] : k;
+        if (!k) break;   // (uniform: every thread took the same maximum)
+        if (last < 0) in_lds = n_surv <= CLUSTER_LDS;
+        last = (int)(0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFull));
+        if (threadIdx.x == 0) hyp_idx[h0 + kept] = last;
+        if (threadIdx.x < 16) acc[threadIdx.x] = P[((size_t)i0 + (size_t)last) * 16 + threadIdx.x];
+        ++kept;
+        __syncthreads();   // acc written, sh read by all
+        if (kept > a.count) break;   // sic: size > count
     }
-    rot_err = std::max(std::max(e[0], e[1]), e[2]);
-    tr_err = (float)sqrt(pow((double)(base[12] - test[12]), 2) + pow((double)(base[13] - test[13]), 2) +
-                         pow((double)(base[14] - test[14]), 2));
+    if (threadIdx.x == 0) hyp_cnt[t] = kept;
+}
+
+int enqueue_trial_cluster(stocs_ctx* c, int n_trials, const float* d_P, const float* d_lcp, const int32_t* d_cand_off, const float* d_best18,
+                          const TrialClusterArgs& a, uint8_t* d_alive, const int32_t* d_hyp_off, int32_t* d_hyp_cnt, int32_t* d_hyp_idx) {
+    if (n_trials <= 0) return STOCS_OK;
+    hipLaunchKernelGGL(trial_cluster_kernel, dim3((unsigned)n_trials), dim3(256), 0, c->stream, d_P, d_lcp, d_cand_off, d_best18, a, d_alive, d_hyp_off,
+                       d_hyp_cnt, d_hyp_idx);
+    STOCS_HIP_CHECK(hipGetLastError());
+    return STOCS_OK;
 }
 
 }  // namespace stocs

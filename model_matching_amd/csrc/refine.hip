@@ -145,7 +145,8 @@ STOCS_HD bool solve6(double A[6][6], double b[6], double x[6]) {
     return true;
 }
 
-__global__ __launch_bounds__(64) void refine_init_kernel(const float* __restrict__ Tin, int n, RefHyp* __restrict__ hyp) {
+// live != NULL: hypothesis k takes part only when live[k] (the unused slots of a trial batch's hypotheses start frozen)
+__global__ __launch_bounds__(64) void refine_init_kernel(const float* __restrict__ Tin, int n, const int32_t* __restrict__ live, RefHyp* __restrict__ hyp) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
     if (k >= n) return;
     const float* T = Tin + (size_t)k * 16;
@@ -155,7 +156,7 @@ __global__ __launch_bounds__(64) void refine_init_kernel(const float* __restrict
     const bool ok = inv34(M, h.Tinv);
     if (!ok) for (int i = 0; i < 12; ++i) h.Tinv[i] = 0.0;
     for (int i = 0; i < 12; ++i) h.U[i] = (i % 5 == 0) ? 1.0 : 0.0;
-    h.ncorr = 0; h.iters = 0; h.frozen = ok ? 0 : 1; h.pad = 0;
+    h.ncorr = 0; h.iters = 0; h.frozen = ok && (!live || live[k]) ? 0 : 1; h.pad = 0;
     hyp[k] = h;
 }
 
@@ -402,6 +403,86 @@ static int build_refine_grid(stocs_ctx* c, RefineState* S, float d) {
     return STOCS_OK;
 }
 
+// the model grid for the distance and the grow-only workspace of n hypotheses over nsrc source points (may synchronise when either
+// has to be (re)built or grown; nothing of the workspace may be in flight then)
+int refine_prepare(stocs_ctx* c, int n, int nsrc, float max_correspondence_distance, RefineWork* w) {
+    const int nchunks = (nsrc + REFINE_CHUNK - 1) / REFINE_CHUNK;
+    if ((int64_t)n * std::max(nchunks, 1) >= ((int64_t)1 << 31)) { set_error("stocs_refine_poses: %d hypotheses x %d chunks: too many workgroups", n, nchunks); return STOCS_ERR_INVALID; }
+    if (!c->refine) {
+        RefineState* S = new RefineState();
+        memset(S, 0, sizeof(*S));
+        c->refine = S;
+    }
+    RefineState* S = (RefineState*)c->refine;
+    if (S->g.dist != max_correspondence_distance) {
+        const int rc = build_refine_grid(c, S, max_correspondence_distance);
+        if (rc) { S->g.dist = 0.0f; return rc; }
+    }
+    // device block: hypotheses | T in | source indices | partials | T out | P out | lcp | n_corr | iterations
+    const size_t hb = al256((size_t)n * sizeof(RefHyp)), tb = al256((size_t)n * 64), ib = al256((size_t)std::max(nsrc, 1) * 4);
+    const size_t pb = al256((size_t)n * std::max(nchunks, 1) * 28 * 8);
+    const size_t out_bytes = (size_t)n * (64 + 64 + 4 + 4 + 4);
+    const size_t need = hb + tb + ib + pb + al256(out_bytes);
+    if (S->work_bytes < need) {
+        if (S->d_work) { STOCS_HIP_CHECK(hipStreamSynchronize(c->stream)); (void)hipFree(S->d_work); S->d_work = NULL; S->work_bytes = 0; }
+        STOCS_HIP_CHECK(dev_malloc(&S->d_work, need + need / 4));
+        S->work_bytes = need + need / 4;
+    }
+    char* p = S->d_work;
+    w->d_hyp = p; p += hb;
+    w->d_Tin = (float*)p; p += tb;
+    w->d_idx = (int32_t*)p; p += ib;
+    w->d_part = (double*)p; p += pb;
+    w->d_Tout = (float*)p;
+    w->d_Pout = w->d_Tout + (size_t)n * 16;
+    w->d_lcp = w->d_Pout + (size_t)n * 16;
+    w->d_nc = (int32_t*)(w->d_lcp + n);
+    w->d_it = w->d_nc + n;
+    w->out_bytes = out_bytes;
+    w->n = n; w->nsrc = nsrc; w->nchunks = nchunks;
+    return STOCS_OK;
+}
+
+// init, max_iterations x (accumulate, solve), final, the LCP launch -- on the stream, no copy, no synchronisation.  Input: w.d_Tin
+// (n centred T16); the source is w.d_idx[0 .. nsrc) when use_idx, else every scene point; live: see refine_init_kernel.  The LCP
+// launch follows the context's scoring state (c->snrmw_override / c->lcp_cand_trial of an instance-mode batch included)
+int refine_enqueue(stocs_ctx* c, const RefineWork& w, bool use_idx, const int32_t* d_live, int max_iterations, float max_correspondence_distance) {
+    RefineState* S = (RefineState*)c->refine;
+    const int n = w.n, nchunks = w.nchunks;
+    RefHyp* d_hyp = (RefHyp*)w.d_hyp;
+    const unsigned hblocks = (unsigned)((n + 63) / 64);
+    hipLaunchKernelGGL(refine_init_kernel, dim3(hblocks), dim3(64), 0, c->stream, (const float*)w.d_Tin, n, d_live, d_hyp);
+    STOCS_HIP_CHECK(hipGetLastError());
+    RefArgs a;
+    a.spos = c->d_spos; a.idx = use_idx ? w.d_idx : NULL; a.nsrc = w.nsrc; a.nchunks = nchunks; a.nM = c->nM; a.nsub = 8 * S->g.nx * S->g.ny * S->g.nz;
+    a.octants = c->nM >= REFINE_OCTANT_DENSITY * S->g.nx * S->g.ny * S->g.nz ? 1 : 0;
+    a.off = S->g.d_off; a.gpos = S->g.d_pos; a.mpos = c->d_mpos; a.mnrm = c->d_mnrm;
+    a.ox = S->g.ox; a.oy = S->g.oy; a.oz = S->g.oz; a.inv_h = S->g.inv_h;
+    a.nx = S->g.nx; a.ny = S->g.ny; a.nz = S->g.nz;
+    a.lox = S->g.lo[0]; a.loy = S->g.lo[1]; a.loz = S->g.lo[2]; a.hix = S->g.hi[0]; a.hiy = S->g.hi[1]; a.hiz = S->g.hi[2];
+    a.max_d2 = (double)max_correspondence_distance * (double)max_correspondence_distance;
+    a.max_d2_f = (float)(a.max_d2 * (1.0 + 1e-5));
+    a.h2 = S->g.h * S->g.h;
+    a.margin_u = 1e-3f + 1e-6f * (float)std::max(S->g.nx, std::max(S->g.ny, S->g.nz));
+    const size_t lds_bytes = (size_t)c->nM * 16 + ((size_t)a.nsub + 1) * 4;
+    for (int it = 0; it < max_iterations; ++it) {
+        if (nchunks > 0) {
+            if (lds_bytes <= REFINE_LDS_BYTES)
+                hipLaunchKernelGGL(refine_accumulate_kernel<true>, dim3((unsigned)(n * nchunks)), dim3(REFINE_CHUNK), lds_bytes, c->stream, a,
+                                   (const RefHyp*)d_hyp, w.d_part);
+            else
+                hipLaunchKernelGGL(refine_accumulate_kernel<false>, dim3((unsigned)(n * nchunks)), dim3(REFINE_CHUNK), 0, c->stream, a, (const RefHyp*)d_hyp, w.d_part);
+            STOCS_HIP_CHECK(hipGetLastError());
+        }
+        hipLaunchKernelGGL(refine_solve_kernel, dim3((unsigned)n), dim3(64), 0, c->stream, d_hyp, (const double*)w.d_part, nchunks);
+        STOCS_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(refine_final_kernel, dim3(hblocks), dim3(64), 0, c->stream, (const float*)w.d_Tin, (const RefHyp*)d_hyp, n, c->centroid_scene,
+                       c->centroid_model, w.d_Tout, w.d_Pout, w.d_nc, w.d_it);
+    STOCS_HIP_CHECK(hipGetLastError());
+    return launch_lcp(c, w.d_Tout, n, w.d_lcp, NULL, NULL, NULL, 0);
+}
+
 }  // namespace stocs
 
 using namespace stocs;
@@ -432,41 +513,19 @@ extern "C" int stocs_refine_poses(stocs_ctx* c, const float* T16_in, int n, cons
             if (src_idx[i] < 0 || src_idx[i] >= c->nS) { set_error("stocs_refine_poses: src_idx[%d] = %d outside [0, %d)", i, src_idx[i], c->nS); return STOCS_ERR_INVALID; }
     if (n == 0) return STOCS_OK;
     const int nsrc = src_idx ? n_src : c->nS;
-    const int nchunks = (nsrc + REFINE_CHUNK - 1) / REFINE_CHUNK;
-    if ((int64_t)n * std::max(nchunks, 1) >= ((int64_t)1 << 31)) { set_error("stocs_refine_poses: %d hypotheses x %d chunks: too many workgroups", n, nchunks); return STOCS_ERR_INVALID; }
+    {
+        const int nchunks = (nsrc + REFINE_CHUNK - 1) / REFINE_CHUNK;
+        if ((int64_t)n * std::max(nchunks, 1) >= ((int64_t)1 << 31)) { set_error("stocs_refine_poses: %d hypotheses x %d chunks: too many workgroups", n, nchunks); return STOCS_ERR_INVALID; }
+    }
     DeviceGuard dev_guard(c->device);
     begin_scoring_call(c);
-    if (!c->refine) {
-        RefineState* S = new RefineState();
-        memset(S, 0, sizeof(*S));
-        c->refine = S;
+    RefineWork w;
+    {
+        const int rc = refine_prepare(c, n, nsrc, max_correspondence_distance, &w);
+        if (rc) return rc;
     }
-    RefineState* S = (RefineState*)c->refine;
-    if (S->g.dist != max_correspondence_distance) {
-        const int rc = build_refine_grid(c, S, max_correspondence_distance);
-        if (rc) { S->g.dist = 0.0f; return rc; }
-    }
-    // device block: hypotheses | T in | source indices | partials | T out | P out | lcp | n_corr | iterations
-    const size_t hb = al256((size_t)n * sizeof(RefHyp)), tb = al256((size_t)n * 64), ib = al256((size_t)std::max(nsrc, 1) * 4);
-    const size_t pb = al256((size_t)n * std::max(nchunks, 1) * 28 * 8);
-    const size_t out_bytes = (size_t)n * (64 + 64 + 4 + 4 + 4);
-    const size_t need = hb + tb + ib + pb + al256(out_bytes);
-    if (S->work_bytes < need) {
-        if (S->d_work) { STOCS_HIP_CHECK(hipStreamSynchronize(c->stream)); (void)hipFree(S->d_work); S->d_work = NULL; S->work_bytes = 0; }
-        STOCS_HIP_CHECK(dev_malloc(&S->d_work, need + need / 4));
-        S->work_bytes = need + need / 4;
-    }
-    char* p = S->d_work;
-    RefHyp* d_hyp = (RefHyp*)p; p += hb;
-    float* d_Tin = (float*)p; p += tb;
-    int32_t* d_idx = (int32_t*)p; p += ib;
-    double* d_part = (double*)p; p += pb;
-    float* d_Tout = (float*)p;
-    float* d_Pout = d_Tout + (size_t)n * 16;
-    float* d_lcp = d_Pout + (size_t)n * 16;
-    int32_t* d_nc = (int32_t*)(d_lcp + n);
-    int32_t* d_it = d_nc + n;
     // inputs and outputs go through the context's pinned block (grown only when this call needs more than it has)
+    const size_t out_bytes = w.out_bytes;
     const size_t in_bytes = al256((size_t)n * 64) + al256((size_t)(src_idx ? nsrc : 0) * 4);
     const size_t pin_need = (size_t)PIN_VAR + in_bytes + al256(out_bytes);
     if (c->pin_bytes < pin_need) {
@@ -478,43 +537,13 @@ extern "C" int stocs_refine_poses(stocs_ctx* c, const float* T16_in, int n, cons
     char* hout = hin + in_bytes;
     memcpy(hin, T16_in, (size_t)n * 64);
     if (src_idx && nsrc) memcpy(hin + al256((size_t)n * 64), src_idx, (size_t)nsrc * 4);
-    STOCS_HIP_CHECK(hipMemcpyAsync(d_Tin, hin, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));
-    if (src_idx && nsrc) STOCS_HIP_CHECK(hipMemcpyAsync(d_idx, hin + al256((size_t)n * 64), (size_t)nsrc * 4, hipMemcpyHostToDevice, c->stream));
-    const unsigned hblocks = (unsigned)((n + 63) / 64);
-    hipLaunchKernelGGL(refine_init_kernel, dim3(hblocks), dim3(64), 0, c->stream, d_Tin, n, d_hyp);
-    STOCS_HIP_CHECK(hipGetLastError());
-    RefArgs a;
-    a.spos = c->d_spos; a.idx = src_idx ? d_idx : NULL; a.nsrc = nsrc; a.nchunks = nchunks; a.nM = c->nM; a.nsub = 8 * S->g.nx * S->g.ny * S->g.nz;
-    a.octants = c->nM >= REFINE_OCTANT_DENSITY * S->g.nx * S->g.ny * S->g.nz ? 1 : 0;
-    a.off = S->g.d_off; a.gpos = S->g.d_pos; a.mpos = c->d_mpos; a.mnrm = c->d_mnrm;
-    a.ox = S->g.ox; a.oy = S->g.oy; a.oz = S->g.oz; a.inv_h = S->g.inv_h;
-    a.nx = S->g.nx; a.ny = S->g.ny; a.nz = S->g.nz;
-    a.lox = S->g.lo[0]; a.loy = S->g.lo[1]; a.loz = S->g.lo[2]; a.hix = S->g.hi[0]; a.hiy = S->g.hi[1]; a.hiz = S->g.hi[2];
-    a.max_d2 = (double)max_correspondence_distance * (double)max_correspondence_distance;
-    a.max_d2_f = (float)(a.max_d2 * (1.0 + 1e-5));
-    a.h2 = S->g.h * S->g.h;
-    a.margin_u = 1e-3f + 1e-6f * (float)std::max(S->g.nx, std::max(S->g.ny, S->g.nz));
-    const size_t lds_bytes = (size_t)c->nM * 16 + ((size_t)a.nsub + 1) * 4;
-    for (int it = 0; it < max_iterations; ++it) {
-        if (nchunks > 0) {
-            if (lds_bytes <= REFINE_LDS_BYTES)
-                hipLaunchKernelGGL(refine_accumulate_kernel<true>, dim3((unsigned)(n * nchunks)), dim3(REFINE_CHUNK), lds_bytes, c->stream, a,
-                                   (const RefHyp*)d_hyp, d_part);
-            else
-                hipLaunchKernelGGL(refine_accumulate_kernel<false>, dim3((unsigned)(n * nchunks)), dim3(REFINE_CHUNK), 0, c->stream, a, (const RefHyp*)d_hyp, d_part);
-            STOCS_HIP_CHECK(hipGetLastError());
-        }
-        hipLaunchKernelGGL(refine_solve_kernel, dim3((unsigned)n), dim3(64), 0, c->stream, d_hyp, (const double*)d_part, nchunks);
-        STOCS_HIP_CHECK(hipGetLastError());
-    }
-    hipLaunchKernelGGL(refine_final_kernel, dim3(hblocks), dim3(64), 0, c->stream, (const float*)d_Tin, (const RefHyp*)d_hyp, n, c->centroid_scene,
-                       c->centroid_model, d_Tout, d_Pout, d_nc, d_it);
-    STOCS_HIP_CHECK(hipGetLastError());
+    STOCS_HIP_CHECK(hipMemcpyAsync(w.d_Tin, hin, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));
+    if (src_idx && nsrc) STOCS_HIP_CHECK(hipMemcpyAsync(w.d_idx, hin + al256((size_t)n * 64), (size_t)nsrc * 4, hipMemcpyHostToDevice, c->stream));
     {
-        const int rc = launch_lcp(c, d_Tout, n, d_lcp, NULL, NULL, NULL, 0);
+        const int rc = refine_enqueue(c, w, src_idx != NULL, NULL, max_iterations, max_correspondence_distance);
         if (rc) return rc;
     }
-    STOCS_HIP_CHECK(hipMemcpyAsync(hout, d_Tout, out_bytes, hipMemcpyDeviceToHost, c->stream));
+    STOCS_HIP_CHECK(hipMemcpyAsync(hout, w.d_Tout, out_bytes, hipMemcpyDeviceToHost, c->stream));
     STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
     const char* o = hout;
     if (T16_out) memcpy(T16_out, o, (size_t)n * 64);

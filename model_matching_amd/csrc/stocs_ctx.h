@@ -347,6 +347,19 @@ enum { PIN_CONGRUENT = 0, PIN_TRANSFORMS = 256, PIN_VERIFY = 512, PIN_BEST = 768
 int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d_hit, uint8_t* d_counted, unsigned long long* d_best8, uint32_t id_offset);
 // every scoring entry point calls this first: the tie counters of stocs_last_tie_counts then cover that call alone (no device work)
 inline void begin_scoring_call(stocs_ctx* c) { c->ties_started = false; }
+// refine.hip: stocs_refine_poses as an enqueue step on device-resident hypotheses (the trial batches' post-processing uses it)
+struct RefineWork {
+    void* d_hyp; float* d_Tin; int32_t* d_idx; double* d_part;   // d_Tin: the n centred T16 to refine; d_idx: nsrc source indices
+    float* d_Tout; float* d_Pout; float* d_lcp; int32_t* d_nc; int32_t* d_it;   // contiguous outputs, out_bytes in all
+    size_t out_bytes;
+    int n, nsrc, nchunks;
+};
+int refine_prepare(stocs_ctx* c, int n, int nsrc, float max_correspondence_distance, RefineWork* w);
+int refine_enqueue(stocs_ctx* c, const RefineWork& w, bool use_idx, const int32_t* d_live, int max_iterations, float max_correspondence_distance);
+// cluster.hip: greedy_clustering of every trial of a batch piece on the device (see there); no synchronisation
+struct TrialClusterArgs { float fraction; int32_t count; float min_distance, min_angle; float sym[3]; };
+int enqueue_trial_cluster(stocs_ctx* c, int n_trials, const float* d_P, const float* d_lcp, const int32_t* d_cand_off, const float* d_best18,
+                          const TrialClusterArgs& a, uint8_t* d_alive, const int32_t* d_hyp_off, int32_t* d_hyp_cnt, int32_t* d_hyp_idx);
 int ensure_kdtree(stocs_ctx* c);   // kdtree.hip: the kd-tree of the current scene on the device (exact_ties); synchronises
 int sample_trials(stocs_ctx* c, int mode, int nT, const uint64_t* seeds, int nA, float dispersion, BaseOut* res_host, const float4** snrmw0, size_t* snrmw_stride);   // sample.hip
 int build_ppf_index(stocs_ctx* c);

@@ -37,6 +37,8 @@ struct TrialBatch {
     std::vector<std::vector<long long> > quads;                 // per trial: congruent sets of each valid base
     std::vector<std::vector<float> > T, P, lcp;                 // per trial, when details are kept
     std::vector<std::vector<int32_t> > cbase;
+    bool post = false;                                          // the batch ran with post-processing (stocs_run_trials_post)
+    std::vector<std::vector<stocs_trial_hypothesis> > hyps;     // per trial: its kept hypotheses, in cluster order
     int pieces = 0;
 };
 
@@ -77,7 +79,68 @@ __global__ __launch_bounds__(256) void cand_trial_kernel(const int32_t* __restri
     out[i] = first_trial + lo;
 }
 
+// slot s of the piece's hypotheses -> its trial (last t with hyp_off[t] <= s) and its rank k there.  A slot below the trial's count
+// gets the kept candidate's record (refined fields = the candidate's; refine_trial_hyp_kernel overwrites them after a refinement);
+// with Tin != NULL also the refinement's input: the candidate's centred T16, or for an unused slot a pose parked far outside the scene
+// and the model (refine_init_kernel freezes it, every LCP query of it misses at the first bounds test) -- the slots are sized before
+// the counts are known, and the piece keeps its one synchronisation
+__global__ __launch_bounds__(256) void trial_hyp_gather_kernel(const float* __restrict__ T, const float* __restrict__ P, const float* __restrict__ lcp,
+                                                               const int32_t* __restrict__ cbase, const int32_t* __restrict__ cand_off,
+                                                               const int32_t* __restrict__ hyp_off, const int32_t* __restrict__ hyp_cnt,
+                                                               const int32_t* __restrict__ hyp_idx, int n_trials, int first_trial, int H,
+                                                               stocs_trial_hypothesis* __restrict__ rec, float* __restrict__ Tin, int32_t* __restrict__ live,
+                                                               int32_t* __restrict__ slot_trial) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= H) return;
+    int lo = 0, hi = n_trials - 1;
+    while (lo < hi) { const int mid = (lo + hi + 1) >> 1; if (hyp_off[mid] <= s) lo = mid; else hi = mid - 1; }
+    const int t = lo, k = s - hyp_off[t];
+    const bool on = k < hyp_cnt[t];
+    const int id = on ? hyp_idx[s] : 0;
+    const size_t g = (size_t)cand_off[t] + (size_t)id;
+    if (on) {
+        stocs_trial_hypothesis& r = rec[s];
+        r.candidate_index = id; r.base_index = cbase[g]; r.lcp = lcp[g]; r.refined_lcp = lcp[g];
+        for (int i = 0; i < 16; ++i) { const float v = P[g * 16 + i]; r.pose16[i] = v; r.refined_pose16[i] = v; }
+        r.n_correspondences = 0; r.iterations = 0;
+    }
+    if (Tin) {
+        for (int i = 0; i < 16; ++i) Tin[(size_t)s * 16 + i] = on ? T[g * 16 + i] : (i % 5 == 0 ? 1.0f : (i >= 12 && i < 15 ? 1.0e4f : 0.0f));
+        live[s] = on ? 1 : 0;
+        slot_trial[s] = first_trial + t;
+    }
+}
+
+__global__ __launch_bounds__(256) void refine_trial_hyp_kernel(const int32_t* __restrict__ live, int H, const float* __restrict__ Pout, const float* __restrict__ lcp_out,
+                                                               const int32_t* __restrict__ nc, const int32_t* __restrict__ it, stocs_trial_hypothesis* __restrict__ rec) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= H || !live[s]) return;
+    stocs_trial_hypothesis& r = rec[s];
+    for (int i = 0; i < 16; ++i) r.refined_pose16[i] = Pout[(size_t)s * 16 + i];
+    r.refined_lcp = lcp_out[s]; r.n_correspondences = nc[s]; r.iterations = it[s];
+}
+
 static double now_ms() { return CallTiming::now_s() * 1e3; }
+
+static int check_post(const stocs_trial_post* p) {
+    if (!p) return STOCS_OK;
+    if (p->maximum_pose_count < 0) { set_error("stocs_run_trials_post: maximum_pose_count %d < 0", p->maximum_pose_count); return STOCS_ERR_INVALID; }
+    if (p->refine_iterations < 0) { set_error("stocs_run_trials_post: refine_iterations %d < 0", p->refine_iterations); return STOCS_ERR_INVALID; }
+    if (p->acceptable_fraction != p->acceptable_fraction) { set_error("stocs_run_trials_post: acceptable_fraction is NaN"); return STOCS_ERR_INVALID; }
+    if (!(p->min_distance > 0.0f) || !isfinite(p->min_distance)) {
+        set_error("stocs_run_trials_post: min_distance %g must be positive and finite", (double)p->min_distance);
+        return STOCS_ERR_INVALID;
+    }
+    if (!(p->min_angle > 0.0f) || !isfinite(p->min_angle)) {
+        set_error("stocs_run_trials_post: min_angle %g must be positive and finite", (double)p->min_angle);
+        return STOCS_ERR_INVALID;
+    }
+    if (!(p->max_correspondence_distance > 0.0f) || !isfinite(p->max_correspondence_distance)) {
+        set_error("stocs_run_trials_post: max_correspondence_distance %g must be positive and finite", (double)p->max_correspondence_distance);
+        return STOCS_ERR_INVALID;
+    }
+    return STOCS_OK;
+}
 
 }  // namespace stocs
 
@@ -91,7 +154,13 @@ void stocs_internal_free_trials(stocs_ctx* c) {
 
 int stocs_run_trials(stocs_ctx* c, int mode, int n_trials, const uint64_t* seeds, int n_attempts, float dispersion, int max_per_base, int keep_details,
                      stocs_trial_result* out) {
+    return stocs_run_trials_post(c, mode, n_trials, seeds, n_attempts, dispersion, max_per_base, keep_details, NULL, out);
+}
+
+int stocs_run_trials_post(stocs_ctx* c, int mode, int n_trials, const uint64_t* seeds, int n_attempts, float dispersion, int max_per_base, int keep_details,
+                          const stocs_trial_post* post, stocs_trial_result* out) {
     if (!c || n_trials < 0 || n_attempts < 0 || max_per_base <= 0 || (mode != 0 && mode != 1) || (n_trials && !seeds)) return STOCS_ERR_INVALID;
+    if (check_post(post)) return STOCS_ERR_INVALID;
     DeviceGuard dev_guard(c->device);
     begin_scoring_call(c);
     const double t_entry = now_ms();
@@ -114,6 +183,8 @@ int stocs_run_trials(stocs_ctx* c, int mode, int n_trials, const uint64_t* seeds
     B->quads.assign((size_t)nT, std::vector<long long>());
     B->T.assign((size_t)nT, std::vector<float>()); B->P = B->T; B->lcp = B->T;
     B->cbase.assign((size_t)nT, std::vector<int32_t>());
+    B->post = post != NULL;
+    B->hyps.assign(post ? (size_t)nT : 0, std::vector<stocs_trial_hypothesis>());
     for (int t = 0; t < nT; ++t) { memset(&B->out[(size_t)t], 0, sizeof(stocs_trial_result)); B->out[(size_t)t].best_index = -1; }
     CallTiming& TM = c->timing[3];
     TM.begin();
@@ -154,6 +225,7 @@ int stocs_run_trials(stocs_ctx* c, int mode, int n_trials, const uint64_t* seeds
     // marked invalid) instead of returning from the middle of the loop with a half-filled record that the getters would serve.
 #define TRIALS_HIP_TRY(expr) { const hipError_t e_ = (expr); if (e_ != hipSuccess) { set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e_)); rc = STOCS_ERR_HIP; break; } }
     int rc = STOCS_OK;
+    std::vector<int32_t> hyp_off;
     for (int t0 = 0; t0 < nT && !rc;) {
         int t1 = t0;
         long long nb = 0;
@@ -203,17 +275,43 @@ int stocs_run_trials(stocs_ctx* c, int mode, int n_trials, const uint64_t* seeds
             // scratch of this step (the transform jobs of the piece are done with the area): per-trial candidate offsets | per-trial
             // results | (instance mode) the trial of every candidate
             const bool per_trial_weights = mode == 1 && snrmw0 != NULL;
+            // post-processing: per trial min(count + 1, its candidates) hypothesis slots (the counts come back with the read-back)
+            hyp_off.assign(post ? (size_t)nTp + 1 : 0, 0);
+            for (int t = 0; post && t < nTp; ++t)
+                hyp_off[(size_t)t + 1] = hyp_off[(size_t)t] + (int32_t)std::min<long long>((long long)post->maximum_pose_count + 1,
+                                                                                          (long long)(c->trial_cand_off[(size_t)t + 1] - c->trial_cand_off[(size_t)t]));
+            const int H = post ? hyp_off[(size_t)nTp] : 0;
+            const bool refine = post && post->refine_iterations > 0 && H > 0;
+            auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
+            // scratch: per-trial candidate offsets | per-trial results [| hypothesis counts | hypothesis records] | (instance mode) the
+            // trial of every candidate [| survivor flags | hypothesis offsets | kept indices | slot trial | slot live]
             const size_t ob = (((size_t)nTp + 1) * 4 + 255) & ~(size_t)255, rb = (((size_t)nTp * 18 * 4) + 255) & ~(size_t)255,
                          tb = per_trial_weights ? (((size_t)n_cand * 4 + 255) & ~(size_t)255) : 0;
-            if ((rc = ensure_scratch(c, ob + rb + tb + 256))) break;
-            if ((rc = ensure_pinned(c, (size_t)PIN_VAR + ob + rb + 256))) break;
+            const size_t cb = post ? al((size_t)nTp * 4) : 0, hb = post ? al((size_t)H * sizeof(stocs_trial_hypothesis)) : 0;
+            const size_t fb = post ? al((size_t)n_cand) : 0, hob = post ? al(((size_t)nTp + 1) * 4) : 0, ib = post ? al((size_t)H * 4) : 0;
+            const size_t sb = refine ? al((size_t)H * 4) : 0;
+            if ((rc = ensure_scratch(c, ob + rb + cb + hb + tb + fb + hob + ib + 2 * sb + 256))) break;
+            if ((rc = ensure_pinned(c, (size_t)PIN_VAR + ob + rb + cb + hb + hob + 256))) break;
             int32_t* d_off = (int32_t*)c->d_scratch;
             float* d_out = (float*)((char*)c->d_scratch + ob);
-            int32_t* d_ct = (int32_t*)((char*)c->d_scratch + ob + rb);
+            int32_t* d_hcnt = (int32_t*)((char*)c->d_scratch + ob + rb);
+            stocs_trial_hypothesis* d_hrec = (stocs_trial_hypothesis*)((char*)c->d_scratch + ob + rb + cb);
+            int32_t* d_ct = (int32_t*)((char*)c->d_scratch + ob + rb + cb + hb);
+            char* d_post = (char*)c->d_scratch + ob + rb + cb + hb + tb;
+            uint8_t* d_alive = (uint8_t*)d_post;
+            int32_t* d_hoff = (int32_t*)(d_post + fb);
+            int32_t* d_hidx = (int32_t*)(d_post + fb + hob);
+            int32_t* d_strial = (int32_t*)(d_post + fb + hob + ib);
+            int32_t* d_slive = (int32_t*)(d_post + fb + hob + ib + sb);
             int32_t* off_pin = (int32_t*)((char*)c->h_pin + PIN_VAR);
             float* out_pin = (float*)((char*)c->h_pin + PIN_VAR + ob);
+            int32_t* hoff_pin = (int32_t*)((char*)c->h_pin + PIN_VAR + ob + rb + cb + hb);
             memcpy(off_pin, c->trial_cand_off.data(), 4 * ((size_t)nTp + 1));
             TRIALS_HIP_TRY(hipMemcpyAsync(d_off, off_pin, 4 * ((size_t)nTp + 1), hipMemcpyHostToDevice, c->stream));
+            if (post) {
+                memcpy(hoff_pin, hyp_off.data(), 4 * ((size_t)nTp + 1));
+                TRIALS_HIP_TRY(hipMemcpyAsync(d_hoff, hoff_pin, 4 * ((size_t)nTp + 1), hipMemcpyHostToDevice, c->stream));
+            }
             if (!per_trial_weights) {
                 if ((rc = launch_lcp(c, cand_T(c), n_cand, cand_lcp(c), NULL, NULL, NULL, 0))) break;
             } else {
@@ -228,9 +326,45 @@ int stocs_run_trials(stocs_ctx* c, int mode, int n_trials, const uint64_t* seeds
             }
             hipLaunchKernelGGL(trial_best_kernel, dim3((unsigned)nTp), dim3(256), 0, c->stream, (const float*)cand_lcp(c), (const float*)cand_P(c), (const int32_t*)d_off, d_out);
             TRIALS_HIP_TRY(hipGetLastError());
-            TRIALS_HIP_TRY(hipMemcpyAsync(out_pin, d_out, (size_t)nTp * 18 * 4, hipMemcpyDeviceToHost, c->stream));
+            if (post) {
+                // ---- post-processing of the piece: greedy_clustering of every trial, then (refine_iterations > 0) the point-to-plane
+                //      refinement of every kept hypothesis of the piece in one enqueue, on the whole scene ----
+                TrialClusterArgs ca;
+                ca.fraction = post->acceptable_fraction; ca.count = post->maximum_pose_count; ca.min_distance = post->min_distance; ca.min_angle = post->min_angle;
+                for (int d = 0; d < 3; ++d) ca.sym[d] = post->sym3[d];
+                if ((rc = enqueue_trial_cluster(c, nTp, cand_P(c), cand_lcp(c), d_off, d_out, ca, d_alive, d_hoff, d_hcnt, d_hidx))) break;
+                RefineWork w;
+                if (refine && (rc = refine_prepare(c, H, c->nS, post->max_correspondence_distance, &w))) break;
+                if (H > 0) {
+                    hipLaunchKernelGGL(trial_hyp_gather_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, c->stream, (const float*)cand_T(c),
+                                       (const float*)cand_P(c), (const float*)cand_lcp(c), (const int32_t*)cand_base(c), (const int32_t*)d_off,
+                                       (const int32_t*)d_hoff, (const int32_t*)d_hcnt, (const int32_t*)d_hidx, nTp, t0, H, d_hrec, refine ? w.d_Tin : NULL,
+                                       d_slive, d_strial);
+                    TRIALS_HIP_TRY(hipGetLastError());
+                }
+                if (refine) {
+                    // instance mode: hypothesis s rescored against the weights of its own trial, as the scoring launch above
+                    if (per_trial_weights) { c->snrmw_override = snrmw0; c->lcp_cand_trial = d_strial; }
+                    rc = refine_enqueue(c, w, false, d_slive, post->refine_iterations, post->max_correspondence_distance);
+                    c->snrmw_override = NULL; c->lcp_cand_trial = NULL;
+                    if (rc) break;
+                    hipLaunchKernelGGL(refine_trial_hyp_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, c->stream, (const int32_t*)d_slive, H,
+                                       (const float*)w.d_Pout, (const float*)w.d_lcp, (const int32_t*)w.d_nc, (const int32_t*)w.d_it, d_hrec);
+                    TRIALS_HIP_TRY(hipGetLastError());
+                }
+            }
+            // one read-back: the per-trial results [, the hypothesis counts and records right behind them]
+            TRIALS_HIP_TRY(hipMemcpyAsync(out_pin, d_out, post ? rb + cb + (size_t)H * sizeof(stocs_trial_hypothesis) : (size_t)nTp * 18 * 4, hipMemcpyDeviceToHost, c->stream));
             TRIALS_HIP_TRY(hipStreamSynchronize(c->stream));
             memcpy(out18.data(), out_pin, (size_t)nTp * 18 * 4);
+            if (post) {
+                const int32_t* cnt = (const int32_t*)((const char*)out_pin + rb);
+                const stocs_trial_hypothesis* rec = (const stocs_trial_hypothesis*)((const char*)out_pin + rb + cb);
+                for (int t = 0; t < nTp; ++t) {
+                    const int m = std::min(cnt[t], hyp_off[(size_t)t + 1] - hyp_off[(size_t)t]);
+                    B->hyps[(size_t)(t0 + t)].assign(rec + hyp_off[(size_t)t], rec + hyp_off[(size_t)t] + std::max(m, 0));
+                }
+            }
             c->cands_stale = true;
         }
         ms_ver += now_ms() - ta;
@@ -329,6 +463,19 @@ int stocs_trials_get_quad_counts(stocs_ctx* c, int trial, int64_t* counts, int c
     *n = (int)q.size();
     if (counts) for (int b = 0; b < *n && b < cap; ++b) counts[b] = (int64_t)q[(size_t)b];
     return counts && *n > cap ? STOCS_ERR_CAPACITY : STOCS_OK;
+}
+
+int stocs_trials_get_hypotheses(stocs_ctx* c, int trial, stocs_trial_hypothesis* out, int cap, int* n) {
+    TrialBatch* B = batch_of(c, trial);
+    if (!B) return STOCS_ERR_STATE;
+    if (!n || cap < 0) return STOCS_ERR_INVALID;
+    if (!B->post) { set_error("stocs_trials_get_hypotheses: the batch was run without post-processing"); return STOCS_ERR_STATE; }
+    const std::vector<stocs_trial_hypothesis>& h = B->hyps[(size_t)trial];
+    *n = (int)h.size();
+    if (!out) return STOCS_OK;
+    const int m = std::min(*n, cap);
+    if (m > 0) memcpy(out, h.data(), (size_t)m * sizeof(stocs_trial_hypothesis));
+    return *n > cap ? STOCS_ERR_CAPACITY : STOCS_OK;
 }
 
 int stocs_trials_get_candidates(stocs_ctx* c, int trial, float* T16_centred, float* pose16_camera, float* lcp, int32_t* base_index, int cap, int* n) {

@@ -30,6 +30,9 @@ def _close_all():
 _TRIAL_DTYPE = np.dtype([("n_bases", np.int32), ("n_candidates", np.int32), ("n_quads", np.int64), ("best_lcp", np.float32), ("best_index", np.int32),
                          ("best_pose16", np.float32, (16,))])
 assert _TRIAL_DTYPE.itemsize == C.sizeof(capi.TrialResult)
+_HYP_DTYPE = np.dtype([("candidate_index", np.int32), ("base_index", np.int32), ("lcp", np.float32), ("pose16", np.float32, 16),
+                       ("refined_lcp", np.float32), ("refined_pose16", np.float32, 16), ("n_correspondences", np.int32), ("iterations", np.int32)])
+assert _HYP_DTYPE.itemsize == C.sizeof(capi.TrialHypothesis)
 
 
 class StocsEstimator:
@@ -259,12 +262,19 @@ class StocsEstimator:
         return s.value, i.value, P
 
     # ---- trial batches: N independent trials in one set of launches (stocs_run_trials) ----
-    def run_trials(self, seeds, n_attempts=100, mode=0, dispersion=0.9, max_per_base=200, keep_details=False):
-        """-> list of dicts (n_bases, n_candidates, n_quads, best_lcp, best_index, best_pose 16 floats), one per seed."""
+    def run_trials(self, seeds, n_attempts=100, mode=0, dispersion=0.9, max_per_base=200, keep_details=False, post=None):
+        """-> list of dicts (n_bases, n_candidates, n_quads, best_lcp, best_index, best_pose 16 floats), one per seed.
+        post (a dict of trial_post's fields, or a capi.TrialPost): cluster, and refine, every trial's candidates inside the batch
+        (stocs_run_trials_post); the hypotheses are then read with trials_get_hypotheses(t)."""
         sd = np.ascontiguousarray(seeds, np.uint64)
         res = (capi.TrialResult * max(len(sd), 1))()
-        capi.check(self.L.stocs_run_trials(self.h, mode, len(sd), sd.ctypes.data_as(C.POINTER(C.c_uint64)), n_attempts, dispersion, max_per_base,
-                                           1 if keep_details else 0, res))
+        if post is None:
+            capi.check(self.L.stocs_run_trials(self.h, mode, len(sd), sd.ctypes.data_as(C.POINTER(C.c_uint64)), n_attempts, dispersion, max_per_base,
+                                               1 if keep_details else 0, res))
+        else:
+            pp = post if isinstance(post, capi.TrialPost) else trial_post(**post)
+            capi.check(self.L.stocs_run_trials_post(self.h, mode, len(sd), sd.ctypes.data_as(C.POINTER(C.c_uint64)), n_attempts, dispersion, max_per_base,
+                                                    1 if keep_details else 0, C.byref(pp), res))
         # (one view of the whole result array: a ctypes field access per trial costs ~20 us, and a thousand trials take 60 ms of device time)
         a = np.frombuffer(res, dtype=_TRIAL_DTYPE, count=len(sd))
         nb, nc, nq, bl, bi, bp = (a["n_bases"].tolist(), a["n_candidates"].tolist(), a["n_quads"].tolist(), a["best_lcp"].tolist(), a["best_index"].tolist(),
@@ -286,6 +296,16 @@ class StocsEstimator:
         if n.value:
             capi.check(self.L.stocs_trials_get_quad_counts(self.h, trial, out.ctypes.data_as(capi._i64p), n.value, C.byref(n)))
         return out
+
+    def trials_get_hypotheses(self, trial):
+        """-> the trial's kept hypotheses of the last post-processed batch, in cluster order: a structured array with the fields of
+        stocs_trial_hypothesis (candidate_index, base_index, lcp, pose16, refined_lcp, refined_pose16, n_correspondences, iterations)."""
+        n = C.c_int(0)
+        capi.check(self.L.stocs_trials_get_hypotheses(self.h, trial, None, 0, C.byref(n)))
+        buf = (capi.TrialHypothesis * max(n.value, 1))()
+        if n.value:
+            capi.check(self.L.stocs_trials_get_hypotheses(self.h, trial, buf, n.value, C.byref(n)))
+        return np.frombuffer(buf, dtype=_HYP_DTYPE, count=n.value).copy()
 
     def trial_candidates(self, trial):
         n = C.c_int(0)
@@ -415,6 +435,13 @@ def kdtree_nn_host(pos3, queries3, sqdist):
     out = np.zeros(max(len(q), 1), np.int32)
     capi.check(L.stocs_kdtree_nn_host(pp, len(p), pq, len(q), float(sqdist), out.ctypes.data_as(capi._ip)))
     return out[:len(q)]
+
+
+def trial_post(acceptable_fraction=0.8, maximum_pose_count=10, min_distance=0.02, min_angle=15.0, sym3=(0.0, 0.0, 0.0), refine_iterations=0,
+               max_correspondence_distance=0.035):
+    """stocs_trial_post; the defaults are stocs_single's clustering (0.8, 10, 2 cm, 15 degrees, no symmetry) and the reference's ICP distance"""
+    return capi.TrialPost(acceptable_fraction, maximum_pose_count, min_distance, min_angle, (C.c_float * 3)(*sym3), refine_iterations,
+                          max_correspondence_distance)
 
 
 def cluster_poses(poses16, lcp, acceptable_fraction, best_score, maximum_pose_count, min_distance, min_angle, sym):
