@@ -288,7 +288,11 @@ typedef struct stocs_camera {
     int normal_method;         /* STOCS_NORMALS_* */
 } stocs_camera;
 /* rgbd::load_rgbd_data_sampled (rgbd.cpp:179-281): depth + class-probability images (uint16) -> voxelised,
- * outlier-filtered, oriented scene cloud with class probability and (row, col) pixel per point */
+ * outlier-filtered, oriented scene cloud with class probability and (row, col) pixel per point.  Any depth is accepted (far
+ * background and saturated 65 535 included): the voxel grid covers the whole frame, and the outlier-removal search grid only the
+ * leaves that can hold a centroid with z in [-r, 2 m + r] (r = 2*voxel_size + 5 mm) -- every other centroid lies beyond the
+ * reach of a point the z <= 2 m cut keeps, and is given no neighbours.  STOCS_ERR_INVALID when that near part of the frame needs
+ * more than 2^28 search cells of r, i.e. spans kilometres: intrinsics no camera has (a focal length of a pixel or less). */
 int stocs_ingest_scene(const stocs_camera* cam, const uint16_t* depth, const uint16_t* class_prob, float voxel_size,
                        float class_threshold, int device, float* pos3, float* nrm3, float* prob, int32_t* pixel2,
                        int cap, int* n_out);

@@ -152,7 +152,7 @@ __global__ __launch_bounds__(256) void gradient_normals_kernel(const uint16_t* _
 // pcl::VoxelGrid leaf coordinates floor(p / leaf) (relative to the minimum added on the host)
 __global__ __launch_bounds__(256) void leaf_coords_kernel(const float4* __restrict__ P, int n, double inv_leaf, int3* __restrict__ ijk, int* __restrict__ mm) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (blockIdx.x == 0 && threadIdx.x < 6) mm[threadIdx.x] = threadIdx.x < 3 ? INT_MAX : INT_MIN;   // for minmax_i3_kernel, which runs after this one
+    if (blockIdx.x == 0 && threadIdx.x < 10) mm[threadIdx.x] = (threadIdx.x < 3 || (threadIdx.x >= 6 && threadIdx.x < 8)) ? INT_MAX : INT_MIN;   // for minmax_i3_kernel, which runs after this one
     if (idx >= n) return;
     const float4 p = P[idx];
     ijk[idx] = make_int3((int)floor((double)p.x * inv_leaf), (int)floor((double)p.y * inv_leaf), (int)floor((double)p.z * inv_leaf));
@@ -274,18 +274,28 @@ __global__ __launch_bounds__(256) void centroid_long_kernel(const uint32_t* __re
     }
 }
 
-// pcl::RadiusOutlierRemoval (rgbd.cpp:233-237): number of points (itself included) within radius
-__global__ __launch_bounds__(256) void ror_cell_kernel(const float4* __restrict__ P, int n, double3 mn, double inv_r, int3 dims, uint32_t* __restrict__ cell) {
+// pcl::RadiusOutlierRemoval (rgbd.cpp:233-237): number of points (itself included) within radius.
+// The search grid covers only a box of the cloud (see ingest_shared_stages); a point outside it gets the cell index ncell, which sorts
+// after every real cell and owns no start / end entry.
+__device__ inline bool ror_cell_of(const float4 p, double3 mn, double inv_r, int3 dims, int* cx, int* cy, int* cz) {
+    const double fx = floor(((double)p.x - mn.x) * inv_r), fy = floor(((double)p.y - mn.y) * inv_r), fz = floor(((double)p.z - mn.z) * inv_r);
+    if (!(fx >= 0.0 && fy >= 0.0 && fz >= 0.0 && fx < (double)dims.x && fy < (double)dims.y && fz < (double)dims.z)) return false;
+    *cx = (int)fx; *cy = (int)fy; *cz = (int)fz;
+    return true;
+}
+__global__ __launch_bounds__(256) void ror_cell_kernel(const float4* __restrict__ P, int n, double3 mn, double inv_r, int3 dims, uint32_t ncell,
+                                                       uint32_t* __restrict__ cell) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
-    const float4 p = P[idx];
-    const int cx = (int)floor(((double)p.x - mn.x) * inv_r), cy = (int)floor(((double)p.y - mn.y) * inv_r), cz = (int)floor(((double)p.z - mn.z) * inv_r);
-    cell[idx] = (uint32_t)((cz * dims.y + cy) * dims.x + cx);
+    int cx, cy, cz;
+    cell[idx] = ror_cell_of(P[idx], mn, inv_r, dims, &cx, &cy, &cz) ? (uint32_t)((cz * dims.y + cy) * dims.x + cx) : ncell;
 }
-__global__ __launch_bounds__(256) void cell_start_kernel(const uint32_t* __restrict__ sorted_cell, int n, uint32_t* __restrict__ start, uint32_t* __restrict__ end) {
+__global__ __launch_bounds__(256) void cell_start_kernel(const uint32_t* __restrict__ sorted_cell, int n, uint32_t ncell, uint32_t* __restrict__ start,
+                                                         uint32_t* __restrict__ end) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
     const uint32_t c = sorted_cell[idx];
+    if (c >= ncell) return;
     if (idx == 0 || sorted_cell[idx - 1] != c) start[c] = (uint32_t)idx;
     if (idx == n - 1 || sorted_cell[idx + 1] != c) end[c] = (uint32_t)idx + 1;
 }
@@ -297,7 +307,8 @@ __global__ __launch_bounds__(256) void ror_count_kernel(const float4* __restrict
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= n) return;
     const float4 p = P[idx];
-    const int cx = (int)floor(((double)p.x - mn.x) * inv_r), cy = (int)floor(((double)p.y - mn.y) * inv_r), cz = (int)floor(((double)p.z - mn.z) * inv_r);
+    int cx, cy, cz;
+    if (!ror_cell_of(p, mn, inv_r, dims, &cx, &cy, &cz)) { count[idx] = 0u; return; }   // outside the box: no centroid there can be selected
     uint32_t k = 0;
     const double r2 = radius * radius;
     for (int dz = -1; dz <= 1 && k <= min_pts; ++dz)                  // (the test once per slab of nine cells: their look-ups stay independent)
@@ -413,26 +424,30 @@ struct Buf {   // typed view of workspace memory
     int alloc(size_t n) { return tl_cur->take(n * sizeof(T), (void**)&p); }
 };
 
-// out[0..2] = min, out[3..5] = max of the leaf coordinates (initialised by leaf_coords_kernel): strided partial results,
+// out[0..2] = min, out[3..5] = max of the leaf coordinates; out[6..7] = min, out[8..9] = max of the x and y leaf coordinates of the
+// points whose z leaf coordinate lies in [band_lo, band_hi] (all initialised by leaf_coords_kernel): strided partial results,
 // wavefront reductions, one atomic per wavefront and component
-__global__ __launch_bounds__(256) void minmax_i3_kernel(const int3* __restrict__ v, int n, int* __restrict__ out) {
+__global__ __launch_bounds__(256) void minmax_i3_kernel(const int3* __restrict__ v, int n, int band_lo, int band_hi, int* __restrict__ out) {
     // (one atomic per WORKGROUP and component: 256 workgroups x 4 wavefronts x 6 atomics on six addresses serialised in the L2 -- 73 us of a
     //  frame's ingest in round 5a for a 300 000-point reduction)
-    __shared__ int s_m[6][4];
-    int mn[3] = {INT_MAX, INT_MAX, INT_MAX}, mx[3] = {INT_MIN, INT_MIN, INT_MIN};
+    __shared__ int s_m[10][4];
+    int mn[5] = {INT_MAX, INT_MAX, INT_MAX, INT_MAX, INT_MAX}, mx[5] = {INT_MIN, INT_MIN, INT_MIN, INT_MIN, INT_MIN};
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const int3 c = v[i];
         mn[0] = min(mn[0], c.x); mn[1] = min(mn[1], c.y); mn[2] = min(mn[2], c.z);
         mx[0] = max(mx[0], c.x); mx[1] = max(mx[1], c.y); mx[2] = max(mx[2], c.z);
+        if (c.z >= band_lo && c.z <= band_hi) { mn[3] = min(mn[3], c.x); mn[4] = min(mn[4], c.y); mx[3] = max(mx[3], c.x); mx[4] = max(mx[4], c.y); }
     }
-    for (int k = 0; k < 3; ++k)
+    for (int k = 0; k < 5; ++k)
         for (int off = 32; off > 0; off >>= 1) { mn[k] = min(mn[k], __shfl_xor(mn[k], off, 64)); mx[k] = max(mx[k], __shfl_xor(mx[k], off, 64)); }
-    if ((threadIdx.x & 63) == 0)
+    if ((threadIdx.x & 63) == 0) {
         for (int k = 0; k < 3; ++k) { s_m[k][threadIdx.x >> 6] = mn[k]; s_m[3 + k][threadIdx.x >> 6] = mx[k]; }
+        for (int k = 0; k < 2; ++k) { s_m[6 + k][threadIdx.x >> 6] = mn[3 + k]; s_m[8 + k][threadIdx.x >> 6] = mx[3 + k]; }
+    }
     __syncthreads();
-    if (threadIdx.x < 6) {
+    if (threadIdx.x < 10) {
         const int k = threadIdx.x;
-        if (k < 3) atomicMin(&out[k], min(min(s_m[k][0], s_m[k][1]), min(s_m[k][2], s_m[k][3])));
+        if (k < 3 || k == 6 || k == 7) atomicMin(&out[k], min(min(s_m[k][0], s_m[k][1]), min(s_m[k][2], s_m[k][3])));
         else atomicMax(&out[k], max(max(s_m[k][0], s_m[k][1]), max(s_m[k][2], s_m[k][3])));
     }
 }
@@ -524,24 +539,28 @@ __global__ __launch_bounds__(256) void scene_pack_multi_kernel(const float4* __r
 }
 
 // voxel grid on device points dP[n] (+ optional extra field); outputs device centroid arrays (workspace memory)
+// pin_small: 16 pinned words for the call's small read-backs (else pageable stack words).  box6: a box that holds every centroid (from the
+// leaf bounds, a leaf of slack either side).  band4: the x and y leaf bounds (min x, min y, max x, max y) of the points whose z leaf
+// coordinate lies in [band_lo, band_hi]; min > max when there is none.
 static int voxel_grid_device(const float4* dP, const float4* dExtra, int n, double leaf, Buf<float4>& cen, Buf<float4>& ext, int* n_out, hipStream_t st,
-                             double* box6 = NULL, int* pin_small = NULL) {   // pin_small: 16 pinned words for the call's small read-backs (else pageable stack words)   // box6: a box that holds every centroid (from the leaf bounds, a leaf of slack either side)
+                             double* box6 = NULL, int* pin_small = NULL, int band_lo = INT_MAX, int band_hi = INT_MIN, int* band4 = NULL) {
     *n_out = 0;
     if (n == 0) return STOCS_OK;
     Buf<int3> ijk; Buf<uint64_t> keys, keys_s; Buf<uint32_t> ids, ids_s, head, seg; Buf<char> tmp; Buf<int> mm;
     int rc;
     if ((rc = ijk.alloc(n)) || (rc = keys.alloc(n)) || (rc = keys_s.alloc(n)) || (rc = ids.alloc(n)) || (rc = ids_s.alloc(n)) || (rc = head.alloc(n)) ||
-        (rc = seg.alloc(n)) || (rc = mm.alloc(8)))
+        (rc = seg.alloc(n)) || (rc = mm.alloc(16)))
         return rc;
     const dim3 g((unsigned)((n + 255) / 256));
     hipLaunchKernelGGL(leaf_coords_kernel, g, dim3(256), 0, st, dP, n, 1.0 / leaf, ijk.p, mm.p);
-    hipLaunchKernelGGL(minmax_i3_kernel, dim3(std::min<unsigned>(g.x, 128u)), dim3(256), 0, st, ijk.p, n, mm.p);
-    int h6_stack[6];
+    hipLaunchKernelGGL(minmax_i3_kernel, dim3(std::min<unsigned>(g.x, 128u)), dim3(256), 0, st, ijk.p, n, band_lo, band_hi, mm.p);
+    int h6_stack[10];
     int* h6 = pin_small ? pin_small : h6_stack;
     STOCS_HIP_CHECK(hipMemcpyAsync(h6, mm.p, sizeof(h6_stack), hipMemcpyDeviceToHost, st));
     STOCS_HIP_CHECK(hipStreamSynchronize(st));
     const int3 mn = make_int3(h6[0], h6[1], h6[2]), mx = make_int3(h6[3], h6[4], h6[5]);
     if (box6) for (int k = 0; k < 3; ++k) { box6[k] = ((double)h6[k] - 1.0) * leaf; box6[3 + k] = ((double)h6[3 + k] + 2.0) * leaf; }
+    if (band4) for (int k = 0; k < 4; ++k) band4[k] = h6[6 + k];
     const int3 dims = make_int3(mx.x - mn.x + 1, mx.y - mn.y + 1, mx.z - mn.z + 1);
     if ((double)dims.x * dims.y * dims.z > 9.0e18) { set_error("voxel grid: leaf size too small for the cloud extent"); return STOCS_ERR_INVALID; }
     int key_bits = 1;   // sort only the bits the keys can have
@@ -581,7 +600,7 @@ static int voxel_grid_device(const float4* dP, const float4* dExtra, int n, doub
     }
     STOCS_HIP_CHECK(exclusive_scan(scan_tmp, tb2, head.p, seg.p, (size_t)n, st));
     uint32_t rb_stack[3] = {0, 0, 0};
-    uint32_t* rb = pin_small ? (uint32_t*)pin_small + 8 : rb_stack;
+    uint32_t* rb = pin_small ? (uint32_t*)pin_small + 10 : rb_stack;
     rb[0] = rb[1] = rb[2] = 0u;
     STOCS_HIP_CHECK(hipMemcpyAsync(&rb[0], seg.p + (n - 1), 4, hipMemcpyDeviceToHost, st));
     STOCS_HIP_CHECK(hipMemcpyAsync(&rb[1], head.p + (n - 1), 4, hipMemcpyDeviceToHost, st));
@@ -626,32 +645,50 @@ static int ingest_shared_stages(const stocs_camera* cam, const uint16_t* dD, flo
     tick("upload+backproject+normals");
     Buf<float4> ext;
     int nv = 0;
+    // radius outlier removal: radius 2*voxel + 5 mm, more than 10 points (itself included)   rgbd.cpp:233-237
+    const double radius = 2.0 * (double)voxel_size + 0.005, leaf = (double)voxel_size;
+    // Only a centroid with z in (0, 2] can pass scene_select*, and its count depends only on the centroids within the radius, all of them with
+    // z in [-radius, 2 + radius].  The leaves that can hold such a centroid (a leaf's centroid lies within a leaf of its cell, as for box6):
+    const int band_lo = (int)std::max(floor(-radius / leaf) - 2.0, (double)INT_MIN / 2), band_hi = (int)std::min(ceil((2.0 + radius) / leaf) + 1.0, (double)INT_MAX / 2);
     double box6[6] = {0, 0, 0, 0, 0, 0};
-    if ((rc = voxel_grid_device(dP.p, NULL, npx, (double)voxel_size, cen, ext, &nv, st, box6, pin_small))) return rc;   // rgbd.cpp:228-231
+    int band4[4] = {0, 0, -1, -1};
+    if ((rc = voxel_grid_device(dP.p, NULL, npx, leaf, cen, ext, &nv, st, box6, pin_small, band_lo, band_hi, band4))) return rc;   // rgbd.cpp:228-231
     tick("voxel grid");
     if (nv == 0) return STOCS_OK;
-    // radius outlier removal: radius 2*voxel + 5 mm, more than 10 points (itself included)   rgbd.cpp:233-237
-    const double radius = 2.0 * (double)voxel_size + 0.005;
-    // the search grid only has to hold every centroid (the counts do not depend on where its cells fall): its box comes from
-    // the leaf bounds the voxel grid already read back -- no reduction over the centroids, no synchronisation here
-    const double3 mn = make_double3(box6[0], box6[1], box6[2]), mx = make_double3(box6[3], box6[4], box6[5]);
-    const int3 dims = make_int3((int)floor((mx.x - mn.x) / radius) + 1, (int)floor((mx.y - mn.y) / radius) + 1, (int)floor((mx.z - mn.z) / radius) + 1);
+    if ((rc = count.alloc(nv))) return rc;
+    if (band4[0] > band4[2]) {   // no leaf near the band: no centroid can be selected
+        STOCS_HIP_CHECK(hipMemsetAsync(count.p, 0, sizeof(uint32_t) * (size_t)nv, st));
+        *nv_out = nv;
+        return STOCS_OK;
+    }
+    // The search grid spans those leaves only (the counts do not depend on where its cells fall; far background and saturated depths lie
+    // outside it and get a count of 0, which is exact for every centroid that scene_select* may keep).  Its box comes from the leaf bounds
+    // the voxel grid already read back -- no reduction over the centroids, no synchronisation here.  For a frame whose depths are all in
+    // the band, this is the box of every centroid.
+    const double3 mn = make_double3(((double)band4[0] - 1.0) * leaf, ((double)band4[1] - 1.0) * leaf, std::max(box6[2], ((double)band_lo - 1.0) * leaf));
+    const double3 mx = make_double3(((double)band4[2] + 2.0) * leaf, ((double)band4[3] + 2.0) * leaf, std::min(box6[5], ((double)band_hi + 2.0) * leaf));
+    const double ddx = floor((mx.x - mn.x) / radius) + 1, ddy = floor((mx.y - mn.y) / radius) + 1, ddz = floor((mx.z - mn.z) / radius) + 1;
+    if (ddx * ddy * ddz > (double)((size_t)1 << 28)) {
+        set_error("outlier-removal grid: the part of the scene with z <= 2 m spans %.3g x %.3g m, over 2^28 cells of %.3g m (intrinsics?)", mx.x - mn.x,
+                  mx.y - mn.y, radius);
+        return STOCS_ERR_INVALID;
+    }
+    const int3 dims = make_int3((int)ddx, (int)ddy, (int)ddz);
     const size_t ncell = (size_t)dims.x * dims.y * dims.z;
-    if (ncell > ((size_t)1 << 28)) { set_error("scene extent too large for the outlier-removal grid"); return STOCS_ERR_INVALID; }
     Buf<uint32_t> cell, cell_s, ids, ids_s, cstart, cend; Buf<char> tmp;
-    if ((rc = cell.alloc(nv)) || (rc = cell_s.alloc(nv)) || (rc = ids.alloc(nv)) || (rc = ids_s.alloc(nv)) || (rc = cstart.alloc(ncell)) || (rc = cend.alloc(ncell)) ||
-        (rc = count.alloc(nv))) return rc;
+    if ((rc = cell.alloc(nv)) || (rc = cell_s.alloc(nv)) || (rc = ids.alloc(nv)) || (rc = ids_s.alloc(nv)) || (rc = cstart.alloc(ncell)) || (rc = cend.alloc(ncell)))
+        return rc;
     const dim3 gv((unsigned)((nv + 255) / 256));
-    hipLaunchKernelGGL(ror_cell_kernel, gv, dim3(256), 0, st, cen.p, nv, mn, 1.0 / radius, dims, cell.p);
+    hipLaunchKernelGGL(ror_cell_kernel, gv, dim3(256), 0, st, cen.p, nv, mn, 1.0 / radius, dims, (uint32_t)ncell, cell.p);
     hipLaunchKernelGGL(iota_kernel, gv, dim3(256), 0, st, ids.p, nv);
     size_t tb = 0;
     int cell_bits = 1;
-    while (cell_bits < 32 && ((size_t)1 << cell_bits) < ncell) cell_bits++;
+    while (cell_bits < 32 && ((size_t)1 << cell_bits) <= ncell) cell_bits++;   // (ncell itself: the cell of the centroids outside the box)
     STOCS_HIP_CHECK(sort_pairs(NULL, tb, cell.p, cell_s.p, ids.p, ids_s.p, (size_t)nv, 0, (unsigned)cell_bits, st));
     if ((rc = tmp.alloc(tb))) return rc;
     STOCS_HIP_CHECK(sort_pairs(tmp.p, tb, cell.p, cell_s.p, ids.p, ids_s.p, (size_t)nv, 0, (unsigned)cell_bits, st));
     hipLaunchKernelGGL(zero_u32x2_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, st, cstart.p, cend.p, ncell);
-    hipLaunchKernelGGL(cell_start_kernel, gv, dim3(256), 0, st, cell_s.p, nv, cstart.p, cend.p);
+    hipLaunchKernelGGL(cell_start_kernel, gv, dim3(256), 0, st, cell_s.p, nv, (uint32_t)ncell, cstart.p, cend.p);
     hipLaunchKernelGGL(ror_count_kernel, gv, dim3(256), 0, st, cen.p, nv, mn, 1.0 / radius, dims, radius, cstart.p, cend.p, ids_s.p, count.p, 10u);
     STOCS_HIP_CHECK(hipGetLastError());
     *nv_out = nv;
@@ -740,7 +777,7 @@ int stocs_ingest_scene(const stocs_camera* cam, const uint16_t* depth, const uin
     hipLaunchKernelGGL(scene_pack_kernel, gv, dim3(256), 0, st, cen.p, on.p, op.p, opx.p, keep.p, kpos.p, nv, o_pos.p, o_nrm.p, o_prob.p, o_px.p);
     STOCS_HIP_CHECK(hipGetLastError());
     tick("outlier removal+select");
-    uint32_t* m_pin = (uint32_t*)pin_small + 12;
+    uint32_t* m_pin = (uint32_t*)pin_small + 14;
     *m_pin = 0u;
     STOCS_HIP_CHECK(hipMemcpyAsync(m_pin, kpos.p + nv, 4, hipMemcpyDeviceToHost, st));
     STOCS_HIP_CHECK(hipStreamSynchronize(st));
@@ -823,7 +860,7 @@ int stocs_ingest_scene_multi(const stocs_camera* cam, const uint16_t* depth, int
                        o_pos.p, o_nrm.p, o_prob.p, o_px.p);
     STOCS_HIP_CHECK(hipGetLastError());
     tick("outlier removal+select");
-    int32_t* off_pin = pin_small + 16;   // (words 0-11 are the voxel grid's)
+    int32_t* off_pin = pin_small + 16;   // (words 0-12 are the voxel grid's)
     STOCS_HIP_CHECK(hipMemcpyAsync(off_pin, d_off.p, 4 * ((size_t)K + 1), hipMemcpyDeviceToHost, st));
     STOCS_HIP_CHECK(hipStreamSynchronize(st));
     memcpy(offsets, off_pin, 4 * ((size_t)K + 1));

@@ -154,6 +154,8 @@ def preprocess_model(raw_xyz, normal_radius, voxel, model_scale):
             n = -n
         nrm[i] = -n                                                 # stocs.cpp:47-52 -> away from the origin
     ok = np.isfinite(nrm).all(axis=1)
+    if not ok.any():                                                # no point has a normal: an empty model
+        return np.zeros((0, 3), np.float32), np.zeros((0, 3), np.float32)
     cen, navg = voxel_grid(pts[ok].astype(np.float32), voxel, nrm[ok].astype(np.float32))        # stocs.cpp:54-57
     ln = np.linalg.norm(navg.astype(np.float64), axis=1)
     fin = np.isfinite(navg).all(axis=1) & (ln > 0)
