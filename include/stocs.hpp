@@ -605,7 +605,45 @@ public:
         return out;
     }
 
+    // Tracking across frames (stocs_track_poses; no reference counterpart): the defaults of a local search around a prior pose
+    // (model_matching_amd/estimator.py TRACK_DEFAULTS, chosen by tools/track_time.py's sweep)
+    static stocs_track_params default_track_params() {
+        stocs_track_params p;
+        p.rounds = 6; p.samples = 2048; p.max_translation = 0.02f; p.max_rotation_deg = 10.0f; p.shrink = 0.7f; p.seed = 0;
+        p.refine_iterations = 0; p.max_correspondence_distance = 0.035f; p.keep_details = 0;
+        return p;
+    }
+    // The camera-frame priors (e.g. the previous frame's poses) searched around on this estimator's current scene.  Returns one new
+    // candidate per prior, owned by the estimator until the next call: the better of the search's pose and the refined pose (the search
+    // pose on a tie), with its lcp and the prior's base_index; results (may be NULL) receives the raw records.  Empty on error (the
+    // text goes to the log, as compute_best_transform reports errors).
+    std::vector<PoseCandidate*> track_poses(const std::vector<PoseCandidate*>& priors, const stocs_track_params& prm = default_track_params(),
+                                            std::vector<stocs_track_result>* results = NULL) {
+        tracked_store_.clear();
+        std::vector<PoseCandidate*> out;
+        const int n = (int)priors.size();
+        std::vector<float> P((size_t)n * 16);
+        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], priors[(size_t)i]->transform.data(), 64);
+        std::vector<stocs_track_result> r((size_t)std::max(n, 1));
+        if (n > 0 && stocs_track_poses(ctx_, P.data(), n, &prm, r.data()) != STOCS_OK) {
+            *log_ << "track_poses failed: " << stocs_last_error() << std::endl;
+            return out;
+        }
+        r.resize((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            const stocs_track_result& t = r[(size_t)i];
+            const bool ref = t.refined_lcp > t.lcp;
+            MatrixType m;
+            std::memcpy(m.data(), ref ? t.refined_pose16 : t.pose16, 64);
+            tracked_store_.emplace_back(new PoseCandidate(m, ref ? t.refined_lcp : t.lcp, (float)priors[(size_t)i]->base_index));
+            out.push_back(tracked_store_.back().get());
+        }
+        if (results) *results = r;
+        return out;
+    }
+
 protected:
+    std::vector<std::unique_ptr<PoseCandidate> > tracked_store_;   // results of the last track_poses
     std::unique_ptr<PoseCandidate> trial_best_;
     std::vector<std::unique_ptr<PoseCandidate> > refined_store_;   // results of the last refine_pose_candidates
     std::vector<std::unique_ptr<PoseCandidate> > hyp_store_;       // hypotheses of the last post-processed run_trials

@@ -353,6 +353,59 @@ int stocs_refine_poses(stocs_ctx* ctx, const float* T16_centred_in, int n, const
                        float max_correspondence_distance, float* T16_centred_out, float* pose16_camera_out, float* lcp_out,
                        int32_t* n_corr_out, int32_t* iterations_out);
 
+/* ---- pose tracking across frames: a local search around n prior poses on the context's current scene (no reference counterpart;
+ * the reference detects from scratch on every frame).  Priors are CAMERA-frame poses (column-major, as stocs_get_candidates and the
+ * pose file give them: only the camera frame carries over from frame to frame).  Each is taken to the centred frame on the host, in
+ * float: R is kept, Rcm_r = R_r0 cm_x + (R_r1 cm_y + R_r2 cm_z), t_r = (tc_r - cs_r) + Rcm_r (cs / cm: stocs_get_centroids).
+ * Round r = 0 .. rounds-1, prior p, slot j = 0 .. samples-1: slot 0 is the incumbent as it stands; slot j >= 1 is the incumbent
+ * perturbed about the model centroid (the origin of the centred model): R' = R dR, t' = t + dt.  Its six draws are
+ *     u_k = (rng64(seed, p * rounds + r, 8 * j + k) >> 40) * 2^-24,  k = 0 .. 5   (csrc/stocs_math.h; exact floats in [0, 1))
+ *     dt_k = tau_r * (2 u_k - 1)  (k = 0, 1, 2),   v_k = h_r * (2 u_{k+3} - 1)  (k = 0, 1, 2)
+ * with b_r = shrink^r (a double product, b_0 = 1), tau_r = (float)(max_translation * b_r), h_r = (float)tan(max_rotation_deg * b_r * pi
+ * / 360), both in double on the host.  dR is the rotation of the unit quaternion (1, v) / sqrt(1 + |v|^2):
+ *     d = 1 + (v0 v0 + (v1 v1 + v2 v2)),  s = 1 / sqrt(d),  w = s, x = v0 s, y = v1 s, z = v2 s,
+ *     dR = [[1 - 2 (y y + z z), 2 (x y - w z), 2 (x z + w y)], [2 (x y + w z), 1 - 2 (x x + z z), 2 (y z - w x)],
+ *           [2 (x z - w y), 2 (y z + w x), 1 - 2 (x x + y y)]]
+ *     R'_ab = R_a0 dR_0b + (R_a1 dR_1b + R_a2 dR_2b),   t'_a = t_a + dt_a
+ * (float, IEEE division and square root, no contraction: a float32 restatement reproduces every candidate bit for bit).  v is drawn
+ * from a cube, not a ball: a sample turns by at most 2 atan(sqrt(3) h_r), i.e. up to ~1.7x the nominal bound at a corner.
+ * Every candidate is scored by the context's LCP path as it stands (exact_ties included): bitwise stocs_score_transforms of its T16.
+ * The next incumbent is the first maximum of the prior's slots, key (lcp bits << 32) | ~slot: ties keep the incumbent, so the lcp
+ * never decreases over the rounds and lcp >= prior_lcp.  Rounds chain on the device (no host wait between them).  With
+ * refine_iterations > 0 the final incumbents go through the refinement of stocs_refine_poses: refined_* are bitwise
+ * stocs_refine_poses(incumbent T16, n, NULL, 0, refine_iterations, max_correspondence_distance) on the same context; without it they
+ * repeat lcp / pose16 with counts 0.  A prior's results are bitwise independent of the other priors of the call (its draws depend on
+ * its index p).  The context's bases, candidates and last trial batch are left as they were; tracking has its own grow-only
+ * workspace (a repeated call of the same size allocates nothing) and does one pinned read-back and one synchronisation per call.
+ * Limits: 1 <= rounds <= STOCS_TRACK_MAX_ROUNDS; n_priors * samples <= STOCS_TRACK_MAX_CANDIDATES per round (2^20: one round's
+ * candidates stay within 64 MiB of workspace, or rounds x that with keep_details; a wider search is a detection, stocs_run_trials).
+ * n_priors == 0: no-op.  A NULL pointer, a non-finite prior or one whose rotation is not orthonormal within 1e-3 (max |R^T R - I|),
+ * a parameter outside its range below, or a batch over the limits: STOCS_ERR_INVALID; no scene: STOCS_ERR_STATE. ---- */
+#define STOCS_TRACK_MAX_ROUNDS 64
+#define STOCS_TRACK_MAX_CANDIDATES (1 << 20)
+typedef struct stocs_track_params {
+    int32_t  rounds;                      /* 1 .. STOCS_TRACK_MAX_ROUNDS search rounds                                 */
+    int32_t  samples;                     /* >= 1 candidates per prior per round; slot 0 is the incumbent, unperturbed */
+    float    max_translation;             /* m, round-0 half-edge of the translation cube (> 0, finite)                */
+    float    max_rotation_deg;            /* round-0 rotation bound, degrees, in (0, 180): h_0 = tan(bound / 2)        */
+    float    shrink;                      /* (0, 1]: both bounds are multiplied by it after every round                */
+    uint64_t seed;
+    int32_t  refine_iterations;           /* >= 0; 0: no refinement                                                    */
+    float    max_correspondence_distance; /* m, > 0 and finite, as stocs_refine_poses                                  */
+    int32_t  keep_details;                /* != 0: keep every round's candidates and scores for stocs_track_get_round */
+} stocs_track_params;
+typedef struct stocs_track_result {
+    float   prior_lcp;                    /* the prior's own score (round 0, slot 0)                                   */
+    float   lcp, pose16[16];              /* best after the rounds, camera frame, column-major                         */
+    float   refined_lcp, refined_pose16[16];
+    int32_t n_correspondences, iterations;/* stocs_refine_poses's; == lcp / pose16 and 0, 0 without refinement        */
+} stocs_track_result;
+int stocs_track_poses(stocs_ctx* ctx, const float* prior_pose16_camera, int n_priors, const stocs_track_params* p, stocs_track_result* out);
+/* round `round` of prior `prior` of the last stocs_track_poses: its samples candidates (centred T16, slot order) and their scores.
+ * *n = samples.  The last call did not keep details (or there was none): STOCS_ERR_STATE; prior / round out of range: STOCS_ERR_INVALID;
+ * an output given and cap < samples: STOCS_ERR_CAPACITY (*n set; NULL outputs query the count). */
+int stocs_track_get_round(stocs_ctx* ctx, int prior, int round, float* T16_centred, float* lcp, int cap, int* n);
+
 /* ---- tuning knobs (never change results beyond float summation order).
  * "lcp_variant": 99 = automatic (default): the scan fed from a per-wavefront LDS queue of the queries that have a list -- over
  *   index-ordered lists at cell edge epsilon (24, sparse scenes), over centre-sorted lists with triangle-inequality early exit

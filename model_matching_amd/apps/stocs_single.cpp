@@ -18,6 +18,10 @@
 // pose_clustering.cpp:123-140, batched: stocs_refine_poses); the best refined pose goes to <out>.refined in the same format.
 // --trials N --cluster 1 [--refine K]: the clustering (and refinement) of every trial runs inside the batch, on the device
 // (stocs_run_trials_post); per-trial cluster / refined lines, the best refined pose of the best trial to <out>.refined.
+// --track <pose file> [--track-min-lcp x] (single object): track from a prior pose in the format this driver writes (12 floats, 3x4
+// row-major) -- a local search around it on this frame (stocs_track_poses, the façade's default parameters); when the tracked lcp is
+// below x (default 0.02: a prior that has lost the object scores ~0) the usual detection runs instead.  Prints which route produced
+// the pose ("track: route=tracked ..." / "track: route=detection ...") and writes <out> as detection does.
 // The reference edits its per-data-set constants in the source (README.md:42-66); here they are options with the
 // reference's YCB values as defaults.
 #include <algorithm>
@@ -201,6 +205,44 @@ static int run_search(stocs::stocs_estimator& stocs_ptr, std::ostream& os, const
     return 0;
 }
 
+// --track: the prior from the pose file, tracked on this frame; the detection of run_search when the tracked lcp stays below min_lcp
+static int run_track(stocs::stocs_estimator& est, const std::string& track_path, float min_lcp, const std::string& out_path, const std::string& dbg_dir,
+                     uint64_t seed, int n_trials, int exact_ties, int do_cluster, int n_refine) {
+    std::ifstream f(track_path);
+    float v[12];
+    for (int i = 0; i < 12; ++i)
+        if (!(f >> v[i])) { std::cerr << "cannot read a 3x4 pose from " << track_path << std::endl; return 1; }
+    MatrixType m;   // identity; the bottom row stays 0 0 0 1
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) m(r, c) = v[r * 4 + c];
+    PoseCandidate prior(m, 0.0f, -1.0f);
+    if (exact_ties) est.set_exact_ties(true);
+    std::vector<PoseCandidate*> priors(1, &prior);
+    std::vector<stocs_track_result> res;
+    auto t0 = std::chrono::high_resolution_clock::now();
+    const std::vector<PoseCandidate*> got = est.track_poses(priors, stocs::stocs_estimator::default_track_params(), &res);
+    auto t1 = std::chrono::high_resolution_clock::now();
+    if (got.empty()) { std::cerr << "tracking failed: " << stocs_last_error() << std::endl; return 2; }
+    const long long us = (long long)std::chrono::duration_cast<micro>(t1 - t0).count();
+    char line[256];
+    if (got[0]->lcp < min_lcp) {
+        snprintf(line, sizeof(line), "track: route=detection prior_lcp=%.9g tracked_lcp=%.9g min_lcp=%.9g track_microseconds=%lld", (double)res[0].prior_lcp,
+                 (double)got[0]->lcp, (double)min_lcp, us);
+        std::cout << line << std::endl;
+        return run_search(est, std::cout, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine);
+    }
+    const PoseCandidate* bp = got[0];
+    std::ofstream o(out_path, std::ofstream::out);
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) o << bp->transform(r, c) << (r == 2 && c == 3 ? "" : " ");
+    o << std::endl;
+    std::cout << "pose:";
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) { char b[32]; snprintf(b, sizeof(b), " %.9g", (double)bp->transform(r, c)); std::cout << b; }
+    std::cout << std::endl;
+    snprintf(line, sizeof(line), "track: route=tracked prior_lcp=%.9g best_lcp=%.9g min_lcp=%.9g track_microseconds=%lld", (double)res[0].prior_lcp, (double)bp->lcp,
+             (double)min_lcp, us);
+    std::cout << line << std::endl;
+    return 0;
+}
+
 // Several objects of one frame (<object_name> = a,b,c): every model, PPF index and probability map is read before any GPU work (a
 // missing one ends the run, naming the object); the frame is ingested once for all of them (stocs::load_frame_scenes); then each
 // object is searched on its own context, at most kMaxFrameThreads at a time (every context holds its own trial memory).  Each
@@ -276,7 +318,8 @@ int main(int argc, char** argv) {
     if (clouds && argc < 4) { std::cout << "usage: stocs_single --clouds <scene.stcl> <model.stcl> [options]" << std::endl; return -1; }
     const std::string a1 = argv[clouds ? 2 : 1], a2 = argv[clouds ? 3 : 2];
     if (const char* e = getenv("STOCS_REPO_PATH")) repo_path = e;
-    std::string edge_path, out_path, dbg_dir;
+    std::string edge_path, out_path, dbg_dir, track_path;
+    float track_min_lcp = 0.02f;
     int do_cluster = 0, n_trials = 0, exact_ties = 0, n_refine = 0;
     uint64_t seed = 1;
     for (int i = clouds ? 4 : 3; i + 1 < argc; i += 2) {
@@ -291,6 +334,8 @@ int main(int argc, char** argv) {
         else if (k == "--refine") n_refine = atoi(v.c_str());   // iterations of the refinement of the clustered hypotheses (0: off)
         else if (k == "--trials") n_trials = atoi(v.c_str());   // N independent runs (seeds seed, seed + 1, ...) in one set of GPU launches; the best one is written
         else if (k == "--exact-ties") exact_ties = atoi(v.c_str());   // 1: the reference kd-tree's answer on exact distance ties (set_exact_ties)
+        else if (k == "--track") track_path = v;   // track from this pose file; detection when the tracked lcp is below --track-min-lcp
+        else if (k == "--track-min-lcp") track_min_lcp = (float)atof(v.c_str());
         else if (k == "--repo") repo_path = v;
         else if (k == "--voxel") voxel_size = (float)atof(v.c_str());
         else if (k == "--depth-scale") depth_scale = (float)atof(v.c_str());
@@ -310,8 +355,8 @@ int main(int argc, char** argv) {
         for (size_t k = 0; k < objects.size(); ++k) {
             if (objects[k].empty() || std::count(objects.begin(), objects.end(), objects[k]) > 1) { std::cerr << "object list " << a2 << ": empty or repeated name" << std::endl; return -1; }
         }
-        if (do_cluster || n_refine || !out_path.empty() || !dbg_dir.empty() || !edge_path.empty()) {
-            std::cerr << "several objects: --cluster, --refine, --out, --dbg and --edge take a single object" << std::endl;
+        if (do_cluster || n_refine || !out_path.empty() || !dbg_dir.empty() || !edge_path.empty() || !track_path.empty()) {
+            std::cerr << "several objects: --cluster, --refine, --out, --dbg, --edge and --track take a single object" << std::endl;
             return -1;
         }
         return run_frame_objects(a1, objects, seed, n_trials, exact_ties);
@@ -358,5 +403,6 @@ int main(int argc, char** argv) {
         std::cerr << e.what() << std::endl;  // no GPU => loud failure, never a CPU fallback
         return 2;
     }
+    if (!track_path.empty()) return run_track(*est, track_path, track_min_lcp, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine);
     return run_search(*est, std::cout, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine);
 }

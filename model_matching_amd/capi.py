@@ -44,6 +44,16 @@ class TrialHypothesis(C.Structure):
                 ("refined_lcp", C.c_float), ("refined_pose16", C.c_float * 16), ("n_correspondences", C.c_int32), ("iterations", C.c_int32)]
 
 
+class TrackParams(C.Structure):
+    _fields_ = [("rounds", C.c_int32), ("samples", C.c_int32), ("max_translation", C.c_float), ("max_rotation_deg", C.c_float), ("shrink", C.c_float),
+                ("seed", C.c_uint64), ("refine_iterations", C.c_int32), ("max_correspondence_distance", C.c_float), ("keep_details", C.c_int32)]
+
+
+class TrackResult(C.Structure):
+    _fields_ = [("prior_lcp", C.c_float), ("lcp", C.c_float), ("pose16", C.c_float * 16), ("refined_lcp", C.c_float), ("refined_pose16", C.c_float * 16),
+                ("n_correspondences", C.c_int32), ("iterations", C.c_int32)]
+
+
 class Camera(C.Structure):
     _fields_ = [("fx", C.c_float), ("cx", C.c_float), ("fy", C.c_float), ("cy", C.c_float), ("depth_scale", C.c_float),
                 ("width", C.c_int), ("height", C.c_int), ("normal_method", C.c_int)]
@@ -119,6 +129,8 @@ SIGNATURES = {
     "stocs_trim": (C.c_int, []),
     "stocs_icp_point_to_plane": (C.c_int, [_fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_float, C.c_int, _fp, _intp]),
     "stocs_refine_poses": (C.c_int, [_vp, _fp, C.c_int, _ip, C.c_int, C.c_int, C.c_float, _fp, _fp, _fp, _ip, _ip]),
+    "stocs_track_poses": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(TrackParams), C.POINTER(TrackResult)]),
+    "stocs_track_get_round": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, C.c_int, _intp]),
     "stocs_device_alloc_count": (C.c_int64, []),
     "stocs_debug_stream_audit_selftest": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     "stocs_debug_streams_overlap": (C.c_int, [_vp]),

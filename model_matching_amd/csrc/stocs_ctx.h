@@ -300,6 +300,7 @@ struct stocs_ctx {
     void* cong;
     std::vector<unsigned long long> quad_off;
     void* refine;   // refine.hip (RefineState): the model's correspondence grid of stocs_refine_poses and its grow-only workspace
+    void* track;    // track.hip (TrackState): stocs_track_poses's grow-only workspace and the details of its last call
     int quad_id_bits;
     // candidates of the last stocs_make_transforms: device-resident (compacted, in pick order) as
     // T[n][16] | pose[n][16] | lcp[n] | base[n] inside d_cand; `cands` is the host mirror, filled on demand
@@ -373,6 +374,7 @@ extern "C" void stocs_internal_invalidate_congruent(stocs_ctx* c);
 extern "C" void stocs_internal_free_instance(stocs_ctx* c);
 extern "C" void stocs_internal_free_trials(stocs_ctx* c);
 extern "C" void stocs_internal_free_refine(stocs_ctx* c);
+extern "C" void stocs_internal_free_track(stocs_ctx* c);
 // the congruent phase with a ceiling on its device memory: *too_big != 0 (and STOCS_OK) when the pair lists of the context's base set
 // would need more than max_bytes (0: no ceiling) or exceed 2^32 entries -- a trial batch then splits the base set and tries again
 extern "C" int stocs_internal_find_congruent(stocs_ctx* c, int64_t* total_quads, size_t max_bytes, int* too_big);

@@ -33,6 +33,13 @@ assert _TRIAL_DTYPE.itemsize == C.sizeof(capi.TrialResult)
 _HYP_DTYPE = np.dtype([("candidate_index", np.int32), ("base_index", np.int32), ("lcp", np.float32), ("pose16", np.float32, 16),
                        ("refined_lcp", np.float32), ("refined_pose16", np.float32, 16), ("n_correspondences", np.int32), ("iterations", np.int32)])
 assert _HYP_DTYPE.itemsize == C.sizeof(capi.TrialHypothesis)
+_TRACK_DTYPE = np.dtype([("prior_lcp", np.float32), ("lcp", np.float32), ("pose16", np.float32, 16), ("refined_lcp", np.float32), ("refined_pose16", np.float32, 16),
+                         ("n_correspondences", np.int32), ("iterations", np.int32)])
+assert _TRACK_DTYPE.itemsize == C.sizeof(capi.TrackResult)
+
+# defaults of track_poses (tools/track_time.py's sweep, profiles/track_time.json)
+TRACK_DEFAULTS = dict(rounds=6, samples=2048, max_translation=0.02, max_rotation_deg=10.0, shrink=0.7, seed=0, refine_iterations=0,
+                      max_correspondence_distance=0.035)
 
 
 class StocsEstimator:
@@ -240,6 +247,29 @@ class StocsEstimator:
                                              To.ctypes.data_as(capi._fp), Po.ctypes.data_as(capi._fp), lcp.ctypes.data_as(capi._fp),
                                              nc.ctypes.data_as(capi._ip), it.ctypes.data_as(capi._ip)))
         return To, Po, lcp, nc, it
+
+    def track_poses(self, priors_pose16_camera, rounds=TRACK_DEFAULTS["rounds"], samples=TRACK_DEFAULTS["samples"],
+                    max_translation=TRACK_DEFAULTS["max_translation"], max_rotation_deg=TRACK_DEFAULTS["max_rotation_deg"], shrink=TRACK_DEFAULTS["shrink"],
+                    seed=TRACK_DEFAULTS["seed"], refine_iterations=TRACK_DEFAULTS["refine_iterations"],
+                    max_correspondence_distance=TRACK_DEFAULTS["max_correspondence_distance"], keep_details=False):
+        """Local search around n camera-frame priors (column-major 16 floats each) on this context's scene (stocs_track_poses) -> a
+        structured array with the fields of stocs_track_result (prior_lcp, lcp, pose16, refined_lcp, refined_pose16, n_correspondences,
+        iterations), one record per prior.  keep_details: every round's candidates and scores stay readable through track_round."""
+        P, pP = capi.f32(priors_pose16_camera)
+        n = P.size // 16
+        prm = capi.TrackParams(rounds, samples, max_translation, max_rotation_deg, shrink, seed, refine_iterations, max_correspondence_distance,
+                               1 if keep_details else 0)
+        buf = (capi.TrackResult * max(n, 1))()
+        capi.check(self.L.stocs_track_poses(self.h, pP, n, C.byref(prm), buf))
+        return np.frombuffer(buf, dtype=_TRACK_DTYPE, count=n).copy()
+
+    def track_round(self, prior, round):
+        """-> (T16_centred (samples, 16), lcp (samples,)) of one round of one prior of the last track_poses(keep_details=True)."""
+        n = C.c_int(0)
+        capi.check(self.L.stocs_track_get_round(self.h, prior, round, None, None, 0, C.byref(n)))
+        T = np.zeros((n.value, 16), np.float32); l = np.zeros(n.value, np.float32)
+        capi.check(self.L.stocs_track_get_round(self.h, prior, round, T.ctypes.data_as(capi._fp), l.ctypes.data_as(capi._fp), n.value, C.byref(n)))
+        return T, l
 
     def lcp_detail(self, T16):
         T, pT = capi.f32(T16)

@@ -296,3 +296,19 @@ def workload(name: str = "Cm"):
         m = make_model(1000, seed=SEED_MODEL + 11)
         return m, make_scene(m, 5000, seed=SEED_SCENE + 11), 2048
     raise KeyError(name)
+
+
+def motion_sequence(T0: np.ndarray, n_frames: int, max_t: float = 0.015, max_deg: float = 8.0, seed: int = SEED_POSE + 303) -> list:
+    """Camera-frame object poses of a moving object (tracking tests and tools/track_time.py): frame 0 is T0; frame k+1 is frame k
+    turned about the object's own origin by between half and all of max_deg, about a random axis, and moved by between half and all
+    of max_t in a random direction."""
+    rng = np.random.Generator(np.random.PCG64(seed))
+    out = [np.asarray(T0, np.float64).copy()]
+    for _ in range(n_frames - 1):
+        T = out[-1].copy()
+        dR = _rot_axis_angle(rng.normal(size=3), np.deg2rad(max_deg) * rng.uniform(0.5, 1.0))
+        d = rng.normal(size=3)
+        T[:3, :3] = T[:3, :3] @ dR
+        T[:3, 3] = T[:3, 3] + d / np.linalg.norm(d) * max_t * rng.uniform(0.5, 1.0)
+        out.append(T)
+    return out
