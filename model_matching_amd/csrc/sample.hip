@@ -708,11 +708,140 @@ __device__ __noinline__ void finalize_one_wave_call(const float4* spos, int b0, 
 template <bool WLDS> struct InstTypes { typedef int32_t sv_t; };
 template <> struct InstTypes<true> { typedef uint16_t sv_t; };
 
+// ---------------------------------------------------------------------------------------------------------------
+// The stages the one-launch kernels below share, each written once: NT threads per workgroup (1024 in the instance kernel and
+// the full-size class kernel, 256 / 512 / 1024 in the lean one), SV the type of a scene index in the attempt's lists.
 // Every loop over the scene points handles 4 points per thread with the loads of all four issued before the first use:
 // the stages run in one workgroup, so memory latency is not hidden by other workgroups -- it is paid once per stage instead
 // of once per point.
-//
-// TWO workgroups share the attempts as a pipeline.  What makes the attempts sequential is the image-space state (the
+// ---------------------------------------------------------------------------------------------------------------
+// the thread index is made opaque at the start of every stage: otherwise the compiler hoists per-thread addresses of
+// every array out of the attempt loop, and a hundred registers of them spill to scratch around every stage
+#define STAGE_THREAD() int t = threadIdx.x; asm volatile("" : "+v"(t)); const int lane = t & 63, wv = t >> 6; (void)lane; (void)wv;
+
+// Pass 1 (stocs.cpp:395-407 / 596-609), stage A, distance alone (the first component of the key, rgbd.cpp:103): a point farther
+// from point 1 than the longest model pair (or within 5 mm) has no key whatever its angles; the others are listed in `list`,
+// *sh_count of them (zero on entry).  W_ARRAY: the attempt's weights are w[], and a point that cannot have a key gets its weight
+// zeroed; otherwise (the lean kernel) the weight is the prior, the .w of the scene position, and nothing is written.
+template <int NT, bool W_ARRAY, class SV>
+__device__ __forceinline__ void pass1_list_in_range(const PassArgs& pa, int b1, V3 pc, float* w, SV* list, int* sh_count) {
+    STAGE_THREAD()
+    const int S = pa.S;
+    const float4* spos = pa.spos;
+    for (int i0 = 0; i0 < S; i0 += 4 * NT) {
+        float wi[4]; float4 P[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int i = i0 + k * NT + t;
+            if (W_ARRAY) {
+                wi[k] = (i < S) ? w[i] : 0.0f;
+                P[k] = make_float4(0, 0, 0, 0);
+                if (wi[k] != 0.0f) P[k] = spos[i];
+            } else {
+                P[k] = i < S ? spos[i] : make_float4(0, 0, 0, 0);
+                wi[k] = P[k].w;
+            }
+        }
+        bool cand[4];
+        unsigned long long cm[4];
+        int n_here = 0;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int i = i0 + k * NT + t;
+            cand[k] = false;
+            if (wi[k] != 0.0f) {
+                cand[k] = i != b1 && ppf_distance_may_have_key(pa.ix, pc - mk3(P[k].x, P[k].y, P[k].z));
+                if (W_ARRAY && !cand[k]) w[i] = 0.0f;
+            }
+            cm[k] = __ballot(cand[k]);
+            n_here += __popcll(cm[k]);
+        }
+        int base_pos = 0;                                             // one atomic per wavefront for its (up to) 256 points
+        if (lane == 0 && n_here) base_pos = atomicAdd(sh_count, n_here);
+        base_pos = __builtin_amdgcn_readfirstlane(base_pos);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (cand[k]) list[base_pos + __popcll(cm[k] & ((1ull << lane) - 1ull))] = (SV)(i0 + k * NT + t);
+            base_pos += __popcll(cm[k]);
+        }
+    }
+}
+
+// Pass 1, stage B, the angles of the n_cand listed points (two per thread and turn, loads first): on_point(i, present, pixel)
+// runs for every listed point i with whether the model has the key of (point 1, i).  PIX: the point's pixel is loaded with
+// the other loads of the turn (the instance kernel); otherwise `pix` is not read.
+template <int NT, bool PIX, class SV, class OnPoint>
+__device__ __forceinline__ void pass1_angles(const PassArgs& pa, V3 pc, V3 nc, const SV* list, int n_cand, const int2* pix, OnPoint on_point) {
+    STAGE_THREAD()
+    const float4* spos = pa.spos;
+    const float4* snrm = pa.snrm;
+    for (int j0 = 0; j0 < n_cand; j0 += 2 * NT) {
+        int ii[2]; float4 P[2], N[2]; int2 px[2]; uint32_t key[2];
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const int j = j0 + k * NT + t;
+            ii[k] = -1; P[k] = make_float4(0, 0, 0, 0); N[k] = P[k]; px[k] = make_int2(0, 0);
+            if (j < n_cand) { ii[k] = (int)list[j]; P[k] = spos[ii[k]]; N[k] = snrm[ii[k]]; if (PIX) px[k] = pix[ii[k]]; }
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            key[k] = PPF_NO_KEY;
+            if (ii[k] >= 0) key[k] = ppf_key_device(pa.ix, pc, nc, mk3(P[k].x, P[k].y, P[k].z), mk3(N[k].x, N[k].y, N[k].z));
+        }
+#pragma unroll
+        for (int k = 0; k < 2; ++k)
+            if (ii[k] >= 0) on_point(ii[k], ppf_key_present(pa.ix, key[k]), px[k]);
+    }
+}
+
+// Compaction in scene order, per block of 4 096 points: sh_cnt holds the survivors of every (k, wavefront) of the block -- scene
+// order inside the block is k, wavefront, lane -- and the first wavefront scans them: sh_cex[x] = survivors before x, sh_cex[64]
+// the block's.  Both barriers of the scan are in here; lane and wv come from the caller's opaque thread index.
+__device__ __forceinline__ void scan_block_counts(const int* sh_cnt, int* sh_cex, int lane, int wv) {
+    __syncthreads();
+    if (wv == 0) {
+        const int v = sh_cnt[lane];
+        int inc = v;
+        for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
+        sh_cex[lane] = inc - v;
+        if (lane == 63) sh_cex[64] = inc;
+    }
+    __syncthreads();
+}
+
+// Points 2..4 (stocs.cpp:410-505 / 640-751) over the n_surv survivors of pass 1 (weights w, scene indices sv): a draw, then the
+// pass of the point drawn over the survivors that are left.  bidx[0] is point 1; fills bidx[1..3].  Returns 1 when a draw
+// found every weight zero (the attempt fails; the same in every thread), else 0.
+template <int NT, class SV>
+__device__ __forceinline__ int draw_points_2_to_4(float* w, const SV* sv, int n_surv, const PassArgs& pa, uint64_t seed, int attempt, int32_t* bidx,
+                                                  uint64_t* sh16, int* sh_pick, int draw_per_thread) {
+    int fail = 0;                                                             // (a flag and a break, not a return from inside the loop: that form spills four more registers in the lean kernel)
+    for (int k = 1; k < 4 && !fail; ++k) {
+        STAGE_THREAD()
+        const int pos = draw_block_fast(w, n_surv, rng64(seed, (uint64_t)attempt, (uint64_t)k), sh16, sh_pick, k & 1, draw_per_thread);
+        if (pos < 0) { fail = 1; break; }
+        bidx[k] = (int32_t)sv[pos];
+        if (k < 3) {
+            for (int j = t; j < n_surv; j += NT) {
+                if (w[j] == 0.0f) continue;                                   // already zero: nothing to decide
+                const int i = (int)sv[j];
+                const bool z = (k == 1) ? pass_zeroes<2>(pa, bidx[0], bidx[1], -1, i) : pass_zeroes<3>(pa, bidx[0], bidx[1], bidx[2], i);
+                if (z) w[j] = 0.0f;
+            }
+            __syncthreads();
+        }
+    }
+    return fail;
+}
+
+// the result of an attempt that has no ordered base (yet): the points as far as they were drawn (-1: none), no invariants.
+// pad = 1 marks an attempt of the lean kernel that the full-size kernel has to redo.
+__device__ __forceinline__ void write_unordered_base(BaseOut* o, int b0, int b1, int b2, int b3, int valid, int pad) {
+    o->ids[0] = b0; o->ids[1] = b1; o->ids[2] = b2; o->ids[3] = b3;
+    o->inv[0] = o->inv[1] = 0.0f; o->valid = valid; o->pad = pad;
+}
+
+// The instance kernel: two workgroups share the attempts as a pipeline.  What makes the attempts sequential is the image-space state (the
 // decayed prior, previous_segment, the segmentation buffer): it is complete once an attempt has its mask.  Points 2..4 of
 // an attempt (stocs.cpp:640-751) read that attempt's survivors only and write nothing a later attempt reads.  So the
 // first workgroup of the grid runs weights -> point 1 -> pass 1 -> mask -> bookkeeping of every attempt and hands the
@@ -747,11 +876,8 @@ __global__ __launch_bounds__(1024) void instance_attempts_kernel(InstanceArgs A,
         INST_ADV(A.cls); INST_ADV(A.prev_in); INST_ADV(A.label); INST_ADV(A.maskbits); INST_ADV(A.segbits); INST_ADV(A.parent_g); INST_ADV(A.w); INST_ADV(A.sv);
         INST_ADV(A.snrm_w); INST_ADV(A.res); INST_ADV(A.q_hdr); INST_ADV(A.q_sv); INST_ADV(A.q_w); INST_ADV(A.q_flag); INST_ADV(A.q_err);
 #undef INST_ADV
-    } else if (blockIdx.x != 0 && blockIdx.x + 1 != gridDim.x) return;     // (placement experiments launch idle workgroups in between)
+    }
     unsigned long long tprev = A.stamps ? __builtin_amdgcn_s_memtime() : 0ull;
-    // the thread index is made opaque at the start of every stage: otherwise the compiler hoists per-thread addresses of
-    // every array out of the attempt loop, and a hundred registers of them spill to scratch around every stage
-#define INST_THREAD() int t = threadIdx.x; asm volatile("" : "+v"(t)); const int lane = t & 63, wv = t >> 6; (void)lane; (void)wv;
     // (debug) the stage clocks are summed in scalar registers and written once at the end: a read-modify-write of device
     // memory per stamp would cost more than most stages
     unsigned long long acc0 = 0, acc1 = 0, acc2 = 0, acc3 = 0, acc4 = 0, acc5 = 0, acc6 = 0, acc7 = 0;
@@ -761,7 +887,7 @@ __global__ __launch_bounds__(1024) void instance_attempts_kernel(InstanceArgs A,
         const int attempt = first_attempt + a, base_num = attempt + 1;
         // ---- weights: compounding decay of the prior inside the previous segment, edge pixels pruned (stocs.cpp:572-584) ----
         {
-        INST_THREAD()
+        STAGE_THREAD()
         for (int i0 = 0; i0 < S; i0 += 4096) {
             float c[4]; uint8_t pin[4], ep[4];
 #pragma unroll
@@ -797,70 +923,19 @@ __global__ __launch_bounds__(1024) void instance_attempts_kernel(InstanceArgs A,
         const int lab = A.label[b1];
         // ---- pass 1 (stocs.cpp:596-609) + the largest pixel distance of a survivor (:610-618) ----
         {
-            INST_THREAD()
             const float4 pc4 = spos[b1], nc4 = snrm[b1];
             const V3 pc = mk3(pc4.x, pc4.y, pc4.z), nc = mk3(nc4.x, nc4.y, nc4.z);
-            int my_max = 0;
-            // stage A, distance alone (the first component of the key, rgbd.cpp:103): a point farther from P1 than the
-            // longest model pair (or within 5 mm) has no key whatever its angles; the others are listed in `sv`
-            for (int i0 = 0; i0 < S; i0 += 4096) {
-                float wi[4]; float4 P[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int i = i0 + k * 1024 + t;
-                    wi[k] = (i < S) ? w[i] : 0.0f;
-                    P[k] = make_float4(0, 0, 0, 0);
-                    if (wi[k] != 0.0f) P[k] = spos[i];
-                }
-                bool cand[4];
-                unsigned long long cm[4];
-                int n_here = 0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int i = i0 + k * 1024 + t;
-                    cand[k] = false;
-                    if (wi[k] != 0.0f) {
-                        cand[k] = i != b1 && ppf_distance_may_have_key(A.pa.ix, pc - mk3(P[k].x, P[k].y, P[k].z));
-                        if (!cand[k]) w[i] = 0.0f;
-                    }
-                    cm[k] = __ballot(cand[k]);
-                    n_here += __popcll(cm[k]);
-                }
-                int base_pos = 0;                                             // one atomic per wavefront for its (up to) 256 points
-                if (lane == 0 && n_here) base_pos = atomicAdd(&sh_nunc, n_here);
-                base_pos = __builtin_amdgcn_readfirstlane(base_pos);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    if (cand[k]) sv[base_pos + __popcll(cm[k] & ((1ull << lane) - 1ull))] = (sv_t)(i0 + k * 1024 + t);
-                    base_pos += __popcll(cm[k]);
-                }
-            }
+            pass1_list_in_range<1024, true>(A.pa, b1, pc, w, sv, &sh_nunc);
             __syncthreads();
-            // stage B, the angles of the listed points (two per thread and turn, loads first)
             const int n_cand = sh_nunc;
             if (A.stamps && threadIdx.x == 0) { A.stamps[8] += (unsigned long long)n_cand; A.stamps[10] += __builtin_amdgcn_s_memtime() - tprev; }
-            for (int j0 = 0; j0 < n_cand; j0 += 2048) {
-                int ii[2]; float4 P[2], N[2]; int2 px[2]; uint32_t key[2];
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const int j = j0 + k * 1024 + t;
-                    ii[k] = -1; P[k] = make_float4(0, 0, 0, 0); N[k] = P[k]; px[k] = make_int2(0, 0);
-                    if (j < n_cand) { ii[k] = (int)sv[j]; P[k] = spos[ii[k]]; N[k] = snrm[ii[k]]; px[k] = A.pix[ii[k]]; }
-                }
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    key[k] = PPF_NO_KEY;
-                    if (ii[k] >= 0) key[k] = ppf_key_device(A.pa.ix, pc, nc, mk3(P[k].x, P[k].y, P[k].z), mk3(N[k].x, N[k].y, N[k].z));
-                }
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    if (ii[k] < 0) continue;
-                    if (!ppf_key_present(A.pa.ix, key[k])) w[ii[k]] = 0.0f;
-                    else { const int dr = sp.x - px[k].x, dc = sp.y - px[k].y; my_max = max(my_max, dr * dr + dc * dc); }
-                }
-            }
+            int my_max = 0;
+            pass1_angles<1024, true>(A.pa, pc, nc, sv, n_cand, A.pix, [&](int i, bool present, int2 px) {
+                if (!present) w[i] = 0.0f;
+                else { const int dr = sp.x - px.x, dc = sp.y - px.y; my_max = max(my_max, dr * dr + dc * dc); }
+            });
             for (int off = 32; off > 0; off >>= 1) my_max = max(my_max, __shfl_xor(my_max, off, 64));
-            if (lane == 0 && my_max) atomicMax(&sh_max, my_max);
+            if ((threadIdx.x & 63) == 0 && my_max) atomicMax(&sh_max, my_max);
         }
         __syncthreads();
         INST_STAMP(2)
@@ -882,7 +957,7 @@ __global__ __launch_bounds__(1024) void instance_attempts_kernel(InstanceArgs A,
         //      drawn among them alone ----
         int n_surv = 0;
         {
-        INST_THREAD()
+        STAGE_THREAD()
         for (int i0 = 0; i0 < S; i0 += 4096) {
             float wi[4]; int2 px[4]; int run[4]; uint32_t mw[4];
 #pragma unroll
@@ -925,15 +1000,7 @@ __global__ __launch_bounds__(1024) void instance_attempts_kernel(InstanceArgs A,
                     sh_cnt[k * 16 + wv] = __popcll(sbal[k]);                   // scene order inside the block of 4096: k, wavefront, lane
                 }
             }
-            __syncthreads();
-            if (wv == 0) {
-                const int v = sh_cnt[lane];
-                int inc = v;
-                for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
-                sh_cex[lane] = inc - v;
-                if (lane == 63) sh_cex[64] = inc;
-            }
-            __syncthreads();
+            scan_block_counts(sh_cnt, sh_cex, lane, wv);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
                 if (keep[k]) {
@@ -946,7 +1013,7 @@ __global__ __launch_bounds__(1024) void instance_attempts_kernel(InstanceArgs A,
         }
         // ---- hand the survivors over (published at the next barrier that follows these stores) ----
         {
-            INST_THREAD()
+            STAGE_THREAD()
             for (int j = t; j < n_surv; j += 1024) { A.q_sv[(size_t)a * S + j] = (int32_t)sv[j]; A.q_w[(size_t)a * S + j] = w[j]; }
             if (t == 0) A.q_hdr[a] = make_int4(n_surv, b1, 1, 0);
         }
@@ -986,7 +1053,7 @@ __global__ __launch_bounds__(1024) void instance_attempts_kernel(InstanceArgs A,
         if (sh_abort) {                                                       // the same in every thread
             if (threadIdx.x == 0) {
                 *A.q_err = 1u;
-                for (int r = a; r < n_attempts; ++r) { BaseOut* o = A.res + r; for (int k = 0; k < 4; ++k) o->ids[k] = -1; o->inv[0] = o->inv[1] = 0; o->valid = 0; o->pad = 0; }
+                for (int r = a; r < n_attempts; ++r) write_unordered_base(A.res + r, -1, -1, -1, -1, 0, 0);
             }
             break;
         }
@@ -999,7 +1066,7 @@ __global__ __launch_bounds__(1024) void instance_attempts_kernel(InstanceArgs A,
         float* wq = w;
         sv_t* svq = sv;
         if (!fail) {
-            INST_THREAD()
+            STAGE_THREAD()
             if (WLDS) {
                 for (int j = t; j < n_surv; j += 1024) { w[j] = A.q_w[(size_t)a * S + j]; sv[j] = (sv_t)A.q_sv[(size_t)a * S + j]; }
                 __syncthreads();
@@ -1008,23 +1075,9 @@ __global__ __launch_bounds__(1024) void instance_attempts_kernel(InstanceArgs A,
                 svq = (sv_t*)(A.q_sv + (size_t)a * S);
             }
         }
-        for (int k = 1; k < 4 && !fail; ++k) {
-            INST_THREAD()
-            const int pos = draw_block_fast(wq, n_surv, rng64(seed, (uint64_t)attempt, (uint64_t)k), sh16, sh_pick, k & 1, A.draw_per_thread);
-            if (pos < 0) { fail = 1; break; }
-            bidx[k] = (int32_t)svq[pos];
-            if (k < 3) {
-                for (int j = t; j < n_surv; j += 1024) {
-                    if (wq[j] == 0.0f) continue;                              // already zero: nothing to decide
-                    const int i = (int)svq[j];
-                    const bool z = (k == 1) ? pass_zeroes<2>(A.pa, bidx[0], bidx[1], -1, i) : pass_zeroes<3>(A.pa, bidx[0], bidx[1], bidx[2], i);
-                    if (z) wq[j] = 0.0f;
-                }
-                __syncthreads();
-            }
-        }
+        if (!fail) fail = draw_points_2_to_4<1024>(wq, svq, n_surv, A.pa, seed, attempt, bidx, sh16, sh_pick, A.draw_per_thread);
         // the four points as drawn; their ordering (try_sampled_base) waits for the end of the kernel
-        if (threadIdx.x == 0) { for (int k = 0; k < 4; ++k) out->ids[k] = bidx[k]; out->inv[0] = out->inv[1] = 0; out->valid = fail ? 0 : 1; out->pad = 0; }
+        if (threadIdx.x == 0) write_unordered_base(out, bidx[0], bidx[1], bidx[2], bidx[3], fail ? 0 : 1, 0);
         __syncthreads();
         INST_STAMP(6)
     }
@@ -1050,7 +1103,6 @@ __global__ __launch_bounds__(1024) void instance_attempts_kernel(InstanceArgs A,
 // exceeds r is a non-zero one), so drawing among the compacted survivors equals drawing among all points.
 // Replaces nine launches (init, 4 x draw, 3 x pass, finalize) whose passes each walked every scene point of every attempt.
 // ---------------------------------------------------------------------------------------------------------------
-#define CLASS_TWO_LDS ((size_t)78 * 1024)     // two workgroups of class_attempts_kernel<true, true> on a CU: 2 x (this + ~1 KB of static LDS) <= 160 KB
 struct ClassArgs {
     PassArgs pa;
     int draw_per_thread;        // (the prior every attempt starts from, stocs.cpp:372-381, is the .w of the scene positions)
@@ -1064,12 +1116,8 @@ struct ClassArgs {
     const int32_t* slot_list;   // != NULL: workgroup blockIdx.x redoes attempt slot slot_list[blockIdx.x] (the lean kernel's rare overflows)
 };
 
-// TWO: built for 64 VGPRs (a few spills) so that TWO workgroups share a CU when the attempt's LDS image allows it (scenes up to ~13 000
-// points): the kernel waits on its bitmap probes and barriers most of the time, and a trial batch brings thousands of workgroups -- 64
-// linemod trials 0.90 -> 0.65 ms of sampling (33 000 -> 36 600 trials/s; 1 024 trials in one call 45 900 -> 53 500).  The 80-VGPR build
-// serves larger scenes (one workgroup per CU either way).
-template <bool WLDS, bool TWO = false>
-__global__ __launch_bounds__(1024, TWO ? 8 : 4) void class_attempts_kernel(ClassArgs A, uint64_t seed, int first_attempt, int n_attempts) {
+template <bool WLDS>
+__global__ __launch_bounds__(1024, 4) void class_attempts_kernel(ClassArgs A, uint64_t seed, int first_attempt, int n_attempts) {
     typedef typename InstTypes<WLDS>::sv_t sv_t;
     extern __shared__ __align__(16) unsigned char cls_dyn[];
     __shared__ uint64_t sh16[32];
@@ -1089,12 +1137,11 @@ __global__ __launch_bounds__(1024, TWO ? 8 : 4) void class_attempts_kernel(Class
     BaseOut* out = A.res + slot;
     int32_t bidx[4] = {-1, -1, -1, -1};
     int fail = 0;
-#define CLS_THREAD() int t = threadIdx.x; asm volatile("" : "+v"(t)); const int lane = t & 63, wv = t >> 6; (void)lane; (void)wv;
     unsigned long long tprev = A.stamps ? __builtin_amdgcn_s_memtime() : 0ull;
 #define CLS_STAMP(k) if (A.stamps && blockIdx.x == 0 && threadIdx.x == 0) { const unsigned long long now_ = __builtin_amdgcn_s_memtime(); A.stamps[k] = now_ - tprev; tprev = now_; }
     // ---- "every base will start from the prior" (stocs.cpp:372-381) ----
     {
-        CLS_THREAD()
+        STAGE_THREAD()
         for (int i0 = 0; i0 < S; i0 += 8192) {                          // the class probability travels with the scene arrays (what the LCP adds, Q8)
             float v[8];
 #pragma unroll
@@ -1115,70 +1162,17 @@ __global__ __launch_bounds__(1024, TWO ? 8 : 4) void class_attempts_kernel(Class
         const int b1 = bidx[0];
         const float4 pc4 = spos[b1], nc4 = snrm[b1];
         const V3 pc = mk3(pc4.x, pc4.y, pc4.z), nc = mk3(nc4.x, nc4.y, nc4.z);
-        {
-            CLS_THREAD()
-            for (int i0 = 0; i0 < S; i0 += 4096) {
-                float wi[4]; float4 P[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int i = i0 + k * 1024 + t;
-                    wi[k] = (i < S) ? w[i] : 0.0f;
-                    P[k] = make_float4(0, 0, 0, 0);
-                    if (wi[k] != 0.0f) P[k] = spos[i];
-                }
-                bool cand[4];
-                unsigned long long cm[4];
-                int n_here = 0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int i = i0 + k * 1024 + t;
-                    cand[k] = false;
-                    if (wi[k] != 0.0f) {
-                        cand[k] = i != b1 && ppf_distance_may_have_key(A.pa.ix, pc - mk3(P[k].x, P[k].y, P[k].z));
-                        if (!cand[k]) w[i] = 0.0f;
-                    }
-                    cm[k] = __ballot(cand[k]);
-                    n_here += __popcll(cm[k]);
-                }
-                int base_pos = 0;
-                if (lane == 0 && n_here) base_pos = atomicAdd(&sh_ncand, n_here);
-                base_pos = __builtin_amdgcn_readfirstlane(base_pos);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    if (cand[k]) sv[base_pos + __popcll(cm[k] & ((1ull << lane) - 1ull))] = (sv_t)(i0 + k * 1024 + t);
-                    base_pos += __popcll(cm[k]);
-                }
-            }
-        }
+        pass1_list_in_range<1024, true>(A.pa, b1, pc, w, sv, &sh_ncand);
         __syncthreads();
         CLS_STAMP(2)
-        {
-            CLS_THREAD()
-            const int n_cand = sh_ncand;
-            if (A.stamps && blockIdx.x == 0 && t == 0) A.stamps[8] = (unsigned long long)n_cand;
-            for (int j0 = 0; j0 < n_cand; j0 += 2048) {
-                int ii[2]; float4 P[2], N[2]; uint32_t key[2];
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const int j = j0 + k * 1024 + t;
-                    ii[k] = -1; P[k] = make_float4(0, 0, 0, 0); N[k] = P[k];
-                    if (j < n_cand) { ii[k] = (int)sv[j]; P[k] = spos[ii[k]]; N[k] = snrm[ii[k]]; }
-                }
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    key[k] = PPF_NO_KEY;
-                    if (ii[k] >= 0) key[k] = ppf_key_device(A.pa.ix, pc, nc, mk3(P[k].x, P[k].y, P[k].z), mk3(N[k].x, N[k].y, N[k].z));
-                }
-#pragma unroll
-                for (int k = 0; k < 2; ++k)
-                    if (ii[k] >= 0 && !ppf_key_present(A.pa.ix, key[k])) w[ii[k]] = 0.0f;
-            }
-        }
+        const int n_cand = sh_ncand;
+        if (A.stamps && blockIdx.x == 0 && threadIdx.x == 0) A.stamps[8] = (unsigned long long)n_cand;
+        pass1_angles<1024, false>(A.pa, pc, nc, sv, n_cand, (const int2*)NULL, [&](int i, bool present, int2) { if (!present) w[i] = 0.0f; });
         __syncthreads();
         CLS_STAMP(3)
         // ---- the surviving weights compacted in scene order, in place (position <= index) ----
         {
-            CLS_THREAD()
+            STAGE_THREAD()
             for (int i0 = 0; i0 < S; i0 += 4096) {
                 float wi[4];
                 unsigned long long sbal[4];
@@ -1189,15 +1183,7 @@ __global__ __launch_bounds__(1024, TWO ? 8 : 4) void class_attempts_kernel(Class
                     sbal[k] = __ballot(wi[k] != 0.0f);
                     if (lane == 0) sh_cnt[k * 16 + wv] = __popcll(sbal[k]);
                 }
-                __syncthreads();
-                if (wv == 0) {
-                    const int v = sh_cnt[lane];
-                    int inc = v;
-                    for (int d = 1; d < 64; d <<= 1) { const int o = __shfl_up(inc, d, 64); if (lane >= d) inc += o; }
-                    sh_cex[lane] = inc - v;
-                    if (lane == 63) sh_cex[64] = inc;
-                }
-                __syncthreads();
+                scan_block_counts(sh_cnt, sh_cex, lane, wv);
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
                     if (wi[k] != 0.0f) {
@@ -1211,23 +1197,8 @@ __global__ __launch_bounds__(1024, TWO ? 8 : 4) void class_attempts_kernel(Class
         CLS_STAMP(4)
         if (A.stamps && blockIdx.x == 0 && threadIdx.x == 0) A.stamps[9] = (unsigned long long)n_surv;
         // ---- points 2..4 (stocs.cpp:410-505) over the survivors ----
-        for (int k = 1; k < 4 && !fail; ++k) {
-            CLS_THREAD()
-            const int pos = draw_block_fast(w, n_surv, rng64(seed, (uint64_t)attempt, (uint64_t)k), sh16, sh_pick, k & 1, A.draw_per_thread);
-            if (pos < 0) { fail = 1; break; }
-            bidx[k] = (int32_t)sv[pos];
-            if (k < 3) {
-                for (int j = t; j < n_surv; j += 1024) {
-                    if (w[j] == 0.0f) continue;                               // already zero: nothing to decide
-                    const int i = (int)sv[j];
-                    const bool z = (k == 1) ? pass_zeroes<2>(A.pa, bidx[0], bidx[1], -1, i) : pass_zeroes<3>(A.pa, bidx[0], bidx[1], bidx[2], i);
-                    if (z) w[j] = 0.0f;
-                }
-                __syncthreads();
-            }
-        }
+        fail = draw_points_2_to_4<1024>(w, sv, n_surv, A.pa, seed, attempt, bidx, sh16, sh_pick, A.draw_per_thread);
     }
-#undef CLS_THREAD
     CLS_STAMP(5)
     if (threadIdx.x < 64) finalize_one_wave_call(A.pa.spos, bidx[0], bidx[1], bidx[2], bidx[3], fail, out);
     CLS_STAMP(6)
@@ -1236,7 +1207,7 @@ __global__ __launch_bounds__(1024, TWO ? 8 : 4) void class_attempts_kernel(Class
 
 // ---------------------------------------------------------------------------------------------------------------
 // The lean form of class_attempts_kernel (round 5): the same attempt, the same bases bit for bit, in 2 bytes of LDS per scene point
-// instead of 6 -- so that TWO 1024-thread workgroups share a CU on the ycb frame (14 247 points: 85 KB -> 32 KB) and on the metric
+// instead of 6 -- so that two 1024-thread workgroups share a CU on the ycb frame (14 247 points: 85 KB -> 32 KB) and on the metric
 // scene (20 000: 120 KB -> 44 KB), where a small-frame trial batch spends most of its time (64 ycb trials: 6 400 attempts on 256 CUs).
 //   * every attempt starts from the prior (stocs.cpp:372-381), so point 1 is drawn from ONE table for all attempts: the inclusive prefix
 //     sums of the 2^32 fixed-point prior weights in scene order (prior_cdf_kernel + scan, once per prior); the draw of
@@ -1248,6 +1219,7 @@ __global__ __launch_bounds__(1024, TWO ? 8 : 4) void class_attempts_kernel(Class
 // ---------------------------------------------------------------------------------------------------------------
 #define LEAN_MAX_S 32768
 #define LEAN_QUARTER_S 8000
+#define LEAN_MAX_LDS 76800   // the most dynamic LDS the lean kernel takes: two 1024-thread workgroups per CU (see lean_lds_bytes)
 #define LEAN_HALF_S 24000   // scenes up to here run the lean kernel with 512 threads, four workgroups per CU (see lean_lds_bytes)
 __global__ __launch_bounds__(256) void prior_fix_kernel(const float4* __restrict__ spos, int S, unsigned long long* __restrict__ fix) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -1278,10 +1250,9 @@ __global__ __launch_bounds__(NT, 8) void class_attempts_lean_kernel(ClassArgs A,
     BaseOut* out = A.res + slot;
     int32_t bidx[4] = {-1, -1, -1, -1};
     int fail = 0;
-#define CLS_THREAD() int t = threadIdx.x; asm volatile("" : "+v"(t)); const int lane = t & 63, wv = t >> 6; (void)lane; (void)wv;
     // ---- point 1: 64-ary search of the prior's prefix sums by the first wavefront ----
     {
-        CLS_THREAD()
+        STAGE_THREAD()
         if (t == 0) sh_ncand = 0;
         for (int i = t; i < (S + 31) / 32; i += NT) sh_alive[i] = 0u;
         if (wv == 0) {
@@ -1315,57 +1286,13 @@ __global__ __launch_bounds__(NT, 8) void class_attempts_lean_kernel(ClassArgs A,
         const int b1 = bidx[0];
         const float4 pc4 = spos[b1], nc4 = snrm[b1];
         const V3 pc = mk3(pc4.x, pc4.y, pc4.z), nc = mk3(nc4.x, nc4.y, nc4.z);
-        {
-            CLS_THREAD()
-            for (int i0 = 0; i0 < S; i0 += 4 * NT) {
-                float4 P[4];
-#pragma unroll
-                for (int k = 0; k < 4; ++k) { const int i = i0 + k * NT + t; P[k] = i < S ? spos[i] : make_float4(0, 0, 0, 0); }
-                bool cand[4];
-                unsigned long long cm[4];
-                int n_here = 0;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int i = i0 + k * NT + t;
-                    cand[k] = i < S && P[k].w != 0.0f && i != b1 && ppf_distance_may_have_key(A.pa.ix, pc - mk3(P[k].x, P[k].y, P[k].z));
-                    cm[k] = __ballot(cand[k]);
-                    n_here += __popcll(cm[k]);
-                }
-                int base_pos = 0;
-                if (lane == 0 && n_here) base_pos = atomicAdd(&sh_ncand, n_here);
-                base_pos = __builtin_amdgcn_readfirstlane(base_pos);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    if (cand[k]) cl[base_pos + __popcll(cm[k] & ((1ull << lane) - 1ull))] = (uint16_t)(i0 + k * NT + t);
-                    base_pos += __popcll(cm[k]);
-                }
-            }
-        }
+        pass1_list_in_range<NT, false>(A.pa, b1, pc, (float*)NULL, cl, &sh_ncand);
         __syncthreads();
-        {   // the angles of the listed points: a point whose key the model has survives (one bit)
-            CLS_THREAD()
-            const int n_cand = sh_ncand;
-            for (int j0 = 0; j0 < n_cand; j0 += 2 * NT) {
-                int ii[2]; float4 P[2], N[2]; uint32_t key[2];
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    const int j = j0 + k * NT + t;
-                    ii[k] = -1; P[k] = make_float4(0, 0, 0, 0); N[k] = P[k];
-                    if (j < n_cand) { ii[k] = (int)cl[j]; P[k] = spos[ii[k]]; N[k] = snrm[ii[k]]; }
-                }
-#pragma unroll
-                for (int k = 0; k < 2; ++k) {
-                    key[k] = PPF_NO_KEY;
-                    if (ii[k] >= 0) key[k] = ppf_key_device(A.pa.ix, pc, nc, mk3(P[k].x, P[k].y, P[k].z), mk3(N[k].x, N[k].y, N[k].z));
-                }
-#pragma unroll
-                for (int k = 0; k < 2; ++k)
-                    if (ii[k] >= 0 && ppf_key_present(A.pa.ix, key[k])) atomicOr(&sh_alive[ii[k] >> 5], 1u << (ii[k] & 31));
-            }
-        }
+        // the angles of the listed points: a point whose key the model has survives (one bit)
+        pass1_angles<NT, false>(A.pa, pc, nc, cl, sh_ncand, (const int2*)NULL, [&](int i, bool present, int2) { if (present) atomicOr(&sh_alive[i >> 5], 1u << (i & 31)); });
         __syncthreads();
         {   // ---- the survivors in scene order: thread t owns 32 * WPT consecutive points (WPT words of the bitmap) ----
-            CLS_THREAD()
+            STAGE_THREAD()
             constexpr int WPT = LEAN_MAX_S / 32 / NT;                 // 1 with 1024 threads, 2 with 512
             uint32_t bw[WPT];
             int cnt = 0;
@@ -1379,7 +1306,7 @@ __global__ __launch_bounds__(NT, 8) void class_attempts_lean_kernel(ClassArgs A,
             for (int x = 0; x < NT / 64; ++x) { const int v = sh_cnt[x]; if (x < wv) pre += v; tot += v; }
             n_surv = tot;
             if (n_surv > cap) {                                   // (uniform) more survivors than the list holds: the full-size kernel redoes this attempt
-                if (t == 0) { for (int k = 0; k < 4; ++k) out->ids[k] = -1; out->inv[0] = out->inv[1] = 0.0f; out->valid = 0; out->pad = 1; }
+                if (t == 0) write_unordered_base(out, -1, -1, -1, -1, 0, 1);
                 return;
             }
             int pos = pre + inc - cnt;
@@ -1396,23 +1323,8 @@ __global__ __launch_bounds__(NT, 8) void class_attempts_lean_kernel(ClassArgs A,
         }
         __syncthreads();
         // ---- points 2..4 (stocs.cpp:410-505) over the survivors ----
-        for (int k = 1; k < 4 && !fail; ++k) {
-            CLS_THREAD()
-            const int pos = draw_block_fast(w, n_surv, rng64(seed, (uint64_t)attempt, (uint64_t)k), sh16, sh_pick, k & 1, A.draw_per_thread);
-            if (pos < 0) { fail = 1; break; }
-            bidx[k] = (int32_t)sv[pos];
-            if (k < 3) {
-                for (int j = t; j < n_surv; j += NT) {
-                    if (w[j] == 0.0f) continue;                               // already zero: nothing to decide
-                    const int i = (int)sv[j];
-                    const bool z = (k == 1) ? pass_zeroes<2>(A.pa, bidx[0], bidx[1], -1, i) : pass_zeroes<3>(A.pa, bidx[0], bidx[1], bidx[2], i);
-                    if (z) w[j] = 0.0f;
-                }
-                __syncthreads();
-            }
-        }
+        fail = draw_points_2_to_4<NT>(w, sv, n_surv, A.pa, seed, attempt, bidx, sh16, sh_pick, A.draw_per_thread);
     }
-#undef CLS_THREAD
     if (threadIdx.x < 64) finalize_one_wave_call(A.pa.spos, bidx[0], bidx[1], bidx[2], bidx[3], fail, out);
 }
 
@@ -1448,7 +1360,7 @@ static int ensure_prior_cdf(stocs_ctx* c) {
 static inline bool lean_half(size_t S) { return S <= LEAN_HALF_S && !getenv("STOCS_CLASS_LEAN_1024"); }
 static inline bool lean_quarter(size_t S) { return S <= LEAN_QUARTER_S && lean_half(S) && !getenv("STOCS_CLASS_LEAN_512"); }   // 256 threads, eight attempts per CU
 static inline size_t lean_lds_bytes(size_t S) {
-    const size_t top = lean_quarter(S) ? 16384 : (lean_half(S) ? 36864 : 76800);
+    const size_t top = lean_quarter(S) ? 16384 : (lean_half(S) ? 36864 : LEAN_MAX_LDS);
     return std::max((S * 2 + 15) & ~(size_t)15, std::min<size_t>(top, (S * 6 + 31) & ~(size_t)15));
 }
 static inline int lean_cap(size_t S) {
@@ -1458,20 +1370,65 @@ static inline int lean_cap(size_t S) {
 }
 static inline bool lean_usable(const stocs_ctx* c) { return c->nS >= 64 && c->nS <= LEAN_MAX_S && !getenv("STOCS_CLASS_FULL_KERNEL") && !getenv("STOCS_INSTANCE_NO_LDS"); }
 
+// the working set of an attempt of the full-size class kernel, and of the instance kernel: 4 bytes of weight + 2 of survivor index per scene point
+static inline size_t class_work_lds(size_t S) { return ((S * 4 + 15) & ~(size_t)15) + S * 2 + 16; }
+#define MAX_DYNAMIC_LDS (160 * 1024 - 2048)   // of the 160 KB of a CU, what the static LDS of the full-size and instance kernels leaves
+
+// Which one-launch kernel runs the attempts of a scene, and with what: the one place that decides it, for a single call, a trial batch and
+// the redo of the lean kernel's overflows alike.
+enum ClassKernel { CLASS_LEAN, CLASS_FULL_LDS, CLASS_FULL_DEVICE_MEMORY };
+struct ClassForm {
+    ClassKernel kernel;
+    int threads;      // per workgroup
+    size_t lds;       // dynamic LDS per workgroup
+    int cap;          // survivors the lean kernel's list holds
+};
+// prefer_lean: whether the caller wants the lean kernel where the scene allows it.  A trial batch always does.  A single trial's 100 attempts
+// have a CU each either way: there the lean kernel pays when there are more workgroups than CUs, or when the prior's prefix sums exist
+// already -- a new frame would otherwise pay 13 us for three small launches it has no use for (sample_class).  false: the full-size kernel.
+static ClassForm choose_class_form(const stocs_ctx* c, bool prefer_lean) {
+    const size_t S = (size_t)c->nS;
+    const bool wlds = S <= 26000 && !getenv("STOCS_INSTANCE_NO_LDS");        // 6 bytes per point of the 160 KB
+    ClassForm f;
+    if (wlds && prefer_lean && lean_usable(c)) {      // 2 bytes of LDS per scene point: two to eight workgroups per CU (the rare attempt with too many survivors is redone)
+        f.kernel = CLASS_LEAN; f.threads = lean_quarter(S) ? 256 : (lean_half(S) ? 512 : 1024); f.lds = lean_lds_bytes(S); f.cap = lean_cap(S);
+    } else {
+        f.kernel = wlds ? CLASS_FULL_LDS : CLASS_FULL_DEVICE_MEMORY; f.threads = 1024; f.lds = wlds ? class_work_lds(S) : 0; f.cap = 0;
+    }
+    return f;
+}
+
+// n_workgroups attempts through the kernel of `f` -- the only code that names the instantiations of the one-launch class kernels
+static int launch_class_attempts(stocs_ctx* c, ClassArgs A, unsigned n_workgroups, uint64_t seed, int first_attempt, const ClassForm& f) {
+    const void* fn = NULL;
+    switch (f.kernel) {
+    case CLASS_LEAN:
+        fn = f.threads == 256 ? (const void*)class_attempts_lean_kernel<256> : (f.threads == 512 ? (const void*)class_attempts_lean_kernel<512> : (const void*)class_attempts_lean_kernel<1024>);
+        { const int rc = ensure_prior_cdf(c); if (rc) return rc; }
+        break;
+    case CLASS_FULL_LDS: fn = (const void*)class_attempts_kernel<true>; break;
+    case CLASS_FULL_DEVICE_MEMORY: fn = (const void*)class_attempts_kernel<false>; break;
+    }
+    // beyond 64 KB a kernel has to be told; the kernel's ceiling, not this launch's size: contexts on other threads launch the same kernels
+    // (and the runtime refuses a value that does not fit the 160 KB together with the kernel's static LDS: 4.4 KB in the lean kernel)
+    if (f.lds > 64 * 1024) STOCS_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, f.kernel == CLASS_LEAN ? LEAN_MAX_LDS : MAX_DYNAMIC_LDS));
+    int n_attempts = (int)n_workgroups, cap = f.cap;
+    const unsigned long long* cdf = (const unsigned long long*)c->d_cdf;
+    void* args[] = {&A, &seed, &first_attempt, &n_attempts, &cdf, &cap};     // (the full-size kernels take the first four)
+    STOCS_HIP_CHECK(hipLaunchKernel(fn, dim3(n_workgroups), dim3((unsigned)f.threads), args, f.lds, c->stream));
+    return STOCS_OK;
+}
+
 // attempts the lean kernel flagged (more survivors than its list holds; pad == 1 in their result): redone by the full-size kernel, in place
 static int redo_lean_overflows(stocs_ctx* c, ClassArgs A, uint64_t seed, int first_attempt, BaseOut* res_host, size_t n, int32_t* d_slots) {
     std::vector<int32_t> slots;
     for (size_t i = 0; i < n; ++i) if (res_host[i].pad == 1) slots.push_back((int32_t)i);
     if (slots.empty()) return STOCS_OK;
-    const size_t S = (size_t)c->nS;
     int rc = STOCS_OK;
     do {
         if (hipMemcpyAsync(d_slots, slots.data(), slots.size() * 4, hipMemcpyHostToDevice, c->stream) != hipSuccess) { rc = STOCS_ERR_HIP; break; }
         A.slot_list = d_slots;
-        const size_t lds = ((S * 4 + 15) & ~(size_t)15) + S * 2 + 16;
-        if (hipFuncSetAttribute((const void*)class_attempts_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048) != hipSuccess) { rc = STOCS_ERR_HIP; break; }
-        hipLaunchKernelGGL(class_attempts_kernel<true>, dim3((unsigned)slots.size()), dim3(1024), lds, c->stream, A, seed, first_attempt, (int)slots.size());
-        if (hipGetLastError() != hipSuccess) { rc = STOCS_ERR_HIP; break; }
+        if ((rc = launch_class_attempts(c, A, (unsigned)slots.size(), seed, first_attempt, choose_class_form(c, false)))) break;
         for (size_t k = 0; k < slots.size() && !rc; ++k)
             if (hipMemcpyAsync(&res_host[slots[k]], A.res + slots[k], sizeof(BaseOut), hipMemcpyDeviceToHost, c->stream) != hipSuccess) rc = STOCS_ERR_HIP;
         if (hipStreamSynchronize(c->stream) != hipSuccess) rc = STOCS_ERR_HIP;
@@ -1484,7 +1441,10 @@ static int redo_lean_overflows(stocs_ctx* c, ClassArgs A, uint64_t seed, int fir
 static int sample_class(stocs_ctx* c, uint64_t seed, int first_attempt, int nB, int32_t* ids, float* inv, int32_t* valid) {
     if (getenv("STOCS_CLASS_MULTI_KERNEL")) return sample_class_multi(c, seed, first_attempt, nB, ids, inv, valid);   // the nine-launch form (A/B)
     const size_t S = (size_t)c->nS;
-    const bool wlds = S <= 26000 && !getenv("STOCS_INSTANCE_NO_LDS");        // 6 bytes per point of the 160 KB
+    const bool dbg = getenv("STOCS_DEBUG_TIMING") != NULL;
+    const bool cdf_current = c->d_cdf && c->cdf_epoch == c->prior_epoch && c->cdf_n == S;
+    const ClassForm form = choose_class_form(c, !dbg && (nB > 256 || cdf_current || getenv("STOCS_CLASS_LEAN_KERNEL")));   // (the reasons: at choose_class_form)
+    const bool lean = form.kernel == CLASS_LEAN, wlds = form.kernel != CLASS_FULL_DEVICE_MEMORY;
     auto al = [](size_t x) { return (x + 255) / 256 * 256; };
     const size_t b_res = al((size_t)nB * sizeof(BaseOut)), b_w = wlds ? 0 : al((size_t)nB * S * 4), b_sv = wlds ? 0 : al((size_t)nB * S * 4), b_slots = al((size_t)nB * 4);
     int rc = ensure_scratch(c, b_res + b_w + b_sv + b_slots + 256);
@@ -1498,7 +1458,6 @@ static int sample_class(stocs_ctx* c, uint64_t seed, int first_attempt, int nB, 
     int32_t* d_slots = (int32_t*)((char*)c->d_scratch + b_res + b_w + b_sv + 256);   // (behind the debug stamps)
     A.draw_per_thread = 2;
     A.seeds = NULL; A.per_trial = 0; A.wg_offset = 0; A.slot_list = NULL;
-    const bool dbg = getenv("STOCS_DEBUG_TIMING") != NULL;
     A.stamps = NULL;
     if (dbg) {   // behind everything else in the scratch area
         rc = ensure_scratch(c, b_res + b_w + b_sv + 256);
@@ -1508,26 +1467,7 @@ static int sample_class(stocs_ctx* c, uint64_t seed, int first_attempt, int nB, 
         A.stamps = (unsigned long long*)(p + b_res + b_w + b_sv);
         STOCS_HIP_CHECK(hipMemsetAsync(A.stamps, 0, 128, c->stream));
     }
-    const size_t lds = wlds ? ((S * 4 + 15) & ~(size_t)15) + S * 2 + 16 : 0;
-    // (a single trial's 100 attempts have a CU each either way: the lean kernel pays when there are more workgroups than CUs, or when the
-    //  prior's prefix sums exist already -- a new frame would otherwise pay 13 us for three small launches it has no use for)
-    const bool lean = wlds && lean_usable(c) && !dbg && (nB > 256 || (c->d_cdf && c->cdf_epoch == c->prior_epoch && c->cdf_n == S) || getenv("STOCS_CLASS_LEAN_KERNEL"));
-    if (lean) {      // 2 bytes of LDS per scene point: two workgroups per CU (the rare attempt with too many survivors is redone below)
-        if ((rc = ensure_prior_cdf(c))) return rc;
-        if (lean_quarter(S)) hipLaunchKernelGGL(class_attempts_lean_kernel<256>, dim3((unsigned)nB), dim3(256), lean_lds_bytes(S), c->stream, A, seed, first_attempt, nB, (const unsigned long long*)c->d_cdf, lean_cap(S));
-        else if (lean_half(S)) hipLaunchKernelGGL(class_attempts_lean_kernel<512>, dim3((unsigned)nB), dim3(512), lean_lds_bytes(S), c->stream, A, seed, first_attempt, nB, (const unsigned long long*)c->d_cdf, lean_cap(S));
-        else hipLaunchKernelGGL(class_attempts_lean_kernel<1024>, dim3((unsigned)nB), dim3(1024), lean_lds_bytes(S), c->stream, A, seed, first_attempt, nB, (const unsigned long long*)c->d_cdf, lean_cap(S));
-    } else
-    if (wlds && lds <= CLASS_TWO_LDS && nB > 256) {     // (more workgroups than CUs: two per CU pay)
-        STOCS_HIP_CHECK(hipFuncSetAttribute((const void*)class_attempts_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CLASS_TWO_LDS));
-        hipLaunchKernelGGL((class_attempts_kernel<true, true>), dim3((unsigned)nB), dim3(1024), lds, c->stream, A, seed, first_attempt, nB);
-    } else if (wlds) {
-        STOCS_HIP_CHECK(hipFuncSetAttribute((const void*)class_attempts_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
-        hipLaunchKernelGGL(class_attempts_kernel<true>, dim3((unsigned)nB), dim3(1024), lds, c->stream, A, seed, first_attempt, nB);
-    } else {
-        hipLaunchKernelGGL(class_attempts_kernel<false>, dim3((unsigned)nB), dim3(1024), 0, c->stream, A, seed, first_attempt, nB);
-    }
-    STOCS_HIP_CHECK(hipGetLastError());
+    if ((rc = launch_class_attempts(c, A, (unsigned)nB, seed, first_attempt, form))) return rc;
     // (the attempts' results come back through the context's pinned block: a copy into a pageable std::vector takes the runtime's staging path,
     //  ~30 us of a trial)
     if ((rc = ensure_pinned(c, (size_t)PIN_VAR + (size_t)nB * sizeof(BaseOut) + 256))) return rc;
@@ -1690,12 +1630,8 @@ static int reset_instance_trial(stocs_ctx* c) {
     return STOCS_OK;
 }
 
-static int sample_instance(stocs_ctx* c, uint64_t seed, int first_attempt, int nB, float dispersion, int32_t* ids, float* inv, int32_t* valid) {
-    int rc = prepare_instance_state(c);
-    if (rc) return rc;
-    InstanceState* I = (InstanceState*)c->inst;
-    SampleBuffers sb;
-    if ((rc = carve(c, std::max(nB, 1), &sb))) return rc;
+// what the instance kernel reads that does not depend on the trial: the scene, the edge map's runs, the draw's chunking
+static InstanceArgs instance_args(const stocs_ctx* c, const InstanceState* I) {
     InstanceArgs A;
     A.pa = pass_args(c);
     A.pix = c->d_spix; A.edge_pt = I->d_edge_pt; A.pt_run = I->d_pt_run; A.run_s = I->d_run_s; A.run_e = I->d_run_e; A.row_off = I->d_row_off;
@@ -1703,9 +1639,32 @@ static int sample_instance(stocs_ctx* c, uint64_t seed, int first_attempt, int n
     A.draw_per_thread = 2;   // measured on the packed frame (3 415 points, ~290 survivors): 1..4 within 2 %, 8 and 16 slower
     if (const char* e = getenv("STOCS_DRAW_PER_THREAD")) A.draw_per_thread = std::max(1, atoi(e));
     A.H = c->prm.image_height; A.W = c->prm.image_width; A.Sw = I->Sw;
+    A.stamps = NULL;
+    return A;
+}
+
+// n_workgroups of the instance kernel (a pair per trial): the union-find parents, and up to INST_LDS_POINTS points' weights + survivor
+// indices, in LDS (<= 160 KB per workgroup on gfx950)
+static int launch_instance_attempts(stocs_ctx* c, const InstanceArgs& A, unsigned n_workgroups, uint64_t seed, int first_attempt, int n_attempts, float dispersion) {
+    const size_t lds_parent = ((size_t)(INST_MAX_NODES + 1) * 4 + 15) & ~(size_t)15;
+    const bool wlds = c->nS <= INST_LDS_POINTS && !getenv("STOCS_INSTANCE_NO_LDS");
+    const size_t lds = lds_parent + (wlds ? class_work_lds((size_t)c->nS) : 0);
+    const void* fn = wlds ? (const void*)instance_attempts_kernel<true> : (const void*)instance_attempts_kernel<false>;
+    STOCS_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYNAMIC_LDS));   // (the parents alone are beyond 64 KB)
+    void* args[] = {(void*)&A, &seed, &first_attempt, &n_attempts, &dispersion};
+    STOCS_HIP_CHECK(hipLaunchKernel(fn, dim3(n_workgroups), dim3(1024), args, lds, c->stream));
+    return STOCS_OK;
+}
+
+static int sample_instance(stocs_ctx* c, uint64_t seed, int first_attempt, int nB, float dispersion, int32_t* ids, float* inv, int32_t* valid) {
+    int rc = prepare_instance_state(c);
+    if (rc) return rc;
+    InstanceState* I = (InstanceState*)c->inst;
+    SampleBuffers sb;
+    if ((rc = carve(c, std::max(nB, 1), &sb))) return rc;
+    InstanceArgs A = instance_args(c, I);
     A.cls = I->d_cls; A.prev_in = I->d_prev_in; A.label = I->d_label; A.maskbits = I->d_maskbits; A.segbits = I->d_segbits; A.parent_g = I->d_parent;
     const bool dbg = getenv("STOCS_DEBUG_TIMING") != NULL;
-    A.stamps = NULL;
     if (dbg) { A.stamps = (unsigned long long*)I->d_parent; STOCS_HIP_CHECK(hipMemsetAsync(I->d_parent, 0, 128, c->stream)); }   // parent_g is idle for small discs
     A.w = I->d_w; A.sv = I->d_sv; A.spos_w = c->d_spos; A.snrm_w = c->d_snrmw; A.res = sb.res;
     c->prior_epoch++;       // (the kernel writes the decayed prior into the scene arrays)
@@ -1727,19 +1686,7 @@ static int sample_instance(stocs_ctx* c, uint64_t seed, int first_attempt, int n
         A.q_sv = (int32_t*)(I->d_queue + o_sv); A.q_w = (float*)(I->d_queue + o_w);
         STOCS_HIP_CHECK(hipMemsetAsync(I->d_queue + o_flag, 0, o_sv - o_flag, c->stream));   // flags and the error word
     }
-    // parents, and up to INST_LDS_POINTS points' weights + survivor indices, in LDS (<= 160 KB per workgroup on gfx950)
-    const size_t lds_parent = ((size_t)(INST_MAX_NODES + 1) * 4 + 15) & ~(size_t)15;
-    const bool wlds = c->nS <= INST_LDS_POINTS && !getenv("STOCS_INSTANCE_NO_LDS");
-    const size_t lds = lds_parent + (wlds ? ((((size_t)c->nS * 4 + 15) & ~(size_t)15) + (size_t)c->nS * 2 + 16) : 0);
-    {
-        const void* fn = wlds ? (const void*)instance_attempts_kernel<true> : (const void*)instance_attempts_kernel<false>;
-        STOCS_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
-    }
-    unsigned n_wg = 2;
-    if (const char* e = getenv("STOCS_INSTANCE_GRID")) n_wg = (unsigned)std::max(2, atoi(e));   // 9: both working workgroups on one XCD (A/B of the placement)
-    if (wlds) hipLaunchKernelGGL(instance_attempts_kernel<true>, dim3(n_wg), dim3(1024), lds, c->stream, A, seed, first_attempt, nB, dispersion);
-    else hipLaunchKernelGGL(instance_attempts_kernel<false>, dim3(n_wg), dim3(1024), lds, c->stream, A, seed, first_attempt, nB, dispersion);
-    STOCS_HIP_CHECK(hipGetLastError());
+    if ((rc = launch_instance_attempts(c, A, 2, seed, first_attempt, nB, dispersion))) return rc;
     I->h_segbits.assign((size_t)I->Sw, 0);
     // everything that comes back lands in the context's pinned block first (results | decayed prior | segment bits | error word)
     const size_t rb_res = ((size_t)nB * sizeof(BaseOut) + 255) & ~(size_t)255, rb_cls = ((size_t)c->nS * 4 + 255) & ~(size_t)255, rb_seg = ((size_t)I->Sw * 4 + 255) & ~(size_t)255;
@@ -1795,7 +1742,8 @@ int sample_trials(stocs_ctx* c, int mode, int nT, const uint64_t* seeds, int nA,
     const size_t S = (size_t)c->nS, nW = (size_t)nT * (size_t)nA;
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     if (mode == 0) {
-        const bool wlds = S <= 26000 && !getenv("STOCS_INSTANCE_NO_LDS");
+        const ClassForm form = choose_class_form(c, true);
+        const bool lean = form.kernel == CLASS_LEAN, wlds = form.kernel != CLASS_FULL_DEVICE_MEMORY;
         // scenes beyond the LDS working set keep 8 bytes per (attempt, point) in device memory: at most ~1 GB of it per launch
         const size_t per_launch = wlds ? nW : std::max<size_t>(1, std::min<size_t>(nW, ((size_t)1 << 30) / (S * 8)));
         const size_t b_res = al(nW * sizeof(BaseOut)), b_seed = al((size_t)nT * 8), b_w = wlds ? 0 : al(per_launch * S * 4), b_slots = al(nW * 4);
@@ -1812,22 +1760,10 @@ int sample_trials(stocs_ctx* c, int mode, int nT, const uint64_t* seeds, int nA,
         A.seeds = d_seeds; A.per_trial = nA; A.slot_list = NULL;
         memcpy((char*)c->h_pin + PIN_VAR, seeds, (size_t)nT * 8);
         STOCS_HIP_CHECK(hipMemcpyAsync(d_seeds, (char*)c->h_pin + PIN_VAR, (size_t)nT * 8, hipMemcpyHostToDevice, c->stream));
-        const size_t lds = wlds ? ((S * 4 + 15) & ~(size_t)15) + S * 2 + 16 : 0;
-        if (wlds) STOCS_HIP_CHECK(hipFuncSetAttribute((const void*)class_attempts_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
-        if (wlds && lds <= CLASS_TWO_LDS) STOCS_HIP_CHECK(hipFuncSetAttribute((const void*)class_attempts_kernel<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)CLASS_TWO_LDS));
-        const bool lean = wlds && lean_usable(c);
-        if (lean && (rc = ensure_prior_cdf(c))) return rc;
         for (size_t w0 = 0; w0 < nW; w0 += per_launch) {
-            const unsigned n = (unsigned)std::min(per_launch, nW - w0);
             A.wg_offset = (int)w0;
-            if (lean && lean_quarter(S)) hipLaunchKernelGGL(class_attempts_lean_kernel<256>, dim3(n), dim3(256), lean_lds_bytes(S), c->stream, A, (uint64_t)0, 0, (int)n, (const unsigned long long*)c->d_cdf, lean_cap(S));
-            else if (lean && lean_half(S)) hipLaunchKernelGGL(class_attempts_lean_kernel<512>, dim3(n), dim3(512), lean_lds_bytes(S), c->stream, A, (uint64_t)0, 0, (int)n, (const unsigned long long*)c->d_cdf, lean_cap(S));
-            else if (lean) hipLaunchKernelGGL(class_attempts_lean_kernel<1024>, dim3(n), dim3(1024), lean_lds_bytes(S), c->stream, A, (uint64_t)0, 0, (int)n, (const unsigned long long*)c->d_cdf, lean_cap(S));
-            else if (wlds && lds <= CLASS_TWO_LDS && n > 256) hipLaunchKernelGGL((class_attempts_kernel<true, true>), dim3(n), dim3(1024), lds, c->stream, A, (uint64_t)0, 0, (int)n);
-            else if (wlds) hipLaunchKernelGGL(class_attempts_kernel<true>, dim3(n), dim3(1024), lds, c->stream, A, (uint64_t)0, 0, (int)n);
-            else hipLaunchKernelGGL(class_attempts_kernel<false>, dim3(n), dim3(1024), 0, c->stream, A, (uint64_t)0, 0, (int)n);
+            if ((rc = launch_class_attempts(c, A, (unsigned)std::min(per_launch, nW - w0), 0, 0, form))) return rc;
         }
-        STOCS_HIP_CHECK(hipGetLastError());
         // (through the pinned block: 200 KB of results for 64 trials into the caller's pageable vector took the runtime's staging path)
         char* res_pin = (char*)c->h_pin + PIN_VAR + b_seed;
         STOCS_HIP_CHECK(hipMemcpyAsync(res_pin, A.res, nW * sizeof(BaseOut), hipMemcpyDeviceToHost, c->stream));
@@ -1861,27 +1797,13 @@ int sample_trials(stocs_ctx* c, int mode, int nT, const uint64_t* seeds, int nA,
         hipLaunchKernelGGL(init_trial_state_kernel, dim3((unsigned)((n + 255) / 256), (unsigned)nT), dim3(256), 0, c->stream, blk, stride, zw, o_cl, o_sn,
                            (const float4*)c->d_snrmw, (int)S);
     }
-    InstanceArgs A;
-    A.pa = pass_args(c);
-    A.pix = c->d_spix; A.edge_pt = I->d_edge_pt; A.pt_run = I->d_pt_run; A.run_s = I->d_run_s; A.run_e = I->d_run_e; A.row_off = I->d_row_off;
-    A.pairs = I->d_pairs; A.pair_off = I->d_pair_off;
-    A.draw_per_thread = 2;
-    if (const char* e = getenv("STOCS_DRAW_PER_THREAD")) A.draw_per_thread = std::max(1, atoi(e));
-    A.H = c->prm.image_height; A.W = c->prm.image_width; A.Sw = I->Sw;
+    InstanceArgs A = instance_args(c, I);
     A.cls = (float*)(blk + o_cl); A.prev_in = (uint8_t*)(blk + o_pi); A.label = (uint8_t*)(blk + o_lb); A.maskbits = (uint32_t*)(blk + o_mb);
     A.segbits = (uint32_t*)(blk + o_sb); A.parent_g = (uint32_t*)(blk + o_pa);
-    A.stamps = NULL;
     A.w = (float*)(blk + o_w); A.sv = (int32_t*)(blk + o_sv); A.spos_w = NULL; A.snrm_w = (float4*)(blk + o_sn); A.res = (BaseOut*)(blk + o_rs);
     A.q_hdr = (int4*)(blk + o_hd); A.q_flag = (unsigned int*)(blk + o_fl); A.q_err = (unsigned int*)(blk + o_er);
     A.q_sv = (int32_t*)(blk + o_qs); A.q_w = (float*)(blk + o_qw);
     A.n_trials = nT; A.trial_stride = stride; A.seeds = d_seeds;
-    const size_t lds_parent = ((size_t)(INST_MAX_NODES + 1) * 4 + 15) & ~(size_t)15;
-    const bool wlds = c->nS <= INST_LDS_POINTS && !getenv("STOCS_INSTANCE_NO_LDS");
-    const size_t lds = lds_parent + (wlds ? (((S * 4 + 15) & ~(size_t)15) + S * 2 + 16) : 0);
-    {
-        const void* fn = wlds ? (const void*)instance_attempts_kernel<true> : (const void*)instance_attempts_kernel<false>;
-        STOCS_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 2048));
-    }
     // The second workgroup of a trial polls the first's flags.  Correctness does not depend on the launch size: a consumer only waits
     // for the producer with the next-lower workgroup index, which the hardware has dispatched before it (workgroups start in index
     // order).  The launch is cut to one workgroup per CU of THIS device (a 1024-thread workgroup with this much LDS takes a whole
@@ -1897,10 +1819,8 @@ int sample_trials(stocs_ctx* c, int mode, int nT, const uint64_t* seeds, int nA,
         TR_ADV(cls); TR_ADV(prev_in); TR_ADV(label); TR_ADV(maskbits); TR_ADV(segbits); TR_ADV(parent_g); TR_ADV(w); TR_ADV(sv); TR_ADV(snrm_w); TR_ADV(res);
         TR_ADV(q_hdr); TR_ADV(q_sv); TR_ADV(q_w); TR_ADV(q_flag); TR_ADV(q_err);
 #undef TR_ADV
-        if (wlds) hipLaunchKernelGGL(instance_attempts_kernel<true>, dim3(2u * (unsigned)n), dim3(1024), lds, c->stream, B, (uint64_t)0, 0, nA, dispersion);
-        else hipLaunchKernelGGL(instance_attempts_kernel<false>, dim3(2u * (unsigned)n), dim3(1024), lds, c->stream, B, (uint64_t)0, 0, nA, dispersion);
+        if ((rc = launch_instance_attempts(c, B, 2u * (unsigned)n, 0, 0, nA, dispersion))) return rc;
     }
-    STOCS_HIP_CHECK(hipGetLastError());
     // results and error words of all trials: strided rows of the block
     std::vector<unsigned int> q_err((size_t)nT, 0u);
     STOCS_HIP_CHECK(hipMemcpy2DAsync(res_host, (size_t)nA * sizeof(BaseOut), blk + o_rs, stride, (size_t)nA * sizeof(BaseOut), (size_t)nT, hipMemcpyDeviceToHost, c->stream));

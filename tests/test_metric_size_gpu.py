@@ -98,3 +98,27 @@ def test_a_batch_at_the_metric_size_is_cut_where_the_quad_keys_end(cm_est, monke
     assert sum(r["n_candidates"] for r in res) > 44 * 3000
     for t in (0, 39, 40, 43):                                              # first and last trial of either piece
         _trial_equals_single(est, res, t, seeds[t])
+
+
+def test_the_class_kernels_agree_at_the_metric_size(cm_est, monkeypatch):
+    """100 attempts of one seed on the 20 000-point scene through the lean kernel with 1024 threads (76 800 B of dynamic LDS: beyond the
+    64 KB a launch gets without hipFuncAttributeMaxDynamicSharedMemorySize), through the full-size kernel (120 KB), and through whatever
+    the library chooses by itself: the same bases and invariants bit for bit.  (Each form against the oracle: test_pipeline_gpu.py
+    ::test_class_bases_equal_oracle on the tiny scene; the CPU oracle's index at this size is too slow for the suite.)"""
+    m, s, est = cm_est
+    got = {}
+    for form, env in (("lean_1024", ("STOCS_CLASS_LEAN_KERNEL", "STOCS_CLASS_LEAN_1024")), ("full", ("STOCS_CLASS_FULL_KERNEL",)), ("default", ())):
+        for name in env:
+            monkeypatch.setenv(name, "1")
+        est.reset_trial()
+        valid, ids, inv = est.sample_bases(4243, 100)
+        got[form] = (valid.copy(), ids.copy(), inv.copy())
+        for name in env:
+            monkeypatch.delenv(name)
+    valid, ids, inv = got["default"]
+    assert int(valid.sum()) >= 20
+    for form in ("lean_1024", "full"):
+        v, i, f = got[form]
+        assert np.array_equal(v, valid), form
+        assert np.array_equal(i, ids), form
+        assert np.array_equal(f.view(np.uint32), inv.view(np.uint32)), form
