@@ -411,7 +411,7 @@ int stocs_track_get_round(stocs_ctx* ctx, int prior, int round, float* T16_centr
  *   index-ordered lists at cell edge epsilon (24, sparse scenes), over centre-sorted lists with triangle-inequality early exit
  *   at epsilon/2 or epsilon/4 (39, dense scenes); selectable cross-checks: 31 (the per-step cooperative scan of round 2 over the
  *   centre-sorted lists) and 0 (plain lane-per-query scan).  Every selectable kernel returns the reference's scores; any other
- *   value is STOCS_ERR_INVALID (the variants that lost their A/B runs exist in the measurement build only: make tools).
+ *   value is STOCS_ERR_INVALID (the variants that lost their A/B runs are no longer in the code: DESIGN_HISTORY.md lists them).
  * "device_clock": 1 = stocs_find_congruent_all records HIP events between its kernel groups and stocs_last_call_timing reports them as
  *   "device: ..." steps; 0 (default; STOCS_DEVICE_CLOCK=1 in the environment turns it on at context creation) = the host's steps only --
  *   an event between two kernels of a stream costs ~5 us of idle queue on this runtime, nine of them 45 us of a 600 us call.
@@ -434,8 +434,8 @@ int stocs_track_get_round(stocs_ctx* ctx, int prior, int round, float* T16_centr
  *   crosses the threshold within a call or two.  When the scene BEFORE the current one crossed it, stocs_ctx_set_scene fills
  *   the new scene's field at once, on the context's auxiliary stream (a frame stream on a fixed camera will cross it again).
  * "lcp_group": lanes that verify one queued query together in the queue-fed kernels: 4 (two entries of a 128-byte list line per
- *   lane, sixteen queries per trip).  The only value of the product library (8, one entry per lane, is the form of rounds 1-3a
- *   and lives in the measurement build).
+ *   lane, sixteen queries per trip).  The only value, in every build: anything else is STOCS_ERR_INVALID (8, one entry per lane,
+ *   was the form of rounds 1-3a; DESIGN_HISTORY.md).
  * "exact_ties": 0 (default) = a query whose nearest scene points lie at exactly the same float32 distance takes the one with the
  *   largest scene index (divergence Q11: every other integer result already equals the reference's).  1 = it takes the point the
  *   reference's kd-tree (kdtree.h:394-459) returns -- the one its visiting order reaches last -- so that every (candidate, model

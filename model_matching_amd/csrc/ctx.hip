@@ -541,7 +541,6 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
     c->d_spos = c->d_snrmw = c->d_mpos = c->d_mnrm = c->d_munit = c->d_mpos_raw = c->d_mpos_s = c->d_mnrm_s = NULL;
     c->d_spix = NULL; c->d_mperm = NULL; c->d_mpatch = NULL; c->d_msub = NULL; c->d_scene_mem = NULL; c->scene_cap = 0;
     c->patch_r_ref = 0.0f; c->scene_scored = 0; c->scene_work = 0.0;
-    c->lcp_group = getenv("STOCS_LCP_GROUP") ? atoi(getenv("STOCS_LCP_GROUP")) : 4;
     c->lcp_cull = getenv("STOCS_LCP_CULL") ? atoi(getenv("STOCS_LCP_CULL")) : 1;
     c->lcp_cull_unit = 16;
     c->lcp_cull_after = 1.0e9; c->prev_scene_warm = false; c->cull_pending = false; c->ev_cull = NULL;

@@ -20,6 +20,11 @@
 // queries that survive the sub-cell mask in a per-wave LDS ring and verifies them 16 at a time, four lanes per query
 // with two entries of a 128-byte list line each.
 //
+// Kernels: lcp_coopq_kernel (six named switches, the table of its legal forms above it), lcp_coop_kernel (the per-step scan of dense
+// scenes, a cross-check), lcp_kernel (a lane per query, a cross-check) and lcp_exact_kernel (exact_ties).  choose_lcp_form picks one,
+// launch_lcp_form is the only place that names their instantiations.  The forms that lost their A/B runs are listed in
+// DESIGN_HISTORY.md with the last commit that holds their code; a measurement build (make tools) adds the ablation bits only.
+//
 // Roofline: HBM-read model, algorithmic bytes 68 + 52*|M| per pose.
 #include <stdlib.h>
 #include <string.h>
@@ -28,6 +33,7 @@
 
 
 #include <algorithm>
+#include <utility>
 
 #include "kdtree.h"
 #include "prims.h"
@@ -107,7 +113,6 @@ __device__ __forceinline__ const float4* lcp_weights_of(const LcpArgs& a, int ca
 #define DPP_QUAD_XOR1 0xB1   /* quad_perm [1,0,3,2] */
 #define DPP_QUAD_XOR2 0x4E   /* quad_perm [2,3,0,1] */
 #define DPP_HALF_MIRROR 0x141 /* lane k <-> 7-k inside each group of 8 */
-#define DPP_ROW_SHR(n) (0x110 + (n))
 
 // Score accumulation.  The reference adds class probabilities in a sequential float loop (stocs.cpp:1033); a parallel
 // kernel cannot keep that order, so the weights are added as 2^32 fixed-point integers instead: exact for every weight
@@ -201,15 +206,17 @@ __global__ __launch_bounds__(256) void lcp_kernel(LcpArgs a, const float* __rest
 }
 
 // ---------------------------------------------------------------------------------------------
-// Variant 1 ("coop8"): what the ISA of v0 shows (profiles/r01_lcp_analysis.md): its list loop issues
-// ~18 instructions per trip for the ~18 of 64 lanes that own a list, i.e. about one issued
-// wave-instruction per list entry, and every entry is its own 16-byte gather.  Here the hit queries
-// of a step are compacted through LDS and each 8-lane group takes ONE query: the group streams the
-// query's 8-padded list one 128-byte line per load (all 64 lanes useful), keeps its running best in
-// registers across chunks, and reduces once per query with DPP (pure VALU; __shfl/ds_bpermute would go
-// through the LDS pipeline).  ~13 instructions per 64 entries instead of ~18 per ~18.
-// Tie rule identical to v0: smallest d^2, then largest scene index; same lane -> point assignment
-// and reduction tree, so scores are bitwise equal to v0.
+// Per-step cooperative scan of dense scenes (lcp_variant 31): the independent cross-check of the queue kernel's dense form.
+// What the ISA of lcp_kernel shows (profiles/r01_lcp_analysis.md): its list loop issues ~18 instructions per trip for the ~18 of
+// 64 lanes that own a list, i.e. about one issued wave-instruction per list entry, and every entry is its own 16-byte gather.
+// Here the hit queries of a step are compacted through LDS and each 8-lane group takes ONE query: the group streams the query's
+// 8-padded list two 128-byte lines per trip (all 64 lanes useful), keeps its running best in registers across lines, and reduces
+// once per query with DPP (pure VALU; __shfl/ds_bpermute would go through the LDS pipeline).  The lists are sorted by distance
+// from the cell centre, with a lower bound of that distance per line: a query stops at the first line that the triangle
+// inequality rules out.  Tie rule identical to lcp_kernel: smallest d^2, then largest scene index; same lane -> point assignment
+// and reduction tree, so scores are bitwise equal to it.
+// SPLIT: four wavefronts share one candidate (see lcp_coopq_kernel); else one wavefront per candidate -- one per workgroup when
+// scoring, four candidates per 256-thread workgroup in the detail form.
 // ---------------------------------------------------------------------------------------------
 template <int CTRL>
 __device__ __forceinline__ float dpp_f32(float v) {
@@ -220,10 +227,10 @@ __device__ __forceinline__ int dpp_i32(int v) {
     return __builtin_amdgcn_update_dpp(0, v, CTRL, 0xF, 0xF, true);
 }
 
-// minimum of a squared distance over the 8 lanes of a query group.  Squared distances are non-negative and never NaN here
+// minimum of a squared distance over the GL lanes of a query group.  Squared distances are non-negative and never NaN here
 // (a NaN distance fails `d <= best` and is never kept), so their bit patterns order like unsigned integers: an integer
 // minimum needs no NaN canonicalisation and takes its DPP operand directly -- 3 instructions instead of 10.
-template <int GL = 8>
+template <int GL>
 __device__ __forceinline__ float group_min_nonneg(float v) {
     uint32_t u = __float_as_uint(v);
     if (GL >= 2) u = min(u, (uint32_t)__builtin_amdgcn_update_dpp((int)u, (int)u, DPP_QUAD_XOR1, 0xF, 0xF, false));
@@ -231,17 +238,23 @@ __device__ __forceinline__ float group_min_nonneg(float v) {
     if (GL == 8) u = min(u, (uint32_t)__builtin_amdgcn_update_dpp((int)u, (int)u, DPP_HALF_MIRROR, 0xF, 0xF, false));
     return __uint_as_float(u);
 }
-__device__ __forceinline__ float group8_min_nonneg(float v) { return group_min_nonneg<8>(v); }
 
-template <bool DETAIL, int UNR, bool MASK = true, bool EARLY = false, bool IDX = true, int WPB = 4, bool SPLIT = false>
-__global__ __launch_bounds__(64 * WPB) void lcp_coop_kernel(LcpArgs a, const float* __restrict__ T16, float* __restrict__ out,
+// wavefronts per workgroup of the cooperative kernels: the four that share a candidate (SPLIT); four candidates side by side in
+// the detail form; else a workgroup is one wavefront
+constexpr int lcp_waves_per_block(bool detail, bool split) { return (split || detail) ? 4 : 1; }
+
+template <bool DETAIL, bool SPLIT>
+__global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT)) void lcp_coop_kernel(LcpArgs a, const float* __restrict__ T16, float* __restrict__ out,
                                                        int n, int32_t* __restrict__ hit_out, uint8_t* __restrict__ cnt_out) {
+    static_assert(!(DETAIL && SPLIT), "the detail form is not split");
+    constexpr int WPB = lcp_waves_per_block(DETAIL, SPLIT);
+    constexpr int UNR = 2;             // list lines per trip
     __shared__ float4 qt[WPB][64];     // per lane: qx, qy, qz, bits(list offset)
     __shared__ uint32_t qn[WPB][64];   // per lane: list length
     __shared__ uint32_t hl[WPB][64];   // compacted hit list: r-th hit lane
     __shared__ float rd[WPB][64];      // per lane: best d^2
     __shared__ int ri[WPB][64];        // per lane: best scene index
-    __shared__ float qd[WPB][64];      // per lane: |query - cell centre| (EARLY)
+    __shared__ float qd[WPB][64];      // per lane: |query - cell centre|
     __shared__ unsigned long long part[WPB];
     const int lane = threadIdx.x & 63;
     const int sub = lane & 7, grp = lane >> 3;
@@ -275,13 +288,11 @@ __global__ __launch_bounds__(64 * WPB) void lcp_coop_kernel(LcpArgs a, const flo
                     // sub-cell filter: no scene point within epsilon of this 1/4-cell => no neighbour possible
                     const int sb = ((int)((uz - fz) * 4.0f) << 4) | ((int)((uy - fy) * 4.0f) << 2) | (int)((ux - fx) * 4.0f);
                     const uint32_t mw = a.has_nearest ? 0xFFFFFFFFu : (sb < 32 ? cw.z : cw.w);   // (has_nearest: no mask on this grid, z holds a distance)
-                    off = cw.x; cnt = (!MASK || ((mw >> (sb & 31)) & 1u)) ? cw.y : 0u;
+                    off = cw.x; cnt = ((mw >> (sb & 31)) & 1u) ? cw.y : 0u;
                     if (STOCS_ABLATE(a, 2)) cnt = cw.x == 0xFFFFFFF1u ? 1u : 0u;   // 2: look-ups done, nobody survives
-                    if (EARLY) {
-                        const float ex = qx - (a.ox + ((float)cx + 0.5f) * a.h), ey = qy - (a.oy + ((float)cy + 0.5f) * a.h),
-                                    ez = qz - (a.oz + ((float)cz + 0.5f) * a.h);
-                        qcd = sqrtf(ex * ex + (ey * ey + ez * ez));
-                    }
+                    const float ex = qx - (a.ox + ((float)cx + 0.5f) * a.h), ey = qy - (a.oy + ((float)cy + 0.5f) * a.h),
+                                ez = qz - (a.oz + ((float)cz + 0.5f) * a.h);
+                    qcd = sqrtf(ex * ex + (ey * ey + ez * ez));
                 }
             }
         }
@@ -295,7 +306,7 @@ __global__ __launch_bounds__(64 * WPB) void lcp_coop_kernel(LcpArgs a, const flo
                 hl[w][rank] = (uint32_t)lane;
                 qt[w][lane] = make_float4(qx, qy, qz, __int_as_float((int)off));
                 qn[w][lane] = cnt;
-                if (EARLY) qd[w][lane] = qcd;
+                qd[w][lane] = qcd;
             }
             __builtin_amdgcn_wave_barrier();
             for (int s = 0; s < nh; s += 8) {
@@ -307,47 +318,31 @@ __global__ __launch_bounds__(64 * WPB) void lcp_coop_kernel(LcpArgs a, const flo
                 const float4* lp = a.list + (uint32_t)__float_as_int(qq.w) + sub;
                 float gd = a.sq_eps;
                 int gi = -1;
-                if (EARLY) {
-                    // lists are sorted by distance from the cell centre: stop at the first chunk that the
-                    // triangle inequality rules out (|q - p| >= |p - c| - |q - c| > sqrt(best) for all later p)
-                    const float qcg = qd[w][L];
-                    const uint32_t chunk0 = (uint32_t)__float_as_int(qq.w) >> 3;
-                    uint32_t nchunks = (c + 7u) >> 3;
-                    float gb = a.sq_eps;   // best d^2 of the whole group so far
-                    if (STOCS_ABLATE(a, 4)) nchunks = min(nchunks, (uint32_t)UNR);   // 4: the first trip of every list only
-                    for (uint32_t j = 0; __any(j < nchunks); j += UNR) {
-                        if (j < nchunks && j > 0 && (STOCS_ABLATE(a, 256) ? 0.0f : a.chunk_r[chunk0 + j]) - qcg > sqrtf(gb) + a.bound_margin) nchunks = 0;   // 256: no chunk bounds (scan everything)
-                        float4 e[UNR];
-#pragma unroll
-                        for (int u = 0; u < UNR; ++u) {
-                            e[u] = make_float4(1e30f, 1e30f, 1e30f, __int_as_float(-1));
-                            if (j + u < nchunks) e[u] = lp[(j + u) << 3];
-                        }
-#pragma unroll
-                        for (int u = 0; u < UNR; ++u) {
-                            const float dx = qq.x - e[u].x, dy = qq.y - e[u].y, dz = qq.z - e[u].z;
-                            const float d = dx * dx + (dy * dy + dz * dz);
-                            const int ei = __float_as_int(e[u].w);
-                            if (d < gd || (d == gd && ei > gi)) { gd = d; gi = ei; }   // lists are no longer in index order
-                        }
-                        gb = fminf(gd, dpp_f32<DPP_QUAD_XOR1>(gd));
-                        gb = fminf(gb, dpp_f32<DPP_QUAD_XOR2>(gb));
-                        gb = fminf(gb, dpp_f32<DPP_HALF_MIRROR>(gb));
-                    }
-                } else
-                for (uint32_t k = 0; __any(k < c); k += 8 * UNR) {
+                // lists are sorted by distance from the cell centre: stop at the first chunk that the
+                // triangle inequality rules out (|q - p| >= |p - c| - |q - c| > sqrt(best) for all later p)
+                const float qcg = qd[w][L];
+                const uint32_t chunk0 = (uint32_t)__float_as_int(qq.w) >> 3;
+                uint32_t nchunks = (c + 7u) >> 3;
+                float gb = a.sq_eps;   // best d^2 of the whole group so far
+                if (STOCS_ABLATE(a, 4)) nchunks = min(nchunks, (uint32_t)UNR);   // 4: the first trip of every list only
+                for (uint32_t j = 0; __any(j < nchunks); j += UNR) {
+                    if (j < nchunks && j > 0 && (STOCS_ABLATE(a, 256) ? 0.0f : a.chunk_r[chunk0 + j]) - qcg > sqrtf(gb) + a.bound_margin) nchunks = 0;   // 256: no chunk bounds (scan everything)
                     float4 e[UNR];
 #pragma unroll
                     for (int u = 0; u < UNR; ++u) {
                         e[u] = make_float4(1e30f, 1e30f, 1e30f, __int_as_float(-1));
-                        if (k + 8 * u < c) e[u] = lp[k + 8 * u];   // whole 128-byte line per group; tail entries are sentinels
+                        if (j + u < nchunks) e[u] = lp[(j + u) << 3];   // whole 128-byte line per group; tail entries are sentinels
                     }
 #pragma unroll
                     for (int u = 0; u < UNR; ++u) {
                         const float dx = qq.x - e[u].x, dy = qq.y - e[u].y, dz = qq.z - e[u].z;
                         const float d = dx * dx + (dy * dy + dz * dz);
-                        take_if_better<IDX>(d, __float_as_int(e[u].w), gd, gi);
+                        const int ei = __float_as_int(e[u].w);
+                        if (d < gd || (d == gd && ei > gi)) { gd = d; gi = ei; }   // the lists are not in index order
                     }
+                    gb = fminf(gd, dpp_f32<DPP_QUAD_XOR1>(gd));
+                    gb = fminf(gb, dpp_f32<DPP_QUAD_XOR2>(gb));
+                    gb = fminf(gb, dpp_f32<DPP_HALF_MIRROR>(gb));
                 }
                 // group minimum of d^2 (DPP), then the largest index among the lanes that hold it
                 float dm = fminf(gd, dpp_f32<DPP_QUAD_XOR1>(gd));
@@ -430,90 +425,102 @@ __device__ __forceinline__ bool lcp_patch_dead(const LcpArgs& a, const float4 sp
 }
 
 // ---------------------------------------------------------------------------------------------
-// Variant 20 ("coop8 + queue"): the cooperative scan of variant 1 fed from a per-wave LDS ring that
-// collects the hit queries of successive steps (ballot + mbcnt compaction), so that every 8-lane group
-// always owns a query (with ~11 hits per 64-point step the groups of variant 1 are ~69 % busy) and the
-// normal test runs on full wavefronts.  Lane <-> point assignment of the accumulation differs from v0,
-// so scores agree with v0 to rounding (1e-7), not bitwise; still run-to-run deterministic.
+// Queue-fed cooperative scan (lcp_variant 24 on sparse scenes, 39 on dense ones; the automatic choice): the cooperative scan of
+// lcp_coop_kernel fed from a per-wave LDS ring that collects the hit queries of successive steps (ballot + mbcnt compaction), so
+// that every lane group always owns a query (with ~11 hits per 64-point step the groups of the per-step scan are ~69 % busy) and
+// the normal test runs on full wavefronts.  Lane <-> point assignment of the accumulation differs from lcp_kernel, the sums are
+// integers: the scores are the same bit for bit, and run-to-run deterministic.
+//
+// The switches:
+//   DETAIL  write hit_out / cnt_out (per-point results for the parity tests).  Changes what is written, not how it is computed --
+//           but for the workgroup shape: four candidates per 256-thread workgroup, not split, brick look-ups.
+//   DENSE   dense scenes: lists sorted by distance from the cell centre (not by index), a lower bound of that distance per
+//           8-entry line; a query stops at the first line the triangle inequality rules out, as in lcp_coop_kernel -- but fed from
+//           the queue, so that the first lines of 16 queries are in flight together.  Else index-ordered lists, walked to the end.
+//   SPLIT   the four wavefronts of a workgroup share ONE candidate and take its 64-point steps round-robin (a trial's ~8 000
+//           candidates are a single round of wavefronts on the chip, and four times as many, four times shorter wavefronts finish
+//           it sooner; big batches lose nothing); the partial sums are integers, so the score is the same bit for bit.
+//           Else one wavefront per candidate.
+//   FLAT    the cell word comes from the flat cell table (one look-up) instead of top -> brick -> cell.
+//   NEAR    pruned lists on grids finer than epsilon (has_nearest): the cell word's z is a lower bound of |cell centre - nearest
+//           listed point| (no sub-cell mask there); a query farther from the centre than that bound + epsilon never touches the
+//           list -- DENSE's first test without its line-by-line exit, which lists of ~5 entries have no use for.
+//   CU      (lcp_cull_unit) points per bounding sphere of the patch test: 64, whole steps; 16, sub-patches, the live ones packed
+//           four to a step.
+//
+// The legal forms (24 instantiations; the static_assert rejects every other):
+//   scoring, sparse   DENSE = 0, SPLIT in {0, 1}, FLAT in {0, 1}, NEAR in {0, 1}, CU in {16, 64}         16 forms
+//   scoring, dense    DENSE = 1, SPLIT = 1, FLAT = 0, NEAR = 0, CU in {16, 64}                            2 forms
+//                     (the dense queue form is always split, whatever lcp_split and the model size say)
+//   detail, sparse    DENSE = 0, SPLIT = 0, FLAT = 0, NEAR in {0, 1}, CU in {16, 64}                      4 forms
+//   detail, dense     DENSE = 1, SPLIT = 0, FLAT = 0, NEAR = 0, CU in {16, 64}                            2 forms
 // ---------------------------------------------------------------------------------------------
-// SPLIT: the WPB wavefronts of a workgroup share ONE candidate and take its 64-point steps round-robin (a trial's ~8 000
-// candidates are a single round of wavefronts on the chip, and four times as many, four times shorter wavefronts finish
-// it sooner; big batches lose nothing); the partial sums are integers, so the score is the same bit for bit.
-// TILE (tools build, A/B only): the WPB candidates of a workgroup read the model points from a 256-point tile staged in LDS
-// (one global load per point and workgroup instead of one per wavefront), at the price of a workgroup barrier per tile.
-// EARLY (dense scenes: lists sorted by distance from the cell centre, a lower bound of that distance per 8-entry line): a query
-// stops at the first line the triangle inequality rules out, as in variant 31 -- but fed from the queue, so that the first
-// lines of 32 queries are in flight together where variant 31 has the two lines of 8.
-// NEAR (pruned lists on grids finer than epsilon, round 5): the cell word's z is a lower bound of |cell centre - nearest listed point|
-// (no sub-cell mask there); a query farther from the centre than that bound + epsilon never touches the list -- EARLY's first test
-// without its line-by-line exit, which lists of ~5 entries have no use for.
-// TINY (round 5, with GL = 4 on index-ordered lists): after the dominance pruning most surviving queries see a list of at most four entries.
-// Those are verified by TWO lanes each (two entries per lane, 32 queries per trip of the wavefront) instead of four: the texture addresser
-// -- the unit this kernel sits on -- takes four lane addresses per clock whatever their width, so a four-entry list read by four lanes x two
-// entries costs twice the addresses it needs.  The pending queries are ordered tiny lists first; a trip is a two-lane trip while 32 tiny
-// queries are left.
-// CU (lcp_cull_unit): points per bounding sphere of the patch test -- 64, whole steps; 16, sub-patches, the live ones packed four to a step.
-template <bool DETAIL, int UNR, bool SORTQ = false, int PIPE = 4, bool IDX = true, int WPB = 4, int FLAT = 0, bool SPLIT = false, bool TILE = false, bool EARLY = false, int GL = 8, int FIRST = 1, bool NOSENT = false, bool NEAR = false, bool TINY = false, int CU = 64>
-__global__ __launch_bounds__(64 * WPB, 8) void lcp_coopq_kernel(LcpArgs a, const float* __restrict__ T16, float* __restrict__ out,
+constexpr bool lcp_queue_form_legal(bool detail, bool dense, bool split, bool flat, bool near, int cu) {
+    return (cu == 16 || cu == 64) && (detail ? (!split && !flat && !(dense && near)) : (!dense || (split && !flat && !near)));
+}
+
+template <bool DETAIL, bool DENSE, bool SPLIT, bool FLAT, bool NEAR, int CU>
+__global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lcp_coopq_kernel(LcpArgs a, const float* __restrict__ T16, float* __restrict__ out,
                                                         int n, int32_t* __restrict__ hit_out, uint8_t* __restrict__ cnt_out) {
+    static_assert(lcp_queue_form_legal(DETAIL, DENSE, SPLIT, FLAT, NEAR, CU), "not one of the forms in the table above");
+    constexpr int WPB = lcp_waves_per_block(DETAIL, SPLIT);
+    constexpr bool IDX = !DENSE;     // index-ordered lists: `<=` implements the tie rule (take_if_better)
+    constexpr bool EARLY = DENSE;    // centre-sorted lists: line-by-line exit
+    // GL lanes verify one query together: each reads EPL entries of a 128-byte list line, NG queries per trip.  Four lanes with two
+    // entries each and one trip in flight: Cm 1.34 -> 1.18 ms against eight lanes with one entry each and four trips in flight
+    // (profiles/r03_lcp_patch_and_group_ab.json); two lanes 1.45 ms, a lane per query 3.16 ms
+    constexpr int GL = 4, EPL = 8 / GL, NG = 64 / GL;
+    // FIRST: list lines requested in a query's first trip (the second line of a list that has one arrives with the first: half of
+    // the survivors' lists at Cm are longer than a line; one line: +2 % at 65 536 candidates, +7 % at 8 192; three: +3 %); not with
+    // EARLY, whose later lines wait for the bound test -- early exit decides line by line
+    constexpr int FIRST = DENSE ? 1 : 2, E0 = EPL * FIRST;
+    // NOSENT: no sentinel entries, no predicated list loads -- a group without a query reads list line 0 (its result is never
+    // stored), a list shorter than the trip reads its last line again: the same entries, the same winner (predicated loads and
+    // sentinels: +1.2 %, +2.4 % at 8 192 candidates).  Not with EARLY, which skips the lines it rules out instead of reading them
+    constexpr bool NOSENT = !DENSE;
+    constexpr int UNR = 1;           // list lines per trip after the first (two: +3 %)
+    constexpr int PIPE = 1;          // trips in flight (two: 1.18 -> 1.185 ms at Cm; three and four spill)
+    static_assert(!EARLY || (FIRST == 1 && !NOSENT), "early exit decides line by line");
     __shared__ float4 qt[WPB][128];     // qx, qy, qz, bits(list offset)
     __shared__ float qcd[EARLY ? WPB : 1][EARLY ? 128 : 1];   // |query - cell centre| (EARLY)
     __shared__ uint32_t qn[WPB][128];   // list length
     __shared__ uint32_t qs[WPB][128];   // model slot (patch order)
     __shared__ int ri[WPB][128];        // best scene index
-    __shared__ uint8_t ord[WPB][64];    // batch order sorted by list length (SORTQ)
+    __shared__ uint8_t ord[WPB][64];    // batch order sorted by list length
     __shared__ unsigned long long part[WPB];
     const int lane = threadIdx.x & 63;
-    // GL lanes verify one query together: each reads EPL = 8 / GL entries of a 128-byte list line (GL = 8: one entry per lane, eight
-    // queries per trip; GL = 4: two entries per lane, sixteen queries per trip and one reduction level less)
-    // FIRST: list lines requested in a query's first trip (the second line of a list that has one arrives with the first: half of
-    // the survivors' lists at Cm are longer than a line); not with EARLY, whose later lines wait for the bound test
-    constexpr int EPL = 8 / GL, E0 = EPL * FIRST;
-    static_assert(!EARLY || FIRST == 1, "early exit decides line by line");
-    static_assert(!TINY || (GL == 4 && SORTQ && IDX && !EARLY && PIPE == 1), "two-lane trips: the four-lane queue form on index-ordered lists");
-#if defined(STOCS_TOOLS_BUILD) && defined(STOCS_LCP_W_UNIFORM)
-    // measurement build only (profiles/r04_lcp_w_uniform_isa.md): the wavefront index forced into an SGPR.  63 VGPRs, 8 waves -- and
-    // 12 % SLOWER: every LDS address of the per-wavefront queue (qt[w][..], qn[w][..], ri[w][..]) is then formed as "scalar base +
-    // vector index" with the scalar part re-materialised into a VGPR at each use instead of living in one address VGPR
-    const int w = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-#else
+    // (the wavefront index stays in a VGPR: forced into an SGPR the kernel is 12 % slower, profiles/r04_lcp_w_uniform_isa.md)
     const int w = threadIdx.x >> 6;
-#endif
     const int cand = SPLIT ? lcp_candidate(a, n, 0, 1) : lcp_candidate(a, n, w, WPB);
-    if (cand < 0 && !TILE) return;   // SPLIT: the whole workgroup leaves together; TILE: the wavefront stays for the barriers
+    if (cand < 0) return;   // SPLIT: the whole workgroup leaves together
     const float4* __restrict__ snrmw = lcp_weights_of(a, cand);
-    const float* T = T16 + (size_t)(cand < 0 ? 0 : cand) * 16;
+    const float* T = T16 + (size_t)cand * 16;
     const float t0 = T[0], t1 = T[1], t2 = T[2], t4 = T[4], t5 = T[5], t6 = T[6], t8 = T[8], t9 = T[9], t10 = T[10],
                 t12 = T[12], t13 = T[13], t14 = T[14];
     unsigned long long acc = 0ull;
     int head = 0, tail = 0;
 
     auto process = [&](int nq) {
-        int n_tiny = 0;
-        // order the pending queries by list length (number of 128-byte chunks) so that the eight
-        // groups of a step stream lists of similar length: a counting sort on <= 8 classes with ballots
-        if (SORTQ) {
-            // (most lists are one or two lines: three classes -- one line, two, more -- keep the eight groups of a step on
-            //  lists of similar length at a third of the instructions of a sort over all lengths)
-            uint32_t cls = 4;
+        // order the pending queries by list length (number of 128-byte lines) so that the groups of a trip stream lists of
+        // similar length: a counting sort with ballots (without it, two trips in flight: Cm 1.185 -> 1.24 ms).  Most lists are one or two lines:
+        // three classes -- one trip, two, more -- do it at a third of the instructions of a sort over all lengths
+        {
+            uint32_t cls = 4;   // no query
             if (lane < nq) {
-                const uint32_t cq = qn[w][(head + lane) & 127], nch = (cq + 7u) >> 3;
-                cls = (TINY && cq <= 4u) ? 0u : (nch <= (uint32_t)FIRST ? 1u : (nch <= (uint32_t)(FIRST + UNR) ? 2u : 3u));   // at most four entries; one trip, two, more
+                const uint32_t nch = (qn[w][(head + lane) & 127] + 7u) >> 3;
+                cls = nch <= (uint32_t)FIRST ? 1u : (nch <= (uint32_t)(FIRST + UNR) ? 2u : 3u);
             }
             const unsigned long long below = (1ull << lane) - 1ull;
-            const unsigned long long mt = __ballot(cls == 0u), m0 = __ballot(cls == 1u), m1 = __ballot(cls == 2u), m2 = __ballot(cls == 3u);
-            const int nt = __popcll(mt), n0 = __popcll(m0), n1 = __popcll(m1);
-            n_tiny = nt;
-            const int pos = cls == 0u ? __popcll(mt & below) : (cls == 1u ? nt + __popcll(m0 & below) : (cls == 2u ? nt + n0 + __popcll(m1 & below) : nt + n0 + n1 + __popcll(m2 & below)));
+            const unsigned long long m1 = __ballot(cls == 1u), m2 = __ballot(cls == 2u), m3 = __ballot(cls == 3u);
+            const int n1 = __popcll(m1), n2 = __popcll(m2);
+            const int pos = cls == 1u ? __popcll(m1 & below) : (cls == 2u ? n1 + __popcll(m2 & below) : n1 + n2 + __popcll(m3 & below));
             if (lane < nq) ord[w][pos] = (uint8_t)lane;
             __builtin_amdgcn_wave_barrier();
         }
-        // PIPE query-steps are in flight together: their first 128-byte list lines (most lists are a single
-        // line) are requested back to back, so one memory round trip serves PIPE*8 queries
-        for (int s0 = 0; s0 < nq;) {
-            const bool two = TINY && s0 + 32 <= n_tiny;          // (uniform) a trip of 32 tiny lists, two lanes each
-            const int gl = two ? 2 : GL, NG = two ? 32 : 64 / GL;
-            const int sub = lane & (gl - 1), grp = two ? (lane >> 1) : lane / GL;
+        // a trip: NG queries, GL lanes each.  The first FIRST lines of the lists of PIPE trips are requested back to back, then
+        // compared: one memory round trip serves most of the queries
+        for (int s0 = 0; s0 < nq; s0 += NG * PIPE) {
+            const int sub = lane & (GL - 1), grp = lane / GL;
             float4 e0[PIPE][E0];
             bool wide[PIPE];
             int idxs[PIPE];
@@ -522,7 +529,7 @@ __global__ __launch_bounds__(64 * WPB, 8) void lcp_coopq_kernel(LcpArgs a, const
             for (int u = 0; u < PIPE; ++u) {
                 const int slot = s0 + NG * u + grp;
                 const bool gact = slot < nq;
-                idxs[u] = (head + (SORTQ ? (int)ord[w][gact ? slot : 0] : slot)) & 127;
+                idxs[u] = (head + (int)ord[w][gact ? slot : 0]) & 127;
                 cs[u] = gact ? qn[w][idxs[u]] : 0u;
                 wide[u] = true;
                 if (!NOSENT) {
@@ -539,20 +546,19 @@ __global__ __launch_bounds__(64 * WPB, 8) void lcp_coopq_kernel(LcpArgs a, const
                     const float4* l0 = a.list + (cs[u] ? (uint32_t)__float_as_int(qt[w][idxs[u]].w) : 0u) + sub;
                     const uint32_t last = cs[u] ? ((cs[u] - 1u) & ~7u) : 0u;
 #pragma unroll
-                    for (int e = 0; e < EPL; ++e) e0[u][e] = l0[gl * e];
+                    for (int e = 0; e < EPL; ++e) e0[u][e] = l0[GL * e];
                     // the later lines of the first trip only when some list of this trip has them (the queries are ordered by list
                     // length, so a third of the trips are single-line lists throughout: no addresses spent on re-reading those)
                     wide[u] = FIRST > 1 && __any(cs[u] > 8u);
                     if (wide[u]) {
 #pragma unroll
-                        for (int e = EPL; e < E0; ++e) e0[u][e] = l0[min((uint32_t)(8 * (e / EPL)), last) + gl * (e % EPL)];
+                        for (int e = EPL; e < E0; ++e) e0[u][e] = l0[min((uint32_t)(8 * (e / EPL)), last) + GL * (e % EPL)];
                     }
                 }
                 else if (cs[u]) {
                     const float4* l0 = a.list + (uint32_t)__float_as_int(qt[w][idxs[u]].w) + sub;
 #pragma unroll
-                    for (int e = 0; e < E0; ++e)
-                        if (e < EPL || (uint32_t)(8 * (e / EPL)) < cs[u]) e0[u][e] = l0[8 * (e / EPL) + gl * (e % EPL)];
+                    for (int e = 0; e < E0; ++e) e0[u][e] = l0[GL * e];   // (E0 = EPL: one line)
                 }
             }
 #pragma unroll
@@ -569,7 +575,7 @@ __global__ __launch_bounds__(64 * WPB, 8) void lcp_coopq_kernel(LcpArgs a, const
                     const float d = dx * dx + (dy * dy + dz * dz);
                     take_if_better<IDX>(d, __float_as_int(e0[u][e].w), gd, gi);
                 }
-                if (FIRST > 1 && (!NOSENT || wide[u])) {
+                if (FIRST > 1 && wide[u]) {
 #pragma unroll
                     for (int e = EPL; e < E0; ++e) {
                         const float dx = qq.x - e0[u][e].x, dy = qq.y - e0[u][e].y, dz = qq.z - e0[u][e].z;
@@ -584,60 +590,41 @@ __global__ __launch_bounds__(64 * WPB, 8) void lcp_coopq_kernel(LcpArgs a, const
                     for (uint32_t k = 8; __any(k < cc); k += 8 * UNR) {
                         // |q - p| >= |p - centre| - |q - centre| > sqrt(best of the group) for every later p: stop
                         if (k < cc && a.chunk_r[chunk0 + (k >> 3)] - qcg > sqrtf(group_min_nonneg<GL>(gd)) + a.bound_margin) cc = 0;
-                        float4 e[UNR][EPL];
+                        float4 e[EPL];
+                        if (k < cc) {   // a line's entries under ONE condition: its loads leave together
 #pragma unroll
-                        for (int v = 0; v < UNR; ++v) {   // a line's entries under ONE condition: its loads leave together
-                            if (k + 8 * v < cc) {
-#pragma unroll
-                                for (int x = 0; x < EPL; ++x) e[v][x] = lp[k + 8 * v + gl * x];
-                            } else {
-#pragma unroll
-                                for (int x = 0; x < EPL; ++x) e[v][x] = make_float4(1e30f, 1e30f, 1e30f, __int_as_float(-1));
-                            }
-                        }
-#pragma unroll
-                        for (int v = 0; v < UNR; ++v)
-#pragma unroll
-                            for (int x = 0; x < EPL; ++x) {
-                                const float dx = qq.x - e[v][x].x, dy = qq.y - e[v][x].y, dz = qq.z - e[v][x].z;
-                                const float d = dx * dx + (dy * dy + dz * dz);
-                                take_if_better<IDX>(d, __float_as_int(e[v][x].w), gd, gi);
-                            }
-                    }
-                } else
-                for (uint32_t k = 8 * FIRST; __any(k < c); k += 8 * UNR) {
-                    float4 e[UNR][EPL];
-#pragma unroll
-                    for (int v = 0; v < UNR; ++v) {
-                        if (NOSENT) {   // a list shorter than this trip reads its last line again (the same entries: harmless)
-                            const uint32_t kk = min(k + 8u * v, last_line);
-#pragma unroll
-                            for (int x = 0; x < EPL; ++x) e[v][x] = lp[kk + gl * x];
-                        } else if (k + 8 * v < c) {
-#pragma unroll
-                            for (int x = 0; x < EPL; ++x) e[v][x] = lp[k + 8 * v + gl * x];
+                            for (int x = 0; x < EPL; ++x) e[x] = lp[k + GL * x];
                         } else {
 #pragma unroll
-                            for (int x = 0; x < EPL; ++x) e[v][x] = make_float4(1e30f, 1e30f, 1e30f, __int_as_float(-1));
+                            for (int x = 0; x < EPL; ++x) e[x] = make_float4(1e30f, 1e30f, 1e30f, __int_as_float(-1));
                         }
-                    }
-#pragma unroll
-                    for (int v = 0; v < UNR; ++v)
 #pragma unroll
                         for (int x = 0; x < EPL; ++x) {
-                            const float dx = qq.x - e[v][x].x, dy = qq.y - e[v][x].y, dz = qq.z - e[v][x].z;
+                            const float dx = qq.x - e[x].x, dy = qq.y - e[x].y, dz = qq.z - e[x].z;
                             const float d = dx * dx + (dy * dy + dz * dz);
-                            take_if_better<IDX>(d, __float_as_int(e[v][x].w), gd, gi);
+                            take_if_better<IDX>(d, __float_as_int(e[x].w), gd, gi);
                         }
+                    }
+                } else {
+                    for (uint32_t k = 8 * FIRST; __any(k < c); k += 8 * UNR) {
+                        const uint32_t kk = min(k, last_line);   // a list shorter than this trip reads its last line again (the same entries: harmless)
+                        float4 e[EPL];
+#pragma unroll
+                        for (int x = 0; x < EPL; ++x) e[x] = lp[kk + GL * x];
+#pragma unroll
+                        for (int x = 0; x < EPL; ++x) {
+                            const float dx = qq.x - e[x].x, dy = qq.y - e[x].y, dz = qq.z - e[x].z;
+                            const float d = dx * dx + (dy * dy + dz * dz);
+                            take_if_better<IDX>(d, __float_as_int(e[x].w), gd, gi);
+                        }
+                    }
                 }
-                const float dm = two ? group_min_nonneg<2>(gd) : group_min_nonneg<GL>(gd);
+                const float dm = group_min_nonneg<GL>(gd);
                 int im = (gd == dm) ? gi : -1;
-                if (GL >= 2) im = max(im, dpp_i32<DPP_QUAD_XOR1>(im));
-                if (GL >= 4 && !two) im = max(im, dpp_i32<DPP_QUAD_XOR2>(im));
-                if (GL == 8) im = max(im, dpp_i32<DPP_HALF_MIRROR>(im));
+                im = max(im, dpp_i32<DPP_QUAD_XOR1>(im));
+                im = max(im, dpp_i32<DPP_QUAD_XOR2>(im));
                 if (c && sub == 0) ri[w][idxs[u]] = im;
             }
-            s0 += NG * PIPE;
         }
         __builtin_amdgcn_wave_barrier();
         if (lane < nq) {
@@ -731,24 +718,7 @@ __global__ __launch_bounds__(64 * WPB, 8) void lcp_coopq_kernel(LcpArgs a, const
             }
         }
     };
-    if (TILE) {
-        __shared__ float4 tile[2][64 * WPB];
-        const int tid = threadIdx.x;
-        const float4 pad = make_float4(__int_as_float(0x7fc00000), __int_as_float(0x7fc00000), __int_as_float(0x7fc00000), 0.f);   // matches nothing
-        tile[0][tid] = tid < a.M ? a.mpos[tid] : pad;
-        __syncthreads();
-        int buf = 0;
-        for (int tbase = 0; tbase < a.M; tbase += 64 * WPB) {
-            const int nxt = tbase + 64 * WPB + tid;                  // the next tile is requested before this one is worked on
-            const float4 gn = nxt < a.M ? a.mpos[nxt] : pad;
-            if (cand >= 0)
-                for (int s = 0; s < WPB && tbase + 64 * s < a.M; ++s) step(tbase + 64 * s + lane, tile[buf][64 * s + lane]);
-            tile[buf ^ 1][tid] = gn;
-            __syncthreads();
-            buf ^= 1;
-        }
-        if (cand < 0) return;
-    } else if (CU == 16) {
+    if (CU == 16) {
     // The wavefront's steps as 16-point sub-patches, four per step, 64 at a time: every lane tests the sphere of one sub-patch
     // (a.sub), and the live ones join a per-wave ring in LDS (ballot + mbcnt compaction, as the query queue).  Each 64-lane step
     // takes the next four entries of the ring -- lane l walks point l & 15 of the (l >> 4)-th -- and a window is tested only when
@@ -1013,31 +983,92 @@ __global__ __launch_bounds__(256) void order_keys_kernel(const float* __restrict
     vals[i] = i;
 }
 
-// Kernel selection.  The product library ships the kernels the automatic choice uses (24: scan fed from an LDS queue over
-// index-ordered lists, sparse scenes; 39: the same over centre-sorted lists with early exit, dense scenes) plus two independent
-// cross-checks: the per-step cooperative scan of round 2 over the centre-sorted lists (31) and the plain lane-per-query kernel
-// (0); every one of them returns the reference's scores.  Everything that lost an A/B run (profiles/r01_lcp_analysis.md,
-// profiles/r03_lcp_patch_and_group_ab.json: the per-step scan over index-ordered lists 15, eight lanes per query, ...) exists
-// only in a tools build (make tools -> libstocs_hip_tools.so, -DSTOCS_TOOLS_BUILD), which also honours STOCS_LCP_VARIANT.
-static bool lcp_variant_selectable(int v) {
-    if (v == 99 || v == 0 || v == 24 || v == 31 || v == 39) return true;
-#ifdef STOCS_TOOLS_BUILD
-    static const int extra[] = {15, 1, 9, 16, 17, 20, 25, 26, 27, 28, 30, 32, 33, 34, 35, 40, 41, 42, 43, 44, 45, 46};
-    for (size_t i = 0; i < sizeof(extra) / sizeof(extra[0]); ++i) if (extra[i] == v) return true;
-#endif
-    return false;
-}
-static int lcp_variant() {
-#ifdef STOCS_TOOLS_BUILD
-    static int v = -1;
-    if (v < 0) {
-        const char* e = getenv("STOCS_LCP_VARIANT");
-        v = (e && lcp_variant_selectable(atoi(e))) ? atoi(e) : 99;
+// ---------------------------------------------------------------------------------------------
+// Kernel selection.  The library ships the kernels the automatic choice uses -- the queue-fed scan over index-ordered lists on
+// sparse scenes (lcp_variant 24), over centre-sorted lists with early exit on dense ones (39) -- plus two independent
+// cross-checks: the per-step cooperative scan over the centre-sorted lists (31) and the plain lane-per-query kernel (0); every
+// one of them returns the reference's scores.  What lost an A/B run is gone from the code (DESIGN_HISTORY.md lists the forms and
+// the last commit that holds them; profiles/r01_lcp_analysis.md, profiles/r03_lcp_patch_and_group_ab.json hold their figures).
+// ---------------------------------------------------------------------------------------------
+enum LcpKernel { LCP_PLAIN, LCP_STEP, LCP_QUEUE, LCP_EXACT };   // lcp_kernel, lcp_coop_kernel, lcp_coopq_kernel, lcp_exact_kernel
+struct LcpForm {
+    LcpKernel kernel;
+    bool detail;   // every kernel: per-point output
+    bool dense;    // plain and queue kernels: centre-sorted lists (the per-step kernel knows no other)
+    bool split;    // per-step and queue kernels: four wavefronts share a candidate
+    bool flat, near;   // queue kernel (see the table above it); false elsewhere
+    int cu;            // queue kernel: 16 or 64; 64 elsewhere
+};
+
+static bool lcp_variant_selectable(int v) { return v == 99 || v == 0 || v == 24 || v == 31 || v == 39; }
+
+// The form a call runs.  Must not depend on the batch size (a candidate's score is batch-invariant).
+static LcpForm choose_lcp_form(const stocs_ctx* c, const LcpArgs& a, bool detail) {
+    LcpForm f = {LCP_QUEUE, detail, false, false, false, false, 64};
+    if (c->exact_ties) { f.kernel = LCP_EXACT; return f; }
+    // dense grids keep their lists sorted by distance from the cell centre (not by index): only kernels instantiated with the
+    // order-independent tie rule may scan them
+    f.dense = c->grid.d_chunk_r != NULL;
+    const int variant = c->lcp_variant >= 0 ? c->lcp_variant : 99;
+    // automatic: the queue kernel on every grid.  (Sparse grids with more than 10 entries per list once went to a per-step scan; since
+    // the queue kernel verifies with four lanes per query it wins there too: 50 000 / 12 500 points 3.54 -> 2.35 ms.)  On dense grids
+    // it runs with early exit, lanes per query as on sparse scenes (C5: 6.33 -> 5.81 ms).  A variant the grid cannot run maps to the
+    // queue form of that grid: 24 on a dense grid -> 39, 31 and 39 on a sparse one -> 24
+    if (variant == 0) f.kernel = (detail && f.dense) ? LCP_STEP : LCP_PLAIN;   // (no plain detail kernel for centre-sorted lists)
+    else if (variant == 31 && f.dense) f.kernel = LCP_STEP;
+    // four wavefronts per candidate pay from 512 model points on.  Queue kernel: a trial's ~8 000 candidates finish 40 % sooner (one
+    // round of long wavefronts becomes four rounds of short ones), 32 768 candidates 9 % sooner, 65 536 the same.  Per-step kernel:
+    // C5 (16 384 candidates x 50 000 points) 11.6 -> 8.3 ms; eight: 8.1 ms, but 20 % slower at Cm.  The detail forms are never
+    // split, the dense queue form always is
+    const bool split = c->lcp_split && a.M >= 512;
+    if (f.kernel == LCP_STEP) f.split = !detail && split;
+    if (f.kernel == LCP_QUEUE) {
+        f.split = !detail && (f.dense || split);
+        f.flat = !detail && !f.dense && c->lcp_flat && a.flat;
+        f.near = !f.dense && a.has_nearest;   // pruned lists on a grid finer than epsilon: the distance bound in place of the sub-cell mask
+        // the unit of the patch test (lcp_cull_unit); without the test the walk of whole steps (CU = 64) is the one to run
+        f.cu = (a.patch && c->lcp_cull_unit == 16) ? 16 : 64;
     }
-    return v;
-#else
-    return 99;
-#endif
+    return f;
+}
+
+typedef void (*LcpScanFn)(LcpArgs, const float*, float*, int, int32_t*, uint8_t*);
+
+// the queue kernel of a form: bits 0..5 of I are DETAIL, DENSE, SPLIT, FLAT, NEAR and CU == 16; NULL where the form is not legal
+template <int I>
+static LcpScanFn lcp_queue_fn() {
+    constexpr bool DETAIL = (I & 1) != 0, DENSE = (I & 2) != 0, SPLIT = (I & 4) != 0, FLAT = (I & 8) != 0, NEAR = (I & 16) != 0;
+    constexpr int CU = (I & 32) ? 16 : 64;
+    if constexpr (lcp_queue_form_legal(DETAIL, DENSE, SPLIT, FLAT, NEAR, CU)) return lcp_coopq_kernel<DETAIL, DENSE, SPLIT, FLAT, NEAR, CU>;
+    else return NULL;
+}
+template <int... I>
+static LcpScanFn lcp_queue_fn(const LcpForm& f, std::integer_sequence<int, I...>) {
+    static const LcpScanFn table[] = {lcp_queue_fn<I>()...};
+    return table[(f.detail ? 1 : 0) | (f.dense ? 2 : 0) | (f.split ? 4 : 0) | (f.flat ? 8 : 0) | (f.near ? 16 : 0) | (f.cu == 16 ? 32 : 0)];
+}
+
+// Run-time form -> template instantiation, grid and block: the one place that names the kernels.
+static int launch_lcp_form(stocs_ctx* c, const LcpForm& f, const LcpArgs& a, const float* d_T16, int n, float* d_lcp, int32_t* d_hit, uint8_t* d_counted) {
+    // split: a workgroup of four wavefronts per candidate.  Else the cooperative scoring kernels run one wavefront per workgroup and
+    // candidate; the plain and exact kernels and every detail form put four candidates into a workgroup
+    const bool cooperative = f.kernel == LCP_STEP || f.kernel == LCP_QUEUE;
+    const bool one_wave = cooperative && !f.detail && !f.split;
+    const dim3 grid((unsigned)(f.split || one_wave ? n : (n + 3) / 4)), block(one_wave ? 64 : 256);
+    if (f.kernel == LCP_EXACT) {
+        if (f.detail) hipLaunchKernelGGL(lcp_exact_kernel<true>, grid, block, 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted, c->d_kd_nodes, c->d_kd_pts, c->d_ties);
+        else hipLaunchKernelGGL(lcp_exact_kernel<false>, grid, block, 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted, c->d_kd_nodes, c->d_kd_pts, c->d_ties);
+    } else {
+        LcpScanFn fn = NULL;
+        if (f.kernel == LCP_QUEUE) fn = lcp_queue_fn(f, std::make_integer_sequence<int, 64>());
+        else if (f.kernel == LCP_STEP) fn = f.detail ? lcp_coop_kernel<true, false> : (f.split ? lcp_coop_kernel<false, true> : lcp_coop_kernel<false, false>);
+        else if (!f.detail) fn = f.dense ? lcp_kernel<false, false> : lcp_kernel<false, true>;
+        else if (!f.dense) fn = lcp_kernel<true, true>;
+        if (!fn) { set_error("launch_lcp: no kernel for this form (kernel %d, detail %d, dense %d, split %d, flat %d, near %d, cu %d)", (int)f.kernel, (int)f.detail, (int)f.dense, (int)f.split, (int)f.flat, (int)f.near, f.cu); return STOCS_ERR_STATE; }
+        hipLaunchKernelGGL(fn, grid, block, 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted);
+    }
+    STOCS_HIP_CHECK(hipGetLastError());
+    return STOCS_OK;
 }
 
 int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d_hit, uint8_t* d_counted, unsigned long long* d_best8, uint32_t id_offset) {
@@ -1045,6 +1076,9 @@ int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d
     bool best_zeroed = false;
     LcpArgs a;
     a.best = d_best8; a.id_offset = id_offset;
+#ifdef STOCS_TOOLS_BUILD
+    a.ablate = getenv("STOCS_LCP_ABLATE") ? atoi(getenv("STOCS_LCP_ABLATE")) : 0;
+#endif
     a.mpos = c->d_mpos_s; a.mnrm = c->d_mnrm_s; a.mperm = c->d_mperm; a.M = c->nM;
     a.top = c->grid.d_top; a.cells = c->grid.d_cells; a.flat = c->grid.d_flat; a.list = c->grid.d_list; a.snrmw = c->snrmw_override ? c->snrmw_override : c->d_snrmw;
     a.cand_trial = c->lcp_cand_trial; a.snrmw_stride = c->lcp_cand_trial ? c->snrmw_stride : 0;
@@ -1072,15 +1106,9 @@ int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d
         if (rc) return rc;
         if (!c->ties_started) { STOCS_HIP_CHECK(hipMemsetAsync(c->d_ties, 0, 16, c->stream)); c->ties_started = true; }
         a.order = NULL; a.xcd_blocks = 0;
-#ifdef STOCS_TOOLS_BUILD
-        a.ablate = 0;
-#endif
         if (d_best8 && !(d_best8 == c->d_best && c->best_is_zero)) STOCS_HIP_CHECK(hipMemsetAsync(d_best8, 0, 8, c->stream));
         if (d_best8 == c->d_best) c->best_is_zero = false;
-        if (d_hit) hipLaunchKernelGGL((lcp_exact_kernel<true>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted, c->d_kd_nodes, c->d_kd_pts, c->d_ties);
-        else hipLaunchKernelGGL((lcp_exact_kernel<false>), dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted, c->d_kd_nodes, c->d_kd_pts, c->d_ties);
-        STOCS_HIP_CHECK(hipGetLastError());
-        return STOCS_OK;
+        return launch_lcp_form(c, choose_lcp_form(c, a, d_hit != NULL), a, d_T16, n, d_lcp, d_hit, d_counted);
     }
     if (c->lcp_cull && c->grid.d_dist && c->d_mpatch && (c->grid.dist_ready || c->lcp_cull >= 2 || c->scene_work >= c->lcp_cull_after)) {
         int rc = fill_cull_field(c);
@@ -1090,11 +1118,7 @@ int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d
         a.gox = c->grid.cg_ox; a.goy = c->grid.cg_oy; a.goz = c->grid.cg_oz; a.g = c->grid.cg_g; a.inv_g = c->grid.cg_inv_g; a.cap = c->grid.cg_cap;
         a.gnx = c->grid.cg_nx; a.gny = c->grid.cg_ny; a.gnz = c->grid.cg_nz;
     }
-    const int blocks = (n + 3) / 4;
     a.order = NULL; a.xcd_blocks = 0;
-#ifdef STOCS_TOOLS_BUILD
-    a.ablate = getenv("STOCS_LCP_ABLATE") ? atoi(getenv("STOCS_LCP_ABLATE")) : 0;
-#endif
     // big batches against scenes whose lists do not stay in the caches: spatially ordered processing (the ordering costs ~50 us; scores
     // do not depend on it).  Until the first half of round 3 it paid at Cm too (1.67 -> 1.44 ms in round 1); with the four-lane verify
     // trips it is a wash there (9 MB of lists: 1.115 ms either way at 65 536 candidates, +3 % at 32 768, +8 % for a 1 000-point model)
@@ -1132,140 +1156,30 @@ int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d
     if (d_best8 && d_best8 == c->d_best && c->best_is_zero) best_zeroed = true;   // stocs_make_transforms left the word zeroed for this launch
     if (d_best8 == c->d_best) c->best_is_zero = false;
     if (d_best8 && !best_zeroed) STOCS_HIP_CHECK(hipMemsetAsync(d_best8, 0, 8, c->stream));
-    int variant = c->lcp_variant >= 0 ? c->lcp_variant : lcp_variant();
-    // dense grids keep their lists sorted by distance from the cell centre (not by index): only kernels
-    // instantiated with the order-independent tie rule may scan them
-    const bool dense = c->grid.d_chunk_r != NULL;
-    if (variant == 99)   // automatic; must not depend on the batch size (a candidate's score is batch-invariant)
-        // (until the first half of round 3 sparse grids with more than 10 entries per list went to the per-step scan, variant 15; since the
-        //  queue kernel verifies with four lanes per query it wins there too: 50 000 / 12 500 points 3.54 -> 2.35 ms, tools/sweep_variants.py)
-        variant = dense ? 39 : 24;
-    const bool dense_only = (variant >= 30 && variant <= 35) || variant == 39 || (variant >= 41 && variant <= 43);   // kernels with the order-independent tie rule / early exit
-    if (dense && !(variant == 0 || variant == 16 || dense_only)) variant = 39;
-    if (!dense && dense_only) variant = 24;
-#define STOCS_LCP_LAUNCH(...) hipLaunchKernelGGL((__VA_ARGS__), dim3(blocks), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted)
-    // the unit of the patch test (lcp_cull_unit); without the test the walk of whole steps (CU = 64) is the one to run
-    const bool cu16 = a.patch && c->lcp_cull_unit == 16;
-    if (d_hit) {   // per-point detail (parity tests)
-        if (dense && variant == 39) {
-            if (cu16) STOCS_LCP_LAUNCH(lcp_coopq_kernel<true, 1, true, 4, false, 4, 0, false, false, true, 8, 1, false, false, false, 16>);
-            else STOCS_LCP_LAUNCH(lcp_coopq_kernel<true, 1, true, 4, false, 4, 0, false, false, true>);
-        }
-        else if (dense) STOCS_LCP_LAUNCH(lcp_coop_kernel<true, 2, true, true, false>);
-        else if (variant == 0) STOCS_LCP_LAUNCH(lcp_kernel<true, true>);
-#ifdef STOCS_TOOLS_BUILD
-        else if (!(variant >= 20 && variant <= 28)) STOCS_LCP_LAUNCH(lcp_coop_kernel<true, 1, true, false, true>);
-#endif
-        else if (a.has_nearest) {   // pruned lists on a grid finer than epsilon
-            if (cu16) STOCS_LCP_LAUNCH(lcp_coopq_kernel<true, 1, true, 4, true, 4, 0, false, false, false, 8, 1, false, true, false, 16>);
-            else STOCS_LCP_LAUNCH(lcp_coopq_kernel<true, 1, true, 4, true, 4, 0, false, false, false, 8, 1, false, true>);
-        }
-        else if (cu16) STOCS_LCP_LAUNCH(lcp_coopq_kernel<true, 1, true, 4, true, 4, 0, false, false, false, 8, 1, false, false, false, 16>);
-        else STOCS_LCP_LAUNCH(lcp_coopq_kernel<true, 1, true, 4, true>);
-    } else if (dense) {
-        switch (variant) {
-            case 0: STOCS_LCP_LAUNCH(lcp_kernel<false, false>); break;
-#ifdef STOCS_TOOLS_BUILD
-            case 16: STOCS_LCP_LAUNCH(lcp_coop_kernel<false, 8, true, false, false>); break;
-            case 30: STOCS_LCP_LAUNCH(lcp_coop_kernel<false, 1, true, true, false>); break;
-            case 32: STOCS_LCP_LAUNCH(lcp_coop_kernel<false, 4, true, true, false>); break;
-            case 33: STOCS_LCP_LAUNCH(lcp_coop_kernel<false, 2, true, true, false>); break;   // 31 with four waves per workgroup
-            case 34: hipLaunchKernelGGL((lcp_coop_kernel<false, 1, true, true, false, 4, true>), dim3(n), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted); break;   // 31 with one line per trip
-            case 35: hipLaunchKernelGGL((lcp_coop_kernel<false, 4, true, true, false, 4, true>), dim3(n), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted); break;   // 31 with four lines per trip
-#endif
-            case 39:   // queue-fed scan with early exit (16-byte lists); lanes per query as on sparse scenes (C5: 6.33 -> 5.81 ms)
-#ifdef STOCS_TOOLS_BUILD
-                if (c->lcp_group == 8) hipLaunchKernelGGL((lcp_coopq_kernel<false, 1, true, 4, false, 4, 0, true, false, true, 8>), dim3(n), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted);
-                else if (c->lcp_group == 42) hipLaunchKernelGGL((lcp_coopq_kernel<false, 1, true, 2, false, 4, 0, true, false, true, 4>), dim3(n), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted);
-                else if (c->lcp_group == 2) hipLaunchKernelGGL((lcp_coopq_kernel<false, 1, true, 1, false, 4, 0, true, false, true, 2>), dim3(n), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted);
-                else
-#endif
-                if (cu16) hipLaunchKernelGGL((lcp_coopq_kernel<false, 1, true, 1, false, 4, 0, true, false, true, 4, 1, false, false, false, 16>), dim3(n), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted);
-                else hipLaunchKernelGGL((lcp_coopq_kernel<false, 1, true, 1, false, 4, 0, true, false, true, 4>), dim3(n), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted);
-                break;
-#ifdef STOCS_TOOLS_BUILD
-            case 41: hipLaunchKernelGGL((lcp_coopq_kernel<false, 2, true, 4, false, 4, 0, true, false, true>), dim3(n), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted); break;   // 39, two lines per trip after the first
-            case 42: hipLaunchKernelGGL((lcp_coopq_kernel<false, 1, true, 8, false, 4, 0, true, false, true>), dim3(n), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted); break;   // 39, eight first lines in flight
-            case 43: hipLaunchKernelGGL((lcp_coopq_kernel<false, 1, false, 4, false, 4, 0, true, false, true>), dim3(n), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted); break;  // 39 without the ordering by list length
-#endif
-            default:   // 31
-                // four wavefronts per candidate: C5 (16 384 candidates x 50 000 points) 11.6 -> 8.3 ms; eight: 8.1 ms, but 20 % slower at Cm
-                if (c->lcp_split && a.M >= 512) hipLaunchKernelGGL((lcp_coop_kernel<false, 2, true, true, false, 4, true>), dim3(n), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted);
-                else hipLaunchKernelGGL((lcp_coop_kernel<false, 2, true, true, false, 1>), dim3(n), dim3(64), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted);
-                break;
-        }
+    return launch_lcp_form(c, choose_lcp_form(c, a, d_hit != NULL), a, d_T16, n, d_lcp, d_hit, d_counted);
+}
+
+// the arg-max key of n scores (n > 0) into *d_key8, on the context's stream: one workgroup up to 2^18 scores, else zero fill + atomic max
+static int enqueue_best(stocs_ctx* c, const float* d_lcp, int n, uint32_t id_offset, unsigned long long* d_key8) {
+    if (n <= (1 << 18)) {
+        hipLaunchKernelGGL(best_single_kernel, dim3(1), dim3(1024), 0, c->stream, d_lcp, n, id_offset, d_key8);
     } else {
-        switch (variant) {
-            case 0: STOCS_LCP_LAUNCH(lcp_kernel<false, true>); break;
-#ifdef STOCS_TOOLS_BUILD
-            case 15: STOCS_LCP_LAUNCH(lcp_coop_kernel<false, 4, true, false, true>); break;
-            case 1: STOCS_LCP_LAUNCH(lcp_coop_kernel<false, 1, true, false, true>); break;
-            case 9: STOCS_LCP_LAUNCH(lcp_coop_kernel<false, 2, true, false, true>); break;
-            case 16: STOCS_LCP_LAUNCH(lcp_coop_kernel<false, 8, true, false, true>); break;
-            case 17: STOCS_LCP_LAUNCH(lcp_coop_kernel<false, 2, false, false, true>); break;   // no sub-cell mask
-            case 20: STOCS_LCP_LAUNCH(lcp_coopq_kernel<false, 1, false, 4, true>); break;
-            case 26: STOCS_LCP_LAUNCH(lcp_coopq_kernel<false, 1, true, 1, true>); break;
-            case 27: STOCS_LCP_LAUNCH(lcp_coopq_kernel<false, 1, true, 2, true>); break;
-            case 28: STOCS_LCP_LAUNCH(lcp_coopq_kernel<false, 1, true, 8, true>); break;
-            case 25: STOCS_LCP_LAUNCH(lcp_coopq_kernel<false, 2, true, 4, true>); break;
-            // waves per workgroup (the kernel has no workgroup-wide barrier): 16 / 8 / 4 / 2 / 1 -> 1.83 / 1.62 / 1.51 / 1.51 / 1.475 ms at Cm
-            case 40: hipLaunchKernelGGL((lcp_coopq_kernel<false, 1, true, 4, true, 8>), dim3((n + 7) / 8), dim3(512), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted); break;
-            case 44: STOCS_LCP_LAUNCH(lcp_coopq_kernel<false, 1, true, 4, true, 4>); break;
-            // model tile shared through LDS by the four candidates of a workgroup (45), next to the same workgroup shape without it (46)
-            case 45: if (a.flat) STOCS_LCP_LAUNCH(lcp_coopq_kernel<false, 1, true, 4, true, 4, 1, false, true>); else STOCS_LCP_LAUNCH(lcp_coopq_kernel<false, 1, true, 4, true, 4, 0, false, true>); break;
-            case 46: if (a.flat) STOCS_LCP_LAUNCH(lcp_coopq_kernel<false, 1, true, 4, true, 4, 1>); else STOCS_LCP_LAUNCH(lcp_coopq_kernel<false, 1, true, 4, true, 4>); break;
-#endif
-            default: {  // 24
-                const int flat = (c->lcp_flat && a.flat) ? 1 : 0;
-                // four wavefronts per candidate: a trial's ~8 000 candidates finish 40 % sooner (one round of long wavefronts
-                // becomes four rounds of short ones), 32 768 candidates 9 % sooner, 65 536 the same (tools/lcp_flat_ab.py)
-                const bool split = c->lcp_split && a.M >= 512;
-#define STOCS_LCP_Q(SORTV, PIPEV, GLV, UNRV, ...) do { \
-                    if (split) { if (flat) hipLaunchKernelGGL((lcp_coopq_kernel<false, UNRV, SORTV, PIPEV, true, 4, 1, true, false, false, GLV, ##__VA_ARGS__>), dim3(n), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted); \
-                                 else hipLaunchKernelGGL((lcp_coopq_kernel<false, UNRV, SORTV, PIPEV, true, 4, 0, true, false, false, GLV, ##__VA_ARGS__>), dim3(n), dim3(256), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted); } \
-                    else { if (flat) hipLaunchKernelGGL((lcp_coopq_kernel<false, UNRV, SORTV, PIPEV, true, 1, 1, false, false, false, GLV, ##__VA_ARGS__>), dim3(n), dim3(64), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted); \
-                           else hipLaunchKernelGGL((lcp_coopq_kernel<false, UNRV, SORTV, PIPEV, true, 1, 0, false, false, false, GLV, ##__VA_ARGS__>), dim3(n), dim3(64), 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted); } } while (0)
-                // lanes per queued query in the verify trips (stocs_set_option "lcp_group"; profiles/r03_lcp_group_ab.json): 4 lanes with
-                // two list entries each and one trip (16 queries) in flight -- Cm 1.34 -> 1.18 ms; 8 lanes with one entry each and four
-                // trips in flight is the form of rounds 1-3 (tools build)
-                switch (c->lcp_group) {
-#ifdef STOCS_TOOLS_BUILD
-                    case 8: STOCS_LCP_Q(true, 4, 8, 1); break;       // eight lanes with one entry each, four trips in flight: the form of rounds 1-3a
-                    case 42: STOCS_LCP_Q(true, 2, 4, 1); break;    // 4 lanes, two trips in flight (1.185 ms)
-                    case 41: STOCS_LCP_Q(true, 1, 4, 1, 1); break; // 4 with one line in the first trip (+2 % at 65 536 candidates, +7 % at 8 192)
-                    case 49: STOCS_LCP_Q(true, 1, 4, 1, 2, false); break; // 4 with predicated list loads and sentinel entries (+1.2 %; +2.4 % at 8 192)
-                    case 46: STOCS_LCP_Q(true, 1, 4, 1, 3); break; // ... three lines (+3 %)
-                    case 47: STOCS_LCP_Q(true, 1, 4, 2, 2); break; // 4 with two lines per later trip as well (+3 %)
-                    case 48: STOCS_LCP_Q(true, 1, 4, 2, 1); break; // one line first, then two per trip (+5 %)
-                    case 85: STOCS_LCP_Q(true, 2, 8, 1, 2); break; // 8 lanes, two trips, two lines
-                    case 43: STOCS_LCP_Q(true, 3, 4, 1); break;    // ... three (1.35 ms: spills)
-                    case 44: STOCS_LCP_Q(true, 4, 4, 1); break;    // ... four (2.56 ms: spills)
-                    case 40: STOCS_LCP_Q(false, 2, 4, 1); break;   // 42 without the ordering by list length (1.24 ms)
-                    case 2: STOCS_LCP_Q(true, 1, 2, 1); break;     // 2 lanes, four entries each (1.45 ms)
-                    case 22: STOCS_LCP_Q(true, 2, 2, 1); break;    // ... two trips in flight (2.11 ms)
-                    case 1: STOCS_LCP_Q(true, 1, 1, 1); break;     // a lane per query, a whole line per lane (3.16 ms)
-#endif
-                    default:
-                        // four lanes per query, one trip in flight, a list's first two lines together, no sentinels.  has_nearest: pruned lists on a grid
-                        // finer than epsilon, the distance bound in place of the sub-cell mask.  (Round 5 measured and did not keep TINY -- lists of at
-                        // most four entries verified by two lanes, 32 queries per trip: Cm 0.939 -> 1.001 ms, C5 3.30 -> 3.50 ms, scores bitwise equal:
-                        // the runtime lane mapping and the fourth ordering class cost more instructions than the saved addresses are worth.  The
-                        // form lives in the tools build, STOCS_LCP_TINY=1.)
-#ifdef STOCS_TOOLS_BUILD
-                        if (getenv("STOCS_LCP_TINY")) { if (a.has_nearest) STOCS_LCP_Q(true, 1, 4, 1, 2, true, true, true); else STOCS_LCP_Q(true, 1, 4, 1, 2, true, false, true); break; }
-#endif
-                        if (a.has_nearest) { if (cu16) STOCS_LCP_Q(true, 1, 4, 1, 2, true, true, false, 16); else STOCS_LCP_Q(true, 1, 4, 1, 2, true, true); }
-                        else if (cu16) STOCS_LCP_Q(true, 1, 4, 1, 2, true, false, false, 16);
-                        else STOCS_LCP_Q(true, 1, 4, 1, 2, true);
-                        break;
-                }
-#undef STOCS_LCP_Q
-                break;
-            }
-        }
+        STOCS_HIP_CHECK(hipMemsetAsync(d_key8, 0, 8, c->stream));
+        const int blocks = std::min((n + 255) / 256, 1024);
+        hipLaunchKernelGGL(best_kernel, dim3(blocks), dim3(256), 0, c->stream, d_lcp, n, id_offset, d_key8);
     }
-#undef STOCS_LCP_LAUNCH
     STOCS_HIP_CHECK(hipGetLastError());
+    return STOCS_OK;
+}
+
+// the context's own key word (c->d_best) -> host, through pinned memory; waits for the stream
+static int read_best_key(stocs_ctx* c, uint64_t* key) {
+    int rc = ensure_pinned(c, PIN_VAR);
+    if (rc) return rc;
+    uint64_t* key_pin = (uint64_t*)((char*)c->h_pin + PIN_BEST);
+    STOCS_HIP_CHECK(hipMemcpyAsync(key_pin, c->d_best, 8, hipMemcpyDeviceToHost, c->stream));
+    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    *key = *key_pin;
     return STOCS_OK;
 }
 
@@ -1370,35 +1284,16 @@ int stocs_best_device(stocs_ctx* c, const void* d_lcp, int n, uint32_t id_offset
     if (n == 0) return STOCS_OK;
     if (!c->d_best) STOCS_HIP_CHECK(dev_malloc((void**)&c->d_best, 8));
     c->best_is_zero = false;
-    if (n <= (1 << 18)) {
-        hipLaunchKernelGGL(best_single_kernel, dim3(1), dim3(1024), 0, c->stream, (const float*)d_lcp, n, id_offset, c->d_best);
-    } else {
-        STOCS_HIP_CHECK(hipMemsetAsync(c->d_best, 0, 8, c->stream));
-        const int blocks = std::min((n + 255) / 256, 1024);
-        hipLaunchKernelGGL(best_kernel, dim3(blocks), dim3(256), 0, c->stream, (const float*)d_lcp, n, id_offset, c->d_best);
-    }
-    STOCS_HIP_CHECK(hipGetLastError());
-    { int rc = ensure_pinned(c, PIN_VAR); if (rc) return rc; }
-    uint64_t* key_pin = (uint64_t*)((char*)c->h_pin + PIN_BEST);
-    STOCS_HIP_CHECK(hipMemcpyAsync(key_pin, c->d_best, 8, hipMemcpyDeviceToHost, c->stream));
-    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    *key = *key_pin;
-    return STOCS_OK;
+    int rc = enqueue_best(c, (const float*)d_lcp, n, id_offset, c->d_best);
+    if (rc) return rc;
+    return read_best_key(c, key);
 }
 
 int stocs_best_device_async(stocs_ctx* c, const void* d_lcp, int n, uint32_t id_offset, void* d_key8) {
     if (!c || !d_key8 || n < 0 || (n && !d_lcp)) return STOCS_ERR_INVALID;
     DeviceGuard dev_guard(c->device);
     if (n == 0) { STOCS_HIP_CHECK(hipMemsetAsync(d_key8, 0, 8, c->stream)); return STOCS_OK; }
-    if (n <= (1 << 18)) {
-        hipLaunchKernelGGL(best_single_kernel, dim3(1), dim3(1024), 0, c->stream, (const float*)d_lcp, n, id_offset, (unsigned long long*)d_key8);
-    } else {
-        STOCS_HIP_CHECK(hipMemsetAsync(d_key8, 0, 8, c->stream));
-        const int blocks = std::min((n + 255) / 256, 1024);
-        hipLaunchKernelGGL(best_kernel, dim3(blocks), dim3(256), 0, c->stream, (const float*)d_lcp, n, id_offset, (unsigned long long*)d_key8);
-    }
-    STOCS_HIP_CHECK(hipGetLastError());
-    return STOCS_OK;
+    return enqueue_best(c, (const float*)d_lcp, n, id_offset, (unsigned long long*)d_key8);
 }
 
 int stocs_score_best_device_async(stocs_ctx* c, const void* d_T16, int n, void* d_lcp, uint32_t id_offset, void* d_key8) {
@@ -1414,12 +1309,7 @@ int stocs_score_best_device(stocs_ctx* c, const void* d_T16, int n, void* d_lcp,
     if (!c->d_best) STOCS_HIP_CHECK(dev_malloc((void**)&c->d_best, 8));
     int rc = stocs_score_best_device_async(c, d_T16, n, d_lcp, id_offset, c->d_best);
     if (rc) return rc;
-    if ((rc = ensure_pinned(c, PIN_VAR))) return rc;
-    uint64_t* key_pin = (uint64_t*)((char*)c->h_pin + PIN_BEST);
-    STOCS_HIP_CHECK(hipMemcpyAsync(key_pin, c->d_best, 8, hipMemcpyDeviceToHost, c->stream));
-    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    *key = *key_pin;
-    return STOCS_OK;
+    return read_best_key(c, key);
 }
 
 int stocs_set_option(stocs_ctx* c, const char* key, int value) {
@@ -1431,10 +1321,10 @@ int stocs_set_option(stocs_ctx* c, const char* key, int value) {
     }
     // 0 off, 1 spatial order, 2 + XCD-contiguous halves of the list, k > 2 + chunks of k consecutive slots per XCD
     if (!strcmp(key, "lcp_order") && value >= 0 && value <= 4096) { c->lcp_order = value; return STOCS_OK; }
-    // 0: brick look-ups only, 1: the flat cell table when the grid has one (takes effect for kernels launched afterwards;
-    // the table itself is built with the scene grid)
     // 1: stocs_find_congruent_all times its kernel groups with HIP events ("device: ..." steps of stocs_last_call_timing); 0 (default): host steps only
     if (!strcmp(key, "device_clock") && (value == 0 || value == 1)) { c->device_clock = value; return STOCS_OK; }
+    // 0: brick look-ups only, 1: the flat cell table when the grid has one (takes effect for kernels launched afterwards;
+    // the table itself is built with the scene grid)
     if (!strcmp(key, "lcp_flat") && (value == 0 || value == 1)) { c->lcp_flat = value; return STOCS_OK; }
     // 1: tied nearest-neighbour queries take the reference kd-tree's answer (lcp_exact_kernel, kdtree.h); 0 (default): largest index
     if (!strcmp(key, "exact_ties")) {
@@ -1452,14 +1342,8 @@ int stocs_set_option(stocs_ctx* c, const char* key, int value) {
     // the threshold of lcp_cull = 1, in MILLIONS of point queries (candidates x model points) scored against the current scene:
     // default 1000 (= 1e9: the field costs ~0.25 ms at 20 000 scene points and takes ~6 % off a launch); 0 = from the first call
     if (!strcmp(key, "lcp_cull_after") && value >= 0) { c->lcp_cull_after = (double)value * 1.0e6; return STOCS_OK; }
-    // lanes that verify one queued query together: 4 (two list entries per lane); the eight-lane form of rounds 1-3a lost its A/B and lives in the tools build
-    if (!strcmp(key, "lcp_group")) {
-        bool ok = value == 4;
-#ifdef STOCS_TOOLS_BUILD
-        ok = ok || value == 8 || value == 41 || value == 49 || value == 46 || value == 47 || value == 48 || value == 85 || value == 42 || value == 43 || value == 44 || value == 40 || value == 2 || value == 22 || value == 1;
-#endif
-        if (ok) { c->lcp_group = value; return STOCS_OK; }
-    }
+    // lanes that verify one queued query together: 4 (two list entries per lane) is the only form; the key is kept for callers that set it
+    if (!strcmp(key, "lcp_group") && value == 4) return STOCS_OK;
     set_error("stocs_set_option: unknown option or value");
     return STOCS_ERR_INVALID;
 }

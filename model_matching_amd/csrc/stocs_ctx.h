@@ -236,7 +236,6 @@ struct stocs_ctx {
     float patch_r_ref; // the radius most patches stay below (sizes the cap of the scene's distance field)
     int lcp_cull;      // 1: the scan kernels skip the 64-point steps whose bounding sphere is farther than epsilon from every scene point
     int lcp_cull_unit; // points per sphere of that test: 16 (default; live sub-patches are packed four to a step) or 64 (whole steps)
-    int lcp_group;     // lanes per queued query in the verify trips: 4 (default, two list entries per lane) or 8 (one entry per lane)
     double lcp_cull_after;   // lcp_cull == 1: the distance field is filled once this many point queries were scored against the scene (default 1e9)
     bool prev_scene_warm;    // the scene before this one crossed that threshold: a stream of frames will again, so the field of a new frame
                              // is filled right away, on the auxiliary stream (cull_pending: the scoring stream has not waited for it yet)
@@ -250,7 +249,7 @@ struct stocs_ctx {
     stocs::Arena grid_ws;    // temporaries of a grid build
     int grid_div;   // cell edge = epsilon / grid_div
     int grid_prune; // 1 (default): the grid's lists are dominance-pruned (grid.hip); 0: the layouts of rounds 2-4 (STOCS_GRID_PRUNE, read at stocs_ctx_create)
-    int lcp_variant;   // -1: STOCS_LCP_VARIANT or automatic; else stocs_set_option("lcp_variant")
+    int lcp_variant;   // -1: automatic; else stocs_set_option("lcp_variant")
     int device_clock;  // 1: stocs_find_congruent_all records HIP events between its kernel groups ("device: ..." steps of stocs_last_call_timing); default 0 (STOCS_DEVICE_CLOCK=1 turns it on)
     int lcp_split;     // 1: four wavefronts share one candidate (default), 0: one wavefront per candidate
     int lcp_flat;      // 1: build and use the flat cell table when it fits (default), 0: brick look-ups only

@@ -43,9 +43,19 @@ def test_pruned_lists_give_the_scores_of_the_full_lists_bit_for_bit(name, oracle
         assert same.mean() > 0.999 and np.array_equal(cp[same], co[same]), c  # (only exact-distance ties may differ from the kd-tree, Q11)
     # the early-exit kernels of rounds 2-4 stay in the library as cross-checks: on the unpruned dense grid they still run, same scores
     if name == "dense":
+        best = int(np.argmax(got_p))
+        ho, co = orc.lcp_detail(T[best])
         for v in (0, 31, 39):
             un.set_option("lcp_variant", v)
             assert np.array_equal(un.score_transforms(T).view(np.uint32), got_u.view(np.uint32)), v
+            # their per-point rows: the per-step kernel (0, 31) and the dense queue forms (39) without the patch test (whole steps)
+            # and with it (16-point sub-patches)
+            for cull in (0, 2):
+                un.set_option("lcp_cull", cull)
+                hv, cv = un.lcp_detail(T[best])
+                same = hv == ho
+                assert same.mean() > 0.999 and np.array_equal(cv[same], co[same]), (v, cull)
+            un.set_option("lcp_cull", 1)
         un.set_option("lcp_variant", 99)
     for v in (0, 24):                                                        # the plain lane-per-query kernel reads the pruned lists too
         pr.set_option("lcp_variant", v)

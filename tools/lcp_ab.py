@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Interleaved A/B timing of the LCP kernel variants in ONE process (HIP events on the context's
-stream), plus a bitwise comparison of their scores.  usage: python tools/lcp_ab.py [Cm|C5|small] [rounds]"""
+stream), plus a bitwise comparison of their scores.  usage: python tools/lcp_ab.py [Cm|C5|small] [rounds] [variants, e.g. 0,24]"""
 import json
 import os
 import sys
@@ -10,7 +10,7 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import os as _os; _os.environ.setdefault("STOCS_PIN_BLAS", "1")   # harness side: one BLAS thread under the cgroup CPU quota; the library import itself has no side effects
 from model_matching_amd import capi, synth  # noqa: E402
-# variants beyond 0 / 15 / 24 / 31 exist only in the measurement build (make -C model_matching_amd/csrc tools)
+# selectable variants: 99 (automatic), 0, 24, 31, 39; the measurement build (make -C model_matching_amd/csrc tools) is preferred when it is there
 _tools_lib = os.path.join(os.path.dirname(capi.LIB_PATH), "libstocs_hip_tools.so")
 if os.path.exists(_tools_lib):
     capi.LIB_PATH = _tools_lib
@@ -20,7 +20,7 @@ from model_matching_amd.estimator import StocsEstimator  # noqa: E402
 def main():
     name = sys.argv[1] if len(sys.argv) > 1 else "Cm"
     rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 5
-    variants = [int(v) for v in (sys.argv[3].split(",") if len(sys.argv) > 3 else ["0", "1"])]
+    variants = [int(v) for v in (sys.argv[3].split(",") if len(sys.argv) > 3 else ["0", "99"])]
     m, s, k = synth.workload(name)
     est = StocsEstimator(s.pos, s.nrm, s.prob, s.pixel, m.pos, m.nrm, build_index=False)
     cs = est.get_scene_centroid().astype(np.float64)

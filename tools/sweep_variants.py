@@ -11,7 +11,7 @@ for nS, nM, K, lattice in [(50000, 12500, 32768, 0.0032), (35000, 8000, 32768, 0
     T = synth.make_candidates(synth.centred_gt(s.T_gt, cs, cm), K)
     dT, dL = est.dev_alloc(T.nbytes), est.dev_alloc(K * 4); est.dev_upload(dT, T)
     out = {}
-    for v in (99, 15, 24, 39):
+    for v in (99, 0, 24, 31, 39):
         try:
             est.set_option("lcp_variant", v)
         except Exception as e:
