@@ -12,15 +12,17 @@
 // Per query: transform the point, locate its cell (one word of the flat cell table, or top -> brick -> cell word), scan that cell's
 // candidate list (every scene point within epsilon of the cell box) for the nearest point with
 // d^2 <= epsilon^2, then the 30-degree normal test as an exact threshold on the dot product, and an
-// integer (2^32 fixed-point) sum of the class-probability weights.  No atomics: results are run-to-run
-// deterministic and do not depend on the batch or on how the points are split over wavefronts.
+// integer (2^32 fixed-point) sum of the class-probability weights.  No atomics on the sums: results are run-to-run
+// deterministic and do not depend on the batch or on how the points are split over wavefronts.  (The one atomic of the walk, an
+// LDS add per window of the split forms' shared list of live sub-patches, decides the ORDER in which a candidate's sub-patches
+// are walked and by which wavefront -- not deterministic -- and nothing else: integer sums do not depend on that order.)
 // The queue-fed kernel (lcp_coopq_kernel, the automatic choice) first rules out the 16-point sub-patches whose bounding
 // sphere is out of reach of the scene (patch test, one look-up in a distance field of the scene) and walks the live ones
-// four to a step, collects the
+// four to a step -- the four wavefronts of a candidate from one list in LDS, step s to wavefront s & 3 --, collects the
 // queries that survive the sub-cell mask in a per-wave LDS ring and verifies them 16 at a time, four lanes per query
 // with two entries of a 128-byte list line each.
 //
-// Kernels: lcp_coopq_kernel (six named switches, the table of its legal forms above it), lcp_coop_kernel (the per-step scan of dense
+// Kernels: lcp_coopq_kernel (seven named switches, the table of its legal forms above it), lcp_coop_kernel (the per-step scan of dense
 // scenes, a cross-check), lcp_kernel (a lane per query, a cross-check) and lcp_exact_kernel (exact_ties).  choose_lcp_form picks one,
 // launch_lcp_form is the only place that names their instantiations.  The forms that lost their A/B runs are listed in
 // DESIGN_HISTORY.md with the last commit that holds their code; a measurement build (make tools) adds the ablation bits only.
@@ -447,22 +449,30 @@ __device__ __forceinline__ bool lcp_patch_dead(const LcpArgs& a, const float4 sp
 //           list -- DENSE's first test without its line-by-line exit, which lists of ~5 entries have no use for.
 //   CU      (lcp_cull_unit) points per bounding sphere of the patch test: 64, whole steps; 16, sub-patches, the live ones packed
 //           four to a step.
+//   SHARED  (with SPLIT and CU = 16, models of up to 8 192 points) the four wavefronts of a candidate fill and walk ONE list of live
+//           sub-patches (LCP_SHARED_LIVE entries, the memory of the four rings), step s of it to wavefront s & 3.  Else a ring per
+//           wavefront: larger models, whose sub-patches the list does not hold, and every form that is not split.  Chosen on the
+//           host by the model size alone, so that a larger model runs exactly the code it ran before the list existed.
 //
-// The legal forms (24 instantiations; the static_assert rejects every other):
+// The legal forms (29 instantiations; SHARED = 0 unless stated; the static_assert rejects every other):
 //   scoring, sparse   DENSE = 0, SPLIT in {0, 1}, FLAT in {0, 1}, NEAR in {0, 1}, CU in {16, 64}         16 forms
 //   scoring, dense    DENSE = 1, SPLIT = 1, FLAT = 0, NEAR = 0, CU in {16, 64}                            2 forms
+//   shared list       every scoring form with SPLIT = 1 and CU = 16 once more with SHARED = 1            5 forms
 //                     (the dense queue form is always split, whatever lcp_split and the model size say)
 //   detail, sparse    DENSE = 0, SPLIT = 0, FLAT = 0, NEAR in {0, 1}, CU in {16, 64}                      4 forms
 //   detail, dense     DENSE = 1, SPLIT = 0, FLAT = 0, NEAR = 0, CU in {16, 64}                            2 forms
 // ---------------------------------------------------------------------------------------------
-constexpr bool lcp_queue_form_legal(bool detail, bool dense, bool split, bool flat, bool near, int cu) {
-    return (cu == 16 || cu == 64) && (detail ? (!split && !flat && !(dense && near)) : (!dense || (split && !flat && !near)));
+// entries of the workgroup-wide list of live sub-patches (SPLIT, CU = 16): the sub-patches of a model of up to 8 192 points
+constexpr int LCP_SHARED_LIVE = 512;
+
+constexpr bool lcp_queue_form_legal(bool detail, bool dense, bool split, bool flat, bool near, int cu, bool shared) {
+    return (cu == 16 || cu == 64) && (!shared || (split && cu == 16)) && (detail ? (!split && !flat && !(dense && near)) : (!dense || (split && !flat && !near)));
 }
 
-template <bool DETAIL, bool DENSE, bool SPLIT, bool FLAT, bool NEAR, int CU>
+template <bool DETAIL, bool DENSE, bool SPLIT, bool FLAT, bool NEAR, int CU, bool SHARED>
 __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lcp_coopq_kernel(LcpArgs a, const float* __restrict__ T16, float* __restrict__ out,
                                                         int n, int32_t* __restrict__ hit_out, uint8_t* __restrict__ cnt_out) {
-    static_assert(lcp_queue_form_legal(DETAIL, DENSE, SPLIT, FLAT, NEAR, CU), "not one of the forms in the table above");
+    static_assert(lcp_queue_form_legal(DETAIL, DENSE, SPLIT, FLAT, NEAR, CU, SHARED), "not one of the forms in the table above");
     constexpr int WPB = lcp_waves_per_block(DETAIL, SPLIT);
     constexpr bool IDX = !DENSE;     // index-ordered lists: `<=` implements the tie rule (take_if_better)
     constexpr bool EARLY = DENSE;    // centre-sorted lists: line-by-line exit
@@ -728,6 +738,61 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
     // one step ahead, as below.
     __shared__ uint16_t live_q[WPB][128];   // global sub-patch indices, a ring (at most 3 + 64 entries pending)
     const int nsteps = (a.M + 63) >> 6;
+    if (SHARED) {   // (a.M <= 16 * LCP_SHARED_LIVE: choose_lcp_form)
+    // The four wavefronts of a candidate share ONE list of live sub-patches (the memory of the four rings, taken as one array).
+    // Window k (sub-patches 64 k .. 64 k + 63) is tested by wavefront k & 3; the live ones of a window are appended behind a base
+    // taken with one LDS atomic add per window, so the order of the list differs from run to run -- the scores do not, their sums
+    // are integers.  After one barrier the 64-lane steps are dealt round-robin: step s = entries 4 s .. 4 s + 3 goes to wavefront
+    // s & 3.  Every wavefront then runs ceil or floor of a quarter of the candidate's steps whatever part of the model the pose
+    // leaves alive, the candidate has one partial step instead of up to four (its empty lanes read the NaN padding behind the
+    // model), and its sub-patches take ceil(n / 64) windows instead of two per wavefront.  The step loop is a counted loop; the
+    // model point of the next step is requested one step ahead, as below.
+    __shared__ int live_n;
+    uint16_t* const live_all = &live_q[0][0];
+    static_assert(!SHARED || WPB * 128 == LCP_SHARED_LIVE, "the shared list is the memory of the per-wave rings");
+    if (threadIdx.x == 0) live_n = 0;
+    const int nsubs = (a.M + 15) >> 4;   // <= LCP_SHARED_LIVE: at most two windows per wavefront
+    const float snorm = a.patch ? lcp_linear_norm_bound(t0, t1, t2, t4, t5, t6, t8, t9, t10) : 0.0f;
+    unsigned long long lm[2];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {   // windows w and w + 4
+        const int q = ((w + 4 * j) << 6) + lane;
+        bool live = q < nsubs;
+        if (a.patch && live && !STOCS_ABLATE(a, 64))
+            live = !lcp_patch_dead(a, a.sub[q], snorm, t0, t1, t2, t4, t5, t6, t8, t9, t10, t12, t13, t14);
+        lm[j] = __ballot(live);
+    }
+    __syncthreads();   // live_n is zero for everyone (the tests above needed no LDS: nobody waits here for long)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        if (lm[j]) {   // (wave-uniform)
+            int base = 0;
+            if (lane == 0) base = atomicAdd(&live_n, __popcll(lm[j]));
+            base = __builtin_amdgcn_readfirstlane(base);
+            if ((lm[j] >> lane) & 1ull)   // base + rank < the candidate's live sub-patches <= nsubs <= LCP_SHARED_LIVE
+                live_all[base + __popcll(lm[j] & ((1ull << lane) - 1ull))] = (uint16_t)(((w + 4 * j) << 6) + lane);
+        }
+    }
+    __syncthreads();
+    const int nlive = __builtin_amdgcn_readfirstlane(live_n);
+    const int nst = (nlive + 3) >> 2;                                          // steps of the candidate
+    const int mine = __builtin_amdgcn_readfirstlane((nst + 3 - w) >> 2);       // steps w, w + 4, ... of them
+    // lane l of this wavefront's k-th step walks point l & 15 of entry 16 k + 4 w + (l >> 4); entries beyond the list: the NaN padding
+    const int e0 = 4 * w + (lane >> 4);
+    auto slot = [&](int k) { const int e = e0 + 16 * k; return e < nlive ? ((int)live_all[e] << 4) + (lane & 15) : (nsteps << 6) + lane; };
+    if (mine > 0) {
+        // (the sorted positions are padded to whole steps and one step beyond: no bounds checks on these loads)
+        int i = slot(0);
+        float4 p_next = a.mpos[i];
+        for (int k = 0; k < mine; ++k) {
+            const int ic = i;
+            const float4 p = p_next;
+            i = k + 1 < mine ? slot(k + 1) : ic;   // behind the last step its own point is requested once more: no branch around the load
+            p_next = a.mpos[i];
+            step(ic, p);
+        }
+    }
+    } else {
     const int wfirst = SPLIT ? w : 0, nw = SPLIT ? WPB : 1;
     // this wavefront's sub-patches: k -> step wfirst + (k >> 2) * nw, quarter k & 3 (wave-uniform: the walk's loops branch on scalars)
     const int nsub = __builtin_amdgcn_readfirstlane(4 * ((nsteps - wfirst + nw - 1) / nw));
@@ -780,6 +845,7 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
             }
         }
         if (last) break;
+    }
     }
     } else {
     // The wavefront's steps, 64 at a time: every lane tests the patch of one step (a.patch), the ballot is the list of the
@@ -998,13 +1064,14 @@ struct LcpForm {
     bool split;    // per-step and queue kernels: four wavefronts share a candidate
     bool flat, near;   // queue kernel (see the table above it); false elsewhere
     int cu;            // queue kernel: 16 or 64; 64 elsewhere
+    bool shared;       // queue kernel, split and cu == 16: one list of live sub-patches per candidate (models of up to 8 192 points)
 };
 
 static bool lcp_variant_selectable(int v) { return v == 99 || v == 0 || v == 24 || v == 31 || v == 39; }
 
 // The form a call runs.  Must not depend on the batch size (a candidate's score is batch-invariant).
 static LcpForm choose_lcp_form(const stocs_ctx* c, const LcpArgs& a, bool detail) {
-    LcpForm f = {LCP_QUEUE, detail, false, false, false, false, 64};
+    LcpForm f = {LCP_QUEUE, detail, false, false, false, false, 64, false};
     if (c->exact_ties) { f.kernel = LCP_EXACT; return f; }
     // dense grids keep their lists sorted by distance from the cell centre (not by index): only kernels instantiated with the
     // order-independent tie rule may scan them
@@ -1028,24 +1095,26 @@ static LcpForm choose_lcp_form(const stocs_ctx* c, const LcpArgs& a, bool detail
         f.near = !f.dense && a.has_nearest;   // pruned lists on a grid finer than epsilon: the distance bound in place of the sub-cell mask
         // the unit of the patch test (lcp_cull_unit); without the test the walk of whole steps (CU = 64) is the one to run
         f.cu = (a.patch && c->lcp_cull_unit == 16) ? 16 : 64;
+        f.shared = f.split && f.cu == 16 && a.M <= 16 * LCP_SHARED_LIVE;   // (the model size, never the batch)
     }
     return f;
 }
 
 typedef void (*LcpScanFn)(LcpArgs, const float*, float*, int, int32_t*, uint8_t*);
 
-// the queue kernel of a form: bits 0..5 of I are DETAIL, DENSE, SPLIT, FLAT, NEAR and CU == 16; NULL where the form is not legal
+// the queue kernel of a form: bits 0..6 of I are DETAIL, DENSE, SPLIT, FLAT, NEAR, CU == 16 and SHARED; NULL where the form is not legal
 template <int I>
 static LcpScanFn lcp_queue_fn() {
     constexpr bool DETAIL = (I & 1) != 0, DENSE = (I & 2) != 0, SPLIT = (I & 4) != 0, FLAT = (I & 8) != 0, NEAR = (I & 16) != 0;
     constexpr int CU = (I & 32) ? 16 : 64;
-    if constexpr (lcp_queue_form_legal(DETAIL, DENSE, SPLIT, FLAT, NEAR, CU)) return lcp_coopq_kernel<DETAIL, DENSE, SPLIT, FLAT, NEAR, CU>;
+    constexpr bool SHARED = (I & 64) != 0;
+    if constexpr (lcp_queue_form_legal(DETAIL, DENSE, SPLIT, FLAT, NEAR, CU, SHARED)) return lcp_coopq_kernel<DETAIL, DENSE, SPLIT, FLAT, NEAR, CU, SHARED>;
     else return NULL;
 }
 template <int... I>
 static LcpScanFn lcp_queue_fn(const LcpForm& f, std::integer_sequence<int, I...>) {
     static const LcpScanFn table[] = {lcp_queue_fn<I>()...};
-    return table[(f.detail ? 1 : 0) | (f.dense ? 2 : 0) | (f.split ? 4 : 0) | (f.flat ? 8 : 0) | (f.near ? 16 : 0) | (f.cu == 16 ? 32 : 0)];
+    return table[(f.detail ? 1 : 0) | (f.dense ? 2 : 0) | (f.split ? 4 : 0) | (f.flat ? 8 : 0) | (f.near ? 16 : 0) | (f.cu == 16 ? 32 : 0) | (f.shared ? 64 : 0)];
 }
 
 // Run-time form -> template instantiation, grid and block: the one place that names the kernels.
@@ -1060,11 +1129,11 @@ static int launch_lcp_form(stocs_ctx* c, const LcpForm& f, const LcpArgs& a, con
         else hipLaunchKernelGGL(lcp_exact_kernel<false>, grid, block, 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted, c->d_kd_nodes, c->d_kd_pts, c->d_ties);
     } else {
         LcpScanFn fn = NULL;
-        if (f.kernel == LCP_QUEUE) fn = lcp_queue_fn(f, std::make_integer_sequence<int, 64>());
+        if (f.kernel == LCP_QUEUE) fn = lcp_queue_fn(f, std::make_integer_sequence<int, 128>());
         else if (f.kernel == LCP_STEP) fn = f.detail ? lcp_coop_kernel<true, false> : (f.split ? lcp_coop_kernel<false, true> : lcp_coop_kernel<false, false>);
         else if (!f.detail) fn = f.dense ? lcp_kernel<false, false> : lcp_kernel<false, true>;
         else if (!f.dense) fn = lcp_kernel<true, true>;
-        if (!fn) { set_error("launch_lcp: no kernel for this form (kernel %d, detail %d, dense %d, split %d, flat %d, near %d, cu %d)", (int)f.kernel, (int)f.detail, (int)f.dense, (int)f.split, (int)f.flat, (int)f.near, f.cu); return STOCS_ERR_STATE; }
+        if (!fn) { set_error("launch_lcp: no kernel for this form (kernel %d, detail %d, dense %d, split %d, flat %d, near %d, cu %d, shared %d)", (int)f.kernel, (int)f.detail, (int)f.dense, (int)f.split, (int)f.flat, (int)f.near, f.cu, (int)f.shared); return STOCS_ERR_STATE; }
         hipLaunchKernelGGL(fn, grid, block, 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted);
     }
     STOCS_HIP_CHECK(hipGetLastError());

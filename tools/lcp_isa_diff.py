@@ -43,7 +43,8 @@ def pair_name(old):
     if "lcp_coopq_kernel" in old:
         if len(a) == 16:   # DETAIL UNR SORTQ PIPE IDX WPB FLAT SPLIT TILE EARLY GL FIRST NOSENT NEAR TINY CU
             a = [a[0], a[9], a[7], a[6], a[13], a[15]]
-        return "queue<detail=%d dense=%d split=%d flat=%d near=%d cu=%d>" % tuple(a)
+        shared = len(a) == 7 and a.pop() == 1   # SHARED = 1 has no form of its own in an older listing: main() compares it with SHARED = 0
+        return "queue<detail=%d dense=%d split=%d flat=%d near=%d cu=%d>" % tuple(a) + (" shared" if shared else "")
     if "lcp_coop_kernel" in old:
         if len(a) == 7:    # DETAIL UNR MASK EARLY IDX WPB SPLIT
             a = [a[0], a[6]]
@@ -57,16 +58,20 @@ def main():
     oldk = {pair_name(k): v for k, v in old.items()}
     print("| kernel | body | VGPR | SGPR | LDS B | scratch B |")
     print("|---|---|---|---|---|---|")
+    seen = set()
     for k, (body, res) in sorted((pair_name(k), v) for k, v in new.items()):
+        if k not in oldk and k.endswith(" shared") and k[:-7] in oldk:
+            oldk[k] = oldk[k[:-7]]
         if k not in oldk:
             print("| %s | no counterpart | %s |" % (k, res))
             continue
-        obody, ores = oldk.pop(k)
+        obody, ores = oldk[k]
+        seen.add(k)
         nd = sum(1 for l in difflib.unified_diff(obody, body, lineterm="", n=0) if l[:1] in "+-" and l[:3] not in ("+++", "---"))
         cell = lambda key: ("%d" % res[key]) if ores[key] == res[key] else "%d -> %d" % (ores[key], res[key])
         print("| %s | %s | %s | %s | %s | %s |" % (k, "identical" if nd == 0 else "differs by %d lines (%d -> %d)" % (nd, len(obody), len(body)),
                                                  cell("next_free_vgpr"), cell("next_free_sgpr"), cell("group_segment_fixed_size"), cell("private_segment_fixed_size")))
-    for k in sorted(oldk):
+    for k in sorted(set(oldk) - seen):
         print("| %s | only in the old listing | |" % k)
 
 
