@@ -5,7 +5,7 @@
 // reproducible.
 // Device (trial batches, stocs_run_trials_post): the candidates of a batch already sit on the device, so every trial of a piece is
 // clustered there, one workgroup per trial.  The host loop is greedy non-maximum suppression, so no sort is needed: the arg-max of
-// the survivors by (lcp bits, ~local index) -- highest score first, lowest index on ties, std::stable_sort's order -- is the next
+// the survivors by best_key (stocs_math.h) -- highest score first, lowest index on ties, std::stable_sort's order -- is the next
 // kept cluster, and every survivor within the thresholds of it (get_pose_diff(survivor, cluster), the host's argument order) drops
 // out.  Same decisions as the host function, rounds = kept clusters.
 #include <math.h>
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256) void trial_cluster_kernel(const float* __restr
                     const bool live = v[u] > thr;
                     alive[g] = live ? 1 : 0;
                     if (!live) continue;
-                    const unsigned long long key = ((unsigned long long)__float_as_uint(v[u]) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)i);
+                    const unsigned long long key = best_key(v[u], (uint32_t)i);
                     k = key > k ? key : k;
                     const int slot = atomicAdd(&n_surv, 1);
                     if (slot < CLUSTER_LDS) {
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(256) void trial_cluster_kernel(const float* __restr
             for (int j = (int)threadIdx.x; j < n_surv; j += 256) {
                 const unsigned long long key = skey[j];
                 if (!key) continue;
-                const int i = (int)(0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull));
+                const int i = (int)best_key_index(key);
                 bool live = i != last;
                 if (live && pose_trans_err3(strans[j], acc + 12) < a.min_distance &&
                     pose_rot_err(pose_inverse_rotation(P + ((size_t)i0 + (size_t)i) * 16), acc, a.sym) < a.min_angle)
@@ -97,18 +97,15 @@ __global__ __launch_bounds__(256) void trial_cluster_kernel(const float* __restr
                 }
                 if (!live) alive[g] = 0;
                 else {
-                    const unsigned long long key = ((unsigned long long)__float_as_uint(lcp[g]) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)i);
+                    const unsigned long long key = best_key(lcp[g], (uint32_t)i);
                     k = key > k ? key : k;
                 }
             }
         }
-        for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(k, off, 64); k = o > k ? o : k; }
-        if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = k;
-        __syncthreads();   // (also: the survivor list of the first pass is complete)
-        for (int w = 0; w < 4; ++w) k = sh[w] > k ? sh[w] : k;
+        k = wg_max_key<4>(k, sh);   // (its barrier also completes the survivor list of the first pass)
         if (!k) break;   // (uniform: every thread took the same maximum)
         if (last < 0) in_lds = n_surv <= CLUSTER_LDS;
-        last = (int)(0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFull));
+        last = (int)best_key_index(k);
         if (threadIdx.x == 0) hyp_idx[h0 + kept] = last;
         if (threadIdx.x < 16) acc[threadIdx.x] = P[((size_t)i0 + (size_t)last) * 16 + threadIdx.x];
         ++kept;

@@ -1308,13 +1308,12 @@ struct PlanLayout {
     size_t jobs, bids, err, rng, nr, tot, pseg, qseg, poff, qoff, spo, sqo, out, bytes;   // device
     size_t up, cone, stage;                                                                // pinned staging
     explicit PlanLayout(int nB) {
-        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
         const size_t nb = (size_t)nB;
-        jobs = 0; bids = jobs + al(sizeof(BaseJob) * nb); err = bids + al(16 * nb); rng = err + 256; nr = rng + al(2 * nb * 128 * 8);
-        tot = nr + al(2 * nb * 4); pseg = tot + al(2 * nb * 4); qseg = pseg + al(nb * 128 * sizeof(Segment));
-        poff = qseg + al(nb * 128 * sizeof(Segment)); qoff = poff + al((nb + 1) * 4); spo = qoff + al((nb + 2) * 4); sqo = spo + al((nb + 1) * 4);
-        out = sqo + al((nb + 1) * 4); bytes = out + 256;
-        up = err + 256; cone = up; stage = cone + al(sizeof(float4) * nb);
+        jobs = 0; bids = jobs + al256(sizeof(BaseJob) * nb); err = bids + al256(16 * nb); rng = err + 256; nr = rng + al256(2 * nb * 128 * 8);
+        tot = nr + al256(2 * nb * 4); pseg = tot + al256(2 * nb * 4); qseg = pseg + al256(nb * 128 * sizeof(Segment));
+        poff = qseg + al256(nb * 128 * sizeof(Segment)); qoff = poff + al256((nb + 1) * 4); spo = qoff + al256((nb + 2) * 4); sqo = spo + al256((nb + 1) * 4);
+        out = sqo + al256((nb + 1) * 4); bytes = out + 256;
+        up = err + 256; cone = up; stage = cone + al256(sizeof(float4) * nb);
     }
 };
 

@@ -534,9 +534,8 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
     c->lcp_split = 1;
     c->lcp_flat = getenv("STOCS_LCP_FLAT") ? atoi(getenv("STOCS_LCP_FLAT")) : 1;
     c->lcp_order = getenv("STOCS_LCP_ORDER") ? atoi(getenv("STOCS_LCP_ORDER")) : 1;
-    c->d_order = NULL; c->order_bytes = 0;
-    c->exact_ties = 0; c->kd_ready = false; c->d_kd = NULL; c->kd_bytes = 0; c->d_kd_nodes = NULL; c->d_kd_pts = NULL; c->d_ties = NULL; c->ties_started = false;
-    c->d_cdf = NULL; c->cdf_bytes = 0; c->cdf_n = 0; c->prior_epoch = 1; c->cdf_epoch = 0;
+    c->exact_ties = 0; c->kd_ready = false; c->d_kd_nodes = NULL; c->d_kd_pts = NULL; c->d_ties = NULL; c->ties_started = false;
+    c->cdf_n = 0; c->prior_epoch = 1; c->cdf_epoch = 0;
     memset(&c->grid, 0, sizeof(c->grid));
     c->d_spos = c->d_snrmw = c->d_mpos = c->d_mnrm = c->d_munit = c->d_mpos_raw = c->d_mpos_s = c->d_mnrm_s = NULL;
     c->d_spix = NULL; c->d_mperm = NULL; c->d_mpatch = NULL; c->d_msub = NULL; c->d_scene_mem = NULL; c->scene_cap = 0;
@@ -658,13 +657,14 @@ int stocs_ctx_destroy(stocs_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     void* ptrs[] = {c->d_scene_mem, c->d_mpos, c->d_mnrm, c->d_munit, c->d_mpos_raw, c->d_mpos_s,
                     c->d_mnrm_s, c->d_mperm, c->d_mpatch, c->d_msub, c->index.d_bucket_start,
-                    c->index.d_pairs, c->index.d_exists, c->d_scratch, c->d_best, c->d_cand, c->d_order, c->d_cdf, c->d_kd};
+                    c->index.d_pairs, c->index.d_exists, c->d_scratch, c->d_best, c->d_cand};
     stocs_internal_free_congruent(c);
     stocs_internal_free_instance(c);
     stocs_internal_free_trials(c);
     stocs_internal_free_refine(c);
     stocs_internal_free_track(c);
     c->grid_mem.destroy(); c->grid_ws.destroy();
+    c->order.free(); c->cdf.free(); c->kd.free();
     if (c->h_pin) (void)hipHostFree(c->h_pin);
     for (void* p : ptrs) if (p) (void)hipFree(p);
     (void)hipEventDestroy(c->ev0);
@@ -805,15 +805,11 @@ int64_t stocs_device_alloc_count(void) { return (int64_t)__atomic_load_n(&g_dev_
 uint64_t stocs_pack_best(float lcp, uint32_t id) {
     // a score that is not positive never wins (stocs.cpp:987-998: strict > from 0, all-zero => no pose): its key is 0 =
     // "none", the same value best_kernel produces, so a rank whose candidates all scored 0 cannot win the all-reduce
-    if (!(lcp > 0.0f)) return 0;
-    uint32_t bits;
-    memcpy(&bits, &lcp, 4);
-    return ((uint64_t)bits << 32) | (uint64_t)(0xFFFFFFFFu - id);
+    return lcp > 0.0f ? (uint64_t)best_key(lcp, id) : 0;
 }
 void stocs_unpack_best(uint64_t key, float* lcp, uint32_t* id) {
-    uint32_t bits = (uint32_t)(key >> 32);
-    if (lcp) memcpy(lcp, &bits, 4);
-    if (id) *id = 0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFu);
+    if (lcp) *lcp = best_key_score(key);
+    if (id) *id = best_key_index(key);
 }
 
 }  // extern "C"

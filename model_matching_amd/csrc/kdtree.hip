@@ -103,20 +103,17 @@ int ensure_kdtree(stocs_ctx* c) {
     std::vector<float> p3((size_t)c->nS * 3);
     for (int i = 0; i < c->nS; ++i) { p3[3 * (size_t)i] = c->h_spos[i].x; p3[3 * (size_t)i + 1] = c->h_spos[i].y; p3[3 * (size_t)i + 2] = c->h_spos[i].z; }
     kd_build_host(p3.data(), c->nS, &c->kd_host);
-    const size_t nb = ((c->kd_host.nodes.size() * sizeof(KdNodeP) + 255) / 256) * 256, pb = c->kd_host.pts.size() * sizeof(float4);
+    const size_t nb = al256(c->kd_host.nodes.size() * sizeof(KdNodeP)), pb = c->kd_host.pts.size() * sizeof(float4);
     const size_t need = 256 + nb + pb;
     STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));   // nothing may still read the old tree (nor the counters)
-    if (need > c->kd_bytes) {
-        if (c->d_kd) { (void)hipFree(c->d_kd); c->d_kd = NULL; c->kd_bytes = 0; }
-        STOCS_HIP_CHECK(dev_malloc((void**)&c->d_kd, need + need / 4));
-        c->kd_bytes = need + need / 4;
-        STOCS_HIP_CHECK(hipMemsetAsync(c->d_kd, 0, 256, c->stream));
-    }
-    c->d_ties = (unsigned long long*)c->d_kd;
-    c->d_kd_nodes = c->kd_host.nodes.empty() ? NULL : (const KdNodeP*)(c->d_kd + 256);
-    c->d_kd_pts = (const float4*)(c->d_kd + 256 + nb);
-    if (nb) STOCS_HIP_CHECK(hipMemcpyAsync(c->d_kd + 256, c->kd_host.nodes.data(), c->kd_host.nodes.size() * sizeof(KdNodeP), hipMemcpyHostToDevice, c->stream));
-    if (pb) STOCS_HIP_CHECK(hipMemcpyAsync(c->d_kd + 256 + nb, c->kd_host.pts.data(), pb, hipMemcpyHostToDevice, c->stream));
+    const size_t had = c->kd.bytes;
+    { const int rc = c->kd.grow(c->stream, need); if (rc) return rc; }
+    if (c->kd.bytes != had) STOCS_HIP_CHECK(hipMemsetAsync(c->kd.p, 0, 256, c->stream));   // a new block: the counters start at 0
+    c->d_ties = (unsigned long long*)c->kd.p;
+    c->d_kd_nodes = c->kd_host.nodes.empty() ? NULL : (const KdNodeP*)(c->kd.p + 256);
+    c->d_kd_pts = (const float4*)(c->kd.p + 256 + nb);
+    if (nb) STOCS_HIP_CHECK(hipMemcpyAsync(c->kd.p + 256, c->kd_host.nodes.data(), c->kd_host.nodes.size() * sizeof(KdNodeP), hipMemcpyHostToDevice, c->stream));
+    if (pb) STOCS_HIP_CHECK(hipMemcpyAsync(c->kd.p + 256 + nb, c->kd_host.pts.data(), pb, hipMemcpyHostToDevice, c->stream));
     STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));   // (pageable sources)
     c->kd_ready = true;
     return STOCS_OK;

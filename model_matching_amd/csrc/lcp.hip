@@ -137,7 +137,7 @@ __device__ __forceinline__ void lcp_store(const LcpArgs& a, float* __restrict__ 
     const float s = lcp_finish(total, a.M);
     out[cand] = s;
     if (a.best && s > 0.0f)
-        atomicMax(a.best, ((unsigned long long)__float_as_uint(s) << 32) | (unsigned long long)(0xFFFFFFFFu - (a.id_offset + (uint32_t)cand)));
+        atomicMax(a.best, best_key(s, a.id_offset + (uint32_t)cand));
 }
 
 // candidate update: inclusive radius (kdtree.h:424), ties -> larger scene index.  When a list is stored in
@@ -988,25 +988,19 @@ __global__ __launch_bounds__(256) void lcp_exact_kernel(LcpArgs a, const float* 
     }
 }
 
-// compute_best_transform (stocs.cpp:982-1004) on the device: max of the packed (score, ~id) keys --
-// larger score wins, lower id wins ties, non-positive scores never win.  Integer max: order independent.
+// compute_best_transform (stocs.cpp:982-1004) on the device: the maximum of the positive scores' keys (best_key, stocs_math.h)
 __global__ __launch_bounds__(256) void best_kernel(const float* __restrict__ lcp, int n, uint32_t id_offset, unsigned long long* __restrict__ best) {
     unsigned long long k = 0;
     for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
         const float s = lcp[i];
-        if (s > 0.0f) {
-            const unsigned long long key = ((unsigned long long)__float_as_uint(s) << 32) | (unsigned long long)(0xFFFFFFFFu - (id_offset + (uint32_t)i));
-            k = key > k ? key : k;
-        }
+        if (s > 0.0f) { const unsigned long long key = best_key(s, id_offset + (uint32_t)i); k = key > k ? key : k; }
     }
-    for (int off = 32; off > 0; off >>= 1) {
-        const unsigned long long o = __shfl_xor(k, off, 64);
-        k = o > k ? o : k;
-    }
+    k = wave_max_key(k);
     if ((threadIdx.x & 63) == 0 && k) atomicMax(best, k);
 }
 
-// the same for one batch of moderate size in ONE workgroup: no zero fill in front, no atomics, the key is simply written
+// the same for one batch of moderate size in ONE workgroup: no zero fill in front, no atomics, the key is simply written.  best_key and wave_max_key
+// stay written out here: with either the compiler orders this kernel's instructions differently (profiles/post_layer_refactor.md)
 __global__ __launch_bounds__(1024) void best_single_kernel(const float* __restrict__ lcp, int n, uint32_t id_offset, unsigned long long* __restrict__ best) {
     __shared__ unsigned long long sh[16];
     unsigned long long k = 0;
@@ -1195,16 +1189,12 @@ int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d
     // lcp_order >= 2 orders whatever the size
     const bool lists_spill = (double)c->grid.n_entries * 16.0 >= 12.0e6;
     if (!d_hit && n >= 1024 && (double)n * (double)c->nM >= 1.5e8 && c->lcp_order && (lists_spill || c->lcp_order >= 2)) {
-        const size_t kb = (((size_t)n * 4 + 255) / 256) * 256;
+        const size_t kb = al256((size_t)n * 4);
         size_t tb = 0;
         STOCS_HIP_CHECK(sort_pairs(NULL, tb, (const uint32_t*)NULL, (uint32_t*)NULL, (const uint32_t*)NULL, (uint32_t*)NULL, (size_t)n, 0, 24, c->stream));
         const size_t need = 4 * kb + tb;
-        if (c->order_bytes < need) {
-            if (c->d_order) { STOCS_HIP_CHECK(hipStreamSynchronize(c->stream)); (void)hipFree(c->d_order); c->d_order = NULL; c->order_bytes = 0; }
-            STOCS_HIP_CHECK(dev_malloc(&c->d_order, need + need / 4));
-            c->order_bytes = need + need / 4;
-        }
-        char* p = (char*)c->d_order;
+        { const int rc = c->order.grow(c->stream, need); if (rc) return rc; }
+        char* p = c->order.p;
         uint32_t* keys = (uint32_t*)p; uint32_t* keys_s = (uint32_t*)(p + kb);
         int32_t* vals = (int32_t*)(p + 2 * kb); int32_t* order = (int32_t*)(p + 3 * kb);
         void* tmp = p + 4 * kb;
@@ -1274,7 +1264,7 @@ int stocs_score_transforms(stocs_ctx* c, const float* T_host, int n, float* lcp_
     int rc = ensure_scratch(c, tb + lb + 256);
     if (rc) return rc;
     float* dT = (float*)c->d_scratch;
-    float* dL = (float*)((char*)c->d_scratch + ((tb + 255) / 256) * 256);
+    float* dL = (float*)((char*)c->d_scratch + al256(tb));
     STOCS_HIP_CHECK(hipMemcpyAsync(dT, T_host, tb, hipMemcpyHostToDevice, c->stream));
     rc = launch_lcp(c, dT, n, dL, NULL, NULL, NULL, 0);
     if (rc) return rc;
@@ -1294,7 +1284,7 @@ int stocs_lcp_detail(stocs_ctx* c, const float* T_host, int32_t* hit, uint8_t* c
     float* dT = (float*)base;
     float* dL = (float*)(base + 256);
     int32_t* dH = (int32_t*)(base + 512);
-    uint8_t* dC = (uint8_t*)(base + 512 + ((M * 4 + 255) / 256) * 256);
+    uint8_t* dC = (uint8_t*)(base + 512 + al256(M * 4));
     STOCS_HIP_CHECK(hipMemcpyAsync(dT, T_host, 64, hipMemcpyHostToDevice, c->stream));
     rc = launch_lcp(c, dT, 1, dL, dH, dC, NULL, 0);
     if (rc) return rc;
@@ -1321,7 +1311,7 @@ int stocs_lcp_hit_count(stocs_ctx* c, const void* d_T16, int n, int64_t* hits, i
     if (n == 0 || c->nM == 0) return STOCS_OK;
     const size_t M = (size_t)c->nM;
     const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)256 << 20) / (5 * M)));
-    const size_t hb = (((size_t)chunk * M * 4 + 255) / 256) * 256, cb = (((size_t)chunk * M + 255) / 256) * 256, lb = (((size_t)chunk * 4 + 255) / 256) * 256;
+    const size_t hb = al256((size_t)chunk * M * 4), cb = al256((size_t)chunk * M), lb = al256((size_t)chunk * 4);
     int rc = ensure_scratch(c, 256 + lb + hb + cb);
     if (rc) return rc;
     char* base = (char*)c->d_scratch;

@@ -51,15 +51,13 @@ struct RefineGrid {
     float lo[3], hi[3];   // model box widened by the distance: a source point outside it has no correspondence
     uint32_t* d_off;      // 8 ncells + 1 offsets into the cell-ordered positions: cell c, octant o starts at d_off[8 c + o]
     float4* d_pos;        // xyz + bits(model index)
-    char* mem; size_t bytes;
+    DevBlock mem;
 };
 
 struct RefineState {
     RefineGrid g;
-    char* d_work; size_t work_bytes;   // hypotheses | T in | source indices | partials | outputs (grow-only)
+    DevBlock work;   // hypotheses | T in | source indices | partials | outputs (grow-only)
 };
-
-static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 __global__ __launch_bounds__(256) void refine_keys_kernel(const float4* __restrict__ mpos, int nM, float ox, float oy, float oz, float inv_h, int nx, int ny,
                                                           int nz, uint32_t* __restrict__ keys, uint32_t* __restrict__ vals) {
@@ -319,8 +317,8 @@ __global__ __launch_bounds__(64) void refine_solve_kernel(RefHyp* __restrict__ h
     H->iters += 1;
 }
 
-// T' = T U^-1 (centred frames), its camera form with the arithmetic of rigid_transform_kernel (transform.hip: tc = (c1 + cscene) -
-// R (c2 + cmodel), here with c1 = t', c2 = 0), the counts.  A hypothesis that was never updated comes back bit for bit.
+// T' = T U^-1 (centred frames), its camera form (camera_from_centred: rigid_transform_kernel's tc = (c1 + cscene) - R (c2 + cmodel)
+// with c1 = t', c2 = 0), the counts.  A hypothesis that was never updated comes back bit for bit.
 __global__ __launch_bounds__(64) void refine_final_kernel(const float* __restrict__ Tin, const RefHyp* __restrict__ hyp, int n, V3 cscene, V3 cmodel,
                                                           float* __restrict__ Tout, float* __restrict__ Pout, int32_t* __restrict__ ncorr, int32_t* __restrict__ iters) {
     const int k = blockIdx.x * blockDim.x + threadIdx.x;
@@ -341,12 +339,7 @@ __global__ __launch_bounds__(64) void refine_final_kernel(const float* __restric
         }
         To[3] = To[7] = To[11] = 0.0f; To[15] = 1.0f;
     }
-    const V3 t = mk3(To[12], To[13], To[14]);
-    const V3 cm = cmodel;
-    const V3 Rcm = mk3(To[0] * cm.x + (To[4] * cm.y + To[8] * cm.z), To[1] * cm.x + (To[5] * cm.y + To[9] * cm.z), To[2] * cm.x + (To[6] * cm.y + To[10] * cm.z));
-    const V3 tc = (t + cscene) - Rcm;
-    for (int c = 0; c < 3; ++c) { for (int r = 0; r < 3; ++r) Po[c * 4 + r] = To[c * 4 + r]; Po[c * 4 + 3] = 0.0f; }
-    Po[12] = tc.x; Po[13] = tc.y; Po[14] = tc.z; Po[15] = 1.0f;
+    camera_from_centred(To, cscene, cmodel, Po);
     ncorr[k] = H.ncorr;
     iters[k] = H.iters;
 }
@@ -377,24 +370,18 @@ static int build_refine_grid(stocs_ctx* c, RefineState* S, float d) {
     while (((int64_t)1 << bits) < nsub) ++bits;
     size_t tmp_bytes = 0;
     STOCS_HIP_CHECK(sort_pairs(NULL, tmp_bytes, (const uint32_t*)NULL, (uint32_t*)NULL, (const uint32_t*)NULL, (uint32_t*)NULL, (size_t)nM, 0, (unsigned)bits, c->stream));
-    const size_t ob = al256((size_t)(nsub + 1) * 4), pb = al256((size_t)nM * 16), kb = al256((size_t)nM * 4);
-    const size_t need = ob + pb + 4 * kb + al256(tmp_bytes);
-    if (g.bytes < need) {
-        if (g.mem) { STOCS_HIP_CHECK(hipStreamSynchronize(c->stream)); (void)hipFree(g.mem); g.mem = NULL; g.bytes = 0; }
-        STOCS_HIP_CHECK(dev_malloc(&g.mem, need + need / 4));
-        g.bytes = need + need / 4;
-    }
-    char* p = g.mem;
-    g.d_off = (uint32_t*)p; p += ob;
-    g.d_pos = (float4*)p; p += pb;
-    uint32_t* keys = (uint32_t*)p; p += kb;
-    uint32_t* keys_s = (uint32_t*)p; p += kb;
-    uint32_t* vals = (uint32_t*)p; p += kb;
-    uint32_t* vals_s = (uint32_t*)p; p += kb;
+    // offsets | cell-ordered positions | keys, sorted keys, values, sorted values | sort scratch
+    Carve cv;
+    const size_t o_off = cv.take((size_t)(nsub + 1) * 4), o_pos = cv.take((size_t)nM * 16), o_keys = cv.take((size_t)nM * 4), o_keys_s = cv.take((size_t)nM * 4),
+                 o_vals = cv.take((size_t)nM * 4), o_vals_s = cv.take((size_t)nM * 4), o_tmp = cv.take(tmp_bytes);
+    { const int rc = g.mem.grow(c->stream, cv.total); if (rc) return rc; }
+    g.d_off = Carve::at<uint32_t>(g.mem.p, o_off); g.d_pos = Carve::at<float4>(g.mem.p, o_pos);
+    uint32_t* keys = Carve::at<uint32_t>(g.mem.p, o_keys); uint32_t* keys_s = Carve::at<uint32_t>(g.mem.p, o_keys_s);
+    uint32_t* vals = Carve::at<uint32_t>(g.mem.p, o_vals); uint32_t* vals_s = Carve::at<uint32_t>(g.mem.p, o_vals_s);
     const unsigned mb = (unsigned)((nM + 255) / 256);
     hipLaunchKernelGGL(refine_keys_kernel, dim3(mb), dim3(256), 0, c->stream, c->d_mpos, nM, g.ox, g.oy, g.oz, g.inv_h, g.nx, g.ny, g.nz, keys, vals);
     STOCS_HIP_CHECK(hipGetLastError());
-    STOCS_HIP_CHECK(sort_pairs(p, tmp_bytes, keys, keys_s, vals, vals_s, (size_t)nM, 0, (unsigned)bits, c->stream));
+    STOCS_HIP_CHECK(sort_pairs(g.mem.p + o_tmp, tmp_bytes, keys, keys_s, vals, vals_s, (size_t)nM, 0, (unsigned)bits, c->stream));
     hipLaunchKernelGGL(refine_scatter_kernel, dim3(mb), dim3(256), 0, c->stream, c->d_mpos, nM, vals_s, g.d_pos);
     STOCS_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(refine_offsets_kernel, dim3((unsigned)((nsub + 1 + 255) / 256)), dim3(256), 0, c->stream, keys_s, nM, (int)nsub, g.d_off);
@@ -409,9 +396,7 @@ int refine_prepare(stocs_ctx* c, int n, int nsrc, float max_correspondence_dista
     const int nchunks = (nsrc + REFINE_CHUNK - 1) / REFINE_CHUNK;
     if ((int64_t)n * std::max(nchunks, 1) >= ((int64_t)1 << 31)) { set_error("stocs_refine_poses: %d hypotheses x %d chunks: too many workgroups", n, nchunks); return STOCS_ERR_INVALID; }
     if (!c->refine) {
-        RefineState* S = new RefineState();
-        memset(S, 0, sizeof(*S));
-        c->refine = S;
+        c->refine = new RefineState();   // (value-initialised: no grid, no workspace)
     }
     RefineState* S = (RefineState*)c->refine;
     if (S->g.dist != max_correspondence_distance) {
@@ -419,21 +404,13 @@ int refine_prepare(stocs_ctx* c, int n, int nsrc, float max_correspondence_dista
         if (rc) { S->g.dist = 0.0f; return rc; }
     }
     // device block: hypotheses | T in | source indices | partials | T out | P out | lcp | n_corr | iterations
-    const size_t hb = al256((size_t)n * sizeof(RefHyp)), tb = al256((size_t)n * 64), ib = al256((size_t)std::max(nsrc, 1) * 4);
-    const size_t pb = al256((size_t)n * std::max(nchunks, 1) * 28 * 8);
     const size_t out_bytes = (size_t)n * (64 + 64 + 4 + 4 + 4);
-    const size_t need = hb + tb + ib + pb + al256(out_bytes);
-    if (S->work_bytes < need) {
-        if (S->d_work) { STOCS_HIP_CHECK(hipStreamSynchronize(c->stream)); (void)hipFree(S->d_work); S->d_work = NULL; S->work_bytes = 0; }
-        STOCS_HIP_CHECK(dev_malloc(&S->d_work, need + need / 4));
-        S->work_bytes = need + need / 4;
-    }
-    char* p = S->d_work;
-    w->d_hyp = p; p += hb;
-    w->d_Tin = (float*)p; p += tb;
-    w->d_idx = (int32_t*)p; p += ib;
-    w->d_part = (double*)p; p += pb;
-    w->d_Tout = (float*)p;
+    Carve cv;
+    const size_t o_hyp = cv.take((size_t)n * sizeof(RefHyp)), o_Tin = cv.take((size_t)n * 64), o_idx = cv.take((size_t)std::max(nsrc, 1) * 4),
+                 o_part = cv.take((size_t)n * std::max(nchunks, 1) * 28 * 8), o_out = cv.take(out_bytes);
+    { const int rc = S->work.grow(c->stream, cv.total); if (rc) return rc; }
+    w->d_hyp = S->work.p + o_hyp; w->d_Tin = Carve::at<float>(S->work.p, o_Tin); w->d_idx = Carve::at<int32_t>(S->work.p, o_idx);
+    w->d_part = Carve::at<double>(S->work.p, o_part); w->d_Tout = Carve::at<float>(S->work.p, o_out);
     w->d_Pout = w->d_Tout + (size_t)n * 16;
     w->d_lcp = w->d_Pout + (size_t)n * 16;
     w->d_nc = (int32_t*)(w->d_lcp + n);
@@ -490,8 +467,7 @@ using namespace stocs;
 extern "C" void stocs_internal_free_refine(stocs_ctx* c) {
     if (!c || !c->refine) return;
     RefineState* S = (RefineState*)c->refine;
-    if (S->g.mem) (void)hipFree(S->g.mem);
-    if (S->d_work) (void)hipFree(S->d_work);
+    S->g.mem.free(); S->work.free();
     delete S;
     c->refine = NULL;
 }

@@ -463,9 +463,8 @@ struct SampleBuffers {
 
 static int carve(stocs_ctx* c, int nB, SampleBuffers* sb) {
     const size_t S = (size_t)std::max(c->nS, 1);
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t bw = al((size_t)nB * S * 4), bc = al(S * 4), bi = al((size_t)nB * 16), bf = al((size_t)nB * 4), br = al((size_t)nB * 8),
-                 bo = al((size_t)nB * sizeof(BaseOut));
+    const size_t bw = al256((size_t)nB * S * 4), bc = al256(S * 4), bi = al256((size_t)nB * 16), bf = al256((size_t)nB * 4), br = al256((size_t)nB * 8),
+                 bo = al256((size_t)nB * sizeof(BaseOut));
     int rc = ensure_scratch(c, bw + bc + bi + bf + br + bo);
     if (rc) return rc;
     char* p = (char*)c->d_scratch;
@@ -1331,18 +1330,14 @@ __global__ __launch_bounds__(NT, 8) void class_attempts_lean_kernel(ClassArgs A,
 // the prior's prefix sums for the lean kernel: (re)computed when the class probabilities on the device have changed since the last time
 static int ensure_prior_cdf(stocs_ctx* c) {
     const size_t S = (size_t)c->nS;
-    if (c->d_cdf && c->cdf_epoch == c->prior_epoch && c->cdf_n == S) return STOCS_OK;
+    if (c->cdf.p && c->cdf_epoch == c->prior_epoch && c->cdf_n == S) return STOCS_OK;
     size_t tb = 0;
     STOCS_HIP_CHECK(exclusive_scan(NULL, tb, (const unsigned long long*)NULL, (unsigned long long*)NULL, S + 1, c->stream));
     const size_t need = 2 * ((S + 1) * 8 + 256) + tb + 256;
-    if (c->cdf_bytes < need) {
-        if (c->d_cdf) { STOCS_HIP_CHECK(hipStreamSynchronize(c->stream)); (void)hipFree(c->d_cdf); c->d_cdf = NULL; c->cdf_bytes = 0; }
-        STOCS_HIP_CHECK(dev_malloc((void**)&c->d_cdf, need + need / 4));
-        c->cdf_bytes = need + need / 4;
-    }
-    unsigned long long* cdf = (unsigned long long*)c->d_cdf;
-    unsigned long long* fix = (unsigned long long*)((char*)c->d_cdf + (((S + 1) * 8 + 255) & ~(size_t)255));
-    void* tmp = (char*)fix + (((S + 1) * 8 + 255) & ~(size_t)255);
+    { const int rc = c->cdf.grow(c->stream, need); if (rc) return rc; }
+    unsigned long long* cdf = (unsigned long long*)c->cdf.p;
+    unsigned long long* fix = (unsigned long long*)(c->cdf.p + al256((S + 1) * 8));
+    void* tmp = (char*)fix + al256((S + 1) * 8);
     hipLaunchKernelGGL(prior_fix_kernel, dim3((unsigned)((S + 256) / 256)), dim3(256), 0, c->stream, (const float4*)c->d_spos, (int)S, fix);
     STOCS_HIP_CHECK(exclusive_scan(tmp, tb, (const unsigned long long*)fix, cdf, S + 1, c->stream));
     c->cdf_epoch = c->prior_epoch; c->cdf_n = S;
@@ -1413,7 +1408,7 @@ static int launch_class_attempts(stocs_ctx* c, ClassArgs A, unsigned n_workgroup
     // (and the runtime refuses a value that does not fit the 160 KB together with the kernel's static LDS: 4.4 KB in the lean kernel)
     if (f.lds > 64 * 1024) STOCS_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, f.kernel == CLASS_LEAN ? LEAN_MAX_LDS : MAX_DYNAMIC_LDS));
     int n_attempts = (int)n_workgroups, cap = f.cap;
-    const unsigned long long* cdf = (const unsigned long long*)c->d_cdf;
+    const unsigned long long* cdf = (const unsigned long long*)c->cdf.p;
     void* args[] = {&A, &seed, &first_attempt, &n_attempts, &cdf, &cap};     // (the full-size kernels take the first four)
     STOCS_HIP_CHECK(hipLaunchKernel(fn, dim3(n_workgroups), dim3((unsigned)f.threads), args, f.lds, c->stream));
     return STOCS_OK;
@@ -1442,11 +1437,10 @@ static int sample_class(stocs_ctx* c, uint64_t seed, int first_attempt, int nB, 
     if (getenv("STOCS_CLASS_MULTI_KERNEL")) return sample_class_multi(c, seed, first_attempt, nB, ids, inv, valid);   // the nine-launch form (A/B)
     const size_t S = (size_t)c->nS;
     const bool dbg = getenv("STOCS_DEBUG_TIMING") != NULL;
-    const bool cdf_current = c->d_cdf && c->cdf_epoch == c->prior_epoch && c->cdf_n == S;
+    const bool cdf_current = c->cdf.p && c->cdf_epoch == c->prior_epoch && c->cdf_n == S;
     const ClassForm form = choose_class_form(c, !dbg && (nB > 256 || cdf_current || getenv("STOCS_CLASS_LEAN_KERNEL")));   // (the reasons: at choose_class_form)
     const bool lean = form.kernel == CLASS_LEAN, wlds = form.kernel != CLASS_FULL_DEVICE_MEMORY;
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t b_res = al((size_t)nB * sizeof(BaseOut)), b_w = wlds ? 0 : al((size_t)nB * S * 4), b_sv = wlds ? 0 : al((size_t)nB * S * 4), b_slots = al((size_t)nB * 4);
+    const size_t b_res = al256((size_t)nB * sizeof(BaseOut)), b_w = wlds ? 0 : al256((size_t)nB * S * 4), b_sv = wlds ? 0 : al256((size_t)nB * S * 4), b_slots = al256((size_t)nB * 4);
     int rc = ensure_scratch(c, b_res + b_w + b_sv + b_slots + 256);
     if (rc) return rc;
     char* p = (char*)c->d_scratch;
@@ -1503,14 +1497,14 @@ static int refresh_class_prob_on_device(stocs_ctx* c) {
 struct InstanceState {
     bool runs_valid = false;     // runs / pt_run / edge_pt match the current edge map and scene
     int S = 0, Sw = 0;
-    char* d_mem = NULL; size_t mem_bytes = 0;
+    DevBlock mem;                // everything below up to d_pair_off, carved in prepare_instance_state
     uint16_t* d_run_s = NULL; uint16_t* d_run_e = NULL; uint32_t* d_row_off = NULL;
     int32_t* d_pt_run = NULL; uint8_t* d_edge_pt = NULL; uint8_t* d_prev_in = NULL; uint8_t* d_label = NULL;
     float* d_cls = NULL; uint32_t* d_maskbits = NULL; uint32_t* d_segbits = NULL; uint32_t* d_parent = NULL;
     int32_t* d_sv = NULL; float* d_w = NULL;
     RunPair* d_pairs = NULL; uint32_t* d_pair_off = NULL;
     char* d_queue = NULL; size_t queue_bytes = 0;   // hand-over slots between the two workgroups (grown on demand)
-    char* d_trials = NULL; size_t trials_bytes = 0; // per-trial copies of the mutable state of a trial batch (stocs_run_trials)
+    DevBlock trials;                                // per-trial copies of the mutable state of a trial batch (stocs_run_trials)
     size_t n_runs = 0;
     std::vector<uint32_t> h_segbits;
 };
@@ -1518,9 +1512,9 @@ struct InstanceState {
 static void free_instance_state(stocs_ctx* c) {
     InstanceState* I = (InstanceState*)c->inst;
     if (!I) return;
-    if (I->d_mem) (void)hipFree(I->d_mem);
+    I->mem.free();
     if (I->d_queue) (void)hipFree(I->d_queue);
-    if (I->d_trials) (void)hipFree(I->d_trials);
+    I->trials.free();
     delete I;
     c->inst = NULL;
 }
@@ -1577,18 +1571,13 @@ static int prepare_instance_state(stocs_ctx* c) {
         }
     }
     const int Sw = ((S + 63) / 64) * 2;   // whole 64-bit ballots
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     const size_t nr = std::max<size_t>(rs.size(), 1);
-    const size_t o_rs = 0, o_re = o_rs + al(nr * 2), o_ro = o_re + al(nr * 2), o_pr = o_ro + al(((size_t)H + 1) * 4), o_ep = o_pr + al((size_t)S * 4),
-                 o_pi = o_ep + al(S), o_lb = o_pi + al(S), o_cl = o_lb + al(S), o_mb = o_cl + al((size_t)S * 4), o_sb = o_mb + al((size_t)256 * Sw * 4),
-                 o_pa = o_sb + al((size_t)Sw * 4), o_sv = o_pa + al((nr + 1) * 4), o_wc = o_sv + al((size_t)S * 4), o_pp = o_wc + al((size_t)S * 4),
-                 o_po = o_pp + al(std::max<size_t>(pairs.size(), 1) * sizeof(RunPair)), total = o_po + al(((size_t)H + 1) * 4);
-    if (I->mem_bytes < total) {
-        if (I->d_mem) { STOCS_HIP_CHECK(hipStreamSynchronize(c->stream)); (void)hipFree(I->d_mem); I->d_mem = NULL; I->mem_bytes = 0; }
-        STOCS_HIP_CHECK(dev_malloc((void**)&I->d_mem, total + total / 4));
-        I->mem_bytes = total + total / 4;
-    }
-    char* m = I->d_mem;
+    const size_t o_rs = 0, o_re = o_rs + al256(nr * 2), o_ro = o_re + al256(nr * 2), o_pr = o_ro + al256(((size_t)H + 1) * 4), o_ep = o_pr + al256((size_t)S * 4),
+                 o_pi = o_ep + al256(S), o_lb = o_pi + al256(S), o_cl = o_lb + al256(S), o_mb = o_cl + al256((size_t)S * 4), o_sb = o_mb + al256((size_t)256 * Sw * 4),
+                 o_pa = o_sb + al256((size_t)Sw * 4), o_sv = o_pa + al256((nr + 1) * 4), o_wc = o_sv + al256((size_t)S * 4), o_pp = o_wc + al256((size_t)S * 4),
+                 o_po = o_pp + al256(std::max<size_t>(pairs.size(), 1) * sizeof(RunPair)), total = o_po + al256(((size_t)H + 1) * 4);
+    { const int rc = I->mem.grow(c->stream, total); if (rc) return rc; }
+    char* m = I->mem.p;
     I->d_run_s = (uint16_t*)(m + o_rs); I->d_run_e = (uint16_t*)(m + o_re); I->d_row_off = (uint32_t*)(m + o_ro); I->d_pt_run = (int32_t*)(m + o_pr);
     I->d_edge_pt = (uint8_t*)(m + o_ep); I->d_prev_in = (uint8_t*)(m + o_pi); I->d_label = (uint8_t*)(m + o_lb); I->d_cls = (float*)(m + o_cl);
     I->d_maskbits = (uint32_t*)(m + o_mb); I->d_segbits = (uint32_t*)(m + o_sb); I->d_parent = (uint32_t*)(m + o_pa);
@@ -1671,13 +1660,12 @@ static int sample_instance(stocs_ctx* c, uint64_t seed, int first_attempt, int n
     A.n_trials = 0; A.trial_stride = 0; A.seeds = NULL;
     // hand-over slots of the attempts: header, S (index, weight) pairs, flag; one error word
     {
-        auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
         const size_t nq = (size_t)std::max(nB, 1), Sq = (size_t)c->nS;
-        const size_t o_hdr = 0, o_flag = o_hdr + al(nq * 16), o_err = o_flag + al(nq * 4), o_sv = o_err + 256, o_w = o_sv + al(nq * Sq * 4), total = o_w + al(nq * Sq * 4);
+        const size_t o_hdr = 0, o_flag = o_hdr + al256(nq * 16), o_err = o_flag + al256(nq * 4), o_sv = o_err + 256, o_w = o_sv + al256(nq * Sq * 4), total = o_w + al256(nq * Sq * 4);
         if (I->queue_bytes < total) {
             if (I->d_queue) { STOCS_HIP_CHECK(hipStreamSynchronize(c->stream)); (void)hipFree(I->d_queue); I->d_queue = NULL; I->queue_bytes = 0; }
             // sized for a whole trial of this scene at once (<= 254 attempts), so that a caller asking attempt by attempt allocates once
-            const size_t full = o_w - o_sv > 0 ? 256 + al(254 * 16) + al(254 * 4) + 2 * al((size_t)254 * Sq * 4) : total;
+            const size_t full = o_w - o_sv > 0 ? 256 + al256(254 * 16) + al256(254 * 4) + 2 * al256((size_t)254 * Sq * 4) : total;
             const size_t want = std::max(total, std::min<size_t>(full, (size_t)1 << 30));
             STOCS_HIP_CHECK(dev_malloc((void**)&I->d_queue, want));
             I->queue_bytes = want;
@@ -1689,7 +1677,7 @@ static int sample_instance(stocs_ctx* c, uint64_t seed, int first_attempt, int n
     if ((rc = launch_instance_attempts(c, A, 2, seed, first_attempt, nB, dispersion))) return rc;
     I->h_segbits.assign((size_t)I->Sw, 0);
     // everything that comes back lands in the context's pinned block first (results | decayed prior | segment bits | error word)
-    const size_t rb_res = ((size_t)nB * sizeof(BaseOut) + 255) & ~(size_t)255, rb_cls = ((size_t)c->nS * 4 + 255) & ~(size_t)255, rb_seg = ((size_t)I->Sw * 4 + 255) & ~(size_t)255;
+    const size_t rb_res = al256((size_t)nB * sizeof(BaseOut)), rb_cls = al256((size_t)c->nS * 4), rb_seg = al256((size_t)I->Sw * 4);
     { const int rcp = ensure_pinned(c, (size_t)PIN_VAR + rb_res + rb_cls + rb_seg + 256); if (rcp) return rcp; }
     char* rbp = (char*)c->h_pin + PIN_VAR;
     unsigned int* q_err_pin = (unsigned int*)(rbp + rb_res + rb_cls + rb_seg);
@@ -1740,13 +1728,12 @@ __global__ __launch_bounds__(256) void init_trial_state_kernel(char* __restrict_
 int sample_trials(stocs_ctx* c, int mode, int nT, const uint64_t* seeds, int nA, float dispersion, BaseOut* res_host, const float4** snrmw0, size_t* snrmw_stride) {
     *snrmw0 = NULL; *snrmw_stride = 0;
     const size_t S = (size_t)c->nS, nW = (size_t)nT * (size_t)nA;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     if (mode == 0) {
         const ClassForm form = choose_class_form(c, true);
         const bool lean = form.kernel == CLASS_LEAN, wlds = form.kernel != CLASS_FULL_DEVICE_MEMORY;
         // scenes beyond the LDS working set keep 8 bytes per (attempt, point) in device memory: at most ~1 GB of it per launch
         const size_t per_launch = wlds ? nW : std::max<size_t>(1, std::min<size_t>(nW, ((size_t)1 << 30) / (S * 8)));
-        const size_t b_res = al(nW * sizeof(BaseOut)), b_seed = al((size_t)nT * 8), b_w = wlds ? 0 : al(per_launch * S * 4), b_slots = al(nW * 4);
+        const size_t b_res = al256(nW * sizeof(BaseOut)), b_seed = al256((size_t)nT * 8), b_w = wlds ? 0 : al256(per_launch * S * 4), b_slots = al256(nW * 4);
         int rc = ensure_scratch(c, b_res + b_seed + 2 * b_w + b_slots);
         if (rc) return rc;
         if ((rc = ensure_pinned(c, (size_t)PIN_VAR + b_seed + b_res))) return rc;     // seeds up, every attempt's result down
@@ -1778,18 +1765,14 @@ int sample_trials(stocs_ctx* c, int mode, int nT, const uint64_t* seeds, int nA,
     InstanceState* I = (InstanceState*)c->inst;
     const size_t Sw = (size_t)I->Sw, nr = std::max<size_t>(I->n_runs, 1), nq = (size_t)std::max(nA, 1);
     // one trial's block: what has to start from zero comes first (one fill), then everything that is written before it is read
-    const size_t o_pi = 0, o_lb = o_pi + al(S), o_mb = o_lb + al(S), o_sb = o_mb + al(256 * Sw * 4), o_fl = o_sb + al(Sw * 4), o_er = o_fl + al(nq * 4), zero_end = o_er + 256,
-                 o_cl = zero_end, o_pa = o_cl + al(S * 4), o_w = o_pa + al((nr + 1) * 4), o_sv = o_w + al(S * 4), o_sn = o_sv + al(S * 4), o_rs = o_sn + al(S * 16),
-                 o_hd = o_rs + al(nq * sizeof(BaseOut)), o_qs = o_hd + al(nq * 16), o_qw = o_qs + al(nq * S * 4), stride = o_qw + al(nq * S * 4);
-    const size_t b_seed = al((size_t)nT * 8), total = b_seed + (size_t)nT * stride;
-    if (I->trials_bytes < total) {
-        if (I->d_trials) { STOCS_HIP_CHECK(hipStreamSynchronize(c->stream)); (void)hipFree(I->d_trials); I->d_trials = NULL; I->trials_bytes = 0; }
-        STOCS_HIP_CHECK(dev_malloc((void**)&I->d_trials, total + total / 8));
-        I->trials_bytes = total + total / 8;
-    }
+    const size_t o_pi = 0, o_lb = o_pi + al256(S), o_mb = o_lb + al256(S), o_sb = o_mb + al256(256 * Sw * 4), o_fl = o_sb + al256(Sw * 4), o_er = o_fl + al256(nq * 4), zero_end = o_er + 256,
+                 o_cl = zero_end, o_pa = o_cl + al256(S * 4), o_w = o_pa + al256((nr + 1) * 4), o_sv = o_w + al256(S * 4), o_sn = o_sv + al256(S * 4), o_rs = o_sn + al256(S * 16),
+                 o_hd = o_rs + al256(nq * sizeof(BaseOut)), o_qs = o_hd + al256(nq * 16), o_qw = o_qs + al256(nq * S * 4), stride = o_qw + al256(nq * S * 4);
+    const size_t b_seed = al256((size_t)nT * 8), total = b_seed + (size_t)nT * stride;
+    if ((rc = I->trials.grow(c->stream, total, 8))) return rc;
     if ((rc = ensure_pinned(c, (size_t)PIN_VAR + b_seed))) return rc;
-    uint64_t* d_seeds = (uint64_t*)I->d_trials;
-    char* blk = I->d_trials + b_seed;
+    uint64_t* d_seeds = (uint64_t*)I->trials.p;
+    char* blk = I->trials.p + b_seed;
     memcpy((char*)c->h_pin + PIN_VAR, seeds, (size_t)nT * 8);
     STOCS_HIP_CHECK(hipMemcpyAsync(d_seeds, (char*)c->h_pin + PIN_VAR, (size_t)nT * 8, hipMemcpyHostToDevice, c->stream));
     {
@@ -1990,11 +1973,10 @@ int stocs_weight_fix_check(stocs_ctx* c, int64_t* n_mismatch) {
 int stocs_draw(stocs_ctx* c, const float* w, int n, uint64_t r64, int* index) {
     if (!c || !w || n <= 0 || !index) return STOCS_ERR_INVALID;
     DeviceGuard dev_guard(c->device);
-    auto al = [](size_t x) { return (x + 255) / 256 * 256; };
-    int rc = ensure_scratch(c, al((size_t)n * 4) + 1024);
+    int rc = ensure_scratch(c, al256((size_t)n * 4) + 1024);
     if (rc) return rc;
     char* p = (char*)c->d_scratch;
-    float* dw = (float*)p; p += al((size_t)n * 4);
+    float* dw = (float*)p; p += al256((size_t)n * 4);
     int32_t* bidx = (int32_t*)p; p += 256;
     int32_t* fail = (int32_t*)p; p += 256;
     uint64_t* rexp = (uint64_t*)p;

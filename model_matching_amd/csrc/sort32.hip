@@ -420,9 +420,8 @@ hipError_t sort_pairs_own(void* tmp, size_t& bytes, const uint32_t* kin, uint32_
     const size_t tile = (size_t)64 * nw * kpt;
     // (only segments beyond SMALL_CAP pairs are cut into tiles: at most n / SMALL_CAP of them)
     const size_t max_tiles = n / tile + std::min<size_t>((size_t)n_seg, n / SMALL_CAP + 1) + 1;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t ctl_b = al(sizeof(SortCtl)), hist_b = al((size_t)P.n_pass * n_seg * 256 * 4), tf_b = al(((size_t)n_seg + 1) * 4), ts_b = al(max_tiles * 4),
-                 lb_b = al(max_tiles * 256 * 4), buf_b = al(n * 4);
+    const size_t ctl_b = al256(sizeof(SortCtl)), hist_b = al256((size_t)P.n_pass * n_seg * 256 * 4), tf_b = al256(((size_t)n_seg + 1) * 4), ts_b = al256(max_tiles * 4),
+                 lb_b = al256(max_tiles * 256 * 4), buf_b = al256(n * 4);
     const size_t need = ctl_b + hist_b + 2 * tf_b + ts_b + 2 * lb_b + (P.n_pass > 1 ? 2 * buf_b : 0);
     if (!tmp) { bytes = need; return hipSuccess; }
     if (bytes < need || n >= ((size_t)1 << 30) || b1 > 32 || b1 <= b0 || P.n_pass > SORT_MAX_PASS || n_seg >= (1u << 24)) return hipErrorInvalidValue;

@@ -76,6 +76,33 @@ struct DeviceGuard {
     DeviceGuard& operator=(const DeviceGuard&) = delete;
 };
 
+// every carved region of a device or pinned block starts on a 256-byte boundary
+inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
+
+// Grow-only device block of one owner: grow() leaves it alone when it holds `need` bytes, else waits for the stream (nothing may
+// still use the old block), frees it and takes need + need / slack_div.  A caller that has to know whether the block is a new one
+// compares `bytes` before and after.
+struct DevBlock {
+    char* p = NULL; size_t bytes = 0;
+    int grow(hipStream_t st, size_t need, size_t slack_div = 4) {
+        if (bytes >= need) return STOCS_OK;
+        if (p) { STOCS_HIP_CHECK(hipStreamSynchronize(st)); (void)hipFree(p); p = NULL; bytes = 0; }
+        const size_t want = need + need / slack_div;
+        STOCS_HIP_CHECK(dev_malloc(&p, want));
+        bytes = want;
+        return STOCS_OK;
+    }
+    void free() { if (p) (void)hipFree(p); p = NULL; bytes = 0; }
+};
+
+// Lays regions out one behind the other, each on a 256-byte boundary: take() gives a region's offset, `total` what the block must
+// hold.  Offsets, not pointers: the same layout serves a device block and its mirror in the pinned block (at() on either base).
+struct Carve {
+    size_t total = 0;
+    size_t take(size_t bytes) { const size_t at = total; total += al256(bytes); return at; }
+    template <class T> static T* at(void* base, size_t off) { return (T*)((char*)base + off); }
+};
+
 // Grow-only device workspace: slabs of plain hipMalloc memory handed out by bumping an offset.  reset() recycles
 // everything (nothing of it may still be in flight); a slab that turned out too small is joined by a bigger one
 // and the slabs are merged at the next reset, so a steady-state caller never calls hipMalloc / hipFree.
@@ -112,7 +139,7 @@ struct Arena {
         return STOCS_OK;
     }
     int take(size_t bytes, void** out) {
-        bytes = (std::max<size_t>(bytes, 1) + 255) & ~(size_t)255;
+        bytes = al256(std::max<size_t>(bytes, 1));
         for (size_t i = 0; i < slabs.size(); ++i)
             if (slabs[i].cap - slabs[i].used >= bytes) { *out = slabs[i].p + slabs[i].used; slabs[i].used += bytes; return STOCS_OK; }
         Slab sl = {NULL, std::max<size_t>(bytes + bytes / 4, slabs.empty() ? ((size_t)64 << 20) : 2 * slabs.back().cap), 0};
@@ -254,22 +281,21 @@ struct stocs_ctx {
     int lcp_split;     // 1: four wavefronts share one candidate (default), 0: one wavefront per candidate
     int lcp_flat;      // 1: build and use the flat cell table when it fits (default), 0: brick look-ups only
     int lcp_order;     // 0: candidates in batch order; 1: spatially ordered processing of big batches; 2: + XCD-contiguous blocks
-    void* d_order;     // keys / permutation / sort scratch of the ordering
-    size_t order_bytes;
+    stocs::DevBlock order;   // keys / permutation / sort scratch of the ordering
     // "exact_ties" (stocs_set_option): tied nearest-neighbour queries answered by the reference-order kd-tree (kdtree.h).  The tree
     // of the current scene is built at the first exact-mode scoring call after a scene change (at stocs_ctx_set_scene when the
     // option is already on) and lives in one grow-only device block: tie counters (flagged, changed) | nodes | points in tree order
     int exact_ties;
     bool kd_ready;                 // kd_host / d_kd hold the tree of the current scene
     stocs::KdTreeHost kd_host;
-    char* d_kd; size_t kd_bytes;
+    stocs::DevBlock kd;
     const stocs::KdNodeP* d_kd_nodes;
     const float4* d_kd_pts;
     unsigned long long* d_ties;    // [0] tied queries seen, [1] those whose reference answer differs from the largest-index rule
     bool ties_started;             // the current entry point has zeroed the counters (stocs_last_tie_counts reads 0 / 0 otherwise)
     // class-mode sampling, lean kernel (sample.hip): exclusive prefix sums of the prior's 2^32 fixed-point weights in scene order (S + 1
     // entries), recomputed when the class probabilities on the device have changed (prior_epoch) or the scene has (cdf_n)
-    void* d_cdf; size_t cdf_bytes, cdf_n; unsigned long long prior_epoch, cdf_epoch;
+    stocs::DevBlock cdf; size_t cdf_n; unsigned long long prior_epoch, cdf_epoch;
     stocs::PpfIndex index;
 
     // image-space state of instance mode (stocs.hpp:153-155)

@@ -68,6 +68,49 @@ STOCS_HD V3 xform_normal(const float* T, V3 n) {
                T[2] * n.x + (T[6] * n.y + T[10] * n.z));
 }
 
+// Centred frames <-> camera frame (stocs.cpp:925-937 without the triangle centroids, which rigid_transform_one folds in itself):
+// a pose T scored between the centred clouds is the camera pose P with the same rotation and tc = (t + cscene) - R cmodel, R cmodel
+// in the 3-term order.  The inverse is t = (tc - cscene) + R cmodel.  Row 3 comes out as (0, 0, 0, 1) either way.
+STOCS_HD void camera_from_centred(const float* T, V3 cscene, V3 cmodel, float* P) {
+    const V3 t = mk3(T[12], T[13], T[14]);
+    const V3 Rcm = xform_normal(T, cmodel);
+    const V3 tc = (t + cscene) - Rcm;
+    for (int c = 0; c < 3; ++c) { for (int r = 0; r < 3; ++r) P[c * 4 + r] = T[c * 4 + r]; P[c * 4 + 3] = 0.0f; }
+    P[12] = tc.x; P[13] = tc.y; P[14] = tc.z; P[15] = 1.0f;
+}
+STOCS_HD void centred_from_camera(const float* P, V3 cscene, V3 cmodel, float* T) {
+    const V3 Rcm = xform_normal(P, cmodel);
+    for (int c = 0; c < 3; ++c) { for (int r = 0; r < 3; ++r) T[c * 4 + r] = P[c * 4 + r]; T[c * 4 + 3] = 0.0f; }
+    T[12] = (P[12] - cscene.x) + Rcm.x; T[13] = (P[13] - cscene.y) + Rcm.y; T[14] = (P[14] - cscene.z) + Rcm.z; T[15] = 1.0f;
+}
+
+// The "first maximum" of compute_best_transform (stocs.cpp:982-1004) as an integer maximum: key = (score bits << 32) | ~index.
+// Scores are never negative, so their bits order as the floats do: the larger score wins, and among equal scores the LOWER index
+// (its complement is larger).  Key 0 means "none".  A caller that follows the reference's strict > from 0 (a score that is not
+// positive never wins, all-zero => no pose) forms keys only for scores > 0; tracking forms them for every slot, so that slot 0 --
+// the incumbent -- wins when all scores are 0.  An integer maximum is independent of the order it is taken in.
+STOCS_HD unsigned long long best_key(float score, uint32_t index) {
+    union { float f; uint32_t u; } cv; cv.f = score; return ((unsigned long long)cv.u << 32) | (unsigned long long)(0xFFFFFFFFu - index);
+}
+STOCS_HD uint32_t best_key_index(unsigned long long key) { return 0xFFFFFFFFu - (uint32_t)(key & 0xFFFFFFFFull); }
+STOCS_HD float best_key_score(unsigned long long key) { union { float f; uint32_t u; } cv; cv.u = (uint32_t)(key >> 32); return cv.f; }
+#if defined(__HIPCC__)
+// the maximum of a wavefront's keys, in every lane
+__device__ __forceinline__ unsigned long long wave_max_key(unsigned long long k) {
+    for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(k, off, 64); k = o > k ? o : k; }
+    return k;
+}
+// the maximum of a workgroup of WAVES wavefronts, in every thread; sh: WAVES words of LDS, free again after the caller's next barrier
+template <int WAVES>
+__device__ __forceinline__ unsigned long long wg_max_key(unsigned long long k, unsigned long long* sh) {
+    k = wave_max_key(k);
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = k;
+    __syncthreads();
+    for (int w = 0; w < WAVES; ++w) k = sh[w] > k ? sh[w] : k;
+    return k;
+}
+#endif
+
 // ---------------------------------------------------------------------------------------------
 // deterministic double atan2 for y >= 0 or any sign; basic IEEE operations only.
 // atan(r), r in [0,1]:  c = k/8 (k = round(8r)), t = (r - c)/(1 + r c), atan r = atan c + atan t,

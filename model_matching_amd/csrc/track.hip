@@ -24,13 +24,11 @@
 namespace stocs {
 
 struct TrackState {
-    char* d_mem; size_t bytes;   // incumbents | incumbent lcp | prior lcp | results | candidates | scores (grow-only)
+    DevBlock mem;   // incumbents | incumbent lcp | prior lcp | results | candidates | scores (grow-only)
     bool kept;                   // the last call kept its details (hT / hL below)
     int n, samples, rounds;
     std::vector<float> hT, hL;   // round-major: round r, prior p, slot j at (r * n + p) * samples + j
 };
-
-static inline size_t al256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // round r's candidates: thread i = p * S + j.  Slot 0 copies the incumbent; slot j >= 1 perturbs it about the model origin with the
 // draws and the float order of the header (every operation a single IEEE add / sub / mul / div / sqrt, -ffp-contract=off)
@@ -71,8 +69,8 @@ __global__ __launch_bounds__(256) void track_perturb_kernel(const float* __restr
     o[12] = T[12] + dtx; o[13] = T[13] + dty; o[14] = T[14] + dtz; o[15] = 1.0f;
 }
 
-// one workgroup per prior: the first maximum of its S scores, key (lcp bits << 32) | ~slot (scores are never negative, so their bits
-// order as the floats do; slot 0 wins every tie, also when all scores are 0).  Writes the next incumbent and its score; round 0 also
+// one workgroup per prior: the first maximum of its S scores by best_key (stocs_math.h), a key for EVERY slot whatever its score:
+// slot 0 wins every tie, also when all scores are 0.  Writes the next incumbent and its score; round 0 also
 // records the prior's own score (slot 0)
 __global__ __launch_bounds__(256) void track_best_kernel(const float* __restrict__ cand, const float* __restrict__ lcp, int S, int r, float* __restrict__ inc,
                                                          float* __restrict__ inc_lcp, float* __restrict__ prior_lcp) {
@@ -81,22 +79,19 @@ __global__ __launch_bounds__(256) void track_best_kernel(const float* __restrict
     const size_t base = (size_t)p * S;
     unsigned long long k = 0;
     for (int j = (int)threadIdx.x; j < S; j += 256) {
-        const unsigned long long key = ((unsigned long long)__float_as_uint(lcp[base + j]) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)j);
+        const unsigned long long key = best_key(lcp[base + j], (uint32_t)j);
         k = key > k ? key : k;
     }
-    for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(k, off, 64); k = o > k ? o : k; }
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = k;
-    __syncthreads();
-    for (int w = 0; w < 4; ++w) k = sh[w] > k ? sh[w] : k;
-    const uint32_t j = 0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFull);   // < S: every key above 0 came from a slot of this prior
+    k = wg_max_key<4>(k, sh);
+    const uint32_t j = best_key_index(k);   // < S: every key above 0 came from a slot of this prior
     if (threadIdx.x < 16) inc[(size_t)p * 16 + threadIdx.x] = cand[(base + j) * 16 + threadIdx.x];
     if (threadIdx.x == 0) {
-        inc_lcp[p] = __uint_as_float((uint32_t)(k >> 32));
+        inc_lcp[p] = best_key_score(k);
         if (r == 0) prior_lcp[p] = lcp[base];
     }
 }
 
-// the result records: the incumbent's camera form with the arithmetic of refine_final_kernel (tc = (t + cscene) - R cmodel) and, with
+// the result records: the incumbent's camera form (camera_from_centred, as refine_final_kernel) and, with
 // refinement (Pr != NULL), refine.hip's outputs
 __global__ __launch_bounds__(64) void track_result_kernel(const float* __restrict__ inc, const float* __restrict__ inc_lcp, const float* __restrict__ prior_lcp, int n,
                                                           V3 cscene, V3 cmodel, const float* __restrict__ Pr, const float* __restrict__ lr,
@@ -105,13 +100,8 @@ __global__ __launch_bounds__(64) void track_result_kernel(const float* __restric
     if (k >= n) return;
     const float* To = inc + (size_t)k * 16;
     stocs_track_result* R = res + k;
-    const V3 t = mk3(To[12], To[13], To[14]);
-    const V3 cm = cmodel;
-    const V3 Rcm = mk3(To[0] * cm.x + (To[4] * cm.y + To[8] * cm.z), To[1] * cm.x + (To[5] * cm.y + To[9] * cm.z), To[2] * cm.x + (To[6] * cm.y + To[10] * cm.z));
-    const V3 tc = (t + cscene) - Rcm;
     float P[16];
-    for (int c = 0; c < 3; ++c) { for (int r = 0; r < 3; ++r) P[c * 4 + r] = To[c * 4 + r]; P[c * 4 + 3] = 0.0f; }
-    P[12] = tc.x; P[13] = tc.y; P[14] = tc.z; P[15] = 1.0f;
+    camera_from_centred(To, cscene, cmodel, P);
     R->prior_lcp = prior_lcp[k];
     R->lcp = inc_lcp[k];
     for (int i = 0; i < 16; ++i) R->pose16[i] = P[i];
@@ -161,7 +151,7 @@ using namespace stocs;
 extern "C" void stocs_internal_free_track(stocs_ctx* c) {
     if (!c || !c->track) return;
     TrackState* S = (TrackState*)c->track;
-    if (S->d_mem) (void)hipFree(S->d_mem);
+    S->mem.free();
     delete S;
     c->track = NULL;
 }
@@ -187,7 +177,7 @@ extern "C" int stocs_track_poses(stocs_ctx* c, const float* priors, int n, const
     begin_scoring_call(c);
     if (!c->track) {
         TrackState* T = new TrackState();
-        T->d_mem = NULL; T->bytes = 0; T->kept = false; T->n = T->samples = T->rounds = 0;
+        T->kept = false; T->n = T->samples = T->rounds = 0;
         c->track = T;
     }
     TrackState* st = (TrackState*)c->track;
@@ -202,41 +192,27 @@ extern "C" int stocs_track_poses(stocs_ctx* c, const float* priors, int n, const
         const int rc = refine_prepare(c, n, c->nS, prm->max_correspondence_distance, &w);
         if (rc) return rc;
     }
-    const size_t ib = al256((size_t)n * 64), lb = al256((size_t)n * 4), rb = al256((size_t)n * sizeof(stocs_track_result));
-    const size_t cb = al256((size_t)kr * nc * 64), sb = al256((size_t)kr * nc * 4);
-    const size_t need = ib + 2 * lb + rb + cb + sb;
-    if (st->bytes < need) {
-        if (st->d_mem) { STOCS_HIP_CHECK(hipStreamSynchronize(c->stream)); (void)hipFree(st->d_mem); st->d_mem = NULL; st->bytes = 0; }
-        STOCS_HIP_CHECK(dev_malloc(&st->d_mem, need + need / 4));
-        st->bytes = need + need / 4;
-    }
-    char* q = st->d_mem;
-    float* d_inc = (float*)q; q += ib;
-    float* d_inc_lcp = (float*)q; q += lb;
-    float* d_prior_lcp = (float*)q; q += lb;
-    stocs_track_result* d_res = (stocs_track_result*)q; q += rb;
-    float* d_cand = (float*)q; q += cb;
-    float* d_lcp = (float*)q;
-    // the read-back: the results, then (details) every round's candidates and scores -- one contiguous block
-    const size_t back = keep ? rb + cb + (size_t)kr * nc * 4 : (size_t)n * sizeof(stocs_track_result);
+    Carve cv;
+    const size_t o_inc = cv.take((size_t)n * 64), o_inc_lcp = cv.take((size_t)n * 4), o_prior_lcp = cv.take((size_t)n * 4),
+                 o_res = cv.take((size_t)n * sizeof(stocs_track_result)), o_cand = cv.take((size_t)kr * nc * 64), o_lcp = cv.take((size_t)kr * nc * 4);
+    { const int rc = st->mem.grow(c->stream, cv.total); if (rc) return rc; }
+    float* d_inc = Carve::at<float>(st->mem.p, o_inc); float* d_inc_lcp = Carve::at<float>(st->mem.p, o_inc_lcp); float* d_prior_lcp = Carve::at<float>(st->mem.p, o_prior_lcp);
+    stocs_track_result* d_res = Carve::at<stocs_track_result>(st->mem.p, o_res); float* d_cand = Carve::at<float>(st->mem.p, o_cand); float* d_lcp = Carve::at<float>(st->mem.p, o_lcp);
+    // the read-back: the results, then (details) every round's candidates and scores -- one contiguous block, laid out as on the device
+    const size_t back_cand = o_cand - o_res, back_lcp = o_lcp - o_res;
+    const size_t back = keep ? back_lcp + (size_t)kr * nc * 4 : (size_t)n * sizeof(stocs_track_result);
+    const size_t ib = o_inc_lcp - o_inc;   // the priors go up through the front of the pinned part
     const size_t pin_need = (size_t)PIN_VAR + ib + al256(back);
     if (c->pin_bytes < pin_need) {
         STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));   // nothing may still be copying into the old block
         const int rc = ensure_pinned(c, pin_need);
         if (rc) return rc;
     }
-    // camera -> centred on the host, in float: R kept, t = (tc - cs) + R cm with R cm in the 3-term order of stocs_math.h
+    // camera -> centred on the host, in float (centred_from_camera: the arithmetic the device would do)
     float* hin = (float*)((char*)c->h_pin + PIN_VAR);
     char* hout = (char*)c->h_pin + PIN_VAR + ib;
     const V3 cs = c->centroid_scene, cm = c->centroid_model;
-    for (int k = 0; k < n; ++k) {
-        const float* P = priors + (size_t)k * 16;
-        float* T = hin + (size_t)k * 16;
-        for (int i = 0; i < 16; ++i) T[i] = P[i];
-        const V3 Rcm = mk3(P[0] * cm.x + (P[4] * cm.y + P[8] * cm.z), P[1] * cm.x + (P[5] * cm.y + P[9] * cm.z), P[2] * cm.x + (P[6] * cm.y + P[10] * cm.z));
-        T[12] = (P[12] - cs.x) + Rcm.x; T[13] = (P[13] - cs.y) + Rcm.y; T[14] = (P[14] - cs.z) + Rcm.z;
-        T[3] = 0.0f; T[7] = 0.0f; T[11] = 0.0f; T[15] = 1.0f;
-    }
+    for (int k = 0; k < n; ++k) centred_from_camera(priors + (size_t)k * 16, cs, cm, hin + (size_t)k * 16);
     STOCS_HIP_CHECK(hipMemcpyAsync(d_inc, hin, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));
     const unsigned pblocks = (unsigned)((nc + 255) / 256);
     double b = 1.0;   // shrink^r
@@ -269,8 +245,8 @@ extern "C" int stocs_track_poses(stocs_ctx* c, const float* priors, int n, const
     memcpy(out, hout, (size_t)n * sizeof(stocs_track_result));
     st->n = n; st->samples = S; st->rounds = R;
     if (keep) {
-        st->hT.assign((const float*)(hout + rb), (const float*)(hout + rb) + (size_t)R * nc * 16);
-        st->hL.assign((const float*)(hout + rb + cb), (const float*)(hout + rb + cb) + (size_t)R * nc);
+        st->hT.assign((const float*)(hout + back_cand), (const float*)(hout + back_cand) + (size_t)R * nc * 16);
+        st->hL.assign((const float*)(hout + back_lcp), (const float*)(hout + back_lcp) + (size_t)R * nc);
         st->kept = true;
     } else {
         st->hT.clear(); st->hL.clear();

@@ -128,7 +128,7 @@ __global__ __launch_bounds__(64) void winner_pose_kernel(const unsigned long lon
     const unsigned long long k = *key;
     if (threadIdx.x == 0) { out18[0] = __uint_as_float((uint32_t)(k & 0xFFFFFFFFull)); out18[1] = __uint_as_float((uint32_t)(k >> 32)); }
     if (threadIdx.x < 16) {
-        const uint32_t id = 0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFull);
+        const uint32_t id = 0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFull);   // best_key_index(k), written out: the helper changes this kernel's code
         out18[2 + threadIdx.x] = (k && id < (uint32_t)n) ? P[(size_t)id * 16 + threadIdx.x] : 0.0f;
     }
 }
@@ -267,7 +267,7 @@ int stocs_make_transforms(stocs_ctx* c, int max_per_base, uint64_t seed, int* n_
     // a batch of trials (stocs_run_trials): every base draws with the seed of its trial and under its slot there
     const bool batch = !c->base_seed.empty();
     if (batch && (c->base_seed.size() != c->bases.size() || c->base_local.size() != c->bases.size())) { set_error("internal: trial tables do not match the base set"); return STOCS_ERR_STATE; }
-    const size_t nbases = c->bases.size(), tab_bytes = (16 * nbases + 255) & ~(size_t)255;
+    const size_t nbases = c->bases.size(), tab_bytes = al256(16 * nbases);
     const size_t n_tr = batch ? c->trial_first_base.size() : 0;     // trials + 1
     std::vector<size_t> first_job(nbases + 1, 0);
     size_t n_dev = 0;
@@ -332,12 +332,12 @@ int stocs_make_transforms(stocs_ctx* c, int max_per_base, uint64_t seed, int* n_
     c->best_lcp = 0; c->best_index = -1;
     if (n) {
         // candidates stay on the device: jobs -> transforms -> order-preserving compaction of the accepted ones
-        const size_t jb = ((n * sizeof(XformJob) + 255) / 256) * 256, tb = n * 64, ob = (((n + 1) * 4 + 255) / 256) * 256;
+        const size_t jb = al256(n * sizeof(XformJob)), tb = n * 64, ob = al256((n + 1) * 4);
         size_t scan_tmp = 0;
         STOCS_HIP_CHECK(exclusive_scan(NULL, scan_tmp, (const uint32_t*)NULL, (uint32_t*)NULL, n + 1, c->stream));
-        scan_tmp = ((scan_tmp + 255) / 256) * 256;
-        const size_t pb = device_picks ? ((n * 16 + 255) / 256) * 256 + 2 * tab_bytes : 0;   // picks + the two tables
-        const size_t trb = batch ? ((8 * n_tr + 255) / 256) * 256 : 0;                        // first jobs of the trials + their candidate offsets
+        scan_tmp = al256(scan_tmp);
+        const size_t pb = device_picks ? al256(n * 16) + 2 * tab_bytes : 0;   // picks + the two tables
+        const size_t trb = batch ? al256(8 * n_tr) : 0;                        // first jobs of the trials + their candidate offsets
         int rc = ensure_scratch(c, jb + 2 * tb + 3 * ob + scan_tmp + pb + trb);
         if (rc) return rc;
         if (!device_picks && (rc = ensure_pinned(c, (size_t)PIN_VAR + 2 * tab_bytes + 4 * n_tr + 256))) return rc;
@@ -361,7 +361,7 @@ int stocs_make_transforms(stocs_ctx* c, int max_per_base, uint64_t seed, int* n_
         const int32_t* d_picks = NULL;
         if (device_picks) {
             char* pk = base + jb + 2 * tb + 3 * ob + scan_tmp;
-            uint4* d_table = (uint4*)(pk + ((n * 16 + 255) / 256) * 256);
+            uint4* d_table = (uint4*)(pk + al256(n * 16));
             d_picks = (const int32_t*)pk;
             const size_t lds = (size_t)(2 * (hmask + 1) + ((max_per_base + 1) & ~1)) * 4 + (size_t)max_per_base * 8;
             // The table goes up on the MAIN stream: a host-to-device copy of a few hundred kilobytes enqueued on the otherwise idle auxiliary

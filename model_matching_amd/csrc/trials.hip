@@ -42,9 +42,9 @@ struct TrialBatch {
     int pieces = 0;
 };
 
-// compute_best_transform (stocs.cpp:982-1004) of every trial of a piece: strict > from 0 -- the first maximum wins, a trial
-// whose scores are all 0 has no pose -- over the trial's own stretch of the score array, and the winner's camera-frame pose
-// next to it.  One workgroup per trial; out18[t] = (key lo, key hi, pose[16]) with the candidate index counted inside the trial.
+// compute_best_transform (stocs.cpp:982-1004) of every trial of a piece: the first maximum of the trial's positive scores (best_key,
+// stocs_math.h; a trial whose scores are all 0 has no pose) over the trial's own stretch of the score array, and the winner's
+// camera-frame pose next to it.  One workgroup per trial; out18[t] = (key lo, key hi, pose[16]) with the candidate index counted inside the trial.
 __global__ __launch_bounds__(256) void trial_best_kernel(const float* __restrict__ lcp, const float* __restrict__ P, const int32_t* __restrict__ cand_off,
                                                          float* __restrict__ out18) {
     __shared__ unsigned long long sh[4];
@@ -53,21 +53,12 @@ __global__ __launch_bounds__(256) void trial_best_kernel(const float* __restrict
     unsigned long long k = 0;
     for (int i = i0 + (int)threadIdx.x; i < i1; i += 256) {
         const float s = lcp[i];
-        if (s > 0.0f) {
-            const unsigned long long key = ((unsigned long long)__float_as_uint(s) << 32) | (unsigned long long)(0xFFFFFFFFu - (uint32_t)(i - i0));
-            k = key > k ? key : k;
-        }
+        if (s > 0.0f) { const unsigned long long key = best_key(s, (uint32_t)(i - i0)); k = key > k ? key : k; }
     }
-    for (int off = 32; off > 0; off >>= 1) { const unsigned long long o = __shfl_xor(k, off, 64); k = o > k ? o : k; }
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = k;
-    __syncthreads();
-    for (int w = 0; w < 4; ++w) k = sh[w] > k ? sh[w] : k;
+    k = wg_max_key<4>(k, sh);
     float* o = out18 + (size_t)t * 18;
     if (threadIdx.x == 0) { o[0] = __uint_as_float((uint32_t)(k & 0xFFFFFFFFull)); o[1] = __uint_as_float((uint32_t)(k >> 32)); }
-    if (threadIdx.x < 16) {
-        const uint32_t id = 0xFFFFFFFFu - (uint32_t)(k & 0xFFFFFFFFull);
-        o[2 + threadIdx.x] = k ? P[((size_t)i0 + id) * 16 + threadIdx.x] : 0.0f;
-    }
+    if (threadIdx.x < 16) o[2 + threadIdx.x] = k ? P[((size_t)i0 + best_key_index(k)) * 16 + threadIdx.x] : 0.0f;
 }
 
 // candidate -> trial of the piece (candidates come out trial by trial: a binary search in the per-trial offsets)
@@ -142,6 +133,205 @@ static int check_post(const stocs_trial_post* p) {
     return STOCS_OK;
 }
 
+// ---- how many bases one set of launches can take (congruent.hip: 32-bit (base, cell) sort keys with the run table, packed 64-bit
+//      quads with the base above the four model ids) ----
+static long long max_bases_per_piece(const stocs_ctx* c, int nA) {
+    long long max_bases = 1 << 20;
+    const float eps_unit = c->prm.distance_threshold / c->ratio;
+    const int gridDepth = (int)(-log2f(eps_unit));
+    const int egSize = (int)pow(2.0, (double)gridDepth);
+    const long long NC = (long long)egSize * egSize * egSize;
+    int id_bits = 1, cell_bits = 1;
+    while ((1 << id_bits) < c->nM) id_bits++;
+    if (NC > 0 && NC < (1ll << 31)) {
+        while (cell_bits < 40 && (((unsigned long long)1 << cell_bits) - 1ull) < (unsigned long long)NC) cell_bits++;
+        if (cell_bits < 32) max_bases = std::min(max_bases, 1ll << (32 - cell_bits));
+        max_bases = std::min(max_bases, std::max(1ll, (1ll << 27) / NC));
+    }
+    if (4 * id_bits < 64) max_bases = std::min(max_bases, 1ll << std::min(20, 64 - 4 * id_bits));
+    return std::max(max_bases, (long long)std::max(nA, 1));     // a single trial always goes through (as it does alone)
+}
+
+// the context's base set = the valid bases of trials t0 .. t1 one behind the other, each with its trial's seed and its slot there
+static void assemble_piece(stocs_ctx* c, const TrialBatch* B, int t0, int t1) {
+    c->bases.clear(); c->base_seed.clear(); c->base_local.clear(); c->trial_first_base.clear(); c->trial_cand_off.clear();
+    c->quad_off.clear(); clear_candidates(c);
+    for (int t = t0; t < t1; ++t) {
+        c->trial_first_base.push_back((int32_t)c->bases.size());
+        int slot = 0;
+        for (int a = 0; a < B->nA; ++a) {
+            const BaseOut& r = B->res[(size_t)t * B->nA + a];
+            if (!r.valid) continue;
+            BaseRec br; br.inv1 = r.inv[0]; br.inv2 = r.inv[1];
+            for (int k = 0; k < 4; ++k) br.ids[k] = r.ids[k];
+            c->bases.push_back(br);
+            c->base_seed.push_back(B->seeds[(size_t)t]);
+            c->base_local.push_back(slot++);
+        }
+    }
+    c->trial_first_base.push_back((int32_t)c->bases.size());
+}
+
+// One piece (trials first .. first + n_trials of the batch) between its transforms and its results.
+struct Piece {
+    int first = 0, n_trials = 0, n_cand = 0;
+    const stocs_trial_post* post = NULL;     // NULL: no post-processing
+    const float4* trial_weights = NULL;      // != NULL (instance mode): every candidate scores against the weights of its own trial (Q8)
+    int n_slots = 0; bool refine = false;    // post: hypothesis slots of the piece, per trial min(count + 1, its candidates); they are refined
+    std::vector<int32_t> hyp_off;            // post: first slot of every trial (+ 1)
+    std::vector<float> best18;               // per trial (key lo, key hi, pose[16]); all zero for a trial without a positive score
+    // The scratch of the scoring step (the transform jobs of the piece are done with the area), one layout for the device block and the
+    // pinned block: the regions up to hyp_off exist in both (h_* mirrors d_*), the rest on the device only.  best18 | hyp_count |
+    // hyp_records come back in ONE copy of back_bytes.
+    int32_t* d_cand_off; float* d_best18; int32_t* d_hyp_count; stocs_trial_hypothesis* d_hyp_records; int32_t* d_hyp_off;
+    int32_t* d_cand_trial; uint8_t* d_alive; int32_t* d_hyp_index; int32_t* d_slot_trial; int32_t* d_slot_live;
+    int32_t* h_cand_off; float* h_best18; int32_t* h_hyp_count; stocs_trial_hypothesis* h_hyp_records; int32_t* h_hyp_off; size_t back_bytes;
+};
+
+// sizes the hypothesis slots and lays the piece's scratch out (grows the context's scratch and pinned blocks when they are too small)
+static int plan_piece(stocs_ctx* c, Piece& pc) {
+    const size_t nT = (size_t)pc.n_trials, n_cand = (size_t)pc.n_cand; const bool post = pc.post != NULL;
+    pc.hyp_off.assign(post ? nT + 1 : 0, 0);
+    for (size_t t = 0; post && t < nT; ++t)   // (the counts come back with the read-back)
+        pc.hyp_off[t + 1] = pc.hyp_off[t] + (int32_t)std::min<long long>((long long)pc.post->maximum_pose_count + 1, (long long)(c->trial_cand_off[t + 1] - c->trial_cand_off[t]));
+    pc.n_slots = post ? pc.hyp_off[nT] : 0;
+    pc.refine = post && pc.post->refine_iterations > 0 && pc.n_slots > 0;
+    const size_t H = (size_t)pc.n_slots;
+    Carve cv;
+    const size_t cand_off = cv.take((nT + 1) * 4), best18 = cv.take(nT * 18 * 4), hyp_count = cv.take(post ? nT * 4 : 0),
+                 hyp_records = cv.take(post ? H * sizeof(stocs_trial_hypothesis) : 0), hyp_off = cv.take(post ? (nT + 1) * 4 : 0), mirrored = cv.total;
+    const size_t cand_trial = cv.take(pc.trial_weights ? n_cand * 4 : 0), alive = cv.take(post ? n_cand : 0), hyp_index = cv.take(post ? H * 4 : 0),
+                 slot_trial = cv.take(pc.refine ? H * 4 : 0), slot_live = cv.take(pc.refine ? H * 4 : 0);
+    if (int rc = ensure_scratch(c, cv.total + 256)) return rc;
+    if (int rc = ensure_pinned(c, (size_t)PIN_VAR + mirrored + 256)) return rc;
+    void* d = c->d_scratch; void* h = (char*)c->h_pin + PIN_VAR;
+    pc.d_cand_off = Carve::at<int32_t>(d, cand_off); pc.h_cand_off = Carve::at<int32_t>(h, cand_off); pc.d_best18 = Carve::at<float>(d, best18); pc.h_best18 = Carve::at<float>(h, best18);
+    pc.d_hyp_count = Carve::at<int32_t>(d, hyp_count); pc.h_hyp_count = Carve::at<int32_t>(h, hyp_count); pc.d_hyp_off = Carve::at<int32_t>(d, hyp_off); pc.h_hyp_off = Carve::at<int32_t>(h, hyp_off);
+    pc.d_hyp_records = Carve::at<stocs_trial_hypothesis>(d, hyp_records); pc.h_hyp_records = Carve::at<stocs_trial_hypothesis>(h, hyp_records);
+    pc.d_cand_trial = Carve::at<int32_t>(d, cand_trial); pc.d_alive = Carve::at<uint8_t>(d, alive); pc.d_hyp_index = Carve::at<int32_t>(d, hyp_index);
+    pc.d_slot_trial = Carve::at<int32_t>(d, slot_trial); pc.d_slot_live = Carve::at<int32_t>(d, slot_live);
+    pc.back_bytes = post ? (hyp_records - best18) + H * sizeof(stocs_trial_hypothesis) : nT * 18 * 4;
+    return STOCS_OK;
+}
+
+// While it lives, the context's scoring launches take candidate i's scene normals + weights from trial cand_trial[i]'s copy
+// (LcpArgs::cand_trial); nothing when the piece has no per-trial weights.
+struct TrialWeightsScope {
+    stocs_ctx* c;
+    TrialWeightsScope(stocs_ctx* ctx, const float4* weights, const int32_t* d_cand_trial) : c(ctx) { if (weights) { c->snrmw_override = weights; c->lcp_cand_trial = d_cand_trial; } }
+    ~TrialWeightsScope() { c->snrmw_override = NULL; c->lcp_cand_trial = NULL; }
+};
+
+// the offsets go up, every candidate of the piece is scored in ONE launch, then the arg-max of each trial
+static int score_piece(stocs_ctx* c, const Piece& pc) {
+    const size_t off_bytes = 4 * ((size_t)pc.n_trials + 1);
+    memcpy(pc.h_cand_off, c->trial_cand_off.data(), off_bytes);
+    STOCS_HIP_CHECK(hipMemcpyAsync(pc.d_cand_off, pc.h_cand_off, off_bytes, hipMemcpyHostToDevice, c->stream));
+    if (pc.post) {
+        memcpy(pc.h_hyp_off, pc.hyp_off.data(), off_bytes);
+        STOCS_HIP_CHECK(hipMemcpyAsync(pc.d_hyp_off, pc.h_hyp_off, off_bytes, hipMemcpyHostToDevice, c->stream));
+    }
+    if (pc.trial_weights) {
+        hipLaunchKernelGGL(cand_trial_kernel, dim3((unsigned)((pc.n_cand + 255) / 256)), dim3(256), 0, c->stream, (const int32_t*)pc.d_cand_off, pc.n_trials, pc.first,
+                           pc.n_cand, pc.d_cand_trial);
+        STOCS_HIP_CHECK(hipGetLastError());
+    }
+    int rc;
+    { TrialWeightsScope weights(c, pc.trial_weights, pc.d_cand_trial); rc = launch_lcp(c, cand_T(c), pc.n_cand, cand_lcp(c), NULL, NULL, NULL, 0); }
+    if (rc) return rc;
+    hipLaunchKernelGGL(trial_best_kernel, dim3((unsigned)pc.n_trials), dim3(256), 0, c->stream, (const float*)cand_lcp(c), (const float*)cand_P(c),
+                       (const int32_t*)pc.d_cand_off, pc.d_best18);
+    STOCS_HIP_CHECK(hipGetLastError());
+    return STOCS_OK;
+}
+
+// post-processing of the piece: greedy_clustering of every trial, the kept candidates' records, then (refine_iterations > 0) the
+// point-to-plane refinement of every kept hypothesis of the piece in one enqueue, on the whole scene, written back into the records
+static int post_piece(stocs_ctx* c, const Piece& pc) {
+    const stocs_trial_post* post = pc.post;
+    const int H = pc.n_slots;
+    TrialClusterArgs ca;
+    ca.fraction = post->acceptable_fraction; ca.count = post->maximum_pose_count; ca.min_distance = post->min_distance; ca.min_angle = post->min_angle;
+    for (int d = 0; d < 3; ++d) ca.sym[d] = post->sym3[d];
+    int rc = enqueue_trial_cluster(c, pc.n_trials, cand_P(c), cand_lcp(c), pc.d_cand_off, pc.d_best18, ca, pc.d_alive, pc.d_hyp_off, pc.d_hyp_count, pc.d_hyp_index);
+    if (rc) return rc;
+    RefineWork w;
+    if (pc.refine && (rc = refine_prepare(c, H, c->nS, post->max_correspondence_distance, &w))) return rc;
+    if (H > 0) {
+        hipLaunchKernelGGL(trial_hyp_gather_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, c->stream, (const float*)cand_T(c), (const float*)cand_P(c),
+                           (const float*)cand_lcp(c), (const int32_t*)cand_base(c), (const int32_t*)pc.d_cand_off, (const int32_t*)pc.d_hyp_off,
+                           (const int32_t*)pc.d_hyp_count, (const int32_t*)pc.d_hyp_index, pc.n_trials, pc.first, H, pc.d_hyp_records, pc.refine ? w.d_Tin : NULL,
+                           pc.d_slot_live, pc.d_slot_trial);
+        STOCS_HIP_CHECK(hipGetLastError());
+    }
+    if (!pc.refine) return STOCS_OK;
+    {   // instance mode: hypothesis s rescored against the weights of its own trial, as the scoring launch
+        TrialWeightsScope weights(c, pc.trial_weights, pc.d_slot_trial);
+        rc = refine_enqueue(c, w, false, pc.d_slot_live, post->refine_iterations, post->max_correspondence_distance);
+    }
+    if (rc) return rc;
+    hipLaunchKernelGGL(refine_trial_hyp_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, c->stream, (const int32_t*)pc.d_slot_live, H, (const float*)w.d_Pout,
+                       (const float*)w.d_lcp, (const int32_t*)w.d_nc, (const int32_t*)w.d_it, pc.d_hyp_records);
+    STOCS_HIP_CHECK(hipGetLastError());
+    return STOCS_OK;
+}
+
+// the piece's one read-back and its one synchronisation: the per-trial results [, the hypothesis counts and records behind them]
+static int fetch_piece(stocs_ctx* c, TrialBatch* B, Piece& pc) {
+    STOCS_HIP_CHECK(hipMemcpyAsync(pc.h_best18, pc.d_best18, pc.back_bytes, hipMemcpyDeviceToHost, c->stream));
+    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    memcpy(pc.best18.data(), pc.h_best18, (size_t)pc.n_trials * 18 * 4);
+    for (int t = 0; pc.post && t < pc.n_trials; ++t) {
+        const int m = std::min(pc.h_hyp_count[t], pc.hyp_off[(size_t)t + 1] - pc.hyp_off[(size_t)t]);
+        B->hyps[(size_t)(pc.first + t)].assign(pc.h_hyp_records + pc.hyp_off[(size_t)t], pc.h_hyp_records + pc.hyp_off[(size_t)t] + std::max(m, 0));
+    }
+    c->cands_stale = true;
+    return STOCS_OK;
+}
+
+// the per-trial results of the piece, and with keep_details every trial's candidates
+static int collect_piece(stocs_ctx* c, TrialBatch* B, const Piece& pc) {
+    const size_t n_cand = (size_t)pc.n_cand;
+    std::vector<float> hT, hP, hL; std::vector<int32_t> hB;
+    if (B->keep && n_cand > 0) {
+        hT.resize(n_cand * 16); hP.resize(n_cand * 16); hL.resize(n_cand); hB.resize(n_cand);
+        STOCS_HIP_CHECK(hipMemcpyAsync(hT.data(), cand_T(c), n_cand * 64, hipMemcpyDeviceToHost, c->stream));
+        STOCS_HIP_CHECK(hipMemcpyAsync(hP.data(), cand_P(c), n_cand * 64, hipMemcpyDeviceToHost, c->stream));
+        STOCS_HIP_CHECK(hipMemcpyAsync(hL.data(), cand_lcp(c), n_cand * 4, hipMemcpyDeviceToHost, c->stream));
+        STOCS_HIP_CHECK(hipMemcpyAsync(hB.data(), cand_base(c), n_cand * 4, hipMemcpyDeviceToHost, c->stream));
+        STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    }
+    for (int t = 0; t < pc.n_trials; ++t) {
+        const size_t bt = (size_t)(pc.first + t);
+        stocs_trial_result& R = B->out[bt];
+        const int b0 = c->trial_first_base[(size_t)t], b1 = c->trial_first_base[(size_t)t + 1];
+        const int o0 = c->trial_cand_off[(size_t)t], o1 = c->trial_cand_off[(size_t)t + 1];
+        R.n_bases = b1 - b0; R.n_candidates = o1 - o0; R.n_quads = 0;
+        std::vector<long long>& q = B->quads[bt];
+        q.resize((size_t)(b1 - b0));
+        for (int b = b0; b < b1; ++b) {
+            const long long nq = (size_t)b + 1 < c->quad_off.size() ? (long long)(c->quad_off[(size_t)b + 1] - c->quad_off[(size_t)b]) : 0;
+            q[(size_t)(b - b0)] = nq; R.n_quads += nq;
+        }
+        const float* r18 = &pc.best18[(size_t)t * 18];
+        uint32_t lo, hi; memcpy(&lo, r18, 4); memcpy(&hi, r18 + 1, 4);
+        const unsigned long long key = ((unsigned long long)hi << 32) | lo;
+        R.best_lcp = 0.0f; R.best_index = -1; memset(R.best_pose16, 0, sizeof(R.best_pose16));
+        if (key) {
+            R.best_lcp = best_key_score(key);
+            R.best_index = (int32_t)best_key_index(key);
+            memcpy(R.best_pose16, r18 + 2, 64);
+        }
+        if (B->keep && o1 > o0) {
+            B->T[bt].assign(hT.begin() + (size_t)o0 * 16, hT.begin() + (size_t)o1 * 16);
+            B->P[bt].assign(hP.begin() + (size_t)o0 * 16, hP.begin() + (size_t)o1 * 16);
+            B->lcp[bt].assign(hL.begin() + o0, hL.begin() + o1);
+            B->cbase[bt].assign(hB.begin() + o0, hB.begin() + o1);
+        }
+    }
+    return STOCS_OK;
+}
+
 }  // namespace stocs
 
 using namespace stocs;
@@ -195,37 +385,18 @@ int stocs_run_trials_post(stocs_ctx* c, int mode, int n_trials, const uint64_t* 
         const int rc = sample_trials(c, mode, nT, seeds, nA, dispersion, B->res.data(), &c->snrmw_trial0, &c->snrmw_stride);
         if (rc) { clear_trial_batch(c); B->nT = 0; B->out.clear(); return rc; }
     }
-    const float4* snrmw0 = c->snrmw_trial0;
+    const float4* trial_weights = mode == 1 ? c->snrmw_trial0 : NULL;
     TM.lap("sampling: every attempt of every trial in one launch + read-back");
-    // ---- how many bases one set of launches can take (congruent.hip: 32-bit (base, cell) sort keys with the run table, packed
-    //      64-bit quads with the base above the four model ids) ----
-    long long max_bases = 1 << 20;
-    {
-        const float eps_unit = c->prm.distance_threshold / c->ratio;
-        const int gridDepth = (int)(-log2f(eps_unit));
-        const int egSize = (int)pow(2.0, (double)gridDepth);
-        const long long NC = (long long)egSize * egSize * egSize;
-        int id_bits = 1, cell_bits = 1;
-        while ((1 << id_bits) < c->nM) id_bits++;
-        if (NC > 0 && NC < (1ll << 31)) {
-            while (cell_bits < 40 && (((unsigned long long)1 << cell_bits) - 1ull) < (unsigned long long)NC) cell_bits++;
-            if (cell_bits < 32) max_bases = std::min(max_bases, 1ll << (32 - cell_bits));
-            max_bases = std::min(max_bases, std::max(1ll, (1ll << 27) / NC));
-        }
-        if (4 * id_bits < 64) max_bases = std::min(max_bases, 1ll << std::min(20, 64 - 4 * id_bits));
-        max_bases = std::max(max_bases, (long long)std::max(nA, 1));     // a single trial always goes through (as it does alone)
-    }
+    const long long max_bases = max_bases_per_piece(c, nA);
     size_t max_bytes = (size_t)48 << 30;      // of 288 GB: a Cm trial is ~0.9 GB of pair lists, and at Cm a piece is then what the 64-bit quads can key (40 trials)
     if (const char* e = getenv("STOCS_TRIALS_MAX_MB")) max_bytes = (size_t)std::max(1, atoi(e)) << 20;
     int piece_cap = nT;
     if (const char* e = getenv("STOCS_TRIALS_PER_PIECE")) piece_cap = std::max(1, atoi(e));   // (tests: forces several pieces)
     std::vector<int32_t> n_valid((size_t)nT, 0);
     for (int t = 0; t < nT; ++t) for (int a = 0; a < nA; ++a) n_valid[(size_t)t] += B->res[(size_t)t * nA + a].valid ? 1 : 0;
-    // A HIP error inside a piece leaves through the common epilogue below (batch state cleared, context reset, the batch record
-    // marked invalid) instead of returning from the middle of the loop with a half-filled record that the getters would serve.
-#define TRIALS_HIP_TRY(expr) { const hipError_t e_ = (expr); if (e_ != hipSuccess) { set_error("%s:%d: %s -> %s", __FILE__, __LINE__, #expr, hipGetErrorString(e_)); rc = STOCS_ERR_HIP; break; } }
+    // An error inside a piece leaves through the common epilogue below (batch state cleared, context reset, the batch record marked
+    // invalid) instead of returning from the middle of the loop with a half-filled record that the getters would serve.
     int rc = STOCS_OK;
-    std::vector<int32_t> hyp_off;
     for (int t0 = 0; t0 < nT && !rc;) {
         int t1 = t0;
         long long nb = 0;
@@ -233,23 +404,7 @@ int stocs_run_trials_post(stocs_ctx* c, int mode, int n_trials, const uint64_t* 
         int64_t total_quads = 0;
         for (;;) {   // the piece t0 .. t1: halved until its pair lists fit the ceiling
             const double t_asm = now_ms();
-            c->bases.clear(); c->base_seed.clear(); c->base_local.clear(); c->trial_first_base.clear(); c->trial_cand_off.clear();
-            c->quad_off.clear(); clear_candidates(c);
-            for (int t = t0; t < t1; ++t) {
-                c->trial_first_base.push_back((int32_t)c->bases.size());
-                int slot = 0;
-                for (int a = 0; a < nA; ++a) {
-                    const BaseOut& r = B->res[(size_t)t * nA + a];
-                    if (!r.valid) continue;
-                    BaseRec br;
-                    for (int k = 0; k < 4; ++k) br.ids[k] = r.ids[k];
-                    br.inv1 = r.inv[0]; br.inv2 = r.inv[1];
-                    c->bases.push_back(br);
-                    c->base_seed.push_back(seeds[t]);
-                    c->base_local.push_back(slot++);
-                }
-            }
-            c->trial_first_base.push_back((int32_t)c->bases.size());
+            assemble_piece(c, B, t0, t1);
             const double ta = now_ms();
             ms_asm += ta - t_asm;
             int too_big = 0;
@@ -262,158 +417,22 @@ int stocs_run_trials_post(stocs_ctx* c, int mode, int n_trials, const uint64_t* 
         }
         if (rc) break;
         B->pieces++;
-        const int nTp = t1 - t0;
+        Piece pc;
+        pc.first = t0; pc.n_trials = t1 - t0; pc.post = post; pc.trial_weights = trial_weights;
+        pc.best18.assign((size_t)pc.n_trials * 18, 0.0f);
         double ta = now_ms();
-        int n_cand = 0;
-        if ((rc = stocs_make_transforms(c, max_per_base, 0, &n_cand))) break;
+        if ((rc = stocs_make_transforms(c, max_per_base, 0, &pc.n_cand))) break;
         ms_xf += now_ms() - ta;
         ta = now_ms();
-        if ((int)c->trial_cand_off.size() != nTp + 1) c->trial_cand_off.assign((size_t)nTp + 1, 0);   // (a piece without any base)
-        // ---- verification: every candidate of the piece scored, then the arg-max of each trial ----
-        std::vector<float> out18((size_t)nTp * 18, 0.0f);
-        if (n_cand > 0) {
-            // scratch of this step (the transform jobs of the piece are done with the area): per-trial candidate offsets | per-trial
-            // results | (instance mode) the trial of every candidate
-            const bool per_trial_weights = mode == 1 && snrmw0 != NULL;
-            // post-processing: per trial min(count + 1, its candidates) hypothesis slots (the counts come back with the read-back)
-            hyp_off.assign(post ? (size_t)nTp + 1 : 0, 0);
-            for (int t = 0; post && t < nTp; ++t)
-                hyp_off[(size_t)t + 1] = hyp_off[(size_t)t] + (int32_t)std::min<long long>((long long)post->maximum_pose_count + 1,
-                                                                                          (long long)(c->trial_cand_off[(size_t)t + 1] - c->trial_cand_off[(size_t)t]));
-            const int H = post ? hyp_off[(size_t)nTp] : 0;
-            const bool refine = post && post->refine_iterations > 0 && H > 0;
-            auto al = [](size_t b) { return (b + 255) & ~(size_t)255; };
-            // scratch: per-trial candidate offsets | per-trial results [| hypothesis counts | hypothesis records] | (instance mode) the
-            // trial of every candidate [| survivor flags | hypothesis offsets | kept indices | slot trial | slot live]
-            const size_t ob = (((size_t)nTp + 1) * 4 + 255) & ~(size_t)255, rb = (((size_t)nTp * 18 * 4) + 255) & ~(size_t)255,
-                         tb = per_trial_weights ? (((size_t)n_cand * 4 + 255) & ~(size_t)255) : 0;
-            const size_t cb = post ? al((size_t)nTp * 4) : 0, hb = post ? al((size_t)H * sizeof(stocs_trial_hypothesis)) : 0;
-            const size_t fb = post ? al((size_t)n_cand) : 0, hob = post ? al(((size_t)nTp + 1) * 4) : 0, ib = post ? al((size_t)H * 4) : 0;
-            const size_t sb = refine ? al((size_t)H * 4) : 0;
-            if ((rc = ensure_scratch(c, ob + rb + cb + hb + tb + fb + hob + ib + 2 * sb + 256))) break;
-            if ((rc = ensure_pinned(c, (size_t)PIN_VAR + ob + rb + cb + hb + hob + 256))) break;
-            int32_t* d_off = (int32_t*)c->d_scratch;
-            float* d_out = (float*)((char*)c->d_scratch + ob);
-            int32_t* d_hcnt = (int32_t*)((char*)c->d_scratch + ob + rb);
-            stocs_trial_hypothesis* d_hrec = (stocs_trial_hypothesis*)((char*)c->d_scratch + ob + rb + cb);
-            int32_t* d_ct = (int32_t*)((char*)c->d_scratch + ob + rb + cb + hb);
-            char* d_post = (char*)c->d_scratch + ob + rb + cb + hb + tb;
-            uint8_t* d_alive = (uint8_t*)d_post;
-            int32_t* d_hoff = (int32_t*)(d_post + fb);
-            int32_t* d_hidx = (int32_t*)(d_post + fb + hob);
-            int32_t* d_strial = (int32_t*)(d_post + fb + hob + ib);
-            int32_t* d_slive = (int32_t*)(d_post + fb + hob + ib + sb);
-            int32_t* off_pin = (int32_t*)((char*)c->h_pin + PIN_VAR);
-            float* out_pin = (float*)((char*)c->h_pin + PIN_VAR + ob);
-            int32_t* hoff_pin = (int32_t*)((char*)c->h_pin + PIN_VAR + ob + rb + cb + hb);
-            memcpy(off_pin, c->trial_cand_off.data(), 4 * ((size_t)nTp + 1));
-            TRIALS_HIP_TRY(hipMemcpyAsync(d_off, off_pin, 4 * ((size_t)nTp + 1), hipMemcpyHostToDevice, c->stream));
-            if (post) {
-                memcpy(hoff_pin, hyp_off.data(), 4 * ((size_t)nTp + 1));
-                TRIALS_HIP_TRY(hipMemcpyAsync(d_hoff, hoff_pin, 4 * ((size_t)nTp + 1), hipMemcpyHostToDevice, c->stream));
-            }
-            if (!per_trial_weights) {
-                if ((rc = launch_lcp(c, cand_T(c), n_cand, cand_lcp(c), NULL, NULL, NULL, 0))) break;
-            } else {
-                // instance mode: every candidate against the class probabilities as ITS trial's sampling decayed them (Q8) -- still ONE
-                // launch: the kernel picks the trial's copy of the scene normals + weights per candidate (LcpArgs::cand_trial)
-                hipLaunchKernelGGL(cand_trial_kernel, dim3((unsigned)((n_cand + 255) / 256)), dim3(256), 0, c->stream, (const int32_t*)d_off, nTp, t0, n_cand, d_ct);
-                TRIALS_HIP_TRY(hipGetLastError());
-                c->snrmw_override = snrmw0; c->lcp_cand_trial = d_ct;
-                rc = launch_lcp(c, cand_T(c), n_cand, cand_lcp(c), NULL, NULL, NULL, 0);
-                c->snrmw_override = NULL; c->lcp_cand_trial = NULL;
-                if (rc) break;
-            }
-            hipLaunchKernelGGL(trial_best_kernel, dim3((unsigned)nTp), dim3(256), 0, c->stream, (const float*)cand_lcp(c), (const float*)cand_P(c), (const int32_t*)d_off, d_out);
-            TRIALS_HIP_TRY(hipGetLastError());
-            if (post) {
-                // ---- post-processing of the piece: greedy_clustering of every trial, then (refine_iterations > 0) the point-to-plane
-                //      refinement of every kept hypothesis of the piece in one enqueue, on the whole scene ----
-                TrialClusterArgs ca;
-                ca.fraction = post->acceptable_fraction; ca.count = post->maximum_pose_count; ca.min_distance = post->min_distance; ca.min_angle = post->min_angle;
-                for (int d = 0; d < 3; ++d) ca.sym[d] = post->sym3[d];
-                if ((rc = enqueue_trial_cluster(c, nTp, cand_P(c), cand_lcp(c), d_off, d_out, ca, d_alive, d_hoff, d_hcnt, d_hidx))) break;
-                RefineWork w;
-                if (refine && (rc = refine_prepare(c, H, c->nS, post->max_correspondence_distance, &w))) break;
-                if (H > 0) {
-                    hipLaunchKernelGGL(trial_hyp_gather_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, c->stream, (const float*)cand_T(c),
-                                       (const float*)cand_P(c), (const float*)cand_lcp(c), (const int32_t*)cand_base(c), (const int32_t*)d_off,
-                                       (const int32_t*)d_hoff, (const int32_t*)d_hcnt, (const int32_t*)d_hidx, nTp, t0, H, d_hrec, refine ? w.d_Tin : NULL,
-                                       d_slive, d_strial);
-                    TRIALS_HIP_TRY(hipGetLastError());
-                }
-                if (refine) {
-                    // instance mode: hypothesis s rescored against the weights of its own trial, as the scoring launch above
-                    if (per_trial_weights) { c->snrmw_override = snrmw0; c->lcp_cand_trial = d_strial; }
-                    rc = refine_enqueue(c, w, false, d_slive, post->refine_iterations, post->max_correspondence_distance);
-                    c->snrmw_override = NULL; c->lcp_cand_trial = NULL;
-                    if (rc) break;
-                    hipLaunchKernelGGL(refine_trial_hyp_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, c->stream, (const int32_t*)d_slive, H,
-                                       (const float*)w.d_Pout, (const float*)w.d_lcp, (const int32_t*)w.d_nc, (const int32_t*)w.d_it, d_hrec);
-                    TRIALS_HIP_TRY(hipGetLastError());
-                }
-            }
-            // one read-back: the per-trial results [, the hypothesis counts and records right behind them]
-            TRIALS_HIP_TRY(hipMemcpyAsync(out_pin, d_out, post ? rb + cb + (size_t)H * sizeof(stocs_trial_hypothesis) : (size_t)nTp * 18 * 4, hipMemcpyDeviceToHost, c->stream));
-            TRIALS_HIP_TRY(hipStreamSynchronize(c->stream));
-            memcpy(out18.data(), out_pin, (size_t)nTp * 18 * 4);
-            if (post) {
-                const int32_t* cnt = (const int32_t*)((const char*)out_pin + rb);
-                const stocs_trial_hypothesis* rec = (const stocs_trial_hypothesis*)((const char*)out_pin + rb + cb);
-                for (int t = 0; t < nTp; ++t) {
-                    const int m = std::min(cnt[t], hyp_off[(size_t)t + 1] - hyp_off[(size_t)t]);
-                    B->hyps[(size_t)(t0 + t)].assign(rec + hyp_off[(size_t)t], rec + hyp_off[(size_t)t] + std::max(m, 0));
-                }
-            }
-            c->cands_stale = true;
-        }
+        if ((int)c->trial_cand_off.size() != pc.n_trials + 1) c->trial_cand_off.assign((size_t)pc.n_trials + 1, 0);   // (a piece without any base)
+        // ---- verification: every candidate of the piece scored, the arg-max of each trial [, clustered and refined], one synchronisation ----
+        if (pc.n_cand > 0 && ((rc = plan_piece(c, pc)) || (rc = score_piece(c, pc)) || (post && (rc = post_piece(c, pc))) || (rc = fetch_piece(c, B, pc)))) break;
         ms_ver += now_ms() - ta;
         ta = now_ms();
-        // ---- results of the piece ----
-        std::vector<float> hT, hP, hL; std::vector<int32_t> hB;
-        if (B->keep && n_cand > 0) {
-            hT.resize((size_t)n_cand * 16); hP.resize((size_t)n_cand * 16); hL.resize((size_t)n_cand); hB.resize((size_t)n_cand);
-            TRIALS_HIP_TRY(hipMemcpyAsync(hT.data(), cand_T(c), (size_t)n_cand * 64, hipMemcpyDeviceToHost, c->stream));
-            TRIALS_HIP_TRY(hipMemcpyAsync(hP.data(), cand_P(c), (size_t)n_cand * 64, hipMemcpyDeviceToHost, c->stream));
-            TRIALS_HIP_TRY(hipMemcpyAsync(hL.data(), cand_lcp(c), (size_t)n_cand * 4, hipMemcpyDeviceToHost, c->stream));
-            TRIALS_HIP_TRY(hipMemcpyAsync(hB.data(), cand_base(c), (size_t)n_cand * 4, hipMemcpyDeviceToHost, c->stream));
-            TRIALS_HIP_TRY(hipStreamSynchronize(c->stream));
-        }
-        for (int t = 0; t < nTp; ++t) {
-            stocs_trial_result& R = B->out[(size_t)(t0 + t)];
-            const int b0 = c->trial_first_base[(size_t)t], b1 = c->trial_first_base[(size_t)t + 1];
-            const int o0 = c->trial_cand_off[(size_t)t], o1 = c->trial_cand_off[(size_t)t + 1];
-            R.n_bases = b1 - b0;
-            R.n_candidates = o1 - o0;
-            R.n_quads = 0;
-            std::vector<long long>& q = B->quads[(size_t)(t0 + t)];
-            q.resize((size_t)(b1 - b0));
-            for (int b = b0; b < b1; ++b) {
-                const long long nq = (size_t)b + 1 < c->quad_off.size() ? (long long)(c->quad_off[(size_t)b + 1] - c->quad_off[(size_t)b]) : 0;
-                q[(size_t)(b - b0)] = nq; R.n_quads += nq;
-            }
-            uint32_t lo, hi;
-            memcpy(&lo, &out18[(size_t)t * 18], 4); memcpy(&hi, &out18[(size_t)t * 18 + 1], 4);
-            const uint64_t key = ((uint64_t)hi << 32) | lo;
-            R.best_lcp = 0.0f; R.best_index = -1;
-            memset(R.best_pose16, 0, sizeof(R.best_pose16));
-            if (key) {
-                uint32_t id = 0;
-                stocs_unpack_best(key, &R.best_lcp, &id);
-                R.best_index = (int32_t)id;
-                memcpy(R.best_pose16, &out18[(size_t)t * 18 + 2], 64);
-            }
-            if (B->keep && o1 > o0) {
-                B->T[(size_t)(t0 + t)].assign(hT.begin() + (size_t)o0 * 16, hT.begin() + (size_t)o1 * 16);
-                B->P[(size_t)(t0 + t)].assign(hP.begin() + (size_t)o0 * 16, hP.begin() + (size_t)o1 * 16);
-                B->lcp[(size_t)(t0 + t)].assign(hL.begin() + o0, hL.begin() + o1);
-                B->cbase[(size_t)(t0 + t)].assign(hB.begin() + o0, hB.begin() + o1);
-            }
-        }
+        if ((rc = collect_piece(c, B, pc))) break;
         ms_res += now_ms() - ta;
         t0 = t1;
     }
-#undef TRIALS_HIP_TRY
     // the context is left as stocs_reset_trial leaves it: no bases, no candidates (the batch's results live in the batch record)
     clear_trial_batch(c);
     c->bases.clear(); c->quad_off.clear(); clear_candidates(c);

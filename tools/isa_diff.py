@@ -1,12 +1,13 @@
 #!/usr/bin/env python3
-"""Compare the kernels of two device-only assembly listings of lcp.hip (hipcc ... --cuda-device-only -S), kernel by kernel.
+"""Compare the kernels of two device-only assembly listings of one source file of model_matching_amd/csrc, kernel by kernel: the
+same file compiled at two commits with the Makefile's flags plus --cuda-device-only -S.
 
-usage: lcp_isa_diff.py OLD.s NEW.s [--map OLD_MANGLED=NEW_MANGLED ...]
+usage: isa_diff.py OLD.s NEW.s
 
 A kernel's body is the text between its label and its .Lfunc_end; mangled names and basic-block numbers are replaced by
 placeholders before the comparison.  Prints one markdown table row per kernel of NEW: identical or the number of differing lines,
-and VGPRs / SGPRs / LDS bytes / scratch bytes of both listings.  Kernels are paired by their demangled names through
-pair_name(), which knows how the template arguments of the queue and per-step kernels were renamed."""
+and VGPRs / SGPRs / LDS bytes / scratch bytes of both listings.  Kernels are paired by their demangled names (any file); for the
+queue and per-step kernels of lcp.hip pair_name() also knows how their template arguments were renamed."""
 import difflib
 import re
 import subprocess
