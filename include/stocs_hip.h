@@ -353,6 +353,20 @@ int stocs_refine_poses(stocs_ctx* ctx, const float* T16_centred_in, int n, const
                        float max_correspondence_distance, float* T16_centred_out, float* pose16_camera_out, float* lcp_out,
                        int32_t* n_corr_out, int32_t* iterations_out);
 
+/* Test and diagnosis facility of the refinement (as stocs_lcp_detail is of the scoring): the FIRST evaluation (U = I) of ONE
+ * hypothesis, by the walk, the grid, the staging (LDS or global memory), the octant switch and the margins stocs_refine_poses uses
+ * for that distance on this context.  Source point i = src_idx[i] (NULL: every scene point, n_src ignored), taken to the model frame
+ * by T^-1 and rounded to float.  match[i]: the model index the walk chose -- the nearest centred model point by the float squared
+ * distance fma(dz, dz, fma(dy, dy, dx dx)) among those below the search bound (float)(d^2 (1 + 1e-5)), THE LOWEST MODEL INDEX ON
+ * EQUAL DISTANCE -- or -1 when there is none or the point lies outside the model's box widened by the distance.  counted[i]: 1 when
+ * that pair passed the double test |s - t|^2 <= (double)d (double)d and entered the sums.  sums28 (may be NULL): the 21 entries of
+ * the upper triangle of A^T A (row by row), the 6 of A^T b and the count, in double, summed as the solve step sums them.  A
+ * hypothesis whose linear part is singular or not finite matches nothing: match -1, counted 0, sums 0.  Argument checking as
+ * stocs_refine_poses (one hypothesis, never NULL; match and counted must not be NULL when there are source points).  Changes no
+ * state but the refinement's workspace; synchronises. */
+int stocs_refine_detail(stocs_ctx* ctx, const float* T16_centred, const int32_t* src_idx, int n_src, float max_correspondence_distance,
+                        int32_t* match, uint8_t* counted, double* sums28);
+
 /* ---- pose tracking across frames: a local search around n prior poses on the context's current scene (no reference counterpart;
  * the reference detects from scratch on every frame).  Priors are CAMERA-frame poses (column-major, as stocs_get_candidates and the
  * pose file give them: only the camera frame carries over from frame to frame).  Each is taken to the centred frame on the host, in

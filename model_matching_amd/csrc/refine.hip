@@ -57,6 +57,7 @@ struct RefineGrid {
 struct RefineState {
     RefineGrid g;
     DevBlock work;   // hypotheses | T in | source indices | partials | outputs (grow-only)
+    DevBlock detail; // stocs_refine_detail: match | counted | sums (grow-only)
 };
 
 __global__ __launch_bounds__(256) void refine_keys_kernel(const float4* __restrict__ mpos, int nM, float ox, float oy, float oz, float inv_h, int nx, int ny,
@@ -175,10 +176,21 @@ struct RefArgs {
     double max_d2;
 };
 
+// What stocs_refine_detail reads out of the accumulation and the summation of ONE hypothesis (arrays preset to -1 / 0 / 0: a lane
+// that never reaches a store leaves them).  The shipping kernels are the RefNoDetail instantiations: an empty trailing argument, every
+// `if constexpr (Detail::on)` discarded, the same instructions as without it.
+struct RefNoDetail { static constexpr bool on = false; };
+struct RefDetailOut {
+    static constexpr bool on = true;
+    int32_t* match;     // nsrc: the model index the walk chose, -1 none
+    uint8_t* counted;   // nsrc: passed the double threshold test
+    double* sums28;     // the 28 sums as the solve step forms them
+};
+
 // kLds: the cell-ordered model positions and the offsets are staged in LDS first (small models, REFINE_LDS_BYTES): the walk's loads
 // then cost a fraction of a cache hit
-template <bool kLds>
-__global__ __launch_bounds__(256) void refine_accumulate_kernel(RefArgs a, const RefHyp* __restrict__ hyp, double* __restrict__ partial) {
+template <bool kLds, class Detail>
+__global__ __launch_bounds__(256) void refine_accumulate_kernel(RefArgs a, const RefHyp* __restrict__ hyp, double* __restrict__ partial, Detail det) {
     extern __shared__ float4 lds_pos[];   // kLds: nM positions, then the nsub + 1 octant offsets
     uint32_t* lds_off = (uint32_t*)(lds_pos + a.nM);
     const int hk = blockIdx.x / a.nchunks, ch = blockIdx.x - hk * a.nchunks;
@@ -246,6 +258,7 @@ __global__ __launch_bounds__(256) void refine_accumulate_kernel(RefArgs a, const
                     }
                 }
             }
+            if constexpr (Detail::on) det.match[i] = (int32_t)(uint32_t)key;   // the key's start value carries index -1
             if ((uint32_t)key != 0xFFFFFFFFu) {
                 const uint32_t id = (uint32_t)key;
                 const float4 t = a.mpos[id], nn = a.mnrm[id];
@@ -261,6 +274,7 @@ __global__ __launch_bounds__(256) void refine_accumulate_kernel(RefArgs a, const
 #pragma unroll
                     for (int r = 0; r < 6; ++r) v[21 + r] = ar[r] * b;
                     v[27] = 1.0;
+                    if constexpr (Detail::on) det.counted[i] = 1;
                 }
             }
         }
@@ -280,7 +294,9 @@ __global__ __launch_bounds__(256) void refine_accumulate_kernel(RefArgs a, const
     if (threadIdx.x < 28) partial[(size_t)blockIdx.x * 28 + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
 
-__global__ __launch_bounds__(64) void refine_solve_kernel(RefHyp* __restrict__ hyp, const double* __restrict__ partial, int nchunks) {
+// Detail::on: the sums go to det.sums28 and nothing else happens (no solve, the hypothesis stays as it is)
+template <class Detail>
+__global__ __launch_bounds__(64) void refine_solve_kernel(RefHyp* __restrict__ hyp, const double* __restrict__ partial, int nchunks, Detail det) {
     RefHyp* H = hyp + blockIdx.x;
     if (H->frozen) return;
     // lane l sums chunks l, l + 64, ... in order, then a butterfly over the wavefront: a fixed order, whatever the batch
@@ -295,6 +311,11 @@ __global__ __launch_bounds__(64) void refine_solve_kernel(RefHyp* __restrict__ h
 #pragma unroll
         for (int k = 0; k < 28; ++k) acc[k] += __shfl_xor(acc[k], o, 64);
     if (threadIdx.x) return;
+    if constexpr (Detail::on) {
+#pragma unroll
+        for (int k = 0; k < 28; ++k) det.sums28[k] = acc[k];
+        return;
+    }
     const int ncorr = (int)acc[27];
     H->ncorr = ncorr;
     if (ncorr < 6) { H->frozen = 1; return; }   // not enough correspondences: keep the current estimate
@@ -394,7 +415,7 @@ static int build_refine_grid(stocs_ctx* c, RefineState* S, float d) {
 // has to be (re)built or grown; nothing of the workspace may be in flight then)
 int refine_prepare(stocs_ctx* c, int n, int nsrc, float max_correspondence_distance, RefineWork* w) {
     const int nchunks = (nsrc + REFINE_CHUNK - 1) / REFINE_CHUNK;
-    if ((int64_t)n * std::max(nchunks, 1) >= ((int64_t)1 << 31)) { set_error("stocs_refine_poses: %d hypotheses x %d chunks: too many workgroups", n, nchunks); return STOCS_ERR_INVALID; }
+    if ((int64_t)n * std::max(nchunks, 1) >= ((int64_t)1 << 31)) { set_error("refinement: %d hypotheses x %d chunks: too many workgroups", n, nchunks); return STOCS_ERR_INVALID; }
     if (!c->refine) {
         c->refine = new RefineState();   // (value-initialised: no grid, no workspace)
     }
@@ -420,16 +441,10 @@ int refine_prepare(stocs_ctx* c, int n, int nsrc, float max_correspondence_dista
     return STOCS_OK;
 }
 
-// init, max_iterations x (accumulate, solve), final, the LCP launch -- on the stream, no copy, no synchronisation.  Input: w.d_Tin
-// (n centred T16); the source is w.d_idx[0 .. nsrc) when use_idx, else every scene point; live: see refine_init_kernel.  The LCP
-// launch follows the context's scoring state (c->snrmw_override / c->lcp_cand_trial of an instance-mode batch included)
-int refine_enqueue(stocs_ctx* c, const RefineWork& w, bool use_idx, const int32_t* d_live, int max_iterations, float max_correspondence_distance) {
+// the accumulation's arguments for the context's grid and this distance; *lds_bytes: what staging the model in LDS takes
+static RefArgs refine_args(stocs_ctx* c, const RefineWork& w, bool use_idx, float max_correspondence_distance, size_t* lds_bytes) {
     RefineState* S = (RefineState*)c->refine;
-    const int n = w.n, nchunks = w.nchunks;
-    RefHyp* d_hyp = (RefHyp*)w.d_hyp;
-    const unsigned hblocks = (unsigned)((n + 63) / 64);
-    hipLaunchKernelGGL(refine_init_kernel, dim3(hblocks), dim3(64), 0, c->stream, (const float*)w.d_Tin, n, d_live, d_hyp);
-    STOCS_HIP_CHECK(hipGetLastError());
+    const int nchunks = w.nchunks;
     RefArgs a;
     a.spos = c->d_spos; a.idx = use_idx ? w.d_idx : NULL; a.nsrc = w.nsrc; a.nchunks = nchunks; a.nM = c->nM; a.nsub = 8 * S->g.nx * S->g.ny * S->g.nz;
     a.octants = c->nM >= REFINE_OCTANT_DENSITY * S->g.nx * S->g.ny * S->g.nz ? 1 : 0;
@@ -441,17 +456,32 @@ int refine_enqueue(stocs_ctx* c, const RefineWork& w, bool use_idx, const int32_
     a.max_d2_f = (float)(a.max_d2 * (1.0 + 1e-5));
     a.h2 = S->g.h * S->g.h;
     a.margin_u = 1e-3f + 1e-6f * (float)std::max(S->g.nx, std::max(S->g.ny, S->g.nz));
-    const size_t lds_bytes = (size_t)c->nM * 16 + ((size_t)a.nsub + 1) * 4;
+    *lds_bytes = (size_t)c->nM * 16 + ((size_t)a.nsub + 1) * 4;
+    return a;
+}
+
+// init, max_iterations x (accumulate, solve), final, the LCP launch -- on the stream, no copy, no synchronisation.  Input: w.d_Tin
+// (n centred T16); the source is w.d_idx[0 .. nsrc) when use_idx, else every scene point; live: see refine_init_kernel.  The LCP
+// launch follows the context's scoring state (c->snrmw_override / c->lcp_cand_trial of an instance-mode batch included)
+int refine_enqueue(stocs_ctx* c, const RefineWork& w, bool use_idx, const int32_t* d_live, int max_iterations, float max_correspondence_distance) {
+    const int n = w.n, nchunks = w.nchunks;
+    RefHyp* d_hyp = (RefHyp*)w.d_hyp;
+    const unsigned hblocks = (unsigned)((n + 63) / 64);
+    hipLaunchKernelGGL(refine_init_kernel, dim3(hblocks), dim3(64), 0, c->stream, (const float*)w.d_Tin, n, d_live, d_hyp);
+    STOCS_HIP_CHECK(hipGetLastError());
+    size_t lds_bytes = 0;
+    const RefArgs a = refine_args(c, w, use_idx, max_correspondence_distance, &lds_bytes);
     for (int it = 0; it < max_iterations; ++it) {
         if (nchunks > 0) {
             if (lds_bytes <= REFINE_LDS_BYTES)
-                hipLaunchKernelGGL(refine_accumulate_kernel<true>, dim3((unsigned)(n * nchunks)), dim3(REFINE_CHUNK), lds_bytes, c->stream, a,
-                                   (const RefHyp*)d_hyp, w.d_part);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(refine_accumulate_kernel<true, RefNoDetail>), dim3((unsigned)(n * nchunks)), dim3(REFINE_CHUNK), lds_bytes, c->stream, a,
+                                   (const RefHyp*)d_hyp, w.d_part, RefNoDetail());
             else
-                hipLaunchKernelGGL(refine_accumulate_kernel<false>, dim3((unsigned)(n * nchunks)), dim3(REFINE_CHUNK), 0, c->stream, a, (const RefHyp*)d_hyp, w.d_part);
+                hipLaunchKernelGGL(HIP_KERNEL_NAME(refine_accumulate_kernel<false, RefNoDetail>), dim3((unsigned)(n * nchunks)), dim3(REFINE_CHUNK), 0, c->stream, a,
+                                   (const RefHyp*)d_hyp, w.d_part, RefNoDetail());
             STOCS_HIP_CHECK(hipGetLastError());
         }
-        hipLaunchKernelGGL(refine_solve_kernel, dim3((unsigned)n), dim3(64), 0, c->stream, d_hyp, (const double*)w.d_part, nchunks);
+        hipLaunchKernelGGL(refine_solve_kernel<RefNoDetail>, dim3((unsigned)n), dim3(64), 0, c->stream, d_hyp, (const double*)w.d_part, nchunks, RefNoDetail());
         STOCS_HIP_CHECK(hipGetLastError());
     }
     hipLaunchKernelGGL(refine_final_kernel, dim3(hblocks), dim3(64), 0, c->stream, (const float*)w.d_Tin, (const RefHyp*)d_hyp, n, c->centroid_scene,
@@ -467,7 +497,7 @@ using namespace stocs;
 extern "C" void stocs_internal_free_refine(stocs_ctx* c) {
     if (!c || !c->refine) return;
     RefineState* S = (RefineState*)c->refine;
-    S->g.mem.free(); S->work.free();
+    S->g.mem.free(); S->work.free(); S->detail.free();
     delete S;
     c->refine = NULL;
 }
@@ -527,5 +557,66 @@ extern "C" int stocs_refine_poses(stocs_ctx* c, const float* T16_in, int n, cons
     if (lcp_out) memcpy(lcp_out, o + (size_t)n * 128, (size_t)n * 4);
     if (n_corr_out) memcpy(n_corr_out, o + (size_t)n * 132, (size_t)n * 4);
     if (iterations_out) memcpy(iterations_out, o + (size_t)n * 136, (size_t)n * 4);
+    return STOCS_OK;
+}
+
+extern "C" int stocs_refine_detail(stocs_ctx* c, const float* T16_in, const int32_t* src_idx, int n_src, float max_correspondence_distance, int32_t* match,
+                                   uint8_t* counted, double* sums28) {
+    if (!c) { set_error("stocs_refine_detail: NULL context"); return STOCS_ERR_INVALID; }
+    if (n_src < 0) { set_error("stocs_refine_detail: negative size (n_src %d)", n_src); return STOCS_ERR_INVALID; }
+    if (!T16_in) { set_error("stocs_refine_detail: NULL hypothesis"); return STOCS_ERR_INVALID; }
+    if (!(max_correspondence_distance > 0.0f) || !isfinite(max_correspondence_distance)) {
+        set_error("stocs_refine_detail: correspondence distance %g must be positive and finite", (double)max_correspondence_distance);
+        return STOCS_ERR_INVALID;
+    }
+    if (c->nS <= 0) { set_error("stocs_refine_detail: the context has no scene"); return STOCS_ERR_STATE; }
+    if (src_idx)
+        for (int i = 0; i < n_src; ++i)
+            if (src_idx[i] < 0 || src_idx[i] >= c->nS) { set_error("stocs_refine_detail: src_idx[%d] = %d outside [0, %d)", i, src_idx[i], c->nS); return STOCS_ERR_INVALID; }
+    const int nsrc = src_idx ? n_src : c->nS;
+    if (nsrc > 0 && (!match || !counted)) { set_error("stocs_refine_detail: NULL output"); return STOCS_ERR_INVALID; }
+    DeviceGuard dev_guard(c->device);
+    RefineWork w;
+    {
+        const int rc = refine_prepare(c, 1, nsrc, max_correspondence_distance, &w);
+        if (rc) return rc;
+    }
+    RefineState* S = (RefineState*)c->refine;
+    Carve cv;
+    const size_t o_match = cv.take((size_t)std::max(nsrc, 1) * 4), o_cnt = cv.take((size_t)std::max(nsrc, 1)), o_sums = cv.take(28 * 8);
+    { const int rc = S->detail.grow(c->stream, cv.total); if (rc) return rc; }
+    int32_t* d_match = Carve::at<int32_t>(S->detail.p, o_match);
+    uint8_t* d_cnt = Carve::at<uint8_t>(S->detail.p, o_cnt);
+    double* d_sums = Carve::at<double>(S->detail.p, o_sums);
+    // a plain, synchronous path (a test and diagnosis facility): pageable copies, one hypothesis
+    STOCS_HIP_CHECK(hipMemcpyAsync(w.d_Tin, T16_in, 64, hipMemcpyHostToDevice, c->stream));
+    if (src_idx && nsrc) STOCS_HIP_CHECK(hipMemcpyAsync(w.d_idx, src_idx, (size_t)nsrc * 4, hipMemcpyHostToDevice, c->stream));
+    STOCS_HIP_CHECK(hipMemsetAsync(d_match, 0xFF, (size_t)std::max(nsrc, 1) * 4, c->stream));
+    STOCS_HIP_CHECK(hipMemsetAsync(d_cnt, 0, (size_t)std::max(nsrc, 1), c->stream));
+    STOCS_HIP_CHECK(hipMemsetAsync(d_sums, 0, 28 * 8, c->stream));   // (a frozen hypothesis is summed by nobody)
+    RefDetailOut det;
+    det.match = d_match; det.counted = d_cnt; det.sums28 = d_sums;
+    RefHyp* d_hyp = (RefHyp*)w.d_hyp;
+    hipLaunchKernelGGL(refine_init_kernel, dim3(1), dim3(64), 0, c->stream, (const float*)w.d_Tin, 1, (const int32_t*)NULL, d_hyp);
+    STOCS_HIP_CHECK(hipGetLastError());
+    size_t lds_bytes = 0;
+    const RefArgs a = refine_args(c, w, src_idx != NULL, max_correspondence_distance, &lds_bytes);
+    if (w.nchunks > 0) {
+        if (lds_bytes <= REFINE_LDS_BYTES)
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(refine_accumulate_kernel<true, RefDetailOut>), dim3((unsigned)w.nchunks), dim3(REFINE_CHUNK), lds_bytes, c->stream, a,
+                               (const RefHyp*)d_hyp, w.d_part, det);
+        else
+            hipLaunchKernelGGL(HIP_KERNEL_NAME(refine_accumulate_kernel<false, RefDetailOut>), dim3((unsigned)w.nchunks), dim3(REFINE_CHUNK), 0, c->stream, a,
+                               (const RefHyp*)d_hyp, w.d_part, det);
+        STOCS_HIP_CHECK(hipGetLastError());
+    }
+    hipLaunchKernelGGL(refine_solve_kernel<RefDetailOut>, dim3(1), dim3(64), 0, c->stream, d_hyp, (const double*)w.d_part, w.nchunks, det);
+    STOCS_HIP_CHECK(hipGetLastError());
+    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (nsrc) {
+        STOCS_HIP_CHECK(hipMemcpy(match, d_match, (size_t)nsrc * 4, hipMemcpyDeviceToHost));
+        STOCS_HIP_CHECK(hipMemcpy(counted, d_cnt, (size_t)nsrc, hipMemcpyDeviceToHost));
+    }
+    if (sums28) STOCS_HIP_CHECK(hipMemcpy(sums28, d_sums, 28 * 8, hipMemcpyDeviceToHost));
     return STOCS_OK;
 }

@@ -248,6 +248,19 @@ class StocsEstimator:
                                              nc.ctypes.data_as(capi._ip), it.ctypes.data_as(capi._ip)))
         return To, Po, lcp, nc, it
 
+    def refine_detail(self, T16, max_correspondence_distance=0.035, src_idx=None, sums=True):
+        """The refinement's first evaluation of one centred-frame hypothesis (stocs_refine_detail) -> (match (n_src,) model index or
+        -1, counted (n_src,) uint8, sums28 (28,) float64: A^T A upper triangle | A^T b | count, or None)."""
+        T, pT = capi.f32(T16)
+        assert T.size == 16
+        idx, pidx = (None, None) if src_idx is None else capi.i32(src_idx)
+        n = self.nS if idx is None else len(idx)
+        match = np.zeros(max(n, 1), np.int32); counted = np.zeros(max(n, 1), np.uint8)
+        s28 = np.zeros(28, np.float64) if sums else None
+        capi.check(self.L.stocs_refine_detail(self.h, pT, pidx, 0 if idx is None else n, max_correspondence_distance, match.ctypes.data_as(capi._ip),
+                                              counted.ctypes.data_as(capi._u8p), s28.ctypes.data_as(C.POINTER(C.c_double)) if sums else None))
+        return match[:n], counted[:n], s28
+
     def track_poses(self, priors_pose16_camera, rounds=TRACK_DEFAULTS["rounds"], samples=TRACK_DEFAULTS["samples"],
                     max_translation=TRACK_DEFAULTS["max_translation"], max_rotation_deg=TRACK_DEFAULTS["max_rotation_deg"], shrink=TRACK_DEFAULTS["shrink"],
                     seed=TRACK_DEFAULTS["seed"], refine_iterations=TRACK_DEFAULTS["refine_iterations"],

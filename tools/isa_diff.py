@@ -51,7 +51,8 @@ def pair_name(old):
             a = [a[0], a[6]]
         return "step<detail=%d split=%d>" % tuple(a)
     d = subprocess.run(["c++filt", old], capture_output=True, text=True).stdout.strip()
-    return re.sub(r"\(.*", "", d).replace("void ", "").replace("stocs::", "")
+    d = re.sub(r"\(.*", "", d).replace("void ", "").replace("stocs::", "")
+    return d.replace(", RefNoDetail>", ">").replace("<RefNoDetail>", "")   # refine.hip: the shipping forms carry an empty detail argument
 
 
 def main():
