@@ -642,6 +642,35 @@ public:
         return out;
     }
 
+    // Depth-image verification (stocs_ctx_set_frame / stocs_depth_check_poses; no reference counterpart): the camera frame this
+    // estimator's scene came from -- depth and, optionally, the object's class-probability image (may be NULL), image_height x
+    // image_width, row-major -- handed to the context once; then any number of camera-frame hypotheses (get_pose_candidates, the
+    // hypotheses of run_trials, track_poses' results) are scored against it in one GPU pass: one record per hypothesis, in input
+    // order.  Empty on error (the text goes to the log).
+    static stocs_depth_params default_depth_params() {
+        stocs_depth_params p;
+        stocs_default_depth_params(&p);
+        return p;
+    }
+    void set_frame(const uint16_t* depth, const uint16_t* class_probability_map, const std::vector<float>& camera_intrinsics, float read_depth_scale) {
+        if (camera_intrinsics.size() < 4) throw std::runtime_error("camera_intrinsics must hold {fx, cx, fy, cy}");
+        stocs_camera cam;
+        cam.fx = camera_intrinsics[0]; cam.cx = camera_intrinsics[1]; cam.fy = camera_intrinsics[2]; cam.cy = camera_intrinsics[3];
+        cam.depth_scale = read_depth_scale; cam.width = image_width; cam.height = image_height; cam.normal_method = STOCS_NORMALS_DEPTH_GRADIENT;
+        if (stocs_ctx_set_frame(ctx_, &cam, depth, class_probability_map) != STOCS_OK) throw std::runtime_error(std::string("stocs_ctx_set_frame: ") + stocs_last_error());
+    }
+    std::vector<stocs_depth_result> depth_check_poses(const std::vector<PoseCandidate*>& poses, const stocs_depth_params& prm = default_depth_params()) {
+        const int n = (int)poses.size();
+        std::vector<float> P((size_t)n * 16);
+        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], poses[(size_t)i]->transform.data(), 64);
+        std::vector<stocs_depth_result> r((size_t)n);
+        if (n > 0 && stocs_depth_check_poses(ctx_, P.data(), n, &prm, r.data()) != STOCS_OK) {
+            *log_ << "depth_check_poses failed: " << stocs_last_error() << std::endl;
+            r.clear();
+        }
+        return r;
+    }
+
 protected:
     std::vector<std::unique_ptr<PoseCandidate> > tracked_store_;   // results of the last track_poses
     std::unique_ptr<PoseCandidate> trial_best_;

@@ -420,6 +420,56 @@ int stocs_track_poses(stocs_ctx* ctx, const float* prior_pose16_camera, int n_pr
  * an output given and cap < samples: STOCS_ERR_CAPACITY (*n set; NULL outputs query the count). */
 int stocs_track_get_round(stocs_ctx* ctx, int prior, int round, float* T16_centred, float* lcp, int cap, int* n);
 
+/* ---- depth-image verification of pose hypotheses (no reference counterpart: the reference scores by LCP alone, which only rewards;
+ * the host restatement this replaces is tools/pose_check.py::depth_agreement).  stocs_ctx_set_frame hands over the camera frame the
+ * context's scene came from: depth (height*width uint16, row-major) and, optionally, the object's class-probability image (may be
+ * NULL), copied to the device and kept until the next stocs_ctx_set_frame / stocs_ctx_destroy.  Independent of stocs_ctx_set_scene
+ * (the caller keeps the two in step).  cam->normal_method is ignored.  NULL ctx / cam / depth, width or height < 1:
+ * STOCS_ERR_INVALID.  Synchronises once.
+ * stocs_depth_check_poses scores n CAMERA-frame poses (column-major, as stocs_get_candidates, stocs_trial_hypothesis::pose16 /
+ * refined_pose16 and stocs_track_result::pose16 give them) against that frame in one launch.  A pose acts on the model positions as
+ * handed to stocs_ctx_create and on the context's unit normals (normalised as Point3D::set_normal does).  Per hypothesis P and
+ * model point m with normal k, all in float, every operation a single IEEE add / sub / mul / div / floor, no contraction
+ * (R_ab = P[4b + a], t_a = P[12 + a]):
+ *   1. p_a = (R_a0 m_x + (R_a1 m_y + R_a2 m_z)) + t_a,   q_a = R_a0 k_x + (R_a1 k_y + R_a2 k_z)
+ *   2. facing <=> (q_0 p_0 + (q_1 p_1 + q_2 p_2)) < 0 and p_2 > 1e-6f (comparisons with NaN are false).  A pose with a non-finite
+ *      entry among the twelve R_ab, t_a gives an all-zero record; so does an all-zero pose (a "no pose" record of a trial batch):
+ *      neither is an error.
+ *   3. a = floorf(((fx p_0) / p_2 + cx) + 0.5f), b = floorf(((fy p_1) / p_2 + cy) + 0.5f);
+ *      in_image <=> facing and 0 <= a < (float)width and 0 <= b < (float)height, tested on the floats; then col = (int)a, row = (int)b.
+ *   4. self_occlusion == 1: over the in_image points c0 / c1 / r0 / r1 are the min and max of col and row; the stride is
+ *      s = max(cell_px, ceil(max(c1 - c0 + 1, r1 - r0 + 1) / 64)) in integers, a point's cell ((row - r0) / s) * 64 + (col - c0) / s
+ *      on a 64 x 64 grid, zmin[cell] the minimum p_2 of the cell's points; self_occluded <=> p_2 > zmin[cell] + occlusion_margin.
+ *      self_occlusion == 0: nothing is self-occluded.
+ *   5. for the remaining in_image points: raw = depth[row * width + col]; no_depth <=> raw == 0; otherwise zo = (float)raw * depth_scale
+ *      (the expression of the scene ingest's back-projection) and d = p_2 - zo:  agree <=> fabsf(d) <= tolerance;  in_front <=> d <
+ *      -tolerance (the camera measured a surface BEHIND where the model should have been: a free-space violation);  behind <=> d >
+ *      tolerance (hidden by something else: neutral).
+ *   6. on_mask <=> agree, a class image is present and !(cp < class_threshold), cp = (float)((double)class_prob[row * width + col] *
+ *      (1.0 / 10000)) as stocs_ingest_scene forms it.
+ * Hence facing >= in_image == self_occluded + no_depth + agree + in_front + behind.  All counts are integer sums and the z-buffer is
+ * a minimum: a hypothesis's record is bitwise independent of the batch it shares and of its position in it, and a float32
+ * restatement of the six steps reproduces every count (tests/depth_check_ref.py).
+ * n == 0: no-op.  NULL ctx / p / out / poses with n > 0, n < 0, a parameter outside the ranges below, a camera width or height
+ * < 1: STOCS_ERR_INVALID; no frame set, or a frame whose width * height differs from what was uploaded: STOCS_ERR_STATE.  Its own
+ * grow-only workspace on the context (a second call of the same size allocates nothing); one pinned read-back and one
+ * synchronisation per call.  Known limit: one workgroup per hypothesis, so with n far below the number of compute units a call is
+ * latency-bound. ---- */
+int stocs_ctx_set_frame(stocs_ctx* ctx, const stocs_camera* cam, const uint16_t* depth, const uint16_t* class_prob);
+typedef struct stocs_depth_params {
+    float   tolerance;          /* m, > 0 finite: |model z - observed z| <= tolerance agrees (default 0.01)          */
+    float   class_threshold;    /* finite, as stocs_ingest_scene's (default 0.10); unused without a class image      */
+    int32_t self_occlusion;     /* 0: off; 1: per-hypothesis z-buffer (default 1)                                    */
+    int32_t cell_px;            /* >= 1: smallest z-buffer cell edge in pixels (default 8)                           */
+    float   occlusion_margin;   /* m, >= 0 finite: a point farther than its cell's nearest + margin is hidden (0.01) */
+} stocs_depth_params;
+typedef struct stocs_depth_result {
+    int32_t facing, in_image, self_occluded, no_depth, agree, in_front, behind, on_mask;
+    float   score, violation;   /* (float)agree / (float)facing, (float)in_front / (float)facing; 0 when facing == 0 */
+} stocs_depth_result;
+void stocs_default_depth_params(stocs_depth_params* p);
+int stocs_depth_check_poses(stocs_ctx* ctx, const float* pose16_camera, int n, const stocs_depth_params* p, stocs_depth_result* out);
+
 /* ---- tuning knobs (never change results beyond float summation order).
  * "lcp_variant": 99 = automatic (default): the scan fed from a per-wavefront LDS queue of the queries that have a list -- over
  *   index-ordered lists at cell edge epsilon (24, sparse scenes), over centre-sorted lists with triangle-inequality early exit

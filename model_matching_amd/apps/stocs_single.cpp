@@ -22,6 +22,10 @@
 // row-major) -- a local search around it on this frame (stocs_track_poses, the façade's default parameters); when the tracked lcp is
 // below x (default 0.02: a prior that has lost the object scores ~0) the usual detection runs instead.  Prints which route produced
 // the pose ("track: route=tracked ..." / "track: route=detection ...") and writes <out> as detection does.
+// --depth-check (with --trials N --cluster 1 [--refine K], a scene directory): every trial's hypotheses -- the refined poses when
+// refinement ran -- scored against the frame's own depth image and class-probability map (stocs_depth_check_poses); one "depth t.i:"
+// line per hypothesis, and <out> is written from the first maximum of score - violation (ties: the higher lcp, then the lower trial
+// and hypothesis index) instead of the LCP winner.  Every other line is what the run prints without the flag.
 // The reference edits its per-data-set constants in the source (README.md:42-66); here they are options with the
 // reference's YCB values as defaults.
 #include <algorithm>
@@ -73,7 +77,7 @@ static bool read_stcl(const std::string& path, std::vector<float>& pos, std::vec
 
 // everything after the estimator is built (:79-185): one run, or n_trials in one batch; lines to os, the pose to out_path
 static int run_search(stocs::stocs_estimator& stocs_ptr, std::ostream& os, const std::string& out_path, const std::string& dbg_dir, uint64_t seed, int n_trials,
-                      int exact_ties, int do_cluster, int n_refine) {
+                      int exact_ties, int do_cluster, int n_refine, int depth_check = 0) {
     stocs_ptr.set_seed(seed);
     if (exact_ties) stocs_ptr.set_exact_ties(true);
 
@@ -135,6 +139,43 @@ static int run_search(stocs::stocs_estimator& stocs_ptr, std::ostream& os, const
             os << "no pose found" << std::endl;
         }
         os << tl << std::endl;
+        if (depth_check) {
+            const std::vector<std::vector<PoseCandidate*> >& src = n_refine > 0 ? refined : hyps;
+            std::vector<PoseCandidate*> flat;
+            std::vector<std::pair<int, int> > id;
+            for (size_t t = 0; t < src.size(); ++t)
+                for (size_t i = 0; i < src[t].size(); ++i) { flat.push_back(src[t][i]); id.push_back(std::make_pair((int)t, (int)i)); }
+            const std::vector<stocs_depth_result> dr = stocs_ptr.depth_check_poses(flat);
+            if (dr.size() != flat.size()) { std::cerr << "depth check failed: " << stocs_last_error() << std::endl; return 2; }
+            int w = -1;
+            for (size_t k = 0; k < dr.size(); ++k) {
+                char b[384];
+                snprintf(b, sizeof(b), "  depth %d.%d: facing %d in_image %d self_occluded %d no_depth %d agree %d in_front %d behind %d on_mask %d score %.9g violation %.9g lcp %.9g",
+                         id[k].first, id[k].second, dr[k].facing, dr[k].in_image, dr[k].self_occluded, dr[k].no_depth, dr[k].agree, dr[k].in_front, dr[k].behind,
+                         dr[k].on_mask, (double)dr[k].score, (double)dr[k].violation, (double)flat[k]->lcp);
+                os << b << std::endl;
+                // first maximum of score - violation; on a tie the higher lcp; then the lower (trial, hypothesis), i.e. the earlier k
+                const float key = dr[k].score - dr[k].violation;
+                if (w < 0 || key > dr[(size_t)w].score - dr[(size_t)w].violation ||
+                    (key == dr[(size_t)w].score - dr[(size_t)w].violation && flat[k]->lcp > flat[(size_t)w]->lcp))
+                    w = (int)k;
+            }
+            if (w >= 0) {
+                const PoseCandidate* bp = flat[(size_t)w];
+                std::ofstream o(out_path, std::ofstream::out);
+                for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) o << bp->transform(r, c) << (r == 2 && c == 3 ? "" : " ");
+                o << std::endl;
+                os << "depth pose:";
+                for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) { char b[32]; snprintf(b, sizeof(b), " %.9g", (double)bp->transform(r, c)); os << b; }
+                os << std::endl;
+                char b[256];
+                snprintf(b, sizeof(b), "depth check: hypotheses=%d best_trial=%d best_hypothesis=%d score=%.9g violation=%.9g lcp=%.9g", (int)dr.size(), id[(size_t)w].first,
+                         id[(size_t)w].second, (double)dr[(size_t)w].score, (double)dr[(size_t)w].violation, (double)bp->lcp);
+                os << b << std::endl;
+            } else {
+                os << "depth check: hypotheses=0" << std::endl;
+            }
+        }
         return 0;
     }
 
@@ -320,9 +361,11 @@ int main(int argc, char** argv) {
     if (const char* e = getenv("STOCS_REPO_PATH")) repo_path = e;
     std::string edge_path, out_path, dbg_dir, track_path;
     float track_min_lcp = 0.02f;
-    int do_cluster = 0, n_trials = 0, exact_ties = 0, n_refine = 0;
+    int do_cluster = 0, n_trials = 0, exact_ties = 0, n_refine = 0, depth_check = 0;
     uint64_t seed = 1;
-    for (int i = clouds ? 4 : 3; i + 1 < argc; i += 2) {
+    for (int i = clouds ? 4 : 3; i < argc; i += 2) {
+        if (std::string(argv[i]) == "--depth-check") { depth_check = 1; --i; continue; }   // the one option without a value
+        if (i + 1 >= argc) break;
         const std::string k = argv[i], v = argv[i + 1];
         if (k == "--edge") edge_path = v;
         else if (k == "--seed") seed = strtoull(v.c_str(), NULL, 10);
@@ -346,6 +389,11 @@ int main(int argc, char** argv) {
     }
 
     if (n_refine < 0 || (n_refine > 0 && !do_cluster)) { std::cerr << "--refine N needs N >= 0 and --cluster 1" << std::endl; return -1; }
+
+    if (depth_check && (clouds || n_trials <= 0 || !do_cluster || !track_path.empty() || a2.find(',') != std::string::npos)) {
+        std::cerr << "--depth-check needs a scene directory, a single object, --trials N and --cluster 1" << std::endl;
+        return -1;
+    }
 
     if (!clouds && a2.find(',') != std::string::npos) {
         std::vector<std::string> objects;
@@ -398,11 +446,17 @@ int main(int argc, char** argv) {
             est.reset(new stocs::stocs_estimator(model_path, model_map, rgb_path, depth_path, class_probability_path, edge_probability_path, dbg_dir, cam_intrinsics,
                                                  image_width, image_height, depth_scale, 1.0f, voxel_size, distance_threshold, ppf_tr_discretization,
                                                  ppf_rot_discretization, edge_threshold, class_threshold));
+            if (depth_check) {   // the frame the scene was ingested from, for stocs_depth_check_poses
+                std::vector<uint16_t> depth, prob;
+                stocs::read_image(depth_path, 1, 16, image_width, image_height, &depth);
+                stocs::read_image(class_probability_path, 1, 16, image_width, image_height, &prob);
+                est->set_frame(depth.data(), prob.data(), cam_intrinsics, depth_scale);
+            }
         }
     } catch (const std::exception& e) {
         std::cerr << e.what() << std::endl;  // no GPU => loud failure, never a CPU fallback
         return 2;
     }
     if (!track_path.empty()) return run_track(*est, track_path, track_min_lcp, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine);
-    return run_search(*est, std::cout, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine);
+    return run_search(*est, std::cout, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine, depth_check);
 }

@@ -54,6 +54,16 @@ class TrackResult(C.Structure):
                 ("n_correspondences", C.c_int32), ("iterations", C.c_int32)]
 
 
+class DepthParams(C.Structure):
+    _fields_ = [("tolerance", C.c_float), ("class_threshold", C.c_float), ("self_occlusion", C.c_int32), ("cell_px", C.c_int32),
+                ("occlusion_margin", C.c_float)]
+
+
+class DepthResult(C.Structure):
+    _fields_ = [("facing", C.c_int32), ("in_image", C.c_int32), ("self_occluded", C.c_int32), ("no_depth", C.c_int32), ("agree", C.c_int32),
+                ("in_front", C.c_int32), ("behind", C.c_int32), ("on_mask", C.c_int32), ("score", C.c_float), ("violation", C.c_float)]
+
+
 class Camera(C.Structure):
     _fields_ = [("fx", C.c_float), ("cx", C.c_float), ("fy", C.c_float), ("cy", C.c_float), ("depth_scale", C.c_float),
                 ("width", C.c_int), ("height", C.c_int), ("normal_method", C.c_int)]
@@ -132,6 +142,9 @@ SIGNATURES = {
     "stocs_refine_detail": (C.c_int, [_vp, _fp, _ip, C.c_int, C.c_float, _ip, _u8p, C.POINTER(C.c_double)]),
     "stocs_track_poses": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(TrackParams), C.POINTER(TrackResult)]),
     "stocs_track_get_round": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, C.c_int, _intp]),
+    "stocs_ctx_set_frame": (C.c_int, [_vp, C.POINTER(Camera), C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
+    "stocs_default_depth_params": (None, [C.POINTER(DepthParams)]),
+    "stocs_depth_check_poses": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(DepthParams), C.POINTER(DepthResult)]),
     "stocs_device_alloc_count": (C.c_int64, []),
     "stocs_debug_stream_audit_selftest": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     "stocs_debug_streams_overlap": (C.c_int, [_vp]),

@@ -351,6 +351,8 @@ struct stocs_ctx {
     // scratch
     void* d_scratch;
     size_t scratch_bytes;
+
+    void* depth;    // depth.hip (DepthState): the frame of stocs_ctx_set_frame and stocs_depth_check_poses's grow-only workspace (last: no other member moves)
 };
 
 namespace stocs {
@@ -400,6 +402,7 @@ extern "C" void stocs_internal_free_instance(stocs_ctx* c);
 extern "C" void stocs_internal_free_trials(stocs_ctx* c);
 extern "C" void stocs_internal_free_refine(stocs_ctx* c);
 extern "C" void stocs_internal_free_track(stocs_ctx* c);
+extern "C" void stocs_internal_free_depth(stocs_ctx* c);
 // the congruent phase with a ceiling on its device memory: *too_big != 0 (and STOCS_OK) when the pair lists of the context's base set
 // would need more than max_bytes (0: no ceiling) or exceed 2^32 entries -- a trial batch then splits the base set and tries again
 extern "C" int stocs_internal_find_congruent(stocs_ctx* c, int64_t* total_quads, size_t max_bytes, int* too_big);

@@ -36,6 +36,9 @@ assert _HYP_DTYPE.itemsize == C.sizeof(capi.TrialHypothesis)
 _TRACK_DTYPE = np.dtype([("prior_lcp", np.float32), ("lcp", np.float32), ("pose16", np.float32, 16), ("refined_lcp", np.float32), ("refined_pose16", np.float32, 16),
                          ("n_correspondences", np.int32), ("iterations", np.int32)])
 assert _TRACK_DTYPE.itemsize == C.sizeof(capi.TrackResult)
+_DEPTH_DTYPE = np.dtype([("facing", np.int32), ("in_image", np.int32), ("self_occluded", np.int32), ("no_depth", np.int32), ("agree", np.int32),
+                         ("in_front", np.int32), ("behind", np.int32), ("on_mask", np.int32), ("score", np.float32), ("violation", np.float32)])
+assert _DEPTH_DTYPE.itemsize == C.sizeof(capi.DepthResult)
 
 # defaults of track_poses (tools/track_time.py's sweep, profiles/track_time.json)
 TRACK_DEFAULTS = dict(rounds=6, samples=2048, max_translation=0.02, max_rotation_deg=10.0, shrink=0.7, seed=0, refine_iterations=0,
@@ -275,6 +278,38 @@ class StocsEstimator:
         buf = (capi.TrackResult * max(n, 1))()
         capi.check(self.L.stocs_track_poses(self.h, pP, n, C.byref(prm), buf))
         return np.frombuffer(buf, dtype=_TRACK_DTYPE, count=n).copy()
+
+    def set_frame(self, depth_u16, prob_u16, K, depth_scale):
+        """The camera frame this context's scene came from (stocs_ctx_set_frame): depth (height, width) uint16, the object's
+        class-probability image of the same shape or None, K = (fx, cx, fy, cy), metres per depth unit.  Kept on the device until the
+        next set_frame; independent of set_scene."""
+        d = np.ascontiguousarray(depth_u16, np.uint16)
+        if d.ndim != 2:
+            raise ValueError("depth image must be (height, width)")
+        pp = None
+        if prob_u16 is not None:
+            p = np.ascontiguousarray(prob_u16, np.uint16)
+            if p.shape != d.shape:
+                raise ValueError("class-probability image %s does not match the depth image %s" % (p.shape, d.shape))
+            pp = p.ctypes.data_as(C.POINTER(C.c_uint16))
+        cam = capi.Camera(float(K[0]), float(K[1]), float(K[2]), float(K[3]), float(depth_scale), d.shape[1], d.shape[0], 0)
+        capi.check(self.L.stocs_ctx_set_frame(self.h, C.byref(cam), d.ctypes.data_as(C.POINTER(C.c_uint16)), pp))
+
+    def depth_check_poses(self, poses16, **params):
+        """n camera-frame poses (column-major 16 floats each) against the frame of set_frame (stocs_depth_check_poses) -> a structured
+        array with the fields of stocs_depth_result, one record per pose.  params: fields of stocs_depth_params (tolerance,
+        class_threshold, self_occlusion, cell_px, occlusion_margin) over the library's defaults."""
+        P, pP = capi.f32(poses16)
+        n = P.size // 16
+        prm = capi.DepthParams()
+        self.L.stocs_default_depth_params(C.byref(prm))
+        for k, v in params.items():
+            if k not in dict(capi.DepthParams._fields_):
+                raise TypeError("depth_check_poses: unknown parameter %r" % k)
+            setattr(prm, k, v)
+        buf = (capi.DepthResult * max(n, 1))()
+        capi.check(self.L.stocs_depth_check_poses(self.h, pP, n, C.byref(prm), buf))
+        return np.frombuffer(buf, dtype=_DEPTH_DTYPE, count=n).copy()
 
     def track_round(self, prior, round):
         """-> (T16_centred (samples, 16), lcp (samples,)) of one round of one prior of the last track_poses(keep_details=True)."""
