@@ -266,6 +266,24 @@ int stocs_allreduce_best(stocs_comm* comm, void* hip_stream, uint64_t* key_inout
 int stocs_cluster_poses(const float* poses16, const float* lcp, int n, float acceptable_fraction,
                         float best_score, int maximum_pose_count, float min_distance, float min_angle,
                         const float* sym3, int32_t* out_idx, int cap, int* n_out);
+/* ---- the device clustering of trial batches (csrc/cluster.hip, trial_cluster_kernel) on candidates the caller gives: the kernel
+ * stocs_run_trials_post runs, through the same launcher, without the rest of a batch.  poses16: N x 16 camera-frame, column-major;
+ * lcp: N scores; cand_off: n_trials + 1 offsets into both, cand_off[0] = 0, not decreasing, N = cand_off[n_trials]; best_score[t]:
+ * trial t's best_lcp as the batch's arg-max leaves it (its largest positive score, 0 when it has none).  Trial t's result is, bit for
+ * bit, stocs_cluster_poses(its poses, its lcp, n_t, acceptable_fraction, best_score[t], ...): out_cnt[t] indices (local to the trial)
+ * at out_idx[out_off[t] ..], in cluster order.  out_off[t + 1] - out_off[t] = min(maximum_pose_count + 1, n_t) slots as in
+ * stocs_run_trials_post; slots past the count keep the -1 they are filled with before the launch.  out_cap: entries out_idx holds
+ * (too few: STOCS_ERR_CAPACITY, out_off is valid).  round0_survivors (n_trials, may be NULL): per trial, how many candidates the
+ * kernel's first pass let through (lcp > acceptable_fraction * best_score[t]) -- at most 2048 and the later rounds walk the list in
+ * LDS, above it the flags in global memory.  Taken from the flags of a launch with count 0 in front of the real one.
+ * DOMAIN: every lcp and best_score is +0 or above, or NaN (never a survivor).  Negative scores and -0.0 are STOCS_ERR_INVALID: the
+ * pipeline cannot produce them, and the arg-max key orders the scores' bits as unsigned integers.  Also STOCS_ERR_INVALID, with a
+ * message: a NULL argument, n_trials < 0, maximum_pose_count < 0, a NaN fraction, a min_distance / min_angle that is <= 0 or not
+ * finite, offsets that decrease or do not start at 0.  n_trials = 0 is STOCS_OK (out_off[0] = 0).  Synchronises once; a test and
+ * diagnosis facility (pageable copies). ---- */
+int stocs_cluster_trials_device(stocs_ctx* ctx, const float* poses16, const float* lcp, const int32_t* cand_off, const float* best_score, int n_trials,
+                                float acceptable_fraction, int maximum_pose_count, float min_distance, float min_angle, const float* sym3,
+                                int32_t* out_off, int32_t* out_cnt, int32_t* out_idx, int out_cap, int32_t* round0_survivors);
 
 /* ---- upstream rows, GPU implementations.  PARITY WITH THE REFERENCE IS UNPINNED:
  * their arithmetic lives in PCL / OpenCV-contrib, absent here; these are pinned against this repo's

@@ -132,6 +132,7 @@ SIGNATURES = {
     "stocs_comm_destroy": (C.c_int, [_vp]),
     "stocs_allreduce_best": (C.c_int, [_vp, _vp, C.POINTER(C.c_uint64), _fp, C.c_uint32]),
     "stocs_cluster_poses": (C.c_int, [_fp, _fp, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, C.c_float, _fp, _ip, C.c_int, _intp]),
+    "stocs_cluster_trials_device": (C.c_int, [_vp, _fp, _fp, _ip, _fp, C.c_int, C.c_float, C.c_int, C.c_float, C.c_float, _fp, _ip, _ip, _ip, C.c_int, _ip]),
     "stocs_ingest_scene": (C.c_int, [C.POINTER(Camera), C.POINTER(C.c_uint16), C.POINTER(C.c_uint16), C.c_float, C.c_float, C.c_int, _fp, _fp, _fp, _ip, C.c_int, _intp]),
     "stocs_ingest_scene_multi": (C.c_int, [C.POINTER(Camera), C.POINTER(C.c_uint16), C.c_int, C.POINTER(C.c_uint16), _fp, C.c_float, C.c_int, _fp, _fp, _fp, _ip,
                                            C.c_int, _ip]),

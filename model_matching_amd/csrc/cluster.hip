@@ -9,6 +9,7 @@
 // kept cluster, and every survivor within the thresholds of it (get_pose_diff(survivor, cluster), the host's argument order) drops
 // out.  Same decisions as the host function, rounds = kept clusters.
 #include <math.h>
+#include <string.h>
 
 #include <algorithm>
 #include <vector>
@@ -151,4 +152,81 @@ extern "C" int stocs_cluster_poses(const float* poses16, const float* lcp, int n
     *n_out = (int)kept.size();
     for (size_t i = 0; i < kept.size() && (int)i < cap; ++i) out_idx[i] = kept[i];
     return ((int)kept.size() > cap && out_idx) ? STOCS_ERR_CAPACITY : STOCS_OK;
+}
+
+// The device clustering on its own (a test and diagnosis facility: pageable copies, one synchronisation).  The kernel and its launcher
+// are the pipeline's; this only puts the caller's arrays where post_piece finds the batch's.
+static bool score_in_domain(float v) { return v != v || !signbit(v); }   // +0 and above, or NaN
+
+extern "C" int stocs_cluster_trials_device(stocs_ctx* c, const float* poses16, const float* lcp, const int32_t* cand_off, const float* best_score, int n_trials,
+                                           float acceptable_fraction, int maximum_pose_count, float min_distance, float min_angle, const float* sym3,
+                                           int32_t* out_off, int32_t* out_cnt, int32_t* out_idx, int out_cap, int32_t* round0_survivors) {
+    const char* me = "stocs_cluster_trials_device";
+    if (!c) { set_error("%s: NULL context", me); return STOCS_ERR_INVALID; }
+    if (n_trials < 0) { set_error("%s: negative size (n_trials %d)", me, n_trials); return STOCS_ERR_INVALID; }
+    if (!cand_off || !sym3 || !out_off || (n_trials && (!best_score || !out_cnt))) { set_error("%s: NULL argument", me); return STOCS_ERR_INVALID; }
+    if (maximum_pose_count < 0) { set_error("%s: maximum_pose_count %d < 0", me, maximum_pose_count); return STOCS_ERR_INVALID; }
+    if (acceptable_fraction != acceptable_fraction) { set_error("%s: acceptable_fraction is NaN", me); return STOCS_ERR_INVALID; }
+    if (!(min_distance > 0.0f) || !isfinite(min_distance)) { set_error("%s: min_distance %g must be positive and finite", me, (double)min_distance); return STOCS_ERR_INVALID; }
+    if (!(min_angle > 0.0f) || !isfinite(min_angle)) { set_error("%s: min_angle %g must be positive and finite", me, (double)min_angle); return STOCS_ERR_INVALID; }
+    if (out_cap < 0) { set_error("%s: negative capacity (out_cap %d)", me, out_cap); return STOCS_ERR_INVALID; }
+    if (cand_off[0] != 0) { set_error("%s: cand_off[0] = %d, not 0", me, cand_off[0]); return STOCS_ERR_INVALID; }
+    for (int t = 0; t < n_trials; ++t)
+        if (cand_off[t + 1] < cand_off[t]) { set_error("%s: cand_off decreases at trial %d (%d -> %d)", me, t, cand_off[t], cand_off[t + 1]); return STOCS_ERR_INVALID; }
+    const size_t N = (size_t)cand_off[n_trials], nT = (size_t)n_trials;
+    if (N && (!poses16 || !lcp)) { set_error("%s: NULL candidates", me); return STOCS_ERR_INVALID; }
+    for (size_t i = 0; i < N; ++i)
+        if (!score_in_domain(lcp[i])) { set_error("%s: lcp[%zu] = %g is negative (scores are +0 and above, or NaN)", me, i, (double)lcp[i]); return STOCS_ERR_INVALID; }
+    for (size_t t = 0; t < nT; ++t)
+        if (!score_in_domain(best_score[t])) { set_error("%s: best_score[%zu] = %g is negative", me, t, (double)best_score[t]); return STOCS_ERR_INVALID; }
+    out_off[0] = 0;
+    for (size_t t = 0; t < nT; ++t) {
+        const long long next = (long long)out_off[t] + trial_hyp_slots(maximum_pose_count, (long long)(cand_off[t + 1] - cand_off[t]));
+        if (next > 0x7FFFFFFFll) { set_error("%s: more than 2^31 - 1 hypothesis slots", me); return STOCS_ERR_INVALID; }
+        out_off[t + 1] = (int32_t)next;
+    }
+    const size_t H = (size_t)out_off[nT];
+    if (H > (size_t)out_cap || (H && !out_idx)) { set_error("%s: out_idx holds %d entries, %zu are needed", me, out_idx ? out_cap : 0, H); return out_idx ? STOCS_ERR_CAPACITY : STOCS_ERR_INVALID; }
+    if (n_trials == 0) return STOCS_OK;
+    DeviceGuard dev_guard(c->device);
+    Carve cv;
+    const size_t o_P = cv.take(N * 64), o_lcp = cv.take(N * 4), o_coff = cv.take((nT + 1) * 4), o_b18 = cv.take(nT * 18 * 4), o_hoff = cv.take((nT + 1) * 4),
+                 o_cnt = cv.take(nT * 4), o_idx = cv.take(H * 4), o_alive = cv.take(N);
+    if (int rc = ensure_scratch(c, cv.total + 256)) return rc;
+    void* d = c->d_scratch;
+    float* d_P = Carve::at<float>(d, o_P); float* d_lcp = Carve::at<float>(d, o_lcp); int32_t* d_coff = Carve::at<int32_t>(d, o_coff);
+    float* d_b18 = Carve::at<float>(d, o_b18); int32_t* d_hoff = Carve::at<int32_t>(d, o_hoff); int32_t* d_cnt = Carve::at<int32_t>(d, o_cnt);
+    int32_t* d_idx = Carve::at<int32_t>(d, o_idx); uint8_t* d_alive = Carve::at<uint8_t>(d, o_alive);
+    std::vector<float> b18(nT * 18, 0.0f);   // (key lo, key hi, pose[16]) per trial; the kernel reads the score in slot 1 alone
+    for (size_t t = 0; t < nT; ++t) b18[t * 18 + 1] = best_score[t];
+    if (N) {
+        STOCS_HIP_CHECK(hipMemcpyAsync(d_P, poses16, N * 64, hipMemcpyHostToDevice, c->stream));
+        STOCS_HIP_CHECK(hipMemcpyAsync(d_lcp, lcp, N * 4, hipMemcpyHostToDevice, c->stream));
+    }
+    STOCS_HIP_CHECK(hipMemcpyAsync(d_coff, cand_off, (nT + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    STOCS_HIP_CHECK(hipMemcpyAsync(d_b18, b18.data(), nT * 18 * 4, hipMemcpyHostToDevice, c->stream));
+    STOCS_HIP_CHECK(hipMemcpyAsync(d_hoff, out_off, (nT + 1) * 4, hipMemcpyHostToDevice, c->stream));
+    TrialClusterArgs a;
+    a.fraction = acceptable_fraction; a.count = maximum_pose_count; a.min_distance = min_distance; a.min_angle = min_angle;
+    for (int k = 0; k < 3; ++k) a.sym[k] = sym3[k];
+    // The survivors of round 0, as the kernel itself decides them: with count 0 it stops after its first pass, and `alive` then holds
+    // exactly that pass's flags (the full run below overwrites them on the path that walks them).
+    std::vector<uint8_t> alive0(round0_survivors ? N : 0);
+    if (round0_survivors) {
+        TrialClusterArgs probe = a; probe.count = 0;
+        if (int rc = enqueue_trial_cluster(c, n_trials, d_P, d_lcp, d_coff, d_b18, probe, d_alive, d_hoff, d_cnt, d_idx)) return rc;
+        if (N) STOCS_HIP_CHECK(hipMemcpyAsync(alive0.data(), d_alive, N, hipMemcpyDeviceToHost, c->stream));
+    }
+    STOCS_HIP_CHECK(hipMemsetAsync(d_cnt, 0xFF, nT * 4, c->stream));
+    if (H) STOCS_HIP_CHECK(hipMemsetAsync(d_idx, 0xFF, H * 4, c->stream));
+    if (int rc = enqueue_trial_cluster(c, n_trials, d_P, d_lcp, d_coff, d_b18, a, d_alive, d_hoff, d_cnt, d_idx)) return rc;
+    STOCS_HIP_CHECK(hipMemcpyAsync(out_cnt, d_cnt, nT * 4, hipMemcpyDeviceToHost, c->stream));
+    if (H) STOCS_HIP_CHECK(hipMemcpyAsync(out_idx, d_idx, H * 4, hipMemcpyDeviceToHost, c->stream));
+    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    for (size_t t = 0; round0_survivors && t < nT; ++t) {
+        int32_t s = 0;
+        for (int32_t i = cand_off[t]; i < cand_off[t + 1]; ++i) s += alive0[(size_t)i] ? 1 : 0;
+        round0_survivors[t] = s;
+    }
+    return STOCS_OK;
 }

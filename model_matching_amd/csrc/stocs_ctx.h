@@ -386,6 +386,9 @@ int refine_prepare(stocs_ctx* c, int n, int nsrc, float max_correspondence_dista
 int refine_enqueue(stocs_ctx* c, const RefineWork& w, bool use_idx, const int32_t* d_live, int max_iterations, float max_correspondence_distance);
 // cluster.hip: greedy_clustering of every trial of a batch piece on the device (see there); no synchronisation
 struct TrialClusterArgs { float fraction; int32_t count; float min_distance, min_angle; float sym[3]; };
+// hypothesis slots of a trial with n candidates: the reference's `size() > count` break keeps up to count + 1 of them.  The one rule
+// for stocs_run_trials_post and stocs_cluster_trials_device (the kernel's `cap`)
+inline int32_t trial_hyp_slots(int count, long long n) { const long long m = (long long)count + 1; return (int32_t)(m < n ? m : n); }
 int enqueue_trial_cluster(stocs_ctx* c, int n_trials, const float* d_P, const float* d_lcp, const int32_t* d_cand_off, const float* d_best18,
                           const TrialClusterArgs& a, uint8_t* d_alive, const int32_t* d_hyp_off, int32_t* d_hyp_cnt, int32_t* d_hyp_idx);
 int ensure_kdtree(stocs_ctx* c);   // kdtree.hip: the kd-tree of the current scene on the device (exact_ties); synchronises

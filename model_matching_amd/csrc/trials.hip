@@ -193,7 +193,7 @@ static int plan_piece(stocs_ctx* c, Piece& pc) {
     const size_t nT = (size_t)pc.n_trials, n_cand = (size_t)pc.n_cand; const bool post = pc.post != NULL;
     pc.hyp_off.assign(post ? nT + 1 : 0, 0);
     for (size_t t = 0; post && t < nT; ++t)   // (the counts come back with the read-back)
-        pc.hyp_off[t + 1] = pc.hyp_off[t] + (int32_t)std::min<long long>((long long)pc.post->maximum_pose_count + 1, (long long)(c->trial_cand_off[t + 1] - c->trial_cand_off[t]));
+        pc.hyp_off[t + 1] = pc.hyp_off[t] + trial_hyp_slots(pc.post->maximum_pose_count, (long long)(c->trial_cand_off[t + 1] - c->trial_cand_off[t]));
     pc.n_slots = post ? pc.hyp_off[nT] : 0;
     pc.refine = post && pc.post->refine_iterations > 0 && pc.n_slots > 0;
     const size_t H = (size_t)pc.n_slots;

@@ -264,6 +264,21 @@ class StocsEstimator:
                                               counted.ctypes.data_as(capi._u8p), s28.ctypes.data_as(C.POINTER(C.c_double)) if sums else None))
         return match[:n], counted[:n], s28
 
+    def cluster_trials_device(self, poses16, lcp, cand_off, best_score, acceptable_fraction, maximum_pose_count, min_distance, min_angle, sym):
+        """The device clustering of trial batches on given candidates (stocs_cluster_trials_device) -> (out_off (n_trials + 1,), out_cnt
+        (n_trials,), out_idx (out_off[-1],) with -1 in the unused slots, round0_survivors (n_trials,))."""
+        P, pP = capi.f32(poses16); l, pl = capi.f32(lcp); off, poff = capi.i32(cand_off); b, pb = capi.f32(best_score); s, ps = capi.f32(sym)
+        nT = len(off) - 1
+        assert nT >= 0 and len(b) == nT and s.size == 3
+        n = np.diff(off.astype(np.int64))
+        cap = int(np.minimum(max(int(maximum_pose_count), 0) + 1, np.maximum(n, 0)).sum()) if nT else 0
+        out_off = np.zeros(nT + 1, np.int32); out_cnt = np.zeros(max(nT, 1), np.int32); out_idx = np.zeros(max(cap, 1), np.int32)
+        surv = np.zeros(max(nT, 1), np.int32)
+        capi.check(self.L.stocs_cluster_trials_device(self.h, pP, pl, poff, pb, nT, acceptable_fraction, maximum_pose_count, min_distance, min_angle, ps,
+                                                      out_off.ctypes.data_as(capi._ip), out_cnt.ctypes.data_as(capi._ip), out_idx.ctypes.data_as(capi._ip),
+                                                      cap, surv.ctypes.data_as(capi._ip)))
+        return out_off, out_cnt[:nT], out_idx[:cap], surv[:nT]
+
     def track_poses(self, priors_pose16_camera, rounds=TRACK_DEFAULTS["rounds"], samples=TRACK_DEFAULTS["samples"],
                     max_translation=TRACK_DEFAULTS["max_translation"], max_rotation_deg=TRACK_DEFAULTS["max_rotation_deg"], shrink=TRACK_DEFAULTS["shrink"],
                     seed=TRACK_DEFAULTS["seed"], refine_iterations=TRACK_DEFAULTS["refine_iterations"],
