@@ -962,16 +962,18 @@ __global__ __launch_bounds__(256) void join_fill_kernel(JoinArgs<KeyT> A, const 
     join_one<1>(A, i, lds, b0, quads + ob + (o0 - qoffe[A.q_off[b]]));
 }
 
-struct XformJobC { int32_t s[4]; int32_t q[4]; };
-struct Pick { int32_t base, rank, dst, sorted; };   // sorted: rank counts in the base's materialised, sorted run
-
-__device__ __forceinline__ void store_job(XformJobC* jobs, int dst, const int32_t* base_ids, int b, uint64_t key, int id_bits) {
+// the four model ids of a packed quad key (id_bits each, below the base when the key carries one)
+STOCS_HD void unpack_quad(uint64_t key, int id_bits, int32_t out[4]) {
     const uint64_t m = (1ull << id_bits) - 1ull;
-    XformJobC job;
+    out[0] = (int32_t)((key >> (3 * id_bits)) & m); out[1] = (int32_t)((key >> (2 * id_bits)) & m);
+    out[2] = (int32_t)((key >> id_bits) & m); out[3] = (int32_t)(key & m);
+}
+
+__device__ __forceinline__ void store_job(XformJob* jobs, int dst, const int32_t* base_ids, int b, uint64_t key, int id_bits) {
+    XformJob job;
 #pragma unroll
     for (int k = 0; k < 4; ++k) job.s[k] = base_ids[4 * b + k];
-    job.q[0] = (int)((key >> (3 * id_bits)) & m); job.q[1] = (int)((key >> (2 * id_bits)) & m);
-    job.q[2] = (int)((key >> id_bits) & m); job.q[3] = (int)(key & m);
+    unpack_quad(key, id_bits, job.q);
     jobs[dst] = job;
 }
 
@@ -984,7 +986,7 @@ __device__ __forceinline__ void store_job(XformJobC* jobs, int dst, const int32_
 template <class KeyT>
 __global__ __launch_bounds__(256) void resolve_picks_kernel(JoinArgs<KeyT> A, const unsigned long long* __restrict__ qoffe, const Pick* __restrict__ picks, int n,
                                                             const uint64_t* __restrict__ sorted_quads, const unsigned long long* __restrict__ sorted_off,
-                                                            const int32_t* __restrict__ base_ids, XformJobC* __restrict__ jobs,
+                                                            const int32_t* __restrict__ base_ids, XformJob* __restrict__ jobs,
                                                             uint64_t* __restrict__ keys_out, unsigned int* __restrict__ n_unresolved) {
     __shared__ uint32_t seen_all[4][12];
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
@@ -1208,6 +1210,20 @@ static int materialise_t(stocs_ctx* c, CongruentState* S, const std::vector<char
 }
 static int materialise(stocs_ctx* c, CongruentState* S, const std::vector<char>& sel, DevBuf<uint64_t>* out, std::vector<unsigned long long>* off) {
     return S->wide ? materialise_t<uint64_t>(c, S, sel, out, off) : materialise_t<uint32_t>(c, S, sel, out, off);
+}
+
+template <class KeyT>
+static void launch_resolve_picks_t(stocs_ctx* c, CongruentState* S, const Pick* picks, int n, const uint64_t* sorted, const unsigned long long* soff, XformJob* jobs, uint64_t* keys_out) {
+    hipLaunchKernelGGL(resolve_picks_kernel<KeyT>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, S->template args<KeyT>(c), S->d_qoffe.p, picks, n, sorted, soff,
+                       S->d_bids.p, jobs, keys_out, S->d_err.p);
+}
+// n device-resident picks -> transform jobs and / or packed quad keys (either may be NULL), one wavefront per pick on the context's
+// stream; sorted / soff: the materialised runs the picks with sorted != 0 refer to (NULL when there are none)
+static int launch_resolve_picks(stocs_ctx* c, CongruentState* S, const Pick* picks, int n, const uint64_t* sorted, const unsigned long long* soff, XformJob* jobs, uint64_t* keys_out) {
+    if (S->wide) launch_resolve_picks_t<uint64_t>(c, S, picks, n, sorted, soff, jobs, keys_out);
+    else launch_resolve_picks_t<uint32_t>(c, S, picks, n, sorted, soff, jobs, keys_out);
+    STOCS_HIP_CHECK(hipGetLastError());
+    return STOCS_OK;
 }
 
 // (cos, sin) of the sample angles theta_a = a * angleStep for every sample count nb (normalset.hpp:183-188: float libm on per-count
@@ -1993,14 +2009,7 @@ int stocs_get_quads(stocs_ctx* c, int slot, int32_t* quads4, int64_t cap, int64_
         STOCS_HIP_CHECK(hipMemcpyAsync(q.data(), d_sorted.p + off[slot], 8 * (size_t)m, hipMemcpyDeviceToHost, c->stream));
         STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
     }
-    const int bits = c->quad_id_bits;
-    const uint64_t mask = (1ull << bits) - 1ull;
-    for (int64_t i = 0; i < m; ++i) {
-        quads4[4 * i + 0] = (int32_t)((q[i] >> (3 * bits)) & mask);
-        quads4[4 * i + 1] = (int32_t)((q[i] >> (2 * bits)) & mask);
-        quads4[4 * i + 2] = (int32_t)((q[i] >> bits) & mask);
-        quads4[4 * i + 3] = (int32_t)(q[i] & mask);
-    }
+    for (int64_t i = 0; i < m; ++i) unpack_quad(q[i], c->quad_id_bits, quads4 + 4 * i);
     return (*n > cap) ? STOCS_ERR_CAPACITY : STOCS_OK;
 }
 
@@ -2030,36 +2039,19 @@ int stocs_get_quads_at(stocs_ctx* c, int slot, const int64_t* ranks, int n, int3
     uint64_t* keys = (uint64_t*)((char*)c->h_pin + PIN_VAR);
     unsigned int* n_err_pin = (unsigned int*)((char*)c->h_pin + PIN_CONGRUENT);
     STOCS_HIP_CHECK(hipMemcpyAsync(d_picks.p, picks.data(), sizeof(Pick) * (size_t)n, hipMemcpyHostToDevice, c->stream));
-    if (S->wide)
-        hipLaunchKernelGGL(resolve_picks_kernel<uint64_t>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, S->args<uint64_t>(c), S->d_qoffe.p, d_picks.p, n,
-                           (const uint64_t*)NULL, (const unsigned long long*)NULL, S->d_bids.p, (XformJobC*)NULL, d_keys.p, S->d_err.p);
-    else
-        hipLaunchKernelGGL(resolve_picks_kernel<uint32_t>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, S->args<uint32_t>(c), S->d_qoffe.p, d_picks.p, n,
-                           (const uint64_t*)NULL, (const unsigned long long*)NULL, S->d_bids.p, (XformJobC*)NULL, d_keys.p, S->d_err.p);
-    STOCS_HIP_CHECK(hipGetLastError());
+    if ((rc = launch_resolve_picks(c, S, d_picks.p, n, NULL, NULL, NULL, d_keys.p))) return rc;
     STOCS_HIP_CHECK(hipMemcpyAsync(keys, d_keys.p, 8 * (size_t)n, hipMemcpyDeviceToHost, c->stream));
     STOCS_HIP_CHECK(hipMemcpyAsync(n_err_pin, S->d_err.p, 4, hipMemcpyDeviceToHost, c->stream));
     STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
     const unsigned int n_err = *n_err_pin;
     if (n_err) { set_error("stocs_get_quads_at: %u ranks could not be resolved (internal inconsistency)", n_err); return STOCS_ERR_STATE; }
-    const int bits = c->quad_id_bits;
-    const uint64_t mask = (1ull << bits) - 1ull;
-    for (int i = 0; i < n; ++i) {
-        quads4[4 * i + 0] = (int32_t)((keys[i] >> (3 * bits)) & mask);
-        quads4[4 * i + 1] = (int32_t)((keys[i] >> (2 * bits)) & mask);
-        quads4[4 * i + 2] = (int32_t)((keys[i] >> bits) & mask);
-        quads4[4 * i + 3] = (int32_t)(keys[i] & mask);
-    }
+    for (int i = 0; i < n; ++i) unpack_quad(keys[i], c->quad_id_bits, quads4 + 4 * (size_t)i);
     return STOCS_OK;
 }
 
-// device side of stocs_make_transforms: picks4 = (base, rank, destination job, sorted?) records -> XformJob records
-// on the device.  Bases picked with sorted != 0 are materialised and sorted first (they are the small ones).
-// *d_unresolved_out: device counter of the picks the kernel could not resolve (0 while counts and join agree); the
-// caller reads it behind its own synchronisation point, this call does not wait for the device
-// First half of stocs_make_transforms' device work, launched BEFORE the host draws its picks: the bases with fewer quads than
-// the per-base maximum are materialised and sorted (they are used whole, in the std::set order).  Which bases those are
-// follows from the counts alone, so the fill + sort run while the host is busy with the seeded subsets of the large bases.
+// Device side of stocs_make_transforms, in two halves.  First, before the picks exist: the bases used whole (base_used_whole: fewer quads
+// than the per-base maximum) are materialised and sorted into the std::set order.  Which bases those are follows from the counts alone,
+// so the fill + sort run while the host draws the seeded subsets of the large bases, or next to the draw on the auxiliary stream.
 int stocs_internal_prepare_small(stocs_ctx* c, int max_per_base) {
     CongruentState* S = (CongruentState*)c->cong;
     if (!S || !S->valid) { set_error("stocs_make_transforms: no congruent state (call stocs_find_congruent_all first)"); return STOCS_ERR_STATE; }
@@ -2069,7 +2061,7 @@ int stocs_internal_prepare_small(stocs_ctx* c, int max_per_base) {
     std::vector<char> sel(S->nB, 0);
     for (int b = 0; b < S->nB; ++b) {
         const unsigned long long nq = c->quad_off[b + 1] - c->quad_off[b];
-        if (nq > 0 && nq < (unsigned long long)max_per_base) { sel[b] = 1; S->small_any = true; }
+        if (nq > 0 && base_used_whole((long long)nq, max_per_base)) { sel[b] = 1; S->small_any = true; }
     }
     if (!S->small_any) return STOCS_OK;
     std::vector<unsigned long long>& off = S->h_off;
@@ -2079,48 +2071,27 @@ int stocs_internal_prepare_small(stocs_ctx* c, int max_per_base) {
     return STOCS_OK;
 }
 
-// picks4_dev != NULL: the picks are on the device already (drawn there; stocs_internal_prepare_small has run)
-int stocs_internal_make_jobs(stocs_ctx* c, const int32_t* picks4_host, const int32_t* picks4_dev, int n, void* d_jobs_out, const unsigned int** d_unresolved_out) {
+// Second half: n picks -> XformJob records on the device.  The picks are either on the device already (picks_dev, drawn there) or
+// uploaded from picks_host; those with sorted != 0 refer to the runs stocs_internal_prepare_small left in the arena, so that call
+// must have run since the arena was last reset.  *d_unresolved_out: device counter of the picks the kernel could not resolve (0 while
+// counts and join agree); the caller reads it behind its own synchronisation point, this call does not wait for the device.
+int stocs_internal_make_jobs(stocs_ctx* c, const Pick* picks_host, const Pick* picks_dev, int n, XformJob* d_jobs_out, const unsigned int** d_unresolved_out) {
     if (d_unresolved_out) *d_unresolved_out = NULL;
     CongruentState* S = (CongruentState*)c->cong;
     const bool prepared = S && S->small_ready;
     if (S) S->small_ready = false;
     if (n <= 0) return STOCS_OK;
     if (!S || !S->valid) { set_error("stocs_make_transforms: no congruent state (call stocs_find_congruent_all first)"); return STOCS_ERR_STATE; }
-    const Pick* picks = (const Pick*)picks4_host;
-    const uint64_t* d_sorted = NULL; const unsigned long long* d_soff = NULL;
-    DevBuf<uint64_t> d_sorted_here; DevBuf<unsigned long long> d_soff_here; DevBuf<Pick> d_picks;
+    if (!prepared) { set_error("internal: device picks without the small bases prepared"); return STOCS_ERR_STATE; }
+    tl_arena = &S->arena_tmp;   // the temporaries of stocs_internal_prepare_small are still in it
     int rc;
-    if (picks4_dev && !prepared) { set_error("internal: device picks without the small bases prepared"); return STOCS_ERR_STATE; }
-    if (prepared) {   // the temporaries of stocs_internal_prepare_small are still in the arena
-        tl_arena = &S->arena_tmp;
-        if (S->small_any) { d_sorted = S->d_small_sorted.p; d_soff = S->d_small_soff.p; }
-    } else {
-        { int rc0 = S->arena_tmp.reset(); if (rc0) return rc0; }
-        tl_arena = &S->arena_tmp;
-        std::vector<char> sel(S->nB, 0);
-        bool any_sorted = false;
-        for (int i = 0; i < n; ++i) if (picks[i].sorted) { sel[picks[i].base] = 1; any_sorted = true; }
-        std::vector<unsigned long long>& off = S->h_off;
-        if (any_sorted) {
-            if ((rc = materialise(c, S, sel, &d_sorted_here, &off)) || (rc = d_soff_here.alloc(off.size()))) return rc;
-            STOCS_HIP_CHECK(hipMemcpyAsync(d_soff_here.p, off.data(), 8 * off.size(), hipMemcpyHostToDevice, c->stream));
-            d_sorted = d_sorted_here.p; d_soff = d_soff_here.p;
-        }
-    }
-    if (picks4_dev) {
-        d_picks.p = (Pick*)picks4_dev;
-    } else {
+    if (!picks_dev) {
+        DevBuf<Pick> d_picks;
         if ((rc = d_picks.alloc(n))) return rc;
-        STOCS_HIP_CHECK(hipMemcpyAsync(d_picks.p, picks, sizeof(Pick) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        STOCS_HIP_CHECK(hipMemcpyAsync(d_picks.p, picks_host, sizeof(Pick) * (size_t)n, hipMemcpyHostToDevice, c->stream));
+        picks_dev = d_picks.p;
     }
-    if (S->wide)
-        hipLaunchKernelGGL(resolve_picks_kernel<uint64_t>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, S->args<uint64_t>(c), S->d_qoffe.p, d_picks.p, n, d_sorted,
-                           d_soff, S->d_bids.p, (XformJobC*)d_jobs_out, (uint64_t*)NULL, S->d_err.p);
-    else
-        hipLaunchKernelGGL(resolve_picks_kernel<uint32_t>, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, S->args<uint32_t>(c), S->d_qoffe.p, d_picks.p, n, d_sorted,
-                           d_soff, S->d_bids.p, (XformJobC*)d_jobs_out, (uint64_t*)NULL, S->d_err.p);
-    STOCS_HIP_CHECK(hipGetLastError());
+    if ((rc = launch_resolve_picks(c, S, picks_dev, n, S->small_any ? S->d_small_sorted.p : NULL, S->small_any ? S->d_small_soff.p : NULL, d_jobs_out, NULL))) return rc;
     if (d_unresolved_out) *d_unresolved_out = S->d_err.p;
     return STOCS_OK;
 }

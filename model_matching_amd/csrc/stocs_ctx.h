@@ -218,6 +218,16 @@ struct Candidate {
     int base_index;
 };
 
+// The two records that pass between the candidate phase (transform.hip) and the congruent state that resolves them (congruent.hip)
+struct XformJob { int32_t s[4]; int32_t q[4]; };                // scene base ids, model quad ids
+// quad `rank` of `base` -> job `dst`; sorted: rank counts in the base's materialised, sorted run (else in its walk order).  Aligned so that
+// the kernels read and write a pick as one 128-bit access
+struct alignas(16) Pick { int32_t base, rank, dst, sorted; };
+// stocs_match_one_object.cpp:126: a base with STRICTLY fewer quads than the per-base maximum is used whole, in the std::set order of
+// stocs.cpp:860-866 (materialised and sorted); one at the maximum or above it contributes a seeded draw of max_per_base quads
+STOCS_HD bool base_used_whole(long long nq, int max_per_base) { return nq < max_per_base; }
+STOCS_HD long long base_pick_count(long long nq, int max_per_base) { return base_used_whole(nq, max_per_base) ? nq : (long long)max_per_base; }
+
 struct Thresholds {
     float lcp_dot_lo;   // normal test true  <=>  lcp_dot_lo <= dot <= 1
     float ang_dot_hi;   // internal-angle reject <=> (ang_dot_hi <= dot <= 1) || (-1 <= dot <= ang_dot_lo)
@@ -397,8 +407,9 @@ int build_ppf_index(stocs_ctx* c);
 int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune);
 int prepare_cull_field(stocs_ctx* c);   // geometry + memory of SceneGrid::d_dist for the current grid and model (end of a grid build)
 int fill_cull_field(stocs_ctx* c, hipStream_t st = NULL);      // the values, on st (NULL: c->stream); no synchronisation
-extern "C" int stocs_internal_make_jobs(stocs_ctx* c, const int32_t* picks4_host, const int32_t* picks4_dev, int n, void* d_jobs_out, const unsigned int** d_unresolved_out);
-extern "C" int stocs_internal_prepare_small(stocs_ctx* c, int max_per_base);   // small bases materialised while the host draws the picks
+// congruent.hip, the device side of stocs_make_transforms: the bases used whole materialised and sorted, then picks -> jobs (see there)
+extern "C" int stocs_internal_prepare_small(stocs_ctx* c, int max_per_base);
+extern "C" int stocs_internal_make_jobs(stocs_ctx* c, const Pick* picks_host, const Pick* picks_dev, int n, XformJob* d_jobs_out, const unsigned int** d_unresolved_out);
 extern "C" void stocs_internal_free_congruent(stocs_ctx* c);
 extern "C" void stocs_internal_invalidate_congruent(stocs_ctx* c);
 extern "C" void stocs_internal_free_instance(stocs_ctx* c);

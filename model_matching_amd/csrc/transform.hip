@@ -9,13 +9,9 @@
 // stocs_math.h, so the result is bit-identical to the CPU restatement.
 #include <stdlib.h>
 #include <string.h>
-#include <time.h>
-
-#include <cstring>
-
 
 #include <algorithm>
-#include <unordered_map>
+#include <vector>
 
 #include "prims.h"
 #include "stocs_ctx.h"
@@ -38,8 +34,6 @@ STOCS_HD V3 mul3v(const M3& A, V3 v) {
                A.m[2][0] * v.x + (A.m[2][1] * v.y + A.m[2][2] * v.z));
 }
 __device__ __forceinline__ V3 ld3(const float4* a, int i) { float4 v = a[i]; return mk3(v.x, v.y, v.z); }
-
-struct XformJob { int32_t s[4]; int32_t q[4]; };  // scene base ids, model quad ids
 
 // One candidate: the arithmetic of ComputeRigidTransformation + get_rigid_transform_from_congruent_pair on three point
 // pairs.  Host and device run this same function (IEEE float operations in a fixed order, sqrt the only non-trivial one),
@@ -133,56 +127,72 @@ __global__ __launch_bounds__(64) void winner_pose_kernel(const unsigned long lon
     }
 }
 
-// The picks of stocs_make_transforms on the device, one workgroup per base: a base with fewer quads than the per-base maximum is
-// used whole (ranks 0 .. nq-1 of its sorted run); a larger one gets the seeded sample without replacement -- the same sparse
-// partial Fisher-Yates the host form runs (open-addressing table of the touched entries of the identity permutation, here in
-// LDS): the draws r_j are independent and computed by all threads, the swaps are sequential and done by one.  Runs on the
-// auxiliary stream next to the materialisation of the small bases.  table[b] = (first job, quad count lo, hi, unused).
-// trial (when != NULL; stocs_run_trials): per base (seed lo, seed hi, slot of the base in ITS trial, 0) -- the draw of a base is
-// rng(seed of its trial, its slot there, j), and its candidates carry that slot, exactly as when the trial runs alone.
+// ---- the pick draw of stocs_make_transforms: one text for the kernel below and for the host form (draw_picks_host) ----
+// A base used whole (base_used_whole) contributes ranks 0 .. nq-1 of its sorted run.  A larger one gets a seeded sample without
+// replacement (divergence Q5 from the biased 2N-vector shuffle of stocs_match_one_object.cpp:134-142, whose result depends on the C
+// library's unseeded generator): a partial Fisher-Yates over the base's quads in EMISSION order (the order the loop of stocs.cpp:827-858
+// finds them; any fixed enumeration serves a uniform draw, and this one needs no sort), kept sparse: only the touched entries of the
+// identity permutation are stored, in an open-addressing table of hmask + 1 >= 4 * max_per_base slots (hkeys[h] = -1: free), reset
+// per base.  The random words are independent of the swaps: word j of a base is rng(seed of its trial, its slot there, j).
+STOCS_HD uint64_t pick_word(uint64_t seed, int slot, int j) { return rng64(seed, 0x5E1EC7ull + (uint64_t)slot, (uint64_t)j); }
+inline uint32_t pick_table_mask(int max_per_base) {
+    uint32_t hsize = 64;
+    while (hsize < 4u * (uint32_t)max_per_base) hsize <<= 1;
+    return hsize - 1;
+}
+// step j (upward from 0) with its word r_j: swap position j with position k = j + floor(r_j (nq - j) / 2^64) and return what is now at
+// position j, the j-th pick.  Only position k is stored: steps go upward and k >= j, so position j is never read again.
+STOCS_HD int draw_pick_step(int* hkeys, int* hvals, uint32_t hmask, long long nq, int j, uint64_t r_j) {
+    auto slot_of = [&](int i) {
+        uint32_t h = ((uint32_t)i * 2654435761u) & hmask;
+        while (hkeys[h] != -1 && hkeys[h] != i) h = (h + 1) & hmask;
+        return h;
+    };
+    const int k = j + (int)mulhi64(r_j, (uint64_t)(nq - j));
+    const uint32_t hj = slot_of(j);
+    const int vj = hkeys[hj] == j ? hvals[hj] : j;
+    int vk = vj;
+    if (k != j) {
+        const uint32_t hk = slot_of(k);
+        vk = hkeys[hk] == k ? hvals[hk] : k;
+        hkeys[hk] = k; hvals[hk] = vj;
+    }
+    return vk;
+}
+// Row b of the pick table: table[b] = (first job, quad count lo, hi, unused); trial[b] (a batch of trials, stocs_run_trials; else NULL)
+// = (seed lo, seed hi, slot of the base in ITS trial, 0): the base draws with the seed of its trial and under its slot there, and its
+// candidates carry that slot, exactly as when the trial runs alone.
+struct BaseDraw { int first; long long nq; uint64_t seed; int slot; };
+STOCS_HD BaseDraw base_draw(const uint4* table, const uint4* trial, int b, uint64_t seed) {
+    const uint4 t = table[b];
+    BaseDraw d = {(int)t.x, (long long)(((unsigned long long)t.z << 32) | (unsigned long long)t.y), seed, b};
+    if (trial) { const uint4 tr = trial[b]; d.seed = ((uint64_t)tr.y << 32) | (uint64_t)tr.x; d.slot = (int)tr.z; }
+    return d;
+}
+
+// The draw on the device, one workgroup per base, table in LDS: the words r_j are computed by all threads, the swaps are sequential
+// and done by one.  Runs on the auxiliary stream next to the materialisation of the small bases.
 __global__ __launch_bounds__(256) void draw_picks_kernel(const uint4* __restrict__ table, const uint4* __restrict__ trial, uint64_t seed, int max_per_base, uint32_t hmask,
-                                                         int4* __restrict__ picks, int32_t* __restrict__ job_base) {
+                                                         Pick* __restrict__ picks, int32_t* __restrict__ job_base) {
     extern __shared__ uint32_t lds_dyn[];
     int* hkeys = (int*)lds_dyn;                          // hmask + 1
     int* hvals = hkeys + (hmask + 1);                    // hmask + 1
     int* out = hvals + (hmask + 1);                      // max_per_base
     uint64_t* r = (uint64_t*)(out + ((max_per_base + 1) & ~1));   // max_per_base (8-byte aligned: everything before is an even number of words)
     const int b = blockIdx.x;
-    const uint4 t = table[b];
-    const int first = (int)t.x;
-    const long long nq = (long long)(((unsigned long long)t.z << 32) | (unsigned long long)t.y);
-    if (nq <= 0) return;
-    int b_own = b;                                   // the base's slot in its own trial
-    if (trial) { const uint4 tr = trial[b]; seed = ((uint64_t)tr.y << 32) | (uint64_t)tr.x; b_own = (int)tr.z; }
-    if (nq < max_per_base) {   // stocs_match_one_object.cpp:126: strictly fewer -> all, in the std::set order of stocs.cpp:860-866
-        for (int i = threadIdx.x; i < (int)nq; i += blockDim.x) { picks[first + i] = make_int4(b, i, first + i, 1); job_base[first + i] = b_own; }
+    const BaseDraw d = base_draw(table, trial, b, seed);
+    if (d.nq <= 0) return;
+    if (base_used_whole(d.nq, max_per_base)) {
+        for (int i = threadIdx.x; i < (int)d.nq; i += blockDim.x) { picks[d.first + i] = Pick{b, i, d.first + i, 1}; job_base[d.first + i] = d.slot; }
         return;
     }
     for (uint32_t h = threadIdx.x; h <= hmask; h += blockDim.x) hkeys[h] = -1;
-    for (int j = threadIdx.x; j < max_per_base; j += blockDim.x) r[j] = rng64(seed, 0x5E1EC7ull + (uint64_t)b_own, (uint64_t)j);
+    for (int j = threadIdx.x; j < max_per_base; j += blockDim.x) r[j] = pick_word(d.seed, d.slot, j);
     __syncthreads();
-    if (threadIdx.x == 0) {
-        auto slot_of = [&](int i) {
-            uint32_t h = ((uint32_t)i * 2654435761u) & hmask;
-            while (hkeys[h] != -1 && hkeys[h] != i) h = (h + 1) & hmask;
-            return h;
-        };
-        for (int j = 0; j < max_per_base; ++j) {
-            const int k = j + (int)mulhi64(r[j], (uint64_t)(nq - j));
-            const uint32_t hj = slot_of(j);
-            const int vj = hkeys[hj] == j ? hvals[hj] : j;
-            int vk = vj;
-            if (k != j) {
-                const uint32_t hk = slot_of(k);
-                vk = hkeys[hk] == k ? hvals[hk] : k;
-                hkeys[hk] = k; hvals[hk] = vj;
-            }
-            // (position j is never read again: steps go upward and k >= j -- the host form stores it all the same, with the same result)
-            out[j] = vk;
-        }
-    }
+    if (threadIdx.x == 0)
+        for (int j = 0; j < max_per_base; ++j) out[j] = draw_pick_step(hkeys, hvals, hmask, d.nq, j, r[j]);
     __syncthreads();
-    for (int j = threadIdx.x; j < max_per_base; j += blockDim.x) { picks[first + j] = make_int4(b, out[j], first + j, 0); job_base[first + j] = b_own; }
+    for (int j = threadIdx.x; j < max_per_base; j += blockDim.x) { picks[d.first + j] = Pick{b, out[j], d.first + j, 0}; job_base[d.first + j] = d.slot; }
 }
 
 // out[k] = a[idx[k]]: the accepted-candidate counts in front of every trial's first job (= where its candidates start)
@@ -204,6 +214,81 @@ __global__ __launch_bounds__(256) void compact_candidates_kernel(const float4* _
     for (int k = 0; k < 4; ++k) { To[(size_t)d * 4 + k] = T[(size_t)j * 4 + k]; Po[(size_t)d * 4 + k] = P[(size_t)j * 4 + k]; }
     lcp[d] = 0.0f;   // "score is not computed at this time" (stocs.cpp:935-936)
     base_out[d] = job_base[j];
+}
+
+// Where the buffers of one stocs_make_transforms call lie.  `var` is the part the host fills in the pinned block (behind PIN_VAR) and
+// the device reads at the same offsets inside the scratch block (from var_at on): the two tables of base_draw and, for a batch, the
+// trial words (first job of every trial in; first candidate of every trial out, behind them).
+struct CandLayout {
+    Carve var, dev;
+    size_t table, trial, words;                                          // in var
+    size_t jobs, T, P, ok, pos, job_base, scan, picks, var_at;           // in the scratch block
+    CandLayout(size_t nbases, size_t n_tr) { table = var.take(16 * nbases); trial = var.take(16 * nbases); words = var.take(8 * n_tr); }
+    // n jobs; flags and their exclusive scan have n + 1 entries (the last flag is 0, the last scan entry the accepted count)
+    void carve_scratch(size_t n, size_t scan_bytes, size_t n_device_picks) {
+        jobs = dev.take(n * sizeof(XformJob)); T = dev.take(n * 64); P = dev.take(n * 64);
+        ok = dev.take((n + 1) * 4); pos = dev.take((n + 1) * 4); job_base = dev.take((n + 1) * 4);
+        scan = dev.take(scan_bytes); picks = dev.take(n_device_picks * sizeof(Pick)); var_at = dev.take(var.total);
+    }
+};
+
+// The pick table of the context's base set (rows as base_draw reads them), written once for both forms of the draw; *n_jobs: the picks
+// of all bases together.  A base's ranks are 32-bit: this is the one place that refuses more quads.
+static int build_pick_table(stocs_ctx* c, int max_per_base, uint4* table, uint4* trial, size_t* n_jobs) {
+    size_t n = 0;
+    for (size_t b = 0; b < c->bases.size(); ++b) {
+        const unsigned long long nq64 = c->quad_off[b + 1] - c->quad_off[b];
+        if (nq64 > 0x7FFFFFFFull) { set_error("base %zu has %llu congruent quads (more than 2^31 - 1)", b, nq64); return STOCS_ERR_CAPACITY; }
+        table[b] = make_uint4((uint32_t)n, (uint32_t)nq64, (uint32_t)(nq64 >> 32), 0u);
+        if (trial) trial[b] = make_uint4((uint32_t)c->base_seed[b], (uint32_t)(c->base_seed[b] >> 32), (uint32_t)c->base_local[b], 0u);
+        n += (size_t)base_pick_count((long long)nq64, max_per_base);
+    }
+    *n_jobs = n;
+    return STOCS_OK;
+}
+
+// The draw on the host (per-base maxima whose table does not fit LDS, contexts without an auxiliary stream): what draw_picks_kernel
+// writes to the device, into two vectors
+static void draw_picks_host(const uint4* table, const uint4* trial, size_t nbases, uint64_t seed, int max_per_base, std::vector<Pick>* picks, std::vector<int>* job_base) {
+    const uint32_t hmask = pick_table_mask(max_per_base);
+    std::vector<int> hkeys(hmask + 1), hvals(hmask + 1);
+    for (size_t b = 0; b < nbases; ++b) {
+        const BaseDraw d = base_draw(table, trial, (int)b, seed);
+        const bool whole = base_used_whole(d.nq, max_per_base);
+        if (!whole) std::fill(hkeys.begin(), hkeys.end(), -1);
+        const int count = (int)base_pick_count(d.nq, max_per_base);
+        for (int j = 0; j < count; ++j)
+            picks->push_back(Pick{(int32_t)b, whole ? j : draw_pick_step(hkeys.data(), hvals.data(), hmask, d.nq, j, pick_word(d.seed, d.slot, j)), d.first + j, whole});
+        job_base->insert(job_base->end(), (size_t)count, d.slot);
+    }
+}
+
+// The draw on the device, enqueued: table upload, fork, the small bases on the main stream next to draw_picks_kernel on the auxiliary
+// one, join.  The table goes up on the MAIN stream: a host-to-device copy of a few hundred kilobytes enqueued on the otherwise idle
+// auxiliary stream blocked the calling thread for 5.6 ms (64 trials of the ycb frame: 195 KB; measured, profiles/r04_trials_steps.json),
+// the same copy on the stream that carries the rest of the call's work returns at once.
+static int enqueue_device_picks(stocs_ctx* c, const CandLayout& L, bool batch, uint64_t seed, int max_per_base) {
+    const size_t nbases = c->bases.size();
+    char* d_var = Carve::at<char>(c->d_scratch, L.var_at);
+    uint4* d_table = Carve::at<uint4>(d_var, L.table);
+    Pick* d_picks = Carve::at<Pick>(c->d_scratch, L.picks);
+    int32_t* dB = Carve::at<int32_t>(c->d_scratch, L.job_base);
+    const uint32_t hmask = pick_table_mask(max_per_base);
+    const size_t lds = (size_t)(2 * (hmask + 1) + ((max_per_base + 1) & ~1)) * 4 + (size_t)max_per_base * 8;
+    STOCS_HIP_CHECK(hipMemcpyAsync(d_var, (char*)c->h_pin + PIN_VAR, (batch ? L.trial : L.table) + 16 * nbases, hipMemcpyHostToDevice, c->stream));
+    STOCS_HIP_CHECK(hipEventRecord(c->ev_fork, c->stream));
+    STOCS_HIP_CHECK(hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
+    c->audit.use(0, d_table, true, "pick table", "table upload"); c->audit.record(c->ev_fork, 0); c->audit.wait(1, c->ev_fork);
+    const int rc = stocs_internal_prepare_small(c, max_per_base);
+    if (rc) return rc;
+    hipLaunchKernelGGL(draw_picks_kernel, dim3((unsigned)nbases), dim3(256), lds, c->aux_stream, (const uint4*)d_table,
+                       batch ? Carve::at<const uint4>(d_var, L.trial) : (const uint4*)NULL, seed, max_per_base, hmask, d_picks, dB);
+    STOCS_HIP_CHECK(hipGetLastError());
+    STOCS_HIP_CHECK(hipEventRecord(c->ev_join, c->aux_stream));
+    STOCS_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
+    c->audit.use(1, d_table, false, "pick table", "draw picks"); c->audit.use(1, d_picks, true, "picks", "draw picks"); c->audit.use(1, dB, true, "job bases", "draw picks");
+    c->audit.record(c->ev_join, 1); c->audit.wait(0, c->ev_join);
+    return STOCS_OK;
 }
 
 }  // namespace stocs
@@ -231,17 +316,8 @@ int stocs_make_transforms(stocs_ctx* c, int max_per_base, uint64_t seed, int* n_
     if (!c || max_per_base <= 0) return STOCS_ERR_INVALID;
     DeviceGuard dev_guard(c->device);
     if (c->quad_off.size() != c->bases.size() + 1) { set_error("stocs_make_transforms: call stocs_find_congruent_all first"); return STOCS_ERR_STATE; }
-    const bool dbg = getenv("STOCS_DEBUG_TIMING") != NULL;
-    struct timespec ts0; clock_gettime(CLOCK_MONOTONIC, &ts0);
-    c->timing[1].begin();
-    auto tick = [&](const char* label) {
-        if (!dbg) return;
-        (void)hipStreamSynchronize(c->stream);
-        struct timespec t1; clock_gettime(CLOCK_MONOTONIC, &t1);
-        fprintf(stderr, "[stocs transforms] %-18s %8.3f ms\n", label, (t1.tv_sec - ts0.tv_sec) * 1e3 + (t1.tv_nsec - ts0.tv_nsec) * 1e-6);
-        ts0 = t1;
-    };
-    // A trial without a single congruent set -- no bases, empty pair lists, or no (base, cell) that both lists occupy -- is a valid,
+    c->timing[1].begin();   // (the steps of this call: stocs_last_call_timing(ctx, 1, ...))
+    // 1. A trial without a single congruent set -- no bases, empty pair lists, or no (base, cell) that both lists occupy -- is a valid,
     // empty result (the reference's loop simply appends nothing, stocs_match_one_object.cpp:111-147): no candidates, "no pose".
     if (c->quad_off.back() == 0) {
         clear_candidates(c);
@@ -251,181 +327,101 @@ int stocs_make_transforms(stocs_ctx* c, int max_per_base, uint64_t seed, int* n_
         c->timing[1].lap("no congruent sets");
         return STOCS_OK;
     }
-    // picks = (base, rank, job slot, sorted?) records; the quads themselves are produced on the device
-    std::vector<int32_t> picks;
-    std::vector<int> job_base;
     if (max_per_base > (1 << 24)) { set_error("stocs_make_transforms: max_per_base %d exceeds 2^24", max_per_base); return STOCS_ERR_INVALID; }
-    uint32_t hsize = 64;
-    while (hsize < 4u * (uint32_t)max_per_base) hsize <<= 1;
-    const uint32_t hmask = hsize - 1;
-    // the picks are drawn on the device (draw_picks_kernel, on the auxiliary stream next to the small bases' materialisation)
-    // while the table of touched entries fits LDS; the host form below is the same draw and serves larger per-base maxima
+    // the picks are drawn on the device while the table of touched entries fits LDS; the host form, the same draw, serves larger maxima
     const bool device_picks = max_per_base <= 1024 && c->aux_stream && !getenv("STOCS_TRANSFORMS_HOST_PICKS");
-    // host-drawn picks: the device starts on the small bases (used whole: materialised and sorted) while the host draws the subsets
-    // of the large ones; device-drawn picks: behind the upload of the pick table, further down
-    if (!device_picks && !c->bases.empty()) { const int rc0 = stocs_internal_prepare_small(c, max_per_base); if (rc0) return rc0; }
+    int rc;
+    // host-drawn picks: the device starts on the small bases while the host draws the subsets of the large ones
+    if (!device_picks && (rc = stocs_internal_prepare_small(c, max_per_base))) return rc;
     // a batch of trials (stocs_run_trials): every base draws with the seed of its trial and under its slot there
     const bool batch = !c->base_seed.empty();
     if (batch && (c->base_seed.size() != c->bases.size() || c->base_local.size() != c->bases.size())) { set_error("internal: trial tables do not match the base set"); return STOCS_ERR_STATE; }
-    const size_t nbases = c->bases.size(), tab_bytes = al256(16 * nbases);
-    const size_t n_tr = batch ? c->trial_first_base.size() : 0;     // trials + 1
-    std::vector<size_t> first_job(nbases + 1, 0);
-    size_t n_dev = 0;
-    if (device_picks) {
-        int rc0 = ensure_pinned(c, (size_t)PIN_VAR + 2 * tab_bytes + 4 * n_tr + 256);
-        if (rc0) return rc0;
-        uint4* table = (uint4*)((char*)c->h_pin + PIN_VAR);
-        uint4* table2 = (uint4*)((char*)c->h_pin + PIN_VAR + tab_bytes);
-        for (size_t b = 0; b < nbases; ++b) {
-            const unsigned long long nq64 = c->quad_off[b + 1] - c->quad_off[b];
-            if (nq64 > 0x7FFFFFFFull) { set_error("base %zu has %llu congruent quads (more than 2^31 - 1)", b, nq64); return STOCS_ERR_CAPACITY; }
-            table[b] = make_uint4((uint32_t)n_dev, (uint32_t)nq64, (uint32_t)(nq64 >> 32), 0u);
-            if (batch) table2[b] = make_uint4((uint32_t)c->base_seed[b], (uint32_t)(c->base_seed[b] >> 32), (uint32_t)c->base_local[b], 0u);
-            first_job[b] = n_dev;
-            n_dev += (size_t)std::min<unsigned long long>(nq64, (unsigned long long)max_per_base);
-        }
-        first_job[nbases] = n_dev;
-    }
-    std::vector<int> hkeys(hsize), hvals(hsize);
-    auto add_pick = [&](size_t b, int rank, int sorted) {
-        picks.push_back((int32_t)b); picks.push_back((int32_t)rank); picks.push_back((int32_t)job_base.size()); picks.push_back(sorted);
-        job_base.push_back(batch ? (int)c->base_local[b] : (int)b);
-    };
-    for (size_t b = 0; b < c->bases.size() && !device_picks; ++b) {
-        first_job[b] = job_base.size();
-        const uint64_t seed_b = batch ? c->base_seed[b] : seed;
-        const uint64_t slot_b = batch ? (uint64_t)c->base_local[b] : (uint64_t)b;
-        const unsigned long long nq64 = c->quad_off[b + 1] - c->quad_off[b];
-        if (nq64 > 0x7FFFFFFFull) { set_error("base %zu has %llu congruent quads (more than 2^31 - 1)", b, nq64); return STOCS_ERR_CAPACITY; }
-        const long long nq = (long long)nq64;
-        if (nq < max_per_base) {  // stocs_match_one_object.cpp:126: strictly fewer -> all, in the std::set order of stocs.cpp:860-866
-            for (long long i = 0; i < nq; ++i) add_pick(b, (int)i, 1);
-        } else {
-            // seeded sample without replacement (divergence Q5 from the biased 2N-vector shuffle of
-            // stocs_match_one_object.cpp:134-142, whose result depends on the C library's unseeded generator):
-            // partial Fisher-Yates over the base's quads in EMISSION order (the order the loop of
-            // stocs.cpp:827-858 finds them), kept sparse (only the touched entries of the identity
-            // permutation are stored).  Any fixed enumeration serves a uniform draw; this one needs no sort.
-            // sparse identity permutation: open-addressing table, reset per base (<= 2 * max_per_base live keys)
-            std::fill(hkeys.begin(), hkeys.end(), -1);
-            auto slot_of = [&](int i) {
-                uint32_t h = ((uint32_t)i * 2654435761u) & hmask;
-                while (hkeys[h] != -1 && hkeys[h] != i) h = (h + 1) & hmask;
-                return h;
-            };
-            auto at = [&](int i) { const uint32_t h = slot_of(i); return hkeys[h] == i ? hvals[h] : i; };
-            auto put = [&](int i, int v) { const uint32_t h = slot_of(i); hkeys[h] = i; hvals[h] = v; };
-            for (int j = 0; j < max_per_base; ++j) {
-                const uint64_t r = rng64(seed_b, 0x5E1EC7ull + slot_b, (uint64_t)j);
-                const int k = j + (int)mulhi64(r, (uint64_t)(nq - j));
-                const int vj = at(j), vk = at(k);
-                put(j, vk); put(k, vj);
-                add_pick(b, vk, 0);
-            }
-        }
-    }
-    if (!device_picks) first_job[nbases] = job_base.size();
-    const size_t n = device_picks ? n_dev : job_base.size();
+    const size_t nbases = c->bases.size(), n_tr = batch ? c->trial_first_base.size() : 0;     // n_tr: trials + 1
+    // 2. the pick table, 3. the picks when the host draws them (the quads themselves are produced on the device).  n > 0: some base has quads
+    CandLayout L(nbases, n_tr);
+    if ((rc = ensure_pinned(c, (size_t)PIN_VAR + L.var.total))) return rc;
+    char* pin_var = (char*)c->h_pin + PIN_VAR;
+    uint4* table = Carve::at<uint4>(pin_var, L.table);
+    uint4* trial = batch ? Carve::at<uint4>(pin_var, L.trial) : NULL;
+    size_t n = 0;
+    if ((rc = build_pick_table(c, max_per_base, table, trial, &n))) return rc;
+    std::vector<Pick> picks;
+    std::vector<int> job_base;   // per job: the slot of its base in its own trial (what its candidates carry)
+    if (!device_picks) draw_picks_host(table, trial, nbases, seed, max_per_base, &picks, &job_base);
     c->timing[1].lap(device_picks ? "pick table (host)" : "small bases enqueued + host picks");
-    tick("host picks");
     clear_candidates(c);
     c->best_lcp = 0; c->best_index = -1;
-    if (n) {
-        // candidates stay on the device: jobs -> transforms -> order-preserving compaction of the accepted ones
-        const size_t jb = al256(n * sizeof(XformJob)), tb = n * 64, ob = al256((n + 1) * 4);
-        size_t scan_tmp = 0;
-        STOCS_HIP_CHECK(exclusive_scan(NULL, scan_tmp, (const uint32_t*)NULL, (uint32_t*)NULL, n + 1, c->stream));
-        scan_tmp = al256(scan_tmp);
-        const size_t pb = device_picks ? al256(n * 16) + 2 * tab_bytes : 0;   // picks + the two tables
-        const size_t trb = batch ? al256(8 * n_tr) : 0;                        // first jobs of the trials + their candidate offsets
-        int rc = ensure_scratch(c, jb + 2 * tb + 3 * ob + scan_tmp + pb + trb);
-        if (rc) return rc;
-        if (!device_picks && (rc = ensure_pinned(c, (size_t)PIN_VAR + 2 * tab_bytes + 4 * n_tr + 256))) return rc;
-        if ((size_t)c->cand_cap < n) {
-            if (c->d_cand) { STOCS_HIP_CHECK(hipStreamSynchronize(c->stream)); (void)hipFree(c->d_cand); c->d_cand = NULL; }
-            c->cand_cap = (int)(n + n / 4 + 1024);
-            c->cand_bytes = (size_t)c->cand_cap * (16 + 16 + 1 + 1) * 4;
-            STOCS_HIP_CHECK(dev_malloc((void**)&c->d_cand, c->cand_bytes));
-        }
-        c->timing[1].lap("buffers (scratch, pinned, candidate block)");
-        if (!c->d_best) STOCS_HIP_CHECK(dev_malloc((void**)&c->d_best, 8));
-        char* base = (char*)c->d_scratch;
-        XformJob* dJ = (XformJob*)base;
-        float* dT = (float*)(base + jb);
-        float* dP = (float*)(base + jb + tb);
-        int32_t* dO = (int32_t*)(base + jb + 2 * tb);          // n + 1 flags (the last one is 0)
-        int32_t* dPos = (int32_t*)(base + jb + 2 * tb + ob);   // their exclusive scan; dPos[n] = accepted count
-        int32_t* dB = (int32_t*)(base + jb + 2 * tb + 2 * ob);
-        void* dTmp = base + jb + 2 * tb + 3 * ob;
-        const unsigned int* d_unresolved = NULL;
-        const int32_t* d_picks = NULL;
-        if (device_picks) {
-            char* pk = base + jb + 2 * tb + 3 * ob + scan_tmp;
-            uint4* d_table = (uint4*)(pk + al256(n * 16));
-            d_picks = (const int32_t*)pk;
-            const size_t lds = (size_t)(2 * (hmask + 1) + ((max_per_base + 1) & ~1)) * 4 + (size_t)max_per_base * 8;
-            // The table goes up on the MAIN stream: a host-to-device copy of a few hundred kilobytes enqueued on the otherwise idle auxiliary
-            // stream blocked the calling thread for 5.6 ms (64 trials of the ycb frame: 195 KB; measured, profiles/r04_trials_steps.json),
-            // the same copy on the stream that carries the rest of the call's work returns at once.  The draws then run on the auxiliary
-            // stream behind an event, next to the small bases' materialisation, which is enqueued behind the copy.
-            STOCS_HIP_CHECK(hipMemcpyAsync(d_table, (char*)c->h_pin + PIN_VAR, batch ? 2 * tab_bytes : 16 * nbases, hipMemcpyHostToDevice, c->stream));
-            STOCS_HIP_CHECK(hipEventRecord(c->ev_fork, c->stream));
-            STOCS_HIP_CHECK(hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
-            c->audit.use(0, d_table, true, "pick table", "table upload"); c->audit.record(c->ev_fork, 0); c->audit.wait(1, c->ev_fork);
-            if (!c->bases.empty()) { const int rc0 = stocs_internal_prepare_small(c, max_per_base); if (rc0) return rc0; }
-            hipLaunchKernelGGL(draw_picks_kernel, dim3((unsigned)c->bases.size()), dim3(256), lds, c->aux_stream, (const uint4*)d_table,
-                               batch ? (const uint4*)((char*)d_table + tab_bytes) : (const uint4*)NULL, seed, max_per_base, hmask, (int4*)pk, dB);
-            STOCS_HIP_CHECK(hipGetLastError());
-            STOCS_HIP_CHECK(hipEventRecord(c->ev_join, c->aux_stream));
-            STOCS_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-            c->audit.use(1, d_table, false, "pick table", "draw picks"); c->audit.use(1, pk, true, "picks", "draw picks"); c->audit.use(1, dB, true, "job bases", "draw picks");
-            c->audit.record(c->ev_join, 1); c->audit.wait(0, c->ev_join);
-        }
-        c->timing[1].lap("enqueue pick table upload + small bases + draws (auxiliary stream)");
-        rc = stocs_internal_make_jobs(c, device_picks ? NULL : picks.data(), d_picks, (int)n, dJ, &d_unresolved);
-        if (rc) return rc;
-        c->timing[1].lap("enqueue resolve");
-        tick("resolve picks");
-        if (!device_picks) STOCS_HIP_CHECK(hipMemcpyAsync(dB, job_base.data(), n * 4, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(rigid_transform_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_spos, c->d_mpos, dJ, (int)n,
-                           c->centroid_scene, c->centroid_model, dT, dP, dO);
-        STOCS_HIP_CHECK(hipGetLastError());
-        STOCS_HIP_CHECK(exclusive_scan(dTmp, scan_tmp, (const uint32_t*)dO, (uint32_t*)dPos, n + 1, c->stream));
-        hipLaunchKernelGGL(compact_candidates_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const float4*)dT, (const float4*)dP, dO, dPos, dB,
-                           (int)n, (float4*)cand_T(c), (float4*)cand_P(c), cand_lcp(c), cand_base(c), c->d_best);
-        c->best_is_zero = true;
-        STOCS_HIP_CHECK(hipGetLastError());
-        int32_t* rb = (int32_t*)((char*)c->h_pin + PIN_TRANSFORMS);   // pinned read-back slot: accepted count, unresolved picks
-        rb[0] = 0; rb[1] = 0;
-        int32_t* tr_pin = (int32_t*)((char*)c->h_pin + PIN_VAR + 2 * tab_bytes);   // batch: first job of every trial in, first candidate of every trial out
-        if (batch) {
-            int32_t* d_tr = (int32_t*)(base + jb + 2 * tb + 3 * ob + scan_tmp + pb);
-            for (size_t t = 0; t < n_tr; ++t) tr_pin[t] = (int32_t)first_job[(size_t)c->trial_first_base[t]];
-            STOCS_HIP_CHECK(hipMemcpyAsync(d_tr, tr_pin, 4 * n_tr, hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(gather_i32_kernel, dim3((unsigned)((n_tr + 255) / 256)), dim3(256), 0, c->stream, (const int32_t*)dPos, (const int32_t*)d_tr, (int)n_tr, d_tr + n_tr);
-            STOCS_HIP_CHECK(hipGetLastError());
-            STOCS_HIP_CHECK(hipMemcpyAsync(tr_pin, d_tr + n_tr, 4 * n_tr, hipMemcpyDeviceToHost, c->stream));
-        }
-        STOCS_HIP_CHECK(hipMemcpyAsync(&rb[0], dPos + n, 4, hipMemcpyDeviceToHost, c->stream));
-        if (d_unresolved) STOCS_HIP_CHECK(hipMemcpyAsync(&rb[1], d_unresolved, 4, hipMemcpyDeviceToHost, c->stream));
-        c->audit.use(0, d_picks, false, "picks", "resolve picks"); c->audit.use(0, dB, false, "job bases", "compact candidates");
-        c->timing[1].lap("enqueue transform/scan/compact + read-backs");
-        STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));   // the one synchronisation point of this call
-        c->audit.host_sync(0);
-        if (!c->audit.violations.empty()) {
-            set_error("stocs_make_transforms: %zu stream-ordering violation(s); first: %s", c->audit.violations.size(), c->audit.violations[0].c_str());
-            c->audit.violations.clear();
-            return STOCS_ERR_STATE;
-        }
-        c->timing[1].lap("wait for the device");
-        const int32_t n_ok = rb[0];
-        const unsigned int n_unresolved = (unsigned int)rb[1];
-        if (n_unresolved) { set_error("stocs_make_transforms: %u picks could not be resolved (internal inconsistency)", n_unresolved); return STOCS_ERR_STATE; }
-        c->n_cands = n_ok;
-        c->cands_stale = n_ok > 0;
-        if (batch) c->trial_cand_off.assign(tr_pin, tr_pin + n_tr);
-        tick("transform+compact");
+    // 4. buffers.  Candidates stay on the device: jobs -> transforms -> order-preserving compaction of the accepted ones
+    size_t scan_tmp = 0;
+    STOCS_HIP_CHECK(exclusive_scan(NULL, scan_tmp, (const uint32_t*)NULL, (uint32_t*)NULL, n + 1, c->stream));
+    scan_tmp = al256(scan_tmp);
+    L.carve_scratch(n, scan_tmp, device_picks ? n : 0);
+    if ((rc = ensure_scratch(c, L.dev.total))) return rc;
+    if ((size_t)c->cand_cap < n) {
+        if (c->d_cand) { STOCS_HIP_CHECK(hipStreamSynchronize(c->stream)); (void)hipFree(c->d_cand); c->d_cand = NULL; }
+        c->cand_cap = (int)(n + n / 4 + 1024);
+        c->cand_bytes = (size_t)c->cand_cap * (16 + 16 + 1 + 1) * 4;
+        STOCS_HIP_CHECK(dev_malloc((void**)&c->d_cand, c->cand_bytes));
     }
+    c->timing[1].lap("buffers (scratch, pinned, candidate block)");
+    if (!c->d_best) STOCS_HIP_CHECK(dev_malloc((void**)&c->d_best, 8));
+    XformJob* dJ = Carve::at<XformJob>(c->d_scratch, L.jobs);
+    float *dT = Carve::at<float>(c->d_scratch, L.T), *dP = Carve::at<float>(c->d_scratch, L.P);
+    int32_t* dO = Carve::at<int32_t>(c->d_scratch, L.ok);        // n + 1 flags (the last one is 0)
+    int32_t* dPos = Carve::at<int32_t>(c->d_scratch, L.pos);     // their exclusive scan; dPos[n] = accepted count
+    int32_t* dB = Carve::at<int32_t>(c->d_scratch, L.job_base);
+    const Pick* d_picks = NULL;
+    // 3. the picks when the device draws them: behind the upload of the pick table
+    if (device_picks) {
+        if ((rc = enqueue_device_picks(c, L, batch, seed, max_per_base))) return rc;
+        d_picks = Carve::at<Pick>(c->d_scratch, L.picks);
+    }
+    c->timing[1].lap("enqueue pick table upload + small bases + draws (auxiliary stream)");
+    // 5. resolve: picks -> jobs
+    const unsigned int* d_unresolved = NULL;
+    if ((rc = stocs_internal_make_jobs(c, picks.data(), d_picks, (int)n, dJ, &d_unresolved))) return rc;
+    c->timing[1].lap("enqueue resolve");
+    // 6. transform, scan, compact
+    if (!device_picks) STOCS_HIP_CHECK(hipMemcpyAsync(dB, job_base.data(), n * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(rigid_transform_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_spos, c->d_mpos, dJ, (int)n,
+                       c->centroid_scene, c->centroid_model, dT, dP, dO);
+    STOCS_HIP_CHECK(hipGetLastError());
+    STOCS_HIP_CHECK(exclusive_scan(Carve::at<void>(c->d_scratch, L.scan), scan_tmp, (const uint32_t*)dO, (uint32_t*)dPos, n + 1, c->stream));
+    hipLaunchKernelGGL(compact_candidates_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, (const float4*)dT, (const float4*)dP, dO, dPos, dB,
+                       (int)n, (float4*)cand_T(c), (float4*)cand_P(c), cand_lcp(c), cand_base(c), c->d_best);
+    c->best_is_zero = true;
+    STOCS_HIP_CHECK(hipGetLastError());
+    // 7. read-backs: accepted count and unresolved picks into their pinned slot; batch: first job of every trial in, first candidate out
+    int32_t* rb = (int32_t*)((char*)c->h_pin + PIN_TRANSFORMS);
+    rb[0] = 0; rb[1] = 0;
+    int32_t* tr_pin = Carve::at<int32_t>(pin_var, L.words);
+    if (batch) {
+        int32_t* d_tr = Carve::at<int32_t>(c->d_scratch, L.var_at + L.words);
+        for (size_t t = 0; t < n_tr; ++t) { const size_t b = (size_t)c->trial_first_base[t]; tr_pin[t] = (int32_t)(b < nbases ? table[b].x : n); }
+        STOCS_HIP_CHECK(hipMemcpyAsync(d_tr, tr_pin, 4 * n_tr, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(gather_i32_kernel, dim3((unsigned)((n_tr + 255) / 256)), dim3(256), 0, c->stream, (const int32_t*)dPos, (const int32_t*)d_tr, (int)n_tr, d_tr + n_tr);
+        STOCS_HIP_CHECK(hipGetLastError());
+        STOCS_HIP_CHECK(hipMemcpyAsync(tr_pin + n_tr, d_tr + n_tr, 4 * n_tr, hipMemcpyDeviceToHost, c->stream));
+    }
+    STOCS_HIP_CHECK(hipMemcpyAsync(&rb[0], dPos + n, 4, hipMemcpyDeviceToHost, c->stream));
+    if (d_unresolved) STOCS_HIP_CHECK(hipMemcpyAsync(&rb[1], d_unresolved, 4, hipMemcpyDeviceToHost, c->stream));
+    c->audit.use(0, d_picks, false, "picks", "resolve picks"); c->audit.use(0, dB, false, "job bases", "compact candidates");
+    c->timing[1].lap("enqueue transform/scan/compact + read-backs");
+    // 8. the one synchronisation point of this call
+    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    c->audit.host_sync(0);
+    if (!c->audit.violations.empty()) {
+        set_error("stocs_make_transforms: %zu stream-ordering violation(s); first: %s", c->audit.violations.size(), c->audit.violations[0].c_str());
+        c->audit.violations.clear();
+        return STOCS_ERR_STATE;
+    }
+    c->timing[1].lap("wait for the device");
+    // 9. bookkeeping
+    const unsigned int n_unresolved = (unsigned int)rb[1];
+    if (n_unresolved) { set_error("stocs_make_transforms: %u picks could not be resolved (internal inconsistency)", n_unresolved); return STOCS_ERR_STATE; }
+    c->n_cands = rb[0];
+    c->cands_stale = c->n_cands > 0;
+    if (batch) c->trial_cand_off.assign(tr_pin + n_tr, tr_pin + 2 * n_tr);
     if (n_candidates) *n_candidates = c->n_cands;
     return STOCS_OK;
 }
