@@ -135,6 +135,37 @@ int stocs_weight_fix_check(stocs_ctx* ctx, int64_t* n_mismatch);
 int stocs_try_sampled_base(stocs_ctx* ctx, int32_t* ids4_inout, float* inv2, int* valid);
 /* the seeded weighted draw itself (stocs.cpp:133-148 replacement): index or -1 */
 int stocs_draw(stocs_ctx* ctx, const float* w, int n, uint64_t r64, int* index);
+/* Which kernel form the last class-mode stocs_sample_bases or stocs_run_trials* call on the context ran (tests only; no device
+ * work, no synchronisation, no allocation; any output pointer may be NULL).  STOCS_ERR_STATE before the first such call.
+ *   *kernel     one of the STOCS_FORM_* values below
+ *   *threads    threads per workgroup of the attempts kernel
+ *   *lds_bytes  its dynamic LDS per workgroup
+ *   *cap        survivors of pass 1 the lean kernel's list holds (an attempt with more is redone by the full-size kernel)
+ *   *launches   launches of the attempts kernel (the redo of overflowed attempts not counted)
+ *   *redone     attempts redone after a lean overflow
+ * The rule, for a scene of S points (a16(x) = x rounded up to a multiple of 16):
+ *   STOCS_CLASS_MULTI_KERNEL set: NINE_LAUNCH (stocs_sample_bases only); threads = lds_bytes = cap = launches = 0.
+ *   The lean kernel is taken when 64 <= S <= 26000, neither STOCS_CLASS_FULL_KERNEL nor STOCS_INSTANCE_NO_LDS is set, and the call
+ *   is a trial batch, or has more than 256 attempts, or finds the prior's prefix sums current (an earlier lean call since the last
+ *   stocs_ctx_set_scene / stocs_reset_trial), or STOCS_CLASS_LEAN_KERNEL is set.  Then
+ *     threads   = 256 for S <= 8000, 512 for S <= 24000, else 1024; STOCS_CLASS_LEAN_512 makes 256 into 512 and
+ *                 STOCS_CLASS_LEAN_1024 makes both into 1024;
+ *     lds_bytes = max(a16(2 S), min(top, a16(6 S + 16))) with top = 16384, 36864, 76800 for 256, 512, 1024 threads;
+ *     cap       = min(S + 1, (lds_bytes - 8) / 6) rounded down to an even number; STOCS_CLASS_LEAN_CAP = v lowers it to
+ *                 max(2, v rounded down to an even number);
+ *     launches  = 1.
+ *   Otherwise the full-size kernel, 1024 threads, cap = 0:
+ *     S <= 26000 and STOCS_INSTANCE_NO_LDS unset: FULL_LDS, lds_bytes = a16(4 S) + 2 S + 16, launches = 1;
+ *     else FULL_DEVICE_MEMORY, lds_bytes = 0; stocs_sample_bases: launches = 1; a trial batch of n attempts in all runs
+ *     p = max(1, min(n, floor(2^30 / (8 S)))) attempts per launch (at most 1 GiB of working set): launches = ceil(n / p). */
+enum { STOCS_FORM_LEAN = 0, STOCS_FORM_FULL_LDS = 1, STOCS_FORM_FULL_DEVICE_MEMORY = 2, STOCS_FORM_NINE_LAUNCH = 3 };
+int stocs_last_sampling_form(const stocs_ctx* ctx, int* kernel, int* threads, int64_t* lds_bytes, int* cap, int* launches, int* redone);
+/* Point 1 of the lean class kernel on its own (tests only): index[k] = the point the lean kernel draws first for the 64-bit word
+ * r64[k] against the context's current prior -- the first scene index whose inclusive prefix sum of the 2^32 fixed-point prior
+ * weights exceeds mulhi64(r64[k], total) -- or -1 when the total is zero.  Brings the prior's prefix sums up to date as a lean call
+ * would, then runs the kernel's own search, one wavefront per word.  STOCS_ERR_STATE without a scene, STOCS_ERR_INVALID for a
+ * scene outside 64 <= S <= 32768 (the sizes the lean kernel is compiled for). */
+int stocs_debug_draw_point1(stocs_ctx* ctx, const uint64_t* r64, int n, int32_t* index);
 
 /* ---- congruent sets: find_congruent_sets_on_model (stocs.cpp:753-869) for every base of the base
  * set at once (per-base COUNTS; quads are produced on demand); then per-base read-back:

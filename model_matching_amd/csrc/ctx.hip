@@ -537,6 +537,7 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
     c->lcp_order = getenv("STOCS_LCP_ORDER") ? atoi(getenv("STOCS_LCP_ORDER")) : 1;
     c->exact_ties = 0; c->kd_ready = false; c->d_kd_nodes = NULL; c->d_kd_pts = NULL; c->d_ties = NULL; c->ties_started = false;
     c->cdf_n = 0; c->prior_epoch = 1; c->cdf_epoch = 0;
+    c->last_form.kernel = -1; c->last_form.threads = 0; c->last_form.lds = 0; c->last_form.cap = 0; c->last_form.launches = 0; c->last_form.redone = 0;
     memset(&c->grid, 0, sizeof(c->grid));
     c->d_spos = c->d_snrmw = c->d_mpos = c->d_mnrm = c->d_munit = c->d_mpos_raw = c->d_mpos_s = c->d_mnrm_s = NULL;
     c->d_spix = NULL; c->d_mperm = NULL; c->d_mpatch = NULL; c->d_msub = NULL; c->d_scene_mem = NULL; c->scene_cap = 0;

@@ -1225,6 +1225,37 @@ __global__ __launch_bounds__(256) void prior_fix_kernel(const float4* __restrict
     if (i <= S) fix[i] = i < S ? weight_fix_dev(spos[i].w) : 0ull;      // (S + 1 entries: the exclusive scan's last one is the total)
 }
 
+
+// Point 1 of the lean kernel: the first index whose inclusive prefix cdf[i] exceeds r, for r < cdf[S - 1] (so the total is not zero), by
+// one whole wavefront: a 64-ary search, three dependent loads for any S <= LEAN_MAX_S.  Zero weights repeat their predecessor's prefix
+// and are never the first to exceed r.  The lean kernel and stocs_debug_draw_point1 (draw_point1_kernel) both call this.
+__device__ __forceinline__ int search_prior_cdf(const unsigned long long* __restrict__ cdf, int S, unsigned long long r, int lane) {
+    int lo = 0, hi = S - 1;                              // cdf[hi] > r; the answer -- the first index whose prefix exceeds r -- lies in [lo, hi]
+    while (lo < hi) {
+        const int len = hi - lo + 1, step = (len + 63) >> 6;
+        const int pidx = lo + lane * step;
+        const bool f = pidx <= hi ? (cdf[pidx] > r) : true;
+        const unsigned long long m = __ballot(f);
+        if (m == 0ull) { lo = lo + 63 * step + 1; continue; }     // (every probe below hi and none exceeds r: the answer is behind the last probe)
+        const int k = (int)__builtin_ctzll(m);
+        hi = min(lo + k * step, hi);
+        lo = k ? lo + (k - 1) * step + 1 : lo;
+        if (k == 0) hi = lo;
+    }
+    return lo;
+}
+// stocs_debug_draw_point1: one wavefront per caller-given 64-bit word, against the same table the lean kernel reads
+__global__ __launch_bounds__(64) void draw_point1_kernel(const unsigned long long* __restrict__ cdf_excl, int S, const uint64_t* __restrict__ r64,
+                                                         int n, int32_t* __restrict__ index) {
+    const int b = blockIdx.x, lane = threadIdx.x & 63;
+    if (b >= n) return;
+    const unsigned long long* cdf = cdf_excl + 1;                    // inclusive prefix of point i
+    const unsigned long long total = cdf[S - 1];
+    int pick = -1;
+    if (total != 0ull) pick = search_prior_cdf(cdf, S, mulhi64(r64[b], total), lane);
+    if (lane == 0) index[b] = pick;
+}
+
 template <int NT>
 __global__ __launch_bounds__(NT, 8) void class_attempts_lean_kernel(ClassArgs A, uint64_t seed, int first_attempt, int n_attempts,
                                                                       const unsigned long long* __restrict__ cdf_excl, int cap) {
@@ -1257,22 +1288,7 @@ __global__ __launch_bounds__(NT, 8) void class_attempts_lean_kernel(ClassArgs A,
         if (wv == 0) {
             const unsigned long long total = cdf[S - 1];
             int pick = -1;
-            if (total != 0ull) {
-                const unsigned long long r = mulhi64(rng64(seed, (uint64_t)attempt, 0), total);
-                int lo = 0, hi = S - 1;                              // cdf[hi] > r; the answer -- the first index whose prefix exceeds r -- lies in [lo, hi]
-                while (lo < hi) {
-                    const int len = hi - lo + 1, step = (len + 63) >> 6;
-                    const int pidx = lo + lane * step;
-                    const bool f = pidx <= hi ? (cdf[pidx] > r) : true;
-                    const unsigned long long m = __ballot(f);
-                    if (m == 0ull) { lo = lo + 63 * step + 1; continue; }     // (every probe below hi and none exceeds r: the answer is behind the last probe)
-                    const int k = (int)__builtin_ctzll(m);
-                    hi = min(lo + k * step, hi);
-                    lo = k ? lo + (k - 1) * step + 1 : lo;
-                    if (k == 0) hi = lo;
-                }
-                pick = lo;
-            }
+            if (total != 0ull) pick = search_prior_cdf(cdf, S, mulhi64(rng64(seed, (uint64_t)attempt, 0), total), lane);
             if (lane == 0) sh_b1 = pick;
         }
     }
@@ -1393,6 +1409,15 @@ static ClassForm choose_class_form(const stocs_ctx* c, bool prefer_lean) {
     return f;
 }
 
+// what stocs_last_sampling_form reports of a class-mode call: its form and the launches of the attempts kernel (redo_lean_overflows adds the
+// attempts it redid).  Host bookkeeping only.
+static_assert((int)CLASS_LEAN == STOCS_FORM_LEAN && (int)CLASS_FULL_LDS == STOCS_FORM_FULL_LDS && (int)CLASS_FULL_DEVICE_MEMORY == STOCS_FORM_FULL_DEVICE_MEMORY,
+              "stocs_hip.h names the kernels of ClassKernel");
+static void record_form(stocs_ctx* c, const ClassForm& f, int launches) {
+    c->last_form.kernel = (int)f.kernel; c->last_form.threads = f.threads; c->last_form.lds = f.lds; c->last_form.cap = f.cap;
+    c->last_form.launches = launches; c->last_form.redone = 0;
+}
+
 // n_workgroups attempts through the kernel of `f` -- the only code that names the instantiations of the one-launch class kernels
 static int launch_class_attempts(stocs_ctx* c, ClassArgs A, unsigned n_workgroups, uint64_t seed, int first_attempt, const ClassForm& f) {
     const void* fn = NULL;
@@ -1418,6 +1443,7 @@ static int launch_class_attempts(stocs_ctx* c, ClassArgs A, unsigned n_workgroup
 static int redo_lean_overflows(stocs_ctx* c, ClassArgs A, uint64_t seed, int first_attempt, BaseOut* res_host, size_t n, int32_t* d_slots) {
     std::vector<int32_t> slots;
     for (size_t i = 0; i < n; ++i) if (res_host[i].pad == 1) slots.push_back((int32_t)i);
+    c->last_form.redone = (int)slots.size();
     if (slots.empty()) return STOCS_OK;
     int rc = STOCS_OK;
     do {
@@ -1434,12 +1460,16 @@ static int redo_lean_overflows(stocs_ctx* c, ClassArgs A, uint64_t seed, int fir
 
 // class mode through the one-launch kernel; scenes beyond the LDS working set keep it in device memory (same code)
 static int sample_class(stocs_ctx* c, uint64_t seed, int first_attempt, int nB, int32_t* ids, float* inv, int32_t* valid) {
-    if (getenv("STOCS_CLASS_MULTI_KERNEL")) return sample_class_multi(c, seed, first_attempt, nB, ids, inv, valid);   // the nine-launch form (A/B)
+    if (getenv("STOCS_CLASS_MULTI_KERNEL")) {   // the nine-launch form (A/B)
+        c->last_form.kernel = STOCS_FORM_NINE_LAUNCH; c->last_form.threads = 0; c->last_form.lds = 0; c->last_form.cap = 0; c->last_form.launches = 0; c->last_form.redone = 0;
+        return sample_class_multi(c, seed, first_attempt, nB, ids, inv, valid);
+    }
     const size_t S = (size_t)c->nS;
     const bool dbg = getenv("STOCS_DEBUG_TIMING") != NULL;
     const bool cdf_current = c->cdf.p && c->cdf_epoch == c->prior_epoch && c->cdf_n == S;
     const ClassForm form = choose_class_form(c, !dbg && (nB > 256 || cdf_current || getenv("STOCS_CLASS_LEAN_KERNEL")));   // (the reasons: at choose_class_form)
     const bool lean = form.kernel == CLASS_LEAN, wlds = form.kernel != CLASS_FULL_DEVICE_MEMORY;
+    record_form(c, form, 1);
     const size_t b_res = al256((size_t)nB * sizeof(BaseOut)), b_w = wlds ? 0 : al256((size_t)nB * S * 4), b_sv = wlds ? 0 : al256((size_t)nB * S * 4), b_slots = al256((size_t)nB * 4);
     int rc = ensure_scratch(c, b_res + b_w + b_sv + b_slots + 256);
     if (rc) return rc;
@@ -1733,6 +1763,7 @@ int sample_trials(stocs_ctx* c, int mode, int nT, const uint64_t* seeds, int nA,
         const bool lean = form.kernel == CLASS_LEAN, wlds = form.kernel != CLASS_FULL_DEVICE_MEMORY;
         // scenes beyond the LDS working set keep 8 bytes per (attempt, point) in device memory: at most ~1 GB of it per launch
         const size_t per_launch = wlds ? nW : std::max<size_t>(1, std::min<size_t>(nW, ((size_t)1 << 30) / (S * 8)));
+        record_form(c, form, (int)((nW + per_launch - 1) / per_launch));
         const size_t b_res = al256(nW * sizeof(BaseOut)), b_seed = al256((size_t)nT * 8), b_w = wlds ? 0 : al256(per_launch * S * 4), b_slots = al256(nW * 4);
         int rc = ensure_scratch(c, b_res + b_seed + 2 * b_w + b_slots);
         if (rc) return rc;
@@ -1967,6 +1998,38 @@ int stocs_weight_fix_check(stocs_ctx* c, int64_t* n_mismatch) {
     STOCS_HIP_CHECK(hipMemcpyAsync(&h, d_counts, 4, hipMemcpyDeviceToHost, c->stream));
     STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
     *n_mismatch = h;
+    return STOCS_OK;
+}
+
+int stocs_last_sampling_form(const stocs_ctx* c, int* kernel, int* threads, int64_t* lds_bytes, int* cap, int* launches, int* redone) {
+    if (!c) return STOCS_ERR_INVALID;
+    if (c->last_form.kernel < 0) { set_error("stocs_last_sampling_form: no class-mode sampling call on this context yet"); return STOCS_ERR_STATE; }
+    if (kernel) *kernel = c->last_form.kernel;
+    if (threads) *threads = c->last_form.threads;
+    if (lds_bytes) *lds_bytes = (int64_t)c->last_form.lds;
+    if (cap) *cap = c->last_form.cap;
+    if (launches) *launches = c->last_form.launches;
+    if (redone) *redone = c->last_form.redone;
+    return STOCS_OK;
+}
+
+int stocs_debug_draw_point1(stocs_ctx* c, const uint64_t* r64, int n, int32_t* index) {
+    if (!c || n < 0 || (n && (!r64 || !index))) return STOCS_ERR_INVALID;
+    if (c->nS <= 0 || !c->d_spos) { set_error("stocs_debug_draw_point1: no scene"); return STOCS_ERR_STATE; }
+    if (c->nS < 64 || c->nS > LEAN_MAX_S) { set_error("stocs_debug_draw_point1: the lean kernel takes scenes of 64 to %d points", LEAN_MAX_S); return STOCS_ERR_INVALID; }
+    if (n == 0) return STOCS_OK;
+    DeviceGuard dev_guard(c->device);
+    const size_t b_r = al256((size_t)n * 8);
+    int rc = ensure_scratch(c, b_r + al256((size_t)n * 4));
+    if (rc) return rc;
+    if ((rc = ensure_prior_cdf(c))) return rc;
+    uint64_t* d_r = (uint64_t*)c->d_scratch;
+    int32_t* d_idx = (int32_t*)((char*)c->d_scratch + b_r);
+    STOCS_HIP_CHECK(hipMemcpyAsync(d_r, r64, (size_t)n * 8, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(draw_point1_kernel, dim3((unsigned)n), dim3(64), 0, c->stream, (const unsigned long long*)c->cdf.p, c->nS, (const uint64_t*)d_r, n, d_idx);
+    STOCS_HIP_CHECK(hipGetLastError());
+    STOCS_HIP_CHECK(hipMemcpyAsync(index, d_idx, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
     return STOCS_OK;
 }
 

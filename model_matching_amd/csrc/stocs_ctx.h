@@ -363,6 +363,10 @@ struct stocs_ctx {
     size_t scratch_bytes;
 
     void* depth;    // depth.hip (DepthState): the frame of stocs_ctx_set_frame and stocs_depth_check_poses's grow-only workspace (last: no other member moves)
+
+    // what the last class-mode stocs_sample_bases / stocs_run_trials* call ran (sample.hip; read by stocs_last_sampling_form): host
+    // bookkeeping only.  kernel < 0: no class-mode call yet
+    struct { int kernel, threads; size_t lds; int cap, launches, redone; } last_form;
 };
 
 namespace stocs {

@@ -171,6 +171,22 @@ class StocsEstimator:
         capi.check(self.L.stocs_draw(self.h, pw, len(w), r64, C.byref(idx)))
         return idx.value
 
+    def last_sampling_form(self):
+        """-> dict(kernel, threads, lds_bytes, cap, launches, redone) of the last class-mode sample_bases / run_trials call
+        (stocs_last_sampling_form); kernel is one of capi.FORM_NAMES' names."""
+        k, t, cap, nl, nr = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
+        lds = C.c_int64(0)
+        capi.check(self.L.stocs_last_sampling_form(self.h, C.byref(k), C.byref(t), C.byref(lds), C.byref(cap), C.byref(nl), C.byref(nr)))
+        return dict(kernel=capi.FORM_NAMES[k.value], threads=t.value, lds_bytes=lds.value, cap=cap.value, launches=nl.value, redone=nr.value)
+
+    def debug_draw_point1(self, r64):
+        """-> the point the lean class kernel draws first for every 64-bit word of r64 against the current prior, -1 for a zero
+        total (stocs_debug_draw_point1)."""
+        r = np.ascontiguousarray(r64, np.uint64)
+        idx = np.zeros(len(r), np.int32)
+        capi.check(self.L.stocs_debug_draw_point1(self.h, r.ctypes.data_as(C.POINTER(C.c_uint64)), len(r), idx.ctypes.data_as(capi._ip)))
+        return idx
+
     # ---- congruent sets (stocs.hpp:93-96) ----
     def find_congruent_all(self):
         n = C.c_int64(0)

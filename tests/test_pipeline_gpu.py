@@ -105,6 +105,11 @@ def test_class_bases_equal_oracle(setup, path, monkeypatch):
     m, s, est, orc = setup
     seed, n = 4242, 40
     valid, ids, inv = est.sample_bases(seed, n)
+    form = est.last_sampling_form()                                  # the call took the form it is named for (stocs_last_sampling_form)
+    assert (form["kernel"], form["threads"]) == {"lean": ("lean", 256), "lean_overflow_redone": ("lean", 256), "lean_1024": ("lean", 1024),
+                                                 "one_launch_lds": ("full_lds", 1024), "one_launch_device_memory": ("full_device_memory", 1024),
+                                                 "nine_launches": ("nine_launch", 0)}[path], form
+    assert (form["cap"] == 64 and form["redone"] > 0) if path == "lean_overflow_redone" else form["redone"] == 0, form
     n_ok = 0
     for a in range(n):
         ok, oi, ov = orc.sample_class_base(seed, a)
