@@ -671,6 +671,47 @@ public:
         return r;
     }
 
+    // Multi-instance selection (stocs_select_instances; no reference counterpart): which of the camera-frame hypotheses (the
+    // hypotheses of run_trials, refined or not) are distinct instances of the object and which are one instance found twice.  Walked
+    // best first, a hypothesis is kept only if enough of the scene points it explains are explained by none kept before it.  One record
+    // per hypothesis in input order, and the indices of the kept ones in rank order in *selected.  The poses go to the centred frame in
+    // float, as the tracking entry point brings its priors there: same linear part, t = (t_camera - c_scene) + R c_model.  Empty on
+    // error (the text goes to the log).
+    static stocs_instance_params default_instance_params() {
+        stocs_instance_params p;
+        stocs_default_instance_params(&p);
+        return p;
+    }
+    std::vector<stocs_instance_result> select_instances(const std::vector<PoseCandidate*>& poses, std::vector<int>* selected,
+                                                        const stocs_instance_params& prm = default_instance_params()) {
+        const int n = (int)poses.size();
+        float cs[3], cm[3];
+        stocs_get_centroids(ctx_, cs, cm);
+        std::vector<float> T((size_t)n * 16);
+        for (int i = 0; i < n; ++i) {
+            const float* P = poses[(size_t)i]->transform.data();
+            float* dst = &T[(size_t)i * 16];
+            bool zero = true;
+            for (int k = 0; k < 16; ++k) zero = zero && P[k] == 0.0f;
+            if (zero) { for (int k = 0; k < 16; ++k) dst[k] = 0.0f; continue; }   // a "no pose" record stays one
+            for (int c = 0; c < 3; ++c) { for (int r = 0; r < 3; ++r) dst[c * 4 + r] = P[c * 4 + r]; dst[c * 4 + 3] = 0.0f; }
+            for (int r = 0; r < 3; ++r) {
+                const float rcm = P[r] * cm[0] + (P[4 + r] * cm[1] + P[8 + r] * cm[2]);
+                dst[12 + r] = (P[12 + r] - cs[r]) + rcm;
+            }
+            dst[15] = 1.0f;
+        }
+        std::vector<stocs_instance_result> rec((size_t)n);
+        std::vector<int32_t> sel((size_t)std::max(1, std::min(prm.max_instances, n)));
+        int ns = 0;
+        if (stocs_select_instances(ctx_, T.data(), n, &prm, rec.data(), sel.data(), &ns) != STOCS_OK) {
+            *log_ << "select_instances failed: " << stocs_last_error() << std::endl;
+            rec.clear(); ns = 0;
+        }
+        if (selected) selected->assign(sel.begin(), sel.begin() + ns);
+        return rec;
+    }
+
 protected:
     std::vector<std::unique_ptr<PoseCandidate> > tracked_store_;   // results of the last track_poses
     std::unique_ptr<PoseCandidate> trial_best_;

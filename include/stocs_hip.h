@@ -519,6 +519,53 @@ typedef struct stocs_depth_result {
 void stocs_default_depth_params(stocs_depth_params* p);
 int stocs_depth_check_poses(stocs_ctx* ctx, const float* pose16_camera, int n, const stocs_depth_params* p, stocs_depth_result* out);
 
+/* ---- multi-instance selection (no reference counterpart: the reference returns one pose per object).  Of n hypotheses, which are
+ * distinct instances and which are one instance found twice: walk them best first and keep one only if enough of the scene points it
+ * explains are not explained by one kept before it.  stocs_select_instances takes n CENTRED-frame hypotheses (column-major, as
+ * stocs_score_transforms and stocs_refine_poses take them).  Integer set logic over the scoring kernel's match records; csrc/instances.hip,
+ * restated in numpy in tests/instances_ref.py, equal bit for bit:
+ *   1. Explained set.  E_h = { hit[i] : counted[i] != 0 } over the model points i, hit / counted being the records stocs_lcp_detail(T_h)
+ *      returns (exact_ties honoured): the distinct scene indices the context's own LCP launch counts for T_h.  Several model points
+ *      on one scene point count once; a hit that fails the normal test does not count.  own_h = |E_h|; lcp_h is that launch's score.
+ *   2. Invalid hypotheses.  One with a non-finite entry among its 16, or with all 16 zero (the "no pose" record of a trial batch), has
+ *      own = 0, lcp = 0 and is never selected.  It is not scored as a transform (the zero matrix maps the model onto the centroid).
+ *   3. Order.  Descending stocs_pack_best(lcp_h, h): higher score first, lower index first on equal score.  Scores that are not
+ *      positive (or NaN) all pack to 0 and come last, lower index first.
+ *   4. Walk.  In that order, covered = {} at the start, excl = |E_h \ covered|.  h is selected when excl >= min_points, and
+ *      (float)excl >= min_exclusive_fraction * (float)own_h (one IEEE float multiply, one compare, no contraction), and fewer than
+ *      max_instances are selected so far.  On selection covered |= E_h and h takes the next rank (0, 1, ...).
+ *   5. Output.  out[h] = { rank (-1: not selected), own, exclusive, lcp }.  exclusive of a selected hypothesis is excl at its selection;
+ *      of an unselected one |E_h \ covered_final|, what the chosen set leaves unexplained.  *n_selected (<= min(max_instances, n)) and
+ *      their indices in rank order in selected[] (capacity max_instances, or n if that is smaller).
+ * covered only grows, so a hypothesis that fails against the cover of some of its predecessors fails for good: the kernel tests
+ * sixteen pending hypotheses per round and the results above do not depend on that.  A hypothesis's own and lcp are bitwise independent
+ * of the batch it shares.
+ * n == 0: STOCS_OK, nothing selected.  NULL ctx / p / n_selected, NULL T16 / out / selected with n > 0, n < 0 or n > 16 384,
+ * max_instances < 1, min_points < 1, a fraction that is NaN, <= 0 or > 1: STOCS_ERR_INVALID.  No scene or no model on the context:
+ * STOCS_ERR_STATE.  A scene of more than 2^18 points: STOCS_ERR_CAPACITY (the explained sets are 32 KB bitsets in LDS).
+ * The detail rows are produced in chunks of hypotheses (256 MB of rows, as stocs_lcp_hit_count; STOCS_INSTANCES_CHUNK=<hypotheses> in
+ * the environment forces a chunk size).  Poses go up through the context's pinned block, everything runs on the context's stream,
+ * one pinned read-back and one synchronisation per call; own grow-only workspace on the context (a second call of the same or a
+ * smaller size allocates nothing).
+ * stocs_select_instances_rows runs steps 1 (the set arithmetic), 3, 4 and 5 on GIVEN detail rows: host arrays hit[n * nM],
+ * counted[n * nM], lcp[n] over nS scene points (nM, nS >= 1); step 2 does not apply.  It needs a context for the device and the
+ * workspace only, not its scene.  A counted row whose hit is negative or >= nS is STOCS_ERR_INVALID, checked on the host before
+ * anything is uploaded.  nS > 2^18: STOCS_ERR_CAPACITY.  A test and diagnosis facility (pageable copies). ---- */
+typedef struct stocs_instance_params {
+    int32_t max_instances;            /* >= 1: stop after this many (default 16)                                              */
+    int32_t min_points;               /* >= 1: scene points a hypothesis must explain that no selected one explains (default 20) */
+    float   min_exclusive_fraction;   /* in (0, 1]: ... as a share of all it explains (default 0.5)                           */
+} stocs_instance_params;
+typedef struct stocs_instance_result {
+    int32_t rank, own, exclusive;
+    float   lcp;
+} stocs_instance_result;
+void stocs_default_instance_params(stocs_instance_params* p);
+int stocs_select_instances(stocs_ctx* ctx, const float* T16_centred, int n, const stocs_instance_params* p, stocs_instance_result* out,
+                           int32_t* selected, int* n_selected);
+int stocs_select_instances_rows(stocs_ctx* ctx, const int32_t* hit, const uint8_t* counted, const float* lcp, int n, int nM, int nS,
+                                const stocs_instance_params* p, stocs_instance_result* out, int32_t* selected, int* n_selected);
+
 /* ---- tuning knobs (never change results beyond float summation order).
  * "lcp_variant": 99 = automatic (default): the scan fed from a per-wavefront LDS queue of the queries that have a list -- over
  *   index-ordered lists at cell edge epsilon (24, sparse scenes), over centre-sorted lists with triangle-inequality early exit

@@ -26,6 +26,11 @@
 // refinement ran -- scored against the frame's own depth image and class-probability map (stocs_depth_check_poses); one "depth t.i:"
 // line per hypothesis, and <out> is written from the first maximum of score - violation (ties: the higher lcp, then the lower trial
 // and hypothesis index) instead of the LCP winner.  Every other line is what the run prints without the flag.
+// --instances M [--instance-min-fraction f] [--instance-min-points p] (with --trials N --cluster 1 [--refine K]): the hypotheses of all
+// trials -- the refined poses when refinement ran -- go through stocs_select_instances in one call (at most M instances; f and p default
+// to the library's 0.5 and 20); one "instance r: trial.hyp own exclusive lcp" line per selected instance, and their poses, 3x4 row-major,
+// one per line in rank order, to pose_instances_<object>.txt next to <out> (<object>: the object name, with --clouds the model file's
+// name without its extension).  Every other line and file is what the run writes without the flag.
 // The reference edits its per-data-set constants in the source (README.md:42-66); here they are options with the
 // reference's YCB values as defaults.
 #include <algorithm>
@@ -77,7 +82,8 @@ static bool read_stcl(const std::string& path, std::vector<float>& pos, std::vec
 
 // everything after the estimator is built (:79-185): one run, or n_trials in one batch; lines to os, the pose to out_path
 static int run_search(stocs::stocs_estimator& stocs_ptr, std::ostream& os, const std::string& out_path, const std::string& dbg_dir, uint64_t seed, int n_trials,
-                      int exact_ties, int do_cluster, int n_refine, int depth_check = 0) {
+                      int exact_ties, int do_cluster, int n_refine, int depth_check = 0, const stocs_instance_params* instances = NULL,
+                      const std::string& instances_path = std::string()) {
     stocs_ptr.set_seed(seed);
     if (exact_ties) stocs_ptr.set_exact_ties(true);
 
@@ -175,6 +181,26 @@ static int run_search(stocs::stocs_estimator& stocs_ptr, std::ostream& os, const
             } else {
                 os << "depth check: hypotheses=0" << std::endl;
             }
+        }
+        if (instances) {
+            const std::vector<std::vector<PoseCandidate*> >& src = n_refine > 0 ? refined : hyps;
+            std::vector<PoseCandidate*> flat;
+            std::vector<std::pair<int, int> > id;
+            for (size_t t = 0; t < src.size(); ++t)
+                for (size_t i = 0; i < src[t].size(); ++i) { flat.push_back(src[t][i]); id.push_back(std::make_pair((int)t, (int)i)); }
+            std::vector<int> sel;
+            const std::vector<stocs_instance_result> rec = stocs_ptr.select_instances(flat, &sel, *instances);
+            if (rec.size() != flat.size()) { std::cerr << "instance selection failed: " << stocs_last_error() << std::endl; return 2; }
+            std::ofstream o(instances_path, std::ofstream::out);
+            for (size_t r = 0; r < sel.size(); ++r) {
+                const size_t k = (size_t)sel[r];
+                char b[192];
+                snprintf(b, sizeof(b), "instance %d: %d.%d own %d exclusive %d lcp %.9g", (int)r, id[k].first, id[k].second, rec[k].own, rec[k].exclusive, (double)rec[k].lcp);
+                os << b << std::endl;
+                for (int rr = 0; rr < 3; ++rr) for (int c = 0; c < 4; ++c) { snprintf(b, sizeof(b), "%.9g", (double)flat[k]->transform(rr, c)); o << b << (rr == 2 && c == 3 ? "" : " "); }
+                o << std::endl;
+            }
+            os << "instances: hypotheses=" << flat.size() << " selected=" << sel.size() << std::endl;
         }
         return 0;
     }
@@ -362,6 +388,8 @@ int main(int argc, char** argv) {
     std::string edge_path, out_path, dbg_dir, track_path;
     float track_min_lcp = 0.02f;
     int do_cluster = 0, n_trials = 0, exact_ties = 0, n_refine = 0, depth_check = 0;
+    bool do_instances = false;
+    stocs_instance_params inst_prm = stocs::stocs_estimator::default_instance_params();
     uint64_t seed = 1;
     for (int i = clouds ? 4 : 3; i < argc; i += 2) {
         if (std::string(argv[i]) == "--depth-check") { depth_check = 1; --i; continue; }   // the one option without a value
@@ -379,6 +407,9 @@ int main(int argc, char** argv) {
         else if (k == "--exact-ties") exact_ties = atoi(v.c_str());   // 1: the reference kd-tree's answer on exact distance ties (set_exact_ties)
         else if (k == "--track") track_path = v;   // track from this pose file; detection when the tracked lcp is below --track-min-lcp
         else if (k == "--track-min-lcp") track_min_lcp = (float)atof(v.c_str());
+        else if (k == "--instances") { do_instances = true; inst_prm.max_instances = atoi(v.c_str()); }
+        else if (k == "--instance-min-fraction") inst_prm.min_exclusive_fraction = (float)atof(v.c_str());
+        else if (k == "--instance-min-points") inst_prm.min_points = atoi(v.c_str());
         else if (k == "--repo") repo_path = v;
         else if (k == "--voxel") voxel_size = (float)atof(v.c_str());
         else if (k == "--depth-scale") depth_scale = (float)atof(v.c_str());
@@ -392,6 +423,11 @@ int main(int argc, char** argv) {
 
     if (depth_check && (clouds || n_trials <= 0 || !do_cluster || !track_path.empty() || a2.find(',') != std::string::npos)) {
         std::cerr << "--depth-check needs a scene directory, a single object, --trials N and --cluster 1" << std::endl;
+        return -1;
+    }
+
+    if (do_instances && (n_trials <= 0 || !do_cluster || !track_path.empty() || (!clouds && a2.find(',') != std::string::npos))) {
+        std::cerr << "--instances needs a single object, --trials N and --cluster 1" << std::endl;
         return -1;
     }
 
@@ -457,6 +493,19 @@ int main(int argc, char** argv) {
         std::cerr << e.what() << std::endl;  // no GPU => loud failure, never a CPU fallback
         return 2;
     }
+    std::string instances_path;
+    if (do_instances) {   // next to <out>
+        std::string object = a2;
+        if (clouds) {
+            const size_t sl = object.find_last_of('/');
+            if (sl != std::string::npos) object = object.substr(sl + 1);
+            const size_t dot = object.find_last_of('.');
+            if (dot != std::string::npos && dot > 0) object = object.substr(0, dot);
+        }
+        const size_t sl = out_path.find_last_of('/');
+        instances_path = (sl == std::string::npos ? std::string() : out_path.substr(0, sl + 1)) + "pose_instances_" + object + ".txt";
+    }
     if (!track_path.empty()) return run_track(*est, track_path, track_min_lcp, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine);
-    return run_search(*est, std::cout, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine, depth_check);
+    return run_search(*est, std::cout, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine, depth_check, do_instances ? &inst_prm : NULL,
+                      instances_path);
 }

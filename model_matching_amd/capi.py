@@ -65,6 +65,14 @@ class DepthResult(C.Structure):
                 ("in_front", C.c_int32), ("behind", C.c_int32), ("on_mask", C.c_int32), ("score", C.c_float), ("violation", C.c_float)]
 
 
+class InstanceParams(C.Structure):
+    _fields_ = [("max_instances", C.c_int32), ("min_points", C.c_int32), ("min_exclusive_fraction", C.c_float)]
+
+
+class InstanceResult(C.Structure):
+    _fields_ = [("rank", C.c_int32), ("own", C.c_int32), ("exclusive", C.c_int32), ("lcp", C.c_float)]
+
+
 class Camera(C.Structure):
     _fields_ = [("fx", C.c_float), ("cx", C.c_float), ("fy", C.c_float), ("cy", C.c_float), ("depth_scale", C.c_float),
                 ("width", C.c_int), ("height", C.c_int), ("normal_method", C.c_int)]
@@ -149,6 +157,9 @@ SIGNATURES = {
     "stocs_ctx_set_frame": (C.c_int, [_vp, C.POINTER(Camera), C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
     "stocs_default_depth_params": (None, [C.POINTER(DepthParams)]),
     "stocs_depth_check_poses": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(DepthParams), C.POINTER(DepthResult)]),
+    "stocs_default_instance_params": (None, [C.POINTER(InstanceParams)]),
+    "stocs_select_instances": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(InstanceParams), C.POINTER(InstanceResult), _ip, _intp]),
+    "stocs_select_instances_rows": (C.c_int, [_vp, _ip, _u8p, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(InstanceParams), C.POINTER(InstanceResult), _ip, _intp]),
     "stocs_device_alloc_count": (C.c_int64, []),
     "stocs_debug_stream_audit_selftest": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     "stocs_debug_streams_overlap": (C.c_int, [_vp]),

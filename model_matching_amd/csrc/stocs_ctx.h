@@ -367,6 +367,8 @@ struct stocs_ctx {
     // what the last class-mode stocs_sample_bases / stocs_run_trials* call ran (sample.hip; read by stocs_last_sampling_form): host
     // bookkeeping only.  kernel < 0: no class-mode call yet
     struct { int kernel, threads; size_t lds; int cap, launches, redone; } last_form;
+
+    void* instances;   // instances.hip (InstancesState): stocs_select_instances's grow-only workspace (last: no other member moves)
 };
 
 namespace stocs {
@@ -421,6 +423,7 @@ extern "C" void stocs_internal_free_trials(stocs_ctx* c);
 extern "C" void stocs_internal_free_refine(stocs_ctx* c);
 extern "C" void stocs_internal_free_track(stocs_ctx* c);
 extern "C" void stocs_internal_free_depth(stocs_ctx* c);
+extern "C" void stocs_internal_free_instances(stocs_ctx* c);
 // the congruent phase with a ceiling on its device memory: *too_big != 0 (and STOCS_OK) when the pair lists of the context's base set
 // would need more than max_bytes (0: no ceiling) or exceed 2^32 entries -- a trial batch then splits the base set and tries again
 extern "C" int stocs_internal_find_congruent(stocs_ctx* c, int64_t* total_quads, size_t max_bytes, int* too_big);

@@ -39,6 +39,8 @@ assert _TRACK_DTYPE.itemsize == C.sizeof(capi.TrackResult)
 _DEPTH_DTYPE = np.dtype([("facing", np.int32), ("in_image", np.int32), ("self_occluded", np.int32), ("no_depth", np.int32), ("agree", np.int32),
                          ("in_front", np.int32), ("behind", np.int32), ("on_mask", np.int32), ("score", np.float32), ("violation", np.float32)])
 assert _DEPTH_DTYPE.itemsize == C.sizeof(capi.DepthResult)
+_INSTANCE_DTYPE = np.dtype([("rank", np.int32), ("own", np.int32), ("exclusive", np.int32), ("lcp", np.float32)])
+assert _INSTANCE_DTYPE.itemsize == C.sizeof(capi.InstanceResult)
 
 # defaults of track_poses (tools/track_time.py's sweep, profiles/track_time.json)
 TRACK_DEFAULTS = dict(rounds=6, samples=2048, max_translation=0.02, max_rotation_deg=10.0, shrink=0.7, seed=0, refine_iterations=0,
@@ -341,6 +343,35 @@ class StocsEstimator:
         buf = (capi.DepthResult * max(n, 1))()
         capi.check(self.L.stocs_depth_check_poses(self.h, pP, n, C.byref(prm), buf))
         return np.frombuffer(buf, dtype=_DEPTH_DTYPE, count=n).copy()
+
+    def select_instances(self, T16, max_instances=16, min_points=20, min_exclusive_fraction=0.5):
+        """Which of n centred-frame hypotheses (column-major 16 floats each) are distinct instances (stocs_select_instances): walked best
+        first, one is kept only if enough of the scene points it explains are explained by none kept before it -> (records, selected):
+        a structured array with the fields of stocs_instance_result (rank or -1, own, exclusive, lcp), one record per hypothesis, and
+        the indices of the selected ones in rank order."""
+        T, pT = capi.f32(T16)
+        n = T.size // 16
+        prm = capi.InstanceParams(max_instances, min_points, min_exclusive_fraction)
+        buf = (capi.InstanceResult * max(n, 1))()
+        sel = np.zeros(max(min(max(int(max_instances), 0), n), 1), np.int32); ns = C.c_int(0)
+        capi.check(self.L.stocs_select_instances(self.h, pT, n, C.byref(prm), buf, sel.ctypes.data_as(capi._ip), C.byref(ns)))
+        return np.frombuffer(buf, dtype=_INSTANCE_DTYPE, count=n).copy(), sel[:ns.value].copy()
+
+    def select_instances_rows(self, hit, counted, lcp, nS, max_instances=16, min_points=20, min_exclusive_fraction=0.5):
+        """The set arithmetic, order and walk of select_instances on GIVEN detail rows (stocs_select_instances_rows): hit (n, nM) int32,
+        counted (n, nM) uint8, lcp (n,) over nS scene points -> (records, selected).  Uses this context's device and workspace only."""
+        H, pH = capi.i32(hit)
+        K = np.ascontiguousarray(counted, np.uint8)
+        l, pl = capi.f32(lcp)
+        n = l.size
+        if H.shape != K.shape or H.ndim != 2 or H.shape[0] != n:
+            raise ValueError("hit %s and counted %s must both be (n, nM) with n = %d scores" % (H.shape, K.shape, n))
+        prm = capi.InstanceParams(max_instances, min_points, min_exclusive_fraction)
+        buf = (capi.InstanceResult * max(n, 1))()
+        sel = np.zeros(max(min(max(int(max_instances), 0), n), 1), np.int32); ns = C.c_int(0)
+        capi.check(self.L.stocs_select_instances_rows(self.h, pH, K.ctypes.data_as(capi._u8p), pl, n, H.shape[1], int(nS), C.byref(prm), buf,
+                                                      sel.ctypes.data_as(capi._ip), C.byref(ns)))
+        return np.frombuffer(buf, dtype=_INSTANCE_DTYPE, count=n).copy(), sel[:ns.value].copy()
 
     def track_round(self, prior, round):
         """-> (T16_centred (samples, 16), lcp (samples,)) of one round of one prior of the last track_poses(keep_details=True)."""
