@@ -671,6 +671,34 @@ public:
         return r;
     }
 
+    // Joint rendering (stocs_explain_poses; no reference counterpart): the camera-frame poses -- the instances select_instances kept, say
+    // -- rendered TOGETHER against the frame of set_frame, nearest surface first: one record per pose in input order (footprint,
+    // visible / hidden behind the others, and the visible pixels' agreement with the depth image), and, when `labels` is given, the
+    // image_height x image_width label image (-1: nobody, else the pose's index) with its per-pixel state when `state` is given too.
+    // Empty on error (the text goes to the log).
+    static stocs_render_params default_render_params() {
+        stocs_render_params p;
+        stocs_default_render_params(&p);
+        return p;
+    }
+    std::vector<stocs_render_result> explain_poses(const std::vector<PoseCandidate*>& poses, std::vector<int32_t>* labels = NULL,
+                                                   std::vector<uint8_t>* state = NULL, const stocs_render_params& prm = default_render_params()) {
+        const int n = (int)poses.size();
+        std::vector<float> P((size_t)n * 16);
+        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], poses[(size_t)i]->transform.data(), 64);
+        std::vector<stocs_render_result> r((size_t)n);
+        const size_t npix = (size_t)image_width * (size_t)image_height;
+        if (labels) labels->assign(npix, -1);
+        if (labels && state) state->assign(npix, 0);
+        if (stocs_explain_poses(ctx_, P.data(), n, &prm, r.data(), labels ? labels->data() : NULL, labels && state ? state->data() : NULL) != STOCS_OK) {
+            *log_ << "explain_poses failed: " << stocs_last_error() << std::endl;
+            r.clear();
+            if (labels) labels->clear();
+            if (state) state->clear();
+        }
+        return r;
+    }
+
     // Multi-instance selection (stocs_select_instances; no reference counterpart): which of the camera-frame hypotheses (the
     // hypotheses of run_trials, refined or not) are distinct instances of the object and which are one instance found twice.  Walked
     // best first, a hypothesis is kept only if enough of the scene points it explains are explained by none kept before it.  One record

@@ -566,6 +566,56 @@ int stocs_select_instances(stocs_ctx* ctx, const float* T16_centred, int n, cons
 int stocs_select_instances_rows(stocs_ctx* ctx, const int32_t* hit, const uint8_t* counted, const float* lcp, int n, int nM, int nS,
                                 const stocs_instance_params* p, stocs_instance_result* out, int32_t* selected, int* n_selected);
 
+/* ---- joint rendering of poses: instance masks, visibility, depth agreement (no reference counterpart).  stocs_depth_check_poses judges
+ * every hypothesis alone; these entry points splat the model points of many poses -- of one context, or of several contexts one call
+ * after another -- into ONE frame-sized key buffer, so that a pose standing in front of another hides it, and read the result back per
+ * instance and per pixel.  The frame is the one stocs_ctx_set_frame uploaded; poses are CAMERA-frame and column-major, as for
+ * stocs_depth_check_poses.  csrc/render.hip, restated in float32 numpy in tests/render_ref.py, equal bit for bit.
+ * The key buffer: width*height uint64_t on the device, row-major; empty is all ones.  The caller allocates it (stocs_dev_alloc of any
+ * context on the same device serves).  Several contexts, one per object, may render into the same buffer one call after another.
+ * The splat rule, used by every entry point below.  Hypothesis h has id = id_base + h (id_base >= 0, id_base + n <= 2^31 - 1).  Each
+ * model point goes through steps 1-3 of the depth-check contract above, unchanged.  If the point is in_image:
+ *   s = (int)fminf(floorf((fx * point_radius) / p_2 + 0.5f), (float)max_splat_px)   (float, one IEEE operation at a time; fx serves both axes)
+ * and the point touches every pixel (row + dy, col + dx) with |dy|, |dx| <= s that lies inside the image (tested on integers).  A pose
+ * with a non-finite entry among its twelve used entries, or the all-zero "no pose" record, touches nothing and is no error.
+ *   1. stocs_render_poses: with clear != 0 the buffer is filled with empty first; then every touched pixel gets
+ *      key = min(key, (uint64_t)bits(p_2) << 32 | id).  p_2 > 1e-6, so the float's bits keep its order: the nearest surface wins and on
+ *      an equal depth the lower id.  A minimum: the result does not depend on execution order, on the batch, or on the order of calls.
+ *      Synchronises its stream before it returns, so that another context may continue on the buffer.
+ *   2. stocs_render_resolve: called with the same poses and ids after every render into the buffer is done.  C_h is the set of distinct
+ *      pixels h touches, footprint = |C_h|.  A pixel of C_h whose key's low word is not h's id is hidden (an empty key too); otherwise it is
+ *      visible and, with z = the float in the key's high word, classified by steps 5-6 of the depth-check contract with p_2 := z:
+ *      no_depth, agree, in_front, behind, on_mask.  footprint == visible + hidden, visible == no_depth + agree + in_front + behind.
+ *   3. stocs_render_labels: per pixel, labels (host, width*height int32) = -1 for an empty key, else its id; state (host, width*height
+ *      uint8, may be NULL) = 0 empty, 1 no_depth, 2 agree, 3 in_front, 4 behind, plus 16 when on_mask, classified as in 2.
+ *   4. stocs_explain_poses, the single-object form: the context's own key buffer, id_base 0; clear, render, resolve, and labels / state when
+ *      `labels` is given (state alone is ignored).  One pinned read-back and one synchronisation; a second call of the same size
+ *      allocates nothing.
+ * n == 0: no-op (nothing is cleared either); stocs_explain_poses with n == 0 and labels given still returns the all-empty label image
+ * (it needs the frame for its size, nothing else).  NULL ctx; NULL poses / p / key buffer / out with n > 0; NULL key buffer / p / labels
+ * for stocs_render_labels; n < 0; a parameter outside the ranges below; an id outside 0 .. 2^31 - 2: STOCS_ERR_INVALID.  No frame set, or
+ * a frame whose width * height differs from what was uploaded: STOCS_ERR_STATE.  stocs_render_resolve or stocs_explain_poses (n > 0) on a
+ * frame of more than 2^19 pixels: STOCS_ERR_CAPACITY (the footprint is a 64 KB bitset in LDS); render and labels take any frame.  Poses go
+ * up and results come back through the context's pinned block, everything runs on the context's stream, every call synchronises once;
+ * own grow-only workspace on the context.  Known limits: a point's whole splat is written by one lane; resolve is one workgroup per
+ * hypothesis, so with n far below the number of compute units it is latency-bound. ---- */
+typedef struct stocs_render_params {
+    float   point_radius;      /* m, >= 0 finite: radius of the disc a model point stands for (default 0.005)                  */
+    int32_t max_splat_px;      /* 0..16: largest splat half-width in pixels (default 8)                                        */
+    float   tolerance;         /* m, > 0 finite: |rendered z - observed z| <= tolerance agrees (default 0.01)                  */
+    float   class_threshold;   /* finite, as stocs_ingest_scene's (default 0.10); unused without a class image                 */
+} stocs_render_params;
+typedef struct stocs_render_result {
+    int32_t footprint, visible, hidden, no_depth, agree, in_front, behind, on_mask;
+} stocs_render_result;
+void stocs_default_render_params(stocs_render_params* p);
+int stocs_render_poses(stocs_ctx* ctx, const float* pose16_camera, int n, int id_base, const stocs_render_params* p, void* d_zkey, int clear);
+int stocs_render_resolve(stocs_ctx* ctx, const float* pose16_camera, int n, int id_base, const stocs_render_params* p, const void* d_zkey,
+                         stocs_render_result* out);
+int stocs_render_labels(stocs_ctx* ctx, const void* d_zkey, const stocs_render_params* p, int32_t* labels, uint8_t* state);
+int stocs_explain_poses(stocs_ctx* ctx, const float* pose16_camera, int n, const stocs_render_params* p, stocs_render_result* out,
+                        int32_t* labels, uint8_t* state);
+
 /* ---- tuning knobs (never change results beyond float summation order).
  * "lcp_variant": 99 = automatic (default): the scan fed from a per-wavefront LDS queue of the queries that have a list -- over
  *   index-ordered lists at cell edge epsilon (24, sparse scenes), over centre-sorted lists with triangle-inequality early exit

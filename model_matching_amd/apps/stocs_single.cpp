@@ -31,6 +31,10 @@
 // to the library's 0.5 and 20); one "instance r: trial.hyp own exclusive lcp" line per selected instance, and their poses, 3x4 row-major,
 // one per line in rank order, to pose_instances_<object>.txt next to <out> (<object>: the object name, with --clouds the model file's
 // name without its extension).  Every other line and file is what the run writes without the flag.
+// --masks (with --instances M, a scene directory): the selected instances, in rank order, rendered together against the frame's depth image
+// and class-probability map (stocs_explain_poses); one "mask r: footprint .. visible .. hidden .. agree .. in_front .. behind .. no_depth ..
+// on_mask .." line per instance, and the label image to labels_<object>.pgm next to <out>: binary 16-bit PGM (P5, maxval 65535, most
+// significant byte first), value = rank + 1, 0 = no instance.  Every other line and file is what the run writes without the flag.
 // The reference edits its per-data-set constants in the source (README.md:42-66); here they are options with the
 // reference's YCB values as defaults.
 #include <algorithm>
@@ -83,7 +87,7 @@ static bool read_stcl(const std::string& path, std::vector<float>& pos, std::vec
 // everything after the estimator is built (:79-185): one run, or n_trials in one batch; lines to os, the pose to out_path
 static int run_search(stocs::stocs_estimator& stocs_ptr, std::ostream& os, const std::string& out_path, const std::string& dbg_dir, uint64_t seed, int n_trials,
                       int exact_ties, int do_cluster, int n_refine, int depth_check = 0, const stocs_instance_params* instances = NULL,
-                      const std::string& instances_path = std::string()) {
+                      const std::string& instances_path = std::string(), const std::string& labels_path = std::string()) {
     stocs_ptr.set_seed(seed);
     if (exact_ties) stocs_ptr.set_exact_ties(true);
 
@@ -201,6 +205,24 @@ static int run_search(stocs::stocs_estimator& stocs_ptr, std::ostream& os, const
                 o << std::endl;
             }
             os << "instances: hypotheses=" << flat.size() << " selected=" << sel.size() << std::endl;
+            if (!labels_path.empty()) {
+                std::vector<PoseCandidate*> chosen;
+                for (size_t r = 0; r < sel.size(); ++r) chosen.push_back(flat[(size_t)sel[r]]);
+                std::vector<int32_t> labels;
+                const std::vector<stocs_render_result> mr = stocs_ptr.explain_poses(chosen, &labels);
+                if (mr.size() != chosen.size() || labels.empty()) { std::cerr << "mask rendering failed: " << stocs_last_error() << std::endl; return 2; }
+                for (size_t r = 0; r < mr.size(); ++r) {
+                    char b[256];
+                    snprintf(b, sizeof(b), "mask %d: footprint %d visible %d hidden %d agree %d in_front %d behind %d no_depth %d on_mask %d", (int)r, mr[r].footprint,
+                             mr[r].visible, mr[r].hidden, mr[r].agree, mr[r].in_front, mr[r].behind, mr[r].no_depth, mr[r].on_mask);
+                    os << b << std::endl;
+                }
+                std::vector<unsigned char> px(labels.size() * 2);
+                for (size_t i = 0; i < labels.size(); ++i) { const unsigned v = (unsigned)(labels[i] + 1); px[2 * i] = (unsigned char)(v >> 8); px[2 * i + 1] = (unsigned char)(v & 255u); }
+                std::ofstream pg(labels_path, std::ofstream::out | std::ofstream::binary);
+                pg << "P5\n" << image_width << " " << image_height << "\n65535\n";
+                pg.write((const char*)px.data(), (std::streamsize)px.size());
+            }
         }
         return 0;
     }
@@ -388,11 +410,12 @@ int main(int argc, char** argv) {
     std::string edge_path, out_path, dbg_dir, track_path;
     float track_min_lcp = 0.02f;
     int do_cluster = 0, n_trials = 0, exact_ties = 0, n_refine = 0, depth_check = 0;
-    bool do_instances = false;
+    bool do_instances = false, do_masks = false;
     stocs_instance_params inst_prm = stocs::stocs_estimator::default_instance_params();
     uint64_t seed = 1;
     for (int i = clouds ? 4 : 3; i < argc; i += 2) {
-        if (std::string(argv[i]) == "--depth-check") { depth_check = 1; --i; continue; }   // the one option without a value
+        if (std::string(argv[i]) == "--depth-check") { depth_check = 1; --i; continue; }   // the two options without a value
+        if (std::string(argv[i]) == "--masks") { do_masks = true; --i; continue; }
         if (i + 1 >= argc) break;
         const std::string k = argv[i], v = argv[i + 1];
         if (k == "--edge") edge_path = v;
@@ -428,6 +451,11 @@ int main(int argc, char** argv) {
 
     if (do_instances && (n_trials <= 0 || !do_cluster || !track_path.empty() || (!clouds && a2.find(',') != std::string::npos))) {
         std::cerr << "--instances needs a single object, --trials N and --cluster 1" << std::endl;
+        return -1;
+    }
+
+    if (do_masks && (clouds || !do_instances)) {
+        std::cerr << "--masks needs a scene directory and --instances M" << std::endl;
         return -1;
     }
 
@@ -482,7 +510,7 @@ int main(int argc, char** argv) {
             est.reset(new stocs::stocs_estimator(model_path, model_map, rgb_path, depth_path, class_probability_path, edge_probability_path, dbg_dir, cam_intrinsics,
                                                  image_width, image_height, depth_scale, 1.0f, voxel_size, distance_threshold, ppf_tr_discretization,
                                                  ppf_rot_discretization, edge_threshold, class_threshold));
-            if (depth_check) {   // the frame the scene was ingested from, for stocs_depth_check_poses
+            if (depth_check || do_masks) {   // the frame the scene was ingested from, for stocs_depth_check_poses / stocs_explain_poses
                 std::vector<uint16_t> depth, prob;
                 stocs::read_image(depth_path, 1, 16, image_width, image_height, &depth);
                 stocs::read_image(class_probability_path, 1, 16, image_width, image_height, &prob);
@@ -493,7 +521,7 @@ int main(int argc, char** argv) {
         std::cerr << e.what() << std::endl;  // no GPU => loud failure, never a CPU fallback
         return 2;
     }
-    std::string instances_path;
+    std::string instances_path, labels_path;
     if (do_instances) {   // next to <out>
         std::string object = a2;
         if (clouds) {
@@ -504,8 +532,9 @@ int main(int argc, char** argv) {
         }
         const size_t sl = out_path.find_last_of('/');
         instances_path = (sl == std::string::npos ? std::string() : out_path.substr(0, sl + 1)) + "pose_instances_" + object + ".txt";
+        if (do_masks) labels_path = (sl == std::string::npos ? std::string() : out_path.substr(0, sl + 1)) + "labels_" + object + ".pgm";
     }
     if (!track_path.empty()) return run_track(*est, track_path, track_min_lcp, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine);
     return run_search(*est, std::cout, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine, depth_check, do_instances ? &inst_prm : NULL,
-                      instances_path);
+                      instances_path, labels_path);
 }

@@ -73,6 +73,15 @@ class InstanceResult(C.Structure):
     _fields_ = [("rank", C.c_int32), ("own", C.c_int32), ("exclusive", C.c_int32), ("lcp", C.c_float)]
 
 
+class RenderParams(C.Structure):
+    _fields_ = [("point_radius", C.c_float), ("max_splat_px", C.c_int32), ("tolerance", C.c_float), ("class_threshold", C.c_float)]
+
+
+class RenderResult(C.Structure):
+    _fields_ = [("footprint", C.c_int32), ("visible", C.c_int32), ("hidden", C.c_int32), ("no_depth", C.c_int32), ("agree", C.c_int32),
+                ("in_front", C.c_int32), ("behind", C.c_int32), ("on_mask", C.c_int32)]
+
+
 class Camera(C.Structure):
     _fields_ = [("fx", C.c_float), ("cx", C.c_float), ("fy", C.c_float), ("cy", C.c_float), ("depth_scale", C.c_float),
                 ("width", C.c_int), ("height", C.c_int), ("normal_method", C.c_int)]
@@ -157,6 +166,11 @@ SIGNATURES = {
     "stocs_ctx_set_frame": (C.c_int, [_vp, C.POINTER(Camera), C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
     "stocs_default_depth_params": (None, [C.POINTER(DepthParams)]),
     "stocs_depth_check_poses": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(DepthParams), C.POINTER(DepthResult)]),
+    "stocs_default_render_params": (None, [C.POINTER(RenderParams)]),
+    "stocs_render_poses": (C.c_int, [_vp, _fp, C.c_int, C.c_int, C.POINTER(RenderParams), _vp, C.c_int]),
+    "stocs_render_resolve": (C.c_int, [_vp, _fp, C.c_int, C.c_int, C.POINTER(RenderParams), _vp, C.POINTER(RenderResult)]),
+    "stocs_render_labels": (C.c_int, [_vp, _vp, C.POINTER(RenderParams), _ip, _u8p]),
+    "stocs_explain_poses": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(RenderParams), C.POINTER(RenderResult), _ip, _u8p]),
     "stocs_default_instance_params": (None, [C.POINTER(InstanceParams)]),
     "stocs_select_instances": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(InstanceParams), C.POINTER(InstanceResult), _ip, _intp]),
     "stocs_select_instances_rows": (C.c_int, [_vp, _ip, _u8p, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(InstanceParams), C.POINTER(InstanceResult), _ip, _intp]),

@@ -39,6 +39,8 @@ assert _TRACK_DTYPE.itemsize == C.sizeof(capi.TrackResult)
 _DEPTH_DTYPE = np.dtype([("facing", np.int32), ("in_image", np.int32), ("self_occluded", np.int32), ("no_depth", np.int32), ("agree", np.int32),
                          ("in_front", np.int32), ("behind", np.int32), ("on_mask", np.int32), ("score", np.float32), ("violation", np.float32)])
 assert _DEPTH_DTYPE.itemsize == C.sizeof(capi.DepthResult)
+_RENDER_DTYPE = np.dtype([(f[0], np.int32) for f in capi.RenderResult._fields_])
+assert _RENDER_DTYPE.itemsize == C.sizeof(capi.RenderResult)
 _INSTANCE_DTYPE = np.dtype([("rank", np.int32), ("own", np.int32), ("exclusive", np.int32), ("lcp", np.float32)])
 assert _INSTANCE_DTYPE.itemsize == C.sizeof(capi.InstanceResult)
 
@@ -327,6 +329,7 @@ class StocsEstimator:
             pp = p.ctypes.data_as(C.POINTER(C.c_uint16))
         cam = capi.Camera(float(K[0]), float(K[1]), float(K[2]), float(K[3]), float(depth_scale), d.shape[1], d.shape[0], 0)
         capi.check(self.L.stocs_ctx_set_frame(self.h, C.byref(cam), d.ctypes.data_as(C.POINTER(C.c_uint16)), pp))
+        self._frame_hw = d.shape   # the label images of render_labels / explain_poses take their shape from it
 
     def depth_check_poses(self, poses16, **params):
         """n camera-frame poses (column-major 16 floats each) against the frame of set_frame (stocs_depth_check_poses) -> a structured
@@ -343,6 +346,62 @@ class StocsEstimator:
         buf = (capi.DepthResult * max(n, 1))()
         capi.check(self.L.stocs_depth_check_poses(self.h, pP, n, C.byref(prm), buf))
         return np.frombuffer(buf, dtype=_DEPTH_DTYPE, count=n).copy()
+
+    def _render_params(self, who, params):
+        prm = capi.RenderParams()
+        self.L.stocs_default_render_params(C.byref(prm))
+        for k, v in params.items():
+            if k not in dict(capi.RenderParams._fields_):
+                raise TypeError("%s: unknown parameter %r" % (who, k))
+            setattr(prm, k, v)
+        return prm
+
+    def _frame_shape(self, who):
+        if getattr(self, "_frame_hw", None) is None:
+            raise ValueError("%s: no frame (set_frame)" % who)
+        return self._frame_hw
+
+    def render_poses(self, poses16, zkey, id_base=0, clear=False, **params):
+        """n camera-frame poses (column-major 16 floats each) splatted into the device key buffer zkey (width*height uint64, e.g. from
+        dev_alloc; stocs_render_poses): pose h writes id id_base + h wherever it is the nearest surface.  clear: the buffer is emptied
+        first.  params: fields of stocs_render_params (point_radius, max_splat_px, tolerance, class_threshold) over the defaults."""
+        P, pP = capi.f32(poses16)
+        prm = self._render_params("render_poses", params)
+        capi.check(self.L.stocs_render_poses(self.h, pP, P.size // 16, int(id_base), C.byref(prm), zkey, 1 if clear else 0))
+
+    def render_resolve(self, poses16, zkey, id_base=0, **params):
+        """The same poses and ids against the finished key buffer (stocs_render_resolve) -> a structured array with the fields of
+        stocs_render_result (footprint, visible, hidden, no_depth, agree, in_front, behind, on_mask), one record per pose."""
+        P, pP = capi.f32(poses16)
+        n = P.size // 16
+        prm = self._render_params("render_resolve", params)
+        buf = (capi.RenderResult * max(n, 1))()
+        capi.check(self.L.stocs_render_resolve(self.h, pP, n, int(id_base), C.byref(prm), zkey, buf))
+        return np.frombuffer(buf, dtype=_RENDER_DTYPE, count=n).copy()
+
+    def render_labels(self, zkey, **params):
+        """-> (labels int32, state uint8), both (height, width), of the key buffer (stocs_render_labels): -1 / the id that owns the pixel;
+        0 empty, 1 no_depth, 2 agree, 3 in_front, 4 behind, plus 16 when on_mask."""
+        H, W = self._frame_shape("render_labels")
+        prm = self._render_params("render_labels", params)
+        lab = np.zeros((H, W), np.int32); st = np.zeros((H, W), np.uint8)
+        capi.check(self.L.stocs_render_labels(self.h, zkey, C.byref(prm), lab.ctypes.data_as(capi._ip), st.ctypes.data_as(capi._u8p)))
+        return lab, st
+
+    def explain_poses(self, poses16, labels=False, **params):
+        """n camera-frame poses of this context's model rendered together against the frame of set_frame (stocs_explain_poses) -> records
+        (as render_resolve), or (records, labels, state) with labels=True (as render_labels; ids are the poses' indices)."""
+        P, pP = capi.f32(poses16)
+        n = P.size // 16
+        prm = self._render_params("explain_poses", params)
+        buf = (capi.RenderResult * max(n, 1))()
+        if not labels:
+            capi.check(self.L.stocs_explain_poses(self.h, pP, n, C.byref(prm), buf, None, None))
+            return np.frombuffer(buf, dtype=_RENDER_DTYPE, count=n).copy()
+        H, W = self._frame_shape("explain_poses")
+        lab = np.zeros((H, W), np.int32); st = np.zeros((H, W), np.uint8)
+        capi.check(self.L.stocs_explain_poses(self.h, pP, n, C.byref(prm), buf, lab.ctypes.data_as(capi._ip), st.ctypes.data_as(capi._u8p)))
+        return np.frombuffer(buf, dtype=_RENDER_DTYPE, count=n).copy(), lab, st
 
     def select_instances(self, T16, max_instances=16, min_points=20, min_exclusive_fraction=0.5):
         """Which of n centred-frame hypotheses (column-major 16 floats each) are distinct instances (stocs_select_instances): walked best
