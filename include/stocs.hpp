@@ -740,6 +740,32 @@ public:
         return rec;
     }
 
+    // Scene-level selection across objects (stocs_scene_footprints; no reference counterpart): the pixels of the frame of set_frame that
+    // each camera-frame hypothesis of THIS estimator's model claims -- claim 0: where the depth image agrees with it, 1: those of them on the
+    // object's class mask -- written as bit rows into slots slot_base .. of a device pool that several estimators share (n_slots rows of
+    // stocs_scene_row_words uint32_t each), and one record per hypothesis in input order.  stocs::select_scene below runs the whole step.
+    // Empty on error (the text goes to the log).
+    static stocs_scene_params default_scene_params() {
+        stocs_scene_params p;
+        stocs_default_scene_params(&p);
+        return p;
+    }
+    std::vector<stocs_scene_record> scene_footprints(const std::vector<PoseCandidate*>& poses, void* d_rows, int slot_base, int n_slots, int claim = 0,
+                                                     const stocs_render_params& prm = default_render_params()) {
+        const int n = (int)poses.size();
+        std::vector<float> P((size_t)n * 16);
+        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], poses[(size_t)i]->transform.data(), 64);
+        std::vector<stocs_scene_record> r((size_t)n);
+        if (n > 0 && stocs_scene_footprints(ctx_, P.data(), n, slot_base, n_slots, &prm, claim, d_rows, r.data()) != STOCS_OK) {
+            *log_ << "scene_footprints failed: " << stocs_last_error() << std::endl;
+            r.clear();
+        }
+        return r;
+    }
+    int frame_width() const { return image_width; }
+    int frame_height() const { return image_height; }
+    std::ostream& log() { return *log_; }
+
 protected:
     std::vector<std::unique_ptr<PoseCandidate> > tracked_store_;   // results of the last track_poses
     std::unique_ptr<PoseCandidate> trial_best_;
@@ -922,6 +948,85 @@ protected:
     int la_first_, la_n_, la_cursor_, la_mode_, la_nvalid_;
     bool la_in_ctx_, la_congruent_done_;
 };
+
+// Not in the reference: which hypotheses of several objects form one consistent explanation of the frame (stocs_scene_footprints /
+// stocs_scene_select).  estimators[k] holds object k's model and the frame (set_frame, the same size everywhere), poses[k] its camera-frame
+// hypotheses.  The pool of pixel rows is allocated on the first estimator's device, every estimator writes its footprints into
+// consecutive slots (group = object index), and the first estimator walks the pool.  The score of a slot is float(agree) /
+// float(footprint), 0 where the footprint is empty: visible-surface agreement, comparable across objects.  max_per_object: empty (no
+// cap), one cap for all, or one per object.  with_labels: the selected poses are rendered into one key buffer with id = slot
+// (stocs_render_poses) and labels / state come from stocs_render_labels of the first estimator.  ok == false on error (the text goes to
+// the first estimator's log).
+struct SceneSelection {
+    bool ok;
+    std::vector<int32_t> group, index;             // per slot: the object and the hypothesis of it
+    std::vector<float> score;
+    std::vector<stocs_scene_record> footprints;
+    std::vector<stocs_scene_result> records;
+    std::vector<int> selected;                     // slots in rank order
+    std::vector<int32_t> labels;                   // with_labels: -1 or the slot that owns the pixel
+    std::vector<uint8_t> state;
+};
+inline SceneSelection select_scene(const std::vector<stocs_estimator*>& estimators, const std::vector<std::vector<PoseCandidate*> >& poses,
+                                   const std::vector<int>& max_per_object = std::vector<int>(), bool with_labels = false,
+                                   const stocs_scene_params& prm = stocs_estimator::default_scene_params(),
+                                   const stocs_render_params& render = stocs_estimator::default_render_params(), int claim = 0) {
+    SceneSelection out;
+    out.ok = false;
+    if (estimators.empty() || estimators.size() != poses.size()) throw std::runtime_error("select_scene: one pose set per estimator");
+    if (!max_per_object.empty() && max_per_object.size() != 1 && max_per_object.size() != estimators.size()) throw std::runtime_error("select_scene: one cap, or one per object");
+    stocs_estimator& first = *estimators[0];
+    const int W = first.frame_width(), H = first.frame_height();
+    int n = 0;
+    for (size_t k = 0; k < poses.size(); ++k) {
+        if (estimators[k]->frame_width() != W || estimators[k]->frame_height() != H) throw std::runtime_error("select_scene: the estimators' frames differ in size");
+        for (size_t i = 0; i < poses[k].size(); ++i) { out.group.push_back((int32_t)k); out.index.push_back((int32_t)i); }
+        n += (int)poses[k].size();
+    }
+    const int Wr = stocs_scene_row_words(W, H);
+    void* d_rows = NULL;
+    void* d_zkey = NULL;
+    if (stocs_dev_alloc(first.context(), (int64_t)std::max(n, 1) * Wr * 4, &d_rows) != STOCS_OK) { first.log() << "select_scene failed: " << stocs_last_error() << std::endl; return out; }
+    bool good = true;
+    int base = 0;
+    for (size_t k = 0; good && k < poses.size(); ++k) {
+        const std::vector<stocs_scene_record> r = estimators[k]->scene_footprints(poses[k], d_rows, base, n, claim, render);
+        good = r.size() == poses[k].size();
+        out.footprints.insert(out.footprints.end(), r.begin(), r.end());
+        base += (int)poses[k].size();
+    }
+    if (good) {
+        out.score.resize((size_t)n);
+        for (int h = 0; h < n; ++h) out.score[(size_t)h] = out.footprints[(size_t)h].footprint > 0 ? (float)out.footprints[(size_t)h].agree / (float)out.footprints[(size_t)h].footprint : 0.0f;
+        std::vector<int32_t> cap;
+        for (size_t k = 0; !max_per_object.empty() && k < estimators.size(); ++k) cap.push_back(max_per_object[max_per_object.size() == 1 ? 0 : k]);
+        out.records.resize((size_t)n);
+        std::vector<int32_t> sel((size_t)std::max(n, 1));
+        int ns = 0;
+        good = stocs_scene_select(first.context(), d_rows, n, W, H, out.score.data(), out.group.data(), out.footprints.data(), (int)estimators.size(),
+                                  cap.empty() ? NULL : cap.data(), &prm, out.records.data(), sel.data(), &ns) == STOCS_OK;
+        if (good) out.selected.assign(sel.begin(), sel.begin() + ns);
+    }
+    if (good && with_labels) {
+        const size_t npix = (size_t)W * (size_t)H;
+        out.labels.assign(npix, -1);
+        out.state.assign(npix, 0);
+        if (!out.selected.empty()) {
+            good = stocs_dev_alloc(first.context(), (int64_t)npix * 8, &d_zkey) == STOCS_OK;
+            for (size_t r = 0; good && r < out.selected.size(); ++r) {
+                const int s = out.selected[r];
+                PoseCandidate* pc = poses[(size_t)out.group[(size_t)s]][(size_t)out.index[(size_t)s]];
+                good = stocs_render_poses(estimators[(size_t)out.group[(size_t)s]]->context(), pc->transform.data(), 1, s, &render, d_zkey, r == 0 ? 1 : 0) == STOCS_OK;
+            }
+            good = good && stocs_render_labels(first.context(), d_zkey, &render, out.labels.data(), out.state.data()) == STOCS_OK;
+        }
+    }
+    if (!good) first.log() << "select_scene failed: " << stocs_last_error() << std::endl;
+    if (d_zkey) stocs_dev_free(first.context(), d_zkey);
+    stocs_dev_free(first.context(), d_rows);
+    out.ok = good;
+    return out;
+}
 
 // Not in the reference (its driver runs once per object): every object of one frame from one ingest (stocs_ingest_scene_multi).
 // class_probability_maps holds class_thresholds.size() images of image_height x image_width, object after object; edge (may be NULL)

@@ -616,6 +616,75 @@ int stocs_render_labels(stocs_ctx* ctx, const void* d_zkey, const stocs_render_p
 int stocs_explain_poses(stocs_ctx* ctx, const float* pose16_camera, int n, const stocs_render_params* p, stocs_render_result* out,
                         int32_t* labels, uint8_t* state);
 
+/* ---- scene-level selection across objects on the pixels of the depth image (no reference counterpart).  stocs_select_instances works on
+ * scene-point indices, which every context numbers for itself; stocs_depth_check_poses and stocs_render_resolve judge poses somebody chose.
+ * The one index space all contexts of a frame share is its pixels: these entry points give every hypothesis of every object the set of
+ * depth pixels it claims, and walk the pool best first, keeping a hypothesis only if enough of its pixels are claimed by none kept before
+ * it.  csrc/scene.hip, restated in float32 numpy and integer set logic in tests/scene_ref.py, equal bit for bit.
+ * Pixel rows.  A frame of W x H has npix = W*H pixels; a row is Wr = ceil(npix / 32) rounded up to a multiple of 4 uint32_t words; pixel
+ * i = row*W + col is bit i & 31 of word i >> 5; padding bits are zero.  stocs_scene_row_words(width, height) returns Wr (0 when either is
+ * < 1).  A pool is n_slots * Wr words of device memory the caller allocates (stocs_dev_alloc of any context on the device); several
+ * contexts write into one pool, one call after another.
+ *   1. stocs_scene_footprints: n CAMERA-frame poses (column-major, as for stocs_depth_check_poses) of this context's model against the frame
+ *      of stocs_ctx_set_frame; hypothesis h goes to slot slot_base + h.  Every model point goes through steps 1-3 of the depth-check contract,
+ *      then the splat rule of the render contract, unchanged.  Z_h(pixel) = the minimum p_2 over the points of pose h ALONE that touch the
+ *      pixel: the float in the key stocs_render_poses leaves when this one pose is rendered into a cleared buffer.  Every touched pixel is
+ *      classified by steps 5-6 of the depth-check contract with p_2 := Z_h.  out[h] = { footprint, no_depth, agree, in_front, behind, on_mask,
+ *      claimed }: footprint == no_depth + agree + in_front + behind, claimed = the popcount of the row.  The row holds the agree pixels
+ *      (claim == 0) or the on_mask pixels (claim == 1).  The whole row, padding included, is always written: the pool need not be cleared,
+ *      and slots outside [slot_base, slot_base + n) are not touched.  A pose with a non-finite entry among its twelve used entries, or the
+ *      all-zero "no pose" record, gives an all-zero record and an all-zero row and is no error.  The record of h equals the record
+ *      stocs_explain_poses returns for that pose alone (hidden == 0, visible == footprint).  Bitwise independent of the batch, of the
+ *      position in it and of the chunking (hypotheses are processed in chunks of 256 MB of z-buffers; STOCS_SCENE_CHUNK=<hypotheses> in the
+ *      environment forces a size).
+ *      n == 0: no-op.  NULL ctx; NULL poses / p / rows / out with n > 0; n < 0; claim other than 0 or 1; slot_base < 0;
+ *      slot_base + n > n_slots; a parameter outside the ranges of stocs_render_params: STOCS_ERR_INVALID.  No frame set, or a frame whose
+ *      width * height differs from what was uploaded: STOCS_ERR_STATE.  npix > 2^19: STOCS_ERR_CAPACITY (so that step 2 can walk every pool).
+ *      Poses go up and records come back through the context's pinned block, everything runs on the context's stream, one
+ *      synchronisation; own grow-only workspace on the context (a second call of the same or a smaller size allocates nothing).
+ *   2. stocs_scene_select: slots 0 .. n-1 of the pool, host arrays score[n], group[n] (0 .. n_groups-1, e.g. the object), rec[n] (step 1's
+ *      records), group_cap[n_groups] (>= 1 each; NULL: no cap).  It needs a context for the device and the workspace only, neither its
+ *      scene nor its frame.  own_h = the popcount of row h, counted on the device and not trusted from rec.
+ *      Eligible: score_h > 0 (NaN is not), own_h >= min_pixels, and (float)rec[h].in_front <= max_violation_fraction * (float)rec[h].footprint
+ *      (one IEEE float multiply, one compare, no contraction).
+ *      Order: descending stocs_pack_best(score_h, h): higher score first, lower slot first on equal score; scores that are not positive
+ *      (or NaN) pack to 0 and come last, lower slot first.
+ *      Walk: in that order, covered = {} and cnt[g] = 0 at the start, excl = |A_h \ covered|.  h is selected when it is eligible,
+ *      cnt[group_h] < group_cap[group_h], fewer than max_selected are selected so far, excl >= min_pixels and
+ *      (float)excl >= min_exclusive_fraction * (float)own_h.  On selection covered |= A_h, ++cnt[group_h], and h takes the next rank.
+ *      Output: out[h] = { rank (-1: not selected), own, exclusive, reason }.  exclusive of a selected slot is excl at its selection, of an
+ *      unselected one |A_h \ covered_final|.  reason, decided from the FINAL state, the first that applies: 0 selected, 1 not eligible,
+ *      2 exclusive fails min_pixels or the fraction against the final cover, 3 its group is full at the end, 4 max_selected was reached.
+ *      selected[] (capacity max_selected, or n if that is smaller) lists the slots in rank order, *n_selected their count.
+ *      The cover and the counts only grow, so a slot that fails at its turn fails for good: the kernel tests sixteen pending slots per
+ *      round and the results above do not depend on that.
+ *      NULL ctx / p / n_selected; NULL rows / score / group / rec / out / selected with n > 0; n < 0 or n > 16 384; width or height < 1;
+ *      n_groups < 1 or > 1024; a group id outside 0 .. n_groups-1; a cap < 1; a negative count in rec; max_selected < 1; min_pixels < 1;
+ *      a min_exclusive_fraction that is NaN, <= 0 or > 1; a max_violation_fraction that is NaN, < 0 or > 1: STOCS_ERR_INVALID.
+ *      npix > 2^19: STOCS_ERR_CAPACITY (the cover is a 64 KB bitset in LDS).  n == 0 (after those checks): STOCS_OK, nothing selected.
+ *      One pinned read-back and one synchronisation per call; a second call of the same or a smaller size allocates nothing.
+ * Known limits: the classification walks the whole frame of every hypothesis; the walk is one workgroup, so its time grows with
+ * rounds x Wr. ---- */
+typedef struct stocs_scene_record {
+    int32_t footprint, no_depth, agree, in_front, behind, on_mask, claimed;
+} stocs_scene_record;
+typedef struct stocs_scene_params {
+    int32_t max_selected;             /* >= 1: stop after this many (default 64)                                              */
+    int32_t min_pixels;               /* >= 1: pixels a hypothesis must claim that no selected one claims (default 50)        */
+    float   min_exclusive_fraction;   /* in (0, 1]: ... as a share of all it claims (default 0.5)                             */
+    float   max_violation_fraction;   /* in [0, 1]: largest in_front / footprint of an eligible hypothesis (default 0.2)      */
+} stocs_scene_params;
+typedef struct stocs_scene_result {
+    int32_t rank, own, exclusive, reason;
+} stocs_scene_result;
+void stocs_default_scene_params(stocs_scene_params* p);
+int stocs_scene_row_words(int width, int height);
+int stocs_scene_footprints(stocs_ctx* ctx, const float* pose16_camera, int n, int slot_base, int n_slots, const stocs_render_params* p, int claim,
+                           void* d_rows, stocs_scene_record* out);
+int stocs_scene_select(stocs_ctx* ctx, const void* d_rows, int n, int width, int height, const float* score, const int32_t* group,
+                       const stocs_scene_record* rec, int n_groups, const int32_t* group_cap, const stocs_scene_params* p, stocs_scene_result* out,
+                       int32_t* selected, int* n_selected);
+
 /* ---- tuning knobs (never change results beyond float summation order).
  * "lcp_variant": 99 = automatic (default): the scan fed from a per-wavefront LDS queue of the queries that have a list -- over
  *   index-ordered lists at cell edge epsilon (24, sparse scenes), over centre-sorted lists with triangle-inequality early exit

@@ -31,6 +31,13 @@
 // to the library's 0.5 and 20); one "instance r: trial.hyp own exclusive lcp" line per selected instance, and their poses, 3x4 row-major,
 // one per line in rank order, to pose_instances_<object>.txt next to <out> (<object>: the object name, with --clouds the model file's
 // name without its extension).  Every other line and file is what the run writes without the flag.
+// --scene-select [--scene-max-per-object K] [--masks] (several objects, --trials N): once every object is searched, the N trial winners of
+// every object -- camera-frame poses, one pool over all objects -- are judged together on the pixels of the depth image
+// (stocs::select_scene): walked best first, a pose is kept only if enough of the depth pixels that agree with it are claimed by none
+// kept before it, whatever object it belongs to.  One "scene r: object .. trial .. score .. own .. exclusive .. reason .." line per pool
+// entry, the selected ones first in rank order (r = rank), then the others in pool order (r = -1), and the same entries with their poses
+// to <scene>/scene_selection.txt.  With --masks the selected poses of all objects are rendered into one key buffer and the label image
+// goes to <scene>/labels_scene.pgm (value = pool slot + 1, 0 = nobody; the format of labels_<object>.pgm).
 // --masks (with --instances M, a scene directory): the selected instances, in rank order, rendered together against the frame's depth image
 // and class-probability map (stocs_explain_poses); one "mask r: footprint .. visible .. hidden .. agree .. in_front .. behind .. no_depth ..
 // on_mask .." line per instance, and the label image to labels_<object>.pgm next to <out>: binary 16-bit PGM (P5, maxval 65535, most
@@ -87,7 +94,8 @@ static bool read_stcl(const std::string& path, std::vector<float>& pos, std::vec
 // everything after the estimator is built (:79-185): one run, or n_trials in one batch; lines to os, the pose to out_path
 static int run_search(stocs::stocs_estimator& stocs_ptr, std::ostream& os, const std::string& out_path, const std::string& dbg_dir, uint64_t seed, int n_trials,
                       int exact_ties, int do_cluster, int n_refine, int depth_check = 0, const stocs_instance_params* instances = NULL,
-                      const std::string& instances_path = std::string(), const std::string& labels_path = std::string()) {
+                      const std::string& instances_path = std::string(), const std::string& labels_path = std::string(),
+                      std::vector<stocs::stocs_estimator::TrialResult>* trial_results = NULL) {
     stocs_ptr.set_seed(seed);
     if (exact_ties) stocs_ptr.set_exact_ties(true);
 
@@ -149,6 +157,7 @@ static int run_search(stocs::stocs_estimator& stocs_ptr, std::ostream& os, const
             os << "no pose found" << std::endl;
         }
         os << tl << std::endl;
+        if (trial_results) *trial_results = res;
         if (depth_check) {
             const std::vector<std::vector<PoseCandidate*> >& src = n_refine > 0 ? refined : hyps;
             std::vector<PoseCandidate*> flat;
@@ -338,7 +347,53 @@ static int run_track(stocs::stocs_estimator& est, const std::string& track_path,
 // object writes <scene>/best_pose_candidate_<object>.txt and its block of lines, printed in the order given once all are done.
 static const int kMaxFrameThreads = 4;
 
-static int run_frame_objects(const std::string& scene_path, const std::vector<std::string>& objects, uint64_t seed, int n_trials, int exact_ties) {
+struct SceneSelectOptions { bool on, masks; int max_per_object; };
+
+// --scene-select: the trial winners of every object, judged together; the estimators hold their frames
+static int run_scene_select(const std::string& scene_path, const std::vector<std::string>& objects, std::vector<std::unique_ptr<stocs::stocs_estimator> >& ests,
+                            const std::vector<std::vector<stocs::stocs_estimator::TrialResult> >& results, const SceneSelectOptions& opt) {
+    std::vector<std::vector<std::unique_ptr<PoseCandidate> > > store(objects.size());
+    std::vector<std::vector<PoseCandidate*> > poses(objects.size());
+    std::vector<stocs::stocs_estimator*> ptrs;
+    for (size_t k = 0; k < objects.size(); ++k) {
+        ptrs.push_back(ests[k].get());
+        for (size_t t = 0; t < results[k].size(); ++t) {
+            store[k].emplace_back(new PoseCandidate(results[k][t].best_pose, results[k][t].best_lcp, -1.0f));
+            poses[k].push_back(store[k].back().get());
+        }
+    }
+    std::vector<int> caps;
+    if (opt.max_per_object > 0) caps.push_back(opt.max_per_object);
+    const stocs::SceneSelection sel = stocs::select_scene(ptrs, poses, caps, opt.masks);
+    if (!sel.ok) { std::cerr << "scene selection failed: " << stocs_last_error() << std::endl; return 2; }
+    std::vector<int> order(sel.selected);
+    for (size_t h = 0; h < sel.records.size(); ++h) if (sel.records[h].rank < 0) order.push_back((int)h);
+    std::ofstream o(scene_path + "/scene_selection.txt", std::ofstream::out);
+    for (size_t i = 0; i < order.size(); ++i) {
+        const size_t h = (size_t)order[i];
+        const stocs_scene_result& r = sel.records[h];
+        char b[256];
+        snprintf(b, sizeof(b), "scene %d: object %s trial %d score %.9g own %d exclusive %d reason %d", r.rank, objects[(size_t)sel.group[h]].c_str(), sel.index[h],
+                 (double)sel.score[h], r.own, r.exclusive, r.reason);
+        std::cout << b << std::endl;
+        o << r.rank << " " << objects[(size_t)sel.group[h]] << " " << sel.index[h];
+        const PoseCandidate* pc = poses[(size_t)sel.group[h]][(size_t)sel.index[h]];
+        for (int rr = 0; rr < 3; ++rr) for (int c = 0; c < 4; ++c) { snprintf(b, sizeof(b), " %.9g", (double)pc->transform(rr, c)); o << b; }
+        o << std::endl;
+    }
+    std::cout << "scene: hypotheses=" << sel.records.size() << " selected=" << sel.selected.size() << std::endl;
+    if (opt.masks) {
+        std::vector<unsigned char> px(sel.labels.size() * 2);
+        for (size_t i = 0; i < sel.labels.size(); ++i) { const unsigned v = (unsigned)(sel.labels[i] + 1); px[2 * i] = (unsigned char)(v >> 8); px[2 * i + 1] = (unsigned char)(v & 255u); }
+        std::ofstream pg(scene_path + "/labels_scene.pgm", std::ofstream::out | std::ofstream::binary);
+        pg << "P5\n" << image_width << " " << image_height << "\n65535\n";
+        pg.write((const char*)px.data(), (std::streamsize)px.size());
+    }
+    return 0;
+}
+
+static int run_frame_objects(const std::string& scene_path, const std::vector<std::string>& objects, uint64_t seed, int n_trials, int exact_ties,
+                             const SceneSelectOptions& scene_opt) {
     const size_t n = objects.size();
     std::vector<stocs::ModelCloud> models(n);
     std::vector<PPFMapType> maps(n);
@@ -372,14 +427,34 @@ static int run_frame_objects(const std::string& scene_path, const std::vector<st
     std::vector<std::ostringstream> blocks(n);
     std::vector<int> rcs(n, 0);
     std::atomic<size_t> next(0);
+    // --scene-select: the contexts stay alive until all objects are done, each with the frame (the depth image and its own class image)
+    std::vector<std::unique_ptr<stocs::stocs_estimator> > kept(n);
+    std::vector<std::vector<stocs::stocs_estimator::TrialResult> > trial_results(n);
+    std::vector<uint16_t> frame_depth;
+    if (scene_opt.on) {
+        try {
+            stocs::read_image(scene_path + "/depth.png", 1, 16, image_width, image_height, &frame_depth);
+        } catch (const std::exception& e) {
+            std::cerr << e.what() << std::endl;
+            return 1;
+        }
+    }
     auto worker = [&]() {
         for (size_t k; (k = next.fetch_add(1)) < n;) {
             std::ostringstream& os = blocks[k];
             os << "############# RUNNING STOCS for Scene: " << scene_path << ", Object: " << objects[k] << " ##############" << std::endl;
             try {
-                stocs::stocs_estimator est(models[k], maps[k], scenes[k], std::string(), image_width, image_height, distance_threshold, ppf_tr_discretization,
-                                           ppf_rot_discretization, edge_threshold, class_threshold, -1, &os);
-                rcs[k] = run_search(est, os, scene_path + "/best_pose_candidate_" + objects[k] + ".txt", std::string(), seed, n_trials, exact_ties, 0, 0);
+                std::unique_ptr<stocs::stocs_estimator> est(new stocs::stocs_estimator(models[k], maps[k], scenes[k], std::string(), image_width, image_height,
+                                                                                       distance_threshold, ppf_tr_discretization, ppf_rot_discretization, edge_threshold,
+                                                                                       class_threshold, -1, &os));
+                rcs[k] = run_search(*est, os, scene_path + "/best_pose_candidate_" + objects[k] + ".txt", std::string(), seed, n_trials, exact_ties, 0, 0, 0, NULL, std::string(),
+                                    std::string(), scene_opt.on ? &trial_results[k] : NULL);
+                if (scene_opt.on) {
+                    std::vector<uint16_t> prob;
+                    stocs::read_image(prob_paths[k], 1, 16, image_width, image_height, &prob);
+                    est->set_frame(frame_depth.data(), prob.data(), cam_intrinsics, depth_scale);
+                    kept[k] = std::move(est);
+                }
             } catch (const std::exception& e) {
                 os << "object " << objects[k] << " failed: " << e.what() << std::endl;
                 rcs[k] = 2;
@@ -395,6 +470,7 @@ static int run_frame_objects(const std::string& scene_path, const std::vector<st
         if (rcs[k] != 0 && rc == 0) rc = rcs[k];
     }
     std::cout << std::flush;
+    if (scene_opt.on && rc == 0) rc = run_scene_select(scene_path, objects, kept, trial_results, scene_opt);
     return rc;
 }
 
@@ -411,11 +487,13 @@ int main(int argc, char** argv) {
     float track_min_lcp = 0.02f;
     int do_cluster = 0, n_trials = 0, exact_ties = 0, n_refine = 0, depth_check = 0;
     bool do_instances = false, do_masks = false;
+    SceneSelectOptions scene_opt = {false, false, 0};
     stocs_instance_params inst_prm = stocs::stocs_estimator::default_instance_params();
     uint64_t seed = 1;
     for (int i = clouds ? 4 : 3; i < argc; i += 2) {
-        if (std::string(argv[i]) == "--depth-check") { depth_check = 1; --i; continue; }   // the two options without a value
+        if (std::string(argv[i]) == "--depth-check") { depth_check = 1; --i; continue; }   // the options without a value
         if (std::string(argv[i]) == "--masks") { do_masks = true; --i; continue; }
+        if (std::string(argv[i]) == "--scene-select") { scene_opt.on = true; --i; continue; }
         if (i + 1 >= argc) break;
         const std::string k = argv[i], v = argv[i + 1];
         if (k == "--edge") edge_path = v;
@@ -433,6 +511,7 @@ int main(int argc, char** argv) {
         else if (k == "--instances") { do_instances = true; inst_prm.max_instances = atoi(v.c_str()); }
         else if (k == "--instance-min-fraction") inst_prm.min_exclusive_fraction = (float)atof(v.c_str());
         else if (k == "--instance-min-points") inst_prm.min_points = atoi(v.c_str());
+        else if (k == "--scene-max-per-object") scene_opt.max_per_object = atoi(v.c_str());
         else if (k == "--repo") repo_path = v;
         else if (k == "--voxel") voxel_size = (float)atof(v.c_str());
         else if (k == "--depth-scale") depth_scale = (float)atof(v.c_str());
@@ -454,7 +533,13 @@ int main(int argc, char** argv) {
         return -1;
     }
 
-    if (do_masks && (clouds || !do_instances)) {
+    if ((scene_opt.on || scene_opt.max_per_object != 0) && (!scene_opt.on || clouds || a2.find(',') == std::string::npos || n_trials <= 0 || scene_opt.max_per_object < 0)) {
+        std::cerr << "--scene-select needs several objects and --trials N (--scene-max-per-object K >= 1 goes with it)" << std::endl;
+        return -1;
+    }
+    scene_opt.masks = scene_opt.on && do_masks;
+
+    if (do_masks && !scene_opt.on && (clouds || !do_instances)) {
         std::cerr << "--masks needs a scene directory and --instances M" << std::endl;
         return -1;
     }
@@ -471,7 +556,7 @@ int main(int argc, char** argv) {
             std::cerr << "several objects: --cluster, --refine, --out, --dbg, --edge and --track take a single object" << std::endl;
             return -1;
         }
-        return run_frame_objects(a1, objects, seed, n_trials, exact_ties);
+        return run_frame_objects(a1, objects, seed, n_trials, exact_ties, scene_opt);
     }
 
     std::unique_ptr<stocs::stocs_estimator> est;

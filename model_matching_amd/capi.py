@@ -82,6 +82,19 @@ class RenderResult(C.Structure):
                 ("in_front", C.c_int32), ("behind", C.c_int32), ("on_mask", C.c_int32)]
 
 
+class SceneRecord(C.Structure):
+    _fields_ = [("footprint", C.c_int32), ("no_depth", C.c_int32), ("agree", C.c_int32), ("in_front", C.c_int32), ("behind", C.c_int32),
+                ("on_mask", C.c_int32), ("claimed", C.c_int32)]
+
+
+class SceneParams(C.Structure):
+    _fields_ = [("max_selected", C.c_int32), ("min_pixels", C.c_int32), ("min_exclusive_fraction", C.c_float), ("max_violation_fraction", C.c_float)]
+
+
+class SceneResult(C.Structure):
+    _fields_ = [("rank", C.c_int32), ("own", C.c_int32), ("exclusive", C.c_int32), ("reason", C.c_int32)]
+
+
 class Camera(C.Structure):
     _fields_ = [("fx", C.c_float), ("cx", C.c_float), ("fy", C.c_float), ("cy", C.c_float), ("depth_scale", C.c_float),
                 ("width", C.c_int), ("height", C.c_int), ("normal_method", C.c_int)]
@@ -174,6 +187,11 @@ SIGNATURES = {
     "stocs_default_instance_params": (None, [C.POINTER(InstanceParams)]),
     "stocs_select_instances": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(InstanceParams), C.POINTER(InstanceResult), _ip, _intp]),
     "stocs_select_instances_rows": (C.c_int, [_vp, _ip, _u8p, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(InstanceParams), C.POINTER(InstanceResult), _ip, _intp]),
+    "stocs_default_scene_params": (None, [C.POINTER(SceneParams)]),
+    "stocs_scene_row_words": (C.c_int, [C.c_int, C.c_int]),
+    "stocs_scene_footprints": (C.c_int, [_vp, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(RenderParams), C.c_int, _vp, C.POINTER(SceneRecord)]),
+    "stocs_scene_select": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, _fp, _ip, C.POINTER(SceneRecord), C.c_int, _ip, C.POINTER(SceneParams),
+                                     C.POINTER(SceneResult), _ip, _intp]),
     "stocs_device_alloc_count": (C.c_int64, []),
     "stocs_debug_stream_audit_selftest": (C.c_int, [C.c_int, C.c_char_p, C.c_int]),
     "stocs_debug_streams_overlap": (C.c_int, [_vp]),

@@ -524,6 +524,7 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
     c->depth = NULL;
     c->instances = NULL;
     c->render = NULL;
+    c->scene = NULL;
     c->inst = NULL;
     c->trials = NULL; c->snrmw_trial0 = NULL; c->snrmw_stride = 0; c->snrmw_override = NULL; c->lcp_cand_trial = NULL;
     c->d_cand = NULL; c->cand_bytes = 0; c->n_cands = 0; c->cand_cap = 0; c->cands_stale = false;
@@ -670,6 +671,7 @@ int stocs_ctx_destroy(stocs_ctx* c) {
     stocs_internal_free_depth(c);
     stocs_internal_free_instances(c);
     stocs_internal_free_render(c);
+    stocs_internal_free_scene(c);
     c->grid_mem.destroy(); c->grid_ws.destroy();
     c->order.free(); c->cdf.free(); c->kd.free();
     if (c->h_pin) (void)hipHostFree(c->h_pin);

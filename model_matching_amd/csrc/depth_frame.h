@@ -1,7 +1,8 @@
 // depth_frame.h -- what the entry points that work on the frame of stocs_ctx_set_frame share: the frame's state on the context
 // (depth.hip owns it: stocs_ctx_set_frame fills it, stocs_internal_free_depth frees it), the kernel arguments that describe the camera,
-// and steps 1-3 of the depth-check contract (include/stocs_hip.h).  Included by depth.hip (stocs_depth_check_poses) and render.hip
-// (stocs_render_poses and its kin); both project a model point with the one project_point below.
+// and steps 1-3 of the depth-check contract (include/stocs_hip.h).  Included by depth.hip (stocs_depth_check_poses) and, through
+// render_rules.h, by render.hip (stocs_render_poses and its kin) and scene.hip (stocs_scene_footprints); all project a model point with the
+// one project_point below.
 #ifndef STOCS_DEPTH_FRAME_H
 #define STOCS_DEPTH_FRAME_H
 

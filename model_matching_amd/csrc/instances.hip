@@ -23,6 +23,7 @@
 
 #include "prims.h"
 #include "stocs_ctx.h"
+#include "wave_bits.h"
 
 namespace stocs {
 
@@ -34,15 +35,6 @@ struct InstancesState {
 };
 
 struct InstanceArgs { int32_t max_instances, min_points; float min_fraction; };
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int popc_andnot4(const uint4 e, const uint4 c) {
-    return __popc(e.x & ~c.x) + __popc(e.y & ~c.y) + __popc(e.z & ~c.z) + __popc(e.w & ~c.w);
-}
 
 // hypothesis h0 + blockIdx.x from row blockIdx.x of the chunk.  valid == NULL: every hypothesis is valid.  LDS: Wp words + 4.
 __global__ __launch_bounds__(256) void instance_mark_kernel(const int32_t* __restrict__ hit, const uint8_t* __restrict__ counted, const float* __restrict__ lcp_chunk,

@@ -18,52 +18,16 @@
 #include <string.h>
 
 #include "depth_frame.h"
+#include "render_rules.h"
 
 namespace stocs {
 
-enum { RENDER_CHUNK = 1024, RENDER_MAX_PIXELS = 1 << 19, RENDER_MAX_SPLAT = 16 };
+enum { RENDER_CHUNK = 1024, RENDER_MAX_PIXELS = 1 << 19 };
 enum { RC_FOOTPRINT = 0, RC_HIDDEN, RC_NO_DEPTH, RC_AGREE, RC_IN_FRONT, RC_BEHIND, RC_ON_MASK, RC_COUNTS };
 
 struct RenderState {
     DevBlock work;   // own key buffer (npix uint64, stocs_explain_poses) | poses (n x 16 float) | records | labels | state, grow-only
 };
-
-struct RenderArgs {
-    float point_radius;
-    int max_splat_px, id_base;
-};
-
-// the twelve entries the contract reads are finite (false for NaN); P is the same in every lane
-__device__ __forceinline__ bool pose_finite(const float* P) {
-    bool finite = true;
-#pragma unroll
-    for (int i = 0; i < 15; ++i)
-        if ((i & 3) != 3) finite = finite && (fabsf(P[i]) <= 3.4028234663852886e38f);
-    return finite;
-}
-
-// the splat rule: half-width in pixels of the square an in_image point at depth z touches
-__device__ __forceinline__ int splat_radius(float z, const DepthArgs& a, const RenderArgs& r) {
-    return (int)fminf(floorf((a.fx * r.point_radius) / z + 0.5f), (float)r.max_splat_px);
-}
-
-// steps 5-6 of the depth-check contract for a surface at depth z seen at pixel px: 1 no_depth, 2 agree, 3 in_front, 4 behind, + 16 on_mask
-__device__ __forceinline__ int classify_pixel(float z, size_t px, const uint16_t* __restrict__ depth, const uint16_t* __restrict__ prob, const DepthArgs& a) {
-    const uint16_t raw = depth[px];
-    if (raw == 0) return 1;
-    const float zo = (float)raw * a.depth_scale;
-    const float d = z - zo;
-    if (fabsf(d) <= a.tolerance) {
-        if (prob) {
-            const float cp = (float)((double)prob[px] * (1.0 / 10000));
-            if (!(cp < a.class_threshold)) return 2 + 16;
-        }
-        return 2;
-    }
-    if (d < -a.tolerance) return 3;
-    if (d > a.tolerance) return 4;
-    return 0;   // d is NaN: unreachable, z is a finite p_2 > 1e-6 and zo is finite
-}
 
 __global__ __launch_bounds__(256) void render_splat_kernel(const float* __restrict__ poses, const float4* __restrict__ mpos, const float4* __restrict__ mnrm, int nM,
                                                            DepthArgs a, RenderArgs ra, unsigned long long* __restrict__ zkey) {
@@ -192,32 +156,11 @@ static RenderState* render_state(stocs_ctx* c) {
     return (RenderState*)c->render;
 }
 
-static int check_params(const char* who, const stocs_render_params* p) {
-    if (!(p->point_radius >= 0.0f) || !isfinite(p->point_radius)) { set_error("%s: point_radius %g must be >= 0 and finite", who, (double)p->point_radius); return STOCS_ERR_INVALID; }
-    if (p->max_splat_px < 0 || p->max_splat_px > RENDER_MAX_SPLAT) { set_error("%s: max_splat_px %d outside 0..%d", who, p->max_splat_px, (int)RENDER_MAX_SPLAT); return STOCS_ERR_INVALID; }
-    if (!(p->tolerance > 0.0f) || !isfinite(p->tolerance)) { set_error("%s: tolerance %g must be positive and finite", who, (double)p->tolerance); return STOCS_ERR_INVALID; }
-    if (!isfinite(p->class_threshold)) { set_error("%s: class_threshold is not finite", who); return STOCS_ERR_INVALID; }
-    return STOCS_OK;
-}
-
 static int check_ids(const char* who, int n, int id_base) {
     if (id_base < 0 || (long long)id_base + (long long)n > 2147483647ll) {
         set_error("%s: ids %d .. %lld outside 0 .. 2^31 - 2", who, id_base, (long long)id_base + (long long)n - 1);
         return STOCS_ERR_INVALID;
     }
-    return STOCS_OK;
-}
-
-// the frame of stocs_ctx_set_frame, as stocs_depth_check_poses requires it
-static int check_frame(const char* who, stocs_ctx* c, DepthState** frame) {
-    DepthState* S = (DepthState*)c->depth;
-    if (!S || !S->has_frame) { set_error("%s: no frame (stocs_ctx_set_frame)", who); return STOCS_ERR_STATE; }
-    if (S->cam.width < 1 || S->cam.height < 1) { set_error("%s: image of %d x %d pixels", who, S->cam.width, S->cam.height); return STOCS_ERR_INVALID; }
-    if ((size_t)S->cam.width * (size_t)S->cam.height != S->npix) {
-        set_error("%s: the camera's %d x %d pixels are not the %zu uploaded", who, S->cam.width, S->cam.height, S->npix);
-        return STOCS_ERR_STATE;
-    }
-    *frame = S;
     return STOCS_OK;
 }
 
@@ -228,20 +171,6 @@ static int check_capacity(const char* who, const DepthState* S) {
     }
     return STOCS_OK;
 }
-
-static DepthArgs frame_args(const DepthState* S, const stocs_render_params* prm) {
-    DepthArgs a;
-    a.fx = S->cam.fx; a.cx = S->cam.cx; a.fy = S->cam.fy; a.cy = S->cam.cy; a.depth_scale = S->cam.depth_scale; a.W = S->cam.width; a.H = S->cam.height;
-    a.tolerance = prm->tolerance; a.class_threshold = prm->class_threshold; a.margin = 0.0f; a.self_occlusion = 0; a.cell_px = 1;
-    return a;
-}
-static RenderArgs render_args(const stocs_render_params* prm, int id_base) {
-    RenderArgs r;
-    r.point_radius = prm->point_radius; r.max_splat_px = prm->max_splat_px; r.id_base = id_base;
-    return r;
-}
-static const uint16_t* frame_depth(const DepthState* S) { return (const uint16_t*)S->frame.p; }
-static const uint16_t* frame_prob(const DepthState* S) { return S->has_prob ? (const uint16_t*)(S->frame.p + al256(S->npix * 2)) : (const uint16_t*)NULL; }
 
 // One call's layout.  The device block holds the context's own key buffer first (own_key pixels, 0 for the entry points that work on a
 // caller's buffer), then the regions below; the pinned block mirrors the regions alone, at the same offsets behind PIN_VAR.  Records,

@@ -371,6 +371,8 @@ struct stocs_ctx {
     void* instances;   // instances.hip (InstancesState): stocs_select_instances's grow-only workspace (last: no other member moves)
 
     void* render;      // render.hip (RenderState): the grow-only workspace of stocs_render_poses and its kin (last: no other member moves)
+
+    void* scene;       // scene.hip (SceneState): the grow-only workspaces of stocs_scene_footprints and stocs_scene_select (last: no other member moves)
 };
 
 namespace stocs {
@@ -427,6 +429,7 @@ extern "C" void stocs_internal_free_track(stocs_ctx* c);
 extern "C" void stocs_internal_free_depth(stocs_ctx* c);
 extern "C" void stocs_internal_free_instances(stocs_ctx* c);
 extern "C" void stocs_internal_free_render(stocs_ctx* c);
+extern "C" void stocs_internal_free_scene(stocs_ctx* c);
 // the congruent phase with a ceiling on its device memory: *too_big != 0 (and STOCS_OK) when the pair lists of the context's base set
 // would need more than max_bytes (0: no ceiling) or exceed 2^32 entries -- a trial batch then splits the base set and tries again
 extern "C" int stocs_internal_find_congruent(stocs_ctx* c, int64_t* total_quads, size_t max_bytes, int* too_big);

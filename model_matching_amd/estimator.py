@@ -43,6 +43,11 @@ _RENDER_DTYPE = np.dtype([(f[0], np.int32) for f in capi.RenderResult._fields_])
 assert _RENDER_DTYPE.itemsize == C.sizeof(capi.RenderResult)
 _INSTANCE_DTYPE = np.dtype([("rank", np.int32), ("own", np.int32), ("exclusive", np.int32), ("lcp", np.float32)])
 assert _INSTANCE_DTYPE.itemsize == C.sizeof(capi.InstanceResult)
+_SCENE_RECORD_DTYPE = np.dtype([(f[0], np.int32) for f in capi.SceneRecord._fields_])
+assert _SCENE_RECORD_DTYPE.itemsize == C.sizeof(capi.SceneRecord)
+_SCENE_RESULT_DTYPE = np.dtype([(f[0], np.int32) for f in capi.SceneResult._fields_])
+assert _SCENE_RESULT_DTYPE.itemsize == C.sizeof(capi.SceneResult)
+SCENE_CLAIMS = {"agree": 0, "on_mask": 1}
 
 # defaults of track_poses (tools/track_time.py's sweep, profiles/track_time.json)
 TRACK_DEFAULTS = dict(rounds=6, samples=2048, max_translation=0.02, max_rotation_deg=10.0, shrink=0.7, seed=0, refine_iterations=0,
@@ -403,6 +408,53 @@ class StocsEstimator:
         capi.check(self.L.stocs_explain_poses(self.h, pP, n, C.byref(prm), buf, lab.ctypes.data_as(capi._ip), st.ctypes.data_as(capi._u8p)))
         return np.frombuffer(buf, dtype=_RENDER_DTYPE, count=n).copy(), lab, st
 
+    def scene_footprints(self, poses16, rows, slot_base, n_slots, claim="agree", **render_params):
+        """n camera-frame poses of this context's model against the frame of set_frame (stocs_scene_footprints): pose h writes the pixels it
+        claims -- claim "agree" or "on_mask" -- as the bit row of slot slot_base + h of the device pool rows (n_slots rows of
+        scene_row_words(shape) uint32 each, e.g. from dev_alloc) -> a structured array with the fields of stocs_scene_record (footprint,
+        no_depth, agree, in_front, behind, on_mask, claimed), one record per pose.  render_params: fields of stocs_render_params."""
+        P, pP = capi.f32(poses16)
+        n = P.size // 16
+        if claim not in SCENE_CLAIMS:
+            raise ValueError("scene_footprints: claim %r is neither 'agree' nor 'on_mask'" % (claim,))
+        prm = self._render_params("scene_footprints", render_params)
+        buf = (capi.SceneRecord * max(n, 1))()
+        capi.check(self.L.stocs_scene_footprints(self.h, pP, n, int(slot_base), int(n_slots), C.byref(prm), SCENE_CLAIMS[claim], rows, buf))
+        return np.frombuffer(buf, dtype=_SCENE_RECORD_DTYPE, count=n).copy()
+
+    def scene_select(self, rows, shape, score, group, rec, group_cap=None, **params):
+        """The walk over slots 0 .. n-1 of the pool rows of a frame of shape (height, width) (stocs_scene_select): score (n,), group (n,)
+        ids, rec (n,) records of scene_footprints, group_cap one cap per group or None -> (records, selected): a structured array with
+        the fields of stocs_scene_result (rank or -1, own, exclusive, reason), one per slot, and the selected slots in rank order.
+        params: fields of stocs_scene_params (max_selected, min_pixels, min_exclusive_fraction, max_violation_fraction), and n_groups
+        (default: the number of caps, else the largest group id + 1).  Uses this context's device and workspace only."""
+        sc, psc = capi.f32(score)
+        gr, pgr = capi.i32(group)
+        rc = np.ascontiguousarray(rec, _SCENE_RECORD_DTYPE)
+        n = sc.size
+        if gr.size != n or rc.size != n:
+            raise ValueError("scene_select: %d scores, %d groups, %d records" % (n, gr.size, rc.size))
+        params = dict(params)
+        pcap = None
+        if group_cap is not None:
+            cap, pcap = capi.i32(group_cap)
+        n_groups = params.pop("n_groups", None)
+        if n_groups is None:
+            n_groups = cap.size if group_cap is not None else (int(gr.max()) + 1 if n else 1)
+        if group_cap is not None and cap.size != n_groups:
+            raise ValueError("scene_select: %d caps for %d groups" % (cap.size, n_groups))
+        prm = capi.SceneParams()
+        self.L.stocs_default_scene_params(C.byref(prm))
+        for k, v in params.items():
+            if k not in dict(capi.SceneParams._fields_):
+                raise TypeError("scene_select: unknown parameter %r" % k)
+            setattr(prm, k, v)
+        buf = (capi.SceneResult * max(n, 1))()
+        sel = np.zeros(max(n, 1), np.int32); ns = C.c_int(0)
+        capi.check(self.L.stocs_scene_select(self.h, rows, n, int(shape[1]), int(shape[0]), psc, pgr, rc.ctypes.data_as(C.POINTER(capi.SceneRecord)), int(n_groups),
+                                             pcap, C.byref(prm), buf, sel.ctypes.data_as(capi._ip), C.byref(ns)))
+        return np.frombuffer(buf, dtype=_SCENE_RESULT_DTYPE, count=n).copy(), sel[:ns.value].copy()
+
     def select_instances(self, T16, max_instances=16, min_points=20, min_exclusive_fraction=0.5):
         """Which of n centred-frame hypotheses (column-major 16 floats each) are distinct instances (stocs_select_instances): walked best
         first, one is kept only if enough of the scene points it explains are explained by none kept before it -> (records, selected):
@@ -623,6 +675,75 @@ class StocsEstimator:
         ms = C.c_float(0)
         capi.check(self.L.stocs_time_score_kernel(self.h, dT, n, dL, reps, C.byref(ms)))
         return ms.value
+
+
+def scene_row_words(shape):
+    """uint32 words of one pixel row of a frame of shape (height, width) (stocs_scene_row_words)"""
+    return int(capi.load().stocs_scene_row_words(int(shape[1]), int(shape[0])))
+
+
+def select_scene(estimators, poses_per_object, scores_per_object=None, max_per_object=None, labels=False, **params):
+    """Which hypotheses of several objects form one consistent explanation of the frame: estimators[k] holds object k's model and the
+    frame (set_frame, the same size everywhere), poses_per_object[k] its camera-frame hypotheses (m_k, 16).  The pool of pixel rows is
+    allocated on the first estimator, every estimator writes its footprints into consecutive slots (group = object index), and the
+    first estimator walks the pool (scene_select).  scores_per_object: one score array per object; default
+    float32(agree) / float32(footprint), 0 where the footprint is empty -- visible-surface agreement, comparable across objects (LCP is
+    not: its weights are per-object class probabilities).  max_per_object: an int or one cap per object.  params: fields of
+    stocs_scene_params, of stocs_render_params, and claim.  -> dict(records, selected, footprints, score, group, index) over the slots
+    (group / index: the object and the hypothesis of it a slot holds); with labels=True the selected poses of every object are rendered
+    into one key buffer with id = slot (render_poses, render_resolve, render_labels) and the dict also holds render (records of the
+    selected, in rank order), labels and state (the class image behind state's on_mask bit is the first estimator's)."""
+    if len(estimators) != len(poses_per_object) or not estimators:
+        raise ValueError("select_scene: %d estimators for %d pose sets" % (len(estimators), len(poses_per_object)))
+    render_keys, scene_keys = dict(capi.RenderParams._fields_), dict(capi.SceneParams._fields_)
+    claim = params.pop("claim", "agree")
+    rprm = {k: v for k, v in params.items() if k in render_keys}
+    sprm = {k: v for k, v in params.items() if k in scene_keys}
+    for k in params:
+        if k not in render_keys and k not in scene_keys:
+            raise TypeError("select_scene: unknown parameter %r" % k)
+    first = estimators[0]
+    shape = first._frame_shape("select_scene")
+    if any(e._frame_shape("select_scene") != shape for e in estimators):
+        raise ValueError("select_scene: the estimators' frames differ in size")
+    P = [np.ascontiguousarray(p, np.float32).reshape(-1, 16) for p in poses_per_object]
+    n = sum(len(p) for p in P)
+    group = np.concatenate([np.full(len(p), k, np.int32) for k, p in enumerate(P)])
+    index = np.concatenate([np.arange(len(p), dtype=np.int32) for p in P])
+    cap = None if max_per_object is None else np.ascontiguousarray(np.broadcast_to(np.asarray(max_per_object, np.int32), (len(P),)))
+    out = dict(group=group, index=index)
+    rows = first.dev_alloc(max(n, 1) * scene_row_words(shape) * 4)
+    zkey = None
+    try:
+        foot, base = [], 0
+        for est, p in zip(estimators, P):
+            foot.append(est.scene_footprints(p, rows, base, n, claim, **rprm))
+            base += len(p)
+        foot = np.concatenate(foot)
+        if scores_per_object is None:
+            score = np.zeros(n, np.float32)
+            some = foot["footprint"] > 0
+            score[some] = foot["agree"][some].astype(np.float32) / foot["footprint"][some].astype(np.float32)
+        else:
+            score = np.concatenate([np.asarray(s, np.float32).reshape(-1) for s in scores_per_object]).astype(np.float32)
+            if score.size != n:
+                raise ValueError("select_scene: %d scores for %d hypotheses" % (score.size, n))
+        rec, sel = first.scene_select(rows, shape, score, group, foot, cap, n_groups=len(P), **sprm)
+        out.update(records=rec, selected=sel, footprints=foot, score=score)
+        if labels:
+            if len(sel) == 0:
+                out.update(render=np.zeros(0, _RENDER_DTYPE), labels=np.full(shape, -1, np.int32), state=np.zeros(shape, np.uint8))
+            else:
+                zkey = first.dev_alloc(shape[0] * shape[1] * 8)
+                for i, s in enumerate(sel.tolist()):
+                    estimators[group[s]].render_poses(P[group[s]][index[s]], zkey, s, i == 0, **rprm)
+                out["render"] = np.concatenate([estimators[group[s]].render_resolve(P[group[s]][index[s]], zkey, s, **rprm) for s in sel.tolist()])
+                out["labels"], out["state"] = first.render_labels(zkey, **rprm)
+    finally:
+        first.dev_free(rows)
+        if zkey is not None:
+            first.dev_free(zkey)
+    return out
 
 
 def kdtree_nn_host(pos3, queries3, sqdist):
