@@ -135,8 +135,9 @@ int stocs_weight_fix_check(stocs_ctx* ctx, int64_t* n_mismatch);
 int stocs_try_sampled_base(stocs_ctx* ctx, int32_t* ids4_inout, float* inv2, int* valid);
 /* the seeded weighted draw itself (stocs.cpp:133-148 replacement): index or -1 */
 int stocs_draw(stocs_ctx* ctx, const float* w, int n, uint64_t r64, int* index);
-/* Which kernel form the last class-mode stocs_sample_bases or stocs_run_trials* call on the context ran (tests only; no device
- * work, no synchronisation, no allocation; any output pointer may be NULL).  STOCS_ERR_STATE before the first such call.
+/* Which kernel form the last stocs_sample_bases or stocs_run_trials* call on the context ran, class mode or instance mode (tests only;
+ * no device work, no synchronisation, no allocation; any output pointer may be NULL).  STOCS_ERR_STATE: no sampling call on the
+ * context yet.
  *   *kernel     one of the STOCS_FORM_* values below
  *   *threads    threads per workgroup of the attempts kernel
  *   *lds_bytes  its dynamic LDS per workgroup
@@ -157,9 +158,23 @@ int stocs_draw(stocs_ctx* ctx, const float* w, int n, uint64_t r64, int* index);
  *   Otherwise the full-size kernel, 1024 threads, cap = 0:
  *     S <= 26000 and STOCS_INSTANCE_NO_LDS unset: FULL_LDS, lds_bytes = a16(4 S) + 2 S + 16, launches = 1;
  *     else FULL_DEVICE_MEMORY, lds_bytes = 0; stocs_sample_bases: launches = 1; a trial batch of n attempts in all runs
- *     p = max(1, min(n, floor(2^30 / (8 S)))) attempts per launch (at most 1 GiB of working set): launches = ceil(n / p). */
-enum { STOCS_FORM_LEAN = 0, STOCS_FORM_FULL_LDS = 1, STOCS_FORM_FULL_DEVICE_MEMORY = 2, STOCS_FORM_NINE_LAUNCH = 3 };
+ *     p = max(1, min(n, floor(2^30 / (8 S)))) attempts per launch (at most 1 GiB of working set): launches = ceil(n / p).
+ * Instance mode (mode 1) has one kernel, a pair of 1024-thread workgroups per trial, in two forms of the attempt's working set:
+ *   S <= 16000 and STOCS_INSTANCE_NO_LDS unset: INSTANCE_LDS, lds_bytes = 65552 + a16(4 S) + 2 S + 16 (65552 = a16(4 * 16385): the
+ *   union-find parents of a disc of up to 16384 runs, which both forms keep in LDS); else INSTANCE_DEVICE_MEMORY, lds_bytes = 65552.
+ *   threads = 1024, cap = 0, redone = 0; launches = 1 for stocs_sample_bases, ceil(n_trials / max(1, n_cu / 2)) for a trial batch on a
+ *   device of n_cu compute units. */
+enum { STOCS_FORM_LEAN = 0, STOCS_FORM_FULL_LDS = 1, STOCS_FORM_FULL_DEVICE_MEMORY = 2, STOCS_FORM_NINE_LAUNCH = 3, STOCS_FORM_INSTANCE_LDS = 4,
+       STOCS_FORM_INSTANCE_DEVICE_MEMORY = 5 };
 int stocs_last_sampling_form(const stocs_ctx* ctx, int* kernel, int* threads, int64_t* lds_bytes, int* cap, int* launches, int* redone);
+/* What every attempt of the last stocs_sample_bases(mode 1) call on the context did in its first workgroup (tests only; copies from the
+ * device and may synchronise; not kept for trial batches).  rec4[4 a ..]: the survivors of pass 1 inside the mask, point 1 (-1 when the
+ * first draw failed), 1 when the attempt got as far as its mask, and the path of the mask: the number of passable runs in the image rows
+ * of the disc for a new flood fill (up to 16384 the union-find parents are in LDS, beyond that in device memory), -1 when the seed pixel
+ * was labelled already and the mask of that earlier attempt was taken, 0 when the first draw failed.  *n = attempts of that call; at most
+ * cap records are written (STOCS_ERR_CAPACITY when there are more; rec4 may be NULL to ask for *n).  STOCS_ERR_STATE before the first
+ * such call. */
+int stocs_last_instance_attempts(stocs_ctx* ctx, int32_t* rec4, int cap, int* n);
 /* Point 1 of the lean class kernel on its own (tests only): index[k] = the point the lean kernel draws first for the 64-bit word
  * r64[k] against the context's current prior -- the first scene index whose inclusive prefix sum of the 2^32 fixed-point prior
  * weights exceeds mulhi64(r64[k], total) -- or -1 when the total is zero.  Brings the prior's prefix sums up to date as a lean call

@@ -11,8 +11,8 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libstocs_hip.so")
 
 STOCS_OK = 0
-ERR_INVALID, ERR_CAPACITY = -1, -4
-FORM_NAMES = {0: "lean", 1: "full_lds", 2: "full_device_memory", 3: "nine_launch"}   # STOCS_FORM_* of include/stocs_hip.h
+ERR_INVALID, ERR_CAPACITY, ERR_STATE = -1, -4, -5
+FORM_NAMES = {0: "lean", 1: "full_lds", 2: "full_device_memory", 3: "nine_launch", 4: "instance_lds", 5: "instance_device_memory"}   # STOCS_FORM_* of include/stocs_hip.h
 ERR_NAMES = {0: "OK", -1: "INVALID", -2: "NO_DEVICE", -3: "HIP", -4: "CAPACITY", -5: "STATE", -6: "NOMEM"}
 
 
@@ -136,6 +136,7 @@ SIGNATURES = {
     "stocs_try_sampled_base": (C.c_int, [_vp, _ip, _fp, _intp]),
     "stocs_draw": (C.c_int, [_vp, _fp, C.c_int, C.c_uint64, _intp]),
     "stocs_last_sampling_form": (C.c_int, [_vp, _intp, _intp, _i64p, _intp, _intp, _intp]),
+    "stocs_last_instance_attempts": (C.c_int, [_vp, _ip, C.c_int, _intp]),
     "stocs_debug_draw_point1": (C.c_int, [_vp, C.POINTER(C.c_uint64), C.c_int, _ip]),
     "stocs_find_congruent_all": (C.c_int, [_vp, _i64p]),
     "stocs_get_quads": (C.c_int, [_vp, C.c_int, _ip, C.c_int64, _i64p]),

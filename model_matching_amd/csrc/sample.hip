@@ -616,7 +616,9 @@ struct InstanceArgs {
     float4* spos_w; float4* snrm_w;   // the scene arrays whose .w the LCP adds: refreshed with the decayed prior at the end
     BaseOut* res;
     // hand-over from the workgroup that runs point 1 + mask of every attempt to the one that runs points 2..4 (below)
-    int4* q_hdr;                // per attempt: survivors, point 1, 1 when the attempt got as far as its mask
+    int4* q_hdr;                // per attempt: survivors, point 1, 1 when the attempt got as far as its mask, and which path its mask took: the node
+                                // count of the disc's rows for a new flood fill, -1 for an earlier attempt's mask, 0 when the first draw failed
+                                // (stocs_last_instance_attempts; the second workgroup does not read that word)
     int32_t* q_sv; float* q_w;  // per attempt S slots: the survivors (scene index, weight)
     unsigned int* q_flag;       // per attempt: 1 once the slot is complete
     unsigned int* q_err;        // set when the second workgroup gave up waiting
@@ -860,8 +862,6 @@ __global__ __launch_bounds__(1024) void instance_attempts_kernel(InstanceArgs A,
     uint32_t* parent_l = (uint32_t*)inst_dyn;                               // INST_MAX_NODES + 1
     const int S = A.pa.S;
     const size_t o_w = ((size_t)(INST_MAX_NODES + 1) * 4 + 15) & ~(size_t)15;
-    float* w = WLDS ? (float*)(inst_dyn + o_w) : A.w;                       // weights; after the compaction the survivors' weights
-    sv_t* sv = WLDS ? (sv_t*)(inst_dyn + o_w + (((size_t)S * 4 + 15) & ~(size_t)15)) : (sv_t*)A.sv;   // survivors of pass 1 inside the mask, in scene order
     const float4* spos = A.pa.spos;
     const float4* snrm = A.pa.snrm;
     bool first_role = blockIdx.x == 0;
@@ -876,6 +876,9 @@ __global__ __launch_bounds__(1024) void instance_attempts_kernel(InstanceArgs A,
         INST_ADV(A.snrm_w); INST_ADV(A.res); INST_ADV(A.q_hdr); INST_ADV(A.q_sv); INST_ADV(A.q_w); INST_ADV(A.q_flag); INST_ADV(A.q_err);
 #undef INST_ADV
     }
+    // (behind the trial's offset: in device memory every trial of a batch has a working set of its own)
+    float* w = WLDS ? (float*)(inst_dyn + o_w) : A.w;                       // weights; after the compaction the survivors' weights
+    sv_t* sv = WLDS ? (sv_t*)(inst_dyn + o_w + (((size_t)S * 4 + 15) & ~(size_t)15)) : (sv_t*)A.sv;   // survivors of pass 1 inside the mask, in scene order
     unsigned long long tprev = A.stamps ? __builtin_amdgcn_s_memtime() : 0ull;
     // (debug) the stage clocks are summed in scalar registers and written once at the end: a read-modify-write of device
     // memory per stamp would cost more than most stages
@@ -1014,7 +1017,7 @@ __global__ __launch_bounds__(1024) void instance_attempts_kernel(InstanceArgs A,
         {
             STAGE_THREAD()
             for (int j = t; j < n_surv; j += 1024) { A.q_sv[(size_t)a * S + j] = (int32_t)sv[j]; A.q_w[(size_t)a * S + j] = w[j]; }
-            if (t == 0) A.q_hdr[a] = make_int4(n_surv, b1, 1, 0);
+            if (t == 0) A.q_hdr[a] = make_int4(n_surv, b1, 1, lab == 0 ? (int)nodes : -1);
         }
         INST_STAMP(4)
         if (A.stamps && threadIdx.x == 0) A.stamps[9] += (unsigned long long)n_surv;
@@ -1533,6 +1536,8 @@ struct InstanceState {
     float* d_cls = NULL; uint32_t* d_maskbits = NULL; uint32_t* d_segbits = NULL; uint32_t* d_parent = NULL;
     int32_t* d_sv = NULL; float* d_w = NULL;
     RunPair* d_pairs = NULL; uint32_t* d_pair_off = NULL;
+    unsigned long long* d_stamps = NULL;            // 128 bytes of stage clocks (STOCS_DEBUG_TIMING)
+    int hdr_n = -1;                                 // attempts of the last stocs_sample_bases(mode 1) call whose headers d_queue holds (-1: none)
     char* d_queue = NULL; size_t queue_bytes = 0;   // hand-over slots between the two workgroups (grown on demand)
     DevBlock trials;                                // per-trial copies of the mutable state of a trial batch (stocs_run_trials)
     size_t n_runs = 0;
@@ -1605,14 +1610,14 @@ static int prepare_instance_state(stocs_ctx* c) {
     const size_t o_rs = 0, o_re = o_rs + al256(nr * 2), o_ro = o_re + al256(nr * 2), o_pr = o_ro + al256(((size_t)H + 1) * 4), o_ep = o_pr + al256((size_t)S * 4),
                  o_pi = o_ep + al256(S), o_lb = o_pi + al256(S), o_cl = o_lb + al256(S), o_mb = o_cl + al256((size_t)S * 4), o_sb = o_mb + al256((size_t)256 * Sw * 4),
                  o_pa = o_sb + al256((size_t)Sw * 4), o_sv = o_pa + al256((nr + 1) * 4), o_wc = o_sv + al256((size_t)S * 4), o_pp = o_wc + al256((size_t)S * 4),
-                 o_po = o_pp + al256(std::max<size_t>(pairs.size(), 1) * sizeof(RunPair)), total = o_po + al256(((size_t)H + 1) * 4);
+                 o_po = o_pp + al256(std::max<size_t>(pairs.size(), 1) * sizeof(RunPair)), o_st = o_po + al256(((size_t)H + 1) * 4), total = o_st + 256;
     { const int rc = I->mem.grow(c->stream, total); if (rc) return rc; }
     char* m = I->mem.p;
     I->d_run_s = (uint16_t*)(m + o_rs); I->d_run_e = (uint16_t*)(m + o_re); I->d_row_off = (uint32_t*)(m + o_ro); I->d_pt_run = (int32_t*)(m + o_pr);
     I->d_edge_pt = (uint8_t*)(m + o_ep); I->d_prev_in = (uint8_t*)(m + o_pi); I->d_label = (uint8_t*)(m + o_lb); I->d_cls = (float*)(m + o_cl);
     I->d_maskbits = (uint32_t*)(m + o_mb); I->d_segbits = (uint32_t*)(m + o_sb); I->d_parent = (uint32_t*)(m + o_pa);
     I->d_sv = (int32_t*)(m + o_sv); I->d_w = (float*)(m + o_wc);
-    I->d_pairs = (RunPair*)(m + o_pp); I->d_pair_off = (uint32_t*)(m + o_po);
+    I->d_pairs = (RunPair*)(m + o_pp); I->d_pair_off = (uint32_t*)(m + o_po); I->d_stamps = (unsigned long long*)(m + o_st);
     I->S = S; I->Sw = Sw; I->n_runs = rs.size();
     hipStream_t st = c->stream;
     if (!rs.empty()) {
@@ -1664,10 +1669,13 @@ static InstanceArgs instance_args(const stocs_ctx* c, const InstanceState* I) {
 
 // n_workgroups of the instance kernel (a pair per trial): the union-find parents, and up to INST_LDS_POINTS points' weights + survivor
 // indices, in LDS (<= 160 KB per workgroup on gfx950)
-static int launch_instance_attempts(stocs_ctx* c, const InstanceArgs& A, unsigned n_workgroups, uint64_t seed, int first_attempt, int n_attempts, float dispersion) {
+static int launch_instance_attempts(stocs_ctx* c, const InstanceArgs& A, unsigned n_workgroups, uint64_t seed, int first_attempt, int n_attempts, float dispersion, int launches) {
     const size_t lds_parent = ((size_t)(INST_MAX_NODES + 1) * 4 + 15) & ~(size_t)15;
     const bool wlds = c->nS <= INST_LDS_POINTS && !getenv("STOCS_INSTANCE_NO_LDS");
     const size_t lds = lds_parent + (wlds ? class_work_lds((size_t)c->nS) : 0);
+    // what stocs_last_sampling_form reports of an instance-mode call (`launches`: of the whole call, the same for each of its pieces)
+    c->last_form.kernel = wlds ? STOCS_FORM_INSTANCE_LDS : STOCS_FORM_INSTANCE_DEVICE_MEMORY; c->last_form.threads = 1024; c->last_form.lds = lds;
+    c->last_form.cap = 0; c->last_form.launches = launches; c->last_form.redone = 0;
     const void* fn = wlds ? (const void*)instance_attempts_kernel<true> : (const void*)instance_attempts_kernel<false>;
     STOCS_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, MAX_DYNAMIC_LDS));   // (the parents alone are beyond 64 KB)
     void* args[] = {(void*)&A, &seed, &first_attempt, &n_attempts, &dispersion};
@@ -1684,7 +1692,7 @@ static int sample_instance(stocs_ctx* c, uint64_t seed, int first_attempt, int n
     InstanceArgs A = instance_args(c, I);
     A.cls = I->d_cls; A.prev_in = I->d_prev_in; A.label = I->d_label; A.maskbits = I->d_maskbits; A.segbits = I->d_segbits; A.parent_g = I->d_parent;
     const bool dbg = getenv("STOCS_DEBUG_TIMING") != NULL;
-    if (dbg) { A.stamps = (unsigned long long*)I->d_parent; STOCS_HIP_CHECK(hipMemsetAsync(I->d_parent, 0, 128, c->stream)); }   // parent_g is idle for small discs
+    if (dbg) { A.stamps = I->d_stamps; STOCS_HIP_CHECK(hipMemsetAsync(I->d_stamps, 0, 128, c->stream)); }
     A.w = I->d_w; A.sv = I->d_sv; A.spos_w = c->d_spos; A.snrm_w = c->d_snrmw; A.res = sb.res;
     c->prior_epoch++;       // (the kernel writes the decayed prior into the scene arrays)
     A.n_trials = 0; A.trial_stride = 0; A.seeds = NULL;
@@ -1704,7 +1712,9 @@ static int sample_instance(stocs_ctx* c, uint64_t seed, int first_attempt, int n
         A.q_sv = (int32_t*)(I->d_queue + o_sv); A.q_w = (float*)(I->d_queue + o_w);
         STOCS_HIP_CHECK(hipMemsetAsync(I->d_queue + o_flag, 0, o_sv - o_flag, c->stream));   // flags and the error word
     }
-    if ((rc = launch_instance_attempts(c, A, 2, seed, first_attempt, nB, dispersion))) return rc;
+    I->hdr_n = -1;
+    if ((rc = launch_instance_attempts(c, A, 2, seed, first_attempt, nB, dispersion, 1))) return rc;
+    I->hdr_n = nB;
     I->h_segbits.assign((size_t)I->Sw, 0);
     // everything that comes back lands in the context's pinned block first (results | decayed prior | segment bits | error word)
     const size_t rb_res = al256((size_t)nB * sizeof(BaseOut)), rb_cls = al256((size_t)c->nS * 4), rb_seg = al256((size_t)I->Sw * 4);
@@ -1724,7 +1734,7 @@ static int sample_instance(stocs_ctx* c, uint64_t seed, int first_attempt, int n
     if (q_err) { set_error("instance-mode sampling: the second workgroup gave up waiting for the first"); return STOCS_ERR_HIP; }
     if (dbg) {
         unsigned long long st[16];
-        STOCS_HIP_CHECK(hipMemcpy(st, I->d_parent, 128, hipMemcpyDeviceToHost));
+        STOCS_HIP_CHECK(hipMemcpy(st, I->d_stamps, 128, hipMemcpyDeviceToHost));
         const double per = 1.0 / std::max(nB, 1);
         fprintf(stderr, "[stocs instance] %d attempts, shader cycles per attempt (s_memtime).  first workgroup: weights + publish %.0f | draw 1 %.0f | pass 1 + max distance %.0f | flood fill %.0f | bookkeeping + compaction + hand-over %.0f.  second workgroup: waiting %.0f | points 2-4 %.0f | ordered bases (once, /attempt) %.0f\n",
                 nB, st[0] * per, st[1] * per, st[2] * per, st[3] * per, st[4] * per, st[5] * per, st[6] * per, st[7] * per);
@@ -1833,7 +1843,7 @@ int sample_trials(stocs_ctx* c, int mode, int nT, const uint64_t* seeds, int nA,
         TR_ADV(cls); TR_ADV(prev_in); TR_ADV(label); TR_ADV(maskbits); TR_ADV(segbits); TR_ADV(parent_g); TR_ADV(w); TR_ADV(sv); TR_ADV(snrm_w); TR_ADV(res);
         TR_ADV(q_hdr); TR_ADV(q_sv); TR_ADV(q_w); TR_ADV(q_flag); TR_ADV(q_err);
 #undef TR_ADV
-        if ((rc = launch_instance_attempts(c, B, 2u * (unsigned)n, 0, 0, nA, dispersion))) return rc;
+        if ((rc = launch_instance_attempts(c, B, 2u * (unsigned)n, 0, 0, nA, dispersion, (nT + per_launch - 1) / per_launch))) return rc;
     }
     // results and error words of all trials: strided rows of the block
     std::vector<unsigned int> q_err((size_t)nT, 0u);
@@ -2003,7 +2013,7 @@ int stocs_weight_fix_check(stocs_ctx* c, int64_t* n_mismatch) {
 
 int stocs_last_sampling_form(const stocs_ctx* c, int* kernel, int* threads, int64_t* lds_bytes, int* cap, int* launches, int* redone) {
     if (!c) return STOCS_ERR_INVALID;
-    if (c->last_form.kernel < 0) { set_error("stocs_last_sampling_form: no class-mode sampling call on this context yet"); return STOCS_ERR_STATE; }
+    if (c->last_form.kernel < 0) { set_error("stocs_last_sampling_form: no sampling call on this context yet"); return STOCS_ERR_STATE; }
     if (kernel) *kernel = c->last_form.kernel;
     if (threads) *threads = c->last_form.threads;
     if (lds_bytes) *lds_bytes = (int64_t)c->last_form.lds;
@@ -2011,6 +2021,21 @@ int stocs_last_sampling_form(const stocs_ctx* c, int* kernel, int* threads, int6
     if (launches) *launches = c->last_form.launches;
     if (redone) *redone = c->last_form.redone;
     return STOCS_OK;
+}
+
+int stocs_last_instance_attempts(stocs_ctx* c, int32_t* rec4, int cap, int* n) {
+    if (!c || !n || cap < 0 || (cap && !rec4)) return STOCS_ERR_INVALID;
+    const InstanceState* I = (const InstanceState*)c->inst;
+    if (!I || I->hdr_n < 0 || !I->d_queue) { set_error("stocs_last_instance_attempts: no instance-mode stocs_sample_bases call on this context yet"); return STOCS_ERR_STATE; }
+    *n = I->hdr_n;
+    if (!rec4) return STOCS_OK;
+    DeviceGuard dev_guard(c->device);
+    const int m = std::min(cap, I->hdr_n);
+    if (m > 0) {
+        STOCS_HIP_CHECK(hipMemcpyAsync(rec4, I->d_queue, (size_t)m * 16, hipMemcpyDeviceToHost, c->stream));   // the headers lead the queue
+        STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    }
+    return I->hdr_n > cap ? STOCS_ERR_CAPACITY : STOCS_OK;
 }
 
 int stocs_debug_draw_point1(stocs_ctx* c, const uint64_t* r64, int n, int32_t* index) {

@@ -364,7 +364,7 @@ struct stocs_ctx {
 
     void* depth;    // depth.hip (DepthState): the frame of stocs_ctx_set_frame and stocs_depth_check_poses's grow-only workspace (last: no other member moves)
 
-    // what the last class-mode stocs_sample_bases / stocs_run_trials* call ran (sample.hip; read by stocs_last_sampling_form): host
+    // what the last stocs_sample_bases / stocs_run_trials* call ran, class or instance mode (sample.hip; read by stocs_last_sampling_form): host
     // bookkeeping only.  kernel < 0: no class-mode call yet
     struct { int kernel, threads; size_t lds; int cap, launches, redone; } last_form;
 

@@ -181,12 +181,23 @@ class StocsEstimator:
         return idx.value
 
     def last_sampling_form(self):
-        """-> dict(kernel, threads, lds_bytes, cap, launches, redone) of the last class-mode sample_bases / run_trials call
+        """-> dict(kernel, threads, lds_bytes, cap, launches, redone) of the last sample_bases / run_trials call, class or instance mode
         (stocs_last_sampling_form); kernel is one of capi.FORM_NAMES' names."""
         k, t, cap, nl, nr = C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0), C.c_int(0)
         lds = C.c_int64(0)
         capi.check(self.L.stocs_last_sampling_form(self.h, C.byref(k), C.byref(t), C.byref(lds), C.byref(cap), C.byref(nl), C.byref(nr)))
         return dict(kernel=capi.FORM_NAMES[k.value], threads=t.value, lds_bytes=lds.value, cap=cap.value, launches=nl.value, redone=nr.value)
+
+    def last_instance_attempts(self):
+        """-> (n, 4) int32, one row per attempt of the last sample_bases(mode=1) call: survivors inside the mask, point 1, whether the
+        attempt reached its mask, and the mask's path -- runs in the disc's rows for a new flood fill, -1 for a reused mask, 0 for a
+        failed first draw (stocs_last_instance_attempts)."""
+        n = C.c_int(0)
+        capi.check(self.L.stocs_last_instance_attempts(self.h, None, 0, C.byref(n)))
+        rec = np.zeros((n.value, 4), np.int32)
+        if n.value:
+            capi.check(self.L.stocs_last_instance_attempts(self.h, rec.ctypes.data_as(capi._ip), n.value, C.byref(n)))
+        return rec
 
     def debug_draw_point1(self, r64):
         """-> the point the lean class kernel draws first for every 64-bit word of r64 against the current prior, -1 for a zero

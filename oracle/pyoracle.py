@@ -73,6 +73,8 @@ def lib():
         L.orc_get_scene.argtypes = [vp, fp, fp, fp]
         L.orc_get_model.argtypes = [vp, fp]
         L.orc_set_edge_map.argtypes = [vp, u8p]
+        L.orc_restart_trial.argtypes = [vp, fp]
+        L.orc_restart_trial.restype = None
         L.orc_ctx_index.argtypes = [vp]
         L.orc_ctx_index.restype = vp
         L.orc_rng.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64]
@@ -264,6 +266,10 @@ class Oracle:
     def set_edge_map(self, edge):
         e = np.ascontiguousarray(edge, np.uint8)
         lib().orc_set_edge_map(self.h, e.ctypes.data_as(C.POINTER(C.c_uint8)))
+
+    def restart_trial(self):
+        """a new instance-mode trial: the prior of the constructor, no previous segment, labels or masks (the edge map stays)"""
+        lib().orc_restart_trial(self.h, self.spr.ctypes.data_as(C.POINTER(C.c_float)))
 
     def index_lookup(self, key):
         k, pk = _i(key)

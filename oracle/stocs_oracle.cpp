@@ -1169,6 +1169,14 @@ orc_ctx* orc_ctx_create(const orc_params* prm, const float* sp, const float* sn,
     c->segmentation_buffer.assign(px, 0);
     return c;
 }
+// a new trial on the same scene, model and edge map: the prior as given (the one of orc_ctx_create), no previous segment, no labels, no masks
+void orc_restart_trial(orc_ctx* c, const float* sprob) {
+    for (size_t i = 0; i < c->scene.size(); ++i) c->scene[i].class_prob = c->scene[i].cur_prob = sprob[i];
+    std::fill(c->previous_segment.begin(), c->previous_segment.end(), (uint8_t)0);
+    std::fill(c->segmentation_buffer.begin(), c->segmentation_buffer.end(), (uint8_t)0);
+    c->seg_masks.clear();
+    c->last_segment.clear();
+}
 void orc_ctx_destroy(orc_ctx* c) {
     if (!c) return;
     if (c->index) orc_index_free(c->index);

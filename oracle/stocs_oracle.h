@@ -74,6 +74,8 @@ void     orc_get_centroids(const orc_ctx*, float* scene3, float* model3);
 void     orc_get_scene(const orc_ctx*, float* pos3, float* prob, float* class_prob);
 void     orc_get_model(const orc_ctx*, float* pos3);
 void     orc_set_edge_map(orc_ctx*, const uint8_t* edge /* h*w, png value */);
+/* a new instance-mode trial on the same scene, model and edge map: class probabilities set to sprob (nS), image-space state cleared */
+void     orc_restart_trial(orc_ctx*, const float* sprob);
 const orc_index* orc_ctx_index(const orc_ctx*);
 
 /* ---- rows 3-7: base sampling.  The clock-seeded std::discrete_distribution of

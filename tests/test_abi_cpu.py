@@ -33,25 +33,29 @@ def test_exports_every_declared_symbol(capi):
 
 
 def test_sampling_form_and_point1_entries_are_bound(capi, tmp_path):
-    """stocs_last_sampling_form and stocs_debug_draw_point1: exported, bound with their argument lists, wrapped by the estimator, and
+    """stocs_last_sampling_form, stocs_last_instance_attempts and stocs_debug_draw_point1: exported, bound with their argument lists, wrapped by the estimator, and
     callable from C99 with the header's STOCS_FORM_* names."""
     lib = C.CDLL(capi.LIB_PATH)
-    assert hasattr(lib, "stocs_last_sampling_form") and hasattr(lib, "stocs_debug_draw_point1")
+    assert hasattr(lib, "stocs_last_sampling_form") and hasattr(lib, "stocs_debug_draw_point1") and hasattr(lib, "stocs_last_instance_attempts")
     L = capi.load()
     assert L.stocs_last_sampling_form.restype is C.c_int and len(L.stocs_last_sampling_form.argtypes) == 7
     assert L.stocs_debug_draw_point1.restype is C.c_int and len(L.stocs_debug_draw_point1.argtypes) == 4
     assert L.stocs_last_sampling_form(None, None, None, None, None, None, None) == capi.ERR_INVALID
     assert L.stocs_debug_draw_point1(None, None, 0, None) == capi.ERR_INVALID
-    assert capi.FORM_NAMES == {0: "lean", 1: "full_lds", 2: "full_device_memory", 3: "nine_launch"}
+    assert L.stocs_last_instance_attempts.restype is C.c_int and len(L.stocs_last_instance_attempts.argtypes) == 4
+    assert L.stocs_last_instance_attempts(None, None, 0, None) == capi.ERR_INVALID
+    assert capi.FORM_NAMES == {0: "lean", 1: "full_lds", 2: "full_device_memory", 3: "nine_launch", 4: "instance_lds", 5: "instance_device_memory"}
     from model_matching_amd.estimator import StocsEstimator
     assert callable(getattr(StocsEstimator, "last_sampling_form")) and callable(getattr(StocsEstimator, "debug_draw_point1"))
+    assert callable(getattr(StocsEstimator, "last_instance_attempts"))
     src = tmp_path / "form_c99.c"
     src.write_text(
         "#include <stddef.h>\n#include \"stocs_hip.h\"\n"
         "int call(stocs_ctx* c, const uint64_t* r, int32_t* idx) {\n"
-        "    int kernel, threads, cap, launches, redone; int64_t lds;\n"
+        "    int kernel, threads, cap, launches, redone, n; int64_t lds;\n"
         "    int rc = stocs_last_sampling_form(c, &kernel, &threads, &lds, &cap, &launches, &redone) + stocs_last_sampling_form(c, NULL, NULL, NULL, NULL, NULL, NULL);\n"
         "    return rc + (kernel == STOCS_FORM_LEAN) + (kernel == STOCS_FORM_FULL_LDS) + (kernel == STOCS_FORM_FULL_DEVICE_MEMORY) + (kernel == STOCS_FORM_NINE_LAUNCH)\n"
+        "         + (kernel == STOCS_FORM_INSTANCE_LDS) + (kernel == STOCS_FORM_INSTANCE_DEVICE_MEMORY) + stocs_last_instance_attempts(c, idx, 0, &n) + n\n"
         "         + stocs_debug_draw_point1(c, r, 2, idx);\n"
         "}\n")
     r = subprocess.run(["gcc", "-std=c99", "-Wall", "-Wextra", "-pedantic", "-Werror", "-fsyntax-only", "-I", os.path.join(ROOT, "include"), str(src)],
