@@ -137,6 +137,24 @@ int ensure_pinned(stocs_ctx* c, size_t bytes) {
     return STOCS_OK;
 }
 
+int pinned_var(stocs_ctx* c, size_t bytes, char** h) {
+    const size_t pin_need = (size_t)PIN_VAR + bytes;
+    if (c->pin_bytes < pin_need) {
+        STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));   // nothing may still be copying into the old block
+        const int rc = ensure_pinned(c, pin_need);
+        if (rc) return rc;
+    }
+    *h = (char*)c->h_pin + PIN_VAR;
+    return STOCS_OK;
+}
+
+int pinned_for(stocs_ctx* c, size_t in_bytes, size_t back_bytes, char** h_in, char** h_back) {
+    const int rc = pinned_var(c, al256(in_bytes) + back_bytes, h_in);
+    if (rc) return rc;
+    *h_back = *h_in + al256(in_bytes);
+    return STOCS_OK;
+}
+
 static inline uint32_t part1by2(uint32_t x) {
     x &= 0x3ff;
     x = (x | (x << 16)) & 0x30000ff;

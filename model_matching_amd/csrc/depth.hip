@@ -14,28 +14,21 @@
 //   pass 2 (self-occlusion only)  the 64 x 64 z-buffer in LDS: atomicMin on the bits of p_2, which is positive there, so the order of
 //                                 the bits is the order of the floats and the minimum does not depend on the execution order;
 //   pass 3                        classification: one gathered uint16 of the depth image (and of the class image) per point that is in
-//                                 the image and not hidden; every count is a __ballot + __popcll per wavefront, kept in wave-uniform
-//                                 registers, added to eight LDS words at the end; thread 0 stores the record.
+//                                 the image and not hidden, classified by classify_pixel (render_rules.h); every count is a __ballot +
+//                                 __popcll per wavefront, kept in wave-uniform registers, added to eight LDS words at the end; thread 0
+//                                 stores the record.
+// The frame's checks, arguments and image pointers are depth_frame.h's (this file owns the frame), pose_finite and classify_pixel are
+// render_rules.h's, the wavefront reductions wave_bits.h's, the pinned staging pinned_var (stocs_ctx.h).
 // Known limit: one workgroup per hypothesis -- with far fewer hypotheses than compute units the launch is latency-bound.
 #include <math.h>
 #include <string.h>
 
-#include "depth_frame.h"
+#include "render_rules.h"
+#include "wave_bits.h"
 
 namespace stocs {
 
 enum { DC_FACING = 0, DC_IN_IMAGE, DC_SELF_OCC, DC_NO_DEPTH, DC_AGREE, DC_IN_FRONT, DC_BEHIND, DC_ON_MASK, DC_COUNTS };
-
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(v, o, 64); v = w < v ? w : v; }
-    return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
-    return v;
-}
 
 __global__ __launch_bounds__(256) void depth_check_kernel(const float* __restrict__ poses, const float4* __restrict__ mpos, const float4* __restrict__ mnrm, int nM,
                                                           const uint16_t* __restrict__ depth, const uint16_t* __restrict__ prob, DepthArgs a,
@@ -46,14 +39,10 @@ __global__ __launch_bounds__(256) void depth_check_kernel(const float* __restric
     const int tid = (int)threadIdx.x;
     const int h = (int)blockIdx.x;
     float P[16];
-    bool finite = true;
 #pragma unroll
     for (int i = 0; i < 16; ++i) P[i] = poses[(size_t)h * 16 + i];   // the same address in every lane: uniform loads
-#pragma unroll
-    for (int i = 0; i < 15; ++i)
-        if ((i & 3) != 3) finite = finite && (fabsf(P[i]) <= 3.4028234663852886e38f);   // the twelve entries the contract reads; false for NaN
     if (tid < DC_COUNTS) cnt[tid] = 0;
-    if (!finite) {   // a non-finite pose: a zero record (wave-uniform exit: P is the same in every lane)
+    if (!pose_finite(P)) {   // a non-finite pose: a zero record (wave-uniform exit: P is the same in every lane)
         if (tid == 0) {
             stocs_depth_result r;
             r.facing = r.in_image = r.self_occluded = r.no_depth = r.agree = r.in_front = r.behind = r.on_mask = 0;
@@ -108,7 +97,8 @@ __global__ __launch_bounds__(256) void depth_check_kernel(const float* __restric
     int n_face = 0, n_in = 0, n_self = 0, n_nod = 0, n_agree = 0, n_front = 0, n_behind = 0, n_mask = 0;
     for (int base = 0; base < nM; base += 256) {
         const int i = base + tid;
-        bool facing = false, in_image = false, self_occ = false, no_depth = false, agree = false, in_front = false, behind = false, on_mask = false;
+        bool facing = false, in_image = false, self_occ = false;
+        int cls = 0;   // steps 5-6: 1 no_depth, 2 agree, 3 in_front, 4 behind, + 16 on_mask
         if (i < nM) {
             const Projected p = project_point(P, mpos[i], mnrm[i], a);
             facing = p.facing; in_image = p.in_image;
@@ -117,28 +107,12 @@ __global__ __launch_bounds__(256) void depth_check_kernel(const float* __restric
                     const float zmin = __uint_as_float(zbuf[((p.row - r0) / s) * 64 + (p.col - c0) / s]);
                     self_occ = p.z > zmin + a.margin;
                 }
-                if (!self_occ) {
-                    const size_t px = (size_t)p.row * (size_t)a.W + (size_t)p.col;
-                    const uint16_t raw = depth[px];
-                    if (raw == 0) {
-                        no_depth = true;
-                    } else {
-                        const float zo = (float)raw * a.depth_scale;   // as backproject_kernel forms it (ingest.hip:70)
-                        const float d = p.z - zo;
-                        agree = fabsf(d) <= a.tolerance;
-                        in_front = d < -a.tolerance;
-                        behind = d > a.tolerance;
-                        if (agree && prob) {
-                            const float cp = (float)((double)prob[px] * (1.0 / 10000));   // as scene_select_kernel forms it (ingest.hip:343)
-                            on_mask = !(cp < a.class_threshold);
-                        }
-                    }
-                }
+                if (!self_occ) cls = classify_pixel(p.z, (size_t)p.row * (size_t)a.W + (size_t)p.col, depth, prob, a);
             }
         }
         n_face += __popcll(__ballot(facing)); n_in += __popcll(__ballot(in_image)); n_self += __popcll(__ballot(self_occ));
-        n_nod += __popcll(__ballot(no_depth)); n_agree += __popcll(__ballot(agree)); n_front += __popcll(__ballot(in_front));
-        n_behind += __popcll(__ballot(behind)); n_mask += __popcll(__ballot(on_mask));
+        n_nod += __popcll(__ballot((cls & 15) == 1)); n_agree += __popcll(__ballot((cls & 15) == 2)); n_front += __popcll(__ballot((cls & 15) == 3));
+        n_behind += __popcll(__ballot((cls & 15) == 4)); n_mask += __popcll(__ballot((cls & 16) != 0));
     }
     if ((tid & 63) == 0) {
         atomicAdd(&cnt[DC_FACING], n_face); atomicAdd(&cnt[DC_IN_IMAGE], n_in); atomicAdd(&cnt[DC_SELF_OCC], n_self); atomicAdd(&cnt[DC_NO_DEPTH], n_nod);
@@ -203,13 +177,8 @@ extern "C" int stocs_ctx_set_frame(stocs_ctx* c, const stocs_camera* cam, const 
     const size_t img = al256(npix * 2);
     S->has_frame = false;
     { const int rc = S->frame.grow(c->stream, 2 * img); if (rc) return rc; }
-    const size_t pin_need = (size_t)PIN_VAR + 2 * img;
-    if (c->pin_bytes < pin_need) {
-        STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));   // nothing may still be copying into the old block
-        const int rc = ensure_pinned(c, pin_need);
-        if (rc) return rc;
-    }
-    char* hp = (char*)c->h_pin + PIN_VAR;
+    char* hp;
+    { const int rc = pinned_var(c, 2 * img, &hp); if (rc) return rc; }
     memcpy(hp, depth, npix * 2);
     if (class_prob) memcpy(hp + img, class_prob, npix * 2);
     STOCS_HIP_CHECK(hipMemcpyAsync(S->frame.p, hp, class_prob ? 2 * img : img, hipMemcpyHostToDevice, c->stream));
@@ -224,37 +193,24 @@ extern "C" int stocs_depth_check_poses(stocs_ctx* c, const float* poses, int n, 
     if (n == 0) return STOCS_OK;
     if (!poses || !prm || !out) { set_error("stocs_depth_check_poses: NULL poses, parameters or results"); return STOCS_ERR_INVALID; }
     { const int rc = check_params(prm); if (rc) return rc; }
-    DepthState* S = (DepthState*)c->depth;
-    if (!S || !S->has_frame) { set_error("stocs_depth_check_poses: no frame (stocs_ctx_set_frame)"); return STOCS_ERR_STATE; }
-    if (S->cam.width < 1 || S->cam.height < 1) { set_error("stocs_depth_check_poses: image of %d x %d pixels", S->cam.width, S->cam.height); return STOCS_ERR_INVALID; }
-    if ((size_t)S->cam.width * (size_t)S->cam.height != S->npix) {
-        set_error("stocs_depth_check_poses: the camera's %d x %d pixels are not the %zu uploaded", S->cam.width, S->cam.height, S->npix);
-        return STOCS_ERR_STATE;
-    }
+    DepthState* S = NULL;
+    { const int rc = check_frame("stocs_depth_check_poses", c, &S); if (rc) return rc; }
     DeviceGuard dev_guard(c->device);
     Carve cv;
     const size_t o_pose = cv.take((size_t)n * 64), o_res = cv.take((size_t)n * sizeof(stocs_depth_result));
     { const int rc = S->work.grow(c->stream, cv.total); if (rc) return rc; }
-    const size_t pin_need = (size_t)PIN_VAR + cv.total;
-    if (c->pin_bytes < pin_need) {
-        STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));   // nothing may still be copying into the old block
-        const int rc = ensure_pinned(c, pin_need);
-        if (rc) return rc;
-    }
+    char* hp;   // the pinned mirror of the two regions, at the same offsets
+    { const int rc = pinned_var(c, cv.total, &hp); if (rc) return rc; }
     float* d_pose = Carve::at<float>(S->work.p, o_pose);
     stocs_depth_result* d_res = Carve::at<stocs_depth_result>(S->work.p, o_res);
-    float* h_pose = Carve::at<float>((char*)c->h_pin + PIN_VAR, o_pose);
-    stocs_depth_result* h_res = Carve::at<stocs_depth_result>((char*)c->h_pin + PIN_VAR, o_res);
+    float* h_pose = Carve::at<float>(hp, o_pose);
+    stocs_depth_result* h_res = Carve::at<stocs_depth_result>(hp, o_res);
     memcpy(h_pose, poses, (size_t)n * 64);
     STOCS_HIP_CHECK(hipMemcpyAsync(d_pose, h_pose, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));
-    DepthArgs a;
-    a.fx = S->cam.fx; a.cx = S->cam.cx; a.fy = S->cam.fy; a.cy = S->cam.cy; a.depth_scale = S->cam.depth_scale; a.W = S->cam.width; a.H = S->cam.height;
-    a.tolerance = prm->tolerance; a.class_threshold = prm->class_threshold; a.margin = prm->occlusion_margin;
-    a.self_occlusion = prm->self_occlusion; a.cell_px = prm->cell_px;
-    const uint16_t* d_depth = (const uint16_t*)S->frame.p;
-    const uint16_t* d_prob = S->has_prob ? (const uint16_t*)(S->frame.p + al256(S->npix * 2)) : (const uint16_t*)NULL;
+    DepthArgs a = frame_args(S, prm->tolerance, prm->class_threshold);
+    a.margin = prm->occlusion_margin; a.self_occlusion = prm->self_occlusion; a.cell_px = prm->cell_px;
     hipLaunchKernelGGL(depth_check_kernel, dim3((unsigned)n), dim3(256), 0, c->stream, (const float*)d_pose, (const float4*)c->d_mpos_raw, (const float4*)c->d_mnrm,
-                       c->nM, d_depth, d_prob, a, d_res);
+                       c->nM, frame_depth(S), frame_prob(S), a, d_res);
     STOCS_HIP_CHECK(hipGetLastError());
     STOCS_HIP_CHECK(hipMemcpyAsync(h_res, d_res, (size_t)n * sizeof(stocs_depth_result), hipMemcpyDeviceToHost, c->stream));
     STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));

@@ -1,8 +1,8 @@
 // depth_frame.h -- what the entry points that work on the frame of stocs_ctx_set_frame share: the frame's state on the context
 // (depth.hip owns it: stocs_ctx_set_frame fills it, stocs_internal_free_depth frees it), the kernel arguments that describe the camera,
-// and steps 1-3 of the depth-check contract (include/stocs_hip.h).  Included by depth.hip (stocs_depth_check_poses) and, through
-// render_rules.h, by render.hip (stocs_render_poses and its kin) and scene.hip (stocs_scene_footprints); all project a model point with the
-// one project_point below.
+// steps 1-3 of the depth-check contract (include/stocs_hip.h), and on the host the checks of the frame, the fill of the arguments and the
+// pointers to its two images.  Included through render_rules.h by depth.hip (stocs_depth_check_poses), render.hip (stocs_render_poses and
+// its kin) and scene.hip (stocs_scene_footprints); all project a model point with the one project_point below.
 #ifndef STOCS_DEPTH_FRAME_H
 #define STOCS_DEPTH_FRAME_H
 
@@ -44,6 +44,29 @@ __device__ __forceinline__ Projected project_point(const float* P, const float4 
     r.row = r.in_image ? (int)v : 0;
     return r;
 }
+
+// ---- host side: the frame as every entry point on it requires it, and the kernel arguments from it ----
+static int check_frame(const char* who, stocs_ctx* c, DepthState** frame) {
+    DepthState* S = (DepthState*)c->depth;
+    if (!S || !S->has_frame) { set_error("%s: no frame (stocs_ctx_set_frame)", who); return STOCS_ERR_STATE; }
+    if (S->cam.width < 1 || S->cam.height < 1) { set_error("%s: image of %d x %d pixels", who, S->cam.width, S->cam.height); return STOCS_ERR_INVALID; }
+    if ((size_t)S->cam.width * (size_t)S->cam.height != S->npix) {
+        set_error("%s: the camera's %d x %d pixels are not the %zu uploaded", who, S->cam.width, S->cam.height, S->npix);
+        return STOCS_ERR_STATE;
+    }
+    *frame = S;
+    return STOCS_OK;
+}
+
+// the camera and the two thresholds; no self-occlusion test (margin 0, one pixel per cell) unless the caller sets those three fields
+static DepthArgs frame_args(const DepthState* S, float tolerance, float class_threshold) {
+    DepthArgs a;
+    a.fx = S->cam.fx; a.cx = S->cam.cx; a.fy = S->cam.fy; a.cy = S->cam.cy; a.depth_scale = S->cam.depth_scale; a.W = S->cam.width; a.H = S->cam.height;
+    a.tolerance = tolerance; a.class_threshold = class_threshold; a.margin = 0.0f; a.self_occlusion = 0; a.cell_px = 1;
+    return a;
+}
+static const uint16_t* frame_depth(const DepthState* S) { return (const uint16_t*)S->frame.p; }
+static const uint16_t* frame_prob(const DepthState* S) { return S->has_prob ? (const uint16_t*)(S->frame.p + al256(S->npix * 2)) : (const uint16_t*)NULL; }
 
 }  // namespace stocs
 

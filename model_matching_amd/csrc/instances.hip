@@ -12,29 +12,26 @@
 //             (zero padded, so that the later kernels read rows as 16-byte words); own_h = its popcount; the sort key of step 3.
 //   order     one 64-bit radix sort (prims.h) of the complemented keys with the indices as values: ascending and stable, hence
 //             descending stocs_pack_best and, among the hypotheses that share the key 0, ascending index.
-//   select    instance_select_kernel, ONE workgroup of 16 wavefronts with `covered` in LDS: each round wavefront k tests the k-th
-//             pending hypothesis in order against the cover; the first that passes is selected, those before it are dropped for good
-//             (the cover only grows), those behind it stay pending and are tested again against the new cover.
+//   select    instance_select_kernel, ONE workgroup of 16 wavefronts with `covered` in LDS: the walk of cover_walk.h, which scene.hip
+//             shares, behind this file's gate (own_h >= min_points).
 //   finish    instance_finish_kernel, a wavefront per hypothesis: |E_h \ covered_final| for the unselected ones, and the records.
+// The order key, the exclusive count, the ordering sort and the read-back region (records | selected | count) are cover_walk.h's too; the
+// pinned staging is pinned_for (stocs_ctx.h).
 // Known limits: nS <= 2^18 (a 32 KB bitset), n <= 16 384; the walk is one workgroup, so its time grows with rounds x W.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include "prims.h"
-#include "stocs_ctx.h"
-#include "wave_bits.h"
+#include "cover_walk.h"
 
 namespace stocs {
 
-enum { INST_MAX_SCENE = 1 << 18, INST_MAX_N = 16384, INST_SELECT_WAVES = 16 };
+enum { INST_MAX_SCENE = 1 << 18, INST_MAX_N = 16384 };
 
 struct InstancesState {
     DevBlock rows;   // one chunk of detail rows: lcp | hit | counted
     DevBlock work;   // poses | valid | lcp | own | keys (2) | indices (2) | rank | excl | cover | records + selected + count | sort scratch | E
 };
-
-struct InstanceArgs { int32_t max_instances, min_points; float min_fraction; };
 
 // hypothesis h0 + blockIdx.x from row blockIdx.x of the chunk.  valid == NULL: every hypothesis is valid.  LDS: Wp words + 4.
 __global__ __launch_bounds__(256) void instance_mark_kernel(const int32_t* __restrict__ hit, const uint8_t* __restrict__ counted, const float* __restrict__ lcp_chunk,
@@ -68,63 +65,26 @@ __global__ __launch_bounds__(256) void instance_mark_kernel(const int32_t* __res
         const float l = ok ? lcp_chunk[blockIdx.x] : 0.0f;
         own[h] = *total;
         lcp_out[h] = l;
-        // step 3 of the contract: ~stocs_pack_best(l, h), so that the ascending stable sort walks the keys downwards
-        key[h] = ~(l > 0.0f ? (uint64_t)best_key(l, (uint32_t)h) : (uint64_t)0);
+        key[h] = cover_order_key(l, h);   // step 3 of the contract
         idx[h] = (uint32_t)h;
     }
 }
 
-// the walk (step 4).  One workgroup of 16 wavefronts; p (first position of the order not yet decided) and nsel are the same in every
-// thread.  LDS: Wp words of cover, then 3 x 16 words of the round's results.
-__global__ __launch_bounds__(64 * INST_SELECT_WAVES) void instance_select_kernel(const uint32_t* __restrict__ E, int Wp, const uint32_t* __restrict__ order,
-                                                                                 const int32_t* __restrict__ own, int n, InstanceArgs a, int32_t* __restrict__ rank,
-                                                                                 int32_t* __restrict__ excl, int32_t* __restrict__ selected,
-                                                                                 int32_t* __restrict__ n_selected, uint32_t* __restrict__ cover_out) {
+// the gate of this walk: excl <= own, so below min_points the row need not be read.  A selection has no side effect
+struct InstanceGate {
+    const int32_t* __restrict__ own; int min_points;
+    __device__ __forceinline__ bool open(int h) const { return own[h] >= min_points; }
+    __device__ __forceinline__ void took(int, int) const {}
+};
+
+// the walk (step 4): cover_walk (cover_walk.h) by one workgroup.  LDS: Wp words of cover, then 3 x 16 words of the round's results.
+__global__ __launch_bounds__(64 * COVER_WAVES) void instance_select_kernel(const uint32_t* __restrict__ E, int Wp, const uint32_t* __restrict__ order,
+                                                                           const int32_t* __restrict__ own, int n, CoverArgs a, int32_t* __restrict__ rank,
+                                                                           int32_t* __restrict__ excl, int32_t* __restrict__ selected, int32_t* __restrict__ n_selected,
+                                                                           uint32_t* __restrict__ cover_out) {
     extern __shared__ __attribute__((aligned(16))) uint32_t sel_lds[];
-    uint4* cov = (uint4*)sel_lds;
-    int* r_pass = (int*)(sel_lds + Wp);
-    int* r_excl = r_pass + INST_SELECT_WAVES;
-    int* r_h = r_excl + INST_SELECT_WAVES;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int threads = 64 * INST_SELECT_WAVES;
-    const int W4 = Wp >> 2;
-    for (int i = tid; i < W4; i += threads) cov[i] = make_uint4(0u, 0u, 0u, 0u);
-    for (int i = tid; i < n; i += threads) rank[i] = -1;
-    __syncthreads();
-    int p = 0, nsel = 0;
-    while (p < n && nsel < a.max_instances) {
-        const int pos = p + wave;
-        int h = -1, ex = 0, pass = 0;
-        if (pos < n) {   // wave-uniform
-            h = (int)order[pos];
-            const int o = own[h];
-            if (o >= a.min_points) {   // excl <= own: below min_points the row need not be read
-                const uint4* row = (const uint4*)(E + (size_t)h * (size_t)Wp);
-                for (int i = lane; i < W4; i += 64) ex += popc_andnot4(row[i], cov[i]);
-                ex = wave_sum_i(ex);
-                pass = (ex >= a.min_points && (float)ex >= a.min_fraction * (float)o) ? 1 : 0;
-            }
-        }
-        if (lane == 0) { r_pass[wave] = pass; r_excl[wave] = ex; r_h[wave] = h; }
-        __syncthreads();
-        int k = -1;
-#pragma unroll
-        for (int j = INST_SELECT_WAVES - 1; j >= 0; --j) k = r_pass[j] ? j : k;   // the first that passes, in order
-        if (k < 0) {
-            p += INST_SELECT_WAVES;   // all sixteen fail against a subset of their final cover: dropped
-        } else {
-            const int hs = r_h[k];
-            if (tid == 0) { rank[hs] = nsel; excl[hs] = r_excl[k]; selected[nsel] = hs; }
-            const uint4* row = (const uint4*)(E + (size_t)hs * (size_t)Wp);
-            for (int i = tid; i < W4; i += threads) { const uint4 e = row[i]; uint4 c = cov[i]; c.x |= e.x; c.y |= e.y; c.z |= e.z; c.w |= e.w; cov[i] = c; }
-            ++nsel;
-            p += k + 1;   // those in front of it are dropped, those behind it are tested again
-        }
-        __syncthreads();
-    }
-    uint4* co = (uint4*)cover_out;
-    for (int i = tid; i < W4; i += threads) co[i] = cov[i];
-    if (tid == 0) *n_selected = nsel;
+    const InstanceGate gate = {own, a.min_count};
+    cover_walk(E, Wp, order, own, n, a, gate, (uint4*)sel_lds, (int*)(sel_lds + Wp), rank, excl, selected, n_selected, cover_out);
 }
 
 // step 5: a wavefront per hypothesis, four to a workgroup
@@ -135,16 +95,7 @@ __global__ __launch_bounds__(256) void instance_finish_kernel(const uint32_t* __
     const int h = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
     if (h >= n) return;   // wave-uniform
     const int r = rank[h];
-    int ex = 0;
-    if (r < 0) {
-        const int W4 = Wp >> 2;
-        const uint4* row = (const uint4*)(E + (size_t)h * (size_t)Wp);
-        const uint4* cov = (const uint4*)cover;
-        for (int i = lane; i < W4; i += 64) ex += popc_andnot4(row[i], cov[i]);
-        ex = wave_sum_i(ex);
-    } else {
-        ex = excl[h];
-    }
+    const int ex = cover_final_exclusive(E, Wp, cover, excl, h, r, lane);
     if (lane == 0) {
         stocs_instance_result o;
         o.rank = r; o.own = own[h]; o.exclusive = ex; o.lcp = lcp[h];
@@ -178,38 +129,34 @@ static int check_scene_size(const char* who, int nS) {
     return STOCS_OK;
 }
 
-// the device arrays of one call, carved from InstancesState::work; the read-back (records | selected | count) is one region
+// the device arrays of one call, carved from InstancesState::work; the read-back is one region, laid out by `bk`
 struct InstancesWork {
     float* pose; uint8_t* valid; float* lcp; int32_t* own; uint64_t* key; uint64_t* key_s; uint32_t* idx; uint32_t* idx_s; int32_t* rank; int32_t* excl;
     uint32_t* cover; char* back; void* sort_tmp; uint32_t* E;
-    size_t o_pose, o_valid, o_back, back_bytes, sort_bytes;
-    int Wp;
-    stocs_instance_result* rec() const { return (stocs_instance_result*)back; }
-    int32_t* selected(int n) const { return (int32_t*)(back + al256((size_t)n * sizeof(stocs_instance_result))); }
-    static size_t back_size(int n, int max_inst) { return al256((size_t)n * sizeof(stocs_instance_result)) + al256((size_t)max_inst * 4) + 256; }
+    size_t o_pose, o_valid;
+    CoverBack bk;
+    int Wp, max_sel;
 };
 
-static int carve_work(stocs_ctx* c, InstancesState* S, int n, int nS, int n_sel_cap, InstancesWork* w) {
+static int carve_work(stocs_ctx* c, InstancesState* S, int n, int nS, const stocs_instance_params* prm, InstancesWork* w) {
     const int W = (nS + 31) / 32;
     w->Wp = (W + 3) & ~3;
-    w->sort_bytes = 0;
-    STOCS_HIP_CHECK(sort_pairs(NULL, w->sort_bytes, (const uint64_t*)NULL, (uint64_t*)NULL, (const uint32_t*)NULL, (uint32_t*)NULL, (size_t)n, 0, 64, c->stream));
-    w->back_bytes = InstancesWork::back_size(n, n_sel_cap);
+    w->max_sel = prm->max_instances < n ? prm->max_instances : n;   // no more can be selected than there are
+    { const int rc = w->bk.plan(c, n, sizeof(stocs_instance_result), w->max_sel); if (rc) return rc; }
     Carve cv;
     w->o_pose = cv.take((size_t)n * 64);
     w->o_valid = cv.take((size_t)n);
     const size_t o_lcp = cv.take((size_t)n * 4), o_own = cv.take((size_t)n * 4), o_key = cv.take((size_t)n * 8), o_key_s = cv.take((size_t)n * 8);
     const size_t o_idx = cv.take((size_t)n * 4), o_idx_s = cv.take((size_t)n * 4), o_rank = cv.take((size_t)n * 4), o_excl = cv.take((size_t)n * 4);
     const size_t o_cover = cv.take((size_t)w->Wp * 4);
-    w->o_back = cv.take(w->back_bytes);
-    const size_t o_sort = cv.take(w->sort_bytes);
+    const size_t o_back = cv.take(w->bk.total), o_sort = cv.take(w->bk.sort_bytes);
     const size_t o_E = cv.take((size_t)n * (size_t)w->Wp * 4);
     { const int rc = S->work.grow(c->stream, cv.total); if (rc) return rc; }
     char* b = S->work.p;
     w->pose = Carve::at<float>(b, w->o_pose); w->valid = Carve::at<uint8_t>(b, w->o_valid); w->lcp = Carve::at<float>(b, o_lcp); w->own = Carve::at<int32_t>(b, o_own);
     w->key = Carve::at<uint64_t>(b, o_key); w->key_s = Carve::at<uint64_t>(b, o_key_s); w->idx = Carve::at<uint32_t>(b, o_idx); w->idx_s = Carve::at<uint32_t>(b, o_idx_s);
     w->rank = Carve::at<int32_t>(b, o_rank); w->excl = Carve::at<int32_t>(b, o_excl); w->cover = Carve::at<uint32_t>(b, o_cover);
-    w->back = b + w->o_back; w->sort_tmp = b + o_sort; w->E = Carve::at<uint32_t>(b, o_E);
+    w->back = b + o_back; w->sort_tmp = b + o_sort; w->E = Carve::at<uint32_t>(b, o_E);
     return STOCS_OK;
 }
 
@@ -221,44 +168,19 @@ static int enqueue_mark(stocs_ctx* c, const InstancesWork& w, const int32_t* d_h
     return STOCS_OK;
 }
 
-// order, walk, records, read-back into the pinned mirror of `back`, the call's one synchronisation, results to the caller
+// order, walk, records, then CoverBack::read_back: the pinned mirror of `back`, the call's one synchronisation, results to the caller
 static int order_select_finish(stocs_ctx* c, const InstancesWork& w, int n, const stocs_instance_params* prm, char* h_back, stocs_instance_result* out, int32_t* selected,
                                int* n_selected) {
-    size_t tb = w.sort_bytes;
-    STOCS_HIP_CHECK(sort_pairs(w.sort_tmp, tb, (const uint64_t*)w.key, w.key_s, (const uint32_t*)w.idx, w.idx_s, (size_t)n, 0, 64, c->stream));
-    InstanceArgs a;
-    a.max_instances = prm->max_instances < n ? prm->max_instances : n;   // no more can be selected than there are
-    a.min_points = prm->min_points; a.min_fraction = prm->min_exclusive_fraction;
-    int32_t* d_sel = w.selected(n);
-    int32_t* d_nsel = (int32_t*)((char*)d_sel + al256((size_t)a.max_instances * 4));
-    hipLaunchKernelGGL(instance_select_kernel, dim3(1), dim3(64 * INST_SELECT_WAVES), (size_t)(w.Wp + 3 * INST_SELECT_WAVES) * 4, c->stream, (const uint32_t*)w.E, w.Wp,
-                       (const uint32_t*)w.idx_s, (const int32_t*)w.own, n, a, w.rank, w.excl, d_sel, d_nsel, w.cover);
+    { const int rc = w.bk.order(c, w.sort_tmp, w.key, w.key_s, w.idx, w.idx_s, n); if (rc) return rc; }
+    const CoverArgs a = {w.max_sel, prm->min_points, prm->min_exclusive_fraction};
+    hipLaunchKernelGGL(instance_select_kernel, dim3(1), dim3(64 * COVER_WAVES), (size_t)(w.Wp + 3 * COVER_WAVES) * 4, c->stream, (const uint32_t*)w.E, w.Wp,
+                       (const uint32_t*)w.idx_s, (const int32_t*)w.own, n, a, w.rank, w.excl, Carve::at<int32_t>(w.back, w.bk.o_sel), Carve::at<int32_t>(w.back, w.bk.o_cnt),
+                       w.cover);
     STOCS_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(instance_finish_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, (const uint32_t*)w.E, w.Wp, (const uint32_t*)w.cover,
-                       (const int32_t*)w.own, (const float*)w.lcp, (const int32_t*)w.rank, (const int32_t*)w.excl, n, w.rec());
+                       (const int32_t*)w.own, (const float*)w.lcp, (const int32_t*)w.rank, (const int32_t*)w.excl, n, Carve::at<stocs_instance_result>(w.back, w.bk.o_rec));
     STOCS_HIP_CHECK(hipGetLastError());
-    const size_t back = InstancesWork::back_size(n, a.max_instances);
-    STOCS_HIP_CHECK(hipMemcpyAsync(h_back, w.back, back, hipMemcpyDeviceToHost, c->stream));
-    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    const char* h_sel = h_back + al256((size_t)n * sizeof(stocs_instance_result));
-    const int ns = *(const int32_t*)(h_sel + al256((size_t)a.max_instances * 4));
-    memcpy(out, h_back, (size_t)n * sizeof(stocs_instance_result));
-    memcpy(selected, h_sel, (size_t)ns * 4);
-    *n_selected = ns;
-    return STOCS_OK;
-}
-
-// the pinned block holds what the call sends up (in_bytes at PIN_VAR) and, behind it, the mirror of the read-back
-static int pinned_for(stocs_ctx* c, size_t in_bytes, size_t back_bytes, char** h_in, char** h_back) {
-    const size_t pin_need = (size_t)PIN_VAR + al256(in_bytes) + back_bytes;
-    if (c->pin_bytes < pin_need) {
-        STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));   // nothing may still be copying into the old block
-        const int rc = ensure_pinned(c, pin_need);
-        if (rc) return rc;
-    }
-    *h_in = (char*)c->h_pin + PIN_VAR;
-    *h_back = *h_in + al256(in_bytes);
-    return STOCS_OK;
+    return w.bk.read_back(c, w.back, h_back, out, selected, n_selected);
 }
 
 }  // namespace stocs
@@ -298,12 +220,11 @@ extern "C" int stocs_select_instances(stocs_ctx* c, const float* T16, int n, con
     Carve rv;
     const size_t o_l = rv.take(chunk * 4), o_h = rv.take(chunk * M * 4), o_c = rv.take(chunk * M);
     { const int rc = S->rows.grow(c->stream, rv.total); if (rc) return rc; }
-    const int sel_cap = prm->max_instances < n ? prm->max_instances : n;
     InstancesWork w;
-    { const int rc = carve_work(c, S, n, c->nS, sel_cap, &w); if (rc) return rc; }
+    { const int rc = carve_work(c, S, n, c->nS, prm, &w); if (rc) return rc; }
     char* h_in; char* h_back;
     const size_t in_bytes = al256((size_t)n * 64) + al256((size_t)n);
-    { const int rc = pinned_for(c, in_bytes, w.back_bytes, &h_in, &h_back); if (rc) return rc; }
+    { const int rc = pinned_for(c, in_bytes, w.bk.total, &h_in, &h_back); if (rc) return rc; }
     // step 2: a hypothesis with a non-finite entry, or all zeros, is not scored as a transform -- the launch gets the identity in its
     // place (a pose like any other to the kernel) and the marking kernel zeroes its record
     float* h_pose = (float*)h_in;
@@ -351,11 +272,10 @@ extern "C" int stocs_select_instances_rows(stocs_ctx* c, const int32_t* hit, con
     Carve rv;
     const size_t o_l = rv.take((size_t)n * 4), o_h = rv.take(cells * 4), o_c = rv.take(cells);
     { const int rc = S->rows.grow(c->stream, rv.total); if (rc) return rc; }
-    const int sel_cap = prm->max_instances < n ? prm->max_instances : n;
     InstancesWork w;
-    { const int rc = carve_work(c, S, n, nS, sel_cap, &w); if (rc) return rc; }
+    { const int rc = carve_work(c, S, n, nS, prm, &w); if (rc) return rc; }
     char* h_in; char* h_back;
-    { const int rc = pinned_for(c, 0, w.back_bytes, &h_in, &h_back); if (rc) return rc; }
+    { const int rc = pinned_for(c, 0, w.bk.total, &h_in, &h_back); if (rc) return rc; }
     float* dL = Carve::at<float>(S->rows.p, o_l);
     int32_t* dH = Carve::at<int32_t>(S->rows.p, o_h);
     uint8_t* dC = Carve::at<uint8_t>(S->rows.p, o_c);

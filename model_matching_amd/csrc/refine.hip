@@ -533,14 +533,8 @@ extern "C" int stocs_refine_poses(stocs_ctx* c, const float* T16_in, int n, cons
     // inputs and outputs go through the context's pinned block (grown only when this call needs more than it has)
     const size_t out_bytes = w.out_bytes;
     const size_t in_bytes = al256((size_t)n * 64) + al256((size_t)(src_idx ? nsrc : 0) * 4);
-    const size_t pin_need = (size_t)PIN_VAR + in_bytes + al256(out_bytes);
-    if (c->pin_bytes < pin_need) {
-        STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));   // nothing may still be copying into the old block
-        const int rc = ensure_pinned(c, pin_need);
-        if (rc) return rc;
-    }
-    char* hin = (char*)c->h_pin + PIN_VAR;
-    char* hout = hin + in_bytes;
+    char* hin; char* hout;
+    { const int rc = pinned_for(c, in_bytes, al256(out_bytes), &hin, &hout); if (rc) return rc; }   // in_bytes is a multiple of 256: hout = hin + in_bytes
     memcpy(hin, T16_in, (size_t)n * 64);
     if (src_idx && nsrc) memcpy(hin + al256((size_t)n * 64), src_idx, (size_t)nsrc * 4);
     STOCS_HIP_CHECK(hipMemcpyAsync(w.d_Tin, hin, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));

@@ -5,11 +5,13 @@
 // for bit: keys are packed integers under a minimum, counts are integer sums.
 //
 //   render_splat_kernel    one workgroup of 256 threads per (hypothesis, chunk of RENDER_CHUNK model points): every point goes through
-//                          project_point (depth_frame.h, the depth check's steps 1-3); a point in the image takes its splat radius s and
-//                          issues one 64-bit atomicMin on the key buffer per pixel of its (2s+1)^2 square that lies inside the image.
+//                          project_point (depth_frame.h, the depth check's steps 1-3); a point in the image walks its splat square
+//                          (splat_square, render_rules.h: (2s+1)^2 pixels clamped to the image) with one 64-bit atomicMin on the key
+//                          buffer per pixel.
 //   render_resolve_kernel  one workgroup per hypothesis: its footprint as a bitset of ceil(W*H/32) words in dynamic LDS (the model is
-//                          projected again, bits set with atomicOr), then the pixels of the rows it touched are walked one thread per
-//                          pixel: a set bit costs one key load and the classification of the depth check's steps 5-6 with the key's z.
+//                          projected again, the same splat_square setting bits with atomicOr), then the pixels of the rows it touched
+//                          are walked one thread per pixel: a set bit costs one key load and the classification of the depth check's
+//                          steps 5-6 with the key's z.
 //                          Every count is a __ballot + __popcll per wavefront in wave-uniform registers; thread 0 stores the record.
 //   render_labels_kernel   one thread per pixel: label and state of the key.
 // The clear is a hipMemsetAsync with 0xFF.  Known limits: a point's splat is walked by the one lane that projected it (up to 33 x 33
@@ -17,8 +19,8 @@
 #include <math.h>
 #include <string.h>
 
-#include "depth_frame.h"
 #include "render_rules.h"
+#include "wave_bits.h"
 
 namespace stocs {
 
@@ -42,24 +44,9 @@ __global__ __launch_bounds__(256) void render_splat_kernel(const float* __restri
     for (int i = first + (int)threadIdx.x; i < last; i += 256) {
         const Projected p = project_point(P, mpos[i], mnrm[i], a);
         if (!p.in_image) continue;
-        const int s = splat_radius(p.z, a, ra);
         const unsigned long long key = ((unsigned long long)__float_as_uint(p.z) << 32) | id;
-        const int r0 = p.row - s > 0 ? p.row - s : 0, r1 = p.row + s < a.H - 1 ? p.row + s : a.H - 1;
-        const int c0 = p.col - s > 0 ? p.col - s : 0, c1 = p.col + s < a.W - 1 ? p.col + s : a.W - 1;
-        for (int r = r0; r <= r1; ++r)
-            for (int c = c0; c <= c1; ++c) atomicMin(&zkey[(size_t)r * (size_t)a.W + (size_t)c], key);
+        splat_square(p, a, ra, [&](int r, int c) { atomicMin(&zkey[(size_t)r * (size_t)a.W + (size_t)c], key); });
     }
-}
-
-__device__ __forceinline__ int wave_min_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(v, o, 64); v = w < v ? w : v; }
-    return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const int w = __shfl_xor(v, o, 64); v = w > v ? w : v; }
-    return v;
 }
 
 // dynamic LDS: ceil(W*H/32) words, the footprint bitset (bit px & 31 of word px >> 5, px = row * W + col)
@@ -93,15 +80,11 @@ __global__ __launch_bounds__(256) void render_resolve_kernel(const float* __rest
     for (int i = tid; i < nM; i += 256) {
         const Projected p = project_point(P, mpos[i], mnrm[i], a);
         if (!p.in_image) continue;
-        const int s = splat_radius(p.z, a, ra);
-        const int r0 = p.row - s > 0 ? p.row - s : 0, r1 = p.row + s < a.H - 1 ? p.row + s : a.H - 1;
-        const int c0 = p.col - s > 0 ? p.col - s : 0, c1 = p.col + s < a.W - 1 ? p.col + s : a.W - 1;
-        mnr = r0 < mnr ? r0 : mnr; mxr = r1 > mxr ? r1 : mxr;
-        for (int r = r0; r <= r1; ++r)
-            for (int c = c0; c <= c1; ++c) {
-                const int px = r * a.W + c;
-                atomicOr(&foot[px >> 5], 1u << (px & 31));
-            }
+        const int2 rr = splat_square(p, a, ra, [&](int r, int c) {
+            const int px = r * a.W + c;
+            atomicOr(&foot[px >> 5], 1u << (px & 31));
+        });
+        mnr = rr.x < mnr ? rr.x : mnr; mxr = rr.y > mxr ? rr.y : mxr;
     }
     mnr = wave_min_i(mnr); mxr = wave_max_i(mxr);
     if ((tid & 63) == 0) { atomicMin(&rows[0], mnr); atomicMax(&rows[1], mxr); }
@@ -187,13 +170,8 @@ static int render_layout(stocs_ctx* c, size_t own_key, int n, size_t label_px, R
     L->o_lab = cv.take(label_px * 4); L->o_state = cv.take(label_px);
     L->total = cv.total;
     { const int rc = R->work.grow(c->stream, L->key_bytes + cv.total); if (rc) return rc; }
-    const size_t pin_need = (size_t)PIN_VAR + cv.total;
-    if (c->pin_bytes < pin_need) {
-        STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));   // nothing may still be copying into the old block
-        const int rc = ensure_pinned(c, pin_need);
-        if (rc) return rc;
-    }
-    L->d = R->work.p + L->key_bytes; L->h = (char*)c->h_pin + PIN_VAR;
+    { const int rc = pinned_var(c, cv.total, &L->h); if (rc) return rc; }
+    L->d = R->work.p + L->key_bytes;
     return STOCS_OK;
 }
 

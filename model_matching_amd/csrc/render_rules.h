@@ -1,6 +1,8 @@
-// render_rules.h -- the rules of the render contract (include/stocs_hip.h) that more than one file applies: which poses touch nothing, the
-// splat radius of an in_image point, and steps 5-6 of the depth-check contract for a surface at depth z seen at a pixel.  Included by
-// render.hip (stocs_render_poses and its kin) and scene.hip (stocs_scene_footprints).
+// render_rules.h -- the rules of the render and depth-check contracts (include/stocs_hip.h) that more than one file applies: which poses
+// touch nothing, the splat radius of an in_image point and the walk over its square, and steps 5-6 of the depth-check contract for a
+// surface at depth z seen at a pixel; on the host, the check of stocs_render_params and the render arguments.  Included by depth.hip
+// (pose_finite, classify_pixel), render.hip (stocs_render_poses and its kin) and scene.hip (stocs_scene_footprints).  The frame itself,
+// its checks and its arguments are depth_frame.h's.
 #ifndef STOCS_RENDER_RULES_H
 #define STOCS_RENDER_RULES_H
 
@@ -31,6 +33,18 @@ __device__ __forceinline__ int splat_radius(float z, const DepthArgs& a, const R
     return (int)fminf(floorf((a.fx * r.point_radius) / z + 0.5f), (float)r.max_splat_px);
 }
 
+// the splat walk: f(row, col) for every pixel of the square of half-width splat_radius around the in_image point p that lies inside the
+// image; returns the first and the last row of the square
+template <class F>
+__device__ __forceinline__ int2 splat_square(const Projected& p, const DepthArgs& a, const RenderArgs& ra, F f) {
+    const int s = splat_radius(p.z, a, ra);
+    const int r0 = p.row - s > 0 ? p.row - s : 0, r1 = p.row + s < a.H - 1 ? p.row + s : a.H - 1;
+    const int c0 = p.col - s > 0 ? p.col - s : 0, c1 = p.col + s < a.W - 1 ? p.col + s : a.W - 1;
+    for (int r = r0; r <= r1; ++r)
+        for (int c = c0; c <= c1; ++c) f(r, c);
+    return make_int2(r0, r1);
+}
+
 // steps 5-6 of the depth-check contract for a surface at depth z seen at pixel px: 1 no_depth, 2 agree, 3 in_front, 4 behind, + 16 on_mask
 __device__ __forceinline__ int classify_pixel(float z, size_t px, const uint16_t* __restrict__ depth, const uint16_t* __restrict__ prob, const DepthArgs& a) {
     const uint16_t raw = depth[px];
@@ -49,8 +63,7 @@ __device__ __forceinline__ int classify_pixel(float z, size_t px, const uint16_t
     return 0;   // d is NaN: unreachable, z is a finite p_2 > 1e-6 and zo is finite
 }
 
-
-// ---- host side: the checks and kernel arguments every entry point on the frame shares ----
+// ---- host side: the parameter check and the kernel arguments of the render entry points ----
 static int check_params(const char* who, const stocs_render_params* p) {
     if (!(p->point_radius >= 0.0f) || !isfinite(p->point_radius)) { set_error("%s: point_radius %g must be >= 0 and finite", who, (double)p->point_radius); return STOCS_ERR_INVALID; }
     if (p->max_splat_px < 0 || p->max_splat_px > RENDER_MAX_SPLAT) { set_error("%s: max_splat_px %d outside 0..%d", who, p->max_splat_px, (int)RENDER_MAX_SPLAT); return STOCS_ERR_INVALID; }
@@ -59,33 +72,12 @@ static int check_params(const char* who, const stocs_render_params* p) {
     return STOCS_OK;
 }
 
-
-// the frame of stocs_ctx_set_frame, as stocs_depth_check_poses requires it
-static int check_frame(const char* who, stocs_ctx* c, DepthState** frame) {
-    DepthState* S = (DepthState*)c->depth;
-    if (!S || !S->has_frame) { set_error("%s: no frame (stocs_ctx_set_frame)", who); return STOCS_ERR_STATE; }
-    if (S->cam.width < 1 || S->cam.height < 1) { set_error("%s: image of %d x %d pixels", who, S->cam.width, S->cam.height); return STOCS_ERR_INVALID; }
-    if ((size_t)S->cam.width * (size_t)S->cam.height != S->npix) {
-        set_error("%s: the camera's %d x %d pixels are not the %zu uploaded", who, S->cam.width, S->cam.height, S->npix);
-        return STOCS_ERR_STATE;
-    }
-    *frame = S;
-    return STOCS_OK;
-}
-
-static DepthArgs frame_args(const DepthState* S, const stocs_render_params* prm) {
-    DepthArgs a;
-    a.fx = S->cam.fx; a.cx = S->cam.cx; a.fy = S->cam.fy; a.cy = S->cam.cy; a.depth_scale = S->cam.depth_scale; a.W = S->cam.width; a.H = S->cam.height;
-    a.tolerance = prm->tolerance; a.class_threshold = prm->class_threshold; a.margin = 0.0f; a.self_occlusion = 0; a.cell_px = 1;
-    return a;
-}
+static DepthArgs frame_args(const DepthState* S, const stocs_render_params* prm) { return frame_args(S, prm->tolerance, prm->class_threshold); }
 static RenderArgs render_args(const stocs_render_params* prm, int id_base) {
     RenderArgs r;
     r.point_radius = prm->point_radius; r.max_splat_px = prm->max_splat_px; r.id_base = id_base;
     return r;
 }
-static const uint16_t* frame_depth(const DepthState* S) { return (const uint16_t*)S->frame.p; }
-static const uint16_t* frame_prob(const DepthState* S) { return S->has_prob ? (const uint16_t*)(S->frame.p + al256(S->npix * 2)) : (const uint16_t*)NULL; }
 
 }  // namespace stocs
 

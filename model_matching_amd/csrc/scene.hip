@@ -7,33 +7,34 @@
 // stocs_scene_footprints, per chunk of hypotheses (256 MB of z-buffers; STOCS_SCENE_CHUNK=<hypotheses> forces a size):
 //   clear     hipMemsetAsync with 0xFF: every hypothesis of the chunk has its own z-buffer of npix uint32 float bits, empty = all ones.
 //   splat     scene_splat_kernel, render_splat_kernel's work split: one workgroup of 256 threads per (hypothesis, chunk of SCENE_CHUNK_POINTS
-//             model points), the pose in scalar registers, one 32-bit atomicMin per touched pixel (p_2 > 1e-6: the bits keep the order).
+//             model points), the pose in scalar registers, one 32-bit atomicMin per pixel of splat_square (render_rules.h; p_2 > 1e-6: the
+//             bits keep the order).
 //   classify  scene_classify_kernel: a wavefront takes runs of 64 consecutive pixels of one hypothesis, classifies the touched ones with
 //             z = its own minimum, turns the claim predicate into two row words with one __ballot (lane 0 stores them: no atomic on a row,
 //             no bitset in LDS, padding words included) and counts with __popcll in wave-uniform registers; one integer atomicAdd per
 //             counter and workgroup into the record.
 // stocs_scene_select, one pinned read-back, ONE synchronisation:
-//   own       scene_own_kernel, a wavefront per slot: popcount of the row, the sort key, the eligibility.
+//   own       scene_own_kernel, a wavefront per slot: popcount of the row, the sort key (cover_walk.h), the eligibility.
 //   order     one 64-bit radix sort (prims.h) of the complemented keys with the slots as values, as instances.hip orders its hypotheses.
-//   select    scene_select_kernel, ONE workgroup of 16 wavefronts with `covered` (up to 64 KB) and the group counts in LDS, the round
-//             structure of instance_select_kernel: wavefront k tests the k-th pending slot; the first that passes is selected, those
-//             before it are dropped for good (cover and counts only grow), those behind it are tested again.
+//   select    scene_select_kernel, ONE workgroup of 16 wavefronts with `covered` (up to 64 KB) and the group counts in LDS: the walk of
+//             cover_walk.h, which instances.hip shares, behind this file's gate (eligible, and the slot's group not full; a selection
+//             counts towards its group).  Cover and counts only grow.
 //   finish    scene_finish_kernel, a wavefront per slot: |A_h \ covered_final| of the unselected ones and the reason, from the final state.
+// The ordering sort and the read-back region (results | selected | count) are cover_walk.h's; the pinned staging is pinned_for (stocs_ctx.h).
 // Known limits: npix <= 2^19, n <= 16 384 slots, 1024 groups; classify walks the whole frame of every hypothesis; the walk is one workgroup.
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
-#include "prims.h"
+#include "cover_walk.h"
 #include "render_rules.h"
-#include "wave_bits.h"
 
 namespace stocs {
 
-enum { SCENE_CHUNK_POINTS = 1024, SCENE_MAX_PIXELS = 1 << 19, SCENE_MAX_N = 16384, SCENE_MAX_GROUPS = 1024, SCENE_SELECT_WAVES = 16, SCENE_RUNS_PER_WAVE = 8 };
+enum { SCENE_CHUNK_POINTS = 1024, SCENE_MAX_PIXELS = 1 << 19, SCENE_MAX_N = 16384, SCENE_MAX_GROUPS = 1024, SCENE_RUNS_PER_WAVE = 8 };
 enum { SC_FOOTPRINT = 0, SC_NO_DEPTH, SC_AGREE, SC_IN_FRONT, SC_BEHIND, SC_ON_MASK, SC_CLAIMED, SC_COUNTS };
 // the most dynamic LDS scene_select_kernel takes: the cover of 2^19 pixels, 1024 group counts, the round's results (of the CU's 160 KB)
-#define SCENE_SELECT_MAX_LDS ((SCENE_MAX_PIXELS / 8) + SCENE_MAX_GROUPS * 4 + 4 * SCENE_SELECT_WAVES * 4)
+#define SCENE_SELECT_MAX_LDS ((SCENE_MAX_PIXELS / 8) + SCENE_MAX_GROUPS * 4 + 4 * COVER_WAVES * 4)
 
 struct SceneState {
     DevBlock work;   // footprints: poses (n x 16 float) | records | one chunk of z-buffers, grow-only
@@ -58,12 +59,8 @@ __global__ __launch_bounds__(256) void scene_splat_kernel(const float* __restric
     for (int i = first + (int)threadIdx.x; i < last; i += 256) {
         const Projected p = project_point(P, mpos[i], mnrm[i], a);
         if (!p.in_image) continue;
-        const int s = splat_radius(p.z, a, ra);
         const uint32_t bits = __float_as_uint(p.z);
-        const int r0 = p.row - s > 0 ? p.row - s : 0, r1 = p.row + s < a.H - 1 ? p.row + s : a.H - 1;
-        const int c0 = p.col - s > 0 ? p.col - s : 0, c1 = p.col + s < a.W - 1 ? p.col + s : a.W - 1;
-        for (int r = r0; r <= r1; ++r)
-            for (int c = c0; c <= c1; ++c) atomicMin(&z[(size_t)r * (size_t)a.W + (size_t)c], bits);
+        splat_square(p, a, ra, [&](int r, int c) { atomicMin(&z[(size_t)r * (size_t)a.W + (size_t)c], bits); });
     }
 }
 
@@ -119,70 +116,41 @@ __global__ __launch_bounds__(256) void scene_own_kernel(const uint32_t* __restri
         const float limit = a.max_violation * (float)footprint[h];
         own[h] = o;
         eligible[h] = (s > 0.0f && o >= a.min_pixels && (float)in_front[h] <= limit) ? 1 : 0;
-        // ~stocs_pack_best(s, h): the ascending stable sort walks the keys downwards, the keys 0 in slot order
-        key[h] = ~(s > 0.0f ? (uint64_t)best_key(s, (uint32_t)h) : (uint64_t)0);
+        key[h] = cover_order_key(s, h);
         idx[h] = (uint32_t)h;
     }
 }
 
-// the walk.  One workgroup of 16 wavefronts; p (first position of the order not yet decided) and nsel are the same in every thread.
-// LDS: Wr words of cover, n_groups counts, then 4 x 16 words of the round's results.
-__global__ __launch_bounds__(64 * SCENE_SELECT_WAVES) void scene_select_kernel(const uint32_t* __restrict__ rows, int Wr, const uint32_t* __restrict__ order,
-                                                                               const int32_t* __restrict__ own, const uint8_t* __restrict__ eligible,
-                                                                               const int32_t* __restrict__ group, const int32_t* __restrict__ cap, int n, int n_groups,
-                                                                               SceneArgs a, int32_t* __restrict__ rank, int32_t* __restrict__ excl,
-                                                                               int32_t* __restrict__ selected, int32_t* __restrict__ n_selected,
-                                                                               uint32_t* __restrict__ cover_out, int32_t* __restrict__ cnt_out) {
-    extern __shared__ __attribute__((aligned(16))) uint32_t sel_lds[];
-    uint4* cov = (uint4*)sel_lds;
-    int* cnt = (int*)(sel_lds + Wr);
-    int* r_pass = cnt + n_groups;
-    int* r_excl = r_pass + SCENE_SELECT_WAVES;
-    int* r_h = r_excl + SCENE_SELECT_WAVES;
-    int* r_g = r_h + SCENE_SELECT_WAVES;
-    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int threads = 64 * SCENE_SELECT_WAVES;
-    const int W4 = Wr >> 2;
-    for (int i = tid; i < W4; i += threads) cov[i] = make_uint4(0u, 0u, 0u, 0u);
-    for (int i = tid; i < n_groups; i += threads) cnt[i] = 0;
-    for (int i = tid; i < n; i += threads) rank[i] = -1;
-    __syncthreads();
-    int p = 0, nsel = 0;
-    while (p < n && nsel < a.max_selected) {
-        const int pos = p + wave;
-        int h = -1, g = 0, ex = 0, pass = 0;
-        if (pos < n) {   // wave-uniform
-            h = (int)order[pos];
-            g = group[h];
-            if (eligible[h] != 0 && cnt[g] < cap[g]) {   // neither comes back: an ineligible slot's row need not be read, nor that of a full group
-                const int o = own[h];
-                const uint4* row = (const uint4*)(rows + (size_t)h * (size_t)Wr);
-                for (int i = lane; i < W4; i += 64) ex += popc_andnot4(row[i], cov[i]);
-                ex = wave_sum_i(ex);
-                pass = (ex >= a.min_pixels && (float)ex >= a.min_fraction * (float)o) ? 1 : 0;
-            }
-        }
-        if (lane == 0) { r_pass[wave] = pass; r_excl[wave] = ex; r_h[wave] = h; r_g[wave] = g; }
-        __syncthreads();
-        int k = -1;
-#pragma unroll
-        for (int j = SCENE_SELECT_WAVES - 1; j >= 0; --j) k = r_pass[j] ? j : k;   // the first that passes, in order
-        if (k < 0) {
-            p += SCENE_SELECT_WAVES;   // all sixteen fail against a subset of their final cover and counts: dropped
-        } else {
-            const int hs = r_h[k], gs = r_g[k];
-            const uint4* row = (const uint4*)(rows + (size_t)hs * (size_t)Wr);
-            for (int i = tid; i < W4; i += threads) { const uint4 e = row[i]; uint4 c = cov[i]; c.x |= e.x; c.y |= e.y; c.z |= e.z; c.w |= e.w; cov[i] = c; }
-            if (tid == 0) { rank[hs] = nsel; excl[hs] = r_excl[k]; selected[nsel] = hs; cnt[gs] += 1; }   // (the counts are read in front of the round's barrier)
-            ++nsel;
-            p += k + 1;   // those in front of it are dropped, those behind it are tested again
-        }
-        __syncthreads();
+// the gate of this walk: neither an ineligible slot nor one of a full group comes back, so its row need not be read.  cnt and r_g are in
+// LDS: r_g[k] is the group of the slot wavefront k tests this round, kept for thread 0, which counts a selection towards it
+struct SceneGate {
+    const uint8_t* __restrict__ eligible; const int32_t* __restrict__ group; const int32_t* __restrict__ cap;
+    int* cnt; int* r_g;
+    __device__ __forceinline__ bool open(int h) const {
+        const int g = group[h];
+        if ((threadIdx.x & 63) == 0) r_g[threadIdx.x >> 6] = g;
+        return eligible[h] != 0 && cnt[g] < cap[g];
     }
-    uint4* co = (uint4*)cover_out;
-    for (int i = tid; i < W4; i += threads) co[i] = cov[i];
+    __device__ __forceinline__ void took(int, int k) const { cnt[r_g[k]] += 1; }
+};
+
+// the walk: cover_walk (cover_walk.h) by one workgroup.  LDS: Wr words of cover, n_groups counts, then 4 x 16 words of the round's
+// results (the walk's three, then the groups).
+__global__ __launch_bounds__(64 * COVER_WAVES) void scene_select_kernel(const uint32_t* __restrict__ rows, int Wr, const uint32_t* __restrict__ order,
+                                                                        const int32_t* __restrict__ own, const uint8_t* __restrict__ eligible,
+                                                                        const int32_t* __restrict__ group, const int32_t* __restrict__ cap, int n, int n_groups,
+                                                                        SceneArgs a, int32_t* __restrict__ rank, int32_t* __restrict__ excl,
+                                                                        int32_t* __restrict__ selected, int32_t* __restrict__ n_selected,
+                                                                        uint32_t* __restrict__ cover_out, int32_t* __restrict__ cnt_out) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t sel_lds[];
+    int* cnt = (int*)(sel_lds + Wr);
+    int* r = cnt + n_groups;
+    const SceneGate gate = {eligible, group, cap, cnt, r + 3 * COVER_WAVES};
+    const CoverArgs wa = {a.max_selected, a.min_pixels, a.min_fraction};
+    const int tid = (int)threadIdx.x, threads = 64 * COVER_WAVES;
+    for (int i = tid; i < n_groups; i += threads) cnt[i] = 0;   // in front of the walk's first barrier
+    cover_walk(rows, Wr, order, own, n, wa, gate, (uint4*)sel_lds, r, rank, excl, selected, n_selected, cover_out);
     for (int i = tid; i < n_groups; i += threads) cnt_out[i] = cnt[i];
-    if (tid == 0) *n_selected = nsel;
 }
 
 // a wavefront per slot, four to a workgroup: the record, decided from the final cover and counts
@@ -194,16 +162,7 @@ __global__ __launch_bounds__(256) void scene_finish_kernel(const uint32_t* __res
     const int h = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);
     if (h >= n) return;   // wave-uniform
     const int r = rank[h];
-    int ex = 0;
-    if (r < 0) {
-        const int W4 = Wr >> 2;
-        const uint4* row = (const uint4*)(rows + (size_t)h * (size_t)Wr);
-        const uint4* cov = (const uint4*)cover;
-        for (int i = lane; i < W4; i += 64) ex += popc_andnot4(row[i], cov[i]);
-        ex = wave_sum_i(ex);
-    } else {
-        ex = excl[h];
-    }
+    const int ex = cover_final_exclusive(rows, Wr, cover, excl, h, r, lane);
     if (lane == 0) {
         const int o = own[h], g = group[h];
         int reason = 0;
@@ -243,19 +202,6 @@ static int check_pixels(const char* who, size_t npix) {
         set_error("%s: a frame of %zu pixels, at most %d (the cover of the walk is a 64 KB bitset in LDS)", who, npix, (int)SCENE_MAX_PIXELS);
         return STOCS_ERR_CAPACITY;
     }
-    return STOCS_OK;
-}
-
-// the pinned block holds what the call sends up (in_bytes at PIN_VAR) and, behind it, the mirror of the read-back
-static int pinned_for(stocs_ctx* c, size_t in_bytes, size_t back_bytes, char** h_in, char** h_back) {
-    const size_t pin_need = (size_t)PIN_VAR + al256(in_bytes) + back_bytes;
-    if (c->pin_bytes < pin_need) {
-        STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));   // nothing may still be copying into the old block
-        const int rc = ensure_pinned(c, pin_need);
-        if (rc) return rc;
-    }
-    *h_in = (char*)c->h_pin + PIN_VAR;
-    *h_back = *h_in + al256(in_bytes);
     return STOCS_OK;
 }
 
@@ -372,18 +318,16 @@ extern "C" int stocs_scene_select(stocs_ctx* c, const void* d_rows, int n, int w
     SceneArgs a;
     a.max_selected = prm->max_selected < n ? prm->max_selected : n;   // no more can be selected than there are
     a.min_pixels = prm->min_pixels; a.min_fraction = prm->min_exclusive_fraction; a.max_violation = prm->max_violation_fraction;
-    size_t sort_bytes = 0;
-    STOCS_HIP_CHECK(sort_pairs(NULL, sort_bytes, (const uint64_t*)NULL, (uint64_t*)NULL, (const uint32_t*)NULL, (uint32_t*)NULL, (size_t)n, 0, 64, c->stream));
     // what goes up is one region (score | group | in_front | footprint | caps), what comes back another (results | selected | count)
     Carve in;
     const size_t i_score = in.take((size_t)n * 4), i_group = in.take((size_t)n * 4), i_front = in.take((size_t)n * 4), i_foot = in.take((size_t)n * 4),
                  i_cap = in.take((size_t)n_groups * 4);
-    Carve bk;
-    const size_t b_res = bk.take((size_t)n * sizeof(stocs_scene_result)), b_sel = bk.take((size_t)a.max_selected * 4), b_cnt = bk.take(4);
+    CoverBack bk;
+    { const int rc = bk.plan(c, n, sizeof(stocs_scene_result), a.max_selected); if (rc) return rc; }
     Carve cv;
     const size_t o_in = cv.take(in.total), o_own = cv.take((size_t)n * 4), o_elig = cv.take((size_t)n), o_key = cv.take((size_t)n * 8), o_key_s = cv.take((size_t)n * 8),
                  o_idx = cv.take((size_t)n * 4), o_idx_s = cv.take((size_t)n * 4), o_rank = cv.take((size_t)n * 4), o_excl = cv.take((size_t)n * 4),
-                 o_cover = cv.take((size_t)Wr * 4), o_cnt = cv.take((size_t)n_groups * 4), o_back = cv.take(bk.total), o_sort = cv.take(sort_bytes);
+                 o_cover = cv.take((size_t)Wr * 4), o_cnt = cv.take((size_t)n_groups * 4), o_back = cv.take(bk.total), o_sort = cv.take(bk.sort_bytes);
     { const int rc = S->sel.grow(c->stream, cv.total); if (rc) return rc; }
     char* h_in; char* h_back;
     { const int rc = pinned_for(c, in.total, bk.total, &h_in, &h_back); if (rc) return rc; }
@@ -408,25 +352,17 @@ extern "C" int stocs_scene_select(stocs_ctx* c, const void* d_rows, int n, int w
     hipLaunchKernelGGL(scene_own_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, rows, Wr, n, Carve::at<float>(d_in, i_score), Carve::at<int32_t>(d_in, i_front),
                        Carve::at<int32_t>(d_in, i_foot), a, d_own, d_elig, Carve::at<uint64_t>(b, o_key), Carve::at<uint32_t>(b, o_idx));
     STOCS_HIP_CHECK(hipGetLastError());
-    size_t tb = sort_bytes;
-    STOCS_HIP_CHECK(sort_pairs(b + o_sort, tb, (const uint64_t*)Carve::at<uint64_t>(b, o_key), Carve::at<uint64_t>(b, o_key_s), (const uint32_t*)Carve::at<uint32_t>(b, o_idx),
-                               d_idx_s, (size_t)n, 0, 64, c->stream));
-    const size_t lds = (size_t)Wr * 4 + (size_t)n_groups * 4 + 4 * SCENE_SELECT_WAVES * 4;
+    { const int rc = bk.order(c, b + o_sort, Carve::at<uint64_t>(b, o_key), Carve::at<uint64_t>(b, o_key_s), Carve::at<uint32_t>(b, o_idx), d_idx_s, n); if (rc) return rc; }
+    const size_t lds = (size_t)Wr * 4 + (size_t)n_groups * 4 + 4 * COVER_WAVES * 4;
     // beyond 64 KB a kernel has to be told; the kernel's ceiling, not this launch's size: contexts on other threads launch the same kernel
     if (lds > 64 * 1024) STOCS_HIP_CHECK(hipFuncSetAttribute((const void*)scene_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SCENE_SELECT_MAX_LDS));
-    hipLaunchKernelGGL(scene_select_kernel, dim3(1), dim3(64 * SCENE_SELECT_WAVES), lds, c->stream, rows, Wr, (const uint32_t*)d_idx_s, (const int32_t*)d_own,
-                       (const uint8_t*)d_elig, d_group, d_cap, n, n_groups, a, d_rank, d_excl, Carve::at<int32_t>(d_back, b_sel), Carve::at<int32_t>(d_back, b_cnt), d_cover,
+    hipLaunchKernelGGL(scene_select_kernel, dim3(1), dim3(64 * COVER_WAVES), lds, c->stream, rows, Wr, (const uint32_t*)d_idx_s, (const int32_t*)d_own,
+                       (const uint8_t*)d_elig, d_group, d_cap, n, n_groups, a, d_rank, d_excl, Carve::at<int32_t>(d_back, bk.o_sel), Carve::at<int32_t>(d_back, bk.o_cnt), d_cover,
                        d_cnt);
     STOCS_HIP_CHECK(hipGetLastError());
     hipLaunchKernelGGL(scene_finish_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, rows, Wr, (const uint32_t*)d_cover, (const int32_t*)d_own,
                        (const uint8_t*)d_elig, d_group, d_cap, (const int32_t*)d_cnt, (const int32_t*)d_rank, (const int32_t*)d_excl, n, a,
-                       Carve::at<stocs_scene_result>(d_back, b_res));
+                       Carve::at<stocs_scene_result>(d_back, bk.o_rec));
     STOCS_HIP_CHECK(hipGetLastError());
-    STOCS_HIP_CHECK(hipMemcpyAsync(h_back, d_back, bk.total, hipMemcpyDeviceToHost, c->stream));
-    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    const int ns = *(const int32_t*)(h_back + b_cnt);
-    memcpy(out, h_back + b_res, (size_t)n * sizeof(stocs_scene_result));
-    memcpy(selected, h_back + b_sel, (size_t)ns * 4);
-    *n_selected = ns;
-    return STOCS_OK;
+    return bk.read_back(c, d_back, h_back, out, selected, n_selected);
 }

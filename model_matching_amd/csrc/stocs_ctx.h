@@ -391,6 +391,11 @@ inline int32_t* cand_base(stocs_ctx* c) { return (int32_t*)((float*)c->d_cand + 
 int ensure_scratch(stocs_ctx* c, size_t bytes);
 int ensure_pinned(stocs_ctx* c, size_t bytes);   // c->h_pin of at least `bytes` (nothing may still be copying into the old block)
 enum { PIN_CONGRUENT = 0, PIN_TRANSFORMS = 256, PIN_VERIFY = 512, PIN_BEST = 768, PIN_VAR = 1024 };   // fixed slots, then the per-call variable part
+// The per-call staging: *h = the variable part of the pinned block, holding at least `bytes`.  The one place where the block grows under a
+// call: the stream is synchronised first if it has to move (nothing may still be copying into the old block).
+int pinned_var(stocs_ctx* c, size_t bytes, char** h);
+// ... split into what the call sends up (in_bytes at *h_in) and, behind it at al256(in_bytes), the mirror of its read-back (back_bytes)
+int pinned_for(stocs_ctx* c, size_t in_bytes, size_t back_bytes, char** h_in, char** h_back);
 // d_best8 != NULL: the kernel's epilogue also takes the arg-max of compute_best_transform over the batch into that word (zeroed in front)
 int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d_hit, uint8_t* d_counted, unsigned long long* d_best8, uint32_t id_offset);
 // every scoring entry point calls this first: the tie counters of stocs_last_tie_counts then cover that call alone (no device work)

@@ -202,15 +202,10 @@ extern "C" int stocs_track_poses(stocs_ctx* c, const float* priors, int n, const
     const size_t back_cand = o_cand - o_res, back_lcp = o_lcp - o_res;
     const size_t back = keep ? back_lcp + (size_t)kr * nc * 4 : (size_t)n * sizeof(stocs_track_result);
     const size_t ib = o_inc_lcp - o_inc;   // the priors go up through the front of the pinned part
-    const size_t pin_need = (size_t)PIN_VAR + ib + al256(back);
-    if (c->pin_bytes < pin_need) {
-        STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));   // nothing may still be copying into the old block
-        const int rc = ensure_pinned(c, pin_need);
-        if (rc) return rc;
-    }
+    char* h_in; char* hout;
+    { const int rc = pinned_for(c, ib, al256(back), &h_in, &hout); if (rc) return rc; }   // ib is a multiple of 256: hout = h_in + ib
     // camera -> centred on the host, in float (centred_from_camera: the arithmetic the device would do)
-    float* hin = (float*)((char*)c->h_pin + PIN_VAR);
-    char* hout = (char*)c->h_pin + PIN_VAR + ib;
+    float* hin = (float*)h_in;
     const V3 cs = c->centroid_scene, cm = c->centroid_model;
     for (int k = 0; k < n; ++k) centred_from_camera(priors + (size_t)k * 16, cs, cm, hin + (size_t)k * 16);
     STOCS_HIP_CHECK(hipMemcpyAsync(d_inc, hin, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));

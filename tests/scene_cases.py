@@ -111,6 +111,22 @@ def random_pool(seed):
                             min_exclusive_fraction=float(rng.choice([0.1, 0.25, 0.5, 0.75, 1.0])), max_violation_fraction=float(rng.choice([0.0, 0.1, 0.25, 0.5, 1.0]))))
 
 
+def walk_pair(seed):
+    """the same sets for the two entry points of the shared cover walk: a rows case of instances_cases.random_rows (40 hypotheses, more than
+    two rounds of sixteen; 300 scene points, a row of 10 words padded to 12) with its scores made strictly positive, ties kept, and the pool
+    that is the same selection to stocs_scene_select: every hypothesis's counted hits as a pixel mask of 300 bits, one group without a cap,
+    no violation, min_pixels = min_points, the same fraction and maximum -> (rows case, pool)"""
+    import instances_cases
+    import instances_ref
+    rows = instances_cases.random_rows(seed, n=40, nS=300)
+    rows["lcp"] = (rows["lcp"] + F(1.0 / 64)).astype(F)
+    assert (rows["lcp"] > 0).all() and len(np.unique(rows["lcp"])) < len(rows["lcp"])
+    claims = instances_ref.explained_sets(rows["hit"], rows["counted"])
+    prm = rows["prm"]
+    return rows, pool("walk_pair_%d" % seed, 300, claims, score=rows["lcp"], max_selected=prm["max_instances"], min_pixels=prm["min_points"],
+                      min_exclusive_fraction=prm["min_exclusive_fraction"], max_violation_fraction=1.0)
+
+
 # ---- models, poses and frames of the footprint tests (hand-built frames: power-of-two intrinsics and depth scale) ----
 EPS = float(2.0 ** -7)          # tolerance of the hand-built cases: a representable float
 SCALE = float(2.0 ** -10)       # depth unit of the hand-built frames: raw 1024 is exactly 1 m

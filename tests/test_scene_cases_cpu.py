@@ -86,6 +86,16 @@ def test_the_sequential_walk_equals_sixteen_per_round_on_300_seeded_pools():
     assert reasons == {0, 1, 2, 3, 4}
 
 
+@pytest.mark.parametrize("seed", range(3))
+def test_the_two_references_agree_on_the_walk_pairs(seed):
+    """the inputs of the GPU test that feeds both entry points of the shared walk: if the references disagreed, the inputs would be wrong"""
+    import instances_ref
+    rows, c = cases.walk_pair(seed)
+    (i_rec, i_sel), (s_rec, s_sel) = instances_ref.select(rows["hit"], rows["counted"], rows["lcp"], **rows["prm"]), cases.run_ref(c)
+    assert all(np.array_equal(i_rec[f], s_rec[f]) for f in ("rank", "own", "exclusive")) and np.array_equal(i_sel, s_sel)
+    assert len(i_sel) >= 2 and (i_rec["rank"] < 0).any()   # something is selected and something is not
+
+
 @pytest.mark.parametrize("name", sorted(cases.hand_pools()))
 def test_hand_built_pools_reach_their_branch(name):
     c = cases.hand_pools()[name]

@@ -292,6 +292,22 @@ def test_200_seeded_random_pools(walker):
     assert reasons == {0, 1, 2, 3, 4}
 
 
+@pytest.mark.parametrize("seed", range(3))
+def test_the_two_entry_points_of_the_shared_walk_agree(walker, seed):
+    """stocs_select_instances_rows and stocs_scene_select on the same sets (scene_cases.walk_pair): rank, own and exclusive per slot and
+    the selected lists are equal -- to each other and, the references agreeing on these inputs, to both references"""
+    import instances_ref
+    rows, c = cases.walk_pair(seed)
+    i_want, s_want = instances_ref.select(rows["hit"], rows["counted"], rows["lcp"], **rows["prm"]), cases.run_ref(c)
+    assert all(np.array_equal(i_want[0][f], s_want[0][f]) for f in ("rank", "own", "exclusive")) and np.array_equal(i_want[1], s_want[1])
+    i_rec, i_sel = walker.select_instances_rows(rows["hit"], rows["counted"], rows["lcp"], rows["nS"], **rows["prm"])
+    s_rec, s_sel = _select(walker, c)
+    for f in ("rank", "own", "exclusive"):
+        assert np.array_equal(i_rec[f], s_rec[f]), (f, i_rec[f], s_rec[f])
+    assert np.array_equal(i_sel, s_sel), (i_sel, s_sel)
+    assert _same((s_rec, s_sel), s_want)
+
+
 def test_select_n_0_a_second_call_and_the_errors(walker):
     from model_matching_amd import capi
     L = capi.load()
