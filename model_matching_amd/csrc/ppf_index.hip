@@ -49,28 +49,31 @@ __global__ __launch_bounds__(256) void ppf_unpack_pairs_kernel(const uint64_t* _
     if (e < n) pairs[e] = (uint32_t)(sorted[e] & 0xFFFFFFFFull);
 }
 
-// set the 128 map keys of every non-empty bucket (rgbd.cpp:130-137)
+// set the 128 map keys of every non-empty bucket (rgbd.cpp:130-137); a block per bucket, striding: the grid is bounded by the
+// launch (PPF_EXISTS_MAX_BLOCKS), the key space is not
+static const int64_t PPF_EXISTS_MAX_BLOCKS = (int64_t)1 << 22;  // x 128 threads = 2^29: a launch of 2^32 threads or more does not run
 __global__ __launch_bounds__(128) void ppf_exists_kernel(const uint32_t* __restrict__ hist, int64_t n_keys, int tr, int rot, int NA,
                                                          int nD, uint32_t* __restrict__ bits) {
-    const int64_t key = blockIdx.x;
-    if (key >= n_keys || hist[key] == 0) return;
-    int rest = (int)key;
-    const int a3 = rest % NA; rest /= NA;
-    const int a2 = rest % NA; rest /= NA;
-    const int a1 = rest % NA; rest /= NA;
-    const int d = rest;
-    const int o = threadIdx.x;  // 0..127
-    const int o0 = (o >> 6) & 1, o1 = (o >> 4) & 3, o2 = (o >> 2) & 3, o3 = o & 3;
-    // p1 in {F0 - tr, F0}; pk in {Fk - 2rot, Fk - rot, Fk, Fk + rot}
-    const int K0 = d * tr - tr + o0 * tr;
-    const int K1 = a1 * rot - 2 * rot + o1 * rot;
-    const int K2 = a2 * rot - 2 * rot + o2 * rot;
-    const int K3 = a3 * rot - 2 * rot + o3 * rot;
-    if (K0 <= 5 || K1 < 0 || K2 < 0 || K3 < 0) return;  // rgbd.cpp:136 (literal 5)
-    const int kd = K0 / tr, k1 = K1 / rot, k2 = K2 / rot, k3 = K3 / rot;
-    if (kd >= nD || k1 >= NA || k2 >= NA || k3 >= NA) return;  // never produced by ppf_compute
-    const uint32_t K = ppf_pack(kd, k1, k2, k3, NA);
-    atomicOr(&bits[K >> 5], 1u << (K & 31));
+    for (int64_t key = blockIdx.x; key < n_keys; key += gridDim.x) {
+        if (hist[key] == 0) continue;
+        int rest = (int)key;
+        const int a3 = rest % NA; rest /= NA;
+        const int a2 = rest % NA; rest /= NA;
+        const int a1 = rest % NA; rest /= NA;
+        const int d = rest;
+        const int o = threadIdx.x;  // 0..127
+        const int o0 = (o >> 6) & 1, o1 = (o >> 4) & 3, o2 = (o >> 2) & 3, o3 = o & 3;
+        // p1 in {F0 - tr, F0}; pk in {Fk - 2rot, Fk - rot, Fk, Fk + rot}
+        const int K0 = d * tr - tr + o0 * tr;
+        const int K1 = a1 * rot - 2 * rot + o1 * rot;
+        const int K2 = a2 * rot - 2 * rot + o2 * rot;
+        const int K3 = a3 * rot - 2 * rot + o3 * rot;
+        if (K0 <= 5 || K1 < 0 || K2 < 0 || K3 < 0) continue;  // rgbd.cpp:136 (literal 5)
+        const int kd = K0 / tr, k1 = K1 / rot, k2 = K2 / rot, k3 = K3 / rot;
+        if (kd >= nD || k1 >= NA || k2 >= NA || k3 >= NA) continue;  // outside the key space: never produced by ppf_compute
+        const uint32_t K = ppf_pack(kd, k1, k2, k3, NA);
+        atomicOr(&bits[K >> 5], 1u << (K & 31));
+    }
 }
 
 int build_ppf_index(stocs_ctx* c) {
@@ -124,7 +127,7 @@ int build_ppf_index(stocs_ctx* c) {
         STOCS_HIP_CHECK(sort_keys(NULL, tmp_bytes, d_keys, d_sorted, (size_t)total, 0, end_bit, c->stream));
         STOCS_HIP_CHECK(dev_malloc(&d_tmp, tmp_bytes));
         STOCS_HIP_CHECK(sort_keys(d_tmp, tmp_bytes, d_keys, d_sorted, (size_t)total, 0, end_bit, c->stream));
-        hipLaunchKernelGGL(ppf_exists_kernel, dim3((unsigned)ix.n_keys), dim3(128), 0, c->stream, d_hist, ix.n_keys, ix.tr, ix.rot,
+        hipLaunchKernelGGL(ppf_exists_kernel, dim3((unsigned)std::min(ix.n_keys, PPF_EXISTS_MAX_BLOCKS)), dim3(128), 0, c->stream, d_hist, ix.n_keys, ix.tr, ix.rot,
                            ix.NA, ix.nD, ix.d_exists);
         STOCS_HIP_CHECK(hipGetLastError());
     }
@@ -165,6 +168,9 @@ int plan_lookup(const PpfIndex& ix, const int* K, std::vector<std::pair<uint32_t
     ranges->clear();
     if (K[0] <= 5 || K[1] < 0 || K[2] < 0 || K[3] < 0) return 0;
     if (K[0] % ix.tr || K[1] % ix.rot || K[2] % ix.rot || K[3] % ix.rot) return 0;
+    // outside the key space: the reference's map holds the + rot offset of a feature at 180, a key no feature ever equals;
+    // absent here, for lookup as for the bitmap (deliberate divergences)
+    if (K[1] > 180 || K[2] > 180 || K[3] > 180) return 0;
     int64_t total = 0;
     // F = K - o, o0 in {-tr,0}, ok in {-2rot,-rot,0,rot}, visited in ASCENDING key order (every F component ascending), so
     // the ranges come out in ascending index position; adjacent buckets are merged on the fly (the 4 consecutive a3 bins of

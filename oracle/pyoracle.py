@@ -59,6 +59,8 @@ def lib():
         L.orc_index_exists.restype = C.c_int
         L.orc_index_num_pairs.argtypes = [vp]
         L.orc_index_num_pairs.restype = C.c_int64
+        L.orc_index_num_features.argtypes = [vp]
+        L.orc_index_num_features.restype = C.c_int64
         L.orc_index_lit_build.argtypes = [fp, fp, C.c_int, C.c_int, C.c_int]
         L.orc_index_lit_build.restype = vp
         L.orc_index_lit_free.argtypes = [vp]
@@ -203,6 +205,9 @@ class Index:
 
     def num_pairs(self):
         return lib().orc_index_num_pairs(self.h)
+
+    def num_features(self):
+        return lib().orc_index_num_features(self.h)
 
     def num_keys(self):
         return lib().orc_index_lit_num_keys(self.h)

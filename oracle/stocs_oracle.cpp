@@ -1096,6 +1096,8 @@ int64_t orc_index_lookup(const orc_index* ix, const int* key4, int32_t* pairs2, 
 }
 int orc_index_exists(const orc_index* ix, const int* key4) { return index_exists(ix, key4) ? 1 : 0; }
 int64_t orc_index_num_pairs(const orc_index* ix) { return ix->npairs; }
+// distinct quantised features F with at least one pair (a NaN normal's INT_MIN features included)
+int64_t orc_index_num_features(const orc_index* ix) { return (int64_t)ix->base.size(); }
 
 orc_index_lit* orc_index_lit_build(const float* pos3, const float* nrm3, int n, int tr_i, int rot_i) {
     orc_index_lit* ix = new orc_index_lit;

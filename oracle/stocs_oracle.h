@@ -56,6 +56,7 @@ void       orc_index_free(orc_index*);
 int64_t    orc_index_lookup(const orc_index*, const int* key4, int32_t* pairs2, int64_t cap);
 int        orc_index_exists(const orc_index*, const int* key4);
 int64_t    orc_index_num_pairs(const orc_index*);
+int64_t    orc_index_num_features(const orc_index*);
 /* literal std::map with the 128-key insertion of rgbd.cpp:123-154 (small n only) */
 typedef struct orc_index_lit orc_index_lit;
 orc_index_lit* orc_index_lit_build(const float* pos3, const float* nrm3, int n, int tr, int rot);
