@@ -671,6 +671,31 @@ public:
         return r;
     }
 
+    // Pose errors against ground truth (stocs_pose_errors / stocs_model_diameter; no reference counterpart): the camera-frame estimates
+    // against one ground-truth pose (gt.size() == 1) or one each (gt.size() == est.size()), in one GPU pass: ADD, ADD-S and their maxima
+    // in metres, one record per estimate in input order.  Empty on error (the text goes to the log).  model_diameter: the largest
+    // distance between two model points, computed on the device once; negative on error.
+    std::vector<stocs_pose_error> pose_errors(const std::vector<PoseCandidate*>& est, const std::vector<PoseCandidate*>& gt) {
+        const int n = (int)est.size(), n_gt = (int)gt.size();
+        std::vector<float> P((size_t)n * 16), G((size_t)n_gt * 16);
+        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], est[(size_t)i]->transform.data(), 64);
+        for (int i = 0; i < n_gt; ++i) std::memcpy(&G[(size_t)i * 16], gt[(size_t)i]->transform.data(), 64);
+        std::vector<stocs_pose_error> r((size_t)n);
+        if (n > 0 && stocs_pose_errors(ctx_, P.data(), n, G.data(), n_gt, r.data()) != STOCS_OK) {
+            *log_ << "pose_errors failed: " << stocs_last_error() << std::endl;
+            r.clear();
+        }
+        return r;
+    }
+    float model_diameter() {
+        float d = -1.0f;
+        if (stocs_model_diameter(ctx_, &d) != STOCS_OK) {
+            *log_ << "model_diameter failed: " << stocs_last_error() << std::endl;
+            return -1.0f;
+        }
+        return d;
+    }
+
     // Joint rendering (stocs_explain_poses; no reference counterpart): the camera-frame poses -- the instances select_instances kept, say
     // -- rendered TOGETHER against the frame of set_frame, nearest surface first: one record per pose in input order (footprint,
     // visible / hidden behind the others, and the visible pixels' agreement with the depth image), and, when `labels` is given, the

@@ -534,6 +534,51 @@ typedef struct stocs_depth_result {
 void stocs_default_depth_params(stocs_depth_params* p);
 int stocs_depth_check_poses(stocs_ctx* ctx, const float* pose16_camera, int n, const stocs_depth_params* p, stocs_depth_result* out);
 
+/* ---- pose errors against ground truth: ADD, ADD-S, model diameter (no reference counterpart; the host method this replaces is a
+ * kd-tree query plus float64 products per pose).  stocs_pose_errors compares n estimated CAMERA-frame poses (column-major, as
+ * stocs_depth_check_poses takes them) with ground-truth poses of the same kind: n_gt == 1, every estimate against the one ground
+ * truth; n_gt == n, estimate k against ground truth k; any other n_gt is STOCS_ERR_INVALID.  Poses act on the model positions as
+ * handed to stocs_ctx_create (M of them).  Per pair, all in float, every operation a single IEEE add / sub / mul / sqrt, no
+ * contraction (R_ab = P[4b + a], t_a = P[12 + a]):
+ *   1. p_a(i) = (R_a0 m_x + (R_a1 m_y + R_a2 m_z)) + t_a under the estimate, g_a(j) the same expression under the ground truth
+ *      (step 1 of the depth check).
+ *   2. D(i, j) = (dx dx) + ((dy dy) + (dz dz)),  d = p(i) - g(j).
+ *   3. e_i = r(D(i, i)),  s_i = r(min_j D(i, j)); the minimum starts at +inf and is replaced only on `<`, so a NaN never wins it;
+ *      r(x) = +inf for NaN, else the correctly rounded float square root; nn_i = the lowest j that attains the minimum, -1 when
+ *      none does.  j = i is among the candidates with the identical expression: s_i <= e_i holds bit for bit.
+ *   4. q(x) = (uint64) floor(min(x, 32768.f) * 2^32) (exact);  add_fix = sum_i q(e_i),  adds_fix = sum_i q(s_i);
+ *      add = (float)((double)add_fix / 2^32 / (double)M), adds likewise;  add_max = max_i e_i,  adds_max = max_i s_i.
+ *      Integer sums and maxima: a record is bitwise independent of the batch it shares, of its position there and of any reduction
+ *      order, and a float32 numpy restatement reproduces every field (tests/pose_error_ref.py).
+ *   5. valid = 0, zero sums and four +inf when one of the pair's two poses has a non-finite entry among the twelve R_ab, t_a, or
+ *      when all sixteen entries of the estimate are zero (a trial batch's "no pose" record).  Neither is an error.
+ *   6. stocs_model_diameter: max over i < j of r(D(i, j)) with both points untransformed (p = m_i, g = m_j) and step 2's expression
+ *      as it stands; 0 for M == 1.  Computed on the device at the first call and kept on the context (the model is fixed per context).
+ * stocs_pose_errors_detail gives e, s and nn (M entries each, any may be NULL) of ONE pair; it applies steps 1-3 to the poses as
+ * given (step 5 does not apply: a non-finite pose yields +inf and -1 by the arithmetic alone).
+ * Checked in this order: a NULL ctx (whatever n) and n < 0 are STOCS_ERR_INVALID; n == 0 is then a no-op that looks at no other
+ * argument; with n > 0 a NULL out or pose pointer, and an n_gt other than 1 or n, are STOCS_ERR_INVALID.  stocs_pose_errors_detail:
+ * a NULL ctx or pose; stocs_model_diameter: a NULL ctx or result.  Its own grow-only workspace on the context (a second
+ * call of the same or a smaller size allocates nothing, stocs_device_alloc_count); on the context's stream, one pinned read-back and
+ * one synchronisation per call.  stocs_last_call_timing(which = 4) gives the host steps of the last stocs_pose_errors and, with the
+ * "device_clock" option on, the HIP-event time of its launches.
+ * The kernel (csrc/pose_error.hip) is exact brute force: workgroups of STOCS_POSE_ERROR_THREADS threads on a grid (query chunks,
+ * pairs); a chunk is STOCS_POSE_ERROR_CHUNK query points (four rows of one per thread; a chunk with fewer rows runs a loop
+ * instantiated for 1, 2 or 3), and the targets pass through LDS in tiles of STOCS_POSE_ERROR_TILE points.  A call of more than
+ * 65 535 pairs is several launches.  Known limit: few pairs on a small model leave most compute units idle. ---- */
+#define STOCS_POSE_ERROR_THREADS 256
+#define STOCS_POSE_ERROR_CHUNK 1024
+#define STOCS_POSE_ERROR_TILE 1024
+typedef struct stocs_pose_error {
+    uint64_t add_fix, adds_fix;              /* sums of step 4 */
+    float    add, add_max, adds, adds_max;   /* metres */
+    int32_t  valid, reserved;
+} stocs_pose_error;
+int stocs_pose_errors(stocs_ctx* ctx, const float* est_pose16_camera, int n, const float* gt_pose16_camera, int n_gt, stocs_pose_error* out);
+int stocs_pose_errors_detail(stocs_ctx* ctx, const float* est_pose16_camera, const float* gt_pose16_camera,
+                             float* e /*M*/, float* s /*M*/, int32_t* nn /*M*/);   /* one pair; any output may be NULL */
+int stocs_model_diameter(stocs_ctx* ctx, float* diameter);
+
 /* ---- multi-instance selection (no reference counterpart: the reference returns one pose per object).  Of n hypotheses, which are
  * distinct instances and which are one instance found twice: walk them best first and keep one only if enough of the scene points it
  * explains are not explained by one kept before it.  stocs_select_instances takes n CENTRED-frame hypotheses (column-major, as
@@ -805,7 +850,8 @@ int stocs_debug_sort_pairs(int device, const uint32_t* keys, const uint32_t* val
  * difference across them is 0. */
 int64_t stocs_device_alloc_count(void);
 /* host wall clock, in milliseconds, of the steps of the context's LAST stocs_find_congruent_all (which = 0),
- * stocs_make_transforms (1), stocs_verify_all (2) or stocs_run_trials (3: its phases summed over the pieces of the batch): always recorded (a few clock reads per call, no synchronisation of its
+ * stocs_make_transforms (1), stocs_verify_all (2), stocs_run_trials (3: its phases summed over the pieces of the batch) or stocs_pose_errors
+ * (4; with "device_clock" 1 also "device: kernel", the HIP-event time of its launches): always recorded (a few clock reads per call, no synchronisation of its
  * own), so that a call that stalls -- tens of milliseconds instead of one -- names the step it stalled in.  Steps are host
  * intervals between the call's existing synchronisation points: "wait for the device" steps hold the GPU work, the others
  * host work and runtime calls; entries whose label starts with "device:" are HIP-event times of the kernel groups that

@@ -22,6 +22,11 @@
 // row-major) -- a local search around it on this frame (stocs_track_poses, the façade's default parameters); when the tracked lcp is
 // below x (default 0.02: a prior that has lost the object scores ~0) the usual detection runs instead.  Prints which route produced
 // the pose ("track: route=tracked ..." / "track: route=detection ...") and writes <out> as detection does.
+// --gt <pose file> (single object): a ground-truth pose in the same format.  After the run, "gt <object>: add=... add_max=... adds=...
+// adds_max=... diameter=... adds_over_diameter=... valid=..." (metres; stocs_pose_errors on the pose file this run wrote, read back as the
+// ground truth is) and, with --trials N, "gt <object> recall: trials=N valid=... threshold=... add=... adds=...": the share of the trials'
+// winners whose ADD / ADD-S is below 0.1 diameter (with --track only when the run fell back to detection: a tracked pose ran no trials).
+// A pose file left at <out> by an earlier run is removed first; when this run finds no pose the line reads "gt <object>: no pose".
 // --depth-check (with --trials N --cluster 1 [--refine K], a scene directory): every trial's hypotheses -- the refined poses when
 // refinement ran -- scored against the frame's own depth image and class-probability map (stocs_depth_check_poses); one "depth t.i:"
 // line per hypothesis, and <out> is written from the first maximum of score - violation (ties: the higher lcp, then the lower trial
@@ -303,15 +308,65 @@ static int run_search(stocs::stocs_estimator& stocs_ptr, std::ostream& os, const
     return 0;
 }
 
-// --track: the prior from the pose file, tracked on this frame; the detection of run_search when the tracked lcp stays below min_lcp
-static int run_track(stocs::stocs_estimator& est, const std::string& track_path, float min_lcp, const std::string& out_path, const std::string& dbg_dir,
-                     uint64_t seed, int n_trials, int exact_ties, int do_cluster, int n_refine) {
-    std::ifstream f(track_path);
+// a pose file in the format this driver writes (12 floats, 3x4 row-major): the reader of --track and --gt
+static bool read_pose_file(const std::string& path, MatrixType& m) {
+    std::ifstream f(path);
     float v[12];
     for (int i = 0; i < 12; ++i)
-        if (!(f >> v[i])) { std::cerr << "cannot read a 3x4 pose from " << track_path << std::endl; return 1; }
-    MatrixType m;   // identity; the bottom row stays 0 0 0 1
+        if (!(f >> v[i])) return false;
+    m = MatrixType();   // identity; the bottom row stays 0 0 0 1
     for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) m(r, c) = v[r * 4 + c];
+    return true;
+}
+
+// --gt: the pose this run wrote to out_path, read back with the reader the ground truth goes through (what is scored is what a reader of
+// the file gets), against the ground truth: ADD, ADD-S, their maxima, the model's diameter (stocs_pose_errors, stocs_model_diameter); with
+// --trials N also the share of the trials' winners (full precision, a trial without a pose left out) within 0.1 diameter
+static int report_gt(stocs::stocs_estimator& est, const std::string& gt_path, const std::string& out_path, const std::string& object,
+                     const std::vector<stocs::stocs_estimator::TrialResult>& trials) {
+    MatrixType g, p;
+    if (!read_pose_file(gt_path, g)) { std::cerr << "cannot read a 3x4 pose from " << gt_path << std::endl; return 1; }
+    PoseCandidate gt(g, 0.0f, -1.0f);
+    const std::vector<PoseCandidate*> gts(1, &gt);
+    const float diameter = est.model_diameter();
+    if (diameter < 0.0f) { std::cerr << "model diameter failed: " << stocs_last_error() << std::endl; return 2; }
+    char b[384];
+    if (!read_pose_file(out_path, p)) {
+        std::cout << "gt " << object << ": no pose" << std::endl;
+    } else {
+        PoseCandidate e(p, 0.0f, -1.0f);
+        const std::vector<stocs_pose_error> r = est.pose_errors(std::vector<PoseCandidate*>(1, &e), gts);
+        if (r.size() != 1) { std::cerr << "pose errors failed: " << stocs_last_error() << std::endl; return 2; }
+        snprintf(b, sizeof(b), "gt %s: add=%.9g add_max=%.9g adds=%.9g adds_max=%.9g diameter=%.9g adds_over_diameter=%.9g valid=%d", object.c_str(), (double)r[0].add,
+                 (double)r[0].add_max, (double)r[0].adds, (double)r[0].adds_max, (double)diameter, diameter > 0.0f ? (double)(r[0].adds / diameter) : 0.0, r[0].valid);
+        std::cout << b << std::endl;
+    }
+    if (!trials.empty()) {
+        std::vector<PoseCandidate> w;
+        for (size_t t = 0; t < trials.size(); ++t) w.push_back(PoseCandidate(trials[t].best_pose, trials[t].best_lcp, -1.0f));
+        std::vector<PoseCandidate*> wp;
+        for (size_t t = 0; t < w.size(); ++t) wp.push_back(&w[t]);
+        const std::vector<stocs_pose_error> r = est.pose_errors(wp, gts);
+        if (r.size() != wp.size()) { std::cerr << "pose errors failed: " << stocs_last_error() << std::endl; return 2; }
+        const float thr = 0.1f * diameter;
+        int valid = 0, hit_add = 0, hit_adds = 0;
+        for (size_t t = 0; t < r.size(); ++t) {
+            if (!r[t].valid) continue;
+            ++valid; hit_add += r[t].add < thr; hit_adds += r[t].adds < thr;
+        }
+        snprintf(b, sizeof(b), "gt %s recall: trials=%d valid=%d threshold=%.9g add=%.9g adds=%.9g", object.c_str(), (int)r.size(), valid, (double)thr,
+                 valid ? (double)hit_add / valid : 0.0, valid ? (double)hit_adds / valid : 0.0);
+        std::cout << b << std::endl;
+    }
+    return 0;
+}
+
+// --track: the prior from the pose file, tracked on this frame; the detection of run_search when the tracked lcp stays below min_lcp
+static int run_track(stocs::stocs_estimator& est, const std::string& track_path, float min_lcp, const std::string& out_path, const std::string& dbg_dir,
+                     uint64_t seed, int n_trials, int exact_ties, int do_cluster, int n_refine,
+                     std::vector<stocs::stocs_estimator::TrialResult>* trial_results = NULL) {
+    MatrixType m;
+    if (!read_pose_file(track_path, m)) { std::cerr << "cannot read a 3x4 pose from " << track_path << std::endl; return 1; }
     PoseCandidate prior(m, 0.0f, -1.0f);
     if (exact_ties) est.set_exact_ties(true);
     std::vector<PoseCandidate*> priors(1, &prior);
@@ -326,7 +381,7 @@ static int run_track(stocs::stocs_estimator& est, const std::string& track_path,
         snprintf(line, sizeof(line), "track: route=detection prior_lcp=%.9g tracked_lcp=%.9g min_lcp=%.9g track_microseconds=%lld", (double)res[0].prior_lcp,
                  (double)got[0]->lcp, (double)min_lcp, us);
         std::cout << line << std::endl;
-        return run_search(est, std::cout, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine);
+        return run_search(est, std::cout, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine, 0, NULL, std::string(), std::string(), trial_results);
     }
     const PoseCandidate* bp = got[0];
     std::ofstream o(out_path, std::ofstream::out);
@@ -483,7 +538,7 @@ int main(int argc, char** argv) {
     if (clouds && argc < 4) { std::cout << "usage: stocs_single --clouds <scene.stcl> <model.stcl> [options]" << std::endl; return -1; }
     const std::string a1 = argv[clouds ? 2 : 1], a2 = argv[clouds ? 3 : 2];
     if (const char* e = getenv("STOCS_REPO_PATH")) repo_path = e;
-    std::string edge_path, out_path, dbg_dir, track_path;
+    std::string edge_path, out_path, dbg_dir, track_path, gt_path;
     float track_min_lcp = 0.02f;
     int do_cluster = 0, n_trials = 0, exact_ties = 0, n_refine = 0, depth_check = 0;
     bool do_instances = false, do_masks = false;
@@ -508,6 +563,7 @@ int main(int argc, char** argv) {
         else if (k == "--exact-ties") exact_ties = atoi(v.c_str());   // 1: the reference kd-tree's answer on exact distance ties (set_exact_ties)
         else if (k == "--track") track_path = v;   // track from this pose file; detection when the tracked lcp is below --track-min-lcp
         else if (k == "--track-min-lcp") track_min_lcp = (float)atof(v.c_str());
+        else if (k == "--gt") gt_path = v;   // ground-truth pose file (the format of --track): ADD / ADD-S of the pose this run writes
         else if (k == "--instances") { do_instances = true; inst_prm.max_instances = atoi(v.c_str()); }
         else if (k == "--instance-min-fraction") inst_prm.min_exclusive_fraction = (float)atof(v.c_str());
         else if (k == "--instance-min-points") inst_prm.min_points = atoi(v.c_str());
@@ -519,6 +575,11 @@ int main(int argc, char** argv) {
         else if (k == "--intrinsics") {
             if (sscanf(v.c_str(), "%f,%f,%f,%f", &cam_intrinsics[0], &cam_intrinsics[1], &cam_intrinsics[2], &cam_intrinsics[3]) != 4) { std::cerr << "--intrinsics fx,cx,fy,cy" << std::endl; return -1; }
         } else { std::cerr << "unknown option " << k << std::endl; return -1; }
+    }
+
+    if (!gt_path.empty()) {   // before any search: a ground truth that cannot be read ends the run here
+        MatrixType g;
+        if (!read_pose_file(gt_path, g)) { std::cerr << "cannot read a 3x4 pose from " << gt_path << std::endl; return 1; }
     }
 
     if (n_refine < 0 || (n_refine > 0 && !do_cluster)) { std::cerr << "--refine N needs N >= 0 and --cluster 1" << std::endl; return -1; }
@@ -552,8 +613,8 @@ int main(int argc, char** argv) {
         for (size_t k = 0; k < objects.size(); ++k) {
             if (objects[k].empty() || std::count(objects.begin(), objects.end(), objects[k]) > 1) { std::cerr << "object list " << a2 << ": empty or repeated name" << std::endl; return -1; }
         }
-        if (do_cluster || n_refine || !out_path.empty() || !dbg_dir.empty() || !edge_path.empty() || !track_path.empty()) {
-            std::cerr << "several objects: --cluster, --refine, --out, --dbg, --edge and --track take a single object" << std::endl;
+        if (do_cluster || n_refine || !out_path.empty() || !dbg_dir.empty() || !edge_path.empty() || !track_path.empty() || !gt_path.empty()) {
+            std::cerr << "several objects: --cluster, --refine, --out, --dbg, --edge, --track and --gt take a single object" << std::endl;
             return -1;
         }
         return run_frame_objects(a1, objects, seed, n_trials, exact_ties, scene_opt);
@@ -607,19 +668,24 @@ int main(int argc, char** argv) {
         return 2;
     }
     std::string instances_path, labels_path;
+    std::string object = a2;
+    if (clouds) {
+        const size_t sl = object.find_last_of('/');
+        if (sl != std::string::npos) object = object.substr(sl + 1);
+        const size_t dot = object.find_last_of('.');
+        if (dot != std::string::npos && dot > 0) object = object.substr(0, dot);
+    }
     if (do_instances) {   // next to <out>
-        std::string object = a2;
-        if (clouds) {
-            const size_t sl = object.find_last_of('/');
-            if (sl != std::string::npos) object = object.substr(sl + 1);
-            const size_t dot = object.find_last_of('.');
-            if (dot != std::string::npos && dot > 0) object = object.substr(0, dot);
-        }
         const size_t sl = out_path.find_last_of('/');
         instances_path = (sl == std::string::npos ? std::string() : out_path.substr(0, sl + 1)) + "pose_instances_" + object + ".txt";
         if (do_masks) labels_path = (sl == std::string::npos ? std::string() : out_path.substr(0, sl + 1)) + "labels_" + object + ".pgm";
     }
-    if (!track_path.empty()) return run_track(*est, track_path, track_min_lcp, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine);
-    return run_search(*est, std::cout, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine, depth_check, do_instances ? &inst_prm : NULL,
-                      instances_path, labels_path);
+    std::vector<stocs::stocs_estimator::TrialResult> trial_results;
+    // --gt scores the pose file THIS run writes: one left at out_path by an earlier run must not stand in for it when this run finds no pose
+    if (!gt_path.empty()) std::remove(out_path.c_str());
+    const int rc = !track_path.empty() ? run_track(*est, track_path, track_min_lcp, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine, &trial_results)
+                                       : run_search(*est, std::cout, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine, depth_check,
+                                                    do_instances ? &inst_prm : NULL, instances_path, labels_path, &trial_results);
+    if (rc != 0 || gt_path.empty()) return rc;
+    return report_gt(*est, gt_path, out_path, object, trial_results);
 }

@@ -65,6 +65,11 @@ class DepthResult(C.Structure):
                 ("in_front", C.c_int32), ("behind", C.c_int32), ("on_mask", C.c_int32), ("score", C.c_float), ("violation", C.c_float)]
 
 
+class PoseError(C.Structure):
+    _fields_ = [("add_fix", C.c_uint64), ("adds_fix", C.c_uint64), ("add", C.c_float), ("add_max", C.c_float), ("adds", C.c_float),
+                ("adds_max", C.c_float), ("valid", C.c_int32), ("reserved", C.c_int32)]
+
+
 class InstanceParams(C.Structure):
     _fields_ = [("max_instances", C.c_int32), ("min_points", C.c_int32), ("min_exclusive_fraction", C.c_float)]
 
@@ -180,6 +185,9 @@ SIGNATURES = {
     "stocs_ctx_set_frame": (C.c_int, [_vp, C.POINTER(Camera), C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
     "stocs_default_depth_params": (None, [C.POINTER(DepthParams)]),
     "stocs_depth_check_poses": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(DepthParams), C.POINTER(DepthResult)]),
+    "stocs_pose_errors": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, C.POINTER(PoseError)]),
+    "stocs_pose_errors_detail": (C.c_int, [_vp, _fp, _fp, _fp, _fp, _ip]),
+    "stocs_model_diameter": (C.c_int, [_vp, _fp]),
     "stocs_default_render_params": (None, [C.POINTER(RenderParams)]),
     "stocs_render_poses": (C.c_int, [_vp, _fp, C.c_int, C.c_int, C.POINTER(RenderParams), _vp, C.c_int]),
     "stocs_render_resolve": (C.c_int, [_vp, _fp, C.c_int, C.c_int, C.POINTER(RenderParams), _vp, C.POINTER(RenderResult)]),

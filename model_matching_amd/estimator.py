@@ -39,6 +39,9 @@ assert _TRACK_DTYPE.itemsize == C.sizeof(capi.TrackResult)
 _DEPTH_DTYPE = np.dtype([("facing", np.int32), ("in_image", np.int32), ("self_occluded", np.int32), ("no_depth", np.int32), ("agree", np.int32),
                          ("in_front", np.int32), ("behind", np.int32), ("on_mask", np.int32), ("score", np.float32), ("violation", np.float32)])
 assert _DEPTH_DTYPE.itemsize == C.sizeof(capi.DepthResult)
+_POSE_ERROR_DTYPE = np.dtype([("add_fix", np.uint64), ("adds_fix", np.uint64), ("add", np.float32), ("add_max", np.float32), ("adds", np.float32),
+                              ("adds_max", np.float32), ("valid", np.int32), ("reserved", np.int32)])
+assert _POSE_ERROR_DTYPE.itemsize == C.sizeof(capi.PoseError)
 _RENDER_DTYPE = np.dtype([(f[0], np.int32) for f in capi.RenderResult._fields_])
 assert _RENDER_DTYPE.itemsize == C.sizeof(capi.RenderResult)
 _INSTANCE_DTYPE = np.dtype([("rank", np.int32), ("own", np.int32), ("exclusive", np.int32), ("lcp", np.float32)])
@@ -363,6 +366,36 @@ class StocsEstimator:
         capi.check(self.L.stocs_depth_check_poses(self.h, pP, n, C.byref(prm), buf))
         return np.frombuffer(buf, dtype=_DEPTH_DTYPE, count=n).copy()
 
+    def pose_errors(self, est, gt):
+        """n estimated camera-frame poses (column-major 16 floats each) against ground truth (stocs_pose_errors): gt holds one pose (every
+        estimate against it) or n (estimate k against gt k) -> a structured array with the fields of stocs_pose_error, one record per
+        estimate: ADD (`add`), ADD-S (`adds`), their maxima, in metres."""
+        P, pP = capi.f32(est)
+        G, pG = capi.f32(gt)
+        if P.size % 16 or G.size % 16 or G.size == 0:
+            raise ValueError("pose_errors: poses are 16 floats each")
+        n, n_gt = P.size // 16, G.size // 16
+        buf = (capi.PoseError * max(n, 1))()
+        capi.check(self.L.stocs_pose_errors(self.h, pP, n, pG, n_gt, buf))
+        return np.frombuffer(buf, dtype=_POSE_ERROR_DTYPE, count=n).copy()
+
+    def pose_errors_detail(self, est, gt):
+        """One pair of camera-frame poses (stocs_pose_errors_detail) -> (e, s, nn), one entry per model point: the distance to the same
+        point under gt, the distance to the nearest point under gt, and that point's index (-1: none)."""
+        P, pP = capi.f32(est)
+        G, pG = capi.f32(gt)
+        if P.size != 16 or G.size != 16:
+            raise ValueError("pose_errors_detail: one pose of 16 floats each")
+        e, s, nn = np.empty(self.nM, np.float32), np.empty(self.nM, np.float32), np.empty(self.nM, np.int32)
+        capi.check(self.L.stocs_pose_errors_detail(self.h, pP, pG, e.ctypes.data_as(capi._fp), s.ctypes.data_as(capi._fp), nn.ctypes.data_as(capi._ip)))
+        return e, s, nn
+
+    def model_diameter(self):
+        """The largest distance between two model points (stocs_model_diameter), computed on the device once per context."""
+        d = C.c_float()
+        capi.check(self.L.stocs_model_diameter(self.h, C.byref(d)))
+        return np.float32(d.value)
+
     def _render_params(self, who, params):
         prm = capi.RenderParams()
         self.L.stocs_default_render_params(C.byref(prm))
@@ -676,7 +709,7 @@ class StocsEstimator:
     def last_call_timing(self, which):
         """[(step, milliseconds)] of the last find_congruent_all (0), make_transforms (1) or compute_best_transform (2):
         host wall clock between the call's own synchronisation points, always recorded by the library."""
-        labels = (C.c_char_p * 18)()   # which = 3: the phases of the last run_trials
+        labels = (C.c_char_p * 18)()   # which = 3: the phases of the last run_trials; 4: the last pose_errors
         ms = (C.c_double * 18)()
         n = C.c_int(0)
         capi.check(self.L.stocs_last_call_timing(self.h, which, labels, ms, 18, C.byref(n)))
@@ -755,6 +788,18 @@ def select_scene(estimators, poses_per_object, scores_per_object=None, max_per_o
         if zkey is not None:
             first.dev_free(zkey)
     return out
+
+
+def pose_recall(errors, diameter, k=0.1):
+    """Share of the valid records of pose_errors whose ADD, and whose ADD-S, is below k * diameter -> (recall_add, recall_adds, n_valid);
+    (nan, nan, 0) when no record is valid.  Invalid records ("no pose") are left out, not counted as misses."""
+    errors = np.asarray(errors)
+    ok = errors["valid"] != 0
+    nv = int(ok.sum())
+    if nv == 0:
+        return float("nan"), float("nan"), 0
+    thr = np.float32(k) * np.float32(diameter)
+    return float((errors["add"][ok] < thr).mean()), float((errors["adds"][ok] < thr).mean()), nv
 
 
 def kdtree_nn_host(pos3, queries3, sqdist):

@@ -1,0 +1,77 @@
+"""Recall of StoCS trials against the synthetic ground truth -> profiles/trial_recall.json.
+
+    python tools/trial_recall.py --example synth:Cm_asym --trials 256 [--post]
+
+Runs --trials independent trials as one batch (run_trials, seeds --seed, --seed + 1, ...), scores every trial's winner against the scene's
+T_gt with pose_errors (ADD, ADD-S on the GPU) and reports the share of trials whose error is below 0.1 of the model's diameter: of the
+trials that returned a pose (pose_recall) and of all trials.  With --post the batch clusters and refines (5 iterations) inside the call and
+the best refined hypothesis of every trial (first maximum of the rescored lcp) is scored too.  synth:Cm is an ellipsoid of revolution
+with one bump: its ADD says little, its ADD-S is the meaningful one; synth:Cm_asym has no symmetry.  No GPU: the tool fails."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from model_matching_amd import synth  # noqa: E402
+from model_matching_amd.estimator import StocsEstimator, pose_recall  # noqa: E402
+
+
+def summary(err, diameter, n_trials):
+    ra, rs, nv = pose_recall(err, diameter, 0.1)
+    ok = err["valid"] != 0
+    thr = np.float32(0.1) * np.float32(diameter)
+    return {"trials": n_trials, "with_pose": nv, "recall_add_of_poses": ra, "recall_adds_of_poses": rs,
+            "recall_add_of_trials": float((ok & (err["add"] < thr)).sum()) / n_trials,
+            "recall_adds_of_trials": float((ok & (err["adds"] < thr)).sum()) / n_trials,
+            "median_add_mm": float(np.median(err["add"][ok]) * 1e3) if nv else None,
+            "median_adds_mm": float(np.median(err["adds"][ok]) * 1e3) if nv else None}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--example", default="synth:Cm_asym", choices=["synth:Cm_asym", "synth:Cm"])
+    ap.add_argument("--trials", type=int, default=256)
+    ap.add_argument("--seed", type=int, default=1000)
+    ap.add_argument("--post", action="store_true")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "trial_recall.json"))
+    a = ap.parse_args()
+    name = a.example.split(":", 1)[1]
+    model, scene, _ = synth.workload(name)
+    est = StocsEstimator(scene.pos, scene.nrm, scene.prob, scene.pixel, model.pos, model.nrm, build_index=True)
+    gt16 = np.asarray(scene.T_gt, np.float64).T.reshape(16).astype(np.float32)
+    seeds = list(range(a.seed, a.seed + a.trials))
+    post = dict(refine_iterations=5) if a.post else None
+    res = est.run_trials(seeds, post=post)
+    diameter = float(est.model_diameter())
+    W = np.stack([r["best_pose"] for r in res]).astype(np.float32)
+    row = {"example": a.example, "model_points": len(model.pos), "scene_points": len(scene.pos), "first_seed": a.seed, "model_diameter_m": diameter,
+           "threshold_m": float(np.float32(0.1) * np.float32(diameter)), "winners": summary(est.pose_errors(W, gt16), diameter, a.trials)}
+    if a.post:
+        R = np.zeros((a.trials, 16), np.float32)      # all zero: "no pose"
+        for t in range(a.trials):
+            h = est.trials_get_hypotheses(t)
+            if len(h):
+                R[t] = h["refined_pose16"][int(np.argmax(h["refined_lcp"]))]
+        row["refined_winners"] = summary(est.pose_errors(R, gt16), diameter, a.trials)
+    est.close()
+    print(json.dumps(row), flush=True)
+    # one file, one entry per example (and per --post): a second run adds to it
+    data = {"what": "share of trials whose winner is within 0.1 diameter of T_gt (ADD, ADD-S); one visit's numbers", "rows": []}
+    if os.path.exists(a.out):
+        with open(a.out) as f:
+            data = json.load(f)
+    key = (a.example, a.post)
+    data["rows"] = [r for r in data["rows"] if (r["example"], "refined_winners" in r) != key] + [row]
+    os.makedirs(os.path.dirname(a.out), exist_ok=True)
+    with open(a.out, "w") as f:
+        json.dump(data, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
