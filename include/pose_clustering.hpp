@@ -1,6 +1,7 @@
 // pose_clustering.hpp -- the public surface of the reference's include/pose_clustering.hpp:9-28 on the C ABI of
 // libstocs_hip.so (stocs_cluster_poses, stocs_icp_point_to_plane).  PCL cloud pointers become std::vector<Point3D>,
-// Eigen types the stocs:: ones of stocs.hpp; trimmed_icp is declared but never defined in the reference and is not offered.
+// Eigen types the stocs:: ones of stocs.hpp; trimmed_icp is declared but never defined in the reference and is not offered on clouds
+// (the trimmed, normal-gated refinement of pose hypotheses on the estimator is stocs_estimator::refine_pose_candidates_robust).
 #ifndef STOCS_POSE_CLUSTERING_HPP
 #define STOCS_POSE_CLUSTERING_HPP
 

@@ -605,6 +605,44 @@ public:
         return out;
     }
 
+    // The robust form of refine_pose_candidates (stocs_refine_poses_robust; the reference declares clustering::trimmed_icp and never
+    // defines it): per iteration only the nearest keep_ratio of the candidate pairs enter the system, and with max_normal_deg >= 0 a
+    // pair whose normals differ by more than that angle is no candidate (< 0: no gate; the angle becomes a cosine once:
+    // (float)cos((double)deg * pi / 180)).  keep_ratio = 1 and no gate: bitwise refine_pose_candidates.  Same frame conversion, ownership
+    // and error reporting as refine_pose_candidates; the two calls share one result store.
+    std::vector<PoseCandidate*> refine_pose_candidates_robust(const std::vector<PoseCandidate*>& hypotheses, int max_iterations = 5,
+                                                              float max_correspondence_distance = 0.035f, float keep_ratio = 0.7f,
+                                                              float max_normal_deg = 30.0f) {
+        refined_store_.clear();
+        std::vector<PoseCandidate*> out;
+        const int n = (int)hypotheses.size();
+        float cs[3], cm[3];
+        stocs_get_centroids(ctx_, cs, cm);
+        std::vector<float> T((size_t)n * 16), P((size_t)n * 16), l((size_t)n);
+        for (int i = 0; i < n; ++i) {
+            const float* src = hypotheses[(size_t)i]->transform.data();
+            float* dst = &T[(size_t)i * 16];
+            std::memcpy(dst, src, 64);
+            for (int r = 0; r < 3; ++r)
+                dst[12 + r] = (float)(((double)src[12 + r] - (double)cs[r]) +
+                                      (((double)src[r] * (double)cm[0] + (double)src[4 + r] * (double)cm[1]) + (double)src[8 + r] * (double)cm[2]));
+        }
+        stocs_refine_robust_params prm;
+        prm.max_iterations = max_iterations; prm.max_correspondence_distance = max_correspondence_distance; prm.keep_ratio = keep_ratio;
+        prm.min_normal_cos = max_normal_deg >= 0.0f ? (float)std::cos((double)max_normal_deg * 3.141592653589793 / 180.0) : -2.0f;
+        if (n > 0 && stocs_refine_poses_robust(ctx_, T.data(), n, NULL, 0, &prm, NULL, P.data(), l.data(), NULL, NULL, NULL) != STOCS_OK) {
+            *log_ << "refine_pose_candidates_robust failed: " << stocs_last_error() << std::endl;
+            return out;
+        }
+        for (int i = 0; i < n; ++i) {
+            MatrixType m;
+            std::memcpy(m.data(), &P[(size_t)i * 16], 64);
+            refined_store_.emplace_back(new PoseCandidate(m, l[(size_t)i], (float)hypotheses[(size_t)i]->base_index));
+            out.push_back(refined_store_.back().get());
+        }
+        return out;
+    }
+
     // Tracking across frames (stocs_track_poses; no reference counterpart): the defaults of a local search around a prior pose
     // (model_matching_amd/estimator.py TRACK_DEFAULTS, chosen by tools/track_time.py's sweep)
     static stocs_track_params default_track_params() {

@@ -431,6 +431,56 @@ int stocs_refine_poses(stocs_ctx* ctx, const float* T16_centred_in, int n, const
 int stocs_refine_detail(stocs_ctx* ctx, const float* T16_centred, const int32_t* src_idx, int n_src, float max_correspondence_distance,
                         int32_t* match, uint8_t* counted, double* sums28);
 
+/* ---- robust pose refinement on the context: stocs_refine_poses with two rejectors, a trim (keep the nearest share of the pairs)
+ * and a normal gate (drop a pair whose normals disagree).  No reference counterpart: pose_clustering.hpp:24-28 declares
+ * clustering::trimmed_icp and never defines it.  Everything not named here is exactly stocs_refine_poses: the source, the walk and
+ * its tie rule, the double threshold test, the linearised system, the update and the freeze rules, T U^-1, the camera form, the LCP
+ * rescoring, one synchronisation per call.  Per hypothesis and iteration:
+ *   match      the plain walk's model index, -1 when there is none.
+ *   candidate  a matched pair that passes the double distance test and, with the gate on, the normal test: ns the scene point's unit
+ *              normal as the context holds it (the base scene's, never an instance-mode override), n the matched model normal; in
+ *              double, one operation at a time, left to right: q = Tinv_R ns, g = U_R q, c = (g.x n.x + g.y n.y) + g.z n.z; the
+ *              pair passes iff c >= (double)min_normal_cos.  g is not normalised (unit to rounding for a rigid hypothesis).
+ *   rank       a candidate's rank word is the bit pattern of the float squared distance the walk minimised; any other source
+ *              position has 0xFFFFFFFF.
+ *   trim       n_cand = the number of candidates, k = floor((double)keep_ratio * n_cand) (exact).  KEPT are the k candidates smallest
+ *              by (rank word, position i in the source list): on equal distance the lowest source position wins.  Integer set logic,
+ *              independent of batch, launch shape and reduction order.
+ *   sums       over the kept pairs only, by the plain kernel's expressions in the plain kernel's reduction order; the count that
+ *              decides the freeze (< 6) is k.  With keep_ratio == 1 and the gate off every output is BITWISE stocs_refine_poses's.
+ * Out (any pointer may be NULL): as stocs_refine_poses; n_corr_out = k of the last evaluated iteration, n_cand_out its n_cand.
+ * Results are bitwise independent of the batch.  n == 0: no-op; max_iterations == 0: inputs returned unchanged and scored, counts 0.
+ * STOCS_ERR_INVALID: as stocs_refine_poses, and a NULL params pointer, a keep_ratio outside (0, 1] or NaN, a min_normal_cos > 1 or
+ * NaN, and a workspace demand of n * n_src * 8 bytes above STOCS_REFINE_ROBUST_MAX_WORKSPACE_BYTES (n_src: the source size, every
+ * scene point without src_idx; checked for every keep_ratio, though keep_ratio == 1 stores no rank words).  The workspace is grow-only
+ * and freed with the context: a repeated call allocates nothing.  No host round trip between iterations. ---- */
+#define STOCS_REFINE_ROBUST_MAX_WORKSPACE_BYTES 1073741824 /* 1 GiB */
+typedef struct stocs_refine_robust_params {
+    int32_t max_iterations;               /* >= 0 */
+    float   max_correspondence_distance;  /* m, > 0 and finite */
+    float   keep_ratio;                   /* in (0, 1]: share of the candidate pairs kept, nearest first */
+    float   min_normal_cos;               /* in [-1, 1]: gate on; < -1: gate off; > 1 or NaN: invalid */
+} stocs_refine_robust_params;
+
+int stocs_refine_poses_robust(stocs_ctx* ctx, const float* T16_centred_in, int n, const int32_t* src_idx, int n_src,
+                              const stocs_refine_robust_params* params, float* T16_centred_out, float* pose16_camera_out, float* lcp_out,
+                              int32_t* n_corr_out, int32_t* n_cand_out, int32_t* iterations_out);
+
+/* Test and diagnosis facility of the robust refinement, as stocs_refine_detail is of the plain one: the FIRST evaluation (U = I) of
+ * ONE hypothesis, always by the match, select and kept-accumulation kernels (keep_ratio == 1 included).  Per source position i:
+ * match[i] as stocs_refine_detail; rank[i] the rank word; candidate[i] = (rank[i] != 0xFFFFFFFF); kept[i]: 1 when the pair entered
+ * the sums.  *k_out, *n_cand_out: as defined above.  sums28 (k_out, n_cand_out, sums28 may be NULL): the 28 sums over the kept pairs
+ * as the solve step forms them; no solve.  A hypothesis whose linear part is singular or not finite: match -1, rank 0xFFFFFFFF,
+ * flags, counts and sums 0.  Argument checking as stocs_refine_poses_robust (match, candidate, kept and rank must not be NULL when
+ * there are source points; max_iterations is checked and not used).  Changes no state but the workspace; synchronises. */
+int stocs_refine_robust_detail(stocs_ctx* ctx, const float* T16_centred, const int32_t* src_idx, int n_src,
+                               const stocs_refine_robust_params* params, int32_t* match, uint8_t* candidate, uint8_t* kept, uint32_t* rank,
+                               int32_t* k_out, int32_t* n_cand_out, double* sums28);
+
+/* The robust refinement's device workspace as it stands (address NULL and 0 bytes before the first call): a repeated call of the same
+ * or a smaller size must leave both unchanged.  Either pointer may be NULL.  No device work. */
+int stocs_refine_robust_workspace(stocs_ctx* ctx, void** address, uint64_t* bytes);
+
 /* ---- pose tracking across frames: a local search around n prior poses on the context's current scene (no reference counterpart;
  * the reference detects from scratch on every frame).  Priors are CAMERA-frame poses (column-major, as stocs_get_candidates and the
  * pose file give them: only the camera frame carries over from frame to frame).  Each is taken to the centred frame on the host, in

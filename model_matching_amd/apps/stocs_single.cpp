@@ -16,6 +16,10 @@
 // common options: --seed N --bases 100 --max-sets 200 --out FILE --dbg DIR --cluster 1 --exact-ties 1
 // --refine N (with --cluster 1): N point-to-plane iterations on every clustered hypothesis (clustering::point_to_plane_icp,
 // pose_clustering.cpp:123-140, batched: stocs_refine_poses); the best refined pose goes to <out>.refined in the same format.
+// --trim r [--normal-gate deg] (with --cluster 1 --refine N, without --trials): the robust refinement (stocs_refine_poses_robust): per
+// iteration the nearest share r in (0, 1] of the pairs is kept, and a pair whose normals differ by more than deg is dropped (without
+// --normal-gate: no gate).  Recommended: --trim 0.7 --normal-gate 30 -- on cluttered frames the plain refinement is pulled off the
+// object; either rejector alone helps, only both hold on sparse clouds.  Without --trim the output is the plain one's.
 // --trials N --cluster 1 [--refine K]: the clustering (and refinement) of every trial runs inside the batch, on the device
 // (stocs_run_trials_post); per-trial cluster / refined lines, the best refined pose of the best trial to <out>.refined.
 // --track <pose file> [--track-min-lcp x] (single object): track from a prior pose in the format this driver writes (12 floats, 3x4
@@ -78,6 +82,7 @@ static int maximum_congruent_sets = 200;
 static std::vector<float> cam_intrinsics = {1066.778f, 312.986f, 1067.487f, 241.310f};  // YCB
 static float depth_scale = 1 / 10000.0f;
 static int image_width = 640, image_height = 480;
+static float g_trim = 0.0f, g_gate_deg = -1.0f;   // --trim r [--normal-gate deg]: the robust refinement (0: the plain one; < 0: no gate)
 
 static bool read_stcl(const std::string& path, std::vector<float>& pos, std::vector<float>& nrm, std::vector<float>* prob, std::vector<int32_t>* pixel) {
     FILE* f = fopen(path.c_str(), "rb");
@@ -285,7 +290,8 @@ static int run_search(stocs::stocs_estimator& stocs_ptr, std::ostream& os, const
             os << "clustered hypotheses: " << kept.size() << std::endl;
             for (size_t i = 0; i < kept.size(); ++i) os << "  cluster " << i << ": base " << kept[i]->base_index << " lcp " << kept[i]->lcp << std::endl;
             if (n_refine > 0) {
-                const std::vector<PoseCandidate*> ref = stocs_ptr.refine_pose_candidates(kept, n_refine);
+                const std::vector<PoseCandidate*> ref = g_trim > 0.0f ? stocs_ptr.refine_pose_candidates_robust(kept, n_refine, 0.035f, g_trim, g_gate_deg)
+                                                                      : stocs_ptr.refine_pose_candidates(kept, n_refine);
                 PoseCandidate* rb = NULL;
                 for (size_t i = 0; i < ref.size(); ++i) {
                     os << "  refined " << i << ": base " << ref[i]->base_index << " lcp " << kept[i]->lcp << " -> " << ref[i]->lcp << std::endl;
@@ -541,7 +547,7 @@ int main(int argc, char** argv) {
     std::string edge_path, out_path, dbg_dir, track_path, gt_path;
     float track_min_lcp = 0.02f;
     int do_cluster = 0, n_trials = 0, exact_ties = 0, n_refine = 0, depth_check = 0;
-    bool do_instances = false, do_masks = false;
+    bool do_instances = false, do_masks = false, have_trim = false, have_gate = false;
     SceneSelectOptions scene_opt = {false, false, 0};
     stocs_instance_params inst_prm = stocs::stocs_estimator::default_instance_params();
     uint64_t seed = 1;
@@ -559,6 +565,8 @@ int main(int argc, char** argv) {
         else if (k == "--dbg") dbg_dir = v;
         else if (k == "--cluster") do_cluster = atoi(v.c_str());
         else if (k == "--refine") n_refine = atoi(v.c_str());   // iterations of the refinement of the clustered hypotheses (0: off)
+        else if (k == "--trim") { g_trim = (float)atof(v.c_str()); have_trim = true; }   // robust refinement: share of the pairs kept per iteration
+        else if (k == "--normal-gate") { g_gate_deg = (float)atof(v.c_str()); have_gate = true; }   // and the largest angle between a pair's normals
         else if (k == "--trials") n_trials = atoi(v.c_str());   // N independent runs (seeds seed, seed + 1, ...) in one set of GPU launches; the best one is written
         else if (k == "--exact-ties") exact_ties = atoi(v.c_str());   // 1: the reference kd-tree's answer on exact distance ties (set_exact_ties)
         else if (k == "--track") track_path = v;   // track from this pose file; detection when the tracked lcp is below --track-min-lcp
@@ -583,6 +591,11 @@ int main(int argc, char** argv) {
     }
 
     if (n_refine < 0 || (n_refine > 0 && !do_cluster)) { std::cerr << "--refine N needs N >= 0 and --cluster 1" << std::endl; return -1; }
+    if ((have_trim || have_gate) && (!have_trim || !(g_trim > 0.0f && g_trim <= 1.0f) || (have_gate && !(g_gate_deg >= 0.0f && g_gate_deg <= 180.0f)) || n_refine <= 0 ||
+                                     n_trials > 0 || !track_path.empty())) {
+        std::cerr << "--trim r [--normal-gate deg] needs r in (0, 1], deg in [0, 180], --cluster 1 --refine N, and neither --trials nor --track" << std::endl;
+        return -1;
+    }
 
     if (depth_check && (clouds || n_trials <= 0 || !do_cluster || !track_path.empty() || a2.find(',') != std::string::npos)) {
         std::cerr << "--depth-check needs a scene directory, a single object, --trials N and --cluster 1" << std::endl;

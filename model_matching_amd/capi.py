@@ -55,6 +55,10 @@ class TrackResult(C.Structure):
                 ("n_correspondences", C.c_int32), ("iterations", C.c_int32)]
 
 
+class RefineRobustParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("max_correspondence_distance", C.c_float), ("keep_ratio", C.c_float), ("min_normal_cos", C.c_float)]
+
+
 class DepthParams(C.Structure):
     _fields_ = [("tolerance", C.c_float), ("class_threshold", C.c_float), ("self_occlusion", C.c_int32), ("cell_px", C.c_int32),
                 ("occlusion_margin", C.c_float)]
@@ -180,6 +184,10 @@ SIGNATURES = {
     "stocs_icp_point_to_plane": (C.c_int, [_fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_float, C.c_int, _fp, _intp]),
     "stocs_refine_poses": (C.c_int, [_vp, _fp, C.c_int, _ip, C.c_int, C.c_int, C.c_float, _fp, _fp, _fp, _ip, _ip]),
     "stocs_refine_detail": (C.c_int, [_vp, _fp, _ip, C.c_int, C.c_float, _ip, _u8p, C.POINTER(C.c_double)]),
+    "stocs_refine_poses_robust": (C.c_int, [_vp, _fp, C.c_int, _ip, C.c_int, C.POINTER(RefineRobustParams), _fp, _fp, _fp, _ip, _ip, _ip]),
+    "stocs_refine_robust_detail": (C.c_int, [_vp, _fp, _ip, C.c_int, C.POINTER(RefineRobustParams), _ip, _u8p, _u8p, C.POINTER(C.c_uint32), _ip, _ip,
+                                             C.POINTER(C.c_double)]),
+    "stocs_refine_robust_workspace": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "stocs_track_poses": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(TrackParams), C.POINTER(TrackResult)]),
     "stocs_track_get_round": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, C.c_int, _intp]),
     "stocs_ctx_set_frame": (C.c_int, [_vp, C.POINTER(Camera), C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),

@@ -58,6 +58,7 @@ struct RefineState {
     RefineGrid g;
     DevBlock work;   // hypotheses | T in | source indices | partials | outputs (grow-only)
     DevBlock detail; // stocs_refine_detail: match | counted | sums (grow-only)
+    DevBlock robust; // refine_robust.h: rank words | model indices | select results of stocs_refine_poses_robust (grow-only)
 };
 
 __global__ __launch_bounds__(256) void refine_keys_kernel(const float4* __restrict__ mpos, int nM, float ox, float oy, float oz, float inv_h, int nx, int ny,
@@ -497,7 +498,7 @@ using namespace stocs;
 extern "C" void stocs_internal_free_refine(stocs_ctx* c) {
     if (!c || !c->refine) return;
     RefineState* S = (RefineState*)c->refine;
-    S->g.mem.free(); S->work.free(); S->detail.free();
+    S->g.mem.free(); S->work.free(); S->detail.free(); S->robust.free();
     delete S;
     c->refine = NULL;
 }
@@ -614,3 +615,6 @@ extern "C" int stocs_refine_detail(stocs_ctx* c, const float* T16_in, const int3
     if (sums28) STOCS_HIP_CHECK(hipMemcpy(sums28, d_sums, 28 * 8, hipMemcpyDeviceToHost));
     return STOCS_OK;
 }
+
+// the trimmed, normal-gated form (stocs_refine_poses_robust, stocs_refine_robust_detail): its own kernels on this file's state
+#include "refine_robust.h"

@@ -6,6 +6,7 @@ from __future__ import annotations
 
 import atexit
 import ctypes as C
+import math
 import weakref
 
 import numpy as np
@@ -302,6 +303,54 @@ class StocsEstimator:
         capi.check(self.L.stocs_refine_detail(self.h, pT, pidx, 0 if idx is None else n, max_correspondence_distance, match.ctypes.data_as(capi._ip),
                                               counted.ctypes.data_as(capi._u8p), s28.ctypes.data_as(C.POINTER(C.c_double)) if sums else None))
         return match[:n], counted[:n], s28
+
+    @staticmethod
+    def robust_params(max_iterations=5, max_correspondence_distance=0.035, keep_ratio=0.7, max_normal_deg=30.0):
+        """stocs_refine_robust_params from the Python arguments.  max_normal_deg -> min_normal_cos ONCE: the cosine of the angle in
+        double (math.cos(deg * pi / 180)), rounded to float when it enters the struct -- the conversion include/stocs.hpp's
+        refine_pose_candidates_robust makes; None turns the gate off (min_normal_cos = -2).  A caller who needs an exact cosine (-1, 0,
+        1 at the gate's edges) passes a capi.RefineRobustParams of their own."""
+        mc = -2.0 if max_normal_deg is None else math.cos(float(max_normal_deg) * math.pi / 180.0)
+        return capi.RefineRobustParams(int(max_iterations), float(max_correspondence_distance), float(keep_ratio), mc)
+
+    def refine_poses_robust(self, T16, max_iterations=5, max_correspondence_distance=0.035, keep_ratio=0.7, max_normal_deg=30.0, src_idx=None, params=None):
+        """Trimmed, normal-gated point-to-plane refinement of n centred-frame hypotheses (stocs_refine_poses_robust): per iteration
+        the nearest keep_ratio of the candidate pairs enter the system, and a pair whose normals differ by more than max_normal_deg
+        (None: no gate; converted as robust_params documents) is no candidate.  params: a capi.RefineRobustParams that replaces the
+        four scalars.  -> (T16_refined (n, 16), pose16_camera (n, 16), lcp (n,), n_corr (n,) kept pairs, n_cand (n,), iterations (n,))."""
+        T, pT = capi.f32(T16)
+        n = T.size // 16
+        idx, pidx = (None, None) if src_idx is None else capi.i32(src_idx)
+        prm = params if params is not None else self.robust_params(max_iterations, max_correspondence_distance, keep_ratio, max_normal_deg)
+        To = np.zeros((n, 16), np.float32); Po = np.zeros((n, 16), np.float32); lcp = np.zeros(n, np.float32)
+        nc = np.zeros(n, np.int32); ncand = np.zeros(n, np.int32); it = np.zeros(n, np.int32)
+        capi.check(self.L.stocs_refine_poses_robust(self.h, pT, n, pidx, 0 if idx is None else len(idx), C.byref(prm), To.ctypes.data_as(capi._fp),
+                                                    Po.ctypes.data_as(capi._fp), lcp.ctypes.data_as(capi._fp), nc.ctypes.data_as(capi._ip),
+                                                    ncand.ctypes.data_as(capi._ip), it.ctypes.data_as(capi._ip)))
+        return To, Po, lcp, nc, ncand, it
+
+    def refine_robust_detail(self, T16, max_correspondence_distance=0.035, keep_ratio=0.7, max_normal_deg=30.0, src_idx=None, params=None):
+        """The robust refinement's first evaluation of one centred-frame hypothesis (stocs_refine_robust_detail; arguments as
+        refine_poses_robust) -> dict: match (n_src,) model index or -1, candidate, kept (n_src,) uint8, rank (n_src,) uint32 (the bits
+        of the float squared distance, 0xFFFFFFFF for a non-candidate), k, n_cand, sums28 (28,) float64 over the kept pairs."""
+        T, pT = capi.f32(T16)
+        assert T.size == 16
+        idx, pidx = (None, None) if src_idx is None else capi.i32(src_idx)
+        n = self.nS if idx is None else len(idx)
+        prm = params if params is not None else self.robust_params(1, max_correspondence_distance, keep_ratio, max_normal_deg)
+        m = max(n, 1)
+        match = np.zeros(m, np.int32); cand = np.zeros(m, np.uint8); kept = np.zeros(m, np.uint8); rank = np.zeros(m, np.uint32)
+        k = C.c_int32(0); ncand = C.c_int32(0); s28 = np.zeros(28, np.float64)
+        capi.check(self.L.stocs_refine_robust_detail(self.h, pT, pidx, 0 if idx is None else n, C.byref(prm), match.ctypes.data_as(capi._ip),
+                                                     cand.ctypes.data_as(capi._u8p), kept.ctypes.data_as(capi._u8p), rank.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                                     C.byref(k), C.byref(ncand), s28.ctypes.data_as(C.POINTER(C.c_double))))
+        return dict(match=match[:n], candidate=cand[:n], kept=kept[:n], rank=rank[:n], k=int(k.value), n_cand=int(ncand.value), sums28=s28)
+
+    def refine_robust_workspace(self):
+        """(address, bytes) of the robust refinement's device workspace (stocs_refine_robust_workspace)."""
+        p = C.c_void_p(); b = C.c_uint64(0)
+        capi.check(self.L.stocs_refine_robust_workspace(self.h, C.byref(p), C.byref(b)))
+        return int(p.value or 0), int(b.value)
 
     def cluster_trials_device(self, poses16, lcp, cand_off, best_score, acceptable_fraction, maximum_pose_count, min_distance, min_angle, sym):
         """The device clustering of trial batches on given candidates (stocs_cluster_trials_device) -> (out_off (n_trials + 1,), out_cnt
