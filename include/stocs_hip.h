@@ -228,6 +228,12 @@ int stocs_lcp_detail(stocs_ctx* ctx, const float* T16_centred_host, int32_t* hit
  * records a pose really needs, 28 bytes each) and how many of those passed the normal test of :1028-1032 (*counted, may be NULL).
  * Runs the per-point detail form of the scoring kernel in chunks; synchronises. */
 int stocs_lcp_hit_count(stocs_ctx* ctx, const void* d_T16, int n, int64_t* hits, int64_t* counted);
+/* test aid for the normal-cone gate of the queue-fed scoring kernel ("lcp_normal_gate"; no reference counterpart): over n
+ * device-resident transforms, out[0] = the (candidate, model point) queries that land in a non-empty cell of the scene grid and
+ * survive its sub-cell mask, out[1] = those of them the gate rules out, out[2] = the ruled-out ones that the per-point detail form
+ * of the scoring kernel reports as counted -- 0, or the gate is wrong.  A plain counting kernel, one lane per query, that calls
+ * the scoring kernel's own gate function; on a grid without cones out[1] is 0.  Runs the detail form in chunks; synchronises. */
+int stocs_lcp_gate_count(stocs_ctx* ctx, const void* d_T16, int n, int64_t out[3]);
 /* compute_best_transform (stocs.cpp:982-1004): score every stored candidate, arg-max with first
  * maximum winning; best_idx = -1 and best_lcp = 0 when every score is 0 */
 int stocs_verify_all(stocs_ctx* ctx, float* best_lcp, int* best_idx, float* best_pose16_camera);
@@ -805,6 +811,11 @@ int stocs_scene_select(stocs_ctx* ctx, const void* d_rows, int n, int width, int
  *   "device: ..." steps; 0 (default; STOCS_DEVICE_CLOCK=1 in the environment turns it on at context creation) = the host's steps only --
  *   an event between two kernels of a stream costs ~5 us of idle queue on this runtime, nine of them 45 us of a 600 us call.
  * "lcp_flat": 1 (default) = sparse scenes address a flat copy of the cell table (one look-up per query), 0 = brick look-ups.
+ * "lcp_normal_gate": 1 (default) = the cell words of the scene grid carry a cone of their list's scene normals, and on sparse
+ *   lists the queue-fed scoring kernel drops a query before its list is touched when no normal
+ *   inside the cell's cone can pass the 30-degree test against the rotated model normal; 0 = the forms without the gate; any
+ *   other value is STOCS_ERR_INVALID.  A dropped query is one the ungated kernel would not count: same scores, bitwise.  The
+ *   per-point detail forms and the cross-check kernels (lcp_variant 0, 31, exact_ties) never gate.
  * "lcp_split": 1 (default) = four wavefronts share a candidate's model points, 0 = one wavefront per candidate.  Scores are
  *   accumulated as integers, so neither option changes a single bit of them.
  * "lcp_order": 0 = candidates in batch order, 1 (default) = big batches against scenes whose lists do not stay in the caches

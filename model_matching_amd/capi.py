@@ -159,6 +159,7 @@ SIGNATURES = {
     "stocs_score_best_device": (C.c_int, [_vp, _vp, C.c_int, _vp, C.c_uint32, C.POINTER(C.c_uint64)]),
     "stocs_lcp_detail": (C.c_int, [_vp, _fp, _ip, _u8p]),
     "stocs_lcp_hit_count": (C.c_int, [_vp, _vp, C.c_int, _i64p, _i64p]),
+    "stocs_lcp_gate_count": (C.c_int, [_vp, _vp, C.c_int, _i64p]),
     "stocs_verify_all": (C.c_int, [_vp, _fp, _intp, _fp]),
     "stocs_run_trials": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int, C.c_float, C.c_int, C.c_int, C.POINTER(TrialResult)]),
     "stocs_trials_get_bases": (C.c_int, [_vp, C.c_int, _ip, _fp, _ip, C.c_int, _intp]),

@@ -556,6 +556,7 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
     c->device_clock = (getenv("STOCS_DEVICE_CLOCK") && atoi(getenv("STOCS_DEVICE_CLOCK")) != 0) ? 1 : 0;
     c->lcp_split = 1;
     c->lcp_flat = getenv("STOCS_LCP_FLAT") ? atoi(getenv("STOCS_LCP_FLAT")) : 1;
+    c->lcp_normal_gate = 1;
     c->lcp_order = getenv("STOCS_LCP_ORDER") ? atoi(getenv("STOCS_LCP_ORDER")) : 1;
     c->exact_ties = 0; c->kd_ready = false; c->d_kd_nodes = NULL; c->d_kd_pts = NULL; c->d_ties = NULL; c->ties_started = false;
     c->cdf_n = 0; c->prior_epoch = 1; c->cdf_epoch = 0;
@@ -640,6 +641,7 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
         // the sorted positions are padded to whole 64-point steps with NaN: the scan kernels load and transform a step without
         // bounds checks, and a NaN query matches nothing (every comparison of its distances fails)
         as.resize((size_t)n_patch * 64 + 64, make_float4(NAN, NAN, NAN, 0.f));
+        bs.resize((size_t)n_patch * 64 + 64, make_float4(0.f, 0.f, 0.f, 0.f));   // the gated queue forms load a step's normals next to its positions
         if (!rc) rc = upload(&c->d_mpos, a.data(), a.size());
         if (!rc) rc = upload(&c->d_mnrm, b.data(), b.size());
         if (!rc) rc = upload(&c->d_munit, u.data(), u.size());

@@ -24,6 +24,7 @@
 #include <algorithm>
 #include <vector>
 
+#include "normal_cone.h"
 #include "prims.h"
 #include "stocs_ctx.h"
 
@@ -154,7 +155,8 @@ __global__ __launch_bounds__(256) void cell_words_kernel(GridGeom G, int div, co
                                                          const uint32_t* __restrict__ cell_brick, const uint32_t* __restrict__ list_off,
                                                          uint32_t n_cells, uint32_t n_inc, const uint32_t* __restrict__ vals,
                                                          const float4* __restrict__ spos, int32_t* __restrict__ top, uint4* __restrict__ cells,
-                                                         uint4* __restrict__ flat, const uint32_t* __restrict__ kept) {
+                                                         uint4* __restrict__ flat, const uint32_t* __restrict__ kept,
+                                                         const uint32_t* __restrict__ rank, const float4* __restrict__ snrmw, int cones) {
     const uint32_t c = blockIdx.x * 4 + (threadIdx.x >> 6);
     const int s = threadIdx.x & 63;
     if (c >= n_cells) return;   // whole wavefront
@@ -187,9 +189,57 @@ __global__ __launch_bounds__(256) void cell_words_kernel(GridGeom G, int div, co
         const unsigned long long m = __ballot(any);
         mlo = (uint32_t)(m & 0xFFFFFFFFull); mhi = (uint32_t)(m >> 32);
     }
+    // normal cone of the cell's stored list (normal_cone.h): the lanes take the list's entries in turn.  Axis = the mean direction,
+    // quantised; the half-angle is then measured against the axis as the kernels decode it, in double, and rounded outwards
+    uint32_t cone = 0u;
+    if (cones) {
+        // a lane's first entry stays in registers for the second pass (lists beyond 64 entries are read again); the axis needs no rigour
+        // (float sums: any axis is a valid one), the angle against it does
+        float4 n0 = make_float4(0.f, 0.f, 0.f, 0.f);
+        bool have0 = false, bad = false;
+        float sx = 0.f, sy = 0.f, sz = 0.f;
+        for (uint32_t k = (uint32_t)s; k < cnt; k += 64) {
+            if (rank && rank[first + k] == 0xFFFFFFFFu) continue;   // pruned away: not in the stored list
+            const float4 nf = snrmw[vals[first + k]];
+            if (k < 64) { n0 = nf; have0 = true; }
+            const double n2 = (double)nf.x * nf.x + (double)nf.y * nf.y + (double)nf.z * nf.z;
+            if (!(n2 >= 0.99980001 && n2 <= 1.00020001)) { bad = true; continue; }   // off unit length by more than 1e-4 (NaN included)
+            sx += nf.x; sy += nf.y; sz += nf.z;
+        }
+        for (int off = 32; off > 0; off >>= 1) { sx += __shfl_xor(sx, off, 64); sy += __shfl_xor(sy, off, 64); sz += __shfl_xor(sz, off, 64); }
+        const double l1 = fabs((double)sx) + fabs((double)sy) + fabs((double)sz);
+        if (!__any(bad) && l1 > 1.0e-9) {
+            double px = sx / l1, py = sy / l1;
+            if (sz < 0) { const double qx = (1.0 - fabs(py)) * (px >= 0 ? 1.0 : -1.0), qy = (1.0 - fabs(px)) * (py >= 0 ? 1.0 : -1.0); px = qx; py = qy; }
+            const double amax = (double)STOCS_CONE_AXIS_MAX;
+            const uint32_t u8 = (uint32_t)fmin(fmax(floor((px * 0.5 + 0.5) * amax + 0.5), 0.0), amax);
+            const uint32_t v8 = (uint32_t)fmin(fmax(floor((py * 0.5 + 0.5) * amax + 0.5), 0.0), amax);
+            float fx, fy, fz;
+            cone_axis(cone_pack(u8, v8, 0u), fx, fy, fz);
+            const double o2 = (double)fx * fx + (double)fy * fy + (double)fz * fz;
+            // cos of the angle to the decoded axis, in double, as a float rounded DOWN (a wider cone); minimum over the list
+            auto cos_down = [&](const float4 nf) {
+                const double n2 = (double)nf.x * nf.x + (double)nf.y * nf.y + (double)nf.z * nf.z;
+                return __double2float_rd(((double)nf.x * fx + (double)nf.y * fy + (double)nf.z * fz) / sqrt(n2 * o2));
+            };
+            float cmin = 1.0f;
+            if (have0) cmin = fminf(cmin, cos_down(n0));
+            for (uint32_t k = (uint32_t)s + 64; k < cnt; k += 64) {
+                if (rank && rank[first + k] == 0xFFFFFFFFu) continue;
+                cmin = fminf(cmin, cos_down(snrmw[vals[first + k]]));
+            }
+            for (int off = 32; off > 0; off >>= 1) cmin = fminf(cmin, __shfl_xor(cmin, off, 64));
+            if (cmin > 0.0f) {   // below 90 degrees
+                const double cm = (double)cmin;
+                const double sd = sqrt(fmax((1.0 - cm) * (1.0 + cm), 0.0));
+                const uint32_t cls = (uint32_t)floor(sd * (double)STOCS_CONE_SIN_STEPS + 1.0e-4) + 1u;   // sin(half-angle) < cls / 16, double rounding included
+                if (cls <= STOCS_CONE_MAX_CLASS) cone = cone_pack(u8, v8, cls);
+            }
+        }
+    }
     if (s == 0) {
         top[brick] = (int32_t)b;   // every cell of the brick writes the same value
-        const uint4 w = make_uint4(list_off[c], kept ? kept[c] : cnt, mlo, mhi);   // (pruned lists: the mask above still comes from every point within r)
+        const uint4 w = make_uint4(list_off[c], (kept ? kept[c] : cnt) | cone, mlo, mhi);   // (pruned lists: the mask above still comes from every point within r)
         cells[(size_t)b * 512 + local] = w;
         if (flat) {
             const int bx = (int)(brick % (uint64_t)G.nbx), by = (int)((brick / (uint64_t)G.nbx) % (uint64_t)G.nby), bz = (int)(brick / ((uint64_t)G.nbx * (uint64_t)G.nby));
@@ -423,7 +473,7 @@ int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
     g.nx = n[0]; g.ny = n[1]; g.nz = n[2];
     g.nbx = (n[0] + 7) / 8; g.nby = (n[1] + 7) / 8; g.nbz = (n[2] + 7) / 8;
     g.h = (float)h;
-    g.n_bricks = 0; g.n_entries = 0; g.avg_list_len = 0; g.has_nearest = false;
+    g.n_bricks = 0; g.n_entries = 0; g.avg_list_len = 0; g.has_nearest = false; g.has_cones = false;
     g.d_top = NULL; g.d_cells = NULL; g.d_list = NULL; g.d_chunk_r = NULL; g.d_flat = NULL;
     const int64_t n_top = (int64_t)g.nbx * g.nby * g.nbz;
     if (n_top > (int64_t)400 * 1000 * 1000) { set_error("scene extent too large for the brick grid"); return STOCS_ERR_INVALID; }
@@ -559,6 +609,8 @@ int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
     const unsigned long long n_kept = prune ? rb64[1] : (unsigned long long)n_inc;
     const size_t n_list = tail[0];
     if (tail[1] > 65535u) { set_error("more than 65535 scene points within epsilon of one grid cell"); return STOCS_ERR_INVALID; }
+    // normal cones above the 16-bit counts (normal_cone.h); STOCS_GRID_CONES=0: a grid without them (A/B runs, cross-checks)
+    g.has_cones = !(getenv("STOCS_GRID_CONES") && atoi(getenv("STOCS_GRID_CONES")) == 0);
     // ---- 4. cell words, top table, lists ----
     if ((rc = c->grid_mem.take(std::max<size_t>((size_t)n_bricks * 512, 1) * sizeof(uint4), (void**)&g.d_cells)) ||
         (rc = c->grid_mem.take(std::max<size_t>(n_list, 8) * sizeof(float4), (void**)&g.d_list)))
@@ -573,7 +625,8 @@ int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
     }
     hipLaunchKernelGGL(fill_list_kernel, dim3(grid_of(std::max<size_t>(n_list, 8))), dim3(256), 0, st, g.d_list, std::max<size_t>(n_list, 8));
     hipLaunchKernelGGL(cell_words_kernel, dim3((unsigned)((n_cells + 3) / 4)), dim3(256), 0, st, G, div, d_cell_first, d_cell_key, d_cell_brick, d_list_off, n_cells,
-                       (uint32_t)n_inc, d_vals_s, c->d_spos, g.d_top, g.d_cells, g.d_flat, (const uint32_t*)d_kept);
+                       (uint32_t)n_inc, d_vals_s, c->d_spos, g.d_top, g.d_cells, g.d_flat, (const uint32_t*)d_kept,
+                       (const uint32_t*)d_rank, (const float4*)c->d_snrmw, g.has_cones ? 1 : 0);
     hipLaunchKernelGGL(list_fill_kernel, dim3(grid_of(n_inc)), dim3(256), 0, st, d_cflag, d_cidx, d_cell_first, d_list_off, d_vals_s, n_inc, c->d_spos, g.d_list, (const uint32_t*)d_rank);
     STOCS_HIP_CHECK(hipGetLastError());
     if (prune && div > 1) {   // no sub-cell masks on grids finer than epsilon: the z word takes the distance bound (has_nearest)

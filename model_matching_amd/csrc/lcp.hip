@@ -22,7 +22,7 @@
 // queries that survive the sub-cell mask in a per-wave LDS ring and verifies them 16 at a time, four lanes per query
 // with two entries of a 128-byte list line each.
 //
-// Kernels: lcp_coopq_kernel (seven named switches, the table of its legal forms above it), lcp_coop_kernel (the per-step scan of dense
+// Kernels: lcp_coopq_kernel (eight named switches, the table of its legal forms above it), lcp_coop_kernel (the per-step scan of dense
 // scenes, a cross-check), lcp_kernel (a lane per query, a cross-check) and lcp_exact_kernel (exact_ties).  choose_lcp_form picks one,
 // launch_lcp_form is the only place that names their instantiations.  The forms that lost their A/B runs are listed in
 // DESIGN_HISTORY.md with the last commit that holds their code; a measurement build (make tools) adds the ablation bits only.
@@ -38,6 +38,7 @@
 #include <utility>
 
 #include "kdtree.h"
+#include "normal_cone.h"
 #include "prims.h"
 #include "stocs_ctx.h"
 
@@ -175,7 +176,8 @@ __global__ __launch_bounds__(256) void lcp_kernel(LcpArgs a, const float* __rest
             if (brick >= 0) {
                 const uint4 cw = a.cells[(size_t)brick * 512 + (((cz & 7) << 6) | ((cy & 7) << 3) | (cx & 7))];
                 float bd = a.sq_eps;
-                for (uint32_t k = 0; k < cw.y; ++k) {
+                const uint32_t cn = cw.y & STOCS_CONE_COUNT_MASK;   // (the bits above hold the cell's normal cone: normal_cone.h)
+                for (uint32_t k = 0; k < cn; ++k) {
                     const float4 s = a.list[cw.x + k];
                     const float dx = qx - s.x, dy = qy - s.y, dz = qz - s.z;
                     const float d = dx * dx + (dy * dy + dz * dz);
@@ -290,7 +292,7 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT)) void lcp_c
                     // sub-cell filter: no scene point within epsilon of this 1/4-cell => no neighbour possible
                     const int sb = ((int)((uz - fz) * 4.0f) << 4) | ((int)((uy - fy) * 4.0f) << 2) | (int)((ux - fx) * 4.0f);
                     const uint32_t mw = a.has_nearest ? 0xFFFFFFFFu : (sb < 32 ? cw.z : cw.w);   // (has_nearest: no mask on this grid, z holds a distance)
-                    off = cw.x; cnt = ((mw >> (sb & 31)) & 1u) ? cw.y : 0u;
+                    off = cw.x; cnt = ((mw >> (sb & 31)) & 1u) ? (cw.y & STOCS_CONE_COUNT_MASK) : 0u;
                     if (STOCS_ABLATE(a, 2)) cnt = cw.x == 0xFFFFFFF1u ? 1u : 0u;   // 2: look-ups done, nobody survives
                     const float ex = qx - (a.ox + ((float)cx + 0.5f) * a.h), ey = qy - (a.oy + ((float)cy + 0.5f) * a.h),
                                 ez = qz - (a.oz + ((float)cz + 0.5f) * a.h);
@@ -454,25 +456,32 @@ __device__ __forceinline__ bool lcp_patch_dead(const LcpArgs& a, const float4 sp
 //           wavefront: larger models, whose sub-patches the list does not hold, and every form that is not split.  Chosen on the
 //           host by the model size alone, so that a larger model runs exactly the code it ran before the list existed.
 //
-// The legal forms (29 instantiations; SHARED = 0 unless stated; the static_assert rejects every other):
+//   GATE    (scoring forms on sparse lists: DETAIL = 0, DENSE = 0; a grid with normal cones, lcp_normal_gate) a query whose cell's cone of
+//           scene normals cannot pass the normal test against the rotated model normal never joins the queue (normal_cone.h).  The
+//           detail forms keep every query: hit_out names the neighbour also when it is not counted.  Not for the split ring forms of
+//           CU = 16 (models beyond 8 192 points): they have 62-63 VGPRs without the gate and spill 12 to 20 bytes with it, wherever
+//           the model normal is requested.
+//
+// The legal forms (46 instantiations; SHARED = 0 and GATE = 0 unless stated; the static_assert rejects every other):
 //   scoring, sparse   DENSE = 0, SPLIT in {0, 1}, FLAT in {0, 1}, NEAR in {0, 1}, CU in {16, 64}         16 forms
 //   scoring, dense    DENSE = 1, SPLIT = 1, FLAT = 0, NEAR = 0, CU in {16, 64}                            2 forms
 //   shared list       every scoring form with SPLIT = 1 and CU = 16 once more with SHARED = 1            5 forms
 //                     (the dense queue form is always split, whatever lcp_split and the model size say)
+//   gated             every sparse scoring form but the split ring forms of CU = 16, once more with GATE = 1   17 forms
 //   detail, sparse    DENSE = 0, SPLIT = 0, FLAT = 0, NEAR in {0, 1}, CU in {16, 64}                      4 forms
 //   detail, dense     DENSE = 1, SPLIT = 0, FLAT = 0, NEAR = 0, CU in {16, 64}                            2 forms
 // ---------------------------------------------------------------------------------------------
 // entries of the workgroup-wide list of live sub-patches (SPLIT, CU = 16): the sub-patches of a model of up to 8 192 points
 constexpr int LCP_SHARED_LIVE = 512;
 
-constexpr bool lcp_queue_form_legal(bool detail, bool dense, bool split, bool flat, bool near, int cu, bool shared) {
-    return (cu == 16 || cu == 64) && (!shared || (split && cu == 16)) && (detail ? (!split && !flat && !(dense && near)) : (!dense || (split && !flat && !near)));
+constexpr bool lcp_queue_form_legal(bool detail, bool dense, bool split, bool flat, bool near, int cu, bool shared, bool gate) {
+    return !(gate && (detail || dense || (split && cu == 16 && !shared))) && (cu == 16 || cu == 64) && (!shared || (split && cu == 16)) && (detail ? (!split && !flat && !(dense && near)) : (!dense || (split && !flat && !near)));
 }
 
-template <bool DETAIL, bool DENSE, bool SPLIT, bool FLAT, bool NEAR, int CU, bool SHARED>
+template <bool DETAIL, bool DENSE, bool SPLIT, bool FLAT, bool NEAR, int CU, bool SHARED, bool GATE>
 __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lcp_coopq_kernel(LcpArgs a, const float* __restrict__ T16, float* __restrict__ out,
                                                         int n, int32_t* __restrict__ hit_out, uint8_t* __restrict__ cnt_out) {
-    static_assert(lcp_queue_form_legal(DETAIL, DENSE, SPLIT, FLAT, NEAR, CU, SHARED), "not one of the forms in the table above");
+    static_assert(lcp_queue_form_legal(DETAIL, DENSE, SPLIT, FLAT, NEAR, CU, SHARED, GATE), "not one of the forms in the table above");
     constexpr int WPB = lcp_waves_per_block(DETAIL, SPLIT);
     constexpr bool IDX = !DENSE;     // index-ordered lists: `<=` implements the tie rule (take_if_better)
     constexpr bool EARLY = DENSE;    // centre-sorted lists: line-by-line exit
@@ -665,7 +674,11 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
     // one 64-point step of this wavefront's candidate: model point p of slot i
     auto step = [&](const int i, const float4 p) {
         float qx = 0.f, qy = 0.f, qz = 0.f, qcentre = 0.f, nearest = 0.f;
-        uint32_t off = 0, cnt = 0;
+        uint32_t off = 0, cnt = 0, yw = 0;
+        // GATE: the model normal of the slot, requested in front of the look-up chain (the normals are padded like the positions)
+        float4 gnm = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (GATE) gnm = a.mnrm[i];
+        constexpr uint32_t cmask = STOCS_CONE_COUNT_MASK;   // the list length in the count word; the cell's normal cone sits above it
         // slots beyond the model hold NaN positions (ctx.hip): they run through the look-up like any other query and match nothing;
         // only the per-point outputs of the detail form need the bound
         if (!DETAIL || i < a.M) {
@@ -685,14 +698,15 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
                     if (!STOCS_ABLATE(a, 1))   // 1: no cell-word look-up at all
                         cw = a.flat[(uint32_t)((cz * a.ny + cy) * a.nx + cx)];
                     const uint32_t mw = sb < 32 ? cw.z : cw.w;
-                    off = cw.x; cnt = ((mw >> (sb & 31)) & 1u) ? cw.y : 0u;
+                    off = cw.x; yw = cw.y; cnt = ((mw >> (sb & 31)) & 1u) ? (cw.y & cmask) : 0u;
                     if (STOCS_ABLATE(a, 2)) cnt = cw.x == 0xFFFFFFF1u ? 1u : 0u;   // 2: look-up done, nobody survives
                 } else {
                     const int brick = a.top[((cz >> 3) * a.nby + (cy >> 3)) * a.nbx + (cx >> 3)];
                     if (brick >= 0) {
                         const uint4 cw = a.cells[(uint32_t)brick * 512u + (uint32_t)(((cz & 7) << 6) | ((cy & 7) << 3) | (cx & 7))];
-                        if ((EARLY || NEAR) && a.has_nearest) { off = cw.x; cnt = cw.y; nearest = __uint_as_float(cw.z); }   // no mask on these grids: z = distance bound
-                        else { const uint32_t mw = a.has_nearest ? 0xFFFFFFFFu : (sb < 32 ? cw.z : cw.w); off = cw.x; cnt = ((mw >> (sb & 31)) & 1u) ? cw.y : 0u; }
+                        yw = cw.y;
+                        if ((EARLY || NEAR) && a.has_nearest) { off = cw.x; cnt = cw.y & cmask; nearest = __uint_as_float(cw.z); }   // no mask on these grids: z = distance bound
+                        else { const uint32_t mw = a.has_nearest ? 0xFFFFFFFFu : (sb < 32 ? cw.z : cw.w); off = cw.x; cnt = ((mw >> (sb & 31)) & 1u) ? (cw.y & cmask) : 0u; }
                     }
                 }
             }
@@ -702,6 +716,14 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
                 // every listed point is at least `nearest` from the cell centre, hence at least nearest - |q - centre| from the query:
                 // beyond epsilon the list is not worth a look
                 if (a.has_nearest && nearest - qcentre > a.eps + a.bound_margin) cnt = 0;
+            }
+            // GATE: a query whose cell's normal cone cannot reach dot_lo against the rotated model normal would find its neighbour and
+            // then fail the normal test (cone_rules_out, normal_cone.h): it never joins the queue.  The rotation is the normal test's own
+            if (GATE && cnt) {
+                const float nx = t0 * gnm.x + (t4 * gnm.y + t8 * gnm.z);
+                const float ny = t1 * gnm.x + (t5 * gnm.y + t9 * gnm.z);
+                const float nz = t2 * gnm.x + (t6 * gnm.y + t10 * gnm.z);
+                if (cone_rules_out(yw, nx, ny, nz, a.dot_lo)) cnt = 0;
             }
             if (DETAIL && cnt == 0) {
                 const int orig = a.mperm[i];
@@ -943,7 +965,8 @@ __global__ __launch_bounds__(256) void lcp_exact_kernel(LcpArgs a, const float* 
             const int brick = a.top[((cz >> 3) * a.nby + (cy >> 3)) * a.nbx + (cx >> 3)];
             if (brick >= 0) {
                 const uint4 cw = a.cells[(size_t)brick * 512 + (((cz & 7) << 6) | ((cy & 7) << 3) | (cx & 7))];
-                for (uint32_t k = 0; k < cw.y; ++k) {
+                const uint32_t cn = cw.y & STOCS_CONE_COUNT_MASK;   // (the bits above hold the cell's normal cone: normal_cone.h)
+                for (uint32_t k = 0; k < cn; ++k) {
                     const float4 s = a.list[cw.x + k];
                     const float dx = qx - s.x, dy = qy - s.y, dz = qz - s.z;
                     const float d = dx * dx + (dy * dy + dz * dz);
@@ -1059,13 +1082,14 @@ struct LcpForm {
     bool flat, near;   // queue kernel (see the table above it); false elsewhere
     int cu;            // queue kernel: 16 or 64; 64 elsewhere
     bool shared;       // queue kernel, split and cu == 16: one list of live sub-patches per candidate (models of up to 8 192 points)
+    bool gate;         // queue kernel, scoring forms on sparse lists: the normal-cone gate (a grid with cones, lcp_normal_gate = 1)
 };
 
 static bool lcp_variant_selectable(int v) { return v == 99 || v == 0 || v == 24 || v == 31 || v == 39; }
 
 // The form a call runs.  Must not depend on the batch size (a candidate's score is batch-invariant).
 static LcpForm choose_lcp_form(const stocs_ctx* c, const LcpArgs& a, bool detail) {
-    LcpForm f = {LCP_QUEUE, detail, false, false, false, false, 64, false};
+    LcpForm f = {LCP_QUEUE, detail, false, false, false, false, 64, false, false};
     if (c->exact_ties) { f.kernel = LCP_EXACT; return f; }
     // dense grids keep their lists sorted by distance from the cell centre (not by index): only kernels instantiated with the
     // order-independent tie rule may scan them
@@ -1090,25 +1114,28 @@ static LcpForm choose_lcp_form(const stocs_ctx* c, const LcpArgs& a, bool detail
         // the unit of the patch test (lcp_cull_unit); without the test the walk of whole steps (CU = 64) is the one to run
         f.cu = (a.patch && c->lcp_cull_unit == 16) ? 16 : 64;
         f.shared = f.split && f.cu == 16 && a.M <= 16 * LCP_SHARED_LIVE;   // (the model size, never the batch)
+        // the cones hold the normals of c->d_snrmw; a trial batch's own arrays (snrmw_override, cand_trial) are copies of it whose
+        // weights alone differ (sample.hip: init_trial_state_kernel copies, the sampling writes .w), so those launches stay gated
+        f.gate = !detail && !f.dense && c->grid.has_cones && c->lcp_normal_gate != 0 && !(f.split && f.cu == 16 && !f.shared);   // (no gated split ring form at CU = 16: the table)
     }
     return f;
 }
 
 typedef void (*LcpScanFn)(LcpArgs, const float*, float*, int, int32_t*, uint8_t*);
 
-// the queue kernel of a form: bits 0..6 of I are DETAIL, DENSE, SPLIT, FLAT, NEAR, CU == 16 and SHARED; NULL where the form is not legal
+// the queue kernel of a form: bits 0..7 of I are DETAIL, DENSE, SPLIT, FLAT, NEAR, CU == 16, SHARED and GATE; NULL where the form is not legal
 template <int I>
 static LcpScanFn lcp_queue_fn() {
     constexpr bool DETAIL = (I & 1) != 0, DENSE = (I & 2) != 0, SPLIT = (I & 4) != 0, FLAT = (I & 8) != 0, NEAR = (I & 16) != 0;
     constexpr int CU = (I & 32) ? 16 : 64;
-    constexpr bool SHARED = (I & 64) != 0;
-    if constexpr (lcp_queue_form_legal(DETAIL, DENSE, SPLIT, FLAT, NEAR, CU, SHARED)) return lcp_coopq_kernel<DETAIL, DENSE, SPLIT, FLAT, NEAR, CU, SHARED>;
+    constexpr bool SHARED = (I & 64) != 0, GATE = (I & 128) != 0;
+    if constexpr (lcp_queue_form_legal(DETAIL, DENSE, SPLIT, FLAT, NEAR, CU, SHARED, GATE)) return lcp_coopq_kernel<DETAIL, DENSE, SPLIT, FLAT, NEAR, CU, SHARED, GATE>;
     else return NULL;
 }
 template <int... I>
 static LcpScanFn lcp_queue_fn(const LcpForm& f, std::integer_sequence<int, I...>) {
     static const LcpScanFn table[] = {lcp_queue_fn<I>()...};
-    return table[(f.detail ? 1 : 0) | (f.dense ? 2 : 0) | (f.split ? 4 : 0) | (f.flat ? 8 : 0) | (f.near ? 16 : 0) | (f.cu == 16 ? 32 : 0) | (f.shared ? 64 : 0)];
+    return table[(f.detail ? 1 : 0) | (f.dense ? 2 : 0) | (f.split ? 4 : 0) | (f.flat ? 8 : 0) | (f.near ? 16 : 0) | (f.cu == 16 ? 32 : 0) | (f.shared ? 64 : 0) | (f.gate ? 128 : 0)];
 }
 
 // Run-time form -> template instantiation, grid and block: the one place that names the kernels.
@@ -1123,11 +1150,11 @@ static int launch_lcp_form(stocs_ctx* c, const LcpForm& f, const LcpArgs& a, con
         else hipLaunchKernelGGL(lcp_exact_kernel<false>, grid, block, 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted, c->d_kd_nodes, c->d_kd_pts, c->d_ties);
     } else {
         LcpScanFn fn = NULL;
-        if (f.kernel == LCP_QUEUE) fn = lcp_queue_fn(f, std::make_integer_sequence<int, 128>());
+        if (f.kernel == LCP_QUEUE) fn = lcp_queue_fn(f, std::make_integer_sequence<int, 256>());
         else if (f.kernel == LCP_STEP) fn = f.detail ? lcp_coop_kernel<true, false> : (f.split ? lcp_coop_kernel<false, true> : lcp_coop_kernel<false, false>);
         else if (!f.detail) fn = f.dense ? lcp_kernel<false, false> : lcp_kernel<false, true>;
         else if (!f.dense) fn = lcp_kernel<true, true>;
-        if (!fn) { set_error("launch_lcp: no kernel for this form (kernel %d, detail %d, dense %d, split %d, flat %d, near %d, cu %d, shared %d)", (int)f.kernel, (int)f.detail, (int)f.dense, (int)f.split, (int)f.flat, (int)f.near, f.cu, (int)f.shared); return STOCS_ERR_STATE; }
+        if (!fn) { set_error("launch_lcp: no kernel for this form (kernel %d, detail %d, dense %d, split %d, flat %d, near %d, cu %d, shared %d, gate %d)", (int)f.kernel, (int)f.detail, (int)f.dense, (int)f.split, (int)f.flat, (int)f.near, f.cu, (int)f.shared, (int)f.gate); return STOCS_ERR_STATE; }
         hipLaunchKernelGGL(fn, grid, block, 0, c->stream, a, d_T16, d_lcp, n, d_hit, d_counted);
     }
     STOCS_HIP_CHECK(hipGetLastError());
@@ -1336,6 +1363,91 @@ int stocs_lcp_hit_count(stocs_ctx* c, const void* d_T16, int n, int64_t* hits, i
     return STOCS_OK;
 }
 
+// stocs_lcp_gate_count: one lane per (candidate, model slot).  The query, its cell and the sub-cell mask as the queue kernel's step
+// computes them (brick look-up; no mask on has_nearest grids), then the kernel's own gate function on the kernel's own rotated normal
+__global__ __launch_bounds__(256) void gate_count_kernel(LcpArgs a, const float* __restrict__ T16, size_t total, const uint8_t* __restrict__ counted,
+                                                         unsigned long long* __restrict__ out3, int has_cones) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    unsigned long long nq = 0, nr = 0, nb = 0;
+    if (g < total) {
+        const size_t cand = g / (size_t)a.M;
+        const int i = (int)(g % (size_t)a.M);
+        const float* T = T16 + cand * 16;
+        const float t0 = T[0], t1 = T[1], t2 = T[2], t4 = T[4], t5 = T[5], t6 = T[6], t8 = T[8], t9 = T[9], t10 = T[10], t12 = T[12], t13 = T[13], t14 = T[14];
+        const float4 p = a.mpos[i];
+        const float qx = ((t0 * p.x + t4 * p.y) + t8 * p.z) + t12;
+        const float qy = ((t1 * p.x + t5 * p.y) + t9 * p.z) + t13;
+        const float qz = ((t2 * p.x + t6 * p.y) + t10 * p.z) + t14;
+        const int c4x = __float2int_rd((qx - a.ox) * a.inv_h4), c4y = __float2int_rd((qy - a.oy) * a.inv_h4), c4z = __float2int_rd((qz - a.oz) * a.inv_h4);
+        const int cx = c4x >> 2, cy = c4y >> 2, cz = c4z >> 2;
+        uint32_t cnt = 0, yw = 0;
+        if ((unsigned)cx < (unsigned)a.nx && (unsigned)cy < (unsigned)a.ny && (unsigned)cz < (unsigned)a.nz) {
+            const int sb = ((c4z & 3) << 4) | ((c4y & 3) << 2) | (c4x & 3);
+            const int brick = a.top[((cz >> 3) * a.nby + (cy >> 3)) * a.nbx + (cx >> 3)];
+            if (brick >= 0) {
+                const uint4 cw = a.cells[(uint32_t)brick * 512u + (uint32_t)(((cz & 7) << 6) | ((cy & 7) << 3) | (cx & 7))];
+                const uint32_t mw = a.has_nearest ? 0xFFFFFFFFu : (sb < 32 ? cw.z : cw.w);
+                yw = cw.y; cnt = ((mw >> (sb & 31)) & 1u) ? (cw.y & STOCS_CONE_COUNT_MASK) : 0u;
+            }
+        }
+        if (cnt) {
+            nq = 1;
+            const float4 nm = a.mnrm[i];
+            const float nx = t0 * nm.x + (t4 * nm.y + t8 * nm.z);
+            const float ny = t1 * nm.x + (t5 * nm.y + t9 * nm.z);
+            const float nz = t2 * nm.x + (t6 * nm.y + t10 * nm.z);
+            if (has_cones && cone_rules_out(yw, nx, ny, nz, a.dot_lo)) {
+                nr = 1;
+                nb = counted[cand * (size_t)a.M + (size_t)a.mperm[i]] ? 1 : 0;
+            }
+        }
+    }
+    nq = lcp_wave_sum(nq); nr = lcp_wave_sum(nr); nb = lcp_wave_sum(nb);
+    if ((threadIdx.x & 63) == 0) { if (nq) atomicAdd(&out3[0], nq); if (nr) atomicAdd(&out3[1], nr); if (nb) atomicAdd(&out3[2], nb); }
+}
+
+int stocs_lcp_gate_count(stocs_ctx* c, const void* d_T16, int n, int64_t out[3]) {
+    if (!c || n < 0 || (n && !d_T16) || !out) return STOCS_ERR_INVALID;
+    DeviceGuard dev_guard(c->device);
+    begin_scoring_call(c);
+    out[0] = out[1] = out[2] = 0;
+    if (n == 0 || c->nM == 0 || c->nS == 0) return STOCS_OK;
+    const size_t M = (size_t)c->nM;
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)256 << 20) / (5 * M)));
+    const size_t hb = al256((size_t)chunk * M * 4), cb = al256((size_t)chunk * M), lb = al256((size_t)chunk * 4);
+    int rc = ensure_scratch(c, 256 + lb + hb + cb);
+    if (rc) return rc;
+    char* base = (char*)c->d_scratch;
+    unsigned long long* d_out = (unsigned long long*)base;
+    float* dL = (float*)(base + 256);
+    int32_t* dH = (int32_t*)(base + 256 + lb);
+    uint8_t* dC = (uint8_t*)(base + 256 + lb + hb);
+    LcpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.mpos = c->d_mpos_s; a.mnrm = c->d_mnrm_s; a.mperm = c->d_mperm; a.M = c->nM;
+    a.top = c->grid.d_top; a.cells = c->grid.d_cells;
+    a.ox = c->grid.ox; a.oy = c->grid.oy; a.oz = c->grid.oz; a.inv_h4 = c->grid.inv_h * 4.0f;
+    a.nx = c->grid.nx; a.ny = c->grid.ny; a.nz = c->grid.nz; a.nbx = c->grid.nbx; a.nby = c->grid.nby;
+    a.dot_lo = c->thr.lcp_dot_lo;
+    a.has_nearest = c->grid.has_nearest ? 1 : 0;
+    STOCS_HIP_CHECK(hipMemsetAsync(d_out, 0, 24, c->stream));
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const int m = std::min(chunk, n - i0);
+        const float* dT = (const float*)d_T16 + (size_t)i0 * 16;
+        rc = launch_lcp(c, dT, m, dL, dH, dC, NULL, 0);
+        if (rc) return rc;
+        const size_t total = (size_t)m * M;
+        hipLaunchKernelGGL(gate_count_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, a, dT, total, (const uint8_t*)dC, d_out, c->grid.has_cones ? 1 : 0);
+        STOCS_HIP_CHECK(hipGetLastError());
+    }
+    if ((rc = ensure_pinned(c, PIN_VAR))) return rc;
+    unsigned long long* pin = (unsigned long long*)((char*)c->h_pin + PIN_BEST);
+    STOCS_HIP_CHECK(hipMemcpyAsync(pin, d_out, 24, hipMemcpyDeviceToHost, c->stream));
+    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 3; ++k) out[k] = (int64_t)pin[k];
+    return STOCS_OK;
+}
+
 int stocs_best_device(stocs_ctx* c, const void* d_lcp, int n, uint32_t id_offset, uint64_t* key) {
     if (!c || !key || n < 0 || (n && !d_lcp)) return STOCS_ERR_INVALID;
     DeviceGuard dev_guard(c->device);
@@ -1385,6 +1497,13 @@ int stocs_set_option(stocs_ctx* c, const char* key, int value) {
     // 0: brick look-ups only, 1: the flat cell table when the grid has one (takes effect for kernels launched afterwards;
     // the table itself is built with the scene grid)
     if (!strcmp(key, "lcp_flat") && (value == 0 || value == 1)) { c->lcp_flat = value; return STOCS_OK; }
+    // 1 (default): the queue kernel's scoring forms on sparse lists drop the queries that their cell's normal cone rules out before they
+    // reach the queue (same scores); 0: the forms without the gate
+    if (!strcmp(key, "lcp_normal_gate")) {
+        if (value != 0 && value != 1) { set_error("stocs_set_option: lcp_normal_gate takes 0 or 1, not %d", value); return STOCS_ERR_INVALID; }
+        c->lcp_normal_gate = value;
+        return STOCS_OK;
+    }
     // 1: tied nearest-neighbour queries take the reference kd-tree's answer (lcp_exact_kernel, kdtree.h); 0 (default): largest index
     if (!strcmp(key, "exact_ties")) {
         if (value != 0 && value != 1) { set_error("stocs_set_option: exact_ties takes 0 or 1, not %d", value); return STOCS_ERR_INVALID; }

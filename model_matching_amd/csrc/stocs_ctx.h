@@ -174,6 +174,8 @@ struct SceneGrid {
     float* d_chunk_r;    // dense scenes only: lists sorted by distance from the cell centre; per 8-entry chunk a
                          // lower bound of that distance (early exit by the triangle inequality); else NULL
     float h;             // cell edge
+    bool has_cones;      // the count word of a cell carries a cone of its list's scene normals above the 16-bit list length (normal_cone.h);
+                         // false (empty scene, STOCS_GRID_CONES=0): those bits are zero and no gated kernel form runs
     bool has_nearest;    // dense grids with cell edges below epsilon: the z word of a cell is a lower bound of the distance from the
                          // cell centre to the nearest listed point (the sub-cell mask it replaces is all ones there)
     // Distance field of the scene on a coarse grid (cell edge cg_g >= epsilon), for the patch test of the scan kernels (lcp.hip):
@@ -290,6 +292,7 @@ struct stocs_ctx {
     int device_clock;  // 1: stocs_find_congruent_all records HIP events between its kernel groups ("device: ..." steps of stocs_last_call_timing); default 0 (STOCS_DEVICE_CLOCK=1 turns it on)
     int lcp_split;     // 1: four wavefronts share one candidate (default), 0: one wavefront per candidate
     int lcp_flat;      // 1: build and use the flat cell table when it fits (default), 0: brick look-ups only
+    int lcp_normal_gate;   // 1 (default): the queue kernel drops queries whose cell's normal cone cannot pass the normal test (same scores)
     int lcp_order;     // 0: candidates in batch order; 1: spatially ordered processing of big batches; 2: + XCD-contiguous blocks
     stocs::DevBlock order;   // keys / permutation / sort scratch of the ordering
     // "exact_ties" (stocs_set_option): tied nearest-neighbour queries answered by the reference-order kd-tree (kdtree.h).  The tree

@@ -598,6 +598,13 @@ class StocsEstimator:
         capi.check(self.L.stocs_lcp_hit_count(self.h, dT, n, C.byref(h), C.byref(k)))
         return h.value, k.value
 
+    def lcp_gate_count(self, dT, n):
+        """(queries in non-empty, mask-surviving cells; those the normal-cone gate rules out; ruled-out ones the detail form counts -- 0)
+        over n device-resident transforms (stocs_lcp_gate_count)."""
+        out = (C.c_int64 * 3)(0, 0, 0)
+        capi.check(self.L.stocs_lcp_gate_count(self.h, dT, n, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
     def compute_best_transform(self):
         s = C.c_float(0); i = C.c_int(-1)
         P = np.zeros(16, np.float32)

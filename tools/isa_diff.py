@@ -44,8 +44,9 @@ def pair_name(old):
     if "lcp_coopq_kernel" in old:
         if len(a) == 16:   # DETAIL UNR SORTQ PIPE IDX WPB FLAT SPLIT TILE EARLY GL FIRST NOSENT NEAR TINY CU
             a = [a[0], a[9], a[7], a[6], a[13], a[15]]
+        gate = len(a) == 8 and a.pop() == 1     # GATE = 1 likewise: main() compares it with the form without the gate
         shared = len(a) == 7 and a.pop() == 1   # SHARED = 1 has no form of its own in an older listing: main() compares it with SHARED = 0
-        return "queue<detail=%d dense=%d split=%d flat=%d near=%d cu=%d>" % tuple(a) + (" shared" if shared else "")
+        return "queue<detail=%d dense=%d split=%d flat=%d near=%d cu=%d>" % tuple(a) + (" shared" if shared else "") + (" gate" if gate else "")
     if "lcp_coop_kernel" in old:
         if len(a) == 7:    # DETAIL UNR MASK EARLY IDX WPB SPLIT
             a = [a[0], a[6]]
@@ -62,6 +63,8 @@ def main():
     print("|---|---|---|---|---|---|")
     seen = set()
     for k, (body, res) in sorted((pair_name(k), v) for k, v in new.items()):
+        if k not in oldk and k.endswith(" gate") and k[:-5] in oldk:
+            oldk[k] = oldk[k[:-5]]
         if k not in oldk and k.endswith(" shared") and k[:-7] in oldk:
             oldk[k] = oldk[k[:-7]]
         if k not in oldk:
