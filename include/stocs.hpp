@@ -725,6 +725,23 @@ public:
         }
         return r;
     }
+    // Pose errors under model symmetries (stocs_pose_errors_sym; no reference counterpart): as pose_errors, under the K symmetry transforms
+    // of the model frame in sym16 (K x 16 floats, column-major; symmetry_set below builds them from a clustering descriptor): MSSD and
+    // symmetric ADD in metres and, with a camera (only fx, cx, fy, cy are read), MSPD in pixels, with the symmetry that attains each.  Empty
+    // on error (the text goes to the log).
+    std::vector<stocs_pose_error_sym> pose_errors_sym(const std::vector<PoseCandidate*>& est, const std::vector<PoseCandidate*>& gt, const std::vector<float>& sym16,
+                                                      const stocs_camera* cam = NULL) {
+        const int n = (int)est.size(), n_gt = (int)gt.size();
+        std::vector<float> P((size_t)n * 16), G((size_t)n_gt * 16);
+        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], est[(size_t)i]->transform.data(), 64);
+        for (int i = 0; i < n_gt; ++i) std::memcpy(&G[(size_t)i * 16], gt[(size_t)i]->transform.data(), 64);
+        std::vector<stocs_pose_error_sym> r((size_t)n);
+        if (n > 0 && stocs_pose_errors_sym(ctx_, P.data(), n, G.data(), n_gt, sym16.data(), (int)(sym16.size() / 16), cam, r.data()) != STOCS_OK) {
+            *log_ << "pose_errors_sym failed: " << stocs_last_error() << std::endl;
+            r.clear();
+        }
+        return r;
+    }
     float model_diameter() {
         float d = -1.0f;
         if (stocs_model_diameter(ctx_, &d) != STOCS_OK) {
@@ -1011,6 +1028,17 @@ protected:
     int la_first_, la_n_, la_cursor_, la_mode_, la_nvalid_;
     bool la_in_ctx_, la_congruent_done_;
 };
+
+// Not in the reference: the symmetry transforms that a clustering descriptor (0, 90, 180 or 360 per axis, the reference's sym_info) stands
+// for (stocs_symmetry_set): K x 16 floats, column-major, entry 0 the identity; a continuous axis is sampled at n_continuous steps, the
+// rotations turn about center3 (NULL: the origin).  Empty on error.
+inline std::vector<float> symmetry_set(const float sym3[3], int n_continuous = 72, const float* center3 = NULL) {
+    int K = 0;
+    (void)stocs_symmetry_set(sym3, n_continuous, center3, NULL, 0, &K);   // the count alone: no room is offered
+    std::vector<float> out((size_t)(K > 0 ? K : 0) * 16);
+    if (K < 1 || stocs_symmetry_set(sym3, n_continuous, center3, out.data(), K, &K) != STOCS_OK) out.clear();
+    return out;
+}
 
 // Not in the reference: which hypotheses of several objects form one consistent explanation of the frame (stocs_scene_footprints /
 // stocs_scene_select).  estimators[k] holds object k's model and the frame (set_frame, the same size everywhere), poses[k] its camera-frame

@@ -635,6 +635,72 @@ int stocs_pose_errors_detail(stocs_ctx* ctx, const float* est_pose16_camera, con
                              float* e /*M*/, float* s /*M*/, int32_t* nn /*M*/);   /* one pair; any output may be NULL */
 int stocs_model_diameter(stocs_ctx* ctx, float* diameter);
 
+/* ---- pose errors under model symmetries: MSSD, MSPD, symmetric ADD (the measures of the BOP benchmark; no reference counterpart).
+ * ADD calls every pose turned about a symmetry axis wrong and ADD-S calls nearly anything that overlaps right; these take an EXPLICIT
+ * set of K symmetry transforms of the model and keep the point-to-same-point distance.  stocs_pose_errors_sym compares n estimated
+ * CAMERA-frame poses with ground truth (n_gt == 1 or n, as stocs_pose_errors) under K symmetries: column-major 4x4 in the MODEL frame
+ * handed to stocs_ctx_create, S_ab = S[4b + a], s_a = S[12 + a]; likewise the ground truth G with t_a = G[12 + a].  Per pair and per
+ * symmetry k, all in float, every operation a single IEEE add / sub / mul / div / sqrt, no contraction:
+ *   0. Compose as BOP does (R_gt R_sym, R_gt t_sym + t_gt), once per (pair, k):
+ *        C_ab = G_a0 S_0b + (G_a1 S_1b + G_a2 S_2b),   u_a = (G_a0 s_0 + (G_a1 s_1 + G_a2 s_2)) + t_a.
+ *   1. p(i) under the estimate by step 1 of stocs_pose_errors; g^k(i) by the same expression under (C, u).
+ *   2. D_k(i) by step 2 there with d = p(i) - g^k(i).
+ *   3. e^k_i = r(D_k(i));  add_fix_k = sum_i q(e^k_i);  max3_k = max_i e^k_i  (r and q of stocs_pose_errors; the maximum may be taken
+ *      on D with a NaN counted as +inf and rooted once: the correctly rounded root is monotone).
+ *   4. Projection, only with a camera.  For a transformed point x: a = (fx x_0) / x_2 + cx,  b = (fy x_1) / x_2 + cy (the depth
+ *      check's projection before its + 0.5 and floor).  P_k(i) = (da da) + (db db) with da, db the differences estimate minus
+ *      ground truth; P_k(i) = +inf when !(x_2 > 1e-6f) for the point under either pose or when P is NaN.  max2_k = r(max_i P_k(i)),
+ *      in pixels.  Without a camera max2_k = +inf.
+ *   5. Minimum over k in index order, starting at +inf and replaced only on `<`:  mssd = min_k max3_k,  mspd = min_k max2_k;
+ *      add_fix = min_k add_fix_k as integers (the start is above every sum, so k_add >= 0 for every valid pair);
+ *      add = (float)((double)add_fix / 2^32 / (double)M).  k_mssd, k_mspd, k_add: the LOWEST k that attains the minimum, -1 when no
+ *      k is below +inf.  Integer sums, maxima and index-ordered minima: a record is bitwise independent of the batch it shares and
+ *      of any reduction order, and a float32 numpy restatement reproduces every field (tests/pose_error_sym_ref.py).
+ *   6. valid = 0, a zero sum, three +inf and three -1 for the pairs that step 5 of stocs_pose_errors calls invalid.  Not an error.
+ * With K = 1 and the identity, add_fix and add equal stocs_pose_errors's and mssd its add_max bit for bit for every valid pair: the
+ * composition can only change signs of zero, which the squares of step 2 remove.
+ * stocs_pose_errors_sym_detail gives add_fix_k, max3_k and max2_k (K entries each, any may be NULL) of ONE pair by the same kernel;
+ * as in stocs_pose_errors_detail step 6 does not apply.
+ * Checked in this order: a NULL ctx (whatever n) and n < 0 are STOCS_ERR_INVALID; n == 0 is then a no-op that looks at no other
+ * argument; then K < 1 or K > STOCS_POSE_SYM_MAX, a NULL out, pose or symmetry pointer, an n_gt other than 1 or n, a non-finite
+ * entry among a symmetry's twelve used entries, a non-finite fx, fy, cx or cy of a given camera (its other fields are not read), and a
+ * workspace demand above STOCS_REFINE_ROBUST_MAX_WORKSPACE_BYTES (64 n_gt K + 16 n K bytes and the poses) are STOCS_ERR_INVALID.
+ * Its own grow-only workspace on the context (a second call of the same or a smaller size allocates nothing); on the context's
+ * stream, poses and symmetries up through the pinned block, one read-back of n records and one synchronisation per call.
+ * stocs_last_call_timing(which = 5) gives the host steps of the last stocs_pose_errors_sym and, with "device_clock" on, the
+ * HIP-event time of its launches.
+ * The kernels (csrc/pose_error_sym.hip): one thread per (ground truth, k) composes step 0 into device memory; a workgroup of
+ * STOCS_POSE_SYM_THREADS threads owns one pair and a block of STOCS_POSE_SYM_BLOCK symmetries, whose composed poses it reads as
+ * wave-uniform scalars, and walks the whole model with per-lane accumulators (grid: pairs in x, symmetry blocks in y), then stores
+ * the block's per-k values: no atomics, no memset; one wavefront per pair takes step 5.
+ *
+ * stocs_symmetry_set (host code, no device work) writes the rotations that the clustering's symmetry descriptor names (the
+ * reference's sym_info, folded into stocs_cluster_poses's rotation error).  For a descriptor on x or z the smallest plain rotation
+ * error over the set equals the clustering's folded error for every turn about that axis.  For y that holds only for turns of LESS
+ * than 90 degrees: the clustering takes the pitch by asin, which folds it into +-90 degrees before any symmetry is folded, so beyond
+ * a quarter turn about y its error is 180 degrees whatever the descriptor, while the set holds the true rotations (Ry(100) under
+ * (0, 360, 0): 180 degrees there, 0 here).  A clustering with a y descriptor and these errors can disagree beyond that.  Per axis d the angle list is the multiples of 90 degrees
+ * for sym3[d] == 90, {0, 180} for 180, 360 j / n_continuous (j = 0 .. n_continuous - 1; n_continuous < 1 is invalid there) for 360,
+ * {0} otherwise.  The set is T(c) Rz(gamma) Ry(beta) Rx(alpha) T(-c) over the three lists -- the Euler order of the clustering's
+ * quaternion_to_euler -- with the x angle running fastest, so entry 0 is the identity; c = center3 (NULL: the origin).  Entries are
+ * computed in double and rounded once; angles that are multiples of 90 degrees give exactly 0 and +-1.  *K always receives the count;
+ * cap < K (or a NULL out16) is STOCS_ERR_INVALID and writes nothing.  With more than one non-trivial axis the product list need NOT
+ * be a group (it is not closed under composition in general, and may name one rotation twice); pass an explicit list to
+ * stocs_pose_errors_sym instead where that matters. ---- */
+#define STOCS_POSE_SYM_MAX 4096
+#define STOCS_POSE_SYM_THREADS 256
+#define STOCS_POSE_SYM_BLOCK 4
+typedef struct stocs_pose_error_sym {
+    uint64_t add_fix;                       /* min over k of the step-3 sum */
+    float    add, mssd, mspd, reserved_f;   /* metres, metres, pixels, 0 */
+    int32_t  k_add, k_mssd, k_mspd, valid;  /* the lowest k that attains each minimum; -1: none */
+} stocs_pose_error_sym;                     /* 40 bytes */
+int stocs_pose_errors_sym(stocs_ctx* ctx, const float* est_pose16_camera, int n, const float* gt_pose16_camera, int n_gt,
+                          const float* sym16_model, int K, const stocs_camera* cam /* NULL: no MSPD */, stocs_pose_error_sym* out);
+int stocs_pose_errors_sym_detail(stocs_ctx* ctx, const float* est_pose16_camera, const float* gt_pose16_camera, const float* sym16_model, int K,
+                                 const stocs_camera* cam, uint64_t* add_fix /*K*/, float* max3 /*K*/, float* max2 /*K*/);
+int stocs_symmetry_set(const float sym3[3], int n_continuous, const float* center3 /* NULL: origin */, float* out16, int cap, int* K);
+
 /* ---- multi-instance selection (no reference counterpart: the reference returns one pose per object).  Of n hypotheses, which are
  * distinct instances and which are one instance found twice: walk them best first and keep one only if enough of the scene points it
  * explains are not explained by one kept before it.  stocs_select_instances takes n CENTRED-frame hypotheses (column-major, as
@@ -911,8 +977,8 @@ int stocs_debug_sort_pairs(int device, const uint32_t* keys, const uint32_t* val
  * difference across them is 0. */
 int64_t stocs_device_alloc_count(void);
 /* host wall clock, in milliseconds, of the steps of the context's LAST stocs_find_congruent_all (which = 0),
- * stocs_make_transforms (1), stocs_verify_all (2), stocs_run_trials (3: its phases summed over the pieces of the batch) or stocs_pose_errors
- * (4; with "device_clock" 1 also "device: kernel", the HIP-event time of its launches): always recorded (a few clock reads per call, no synchronisation of its
+ * stocs_make_transforms (1), stocs_verify_all (2), stocs_run_trials (3: its phases summed over the pieces of the batch), stocs_pose_errors
+ * (4; with "device_clock" 1 also "device: kernel", the HIP-event time of its launches) or stocs_pose_errors_sym (5; likewise): always recorded (a few clock reads per call, no synchronisation of its
  * own), so that a call that stalls -- tens of milliseconds instead of one -- names the step it stalled in.  Steps are host
  * intervals between the call's existing synchronisation points: "wait for the device" steps hold the GPU work, the others
  * host work and runtime calls; entries whose label starts with "device:" are HIP-event times of the kernel groups that

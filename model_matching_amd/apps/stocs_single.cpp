@@ -31,6 +31,14 @@
 // ground truth is) and, with --trials N, "gt <object> recall: trials=N valid=... threshold=... add=... adds=...": the share of the trials'
 // winners whose ADD / ADD-S is below 0.1 diameter (with --track only when the run fell back to detection: a tracked pose ran no trials).
 // A pose file left at <out> by an earlier run is removed first; when this run finds no pose the line reads "gt <object>: no pose".
+// --sym a,b,c [--sym-steps n] [--sym-file <K x 16 floats>] (with --gt): the errors under the model's symmetries as well (stocs_pose_errors_sym).
+// a,b,c is the clustering's descriptor (0, 90, 180 or 360 per axis; stocs_symmetry_set, a continuous axis in n steps, default 72);
+// --sym-file replaces the generated set by an explicit one (text, 16 floats per transform, column-major).  After the gt line,
+// "gt <object> sym: symmetries=K mssd=... k_mssd=... add=... k_add=... [mspd=... k_mspd=...] valid=..." (mspd when the run has a
+// camera: a scene directory) and, with --trials N, one "gt <object> sym trial t: mssd=... add=... [mspd=...] valid=..." line per trial's
+// winner and "gt <object> sym recall: trials=N valid=... mssd=... add=... [mspd=...]": BOP's average
+// recall of MSSD over 0.05 .. 0.50 diameters, the share with the symmetric ADD below 0.1 diameter, and the average recall of MSPD over
+// 5 .. 50 pixels x image width / 640.  Without --sym the output is what it is without these options.
 // --depth-check (with --trials N --cluster 1 [--refine K], a scene directory): every trial's hypotheses -- the refined poses when
 // refinement ran -- scored against the frame's own depth image and class-probability map (stocs_depth_check_poses); one "depth t.i:"
 // line per hypothesis, and <out> is written from the first maximum of score - violation (ties: the higher lcp, then the lower trial
@@ -329,7 +337,7 @@ static bool read_pose_file(const std::string& path, MatrixType& m) {
 // the file gets), against the ground truth: ADD, ADD-S, their maxima, the model's diameter (stocs_pose_errors, stocs_model_diameter); with
 // --trials N also the share of the trials' winners (full precision, a trial without a pose left out) within 0.1 diameter
 static int report_gt(stocs::stocs_estimator& est, const std::string& gt_path, const std::string& out_path, const std::string& object,
-                     const std::vector<stocs::stocs_estimator::TrialResult>& trials) {
+                     const std::vector<stocs::stocs_estimator::TrialResult>& trials, const std::vector<float>& syms, const stocs_camera* cam) {
     MatrixType g, p;
     if (!read_pose_file(gt_path, g)) { std::cerr << "cannot read a 3x4 pose from " << gt_path << std::endl; return 1; }
     PoseCandidate gt(g, 0.0f, -1.0f);
@@ -346,6 +354,15 @@ static int report_gt(stocs::stocs_estimator& est, const std::string& gt_path, co
         snprintf(b, sizeof(b), "gt %s: add=%.9g add_max=%.9g adds=%.9g adds_max=%.9g diameter=%.9g adds_over_diameter=%.9g valid=%d", object.c_str(), (double)r[0].add,
                  (double)r[0].add_max, (double)r[0].adds, (double)r[0].adds_max, (double)diameter, diameter > 0.0f ? (double)(r[0].adds / diameter) : 0.0, r[0].valid);
         std::cout << b << std::endl;
+        if (!syms.empty()) {
+            const std::vector<stocs_pose_error_sym> q = est.pose_errors_sym(std::vector<PoseCandidate*>(1, &e), gts, syms, cam);
+            if (q.size() != 1) { std::cerr << "symmetric pose errors failed: " << stocs_last_error() << std::endl; return 2; }
+            int at = snprintf(b, sizeof(b), "gt %s sym: symmetries=%d mssd=%.9g k_mssd=%d add=%.9g k_add=%d", object.c_str(), (int)(syms.size() / 16), (double)q[0].mssd,
+                              q[0].k_mssd, (double)q[0].add, q[0].k_add);
+            if (cam) at += snprintf(b + at, sizeof(b) - (size_t)at, " mspd=%.9g k_mspd=%d", (double)q[0].mspd, q[0].k_mspd);
+            snprintf(b + at, sizeof(b) - (size_t)at, " valid=%d", q[0].valid);
+            std::cout << b << std::endl;
+        }
     }
     if (!trials.empty()) {
         std::vector<PoseCandidate> w;
@@ -363,8 +380,39 @@ static int report_gt(stocs::stocs_estimator& est, const std::string& gt_path, co
         snprintf(b, sizeof(b), "gt %s recall: trials=%d valid=%d threshold=%.9g add=%.9g adds=%.9g", object.c_str(), (int)r.size(), valid, (double)thr,
                  valid ? (double)hit_add / valid : 0.0, valid ? (double)hit_adds / valid : 0.0);
         std::cout << b << std::endl;
+        if (!syms.empty()) {
+            const std::vector<stocs_pose_error_sym> q = est.pose_errors_sym(wp, gts, syms, cam);
+            if (q.size() != wp.size()) { std::cerr << "symmetric pose errors failed: " << stocs_last_error() << std::endl; return 2; }
+            int nv = 0, hit_add = 0, hit3 = 0, hit2 = 0;   // hits summed over the ten thresholds of each average recall
+            for (size_t t = 0; t < q.size(); ++t) {
+                int at = snprintf(b, sizeof(b), "gt %s sym trial %d: mssd=%.9g add=%.9g", object.c_str(), (int)t, (double)q[t].mssd, (double)q[t].add);
+                if (cam) at += snprintf(b + at, sizeof(b) - (size_t)at, " mspd=%.9g", (double)q[t].mspd);
+                snprintf(b + at, sizeof(b) - (size_t)at, " valid=%d", q[t].valid);
+                std::cout << b << std::endl;
+                if (!q[t].valid) continue;
+                ++nv; hit_add += q[t].add < thr;
+                for (int i = 1; i <= 10; ++i) {
+                    hit3 += q[t].mssd < (float)(0.05 * i) * diameter;
+                    hit2 += q[t].mspd < (float)(5.0 * i) * ((float)image_width / 640.0f);
+                }
+            }
+            int at = snprintf(b, sizeof(b), "gt %s sym recall: trials=%d valid=%d mssd=%.9g add=%.9g", object.c_str(), (int)q.size(), nv, nv ? (double)hit3 / (10.0 * nv) : 0.0,
+                              nv ? (double)hit_add / nv : 0.0);
+            if (cam) snprintf(b + at, sizeof(b) - (size_t)at, " mspd=%.9g", nv ? (double)hit2 / (10.0 * nv) : 0.0);
+            std::cout << b << std::endl;
+        }
     }
     return 0;
+}
+
+// a symmetry set as text: 16 floats per transform, column-major; empty when the file holds no whole transform or something else
+static std::vector<float> read_sym_file(const std::string& path) {
+    std::ifstream f(path);
+    std::vector<float> v;
+    float x;
+    while (f >> x) v.push_back(x);
+    if (!f.eof() || v.size() % 16 != 0) v.clear();
+    return v;
 }
 
 // --track: the prior from the pose file, tracked on this frame; the detection of run_search when the tracked lcp stays below min_lcp
@@ -544,7 +592,10 @@ int main(int argc, char** argv) {
     if (clouds && argc < 4) { std::cout << "usage: stocs_single --clouds <scene.stcl> <model.stcl> [options]" << std::endl; return -1; }
     const std::string a1 = argv[clouds ? 2 : 1], a2 = argv[clouds ? 3 : 2];
     if (const char* e = getenv("STOCS_REPO_PATH")) repo_path = e;
-    std::string edge_path, out_path, dbg_dir, track_path, gt_path;
+    std::string edge_path, out_path, dbg_dir, track_path, gt_path, sym_path;
+    float sym3[3] = {0.0f, 0.0f, 0.0f};
+    int sym_steps = 72;
+    bool have_sym = false;
     float track_min_lcp = 0.02f;
     int do_cluster = 0, n_trials = 0, exact_ties = 0, n_refine = 0, depth_check = 0;
     bool do_instances = false, do_masks = false, have_trim = false, have_gate = false;
@@ -572,6 +623,11 @@ int main(int argc, char** argv) {
         else if (k == "--track") track_path = v;   // track from this pose file; detection when the tracked lcp is below --track-min-lcp
         else if (k == "--track-min-lcp") track_min_lcp = (float)atof(v.c_str());
         else if (k == "--gt") gt_path = v;   // ground-truth pose file (the format of --track): ADD / ADD-S of the pose this run writes
+        else if (k == "--sym") {   // with --gt: the errors under the symmetries this clustering descriptor stands for
+            if (sscanf(v.c_str(), "%f,%f,%f", &sym3[0], &sym3[1], &sym3[2]) != 3) { std::cerr << "--sym a,b,c" << std::endl; return -1; }
+            have_sym = true;
+        } else if (k == "--sym-steps") sym_steps = atoi(v.c_str());
+        else if (k == "--sym-file") sym_path = v;
         else if (k == "--instances") { do_instances = true; inst_prm.max_instances = atoi(v.c_str()); }
         else if (k == "--instance-min-fraction") inst_prm.min_exclusive_fraction = (float)atof(v.c_str());
         else if (k == "--instance-min-points") inst_prm.min_points = atoi(v.c_str());
@@ -588,6 +644,16 @@ int main(int argc, char** argv) {
     if (!gt_path.empty()) {   // before any search: a ground truth that cannot be read ends the run here
         MatrixType g;
         if (!read_pose_file(gt_path, g)) { std::cerr << "cannot read a 3x4 pose from " << gt_path << std::endl; return 1; }
+    }
+
+    std::vector<float> syms;   // --sym: the set the report is taken under, settled before any search
+    if (have_sym || !sym_path.empty()) {
+        if (!have_sym || gt_path.empty()) { std::cerr << "--sym a,b,c [--sym-steps n] [--sym-file f] needs --gt" << std::endl; return -1; }
+        syms = sym_path.empty() ? stocs::symmetry_set(sym3, sym_steps) : read_sym_file(sym_path);
+        if (syms.empty() || syms.size() / 16 > (size_t)STOCS_POSE_SYM_MAX) {
+            std::cerr << "no symmetry set of 1 .. " << STOCS_POSE_SYM_MAX << " transforms from " << (sym_path.empty() ? std::string("--sym / --sym-steps") : sym_path) << std::endl;
+            return 1;
+        }
     }
 
     if (n_refine < 0 || (n_refine > 0 && !do_cluster)) { std::cerr << "--refine N needs N >= 0 and --cluster 1" << std::endl; return -1; }
@@ -700,5 +766,8 @@ int main(int argc, char** argv) {
                                        : run_search(*est, std::cout, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine, depth_check,
                                                     do_instances ? &inst_prm : NULL, instances_path, labels_path, &trial_results);
     if (rc != 0 || gt_path.empty()) return rc;
-    return report_gt(*est, gt_path, out_path, object, trial_results);
+    stocs_camera cam;   // a scene directory has a camera: MSPD is reported too
+    memset(&cam, 0, sizeof(cam));
+    cam.fx = cam_intrinsics[0]; cam.cx = cam_intrinsics[1]; cam.fy = cam_intrinsics[2]; cam.cy = cam_intrinsics[3];
+    return report_gt(*est, gt_path, out_path, object, trial_results, syms, clouds ? NULL : &cam);
 }

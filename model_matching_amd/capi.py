@@ -74,6 +74,11 @@ class PoseError(C.Structure):
                 ("adds_max", C.c_float), ("valid", C.c_int32), ("reserved", C.c_int32)]
 
 
+class PoseErrorSym(C.Structure):
+    _fields_ = [("add_fix", C.c_uint64), ("add", C.c_float), ("mssd", C.c_float), ("mspd", C.c_float), ("reserved_f", C.c_float),
+                ("k_add", C.c_int32), ("k_mssd", C.c_int32), ("k_mspd", C.c_int32), ("valid", C.c_int32)]
+
+
 class InstanceParams(C.Structure):
     _fields_ = [("max_instances", C.c_int32), ("min_points", C.c_int32), ("min_exclusive_fraction", C.c_float)]
 
@@ -197,6 +202,9 @@ SIGNATURES = {
     "stocs_pose_errors": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, C.POINTER(PoseError)]),
     "stocs_pose_errors_detail": (C.c_int, [_vp, _fp, _fp, _fp, _fp, _ip]),
     "stocs_model_diameter": (C.c_int, [_vp, _fp]),
+    "stocs_pose_errors_sym": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.POINTER(Camera), C.POINTER(PoseErrorSym)]),
+    "stocs_pose_errors_sym_detail": (C.c_int, [_vp, _fp, _fp, _fp, C.c_int, C.POINTER(Camera), C.POINTER(C.c_uint64), _fp, _fp]),
+    "stocs_symmetry_set": (C.c_int, [_fp, C.c_int, _fp, _fp, C.c_int, _intp]),
     "stocs_default_render_params": (None, [C.POINTER(RenderParams)]),
     "stocs_render_poses": (C.c_int, [_vp, _fp, C.c_int, C.c_int, C.POINTER(RenderParams), _vp, C.c_int]),
     "stocs_render_resolve": (C.c_int, [_vp, _fp, C.c_int, C.c_int, C.POINTER(RenderParams), _vp, C.POINTER(RenderResult)]),

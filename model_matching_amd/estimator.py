@@ -43,6 +43,9 @@ assert _DEPTH_DTYPE.itemsize == C.sizeof(capi.DepthResult)
 _POSE_ERROR_DTYPE = np.dtype([("add_fix", np.uint64), ("adds_fix", np.uint64), ("add", np.float32), ("add_max", np.float32), ("adds", np.float32),
                               ("adds_max", np.float32), ("valid", np.int32), ("reserved", np.int32)])
 assert _POSE_ERROR_DTYPE.itemsize == C.sizeof(capi.PoseError)
+_POSE_ERROR_SYM_DTYPE = np.dtype([("add_fix", np.uint64), ("add", np.float32), ("mssd", np.float32), ("mspd", np.float32), ("reserved_f", np.float32),
+                                  ("k_add", np.int32), ("k_mssd", np.int32), ("k_mspd", np.int32), ("valid", np.int32)])
+assert _POSE_ERROR_SYM_DTYPE.itemsize == C.sizeof(capi.PoseErrorSym)
 _RENDER_DTYPE = np.dtype([(f[0], np.int32) for f in capi.RenderResult._fields_])
 assert _RENDER_DTYPE.itemsize == C.sizeof(capi.RenderResult)
 _INSTANCE_DTYPE = np.dtype([("rank", np.int32), ("own", np.int32), ("exclusive", np.int32), ("lcp", np.float32)])
@@ -438,6 +441,48 @@ class StocsEstimator:
         e, s, nn = np.empty(self.nM, np.float32), np.empty(self.nM, np.float32), np.empty(self.nM, np.int32)
         capi.check(self.L.stocs_pose_errors_detail(self.h, pP, pG, e.ctypes.data_as(capi._fp), s.ctypes.data_as(capi._fp), nn.ctypes.data_as(capi._ip)))
         return e, s, nn
+
+    @staticmethod
+    def _sym_camera(camera):
+        """camera: None, a capi.Camera, or the intrinsics (fx, cx, fy, cy) in set_frame's order"""
+        if camera is None or isinstance(camera, capi.Camera):
+            return camera
+        K = [float(x) for x in camera]
+        if len(K) != 4:
+            raise ValueError("camera: the four intrinsics fx, cx, fy, cy")
+        return capi.Camera(K[0], K[1], K[2], K[3], 1.0, 0, 0, 0)
+
+    def pose_errors_sym(self, est, gt, symmetries, camera=None):
+        """n estimated camera-frame poses against ground truth under K model symmetries (stocs_pose_errors_sym): gt holds one pose or n,
+        symmetries K column-major 4x4 transforms of the model frame (symmetry_set builds them from a descriptor), camera None (no MSPD),
+        the intrinsics (fx, cx, fy, cy) or a capi.Camera -> a structured array with the fields of stocs_pose_error_sym, one record per
+        estimate: MSSD (`mssd`) and symmetric ADD (`add`) in metres, MSPD (`mspd`) in pixels, and the symmetry that attains each."""
+        P, pP = capi.f32(est)
+        G, pG = capi.f32(gt)
+        S, pS = capi.f32(symmetries)
+        if P.size % 16 or G.size % 16 or G.size == 0 or S.size % 16:
+            raise ValueError("pose_errors_sym: poses and symmetries are 16 floats each")
+        n, n_gt, K = P.size // 16, G.size // 16, S.size // 16
+        cam = self._sym_camera(camera)
+        buf = (capi.PoseErrorSym * max(n, 1))()
+        capi.check(self.L.stocs_pose_errors_sym(self.h, pP, n, pG, n_gt, pS, K, None if cam is None else C.byref(cam), buf))
+        return np.frombuffer(buf, dtype=_POSE_ERROR_SYM_DTYPE, count=n).copy()
+
+    def pose_errors_sym_detail(self, est, gt, symmetries, camera=None):
+        """One pair of camera-frame poses under K symmetries (stocs_pose_errors_sym_detail) -> (add_fix, max3, max2), one entry per
+        symmetry: the fixed-point sum of the distances, their maximum (metres) and the maximum projected distance (pixels; +inf without
+        a camera)."""
+        P, pP = capi.f32(est)
+        G, pG = capi.f32(gt)
+        S, pS = capi.f32(symmetries)
+        if P.size != 16 or G.size != 16 or S.size % 16:
+            raise ValueError("pose_errors_sym_detail: one pose of 16 floats each, symmetries of 16 floats each")
+        K = S.size // 16
+        cam = self._sym_camera(camera)
+        af, m3, m2 = np.empty(max(K, 1), np.uint64), np.empty(max(K, 1), np.float32), np.empty(max(K, 1), np.float32)
+        capi.check(self.L.stocs_pose_errors_sym_detail(self.h, pP, pG, pS, K, None if cam is None else C.byref(cam),
+                                                       af.ctypes.data_as(C.POINTER(C.c_uint64)), m3.ctypes.data_as(capi._fp), m2.ctypes.data_as(capi._fp)))
+        return af[:K], m3[:K], m2[:K]
 
     def model_diameter(self):
         """The largest distance between two model points (stocs_model_diameter), computed on the device once per context."""
@@ -856,6 +901,46 @@ def pose_recall(errors, diameter, k=0.1):
         return float("nan"), float("nan"), 0
     thr = np.float32(k) * np.float32(diameter)
     return float((errors["add"][ok] < thr).mean()), float((errors["adds"][ok] < thr).mean()), nv
+
+
+def symmetry_set(sym3, n_continuous=72, center=None):
+    """The symmetry transforms that a clustering descriptor stands for (stocs_symmetry_set): sym3 holds 0, 90, 180 or 360 per axis, a
+    continuous axis (360) is sampled at n_continuous steps, center is the point the rotations turn about (None: the origin) ->
+    (K, 16) float32, column-major 4x4, entry 0 the identity."""
+    L = capi.load()
+    s3 = (C.c_float * 3)(*[float(x) for x in sym3])
+    c3 = None if center is None else (C.c_float * 3)(*[float(x) for x in center])
+    K = C.c_int(0)
+    rc = L.stocs_symmetry_set(s3, int(n_continuous), c3, None, 0, C.byref(K))    # the count alone: no room is offered
+    if K.value < 1:
+        capi.check(rc)
+    out = np.empty((K.value, 16), np.float32)
+    capi.check(L.stocs_symmetry_set(s3, int(n_continuous), c3, out.ctypes.data_as(capi._fp), K.value, C.byref(K)))
+    return out
+
+
+BOP_MSSD_THRESHOLDS = tuple(0.05 * i for i in range(1, 11))     # of the diameter
+BOP_MSPD_THRESHOLDS = tuple(5.0 * i for i in range(1, 11))      # pixels at an image width of 640
+
+
+def pose_recall_sym(records, diameter, image_width=None):
+    """BOP's average recalls over the valid records of pose_errors_sym -> (ar_mssd, ar_mspd, recall_add, n_valid): the mean over the
+    thresholds 0.05, 0.10 .. 0.50 diameters of the share with mssd below the threshold; the mean over 5, 10 .. 50 pixels x
+    image_width / 640 of the share with mspd below it (nan without a width); the share with the symmetric add below 0.1 diameter.
+    (nan, nan, nan, 0) when no record is valid; invalid records are left out, as in pose_recall."""
+    records = np.asarray(records)
+    ok = records["valid"] != 0
+    nv = int(ok.sum())
+    if nv == 0:
+        return float("nan"), float("nan"), float("nan"), 0
+    d = np.float32(diameter)
+    mssd, mspd, add = records["mssd"][ok], records["mspd"][ok], records["add"][ok]
+    ar_mssd = float(np.mean([(mssd < np.float32(t) * d).mean() for t in BOP_MSSD_THRESHOLDS]))
+    ar_mspd = float("nan")
+    if image_width is not None:
+        r = np.float32(image_width) / np.float32(640)
+        ar_mspd = float(np.mean([(mspd < np.float32(t) * r).mean() for t in BOP_MSPD_THRESHOLDS]))
+    return ar_mssd, ar_mspd, float((add < np.float32(0.1) * d).mean()), nv
 
 
 def kdtree_nn_host(pos3, queries3, sqdist):

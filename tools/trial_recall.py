@@ -6,7 +6,10 @@ Runs --trials independent trials as one batch (run_trials, seeds --seed, --seed 
 T_gt with pose_errors (ADD, ADD-S on the GPU) and reports the share of trials whose error is below 0.1 of the model's diameter: of the
 trials that returned a pose (pose_recall) and of all trials.  With --post the batch clusters and refines (5 iterations) inside the call and
 the best refined hypothesis of every trial (first maximum of the rescored lcp) is scored too.  synth:Cm is an ellipsoid of revolution
-with one bump: its ADD says little, its ADD-S is the meaningful one; synth:Cm_asym has no symmetry.  No GPU: the tool fails."""
+with one bump: its ADD says little, its ADD-S is the meaningful one; synth:Cm_asym has no symmetry.  With --sym a,b,c [--sym-steps n] the
+winners are also scored under the symmetries that descriptor stands for (symmetry_set, pose_errors_sym): BOP's average recalls of MSSD and
+MSPD, the share with the symmetric ADD and with MSSD below 0.1 diameter, and how many records' symmetric ADD equals their plain ADD bit
+for bit (all of them under --sym 0,0,0, the identity alone).  A --sym run is a row of its own in the file.  No GPU: the tool fails."""
 import argparse
 import json
 import os
@@ -18,7 +21,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from model_matching_amd import synth  # noqa: E402
-from model_matching_amd.estimator import StocsEstimator, pose_recall  # noqa: E402
+from model_matching_amd.estimator import StocsEstimator, pose_recall, pose_recall_sym, symmetry_set  # noqa: E402
 
 
 def summary(err, diameter, n_trials):
@@ -32,12 +35,27 @@ def summary(err, diameter, n_trials):
             "median_adds_mm": float(np.median(err["adds"][ok]) * 1e3) if nv else None}
 
 
+def summary_sym(err, plain, diameter, n_trials, image_width):
+    ar3, ar2, ra, nv = pose_recall_sym(err, diameter, image_width)
+    ok = err["valid"] != 0
+    thr = np.float32(0.1) * np.float32(diameter)
+    return {"trials": n_trials, "with_pose": nv, "average_recall_mssd_of_poses": ar3, "average_recall_mspd_of_poses": ar2, "recall_sym_add_of_poses": ra,
+            "recall_mssd_of_poses": float((err["mssd"][ok] < thr).mean()) if nv else None,
+            "recall_sym_add_of_trials": float((ok & (err["add"] < thr)).sum()) / n_trials,
+            "recall_mssd_of_trials": float((ok & (err["mssd"] < thr)).sum()) / n_trials,
+            "median_sym_add_mm": float(np.median(err["add"][ok]) * 1e3) if nv else None,
+            "median_mssd_mm": float(np.median(err["mssd"][ok]) * 1e3) if nv else None,
+            "sym_add_equals_add_bitwise": int((err["add_fix"][ok] == plain["add_fix"][ok]).sum())}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--example", default="synth:Cm_asym", choices=["synth:Cm_asym", "synth:Cm"])
     ap.add_argument("--trials", type=int, default=256)
     ap.add_argument("--seed", type=int, default=1000)
     ap.add_argument("--post", action="store_true")
+    ap.add_argument("--sym", default=None, help="a,b,c: the clustering's symmetry descriptor (0, 90, 180 or 360 per axis)")
+    ap.add_argument("--sym-steps", type=int, default=72)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "trial_recall.json"))
     a = ap.parse_args()
     name = a.example.split(":", 1)[1]
@@ -49,15 +67,25 @@ def main():
     res = est.run_trials(seeds, post=post)
     diameter = float(est.model_diameter())
     W = np.stack([r["best_pose"] for r in res]).astype(np.float32)
+    plain_w = est.pose_errors(W, gt16)
     row = {"example": a.example, "model_points": len(model.pos), "scene_points": len(scene.pos), "first_seed": a.seed, "model_diameter_m": diameter,
-           "threshold_m": float(np.float32(0.1) * np.float32(diameter)), "winners": summary(est.pose_errors(W, gt16), diameter, a.trials)}
+           "threshold_m": float(np.float32(0.1) * np.float32(diameter)), "winners": summary(plain_w, diameter, a.trials)}
+    S = None
+    if a.sym is not None:
+        sym3 = [float(x) for x in a.sym.split(",")]
+        S = symmetry_set(sym3, a.sym_steps)
+        row["sym"] = {"descriptor": sym3, "steps": a.sym_steps, "symmetries": len(S)}
+        row["winners_sym"] = summary_sym(est.pose_errors_sym(W, gt16, S, synth.YCB_INTRINSICS), plain_w, diameter, a.trials, 640)
     if a.post:
         R = np.zeros((a.trials, 16), np.float32)      # all zero: "no pose"
         for t in range(a.trials):
             h = est.trials_get_hypotheses(t)
             if len(h):
                 R[t] = h["refined_pose16"][int(np.argmax(h["refined_lcp"]))]
-        row["refined_winners"] = summary(est.pose_errors(R, gt16), diameter, a.trials)
+        plain_r = est.pose_errors(R, gt16)
+        row["refined_winners"] = summary(plain_r, diameter, a.trials)
+        if S is not None:
+            row["refined_winners_sym"] = summary_sym(est.pose_errors_sym(R, gt16, S, synth.YCB_INTRINSICS), plain_r, diameter, a.trials, 640)
     est.close()
     print(json.dumps(row), flush=True)
     # one file, one entry per example (and per --post): a second run adds to it
@@ -65,8 +93,8 @@ def main():
     if os.path.exists(a.out):
         with open(a.out) as f:
             data = json.load(f)
-    key = (a.example, a.post)
-    data["rows"] = [r for r in data["rows"] if (r["example"], "refined_winners" in r) != key] + [row]
+    key = (a.example, a.post, json.dumps(row.get("sym")))
+    data["rows"] = [r for r in data["rows"] if (r["example"], "refined_winners" in r, json.dumps(r.get("sym"))) != key] + [row]
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(data, f, indent=1)
