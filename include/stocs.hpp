@@ -243,6 +243,38 @@ inline void transform_pointset(std::vector<Point3D>& input, std::vector<Point3D>
 
 namespace stocs {
 
+// Not in the reference: what stocs_find_symmetries reports.  axes best first (order 0: continuous); set16 the K x 16 floats of the closed
+// set for pose_errors_sym (entry 0 the identity); sym3 the clustering descriptor, zeros when flags carries
+// STOCS_SYMMETRY_DESCRIPTOR_INEXACT; STOCS_SYMMETRY_SET_TRUNCATED / STOCS_SYMMETRY_NOTHING_FOUND as the header says.
+struct SymmetryResult {
+    bool ok;
+    std::vector<stocs_symmetry_axis> axes;
+    std::vector<float> set16;
+    float sym3[3];
+    int flags;
+};
+inline stocs_symmetry_search default_symmetry_search() {
+    stocs_symmetry_search s;
+    stocs_default_symmetry_search(&s);
+    return s;
+}
+inline SymmetryResult find_symmetries_of(stocs_ctx* ctx, const stocs_symmetry_search& search, const float* center3) {
+    SymmetryResult r;
+    r.ok = false; r.flags = 0; r.sym3[0] = r.sym3[1] = r.sym3[2] = 0.0f;
+    const int cap_axes = search.n_refine > 0 ? search.n_refine : 1;
+    r.axes.resize((size_t)cap_axes);
+    r.set16.resize((size_t)STOCS_POSE_SYM_MAX * 16);
+    int n = 0, K = 0;
+    if (stocs_find_symmetries(ctx, &search, center3, r.axes.data(), cap_axes, &n, r.set16.data(), STOCS_POSE_SYM_MAX, &K, r.sym3, &r.flags) != STOCS_OK) {
+        r.axes.clear(); r.set16.clear();
+        return r;
+    }
+    r.axes.resize((size_t)(n < cap_axes ? n : cap_axes));
+    r.set16.resize((size_t)K * 16);
+    r.ok = true;
+    return r;
+}
+
 class stocs_estimator {
 public:
     // reference stocs.hpp:18-61, argument for argument
@@ -742,6 +774,27 @@ public:
         }
         return r;
     }
+    // The model under K transforms of its own frame against itself (stocs_symmetry_errors; no reference counterpart): sym16 holds K x 16
+    // floats, column-major; reach is the largest distance at which a transformed point still has a neighbour.  One record per transform.
+    // Empty on error (the text goes to the log).
+    std::vector<stocs_symmetry_error> symmetry_errors(const std::vector<float>& sym16, float reach, float cos_normal = 0.8660254037844387f) {
+        const int K = (int)(sym16.size() / 16);
+        stocs_symmetry_params p;
+        p.reach = reach; p.cos_normal = cos_normal; p.reserved[0] = p.reserved[1] = 0;
+        std::vector<stocs_symmetry_error> r((size_t)K);
+        if (K > 0 && stocs_symmetry_errors(ctx_, sym16.data(), K, &p, r.data()) != STOCS_OK) {
+            *log_ << "symmetry_errors failed: " << stocs_last_error() << std::endl;
+            r.clear();
+        }
+        return r;
+    }
+    // The model's symmetry axes and the set they generate (stocs_find_symmetries): see SymmetryResult above the class.  ok == false on error (the
+    // text goes to the log).  center3 NULL: the model's centroid.
+    SymmetryResult find_symmetries(const stocs_symmetry_search& search = default_symmetry_search(), const float* center3 = NULL) {
+        SymmetryResult r = find_symmetries_of(ctx_, search, center3);
+        if (!r.ok) *log_ << "find_symmetries failed: " << stocs_last_error() << std::endl;
+        return r;
+    }
     float model_diameter() {
         float d = -1.0f;
         if (stocs_model_diameter(ctx_, &d) != STOCS_OK) {
@@ -1038,6 +1091,35 @@ inline std::vector<float> symmetry_set(const float sym3[3], int n_continuous = 7
     std::vector<float> out((size_t)(K > 0 ? K : 0) * 16);
     if (K < 1 || stocs_symmetry_set(sym3, n_continuous, center3, out.data(), K, &K) != STOCS_OK) out.clear();
     return out;
+}
+
+// Not in the reference: the closure of generators (n x 16 floats, column-major) under composition (stocs_symmetry_close): K x 16 floats,
+// entry 0 the identity; *truncated (when given) says that the closure stopped at cap.  Empty on error.
+inline std::vector<float> symmetry_close(const std::vector<float>& gen16, float same_deg = 1.25f, int cap = STOCS_POSE_SYM_MAX, bool* truncated = NULL) {
+    std::vector<float> out((size_t)(cap > 0 ? cap : 0) * 16);
+    int K = 0, tr = 0;
+    if (stocs_symmetry_close(gen16.data(), (int)(gen16.size() / 16), same_deg, out.data(), cap, &K, &tr) != STOCS_OK) K = 0;
+    out.resize((size_t)K * 16);
+    if (truncated) *truncated = tr != 0;
+    return out;
+}
+
+// Not in the reference: the symmetries of a sampled model file (model_search.ply, as pre_process_model writes it) without a scene: a
+// context on the model alone (a one-point scene, no index), then stocs_find_symmetries.  Throws when the file or the context fails.
+inline SymmetryResult find_model_symmetries(const std::string& model_location, const stocs_symmetry_search& search = default_symmetry_search()) {
+    ModelCloud m;
+    read_ply(model_location, &m, true);
+    const float sp[3] = {0, 0, 1}, sn[3] = {0, 0, -1}, spr[1] = {1.0f};
+    stocs_params prm;
+    stocs_default_params(&prm);
+    stocs_ctx* ctx = NULL;
+    if (stocs_ctx_create(&prm, sp, sn, spr, NULL, 1, m.pos.data(), m.nrm.data(), m.size(), 0, -1, &ctx) != STOCS_OK)
+        throw std::runtime_error(std::string("stocs_ctx_create: ") + stocs_last_error());
+    SymmetryResult r = find_symmetries_of(ctx, search, NULL);
+    const std::string msg = r.ok ? std::string() : std::string("stocs_find_symmetries: ") + stocs_last_error();
+    stocs_ctx_destroy(ctx);
+    if (!r.ok) throw std::runtime_error(msg);
+    return r;
 }
 
 // Not in the reference: which hypotheses of several objects form one consistent explanation of the frame (stocs_scene_footprints /

@@ -701,6 +701,124 @@ int stocs_pose_errors_sym_detail(stocs_ctx* ctx, const float* est_pose16_camera,
                                  const stocs_camera* cam, uint64_t* add_fix /*K*/, float* max3 /*K*/, float* max2 /*K*/);
 int stocs_symmetry_set(const float sym3[3], int n_continuous, const float* center3 /* NULL: origin */, float* out16, int cap, int* K);
 
+/* ---- finding a model's symmetries: self-distance of the model under K transforms, candidate axes, closure, the search (no
+ * reference counterpart).  stocs_symmetry_errors scores K transforms of the MODEL frame (column-major 4x4 as sym16_model of
+ * stocs_pose_errors_sym, S_ab = S[4b + a], s_a = S[12 + a]) by how well the transformed model lies on the untransformed one.  The
+ * points m_i are those handed to stocs_ctx_create, the normals n_i those normals as the context keeps them: divided by their float
+ * length (x x + (y y + z z), correctly rounded root, three divisions) where that length's square is > 0, else as given.  Per transform,
+ * all in float, every operation a single IEEE add / sub / mul / sqrt, no contraction (r and q of stocs_pose_errors):
+ *   1. p(i) = step 1 of stocs_pose_errors under S;  D(i, j) = step 2 there with d = p(i) - m_j (the target is NOT transformed).
+ *   2. Dmin_i = min_j D(i, j), starting at +inf and replaced only on `<`; nn_i the lowest j that attains it.  Point i is MATCHED iff
+ *      Dmin_i <= reach * reach (one float product, inclusive) and Dmin_i < +inf, else FAR.  Detail of a far point: nn_i = -1, s_i = +inf, dot_i = 0.
+ *   3. s_i = r(Dmin_i) for matched points;  c_i = s_i if matched, else reach;  sum_fix = sum over ALL i of q(c_i);
+ *      mean = (float)((double)sum_fix / 2^32 / (double)M);  max = max of s_i over matched points, 0 when there are none;
+ *      n_far = the count of far points.
+ *   4. n'_a = S_a0 n_x + (S_a1 n_y + S_a2 n_z) of point i's normal, t the normal of target nn_i:
+ *      dot_i = n'_x t_x + (n'_y t_y + n'_z t_z);  n_normal_bad counts the matched points with !(dot_i >= cos_normal): a NaN is bad.
+ *   Integer sums, maxima taken on bits: a record is bitwise independent of the batch it shares, of its position there and of any
+ *   reduction order; valid = 1, reserved = 0.  tests/symmetry_ref.py restates it in float32 numpy.
+ * Identity with stocs_pose_errors_detail: with the identity as ground truth g(j) there is m_j up to the sign of zero, which the squares
+ * of step 2 remove, so stocs_pose_errors_detail(S, I) yields s and nn from the identical expressions: wherever a point is matched this
+ * call's s_i and nn_i equal them bit for bit.
+ * stocs_symmetry_errors_detail gives s, nn and dot (M entries each, any may be NULL) of ONE transform.
+ * Checked in this order: a NULL ctx and K < 0 are STOCS_ERR_INVALID; K == 0 is then a no-op that looks at no other argument; a NULL
+ * transform, parameter or result pointer, a non-finite entry among a transform's twelve used entries, !(reach > 0), a non-finite
+ * reach or one whose float square is below the smallest normal float (about 1.1e-19 m: the squares of step 1 would underflow), and a workspace demand (96 K bytes) above STOCS_REFINE_ROBUST_MAX_WORKSPACE_BYTES are STOCS_ERR_INVALID (the detail form: a
+ * NULL ctx, transform or parameters, the same value checks).  cos_normal is not checked: NaN calls every matched point bad.
+ * The grid.  The target never moves, so it is binned once per (context, reach) on the host into a uniform grid over the model's
+ * bounding box: cell starts plus the points sorted by cell, uploaded into a grow-only block of this feature's own; another reach
+ * rebuilds it.  A second call at the same reach and the same or a smaller K allocates nothing (stocs_device_alloc_count).
+ * Cell edge h = (float) max(reach * 65 / 64, largest box extent / STOCS_SYMMETRY_GRID_SPAN) in double, inv = 1.f / h; the cell of x
+ * along axis a is floorf((x_a - o_a) * inv), o the box minimum: ONE float expression (csrc/symmetry.h) that the host runs on the
+ * targets and the device on the queries.  The walk over the 27 cells about a query's cell misses no target with D <= reach * reach:
+ * the comment in csrc/symmetry.h gives the argument.  Cells are visited in no index order, so the running minimum is kept on (D, j)
+ * keys.  A query outside the box finds fewer cells or none; the normals are read once per query by index.
+ * The kernel (csrc/symmetry.hip): a workgroup of STOCS_SYMMETRY_THREADS threads owns one transform, read as wave-uniform scalars; a
+ * lane takes the queries tid, tid + STOCS_SYMMETRY_THREADS, ...; per-lane accumulators are reduced once (shuffles, LDS) and stored
+ * plainly: no atomics, no memset.  A call of more than STOCS_SYMMETRY_MAX_LAUNCH transforms is several launches.  On the context's
+ * stream: one upload through the pinned block, one read-back of K records, one synchronisation.  stocs_last_call_timing(which = 6)
+ * gives the host steps of the last stocs_symmetry_errors and, with "device_clock" on, the HIP-event time of its launches.
+ *
+ * Host helpers (no device work):
+ * stocs_symmetry_axes writes n_axes >= 3 candidate directions: entries 0, 1, 2 are exactly x, y, z; entry 3 + k (k = 0 .. L - 1,
+ * L = n_axes - 3) is the Fibonacci lattice point of the hemisphere z > 0:  z = 1 - (k + 0.5) / L,  phi = k * pi * (3 - sqrt(5)),
+ * (sqrt(1 - z z) cos phi, sqrt(1 - z z) sin phi, z), normalised, all in double, rounded once.  The lattice's spacing is taken as
+ * sqrt(2 pi / L) radians (the square root of the area per point).  n_axes < 3 is STOCS_ERR_INVALID with *n = 0; otherwise *n always
+ * receives n_axes, and cap < n_axes or a NULL axes3 is STOCS_ERR_INVALID and writes nothing else.
+ * stocs_symmetry_rotation writes T(c) R T(-c), R the Rodrigues rotation c I + s [a]x + (1 - c) a a^T by angle_deg about axis3
+ * normalised in double (a zero or non-finite axis or angle or centre: STOCS_ERR_INVALID), c = center3 (NULL: origin); computed in double
+ * and rounded once, no -0 entries; an angle that is a multiple of 90 degrees takes cos and sin exactly from {0, +-1}, so about a
+ * coordinate axis the entries are exactly 0 and +-1 as stocs_symmetry_set's are.
+ * stocs_symmetry_close closes n_gen generators under composition, breadth first: the list starts with the identity; for every kept
+ * entry g in list order and every generator h in the order given, the product h g (in double, on the generators widened once) is
+ * appended when it is NEW.  NEW: against every kept entry either the relative rotation exceeds same_deg (its trace is below
+ * 1 + 2 cos same_deg) or the translations differ by more than same_deg in radians times the largest translation norm among the
+ * generators.  Entries are rounded once on output, entry 0 is the identity, the order is deterministic.  It stops at cap
+ * (1 .. STOCS_POSE_SYM_MAX; outside: STOCS_ERR_INVALID) with *truncated = 1 when a new entry found no room -- two continuous axes, as
+ * on a sphere, do that; not an error.  *K receives the count written.  n_gen == 0 gives the identity alone.
+ *
+ * stocs_find_symmetries: deterministic host logic around batched stocs_symmetry_errors calls with reach = tol_max and the search's
+ * cos_normal.  c = center3, or with NULL the centroid of the model points summed in double in index order, rounded once to float.
+ * G(a, n) is stocs_symmetry_rotation(a, 360 / n (double), c).  tol_max <= 0 stands for 0.1f * stocs_model_diameter.
+ *   1. Coarse pass.  Every direction d of stocs_symmetry_axes(n_axes) with every order n = 2 .. max_order, candidate index
+ *      d * (max_order - 1) + (n - 2), scored in ONE call; ranked by (mean, index) ascending.
+ *   2. Refinement.  Walk the ranking and keep a candidate when its axis is more than same_deg from every kept axis, up to sign, until
+ *      n_refine are kept.  Then `rounds` rounds, each ONE scoring call for all kept candidates: round r = 0 .. rounds - 1 has the
+ *      half-angle theta = spacing / 2^r (spacing of the lattice as above; n_axes == 3: pi / 4).  About the current axis a (float,
+ *      widened): e = the coordinate axis of smallest |a_e| (lowest index on ties), u = normalise(e - (e . a) a), v = a x u; direction
+ *      k = 0 .. n_local - 1 is normalise(a + tan(theta sqrt((k + 0.5) / n_local)) (cos(k g) u + sin(k g) v)), g = pi (3 - sqrt 5),
+ *      in double, rounded once; each is scored at the candidate's own order.  The candidate moves to the direction of lowest mean when
+ *      that is `<` its current mean (lowest k on ties).
+ *   3. Decision.  Every kept axis with every order 2 .. max_order in ONE call.  Order n PASSES iff n_far == 0, max <= tol_max and
+ *      (float)n_normal_bad <= max_normal_bad * (float)M.  The axis's order is the largest passing n, 0 (continuous) when every n
+ *      passes; an axis where none passes is dropped.  Its max, mean and n_normal_bad are those of that n (continuous: of max_order).
+ *      Axes sorted by (mean, kept rank); one nearer than same_deg, up to sign, to an axis before it is dropped.
+ *   4. Output.  The axes best first (*n_axes receives their count; at most cap_axes are written).  The set is stocs_symmetry_close of
+ *      the generators G(a, order), a continuous axis giving G(a, n_continuous), whose powers are its n_continuous steps, with the
+ *      tolerance min(same_deg, 90 / n_continuous) and cap min(cap_set, STOCS_POSE_SYM_MAX).  sym3 is the clustering descriptor when
+ *      every axis lies within same_deg of a coordinate axis, up to sign, and has an order the descriptor names (2 -> 180, 4 -> 90,
+ *      continuous -> 360) and no two axes lie that near the SAME coordinate axis (two axes more than same_deg apart can); otherwise sym3 is zeros and flags carries
+ *      STOCS_SYMMETRY_DESCRIPTOR_INEXACT.  For a y descriptor the caveat at stocs_symmetry_set applies.  STOCS_SYMMETRY_SET_TRUNCATED:
+ *      the closure stopped at its cap.  STOCS_SYMMETRY_NOTHING_FOUND: no axis; then K = 1, the identity, sym3 zeros.
+ * Defaults (stocs_default_symmetry_search): tol_max 0, cos_normal cos 30 degrees (the LCP's), max_normal_bad 1 (the count is reported,
+ * not used), n_axes 2048, max_order 6, n_continuous 72, n_refine 16, n_local 32, rounds 4, same_deg 6 (2 sin 6 degrees x half a diameter is 0.1 diameter: an axis farther off than that moves
+ * the model's rim by more than the default tolerance under a half turn).  Refused (STOCS_ERR_INVALID):
+ * NULL ctx, search, n_axes, K, sym3 or flags pointer; axes NULL with cap_axes > 0; set16 NULL or cap_set < 1; n_axes < 3, max_order
+ * < 2, n_continuous < 1, n_refine < 1, n_local < 1, rounds < 0, !(same_deg > 0), a non-finite tol_max or centre. ---- */
+#define STOCS_SYMMETRY_THREADS 256
+#define STOCS_SYMMETRY_MAX_LAUNCH 65535
+#define STOCS_SYMMETRY_GRID_SPAN 60
+#define STOCS_SYMMETRY_DESCRIPTOR_INEXACT 1
+#define STOCS_SYMMETRY_SET_TRUNCATED 2
+#define STOCS_SYMMETRY_NOTHING_FOUND 4
+typedef struct stocs_symmetry_params { float reach; float cos_normal; int32_t reserved[2]; } stocs_symmetry_params;
+typedef struct stocs_symmetry_error {
+    uint64_t sum_fix;          /* sum over ALL i of q(c_i) */
+    float    mean, max;        /* metres */
+    int32_t  n_far, n_normal_bad;
+    int32_t  valid, reserved;
+} stocs_symmetry_error;        /* 32 bytes */
+int stocs_symmetry_errors(stocs_ctx* ctx, const float* sym16_model, int K, const stocs_symmetry_params* p, stocs_symmetry_error* out);
+int stocs_symmetry_errors_detail(stocs_ctx* ctx, const float* sym16_model /* one */, const stocs_symmetry_params* p,
+                                 float* s /*M*/, int32_t* nn /*M*/, float* dot /*M*/);   /* any output may be NULL */
+int stocs_symmetry_axes(int n_axes, float* axes3, int cap, int* n);
+int stocs_symmetry_rotation(const float axis3[3], double angle_deg, const float* center3 /* NULL: origin */, float out16[16]);
+int stocs_symmetry_close(const float* gen16, int n_gen, float same_deg, float* out16, int cap, int* K, int* truncated);
+typedef struct stocs_symmetry_search {
+    float tol_max;          /* metres; <= 0: 0.1 x stocs_model_diameter, the project's recall threshold */
+    float cos_normal;       /* gate of the count */
+    float max_normal_bad;   /* accepted share of the model's points failing the gate */
+    int32_t n_axes;         /* coarse directions */
+    int32_t max_order;      /* discrete orders 2 .. max_order */
+    int32_t n_continuous;   /* steps of a continuous axis in the set */
+    int32_t n_refine, n_local, rounds;   /* axes refined, directions per cone, halvings */
+    float same_deg;         /* axes / transforms nearer than this are one */
+} stocs_symmetry_search;
+typedef struct stocs_symmetry_axis { float axis[3]; int32_t order; /* 0: continuous */ float max, mean; int32_t n_normal_bad, reserved; } stocs_symmetry_axis;
+void stocs_default_symmetry_search(stocs_symmetry_search* s);
+int stocs_find_symmetries(stocs_ctx* ctx, const stocs_symmetry_search* s, const float* center3 /* NULL: centroid */,
+                          stocs_symmetry_axis* axes, int cap_axes, int* n_axes, float* set16, int cap_set, int* K, float sym3[3], int* flags);
+
 /* ---- multi-instance selection (no reference counterpart: the reference returns one pose per object).  Of n hypotheses, which are
  * distinct instances and which are one instance found twice: walk them best first and keep one only if enough of the scene points it
  * explains are not explained by one kept before it.  stocs_select_instances takes n CENTRED-frame hypotheses (column-major, as
@@ -978,7 +1096,7 @@ int stocs_debug_sort_pairs(int device, const uint32_t* keys, const uint32_t* val
 int64_t stocs_device_alloc_count(void);
 /* host wall clock, in milliseconds, of the steps of the context's LAST stocs_find_congruent_all (which = 0),
  * stocs_make_transforms (1), stocs_verify_all (2), stocs_run_trials (3: its phases summed over the pieces of the batch), stocs_pose_errors
- * (4; with "device_clock" 1 also "device: kernel", the HIP-event time of its launches) or stocs_pose_errors_sym (5; likewise): always recorded (a few clock reads per call, no synchronisation of its
+ * (4; with "device_clock" 1 also "device: kernel", the HIP-event time of its launches) stocs_pose_errors_sym (5; likewise) or stocs_symmetry_errors (6; likewise): always recorded (a few clock reads per call, no synchronisation of its
  * own), so that a call that stalls -- tens of milliseconds instead of one -- names the step it stalled in.  Steps are host
  * intervals between the call's existing synchronisation points: "wait for the device" steps hold the GPU work, the others
  * host work and runtime calls; entries whose label starts with "device:" are HIP-event times of the kernel groups that

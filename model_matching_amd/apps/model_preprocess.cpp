@@ -2,8 +2,15 @@
 // models/<object>/textured_vertices.ply -> models/<object>/model_search.ply + models/<object>/ppf_map, through
 // stocs::pre_process_model (normals, voxel grid and the O(|M|^2) PPF index all on the GPU).
 //   model_preprocess <object_name> [--repo DIR] [--voxel 0.01] [--normal-radius 0.005] [--model-scale 1.0]
+//                    [--find-symmetry [--sym-tol m] [--sym-steps n]]
 // The reference edits these constants in the source per data set (README.md:42-60); the defaults are its YCB values.
+// --find-symmetry (not in the reference): after the index is written, search the sampled model for its symmetry axes
+// (stocs_find_symmetries; --sym-tol: the tolerance in metres, default a tenth of the diameter; --sym-steps: steps of a continuous axis,
+// default 72), print them, write models/<object>/symmetry.txt -- the text stocs_single --sym-file reads: 16 floats per transform,
+// column-major -- and print the --sym a,b,c line to use with it.
+#include <cstdio>
 #include <cstdlib>
+#include <fstream>
 #include <iostream>
 #include <string>
 
@@ -23,9 +30,16 @@ int main(int argc, char** argv) {
     }
     const std::string object_name = argv[1];
     if (const char* e = getenv("STOCS_REPO_PATH")) repo_path = e;
-    for (int i = 2; i + 1 < argc; i += 2) {
-        const std::string k = argv[i], v = argv[i + 1];
+    bool find_symmetry = false;
+    stocs_symmetry_search search = stocs::default_symmetry_search();
+    for (int i = 2; i < argc; i += 2) {
+        const std::string k = argv[i];
+        if (k == "--find-symmetry") { find_symmetry = true; --i; continue; }   // a flag: no value
+        if (i + 1 >= argc) break;   // a last option without its value is ignored, as it always was
+        const std::string v = argv[i + 1];
         if (k == "--repo") repo_path = v;
+        else if (k == "--sym-tol") search.tol_max = (float)atof(v.c_str());
+        else if (k == "--sym-steps") search.n_continuous = atoi(v.c_str());
         else if (k == "--voxel") voxel_size = (float)atof(v.c_str());
         else if (k == "--normal-radius") normal_radius = (float)atof(v.c_str());
         else if (k == "--model-scale") model_scale = (float)atof(v.c_str());
@@ -37,6 +51,32 @@ int main(int argc, char** argv) {
     try {
         stocs::pre_process_model(model_path + "/textured_vertices.ply", normal_radius, model_scale, 1.0f, voxel_size, ppf_tr_discretization, ppf_rot_discretization,
                                  model_path + "/model_search.ply", model_path + "/ppf_map");
+        if (find_symmetry) {
+            const stocs::SymmetryResult r = stocs::find_model_symmetries(model_path + "/model_search.ply", search);
+            std::cout << "symmetry axes: " << r.axes.size() << std::endl;
+            for (size_t k = 0; k < r.axes.size(); ++k) {
+                const stocs_symmetry_axis& a = r.axes[k];
+                char line[256];
+                snprintf(line, sizeof line, "symmetry axis %zu: axis=%.6f,%.6f,%.6f order=%d max=%.6f mean=%.6f n_normal_bad=%d", k, (double)a.axis[0], (double)a.axis[1],
+                         (double)a.axis[2], a.order, (double)a.max, (double)a.mean, a.n_normal_bad);
+                std::cout << line << std::endl;
+            }
+            const std::string sym_path = model_path + "/symmetry.txt";
+            std::ofstream f(sym_path.c_str());
+            for (size_t k = 0; k < r.set16.size() / 16; ++k) {
+                for (int e = 0; e < 16; ++e) {
+                    char num[32];
+                    snprintf(num, sizeof num, "%.9g", (double)r.set16[k * 16 + e]);
+                    f << num << (e == 15 ? "\n" : " ");
+                }
+            }
+            f.close();
+            if (!f) { std::cerr << "cannot write " << sym_path << std::endl; return 2; }
+            std::cout << "symmetry set: " << r.set16.size() / 16 << " transforms -> " << sym_path
+                      << ((r.flags & STOCS_SYMMETRY_SET_TRUNCATED) ? " (truncated)" : "") << ((r.flags & STOCS_SYMMETRY_NOTHING_FOUND) ? " (nothing found: the identity)" : "") << std::endl;
+            std::cout << "use: --sym " << r.sym3[0] << "," << r.sym3[1] << "," << r.sym3[2] << " --sym-file " << sym_path
+                      << ((r.flags & STOCS_SYMMETRY_DESCRIPTOR_INEXACT) ? "   (the descriptor cannot name these axes: cluster without it, evaluate with the file)" : "") << std::endl;
+        }
     } catch (const std::exception& e) {
         std::cerr << e.what() << std::endl;   // no GPU => loud failure
         return 2;

@@ -79,6 +79,29 @@ class PoseErrorSym(C.Structure):
                 ("k_add", C.c_int32), ("k_mssd", C.c_int32), ("k_mspd", C.c_int32), ("valid", C.c_int32)]
 
 
+class SymmetryParams(C.Structure):
+    _fields_ = [("reach", C.c_float), ("cos_normal", C.c_float), ("reserved", C.c_int32 * 2)]
+
+
+class SymmetryError(C.Structure):
+    _fields_ = [("sum_fix", C.c_uint64), ("mean", C.c_float), ("max", C.c_float), ("n_far", C.c_int32), ("n_normal_bad", C.c_int32),
+                ("valid", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SymmetrySearch(C.Structure):
+    _fields_ = [("tol_max", C.c_float), ("cos_normal", C.c_float), ("max_normal_bad", C.c_float), ("n_axes", C.c_int32), ("max_order", C.c_int32),
+                ("n_continuous", C.c_int32), ("n_refine", C.c_int32), ("n_local", C.c_int32), ("rounds", C.c_int32), ("same_deg", C.c_float)]
+
+
+class SymmetryAxis(C.Structure):
+    _fields_ = [("axis", C.c_float * 3), ("order", C.c_int32), ("max", C.c_float), ("mean", C.c_float), ("n_normal_bad", C.c_int32),
+                ("reserved", C.c_int32)]
+
+
+SYMMETRY_DESCRIPTOR_INEXACT, SYMMETRY_SET_TRUNCATED, SYMMETRY_NOTHING_FOUND = 1, 2, 4
+POSE_SYM_MAX = 4096
+
+
 class InstanceParams(C.Structure):
     _fields_ = [("max_instances", C.c_int32), ("min_points", C.c_int32), ("min_exclusive_fraction", C.c_float)]
 
@@ -205,6 +228,13 @@ SIGNATURES = {
     "stocs_pose_errors_sym": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, C.POINTER(Camera), C.POINTER(PoseErrorSym)]),
     "stocs_pose_errors_sym_detail": (C.c_int, [_vp, _fp, _fp, _fp, C.c_int, C.POINTER(Camera), C.POINTER(C.c_uint64), _fp, _fp]),
     "stocs_symmetry_set": (C.c_int, [_fp, C.c_int, _fp, _fp, C.c_int, _intp]),
+    "stocs_symmetry_errors": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(SymmetryParams), C.POINTER(SymmetryError)]),
+    "stocs_symmetry_errors_detail": (C.c_int, [_vp, _fp, C.POINTER(SymmetryParams), _fp, _ip, _fp]),
+    "stocs_symmetry_axes": (C.c_int, [C.c_int, _fp, C.c_int, _intp]),
+    "stocs_symmetry_rotation": (C.c_int, [_fp, C.c_double, _fp, _fp]),
+    "stocs_symmetry_close": (C.c_int, [_fp, C.c_int, C.c_float, _fp, C.c_int, _intp, _intp]),
+    "stocs_default_symmetry_search": (None, [C.POINTER(SymmetrySearch)]),
+    "stocs_find_symmetries": (C.c_int, [_vp, C.POINTER(SymmetrySearch), _fp, C.POINTER(SymmetryAxis), C.c_int, _intp, _fp, C.c_int, _intp, _fp, _intp]),
     "stocs_default_render_params": (None, [C.POINTER(RenderParams)]),
     "stocs_render_poses": (C.c_int, [_vp, _fp, C.c_int, C.c_int, C.POINTER(RenderParams), _vp, C.c_int]),
     "stocs_render_resolve": (C.c_int, [_vp, _fp, C.c_int, C.c_int, C.POINTER(RenderParams), _vp, C.POINTER(RenderResult)]),

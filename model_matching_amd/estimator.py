@@ -46,6 +46,12 @@ assert _POSE_ERROR_DTYPE.itemsize == C.sizeof(capi.PoseError)
 _POSE_ERROR_SYM_DTYPE = np.dtype([("add_fix", np.uint64), ("add", np.float32), ("mssd", np.float32), ("mspd", np.float32), ("reserved_f", np.float32),
                                   ("k_add", np.int32), ("k_mssd", np.int32), ("k_mspd", np.int32), ("valid", np.int32)])
 assert _POSE_ERROR_SYM_DTYPE.itemsize == C.sizeof(capi.PoseErrorSym)
+_SYMMETRY_ERROR_DTYPE = np.dtype([("sum_fix", np.uint64), ("mean", np.float32), ("max", np.float32), ("n_far", np.int32), ("n_normal_bad", np.int32),
+                                  ("valid", np.int32), ("reserved", np.int32)])
+assert _SYMMETRY_ERROR_DTYPE.itemsize == C.sizeof(capi.SymmetryError)
+_SYMMETRY_AXIS_DTYPE = np.dtype([("axis", np.float32, (3,)), ("order", np.int32), ("max", np.float32), ("mean", np.float32), ("n_normal_bad", np.int32),
+                                 ("reserved", np.int32)])
+assert _SYMMETRY_AXIS_DTYPE.itemsize == C.sizeof(capi.SymmetryAxis)
 _RENDER_DTYPE = np.dtype([(f[0], np.int32) for f in capi.RenderResult._fields_])
 assert _RENDER_DTYPE.itemsize == C.sizeof(capi.RenderResult)
 _INSTANCE_DTYPE = np.dtype([("rank", np.int32), ("own", np.int32), ("exclusive", np.int32), ("lcp", np.float32)])
@@ -484,6 +490,53 @@ class StocsEstimator:
                                                        af.ctypes.data_as(C.POINTER(C.c_uint64)), m3.ctypes.data_as(capi._fp), m2.ctypes.data_as(capi._fp)))
         return af[:K], m3[:K], m2[:K]
 
+    @staticmethod
+    def _symmetry_params(reach, cos_normal):
+        return capi.SymmetryParams(float(reach), float(cos_normal), (C.c_int32 * 2)(0, 0))
+
+    def symmetry_errors(self, transforms, reach, cos_normal=0.8660254037844387):
+        """The model under K transforms of its own frame against itself (stocs_symmetry_errors): transforms K column-major 4x4, reach the
+        largest distance at which a transformed point still has a neighbour -> a structured array with the fields of
+        stocs_symmetry_error, one record per transform: the clamped mean and the largest nearest-neighbour distance in metres, the count
+        of points with no neighbour within reach, and the count of matched points whose normals disagree."""
+        S, pS = capi.f32(transforms)
+        if S.size % 16:
+            raise ValueError("symmetry_errors: transforms are 16 floats each")
+        K = S.size // 16
+        prm = self._symmetry_params(reach, cos_normal)
+        buf = (capi.SymmetryError * max(K, 1))()
+        capi.check(self.L.stocs_symmetry_errors(self.h, pS, K, C.byref(prm), buf))
+        return np.frombuffer(buf, dtype=_SYMMETRY_ERROR_DTYPE, count=K).copy()
+
+    def symmetry_errors_detail(self, transform, reach, cos_normal=0.8660254037844387):
+        """One transform (stocs_symmetry_errors_detail) -> (s, nn, dot), one entry per model point: the distance to the nearest
+        untransformed point (+inf beyond reach), that point's index (-1 beyond reach) and the cosine between the two normals."""
+        S, pS = capi.f32(transform)
+        if S.size != 16:
+            raise ValueError("symmetry_errors_detail: one transform of 16 floats")
+        prm = self._symmetry_params(reach, cos_normal)
+        s, nn, dot = np.empty(self.nM, np.float32), np.empty(self.nM, np.int32), np.empty(self.nM, np.float32)
+        capi.check(self.L.stocs_symmetry_errors_detail(self.h, pS, C.byref(prm), s.ctypes.data_as(capi._fp), nn.ctypes.data_as(capi._ip),
+                                                       dot.ctypes.data_as(capi._fp)))
+        return s, nn, dot
+
+    def find_symmetries(self, center=None, cap_set=capi.POSE_SYM_MAX, **search):
+        """The model's symmetry axes and the set they generate (stocs_find_symmetries): center None (the centroid) or the point the axes
+        pass through, search any field of stocs_symmetry_search -> (axes, set, sym3, flags): a structured array with the fields of
+        stocs_symmetry_axis, best first; (K, 16) float32 transforms for pose_errors_sym, entry 0 the identity; the clustering descriptor
+        (zeros when it cannot name what was found: capi.SYMMETRY_DESCRIPTOR_INEXACT in flags); flags."""
+        prm = symmetry_search(**search)
+        c3 = None if center is None else (C.c_float * 3)(*[float(x) for x in center])
+        cap_axes = int(prm.n_refine)
+        axes = (capi.SymmetryAxis * max(cap_axes, 1))()
+        out = np.empty((max(int(cap_set), 1), 16), np.float32)
+        n, K, flags = C.c_int(0), C.c_int(0), C.c_int(0)
+        sym3 = (C.c_float * 3)()
+        capi.check(self.L.stocs_find_symmetries(self.h, C.byref(prm), c3, axes, cap_axes, C.byref(n), out.ctypes.data_as(capi._fp), int(cap_set), C.byref(K),
+                                                sym3, C.byref(flags)))
+        return (np.frombuffer(axes, dtype=_SYMMETRY_AXIS_DTYPE, count=min(n.value, cap_axes)).copy(), out[:K.value].copy(),
+                np.array(list(sym3), np.float32), flags.value)
+
     def model_diameter(self):
         """The largest distance between two model points (stocs_model_diameter), computed on the device once per context."""
         d = C.c_float()
@@ -917,6 +970,47 @@ def symmetry_set(sym3, n_continuous=72, center=None):
     out = np.empty((K.value, 16), np.float32)
     capi.check(L.stocs_symmetry_set(s3, int(n_continuous), c3, out.ctypes.data_as(capi._fp), K.value, C.byref(K)))
     return out
+
+
+def symmetry_search(**kw):
+    """stocs_symmetry_search with its defaults (stocs_default_symmetry_search), fields overridden by keyword"""
+    prm = capi.SymmetrySearch()
+    capi.load().stocs_default_symmetry_search(C.byref(prm))
+    for k, v in kw.items():
+        if k not in dict(prm._fields_):
+            raise TypeError("symmetry_search: unknown field %r" % k)
+        setattr(prm, k, v)
+    return prm
+
+
+def symmetry_axes(n_axes=2048):
+    """The candidate directions of the symmetry search (stocs_symmetry_axes) -> (n_axes, 3) float32: x, y, z, then a Fibonacci lattice on
+    the hemisphere z > 0."""
+    L = capi.load()
+    out = np.empty((max(int(n_axes), 1), 3), np.float32)
+    n = C.c_int(0)
+    capi.check(L.stocs_symmetry_axes(int(n_axes), out.ctypes.data_as(capi._fp), int(n_axes), C.byref(n)))
+    return out[:n.value]
+
+
+def symmetry_rotation(axis, angle_deg, center=None):
+    """The rotation by angle_deg about axis through center (stocs_symmetry_rotation; None: the origin) -> 16 float32, column-major"""
+    a3 = (C.c_float * 3)(*[float(x) for x in axis])
+    c3 = None if center is None else (C.c_float * 3)(*[float(x) for x in center])
+    out = np.empty(16, np.float32)
+    capi.check(capi.load().stocs_symmetry_rotation(a3, float(angle_deg), c3, out.ctypes.data_as(capi._fp)))
+    return out
+
+
+def symmetry_close(generators, same_deg=1.25, cap=capi.POSE_SYM_MAX):
+    """The closure of generators (n, 16) under composition (stocs_symmetry_close) -> ((K, 16) float32 with the identity first, truncated)"""
+    G, pG = capi.f32(generators)
+    if G.size % 16:
+        raise ValueError("symmetry_close: generators are 16 floats each")
+    out = np.empty((max(int(cap), 1), 16), np.float32)
+    K, tr = C.c_int(0), C.c_int(0)
+    capi.check(capi.load().stocs_symmetry_close(pG, G.size // 16, float(same_deg), out.ctypes.data_as(capi._fp), int(cap), C.byref(K), C.byref(tr)))
+    return out[:K.value].copy(), bool(tr.value)
 
 
 BOP_MSSD_THRESHOLDS = tuple(0.05 * i for i in range(1, 11))     # of the diameter
