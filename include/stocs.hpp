@@ -537,10 +537,31 @@ public:
     int run_trials(int n_trials, uint64_t first_seed, int number_of_bases, int maximum_congruent_sets, float dispersion, const stocs_trial_post& post,
                    std::vector<TrialResult>* results, std::vector<std::vector<PoseCandidate*> >* hypotheses,
                    std::vector<std::vector<PoseCandidate*> >* refined = NULL) {
+        return run_trials_post_impl(n_trials, first_seed, number_of_bases, maximum_congruent_sets, dispersion, post, NULL, results, hypotheses, refined);
+    }
+    // ... with the kept hypotheses refined by the robust form inside the batch (stocs_run_trials_post_robust): keep_ratio and
+    // max_normal_deg as refine_pose_candidates_robust takes them (< 0: no gate; the angle becomes a cosine once:
+    // (float)cos((double)deg * pi / 180)).  keep_ratio = 1 and no gate: bitwise the form above.
+    int run_trials(int n_trials, uint64_t first_seed, int number_of_bases, int maximum_congruent_sets, float dispersion, const stocs_trial_post& post,
+                   std::vector<TrialResult>* results, std::vector<std::vector<PoseCandidate*> >* hypotheses,
+                   std::vector<std::vector<PoseCandidate*> >* refined, float keep_ratio, float max_normal_deg) {
+        const float robust[2] = {keep_ratio, robust_min_cos(max_normal_deg)};
+        return run_trials_post_impl(n_trials, first_seed, number_of_bases, maximum_congruent_sets, dispersion, post, robust, results, hypotheses, refined);
+    }
+    // degrees -> the min_normal_cos of the robust entry points: one conversion, the cosine in double (< 0: gate off)
+    static float robust_min_cos(float max_normal_deg) {
+        return max_normal_deg >= 0.0f ? (float)std::cos((double)max_normal_deg * 3.141592653589793 / 180.0) : -2.0f;
+    }
+
+private:
+    // robust: NULL, or (keep_ratio, min_normal_cos)
+    int run_trials_post_impl(int n_trials, uint64_t first_seed, int number_of_bases, int maximum_congruent_sets, float dispersion, const stocs_trial_post& post,
+                             const float* robust, std::vector<TrialResult>* results, std::vector<std::vector<PoseCandidate*> >* hypotheses,
+                             std::vector<std::vector<PoseCandidate*> >* refined) {
         hyp_store_.clear();
         if (hypotheses) hypotheses->clear();
         if (refined) refined->clear();
-        const int best = run_trials_impl(n_trials, first_seed, number_of_bases, maximum_congruent_sets, dispersion, &post, results);
+        const int best = run_trials_impl(n_trials, first_seed, number_of_bases, maximum_congruent_sets, dispersion, &post, results, robust);
         if (best == -2) return -1;
         std::vector<stocs_trial_hypothesis> h;
         for (int t = 0; t < n_trials; ++t) {
@@ -564,15 +585,16 @@ public:
         return best;
     }
 
-private:
     // -2: the library call failed (the public forms return -1 then, as for "no pose")
     int run_trials_impl(int n_trials, uint64_t first_seed, int number_of_bases, int maximum_congruent_sets, float dispersion, const stocs_trial_post* post,
-                        std::vector<TrialResult>* results) {
+                        std::vector<TrialResult>* results, const float* robust = NULL) {
         std::vector<uint64_t> seeds((size_t)std::max(n_trials, 0));
         for (int t = 0; t < n_trials; ++t) seeds[(size_t)t] = first_seed + (uint64_t)t;
         std::vector<stocs_trial_result> r((size_t)std::max(n_trials, 1));
         la_n_ = 0; la_in_ctx_ = false; batched_ = false; fetched_ = false; n_batched_ = 0;
-        const int rc = post ? stocs_run_trials_post(ctx_, has_edge_map() ? 1 : 0, n_trials, seeds.data(), number_of_bases, dispersion, maximum_congruent_sets, 0,
+        const int rc = post && robust ? stocs_run_trials_post_robust(ctx_, has_edge_map() ? 1 : 0, n_trials, seeds.data(), number_of_bases, dispersion,
+                                                                     maximum_congruent_sets, 0, post, robust[0], robust[1], r.data())
+                       : post ? stocs_run_trials_post(ctx_, has_edge_map() ? 1 : 0, n_trials, seeds.data(), number_of_bases, dispersion, maximum_congruent_sets, 0,
                                                     post, r.data())
                             : stocs_run_trials(ctx_, has_edge_map() ? 1 : 0, n_trials, seeds.data(), number_of_bases, dispersion, maximum_congruent_sets, 0, r.data());
         if (rc != STOCS_OK) return post ? -2 : -1;
@@ -661,7 +683,7 @@ public:
         }
         stocs_refine_robust_params prm;
         prm.max_iterations = max_iterations; prm.max_correspondence_distance = max_correspondence_distance; prm.keep_ratio = keep_ratio;
-        prm.min_normal_cos = max_normal_deg >= 0.0f ? (float)std::cos((double)max_normal_deg * 3.141592653589793 / 180.0) : -2.0f;
+        prm.min_normal_cos = robust_min_cos(max_normal_deg);
         if (n > 0 && stocs_refine_poses_robust(ctx_, T.data(), n, NULL, 0, &prm, NULL, P.data(), l.data(), NULL, NULL, NULL) != STOCS_OK) {
             *log_ << "refine_pose_candidates_robust failed: " << stocs_last_error() << std::endl;
             return out;
@@ -689,13 +711,26 @@ public:
     // text goes to the log, as compute_best_transform reports errors).
     std::vector<PoseCandidate*> track_poses(const std::vector<PoseCandidate*>& priors, const stocs_track_params& prm = default_track_params(),
                                             std::vector<stocs_track_result>* results = NULL) {
+        return track_poses_impl(priors, prm, NULL, results);
+    }
+    // ... with the final incumbents refined by the robust form (stocs_track_poses_robust): keep_ratio and max_normal_deg as
+    // refine_pose_candidates_robust takes them (< 0: no gate).  keep_ratio = 1 and no gate: bitwise the form above.
+    std::vector<PoseCandidate*> track_poses(const std::vector<PoseCandidate*>& priors, const stocs_track_params& prm, float keep_ratio, float max_normal_deg,
+                                            std::vector<stocs_track_result>* results = NULL) {
+        const float robust[2] = {keep_ratio, robust_min_cos(max_normal_deg)};
+        return track_poses_impl(priors, prm, robust, results);
+    }
+
+private:
+    std::vector<PoseCandidate*> track_poses_impl(const std::vector<PoseCandidate*>& priors, const stocs_track_params& prm, const float* robust,
+                                                 std::vector<stocs_track_result>* results) {
         tracked_store_.clear();
         std::vector<PoseCandidate*> out;
         const int n = (int)priors.size();
         std::vector<float> P((size_t)n * 16);
         for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], priors[(size_t)i]->transform.data(), 64);
         std::vector<stocs_track_result> r((size_t)std::max(n, 1));
-        if (n > 0 && stocs_track_poses(ctx_, P.data(), n, &prm, r.data()) != STOCS_OK) {
+        if (n > 0 && (robust ? stocs_track_poses_robust(ctx_, P.data(), n, &prm, robust[0], robust[1], r.data()) : stocs_track_poses(ctx_, P.data(), n, &prm, r.data())) != STOCS_OK) {
             *log_ << "track_poses failed: " << stocs_last_error() << std::endl;
             return out;
         }
@@ -712,6 +747,7 @@ public:
         return out;
     }
 
+public:
     // Depth-image verification (stocs_ctx_set_frame / stocs_depth_check_poses; no reference counterpart): the camera frame this
     // estimator's scene came from -- depth and, optionally, the object's class-probability image (may be NULL), image_height x
     // image_width, row-major -- handed to the context once; then any number of camera-frame hypotheses (get_pose_candidates, the

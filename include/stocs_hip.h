@@ -293,6 +293,32 @@ typedef struct stocs_trial_hypothesis {
 /* the hypotheses of one trial of the last batch, in cluster order (descending lcp); a trial without a pose has none.  The batch ran
  * without post: STOCS_ERR_STATE; out != NULL and cap < the count: STOCS_ERR_CAPACITY (*n is the count either way) */
 int stocs_trials_get_hypotheses(stocs_ctx* ctx, int trial, stocs_trial_hypothesis* out, int cap, int* n);
+/* ---- stocs_run_trials_post with the kept hypotheses refined by the trimmed, normal-gated form (stocs_refine_poses_robust, below)
+ * instead of the plain one.  Iterations and correspondence distance are post's (refine_iterations, max_correspondence_distance);
+ * keep_ratio and min_normal_cos mean what they mean in stocs_refine_robust_params, under the same rules: keep_ratio in (0, 1] and
+ * not NaN; min_normal_cos <= 1 and not NaN, below -1 turns the gate off.  Outside them, or post == NULL: STOCS_ERR_INVALID; every
+ * other argument is checked as stocs_run_trials_post checks it.  The contract:
+ *   - everything up to and including the clustering is stocs_run_trials_post's, bit for bit;
+ *   - with refine_iterations > 0, trial t's refined fields are bitwise what
+ *         stocs_refine_poses_robust(the kept candidates' centred T16, n, NULL, 0,
+ *                                   {refine_iterations, max_correspondence_distance, keep_ratio, min_normal_cos}, ...)
+ *     gives when run on the same context right after that trial alone; in instance mode the pose is rescored against the trial's own
+ *     decayed class probabilities, as in stocs_run_trials_post, and the gate reads the base scene's normals (the decay changes the
+ *     weights, never a normal);
+ *   - n_correspondences is k of the last evaluated iteration (the kept pairs); n_cand is not reported (the record is ABI);
+ *   - the hypotheses are read with stocs_trials_get_hypotheses, unchanged;
+ *   - with keep_ratio == 1 and the gate off, every byte of every record and result equals stocs_run_trials_post's.
+ * The robust workspace takes 8 bytes per (hypothesis, scene point), and a piece's slots are an upper bound (min(count + 1,
+ * candidates) per trial) on the whole scene: a piece refines its slots in GROUPS of consecutive slots that share the workspace, a
+ * group being the largest run whose demand (group x scene points x 8 bytes) stays within STOCS_REFINE_ROBUST_MAX_WORKSPACE_BYTES,
+ * and at least one slot.  Only a scene too large for ONE slot (scene points x 8 bytes above the limit) is STOCS_ERR_INVALID.  The
+ * environment variable STOCS_REFINE_ROBUST_GROUP_BYTES, read per call, lowers the limit (tests: forces several groups).  Results
+ * are bitwise independent of the grouping and of the pieces.  The workspace is grow-only (stocs_refine_robust_workspace): a repeated
+ * call of the same size allocates nothing.  One read-back and one synchronisation per piece, as stocs_run_trials_post.
+ * stocs_last_call_timing(which = 3) reports the groups of the last call next to its pieces. ---- */
+int stocs_run_trials_post_robust(stocs_ctx* ctx, int mode, int n_trials, const uint64_t* seeds, int n_attempts, float dispersion, int max_per_base,
+                                 int keep_details, const stocs_trial_post* post /* not NULL */, float keep_ratio, float min_normal_cos,
+                                 stocs_trial_result* out /* n_trials, may be NULL */);
 
 /* arg-max of n device-resident scores on the device: *key = max over i of
  * stocs_pack_best(lcp[i], id_offset + i), 0 when no score is positive (first maximum wins, as the
@@ -535,6 +561,16 @@ typedef struct stocs_track_result {
     int32_t n_correspondences, iterations;/* stocs_refine_poses's; == lcp / pose16 and 0, 0 without refinement        */
 } stocs_track_result;
 int stocs_track_poses(stocs_ctx* ctx, const float* prior_pose16_camera, int n_priors, const stocs_track_params* p, stocs_track_result* out);
+/* stocs_track_poses with the final incumbents refined by the trimmed, normal-gated form.  The rounds are stocs_track_poses's, bit
+ * for bit (candidates, scores, incumbents, stocs_track_get_round); with refine_iterations > 0, refined_*, n_correspondences (k of
+ * the last evaluated iteration) and iterations are bitwise stocs_refine_poses_robust(incumbent T16, n, NULL, 0, {refine_iterations,
+ * max_correspondence_distance, keep_ratio, min_normal_cos}) on the same context; with keep_ratio == 1 and the gate off every byte of
+ * every record equals stocs_track_poses's.  A prior's results stay independent of the other priors of the call; one pinned
+ * read-back and one synchronisation per call.  keep_ratio / min_normal_cos: the rules of stocs_refine_robust_params (outside them:
+ * STOCS_ERR_INVALID); everything else is checked as stocs_track_poses checks it.  The priors are refined in groups by the rule of
+ * stocs_run_trials_post_robust (same limit, same environment variable, same independence); the workspace is grow-only. */
+int stocs_track_poses_robust(stocs_ctx* ctx, const float* prior_pose16_camera, int n_priors, const stocs_track_params* p, float keep_ratio,
+                             float min_normal_cos, stocs_track_result* out);
 /* round `round` of prior `prior` of the last stocs_track_poses: its samples candidates (centred T16, slot order) and their scores.
  * *n = samples.  The last call did not keep details (or there was none): STOCS_ERR_STATE; prior / round out of range: STOCS_ERR_INVALID;
  * an output given and cap < samples: STOCS_ERR_CAPACITY (*n set; NULL outputs query the count). */

@@ -22,6 +22,11 @@
 // object; either rejector alone helps, only both hold on sparse clouds.  Without --trim the output is the plain one's.
 // --trials N --cluster 1 [--refine K]: the clustering (and refinement) of every trial runs inside the batch, on the device
 // (stocs_run_trials_post); per-trial cluster / refined lines, the best refined pose of the best trial to <out>.refined.
+// --robust keep[,deg] (with --trials N --cluster 1 --refine K, the multi-instance forms included, or with --track <file> --cluster 1
+// --refine K): the refinement inside the batch is the robust one (stocs_run_trials_post_robust): keep in (0, 1] and deg in [0, 180]
+// as --trim and --normal-gate (without deg: no gate).  With --track it applies wherever that path refines: the detection the run
+// falls back to (the batch with --trials, else the single run's refinement).  --robust 1 prints what the run prints without it.
+// Refused, with a message naming --robust, when the values are out of range or there is nothing to refine.
 // --track <pose file> [--track-min-lcp x] (single object): track from a prior pose in the format this driver writes (12 floats, 3x4
 // row-major) -- a local search around it on this frame (stocs_track_poses, the façade's default parameters); when the tracked lcp is
 // below x (default 0.02: a prior that has lost the object scores ~0) the usual detection runs instead.  Prints which route produced
@@ -90,6 +95,8 @@ static int maximum_congruent_sets = 200;
 static std::vector<float> cam_intrinsics = {1066.778f, 312.986f, 1067.487f, 241.310f};  // YCB
 static float depth_scale = 1 / 10000.0f;
 static int image_width = 640, image_height = 480;
+static bool g_robust = false;                       // --robust keep[,deg]: the batched refinement is the robust one
+static float g_robust_keep = 1.0f, g_robust_deg = -1.0f;   // (< 0: no gate)
 static float g_trim = 0.0f, g_gate_deg = -1.0f;   // --trim r [--normal-gate deg]: the robust refinement (0: the plain one; < 0: no gate)
 
 static bool read_stcl(const std::string& path, std::vector<float>& pos, std::vector<float>& nrm, std::vector<float>* prob, std::vector<int32_t>* pixel) {
@@ -131,7 +138,9 @@ static int run_search(stocs::stocs_estimator& stocs_ptr, std::ostream& os, const
             post.acceptable_fraction = 0.8f; post.maximum_pose_count = 10; post.min_distance = 0.02f; post.min_angle = 15.0f;
             post.sym3[0] = post.sym3[1] = post.sym3[2] = 0.0f;
             post.refine_iterations = n_refine; post.max_correspondence_distance = 0.035f;
-            best = stocs_ptr.run_trials(n_trials, seed, number_of_bases, maximum_congruent_sets, sample_dispersion, post, &res, &hyps, &refined);
+            best = g_robust ? stocs_ptr.run_trials(n_trials, seed, number_of_bases, maximum_congruent_sets, sample_dispersion, post, &res, &hyps, &refined,
+                                                   g_robust_keep, g_robust_deg)
+                            : stocs_ptr.run_trials(n_trials, seed, number_of_bases, maximum_congruent_sets, sample_dispersion, post, &res, &hyps, &refined);
         } else {
             best = stocs_ptr.run_trials(n_trials, seed, number_of_bases, maximum_congruent_sets, sample_dispersion, &res);
         }
@@ -618,6 +627,14 @@ int main(int argc, char** argv) {
         else if (k == "--refine") n_refine = atoi(v.c_str());   // iterations of the refinement of the clustered hypotheses (0: off)
         else if (k == "--trim") { g_trim = (float)atof(v.c_str()); have_trim = true; }   // robust refinement: share of the pairs kept per iteration
         else if (k == "--normal-gate") { g_gate_deg = (float)atof(v.c_str()); have_gate = true; }   // and the largest angle between a pair's normals
+        else if (k == "--robust") {   // the robust refinement inside a trial batch or behind --track: keep[,deg]
+            char tail = 0;
+            const int got = sscanf(v.c_str(), "%f,%f%c", &g_robust_keep, &g_robust_deg, &tail);
+            g_robust = true;
+            if (got == 1 && v.find(',') == std::string::npos) g_robust_deg = -1.0f;
+            else if (got != 2) g_robust_keep = -1.0f;   // not keep[,deg]: refused below
+            else if (!(g_robust_deg >= 0.0f && g_robust_deg <= 180.0f)) g_robust_keep = -1.0f;
+        }
         else if (k == "--trials") n_trials = atoi(v.c_str());   // N independent runs (seeds seed, seed + 1, ...) in one set of GPU launches; the best one is written
         else if (k == "--exact-ties") exact_ties = atoi(v.c_str());   // 1: the reference kd-tree's answer on exact distance ties (set_exact_ties)
         else if (k == "--track") track_path = v;   // track from this pose file; detection when the tracked lcp is below --track-min-lcp
@@ -661,6 +678,15 @@ int main(int argc, char** argv) {
                                      n_trials > 0 || !track_path.empty())) {
         std::cerr << "--trim r [--normal-gate deg] needs r in (0, 1], deg in [0, 180], --cluster 1 --refine N, and neither --trials nor --track" << std::endl;
         return -1;
+    }
+
+    if (g_robust) {
+        if (!(g_robust_keep > 0.0f && g_robust_keep <= 1.0f)) { std::cerr << "--robust keep[,deg] needs keep in (0, 1] and deg in [0, 180]" << std::endl; return -1; }
+        if (n_refine <= 0 || !do_cluster || (n_trials <= 0 && track_path.empty())) {
+            std::cerr << "--robust keep[,deg] has nothing to refine: it needs --cluster 1 --refine K with --trials N or --track <file>" << std::endl;
+            return -1;
+        }
+        if (n_trials <= 0) { g_trim = g_robust_keep; g_gate_deg = g_robust_deg; }   // --track without --trials: the single run's refinement
     }
 
     if (depth_check && (clouds || n_trials <= 0 || !do_cluster || !track_path.empty() || a2.find(',') != std::string::npos)) {

@@ -195,6 +195,8 @@ SIGNATURES = {
     "stocs_trials_get_candidates": (C.c_int, [_vp, C.c_int, _fp, _fp, _fp, _ip, C.c_int, _intp]),
     "stocs_run_trials_post": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int, C.c_float, C.c_int, C.c_int, C.POINTER(TrialPost),
                                         C.POINTER(TrialResult)]),
+    "stocs_run_trials_post_robust": (C.c_int, [_vp, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.c_int, C.c_float, C.c_int, C.c_int, C.POINTER(TrialPost),
+                                               C.c_float, C.c_float, C.POINTER(TrialResult)]),
     "stocs_trials_get_hypotheses": (C.c_int, [_vp, C.c_int, C.POINTER(TrialHypothesis), C.c_int, _intp]),
     "stocs_best_device": (C.c_int, [_vp, _vp, C.c_int, C.c_uint32, C.POINTER(C.c_uint64)]),
     "stocs_pack_best": (C.c_uint64, [C.c_float, C.c_uint32]),
@@ -218,6 +220,7 @@ SIGNATURES = {
                                              C.POINTER(C.c_double)]),
     "stocs_refine_robust_workspace": (C.c_int, [_vp, C.POINTER(C.c_void_p), C.POINTER(C.c_uint64)]),
     "stocs_track_poses": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(TrackParams), C.POINTER(TrackResult)]),
+    "stocs_track_poses_robust": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(TrackParams), C.c_float, C.c_float, C.POINTER(TrackResult)]),
     "stocs_track_get_round": (C.c_int, [_vp, C.c_int, C.c_int, _fp, _fp, C.c_int, _intp]),
     "stocs_ctx_set_frame": (C.c_int, [_vp, C.POINTER(Camera), C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
     "stocs_default_depth_params": (None, [C.POINTER(DepthParams)]),

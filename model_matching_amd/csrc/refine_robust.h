@@ -14,6 +14,12 @@
 //           kernel's expressions in the plain kernel's order, into the same partials; refine_solve_kernel consumes them unchanged.
 // keep_ratio == 1 keeps every candidate: match, select and kept fold into ONE launch per iteration (robust_fused_kernel), which with
 // the gate off computes bit for bit what refine_accumulate_kernel does.
+//
+// robust_enqueue is the enqueue form (the counterpart of refine_enqueue) behind stocs_run_trials_post_robust and
+// stocs_track_poses_robust: the same launches on device-resident hypotheses, in groups of consecutive hypotheses that share the
+// workspace (robust_plan), no copy, no synchronisation.
+#include <stdlib.h>
+
 namespace stocs {
 
 struct RobustSel { uint32_t cut_word; int32_t cut_i, k, ncand; };   // kept: (word, i) <= (cut_word, cut_i); k = 0: cut_i = -1 keeps nothing
@@ -344,6 +350,79 @@ static int robust_check_call(stocs_ctx* c, const char* who, const int32_t* src_i
         for (int i = 0; i < n_src; ++i)
             if (src_idx[i] < 0 || src_idx[i] >= c->nS) { set_error("%s: src_idx[%d] = %d outside [0, %d)", who, i, src_idx[i], c->nS); return STOCS_ERR_INVALID; }
     return STOCS_OK;
+}
+
+// The group rule of the enqueue form.  The workspace takes 8 bytes per (hypothesis, source point), and a batch piece's slots are an
+// upper bound taken before the counts are known: n hypotheses are refined in groups of consecutive hypotheses, the largest run
+// whose demand group x nsrc x 8 stays within STOCS_REFINE_ROBUST_MAX_WORKSPACE_BYTES and at least one; only a source too large for
+// ONE hypothesis is refused.  STOCS_REFINE_ROBUST_GROUP_BYTES (read per call) lowers the limit (tests: forces several groups).
+// keep_ratio == 1 stores no rank words: one group.  Grows the workspace (may synchronise: nothing of it may be in flight).
+int robust_plan(stocs_ctx* c, const char* who, int n, int nsrc, float keep_ratio, float min_normal_cos, RobustPlan* plan) {
+    if (const char* why = robust_setting_error(keep_ratio, min_normal_cos)) { set_error("%s: %s", who, why); return STOCS_ERR_INVALID; }
+    const uint64_t per = (uint64_t)std::max(nsrc, 1) * 8u;
+    if (per > (uint64_t)STOCS_REFINE_ROBUST_MAX_WORKSPACE_BYTES) {
+        set_error("%s: %d source points need %llu workspace bytes for one hypothesis, the limit is %llu", who, nsrc, (unsigned long long)per,
+                  (unsigned long long)STOCS_REFINE_ROBUST_MAX_WORKSPACE_BYTES);
+        return STOCS_ERR_INVALID;
+    }
+    uint64_t limit = (uint64_t)STOCS_REFINE_ROBUST_MAX_WORKSPACE_BYTES;
+    if (const char* e = getenv("STOCS_REFINE_ROBUST_GROUP_BYTES")) { const long long v = atoll(e); if (v > 0 && (uint64_t)v < limit) limit = (uint64_t)v; }
+    const bool fused = keep_ratio == 1.0f;
+    const uint64_t fit = std::max<uint64_t>(limit / per, 1);
+    plan->group = fused ? std::max(n, 1) : (int)std::min<uint64_t>(fit, (uint64_t)std::max(n, 1));
+    plan->keep_ratio = keep_ratio; plan->min_normal_cos = min_normal_cos;
+    RobustWork rw;
+    return robust_prepare(c, fused ? 1 : plan->group, fused ? 1 : nsrc, &rw);
+}
+
+// init (d_live != NULL: hypothesis k takes part only when d_live[k]; a dead one starts frozen and every kernel below, the select
+// included, leaves at its first test), then group by group max_iterations x (match, select, kept | fused, solve) on the shared
+// workspace, then final and the LCP launch over all n -- on the stream, no copy, no synchronisation.  Input and outputs as
+// refine_enqueue (w from refine_prepare over all n; every scene point is the source); w.d_nc is k of the last evaluated iteration.
+// A hypothesis's launches see its own RefHyp, partials and workspace rows alone: the results do not depend on the grouping.
+int robust_enqueue(stocs_ctx* c, const RefineWork& w, const RobustPlan& plan, const int32_t* d_live, int max_iterations, float max_correspondence_distance,
+                   int* n_groups) {
+    const int n = w.n;
+    RefineState* S = (RefineState*)c->refine;
+    const bool fused = plan.keep_ratio == 1.0f;
+    const int group = std::max(1, std::min(plan.group, n));
+    RobustWork rw;
+    {   // robust_plan grew the block: this carves it again and allocates nothing
+        const size_t had = S->robust.bytes;
+        const int rc = robust_prepare(c, fused ? 1 : group, fused ? 1 : w.nsrc, &rw);
+        if (rc) return rc;
+        if (S->robust.bytes != had) { set_error("robust_enqueue: the workspace was not planned (robust_plan)"); return STOCS_ERR_STATE; }
+    }
+    RefHyp* d_hyp = (RefHyp*)w.d_hyp;
+    const unsigned hblocks = (unsigned)((n + 63) / 64);
+    hipLaunchKernelGGL(refine_init_kernel, dim3(hblocks), dim3(64), 0, c->stream, (const float*)w.d_Tin, n, d_live, d_hyp);
+    STOCS_HIP_CHECK(hipGetLastError());
+    size_t lds_bytes = 0;
+    const RefArgs a = refine_args(c, w, false, max_correspondence_distance, &lds_bytes);
+    stocs_refine_robust_params p;
+    p.max_iterations = max_iterations; p.max_correspondence_distance = max_correspondence_distance; p.keep_ratio = plan.keep_ratio; p.min_normal_cos = plan.min_normal_cos;
+    const RobustArgs r = robust_args(c, w, rw, &p);
+    int groups = 0;
+    for (int g0 = 0; g0 < n && max_iterations > 0; g0 += group, ++groups) {
+        RefineWork v = w;   // the group's view: hypotheses g0 .. g0 + v.n, their partials; the workspace rows start at 0 again
+        v.n = std::min(group, n - g0);
+        v.d_hyp = d_hyp + g0;
+        v.d_part = w.d_part + (size_t)g0 * (size_t)w.nchunks * 28;
+        for (int it = 0; it < max_iterations; ++it) {
+            if (w.nchunks > 0) {
+                const int rc = robust_enqueue_iteration(c, v, a, r, lds_bytes, plan.keep_ratio, fused, RobustNoDetail());
+                if (rc) return rc;
+            }
+            hipLaunchKernelGGL(refine_solve_kernel<RefNoDetail>, dim3((unsigned)v.n), dim3(64), 0, c->stream, (RefHyp*)v.d_hyp, (const double*)v.d_part, w.nchunks,
+                               RefNoDetail());
+            STOCS_HIP_CHECK(hipGetLastError());
+        }
+    }
+    if (n_groups) *n_groups = groups;
+    hipLaunchKernelGGL(refine_final_kernel, dim3(hblocks), dim3(64), 0, c->stream, (const float*)w.d_Tin, (const RefHyp*)d_hyp, n, c->centroid_scene,
+                       c->centroid_model, w.d_Tout, w.d_Pout, w.d_nc, w.d_it);
+    STOCS_HIP_CHECK(hipGetLastError());
+    return launch_lcp(c, w.d_Tout, n, w.d_lcp, NULL, NULL, NULL, 0);
 }
 
 }  // namespace stocs

@@ -418,6 +418,18 @@ struct RefineWork {
 };
 int refine_prepare(stocs_ctx* c, int n, int nsrc, float max_correspondence_distance, RefineWork* w);
 int refine_enqueue(stocs_ctx* c, const RefineWork& w, bool use_idx, const int32_t* d_live, int max_iterations, float max_correspondence_distance);
+// refine_robust.h: stocs_refine_poses_robust as an enqueue step (stocs_run_trials_post_robust, stocs_track_poses_robust).  robust_plan
+// checks the two settings, sizes the groups the n hypotheses are refined in and grows the workspace (may synchronise); robust_enqueue
+// is refine_enqueue's counterpart on every scene point (*n_groups, may be NULL: the groups it ran)
+struct RobustPlan { int group; float keep_ratio, min_normal_cos; };
+inline const char* robust_setting_error(float keep_ratio, float min_normal_cos) {
+    if (!(keep_ratio > 0.0f && keep_ratio <= 1.0f)) return "keep_ratio must be in (0, 1]";
+    if (!(min_normal_cos <= 1.0f)) return "min_normal_cos must be <= 1 (below -1: gate off)";
+    return NULL;
+}
+int robust_plan(stocs_ctx* c, const char* who, int n, int nsrc, float keep_ratio, float min_normal_cos, RobustPlan* plan);
+int robust_enqueue(stocs_ctx* c, const RefineWork& w, const RobustPlan& plan, const int32_t* d_live, int max_iterations, float max_correspondence_distance,
+                   int* n_groups);
 // cluster.hip: greedy_clustering of every trial of a batch piece on the device (see there); no synchronisation
 struct TrialClusterArgs { float fraction; int32_t count; float min_distance, min_angle; float sym[3]; };
 // hypothesis slots of a trial with n candidates: the reference's `size() > count` break keeps up to count + 1 of them.  The one rule

@@ -7,7 +7,8 @@
 //   rounds x (track_perturb_kernel: one thread per (prior, slot) writes the round's candidates,
 //             launch_lcp: the scoring path of stocs_score_transforms,
 //             track_best_kernel: one workgroup per prior takes the first maximum and writes the next incumbent);
-//   with refinement, the incumbents are copied into refine.hip's workspace and refine_enqueue runs on them;
+//   with refinement, the incumbents are copied into refine.hip's workspace and refine_enqueue runs on them (stocs_track_poses_robust:
+//   robust_enqueue, refine_robust.h, in groups of priors that share the robust workspace);
 //   track_result_kernel forms the camera poses (as refine_final_kernel does) and the result records;
 //   one copy back into the pinned block (the results, then every round's candidates and scores when details are kept), ONE
 //   synchronisation.
@@ -156,7 +157,8 @@ extern "C" void stocs_internal_free_track(stocs_ctx* c) {
     c->track = NULL;
 }
 
-extern "C" int stocs_track_poses(stocs_ctx* c, const float* priors, int n, const stocs_track_params* prm, stocs_track_result* out) {
+// stocs_track_poses and, with robust != NULL, stocs_track_poses_robust
+static int track_poses(stocs_ctx* c, const float* priors, int n, const stocs_track_params* prm, const RobustPlan* robust, stocs_track_result* out) {
     if (!c) { set_error("stocs_track_poses: NULL context"); return STOCS_ERR_INVALID; }
     if (n < 0) { set_error("stocs_track_poses: n_priors %d < 0", n); return STOCS_ERR_INVALID; }
     if (n == 0) return STOCS_OK;
@@ -187,9 +189,11 @@ extern "C" int stocs_track_poses(stocs_ctx* c, const float* priors, int n, const
     const int kr = keep ? R : 1;         // rounds whose candidates stay on the device
     // refine.hip's grid and workspace first: growing them synchronises, and nothing of this call may be in flight then
     RefineWork w;
+    RobustPlan plan;
     const bool refine = prm->refine_iterations > 0;
     if (refine) {
-        const int rc = refine_prepare(c, n, c->nS, prm->max_correspondence_distance, &w);
+        int rc = refine_prepare(c, n, c->nS, prm->max_correspondence_distance, &w);
+        if (!rc && robust) rc = robust_plan(c, "stocs_track_poses_robust", n, c->nS, robust->keep_ratio, robust->min_normal_cos, &plan);
         if (rc) return rc;
     }
     Carve cv;
@@ -228,7 +232,8 @@ extern "C" int stocs_track_poses(stocs_ctx* c, const float* priors, int n, const
     }
     if (refine) {
         STOCS_HIP_CHECK(hipMemcpyAsync(w.d_Tin, d_inc, (size_t)n * 64, hipMemcpyDeviceToDevice, c->stream));
-        const int rc = refine_enqueue(c, w, false, NULL, prm->refine_iterations, prm->max_correspondence_distance);
+        const int rc = robust ? robust_enqueue(c, w, plan, NULL, prm->refine_iterations, prm->max_correspondence_distance, NULL)
+                              : refine_enqueue(c, w, false, NULL, prm->refine_iterations, prm->max_correspondence_distance);
         if (rc) return rc;
     }
     hipLaunchKernelGGL(track_result_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, (const float*)d_inc, (const float*)d_inc_lcp,
@@ -247,6 +252,18 @@ extern "C" int stocs_track_poses(stocs_ctx* c, const float* priors, int n, const
         st->hT.clear(); st->hL.clear();
     }
     return STOCS_OK;
+}
+
+extern "C" int stocs_track_poses(stocs_ctx* c, const float* priors, int n, const stocs_track_params* prm, stocs_track_result* out) {
+    return track_poses(c, priors, n, prm, NULL, out);
+}
+
+extern "C" int stocs_track_poses_robust(stocs_ctx* c, const float* priors, int n, const stocs_track_params* prm, float keep_ratio, float min_normal_cos,
+                                        stocs_track_result* out) {
+    if (const char* why = robust_setting_error(keep_ratio, min_normal_cos)) { set_error("stocs_track_poses_robust: %s", why); return STOCS_ERR_INVALID; }
+    RobustPlan robust;
+    robust.group = 0; robust.keep_ratio = keep_ratio; robust.min_normal_cos = min_normal_cos;
+    return track_poses(c, priors, n, prm, &robust, out);
 }
 
 extern "C" int stocs_track_get_round(stocs_ctx* c, int prior, int round, float* T16, float* lcp, int cap, int* n) {

@@ -322,6 +322,13 @@ class StocsEstimator:
         mc = -2.0 if max_normal_deg is None else math.cos(float(max_normal_deg) * math.pi / 180.0)
         return capi.RefineRobustParams(int(max_iterations), float(max_correspondence_distance), float(keep_ratio), mc)
 
+    @staticmethod
+    def robust_setting(keep_ratio, max_normal_deg):
+        """(keep_ratio, min_normal_cos) as the two floats of stocs_run_trials_post_robust / stocs_track_poses_robust: the conversion of
+        robust_params (degrees -> cosine once, in double, rounded to float at the call; None: gate off)."""
+        prm = StocsEstimator.robust_params(0, 1.0, keep_ratio, max_normal_deg)
+        return prm.keep_ratio, prm.min_normal_cos
+
     def refine_poses_robust(self, T16, max_iterations=5, max_correspondence_distance=0.035, keep_ratio=0.7, max_normal_deg=30.0, src_idx=None, params=None):
         """Trimmed, normal-gated point-to-plane refinement of n centred-frame hypotheses (stocs_refine_poses_robust): per iteration
         the nearest keep_ratio of the candidate pairs enter the system, and a pair whose normals differ by more than max_normal_deg
@@ -379,16 +386,23 @@ class StocsEstimator:
     def track_poses(self, priors_pose16_camera, rounds=TRACK_DEFAULTS["rounds"], samples=TRACK_DEFAULTS["samples"],
                     max_translation=TRACK_DEFAULTS["max_translation"], max_rotation_deg=TRACK_DEFAULTS["max_rotation_deg"], shrink=TRACK_DEFAULTS["shrink"],
                     seed=TRACK_DEFAULTS["seed"], refine_iterations=TRACK_DEFAULTS["refine_iterations"],
-                    max_correspondence_distance=TRACK_DEFAULTS["max_correspondence_distance"], keep_details=False):
+                    max_correspondence_distance=TRACK_DEFAULTS["max_correspondence_distance"], keep_details=False, keep_ratio=None, max_normal_deg=None):
         """Local search around n camera-frame priors (column-major 16 floats each) on this context's scene (stocs_track_poses) -> a
         structured array with the fields of stocs_track_result (prior_lcp, lcp, pose16, refined_lcp, refined_pose16, n_correspondences,
-        iterations), one record per prior.  keep_details: every round's candidates and scores stay readable through track_round."""
+        iterations), one record per prior.  keep_details: every round's candidates and scores stay readable through track_round.
+        keep_ratio / max_normal_deg: with either given, the final incumbents are refined by the trimmed, normal-gated form
+        (stocs_track_poses_robust; keep_ratio defaults to 1, max_normal_deg None leaves the gate off, converted as robust_params
+        documents); both None: the plain entry point."""
         P, pP = capi.f32(priors_pose16_camera)
         n = P.size // 16
         prm = capi.TrackParams(rounds, samples, max_translation, max_rotation_deg, shrink, seed, refine_iterations, max_correspondence_distance,
                                1 if keep_details else 0)
         buf = (capi.TrackResult * max(n, 1))()
-        capi.check(self.L.stocs_track_poses(self.h, pP, n, C.byref(prm), buf))
+        if keep_ratio is None and max_normal_deg is None:
+            capi.check(self.L.stocs_track_poses(self.h, pP, n, C.byref(prm), buf))
+        else:
+            keep, mc = self.robust_setting(1.0 if keep_ratio is None else keep_ratio, max_normal_deg)
+            capi.check(self.L.stocs_track_poses_robust(self.h, pP, n, C.byref(prm), keep, mc, buf))
         return np.frombuffer(buf, dtype=_TRACK_DTYPE, count=n).copy()
 
     def set_frame(self, depth_u16, prob_u16, K, depth_scale):
@@ -711,19 +725,32 @@ class StocsEstimator:
         return s.value, i.value, P
 
     # ---- trial batches: N independent trials in one set of launches (stocs_run_trials) ----
-    def run_trials(self, seeds, n_attempts=100, mode=0, dispersion=0.9, max_per_base=200, keep_details=False, post=None):
+    def run_trials(self, seeds, n_attempts=100, mode=0, dispersion=0.9, max_per_base=200, keep_details=False, post=None, robust=None):
         """-> list of dicts (n_bases, n_candidates, n_quads, best_lcp, best_index, best_pose 16 floats), one per seed.
         post (a dict of trial_post's fields, or a capi.TrialPost): cluster, and refine, every trial's candidates inside the batch
-        (stocs_run_trials_post); the hypotheses are then read with trials_get_hypotheses(t)."""
+        (stocs_run_trials_post); the hypotheses are then read with trials_get_hypotheses(t).
+        robust (needs post): dict(keep_ratio=0.7, max_normal_deg=30.0 | None) -- the kept hypotheses are refined by the trimmed,
+        normal-gated form (stocs_run_trials_post_robust; a missing key takes the default shown, None for the angle leaves the gate
+        off); None: the plain entry point."""
         sd = np.ascontiguousarray(seeds, np.uint64)
         res = (capi.TrialResult * max(len(sd), 1))()
+        if robust is not None and post is None:
+            raise ValueError("run_trials: robust needs post (there is nothing to refine without it)")
         if post is None:
             capi.check(self.L.stocs_run_trials(self.h, mode, len(sd), sd.ctypes.data_as(C.POINTER(C.c_uint64)), n_attempts, dispersion, max_per_base,
                                                1 if keep_details else 0, res))
         else:
             pp = post if isinstance(post, capi.TrialPost) else trial_post(**post)
-            capi.check(self.L.stocs_run_trials_post(self.h, mode, len(sd), sd.ctypes.data_as(C.POINTER(C.c_uint64)), n_attempts, dispersion, max_per_base,
-                                                    1 if keep_details else 0, C.byref(pp), res))
+            if robust is None:
+                capi.check(self.L.stocs_run_trials_post(self.h, mode, len(sd), sd.ctypes.data_as(C.POINTER(C.c_uint64)), n_attempts, dispersion, max_per_base,
+                                                        1 if keep_details else 0, C.byref(pp), res))
+            else:
+                unknown = set(robust) - {"keep_ratio", "max_normal_deg"}
+                if unknown:
+                    raise ValueError("run_trials: robust has no %s" % sorted(unknown))
+                keep, mc = self.robust_setting(robust.get("keep_ratio", 0.7), robust.get("max_normal_deg", 30.0))
+                capi.check(self.L.stocs_run_trials_post_robust(self.h, mode, len(sd), sd.ctypes.data_as(C.POINTER(C.c_uint64)), n_attempts, dispersion,
+                                                               max_per_base, 1 if keep_details else 0, C.byref(pp), keep, mc, res))
         # (one view of the whole result array: a ctypes field access per trial costs ~20 us, and a thousand trials take 60 ms of device time)
         a = np.frombuffer(res, dtype=_TRIAL_DTYPE, count=len(sd))
         nb, nc, nq, bl, bi, bp = (a["n_bases"].tolist(), a["n_candidates"].tolist(), a["n_quads"].tolist(), a["best_lcp"].tolist(), a["best_index"].tolist(),
@@ -1111,13 +1138,14 @@ def ingest_scene_multi(depth_u16, probs_u16, K, depth_scale, voxel_size=0.005, c
 
 
 def estimate_objects(scenes, models, seeds, n_attempts=100, mode=0, dispersion=0.9, max_per_base=200, edge_map=None, options=None,
-                     params=None, max_workers=4, device=-1):
+                     params=None, max_workers=4, device=-1, post=None, robust=None):
     """One estimator per object of a frame, run concurrently on a pool of at most max_workers host threads (each context owns its
     streams; the library calls release the GIL).  scenes[k] = (pos, nrm, prob, pixel) -- e.g. from ingest_scene_multi --, models[k] =
     (pos, nrm).  seeds: an int runs one trial (sample_bases, find_congruent_all, make_transforms, compute_best_transform), a sequence
     runs run_trials over it.  edge_map (instance mode) and options (set_option) apply to every object.  Each context is closed when its
     object is done, so at most max_workers hold trial memory at a time.  Returns, in object order, (best_lcp, best_index, best_pose)
-    for one trial and run_trials' list of dicts otherwise."""
+    for one trial and run_trials' list of dicts otherwise.  post / robust (a sequence of seeds only): run_trials' arguments of the same
+    names; every dict then also carries "hypotheses", the trial's trials_get_hypotheses array (the context is closed on return)."""
     from concurrent.futures import ThreadPoolExecutor
     if len(scenes) != len(models):
         raise ValueError("%d scenes for %d models" % (len(scenes), len(models)))
@@ -1136,7 +1164,12 @@ def estimate_objects(scenes, models, seeds, n_attempts=100, mode=0, dispersion=0
                 est.make_transforms(max_per_base, int(seeds))
                 lcp, idx, pose = est.compute_best_transform()
                 return float(lcp), int(idx), pose
-            return est.run_trials(seeds, n_attempts, mode=mode, dispersion=dispersion, max_per_base=max_per_base)
+            if post is None and robust is None:
+                return est.run_trials(seeds, n_attempts, mode=mode, dispersion=dispersion, max_per_base=max_per_base)
+            res = est.run_trials(seeds, n_attempts, mode=mode, dispersion=dispersion, max_per_base=max_per_base, post=post, robust=robust)
+            for t, r in enumerate(res):
+                r["hypotheses"] = est.trials_get_hypotheses(t)
+            return res
         finally:
             est.close()
 

@@ -8,7 +8,9 @@ sweep: rounds x samples (x shrink) on synthetic motion sequences (synth.motion_s
   truth, frames within 5 mm and 3 degrees, median wall clock of a call.  The defaults are the cheapest setting that keeps the most frames
   (ideally all) of every sequence within 5 mm and 3 degrees.
 also: the lcp of a prior 30 cm behind the object (the driver's fallback threshold), and the ycb check of tests/test_track_gpu.py
-  (a 64-trial winner moved by 1 cm and 5 degrees, tracked with the defaults)."""
+  (a 64-trial winner moved by 1 cm and 5 degrees, tracked with the defaults).
+--robust keep[,deg]: only the cost of the robust refinement behind the tracker (stocs_track_poses_robust) against the plain one in the
+  same process: 1, 10 and 64 priors on ycb and Cm, 5 iterations at 3.5 cm -> profiles/track_robust_time.json (unless --out names another)."""
 import argparse
 import json
 import math
@@ -80,6 +82,35 @@ def cost(args):
             pri = perturbed(P0, npri, seed=1, max_t=0.01, max_deg=5.0)
             for it in (0, 5):
                 row["track_%dpriors_refine%d_ms" % (npri, it)] = wall(lambda: est.track_poses(pri, refine_iterations=it), args.warmup, args.reps)
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+        est.close()
+    return rows
+
+
+def robust_cost(args, keep, deg):
+    rows = []
+    for name in ("ycb_024_bowl", "Cm"):
+        est, P0 = frame(name)
+        row = dict(frame=name, nS=est.nS, nM=est.nM, keep_ratio=keep, max_normal_deg=deg)
+        for npri in (1, 10, 64):
+            pri = perturbed(P0, npri, seed=1, max_t=0.01, max_deg=5.0)
+            forms = dict(search=lambda: est.track_poses(pri, refine_iterations=0), plain=lambda: est.track_poses(pri, refine_iterations=5),
+                         robust=lambda: est.track_poses(pri, refine_iterations=5, keep_ratio=keep, max_normal_deg=deg))
+            for f in forms.values():
+                for _ in range(args.warmup):
+                    f()
+            ts = {k: [] for k in forms}
+            for _ in range(args.reps):   # interleaved: the three forms see the same machine
+                for k, f in forms.items():
+                    t0 = time.perf_counter()
+                    f()
+                    ts[k].append((time.perf_counter() - t0) * 1e3)
+            ms = {k: statistics.median(v) for k, v in ts.items()}
+            row["track_%dpriors" % npri] = dict(search_ms=round(ms["search"], 4), plain_refine5_ms=round(ms["plain"], 4), robust_refine5_ms=round(ms["robust"], 4),
+                                                robust_over_plain_call=round(ms["robust"] / ms["plain"], 4),
+                                                robust_over_plain_refinement_part=round((ms["robust"] - ms["search"]) / max(ms["plain"] - ms["search"], 1e-9), 4))
+        row["robust_workspace_bytes"] = est.refine_robust_workspace()[1]
         rows.append(row)
         print(json.dumps(row), flush=True)
         est.close()
@@ -161,13 +192,23 @@ def ycb_check():
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "track_time.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--robust", default=None, metavar="keep[,deg]")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=15)
     ap.add_argument("--sequences", type=int, default=3)
     ap.add_argument("--frames", type=int, default=12)
     ap.add_argument("--skip-sweep", action="store_true")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "track_robust_time.json" if args.robust else "track_time.json")
+    if args.robust:
+        v = args.robust.split(",")
+        rec = dict(reps=args.reps, warmup=args.warmup, refine_iterations=5, cost=robust_cost(args, float(v[0]), float(v[1]) if len(v) > 1 else None))
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(rec, f, indent=1)
+        return
     rec = dict(defaults=TRACK_DEFAULTS, cost=cost(args), ycb_perturbed_winner=ycb_check())
     if not args.skip_sweep:
         rows, pick, far = sweep(args)

@@ -54,6 +54,7 @@ def main():
     ap.add_argument("--trials", type=int, default=256)
     ap.add_argument("--seed", type=int, default=1000)
     ap.add_argument("--post", action="store_true")
+    ap.add_argument("--robust", default=None, metavar="keep[,deg]", help="with --post: the refinement inside the batch is the robust one")
     ap.add_argument("--sym", default=None, help="a,b,c: the clustering's symmetry descriptor (0, 90, 180 or 360 per axis)")
     ap.add_argument("--sym-steps", type=int, default=72)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "trial_recall.json"))
@@ -64,12 +65,20 @@ def main():
     gt16 = np.asarray(scene.T_gt, np.float64).T.reshape(16).astype(np.float32)
     seeds = list(range(a.seed, a.seed + a.trials))
     post = dict(refine_iterations=5) if a.post else None
-    res = est.run_trials(seeds, post=post)
+    robust = None
+    if a.robust is not None:
+        if not a.post:
+            ap.error("--robust needs --post")
+        v = a.robust.split(",")
+        robust = dict(keep_ratio=float(v[0]), max_normal_deg=float(v[1]) if len(v) > 1 else None)
+    res = est.run_trials(seeds, post=post, robust=robust)
     diameter = float(est.model_diameter())
     W = np.stack([r["best_pose"] for r in res]).astype(np.float32)
     plain_w = est.pose_errors(W, gt16)
     row = {"example": a.example, "model_points": len(model.pos), "scene_points": len(scene.pos), "first_seed": a.seed, "model_diameter_m": diameter,
            "threshold_m": float(np.float32(0.1) * np.float32(diameter)), "winners": summary(plain_w, diameter, a.trials)}
+    if robust is not None:
+        row["robust"] = robust
     S = None
     if a.sym is not None:
         sym3 = [float(x) for x in a.sym.split(",")]
@@ -93,8 +102,9 @@ def main():
     if os.path.exists(a.out):
         with open(a.out) as f:
             data = json.load(f)
-    key = (a.example, a.post, json.dumps(row.get("sym")))
-    data["rows"] = [r for r in data["rows"] if (r["example"], "refined_winners" in r, json.dumps(r.get("sym"))) != key] + [row]
+    key = (a.example, a.post, json.dumps(row.get("sym")), json.dumps(row.get("robust")), a.trials)
+    data["rows"] = [r for r in data["rows"] if (r["example"], "refined_winners" in r, json.dumps(r.get("sym")), json.dumps(r.get("robust")),
+                                                r.get("winners", {}).get("trials", a.trials)) != key] + [row]
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(data, f, indent=1)

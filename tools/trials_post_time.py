@@ -6,9 +6,12 @@ mode) example frames and on Cm:
   (c) (b) + 5 refine iterations of the kept hypotheses;
   (d) the route before it: run_trials with keep_details, host stocs_cluster_poses per trial, one stocs_refine_poses on all kept
       hypotheses;
+  (e) with --robust keep[,deg]: (c) with the robust refinement inside the batch (stocs_run_trials_post_robust), next to (a) and (c)
+      in the same process -- only these three forms are timed then, and the record (default profiles/trials_post_robust_time.json)
+      carries trials/s of (c) and (e), their ratio, the groups the batch refined its slots in and the robust workspace's bytes;
 plus stocs_refine_poses alone on the hypotheses (c) kept.  Clustering: 0.8, 10, 2 cm, 15 degrees, no symmetry (stocs_single
 --cluster 1); refinement: 5 iterations, 3.5 cm.  Medians over reps after a warm-up.  Measurement only.
-usage: python tools/trials_post_time.py [out.json] [reps]"""
+usage: python tools/trials_post_time.py [out.json] [reps] [--robust keep[,deg]]"""
 import json
 import os
 import sys
@@ -50,9 +53,21 @@ def timed(fn, reps):
     return {"median": float(np.median(t)), "min": float(np.min(t))}
 
 
+def robust_option(argv):
+    """--robust keep[,deg] taken out of argv -> dict(keep_ratio, max_normal_deg) or None"""
+    if "--robust" not in argv:
+        return None
+    i = argv.index("--robust")
+    v = argv[i + 1].split(",")
+    del argv[i:i + 2]
+    return dict(keep_ratio=float(v[0]), max_normal_deg=float(v[1]) if len(v) > 1 else None)
+
+
 def main():
-    out_path = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "trials_post_time.json")
-    reps = int(sys.argv[2]) if len(sys.argv) > 2 else 10
+    argv = list(sys.argv)
+    robust = robust_option(argv)
+    out_path = argv[1] if len(argv) > 1 else os.path.join(ROOT, "profiles", "trials_post_robust_time.json" if robust else "trials_post_time.json")
+    reps = int(argv[2]) if len(argv) > 2 else 10
     seeds = list(range(1000, 1000 + N_TRIALS))
     cl = dict(acceptable_fraction=0.8, maximum_pose_count=10, min_distance=0.02, min_angle=15.0, sym3=(0.0, 0.0, 0.0), max_correspondence_distance=0.035)
     rec = {"trials": N_TRIALS, "attempts": N_ATTEMPTS, "max_per_base": MAX_PER_BASE, "clustering": cl, "refine_iterations": 5, "reps": reps,
@@ -79,6 +94,9 @@ def main():
         # against it) is then the same for all four
         forms = {"a_run_trials_ms": lambda: run(), "b_with_clustering_ms": lambda: run(post=p_cluster),
                  "c_with_clustering_refine5_ms": lambda: run(post=p_refine), "d_keep_details_host_cluster_refine_ms": host_route}
+        if robust:
+            forms = {"a_run_trials_ms": forms["a_run_trials_ms"], "c_with_clustering_refine5_ms": forms["c_with_clustering_refine5_ms"],
+                     "e_with_clustering_robust_refine5_ms": lambda: run(post=p_refine, robust=robust)}
         for _ in range(3):
             for f in forms.values():
                 f()
@@ -90,6 +108,25 @@ def main():
                 times[k].append((time.perf_counter() - t0) * 1e3)
         for k, t in times.items():
             w[k] = {"median": float(np.median(t)), "min": float(np.min(t))}
+        if robust:
+            res = run(post=p_refine, robust=robust)
+            H = [est.trials_get_hypotheses(t) for t in range(N_TRIALS)]
+            w["robust"] = robust
+            w["candidates"] = int(sum(r["n_candidates"] for r in res))
+            w["hypotheses"] = int(sum(len(h) for h in H))
+            w["hypotheses_moved"] = int(sum(int((h["iterations"] > 0).sum()) for h in H))
+            w["hypotheses_refined_lcp_up"] = int(sum(int((h["refined_lcp"] > h["lcp"]).sum()) for h in H))
+            w["robust_groups"] = next(v for k, v in est.last_call_timing(3) if k.startswith("robust refinement: groups"))
+            w["robust_workspace_bytes"] = est.refine_robust_workspace()[1]
+            c_ms, e_ms = w["c_with_clustering_refine5_ms"]["median"], w["e_with_clustering_robust_refine5_ms"]["median"]
+            w["plain_trials_per_s"] = N_TRIALS / c_ms * 1e3
+            w["robust_trials_per_s"] = N_TRIALS / e_ms * 1e3
+            w["robust_over_plain_call"] = e_ms / c_ms
+            w["robust_over_plain_refinement_part"] = (e_ms - w["a_run_trials_ms"]["median"]) / (c_ms - w["a_run_trials_ms"]["median"])
+            print(name, json.dumps(w), flush=True)
+            rec["workloads"][name] = w
+            est.close()
+            continue
         res = run(post=p_refine)
         H = [est.trials_get_hypotheses(t) for t in range(N_TRIALS)]
         w["candidates"] = int(sum(r["n_candidates"] for r in res))
