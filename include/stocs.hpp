@@ -840,6 +840,45 @@ public:
         return d;
     }
 
+    // Visible-surface discrepancy (stocs_pose_errors_vsd / stocs_render_depth; no reference counterpart): the camera-frame estimates
+    // against ground truth (one pose or one each, as pose_errors) on the frame of set_frame, each rendered as surfels and compared only
+    // where it is visible in the depth image: BOP's third measure, which needs no symmetry set.  default_vsd_params fills BOP's ten taus,
+    // 0.05, 0.10 .. 0.50 model diameters (n_tau stays 0 when the diameter fails).  render_depth: the z image of every pose, image_height x
+    // image_width floats each, 0 where empty.  Empty on error (the text goes to the log).
+    stocs_vsd_params default_vsd_params() {
+        stocs_vsd_params p;
+        stocs_default_vsd_params(&p);
+        const float d = model_diameter();
+        if (d > 0.0f) {
+            p.n_tau = 10;
+            for (int i = 0; i < 10; ++i) p.tau[i] = (float)(0.05 * (i + 1)) * d;
+        }
+        return p;
+    }
+    std::vector<stocs_vsd_record> pose_errors_vsd(const std::vector<PoseCandidate*>& est, const std::vector<PoseCandidate*>& gt, const stocs_vsd_params& prm) {
+        const int n = (int)est.size(), n_gt = (int)gt.size();
+        std::vector<float> P((size_t)n * 16), G((size_t)n_gt * 16);
+        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], est[(size_t)i]->transform.data(), 64);
+        for (int i = 0; i < n_gt; ++i) std::memcpy(&G[(size_t)i * 16], gt[(size_t)i]->transform.data(), 64);
+        std::vector<stocs_vsd_record> r((size_t)n);
+        if (n > 0 && stocs_pose_errors_vsd(ctx_, P.data(), n, G.data(), n_gt, &prm, r.data()) != STOCS_OK) {
+            *log_ << "pose_errors_vsd failed: " << stocs_last_error() << std::endl;
+            r.clear();
+        }
+        return r;
+    }
+    std::vector<float> render_depth(const std::vector<PoseCandidate*>& poses, const stocs_vsd_params& prm) {
+        const int n = (int)poses.size();
+        std::vector<float> P((size_t)n * 16);
+        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], poses[(size_t)i]->transform.data(), 64);
+        std::vector<float> z((size_t)n * (size_t)image_width * (size_t)image_height);
+        if (n > 0 && stocs_render_depth(ctx_, P.data(), n, &prm, z.data()) != STOCS_OK) {
+            *log_ << "render_depth failed: " << stocs_last_error() << std::endl;
+            z.clear();
+        }
+        return z;
+    }
+
     // Joint rendering (stocs_explain_poses; no reference counterpart): the camera-frame poses -- the instances select_instances kept, say
     // -- rendered TOGETHER against the frame of set_frame, nearest surface first: one record per pose in input order (footprint,
     // visible / hidden behind the others, and the visible pixels' agreement with the depth image), and, when `labels` is given, the

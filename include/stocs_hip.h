@@ -1021,6 +1021,75 @@ int stocs_scene_select(stocs_ctx* ctx, const void* d_rows, int n, int width, int
                        const stocs_scene_record* rec, int n_groups, const int32_t* group_cap, const stocs_scene_params* p, stocs_scene_result* out,
                        int32_t* selected, int* n_selected);
 
+/* ---- visible-surface discrepancy (VSD, the third measure of the BOP benchmark) and the surfel depth renderer under it (no reference
+ * counterpart).  MSSD, MSPD and ADD compare model points; VSD compares what the camera would see: the rendered surface of the estimate
+ * and of the ground truth, each only where it is visible in the frame's depth image.  It needs no symmetry set.  The splats of the render
+ * contract above are screen-aligned squares at the constant depth of their centre: masks, not a surface.  Here a model point is an
+ * oriented disc (a surfel) of radius surfel_radius, ray-cast per pixel.  The frame is the one stocs_ctx_set_frame uploaded; poses are
+ * CAMERA-frame, column-major, and act on the model as in the depth check.  csrc/vsd.hip, restated in float32 numpy in tests/vsd_ref.py,
+ * equal bit for bit.  All in float, every operation one IEEE add / sub / mul / div / floor / correctly rounded sqrt, no contraction.
+ * The surfel rule.  A model point goes through steps 1-3 of the depth-check contract, unchanged: p, q, facing, in_image, col, row, and
+ * f = q_0 p_0 + (q_1 p_1 + q_2 p_2), the facing expression itself.  For an in_image point:
+ *   s = (int)fminf(floorf((fx * surfel_radius) / p_2 + 0.5f), (float)max_splat_px)   (the splat rule's s with surfel_radius)
+ * and for every pixel (r, c) with |r - row|, |c - col| <= s inside the image (tested on integers):
+ *   xn = ((float)c - cx) / fx,  yn = ((float)r - cy) / fy                 the pixel's ray (xn, yn, 1)
+ *   dn = q_0 xn + (q_1 yn + q_2);                  hit only if dn < 0     the ray meets the disc's front
+ *   z  = f / dn;                                   hit only if z > 1e-6f  where the ray meets the disc's plane
+ *   ex = xn z - p_0,  ey = yn z - p_1,  ez = z - p_2
+ *   hit only if (ex ex) + ((ey ey) + (ez ez)) <= surfel_radius * surfel_radius      inside the disc
+ *   a hit pixel gets zbuf = min(zbuf, bits(z)); empty is all ones.  z > 1e-6, so the bits keep the order of the floats.
+ * The z-buffer is a minimum: a render depends neither on the batch, nor on the order, nor on the chunk.  A pose with a non-finite entry
+ * among its twelve used entries, or the all-zero "no pose" record, renders nothing and is no error.
+ * stocs_render_depth: the z image of each of n poses (n * height * width floats, host, row-major), 0.0f where empty.
+ * stocs_pose_errors_vsd: n estimates against ground truth, n_gt == 1 or n as for stocs_pose_errors (with n_gt == 1 the ground truth is
+ * rendered once).  Each pair renders ZE and ZG.  Per pixel, with xn, yn as above, k = sqrtf((xn xn + yn yn) + 1.0f): BOP compares
+ * distances from the camera centre, not z.  dE = ZE k, dG = ZG k, and with raw = depth[pixel], dS = ((float)raw * depth_scale) * k.
+ * Then, as bop_toolkit's `bop19` visibility mode:
+ *   visG  = G present and (raw == 0 or dG - dS <= delta)
+ *   visE  = E present and (raw == 0 or dE - dS <= delta or visG)
+ *   inter = visG and visE,  uni = visG or visE
+ *   on inter: dd = fabsf(dG - dE); for every t < n_tau, far[t] += (dd >= tau[t]).
+ * The record: the integer counts px_est, px_gt (pixels present), vis_est, vis_gt, inter, uni, far[t];
+ * e[t] = (float)(far[t] + (uni - inter)) / (float)uni, 1.0f when uni == 0 (t >= n_tau: far 0, e 0); valid = 0 for the pairs that step 5
+ * of stocs_pose_errors calls invalid -- the arithmetic still runs, so such an estimate scores 1.  Every field is an integer sum: a
+ * record is bitwise independent of the batch it shares and of its position in it.
+ * Checked in this order: a NULL ctx (whatever n) and n < 0 are STOCS_ERR_INVALID; n == 0 is then a no-op; a NULL pose, parameter or
+ * result pointer, an n_gt other than 1 or n (stocs_pose_errors_vsd), a parameter outside the ranges below (stocs_check_vsd_params:
+ * host code, the same check on its own; stocs_render_depth ignores delta, n_tau and tau): STOCS_ERR_INVALID; a context without a model,
+ * no frame set, or a frame whose width * height differs from what was uploaded: STOCS_ERR_STATE.
+ * Own grow-only workspace on the context (a second call of the same or a smaller size allocates nothing); on the context's stream;
+ * stocs_pose_errors_vsd has one pinned read-back and one synchronisation per call, stocs_render_depth one per piece of at most 32 MB
+ * of images.  stocs_last_call_timing(which = 7) gives the host steps of the last stocs_pose_errors_vsd and, with "device_clock" on, the
+ * HIP-event time of its launches.
+ * The kernels (csrc/vsd.hip): a z-buffer of float bits per rendered pose in a chunk of workspace (256 MB; STOCS_VSD_CHUNK=<poses> in
+ * the environment forces a size; a chunk holds whole pairs, and with n_gt == 1 the ground truth's buffer stays beside the chunks).
+ * Render: a workgroup of four wavefronts per (pose, STOCS_VSD_POINTS model points); a wavefront projects 64 points, one per lane, then
+ * takes the in_image ones in turn: the surfel goes into scalar registers and all 64 lanes sweep its square, one 32-bit atomicMin per hit
+ * pixel -- in large calls on dense models only where the stored depth, read first, is not already nearer.  Compare: one pass per pair
+ * over the union of the two poses' bounding rectangles in both z-buffers and the frame, counts by __ballot and popcount in scalar
+ * registers, one integer atomicAdd per counter and workgroup.  STOCS_VSD_FORM=<bits> in the environment forces a form for measurements
+ * and tests (1: compare whole frames; 2: never read first; 4: always read first); no bit changes a result. ---- */
+#define STOCS_VSD_MAX_TAU 16
+#define STOCS_VSD_POINTS 256
+typedef struct stocs_vsd_params {
+    float   surfel_radius;           /* m, > 0 finite: radius of the disc a model point stands for (default 0.006)   */
+    int32_t max_splat_px;            /* 0..16: largest half-width in pixels of the square a surfel is tested on (16) */
+    float   delta;                   /* m, > 0 finite: visibility tolerance (default 0.015, BOP's)                   */
+    int32_t n_tau;                   /* 1..16 (default 0: the caller sets the taus, they depend on the diameter)     */
+    float   tau[STOCS_VSD_MAX_TAU];  /* m, each of the first n_tau > 0 finite: misalignment tolerances               */
+} stocs_vsd_params;                  /* 80 bytes */
+typedef struct stocs_vsd_record {
+    int32_t px_est, px_gt, vis_est, vis_gt, inter, uni;
+    int32_t far[STOCS_VSD_MAX_TAU];
+    float   e[STOCS_VSD_MAX_TAU];
+    int32_t valid, reserved;
+} stocs_vsd_record;                  /* 160 bytes */
+void stocs_default_vsd_params(stocs_vsd_params* p);
+int stocs_check_vsd_params(const stocs_vsd_params* p);
+int stocs_render_depth(stocs_ctx* ctx, const float* pose16_camera, int n, const stocs_vsd_params* p, float* depth /* n*height*width */);
+int stocs_pose_errors_vsd(stocs_ctx* ctx, const float* est_pose16_camera, int n, const float* gt_pose16_camera, int n_gt,
+                          const stocs_vsd_params* p, stocs_vsd_record* out);
+
 /* ---- tuning knobs (never change results beyond float summation order).
  * "lcp_variant": 99 = automatic (default): the scan fed from a per-wavefront LDS queue of the queries that have a list -- over
  *   index-ordered lists at cell edge epsilon (24, sparse scenes), over centre-sorted lists with triangle-inequality early exit
@@ -1132,7 +1201,7 @@ int stocs_debug_sort_pairs(int device, const uint32_t* keys, const uint32_t* val
 int64_t stocs_device_alloc_count(void);
 /* host wall clock, in milliseconds, of the steps of the context's LAST stocs_find_congruent_all (which = 0),
  * stocs_make_transforms (1), stocs_verify_all (2), stocs_run_trials (3: its phases summed over the pieces of the batch), stocs_pose_errors
- * (4; with "device_clock" 1 also "device: kernel", the HIP-event time of its launches) stocs_pose_errors_sym (5; likewise) or stocs_symmetry_errors (6; likewise): always recorded (a few clock reads per call, no synchronisation of its
+ * (4; with "device_clock" 1 also "device: kernel", the HIP-event time of its launches) stocs_pose_errors_sym (5; likewise), stocs_symmetry_errors (6; likewise) or stocs_pose_errors_vsd (7; likewise): always recorded (a few clock reads per call, no synchronisation of its
  * own), so that a call that stalls -- tens of milliseconds instead of one -- names the step it stalled in.  Steps are host
  * intervals between the call's existing synchronisation points: "wait for the device" steps hold the GPU work, the others
  * host work and runtime calls; entries whose label starts with "device:" are HIP-event times of the kernel groups that

@@ -44,6 +44,14 @@
 // winner and "gt <object> sym recall: trials=N valid=... mssd=... add=... [mspd=...]": BOP's average
 // recall of MSSD over 0.05 .. 0.50 diameters, the share with the symmetric ADD below 0.1 diameter, and the average recall of MSPD over
 // 5 .. 50 pixels x image width / 640.  Without --sym the output is what it is without these options.
+// --vsd [--vsd-delta m] [--surfel-radius m] (with --gt, a scene directory, a single object): BOP's visible-surface discrepancy on the
+// frame's own depth image as well (stocs_pose_errors_vsd; the library's delta 0.015 and surfel radius 0.006 unless given).  After the gt
+// lines, "gt <object> vsd: taus=10 delta=... surfel_radius=... e0=... .. e9=... mean=... px_est=... px_gt=... vis_est=... vis_gt=...
+// inter=... uni=... valid=...": the errors at the misalignment tolerances 0.05, 0.10 .. 0.50 model diameters and their mean; with
+// --trials N one "gt <object> vsd trial t: e0=... .. e9=... valid=..." line per trial's winner and "gt <object> vsd recall: trials=N
+// valid=... vsd=...": BOP's average recall of VSD, the mean over the ten taus and the correctness thresholds 0.05 .. 0.50 of the share of
+// ALL trials with e below the threshold (a trial without a pose counts as wrong: VSD is defined for it).  Without --vsd the output is
+// what it is without these options.
 // --depth-check (with --trials N --cluster 1 [--refine K], a scene directory): every trial's hypotheses -- the refined poses when
 // refinement ran -- scored against the frame's own depth image and class-probability map (stocs_depth_check_poses); one "depth t.i:"
 // line per hypothesis, and <out> is written from the first maximum of score - violation (ties: the higher lcp, then the lower trial
@@ -69,6 +77,7 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -345,15 +354,31 @@ static bool read_pose_file(const std::string& path, MatrixType& m) {
 // --gt: the pose this run wrote to out_path, read back with the reader the ground truth goes through (what is scored is what a reader of
 // the file gets), against the ground truth: ADD, ADD-S, their maxima, the model's diameter (stocs_pose_errors, stocs_model_diameter); with
 // --trials N also the share of the trials' winners (full precision, a trial without a pose left out) within 0.1 diameter
+struct VsdOptions { bool on; float delta, surfel_radius; };   // --vsd; a value <= 0 leaves the library's default
+
+// the ten errors of a VSD record as " e0=... .. e9=..." at b + at; returns the new end
+static int print_vsd_errors(char* b, size_t cap, int at, const stocs_vsd_record& r, int n_tau) {
+    for (int t = 0; t < n_tau; ++t) at += snprintf(b + at, cap - (size_t)at, " e%d=%.9g", t, (double)r.e[t]);
+    return at;
+}
+
 static int report_gt(stocs::stocs_estimator& est, const std::string& gt_path, const std::string& out_path, const std::string& object,
-                     const std::vector<stocs::stocs_estimator::TrialResult>& trials, const std::vector<float>& syms, const stocs_camera* cam) {
+                     const std::vector<stocs::stocs_estimator::TrialResult>& trials, const std::vector<float>& syms, const stocs_camera* cam,
+                     const VsdOptions& vsd) {
     MatrixType g, p;
     if (!read_pose_file(gt_path, g)) { std::cerr << "cannot read a 3x4 pose from " << gt_path << std::endl; return 1; }
     PoseCandidate gt(g, 0.0f, -1.0f);
     const std::vector<PoseCandidate*> gts(1, &gt);
     const float diameter = est.model_diameter();
     if (diameter < 0.0f) { std::cerr << "model diameter failed: " << stocs_last_error() << std::endl; return 2; }
-    char b[384];
+    char b[768];
+    stocs_vsd_params vp;
+    memset(&vp, 0, sizeof(vp));
+    if (vsd.on) {
+        vp = est.default_vsd_params();   // BOP's ten taus from the diameter
+        if (vsd.delta > 0.0f) vp.delta = vsd.delta;
+        if (vsd.surfel_radius > 0.0f) vp.surfel_radius = vsd.surfel_radius;
+    }
     if (!read_pose_file(out_path, p)) {
         std::cout << "gt " << object << ": no pose" << std::endl;
     } else {
@@ -370,6 +395,17 @@ static int report_gt(stocs::stocs_estimator& est, const std::string& gt_path, co
                               q[0].k_mssd, (double)q[0].add, q[0].k_add);
             if (cam) at += snprintf(b + at, sizeof(b) - (size_t)at, " mspd=%.9g k_mspd=%d", (double)q[0].mspd, q[0].k_mspd);
             snprintf(b + at, sizeof(b) - (size_t)at, " valid=%d", q[0].valid);
+            std::cout << b << std::endl;
+        }
+        if (vsd.on) {
+            const std::vector<stocs_vsd_record> q = est.pose_errors_vsd(std::vector<PoseCandidate*>(1, &e), gts, vp);
+            if (q.size() != 1) { std::cerr << "visible-surface discrepancy failed: " << stocs_last_error() << std::endl; return 2; }
+            int at = snprintf(b, sizeof(b), "gt %s vsd: taus=%d delta=%.9g surfel_radius=%.9g", object.c_str(), vp.n_tau, (double)vp.delta, (double)vp.surfel_radius);
+            at = print_vsd_errors(b, sizeof(b), at, q[0], vp.n_tau);
+            double mean = 0.0;
+            for (int t = 0; t < vp.n_tau; ++t) mean += (double)q[0].e[t];
+            snprintf(b + at, sizeof(b) - (size_t)at, " mean=%.9g px_est=%d px_gt=%d vis_est=%d vis_gt=%d inter=%d uni=%d valid=%d", mean / vp.n_tau, q[0].px_est, q[0].px_gt,
+                     q[0].vis_est, q[0].vis_gt, q[0].inter, q[0].uni, q[0].valid);
             std::cout << b << std::endl;
         }
     }
@@ -408,6 +444,23 @@ static int report_gt(stocs::stocs_estimator& est, const std::string& gt_path, co
             int at = snprintf(b, sizeof(b), "gt %s sym recall: trials=%d valid=%d mssd=%.9g add=%.9g", object.c_str(), (int)q.size(), nv, nv ? (double)hit3 / (10.0 * nv) : 0.0,
                               nv ? (double)hit_add / nv : 0.0);
             if (cam) snprintf(b + at, sizeof(b) - (size_t)at, " mspd=%.9g", nv ? (double)hit2 / (10.0 * nv) : 0.0);
+            std::cout << b << std::endl;
+        }
+        if (vsd.on) {
+            const std::vector<stocs_vsd_record> q = est.pose_errors_vsd(wp, gts, vp);
+            if (q.size() != wp.size()) { std::cerr << "visible-surface discrepancy failed: " << stocs_last_error() << std::endl; return 2; }
+            int nv = 0, hits = 0;   // hits summed over the taus and the ten correctness thresholds
+            for (size_t t = 0; t < q.size(); ++t) {
+                int at = snprintf(b, sizeof(b), "gt %s vsd trial %d:", object.c_str(), (int)t);
+                at = print_vsd_errors(b, sizeof(b), at, q[t], vp.n_tau);
+                snprintf(b + at, sizeof(b) - (size_t)at, " valid=%d", q[t].valid);
+                std::cout << b << std::endl;
+                if (!q[t].valid) continue;   // wrong under every threshold
+                ++nv;
+                for (int k = 0; k < vp.n_tau; ++k)
+                    for (int i = 1; i <= 10; ++i) hits += q[t].e[k] < (float)(0.05 * i);
+            }
+            snprintf(b, sizeof(b), "gt %s vsd recall: trials=%d valid=%d vsd=%.9g", object.c_str(), (int)q.size(), nv, (double)hits / (10.0 * vp.n_tau * (double)q.size()));
             std::cout << b << std::endl;
         }
     }
@@ -609,12 +662,15 @@ int main(int argc, char** argv) {
     int do_cluster = 0, n_trials = 0, exact_ties = 0, n_refine = 0, depth_check = 0;
     bool do_instances = false, do_masks = false, have_trim = false, have_gate = false;
     SceneSelectOptions scene_opt = {false, false, 0};
+    VsdOptions vsd_opt = {false, 0.0f, 0.0f};
+    bool have_vsd_delta = false, have_surfel_radius = false;
     stocs_instance_params inst_prm = stocs::stocs_estimator::default_instance_params();
     uint64_t seed = 1;
     for (int i = clouds ? 4 : 3; i < argc; i += 2) {
         if (std::string(argv[i]) == "--depth-check") { depth_check = 1; --i; continue; }   // the options without a value
         if (std::string(argv[i]) == "--masks") { do_masks = true; --i; continue; }
         if (std::string(argv[i]) == "--scene-select") { scene_opt.on = true; --i; continue; }
+        if (std::string(argv[i]) == "--vsd") { vsd_opt.on = true; --i; continue; }   // with --gt: the visible-surface discrepancy too
         if (i + 1 >= argc) break;
         const std::string k = argv[i], v = argv[i + 1];
         if (k == "--edge") edge_path = v;
@@ -645,6 +701,8 @@ int main(int argc, char** argv) {
             have_sym = true;
         } else if (k == "--sym-steps") sym_steps = atoi(v.c_str());
         else if (k == "--sym-file") sym_path = v;
+        else if (k == "--vsd-delta") { vsd_opt.delta = (float)atof(v.c_str()); have_vsd_delta = true; }
+        else if (k == "--surfel-radius") { vsd_opt.surfel_radius = (float)atof(v.c_str()); have_surfel_radius = true; }
         else if (k == "--instances") { do_instances = true; inst_prm.max_instances = atoi(v.c_str()); }
         else if (k == "--instance-min-fraction") inst_prm.min_exclusive_fraction = (float)atof(v.c_str());
         else if (k == "--instance-min-points") inst_prm.min_points = atoi(v.c_str());
@@ -670,6 +728,18 @@ int main(int argc, char** argv) {
         if (syms.empty() || syms.size() / 16 > (size_t)STOCS_POSE_SYM_MAX) {
             std::cerr << "no symmetry set of 1 .. " << STOCS_POSE_SYM_MAX << " transforms from " << (sym_path.empty() ? std::string("--sym / --sym-steps") : sym_path) << std::endl;
             return 1;
+        }
+    }
+
+    if (vsd_opt.on || have_vsd_delta || have_surfel_radius) {   // refused before any search
+        if (!vsd_opt.on || gt_path.empty() || clouds || a2.find(',') != std::string::npos) {
+            std::cerr << "--vsd [--vsd-delta m] [--surfel-radius m] needs --gt, a scene directory and a single object" << std::endl;
+            return -1;
+        }
+        if ((have_vsd_delta && !(vsd_opt.delta > 0.0f && std::isfinite(vsd_opt.delta))) ||
+            (have_surfel_radius && !(vsd_opt.surfel_radius > 0.0f && std::isfinite(vsd_opt.surfel_radius)))) {
+            std::cerr << "--vsd-delta and --surfel-radius need positive, finite metres" << std::endl;
+            return -1;
         }
     }
 
@@ -761,7 +831,7 @@ int main(int argc, char** argv) {
             est.reset(new stocs::stocs_estimator(model_path, model_map, rgb_path, depth_path, class_probability_path, edge_probability_path, dbg_dir, cam_intrinsics,
                                                  image_width, image_height, depth_scale, 1.0f, voxel_size, distance_threshold, ppf_tr_discretization,
                                                  ppf_rot_discretization, edge_threshold, class_threshold));
-            if (depth_check || do_masks) {   // the frame the scene was ingested from, for stocs_depth_check_poses / stocs_explain_poses
+            if (depth_check || do_masks || vsd_opt.on) {   // the frame the scene was ingested from, for stocs_depth_check_poses / stocs_explain_poses / stocs_pose_errors_vsd
                 std::vector<uint16_t> depth, prob;
                 stocs::read_image(depth_path, 1, 16, image_width, image_height, &depth);
                 stocs::read_image(class_probability_path, 1, 16, image_width, image_height, &prob);
@@ -795,5 +865,5 @@ int main(int argc, char** argv) {
     stocs_camera cam;   // a scene directory has a camera: MSPD is reported too
     memset(&cam, 0, sizeof(cam));
     cam.fx = cam_intrinsics[0]; cam.cx = cam_intrinsics[1]; cam.fy = cam_intrinsics[2]; cam.cy = cam_intrinsics[3];
-    return report_gt(*est, gt_path, out_path, object, trial_results, syms, clouds ? NULL : &cam);
+    return report_gt(*est, gt_path, out_path, object, trial_results, syms, clouds ? NULL : &cam, vsd_opt);
 }

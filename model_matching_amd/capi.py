@@ -114,6 +114,15 @@ class RenderParams(C.Structure):
     _fields_ = [("point_radius", C.c_float), ("max_splat_px", C.c_int32), ("tolerance", C.c_float), ("class_threshold", C.c_float)]
 
 
+class VsdParams(C.Structure):
+    _fields_ = [("surfel_radius", C.c_float), ("max_splat_px", C.c_int32), ("delta", C.c_float), ("n_tau", C.c_int32), ("tau", C.c_float * 16)]
+
+
+class VsdRecord(C.Structure):
+    _fields_ = [("px_est", C.c_int32), ("px_gt", C.c_int32), ("vis_est", C.c_int32), ("vis_gt", C.c_int32), ("inter", C.c_int32), ("uni", C.c_int32),
+                ("far", C.c_int32 * 16), ("e", C.c_float * 16), ("valid", C.c_int32), ("reserved", C.c_int32)]
+
+
 class RenderResult(C.Structure):
     _fields_ = [("footprint", C.c_int32), ("visible", C.c_int32), ("hidden", C.c_int32), ("no_depth", C.c_int32), ("agree", C.c_int32),
                 ("in_front", C.c_int32), ("behind", C.c_int32), ("on_mask", C.c_int32)]
@@ -225,6 +234,10 @@ SIGNATURES = {
     "stocs_ctx_set_frame": (C.c_int, [_vp, C.POINTER(Camera), C.POINTER(C.c_uint16), C.POINTER(C.c_uint16)]),
     "stocs_default_depth_params": (None, [C.POINTER(DepthParams)]),
     "stocs_depth_check_poses": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(DepthParams), C.POINTER(DepthResult)]),
+    "stocs_default_vsd_params": (None, [C.POINTER(VsdParams)]),
+    "stocs_check_vsd_params": (C.c_int, [C.POINTER(VsdParams)]),
+    "stocs_render_depth": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(VsdParams), _fp]),
+    "stocs_pose_errors_vsd": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, C.POINTER(VsdParams), C.POINTER(VsdRecord)]),
     "stocs_pose_errors": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, C.POINTER(PoseError)]),
     "stocs_pose_errors_detail": (C.c_int, [_vp, _fp, _fp, _fp, _fp, _ip]),
     "stocs_model_diameter": (C.c_int, [_vp, _fp]),

@@ -533,7 +533,7 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
     c->nS = nS; c->nM = nM;
     c->d_scratch = NULL; c->scratch_bytes = 0;
     c->h_pin = NULL; c->pin_bytes = 0;
-    for (int k = 0; k < 7; ++k) c->timing[k].n = 0;
+    for (int k = 0; k < 8; ++k) c->timing[k].n = 0;
     c->index.built = false;
     c->index.d_bucket_start = NULL; c->index.d_pairs = NULL; c->index.d_exists = NULL;
     c->cong = NULL; c->quad_id_bits = 16;
@@ -546,6 +546,7 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
     c->pose_error = NULL;
     c->pose_error_sym = NULL;
     c->symmetry = NULL;
+    c->vsd = NULL;
     c->inst = NULL;
     c->trials = NULL; c->snrmw_trial0 = NULL; c->snrmw_stride = 0; c->snrmw_override = NULL; c->lcp_cand_trial = NULL;
     c->d_cand = NULL; c->cand_bytes = 0; c->n_cands = 0; c->cand_cap = 0; c->cands_stale = false;
@@ -698,6 +699,7 @@ int stocs_ctx_destroy(stocs_ctx* c) {
     stocs_internal_free_pose_error(c);
     stocs_internal_free_pose_error_sym(c);
     stocs_internal_free_symmetry(c);
+    stocs_internal_free_vsd(c);
     c->grid_mem.destroy(); c->grid_ws.destroy();
     c->order.free(); c->cdf.free(); c->kd.free();
     if (c->h_pin) (void)hipHostFree(c->h_pin);
@@ -795,7 +797,7 @@ int stocs_dev_download(stocs_ctx* c, void* host, const void* dptr, int64_t bytes
 }
 
 int stocs_last_call_timing(const stocs_ctx* c, int which, const char** labels, double* ms, int cap, int* n) {
-    if (!c || which < 0 || which > 6 || !n || cap < 0) return STOCS_ERR_INVALID;
+    if (!c || which < 0 || which > 7 || !n || cap < 0) return STOCS_ERR_INVALID;
     const CallTiming& t = c->timing[which];
     *n = t.n;
     for (int i = 0; i < t.n && i < cap; ++i) {

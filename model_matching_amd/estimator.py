@@ -46,6 +46,9 @@ assert _POSE_ERROR_DTYPE.itemsize == C.sizeof(capi.PoseError)
 _POSE_ERROR_SYM_DTYPE = np.dtype([("add_fix", np.uint64), ("add", np.float32), ("mssd", np.float32), ("mspd", np.float32), ("reserved_f", np.float32),
                                   ("k_add", np.int32), ("k_mssd", np.int32), ("k_mspd", np.int32), ("valid", np.int32)])
 assert _POSE_ERROR_SYM_DTYPE.itemsize == C.sizeof(capi.PoseErrorSym)
+_VSD_DTYPE = np.dtype([("px_est", np.int32), ("px_gt", np.int32), ("vis_est", np.int32), ("vis_gt", np.int32), ("inter", np.int32), ("uni", np.int32),
+                       ("far", np.int32, (16,)), ("e", np.float32, (16,)), ("valid", np.int32), ("reserved", np.int32)])
+assert _VSD_DTYPE.itemsize == C.sizeof(capi.VsdRecord)
 _SYMMETRY_ERROR_DTYPE = np.dtype([("sum_fix", np.uint64), ("mean", np.float32), ("max", np.float32), ("n_far", np.int32), ("n_normal_bad", np.int32),
                                   ("valid", np.int32), ("reserved", np.int32)])
 assert _SYMMETRY_ERROR_DTYPE.itemsize == C.sizeof(capi.SymmetryError)
@@ -437,6 +440,52 @@ class StocsEstimator:
         buf = (capi.DepthResult * max(n, 1))()
         capi.check(self.L.stocs_depth_check_poses(self.h, pP, n, C.byref(prm), buf))
         return np.frombuffer(buf, dtype=_DEPTH_DTYPE, count=n).copy()
+
+    def _vsd_params(self, who, params, taus=None):
+        prm = capi.VsdParams()
+        self.L.stocs_default_vsd_params(C.byref(prm))
+        for k, v in params.items():
+            if k not in ("surfel_radius", "max_splat_px", "delta"):
+                raise TypeError("%s: unknown parameter %r" % (who, k))
+            setattr(prm, k, v)
+        if taus is not None:
+            t = [float(x) for x in np.asarray(taus, np.float32).reshape(-1)]
+            if len(t) > 16:
+                raise ValueError("%s: at most 16 taus" % who)
+            prm.n_tau = len(t)
+            for i, x in enumerate(t):
+                prm.tau[i] = x
+        return prm
+
+    def render_depth(self, poses16, **params):
+        """The surfel depth image of each of n camera-frame poses against the camera of set_frame (stocs_render_depth) -> (n, height,
+        width) float32, the z of the nearest surfel per pixel, 0 where nothing is.  params: surfel_radius, max_splat_px over the
+        library's defaults."""
+        P, pP = capi.f32(poses16)
+        n = P.size // 16
+        prm = self._vsd_params("render_depth", params)
+        H, W = self._frame_shape("render_depth")
+        out = np.zeros((n, H, W), np.float32)
+        capi.check(self.L.stocs_render_depth(self.h, pP, n, C.byref(prm), out.ctypes.data_as(capi._fp)))
+        return out
+
+    def pose_errors_vsd(self, est, gt, taus=None, **params):
+        """n estimated camera-frame poses against ground truth by BOP's visible-surface discrepancy on the frame of set_frame
+        (stocs_pose_errors_vsd): gt holds one pose or n; taus the misalignment tolerances in metres (at most 16), None: BOP's 0.05,
+        0.10 .. 0.50 times model_diameter() -> a structured array with the fields of stocs_vsd_record, one record per estimate: `e`
+        holds the error per tau (entries beyond the taus are 0).  params: surfel_radius, max_splat_px, delta over the library's defaults."""
+        P, pP = capi.f32(est)
+        G, pG = capi.f32(gt)
+        if P.size % 16 or G.size % 16 or G.size == 0:
+            raise ValueError("pose_errors_vsd: poses are 16 floats each")
+        n, n_gt = P.size // 16, G.size // 16
+        if taus is None:
+            d = np.float32(self.model_diameter())
+            taus = [np.float32(t) * d for t in BOP_VSD_TAUS]
+        prm = self._vsd_params("pose_errors_vsd", params, taus)
+        buf = (capi.VsdRecord * max(n, 1))()
+        capi.check(self.L.stocs_pose_errors_vsd(self.h, pP, n, pG, n_gt, C.byref(prm), buf))
+        return np.frombuffer(buf, dtype=_VSD_DTYPE, count=n).copy()
 
     def pose_errors(self, est, gt):
         """n estimated camera-frame poses (column-major 16 floats each) against ground truth (stocs_pose_errors): gt holds one pose (every
@@ -1062,6 +1111,28 @@ def pose_recall_sym(records, diameter, image_width=None):
         r = np.float32(image_width) / np.float32(640)
         ar_mspd = float(np.mean([(mspd < np.float32(t) * r).mean() for t in BOP_MSPD_THRESHOLDS]))
     return ar_mssd, ar_mspd, float((add < np.float32(0.1) * d).mean()), nv
+
+
+BOP_VSD_TAUS = tuple(0.05 * i for i in range(1, 11))            # of the diameter: the misalignment tolerances
+BOP_VSD_THRESHOLDS = tuple(0.05 * i for i in range(1, 11))      # of 1: the correctness thresholds on the error
+
+
+def pose_recall_vsd(records, n_tau=None):
+    """BOP's average recall of VSD over the records of pose_errors_vsd -> (ar_vsd, n_valid): the mean over the taus (the first n_tau
+    entries of `e`; None: 10, the BOP set pose_errors_vsd fills by default) and over the correctness thresholds 0.05, 0.10 .. 0.50 of
+    the share of records with e[t] below the threshold.  Unlike pose_recall_sym, which leaves invalid records out, an invalid record
+    counts as WRONG here: VSD is defined for it (an estimate that renders nothing has e = 1), so the share is of all records.  (nan, 0)
+    for no records."""
+    records = np.asarray(records)
+    if records.size == 0:
+        return float("nan"), 0
+    nt = 10 if n_tau is None else int(n_tau)
+    if nt < 1 or nt > 16:
+        raise ValueError("pose_recall_vsd: n_tau %d outside 1..16" % nt)
+    ok = records["valid"].reshape(-1) != 0
+    e = records["e"].reshape(-1, 16)[:, :nt]
+    hit = [(ok[:, None] & (e < np.float32(th))).mean() for th in BOP_VSD_THRESHOLDS]
+    return float(np.mean(hit)), int(ok.sum())
 
 
 def kdtree_nn_host(pos3, queries3, sqdist):

@@ -9,7 +9,11 @@ the best refined hypothesis of every trial (first maximum of the rescored lcp) i
 with one bump: its ADD says little, its ADD-S is the meaningful one; synth:Cm_asym has no symmetry.  With --sym a,b,c [--sym-steps n] the
 winners are also scored under the symmetries that descriptor stands for (symmetry_set, pose_errors_sym): BOP's average recalls of MSSD and
 MSPD, the share with the symmetric ADD and with MSSD below 0.1 diameter, and how many records' symmetric ADD equals their plain ADD bit
-for bit (all of them under --sym 0,0,0, the identity alone).  A --sym run is a row of its own in the file.  No GPU: the tool fails."""
+for bit (all of them under --sym 0,0,0, the identity alone).  A --sym run is a row of its own in the file.  With --vsd the winners are
+scored by BOP's third measure too (pose_errors_vsd, the taus 0.05 .. 0.50 diameters): the frame is the ground truth's own surfel depth
+image (render_depth) in front of a wall at 1.5 m, rounded to depth units of 0.1 mm -- an ideal sensor; the average recall of VSD is taken
+over ALL trials (a trial without a pose counts as wrong).  With --sym as well, `average_recall` is BOP's AR, the mean of the three average
+recalls, each taken over all trials.  A --vsd run is a row of its own too.  No GPU: the tool fails."""
 import argparse
 import json
 import os
@@ -21,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 from model_matching_amd import synth  # noqa: E402
-from model_matching_amd.estimator import StocsEstimator, pose_recall, pose_recall_sym, symmetry_set  # noqa: E402
+from model_matching_amd.estimator import StocsEstimator, pose_recall, pose_recall_sym, pose_recall_vsd, symmetry_set  # noqa: E402
 
 
 def summary(err, diameter, n_trials):
@@ -48,6 +52,20 @@ def summary_sym(err, plain, diameter, n_trials, image_width):
             "sym_add_equals_add_bitwise": int((err["add_fix"][ok] == plain["add_fix"][ok]).sum())}
 
 
+def summary_vsd(err, n_trials):
+    ar, nv = pose_recall_vsd(err)
+    ok = err["valid"] != 0
+    return {"trials": n_trials, "with_pose": nv, "average_recall_vsd_of_trials": ar,
+            "mean_e_at_tau_0.20_of_poses": float(err["e"][ok, 3].mean()) if nv else None,
+            "median_visible_union_px": float(np.median(err["uni"][ok])) if nv else None}
+
+
+def bop_ar(vsd, sym, n_trials):
+    """BOP's AR: the mean of the three average recalls, each over all trials"""
+    share = sym["with_pose"] / n_trials
+    return float(np.mean([vsd["average_recall_vsd_of_trials"], sym["average_recall_mssd_of_poses"] * share, sym["average_recall_mspd_of_poses"] * share])) if sym["with_pose"] else 0.0
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--example", default="synth:Cm_asym", choices=["synth:Cm_asym", "synth:Cm"])
@@ -57,6 +75,7 @@ def main():
     ap.add_argument("--robust", default=None, metavar="keep[,deg]", help="with --post: the refinement inside the batch is the robust one")
     ap.add_argument("--sym", default=None, help="a,b,c: the clustering's symmetry descriptor (0, 90, 180 or 360 per axis)")
     ap.add_argument("--sym-steps", type=int, default=72)
+    ap.add_argument("--vsd", action="store_true", help="score by visible-surface discrepancy on the ground truth's own rendered depth image too")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "trial_recall.json"))
     a = ap.parse_args()
     name = a.example.split(":", 1)[1]
@@ -85,6 +104,14 @@ def main():
         S = symmetry_set(sym3, a.sym_steps)
         row["sym"] = {"descriptor": sym3, "steps": a.sym_steps, "symmetries": len(S)}
         row["winners_sym"] = summary_sym(est.pose_errors_sym(W, gt16, S, synth.YCB_INTRINSICS), plain_w, diameter, a.trials, 640)
+    if a.vsd:
+        est.set_frame(np.zeros((480, 640), np.uint16), None, synth.YCB_INTRINSICS, 1e-4)     # the camera alone: the renderer reads no depth
+        z = est.render_depth(gt16)[0]
+        est.set_frame(np.rint(np.where(z > 0, z, 1.5) / 1e-4).astype(np.uint16), None, synth.YCB_INTRINSICS, 1e-4)
+        row["vsd"] = {"frame": "ground truth rendered, wall at 1.5 m", "delta_m": 0.015, "surfel_radius_m": 0.006, "object_pixels": int((z > 0).sum())}
+        row["winners_vsd"] = summary_vsd(est.pose_errors_vsd(W, gt16), a.trials)
+        if S is not None:
+            row["winners_average_recall"] = bop_ar(row["winners_vsd"], row["winners_sym"], a.trials)
     if a.post:
         R = np.zeros((a.trials, 16), np.float32)      # all zero: "no pose"
         for t in range(a.trials):
@@ -95,6 +122,10 @@ def main():
         row["refined_winners"] = summary(plain_r, diameter, a.trials)
         if S is not None:
             row["refined_winners_sym"] = summary_sym(est.pose_errors_sym(R, gt16, S, synth.YCB_INTRINSICS), plain_r, diameter, a.trials, 640)
+        if a.vsd:
+            row["refined_winners_vsd"] = summary_vsd(est.pose_errors_vsd(R, gt16), a.trials)
+            if S is not None:
+                row["refined_winners_average_recall"] = bop_ar(row["refined_winners_vsd"], row["refined_winners_sym"], a.trials)
     est.close()
     print(json.dumps(row), flush=True)
     # one file, one entry per example (and per --post): a second run adds to it
@@ -102,9 +133,9 @@ def main():
     if os.path.exists(a.out):
         with open(a.out) as f:
             data = json.load(f)
-    key = (a.example, a.post, json.dumps(row.get("sym")), json.dumps(row.get("robust")), a.trials)
+    key = (a.example, a.post, json.dumps(row.get("sym")), json.dumps(row.get("robust")), a.trials, "vsd" in row)
     data["rows"] = [r for r in data["rows"] if (r["example"], "refined_winners" in r, json.dumps(r.get("sym")), json.dumps(r.get("robust")),
-                                                r.get("winners", {}).get("trials", a.trials)) != key] + [row]
+                                                r.get("winners", {}).get("trials", a.trials), "vsd" in r) != key] + [row]
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(data, f, indent=1)
