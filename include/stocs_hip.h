@@ -1146,6 +1146,35 @@ int stocs_last_tie_counts(stocs_ctx* ctx, int64_t* flagged, int64_t* changed);
  * down, capped.  NULL outputs are skipped; *n_patches and *n_dist are always set (0 when the context has no field). */
 int stocs_get_cull_state(stocs_ctx* ctx, float* patches4, int32_t* perm, int* n_patches, float* geom8, float* dist,
                          int64_t dist_cap, int64_t* n_dist);
+/* The scene grid as the last stocs_ctx_create / stocs_ctx_set_scene built it (tests and diagnostics; no reference counterpart; host
+ * records only: no device work, no synchronisation).  The scoring kernels locate a query q in cell floor((q - origin) * inv_h) per
+ * axis, in float; a cell's list holds scene points within r of its box, r = 1.001 epsilon, or epsilon + 2^-21 of the grid's span on
+ * scenes wider than about 2 100 epsilons (where the float rounding of that cell computation would use the thousandth up). */
+#define STOCS_GRID_SORT_ROCPRIM 1
+#define STOCS_GRID_SORT_OWN 2
+typedef struct stocs_grid_info {
+    float origin[3];        /* the float origin the kernels subtract */
+    float h, inv_h;         /* cell edge (epsilon / div) and the float the kernels multiply by */
+    int32_t div;            /* 1..4 */
+    int32_t cells[3];       /* cells per axis */
+    int32_t bricks[3];      /* bricks of 8x8x8 cells per axis (the top table has their product) */
+    int32_t centre_sorted;  /* lists ordered by distance from the cell centre, with chunk bounds (else ascending scene index) */
+    int32_t pruned;         /* lists hold only points that can win somewhere in their cell */
+    int32_t has_nearest;    /* the z word of a cell is a distance bound (div > 1), not half of the sub-cell mask */
+    int32_t has_cones;      /* the count word carries the cell's normal cone */
+    int32_t has_flat;       /* the flat cell table exists */
+    int32_t sort;           /* STOCS_GRID_SORT_*: which sort ordered the (cell, point) incidences */
+    int32_t prune_group;    /* lanes per cell of the prune kernel, 16 or 64; 0 when not pruned */
+    int32_t prune_k;        /* dominators tried per entry, 4, 8 or 16; 0 when not pruned */
+    int32_t longest_list;   /* entries of the longest stored list, before padding to 8 */
+    int32_t reserved;
+    int64_t n_incidences;   /* (cell, point) pairs with the point within r of the cell's box */
+    int64_t n_cells;        /* non-empty cells */
+    int64_t n_bricks;       /* bricks with a non-empty cell */
+    int64_t n_entries;      /* stored list entries, padding included */
+} stocs_grid_info;
+/* STOCS_ERR_INVALID for a NULL argument; STOCS_ERR_STATE ("no scene") for a context whose last scene was refused -- *info is zeroed. */
+int stocs_get_grid_info(stocs_ctx* ctx, stocs_grid_info* info);
 /* The model-side half of that test without a context or a device (host code: what stocs_ctx_create computes): the order in
  * which the scoring kernels walk the model -- perm[slot] = model index, 64 consecutive slots = one compact surface patch --
  * and the bounding sphere of every patch (centre x, y, z in the CENTRED model frame, radius), ceil(nM / 64) of them. */

@@ -141,6 +141,17 @@ class SceneResult(C.Structure):
     _fields_ = [("rank", C.c_int32), ("own", C.c_int32), ("exclusive", C.c_int32), ("reason", C.c_int32)]
 
 
+GRID_SORT_ROCPRIM, GRID_SORT_OWN = 1, 2
+
+
+class GridInfo(C.Structure):
+    _fields_ = [("origin", C.c_float * 3), ("h", C.c_float), ("inv_h", C.c_float), ("div", C.c_int32), ("cells", C.c_int32 * 3),
+                ("bricks", C.c_int32 * 3), ("centre_sorted", C.c_int32), ("pruned", C.c_int32), ("has_nearest", C.c_int32),
+                ("has_cones", C.c_int32), ("has_flat", C.c_int32), ("sort", C.c_int32), ("prune_group", C.c_int32), ("prune_k", C.c_int32),
+                ("longest_list", C.c_int32), ("reserved", C.c_int32), ("n_incidences", C.c_int64), ("n_cells", C.c_int64),
+                ("n_bricks", C.c_int64), ("n_entries", C.c_int64)]
+
+
 class Camera(C.Structure):
     _fields_ = [("fx", C.c_float), ("cx", C.c_float), ("fy", C.c_float), ("cy", C.c_float), ("depth_scale", C.c_float),
                 ("width", C.c_int), ("height", C.c_int), ("normal_method", C.c_int)]
@@ -271,6 +282,7 @@ SIGNATURES = {
     "stocs_last_call_timing": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.c_int, _intp]),
     "stocs_set_option": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "stocs_get_cull_state": (C.c_int, [_vp, _fp, _ip, _intp, _fp, _fp, C.c_int64, _i64p]),
+    "stocs_get_grid_info": (C.c_int, [_vp, C.POINTER(GridInfo)]),
     "stocs_model_patch_order": (C.c_int, [_fp, C.c_int, _ip, _fp]),
     "stocs_model_subpatches": (C.c_int, [_fp, C.c_int, _ip, _fp]),
     "stocs_kdtree_nn_host": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_float, _ip]),

@@ -6,7 +6,7 @@
 // A new scene arrives with every camera frame, so the build is part of the per-frame latency: every step is
 // a kernel or a rocPRIM primitive on the context's stream (the host only sizes buffers):
 //   1. count / fill the (cell, point) incidences: a point belongs to every cell whose box is within
-//      r = 1.001 eps of it (double arithmetic, the same predicate for count and fill);
+//      r = 1.001 eps of it -- more on scenes wider than ~2 100 eps, see build_grid_gpu (double arithmetic, the same predicate for count and fill);
 //   2. one stable radix sort by cell key (brick << 9 | local cell) -- incidences are generated in ascending
 //      point order, so a cell's list comes out in ascending scene index (the tie rule of the scan kernels
 //      relies on it); dense scenes append a 16-bit quantised distance to the cell centre to the key;
@@ -454,7 +454,7 @@ int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
     const double eps = (double)c->prm.distance_threshold;
     if (div < 1 || div > 4) div = 1;
     const double h = eps / div;
-    const double r = eps * 1.001;  // safety margin >> float rounding of the device cell computation
+    const double r0 = eps * 1.001;  // safety margin >> float rounding of the device cell computation -- on scenes of ordinary extent
     double mn[3] = {1e30, 1e30, 1e30}, mx[3] = {-1e30, -1e30, -1e30};
     for (int i = 0; i < nS; ++i) {
         const V3 p = c->h_spos[i];
@@ -464,6 +464,14 @@ int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
     if (nS == 0) { for (int k = 0; k < 3; ++k) { mn[k] = 0; mx[k] = 0; } }
     for (int k = 0; k < 3; ++k) { g.bb_mn[k] = mn[k]; g.bb_mx[k] = mx[k]; }
     g.d_dist = NULL; g.dist_ready = false;
+    // The scan kernels compute floor((q - o_f) * inv_h) in float: the subtraction, the float inv_h and the product each contribute up to
+    // 2^-24 of the offset from the origin, so the face they see can lie 3 * 2^-24 * span from the box face used here (measured: up to
+    // 1.5e-3 eps at an extent of 31 000 eps, 1.1e-2 eps at 262 000).  The margin grows with the extent once 2^-21 of it exceeds the
+    // thousandth of epsilon -- from about 2 100 epsilons on; below that r is what it always was
+    double ext = 0;
+    for (int k = 0; k < 3; ++k) ext = std::max(ext, mx[k] - mn[k]);
+    const double span = ext + 2.0 * (r0 + 2 * h) + h;   // the largest offset from the origin inside the grid
+    const double r = std::max(r0, eps + span * (1.0 / 2097152.0));
     const double pad = r + 2 * h;  // a query outside the grid is farther than epsilon from every point
     const double o[3] = {mn[0] - pad, mn[1] - pad, mn[2] - pad};
     int n[3];
@@ -474,6 +482,7 @@ int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
     g.nbx = (n[0] + 7) / 8; g.nby = (n[1] + 7) / 8; g.nbz = (n[2] + 7) / 8;
     g.h = (float)h;
     g.n_bricks = 0; g.n_entries = 0; g.avg_list_len = 0; g.has_nearest = false; g.has_cones = false;
+    g.div = div; g.sort_kind = 0; g.prune_group = 0; g.prune_k = 0; g.n_inc = 0; g.n_cells = 0; g.longest_list = 0;
     g.d_top = NULL; g.d_cells = NULL; g.d_list = NULL; g.d_chunk_r = NULL; g.d_flat = NULL;
     const int64_t n_top = (int64_t)g.nbx * g.nby * g.nbz;
     if (n_top > (int64_t)400 * 1000 * 1000) { set_error("scene extent too large for the brick grid"); return STOCS_ERR_INVALID; }
@@ -525,6 +534,7 @@ int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
     // padded lists stay below 2^31 entries (32-bit offsets in the cell words)
     if (n_inc64 >= (1ull << 28)) { set_error("scene grid lists too large (%llu incidences)", n_inc64); return STOCS_ERR_INVALID; }
     const size_t n_inc = (size_t)n_inc64;
+    g.n_inc = (int64_t)n_inc64;
     uint64_t *d_keys, *d_keys_s; uint32_t *d_vals, *d_vals_s;
     if ((rc = T.get(&d_keys, n_inc)) || (rc = T.get(&d_keys_s, n_inc)) || (rc = T.get(&d_vals, n_inc)) || (rc = T.get(&d_vals_s, n_inc))) return rc;
     // ---- 2. stable sort by cell (and quantised centre distance) ----
@@ -534,6 +544,7 @@ int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
     // one launch per 8-bit pass) where rocPRIM's 64-bit radix_sort_pairs runs ~17 small launches (150 us of a frame's stocs_ctx_set_scene in
     // round 5a); both stable, the sorted keys are widened back for the kernels behind
     const bool own_sort = end_bit <= 32 && n_inc >= 65536 && n_inc < ((size_t)1 << 30) && !(getenv("STOCS_SORT") && !strcmp(getenv("STOCS_SORT"), "rocprim"));
+    g.sort_kind = own_sort ? STOCS_GRID_SORT_OWN : STOCS_GRID_SORT_ROCPRIM;
     char* d_ts;
     const uint32_t* d_sort_err = NULL;
     if (own_sort) {
@@ -573,6 +584,7 @@ int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
     const uint32_t sort_err = rb32[2];
     if (sort_err) { set_error("scene grid: the incidence sort gave up waiting for a tile (sort32.hip)"); return STOCS_ERR_HIP; }
     const uint32_t n_cells = counts[0], n_bricks = counts[1];
+    g.n_cells = (int64_t)n_cells;
     uint32_t *d_cell_first, *d_cell_brick, *d_padded, *d_list_off, *d_max;
     uint64_t* d_cell_key;
     if ((rc = T.get(&d_cell_first, (size_t)n_cells + 1)) || (rc = T.get(&d_cell_brick, (size_t)n_cells + 1)) || (rc = T.get(&d_padded, (size_t)n_cells + 1)) ||
@@ -596,6 +608,8 @@ int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
         const bool short_lists = (double)n_inc <= 12.0 * (double)n_cells;     // a handful of points per cell: 16 lanes per cell, four cells per wavefront
         if (pk == 4) STOCS_PRUNE_LAUNCH(4); else if (pk == 16) STOCS_PRUNE_LAUNCH(16); else STOCS_PRUNE_LAUNCH(8);
 #undef STOCS_PRUNE_LAUNCH
+        g.prune_group = short_lists ? 16 : 64;
+        g.prune_k = (pk == 4 || pk == 16) ? pk : 8;
         hipLaunchKernelGGL(cell_padded_kept_kernel, dim3(grid_of(n_cells)), dim3(256), 0, st, d_kept, n_cells, 8u, d_padded, d_max, d_total);
     } else
     hipLaunchKernelGGL(cell_padded_kernel, dim3(grid_of(n_cells)), dim3(256), 0, st, d_cell_first, n_cells, (uint32_t)n_inc, 8u, d_padded, d_max);
@@ -608,6 +622,7 @@ int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
     STOCS_HIP_CHECK(hipStreamSynchronize(st));
     const unsigned long long n_kept = prune ? rb64[1] : (unsigned long long)n_inc;
     const size_t n_list = tail[0];
+    g.longest_list = (int)tail[1];
     if (tail[1] > 65535u) { set_error("more than 65535 scene points within epsilon of one grid cell"); return STOCS_ERR_INVALID; }
     // normal cones above the 16-bit counts (normal_cone.h); STOCS_GRID_CONES=0: a grid without them (A/B runs, cross-checks)
     g.has_cones = !(getenv("STOCS_GRID_CONES") && atoi(getenv("STOCS_GRID_CONES")) == 0);

@@ -1554,6 +1554,22 @@ int stocs_get_cull_state(stocs_ctx* c, float* patches4, int32_t* perm, int* n_pa
     return STOCS_OK;
 }
 
+int stocs_get_grid_info(stocs_ctx* c, stocs_grid_info* info) {
+    if (!c || !info) { set_error("stocs_get_grid_info: NULL %s", !c ? "context" : "info"); return STOCS_ERR_INVALID; }
+    memset(info, 0, sizeof(*info));
+    const SceneGrid& g = c->grid;
+    if (c->nS <= 0 || !g.d_top) { set_error("stocs_get_grid_info: no scene"); return STOCS_ERR_STATE; }
+    info->origin[0] = g.ox; info->origin[1] = g.oy; info->origin[2] = g.oz;
+    info->h = g.h; info->inv_h = g.inv_h; info->div = g.div;
+    info->cells[0] = g.nx; info->cells[1] = g.ny; info->cells[2] = g.nz;
+    info->bricks[0] = g.nbx; info->bricks[1] = g.nby; info->bricks[2] = g.nbz;
+    info->centre_sorted = g.d_chunk_r != NULL; info->pruned = g.pruned; info->has_nearest = g.has_nearest; info->has_cones = g.has_cones;
+    info->has_flat = g.d_flat != NULL;
+    info->sort = g.sort_kind; info->prune_group = g.prune_group; info->prune_k = g.prune_k; info->longest_list = g.longest_list;
+    info->n_incidences = g.n_inc; info->n_cells = g.n_cells; info->n_bricks = g.n_bricks; info->n_entries = g.n_entries;
+    return STOCS_OK;
+}
+
 int stocs_time_score_kernel(stocs_ctx* c, const void* d_T16, int n, void* d_lcp, int reps, float* avg_ms) {
     if (!c || !avg_ms || reps <= 0 || n <= 0) return STOCS_ERR_INVALID;
     DeviceGuard dev_guard(c->device);

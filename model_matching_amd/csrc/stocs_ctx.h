@@ -165,7 +165,14 @@ struct SceneGrid {
     double avg_list_len;   // entries per non-empty cell (of the lists as stored: after the dominance pruning, when it is on)
     double avg_dilated_len;   // ... of every scene point within r of the cell box (what the list held before pruning)
     bool pruned;           // the lists hold only points that can be the nearest neighbour of some position in their cell (grid.hip)
-    int32_t* d_top;      // nbx*nby*nbz -> brick id or -1
+    // what the last build did, for stocs_get_grid_info (records only: nothing reads them back into a decision)
+    int div;               // cell edge = epsilon / div
+    int sort_kind;         // STOCS_GRID_SORT_*: which sort ordered the incidences (0: none ran)
+    int prune_group, prune_k;   // lanes per cell and dominators per entry of the prune kernel; 0, 0 when the lists are not pruned
+    int64_t n_inc;         // (cell, point) incidences
+    int64_t n_cells;       // non-empty cells
+    int longest_list;      // entries of the longest stored list (before padding)
+    int32_t* d_top;     // nbx*nby*nbz -> brick id or -1
     uint4* d_flat;       // the same cell words addressed directly, (cz*ny + cy)*nx + cx, when the box is small enough (sparse
                          // scenes, cell edge eps): saves the LCP kernel the dependent `top` look-up; else NULL
     uint4* d_cells;      // n_bricks*512: (offset, count, sub-cell mask lo, hi); mask bit s set <=> some scene

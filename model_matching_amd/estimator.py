@@ -894,6 +894,21 @@ class StocsEstimator:
             dist = None
         return patches[:npat.value], perm, g, dist
 
+    def grid_info(self):
+        """The scene grid as it was built (stocs_get_grid_info; diagnostics): a dict of the struct's fields, the per-axis ones as
+        tuples, origin / h / inv_h as numpy float32."""
+        gi = capi.GridInfo()
+        capi.check(self.L.stocs_get_grid_info(self.h, C.byref(gi)))
+        d = {}
+        for name, _ in capi.GridInfo._fields_:
+            v = getattr(gi, name)
+            d[name] = v
+        d["origin"] = np.array(list(gi.origin), np.float32)
+        d["h"] = np.float32(gi.h); d["inv_h"] = np.float32(gi.inv_h)
+        d["cells"] = tuple(gi.cells); d["bricks"] = tuple(gi.bricks)
+        del d["reserved"]
+        return d
+
     def set_option(self, key, value):
         capi.check(self.L.stocs_set_option(self.h, key.encode(), int(value)))
 
