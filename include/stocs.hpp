@@ -878,6 +878,40 @@ public:
         }
         return z;
     }
+    // The model as a triangle mesh (stocs_ctx_set_mesh; no reference counterpart): vertices (3 floats each) and triangles (3 indices
+    // each) in the frame of the model cloud; kept on the device until the next call, no triangles drops it.  render_depth_mesh and
+    // pose_errors_vsd_mesh are render_depth and pose_errors_vsd with the mesh rasterised exactly in place of the surfels (the two
+    // surfel fields of the parameters are not read).  false / empty on error (the text goes to the log).
+    bool set_mesh(const std::vector<float>& vertices3, const std::vector<int32_t>& triangles3) {
+        if (stocs_ctx_set_mesh(ctx_, vertices3.data(), (int)(vertices3.size() / 3), triangles3.data(), (int)(triangles3.size() / 3)) != STOCS_OK) {
+            *log_ << "set_mesh failed: " << stocs_last_error() << std::endl;
+            return false;
+        }
+        return true;
+    }
+    std::vector<stocs_vsd_record> pose_errors_vsd_mesh(const std::vector<PoseCandidate*>& est, const std::vector<PoseCandidate*>& gt, const stocs_vsd_params& prm) {
+        const int n = (int)est.size(), n_gt = (int)gt.size();
+        std::vector<float> P((size_t)n * 16), G((size_t)n_gt * 16);
+        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], est[(size_t)i]->transform.data(), 64);
+        for (int i = 0; i < n_gt; ++i) std::memcpy(&G[(size_t)i * 16], gt[(size_t)i]->transform.data(), 64);
+        std::vector<stocs_vsd_record> r((size_t)n);
+        if (n > 0 && stocs_pose_errors_vsd_mesh(ctx_, P.data(), n, G.data(), n_gt, &prm, r.data()) != STOCS_OK) {
+            *log_ << "pose_errors_vsd_mesh failed: " << stocs_last_error() << std::endl;
+            r.clear();
+        }
+        return r;
+    }
+    std::vector<float> render_depth_mesh(const std::vector<PoseCandidate*>& poses) {
+        const int n = (int)poses.size();
+        std::vector<float> P((size_t)n * 16);
+        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], poses[(size_t)i]->transform.data(), 64);
+        std::vector<float> z((size_t)n * (size_t)image_width * (size_t)image_height);
+        if (n > 0 && stocs_render_depth_mesh(ctx_, P.data(), n, z.data()) != STOCS_OK) {
+            *log_ << "render_depth_mesh failed: " << stocs_last_error() << std::endl;
+            z.clear();
+        }
+        return z;
+    }
 
     // Joint rendering (stocs_explain_poses; no reference counterpart): the camera-frame poses -- the instances select_instances kept, say
     // -- rendered TOGETHER against the frame of set_frame, nearest surface first: one record per pose in input order (footprint,

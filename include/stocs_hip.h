@@ -423,6 +423,14 @@ int stocs_trim(void);
 int stocs_png_read(const char* path, int* width, int* height, int* channels, int* bit_depth, void* pixels, int64_t cap_bytes);
 int stocs_ply_read(const char* path, float* pos3, float* nrm3, int cap, int* n, int* has_normals);
 int stocs_ply_write(const char* path, const float* pos3, const float* nrm3, int n, float scale);
+/* stocs_ply_read_mesh: the vertex element, then the face element of an ascii or binary_little_endian file: `property list <count type>
+ * <index type> vertex_indices` (or vertex_index), any integer types; other face properties are skipped.  A polygon of k >= 3 corners
+ * becomes the k - 2 triangles (0, i, i + 1) of a fan from its corner 0; one of fewer corners is STOCS_ERR_INVALID.  pos3 == NULL or
+ * tris3 == NULL queries the counts (*nt then counts triangles, after the fans).  `element face 0`, or no face element, gives *nt = 0
+ * and is no error.  Indices are handed on as they stand: stocs_mesh_check judges them.
+ * stocs_ply_write_mesh: ascii, 9 significant digits (floats round-trip), faces as `property list uchar int vertex_indices`. */
+int stocs_ply_read_mesh(const char* path, float* pos3, int cap_v, int* nv, int32_t* tris3, int cap_t, int* nt);
+int stocs_ply_write_mesh(const char* path, const float* pos3, int nv, const int32_t* tris3, int nt);
 
 /* clustering::point_to_plane_icp (pose_clustering.cpp:123-140: PCL IterativeClosestPointWithNormals, 5
  * iterations, 3.5 cm): own linearised point-to-plane ICP; T16_out maps the source cloud onto the target
@@ -1089,6 +1097,60 @@ int stocs_check_vsd_params(const stocs_vsd_params* p);
 int stocs_render_depth(stocs_ctx* ctx, const float* pose16_camera, int n, const stocs_vsd_params* p, float* depth /* n*height*width */);
 int stocs_pose_errors_vsd(stocs_ctx* ctx, const float* est_pose16_camera, int n, const float* gt_pose16_camera, int n_gt,
                           const stocs_vsd_params* p, stocs_vsd_record* out);
+
+/* ---- triangle meshes: a second model representation on the context, an exact, watertight depth rasteriser for it and VSD on that
+ * (no reference counterpart).  BOP, YCB-Video and LINEMOD ship their objects as meshes and bop_toolkit's VSD is defined on the rendered
+ * mesh; a surfel image depends on a radius chosen per model and pads the silhouette by up to that radius.  csrc/mesh.hip, restated in
+ * float32 numpy in tests/mesh_ref.py, equal bit for bit.  All in float, every operation one IEEE add / sub / mul / div / floor, no
+ * contraction.
+ * The mesh: nv vertices (float[3]) and nt triangles (int32[3], indices into the vertices), in the frame of the model points handed to
+ * stocs_ctx_create; keeping the two in step is the caller's job, as it is for the frame and the scene.
+ * A vertex v under a pose (R, t): p_a = (R_a0 v_0 + (R_a1 v_1 + R_a2 v_2)) + t_a, step 1 of the depth-check contract.
+ * A triangle (i0, i1, i2) with camera points A, B, C:
+ *   1. skipped unless all nine coordinates are finite and A_2, B_2, C_2 > 1e-6f.  There is NO near-plane clipping: a triangle that
+ *      reaches the camera plane renders nothing.
+ *   2. per vertex a = (fx * p_0) / p_2 + cx, b = (fy * p_1) / p_2 + cy;  c_lo = fmaxf(floorf(min a) - 1, 0),
+ *      c_hi = fminf(floorf(max a) + 2, W - 1), r_lo and r_hi likewise from b and H; skipped unless c_lo <= c_hi and r_lo <= r_hi, tested
+ *      in float; only then converted to int.  No size cap.
+ *   3. edge normals nA = B x C, nB = C x A, nC = A x B, a cross product written n_x = u_y v_z - u_z v_y, n_y = u_z v_x - u_x v_z,
+ *      n_z = u_x v_y - u_y v_x.
+ *   4. per pixel (r, c) of the box, with the ray of the surfel rule, xn = ((float)c - cx) / fx, yn = ((float)r - cy) / fy:
+ *        u = xn nA_0 + (yn nA_1 + nA_2), v and w likewise from nB and nC;  det = u + (v + w)
+ *        hit only if det != 0 and (u, v, w >= 0 or u, v, w <= 0): edges are inclusive, and there is no back-face culling, so winding
+ *        does not matter and open meshes render
+ *        z = (u A_2 + (v B_2 + w C_2)) / det;  hit only if z > 1e-6f
+ *        a hit pixel gets zbuf = min(zbuf, bits(z)); empty is all ones.
+ * B x A is exactly -(A x B) in IEEE arithmetic and the dot with the ray negates exactly too, so two triangles that share an edge see
+ * the same edge value with opposite sign: a ray is inside at least one of them and a ray exactly on the edge is inside both -- no
+ * pinholes.  The z-buffer is a minimum of float bits: a render depends on neither triangle order, winding, batch nor chunk.  The
+ * reversed triangle (i0, i2, i1) turns u, v, w into -u, -w, -v exactly, and det and z come out the same bits (v + w is w + v).  Which
+ * corner comes first is not winding: (i1, i2, i0) permutes u, v, w, hits the same pixels, and sums det and z in another order, so their
+ * last bits may differ (2 ulp measured).  A pose with a non-finite used entry, or the all-zero record, renders nothing, as for surfels.
+ * stocs_mesh_check: the host check of a mesh on its own (no context, no device): STOCS_ERR_INVALID for a negative count, a NULL array
+ * of a non-zero count, an index outside [0, nv) or a non-finite vertex; STOCS_ERR_CAPACITY above nv <= 2^24, nt <= 2^22.
+ * stocs_ctx_set_mesh: copies the mesh to the device, where it stays until the next call or stocs_ctx_destroy; nt == 0 drops it (and
+ * looks at nothing else).  stocs_mesh_check's answers; synchronises once; grow-only (a second mesh of the same or a smaller size
+ * allocates nothing).  stocs_ctx_mesh_info: the counts on the context (0, 0 without a mesh).
+ * stocs_render_depth_mesh: the images of stocs_render_depth from the mesh.  stocs_pose_errors_vsd_mesh: stocs_pose_errors_vsd with the
+ * mesh rendered in place of the surfels: the same compare pass, the same stocs_vsd_params (surfel_radius and max_splat_px are ignored,
+ * whatever they hold) and the same stocs_vsd_record.  Checked in the order of their surfel counterparts, with "no mesh" where those
+ * have "no model": STOCS_ERR_STATE.  stocs_mesh_last_call_timing gives the steps of the last stocs_pose_errors_vsd_mesh as
+ * stocs_last_call_timing does for the calls it knows.
+ * The kernel (csrc/mesh.hip): a workgroup of four wavefronts per (pose, 256 triangles), one triangle per lane for the set-up; a box of
+ * at most STOCS_MESH_SMALL_PX pixels is walked by its lane, a larger one swept by the wavefront from scalar registers, the largest by
+ * the workgroup.  STOCS_MESH_FORM=<bits> in the environment forces forms for measurements and tests (1: lanes walk their own boxes;
+ * 2: none does; 4: read the stored depth before every atomicMin, 8: never, the default; 16: no box goes to the workgroup); no bit changes a result.
+ * STOCS_VSD_CHUNK keeps its meaning.  stocs_mesh_small_px returns STOCS_MESH_SMALL_PX as the library was built; STOCS_MESH_SMALL_PX=<pixels>
+ * in the environment overrides it for measurements (tools/mesh_time.py --forms) and changes no result either. ---- */
+#define STOCS_MESH_SMALL_PX 120
+int stocs_mesh_small_px(void);
+int stocs_mesh_check(const float* pos3, int nv, const int32_t* tris3, int nt);
+int stocs_ctx_set_mesh(stocs_ctx* ctx, const float* pos3, int nv, const int32_t* tris3, int nt);
+int stocs_ctx_mesh_info(const stocs_ctx* ctx, int* nv, int* nt);
+int stocs_render_depth_mesh(stocs_ctx* ctx, const float* pose16_camera, int n, float* depth /* n*height*width */);
+int stocs_pose_errors_vsd_mesh(stocs_ctx* ctx, const float* est_pose16_camera, int n, const float* gt_pose16_camera, int n_gt,
+                               const stocs_vsd_params* p, stocs_vsd_record* out);
+int stocs_mesh_last_call_timing(const stocs_ctx* ctx, const char** labels, double* ms, int cap, int* n);
 
 /* ---- tuning knobs (never change results beyond float summation order).
  * "lcp_variant": 99 = automatic (default): the scan fed from a per-wavefront LDS queue of the queries that have a list -- over

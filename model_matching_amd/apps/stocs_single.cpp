@@ -51,7 +51,8 @@
 // --trials N one "gt <object> vsd trial t: e0=... .. e9=... valid=..." line per trial's winner and "gt <object> vsd recall: trials=N
 // valid=... vsd=...": BOP's average recall of VSD, the mean over the ten taus and the correctness thresholds 0.05 .. 0.50 of the share of
 // ALL trials with e below the threshold (a trial without a pose counts as wrong: VSD is defined for it).  Without --vsd the output is
-// what it is without these options.
+// what it is without these options.  --mesh <ply> (with --vsd): the model as a triangle mesh, in the frame of the model cloud; the VSD
+// lines then come from the exact rasteriser (stocs_pose_errors_vsd_mesh) and say "mesh=<triangles>" where they said "surfel_radius=...".
 // --depth-check (with --trials N --cluster 1 [--refine K], a scene directory): every trial's hypotheses -- the refined poses when
 // refinement ran -- scored against the frame's own depth image and class-probability map (stocs_depth_check_poses); one "depth t.i:"
 // line per hypothesis, and <out> is written from the first maximum of score - violation (ties: the higher lcp, then the lower trial
@@ -354,7 +355,7 @@ static bool read_pose_file(const std::string& path, MatrixType& m) {
 // --gt: the pose this run wrote to out_path, read back with the reader the ground truth goes through (what is scored is what a reader of
 // the file gets), against the ground truth: ADD, ADD-S, their maxima, the model's diameter (stocs_pose_errors, stocs_model_diameter); with
 // --trials N also the share of the trials' winners (full precision, a trial without a pose left out) within 0.1 diameter
-struct VsdOptions { bool on; float delta, surfel_radius; };   // --vsd; a value <= 0 leaves the library's default
+struct VsdOptions { bool on; float delta, surfel_radius; int mesh_triangles; };   // --vsd; a value <= 0 leaves the library's default; mesh_triangles > 0: --mesh
 
 // the ten errors of a VSD record as " e0=... .. e9=..." at b + at; returns the new end
 static int print_vsd_errors(char* b, size_t cap, int at, const stocs_vsd_record& r, int n_tau) {
@@ -398,9 +399,12 @@ static int report_gt(stocs::stocs_estimator& est, const std::string& gt_path, co
             std::cout << b << std::endl;
         }
         if (vsd.on) {
-            const std::vector<stocs_vsd_record> q = est.pose_errors_vsd(std::vector<PoseCandidate*>(1, &e), gts, vp);
+            const std::vector<PoseCandidate*> es(1, &e);
+            const std::vector<stocs_vsd_record> q = vsd.mesh_triangles > 0 ? est.pose_errors_vsd_mesh(es, gts, vp) : est.pose_errors_vsd(es, gts, vp);
             if (q.size() != 1) { std::cerr << "visible-surface discrepancy failed: " << stocs_last_error() << std::endl; return 2; }
-            int at = snprintf(b, sizeof(b), "gt %s vsd: taus=%d delta=%.9g surfel_radius=%.9g", object.c_str(), vp.n_tau, (double)vp.delta, (double)vp.surfel_radius);
+            int at = snprintf(b, sizeof(b), "gt %s vsd: taus=%d delta=%.9g", object.c_str(), vp.n_tau, (double)vp.delta);
+            if (vsd.mesh_triangles > 0) at += snprintf(b + at, sizeof(b) - (size_t)at, " mesh=%d", vsd.mesh_triangles);
+            else at += snprintf(b + at, sizeof(b) - (size_t)at, " surfel_radius=%.9g", (double)vp.surfel_radius);
             at = print_vsd_errors(b, sizeof(b), at, q[0], vp.n_tau);
             double mean = 0.0;
             for (int t = 0; t < vp.n_tau; ++t) mean += (double)q[0].e[t];
@@ -447,7 +451,7 @@ static int report_gt(stocs::stocs_estimator& est, const std::string& gt_path, co
             std::cout << b << std::endl;
         }
         if (vsd.on) {
-            const std::vector<stocs_vsd_record> q = est.pose_errors_vsd(wp, gts, vp);
+            const std::vector<stocs_vsd_record> q = vsd.mesh_triangles > 0 ? est.pose_errors_vsd_mesh(wp, gts, vp) : est.pose_errors_vsd(wp, gts, vp);
             if (q.size() != wp.size()) { std::cerr << "visible-surface discrepancy failed: " << stocs_last_error() << std::endl; return 2; }
             int nv = 0, hits = 0;   // hits summed over the taus and the ten correctness thresholds
             for (size_t t = 0; t < q.size(); ++t) {
@@ -662,7 +666,8 @@ int main(int argc, char** argv) {
     int do_cluster = 0, n_trials = 0, exact_ties = 0, n_refine = 0, depth_check = 0;
     bool do_instances = false, do_masks = false, have_trim = false, have_gate = false;
     SceneSelectOptions scene_opt = {false, false, 0};
-    VsdOptions vsd_opt = {false, 0.0f, 0.0f};
+    VsdOptions vsd_opt = {false, 0.0f, 0.0f, 0};
+    std::string mesh_path;
     bool have_vsd_delta = false, have_surfel_radius = false;
     stocs_instance_params inst_prm = stocs::stocs_estimator::default_instance_params();
     uint64_t seed = 1;
@@ -703,6 +708,7 @@ int main(int argc, char** argv) {
         else if (k == "--sym-file") sym_path = v;
         else if (k == "--vsd-delta") { vsd_opt.delta = (float)atof(v.c_str()); have_vsd_delta = true; }
         else if (k == "--surfel-radius") { vsd_opt.surfel_radius = (float)atof(v.c_str()); have_surfel_radius = true; }
+        else if (k == "--mesh") mesh_path = v;   // with --vsd: the model as a triangle mesh, rasterised in place of the surfels
         else if (k == "--instances") { do_instances = true; inst_prm.max_instances = atoi(v.c_str()); }
         else if (k == "--instance-min-fraction") inst_prm.min_exclusive_fraction = (float)atof(v.c_str());
         else if (k == "--instance-min-points") inst_prm.min_points = atoi(v.c_str());
@@ -731,6 +737,20 @@ int main(int argc, char** argv) {
         }
     }
 
+    std::vector<float> mesh_v;
+    std::vector<int32_t> mesh_t;
+    if (!mesh_path.empty()) {   // refused before any search
+        if (!vsd_opt.on || have_surfel_radius) { std::cerr << "--mesh <ply> needs --vsd and takes no --surfel-radius" << std::endl; return -1; }
+        int nv = 0, nt = 0;
+        if (stocs_ply_read_mesh(mesh_path.c_str(), NULL, 0, &nv, NULL, 0, &nt) != STOCS_OK) { std::cerr << "cannot read a mesh from " << mesh_path << ": " << stocs_last_error() << std::endl; return 1; }
+        if (nt < 1) { std::cerr << mesh_path << " has no faces" << std::endl; return 1; }
+        mesh_v.resize((size_t)nv * 3); mesh_t.resize((size_t)nt * 3);
+        if (stocs_ply_read_mesh(mesh_path.c_str(), mesh_v.data(), nv, &nv, mesh_t.data(), nt, &nt) != STOCS_OK || stocs_mesh_check(mesh_v.data(), nv, mesh_t.data(), nt) != STOCS_OK) {
+            std::cerr << "cannot read a mesh from " << mesh_path << ": " << stocs_last_error() << std::endl;
+            return 1;
+        }
+        vsd_opt.mesh_triangles = nt;
+    }
     if (vsd_opt.on || have_vsd_delta || have_surfel_radius) {   // refused before any search
         if (!vsd_opt.on || gt_path.empty() || clouds || a2.find(',') != std::string::npos) {
             std::cerr << "--vsd [--vsd-delta m] [--surfel-radius m] needs --gt, a scene directory and a single object" << std::endl;
@@ -862,6 +882,7 @@ int main(int argc, char** argv) {
                                        : run_search(*est, std::cout, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine, depth_check,
                                                     do_instances ? &inst_prm : NULL, instances_path, labels_path, &trial_results);
     if (rc != 0 || gt_path.empty()) return rc;
+    if (vsd_opt.mesh_triangles > 0 && !est->set_mesh(mesh_v, mesh_t)) { std::cerr << "set_mesh failed: " << stocs_last_error() << std::endl; return 2; }
     stocs_camera cam;   // a scene directory has a camera: MSPD is reported too
     memset(&cam, 0, sizeof(cam));
     cam.fx = cam_intrinsics[0]; cam.cx = cam_intrinsics[1]; cam.fy = cam_intrinsics[2]; cam.cy = cam_intrinsics[3];

@@ -184,6 +184,8 @@ SIGNATURES = {
     "stocs_png_read": (C.c_int, [C.c_char_p, _intp, _intp, _intp, _intp, _vp, C.c_int64]),
     "stocs_ply_read": (C.c_int, [C.c_char_p, _fp, _fp, C.c_int, _intp, _intp]),
     "stocs_ply_write": (C.c_int, [C.c_char_p, _fp, _fp, C.c_int, C.c_float]),
+    "stocs_ply_read_mesh": (C.c_int, [C.c_char_p, _fp, C.c_int, _intp, _ip, C.c_int, _intp]),
+    "stocs_ply_write_mesh": (C.c_int, [C.c_char_p, _fp, C.c_int, _ip, C.c_int]),
     "stocs_set_bases": (C.c_int, [_vp, C.c_int, _ip, _fp]),
     "stocs_clear_bases": (C.c_int, [_vp]),
     "stocs_num_bases": (C.c_int, [_vp]),
@@ -249,6 +251,13 @@ SIGNATURES = {
     "stocs_check_vsd_params": (C.c_int, [C.POINTER(VsdParams)]),
     "stocs_render_depth": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(VsdParams), _fp]),
     "stocs_pose_errors_vsd": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, C.POINTER(VsdParams), C.POINTER(VsdRecord)]),
+    "stocs_mesh_small_px": (C.c_int, []),
+    "stocs_mesh_check": (C.c_int, [_fp, C.c_int, _ip, C.c_int]),
+    "stocs_ctx_set_mesh": (C.c_int, [_vp, _fp, C.c_int, _ip, C.c_int]),
+    "stocs_ctx_mesh_info": (C.c_int, [_vp, _intp, _intp]),
+    "stocs_render_depth_mesh": (C.c_int, [_vp, _fp, C.c_int, _fp]),
+    "stocs_pose_errors_vsd_mesh": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, C.POINTER(VsdParams), C.POINTER(VsdRecord)]),
+    "stocs_mesh_last_call_timing": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.c_int, _intp]),
     "stocs_pose_errors": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, C.POINTER(PoseError)]),
     "stocs_pose_errors_detail": (C.c_int, [_vp, _fp, _fp, _fp, _fp, _ip]),
     "stocs_model_diameter": (C.c_int, [_vp, _fp]),

@@ -533,7 +533,7 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
     c->nS = nS; c->nM = nM;
     c->d_scratch = NULL; c->scratch_bytes = 0;
     c->h_pin = NULL; c->pin_bytes = 0;
-    for (int k = 0; k < 8; ++k) c->timing[k].n = 0;
+    for (int k = 0; k < 9; ++k) c->timing[k].n = 0;
     c->index.built = false;
     c->index.d_bucket_start = NULL; c->index.d_pairs = NULL; c->index.d_exists = NULL;
     c->cong = NULL; c->quad_id_bits = 16;
@@ -547,6 +547,7 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
     c->pose_error_sym = NULL;
     c->symmetry = NULL;
     c->vsd = NULL;
+    c->mesh = NULL;
     c->inst = NULL;
     c->trials = NULL; c->snrmw_trial0 = NULL; c->snrmw_stride = 0; c->snrmw_override = NULL; c->lcp_cand_trial = NULL;
     c->d_cand = NULL; c->cand_bytes = 0; c->n_cands = 0; c->cand_cap = 0; c->cands_stale = false;
@@ -700,6 +701,7 @@ int stocs_ctx_destroy(stocs_ctx* c) {
     stocs_internal_free_pose_error_sym(c);
     stocs_internal_free_symmetry(c);
     stocs_internal_free_vsd(c);
+    stocs_internal_free_mesh(c);
     c->grid_mem.destroy(); c->grid_ws.destroy();
     c->order.free(); c->cdf.free(); c->kd.free();
     if (c->h_pin) (void)hipHostFree(c->h_pin);
@@ -796,15 +798,23 @@ int stocs_dev_download(stocs_ctx* c, void* host, const void* dptr, int64_t bytes
     return STOCS_OK;
 }
 
-int stocs_last_call_timing(const stocs_ctx* c, int which, const char** labels, double* ms, int cap, int* n) {
-    if (!c || which < 0 || which > 7 || !n || cap < 0) return STOCS_ERR_INVALID;
-    const CallTiming& t = c->timing[which];
+static int copy_timing(const CallTiming& t, const char** labels, double* ms, int cap, int* n) {
     *n = t.n;
     for (int i = 0; i < t.n && i < cap; ++i) {
         if (labels) labels[i] = t.label[i];
         if (ms) ms[i] = t.ms[i];
     }
     return t.n > cap ? STOCS_ERR_CAPACITY : STOCS_OK;
+}
+
+int stocs_last_call_timing(const stocs_ctx* c, int which, const char** labels, double* ms, int cap, int* n) {
+    if (!c || which < 0 || which > 7 || !n || cap < 0) return STOCS_ERR_INVALID;
+    return copy_timing(c->timing[which], labels, ms, cap, n);
+}
+
+int stocs_mesh_last_call_timing(const stocs_ctx* c, const char** labels, double* ms, int cap, int* n) {
+    if (!c || !n || cap < 0) return STOCS_ERR_INVALID;
+    return copy_timing(c->timing[8], labels, ms, cap, n);
 }
 
 // CPU-only self test of the STOCS_DEBUG_STREAMS checker (stream_audit.h) on canned two-stream sequences: 0 = the fork / join

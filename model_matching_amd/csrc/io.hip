@@ -230,4 +230,124 @@ int stocs_ply_write(const char* path, const float* pos3, const float* nrm3, int 
     return (fclose(f) == 0 && ok) ? STOCS_OK : STOCS_ERR_INVALID;
 }
 
+// the vertex element, then the face element; every element of the header is walked in file order, so that elements between the two
+// and properties beside the index list are stepped over
+int stocs_ply_read_mesh(const char* path, float* pos3, int cap_v, int* nv_out, int32_t* tris3, int cap_t, int* nt_out) {
+    static const char* who = "stocs_ply_read_mesh";
+    if (!path || !nv_out || !nt_out) return STOCS_ERR_INVALID;
+    std::vector<unsigned char> file;
+    if (!read_file(path, &file)) { set_error("cannot read %s", path); return STOCS_ERR_INVALID; }
+    size_t pos = 0;
+    auto next_line = [&](std::string* line) {
+        if (pos >= file.size()) return false;
+        size_t e = pos;
+        while (e < file.size() && file[e] != '\n') ++e;
+        line->assign((const char*)&file[pos], e - pos);
+        if (!line->empty() && line->back() == '\r') line->pop_back();
+        pos = e + 1;
+        return true;
+    };
+    struct Prop { bool list; std::string count_type, type, name; };
+    struct Element { std::string name; long long count; std::vector<Prop> props; };
+    std::vector<Element> els;
+    std::string line;
+    if (!next_line(&line) || line != "ply") { set_error("%s is not a PLY file", path); return STOCS_ERR_INVALID; }
+    int fmt = -1;
+    bool ended = false;
+    while (next_line(&line)) {
+        char a[64] = "", b[64] = "", c3[64] = "", d[64] = "", e5[64] = "";
+        const int k = sscanf(line.c_str(), "%63s %63s %63s %63s %63s", a, b, c3, d, e5);
+        if (k >= 1 && !strcmp(a, "end_header")) { ended = true; break; }
+        if (k >= 2 && !strcmp(a, "format")) fmt = !strcmp(b, "ascii") ? 0 : (!strcmp(b, "binary_little_endian") ? 1 : -1);
+        else if (k >= 3 && !strcmp(a, "element")) { Element el; el.name = b; el.count = atoll(c3); els.push_back(el); }
+        else if (k >= 3 && !strcmp(a, "property") && !els.empty()) {
+            Prop p;
+            p.list = !strcmp(b, "list");
+            if (p.list) { if (k < 5) { set_error("%s: bad list property", path); return STOCS_ERR_INVALID; } p.count_type = c3; p.type = d; p.name = e5; }
+            else { p.type = b; p.name = c3; }
+            if (!ply_type_size(p.type) || (p.list && !ply_type_size(p.count_type))) { set_error("%s: unknown property type in '%s'", path, line.c_str()); return STOCS_ERR_INVALID; }
+            els.back().props.push_back(p);
+        }
+    }
+    if (!ended || fmt < 0 || els.empty() || els[0].name != "vertex" || els[0].count < 0) {
+        set_error("%s: unsupported PLY header (ascii / binary_little_endian with the vertex element first)", path);
+        return STOCS_ERR_INVALID;
+    }
+    const long long nv = els[0].count;
+    if (nv > 0x7FFFFFFF) { set_error("%s: %lld vertices", path, nv); return STOCS_ERR_CAPACITY; }
+    const bool query = !pos3 || !tris3;
+    if (!query && nv > cap_v) { set_error("%s: %lld vertices, capacity %d", who, nv, cap_v); return STOCS_ERR_CAPACITY; }
+    long long nt = 0;
+    bool face_seen = false;
+    std::vector<double> vals;
+    for (size_t ei = 0; ei < els.size(); ++ei) {
+        const Element& el = els[ei];
+        const bool is_vertex = ei == 0, is_face = !face_seen && ei > 0 && el.name == "face";
+        int ix[3] = {-1, -1, -1}, il = -1;
+        for (size_t i = 0; i < el.props.size(); ++i) {
+            const Prop& p = el.props[i];
+            if (is_vertex && p.list) { set_error("%s: list property in the vertex element", path); return STOCS_ERR_INVALID; }
+            if (is_vertex && p.name == "x") ix[0] = (int)i; else if (is_vertex && p.name == "y") ix[1] = (int)i; else if (is_vertex && p.name == "z") ix[2] = (int)i;
+            if (is_face && p.list && (p.name == "vertex_indices" || p.name == "vertex_index")) il = (int)i;
+        }
+        if (is_vertex && (ix[0] < 0 || ix[1] < 0 || ix[2] < 0)) { set_error("%s: no x / y / z vertex properties", path); return STOCS_ERR_INVALID; }
+        if (is_face && el.count > 0 && il < 0) { set_error("%s: the face element has no vertex_indices list", path); return STOCS_ERR_INVALID; }
+        if (is_face) face_seen = true;
+        for (long long r = 0; r < el.count; ++r) {
+            const char* sp = NULL;
+            if (fmt == 0) {
+                if (!next_line(&line)) { set_error("%s: truncated %s list", path, el.name.c_str()); return STOCS_ERR_INVALID; }
+                sp = line.c_str();
+            }
+            auto value = [&](const std::string& type, double* v) {   // the next value of the record, of the given type
+                if (fmt == 0) { char* e = NULL; *v = strtod(sp, &e); if (e == sp) return false; sp = e; return true; }
+                const size_t sz = (size_t)ply_type_size(type);
+                if (pos + sz > file.size()) return false;
+                *v = ply_bin_value(&file[pos], type);
+                pos += sz;
+                return true;
+            };
+            for (size_t i = 0; i < el.props.size(); ++i) {
+                const Prop& p = el.props[i];
+                double v = 0.0;
+                if (!p.list) {
+                    if (!value(p.type, &v)) { set_error("%s: bad or truncated %s record %lld", path, el.name.c_str(), r); return STOCS_ERR_INVALID; }
+                    if (is_vertex && !query) for (int k = 0; k < 3; ++k) if (ix[k] == (int)i) pos3[3 * r + k] = (float)v;
+                    continue;
+                }
+                if (!value(p.count_type, &v) || v < 0 || v > 1e6) { set_error("%s: bad or truncated %s record %lld", path, el.name.c_str(), r); return STOCS_ERR_INVALID; }
+                const int cnt = (int)v;
+                vals.resize((size_t)cnt);
+                for (int j = 0; j < cnt; ++j)
+                    if (!value(p.type, &vals[(size_t)j])) { set_error("%s: bad or truncated %s record %lld", path, el.name.c_str(), r); return STOCS_ERR_INVALID; }
+                if (!is_face || (int)i != il) continue;
+                if (cnt < 3) { set_error("%s: face %lld has %d corners", path, r, cnt); return STOCS_ERR_INVALID; }
+                for (int j = 1; j + 1 < cnt; ++j, ++nt) {   // a fan from corner 0
+                    if (query) continue;
+                    if (nt >= cap_t) { set_error("%s: more than the capacity of %d triangles", who, cap_t); return STOCS_ERR_CAPACITY; }
+                    const double tri[3] = {vals[0], vals[(size_t)j], vals[(size_t)j + 1]};
+                    for (int k = 0; k < 3; ++k) tris3[3 * nt + k] = (tri[k] >= -2147483648.0 && tri[k] <= 2147483647.0) ? (int32_t)tri[k] : -1;
+                }
+            }
+        }
+        if (is_face || (query && face_seen)) break;
+        if (query && is_vertex && !(els.size() > 1)) break;
+    }
+    if (nt > 0x7FFFFFFF) { set_error("%s: %lld triangles", path, nt); return STOCS_ERR_CAPACITY; }
+    *nv_out = (int)nv; *nt_out = (int)nt;
+    return STOCS_OK;
+}
+
+int stocs_ply_write_mesh(const char* path, const float* pos3, int nv, const int32_t* tris3, int nt) {
+    if (!path || nv < 0 || nt < 0 || (nv && !pos3) || (nt && !tris3)) return STOCS_ERR_INVALID;
+    FILE* f = fopen(path, "w");
+    if (!f) { set_error("cannot write %s", path); return STOCS_ERR_INVALID; }
+    fprintf(f, "ply\nformat ascii 1.0\ncomment written by libstocs_hip\nelement vertex %d\nproperty float x\nproperty float y\nproperty float z\n", nv);
+    fprintf(f, "element face %d\nproperty list uchar int vertex_indices\nend_header\n", nt);
+    for (int i = 0; i < nv; ++i) fprintf(f, "%.9g %.9g %.9g\n", (double)pos3[3 * i], (double)pos3[3 * i + 1], (double)pos3[3 * i + 2]);
+    for (int i = 0; i < nt; ++i) fprintf(f, "3 %d %d %d\n", (int)tris3[3 * i], (int)tris3[3 * i + 1], (int)tris3[3 * i + 2]);
+    const bool ok = !ferror(f);
+    return (fclose(f) == 0 && ok) ? STOCS_OK : STOCS_ERR_INVALID;
+}
+
 }  // extern "C"

@@ -364,7 +364,7 @@ struct stocs_ctx {
     // pageable memory goes through the runtime's own staging and is one more thing that can stall (ensure_pinned grows it)
     void* h_pin;
     size_t pin_bytes;
-    stocs::CallTiming timing[8];   // last stocs_find_congruent_all / stocs_make_transforms / stocs_verify_all / stocs_run_trials / stocs_pose_errors / stocs_pose_errors_sym / stocs_symmetry_errors / stocs_pose_errors_vsd
+    stocs::CallTiming timing[9];   // last stocs_find_congruent_all / stocs_make_transforms / stocs_verify_all / stocs_run_trials / stocs_pose_errors / stocs_pose_errors_sym / stocs_symmetry_errors / stocs_pose_errors_vsd / stocs_pose_errors_vsd_mesh (the last through stocs_mesh_last_call_timing)
 
     stocs::StreamAudit audit;   // STOCS_DEBUG_STREAMS=1: happens-before check of the two-stream sections (stream_audit.h); off otherwise
 
@@ -391,6 +391,8 @@ struct stocs_ctx {
     void* symmetry;        // symmetry.hip (SymmetryState): the model's self-distance grid of stocs_symmetry_errors and its grow-only workspace (last: no other member moves)
 
     void* vsd;             // vsd.hip (VsdState): the grow-only workspace of stocs_pose_errors_vsd and stocs_render_depth (last: no other member moves)
+
+    void* mesh;            // mesh.hip (MeshState): the triangle mesh of stocs_ctx_set_mesh on the device (last: no other member moves)
 };
 
 namespace stocs {
@@ -469,6 +471,7 @@ extern "C" void stocs_internal_free_pose_error(stocs_ctx* c);
 extern "C" void stocs_internal_free_pose_error_sym(stocs_ctx* c);
 extern "C" void stocs_internal_free_symmetry(stocs_ctx* c);
 extern "C" void stocs_internal_free_vsd(stocs_ctx* c);
+extern "C" void stocs_internal_free_mesh(stocs_ctx* c);
 // the congruent phase with a ceiling on its device memory: *too_big != 0 (and STOCS_OK) when the pair lists of the context's base set
 // would need more than max_bytes (0: no ceiling) or exceed 2^32 entries -- a trial batch then splits the base set and tries again
 extern "C" int stocs_internal_find_congruent(stocs_ctx* c, int64_t* total_quads, size_t max_bytes, int* too_big);

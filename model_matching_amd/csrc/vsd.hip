@@ -22,6 +22,8 @@
 //             non-zero counter and workgroup into the pair's counts.  A round whose 64 pixels are empty in both buffers reads nothing else.
 // The e[t] of a record are formed on the host from the counts that come back (one division each).  stocs_render_depth runs the render
 // kernel alone and turns bits into floats while it copies the pinned block out.
+// The two call bodies take a renderer (vsd_shared.h): mesh.hip fills the same z-buffers from triangles and shares the chunks, the rectangle
+// slots, the clears, the compare and the records with the surfels.
 // STOCS_VSD_FORM=<bits> forces a form of the kernels (vsd_form below); every form gives the same bits.
 // Known limits: whole frames are cleared (a pose's rectangle is known only after projection); a pixel's ray (two divisions) is recomputed
 // for every surfel that tests it.
@@ -31,6 +33,7 @@
 
 #include "pose_error_math.h"
 #include "render_rules.h"
+#include "vsd_shared.h"
 #include "wave_bits.h"
 
 namespace stocs {
@@ -44,14 +47,6 @@ struct VsdState {
 
 struct VsdSurfelArgs { float radius, r2; int max_px, read_first; };
 struct VsdCompareArgs { float delta; int n_tau; float tau[STOCS_VSD_MAX_TAU]; };
-
-// A rendered pose's bounding rectangle, the union of its surfels' clipped squares, as four maxima (-c0, c1, -r0, r1) so that one byte
-// pattern clears it (0x80: every entry far below any pixel) and one atomicMax per entry and wavefront fills it.  Nothing rendered: it
-// stays cleared, and c1 < c0.
-enum { VB_NEG_C0 = 0, VB_C1, VB_NEG_R0, VB_R1, VSD_BOX_WORDS = 4 };
-
-__device__ __forceinline__ float lane_f(float v, int src) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src)); }
-__device__ __forceinline__ int lane_i(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
 
 // zbuf: the z-buffer of pose blockIdx.y of the launch at zbuf + blockIdx.y * npix, its rectangle at box + blockIdx.y * VSD_BOX_WORDS
 __global__ __launch_bounds__(256) void vsd_render_kernel(const float* __restrict__ poses, const float4* __restrict__ mpos, const float4* __restrict__ mnrm, int nM, DepthArgs a,
@@ -209,13 +204,18 @@ static int check_surfel(const char* who, const stocs_vsd_params* p) {
     return STOCS_OK;
 }
 
-static int check_vsd(const char* who, const stocs_vsd_params* p) {
-    { const int rc = check_surfel(who, p); if (rc) return rc; }
+// delta and the taus, which the compare reads
+static int check_compare(const char* who, const stocs_vsd_params* p) {
     if (!(p->delta > 0.0f) || !isfinite(p->delta)) { set_error("%s: delta %g must be positive and finite", who, (double)p->delta); return STOCS_ERR_INVALID; }
     if (p->n_tau < 1 || p->n_tau > STOCS_VSD_MAX_TAU) { set_error("%s: n_tau %d outside 1..%d", who, p->n_tau, (int)STOCS_VSD_MAX_TAU); return STOCS_ERR_INVALID; }
     for (int t = 0; t < p->n_tau; ++t)
         if (!(p->tau[t] > 0.0f) || !isfinite(p->tau[t])) { set_error("%s: tau[%d] = %g must be positive and finite", who, t, (double)p->tau[t]); return STOCS_ERR_INVALID; }
     return STOCS_OK;
+}
+
+static int check_vsd(const char* who, const stocs_vsd_params* p) {
+    { const int rc = check_surfel(who, p); if (rc) return rc; }
+    return check_compare(who, p);
 }
 
 // STOCS_VSD_FORM=<bits> in the environment chooses the kernels' forms, for measurements and for the tests; no bit changes a result.
@@ -239,6 +239,13 @@ static VsdSurfelArgs surfel_args(const stocs_vsd_params* p, int nM, size_t n_ren
     return s;
 }
 
+// m poses at d_pose into the m z-buffers at d_z and their rectangles at d_box, both cleared first
+static int render_into(stocs_ctx* c, const VsdRenderer& rd, const float* d_pose, int m, const DepthArgs& a, size_t npix, uint32_t* d_z, int32_t* d_box) {
+    STOCS_HIP_CHECK(hipMemsetAsync(d_z, 0xFF, (size_t)m * npix * 4, c->stream));
+    STOCS_HIP_CHECK(hipMemsetAsync(d_box, 0x80, (size_t)m * VSD_BOX_WORDS * 4, c->stream));
+    return rd.render(c, rd.self, d_pose, m, a, d_z, d_box);
+}
+
 // how many rendered poses a chunk of z-buffers holds: 256 MB of them, or what STOCS_VSD_CHUNK says
 static size_t chunk_poses(size_t npix) {
     size_t chunk = std::max<size_t>(2, ((size_t)256 << 20) / (4 * npix));
@@ -246,10 +253,9 @@ static size_t chunk_poses(size_t npix) {
     return std::min<size_t>(chunk, 65534);   // a rendered pose is blockIdx.y
 }
 
-// m poses at d_pose into the m z-buffers at d_z and their rectangles at d_box, both cleared first
-static int render_into(stocs_ctx* c, const float* d_pose, int m, const DepthArgs& a, const VsdSurfelArgs& sa, size_t npix, uint32_t* d_z, int32_t* d_box) {
-    STOCS_HIP_CHECK(hipMemsetAsync(d_z, 0xFF, (size_t)m * npix * 4, c->stream));
-    STOCS_HIP_CHECK(hipMemsetAsync(d_box, 0x80, (size_t)m * VSD_BOX_WORDS * 4, c->stream));
+// the surfel renderer as a VsdRenderer: self is the call's VsdSurfelArgs
+static int render_surfels(stocs_ctx* c, const void* self, const float* d_pose, int m, const DepthArgs& a, uint32_t* d_z, int32_t* d_box) {
+    const VsdSurfelArgs& sa = *(const VsdSurfelArgs*)self;
     const unsigned point_chunks = (unsigned)((c->nM + VSD_POINTS - 1) / VSD_POINTS);
     hipLaunchKernelGGL(vsd_render_kernel, dim3(point_chunks, (unsigned)m), dim3(256), 0, c->stream, d_pose, (const float4*)c->d_mpos_raw, (const float4*)c->d_mnrm, c->nM, a, sa,
                        d_z, d_box);
@@ -280,6 +286,8 @@ extern "C" int stocs_check_vsd_params(const stocs_vsd_params* p) {
     return check_vsd("stocs_check_vsd_params", p);
 }
 
+int stocs::vsd_check_compare_params(const char* who, const stocs_vsd_params* p) { return check_compare(who, p); }
+
 extern "C" int stocs_render_depth(stocs_ctx* c, const float* poses, int n, const stocs_vsd_params* prm, float* depth) {
     static const char* who = "stocs_render_depth";
     if (!c) { set_error("%s: NULL context", who); return STOCS_ERR_INVALID; }
@@ -290,6 +298,12 @@ extern "C" int stocs_render_depth(stocs_ctx* c, const float* poses, int n, const
     if (c->nM < 1) { set_error("%s: the context has no model", who); return STOCS_ERR_STATE; }
     DepthState* F = NULL;
     { const int rc = check_frame(who, c, &F); if (rc) return rc; }
+    const VsdSurfelArgs sa = surfel_args(prm, c->nM, (size_t)n);
+    const VsdRenderer rd = {render_surfels, &sa};
+    return vsd_render_depth_with(c, F, rd, poses, n, depth);
+}
+
+int stocs::vsd_render_depth_with(stocs_ctx* c, DepthState* F, const VsdRenderer& rd, const float* poses, int n, float* depth) {
     DeviceGuard dev_guard(c->device);
     VsdState* S = vsd_state(c);
     const size_t npix = F->npix;
@@ -304,12 +318,11 @@ extern "C" int stocs_render_depth(stocs_ctx* c, const float* poses, int n, const
     uint32_t* d_z = Carve::at<uint32_t>(S->work.p, o_z);
     int32_t* d_box = Carve::at<int32_t>(S->work.p, o_box);
     const DepthArgs a = frame_args(F, 1.0f, 0.0f);
-    const VsdSurfelArgs sa = surfel_args(prm, c->nM, (size_t)n);
     for (int h0 = 0; h0 < n; h0 += (int)piece) {
         const int m = std::min((int)piece, n - h0);
         memcpy(hp + o_pose, poses + (size_t)h0 * 16, (size_t)m * 64);
         STOCS_HIP_CHECK(hipMemcpyAsync(d_pose, hp + o_pose, (size_t)m * 64, hipMemcpyHostToDevice, c->stream));
-        { const int rc = render_into(c, d_pose, m, a, sa, npix, d_z, d_box); if (rc) return rc; }
+        { const int rc = render_into(c, rd, d_pose, m, a, npix, d_z, d_box); if (rc) return rc; }
         STOCS_HIP_CHECK(hipMemcpyAsync(hp + o_z, d_z, (size_t)m * npix * 4, hipMemcpyDeviceToHost, c->stream));
         STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
         const uint32_t* bits = Carve::at<const uint32_t>(hp, o_z);
@@ -335,9 +348,16 @@ extern "C" int stocs_pose_errors_vsd(stocs_ctx* c, const float* est, int n, cons
     if (c->nM < 1) { set_error("%s: the context has no model", who); return STOCS_ERR_STATE; }
     DepthState* F = NULL;
     { const int rc = check_frame(who, c, &F); if (rc) return rc; }
+    const VsdSurfelArgs sa = surfel_args(prm, c->nM, n_gt == 1 ? (size_t)n + 1 : 2 * (size_t)n);
+    const VsdRenderer rd = {render_surfels, &sa};
+    return vsd_pose_errors_with(c, F, 7, rd, est, n, gt, n_gt, prm, out);
+}
+
+int stocs::vsd_pose_errors_with(stocs_ctx* c, DepthState* F, int timing_slot, const VsdRenderer& rd, const float* est, int n, const float* gt, int n_gt,
+                                const stocs_vsd_params* prm, stocs_vsd_record* out) {
     DeviceGuard dev_guard(c->device);
     VsdState* S = vsd_state(c);
-    CallTiming& tm = c->timing[7];   // from here on the call runs: a call refused above leaves the last call's record as it was
+    CallTiming& tm = c->timing[timing_slot];   // from here on the call runs: a call refused above leaves the last call's record as it was
     tm.begin();
     const bool dev_clock = c->device_clock != 0;   // opt-in: an event between two operations of a stream leaves the queue idle for a few microseconds
     const size_t npix = F->npix;
@@ -369,7 +389,6 @@ extern "C" int stocs_pose_errors_vsd(stocs_ctx* c, const float* est, int n, cons
     STOCS_HIP_CHECK(hipMemcpyAsync(d_pose, h_in, n_render * 64, hipMemcpyHostToDevice, c->stream));
     STOCS_HIP_CHECK(hipMemsetAsync(d_cnt, 0, (size_t)n * VSD_REC_WORDS * 4, c->stream));
     const DepthArgs a = frame_args(F, 1.0f, 0.0f);
-    const VsdSurfelArgs sa = surfel_args(prm, c->nM, n_render);
     VsdCompareArgs va;
     va.delta = prm->delta; va.n_tau = prm->n_tau;
     for (int t = 0; t < STOCS_VSD_MAX_TAU; ++t) va.tau[t] = t < prm->n_tau ? prm->tau[t] : 0.0f;
@@ -380,12 +399,12 @@ extern "C" int stocs_pose_errors_vsd(stocs_ctx* c, const float* est, int n, cons
         if (one_gt) {
             // the ground truth's buffer is slot 0 and its pose the first: the first chunk's launch renders it with its estimates
             const int lead = k0 == 0 ? 1 : 0;
-            { const int rc = render_into(c, d_pose + (size_t)(1 - lead + k0) * 16, m + lead, a, sa, npix, d_z + (1 - lead) * npix, d_box + (1 - lead) * VSD_BOX_WORDS); if (rc) return rc; }
+            { const int rc = render_into(c, rd, d_pose + (size_t)(1 - lead + k0) * 16, m + lead, a, npix, d_z + (1 - lead) * npix, d_box + (1 - lead) * VSD_BOX_WORDS); if (rc) return rc; }
             hipLaunchKernelGGL(vsd_compare_kernel, dim3(cmp_blocks, (unsigned)m), dim3(256), 0, c->stream, (const uint32_t*)(d_z + npix), npix, (const uint32_t*)d_z, (size_t)0,
                                rects ? (const int32_t*)(d_box + VSD_BOX_WORDS) : (const int32_t*)NULL, (int)VSD_BOX_WORDS, (const int32_t*)d_box, 0, frame_depth(F), a, va,
                                d_cnt + (size_t)k0 * VSD_REC_WORDS);
         } else {
-            { const int rc = render_into(c, d_pose + (size_t)k0 * 32, 2 * m, a, sa, npix, d_z, d_box); if (rc) return rc; }
+            { const int rc = render_into(c, rd, d_pose + (size_t)k0 * 32, 2 * m, a, npix, d_z, d_box); if (rc) return rc; }
             hipLaunchKernelGGL(vsd_compare_kernel, dim3(cmp_blocks, (unsigned)m), dim3(256), 0, c->stream, (const uint32_t*)(d_z + npix), 2 * npix, (const uint32_t*)d_z, 2 * npix,
                                rects ? (const int32_t*)(d_box + VSD_BOX_WORDS) : (const int32_t*)NULL, 2 * (int)VSD_BOX_WORDS, (const int32_t*)d_box, 2 * (int)VSD_BOX_WORDS,
                                frame_depth(F), a, va, d_cnt + (size_t)k0 * VSD_REC_WORDS);

@@ -487,6 +487,54 @@ class StocsEstimator:
         capi.check(self.L.stocs_pose_errors_vsd(self.h, pP, n, pG, n_gt, C.byref(prm), buf))
         return np.frombuffer(buf, dtype=_VSD_DTYPE, count=n).copy()
 
+    def set_mesh(self, vertices, triangles):
+        """The model as a triangle mesh, in the frame of the model points the estimator was made with (stocs_ctx_set_mesh): vertices
+        (nv, 3) float32, triangles (nt, 3) int32.  It stays on the device until the next call; no triangles drops it."""
+        V = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
+        T = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+        capi.check(self.L.stocs_ctx_set_mesh(self.h, V.ctypes.data_as(capi._fp), len(V), T.ctypes.data_as(capi._ip), len(T)))
+
+    def mesh_info(self):
+        """(vertices, triangles) of the mesh on the context, (0, 0) without one"""
+        nv, nt = C.c_int(0), C.c_int(0)
+        capi.check(self.L.stocs_ctx_mesh_info(self.h, C.byref(nv), C.byref(nt)))
+        return nv.value, nt.value
+
+    def render_depth_mesh(self, poses16):
+        """render_depth from the mesh of set_mesh (stocs_render_depth_mesh): exact, watertight, no radius -> (n, height, width) float32"""
+        P, pP = capi.f32(poses16)
+        n = P.size // 16
+        H, W = self._frame_shape("render_depth_mesh")
+        out = np.zeros((n, H, W), np.float32)
+        capi.check(self.L.stocs_render_depth_mesh(self.h, pP, n, out.ctypes.data_as(capi._fp)))
+        return out
+
+    def pose_errors_vsd_mesh(self, est, gt, taus=None, **params):
+        """pose_errors_vsd with the mesh of set_mesh rendered in place of the surfels (stocs_pose_errors_vsd_mesh): the same records, for
+        pose_recall_vsd as they are.  params: delta over the library's default."""
+        P, pP = capi.f32(est)
+        G, pG = capi.f32(gt)
+        if P.size % 16 or G.size % 16 or G.size == 0:
+            raise ValueError("pose_errors_vsd_mesh: poses are 16 floats each")
+        n, n_gt = P.size // 16, G.size // 16
+        if "surfel_radius" in params or "max_splat_px" in params:
+            raise TypeError("pose_errors_vsd_mesh: a mesh has no surfel parameters")
+        if taus is None:
+            d = np.float32(self.model_diameter())
+            taus = [np.float32(t) * d for t in BOP_VSD_TAUS]
+        prm = self._vsd_params("pose_errors_vsd_mesh", params, taus)
+        buf = (capi.VsdRecord * max(n, 1))()
+        capi.check(self.L.stocs_pose_errors_vsd_mesh(self.h, pP, n, pG, n_gt, C.byref(prm), buf))
+        return np.frombuffer(buf, dtype=_VSD_DTYPE, count=n).copy()
+
+    def last_mesh_call_timing(self):
+        """last_call_timing for the last pose_errors_vsd_mesh (stocs_mesh_last_call_timing)"""
+        labels = (C.c_char_p * 18)()
+        ms = (C.c_double * 18)()
+        n = C.c_int(0)
+        capi.check(self.L.stocs_mesh_last_call_timing(self.h, labels, ms, 18, C.byref(n)))
+        return [(labels[i].decode(), ms[i]) for i in range(n.value)]
+
     def pose_errors(self, est, gt):
         """n estimated camera-frame poses (column-major 16 floats each) against ground truth (stocs_pose_errors): gt holds one pose (every
         estimate against it) or n (estimate k against gt k) -> a structured array with the fields of stocs_pose_error, one record per

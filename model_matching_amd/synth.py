@@ -47,6 +47,13 @@ def _fibonacci_sphere(n: int) -> np.ndarray:
 
 def make_model(n: int = 5000, seed: int = SEED_MODEL, scale: float = 1.0) -> Cloud:
     """Oblate ellipsoid (0.08, 0.08, 0.03) m + spherical bump r=0.02 m at (0.05, 0, 0.02)."""
+    pos, nrm = _model_points(n, seed, scale)
+    pos = pos - pos.mean(axis=0)
+    return Cloud(np.ascontiguousarray(pos, np.float32), np.ascontiguousarray(nrm, np.float32))
+
+
+def _model_points(n, seed, scale):
+    """make_model's points in the solid's own frame, before they are centred on their mean"""
     rng = np.random.Generator(np.random.PCG64(seed))
     abc = np.array([0.08, 0.08, 0.03]) * scale
     bc = np.array([0.05, 0.0, 0.02]) * scale
@@ -77,8 +84,49 @@ def make_model(n: int = 5000, seed: int = SEED_MODEL, scale: float = 1.0) -> Clo
         raise ValueError("oversampling factor too small")
     pos, nrm = pos[perm], nrm[perm]
     pos = pos + rng.normal(0.0, 0.0003 * scale, pos.shape)  # jitter 0.3 mm
-    pos = pos - pos.mean(axis=0)
-    return Cloud(np.ascontiguousarray(pos, np.float32), np.ascontiguousarray(nrm, np.float32))
+    return pos, nrm
+
+
+def icosphere(level: int):
+    """the unit icosahedron subdivided `level` times, every vertex on the unit sphere -> (vertices (nv, 3) float64, triangles
+    (20 * 4^level, 3) int32, outward winding); closed: every edge is shared by exactly two triangles"""
+    g = (1.0 + 5.0 ** 0.5) / 2.0
+    v = [(-1, g, 0), (1, g, 0), (-1, -g, 0), (1, -g, 0), (0, -1, g), (0, 1, g), (0, -1, -g), (0, 1, -g), (g, 0, -1), (g, 0, 1), (-g, 0, -1), (-g, 0, 1)]
+    verts = [np.asarray(p, np.float64) / np.linalg.norm(p) for p in v]
+    tris = [(0, 11, 5), (0, 5, 1), (0, 1, 7), (0, 7, 10), (0, 10, 11), (1, 5, 9), (5, 11, 4), (11, 10, 2), (10, 7, 6), (7, 1, 8),
+            (3, 9, 4), (3, 4, 2), (3, 2, 6), (3, 6, 8), (3, 8, 9), (4, 9, 5), (2, 4, 11), (6, 2, 10), (8, 6, 7), (9, 8, 1)]
+    for _ in range(level):
+        mid = {}
+
+        def midpoint(i, j):
+            key = (i, j) if i < j else (j, i)
+            if key not in mid:
+                m = verts[i] + verts[j]
+                verts.append(m / np.linalg.norm(m))
+                mid[key] = len(verts) - 1
+            return mid[key]
+
+        nxt = []
+        for a, b, c in tris:
+            ab, bc, ca = midpoint(a, b), midpoint(b, c), midpoint(c, a)
+            nxt += [(a, ab, ca), (b, bc, ab), (c, ca, bc), (ab, bc, ca)]
+        tris = nxt
+    return np.asarray(verts, np.float64), np.asarray(tris, np.int32)
+
+
+def make_model_mesh(level: int = 4, n: int = 5000, seed: int = SEED_MODEL, scale: float = 1.0):
+    """make_model's solid as a triangle mesh on the frame of make_model(n, seed, scale): an icosphere of `level` scaled to the
+    ellipsoid plus one of level - 1 (at least 0) for the bump, each closed and whole (where one solid is inside the other its
+    triangles are hidden, not cut), minus the centroid make_model subtracts -> (vertices (nv, 3) float32, triangles (nt, 3) int32)"""
+    abc = np.array([0.08, 0.08, 0.03]) * scale
+    bc = np.array([0.05, 0.0, 0.02]) * scale
+    br = 0.02 * scale
+    ve, te = icosphere(level)
+    vb, tb = icosphere(max(level - 1, 0))
+    centroid = _model_points(n, seed, scale)[0].mean(axis=0)
+    verts = np.concatenate([ve * abc, vb * br + bc]) - centroid
+    tris = np.concatenate([te, tb + len(ve)])
+    return np.ascontiguousarray(verts, np.float32), np.ascontiguousarray(tris, np.int32)
 
 
 def make_model_asym(n: int = 5000, seed: int = SEED_MODEL + 101) -> Cloud:

@@ -24,7 +24,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-from model_matching_amd import synth  # noqa: E402
+from model_matching_amd import cloudio, synth  # noqa: E402
 from model_matching_amd.estimator import StocsEstimator, pose_recall, pose_recall_sym, pose_recall_vsd, symmetry_set  # noqa: E402
 
 
@@ -76,8 +76,12 @@ def main():
     ap.add_argument("--sym", default=None, help="a,b,c: the clustering's symmetry descriptor (0, 90, 180 or 360 per axis)")
     ap.add_argument("--sym-steps", type=int, default=72)
     ap.add_argument("--vsd", action="store_true", help="score by visible-surface discrepancy on the ground truth's own rendered depth image too")
+    ap.add_argument("--mesh", default=None, metavar="ply|level", help="with --vsd: the model as a triangle mesh (a PLY file on the model's frame, or a level "
+                    "of synth.make_model_mesh with synth:Cm), rasterised in place of the surfels")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "trial_recall.json"))
     a = ap.parse_args()
+    if a.mesh is not None and (not a.vsd or (a.mesh.isdigit() and a.example != "synth:Cm")):
+        ap.error("--mesh needs --vsd, and a level needs --example synth:Cm (make_model_mesh is Cm's solid)")
     name = a.example.split(":", 1)[1]
     model, scene, _ = synth.workload(name)
     est = StocsEstimator(scene.pos, scene.nrm, scene.prob, scene.pixel, model.pos, model.nrm, build_index=True)
@@ -106,10 +110,15 @@ def main():
         row["winners_sym"] = summary_sym(est.pose_errors_sym(W, gt16, S, synth.YCB_INTRINSICS), plain_w, diameter, a.trials, 640)
     if a.vsd:
         est.set_frame(np.zeros((480, 640), np.uint16), None, synth.YCB_INTRINSICS, 1e-4)     # the camera alone: the renderer reads no depth
-        z = est.render_depth(gt16)[0]
+        if a.mesh is not None:
+            mv, mt = synth.make_model_mesh(int(a.mesh)) if a.mesh.isdigit() else cloudio.read_ply_mesh(a.mesh)
+            est.set_mesh(mv, mt)
+        vsd_errors = est.pose_errors_vsd if a.mesh is None else est.pose_errors_vsd_mesh
+        z = (est.render_depth(gt16) if a.mesh is None else est.render_depth_mesh(gt16))[0]
         est.set_frame(np.rint(np.where(z > 0, z, 1.5) / 1e-4).astype(np.uint16), None, synth.YCB_INTRINSICS, 1e-4)
-        row["vsd"] = {"frame": "ground truth rendered, wall at 1.5 m", "delta_m": 0.015, "surfel_radius_m": 0.006, "object_pixels": int((z > 0).sum())}
-        row["winners_vsd"] = summary_vsd(est.pose_errors_vsd(W, gt16), a.trials)
+        row["vsd"] = {"frame": "ground truth rendered, wall at 1.5 m", "delta_m": 0.015, "object_pixels": int((z > 0).sum())}
+        row["vsd"].update({"surfel_radius_m": 0.006} if a.mesh is None else {"mesh": a.mesh, "triangles": int(len(mt))})
+        row["winners_vsd"] = summary_vsd(vsd_errors(W, gt16), a.trials)
         if S is not None:
             row["winners_average_recall"] = bop_ar(row["winners_vsd"], row["winners_sym"], a.trials)
     if a.post:
@@ -123,7 +132,7 @@ def main():
         if S is not None:
             row["refined_winners_sym"] = summary_sym(est.pose_errors_sym(R, gt16, S, synth.YCB_INTRINSICS), plain_r, diameter, a.trials, 640)
         if a.vsd:
-            row["refined_winners_vsd"] = summary_vsd(est.pose_errors_vsd(R, gt16), a.trials)
+            row["refined_winners_vsd"] = summary_vsd(vsd_errors(R, gt16), a.trials)
             if S is not None:
                 row["refined_winners_average_recall"] = bop_ar(row["refined_winners_vsd"], row["refined_winners_sym"], a.trials)
     est.close()
@@ -133,9 +142,9 @@ def main():
     if os.path.exists(a.out):
         with open(a.out) as f:
             data = json.load(f)
-    key = (a.example, a.post, json.dumps(row.get("sym")), json.dumps(row.get("robust")), a.trials, "vsd" in row)
+    key = (a.example, a.post, json.dumps(row.get("sym")), json.dumps(row.get("robust")), a.trials, "vsd" in row, row.get("vsd", {}).get("mesh"))
     data["rows"] = [r for r in data["rows"] if (r["example"], "refined_winners" in r, json.dumps(r.get("sym")), json.dumps(r.get("robust")),
-                                                r.get("winners", {}).get("trials", a.trials), "vsd" in r) != key] + [row]
+                                                r.get("winners", {}).get("trials", a.trials), "vsd" in r, r.get("vsd", {}).get("mesh")) != key] + [row]
     os.makedirs(os.path.dirname(a.out), exist_ok=True)
     with open(a.out, "w") as f:
         json.dump(data, f, indent=1)
