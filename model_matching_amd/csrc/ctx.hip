@@ -12,6 +12,7 @@
 #include <limits>
 #include <numeric>
 
+#include "normal_cone.h"
 #include "stocs_ctx.h"
 
 namespace stocs {
@@ -642,10 +643,27 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
             raw[i] = make_float4(c->h_mpos_raw[i].x, c->h_mpos_raw[i].y, c->h_mpos_raw[i].z, 0.f);
         }
         for (int i = 0; i < nM; ++i) { as[i] = a[c->h_mperm[i]]; bs[i] = b[c->h_mperm[i]]; }
+        // the fourth word of a sorted position: the packed model normal of the queue kernel's gate (normal_cone.h).  The gate's margin
+        // is built on STOCS_MODEL_NORMAL_Q >= |unpack(pack(n)) / 511 - n|_2: measured here, in double, over the points without the flag
+        double q_max = 0.0;
+        for (int i = 0; i < nM; ++i) {
+            const uint32_t w = model_normal_pack(bs[i].x, bs[i].y, bs[i].z);
+            union { uint32_t u; float f; } cv; cv.u = w; as[i].w = cv.f;
+            if (w & STOCS_MODEL_NORMAL_NO_GATE) continue;
+            float kx, ky, kz;
+            model_normal_unpack(w, kx, ky, kz);
+            const double dx = (double)kx / (double)STOCS_MODEL_NORMAL_SCALE - (double)bs[i].x, dy = (double)ky / (double)STOCS_MODEL_NORMAL_SCALE - (double)bs[i].y,
+                         dz = (double)kz / (double)STOCS_MODEL_NORMAL_SCALE - (double)bs[i].z;
+            q_max = std::max(q_max, sqrt(dx * dx + dy * dy + dz * dz));
+        }
+        if (!(q_max <= (double)STOCS_MODEL_NORMAL_Q)) {
+            set_error("stocs_ctx_create: a packed model normal is %.3g from its normal (at most %.3g)", q_max, (double)STOCS_MODEL_NORMAL_Q);
+            rc = STOCS_ERR_STATE;
+        }
         // the sorted positions are padded to whole 64-point steps with NaN: the scan kernels load and transform a step without
-        // bounds checks, and a NaN query matches nothing (every comparison of its distances fails)
+        // bounds checks, and a NaN query matches nothing (every comparison of its distances fails); the padding's fourth word stays 0
         as.resize((size_t)n_patch * 64 + 64, make_float4(NAN, NAN, NAN, 0.f));
-        bs.resize((size_t)n_patch * 64 + 64, make_float4(0.f, 0.f, 0.f, 0.f));   // the gated queue forms load a step's normals next to its positions
+        bs.resize((size_t)n_patch * 64 + 64, make_float4(0.f, 0.f, 0.f, 0.f));   // (padded like the positions)
         if (!rc) rc = upload(&c->d_mpos, a.data(), a.size());
         if (!rc) rc = upload(&c->d_mnrm, b.data(), b.size());
         if (!rc) rc = upload(&c->d_munit, u.data(), u.size());

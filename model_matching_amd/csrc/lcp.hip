@@ -45,7 +45,8 @@
 namespace stocs {
 
 struct LcpArgs {
-    const float4* mpos;   // centred model positions in patch order (ctx.hip), NaN-padded to whole 64-point steps + one
+    const float4* mpos;   // centred model positions in patch order (ctx.hip), NaN-padded to whole 64-point steps + one; w: the bits of the
+                          // packed model normal (normal_cone.h), read by the gated queue forms and the gate count only
     const float4* mnrm;
     const int32_t* mperm; // sorted slot -> original model index (detail output only)
     int M;
@@ -396,18 +397,12 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT)) void lcp_c
 // ---------------------------------------------------------------------------------------------
 // Patch test.  The 64 model points of a step lie in a sphere (centre c, radius r; ctx.hip).  Under the candidate transform
 // x -> A x + t every one of them lands within s * r of A c + t, s >= the largest singular value of A (1 for a rigid
-// transform; bounded here by the square root of the largest absolute row sum of A^T A, so that a caller's non-rigid matrix
+// transform; bounded by linear_norm_bound, stocs_math.h: the square root of the largest absolute row sum of A^T A, so that a caller's non-rigid matrix
 // is handled too).  The scene's distance field gives a lower bound of the distance from A c + t to the nearest scene point;
 // when that exceeds s * r + epsilon no point of the step has a scene point within epsilon, the step adds nothing to the
 // score (stocs.cpp:1019-1024) and is skipped: one look-up per step instead of 64.  Margins cover the float rounding of the
 // transform, of the field and of the cell centre; positions that are not finite are never ruled out here.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ float lcp_linear_norm_bound(float t0, float t1, float t2, float t4, float t5, float t6, float t8, float t9, float t10) {
-    const float g00 = t0 * t0 + (t1 * t1 + t2 * t2), g11 = t4 * t4 + (t5 * t5 + t6 * t6), g22 = t8 * t8 + (t9 * t9 + t10 * t10);
-    const float g01 = fabsf(t0 * t4 + (t1 * t5 + t2 * t6)), g02 = fabsf(t0 * t8 + (t1 * t9 + t2 * t10)), g12 = fabsf(t4 * t8 + (t5 * t9 + t6 * t10));
-    const float rho = fmaxf(g00 + (g01 + g02), fmaxf(g11 + (g01 + g12), g22 + (g02 + g12)));
-    return sqrtf(rho) * 1.00001f;   // NaN / inf entries give NaN / inf: nothing is ruled out then (every comparison below fails)
-}
 __device__ __forceinline__ bool lcp_patch_dead(const LcpArgs& a, const float4 sp, float sn, float t0, float t1, float t2, float t4, float t5, float t6,
                                                float t8, float t9, float t10, float t12, float t13, float t14) {
     const float cx = ((t0 * sp.x + t4 * sp.y) + t8 * sp.z) + t12;
@@ -460,14 +455,14 @@ __device__ __forceinline__ bool lcp_patch_dead(const LcpArgs& a, const float4 sp
 //           scene normals cannot pass the normal test against the rotated model normal never joins the queue (normal_cone.h).  The
 //           detail forms keep every query: hit_out names the neighbour also when it is not counted.  Not for the split ring forms of
 //           CU = 16 (models beyond 8 192 points): they have 62-63 VGPRs without the gate and spill 12 to 20 bytes with it, wherever
-//           the model normal is requested.
+//           the model normal is requested -- three of the four still spill with the packed normal of the position's fourth word.
 //
-// The legal forms (46 instantiations; SHARED = 0 and GATE = 0 unless stated; the static_assert rejects every other):
+// The legal forms (45 instantiations; SHARED = 0 and GATE = 0 unless stated; the static_assert rejects every other):
 //   scoring, sparse   DENSE = 0, SPLIT in {0, 1}, FLAT in {0, 1}, NEAR in {0, 1}, CU in {16, 64}         16 forms
 //   scoring, dense    DENSE = 1, SPLIT = 1, FLAT = 0, NEAR = 0, CU in {16, 64}                            2 forms
 //   shared list       every scoring form with SPLIT = 1 and CU = 16 once more with SHARED = 1            5 forms
 //                     (the dense queue form is always split, whatever lcp_split and the model size say)
-//   gated             every sparse scoring form but the split ring forms of CU = 16, once more with GATE = 1   17 forms
+//   gated             every sparse scoring form but the split ring forms of CU = 16, once more with GATE = 1   16 forms
 //   detail, sparse    DENSE = 0, SPLIT = 0, FLAT = 0, NEAR in {0, 1}, CU in {16, 64}                      4 forms
 //   detail, dense     DENSE = 1, SPLIT = 0, FLAT = 0, NEAR = 0, CU in {16, 64}                            2 forms
 // ---------------------------------------------------------------------------------------------
@@ -518,6 +513,10 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
                 t12 = T[12], t13 = T[13], t14 = T[14];
     unsigned long long acc = 0ull;
     int head = 0, tail = 0;
+    // GATE: the norm bound of the linear part (the patch test's too) and, from it, the ONE wave-uniform threshold of the gate on the
+    // packed model normals (normal_cone.h: 511 (dot_lo - s K), rounded downwards; NaN or -inf for a matrix that is not finite)
+    const float gnorm = GATE ? linear_norm_bound(t0, t1, t2, t4, t5, t6, t8, t9, t10) : 0.0f;
+    const float gthr = GATE ? model_normal_gate_threshold(a.dot_lo, gnorm) : 0.0f;
 
     auto process = [&](int nq) {
         // order the pending queries by list length (number of 128-byte lines) so that the groups of a trip stream lists of
@@ -675,9 +674,6 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
     auto step = [&](const int i, const float4 p) {
         float qx = 0.f, qy = 0.f, qz = 0.f, qcentre = 0.f, nearest = 0.f;
         uint32_t off = 0, cnt = 0, yw = 0;
-        // GATE: the model normal of the slot, requested in front of the look-up chain (the normals are padded like the positions)
-        float4 gnm = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (GATE) gnm = a.mnrm[i];
         constexpr uint32_t cmask = STOCS_CONE_COUNT_MASK;   // the list length in the count word; the cell's normal cone sits above it
         // slots beyond the model hold NaN positions (ctx.hip): they run through the look-up like any other query and match nothing;
         // only the per-point outputs of the detail form need the bound
@@ -718,13 +714,9 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
                 if (a.has_nearest && nearest - qcentre > a.eps + a.bound_margin) cnt = 0;
             }
             // GATE: a query whose cell's normal cone cannot reach dot_lo against the rotated model normal would find its neighbour and
-            // then fail the normal test (cone_rules_out, normal_cone.h): it never joins the queue.  The rotation is the normal test's own
-            if (GATE && cnt) {
-                const float nx = t0 * gnm.x + (t4 * gnm.y + t8 * gnm.z);
-                const float ny = t1 * gnm.x + (t5 * gnm.y + t9 * gnm.z);
-                const float nz = t2 * gnm.x + (t6 * gnm.y + t10 * gnm.z);
-                if (cone_rules_out(yw, nx, ny, nz, a.dot_lo)) cnt = 0;
-            }
+            // then fail the normal test (cone_rules_out_packed, normal_cone.h): it never joins the queue.  The model normal is the packed
+            // one in the fourth word of the position (ctx.hip): it arrived with p, one step ahead; the exact one is read by the normal test
+            if (GATE && cnt && cone_rules_out_packed(yw, __float_as_uint(p.w), t0, t1, t2, t4, t5, t6, t8, t9, t10, gthr)) cnt = 0;
             if (DETAIL && cnt == 0) {
                 const int orig = a.mperm[i];
                 hit_out[(size_t)cand * a.M + orig] = -1;
@@ -774,7 +766,7 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
     static_assert(!SHARED || WPB * 128 == LCP_SHARED_LIVE, "the shared list is the memory of the per-wave rings");
     if (threadIdx.x == 0) live_n = 0;
     const int nsubs = (a.M + 15) >> 4;   // <= LCP_SHARED_LIVE: at most two windows per wavefront
-    const float snorm = a.patch ? lcp_linear_norm_bound(t0, t1, t2, t4, t5, t6, t8, t9, t10) : 0.0f;
+    const float snorm = GATE ? gnorm : (a.patch ? linear_norm_bound(t0, t1, t2, t4, t5, t6, t8, t9, t10) : 0.0f);
     unsigned long long lm[2];
 #pragma unroll
     for (int j = 0; j < 2; ++j) {   // windows w and w + 4
@@ -818,7 +810,7 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
     const int wfirst = SPLIT ? w : 0, nw = SPLIT ? WPB : 1;
     // this wavefront's sub-patches: k -> step wfirst + (k >> 2) * nw, quarter k & 3 (wave-uniform: the walk's loops branch on scalars)
     const int nsub = __builtin_amdgcn_readfirstlane(4 * ((nsteps - wfirst + nw - 1) / nw));
-    const float snorm = a.patch ? lcp_linear_norm_bound(t0, t1, t2, t4, t5, t6, t8, t9, t10) : 0.0f;
+    const float snorm = GATE ? gnorm : (a.patch ? linear_norm_bound(t0, t1, t2, t4, t5, t6, t8, t9, t10) : 0.0f);
     int qh = 0, qtl = 0;   // ring head and tail
     for (int s0 = 0;; s0 += 64) {
         {   // the window s0 .. s0 + 63 (wave-uniform)
@@ -876,7 +868,7 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
     const int nsteps = (a.M + 63) >> 6;
     const int wfirst = SPLIT ? w : 0, nw = SPLIT ? WPB : 1;
     const int nk = (nsteps - wfirst + nw - 1) / nw;
-    const float snorm = a.patch ? lcp_linear_norm_bound(t0, t1, t2, t4, t5, t6, t8, t9, t10) : 0.0f;
+    const float snorm = GATE ? gnorm : (a.patch ? linear_norm_bound(t0, t1, t2, t4, t5, t6, t8, t9, t10) : 0.0f);
     for (int k0 = 0; k0 < nk; k0 += 64) {
         const int kk = k0 + lane;
         bool live = kk < nk;
@@ -1364,7 +1356,8 @@ int stocs_lcp_hit_count(stocs_ctx* c, const void* d_T16, int n, int64_t* hits, i
 }
 
 // stocs_lcp_gate_count: one lane per (candidate, model slot).  The query, its cell and the sub-cell mask as the queue kernel's step
-// computes them (brick look-up; no mask on has_nearest grids), then the kernel's own gate function on the kernel's own rotated normal
+// computes them (brick look-up; no mask on has_nearest grids), then the kernel's own gate function on the packed model normal that
+// the kernel reads (the fourth word of the position) with the kernel's own threshold
 __global__ __launch_bounds__(256) void gate_count_kernel(LcpArgs a, const float* __restrict__ T16, size_t total, const uint8_t* __restrict__ counted,
                                                          unsigned long long* __restrict__ out3, int has_cones) {
     const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1392,11 +1385,8 @@ __global__ __launch_bounds__(256) void gate_count_kernel(LcpArgs a, const float*
         }
         if (cnt) {
             nq = 1;
-            const float4 nm = a.mnrm[i];
-            const float nx = t0 * nm.x + (t4 * nm.y + t8 * nm.z);
-            const float ny = t1 * nm.x + (t5 * nm.y + t9 * nm.z);
-            const float nz = t2 * nm.x + (t6 * nm.y + t10 * nm.z);
-            if (has_cones && cone_rules_out(yw, nx, ny, nz, a.dot_lo)) {
+            const float gthr = model_normal_gate_threshold(a.dot_lo, linear_norm_bound(t0, t1, t2, t4, t5, t6, t8, t9, t10));
+            if (has_cones && cone_rules_out_packed(yw, __float_as_uint(p.w), t0, t1, t2, t4, t5, t6, t8, t9, t10, gthr)) {
                 nr = 1;
                 nb = counted[cand * (size_t)a.M + (size_t)a.mperm[i]] ? 1 : 0;
             }

@@ -274,7 +274,7 @@ struct stocs_ctx {
     float4* d_mnrm;
     float4* d_munit;   // unit-cube model (pairCreationFunctor.h:96-132)
     float4* d_mpos_raw;  // un-shifted model positions (index build)
-    float4* d_mpos_s;  // copies in patch order for the LCP kernel (positions NaN-padded to whole 64-point steps + one)
+    float4* d_mpos_s;  // copies in patch order for the LCP kernel (positions NaN-padded to whole 64-point steps + one; w = the packed model normal, normal_cone.h)
     float4* d_mnrm_s;
     int32_t* d_mperm;
     float4* d_mpatch;  // per 64-point step of the sorted model: bounding sphere (centre xyz, radius) of its points (patch test, lcp.hip)

@@ -68,6 +68,15 @@ STOCS_HD V3 xform_normal(const float* T, V3 n) {
                T[2] * n.x + (T[6] * n.y + T[10] * n.z));
 }
 
+// s >= the largest singular value of the linear part of a column-major transform (entries t0..t10 as in T[c*4+r]): the square root
+// of the largest absolute row sum of A^T A.  NaN / inf entries give NaN / inf: nothing is ruled out then (every comparison fails)
+STOCS_HD float linear_norm_bound(float t0, float t1, float t2, float t4, float t5, float t6, float t8, float t9, float t10) {
+    const float g00 = t0 * t0 + (t1 * t1 + t2 * t2), g11 = t4 * t4 + (t5 * t5 + t6 * t6), g22 = t8 * t8 + (t9 * t9 + t10 * t10);
+    const float g01 = fabsf(t0 * t4 + (t1 * t5 + t2 * t6)), g02 = fabsf(t0 * t8 + (t1 * t9 + t2 * t10)), g12 = fabsf(t4 * t8 + (t5 * t9 + t6 * t10));
+    const float rho = fmaxf(g00 + (g01 + g02), fmaxf(g11 + (g01 + g12), g22 + (g02 + g12)));
+    return stocs_sqrtf(rho) * 1.00001f;
+}
+
 // Centred frames <-> camera frame (stocs.cpp:925-937 without the triangle centroids, which rigid_transform_one folds in itself):
 // a pose T scored between the centred clouds is the camera pose P with the same rotation and tc = (t + cscene) - R cmodel, R cmodel
 // in the 3-term order.  The inverse is t = (tc - cscene) + R cmodel.  Row 3 comes out as (0, 0, 0, 1) either way.

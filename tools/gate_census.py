@@ -10,7 +10,12 @@ outwards) and tested with the kernel's bound and margins in float64.  Per pose: 
 also passes the 30-degree normal test), queries that survive the mask, those that also survive the cone, and counted points the
 cone would have lost (must be 0).
 
-usage: python tools/gate_census.py [--axis-bits 6] [--sin-steps 16] [--poses 192]   (prints a markdown table)
+--normal-bits B restates the gate on the PACKED model normal (three signed B-bit components, k = round((2^(B-1) - 1) n), normal_cone.h:
+the library packs 10 bits): the gate sees k / (2^(B-1) - 1) and its threshold drops by s (Q (1 + 1e-4) + 1e-6), Q the quantisation bound
+(10 bits: the library's STOCS_MODEL_NORMAL_Q = 1.7e-3; any other width: the plain sqrt(3) / (2 (2^(B-1) - 1))), s the norm bound of the pose's linear part; the normal test and the
+"counted" column keep the exact normal.  0 (the default): the gate on the exact normal.
+
+usage: python tools/gate_census.py [--axis-bits 6] [--sin-steps 16] [--poses 192] [--normal-bits 10]   (prints a markdown table)
 """
 import argparse
 import os
@@ -95,23 +100,39 @@ def build_grid(spos, snrm, eps, axis_bits, sin_steps):
     return dict(o=o, h=h, n=n, ukey=ukey, mask=mask, axis=axis, cls=cls, half_angle=np.where(cmin > 0, half_angle, 180.0), sin_steps=sin_steps)
 
 
-def rules_out(axis, cls, sin_steps, v):
+def rules_out(axis, cls, sin_steps, v, dot_lo=float(DOT_LO)):
     S = (axis * axis).sum(1); W = (v * axis).sum(1); vv = (v * v).sum(1)
     va = W / np.sqrt(S)
     vp = np.sqrt(np.maximum(vv - va * va, 0.0))
     sd = cls / float(sin_steps); cd = np.sqrt(1.0 - sd * sd)
     bound = va * cd + vp * sd
     l1 = np.abs(v).sum(1)
-    return (cls != 0) & (vp * cd > va * sd) & (bound * 1.0001 + 2e-3 * l1 < float(DOT_LO))
+    return (cls != 0) & (vp * cd > va * sd) & (bound * 1.0001 + 2e-3 * l1 < dot_lo)
 
 
-def census(scene_pos, scene_nrm, model_pos, model_nrm, T, eps, axis_bits, sin_steps):
+def quantise(nrm, bits):
+    """-> the normals as the gate sees them, the bound Q of the header for this width"""
+    scale = float((1 << (bits - 1)) - 1)
+    k = np.clip(np.rint(nrm.astype(np.float64) * scale), -scale, scale)
+    # 10 bits: the library's constant STOCS_MODEL_NORMAL_Q; any other width: the format's plain bound, half a step per component
+    return k / scale, 1.7e-3 if bits == 10 else np.sqrt(3.0) / (2.0 * scale) * (1.0 + 1e-12)
+
+
+def norm_bound(A3):
+    """linear_norm_bound of stocs_math.h: the square root of the largest absolute row sum of A^T A"""
+    return float(np.sqrt(np.abs(A3.T @ A3).sum(1).max()) * 1.00001)
+
+
+def census(scene_pos, scene_nrm, model_pos, model_nrm, T, eps, axis_bits, sin_steps, normal_bits=0):
     cs = scene_pos.mean(0, dtype=np.float32); cm = model_pos.mean(0, dtype=np.float32)
     spos = scene_pos - cs; mpos = model_pos - cm
     snrm = scene_nrm / np.linalg.norm(scene_nrm, axis=1, keepdims=True)
     g = build_grid(spos, snrm, eps, axis_bits, sin_steps)
     tree = cKDTree(spos.astype(np.float64))
     tot = np.zeros(5)
+    gate_nrm, q_bound = quantise(model_nrm, normal_bits) if normal_bits else (model_nrm.astype(np.float64), 0.0)
+    if normal_bits:
+        assert np.linalg.norm(gate_nrm - model_nrm.astype(np.float64), axis=1).max() <= q_bound
     for T16 in T:
         A = T16.reshape(4, 4).T.astype(np.float64)
         qp = mpos.astype(np.float64) @ A[:3, :3].T + A[:3, 3]
@@ -129,7 +150,8 @@ def census(scene_pos, scene_nrm, model_pos, model_nrm, T, eps, axis_bits, sin_st
         found = inside & (g["ukey"][row] == key)
         sb = ((c4[:, 2] & 3) << 4) | ((c4[:, 1] & 3) << 2) | (c4[:, 0] & 3)
         surv = found & (((g["mask"][row] >> sb.astype(np.uint64)) & np.uint64(1)) != 0)
-        ruled = surv & rules_out(g["axis"][row], g["cls"][row], g["sin_steps"], v)
+        thr = float(DOT_LO) - (norm_bound(A[:3, :3]) * (q_bound * 1.0001 + 1e-6) if normal_bits else 0.0)
+        ruled = surv & rules_out(g["axis"][row], g["cls"][row], g["sin_steps"], gate_nrm @ A[:3, :3].T, thr)
         tot += [hit.sum(), counted.sum(), surv.sum(), (surv & ~ruled).sum(), (counted & ruled).sum()]
         assert not (hit & ~surv).any(), "a query with a neighbour within epsilon did not survive the mask"
     return tot / len(T), g
@@ -141,8 +163,10 @@ def main():
     ap.add_argument("--sin-steps", type=int, default=16)
     ap.add_argument("--poses", type=int, default=192)
     ap.add_argument("--workloads", default="Cm,small,Cm_asym")
+    ap.add_argument("--normal-bits", type=int, default=0, help="bits per component of the packed model normal the gate reads (0: the exact normal)")
     args = ap.parse_args()
-    print("axis %d + %d bits octahedral, sin(half-angle) in %d steps; averages per pose\n" % (args.axis_bits, args.axis_bits, args.sin_steps))
+    print("axis %d + %d bits octahedral, sin(half-angle) in %d steps%s; averages per pose\n" % (
+        args.axis_bits, args.axis_bits, args.sin_steps, ", the gate on model normals of %d bits per component" % args.normal_bits if args.normal_bits else ""))
     print("| workload | poses | hits | counted | survive the mask | survive mask and cone | counted points lost | median half-angle |")
     print("|---|---|---|---|---|---|---|---|")
     for name in args.workloads.split(","):
@@ -151,7 +175,7 @@ def main():
         npose = args.poses if name != "Cm_asym" else args.poses // 2
         T = synth.make_candidates(synth.centred_gt(s.T_gt, cs, cm), k, seed=synth.SEED_CAND)[:npose]   # the head of bench.py's own batch
         eps = float(getattr(s, "eps", 0.005))
-        t, g = census(s.pos, s.nrm, m.pos, m.nrm, T, eps, args.axis_bits, args.sin_steps)
+        t, g = census(s.pos, s.nrm, m.pos, m.nrm, T, eps, args.axis_bits, args.sin_steps, args.normal_bits)
         print("| %s | %d | %.0f | %.0f | %.0f | %.0f (%+.0f %%) | %g | %.1f deg |" % (name, npose, t[0], t[1], t[2], t[3], 100.0 * (t[3] / t[2] - 1.0), t[4] * npose,
                                                                                  float(np.median(g["half_angle"]))))
 
