@@ -180,9 +180,19 @@ def test_config5_200k_scene_50k_model(oracle_lib):
     perm = np.random.default_rng(1).permutation(k)
     assert np.array_equal(est.score_transforms(T[perm]), got[perm])
     assert np.array_equal(est.score_transforms(T[5000:5100]), got[5000:5100])
-    # the device arg-max picks the first maximum of those scores
+    # a ragged batch on the automatic ordered path: XCD runs of 128 slots, 15 whole rounds of 8 x 128 workgroups and a tail of 1 021
+    ragged = 16381
+    assert np.array_equal(est.score_transforms(T[:ragged]).view(np.uint32), got[:ragged].view(np.uint32))
     dT, dL = est.dev_alloc(T.nbytes), est.dev_alloc(k * 4)
     est.dev_upload(dT, T)
+    # the same into a buffer that holds -1 everywhere (scores are >= 0): a slot the placement skipped would keep it, while the scratch
+    # block of score_transforms still holds the right score from the call before
+    est.dev_upload(dL, np.full(ragged, -1.0, np.float32))
+    est.score_device(dT, ragged, dL)
+    again = np.zeros(ragged, np.float32)
+    est.dev_download(dL, again)
+    assert not (again == -1.0).any() and np.array_equal(again.view(np.uint32), got[:ragged].view(np.uint32))
+    # the device arg-max picks the first maximum of those scores
     est.score_device(dT, k, dL)
     sc, gid, key = est.best_device(dL, k)
     assert gid == int(np.argmax(got)) and sc == float(got.max())

@@ -196,6 +196,40 @@ def test_parity_by_composition(name, exact):
     assert (plain["n_correspondences"] == 0).all() and (plain["iterations"] == 0).all()
 
 
+@pytest.mark.parametrize("samples", [1, 2, 255, 256, 257, 513])
+def test_per_prior_argmax_at_sample_count_edges(samples):
+    """track_best_kernel (one 256-thread workgroup per prior, a key for every slot) at one sample, on either side of its stride and
+    with a third pass: slot 0 wins every tie, also when all scores are 0 (a prior parked far from the scene: a tie over every
+    wavefront).  check_params bounds samples only through the 2^20 candidates of a round, so 513 runs as it is."""
+    est, P0 = _workload("tiny")
+    cs, cm = est.get_scene_centroid(), est.get_model_centroid()
+    far = P0.copy()
+    far[12:15] += np.array([30.0, -40.0, 50.0], np.float32)
+    priors = np.concatenate([_perturbed(P0, 3, seed=9, max_t=0.01, max_deg=6.0), far[None]])
+    prm = dict(PARITY, rounds=2, samples=samples, seed=777, refine_iterations=0)
+    res = est.track_poses(priors, keep_details=True, **prm)
+    assert len(res) == 4
+    for p in range(4):
+        first = inc = centred_prior(priors[p], cs, cm)
+        for r in range(prm["rounds"]):
+            T, l = est.track_round(p, r)
+            assert T.shape == (samples, 16) and l.shape == (samples,)
+            want = restate_round(inc, p, r, prm["rounds"], samples, prm["seed"], prm["max_translation"], prm["max_rotation_deg"], prm["shrink"])
+            assert np.array_equal(_bits(T), _bits(want)), (samples, p, r)      # slot 0 is the incumbent the round before chose
+            if r == 0:
+                assert _bits(res["prior_lcp"][p:p + 1])[0] == _bits(l[:1])[0]
+            j = _first_max(l)
+            if p == 3:
+                assert not l.any() and j == 0, (samples, r)
+            inc = T[j]
+        assert _bits(res["lcp"][p:p + 1])[0] == _bits(l[j:j + 1])[0], (samples, p)
+        assert np.array_equal(_bits(res["pose16"][p]), _bits(camera_form(inc, cs, cm))), (samples, p)
+        if p == 3 or samples == 1:
+            assert np.array_equal(_bits(inc), _bits(first)), (samples, p)
+            assert _bits(res["lcp"][p:p + 1])[0] == _bits(res["prior_lcp"][p:p + 1])[0]
+    assert res["lcp"][3] == 0.0 and (res["lcp"][:3] > 0.0).all()
+
+
 def _sequence_scenes(n_frames=12, seed=0):
     from model_matching_amd import synth
     m = synth.make_model_asym(2000)

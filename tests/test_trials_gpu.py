@@ -49,6 +49,13 @@ def _assert_trials_equal_singles(est, seeds, n_attempts, mode, max_per_base, min
         assert np.array_equal(ref["lcp"].view(np.uint32), g["lcp"].view(np.uint32)), t     # integer accumulation: a score does not depend on its batch
         assert g["best_index"] == ref["best_index"] and g["best_lcp"] == ref["best_lcp"], t
         assert np.array_equal(ref["best_pose"].view(np.uint32), g["best_pose"].view(np.uint32)), t
+        # the rule itself (compute_best_transform), on the trial's own scores: the first maximum of the positive ones, else no pose
+        if len(g["lcp"]) and g["lcp"].max() > 0:
+            first = int(np.flatnonzero(g["lcp"] == g["lcp"].max())[0])
+            assert g["best_index"] == first and g["best_lcp"] == float(g["lcp"][first]), t
+            assert np.array_equal(g["best_pose"].view(np.uint32), g["P"][first].view(np.uint32)), t
+        else:
+            assert g["best_index"] == -1 and g["best_lcp"] == 0.0 and not g["best_pose"].any(), t
         total += g["n_candidates"]
     assert total >= min_candidates
     return res
