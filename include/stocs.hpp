@@ -1363,17 +1363,10 @@ inline std::vector<SceneCloud> load_frame_scenes(std::string depth_location, con
                              read_depth_scale, voxel_size, device);
 }
 
-// reference stocs.hpp:182-191 / stocs.cpp:28-84: raw model PLY -> normals (radius), flipped, voxel grid, scale -> model_search
-// PLY + the PPF index of the sampled cloud, both on the GPU.  The index is built from the cloud as the estimator will read
-// it back (the written file), so the two always agree bit for bit.
-inline void pre_process_model(std::string src_model_location, float normal_radius, float read_depth_scale, float write_depth_scale, float voxel_size,
-                              float ppf_tr_discretization, float ppf_rot_discretization, std::string dst_model_location, std::string dst_ppf_map_location) {
-    ModelCloud raw, sampled;
-    read_ply(src_model_location, &raw, false);
-    sampled.pos.resize(raw.pos.size()); sampled.nrm.resize(raw.pos.size());
-    int n = 0;
-    if (stocs_preprocess_model(raw.pos.data(), raw.size(), normal_radius, voxel_size, read_depth_scale, -1, sampled.pos.data(), sampled.nrm.data(), raw.size(), &n) != STOCS_OK)
-        throw std::runtime_error(std::string("stocs_preprocess_model: ") + stocs_last_error());
+// The file and index half of model preprocessing: the sampled cloud (n points) -> the model_search PLY + the PPF index of the cloud as
+// the estimator will read it back (the written file), so the two always agree bit for bit.
+inline void write_model_and_index(const ModelCloud& sampled, int n, float write_depth_scale, float ppf_tr_discretization, float ppf_rot_discretization,
+                                  const std::string& dst_model_location, const std::string& dst_ppf_map_location) {
     std::cout << "After sampling |M|= " << n << std::endl;
     if (stocs_ply_write(dst_model_location.c_str(), sampled.pos.data(), sampled.nrm.data(), n, write_depth_scale) != STOCS_OK)
         throw std::runtime_error(std::string("stocs_ply_write: ") + stocs_last_error());
@@ -1400,6 +1393,43 @@ inline void pre_process_model(std::string src_model_location, float normal_radiu
     const std::string msg = rc == STOCS_OK ? std::string() : std::string("stocs_index_save: ") + stocs_last_error();
     stocs_ctx_destroy(ctx);
     if (rc != STOCS_OK) throw std::runtime_error(msg);
+}
+
+// reference stocs.hpp:182-191 / stocs.cpp:28-84: raw model PLY -> normals (radius), flipped, voxel grid, scale -> model_search
+// PLY + the PPF index of the sampled cloud, both on the GPU.
+inline void pre_process_model(std::string src_model_location, float normal_radius, float read_depth_scale, float write_depth_scale, float voxel_size,
+                              float ppf_tr_discretization, float ppf_rot_discretization, std::string dst_model_location, std::string dst_ppf_map_location) {
+    ModelCloud raw, sampled;
+    read_ply(src_model_location, &raw, false);
+    sampled.pos.resize(raw.pos.size()); sampled.nrm.resize(raw.pos.size());
+    int n = 0;
+    if (stocs_preprocess_model(raw.pos.data(), raw.size(), normal_radius, voxel_size, read_depth_scale, -1, sampled.pos.data(), sampled.nrm.data(), raw.size(), &n) != STOCS_OK)
+        throw std::runtime_error(std::string("stocs_preprocess_model: ") + stocs_last_error());
+    write_model_and_index(sampled, n, write_depth_scale, ppf_tr_discretization, ppf_rot_discretization, dst_model_location, dst_ppf_map_location);
+}
+
+// Not in the reference: pre_process_model with the cloud stage exchanged: a triangle mesh (PLY with faces) is sampled on the GPU at one point
+// per spacing^2 of area (0: voxel_size / 4), every normal its facet's (orient 0: the winding's, 1: turned away from the origin), then voxel
+// grid and scale as above (stocs_preprocess_model_mesh).  A file without a readable mesh, or without faces, is refused.
+inline void pre_process_model_mesh(std::string mesh_location, float spacing, uint64_t seed, int orient, float read_depth_scale, float write_depth_scale, float voxel_size,
+                                   float ppf_tr_discretization, float ppf_rot_discretization, std::string dst_model_location, std::string dst_ppf_map_location) {
+    int nv = 0, nt = 0;
+    if (stocs_ply_read_mesh(mesh_location.c_str(), NULL, 0, &nv, NULL, 0, &nt) != STOCS_OK)
+        throw std::runtime_error("cannot read a mesh from " + mesh_location + ": " + stocs_last_error());
+    if (nt < 1) throw std::runtime_error(mesh_location + " has no faces");
+    std::vector<float> mesh_v((size_t)nv * 3);
+    std::vector<int32_t> mesh_t((size_t)nt * 3);
+    if (stocs_ply_read_mesh(mesh_location.c_str(), mesh_v.data(), nv, &nv, mesh_t.data(), nt, &nt) != STOCS_OK)
+        throw std::runtime_error("cannot read a mesh from " + mesh_location + ": " + stocs_last_error());
+    ModelCloud sampled;
+    int n = 0;
+    int rc = stocs_preprocess_model_mesh(mesh_v.data(), nv, mesh_t.data(), nt, spacing, seed, orient, voxel_size, read_depth_scale, -1, NULL, NULL, 0, &n);   // the size
+    if (rc == STOCS_ERR_CAPACITY && n > 0) {
+        sampled.pos.resize((size_t)n * 3); sampled.nrm.resize((size_t)n * 3);
+        rc = stocs_preprocess_model_mesh(mesh_v.data(), nv, mesh_t.data(), nt, spacing, seed, orient, voxel_size, read_depth_scale, -1, sampled.pos.data(), sampled.nrm.data(), n, &n);
+    }
+    if (rc != STOCS_OK) throw std::runtime_error(std::string("stocs_preprocess_model_mesh: ") + stocs_last_error());
+    write_model_and_index(sampled, n, write_depth_scale, ppf_tr_discretization, ppf_rot_discretization, dst_model_location, dst_ppf_map_location);
 }
 
 }  // namespace stocs

@@ -1152,6 +1152,49 @@ int stocs_pose_errors_vsd_mesh(stocs_ctx* ctx, const float* est_pose16_camera, i
                                const stocs_vsd_params* p, stocs_vsd_record* out);
 int stocs_mesh_last_call_timing(const stocs_ctx* ctx, const char** labels, double* ms, int cap, int* n);
 
+/* ---- mesh models: a triangle mesh sampled into the oriented model cloud the search needs (no reference counterpart).  Stand-alone like
+ * stocs_preprocess_model: no context; the same cached per-thread workspace and pinned block (stocs_trim gives them back; a second call of
+ * the same or a smaller size allocates nothing).  csrc/mesh_sample.hip, restated in numpy in tests/mesh_sample_ref.py, equal bit for bit.
+ * The mesh is stocs_ctx_set_mesh's; spacing h > 0 in the mesh's units: one sample per h^2 of area in expectation; seed: any 64 bits.
+ * Per triangle t = (A, B, C), in double from the float coordinates, every operation one IEEE operation in this order:
+ *   e1 = B - A, e2 = C - A, c = e1 x e2 (each component a difference of two rounded products), len = sqrt(cx cx + (cy cy + cz cz)),
+ *   area = 0.5 len, x = area / (hd hd) with hd = (double)h;   n_t = floor(x) + (d_t < x - floor(x)),
+ *   d_t = (key_t >> 40) 2^-24, key_t = mix64(mix64(seed + 0x9E3779B97F4A7C15) ^ (t 0xD1B54A32D192ED03 + 0x8CB92BA72F3D8DD7)) modulo 2^64,
+ *   mix64(z): z = (z ^ (z >> 30)) 0xBF58476D1CE4E5B9; z = (z ^ (z >> 27)) 0x94D049BB133111EB; z ^ (z >> 31).
+ *   A triangle with a non-finite corner or len == 0 has no sample and counts as skipped.  x >= 2^32 - 1 on any triangle, or a total above
+ *   2^31 - 1, is STOCS_ERR_INVALID ("spacing too small for the mesh").
+ * Per sample j < n_t: w = mix64(key_t ^ ((j + 1) 0xDB4F0B9175AE2165)), iu = w >> 40, iv = (w >> 16) & 0xFFFFFF; when iu + iv >= 2^24 both
+ *   are reflected (2^24 - 1 - i); u = iu 2^-24, v = iv 2^-24 (exact floats); in float, per component, position = A + (u (B - A) + v (C - A));
+ *   normal = (float)(c / len) per component.  orient 0: that normal, the winding's (B - A) x (C - A).  orient 1: negated when
+ *   n.x p.x + (n.y p.y + n.z p.z) < 0 in float, p the sample's position: away from the origin, stocs_preprocess_model's convention, for meshes
+ *   whose winding is not consistent.
+ * Samples come in (t, j) order.  A triangle's samples depend on the seed, its index and its corners only.
+ * stocs_mesh_sample_counts: the sizes, and the per-triangle detail.  Checked in this order, all before a device is looked for:
+ *   stocs_mesh_check's answers except the finite-vertex test (a non-finite corner is a skipped triangle here); a spacing that is not
+ *   finite or not above 0: STOCS_ERR_INVALID.  nt == 0: all zero, STOCS_OK.  counts (nt) and every other output may be NULL.
+ *   *area_total: the areas of the triangles that are not skipped, added in triangle order in double.
+ * stocs_mesh_sample: in this order, before a device is looked for: NULL n_out; stocs_mesh_check's answers (a non-finite vertex included); the
+ *   spacing as above; orient outside {0, 1}; cap < 0: STOCS_ERR_INVALID (STOCS_ERR_CAPACITY where stocs_mesh_check says so).  nt == 0 or a
+ *   total of 0: STOCS_OK, *n_out = 0.  A total above cap: STOCS_ERR_CAPACITY, *n_out = the total, nothing else is written.  Any of
+ *   out_pos3, out_nrm3 (total x 3) and out_tri (total) may be NULL.
+ * stocs_preprocess_model_mesh: the samples go through the voxel grid of stocs_preprocess_model on the device (positions and normals
+ *   averaged per leaf; no host round trip between the sample kernel and the grid), then its tail: a leaf whose averaged normal has no
+ *   length is dropped, the others are normalised in double, positions times model_scale.  spacing == 0: voxel_size / 4, about 16 samples
+ *   per leaf face.  Checks as stocs_mesh_sample (spacing 0 allowed), then voxel_size not finite or not above 0, a non-finite
+ *   model_scale, cap < 0: STOCS_ERR_INVALID.  More leaves than cap: STOCS_ERR_CAPACITY with *n_out the count and the first cap written,
+ *   as stocs_preprocess_model.
+ * STOCS_MESH_SAMPLE_FORM=<n> in the environment forces the sample kernel's search form for measurements and tests (1: every lane searches
+ * the whole offset array, the default; 2: a workgroup finds its triangle range once and searches a window of it in LDS); no value changes a
+ * result. ---- */
+#define STOCS_MESH_ORIENT_WINDING 0
+#define STOCS_MESH_ORIENT_ORIGIN 1
+int stocs_mesh_sample_counts(const float* pos3, int nv, const int32_t* tris3, int nt, float spacing, uint64_t seed, int device,
+                             int32_t* counts /* nt or NULL */, double* area_total, int64_t* n_total, int* n_skipped);
+int stocs_mesh_sample(const float* pos3, int nv, const int32_t* tris3, int nt, float spacing, uint64_t seed, int orient, int device,
+                      float* out_pos3, float* out_nrm3, int32_t* out_tri, int cap, int* n_out);
+int stocs_preprocess_model_mesh(const float* pos3, int nv, const int32_t* tris3, int nt, float spacing, uint64_t seed, int orient,
+                                float voxel_size, float model_scale, int device, float* pos3_out, float* nrm3_out, int cap, int* n_out);
+
 /* ---- tuning knobs (never change results beyond float summation order).
  * "lcp_variant": 99 = automatic (default): the scan fed from a per-wavefront LDS queue of the queries that have a list -- over
  *   index-ordered lists at cell edge epsilon (24, sparse scenes), over centre-sorted lists with triangle-inequality early exit

@@ -3,11 +3,16 @@
 // stocs::pre_process_model (normals, voxel grid and the O(|M|^2) PPF index all on the GPU).
 //   model_preprocess <object_name> [--repo DIR] [--voxel 0.01] [--normal-radius 0.005] [--model-scale 1.0]
 //                    [--find-symmetry [--sym-tol m] [--sym-steps n]]
+//                    [--mesh <ply> [--spacing m] [--orient winding|origin] [--sample-seed n]]
 // The reference edits these constants in the source per data set (README.md:42-60); the defaults are its YCB values.
 // --find-symmetry (not in the reference): after the index is written, search the sampled model for its symmetry axes
 // (stocs_find_symmetries; --sym-tol: the tolerance in metres, default a tenth of the diameter; --sym-steps: steps of a continuous axis,
 // default 72), print them, write models/<object>/symmetry.txt -- the text stocs_single --sym-file reads: 16 floats per transform,
 // column-major -- and print the --sym a,b,c line to use with it.
+// --mesh <ply> (not in the reference): the model comes from a triangle mesh in place of textured_vertices.ply: its surface is sampled on
+// the GPU at one point per spacing^2 (--spacing, in the mesh's units; default voxel / 4) with facet normals oriented by the winding
+// (--orient origin: turned away from the origin, for meshes whose winding is not consistent), then voxel grid, scale and index as before;
+// --normal-radius is not read.  A file that holds no mesh, or no faces, is refused.
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -32,6 +37,11 @@ int main(int argc, char** argv) {
     if (const char* e = getenv("STOCS_REPO_PATH")) repo_path = e;
     bool find_symmetry = false;
     stocs_symmetry_search search = stocs::default_symmetry_search();
+    std::string mesh_path;
+    float spacing = 0.0f;
+    int orient = STOCS_MESH_ORIENT_WINDING;
+    unsigned long long sample_seed = 0;
+    bool have_mesh_option = false;
     for (int i = 2; i < argc; i += 2) {
         const std::string k = argv[i];
         if (k == "--find-symmetry") { find_symmetry = true; --i; continue; }   // a flag: no value
@@ -43,14 +53,27 @@ int main(int argc, char** argv) {
         else if (k == "--voxel") voxel_size = (float)atof(v.c_str());
         else if (k == "--normal-radius") normal_radius = (float)atof(v.c_str());
         else if (k == "--model-scale") model_scale = (float)atof(v.c_str());
+        else if (k == "--mesh") mesh_path = v;
+        else if (k == "--spacing") { spacing = (float)atof(v.c_str()); have_mesh_option = true; }
+        else if (k == "--sample-seed") { sample_seed = strtoull(v.c_str(), NULL, 0); have_mesh_option = true; }
+        else if (k == "--orient") {
+            if (v != "winding" && v != "origin") { std::cerr << "--orient takes winding or origin" << std::endl; return -1; }
+            orient = v == "origin" ? STOCS_MESH_ORIENT_ORIGIN : STOCS_MESH_ORIENT_WINDING;
+            have_mesh_option = true;
+        }
         else { std::cerr << "unknown option " << k << std::endl; return -1; }
     }
+    if (have_mesh_option && mesh_path.empty()) { std::cerr << "--spacing, --orient and --sample-seed need --mesh <ply>" << std::endl; return -1; }
     const std::string model_path = repo_path + "/models/" + object_name;
     remove((model_path + "/model_search.ply").c_str());   // :25-26
     remove((model_path + "/ppf_map").c_str());
     try {
-        stocs::pre_process_model(model_path + "/textured_vertices.ply", normal_radius, model_scale, 1.0f, voxel_size, ppf_tr_discretization, ppf_rot_discretization,
-                                 model_path + "/model_search.ply", model_path + "/ppf_map");
+        if (!mesh_path.empty())
+            stocs::pre_process_model_mesh(mesh_path, spacing, (uint64_t)sample_seed, orient, model_scale, 1.0f, voxel_size, ppf_tr_discretization, ppf_rot_discretization,
+                                          model_path + "/model_search.ply", model_path + "/ppf_map");
+        else
+            stocs::pre_process_model(model_path + "/textured_vertices.ply", normal_radius, model_scale, 1.0f, voxel_size, ppf_tr_discretization, ppf_rot_discretization,
+                                     model_path + "/model_search.ply", model_path + "/ppf_map");
         if (find_symmetry) {
             const stocs::SymmetryResult r = stocs::find_model_symmetries(model_path + "/model_search.ply", search);
             std::cout << "symmetry axes: " << r.axes.size() << std::endl;

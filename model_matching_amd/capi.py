@@ -258,6 +258,9 @@ SIGNATURES = {
     "stocs_render_depth_mesh": (C.c_int, [_vp, _fp, C.c_int, _fp]),
     "stocs_pose_errors_vsd_mesh": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, C.POINTER(VsdParams), C.POINTER(VsdRecord)]),
     "stocs_mesh_last_call_timing": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.c_int, _intp]),
+    "stocs_mesh_sample_counts": (C.c_int, [_fp, C.c_int, _ip, C.c_int, C.c_float, C.c_uint64, C.c_int, _ip, C.POINTER(C.c_double), _i64p, _intp]),
+    "stocs_mesh_sample": (C.c_int, [_fp, C.c_int, _ip, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, _fp, _fp, _ip, C.c_int, _intp]),
+    "stocs_preprocess_model_mesh": (C.c_int, [_fp, C.c_int, _ip, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_float, C.c_float, C.c_int, _fp, _fp, C.c_int, _intp]),
     "stocs_pose_errors": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, C.POINTER(PoseError)]),
     "stocs_pose_errors_detail": (C.c_int, [_vp, _fp, _fp, _fp, _fp, _ip]),
     "stocs_model_diameter": (C.c_int, [_vp, _fp]),

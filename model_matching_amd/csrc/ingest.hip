@@ -25,6 +25,7 @@
 #include <map>
 #include <vector>
 
+#include "mesh_sample.h"
 #include "prims.h"
 #include "stocs_ctx.h"
 
@@ -695,6 +696,88 @@ static int ingest_shared_stages(const stocs_camera* cam, const uint16_t* dD, flo
     return STOCS_OK;
 }
 
+// The tail of model preprocessing, shared by the vertex path and the mesh path: the nv leaves' centroids and averaged normals come down,
+// a leaf whose averaged normal has no finite, positive length is dropped, the others are normalised in double and the positions scaled.
+static int model_from_leaves(const Buf<float4>& cen, const Buf<float4>& ext, int nv, float model_scale, float* pos3, float* nrm3, int cap, int* n_out, hipStream_t st) {
+    STOCS_HIP_CHECK(hipStreamSynchronize(st));
+    std::vector<float4> hc((size_t)std::max(nv, 1)), he((size_t)std::max(nv, 1));
+    STOCS_HIP_CHECK(hipMemcpy(hc.data(), cen.p, sizeof(float4) * (size_t)nv, hipMemcpyDeviceToHost));
+    STOCS_HIP_CHECK(hipMemcpy(he.data(), ext.p, sizeof(float4) * (size_t)nv, hipMemcpyDeviceToHost));
+    int m = 0;
+    for (int i = 0; i < nv; ++i) {
+        const V3 nn = mk3(he[i].x, he[i].y, he[i].z);
+        const double len = sqrt((double)nn.x * nn.x + (double)nn.y * nn.y + (double)nn.z * nn.z);
+        if (!(len > 0) || !(len == len)) continue;   // load_ply_model keeps finite normals only (rgbd.cpp:22)
+        if (m < cap) {
+            if (pos3) { pos3[3 * m] = hc[i].x * model_scale; pos3[3 * m + 1] = hc[i].y * model_scale; pos3[3 * m + 2] = hc[i].z * model_scale; }
+            if (nrm3) { nrm3[3 * m] = (float)(nn.x / len); nrm3[3 * m + 1] = (float)(nn.y / len); nrm3[3 * m + 2] = (float)(nn.z / len); }
+        }
+        m++;
+    }
+    *n_out = m;
+    return m > cap ? STOCS_ERR_CAPACITY : STOCS_OK;
+}
+
+// ---- mesh models (stocs_mesh_sample_counts, stocs_mesh_sample, stocs_preprocess_model_mesh): the kernels are mesh_sample.hip's, the workspace,
+// the pinned block and the voxel grid this file's
+static int ingest_require_device() {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: this library has no CPU fallback"); return STOCS_ERR_NO_DEVICE; }
+    return STOCS_OK;
+}
+
+struct MeshSampleRun {
+    Buf<float4> verts, tri_nrm; Buf<int4> tris; Buf<uint32_t> counts, flags; Buf<unsigned long long> offs; Buf<double> area;
+    long long total = 0;
+    int skipped = 0;
+};
+// The mesh goes up through the pinned block, the count pass and the scan run, and the total and the flag words come back: one synchronise.
+// nt >= 1, the indices checked.  An overflowing triangle is STOCS_ERR_INVALID under the caller's name.
+static int mesh_sample_count_run(const char* who, const float* pos3, int nv, const int32_t* tris3, int nt, float spacing, uint64_t seed, bool want_nrm, bool want_area,
+                                 MeshSampleRun& R, hipStream_t st) {
+    int rc;
+    if ((rc = R.verts.alloc(nv)) || (rc = R.tris.alloc(nt)) || (rc = R.counts.alloc((size_t)nt + 1)) || (rc = R.offs.alloc((size_t)nt + 1)) ||
+        (rc = R.flags.alloc(MESH_SAMPLE_FLAG_WORDS)) || (want_nrm && (rc = R.tri_nrm.alloc(nt))) || (want_area && (rc = R.area.alloc(nt))))
+        return rc;
+    char* pin = NULL;
+    const size_t o_v = 4096, o_t = o_v + al256((size_t)nv * 16);
+    if ((rc = staging(o_t + (size_t)nt * 16, &pin))) return rc;
+    float* hv = (float*)(pin + o_v);
+    int32_t* ht = (int32_t*)(pin + o_t);
+    for (int i = 0; i < nv; ++i) { hv[4 * i] = pos3[3 * i]; hv[4 * i + 1] = pos3[3 * i + 1]; hv[4 * i + 2] = pos3[3 * i + 2]; hv[4 * i + 3] = 0.0f; }
+    for (int i = 0; i < nt; ++i) { ht[4 * i] = tris3[3 * i]; ht[4 * i + 1] = tris3[3 * i + 1]; ht[4 * i + 2] = tris3[3 * i + 2]; ht[4 * i + 3] = 0; }
+    STOCS_HIP_CHECK(hipMemcpyAsync(R.verts.p, hv, (size_t)nv * 16, hipMemcpyHostToDevice, st));
+    STOCS_HIP_CHECK(hipMemcpyAsync(R.tris.p, ht, (size_t)nt * 16, hipMemcpyHostToDevice, st));
+    STOCS_HIP_CHECK(hipMemsetAsync(R.flags.p, 0, sizeof(uint32_t) * MESH_SAMPLE_FLAG_WORDS, st));
+    STOCS_HIP_CHECK(mesh_sample_count_launch(R.verts.p, R.tris.p, nt, (double)spacing, seed, R.counts.p, want_nrm ? R.tri_nrm.p : NULL, want_area ? R.area.p : NULL, R.flags.p, st));
+    size_t tb = 0;
+    Buf<char> tmp;
+    STOCS_HIP_CHECK(exclusive_scan(NULL, tb, R.counts.p, R.offs.p, (size_t)nt + 1, st));
+    if ((rc = tmp.alloc(tb))) return rc;
+    STOCS_HIP_CHECK(exclusive_scan(tmp.p, tb, R.counts.p, R.offs.p, (size_t)nt + 1, st));
+    unsigned long long* h_total = (unsigned long long*)pin;
+    uint32_t* h_flags = (uint32_t*)(pin + 8);
+    STOCS_HIP_CHECK(hipMemcpyAsync(h_total, R.offs.p + nt, 8, hipMemcpyDeviceToHost, st));
+    STOCS_HIP_CHECK(hipMemcpyAsync(h_flags, R.flags.p, sizeof(uint32_t) * MESH_SAMPLE_FLAG_WORDS, hipMemcpyDeviceToHost, st));
+    STOCS_HIP_CHECK(hipStreamSynchronize(st));
+    if (h_flags[MESH_SAMPLE_FLAG_OVERFLOW]) { set_error("%s: spacing %g too small for the mesh (a triangle holds 2^32 - 1 samples or more)", who, (double)spacing); return STOCS_ERR_INVALID; }
+    R.total = (long long)*h_total;
+    R.skipped = (int)h_flags[MESH_SAMPLE_FLAG_SKIPPED];
+    if (R.total > (long long)INT_MAX) { set_error("%s: spacing %g too small for the mesh (%lld samples, above 2^31 - 1)", who, (double)spacing, R.total); return STOCS_ERR_INVALID; }
+    return STOCS_OK;
+}
+// the sample pass behind mesh_sample_count_run (want_nrm), R.total > 0: total float4 positions and normals, and the triangle indices when asked
+static int mesh_sample_run(const MeshSampleRun& R, int nt, uint64_t seed, int orient, bool want_tri, Buf<float4>& pos, Buf<float4>& nrm, Buf<int32_t>& tri, hipStream_t st) {
+    int rc;
+    if ((rc = pos.alloc((size_t)R.total)) || (rc = nrm.alloc((size_t)R.total)) || (want_tri && (rc = tri.alloc((size_t)R.total)))) return rc;
+    STOCS_HIP_CHECK(mesh_sample_launch(R.verts.p, R.tris.p, nt, R.offs.p, R.tri_nrm.p, seed, orient, R.total, pos.p, nrm.p, want_tri ? tri.p : NULL, st));
+    return STOCS_OK;
+}
+static int mesh_sample_check_spacing(const char* who, float spacing, bool zero_is_default) {
+    if (!std::isfinite(spacing) || spacing < 0.0f || (spacing == 0.0f && !zero_is_default)) { set_error("%s: spacing %g is not finite or not above 0", who, (double)spacing); return STOCS_ERR_INVALID; }
+    return STOCS_OK;
+}
+
 // STOCS_DEBUG_TIMING: the ingest's stages on stderr (each one synchronised)
 struct IngestTick {
     const char* who;
@@ -915,23 +998,99 @@ int stocs_preprocess_model(const float* raw_pos3, int n_raw, float normal_radius
     STOCS_HIP_CHECK(hipMemcpy(dN2.p, kn.data(), sizeof(float4) * (size_t)nk, hipMemcpyHostToDevice));
     int nv = 0;
     if ((rc = voxel_grid_device(dP2.p, dN2.p, nk, (double)voxel_size, cen, ext, &nv, st))) return rc;   // stocs.cpp:54-57
+    return model_from_leaves(cen, ext, nv, model_scale, pos3, nrm3, cap, n_out, st);
+}
+
+int stocs_mesh_sample_counts(const float* pos3, int nv, const int32_t* tris3, int nt, float spacing, uint64_t seed, int device, int32_t* counts, double* area_total,
+                             int64_t* n_total, int* n_skipped) {
+    static const char* who = "stocs_mesh_sample_counts";
+    int rc;
+    if ((rc = mesh_check_as(who, pos3, nv, tris3, nt, false)) || (rc = mesh_sample_check_spacing(who, spacing, false))) return rc;
+    if (area_total) *area_total = 0.0;
+    if (n_total) *n_total = 0;
+    if (n_skipped) *n_skipped = 0;
+    if (nt == 0) return STOCS_OK;
+    if ((rc = ingest_require_device())) return rc;
+    if (device >= 0) STOCS_HIP_CHECK(hipSetDevice(device));
+    if ((rc = workspace_begin(device))) return rc;
+    hipStream_t st = NULL;
+    MeshSampleRun R;
+    if ((rc = mesh_sample_count_run(who, pos3, nv, tris3, nt, spacing, seed, false, area_total != NULL, R, st))) return rc;
+    if (n_total) *n_total = (int64_t)R.total;
+    if (n_skipped) *n_skipped = R.skipped;
+    if (!counts && !area_total) return STOCS_OK;
+    char* pin = NULL;
+    if ((rc = staging((size_t)nt * 12, &pin))) return rc;   // (the mesh in the block was consumed before the total came back)
+    double* h_area = (double*)pin;
+    int32_t* h_counts = (int32_t*)(pin + (size_t)nt * 8);
+    if (area_total) STOCS_HIP_CHECK(hipMemcpyAsync(h_area, R.area.p, (size_t)nt * 8, hipMemcpyDeviceToHost, st));
+    if (counts) STOCS_HIP_CHECK(hipMemcpyAsync(h_counts, R.counts.p, (size_t)nt * 4, hipMemcpyDeviceToHost, st));
     STOCS_HIP_CHECK(hipStreamSynchronize(st));
-    std::vector<float4> hc((size_t)std::max(nv, 1)), he((size_t)std::max(nv, 1));
-    STOCS_HIP_CHECK(hipMemcpy(hc.data(), cen.p, sizeof(float4) * (size_t)nv, hipMemcpyDeviceToHost));
-    STOCS_HIP_CHECK(hipMemcpy(he.data(), ext.p, sizeof(float4) * (size_t)nv, hipMemcpyDeviceToHost));
-    int m = 0;
-    for (int i = 0; i < nv; ++i) {
-        const V3 nn = mk3(he[i].x, he[i].y, he[i].z);
-        const double len = sqrt((double)nn.x * nn.x + (double)nn.y * nn.y + (double)nn.z * nn.z);
-        if (!(len > 0) || !(len == len)) continue;   // load_ply_model keeps finite normals only (rgbd.cpp:22)
-        if (m < cap) {
-            if (pos3) { pos3[3 * m] = hc[i].x * model_scale; pos3[3 * m + 1] = hc[i].y * model_scale; pos3[3 * m + 2] = hc[i].z * model_scale; }
-            if (nrm3) { nrm3[3 * m] = (float)(nn.x / len); nrm3[3 * m + 1] = (float)(nn.y / len); nrm3[3 * m + 2] = (float)(nn.z / len); }
-        }
-        m++;
-    }
-    *n_out = m;
-    return m > cap ? STOCS_ERR_CAPACITY : STOCS_OK;
+    if (counts) memcpy(counts, h_counts, (size_t)nt * 4);
+    if (area_total) { double a = 0.0; for (int t = 0; t < nt; ++t) a += h_area[t]; *area_total = a; }   // in triangle order: the contract
+    return STOCS_OK;
+}
+
+int stocs_mesh_sample(const float* pos3, int nv, const int32_t* tris3, int nt, float spacing, uint64_t seed, int orient, int device, float* out_pos3, float* out_nrm3,
+                      int32_t* out_tri, int cap, int* n_out) {
+    static const char* who = "stocs_mesh_sample";
+    int rc;
+    if (!n_out) { set_error("%s: NULL n_out", who); return STOCS_ERR_INVALID; }
+    if ((rc = mesh_check_as(who, pos3, nv, tris3, nt, true)) || (rc = mesh_sample_check_spacing(who, spacing, false))) return rc;
+    if (orient != 0 && orient != 1) { set_error("%s: orient %d is neither 0 (winding) nor 1 (away from the origin)", who, orient); return STOCS_ERR_INVALID; }
+    if (cap < 0) { set_error("%s: cap %d < 0", who, cap); return STOCS_ERR_INVALID; }
+    *n_out = 0;
+    if (nt == 0) return STOCS_OK;
+    if ((rc = ingest_require_device())) return rc;
+    if (device >= 0) STOCS_HIP_CHECK(hipSetDevice(device));
+    if ((rc = workspace_begin(device))) return rc;
+    hipStream_t st = NULL;
+    MeshSampleRun R;
+    if ((rc = mesh_sample_count_run(who, pos3, nv, tris3, nt, spacing, seed, true, false, R, st))) return rc;
+    *n_out = (int)R.total;
+    if (R.total > (long long)cap) { set_error("%s: %lld samples, cap %d", who, R.total, cap); return STOCS_ERR_CAPACITY; }
+    if (R.total == 0) return STOCS_OK;
+    const size_t n = (size_t)R.total;
+    Buf<float4> pos, nrm; Buf<int32_t> tri;
+    if ((rc = mesh_sample_run(R, nt, seed, orient, out_tri != NULL, pos, nrm, tri, st))) return rc;
+    char* pin = NULL;
+    if ((rc = staging(36 * n, &pin))) return rc;   // (the mesh in the block was consumed before the total came back)
+    const float4* h_pos = (const float4*)pin; const float4* h_nrm = (const float4*)(pin + 16 * n); const int32_t* h_tri = (const int32_t*)(pin + 32 * n);
+    if (out_pos3) STOCS_HIP_CHECK(hipMemcpyAsync(pin, pos.p, 16 * n, hipMemcpyDeviceToHost, st));
+    if (out_nrm3) STOCS_HIP_CHECK(hipMemcpyAsync(pin + 16 * n, nrm.p, 16 * n, hipMemcpyDeviceToHost, st));
+    if (out_tri) STOCS_HIP_CHECK(hipMemcpyAsync(pin + 32 * n, tri.p, 4 * n, hipMemcpyDeviceToHost, st));
+    STOCS_HIP_CHECK(hipStreamSynchronize(st));
+    for (size_t i = 0; out_pos3 && i < n; ++i) { out_pos3[3 * i] = h_pos[i].x; out_pos3[3 * i + 1] = h_pos[i].y; out_pos3[3 * i + 2] = h_pos[i].z; }
+    for (size_t i = 0; out_nrm3 && i < n; ++i) { out_nrm3[3 * i] = h_nrm[i].x; out_nrm3[3 * i + 1] = h_nrm[i].y; out_nrm3[3 * i + 2] = h_nrm[i].z; }
+    if (out_tri) memcpy(out_tri, h_tri, 4 * n);
+    return STOCS_OK;
+}
+
+int stocs_preprocess_model_mesh(const float* pos3, int nv, const int32_t* tris3, int nt, float spacing, uint64_t seed, int orient, float voxel_size, float model_scale,
+                                int device, float* pos3_out, float* nrm3_out, int cap, int* n_out) {
+    static const char* who = "stocs_preprocess_model_mesh";
+    int rc;
+    if (!n_out) { set_error("%s: NULL n_out", who); return STOCS_ERR_INVALID; }
+    if ((rc = mesh_check_as(who, pos3, nv, tris3, nt, true)) || (rc = mesh_sample_check_spacing(who, spacing, true))) return rc;
+    if (orient != 0 && orient != 1) { set_error("%s: orient %d is neither 0 (winding) nor 1 (away from the origin)", who, orient); return STOCS_ERR_INVALID; }
+    if (!std::isfinite(voxel_size) || !(voxel_size > 0)) { set_error("%s: voxel_size %g is not finite or not above 0", who, (double)voxel_size); return STOCS_ERR_INVALID; }
+    if (!std::isfinite(model_scale)) { set_error("%s: model_scale is not finite", who); return STOCS_ERR_INVALID; }
+    if (cap < 0) { set_error("%s: cap %d < 0", who, cap); return STOCS_ERR_INVALID; }
+    *n_out = 0;
+    if (nt == 0) return STOCS_OK;
+    if ((rc = ingest_require_device())) return rc;
+    if (device >= 0) STOCS_HIP_CHECK(hipSetDevice(device));
+    if ((rc = workspace_begin(device))) return rc;
+    hipStream_t st = NULL;
+    const float h = spacing == 0.0f ? voxel_size / 4.0f : spacing;
+    MeshSampleRun R;
+    if ((rc = mesh_sample_count_run(who, pos3, nv, tris3, nt, h, seed, true, false, R, st))) return rc;
+    if (R.total == 0) return STOCS_OK;
+    Buf<float4> pos, nrm, cen, ext; Buf<int32_t> tri;
+    if ((rc = mesh_sample_run(R, nt, seed, orient, false, pos, nrm, tri, st))) return rc;
+    int n_leaves = 0;
+    if ((rc = voxel_grid_device(pos.p, nrm.p, (int)R.total, (double)voxel_size, cen, ext, &n_leaves, st))) return rc;   // the samples never leave the device
+    return model_from_leaves(cen, ext, n_leaves, model_scale, pos3_out, nrm3_out, cap, n_out, st);
 }
 
 }  // extern "C"

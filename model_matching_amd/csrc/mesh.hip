@@ -27,6 +27,7 @@
 
 #include <vector>
 
+#include "mesh_sample.h"
 #include "pose_error_math.h"
 #include "render_rules.h"
 #include "vsd_shared.h"
@@ -233,17 +234,18 @@ extern "C" void stocs_internal_free_mesh(stocs_ctx* c) {
 
 extern "C" int stocs_mesh_small_px(void) { return (int)MESH_SMALL_PX; }
 
-extern "C" int stocs_mesh_check(const float* pos3, int nv, const int32_t* tris3, int nt) {
-    static const char* who = "stocs_mesh_check";
+int stocs::mesh_check_as(const char* who, const float* pos3, int nv, const int32_t* tris3, int nt, bool finite_vertices) {
     if (nv < 0 || nt < 0) { set_error("%s: nv %d or nt %d < 0", who, nv, nt); return STOCS_ERR_INVALID; }
     if ((nv && !pos3) || (nt && !tris3)) { set_error("%s: NULL vertices or triangles", who); return STOCS_ERR_INVALID; }
     if (nv > MESH_MAX_V || nt > MESH_MAX_T) { set_error("%s: %d vertices, %d triangles above %d, %d", who, nv, nt, (int)MESH_MAX_V, (int)MESH_MAX_T); return STOCS_ERR_CAPACITY; }
-    for (size_t k = 0; k < (size_t)nv * 3; ++k)
+    for (size_t k = 0; finite_vertices && k < (size_t)nv * 3; ++k)
         if (!isfinite(pos3[k])) { set_error("%s: vertex %zu is not finite", who, k / 3); return STOCS_ERR_INVALID; }
     for (size_t k = 0; k < (size_t)nt * 3; ++k)
         if (tris3[k] < 0 || tris3[k] >= nv) { set_error("%s: triangle %zu has index %d outside 0..%d", who, k / 3, (int)tris3[k], nv - 1); return STOCS_ERR_INVALID; }
     return STOCS_OK;
 }
+
+extern "C" int stocs_mesh_check(const float* pos3, int nv, const int32_t* tris3, int nt) { return mesh_check_as("stocs_mesh_check", pos3, nv, tris3, nt, true); }
 
 extern "C" int stocs_ctx_set_mesh(stocs_ctx* c, const float* pos3, int nv, const int32_t* tris3, int nt) {
     static const char* who = "stocs_ctx_set_mesh";

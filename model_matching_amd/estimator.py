@@ -1323,6 +1323,55 @@ def preprocess_model(raw_pos, normal_radius, voxel_size, model_scale=1.0, device
     return pos[:n.value].copy(), nrm[:n.value].copy()
 
 
+def mesh_sample_counts(verts, tris, spacing, seed=0, device=-1):
+    """The sizes of mesh_sample (stocs_mesh_sample_counts): returns (counts (nt,) int32, area_total, n_total, n_skipped)."""
+    L = capi.load()
+    v, pv = capi.f32(verts); t, pt = capi.i32(tris)
+    counts = np.zeros(len(t), np.int32)
+    area, total, skipped = C.c_double(0.0), C.c_int64(0), C.c_int(0)
+    capi.check(L.stocs_mesh_sample_counts(pv, len(v), pt, len(t), spacing, int(seed) & (2 ** 64 - 1), device, counts.ctypes.data_as(capi._ip), C.byref(area),
+                                          C.byref(total), C.byref(skipped)))
+    return counts, area.value, total.value, skipped.value
+
+
+def mesh_sample(verts, tris, spacing, seed=0, orient=0, device=-1):
+    """A triangle mesh sampled at one point per spacing^2 of area (stocs_mesh_sample): returns (pos (n, 3), unit nrm (n, 3), triangle
+    index (n,) int32) in (triangle, sample) order.  orient 0: the normal of the winding, 1: turned away from the origin."""
+    L = capi.load()
+    v, pv = capi.f32(verts); t, pt = capi.i32(tris)
+    n = C.c_int(0)
+    seed = int(seed) & (2 ** 64 - 1)
+    rc = L.stocs_mesh_sample(pv, len(v), pt, len(t), spacing, seed, orient, device, None, None, None, 0, C.byref(n))   # the size
+    if rc != capi.ERR_CAPACITY or n.value == 0:   # (a mesh above stocs_mesh_check's limits is a capacity answer too, with no size)
+        capi.check(rc)
+    cap = n.value
+    pos = np.zeros((cap, 3), np.float32); nrm = np.zeros((cap, 3), np.float32); tri = np.zeros(cap, np.int32)
+    if cap:
+        capi.check(L.stocs_mesh_sample(pv, len(v), pt, len(t), spacing, seed, orient, device, pos.ctypes.data_as(capi._fp), nrm.ctypes.data_as(capi._fp),
+                                       tri.ctypes.data_as(capi._ip), cap, C.byref(n)))
+    return pos, nrm, tri
+
+
+def preprocess_model_mesh(verts, tris, voxel_size, spacing=0.0, seed=0, orient=0, model_scale=1.0, device=-1):
+    """GPU model preprocessing from a mesh (stocs_preprocess_model_mesh): the surface sampled at `spacing` (0: voxel_size / 4), facet
+    normals, voxel grid -> voxelised pos, unit nrm."""
+    L = capi.load()
+    v, pv = capi.f32(verts); t, pt = capi.i32(tris)
+    n = C.c_int(0)
+    seed = int(seed) & (2 ** 64 - 1)
+    cap = 1 << 16
+    for attempt in range(2):
+        pos = np.zeros((cap, 3), np.float32); nrm = np.zeros((cap, 3), np.float32)
+        rc = L.stocs_preprocess_model_mesh(pv, len(v), pt, len(t), spacing, seed, orient, voxel_size, model_scale, device, pos.ctypes.data_as(capi._fp),
+                                           nrm.ctypes.data_as(capi._fp), cap, C.byref(n))
+        if rc == capi.ERR_CAPACITY and attempt == 0:
+            cap = n.value
+            continue
+        capi.check(rc)
+        break
+    return pos[:n.value].copy(), nrm[:n.value].copy()
+
+
 def icp_point_to_plane(src_pos, tgt_pos, tgt_nrm, max_iterations=5, max_correspondence_distance=0.035, device=-1):
     """GPU point-to-plane ICP (stocs_icp_point_to_plane): returns (T 4x4 float32 source->target, n_correspondences)."""
     L = capi.load()

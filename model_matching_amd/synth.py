@@ -129,6 +129,17 @@ def make_model_mesh(level: int = 4, n: int = 5000, seed: int = SEED_MODEL, scale
     return np.ascontiguousarray(verts, np.float32), np.ascontiguousarray(tris, np.int32)
 
 
+def box_mesh(size3):
+    """an axis-aligned box of edge lengths size3 centred on the origin: 8 vertices (vertex i at the sign pattern of its bits, x the
+    lowest), 12 triangles, outward winding -> (vertices (8, 3) float32, triangles (12, 3) int32)"""
+    half = np.asarray(size3, np.float64) / 2.0
+    verts = np.array([[(1 if i & 1 else -1), (1 if i & 2 else -1), (1 if i & 4 else -1)] for i in range(8)], np.float64) * half
+    tris = [(0, 4, 6), (0, 6, 2), (1, 3, 7), (1, 7, 5),      # x = -, x = +
+            (0, 1, 5), (0, 5, 4), (2, 6, 7), (2, 7, 3),      # y = -, y = +
+            (0, 2, 3), (0, 3, 1), (4, 5, 7), (4, 7, 6)]      # z = -, z = +
+    return np.ascontiguousarray(verts, np.float32), np.asarray(tris, np.int32)
+
+
 def make_model_asym(n: int = 5000, seed: int = SEED_MODEL + 101) -> Cloud:
     """A model without any symmetry, for pose-quality reports: tri-axial ellipsoid (0.08, 0.055, 0.03) m with two spherical bumps of
     different size off every symmetry plane -- r = 0.02 m at (0.05, 0.01, 0.02) and r = 0.012 m at (-0.035, 0.03, -0.012).  Every
