@@ -1280,6 +1280,13 @@ typedef struct stocs_grid_info {
 } stocs_grid_info;
 /* STOCS_ERR_INVALID for a NULL argument; STOCS_ERR_STATE ("no scene") for a context whose last scene was refused -- *info is zeroed. */
 int stocs_get_grid_info(stocs_ctx* ctx, stocs_grid_info* info);
+/* The octant lines of that grid (sparse pruned grids at cell edge epsilon with a flat table; STOCS_GRID_OCTANTS=0, read per build,
+ * leaves them out), beside the struct above, whose layout is fixed: counts3[0] = cells whose stored list is longer
+ * than one 128-byte line of 8 entries, [1] = those of them whose eight octants each fit one line (their flat-table word names the block
+ * of octant lines; the rest stay plain), [2] = the entries of those cells' octant lines before padding.  [1] and [2] are 0 until the
+ * scene has been scored for "lcp_cull_after" point queries: the launch that passes the threshold writes the lines.  n_entries above
+ * counts the plain lists only.  Errors as above; the counts are zeroed. */
+int stocs_get_grid_octants(stocs_ctx* ctx, int64_t* counts3);
 /* The model-side half of that test without a context or a device (host code: what stocs_ctx_create computes): the order in
  * which the scoring kernels walk the model -- perm[slot] = model index, 64 consecutive slots = one compact surface patch --
  * and the bounding sphere of every patch (centre x, y, z in the CENTRED model frame, radius), ceil(nM / 64) of them. */

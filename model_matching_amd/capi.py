@@ -295,6 +295,7 @@ SIGNATURES = {
     "stocs_set_option": (C.c_int, [_vp, C.c_char_p, C.c_int]),
     "stocs_get_cull_state": (C.c_int, [_vp, _fp, _ip, _intp, _fp, _fp, C.c_int64, _i64p]),
     "stocs_get_grid_info": (C.c_int, [_vp, C.POINTER(GridInfo)]),
+    "stocs_get_grid_octants": (C.c_int, [_vp, _i64p]),
     "stocs_model_patch_order": (C.c_int, [_fp, C.c_int, _ip, _fp]),
     "stocs_model_subpatches": (C.c_int, [_fp, C.c_int, _ip, _fp]),
     "stocs_kdtree_nn_host": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_float, _ip]),

@@ -176,7 +176,7 @@ static int upload(T** dptr, const T* h, size_t n) {
 
 static void free_grid(stocs_ctx* c) {   // the grid lives in c->grid_mem, which the next build resets
     c->grid.d_top = NULL; c->grid.d_cells = NULL; c->grid.d_list = NULL; c->grid.d_chunk_r = NULL; c->grid.d_flat = NULL;
-    c->grid.d_dist = NULL; c->grid.dist_ready = false;
+    c->grid.d_dist = NULL; c->grid.dist_ready = false; c->grid.oct_pending = false;
 }
 
 // One build at cell edge eps / div.  At eps the index-ordered lists with the flat cell table and the sub-cell masks (the sparse

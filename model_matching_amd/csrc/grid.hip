@@ -25,6 +25,7 @@
 #include <vector>
 
 #include "normal_cone.h"
+#include "octant_lists.h"
 #include "prims.h"
 #include "stocs_ctx.h"
 
@@ -418,16 +419,65 @@ __global__ __launch_bounds__(256) void prune_kernel(GridGeom G, double hh, doubl
     }
 }
 
+// block != 0 (octant lines, below): a cell that keeps more than one line of entries reserves `block` entries behind its padded list;
+// oct[0] counts those cells
 __global__ __launch_bounds__(256) void cell_padded_kept_kernel(const uint32_t* __restrict__ kept, uint32_t n_cells, uint32_t pad, uint32_t* __restrict__ padded,
-                                                               uint32_t* __restrict__ max_count, unsigned long long* __restrict__ total) {
+                                                               uint32_t* __restrict__ max_count, unsigned long long* __restrict__ total, uint32_t block,
+                                                               uint32_t* __restrict__ oct) {
     const uint32_t c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= n_cells) return;
     const uint32_t cnt = kept[c];
-    padded[c] = (cnt + pad - 1u) & ~(pad - 1u);
+    const bool is_long = block && cnt > STOCS_OCTANT_LINE;
+    padded[c] = ((cnt + pad - 1u) & ~(pad - 1u)) + (is_long ? block : 0u);
+    if (is_long) atomicAdd(&oct[0], 1u);
     atomicMax(max_count, cnt);
     unsigned long long t = cnt;
     for (int off = 32; off > 0; off >>= 1) t += __shfl_xor(t, off, 64);
     if ((threadIdx.x & 63) == 0) atomicAdd(total, t);
+}
+
+// ---------------------------------------------------------------------------------------------
+// Octant lines (octant_lists.h; sparse pruned grids at cell edge epsilon with a flat table).  Behind the plain list of every cell that
+// keeps more than 8 entries, cell_padded_kept_kernel reserved 64 entries: eight lines, one per octant of the cell.  One thread per
+// (cell, octant) -- eight neighbouring lanes per cell -- prunes the cell's STORED list over its octant box and writes the line; when
+// all eight octants fit their lines the cell's word in the FLAT table takes the block's offset under the flag and the count 8.  The brick table and
+// the plain list are not touched: every other reader works as before.  oct[1] counts the flagged cells, oct[2] their octants' entries.
+// ---------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void octant_lines_kernel(GridGeom G, double hw, double margin, const uint64_t* __restrict__ cell_key,
+                                                           const uint32_t* __restrict__ list_off, const uint32_t* __restrict__ kept, uint32_t n_cells,
+                                                           float4* __restrict__ list, uint4* __restrict__ flat, uint32_t* __restrict__ oct) {
+    const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
+    const uint32_t c = t >> 3, o = t & 7u;
+    const uint32_t cnt = c < n_cells ? kept[c] : 0u;
+    uint32_t n = 0, block_off = 0;
+    size_t fidx = 0;
+    bool in_flat = false;
+    if (cnt > STOCS_OCTANT_LINE) {
+        const uint64_t key = cell_key[c];
+        const uint64_t brick = key >> 9;
+        const uint32_t local = (uint32_t)(key & 511);
+        const int bx = (int)(brick % (uint64_t)G.nbx), by = (int)((brick / (uint64_t)G.nbx) % (uint64_t)G.nby), bz = (int)(brick / ((uint64_t)G.nbx * (uint64_t)G.nby));
+        const int cx = bx * 8 + (int)(local & 7), cy = by * 8 + (int)((local >> 3) & 7), cz = bz * 8 + (int)(local >> 6);
+        in_flat = cx < G.n[0] && cy < G.n[1] && cz < G.n[2];
+        fidx = ((size_t)cz * G.n[1] + cy) * G.n[0] + cx;
+        const double ctr[3] = {G.of[0] + (cx + 0.25 + 0.5 * (double)(o & 1u)) * G.h, G.of[1] + (cy + 0.25 + 0.5 * (double)((o >> 1) & 1u)) * G.h,
+                               G.of[2] + (cz + 0.25 + 0.5 * (double)(o >> 2)) * G.h};
+        const uint32_t lo = list_off[c];
+        block_off = lo + ((cnt + 7u) & ~7u);      // (the cell's padded size is this plus the block: cell_padded_kept_kernel)
+        n = octant_line_build(list + lo, cnt, ctr, 0.25 * G.h, hw, G.r, margin, list + block_off + octant_line_start_of_octant(o));
+    }
+    // the eight lanes of a cell agree: every octant fits its line (an empty one keeps the sentinel fill; no mask bit leads there)
+    const unsigned long long over = __ballot(n > STOCS_OCTANT_LINE);
+    const int lane = threadIdx.x & 63;
+    const bool fits = cnt > STOCS_OCTANT_LINE && in_flat && ((over >> (lane & ~7)) & 0xFFull) == 0ull;
+    if (fits) {
+        atomicAdd(&oct[2], n);
+        if (o == 0) {   // the block under the flag, and the length of a line for the count (the cone above it stays)
+            flat[fidx].x = octant_word_pack(block_off);
+            flat[fidx].y = (flat[fidx].y & ~STOCS_CONE_COUNT_MASK) | STOCS_OCTANT_LINE;
+            atomicAdd(&oct[1], 1u);
+        }
+    }
 }
 
 __global__ __launch_bounds__(256) void cell_nearest_store_kernel(const uint64_t* __restrict__ cell_key, const uint32_t* __restrict__ cell_brick, uint32_t n_cells,
@@ -483,6 +533,7 @@ int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
     g.h = (float)h;
     g.n_bricks = 0; g.n_entries = 0; g.avg_list_len = 0; g.has_nearest = false; g.has_cones = false;
     g.div = div; g.sort_kind = 0; g.prune_group = 0; g.prune_k = 0; g.n_inc = 0; g.n_cells = 0; g.longest_list = 0;
+    g.n_long_cells = 0; g.n_octant_cells = 0; g.n_octant_entries = 0; g.oct_pending = false;
     g.d_top = NULL; g.d_cells = NULL; g.d_list = NULL; g.d_chunk_r = NULL; g.d_flat = NULL;
     const int64_t n_top = (int64_t)g.nbx * g.nby * g.nbz;
     if (n_top > (int64_t)400 * 1000 * 1000) { set_error("scene extent too large for the brick grid"); return STOCS_ERR_INVALID; }
@@ -594,6 +645,17 @@ int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
                        d_cell_key, d_cell_brick);
     hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(256), 0, st, (int32_t*)d_max, (size_t)1, 0);
     uint32_t *d_rank = NULL, *d_kept = NULL; float* d_near = NULL; unsigned long long* d_total = NULL;
+    // the flat copy of the cell words (sparse scenes, cell edge epsilon): decided here, built in step 4
+    const size_t n_flat = (size_t)n[0] * n[1] * n[2];
+    const bool want_flat = !dense && div == 1 && c->lcp_flat && n_flat * sizeof(uint4) <= ((size_t)512 << 20);
+    // octant lines behind the long lists of such a grid (octant_lists.h); STOCS_GRID_OCTANTS=0, read per build: a grid without them (A/B
+    // runs, cross-checks).  On by default although the step's drop at Cm (2 to 2.9 %, the faster build in all 30 alternations) cleared
+    // three times the run-to-run range in one visit of three only: the line select in the FLAT forms costs a grid WITHOUT lines 1.4 % against
+    // the parent (five alternations, slower in each), so off is the slower default, not the neutral one.
+    // At most n_inc / 9 cells are long: below 2^24 incidences their blocks stay far below the 2^31 entries an offset can address
+    const bool octants = prune && want_flat && n_inc < ((size_t)1 << 24) && !(getenv("STOCS_GRID_OCTANTS") && atoi(getenv("STOCS_GRID_OCTANTS")) == 0);
+    uint32_t* d_oct = NULL;   // [0] long cells, [1] cells with octant lines, [2] entries of those lines
+    double oct_hw = 0, oct_margin = 0;
     if (prune) {
         if ((rc = T.get(&d_rank, n_inc + 1)) || (rc = T.get(&d_kept, (size_t)n_cells + 1)) || (rc = T.get(&d_near, (size_t)n_cells + 1)) || (rc = T.get(&d_total, 1))) return rc;
         // positions the kernels assign to a cell lie inside its box up to the float rounding of floor((q - o) * inv_h): 3 ulp of the
@@ -610,7 +672,11 @@ int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
 #undef STOCS_PRUNE_LAUNCH
         g.prune_group = short_lists ? 16 : 64;
         g.prune_k = (pk == 4 || pk == 16) ? pk : 8;
-        hipLaunchKernelGGL(cell_padded_kept_kernel, dim3(grid_of(n_cells)), dim3(256), 0, st, d_kept, n_cells, 8u, d_padded, d_max, d_total);
+        if ((rc = T.get(&d_oct, 4))) return rc;
+        hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(256), 0, st, (int32_t*)d_oct, (size_t)4, 0);
+        oct_hw = 0.25 * h + (hh - 0.5 * h); oct_margin = margin;   // the octant box, widened by the slack of the cell box
+        hipLaunchKernelGGL(cell_padded_kept_kernel, dim3(grid_of(n_cells)), dim3(256), 0, st, d_kept, n_cells, 8u, d_padded, d_max, d_total,
+                           octants ? STOCS_OCTANT_BLOCK : 0u, d_oct);
     } else
     hipLaunchKernelGGL(cell_padded_kernel, dim3(grid_of(n_cells)), dim3(256), 0, st, d_cell_first, n_cells, (uint32_t)n_inc, 8u, d_padded, d_max);
     hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(256), 0, st, (int32_t*)(d_padded + n_cells), (size_t)1, 0);
@@ -632,8 +698,7 @@ int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
         return rc;
     hipLaunchKernelGGL(zero_cells_kernel, dim3(grid_of((size_t)n_bricks * 512)), dim3(256), 0, st, g.d_cells, (size_t)n_bricks * 512);
     {   // flat copy of the cell words for the sparse-scene kernel: one look-up per query instead of two dependent ones
-        const size_t n_flat = (size_t)n[0] * n[1] * n[2];
-        if (!dense && div == 1 && c->lcp_flat && n_flat * sizeof(uint4) <= ((size_t)512 << 20)) {
+        if (want_flat) {
             if ((rc = c->grid_mem.take(n_flat * sizeof(uint4), (void**)&g.d_flat))) return rc;
             hipLaunchKernelGGL(zero_cells_kernel, dim3(grid_of(n_flat)), dim3(256), 0, st, g.d_flat, n_flat);
         }
@@ -644,6 +709,17 @@ int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
                        (const uint32_t*)d_rank, (const float4*)c->d_snrmw, g.has_cones ? 1 : 0);
     hipLaunchKernelGGL(list_fill_kernel, dim3(grid_of(n_inc)), dim3(256), 0, st, d_cflag, d_cidx, d_cell_first, d_list_off, d_vals_s, n_inc, c->d_spos, g.d_list, (const uint32_t*)d_rank);
     STOCS_HIP_CHECK(hipGetLastError());
+    uint32_t* oct_counts = rb32 + 5;   // [5..7] long cells, cells with octant lines, their entries
+    for (int k = 0; k < 3; ++k) oct_counts[k] = 0;
+    if (octants) {
+        // The lines themselves are written later, by build_octant_lines, once the scene has been scored often enough for them to pay
+        // (lcp.hip; the threshold of the distance field): the build only reserved their blocks and counts the long cells.  What that
+        // call needs stays where it is until the next build resets the workspace
+        STOCS_HIP_CHECK(hipMemcpyAsync(oct_counts, d_oct, 4, hipMemcpyDeviceToHost, st));   // lands with the build's last synchronisation
+        g.oct_pending = true;
+        g.oct_cell_key = d_cell_key; g.oct_list_off = d_list_off; g.oct_kept = d_kept; g.oct_counts = d_oct; g.oct_n_cells = n_cells;
+        g.oct_h = h; g.oct_r = r; g.oct_hw = oct_hw; g.oct_margin = oct_margin;
+    }
     if (prune && div > 1) {   // no sub-cell masks on grids finer than epsilon: the z word takes the distance bound (has_nearest)
         hipLaunchKernelGGL(cell_nearest_store_kernel, dim3(grid_of(n_cells)), dim3(256), 0, st, d_cell_key, d_cell_brick, n_cells, (const float*)d_near, g.d_cells);
         g.has_nearest = true;
@@ -661,10 +737,41 @@ int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
     }
     STOCS_HIP_CHECK(hipStreamSynchronize(st));
     g.n_bricks = (int)n_bricks;
-    g.n_entries = (int64_t)n_list;
+    // the plain lists only: the octant blocks are not part of what the launch layer weighs (lcp.hip: lists_spill, lists_huge)
+    g.n_long_cells = (int64_t)oct_counts[0]; g.n_octant_cells = (int64_t)oct_counts[1]; g.n_octant_entries = (int64_t)oct_counts[2];
+    g.n_entries = (int64_t)n_list - (int64_t)STOCS_OCTANT_BLOCK * g.n_long_cells;
     g.avg_list_len = n_cells ? (double)n_kept / (double)n_cells : 0.0;
     g.avg_dilated_len = n_cells ? (double)n_inc / (double)n_cells : 0.0;
     g.pruned = prune != 0;
+    return STOCS_OK;
+}
+
+// The octant lines of the current grid (octant_lines_kernel), on the context's stream, once per scene; no-op when the grid has none
+// to build.  Called by the scoring launch that takes the scene's work past the threshold: one kernel over the long cells (0.05 ms
+// at Cm or on a camera frame, as much as a launch of 8 000 candidates takes there -- a frame that is scored once never pays it) and
+// one synchronisation for the two counts of stocs_get_grid_octants.
+int build_octant_lines(stocs_ctx* c) {
+    SceneGrid& g = c->grid;
+    if (!g.oct_pending) return STOCS_OK;
+    g.oct_pending = false;
+    if (!g.d_flat || !g.d_list || g.n_long_cells == 0) return STOCS_OK;
+    GridGeom G;
+    G.of[0] = g.ox; G.of[1] = g.oy; G.of[2] = g.oz;
+    G.h = g.oct_h; G.r = g.oct_r;
+    G.n[0] = g.nx; G.n[1] = g.ny; G.n[2] = g.nz;
+    G.nbx = g.nbx; G.nby = g.nby;
+    G.dense = 0; G.qscale = 0.0;
+    int rc;
+    if ((rc = ensure_pinned(c, PIN_VAR))) return rc;
+    uint32_t* counts = (uint32_t*)((char*)c->h_pin + PIN_BEST + 160) + 5;   // (the build's slots)
+    counts[1] = 0; counts[2] = 0;
+    // eight lanes per cell; cells with one line of entries leave at once
+    hipLaunchKernelGGL(octant_lines_kernel, dim3(grid_of((size_t)g.oct_n_cells * 8)), dim3(256), 0, c->stream, G, g.oct_hw, g.oct_margin, g.oct_cell_key,
+                       g.oct_list_off, g.oct_kept, g.oct_n_cells, g.d_list, g.d_flat, g.oct_counts);
+    STOCS_HIP_CHECK(hipGetLastError());
+    STOCS_HIP_CHECK(hipMemcpyAsync(counts + 1, g.oct_counts + 1, 8, hipMemcpyDeviceToHost, c->stream));
+    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    g.n_octant_cells = (int64_t)counts[1]; g.n_octant_entries = (int64_t)counts[2];
     return STOCS_OK;
 }
 

@@ -39,6 +39,7 @@
 
 #include "kdtree.h"
 #include "normal_cone.h"
+#include "octant_lists.h"
 #include "prims.h"
 #include "stocs_ctx.h"
 
@@ -694,7 +695,11 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
                     if (!STOCS_ABLATE(a, 1))   // 1: no cell-word look-up at all
                         cw = a.flat[(uint32_t)((cz * a.ny + cy) * a.nx + cx)];
                     const uint32_t mw = sb < 32 ? cw.z : cw.w;
-                    off = cw.x; yw = cw.y; cnt = ((mw >> (sb & 31)) & 1u) ? (cw.y & cmask) : 0u;
+                    // a flagged word (only the flat table has them) names the cell's block of octant lines: the query reads the ONE line of
+                    // its octant as a list of 8 entries -- the count such a word carries -- a subset of the cell's list that holds the same
+                    // winner (octant_lists.h)
+                    off = octant_word_flagged(cw.x) ? octant_line_offset(cw.x, (uint32_t)sb) : cw.x;
+                    yw = cw.y; cnt = ((mw >> (sb & 31)) & 1u) ? (cw.y & cmask) : 0u;
                     if (STOCS_ABLATE(a, 2)) cnt = cw.x == 0xFFFFFFF1u ? 1u : 0u;   // 2: look-up done, nobody survives
                 } else {
                     const int brick = a.top[((cz >> 3) * a.nby + (cy >> 3)) * a.nbx + (cx >> 3)];
@@ -1200,6 +1205,10 @@ int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d
         a.gox = c->grid.cg_ox; a.goy = c->grid.cg_oy; a.goz = c->grid.cg_oz; a.g = c->grid.cg_g; a.inv_g = c->grid.cg_inv_g; a.cap = c->grid.cg_cap;
         a.gnx = c->grid.cg_nx; a.gny = c->grid.cg_ny; a.gnz = c->grid.cg_nz;
     }
+    // octant lines of the long cells (octant_lists.h): like the distance field they cost about what one launch of 8 000 candidates takes
+    // and pay on big batches (-2 to -2.9 % at Cm; STOCS_GRID_OCTANTS=0 builds a grid without them), so they are written once the scene has seen the same amount of work, whatever lcp_cull says.
+    // The scores do not depend on them
+    if (c->grid.oct_pending && c->scene_work >= c->lcp_cull_after) { int rc = build_octant_lines(c); if (rc) return rc; }
     a.order = NULL; a.xcd_blocks = 0;
     // big batches against scenes whose lists do not stay in the caches: spatially ordered processing (the ordering costs ~50 us; scores
     // do not depend on it).  Until the first half of round 3 it paid at Cm too (1.67 -> 1.44 ms in round 1); with the four-lane verify
@@ -1557,6 +1566,15 @@ int stocs_get_grid_info(stocs_ctx* c, stocs_grid_info* info) {
     info->has_flat = g.d_flat != NULL;
     info->sort = g.sort_kind; info->prune_group = g.prune_group; info->prune_k = g.prune_k; info->longest_list = g.longest_list;
     info->n_incidences = g.n_inc; info->n_cells = g.n_cells; info->n_bricks = g.n_bricks; info->n_entries = g.n_entries;
+    return STOCS_OK;
+}
+
+int stocs_get_grid_octants(stocs_ctx* c, int64_t* counts3) {
+    if (!c || !counts3) { set_error("stocs_get_grid_octants: NULL %s", !c ? "context" : "counts"); return STOCS_ERR_INVALID; }
+    counts3[0] = 0; counts3[1] = 0; counts3[2] = 0;
+    const SceneGrid& g = c->grid;
+    if (c->nS <= 0 || !g.d_top) { set_error("stocs_get_grid_octants: no scene"); return STOCS_ERR_STATE; }
+    counts3[0] = g.n_long_cells; counts3[1] = g.n_octant_cells; counts3[2] = g.n_octant_entries;
     return STOCS_OK;
 }
 

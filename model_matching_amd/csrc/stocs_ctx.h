@@ -172,6 +172,14 @@ struct SceneGrid {
     int64_t n_inc;         // (cell, point) incidences
     int64_t n_cells;       // non-empty cells
     int longest_list;      // entries of the longest stored list (before padding)
+    // octant lines (octant_lists.h): cells whose stored list is longer than a line, those of them whose flat-table word names an octant
+    // block, and the entries of their octant lines before padding; all 0 on a grid without them.  n_entries counts the plain lists only
+    int64_t n_long_cells, n_octant_cells, n_octant_entries;
+    // the lines are written by build_octant_lines once the scene's scoring work makes them pay (lcp.hip); until then: what that call needs
+    // of the build (its temporaries stay in the build's workspace until the next build)
+    bool oct_pending;
+    const uint64_t* oct_cell_key; const uint32_t* oct_list_off; const uint32_t* oct_kept; uint32_t* oct_counts; uint32_t oct_n_cells;
+    double oct_h, oct_r, oct_hw, oct_margin;
     int32_t* d_top;     // nbx*nby*nbz -> brick id or -1
     uint4* d_flat;       // the same cell words addressed directly, (cz*ny + cy)*nx + cx, when the box is small enough (sparse
                          // scenes, cell edge eps): saves the LCP kernel the dependent `top` look-up; else NULL
@@ -453,6 +461,7 @@ int sample_trials(stocs_ctx* c, int mode, int nT, const uint64_t* seeds, int nA,
 int build_ppf_index(stocs_ctx* c);
 int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune);
 int prepare_cull_field(stocs_ctx* c);   // geometry + memory of SceneGrid::d_dist for the current grid and model (end of a grid build)
+int build_octant_lines(stocs_ctx* c);                          // the octant lines of the current grid, on c->stream, once per scene (grid.hip)
 int fill_cull_field(stocs_ctx* c, hipStream_t st = NULL);      // the values, on st (NULL: c->stream); no synchronisation
 // congruent.hip, the device side of stocs_make_transforms: the bases used whole materialised and sorted, then picks -> jobs (see there)
 extern "C" int stocs_internal_prepare_small(stocs_ctx* c, int max_per_base);

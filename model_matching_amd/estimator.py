@@ -955,6 +955,10 @@ class StocsEstimator:
         d["h"] = np.float32(gi.h); d["inv_h"] = np.float32(gi.inv_h)
         d["cells"] = tuple(gi.cells); d["bricks"] = tuple(gi.bricks)
         del d["reserved"]
+        # the octant lines of the grid (stocs_get_grid_octants): cells with more than a line of entries, those that got octant lines, their entries
+        oc = (C.c_int64 * 3)()
+        capi.check(self.L.stocs_get_grid_octants(self.h, oc))
+        d["long_cells"], d["octant_cells"], d["octant_entries"] = int(oc[0]), int(oc[1]), int(oc[2])
         return d
 
     def set_option(self, key, value):
