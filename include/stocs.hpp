@@ -941,6 +941,26 @@ public:
         return r;
     }
 
+    // explain_poses on the mesh of set_mesh (stocs_explain_poses_mesh): the same records, labels and state from the exact surface; of prm
+    // only tolerance and class_threshold are read.  Empty on error (the text goes to the log).
+    std::vector<stocs_render_result> explain_poses_mesh(const std::vector<PoseCandidate*>& poses, std::vector<int32_t>* labels = NULL,
+                                                        std::vector<uint8_t>* state = NULL, const stocs_render_params& prm = default_render_params()) {
+        const int n = (int)poses.size();
+        std::vector<float> P((size_t)n * 16);
+        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], poses[(size_t)i]->transform.data(), 64);
+        std::vector<stocs_render_result> r((size_t)n);
+        const size_t npix = (size_t)image_width * (size_t)image_height;
+        if (labels) labels->assign(npix, -1);
+        if (labels && state) state->assign(npix, 0);
+        if (stocs_explain_poses_mesh(ctx_, P.data(), n, &prm, r.data(), labels ? labels->data() : NULL, labels && state ? state->data() : NULL) != STOCS_OK) {
+            *log_ << "explain_poses_mesh failed: " << stocs_last_error() << std::endl;
+            r.clear();
+            if (labels) labels->clear();
+            if (state) state->clear();
+        }
+        return r;
+    }
+
     // Multi-instance selection (stocs_select_instances; no reference counterpart): which of the camera-frame hypotheses (the
     // hypotheses of run_trials, refined or not) are distinct instances of the object and which are one instance found twice.  Walked
     // best first, a hypothesis is kept only if enough of the scene points it explains are explained by none kept before it.  One record
@@ -1000,6 +1020,19 @@ public:
         std::vector<stocs_scene_record> r((size_t)n);
         if (n > 0 && stocs_scene_footprints(ctx_, P.data(), n, slot_base, n_slots, &prm, claim, d_rows, r.data()) != STOCS_OK) {
             *log_ << "scene_footprints failed: " << stocs_last_error() << std::endl;
+            r.clear();
+        }
+        return r;
+    }
+    // scene_footprints from the mesh of set_mesh (stocs_scene_footprints_mesh): the same rows and records; a pool may mix both kinds
+    std::vector<stocs_scene_record> scene_footprints_mesh(const std::vector<PoseCandidate*>& poses, void* d_rows, int slot_base, int n_slots, int claim = 0,
+                                                          const stocs_render_params& prm = default_render_params()) {
+        const int n = (int)poses.size();
+        std::vector<float> P((size_t)n * 16);
+        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], poses[(size_t)i]->transform.data(), 64);
+        std::vector<stocs_scene_record> r((size_t)n);
+        if (n > 0 && stocs_scene_footprints_mesh(ctx_, P.data(), n, slot_base, n_slots, &prm, claim, d_rows, r.data()) != STOCS_OK) {
+            *log_ << "scene_footprints_mesh failed: " << stocs_last_error() << std::endl;
             r.clear();
         }
         return r;
@@ -1249,13 +1282,18 @@ struct SceneSelection {
     std::vector<int32_t> labels;                   // with_labels: -1 or the slot that owns the pixel
     std::vector<uint8_t> state;
 };
+// The surface an object's footprints and masks are taken from: its model points as splats, or the mesh of its estimator's set_mesh
+enum SceneSurface { SURFACE_POINTS = 0, SURFACE_MESH = 1 };
+// ... with a surface per object (empty: all points): a SURFACE_MESH object goes through scene_footprints_mesh and, with_labels,
+// stocs_render_poses_mesh; both kinds share the pool and the key buffer
 inline SceneSelection select_scene(const std::vector<stocs_estimator*>& estimators, const std::vector<std::vector<PoseCandidate*> >& poses,
-                                   const std::vector<int>& max_per_object = std::vector<int>(), bool with_labels = false,
+                                   const std::vector<SceneSurface>& surface, const std::vector<int>& max_per_object = std::vector<int>(), bool with_labels = false,
                                    const stocs_scene_params& prm = stocs_estimator::default_scene_params(),
                                    const stocs_render_params& render = stocs_estimator::default_render_params(), int claim = 0) {
     SceneSelection out;
     out.ok = false;
     if (estimators.empty() || estimators.size() != poses.size()) throw std::runtime_error("select_scene: one pose set per estimator");
+    if (!surface.empty() && surface.size() != estimators.size()) throw std::runtime_error("select_scene: one surface per object");
     if (!max_per_object.empty() && max_per_object.size() != 1 && max_per_object.size() != estimators.size()) throw std::runtime_error("select_scene: one cap, or one per object");
     stocs_estimator& first = *estimators[0];
     const int W = first.frame_width(), H = first.frame_height();
@@ -1272,7 +1310,9 @@ inline SceneSelection select_scene(const std::vector<stocs_estimator*>& estimato
     bool good = true;
     int base = 0;
     for (size_t k = 0; good && k < poses.size(); ++k) {
-        const std::vector<stocs_scene_record> r = estimators[k]->scene_footprints(poses[k], d_rows, base, n, claim, render);
+        const bool mesh = !surface.empty() && surface[k] == SURFACE_MESH;
+        const std::vector<stocs_scene_record> r = mesh ? estimators[k]->scene_footprints_mesh(poses[k], d_rows, base, n, claim, render)
+                                                       : estimators[k]->scene_footprints(poses[k], d_rows, base, n, claim, render);
         good = r.size() == poses[k].size();
         out.footprints.insert(out.footprints.end(), r.begin(), r.end());
         base += (int)poses[k].size();
@@ -1298,7 +1338,10 @@ inline SceneSelection select_scene(const std::vector<stocs_estimator*>& estimato
             for (size_t r = 0; good && r < out.selected.size(); ++r) {
                 const int s = out.selected[r];
                 PoseCandidate* pc = poses[(size_t)out.group[(size_t)s]][(size_t)out.index[(size_t)s]];
-                good = stocs_render_poses(estimators[(size_t)out.group[(size_t)s]]->context(), pc->transform.data(), 1, s, &render, d_zkey, r == 0 ? 1 : 0) == STOCS_OK;
+                const size_t g = (size_t)out.group[(size_t)s];
+                good = (!surface.empty() && surface[g] == SURFACE_MESH
+                            ? stocs_render_poses_mesh(estimators[g]->context(), pc->transform.data(), 1, s, d_zkey, r == 0 ? 1 : 0)
+                            : stocs_render_poses(estimators[g]->context(), pc->transform.data(), 1, s, &render, d_zkey, r == 0 ? 1 : 0)) == STOCS_OK;
             }
             good = good && stocs_render_labels(first.context(), d_zkey, &render, out.labels.data(), out.state.data()) == STOCS_OK;
         }
@@ -1308,6 +1351,12 @@ inline SceneSelection select_scene(const std::vector<stocs_estimator*>& estimato
     stocs_dev_free(first.context(), d_rows);
     out.ok = good;
     return out;
+}
+inline SceneSelection select_scene(const std::vector<stocs_estimator*>& estimators, const std::vector<std::vector<PoseCandidate*> >& poses,
+                                   const std::vector<int>& max_per_object = std::vector<int>(), bool with_labels = false,
+                                   const stocs_scene_params& prm = stocs_estimator::default_scene_params(),
+                                   const stocs_render_params& render = stocs_estimator::default_render_params(), int claim = 0) {
+    return select_scene(estimators, poses, std::vector<SceneSurface>(), max_per_object, with_labels, prm, render, claim);
 }
 
 // Not in the reference (its driver runs once per object): every object of one frame from one ingest (stocs_ingest_scene_multi).

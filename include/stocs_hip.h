@@ -1152,6 +1152,61 @@ int stocs_pose_errors_vsd_mesh(stocs_ctx* ctx, const float* est_pose16_camera, i
                                const stocs_vsd_params* p, stocs_vsd_record* out);
 int stocs_mesh_last_call_timing(const stocs_ctx* ctx, const char** labels, double* ms, int cap, int* n);
 
+/* ---- the mesh in the joint renderer and in scene selection: exact masks (no reference counterpart).  The splats of the render contract
+ * pad a silhouette by up to point_radius, stand at the constant depth of their centre, let a far-side point of a sparse model through
+ * between near-side ones and need a radius chosen per model.  These entry points make the same judgements -- instance masks, what hides
+ * what, agreement with the depth image, the pixel rows stocs_scene_select walks -- on the mesh of stocs_ctx_set_mesh.  csrc/render_mesh.hip,
+ * restated in float32 numpy in tests/render_mesh_ref.py as a composition of tests/mesh_ref.py, render_ref.py and scene_ref.py, equal bit
+ * for bit.
+ * Z_h: the image of float bits that stocs_render_depth_mesh defines for pose h ALONE against the frame of stocs_ctx_set_frame: steps 1-4
+ * of the mesh contract above, unchanged; empty is all ones.  Everything below is defined through Z_h.  Poses are CAMERA-frame and
+ * column-major; a pose with a non-finite entry among its twelve used entries, or the all-zero "no pose" record, renders nothing, gets a
+ * zero record (and a zero row) and is no error.  The key buffer, the ids (id = id_base + h, id_base >= 0, id_base + n <= 2^31 - 1) and
+ * the `clear` rule are those of stocs_render_poses.
+ *   1. stocs_render_poses_mesh: every pixel where Z_h is not empty gets key = min(key, (uint64_t)Z_h << 32 | (id_base + h)).  The nearest
+ *      surface wins and on an equal depth the lower id; a minimum: the result depends on neither order, batch, kernel form nor the
+ *      sequence of calls.  Splat renders and mesh renders, of this or of other contexts, may share one buffer.  Synchronises its stream
+ *      before it returns.  It takes no stocs_render_params: nothing in the mesh rule has a radius.
+ *   2. stocs_render_resolve_mesh: called with the same poses and ids after every render into the buffer is done.  C_h is the set of
+ *      non-empty pixels of Z_h, footprint = |C_h|.  A pixel of C_h whose key's low word is not h's id is hidden (an empty key too);
+ *      otherwise it is visible and classified by steps 5-6 of the depth-check contract with p_2 := the float in the key's high word.
+ *      The record is stocs_render_result with the identities stated there.  Of p only tolerance and class_threshold are read and checked;
+ *      point_radius and max_splat_px are ignored, whatever they hold (as stocs_pose_errors_vsd_mesh ignores the surfel fields).  There is
+ *      no 2^19-pixel cap: the footprint is no bitset in LDS.
+ *   3. stocs_explain_poses_mesh, the single-object form, exactly as stocs_explain_poses: the context's own key buffer, id_base 0; clear,
+ *      render, resolve, and labels / state when `labels` is given.  One pinned read-back and one synchronisation per call.  n == 0 with
+ *      labels given returns the all-empty image (it needs the frame for its size, neither a mesh nor anything else).
+ *   4. stocs_scene_footprints_mesh: stocs_scene_footprints with Z_h from the mesh in place of the splat minimum: the same classification,
+ *      rows (the whole row is always written) and stocs_scene_record, the 2^19 cap, the chunk rule and STOCS_SCENE_CHUNK.  The record of h
+ *      equals the record stocs_explain_poses_mesh gives for that pose alone (hidden == 0, visible == footprint).  A pool may hold splat
+ *      slots and mesh slots side by side; stocs_scene_select does not know the difference.
+ * stocs_render_labels serves both kinds of buffer, unchanged.
+ * Checked in the order of the splat counterparts: NULL ctx and n < 0 (STOCS_ERR_INVALID); n == 0 is a no-op (stocs_explain_poses_mesh:
+ * unless labels are given); NULL poses / p / key buffer / rows / out; claim, slots; tolerance and class_threshold outside the ranges of
+ * stocs_render_params; an id outside 0 .. 2^31 - 2: STOCS_ERR_INVALID.  Then a context without a mesh: STOCS_ERR_STATE; then the frame
+ * (STOCS_ERR_STATE) and, for stocs_scene_footprints_mesh, npix > 2^19: STOCS_ERR_CAPACITY.
+ * Every entry point has its own grow-only workspace on the context (a second call of the same or a smaller size allocates nothing);
+ * poses go up and results come back through the context's pinned block, everything runs on the context's stream.
+ * The kernels.  Render: mesh.hip's rasteriser (one triangle per lane for the set-up; lane, wavefront and workgroup tiers; the same
+ * STOCS_MESH_FORM bits) with a 64-bit sink: all poses of the launch write the one buffer, one 64-bit atomicMin per hit pixel, the id in a
+ * scalar register.  Resolve: every pose of a chunk is rendered alone into a z-buffer of its own by the depth form of the rasteriser
+ * (chunks of 256 MB of z-buffers; STOCS_RENDER_MESH_CHUNK=<poses> in the environment forces a size), then one kernel walks the rows of
+ * each pose's bounding rectangle in runs of 64 pixels: a 4-byte load of the pose's own depth, where present an 8-byte load of the key,
+ * counts by __ballot and popcount, one integer atomicAdd per counter and workgroup; several workgroups per pose.  Scene footprints: the
+ * depth form into the chunk's z-buffers, then stocs_scene_footprints' classify kernel as it stands.
+ * stocs_render_mesh_last_device_ms: with the option "device_clock" on, the HIP-event time in ms of the key render and of the (last
+ * chunk's) resolve kernel of the last call of 1-3 on this context; -1 for what that call did not run or did not time.
+ * Known limits: resolve rasterises every pose a second time (the key buffer keeps only the winners' depths); the depth check
+ * (stocs_depth_check_poses), trial batches and the tracker still see the model as points. ---- */
+int stocs_render_poses_mesh(stocs_ctx* ctx, const float* pose16_camera, int n, int id_base, void* d_zkey, int clear);
+int stocs_render_resolve_mesh(stocs_ctx* ctx, const float* pose16_camera, int n, int id_base, const stocs_render_params* p, const void* d_zkey,
+                              stocs_render_result* out);
+int stocs_explain_poses_mesh(stocs_ctx* ctx, const float* pose16_camera, int n, const stocs_render_params* p, stocs_render_result* out,
+                             int32_t* labels, uint8_t* state);
+int stocs_scene_footprints_mesh(stocs_ctx* ctx, const float* pose16_camera, int n, int slot_base, int n_slots, const stocs_render_params* p,
+                                int claim, void* d_rows, stocs_scene_record* out);
+int stocs_render_mesh_last_device_ms(const stocs_ctx* ctx, float* key_ms, float* resolve_ms);
+
 /* ---- mesh models: a triangle mesh sampled into the oriented model cloud the search needs (no reference counterpart).  Stand-alone like
  * stocs_preprocess_model: no context; the same cached per-thread workspace and pinned block (stocs_trim gives them back; a second call of
  * the same or a smaller size allocates nothing).  csrc/mesh_sample.hip, restated in numpy in tests/mesh_sample_ref.py, equal bit for bit.

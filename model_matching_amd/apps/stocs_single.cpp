@@ -69,6 +69,9 @@
 // entry, the selected ones first in rank order (r = rank), then the others in pool order (r = -1), and the same entries with their poses
 // to <scene>/scene_selection.txt.  With --masks the selected poses of all objects are rendered into one key buffer and the label image
 // goes to <scene>/labels_scene.pgm (value = pool slot + 1, 0 = nobody; the format of labels_<object>.pgm).
+// --surface points|mesh (default points; mesh needs --mesh <ply> and --masks with --instances M, refused before any search otherwise): with
+// mesh the "mask r:" lines and the label image come from the exact rasteriser on that mesh (stocs_explain_poses_mesh) and every line ends
+// in " mesh=<triangles>".  --mesh then needs no --vsd.  Several objects with --scene-select stay on points: one mesh file names one object.
 // --masks (with --instances M, a scene directory): the selected instances, in rank order, rendered together against the frame's depth image
 // and class-probability map (stocs_explain_poses); one "mask r: footprint .. visible .. hidden .. agree .. in_front .. behind .. no_depth ..
 // on_mask .." line per instance, and the label image to labels_<object>.pgm next to <out>: binary 16-bit PGM (P5, maxval 65535, most
@@ -127,6 +130,8 @@ static bool read_stcl(const std::string& path, std::vector<float>& pos, std::vec
 }
 
 // everything after the estimator is built (:79-185): one run, or n_trials in one batch; lines to os, the pose to out_path
+static int g_mask_mesh_triangles = 0;   // --surface mesh: the triangles of the mesh set on the estimator; 0: the masks come from the model points
+
 static int run_search(stocs::stocs_estimator& stocs_ptr, std::ostream& os, const std::string& out_path, const std::string& dbg_dir, uint64_t seed, int n_trials,
                       int exact_ties, int do_cluster, int n_refine, int depth_check = 0, const stocs_instance_params* instances = NULL,
                       const std::string& instances_path = std::string(), const std::string& labels_path = std::string(),
@@ -255,12 +260,13 @@ static int run_search(stocs::stocs_estimator& stocs_ptr, std::ostream& os, const
                 std::vector<PoseCandidate*> chosen;
                 for (size_t r = 0; r < sel.size(); ++r) chosen.push_back(flat[(size_t)sel[r]]);
                 std::vector<int32_t> labels;
-                const std::vector<stocs_render_result> mr = stocs_ptr.explain_poses(chosen, &labels);
+                const std::vector<stocs_render_result> mr = g_mask_mesh_triangles > 0 ? stocs_ptr.explain_poses_mesh(chosen, &labels) : stocs_ptr.explain_poses(chosen, &labels);
                 if (mr.size() != chosen.size() || labels.empty()) { std::cerr << "mask rendering failed: " << stocs_last_error() << std::endl; return 2; }
                 for (size_t r = 0; r < mr.size(); ++r) {
                     char b[256];
-                    snprintf(b, sizeof(b), "mask %d: footprint %d visible %d hidden %d agree %d in_front %d behind %d no_depth %d on_mask %d", (int)r, mr[r].footprint,
-                             mr[r].visible, mr[r].hidden, mr[r].agree, mr[r].in_front, mr[r].behind, mr[r].no_depth, mr[r].on_mask);
+                    int at = snprintf(b, sizeof(b), "mask %d: footprint %d visible %d hidden %d agree %d in_front %d behind %d no_depth %d on_mask %d", (int)r, mr[r].footprint,
+                                      mr[r].visible, mr[r].hidden, mr[r].agree, mr[r].in_front, mr[r].behind, mr[r].no_depth, mr[r].on_mask);
+                    if (g_mask_mesh_triangles > 0) snprintf(b + at, sizeof(b) - (size_t)at, " mesh=%d", g_mask_mesh_triangles);
                     os << b << std::endl;
                 }
                 std::vector<unsigned char> px(labels.size() * 2);
@@ -667,7 +673,7 @@ int main(int argc, char** argv) {
     bool do_instances = false, do_masks = false, have_trim = false, have_gate = false;
     SceneSelectOptions scene_opt = {false, false, 0};
     VsdOptions vsd_opt = {false, 0.0f, 0.0f, 0};
-    std::string mesh_path;
+    std::string mesh_path, surface = "points";
     bool have_vsd_delta = false, have_surfel_radius = false;
     stocs_instance_params inst_prm = stocs::stocs_estimator::default_instance_params();
     uint64_t seed = 1;
@@ -708,6 +714,7 @@ int main(int argc, char** argv) {
         else if (k == "--sym-file") sym_path = v;
         else if (k == "--vsd-delta") { vsd_opt.delta = (float)atof(v.c_str()); have_vsd_delta = true; }
         else if (k == "--surfel-radius") { vsd_opt.surfel_radius = (float)atof(v.c_str()); have_surfel_radius = true; }
+        else if (k == "--surface") surface = v;   // points | mesh: what --masks renders
         else if (k == "--mesh") mesh_path = v;   // with --vsd: the model as a triangle mesh, rasterised in place of the surfels
         else if (k == "--instances") { do_instances = true; inst_prm.max_instances = atoi(v.c_str()); }
         else if (k == "--instance-min-fraction") inst_prm.min_exclusive_fraction = (float)atof(v.c_str());
@@ -739,8 +746,14 @@ int main(int argc, char** argv) {
 
     std::vector<float> mesh_v;
     std::vector<int32_t> mesh_t;
+    if (surface != "points" && surface != "mesh") { std::cerr << "--surface takes points or mesh" << std::endl; return -1; }
+    const bool surface_mesh = surface == "mesh";
+    if (surface_mesh && (mesh_path.empty() || !do_masks || !do_instances || clouds || a2.find(',') != std::string::npos)) {   // refused before any search
+        std::cerr << "--surface mesh needs --mesh <ply>, --masks with --instances M, a scene directory and a single object" << std::endl;
+        return -1;
+    }
     if (!mesh_path.empty()) {   // refused before any search
-        if (!vsd_opt.on || have_surfel_radius) { std::cerr << "--mesh <ply> needs --vsd and takes no --surfel-radius" << std::endl; return -1; }
+        if ((!vsd_opt.on && !surface_mesh) || have_surfel_radius) { std::cerr << "--mesh <ply> needs --vsd and takes no --surfel-radius" << std::endl; return -1; }
         int nv = 0, nt = 0;
         if (stocs_ply_read_mesh(mesh_path.c_str(), NULL, 0, &nv, NULL, 0, &nt) != STOCS_OK) { std::cerr << "cannot read a mesh from " << mesh_path << ": " << stocs_last_error() << std::endl; return 1; }
         if (nt < 1) { std::cerr << mesh_path << " has no faces" << std::endl; return 1; }
@@ -749,7 +762,8 @@ int main(int argc, char** argv) {
             std::cerr << "cannot read a mesh from " << mesh_path << ": " << stocs_last_error() << std::endl;
             return 1;
         }
-        vsd_opt.mesh_triangles = nt;
+        if (vsd_opt.on) vsd_opt.mesh_triangles = nt;
+        if (surface_mesh) g_mask_mesh_triangles = nt;
     }
     if (vsd_opt.on || have_vsd_delta || have_surfel_radius) {   // refused before any search
         if (!vsd_opt.on || gt_path.empty() || clouds || a2.find(',') != std::string::npos) {
@@ -876,6 +890,7 @@ int main(int argc, char** argv) {
         if (do_masks) labels_path = (sl == std::string::npos ? std::string() : out_path.substr(0, sl + 1)) + "labels_" + object + ".pgm";
     }
     std::vector<stocs::stocs_estimator::TrialResult> trial_results;
+    if (g_mask_mesh_triangles > 0 && !est->set_mesh(mesh_v, mesh_t)) { std::cerr << "set_mesh failed: " << stocs_last_error() << std::endl; return 2; }
     // --gt scores the pose file THIS run writes: one left at out_path by an earlier run must not stand in for it when this run finds no pose
     if (!gt_path.empty()) std::remove(out_path.c_str());
     const int rc = !track_path.empty() ? run_track(*est, track_path, track_min_lcp, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine, &trial_results)

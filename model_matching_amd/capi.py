@@ -258,6 +258,11 @@ SIGNATURES = {
     "stocs_render_depth_mesh": (C.c_int, [_vp, _fp, C.c_int, _fp]),
     "stocs_pose_errors_vsd_mesh": (C.c_int, [_vp, _fp, C.c_int, _fp, C.c_int, C.POINTER(VsdParams), C.POINTER(VsdRecord)]),
     "stocs_mesh_last_call_timing": (C.c_int, [_vp, C.POINTER(C.c_char_p), C.POINTER(C.c_double), C.c_int, _intp]),
+    "stocs_render_poses_mesh": (C.c_int, [_vp, _fp, C.c_int, C.c_int, _vp, C.c_int]),
+    "stocs_render_resolve_mesh": (C.c_int, [_vp, _fp, C.c_int, C.c_int, C.POINTER(RenderParams), _vp, C.POINTER(RenderResult)]),
+    "stocs_explain_poses_mesh": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(RenderParams), C.POINTER(RenderResult), _ip, _u8p]),
+    "stocs_scene_footprints_mesh": (C.c_int, [_vp, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(RenderParams), C.c_int, _vp, C.POINTER(SceneRecord)]),
+    "stocs_render_mesh_last_device_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "stocs_mesh_sample_counts": (C.c_int, [_fp, C.c_int, _ip, C.c_int, C.c_float, C.c_uint64, C.c_int, _ip, C.POINTER(C.c_double), _i64p, _intp]),
     "stocs_mesh_sample": (C.c_int, [_fp, C.c_int, _ip, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, _fp, _fp, _ip, C.c_int, _intp]),
     "stocs_preprocess_model_mesh": (C.c_int, [_fp, C.c_int, _ip, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_float, C.c_float, C.c_int, _fp, _fp, C.c_int, _intp]),

@@ -5,7 +5,10 @@
 // batch, chunk or kernel form (which corner a triangle starts with may change the last bits of its depths, never its pixels: the contract).
 //
 // Everything around the render is vsd.hip's (vsd_shared.h): the chunks of z-buffers, the per-pose rectangles, the clears, the compare
-// kernel and the record read-back.  This file only fills z-buffers.
+// kernel and the record read-back.  This file only fills z-buffers -- and, for render_mesh.hip (render_shared.h), key buffers: the kernel
+// and its helpers are templates on the pixel sink, DepthSink (a z-buffer of float bits per pose, 32-bit atomicMin) or KeySink (one buffer
+// of (float bits << 32 | id) for all poses of the launch, 64-bit atomicMin, the id in a scalar register).  The set-up, the tiers and the
+// forms below are the same text for both.
 //   render    mesh_render_kernel: a workgroup of four wavefronts per (pose, 256 triangles), the pose in scalar registers.  A wavefront sets up
 //             64 triangles, one per lane: three vertex gathers, the transform, the clamped box, the three edge normals.  Then per triangle:
 //               small   a box of at most STOCS_MESH_SMALL_PX pixels: its lane walks it (a dense mesh: a handful of pixels per triangle, and
@@ -15,7 +18,7 @@
 //                       covers the box's width (at most 64): no division, no cap on the box
 //               group   boxes above MESH_GROUP_PX pixels are put into LDS and, behind a barrier, swept by the four wavefronts together in
 //                       tiles of tw x 256 / tw (a CAD model's face is thousands of passes of one wavefront)
-//             One 32-bit atomicMin per hit pixel, blind or behind a read of the stored depth (the stored value only falls, so a stale read
+//             One atomicMin per hit pixel (32-bit depths or 64-bit keys: the sink), blind or behind a read of the stored value (the stored value only falls, so a stale read
 //             costs an atomic and never a result).  Each wavefront adds its triangles' boxes to the pose's rectangle: four atomicMax.
 // STOCS_MESH_FORM=<bits> forces forms (mesh_form below); every form gives the same bits.
 // Known limits: no near-plane clipping (a triangle with a vertex at or behind z = 1e-6 renders nothing); a group box is swept by one
@@ -29,8 +32,7 @@
 
 #include "mesh_sample.h"
 #include "pose_error_math.h"
-#include "render_rules.h"
-#include "vsd_shared.h"
+#include "render_shared.h"
 #include "wave_bits.h"
 
 namespace stocs {
@@ -52,8 +54,35 @@ struct MeshTri {
     int c_lo, c_hi, r_lo, r_hi;
 };
 
+// Where a hit pixel goes.  The kernel and its helpers are templates on the sink; it is made per workgroup from the launch's Target and the
+// pose blockIdx.y, so what it holds is uniform (scalar registers).
+// DepthSink: pose h of the launch has its own z-buffer at zbuf + h * npix, a minimum of float bits (stocs_render_depth_mesh)
+struct DepthSink {
+    typedef uint32_t* Target;
+    uint32_t* z;
+    __device__ __forceinline__ DepthSink(Target zbuf, int h, size_t npix) : z(zbuf + (size_t)h * npix) {}
+    __device__ __forceinline__ void hit(size_t px, uint32_t bits, int read_first) const {
+        uint32_t* cell = &z[px];
+        if (!read_first || bits < *cell) atomicMin(cell, bits);
+    }
+};
+// KeySink: every pose of the launch writes the one key buffer of stocs_render_poses_mesh, a minimum of (float bits << 32 | id)
+struct KeyTarget { unsigned long long* zkey; int id_base; };
+struct KeySink {
+    typedef KeyTarget Target;
+    unsigned long long* z;
+    unsigned long long id;
+    __device__ __forceinline__ KeySink(Target t, int h, size_t) : z(t.zkey), id((unsigned long long)(unsigned)(t.id_base + h)) {}
+    __device__ __forceinline__ void hit(size_t px, uint32_t bits, int read_first) const {
+        unsigned long long* cell = &z[px];
+        const unsigned long long key = ((unsigned long long)bits << 32) | id;
+        if (!read_first || key < *cell) atomicMin(cell, key);
+    }
+};
+
 // step 4 of the contract for pixel (r, c), 0 <= r < H, 0 <= c < W
-__device__ __forceinline__ void mesh_pixel(uint32_t* z, const DepthArgs& a, int read_first, int r, int c, const MeshTri& t) {
+template <class Sink>
+__device__ __forceinline__ void mesh_pixel(const Sink& z, const DepthArgs& a, int read_first, int r, int c, const MeshTri& t) {
     const float xn = ((float)c - a.cx) / a.fx, yn = ((float)r - a.cy) / a.fy;
     const float u = xn * t.a0 + (yn * t.a1 + t.a2);
     const float v = xn * t.b0 + (yn * t.b1 + t.b2);
@@ -63,13 +92,12 @@ __device__ __forceinline__ void mesh_pixel(uint32_t* z, const DepthArgs& a, int 
     if (!inside || !(det != 0.0f)) return;
     const float zz = (u * t.za + (v * t.zb + w * t.zc)) / det;
     if (!(zz > 1e-6f)) return;
-    uint32_t* cell = &z[(size_t)r * (size_t)a.W + (size_t)c];
-    const uint32_t bits = __float_as_uint(zz);
-    if (!read_first || bits < *cell) atomicMin(cell, bits);
+    z.hit((size_t)r * (size_t)a.W + (size_t)c, __float_as_uint(zz), read_first);
 }
 
 // T = 1 << log_t threads (tid among them) sweep the box of t, whose values are uniform over them: tiles of tw x T / tw pixels
-__device__ __forceinline__ void mesh_sweep(uint32_t* z, const DepthArgs& a, int read_first, int tid, int log_t, const MeshTri& t) {
+template <class Sink>
+__device__ __forceinline__ void mesh_sweep(const Sink& z, const DepthArgs& a, int read_first, int tid, int log_t, const MeshTri& t) {
     const int w = t.c_hi - t.c_lo + 1;
     int log_w = 0;
     while (log_w < 6 && (1 << log_w) < w) ++log_w;   // uniform: at most six rounds
@@ -86,9 +114,10 @@ __device__ __forceinline__ void mesh_sweep(uint32_t* z, const DepthArgs& a, int 
 
 __device__ __forceinline__ float uniform_f(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 
-// zbuf: the z-buffer of pose blockIdx.y of the launch at zbuf + blockIdx.y * npix, its rectangle at box + blockIdx.y * VSD_BOX_WORDS
+// target: where pose blockIdx.y of the launch writes (DepthSink, KeySink); its rectangle at box + blockIdx.y * VSD_BOX_WORDS
+template <class Sink>
 __global__ __launch_bounds__(256) void mesh_render_kernel(const float* __restrict__ poses, const float4* __restrict__ verts, const int4* __restrict__ tris, DepthArgs a, MeshArgs ma,
-                                                          uint32_t* zbuf, int32_t* __restrict__ box) {
+                                                          typename Sink::Target target, int32_t* __restrict__ box) {
     __shared__ float g_val[12][MESH_TRIS];
     __shared__ int g_box[4][MESH_TRIS];
     __shared__ int g_n;
@@ -97,7 +126,7 @@ __global__ __launch_bounds__(256) void mesh_render_kernel(const float* __restric
 #pragma unroll
     for (int i = 0; i < 16; ++i) P[i] = poses[(size_t)h * 16 + i];   // the same address in every lane: uniform loads
     if (!pose_finite(P)) return;                                      // the whole workgroup: no barrier is left behind
-    uint32_t* z = zbuf + (size_t)h * ((size_t)a.W * (size_t)a.H);
+    const Sink z(target, h, (size_t)a.W * (size_t)a.H);
     const int tid = (int)threadIdx.x, lane = tid & 63;
     if (tid == 0) g_n = 0;
     __syncthreads();
@@ -209,12 +238,35 @@ static int render_mesh(stocs_ctx* c, const void* self, const float* d_pose, int 
     const MeshArgs& ma = *(const MeshArgs*)self;
     const MeshState* S = (const MeshState*)c->mesh;
     const unsigned tri_chunks = (unsigned)((ma.nt + MESH_TRIS - 1) / MESH_TRIS);
-    hipLaunchKernelGGL(mesh_render_kernel, dim3(tri_chunks, (unsigned)m), dim3(256), 0, c->stream, d_pose, (const float4*)S->verts.p, (const int4*)S->tris.p, a, ma, d_z, d_box);
+    hipLaunchKernelGGL(mesh_render_kernel<DepthSink>, dim3(tri_chunks, (unsigned)m), dim3(256), 0, c->stream, d_pose, (const float4*)S->verts.p, (const int4*)S->tris.p, a, ma, d_z,
+                       d_box);
     STOCS_HIP_CHECK(hipGetLastError());
     return STOCS_OK;
 }
 
-static int check_has_mesh(const char* who, stocs_ctx* c) {
+int mesh_enqueue_depth(stocs_ctx* c, const float* d_pose, int m, const DepthArgs& a, uint32_t* d_z, int32_t* d_box) {
+    const MeshArgs ma = mesh_args(((const MeshState*)c->mesh)->nt);
+    return render_mesh(c, &ma, d_pose, m, a, d_z, d_box);
+}
+
+int mesh_enqueue_keys(stocs_ctx* c, const float* d_pose, int m, const DepthArgs& a, int id_base, unsigned long long* d_zkey, int32_t* d_box) {
+    const MeshState* S = (const MeshState*)c->mesh;
+    const MeshArgs ma = mesh_args(S->nt);
+    const unsigned tri_chunks = (unsigned)((ma.nt + MESH_TRIS - 1) / MESH_TRIS);
+    // the pose is blockIdx.y (at most 65 535 per launch)
+    for (int h0 = 0; h0 < m; h0 += 65535) {
+        const int mh = m - h0 < 65535 ? m - h0 : 65535;
+        const KeyTarget target = {d_zkey, id_base + h0};
+        hipLaunchKernelGGL(mesh_render_kernel<KeySink>, dim3(tri_chunks, (unsigned)mh), dim3(256), 0, c->stream, d_pose + (size_t)h0 * 16, (const float4*)S->verts.p,
+                           (const int4*)S->tris.p, a, ma, target, d_box + (size_t)h0 * VSD_BOX_WORDS);
+        STOCS_HIP_CHECK(hipGetLastError());
+    }
+    return STOCS_OK;
+}
+
+int mesh_triangles(const stocs_ctx* c) { return c->mesh ? ((const MeshState*)c->mesh)->nt : 0; }
+
+int mesh_check_present(const char* who, stocs_ctx* c) {
     const MeshState* S = (const MeshState*)c->mesh;
     if (!S || S->nt < 1) { set_error("%s: the context has no mesh (stocs_ctx_set_mesh)", who); return STOCS_ERR_STATE; }
     return STOCS_OK;
@@ -290,7 +342,7 @@ extern "C" int stocs_render_depth_mesh(stocs_ctx* c, const float* poses, int n, 
     if (n < 0) { set_error("%s: n %d < 0", who, n); return STOCS_ERR_INVALID; }
     if (n == 0) return STOCS_OK;
     if (!poses || !depth) { set_error("%s: NULL poses or images", who); return STOCS_ERR_INVALID; }
-    { const int rc = check_has_mesh(who, c); if (rc) return rc; }
+    { const int rc = mesh_check_present(who, c); if (rc) return rc; }
     DepthState* F = NULL;
     { const int rc = check_frame(who, c, &F); if (rc) return rc; }
     const MeshArgs ma = mesh_args(((const MeshState*)c->mesh)->nt);
@@ -306,7 +358,7 @@ extern "C" int stocs_pose_errors_vsd_mesh(stocs_ctx* c, const float* est, int n,
     if (!est || !gt || !prm || !out) { set_error("%s: NULL estimates, ground truth, parameters or results", who); return STOCS_ERR_INVALID; }
     if (n_gt != 1 && n_gt != n) { set_error("%s: n_gt %d is neither 1 nor n = %d", who, n_gt, n); return STOCS_ERR_INVALID; }
     { const int rc = vsd_check_compare_params(who, prm); if (rc) return rc; }   // surfel_radius and max_splat_px are not read
-    { const int rc = check_has_mesh(who, c); if (rc) return rc; }
+    { const int rc = mesh_check_present(who, c); if (rc) return rc; }
     DepthState* F = NULL;
     { const int rc = check_frame(who, c, &F); if (rc) return rc; }
     const MeshArgs ma = mesh_args(((const MeshState*)c->mesh)->nt);

@@ -14,12 +14,13 @@
 //                          steps 5-6 with the key's z.
 //                          Every count is a __ballot + __popcll per wavefront in wave-uniform registers; thread 0 stores the record.
 //   render_labels_kernel   one thread per pixel: label and state of the key.
-// The clear is a hipMemsetAsync with 0xFF.  Known limits: a point's splat is walked by the one lane that projected it (up to 33 x 33
+// The clear is a hipMemsetAsync with 0xFF.  The call layout, the pose upload, the clear, the labels launch and the read-back are declared in
+// render_shared.h: render_mesh.hip, the same entry points on a triangle mesh, runs through them too.  Known limits: a point's splat is walked by the one lane that projected it (up to 33 x 33
 // pixels); resolve is one workgroup per hypothesis, latency-bound for a few hypotheses, and holds the whole frame's bitset (2^19 pixels).
 #include <math.h>
 #include <string.h>
 
-#include "render_rules.h"
+#include "render_shared.h"
 #include "wave_bits.h"
 
 namespace stocs {
@@ -139,7 +140,7 @@ static RenderState* render_state(stocs_ctx* c) {
     return (RenderState*)c->render;
 }
 
-static int check_ids(const char* who, int n, int id_base) {
+int render_check_ids(const char* who, int n, int id_base) {
     if (id_base < 0 || (long long)id_base + (long long)n > 2147483647ll) {
         set_error("%s: ids %d .. %lld outside 0 .. 2^31 - 2", who, id_base, (long long)id_base + (long long)n - 1);
         return STOCS_ERR_INVALID;
@@ -155,33 +156,28 @@ static int check_capacity(const char* who, const DepthState* S) {
     return STOCS_OK;
 }
 
-// One call's layout.  The device block holds the context's own key buffer first (own_key pixels, 0 for the entry points that work on a
-// caller's buffer), then the regions below; the pinned block mirrors the regions alone, at the same offsets behind PIN_VAR.  Records,
-// labels and state lie one behind the other, so one copy reads back whatever a call produced.
-struct RenderLayout {
-    size_t key_bytes, o_pose, o_res, o_lab, o_state, total;
-    char* d; char* h;   // bases of the regions on the device and in the pinned block
-};
-static int render_layout(stocs_ctx* c, size_t own_key, int n, size_t label_px, RenderLayout* L) {
-    RenderState* R = render_state(c);
+// One call's layout (RenderLayout, render_shared.h) in the block `work` of the entry point
+int render_layout(stocs_ctx* c, DevBlock* work, size_t own_key, int n, size_t label_px, size_t tail, RenderLayout* L) {
     Carve cv;
     L->key_bytes = al256(own_key * 8);
     L->o_pose = cv.take((size_t)n * 64); L->o_res = cv.take((size_t)n * sizeof(stocs_render_result));
     L->o_lab = cv.take(label_px * 4); L->o_state = cv.take(label_px);
+    L->o_tail = cv.total;
     L->total = cv.total;
-    { const int rc = R->work.grow(c->stream, L->key_bytes + cv.total); if (rc) return rc; }
+    { const int rc = work->grow(c->stream, L->key_bytes + cv.total + tail); if (rc) return rc; }
     { const int rc = pinned_var(c, cv.total, &L->h); if (rc) return rc; }
-    L->d = R->work.p + L->key_bytes;
+    L->d = work->p + L->key_bytes;
     return STOCS_OK;
 }
+static int render_layout(stocs_ctx* c, size_t own_key, int n, size_t label_px, RenderLayout* L) { return render_layout(c, &render_state(c)->work, own_key, n, label_px, 0, L); }
 
-static int upload_poses(stocs_ctx* c, const RenderLayout& L, const float* poses, int n) {
+int render_upload_poses(stocs_ctx* c, const RenderLayout& L, const float* poses, int n) {
     memcpy(L.h + L.o_pose, poses, (size_t)n * 64);
     STOCS_HIP_CHECK(hipMemcpyAsync(L.d + L.o_pose, L.h + L.o_pose, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));
     return STOCS_OK;
 }
 
-static int enqueue_clear(stocs_ctx* c, const DepthState* S, void* d_zkey) {
+int render_enqueue_clear(stocs_ctx* c, const DepthState* S, void* d_zkey) {
     STOCS_HIP_CHECK(hipMemsetAsync(d_zkey, 0xFF, S->npix * 8, c->stream));
     return STOCS_OK;
 }
@@ -208,15 +204,17 @@ static int enqueue_resolve(stocs_ctx* c, const DepthState* S, const RenderLayout
     return STOCS_OK;
 }
 
-static int enqueue_labels(stocs_ctx* c, const DepthState* S, const RenderLayout& L, const stocs_render_params* prm, const void* d_zkey) {
+int render_enqueue_labels(stocs_ctx* c, const DepthState* S, const RenderLayout& L, float tolerance, float class_threshold, const void* d_zkey) {
     hipLaunchKernelGGL(render_labels_kernel, dim3((unsigned)((S->npix + 255) / 256)), dim3(256), 0, c->stream, (const unsigned long long*)d_zkey, frame_depth(S),
-                       frame_prob(S), frame_args(S, prm), S->npix, (int32_t*)(L.d + L.o_lab), (uint8_t*)(L.d + L.o_state));
+                       frame_prob(S), frame_args(S, tolerance, class_threshold), S->npix, (int32_t*)(L.d + L.o_lab), (uint8_t*)(L.d + L.o_state));
     STOCS_HIP_CHECK(hipGetLastError());
     return STOCS_OK;
 }
+static int enqueue_labels(stocs_ctx* c, const DepthState* S, const RenderLayout& L, const stocs_render_params* prm, const void* d_zkey) {
+    return render_enqueue_labels(c, S, L, prm->tolerance, prm->class_threshold, d_zkey);
+}
 
-// one copy of [from, to) of the regions into the pinned block, one synchronisation
-static int read_back(stocs_ctx* c, const RenderLayout& L, size_t from, size_t to) {
+int render_read_back(stocs_ctx* c, const RenderLayout& L, size_t from, size_t to) {
     STOCS_HIP_CHECK(hipMemcpyAsync(L.h + from, L.d + from, to - from, hipMemcpyDeviceToHost, c->stream));
     STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
     return STOCS_OK;
@@ -246,14 +244,14 @@ extern "C" int stocs_render_poses(stocs_ctx* c, const float* poses, int n, int i
     if (n == 0) return STOCS_OK;
     if (!poses || !prm || !d_zkey) { set_error("%s: NULL poses, parameters or key buffer", who); return STOCS_ERR_INVALID; }
     { const int rc = check_params(who, prm); if (rc) return rc; }
-    { const int rc = check_ids(who, n, id_base); if (rc) return rc; }
+    { const int rc = render_check_ids(who, n, id_base); if (rc) return rc; }
     DepthState* S = NULL;
     { const int rc = check_frame(who, c, &S); if (rc) return rc; }
     DeviceGuard dev_guard(c->device);
     RenderLayout L;
     { const int rc = render_layout(c, 0, n, 0, &L); if (rc) return rc; }
-    { const int rc = upload_poses(c, L, poses, n); if (rc) return rc; }
-    if (clear) { const int rc = enqueue_clear(c, S, d_zkey); if (rc) return rc; }
+    { const int rc = render_upload_poses(c, L, poses, n); if (rc) return rc; }
+    if (clear) { const int rc = render_enqueue_clear(c, S, d_zkey); if (rc) return rc; }
     { const int rc = enqueue_splat(c, S, L, n, prm, id_base, d_zkey); if (rc) return rc; }
     STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));   // another context may continue on the buffer
     return STOCS_OK;
@@ -267,16 +265,16 @@ extern "C" int stocs_render_resolve(stocs_ctx* c, const float* poses, int n, int
     if (n == 0) return STOCS_OK;
     if (!poses || !prm || !d_zkey || !out) { set_error("%s: NULL poses, parameters, key buffer or results", who); return STOCS_ERR_INVALID; }
     { const int rc = check_params(who, prm); if (rc) return rc; }
-    { const int rc = check_ids(who, n, id_base); if (rc) return rc; }
+    { const int rc = render_check_ids(who, n, id_base); if (rc) return rc; }
     DepthState* S = NULL;
     { const int rc = check_frame(who, c, &S); if (rc) return rc; }
     { const int rc = check_capacity(who, S); if (rc) return rc; }
     DeviceGuard dev_guard(c->device);
     RenderLayout L;
     { const int rc = render_layout(c, 0, n, 0, &L); if (rc) return rc; }
-    { const int rc = upload_poses(c, L, poses, n); if (rc) return rc; }
+    { const int rc = render_upload_poses(c, L, poses, n); if (rc) return rc; }
     { const int rc = enqueue_resolve(c, S, L, n, prm, id_base, d_zkey); if (rc) return rc; }
-    { const int rc = read_back(c, L, L.o_res, L.o_res + (size_t)n * sizeof(stocs_render_result)); if (rc) return rc; }
+    { const int rc = render_read_back(c, L, L.o_res, L.o_res + (size_t)n * sizeof(stocs_render_result)); if (rc) return rc; }
     memcpy(out, L.h + L.o_res, (size_t)n * sizeof(stocs_render_result));
     return STOCS_OK;
 }
@@ -291,7 +289,7 @@ extern "C" int stocs_render_labels(stocs_ctx* c, const void* d_zkey, const stocs
     RenderLayout L;
     { const int rc = render_layout(c, 0, 0, S->npix, &L); if (rc) return rc; }
     { const int rc = enqueue_labels(c, S, L, prm, d_zkey); if (rc) return rc; }
-    { const int rc = read_back(c, L, L.o_lab, L.o_state + S->npix); if (rc) return rc; }
+    { const int rc = render_read_back(c, L, L.o_lab, L.o_state + S->npix); if (rc) return rc; }
     memcpy(labels, L.h + L.o_lab, S->npix * 4);
     if (state) memcpy(state, L.h + L.o_state, S->npix);
     return STOCS_OK;
@@ -306,7 +304,7 @@ extern "C" int stocs_explain_poses(stocs_ctx* c, const float* poses, int n, cons
     if (n > 0) {
         if (!poses || !prm || !out) { set_error("%s: NULL poses, parameters or results", who); return STOCS_ERR_INVALID; }
         { const int rc = check_params(who, prm); if (rc) return rc; }
-        { const int rc = check_ids(who, n, 0); if (rc) return rc; }
+        { const int rc = render_check_ids(who, n, 0); if (rc) return rc; }
     }
     DepthState* S = NULL;
     { const int rc = check_frame(who, c, &S); if (rc) return rc; }
@@ -320,12 +318,12 @@ extern "C" int stocs_explain_poses(stocs_ctx* c, const float* poses, int n, cons
     RenderLayout L;
     { const int rc = render_layout(c, S->npix, n, labels ? S->npix : 0, &L); if (rc) return rc; }
     void* d_zkey = ((RenderState*)c->render)->work.p;
-    { const int rc = upload_poses(c, L, poses, n); if (rc) return rc; }
-    { const int rc = enqueue_clear(c, S, d_zkey); if (rc) return rc; }
+    { const int rc = render_upload_poses(c, L, poses, n); if (rc) return rc; }
+    { const int rc = render_enqueue_clear(c, S, d_zkey); if (rc) return rc; }
     { const int rc = enqueue_splat(c, S, L, n, prm, 0, d_zkey); if (rc) return rc; }
     { const int rc = enqueue_resolve(c, S, L, n, prm, 0, d_zkey); if (rc) return rc; }
     if (labels) { const int rc = enqueue_labels(c, S, L, prm, d_zkey); if (rc) return rc; }
-    { const int rc = read_back(c, L, L.o_res, labels ? L.o_state + S->npix : L.o_res + (size_t)n * sizeof(stocs_render_result)); if (rc) return rc; }
+    { const int rc = render_read_back(c, L, L.o_res, labels ? L.o_state + S->npix : L.o_res + (size_t)n * sizeof(stocs_render_result)); if (rc) return rc; }
     memcpy(out, L.h + L.o_res, (size_t)n * sizeof(stocs_render_result));
     if (labels) memcpy(labels, L.h + L.o_lab, S->npix * 4);
     if (labels && state) memcpy(state, L.h + L.o_state, S->npix);

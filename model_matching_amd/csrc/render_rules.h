@@ -64,12 +64,16 @@ __device__ __forceinline__ int classify_pixel(float z, size_t px, const uint16_t
 }
 
 // ---- host side: the parameter check and the kernel arguments of the render entry points ----
-static int check_params(const char* who, const stocs_render_params* p) {
-    if (!(p->point_radius >= 0.0f) || !isfinite(p->point_radius)) { set_error("%s: point_radius %g must be >= 0 and finite", who, (double)p->point_radius); return STOCS_ERR_INVALID; }
-    if (p->max_splat_px < 0 || p->max_splat_px > RENDER_MAX_SPLAT) { set_error("%s: max_splat_px %d outside 0..%d", who, p->max_splat_px, (int)RENDER_MAX_SPLAT); return STOCS_ERR_INVALID; }
+// the two fields the classification reads: all that the mesh forms (render_mesh.hip) read and check of stocs_render_params
+static int check_classify_params(const char* who, const stocs_render_params* p) {
     if (!(p->tolerance > 0.0f) || !isfinite(p->tolerance)) { set_error("%s: tolerance %g must be positive and finite", who, (double)p->tolerance); return STOCS_ERR_INVALID; }
     if (!isfinite(p->class_threshold)) { set_error("%s: class_threshold is not finite", who); return STOCS_ERR_INVALID; }
     return STOCS_OK;
+}
+static int check_params(const char* who, const stocs_render_params* p) {
+    if (!(p->point_radius >= 0.0f) || !isfinite(p->point_radius)) { set_error("%s: point_radius %g must be >= 0 and finite", who, (double)p->point_radius); return STOCS_ERR_INVALID; }
+    if (p->max_splat_px < 0 || p->max_splat_px > RENDER_MAX_SPLAT) { set_error("%s: max_splat_px %d outside 0..%d", who, p->max_splat_px, (int)RENDER_MAX_SPLAT); return STOCS_ERR_INVALID; }
+    return check_classify_params(who, p);
 }
 
 static DepthArgs frame_args(const DepthState* S, const stocs_render_params* prm) { return frame_args(S, prm->tolerance, prm->class_threshold); }

@@ -20,6 +20,9 @@
 //             cover_walk.h, which instances.hip shares, behind this file's gate (eligible, and the slot's group not full; a selection
 //             counts towards its group).  Cover and counts only grow.
 //   finish    scene_finish_kernel, a wavefront per slot: |A_h \ covered_final| of the unselected ones and the reason, from the final state.
+// The body of stocs_scene_footprints behind its checks is scene_footprints_with (render_shared.h): the chunk loop, the clears, the classify
+// launch and the read-back around a z-buffer filler; the splats are one filler, the mesh of render_mesh.hip (stocs_scene_footprints_mesh)
+// another.
 // The ordering sort and the read-back region (results | selected | count) are cover_walk.h's; the pinned staging is pinned_for (stocs_ctx.h).
 // Known limits: npix <= 2^19, n <= 16 384 slots, 1024 groups; classify walks the whole frame of every hypothesis; the walk is one workgroup.
 #include <math.h>
@@ -27,7 +30,7 @@
 #include <string.h>
 
 #include "cover_walk.h"
-#include "render_rules.h"
+#include "render_shared.h"
 
 namespace stocs {
 
@@ -197,7 +200,7 @@ static int check_params(const char* who, const stocs_scene_params* p) {
     return STOCS_OK;
 }
 
-static int check_pixels(const char* who, size_t npix) {
+int scene_check_pixels(const char* who, size_t npix) {
     if (npix > (size_t)SCENE_MAX_PIXELS) {
         set_error("%s: a frame of %zu pixels, at most %d (the cover of the walk is a 64 KB bitset in LDS)", who, npix, (int)SCENE_MAX_PIXELS);
         return STOCS_ERR_CAPACITY;
@@ -227,6 +230,8 @@ extern "C" int stocs_scene_row_words(int width, int height) {
     return row_words((size_t)width * (size_t)height);
 }
 
+static int fill_splats(stocs_ctx* c, const void* self, const float* d_pose, int m, const DepthArgs& a, uint32_t* d_z, void*);
+
 extern "C" int stocs_scene_footprints(stocs_ctx* c, const float* poses, int n, int slot_base, int n_slots, const stocs_render_params* prm, int claim, void* d_rows,
                                       stocs_scene_record* out) {
     static const char* who = "stocs_scene_footprints";
@@ -242,9 +247,25 @@ extern "C" int stocs_scene_footprints(stocs_ctx* c, const float* poses, int n, i
     { const int rc = check_params(who, prm); if (rc) return rc; }
     DepthState* F = NULL;
     { const int rc = check_frame(who, c, &F); if (rc) return rc; }
-    { const int rc = check_pixels(who, F->npix); if (rc) return rc; }
+    { const int rc = scene_check_pixels(who, F->npix); if (rc) return rc; }
+    const RenderArgs ra = render_args(prm, 0);
+    const SceneFill fill = {fill_splats, &ra, 0};
+    return scene_footprints_with(c, F, &scene_state(c)->work, fill, poses, n, slot_base, prm->tolerance, prm->class_threshold, claim, d_rows, out);
+}
+
+// the splats as a SceneFill: self is the call's RenderArgs
+static int fill_splats(stocs_ctx* c, const void* self, const float* d_pose, int m, const DepthArgs& a, uint32_t* d_z, void*) {
+    const unsigned point_chunks = (unsigned)((c->nM + SCENE_CHUNK_POINTS - 1) / SCENE_CHUNK_POINTS);
+    if (!point_chunks) return STOCS_OK;
+    hipLaunchKernelGGL(scene_splat_kernel, dim3(point_chunks, (unsigned)m), dim3(256), 0, c->stream, d_pose, (const float4*)c->d_mpos_raw, (const float4*)c->d_mnrm, c->nM, a,
+                       *(const RenderArgs*)self, d_z);
+    STOCS_HIP_CHECK(hipGetLastError());
+    return STOCS_OK;
+}
+
+int stocs::scene_footprints_with(stocs_ctx* c, DepthState* F, DevBlock* work, const SceneFill& fill, const float* poses, int n, int slot_base, float tolerance,
+                                 float class_threshold, int claim, void* d_rows, stocs_scene_record* out) {
     DeviceGuard dev_guard(c->device);
-    SceneState* S = scene_state(c);
     const size_t npix = F->npix;
     const int Wr = row_words(npix);
     // one z-buffer per hypothesis of a chunk; the hypothesis is blockIdx.y (at most 65 535 per launch)
@@ -252,28 +273,23 @@ extern "C" int stocs_scene_footprints(stocs_ctx* c, const float* poses, int n, i
     if (const char* e = getenv("STOCS_SCENE_CHUNK")) { const long v = atol(e); if (v >= 1) chunk = std::min<size_t>(std::min<size_t>((size_t)v, (size_t)n), 65535); }
     Carve cv;
     const size_t o_pose = cv.take((size_t)n * 64), o_rec = cv.take((size_t)n * sizeof(stocs_scene_record)), o_z = cv.take(chunk * npix * 4);
-    { const int rc = S->work.grow(c->stream, cv.total); if (rc) return rc; }
+    const size_t o_side = fill.side_bytes ? cv.take(chunk * fill.side_bytes) : 0;
+    { const int rc = work->grow(c->stream, cv.total); if (rc) return rc; }
     char* h_in; char* h_back;
     { const int rc = pinned_for(c, (size_t)n * 64, al256((size_t)n * sizeof(stocs_scene_record)), &h_in, &h_back); if (rc) return rc; }
-    float* d_pose = Carve::at<float>(S->work.p, o_pose);
-    stocs_scene_record* d_rec = Carve::at<stocs_scene_record>(S->work.p, o_rec);
-    uint32_t* d_z = Carve::at<uint32_t>(S->work.p, o_z);
+    float* d_pose = Carve::at<float>(work->p, o_pose);
+    stocs_scene_record* d_rec = Carve::at<stocs_scene_record>(work->p, o_rec);
+    uint32_t* d_z = Carve::at<uint32_t>(work->p, o_z);
     memcpy(h_in, poses, (size_t)n * 64);
     STOCS_HIP_CHECK(hipMemcpyAsync(d_pose, h_in, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));
     STOCS_HIP_CHECK(hipMemsetAsync(d_rec, 0, (size_t)n * sizeof(stocs_scene_record), c->stream));
-    const DepthArgs a = frame_args(F, prm);
-    const RenderArgs ra = render_args(prm, 0);
-    const unsigned point_chunks = (unsigned)((c->nM + SCENE_CHUNK_POINTS - 1) / SCENE_CHUNK_POINTS);
+    const DepthArgs a = frame_args(F, tolerance, class_threshold);
     const unsigned run_blocks = (unsigned)(((size_t)(Wr / 2) + 4 * SCENE_RUNS_PER_WAVE - 1) / (4 * SCENE_RUNS_PER_WAVE));
     uint32_t* rows = (uint32_t*)d_rows + (size_t)slot_base * (size_t)Wr;
     for (int h0 = 0; h0 < n; h0 += (int)chunk) {
         const int m = std::min((int)chunk, n - h0);
         STOCS_HIP_CHECK(hipMemsetAsync(d_z, 0xFF, (size_t)m * npix * 4, c->stream));
-        if (point_chunks) {
-            hipLaunchKernelGGL(scene_splat_kernel, dim3(point_chunks, (unsigned)m), dim3(256), 0, c->stream, (const float*)d_pose + (size_t)h0 * 16,
-                               (const float4*)c->d_mpos_raw, (const float4*)c->d_mnrm, c->nM, a, ra, d_z);
-            STOCS_HIP_CHECK(hipGetLastError());
-        }
+        { const int rc = fill.fill(c, fill.self, (const float*)d_pose + (size_t)h0 * 16, m, a, d_z, work->p + o_side); if (rc) return rc; }
         hipLaunchKernelGGL(scene_classify_kernel, dim3(run_blocks, (unsigned)m), dim3(256), 0, c->stream, (const uint32_t*)d_z, frame_depth(F), frame_prob(F), a, (int)npix,
                            Wr, claim, rows + (size_t)h0 * (size_t)Wr, d_rec + h0);
         STOCS_HIP_CHECK(hipGetLastError());
@@ -309,7 +325,7 @@ extern "C" int stocs_scene_select(stocs_ctx* c, const void* d_rows, int n, int w
         }
     }
     const size_t npix = (size_t)width * (size_t)height;
-    { const int rc = check_pixels(who, npix); if (rc) return rc; }
+    { const int rc = scene_check_pixels(who, npix); if (rc) return rc; }
     *n_selected = 0;
     if (n == 0) return STOCS_OK;
     DeviceGuard dev_guard(c->device);

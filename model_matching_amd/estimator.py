@@ -724,6 +724,60 @@ class StocsEstimator:
         capi.check(self.L.stocs_scene_footprints(self.h, pP, n, int(slot_base), int(n_slots), C.byref(prm), SCENE_CLAIMS[claim], rows, buf))
         return np.frombuffer(buf, dtype=_SCENE_RECORD_DTYPE, count=n).copy()
 
+    def _render_params_mesh(self, who, params):
+        if "point_radius" in params or "max_splat_px" in params:
+            raise TypeError("%s: a mesh has no splat parameters" % who)
+        return self._render_params(who, params)
+
+    def render_poses_mesh(self, poses16, zkey, id_base=0, clear=False):
+        """render_poses from the mesh of set_mesh (stocs_render_poses_mesh): pose h writes id id_base + h wherever its exact surface is
+        the nearest.  The key buffer may be shared with render_poses calls of this or other estimators.  No parameters: no radius."""
+        P, pP = capi.f32(poses16)
+        capi.check(self.L.stocs_render_poses_mesh(self.h, pP, P.size // 16, int(id_base), zkey, 1 if clear else 0))
+
+    def render_resolve_mesh(self, poses16, zkey, id_base=0, **params):
+        """render_resolve for poses rendered by render_poses_mesh (stocs_render_resolve_mesh) -> the same records; a pose's footprint is
+        the pixel set of its own mesh image.  params: tolerance, class_threshold."""
+        P, pP = capi.f32(poses16)
+        n = P.size // 16
+        prm = self._render_params_mesh("render_resolve_mesh", params)
+        buf = (capi.RenderResult * max(n, 1))()
+        capi.check(self.L.stocs_render_resolve_mesh(self.h, pP, n, int(id_base), C.byref(prm), zkey, buf))
+        return np.frombuffer(buf, dtype=_RENDER_DTYPE, count=n).copy()
+
+    def explain_poses_mesh(self, poses16, labels=False, **params):
+        """explain_poses on the mesh of set_mesh (stocs_explain_poses_mesh) -> records, or (records, labels, state) with labels=True.
+        params: tolerance, class_threshold."""
+        P, pP = capi.f32(poses16)
+        n = P.size // 16
+        prm = self._render_params_mesh("explain_poses_mesh", params)
+        buf = (capi.RenderResult * max(n, 1))()
+        if not labels:
+            capi.check(self.L.stocs_explain_poses_mesh(self.h, pP, n, C.byref(prm), buf, None, None))
+            return np.frombuffer(buf, dtype=_RENDER_DTYPE, count=n).copy()
+        H, W = self._frame_shape("explain_poses_mesh")
+        lab = np.zeros((H, W), np.int32); st = np.zeros((H, W), np.uint8)
+        capi.check(self.L.stocs_explain_poses_mesh(self.h, pP, n, C.byref(prm), buf, lab.ctypes.data_as(capi._ip), st.ctypes.data_as(capi._u8p)))
+        return np.frombuffer(buf, dtype=_RENDER_DTYPE, count=n).copy(), lab, st
+
+    def scene_footprints_mesh(self, poses16, rows, slot_base, n_slots, claim="agree", **render_params):
+        """scene_footprints from the mesh of set_mesh (stocs_scene_footprints_mesh): the same rows and records, for scene_select as they
+        are; a pool may mix slots of both kinds.  render_params: tolerance, class_threshold."""
+        P, pP = capi.f32(poses16)
+        n = P.size // 16
+        if claim not in SCENE_CLAIMS:
+            raise ValueError("scene_footprints_mesh: claim %r is neither 'agree' nor 'on_mask'" % (claim,))
+        prm = self._render_params_mesh("scene_footprints_mesh", render_params)
+        buf = (capi.SceneRecord * max(n, 1))()
+        capi.check(self.L.stocs_scene_footprints_mesh(self.h, pP, n, int(slot_base), int(n_slots), C.byref(prm), SCENE_CLAIMS[claim], rows, buf))
+        return np.frombuffer(buf, dtype=_SCENE_RECORD_DTYPE, count=n).copy()
+
+    def render_mesh_last_device_ms(self):
+        """(key render, resolve kernel) HIP-event ms of the last mesh render call with the option device_clock on; -1: not taken"""
+        a, b = C.c_float(-1), C.c_float(-1)
+        capi.check(self.L.stocs_render_mesh_last_device_ms(self.h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
     def scene_select(self, rows, shape, score, group, rec, group_cap=None, **params):
         """The walk over slots 0 .. n-1 of the pool rows of a frame of shape (height, width) (stocs_scene_select): score (n,), group (n,)
         ids, rec (n,) records of scene_footprints, group_cap one cap per group or None -> (records, selected): a structured array with
@@ -1023,13 +1077,15 @@ def scene_row_words(shape):
     return int(capi.load().stocs_scene_row_words(int(shape[1]), int(shape[0])))
 
 
-def select_scene(estimators, poses_per_object, scores_per_object=None, max_per_object=None, labels=False, **params):
+def select_scene(estimators, poses_per_object, scores_per_object=None, max_per_object=None, labels=False, surface=None, **params):
     """Which hypotheses of several objects form one consistent explanation of the frame: estimators[k] holds object k's model and the
     frame (set_frame, the same size everywhere), poses_per_object[k] its camera-frame hypotheses (m_k, 16).  The pool of pixel rows is
     allocated on the first estimator, every estimator writes its footprints into consecutive slots (group = object index), and the
     first estimator walks the pool (scene_select).  scores_per_object: one score array per object; default
     float32(agree) / float32(footprint), 0 where the footprint is empty -- visible-surface agreement, comparable across objects (LCP is
-    not: its weights are per-object class probabilities).  max_per_object: an int or one cap per object.  params: fields of
+    not: its weights are per-object class probabilities).  max_per_object: an int or one cap per object.  surface: "points" or "mesh"
+    per object (None: all points) -- a "mesh" object's footprints, and its masks under labels=True, come from the mesh of its
+    estimator's set_mesh (scene_footprints_mesh, render_poses_mesh, render_resolve_mesh); both kinds share the pool.  params: fields of
     stocs_scene_params, of stocs_render_params, and claim.  -> dict(records, selected, footprints, score, group, index) over the slots
     (group / index: the object and the hypothesis of it a slot holds); with labels=True the selected poses of every object are rendered
     into one key buffer with id = slot (render_poses, render_resolve, render_labels) and the dict also holds render (records of the
@@ -1043,6 +1099,10 @@ def select_scene(estimators, poses_per_object, scores_per_object=None, max_per_o
     for k in params:
         if k not in render_keys and k not in scene_keys:
             raise TypeError("select_scene: unknown parameter %r" % k)
+    surface = ["points"] * len(estimators) if surface is None else list(surface)
+    if len(surface) != len(estimators) or any(s not in ("points", "mesh") for s in surface):
+        raise ValueError("select_scene: surface is one of 'points' / 'mesh' per object, got %r" % (surface,))
+    mprm = {k: v for k, v in rprm.items() if k not in ("point_radius", "max_splat_px")}   # what a mesh reads of them
     first = estimators[0]
     shape = first._frame_shape("select_scene")
     if any(e._frame_shape("select_scene") != shape for e in estimators):
@@ -1057,8 +1117,8 @@ def select_scene(estimators, poses_per_object, scores_per_object=None, max_per_o
     zkey = None
     try:
         foot, base = [], 0
-        for est, p in zip(estimators, P):
-            foot.append(est.scene_footprints(p, rows, base, n, claim, **rprm))
+        for est, p, kind in zip(estimators, P, surface):
+            foot.append(est.scene_footprints_mesh(p, rows, base, n, claim, **mprm) if kind == "mesh" else est.scene_footprints(p, rows, base, n, claim, **rprm))
             base += len(p)
         foot = np.concatenate(foot)
         if scores_per_object is None:
@@ -1077,8 +1137,12 @@ def select_scene(estimators, poses_per_object, scores_per_object=None, max_per_o
             else:
                 zkey = first.dev_alloc(shape[0] * shape[1] * 8)
                 for i, s in enumerate(sel.tolist()):
-                    estimators[group[s]].render_poses(P[group[s]][index[s]], zkey, s, i == 0, **rprm)
-                out["render"] = np.concatenate([estimators[group[s]].render_resolve(P[group[s]][index[s]], zkey, s, **rprm) for s in sel.tolist()])
+                    if surface[group[s]] == "mesh":
+                        estimators[group[s]].render_poses_mesh(P[group[s]][index[s]], zkey, s, i == 0)
+                    else:
+                        estimators[group[s]].render_poses(P[group[s]][index[s]], zkey, s, i == 0, **rprm)
+                out["render"] = np.concatenate([estimators[group[s]].render_resolve_mesh(P[group[s]][index[s]], zkey, s, **mprm) if surface[group[s]] == "mesh"
+                                                else estimators[group[s]].render_resolve(P[group[s]][index[s]], zkey, s, **rprm) for s in sel.tolist()])
                 out["labels"], out["state"] = first.render_labels(zkey, **rprm)
     finally:
         first.dev_free(rows)
