@@ -311,7 +311,8 @@ int stocs_trials_get_hypotheses(stocs_ctx* ctx, int trial, stocs_trial_hypothesi
  * The robust workspace takes 8 bytes per (hypothesis, scene point), and a piece's slots are an upper bound (min(count + 1,
  * candidates) per trial) on the whole scene: a piece refines its slots in GROUPS of consecutive slots that share the workspace, a
  * group being the largest run whose demand (group x scene points x 8 bytes) stays within STOCS_REFINE_ROBUST_MAX_WORKSPACE_BYTES,
- * and at least one slot.  Only a scene too large for ONE slot (scene points x 8 bytes above the limit) is STOCS_ERR_INVALID.  The
+ * and at least one slot.  Only a scene too large for ONE slot (scene points x 8 bytes above the limit, where rank words are stored:
+ * keep_ratio < 1) is STOCS_ERR_INVALID.  The
  * environment variable STOCS_REFINE_ROBUST_GROUP_BYTES, read per call, lowers the limit (tests: forces several groups).  Results
  * are bitwise independent of the grouping and of the pieces.  The workspace is grow-only (stocs_refine_robust_workspace): a repeated
  * call of the same size allocates nothing.  One read-back and one synchronisation per piece, as stocs_run_trials_post.

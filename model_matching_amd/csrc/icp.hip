@@ -8,13 +8,14 @@
 // Per iteration one kernel: each thread owns a source point, the target cloud streams through LDS in
 // 256-point tiles (coalesced float4 loads), the thread keeps its nearest target, then the block reduces
 // the 27 unique entries of A^T A | A^T b in double and writes one partial per block (summed on the host in
-// block order: deterministic).  The 6x6 solve is host code.
+// block order: deterministic).  The 6x6 solve is host code (solve6.h, shared with refine.hip).
 #include <math.h>
 #include <string.h>
 
 #include <algorithm>
 #include <vector>
 
+#include "solve6.h"
 #include "stocs_ctx.h"
 
 namespace stocs {
@@ -74,28 +75,6 @@ __global__ __launch_bounds__(256) void icp_accumulate_kernel(const float4* __res
     }
 }
 
-static bool solve6(double A[6][6], double b[6], double x[6]) {
-    int piv[6];
-    for (int i = 0; i < 6; ++i) piv[i] = i;
-    for (int c = 0; c < 6; ++c) {
-        int p = c;
-        for (int r = c + 1; r < 6; ++r) if (fabs(A[r][c]) > fabs(A[p][c])) p = r;
-        if (fabs(A[p][c]) < 1e-300) return false;
-        if (p != c) { for (int k = 0; k < 6; ++k) std::swap(A[p][k], A[c][k]); std::swap(b[p], b[c]); }
-        for (int r = c + 1; r < 6; ++r) {
-            const double f = A[r][c] / A[c][c];
-            for (int k = c; k < 6; ++k) A[r][k] -= f * A[c][k];
-            b[r] -= f * b[c];
-        }
-    }
-    for (int r = 5; r >= 0; --r) {
-        double s = b[r];
-        for (int k = r + 1; k < 6; ++k) s -= A[r][k] * x[k];
-        x[r] = s / A[r][r];
-    }
-    return true;
-}
-
 }  // namespace stocs
 
 using namespace stocs;
@@ -142,7 +121,8 @@ extern "C" int stocs_icp_point_to_plane(const float* src_pos3, int nsrc, const f
         for (int r = 0; r < 6; ++r) for (int c = r; c < 6; ++c) { A[r][c] = acc[k]; A[c][r] = acc[k]; k++; }
         for (int r = 0; r < 6; ++r) bb[r] = acc[21 + r];
         if (!solve6(A, bb, x)) break;
-        // update = [Rz(gamma) Ry(beta) Rx(alpha) | t], composed on the left of the running estimate
+        // update = [Rz(gamma) Ry(beta) Rx(alpha) | t], composed on the left of the running estimate (refine_solve_kernel holds the other
+        // copy of these lines, see there)
         const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
         const double R[3][3] = {{cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa},
                                 {sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa},

@@ -430,27 +430,34 @@ int pinned_for(stocs_ctx* c, size_t in_bytes, size_t back_bytes, char** h_in, ch
 int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d_hit, uint8_t* d_counted, unsigned long long* d_best8, uint32_t id_offset);
 // every scoring entry point calls this first: the tie counters of stocs_last_tie_counts then cover that call alone (no device work)
 inline void begin_scoring_call(stocs_ctx* c) { c->ties_started = false; }
-// refine.hip: stocs_refine_poses as an enqueue step on device-resident hypotheses (the trial batches' post-processing uses it)
-struct RefineWork {
-    void* d_hyp; float* d_Tin; int32_t* d_idx; double* d_part;   // d_Tin: the n centred T16 to refine; d_idx: nsrc source indices
-    float* d_Tout; float* d_Pout; float* d_lcp; int32_t* d_nc; int32_t* d_it;   // contiguous outputs, out_bytes in all
-    size_t out_bytes;
-    int n, nsrc, nchunks;
-};
-int refine_prepare(stocs_ctx* c, int n, int nsrc, float max_correspondence_distance, RefineWork* w);
-int refine_enqueue(stocs_ctx* c, const RefineWork& w, bool use_idx, const int32_t* d_live, int max_iterations, float max_correspondence_distance);
-// refine_robust.h: stocs_refine_poses_robust as an enqueue step (stocs_run_trials_post_robust, stocs_track_poses_robust).  robust_plan
-// checks the two settings, sizes the groups the n hypotheses are refined in and grows the workspace (may synchronise); robust_enqueue
-// is refine_enqueue's counterpart on every scene point (*n_groups, may be NULL: the groups it ran)
-struct RobustPlan { int group; float keep_ratio, min_normal_cos; };
+// refine.hip: the point-to-plane refinement as a step on device-resident hypotheses (stocs_refine_poses[_robust], the trial batches'
+// post-processing, the tracker).  One settings value covers both forms: plain is keep_ratio 1 with the gate off (refine_plain).
+struct RefineSettings { int iterations; float distance, keep_ratio, min_normal_cos; };   // min_normal_cos below -1: gate off
+inline RefineSettings refine_plain(int iterations, float distance) { return RefineSettings{iterations, distance, 1.0f, -2.0f}; }
 inline const char* robust_setting_error(float keep_ratio, float min_normal_cos) {
     if (!(keep_ratio > 0.0f && keep_ratio <= 1.0f)) return "keep_ratio must be in (0, 1]";
     if (!(min_normal_cos <= 1.0f)) return "min_normal_cos must be <= 1 (below -1: gate off)";
     return NULL;
 }
-int robust_plan(stocs_ctx* c, const char* who, int n, int nsrc, float keep_ratio, float min_normal_cos, RobustPlan* plan);
-int robust_enqueue(stocs_ctx* c, const RefineWork& w, const RobustPlan& plan, const int32_t* d_live, int max_iterations, float max_correspondence_distance,
-                   int* n_groups);
+struct RefineWork {   // what refine_prepare planned (value-initialised: nothing)
+    RefineSettings s = {};
+    void* d_hyp = NULL; float* d_Tin = NULL; int32_t* d_idx = NULL; double* d_part = NULL;   // d_Tin: the n centred T16 to refine; d_idx: nsrc source indices
+    float* d_Tout = NULL; float* d_Pout = NULL; float* d_lcp = NULL; int32_t* d_nc = NULL; int32_t* d_it = NULL;   // contiguous outputs, out_bytes in all
+    size_t out_bytes = 0;
+    int n = 0, nsrc = 0, nchunks = 0;
+    // rows (keep_ratio < 1): rank words | model indices of `group` hypotheses x nsrc and their select results, shared by the groups of
+    // consecutive hypotheses the n are refined in; else one group of n and no rows
+    bool rows = false; int group = 0;
+    uint32_t* d_word = NULL; int32_t* d_match = NULL; void* d_sel = NULL;
+};
+enum { REFINE_ONE_GROUP = 1, REFINE_ROWS = 2 };   // refine_prepare: never group (the caller bounds n x nsrc itself); rows even at keep_ratio 1
+// The model grid for s.distance, the workspace of n hypotheses over nsrc source points and, with rows, the group size and the rows
+// (all grow-only; may synchronise when one has to be built or grown: nothing of them may be in flight).  who: the entry point, for messages
+int refine_prepare(stocs_ctx* c, const char* who, int n, int nsrc, const RefineSettings& s, int flags, RefineWork* w);
+// init (d_live != NULL: hypothesis k takes part only when d_live[k]), group by group s.iterations x (evaluate, solve), final, the LCP
+// launch over all n -- on the stream, no copy, no synchronisation.  Input: w.d_Tin; the source is w.d_idx[0 .. nsrc) when use_idx, else
+// every scene point.  w.d_nc: the pairs that counted in the last evaluated iteration.  *n_groups (may be NULL): the groups it ran
+int refine_enqueue(stocs_ctx* c, const RefineWork& w, bool use_idx, const int32_t* d_live, int* n_groups);
 // cluster.hip: greedy_clustering of every trial of a batch piece on the device (see there); no synchronisation
 struct TrialClusterArgs { float fraction; int32_t count; float min_distance, min_angle; float sym[3]; };
 // hypothesis slots of a trial with n candidates: the reference's `size() > count` break keeps up to count + 1 of them.  The one rule

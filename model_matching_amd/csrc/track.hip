@@ -8,7 +8,7 @@
 //             launch_lcp: the scoring path of stocs_score_transforms,
 //             track_best_kernel: one workgroup per prior takes the first maximum and writes the next incumbent);
 //   with refinement, the incumbents are copied into refine.hip's workspace and refine_enqueue runs on them (stocs_track_poses_robust:
-//   robust_enqueue, refine_robust.h, in groups of priors that share the robust workspace);
+//   the trimmed, normal-gated settings, in groups of priors that share the rows of the workspace);
 //   track_result_kernel forms the camera poses (as refine_final_kernel does) and the result records;
 //   one copy back into the pinned block (the results, then every round's candidates and scores when details are kept), ONE
 //   synchronisation.
@@ -157,8 +157,8 @@ extern "C" void stocs_internal_free_track(stocs_ctx* c) {
     c->track = NULL;
 }
 
-// stocs_track_poses and, with robust != NULL, stocs_track_poses_robust
-static int track_poses(stocs_ctx* c, const float* priors, int n, const stocs_track_params* prm, const RobustPlan* robust, stocs_track_result* out) {
+// stocs_track_poses and stocs_track_poses_robust (who); rs: keep_ratio and min_normal_cos of the refinement, its iterations and distance are prm's
+static int track_poses(stocs_ctx* c, const char* who, const float* priors, int n, const stocs_track_params* prm, RefineSettings rs, stocs_track_result* out) {
     if (!c) { set_error("stocs_track_poses: NULL context"); return STOCS_ERR_INVALID; }
     if (n < 0) { set_error("stocs_track_poses: n_priors %d < 0", n); return STOCS_ERR_INVALID; }
     if (n == 0) return STOCS_OK;
@@ -189,11 +189,10 @@ static int track_poses(stocs_ctx* c, const float* priors, int n, const stocs_tra
     const int kr = keep ? R : 1;         // rounds whose candidates stay on the device
     // refine.hip's grid and workspace first: growing them synchronises, and nothing of this call may be in flight then
     RefineWork w;
-    RobustPlan plan;
     const bool refine = prm->refine_iterations > 0;
+    rs.iterations = prm->refine_iterations; rs.distance = prm->max_correspondence_distance;
     if (refine) {
-        int rc = refine_prepare(c, n, c->nS, prm->max_correspondence_distance, &w);
-        if (!rc && robust) rc = robust_plan(c, "stocs_track_poses_robust", n, c->nS, robust->keep_ratio, robust->min_normal_cos, &plan);
+        const int rc = refine_prepare(c, who, n, c->nS, rs, 0, &w);
         if (rc) return rc;
     }
     Carve cv;
@@ -232,8 +231,7 @@ static int track_poses(stocs_ctx* c, const float* priors, int n, const stocs_tra
     }
     if (refine) {
         STOCS_HIP_CHECK(hipMemcpyAsync(w.d_Tin, d_inc, (size_t)n * 64, hipMemcpyDeviceToDevice, c->stream));
-        const int rc = robust ? robust_enqueue(c, w, plan, NULL, prm->refine_iterations, prm->max_correspondence_distance, NULL)
-                              : refine_enqueue(c, w, false, NULL, prm->refine_iterations, prm->max_correspondence_distance);
+        const int rc = refine_enqueue(c, w, false, NULL, NULL);
         if (rc) return rc;
     }
     hipLaunchKernelGGL(track_result_kernel, dim3((unsigned)((n + 63) / 64)), dim3(64), 0, c->stream, (const float*)d_inc, (const float*)d_inc_lcp,
@@ -255,15 +253,13 @@ static int track_poses(stocs_ctx* c, const float* priors, int n, const stocs_tra
 }
 
 extern "C" int stocs_track_poses(stocs_ctx* c, const float* priors, int n, const stocs_track_params* prm, stocs_track_result* out) {
-    return track_poses(c, priors, n, prm, NULL, out);
+    return track_poses(c, "stocs_track_poses", priors, n, prm, refine_plain(0, 0.0f), out);
 }
 
 extern "C" int stocs_track_poses_robust(stocs_ctx* c, const float* priors, int n, const stocs_track_params* prm, float keep_ratio, float min_normal_cos,
                                         stocs_track_result* out) {
     if (const char* why = robust_setting_error(keep_ratio, min_normal_cos)) { set_error("stocs_track_poses_robust: %s", why); return STOCS_ERR_INVALID; }
-    RobustPlan robust;
-    robust.group = 0; robust.keep_ratio = keep_ratio; robust.min_normal_cos = min_normal_cos;
-    return track_poses(c, priors, n, prm, &robust, out);
+    return track_poses(c, "stocs_track_poses_robust", priors, n, prm, RefineSettings{0, 0.0f, keep_ratio, min_normal_cos}, out);
 }
 
 extern "C" int stocs_track_get_round(stocs_ctx* c, int prior, int round, float* T16, float* lcp, int cap, int* n) {

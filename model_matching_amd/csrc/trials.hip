@@ -177,8 +177,9 @@ static void assemble_piece(stocs_ctx* c, const TrialBatch* B, int t0, int t1) {
 struct Piece {
     int first = 0, n_trials = 0, n_cand = 0;
     const stocs_trial_post* post = NULL;     // NULL: no post-processing
-    const RobustPlan* robust = NULL;         // != NULL (stocs_run_trials_post_robust): the slots are refined by robust_enqueue with these settings
-    RobustPlan plan; int robust_groups = 0;  // ... the piece's group size (robust_plan) and the groups it ran
+    const char* who = NULL;                  // post: the entry point, for messages
+    RefineSettings refine_s = {};            // post: how the slots are refined (stocs_run_trials_post: the plain form)
+    int groups = 0;                          // ... the groups of slots the refinement ran
     const float4* trial_weights = NULL;      // != NULL (instance mode): every candidate scores against the weights of its own trial (Q8)
     int n_slots = 0; bool refine = false;    // post: hypothesis slots of the piece, per trial min(count + 1, its candidates); they are refined
     std::vector<int32_t> hyp_off;            // post: first slot of every trial (+ 1)
@@ -250,7 +251,7 @@ static int score_piece(stocs_ctx* c, const Piece& pc) {
 
 // post-processing of the piece: greedy_clustering of every trial, the kept candidates' records, then (refine_iterations > 0) the
 // point-to-plane refinement of every kept hypothesis of the piece in one enqueue, on the whole scene, written back into the records
-// (pc.robust: the trimmed, normal-gated form, robust_enqueue, in groups of slots that share the robust workspace)
+// (the trimmed form: in groups of slots that share the rows of the workspace)
 static int post_piece(stocs_ctx* c, Piece& pc) {
     const stocs_trial_post* post = pc.post;
     const int H = pc.n_slots;
@@ -260,8 +261,7 @@ static int post_piece(stocs_ctx* c, Piece& pc) {
     int rc = enqueue_trial_cluster(c, pc.n_trials, cand_P(c), cand_lcp(c), pc.d_cand_off, pc.d_best18, ca, pc.d_alive, pc.d_hyp_off, pc.d_hyp_count, pc.d_hyp_index);
     if (rc) return rc;
     RefineWork w;
-    if (pc.refine && (rc = refine_prepare(c, H, c->nS, post->max_correspondence_distance, &w))) return rc;
-    if (pc.refine && pc.robust && (rc = robust_plan(c, "stocs_run_trials_post_robust", H, c->nS, pc.robust->keep_ratio, pc.robust->min_normal_cos, &pc.plan))) return rc;
+    if (pc.refine && (rc = refine_prepare(c, pc.who, H, c->nS, pc.refine_s, 0, &w))) return rc;
     if (H > 0) {
         hipLaunchKernelGGL(trial_hyp_gather_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, c->stream, (const float*)cand_T(c), (const float*)cand_P(c),
                            (const float*)cand_lcp(c), (const int32_t*)cand_base(c), (const int32_t*)pc.d_cand_off, (const int32_t*)pc.d_hyp_off,
@@ -272,8 +272,7 @@ static int post_piece(stocs_ctx* c, Piece& pc) {
     if (!pc.refine) return STOCS_OK;
     {   // instance mode: hypothesis s rescored against the weights of its own trial, as the scoring launch
         TrialWeightsScope weights(c, pc.trial_weights, pc.d_slot_trial);
-        rc = pc.robust ? robust_enqueue(c, w, pc.plan, pc.d_slot_live, post->refine_iterations, post->max_correspondence_distance, &pc.robust_groups)
-                       : refine_enqueue(c, w, false, pc.d_slot_live, post->refine_iterations, post->max_correspondence_distance);
+        rc = refine_enqueue(c, w, false, pc.d_slot_live, &pc.groups);
     }
     if (rc) return rc;
     hipLaunchKernelGGL(refine_trial_hyp_kernel, dim3((unsigned)((H + 255) / 256)), dim3(256), 0, c->stream, (const int32_t*)pc.d_slot_live, H, (const float*)w.d_Pout,
@@ -353,11 +352,13 @@ int stocs_run_trials(stocs_ctx* c, int mode, int n_trials, const uint64_t* seeds
     return stocs_run_trials_post(c, mode, n_trials, seeds, n_attempts, dispersion, max_per_base, keep_details, NULL, out);
 }
 
-// stocs_run_trials_post and, with robust != NULL, stocs_run_trials_post_robust
-static int run_trials_post(stocs_ctx* c, int mode, int n_trials, const uint64_t* seeds, int n_attempts, float dispersion, int max_per_base, int keep_details,
-                           const stocs_trial_post* post, const RobustPlan* robust, stocs_trial_result* out) {
+// stocs_run_trials_post and stocs_run_trials_post_robust (who; robust: it reports its groups); rs: keep_ratio and min_normal_cos of the
+// refinement, its iterations and distance are post's
+static int run_trials_post(stocs_ctx* c, const char* who, int mode, int n_trials, const uint64_t* seeds, int n_attempts, float dispersion, int max_per_base, int keep_details,
+                           const stocs_trial_post* post, RefineSettings rs, bool robust, stocs_trial_result* out) {
     if (!c || n_trials < 0 || n_attempts < 0 || max_per_base <= 0 || (mode != 0 && mode != 1) || (n_trials && !seeds)) return STOCS_ERR_INVALID;
     if (check_post(post)) return STOCS_ERR_INVALID;
+    if (post) { rs.iterations = post->refine_iterations; rs.distance = post->max_correspondence_distance; }
     DeviceGuard dev_guard(c->device);
     begin_scoring_call(c);
     const double t_entry = now_ms();
@@ -425,7 +426,7 @@ static int run_trials_post(stocs_ctx* c, int mode, int n_trials, const uint64_t*
         if (rc) break;
         B->pieces++;
         Piece pc;
-        pc.first = t0; pc.n_trials = t1 - t0; pc.post = post; pc.robust = robust; pc.trial_weights = trial_weights;
+        pc.first = t0; pc.n_trials = t1 - t0; pc.post = post; pc.who = who; pc.refine_s = rs; pc.trial_weights = trial_weights;
         pc.best18.assign((size_t)pc.n_trials * 18, 0.0f);
         double ta = now_ms();
         if ((rc = stocs_make_transforms(c, max_per_base, 0, &pc.n_cand))) break;
@@ -435,7 +436,7 @@ static int run_trials_post(stocs_ctx* c, int mode, int n_trials, const uint64_t*
         // ---- verification: every candidate of the piece scored, the arg-max of each trial [, clustered and refined], one synchronisation ----
         if (pc.n_cand > 0 && ((rc = plan_piece(c, pc)) || (rc = score_piece(c, pc)) || (post && (rc = post_piece(c, pc))) || (rc = fetch_piece(c, B, pc)))) break;
         ms_ver += now_ms() - ta;
-        B->robust_groups += pc.robust_groups;
+        B->robust_groups += pc.groups;
         ta = now_ms();
         if ((rc = collect_piece(c, B, pc))) break;
         ms_res += now_ms() - ta;
@@ -466,7 +467,7 @@ static int run_trials_post(stocs_ctx* c, int mode, int n_trials, const uint64_t*
 
 int stocs_run_trials_post(stocs_ctx* c, int mode, int n_trials, const uint64_t* seeds, int n_attempts, float dispersion, int max_per_base, int keep_details,
                           const stocs_trial_post* post, stocs_trial_result* out) {
-    return run_trials_post(c, mode, n_trials, seeds, n_attempts, dispersion, max_per_base, keep_details, post, NULL, out);
+    return run_trials_post(c, "stocs_run_trials_post", mode, n_trials, seeds, n_attempts, dispersion, max_per_base, keep_details, post, refine_plain(0, 0.0f), false, out);
 }
 
 int stocs_run_trials_post_robust(stocs_ctx* c, int mode, int n_trials, const uint64_t* seeds, int n_attempts, float dispersion, int max_per_base, int keep_details,
@@ -474,9 +475,7 @@ int stocs_run_trials_post_robust(stocs_ctx* c, int mode, int n_trials, const uin
     const char* who = "stocs_run_trials_post_robust";
     if (!post) { set_error("%s: NULL post", who); return STOCS_ERR_INVALID; }
     if (const char* why = robust_setting_error(keep_ratio, min_normal_cos)) { set_error("%s: %s", who, why); return STOCS_ERR_INVALID; }
-    RobustPlan robust;
-    robust.group = 0; robust.keep_ratio = keep_ratio; robust.min_normal_cos = min_normal_cos;
-    return run_trials_post(c, mode, n_trials, seeds, n_attempts, dispersion, max_per_base, keep_details, post, &robust, out);
+    return run_trials_post(c, who, mode, n_trials, seeds, n_attempts, dispersion, max_per_base, keep_details, post, RefineSettings{0, 0.0f, keep_ratio, min_normal_cos}, true, out);
 }
 
 static TrialBatch* batch_of(stocs_ctx* c, int trial) {

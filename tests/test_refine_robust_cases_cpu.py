@@ -130,6 +130,18 @@ def test_restatement_with_everything_kept_is_the_oracle_icp_on_tiny():
         assert np.abs(got["T"][:3, :3] - want[:3, :3]).max() <= 1e-5 and np.abs(got["T"][:3, 3] - want[:3, 3]).max() <= 2e-5
 
 
+@pytest.mark.parametrize("name", ["tiny", "small"])
+def test_everything_kept_with_the_gate_on_is_clear_for_all_six(name):
+    """keep 1 with the 30 degree gate (the accumulation's gate-on form): the restatement of the six table hypotheses is clear at every
+    iteration, so tests/test_refine_robust_gpu.py may compare all six with it.  k about 180 to 185 on tiny, 506 to 513 on small."""
+    sc, sn, mc, mn, Tgt = _held(name)
+    mcos = rr.min_cos_of_degrees(30.0)
+    for h in rc.table_hypotheses(Tgt):
+        ref = rr.robust_loop(h, sc, sn, mc, mn, 5, 0.035, 1.0, mcos)
+        print(name, "clear", ref["clear"], "iterations", ref["iterations"], "k", ref["k"], "n_cand", ref["n_cand"])
+        assert ref["clear"] and ref["iterations"] == 5 and ref["k"] == ref["n_cand"]
+
+
 @pytest.fixture(scope="module")
 def small_rows():
     """ADD in mm of the six table hypotheses on `small`: before, and after 5 iterations of each form, with the clear flags of the

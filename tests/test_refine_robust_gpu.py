@@ -42,6 +42,47 @@ def test_keep_everything_gate_off_is_the_plain_form_bitwise(name):
     est.close()
 
 
+@pytest.mark.parametrize("name", ["tiny", "small"])
+def test_keep_everything_gate_on_against_the_restatement(name):
+    """keep 1 with the 30 degree gate runs the accumulation's gate-on form: the six table hypotheses against the float64 restatement, all
+    six (tests/test_refine_robust_cases_cpu.py: the restatement is clear for every one of them on both workloads)"""
+    m, s, est, Tgt = _workload(name)
+    H = rc.table_hypotheses(Tgt)
+    scene_c, scene_n = est.get_scene()[0], est.get_scene()[1]
+    model_c = (np.asarray(m.pos, F) - est.get_model_centroid()).astype(F)
+    model_n = rr.unit_normals(m.nrm)
+    To, Po, lcp, nc, ncand, it = est.refine_poses_robust(H, 5, 0.035, 1.0, 30.0)
+    for k in range(len(H)):
+        ref = rr.robust_loop(H[k], scene_c, scene_n, model_c, model_n, 5, 0.035, 1.0, rr.min_cos_of_degrees(30.0))
+        G = To[k].reshape(4, 4).T.astype(np.float64)
+        dr, dt = np.abs(G[:3, :3] - ref["T"][:3, :3]).max(), np.abs(G[:3, 3] - ref["T"][:3, 3]).max()
+        print("GATE1 %s %d clear %s k %d/%d n_cand %d it %d/%d dR %.3g dt %.3g" % (name, k, ref["clear"], nc[k], ref["k"], ncand[k], it[k], ref["iterations"], dr, dt))
+        assert nc[k] == ref["k"] and ncand[k] == nc[k] and it[k] == ref["iterations"], k
+        assert dr <= ROT_TOL and dt <= TRANS_TOL, (k, dr, dt)
+    est.close()
+
+
+def test_the_index_list_of_every_point_is_no_index_list_and_a_subset_is_batch_independent():
+    """tiny, 16 hypotheses, the plain and the robust (0.7, 30 degrees) entry point, which share one call frame and one driver:
+    src_idx = 0 .. nS - 1 gives every output bitwise as the call without an index list, and on a 300-point subset a hypothesis refined
+    alone gives bitwise what it gives in the batch"""
+    from model_matching_amd import synth
+    m, s, est, Tgt = _workload("tiny")
+    H = np.concatenate([rc.table_hypotheses(Tgt, 8, seed=11), synth.make_candidates(Tgt, 8, seed=synth.SEED_CAND + 29)])
+    every = np.arange(len(s.pos), dtype=np.int32)
+    subset = np.sort(np.random.default_rng(7).choice(len(s.pos), 300, replace=False)).astype(np.int32)
+    same = lambda a, b: a.dtype == b.dtype and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+    for call in (lambda h, idx: est.refine_poses(h, 5, 0.035, src_idx=idx), lambda h, idx: est.refine_poses_robust(h, 5, 0.035, 0.7, 30.0, src_idx=idx)):
+        whole = call(H, None)
+        assert (whole[-1] > 0).any()
+        assert all(same(a, b) for a, b in zip(whole, call(H, every)))
+        batch = call(H, subset)
+        assert (batch[-1] > 0).any() and not all(same(a, b) for a, b in zip(whole, batch))
+        for k in range(len(H)):
+            assert all(same(a[k:k + 1], b) for a, b in zip(batch, call(H[k:k + 1], subset))), k
+    est.close()
+
+
 def test_batch_independence_and_a_workspace_that_stays():
     from model_matching_amd import capi, synth
     L = capi.load()

@@ -7,7 +7,8 @@ usage: isa_diff.py OLD.s NEW.s
 A kernel's body is the text between its label and its .Lfunc_end; mangled names and basic-block numbers are replaced by
 placeholders before the comparison.  Prints one markdown table row per kernel of NEW: identical or the number of differing lines,
 and VGPRs / SGPRs / LDS bytes / scratch bytes of both listings.  Kernels are paired by their demangled names (any file); for the
-queue and per-step kernels of lcp.hip pair_name() also knows how their template arguments were renamed."""
+queue and per-step kernels of lcp.hip and the accumulation of refine.hip pair_name() also knows how their template arguments were
+renamed."""
 import difflib
 import re
 import subprocess
@@ -53,7 +54,11 @@ def pair_name(old):
         return "step<detail=%d split=%d>" % tuple(a)
     d = subprocess.run(["c++filt", old], capture_output=True, text=True).stdout.strip()
     d = re.sub(r"\(.*", "", d).replace("void ", "").replace("stocs::", "")
-    return d.replace(", RefNoDetail>", ">").replace("<RefNoDetail>", "")   # refine.hip: the shipping forms carry an empty detail argument
+    # refine.hip: the shipping forms carry an empty detail argument and, refine_accumulate_kernel, an empty gate argument; its gate-on
+    # form is what an older listing calls robust_fused_kernel<L>
+    d = d.replace(", RefNoGate>", ">").replace(", RefGate>", ", gate>")
+    d = re.sub(r"robust_fused_kernel<(\w+)>", r"refine_accumulate_kernel<\1, gate>", d)
+    return d.replace(", RefNoDetail", "").replace("<RefNoDetail>", "")
 
 
 def main():

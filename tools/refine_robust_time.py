@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Host wall clock of the robust refinement next to the plain one (5 iterations, 3.5 cm) for 1, 10, 64 and 256 hypotheses on the ycb
-example frame and on Cm, three forms in one process: stocs_refine_poses, stocs_refine_poses_robust with keep 0.7 and a 30 degree gate,
-and stocs_refine_poses_robust with keep 1 and the gate off (one fused launch per iteration).  Method as tools/refine_time.py: median of
+example frame and on Cm, four forms in one process: stocs_refine_poses, stocs_refine_poses_robust with keep 0.7 and a 30 degree gate,
+with keep 1 and the gate off (the plain form's accumulation, one launch per iteration) and with keep 1 and the 30 degree gate (the
+accumulation's gate-on form, one launch per iteration).  Method as tools/refine_time.py: median of
 20 after 5 warm-ups.  The yardstick is the plain call; the record holds the ratio per row.  A kernel trace of ONE call per robust form
 (Cm, 64 hypotheses) is taken in child processes before this process opens the GPU.  Measurement only.
 usage: python tools/refine_robust_time.py [out.json] [reps]        (--one-call WORKLOAD N FORM: the traced child)"""
@@ -20,7 +21,7 @@ sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 os.environ.setdefault("STOCS_PIN_BLAS", "1")
 
 SIZES = (1, 10, 64, 256)
-FORMS = {"plain": None, "robust_0.7_30deg": (0.7, 30.0), "robust_keep1_nogate": (1.0, None)}
+FORMS = {"plain": None, "robust_0.7_30deg": (0.7, 30.0), "robust_keep1_nogate": (1.0, None), "robust_keep1_30deg": (1.0, 30.0)}
 
 
 def call(est, form, h):
