@@ -961,6 +961,33 @@ public:
         return r;
     }
 
+    // Refinement on the visible surface (stocs_refine_poses_visible; no reference counterpart): the camera-frame poses refined against the
+    // frame of set_frame on the surface of the mesh of set_mesh that each pose shows, projective point-to-plane on every depth pixel under
+    // the rendered silhouette.  One record per pose in input order, describing the last evaluation; `refined` (when given) receives the
+    // poses, a pose that could not be refined as it came.  max_iterations 0 scores the poses and changes nothing.  Empty on error (the
+    // text goes to the log).
+    static stocs_refine_visible_params default_refine_visible_params() {
+        stocs_refine_visible_params p;
+        stocs_default_refine_visible_params(&p);
+        return p;
+    }
+    std::vector<stocs_refine_visible_result> refine_poses_visible(const std::vector<PoseCandidate*>& poses, std::vector<MatrixType>* refined = NULL,
+                                                                  const stocs_refine_visible_params& prm = default_refine_visible_params()) {
+        const int n = (int)poses.size();
+        std::vector<float> P((size_t)n * 16), Q((size_t)n * 16);
+        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], poses[(size_t)i]->transform.data(), 64);
+        std::vector<stocs_refine_visible_result> r((size_t)n);
+        if (refined) refined->assign((size_t)n, MatrixType());
+        if (n > 0 && stocs_refine_poses_visible(ctx_, P.data(), n, &prm, Q.data(), r.data()) != STOCS_OK) {
+            *log_ << "refine_poses_visible failed: " << stocs_last_error() << std::endl;
+            r.clear();
+            if (refined) refined->clear();
+            return r;
+        }
+        for (int i = 0; refined && i < n; ++i) std::memcpy((*refined)[(size_t)i].data(), &Q[(size_t)i * 16], 64);
+        return r;
+    }
+
     // Multi-instance selection (stocs_select_instances; no reference counterpart): which of the camera-frame hypotheses (the
     // hypotheses of run_trials, refined or not) are distinct instances of the object and which are one instance found twice.  Walked
     // best first, a hypothesis is kept only if enough of the scene points it explains are explained by none kept before it.  One record

@@ -1198,7 +1198,8 @@ int stocs_mesh_last_call_timing(const stocs_ctx* ctx, const char** labels, doubl
  * stocs_render_mesh_last_device_ms: with the option "device_clock" on, the HIP-event time in ms of the key render and of the (last
  * chunk's) resolve kernel of the last call of 1-3 on this context; -1 for what that call did not run or did not time.
  * Known limits: resolve rasterises every pose a second time (the key buffer keeps only the winners' depths); the depth check
- * (stocs_depth_check_poses), trial batches and the tracker still see the model as points. ---- */
+ * (stocs_depth_check_poses), trial batches and the tracker still see the model as points (a pose can be refined on the mesh by
+ * stocs_refine_poses_visible below, as a step of its own). ---- */
 int stocs_render_poses_mesh(stocs_ctx* ctx, const float* pose16_camera, int n, int id_base, void* d_zkey, int clear);
 int stocs_render_resolve_mesh(stocs_ctx* ctx, const float* pose16_camera, int n, int id_base, const stocs_render_params* p, const void* d_zkey,
                               stocs_render_result* out);
@@ -1207,6 +1208,87 @@ int stocs_explain_poses_mesh(stocs_ctx* ctx, const float* pose16_camera, int n, 
 int stocs_scene_footprints_mesh(stocs_ctx* ctx, const float* pose16_camera, int n, int slot_base, int n_slots, const stocs_render_params* p,
                                 int claim, void* d_rows, stocs_scene_record* out);
 int stocs_render_mesh_last_device_ms(const stocs_ctx* ctx, float* key_ms, float* resolve_ms);
+
+/* ---- refinement on the visible surface: projective, point-to-plane refinement of n CAMERA-frame poses of the mesh of stocs_ctx_set_mesh
+ * against the frame of stocs_ctx_set_frame (no reference counterpart).  stocs_refine_poses pairs a voxel-sampled scene segment with the
+ * nearest point of the whole model cloud, far side included; this one needs no segment, uses every depth pixel under the rendered
+ * silhouette and pairs it with the surface the camera sees there at the current hypothesis, under the exact normal of the facet.
+ * csrc/refine_visible.hip, restated in numpy in tests/refine_visible_ref.py: keys and states equal bit for bit, sums and poses within the
+ * rounding of the double sums.
+ * Per iteration and pose P: render, accumulate, solve.
+ *   The render is the mesh contract above with one addition: a hit pixel gets key = min(key, (uint64_t)bits(z) << 32 | t), t the index of
+ *   the triangle; empty is all ones.  The nearest surface wins and on equal depth bits the lowest triangle index; a minimum: independent of
+ *   order, batch, chunk and kernel form (STOCS_MESH_FORM).
+ * Steps 1-3 in float, every operation one IEEE operation, no contraction; step 4 in double from those floats.  For pixel (r, c) with a
+ * non-empty key (z the float in the high word, t the low word):
+ *   1. xn = ((float)c - cx) / fx, yn = ((float)r - cy) / fy (the mesh rule's ray); model point p = (xn z, yn z, z).
+ *      raw = depth[r W + c]; raw == 0: no_depth.  d = (float)raw * depth_scale, q = (xn d, yn d, d).  With a class image:
+ *      cp = (float)((double)prob[r W + c] * (1.0 / 10000)) (step 6 of the depth-check contract); cp < class_threshold: off_class.
+ *   2. e = p - q, D = e_x e_x + (e_y e_y + e_z e_z); D > max_distance * max_distance (the product in float): too_far; equality is not.
+ *      This is what drops occluders and background.
+ *   3. A, B, C: the triangle's camera points (the mesh contract's vertex rule).  u = B - A, w = C - A,
+ *      m = (u_y w_z - u_z w_y, u_z w_x - u_x w_z, u_x w_y - u_y w_x);  s = m_x p_x + (m_y p_y + m_z p_z), mm and pp likewise from m, m and
+ *      p, p.  m.m == 0 (a degenerate facet), or s s < (min_view_cos * min_view_cos) * (mm * pp): grazing.  min_view_cos == 0: only
+ *      degenerate facets are.
+ *   4. a pixel that passes 1-3 is counted.  In double: len = sqrt(m_x m_x + (m_y m_y + m_z m_z)), n = (g m) / len per component with
+ *      g = -1 when s > 0 (the float of step 3), else 1: the normal faces the camera, whatever the winding.
+ *      a = (q x n, n) = (q_y n_z - q_z n_y, q_z n_x - q_x n_z, q_x n_y - q_y n_x, n_x, n_y, n_z),
+ *      b = (n_x (q_x - p_x) + n_y (q_y - p_y)) + n_z (q_z - p_z).
+ *      The row linearises n'.(p' - q) for a small motion Delta = (Rz(gamma) Ry(beta) Rx(alpha), t) applied ON THE LEFT, in the camera frame;
+ *      the normal turns with the point: r ~ n.(p - q) + omega.(q x n) + t.n.
+ *   5. the 29 sums over the counted pixels, in double: [0..20] the upper triangle of A^T A row by row, [21..26] A^T b, [27] the count,
+ *      [28] b^T b.
+ *   6. count < 6, or a pivot of the 6x6 elimination (partial pivoting) below 1e-300: the pose is frozen, keeps its current value and is
+ *      evaluated no more.  Otherwise x = (alpha, beta, gamma, t) solves A^T A x = A^T b, R = Rz Ry Rx, and P <- (float)(Delta P): entry
+ *      (r, c), r < 3, is (R_r0 P_0c + R_r1 P_1c) + R_r2 P_2c, plus t_r for c = 3, in double, rounded to float; the last row stays.  The
+ *      pose is a float pose between iterations: an iteration is a pure function of 16 floats.
+ *   7. a pose with a non-finite used entry, or the all-zero record, renders nothing, comes back bit for bit with a zero record and is no
+ *      error.
+ * max_iterations == 0 evaluates once and updates nothing: the pose comes back bit for bit and the record is a dense depth score of it.
+ * The record describes the LAST EVALUATION, the pose before the last update (n_corr of stocs_refine_poses has the same convention):
+ * present = no_depth + off_class + too_far + grazing + counted is the number of non-empty keys; iterations the updates applied; frozen 1
+ * when step 6 froze the pose.
+ * stocs_refine_visible_detail: ONE pose, one evaluation, no update (max_iterations is checked and not used): the keys (H W, or NULL),
+ * per pixel state 0 empty, 1 no_depth, 2 off_class, 3 too_far, 4 grazing, 5 counted (H W, or NULL; the tests in the order of the steps)
+ * and the 29 sums.  A synchronous diagnosis path with pageable copies.
+ * Checked in the order of the mesh entry points: NULL ctx, n < 0 (STOCS_ERR_INVALID); n == 0 is a no-op; NULL pointers, parameters out of
+ * range (STOCS_ERR_INVALID); no mesh (STOCS_ERR_STATE); no frame or a frame whose size does not match (STOCS_ERR_STATE).
+ * Its own grow-only workspace on the context (a second call of the same or a smaller size allocates nothing; stocs_ctx_destroy frees
+ * it); poses go up and poses and records come back through the pinned block: one read-back and one synchronisation per call of
+ * stocs_refine_poses_visible.  Everything between runs on the context's stream.
+ * The kernels (csrc/refine_visible.hip).  Key buffers live in chunks of 256 MB (STOCS_REFINE_VISIBLE_CHUNK=<poses> in the environment
+ * forces a size); all iterations of a chunk run before the next chunk starts.  Accumulate: a grid of (G, pose), G =
+ * stocs_refine_visible_groups(width, height) = min(64, max(1, pixels / 2048)); workgroup g walks rows r0 + g, r0 + g + G, ... of the
+ * pose's rectangle in runs of 64 pixels per wavefront; 29 double sums per lane, a butterfly, the four waves in order, one partial per
+ * workgroup, no float atomics; it puts the empty key back where it found one, so only what a render wrote is cleared between
+ * iterations.  Solve: one wavefront per pose.  A pose's result is bitwise independent of the batch, of its position in it and of the
+ * chunk.  stocs_refine_visible_last_device_ms: with the option "device_clock" on, the HIP-event time in ms of the render, the
+ * accumulation and the solve of the last iteration of the last chunk of the last call; -1 otherwise.
+ * Known limits: same-pixel association has no pull from frame pixels outside the rendered silhouette, so a pose that is off by more
+ * than max_distance along the rays, or by more than the object's width across them, does not come back; the step of 6 is undamped and
+ * its rotation is about the camera's origin: where the visible surface constrains a motion weakly (a solid of revolution) it can be large
+ * and leave the pose worse than it came (measured: DESIGN.md 7.19); no trimming by rank; the float pose is not re-orthonormalised
+ * between iterations; not part of trial batches or the tracker. ---- */
+typedef struct stocs_refine_visible_params {
+    int32_t max_iterations;     /* >= 0 (default 5)                                            */
+    float   max_distance;       /* m, > 0 finite (default 0.02)                                */
+    float   min_view_cos;       /* 0 <= . < 1 (default 0: off)                                 */
+    float   class_threshold;    /* finite (default 0.10); unused without a class image         */
+} stocs_refine_visible_params;     /* 16 bytes */
+typedef struct stocs_refine_visible_result {
+    int32_t present, no_depth, off_class, too_far, grazing, counted;  /* present = their sum  */
+    int32_t iterations, frozen;
+    float   rms;                /* sqrtf((float)(btb / count)), 0 when count == 0              */
+    int32_t reserved;
+} stocs_refine_visible_result;     /* 40 bytes */
+void stocs_default_refine_visible_params(stocs_refine_visible_params* p);
+int stocs_check_refine_visible_params(const stocs_refine_visible_params* p);   /* host only */
+int stocs_refine_visible_groups(int width, int height);                        /* host only; 0 for a size below 1 */
+int stocs_refine_poses_visible(stocs_ctx* ctx, const float* pose16_camera, int n, const stocs_refine_visible_params* p, float* pose16_out,
+                               stocs_refine_visible_result* out);
+int stocs_refine_visible_detail(stocs_ctx* ctx, const float* pose16_camera /* one */, const stocs_refine_visible_params* p,
+                                uint64_t* keys /* H*W or NULL */, uint8_t* state /* H*W or NULL */, double* sums29);
+int stocs_refine_visible_last_device_ms(const stocs_ctx* ctx, float* render_ms, float* accumulate_ms, float* solve_ms);
 
 /* ---- mesh models: a triangle mesh sampled into the oriented model cloud the search needs (no reference counterpart).  Stand-alone like
  * stocs_preprocess_model: no context; the same cached per-thread workspace and pinned block (stocs_trim gives them back; a second call of

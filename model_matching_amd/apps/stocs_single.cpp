@@ -72,6 +72,12 @@
 // --surface points|mesh (default points; mesh needs --mesh <ply> and --masks with --instances M, refused before any search otherwise): with
 // mesh the "mask r:" lines and the label image come from the exact rasteriser on that mesh (stocs_explain_poses_mesh) and every line ends
 // in " mesh=<triangles>".  --mesh then needs no --vsd.  Several objects with --scene-select stay on points: one mesh file names one object.
+// --refine-visible K[,dist[,cos]] (needs --mesh <ply>, a scene directory, a single object; --mesh then needs no --vsd): after every other
+// step, the pose this run wrote to <out> is refined on the mesh against the frame's own depth image and class-probability map
+// (stocs_refine_poses_visible: K iterations, max_distance dist and min_view_cos cos, the library's defaults unless given) and <out> is
+// written again from the result; K = 0 scores the pose and leaves the file.  One "refine-visible <object>: iterations=.. frozen=..
+// present=.. no_depth=.. off_class=.. too_far=.. grazing=.. counted=.. rms=.. mesh=<triangles>" line and the refined "pose:" line; with
+// --gt a "refine-visible <object> before: add=.. adds=.." and an "after" line (stocs_pose_errors), and the gt lines score the refined file.
 // --masks (with --instances M, a scene directory): the selected instances, in rank order, rendered together against the frame's depth image
 // and class-probability map (stocs_explain_poses); one "mask r: footprint .. visible .. hidden .. agree .. in_front .. behind .. no_depth ..
 // on_mask .." line per instance, and the label image to labels_<object>.pgm next to <out>: binary 16-bit PGM (P5, maxval 65535, most
@@ -361,12 +367,53 @@ static bool read_pose_file(const std::string& path, MatrixType& m) {
 // --gt: the pose this run wrote to out_path, read back with the reader the ground truth goes through (what is scored is what a reader of
 // the file gets), against the ground truth: ADD, ADD-S, their maxima, the model's diameter (stocs_pose_errors, stocs_model_diameter); with
 // --trials N also the share of the trials' winners (full precision, a trial without a pose left out) within 0.1 diameter
+struct RefineVisibleOptions { bool on; int iterations; float distance, view_cos; int mesh_triangles; };   // --refine-visible K[,dist[,cos]]; a value < 0 leaves the library's default
 struct VsdOptions { bool on; float delta, surfel_radius; int mesh_triangles; };   // --vsd; a value <= 0 leaves the library's default; mesh_triangles > 0: --mesh
 
 // the ten errors of a VSD record as " e0=... .. e9=..." at b + at; returns the new end
 static int print_vsd_errors(char* b, size_t cap, int at, const stocs_vsd_record& r, int n_tau) {
     for (int t = 0; t < n_tau; ++t) at += snprintf(b + at, cap - (size_t)at, " e%d=%.9g", t, (double)r.e[t]);
     return at;
+}
+
+// --refine-visible: the pose this run wrote to out_path, read back as --gt reads it, refined on the mesh against the frame; out_path is
+// written again in the format the search writes it
+static int run_refine_visible(stocs::stocs_estimator& est, const RefineVisibleOptions& rv, const std::string& out_path, const std::string& object, const std::string& gt_path) {
+    MatrixType p, g;
+    if (!read_pose_file(out_path, p)) { std::cout << "refine-visible " << object << ": no pose" << std::endl; return 0; }
+    stocs_refine_visible_params prm = stocs::stocs_estimator::default_refine_visible_params();
+    prm.max_iterations = rv.iterations;
+    if (rv.distance >= 0.0f) prm.max_distance = rv.distance;
+    if (rv.view_cos >= 0.0f) prm.min_view_cos = rv.view_cos;
+    PoseCandidate e(p, 0.0f, -1.0f);
+    std::vector<MatrixType> refined;
+    const std::vector<stocs_refine_visible_result> r = est.refine_poses_visible(std::vector<PoseCandidate*>(1, &e), &refined, prm);
+    if (r.size() != 1 || refined.size() != 1) { std::cerr << "refine-visible failed: " << stocs_last_error() << std::endl; return 2; }
+    char b[512];
+    snprintf(b, sizeof(b), "refine-visible %s: iterations=%d frozen=%d present=%d no_depth=%d off_class=%d too_far=%d grazing=%d counted=%d rms=%.9g mesh=%d", object.c_str(),
+             r[0].iterations, r[0].frozen, r[0].present, r[0].no_depth, r[0].off_class, r[0].too_far, r[0].grazing, r[0].counted, (double)r[0].rms, rv.mesh_triangles);
+    std::cout << b << std::endl;
+    if (r[0].iterations > 0) {
+        std::ofstream f(out_path, std::ofstream::out);
+        for (int i = 0; i < 3; ++i) for (int j = 0; j < 4; ++j) f << refined[0](i, j) << (i == 2 && j == 3 ? "" : " ");
+        f << std::endl;
+    }
+    std::cout << "pose:";
+    for (int i = 0; i < 3; ++i) for (int j = 0; j < 4; ++j) { char t[32]; snprintf(t, sizeof(t), " %.9g", (double)refined[0](i, j)); std::cout << t; }
+    std::cout << std::endl;
+    if (!gt_path.empty() && read_pose_file(gt_path, g)) {
+        PoseCandidate gt(g, 0.0f, -1.0f), a(refined[0], 0.0f, -1.0f);
+        std::vector<PoseCandidate*> both;
+        both.push_back(&e); both.push_back(&a);
+        const std::vector<stocs_pose_error> q = est.pose_errors(both, std::vector<PoseCandidate*>(1, &gt));
+        if (q.size() != 2) { std::cerr << "pose errors failed: " << stocs_last_error() << std::endl; return 2; }
+        for (int k = 0; k < 2; ++k) {
+            snprintf(b, sizeof(b), "refine-visible %s %s: add=%.9g add_max=%.9g adds=%.9g adds_max=%.9g valid=%d", object.c_str(), k ? "after" : "before", (double)q[(size_t)k].add,
+                     (double)q[(size_t)k].add_max, (double)q[(size_t)k].adds, (double)q[(size_t)k].adds_max, q[(size_t)k].valid);
+            std::cout << b << std::endl;
+        }
+    }
+    return 0;
 }
 
 static int report_gt(stocs::stocs_estimator& est, const std::string& gt_path, const std::string& out_path, const std::string& object,
@@ -673,6 +720,7 @@ int main(int argc, char** argv) {
     bool do_instances = false, do_masks = false, have_trim = false, have_gate = false;
     SceneSelectOptions scene_opt = {false, false, 0};
     VsdOptions vsd_opt = {false, 0.0f, 0.0f, 0};
+    RefineVisibleOptions rv_opt = {false, 0, -1.0f, -1.0f, 0};
     std::string mesh_path, surface = "points";
     bool have_vsd_delta = false, have_surfel_radius = false;
     stocs_instance_params inst_prm = stocs::stocs_estimator::default_instance_params();
@@ -715,6 +763,14 @@ int main(int argc, char** argv) {
         else if (k == "--vsd-delta") { vsd_opt.delta = (float)atof(v.c_str()); have_vsd_delta = true; }
         else if (k == "--surfel-radius") { vsd_opt.surfel_radius = (float)atof(v.c_str()); have_surfel_radius = true; }
         else if (k == "--surface") surface = v;   // points | mesh: what --masks renders
+        else if (k == "--refine-visible") {   // K[,dist[,cos]]: the written pose refined on the mesh against the frame (needs --mesh)
+            char tail = 0;
+            const int got = sscanf(v.c_str(), "%d,%f,%f%c", &rv_opt.iterations, &rv_opt.distance, &rv_opt.view_cos, &tail);
+            const size_t commas = (size_t)std::count(v.begin(), v.end(), ',');
+            rv_opt.on = true;
+            if (got < 1 || got > 3 || commas + 1 != (size_t)got) rv_opt.iterations = -1;   // not K[,dist[,cos]]: refused below
+            if ((got >= 2 && !(rv_opt.distance > 0.0f)) || (got == 3 && !(rv_opt.view_cos >= 0.0f))) rv_opt.iterations = -1;   // (a value below 0 means "not given")
+        }
         else if (k == "--mesh") mesh_path = v;   // with --vsd: the model as a triangle mesh, rasterised in place of the surfels
         else if (k == "--instances") { do_instances = true; inst_prm.max_instances = atoi(v.c_str()); }
         else if (k == "--instance-min-fraction") inst_prm.min_exclusive_fraction = (float)atof(v.c_str());
@@ -753,7 +809,7 @@ int main(int argc, char** argv) {
         return -1;
     }
     if (!mesh_path.empty()) {   // refused before any search
-        if ((!vsd_opt.on && !surface_mesh) || have_surfel_radius) { std::cerr << "--mesh <ply> needs --vsd and takes no --surfel-radius" << std::endl; return -1; }
+        if ((!vsd_opt.on && !surface_mesh && !rv_opt.on) || have_surfel_radius) { std::cerr << "--mesh <ply> needs --vsd and takes no --surfel-radius" << std::endl; return -1; }
         int nv = 0, nt = 0;
         if (stocs_ply_read_mesh(mesh_path.c_str(), NULL, 0, &nv, NULL, 0, &nt) != STOCS_OK) { std::cerr << "cannot read a mesh from " << mesh_path << ": " << stocs_last_error() << std::endl; return 1; }
         if (nt < 1) { std::cerr << mesh_path << " has no faces" << std::endl; return 1; }
@@ -764,6 +820,18 @@ int main(int argc, char** argv) {
         }
         if (vsd_opt.on) vsd_opt.mesh_triangles = nt;
         if (surface_mesh) g_mask_mesh_triangles = nt;
+        if (rv_opt.on) rv_opt.mesh_triangles = nt;
+    }
+    if (rv_opt.on) {   // refused before any search
+        stocs_refine_visible_params rp = stocs::stocs_estimator::default_refine_visible_params();
+        rp.max_iterations = rv_opt.iterations;
+        if (rv_opt.distance >= 0.0f) rp.max_distance = rv_opt.distance;
+        if (rv_opt.view_cos >= 0.0f) rp.min_view_cos = rv_opt.view_cos;
+        if (mesh_path.empty() || clouds || a2.find(',') != std::string::npos || stocs_check_refine_visible_params(&rp) != STOCS_OK || !(rv_opt.distance == rv_opt.distance) ||
+            !(rv_opt.view_cos == rv_opt.view_cos)) {
+            std::cerr << "--refine-visible K[,dist[,cos]] needs --mesh <ply>, a scene directory, a single object, K >= 0, dist > 0 and 0 <= cos < 1" << std::endl;
+            return -1;
+        }
     }
     if (vsd_opt.on || have_vsd_delta || have_surfel_radius) {   // refused before any search
         if (!vsd_opt.on || gt_path.empty() || clouds || a2.find(',') != std::string::npos) {
@@ -865,7 +933,7 @@ int main(int argc, char** argv) {
             est.reset(new stocs::stocs_estimator(model_path, model_map, rgb_path, depth_path, class_probability_path, edge_probability_path, dbg_dir, cam_intrinsics,
                                                  image_width, image_height, depth_scale, 1.0f, voxel_size, distance_threshold, ppf_tr_discretization,
                                                  ppf_rot_discretization, edge_threshold, class_threshold));
-            if (depth_check || do_masks || vsd_opt.on) {   // the frame the scene was ingested from, for stocs_depth_check_poses / stocs_explain_poses / stocs_pose_errors_vsd
+            if (depth_check || do_masks || vsd_opt.on || rv_opt.on) {   // the frame the scene was ingested from, for stocs_depth_check_poses / stocs_explain_poses / stocs_pose_errors_vsd
                 std::vector<uint16_t> depth, prob;
                 stocs::read_image(depth_path, 1, 16, image_width, image_height, &depth);
                 stocs::read_image(class_probability_path, 1, 16, image_width, image_height, &prob);
@@ -896,6 +964,11 @@ int main(int argc, char** argv) {
     const int rc = !track_path.empty() ? run_track(*est, track_path, track_min_lcp, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine, &trial_results)
                                        : run_search(*est, std::cout, out_path, dbg_dir, seed, n_trials, exact_ties, do_cluster, n_refine, depth_check,
                                                     do_instances ? &inst_prm : NULL, instances_path, labels_path, &trial_results);
+    if (rc == 0 && rv_opt.on) {   // after every other step, on the pose the run wrote
+        if (!est->set_mesh(mesh_v, mesh_t)) { std::cerr << "set_mesh failed: " << stocs_last_error() << std::endl; return 2; }
+        const int r2 = run_refine_visible(*est, rv_opt, out_path, object, gt_path);
+        if (r2 != 0) return r2;
+    }
     if (rc != 0 || gt_path.empty()) return rc;
     if (vsd_opt.mesh_triangles > 0 && !est->set_mesh(mesh_v, mesh_t)) { std::cerr << "set_mesh failed: " << stocs_last_error() << std::endl; return 2; }
     stocs_camera cam;   // a scene directory has a camera: MSPD is reported too

@@ -128,6 +128,15 @@ class RenderResult(C.Structure):
                 ("in_front", C.c_int32), ("behind", C.c_int32), ("on_mask", C.c_int32)]
 
 
+class RefineVisibleParams(C.Structure):
+    _fields_ = [("max_iterations", C.c_int32), ("max_distance", C.c_float), ("min_view_cos", C.c_float), ("class_threshold", C.c_float)]
+
+
+class RefineVisibleResult(C.Structure):
+    _fields_ = [("present", C.c_int32), ("no_depth", C.c_int32), ("off_class", C.c_int32), ("too_far", C.c_int32), ("grazing", C.c_int32),
+                ("counted", C.c_int32), ("iterations", C.c_int32), ("frozen", C.c_int32), ("rms", C.c_float), ("reserved", C.c_int32)]
+
+
 class SceneRecord(C.Structure):
     _fields_ = [("footprint", C.c_int32), ("no_depth", C.c_int32), ("agree", C.c_int32), ("in_front", C.c_int32), ("behind", C.c_int32),
                 ("on_mask", C.c_int32), ("claimed", C.c_int32)]
@@ -263,6 +272,12 @@ SIGNATURES = {
     "stocs_explain_poses_mesh": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(RenderParams), C.POINTER(RenderResult), _ip, _u8p]),
     "stocs_scene_footprints_mesh": (C.c_int, [_vp, _fp, C.c_int, C.c_int, C.c_int, C.POINTER(RenderParams), C.c_int, _vp, C.POINTER(SceneRecord)]),
     "stocs_render_mesh_last_device_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "stocs_default_refine_visible_params": (None, [C.POINTER(RefineVisibleParams)]),
+    "stocs_check_refine_visible_params": (C.c_int, [C.POINTER(RefineVisibleParams)]),
+    "stocs_refine_visible_groups": (C.c_int, [C.c_int, C.c_int]),
+    "stocs_refine_poses_visible": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(RefineVisibleParams), _fp, C.POINTER(RefineVisibleResult)]),
+    "stocs_refine_visible_detail": (C.c_int, [_vp, _fp, C.POINTER(RefineVisibleParams), C.POINTER(C.c_uint64), _u8p, C.POINTER(C.c_double)]),
+    "stocs_refine_visible_last_device_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "stocs_mesh_sample_counts": (C.c_int, [_fp, C.c_int, _ip, C.c_int, C.c_float, C.c_uint64, C.c_int, _ip, C.POINTER(C.c_double), _i64p, _intp]),
     "stocs_mesh_sample": (C.c_int, [_fp, C.c_int, _ip, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, _fp, _fp, _ip, C.c_int, _intp]),
     "stocs_preprocess_model_mesh": (C.c_int, [_fp, C.c_int, _ip, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_float, C.c_float, C.c_int, _fp, _fp, C.c_int, _intp]),

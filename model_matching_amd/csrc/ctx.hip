@@ -550,6 +550,7 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
     c->vsd = NULL;
     c->mesh = NULL;
     c->render_mesh = NULL;
+    c->refine_visible = NULL;
     c->inst = NULL;
     c->trials = NULL; c->snrmw_trial0 = NULL; c->snrmw_stride = 0; c->snrmw_override = NULL; c->lcp_cand_trial = NULL;
     c->d_cand = NULL; c->cand_bytes = 0; c->n_cands = 0; c->cand_cap = 0; c->cands_stale = false;
@@ -722,6 +723,7 @@ int stocs_ctx_destroy(stocs_ctx* c) {
     stocs_internal_free_vsd(c);
     stocs_internal_free_mesh(c);
     stocs_internal_free_render_mesh(c);
+    stocs_internal_free_refine_visible(c);
     c->grid_mem.destroy(); c->grid_ws.destroy();
     c->order.free(); c->cdf.free(); c->kd.free();
     if (c->h_pin) (void)hipHostFree(c->h_pin);

@@ -8,7 +8,9 @@
 // kernel and the record read-back.  This file only fills z-buffers -- and, for render_mesh.hip (render_shared.h), key buffers: the kernel
 // and its helpers are templates on the pixel sink, DepthSink (a z-buffer of float bits per pose, 32-bit atomicMin) or KeySink (one buffer
 // of (float bits << 32 | id) for all poses of the launch, 64-bit atomicMin, the id in a scalar register).  The set-up, the tiers and the
-// forms below are the same text for both.
+// forms below are the same text for both.  TriKeySink (refine_visible.hip) is the third: pose h has its own buffer of
+// (float bits << 32 | triangle index), so the winner of a pixel names its facet.  It alone asks for the index (Sink::wants_tri): the
+// extra readlane and the extra LDS array are behind `if constexpr`, and the other two instantiations are the instructions they were.
 //   render    mesh_render_kernel: a workgroup of four wavefronts per (pose, 256 triangles), the pose in scalar registers.  A wavefront sets up
 //             64 triangles, one per lane: three vertex gathers, the transform, the clamped box, the three edge normals.  Then per triangle:
 //               small   a box of at most STOCS_MESH_SMALL_PX pixels: its lane walks it (a dense mesh: a handful of pixels per triangle, and
@@ -59,9 +61,10 @@ struct MeshTri {
 // DepthSink: pose h of the launch has its own z-buffer at zbuf + h * npix, a minimum of float bits (stocs_render_depth_mesh)
 struct DepthSink {
     typedef uint32_t* Target;
+    static constexpr bool wants_tri = false;
     uint32_t* z;
     __device__ __forceinline__ DepthSink(Target zbuf, int h, size_t npix) : z(zbuf + (size_t)h * npix) {}
-    __device__ __forceinline__ void hit(size_t px, uint32_t bits, int read_first) const {
+    __device__ __forceinline__ void hit(size_t px, uint32_t bits, int read_first, int) const {
         uint32_t* cell = &z[px];
         if (!read_first || bits < *cell) atomicMin(cell, bits);
     }
@@ -70,19 +73,33 @@ struct DepthSink {
 struct KeyTarget { unsigned long long* zkey; int id_base; };
 struct KeySink {
     typedef KeyTarget Target;
+    static constexpr bool wants_tri = false;
     unsigned long long* z;
     unsigned long long id;
     __device__ __forceinline__ KeySink(Target t, int h, size_t) : z(t.zkey), id((unsigned long long)(unsigned)(t.id_base + h)) {}
-    __device__ __forceinline__ void hit(size_t px, uint32_t bits, int read_first) const {
+    __device__ __forceinline__ void hit(size_t px, uint32_t bits, int read_first, int) const {
         unsigned long long* cell = &z[px];
         const unsigned long long key = ((unsigned long long)bits << 32) | id;
+        if (!read_first || key < *cell) atomicMin(cell, key);
+    }
+};
+// TriKeySink: pose h of the launch has its own key buffer at zkey + h * npix, a minimum of (float bits << 32 | triangle index): the
+// nearest surface, on equal depth bits the lowest triangle (stocs_refine_poses_visible)
+struct TriKeySink {
+    typedef unsigned long long* Target;
+    static constexpr bool wants_tri = true;
+    unsigned long long* z;
+    __device__ __forceinline__ TriKeySink(Target zkey, int h, size_t npix) : z(zkey + (size_t)h * npix) {}
+    __device__ __forceinline__ void hit(size_t px, uint32_t bits, int read_first, int tri) const {
+        unsigned long long* cell = &z[px];
+        const unsigned long long key = ((unsigned long long)bits << 32) | (unsigned long long)(unsigned)tri;
         if (!read_first || key < *cell) atomicMin(cell, key);
     }
 };
 
 // step 4 of the contract for pixel (r, c), 0 <= r < H, 0 <= c < W
 template <class Sink>
-__device__ __forceinline__ void mesh_pixel(const Sink& z, const DepthArgs& a, int read_first, int r, int c, const MeshTri& t) {
+__device__ __forceinline__ void mesh_pixel(const Sink& z, const DepthArgs& a, int read_first, int r, int c, const MeshTri& t, int tri) {
     const float xn = ((float)c - a.cx) / a.fx, yn = ((float)r - a.cy) / a.fy;
     const float u = xn * t.a0 + (yn * t.a1 + t.a2);
     const float v = xn * t.b0 + (yn * t.b1 + t.b2);
@@ -92,12 +109,12 @@ __device__ __forceinline__ void mesh_pixel(const Sink& z, const DepthArgs& a, in
     if (!inside || !(det != 0.0f)) return;
     const float zz = (u * t.za + (v * t.zb + w * t.zc)) / det;
     if (!(zz > 1e-6f)) return;
-    z.hit((size_t)r * (size_t)a.W + (size_t)c, __float_as_uint(zz), read_first);
+    z.hit((size_t)r * (size_t)a.W + (size_t)c, __float_as_uint(zz), read_first, tri);
 }
 
 // T = 1 << log_t threads (tid among them) sweep the box of t, whose values are uniform over them: tiles of tw x T / tw pixels
 template <class Sink>
-__device__ __forceinline__ void mesh_sweep(const Sink& z, const DepthArgs& a, int read_first, int tid, int log_t, const MeshTri& t) {
+__device__ __forceinline__ void mesh_sweep(const Sink& z, const DepthArgs& a, int read_first, int tid, int log_t, const MeshTri& t, int tri) {
     const int w = t.c_hi - t.c_lo + 1;
     int log_w = 0;
     while (log_w < 6 && (1 << log_w) < w) ++log_w;   // uniform: at most six rounds
@@ -107,7 +124,7 @@ __device__ __forceinline__ void mesh_sweep(const Sink& z, const DepthArgs& a, in
         const int r = r0 + dr;
         for (int c0 = t.c_lo; c0 <= t.c_hi; c0 += tw) {
             const int c = c0 + dc;
-            if (r <= t.r_hi && c <= t.c_hi) mesh_pixel(z, a, read_first, r, c, t);   // inside the clamped box: inside the frame
+            if (r <= t.r_hi && c <= t.c_hi) mesh_pixel(z, a, read_first, r, c, t, tri);   // inside the clamped box: inside the frame
         }
     }
 }
@@ -121,6 +138,7 @@ __global__ __launch_bounds__(256) void mesh_render_kernel(const float* __restric
     __shared__ float g_val[12][MESH_TRIS];
     __shared__ int g_box[4][MESH_TRIS];
     __shared__ int g_n;
+    __shared__ int g_tri[Sink::wants_tri ? MESH_TRIS : 1];   // the triangle of a slot, for the sink that keeps it
     const int h = (int)blockIdx.y;
     float P[16];
 #pragma unroll
@@ -163,7 +181,7 @@ __global__ __launch_bounds__(256) void mesh_render_kernel(const float* __restric
     const bool group = live && !small && npx > (long long)ma.group_px;
     if (small) {   // this lane's own box
         for (int r = t.r_lo; r <= t.r_hi; ++r)
-            for (int c = t.c_lo; c <= t.c_hi; ++c) mesh_pixel(z, a, ma.read_first, r, c, t);
+            for (int c = t.c_lo; c <= t.c_hi; ++c) mesh_pixel(z, a, ma.read_first, r, c, t, i);
     }
     unsigned long long todo = __ballot(live && !small && !group);
     while (todo) {   // wave-uniform: one triangle at a time, in scalar registers
@@ -175,13 +193,16 @@ __global__ __launch_bounds__(256) void mesh_render_kernel(const float* __restric
         s.c0 = lane_f(t.c0, src); s.c1 = lane_f(t.c1, src); s.c2 = lane_f(t.c2, src);
         s.za = lane_f(t.za, src); s.zb = lane_f(t.zb, src); s.zc = lane_f(t.zc, src);
         s.c_lo = lane_i(t.c_lo, src); s.c_hi = lane_i(t.c_hi, src); s.r_lo = lane_i(t.r_lo, src); s.r_hi = lane_i(t.r_hi, src);
-        mesh_sweep(z, a, ma.read_first, lane, 6, s);
+        int s_tri = 0;
+        if constexpr (Sink::wants_tri) s_tri = lane_i(i, src);
+        mesh_sweep(z, a, ma.read_first, lane, 6, s, s_tri);
     }
     if (group) {   // at most one per thread: slot < MESH_TRIS
         const int slot = atomicAdd(&g_n, 1);
         g_val[0][slot] = t.a0; g_val[1][slot] = t.a1; g_val[2][slot] = t.a2; g_val[3][slot] = t.b0; g_val[4][slot] = t.b1; g_val[5][slot] = t.b2;
         g_val[6][slot] = t.c0; g_val[7][slot] = t.c1; g_val[8][slot] = t.c2; g_val[9][slot] = t.za; g_val[10][slot] = t.zb; g_val[11][slot] = t.zc;
         g_box[0][slot] = t.c_lo; g_box[1][slot] = t.c_hi; g_box[2][slot] = t.r_lo; g_box[3][slot] = t.r_hi;
+        if constexpr (Sink::wants_tri) g_tri[slot] = i;
     }
     __syncthreads();   // every thread of the workgroup arrives: nothing above returns after the first barrier
     const int n_group = g_n;
@@ -193,7 +214,9 @@ __global__ __launch_bounds__(256) void mesh_render_kernel(const float* __restric
         s.za = uniform_f(g_val[9][e]); s.zb = uniform_f(g_val[10][e]); s.zc = uniform_f(g_val[11][e]);
         s.c_lo = __builtin_amdgcn_readfirstlane(g_box[0][e]); s.c_hi = __builtin_amdgcn_readfirstlane(g_box[1][e]);
         s.r_lo = __builtin_amdgcn_readfirstlane(g_box[2][e]); s.r_hi = __builtin_amdgcn_readfirstlane(g_box[3][e]);
-        mesh_sweep(z, a, ma.read_first, tid, 8, s);
+        int s_tri = 0;
+        if constexpr (Sink::wants_tri) s_tri = __builtin_amdgcn_readfirstlane(g_tri[e]);
+        mesh_sweep(z, a, ma.read_first, tid, 8, s, s_tri);
     }
     // the pose's rectangle: the union of the live triangles' boxes
     int b_nc0 = live ? -t.c_lo : (int)0x80808080, b_c1 = live ? t.c_hi : (int)0x80808080, b_nr0 = live ? -t.r_lo : (int)0x80808080, b_r1 = live ? t.r_hi : (int)0x80808080;
@@ -262,6 +285,23 @@ int mesh_enqueue_keys(stocs_ctx* c, const float* d_pose, int m, const DepthArgs&
         STOCS_HIP_CHECK(hipGetLastError());
     }
     return STOCS_OK;
+}
+
+int mesh_enqueue_tri_keys(stocs_ctx* c, const float* d_pose, int m, const DepthArgs& a, unsigned long long* d_zkey, int32_t* d_box) {
+    const MeshState* S = (const MeshState*)c->mesh;
+    const MeshArgs ma = mesh_args(S->nt);
+    const unsigned tri_chunks = (unsigned)((ma.nt + MESH_TRIS - 1) / MESH_TRIS);
+    // the pose is blockIdx.y: m <= 65 535, the caller's chunks see to that
+    hipLaunchKernelGGL(mesh_render_kernel<TriKeySink>, dim3(tri_chunks, (unsigned)m), dim3(256), 0, c->stream, d_pose, (const float4*)S->verts.p, (const int4*)S->tris.p, a, ma,
+                       d_zkey, d_box);
+    STOCS_HIP_CHECK(hipGetLastError());
+    return STOCS_OK;
+}
+
+// the mesh on the device for a kernel that reads facets by index (refine_visible.hip): nt int4 triangles, float4 vertices
+void mesh_device_arrays(const stocs_ctx* c, const float4** verts, const int4** tris) {
+    const MeshState* S = (const MeshState*)c->mesh;
+    *verts = (const float4*)S->verts.p; *tris = (const int4*)S->tris.p;
 }
 
 int mesh_triangles(const stocs_ctx* c) { return c->mesh ? ((const MeshState*)c->mesh)->nt : 0; }

@@ -49,6 +49,10 @@ int mesh_triangles(const stocs_ctx* c);
 int mesh_enqueue_depth(stocs_ctx* c, const float* d_pose, int m, const DepthArgs& a, uint32_t* d_z, int32_t* d_box);
 // ... all into the ONE key buffer at d_zkey, pose h under id id_base + h (the key sink); d_box as above
 int mesh_enqueue_keys(stocs_ctx* c, const float* d_pose, int m, const DepthArgs& a, int id_base, unsigned long long* d_zkey, int32_t* d_box);
+// ... pose h into its OWN key buffer at d_zkey + h * npix, the key's low word the winning triangle's index (the triangle-key sink); m <= 65 535
+int mesh_enqueue_tri_keys(stocs_ctx* c, const float* d_pose, int m, const DepthArgs& a, unsigned long long* d_zkey, int32_t* d_box);
+// the mesh's arrays on the device: float4 vertices (x, y, z, 0), int4 triangles (i0, i1, i2, 0)
+void mesh_device_arrays(const stocs_ctx* c, const float4** verts, const int4** tris);
 
 }  // namespace stocs
 

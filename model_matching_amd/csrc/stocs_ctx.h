@@ -403,6 +403,8 @@ struct stocs_ctx {
     void* mesh;            // mesh.hip (MeshState): the triangle mesh of stocs_ctx_set_mesh on the device (last: no other member moves)
 
     void* render_mesh;     // render_mesh.hip (RenderMeshState): the grow-only workspaces of stocs_render_poses_mesh and its kin (last: no other member moves)
+
+    void* refine_visible;  // refine_visible.hip (RefineVisibleState): the grow-only workspace of stocs_refine_poses_visible and its detail form (last: no other member moves)
 };
 
 namespace stocs {
@@ -491,6 +493,7 @@ extern "C" void stocs_internal_free_symmetry(stocs_ctx* c);
 extern "C" void stocs_internal_free_vsd(stocs_ctx* c);
 extern "C" void stocs_internal_free_mesh(stocs_ctx* c);
 extern "C" void stocs_internal_free_render_mesh(stocs_ctx* c);
+extern "C" void stocs_internal_free_refine_visible(stocs_ctx* c);
 // the congruent phase with a ceiling on its device memory: *too_big != 0 (and STOCS_OK) when the pair lists of the context's base set
 // would need more than max_bytes (0: no ceiling) or exceed 2^32 entries -- a trial batch then splits the base set and tries again
 extern "C" int stocs_internal_find_congruent(stocs_ctx* c, int64_t* total_quads, size_t max_bytes, int* too_big);

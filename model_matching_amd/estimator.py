@@ -59,6 +59,8 @@ _RENDER_DTYPE = np.dtype([(f[0], np.int32) for f in capi.RenderResult._fields_])
 assert _RENDER_DTYPE.itemsize == C.sizeof(capi.RenderResult)
 _INSTANCE_DTYPE = np.dtype([("rank", np.int32), ("own", np.int32), ("exclusive", np.int32), ("lcp", np.float32)])
 assert _INSTANCE_DTYPE.itemsize == C.sizeof(capi.InstanceResult)
+_REFINE_VISIBLE_DTYPE = np.dtype([(f[0], np.float32 if f[0] == "rms" else np.int32) for f in capi.RefineVisibleResult._fields_])
+assert _REFINE_VISIBLE_DTYPE.itemsize == C.sizeof(capi.RefineVisibleResult)
 _SCENE_RECORD_DTYPE = np.dtype([(f[0], np.int32) for f in capi.SceneRecord._fields_])
 assert _SCENE_RECORD_DTYPE.itemsize == C.sizeof(capi.SceneRecord)
 _SCENE_RESULT_DTYPE = np.dtype([(f[0], np.int32) for f in capi.SceneResult._fields_])
@@ -777,6 +779,52 @@ class StocsEstimator:
         a, b = C.c_float(-1), C.c_float(-1)
         capi.check(self.L.stocs_render_mesh_last_device_ms(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
+
+    def _refine_visible_params(self, who, params):
+        prm = capi.RefineVisibleParams()
+        self.L.stocs_default_refine_visible_params(C.byref(prm))
+        for k, v in params.items():
+            if k not in dict(capi.RefineVisibleParams._fields_):
+                raise TypeError("%s: unknown parameter %r" % (who, k))
+            setattr(prm, k, v)
+        return prm
+
+    def refine_poses_visible(self, poses16, **params):
+        """n camera-frame poses of the mesh of set_mesh refined against the frame of set_frame on the surface each pose shows
+        (stocs_refine_poses_visible): projective point-to-plane, every depth pixel under the rendered silhouette -> (poses (n, 16)
+        float32, records): a structured array with the fields of stocs_refine_visible_result, one per pose, describing the last
+        evaluation.  params: max_iterations, max_distance, min_view_cos, class_threshold over the library's defaults;
+        max_iterations=0 scores the poses and changes nothing."""
+        P, pP = capi.f32(poses16)
+        if P.size % 16:
+            raise ValueError("refine_poses_visible: poses are 16 floats each")
+        n = P.size // 16
+        prm = self._refine_visible_params("refine_poses_visible", params)
+        out = np.zeros((n, 16), np.float32)
+        buf = (capi.RefineVisibleResult * max(n, 1))()
+        capi.check(self.L.stocs_refine_poses_visible(self.h, pP, n, C.byref(prm), out.ctypes.data_as(capi._fp), buf))
+        return out, np.frombuffer(buf, dtype=_REFINE_VISIBLE_DTYPE, count=n).copy()
+
+    def refine_visible_detail(self, pose16, **params):
+        """One evaluation of one pose as refine_poses_visible makes it (stocs_refine_visible_detail) -> (keys (height, width) uint64:
+        float bits of the depth << 32 | triangle, all ones where empty; state (height, width) uint8: 0 empty, 1 no_depth, 2 off_class,
+        3 too_far, 4 grazing, 5 counted; the 29 sums float64)"""
+        P, pP = capi.f32(pose16)
+        if P.size != 16:
+            raise ValueError("refine_visible_detail: one pose of 16 floats")
+        prm = self._refine_visible_params("refine_visible_detail", params)
+        H, W = self._frame_shape("refine_visible_detail")
+        keys = np.zeros((H, W), np.uint64); st = np.zeros((H, W), np.uint8); sums = np.zeros(29, np.float64)
+        capi.check(self.L.stocs_refine_visible_detail(self.h, pP, C.byref(prm), keys.ctypes.data_as(C.POINTER(C.c_uint64)), st.ctypes.data_as(capi._u8p),
+                                                      sums.ctypes.data_as(C.POINTER(C.c_double))))
+        return keys, st, sums
+
+    def refine_visible_last_device_ms(self):
+        """(render, accumulation, solve) HIP-event ms of the last iteration of the last refine_poses_visible call with the option
+        device_clock on; -1: not taken"""
+        a, b, d = C.c_float(-1), C.c_float(-1), C.c_float(-1)
+        capi.check(self.L.stocs_refine_visible_last_device_ms(self.h, C.byref(a), C.byref(b), C.byref(d)))
+        return a.value, b.value, d.value
 
     def scene_select(self, rows, shape, score, group, rec, group_cap=None, **params):
         """The walk over slots 0 .. n-1 of the pool rows of a frame of shape (height, width) (stocs_scene_select): score (n,), group (n,)

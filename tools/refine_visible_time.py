@@ -1,0 +1,108 @@
+#!/usr/bin/env python3
+"""Time of StocsEstimator.refine_poses_visible (stocs_refine_poses_visible: per iteration one triangle-key render, one accumulation and one
+solve; one read-back and one synchronisation per call) for 1, 10, 64 and 256 hypotheses x 5 iterations on a 640 x 480 frame: the Cm meshes
+of levels 4 and 5 (synth.make_model_mesh) around synth.gt_pose() and tools/mesh_time.py's 12-triangle box that fills a third of the frame.
+The frame is the mesh's own depth image at the ground truth.  Median of 20 calls after 5 warm-up calls of the host wall clock, with the
+spread, and the median HIP-event time of the three kernels of the last iteration with the option device_clock on.  Beside the Cm rows, as
+orientation and not as a bar (another algorithm: a voxel-sampled scene segment against the model cloud), stocs_refine_poses on the same
+hypotheses in the centred frames of the Cm workload.  No time is promised.
+
+    python tools/refine_visible_time.py [--out profiles/refine_visible_time.json]
+
+Needs a GPU; no fallback."""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tools"))
+from depth_check_time import clock  # noqa: E402
+from mesh_time import box_mesh_and_pose, frame_from  # noqa: E402
+import mesh_time  # noqa: E402
+
+SIZES = (1, 10, 64, 256)
+REPS, WARM = 20, 5
+ITERATIONS = 5
+F = np.float32
+
+
+def perturbed(P0, n, seed, max_t=0.005, max_deg=3.0):
+    """n hypotheses around the 4x4 pose P0 as 4x4 matrices: <= max_deg about the object's position, <= max_t"""
+    from model_matching_amd import synth
+    rng = np.random.default_rng(seed)
+    out = []
+    for _ in range(n):
+        D = np.eye(4)
+        D[:3, :3] = synth._rot_axis_angle(rng.normal(size=3), np.radians(max_deg) * rng.uniform(-1, 1))
+        d = rng.normal(size=3)
+        D[:3, 3] = P0[:3, 3] - D[:3, :3] @ P0[:3, 3] + d / np.linalg.norm(d) * rng.uniform(0, max_t)
+        out.append(D @ P0)
+    return out
+
+
+def pose16(T):
+    return np.ascontiguousarray(np.asarray(T, np.float64).T.reshape(16), F)
+
+
+def device_medians(est, call):
+    est.set_option("device_clock", 1)
+    t = []
+    for i in range(WARM + REPS):
+        call()
+        if i >= WARM:
+            t.append(est.refine_visible_last_device_ms())
+    est.set_option("device_clock", 0)
+    return [float(x) for x in np.median(np.asarray(t), axis=0)]
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "refine_visible_time.json"))
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("refine_visible_time.py needs a GPU: no time is taken without one")
+    from model_matching_amd import synth
+    from model_matching_amd.estimator import StocsEstimator
+    mesh_time.K = [float(v) for v in synth.YCB_INTRINSICS]
+    m, s, _ = synth.workload("Cm")
+    est = StocsEstimator(s.pos, s.nrm, s.prob, s.pixel, m.pos, m.nrm, build_index=False)
+    cs, cm = est.get_scene_centroid().astype(np.float64), est.get_model_centroid().astype(np.float64)
+    bv, bt, bP = box_mesh_and_pose()
+    rows = []
+    for label, v, t, P0, with_points in (("Cm level 4", *synth.make_model_mesh(4), s.T_gt, True), ("Cm level 5", *synth.make_model_mesh(5), s.T_gt, True),
+                                          ("box 12 triangles", bv, bt, bP, False)):
+        est.set_mesh(v, t)
+        share = frame_from(est, np.asarray(P0, np.float64))
+        for n in SIZES:
+            hyp = perturbed(np.asarray(P0, np.float64), n, 100 + n)
+            poses = np.stack([pose16(T) for T in hyp])
+            call = lambda: est.refine_poses_visible(poses, max_iterations=ITERATIONS)
+            out, rec = call()
+            render_ms, acc_ms, solve_ms = device_medians(est, call)
+            row = {"workload": label, "triangles": int(len(t)), "frame_share": round(share, 3), "hypotheses": n, "iterations": ITERATIONS,
+                   "refine_poses_visible": clock(call), "render_kernel_ms": render_ms, "accumulate_kernel_ms": acc_ms, "solve_kernel_ms": solve_ms,
+                   "mean_counted": float(rec["counted"].mean()), "mean_iterations": float(rec["iterations"].mean()), "frozen": int(rec["frozen"].sum())}
+            if with_points:
+                T16 = np.stack([pose16(synth.centred_gt(T, cs, cm)) for T in hyp])
+                row["stocs_refine_poses_same_hypotheses"] = clock(lambda: est.refine_poses(T16, ITERATIONS, 0.035))
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    est.close()
+    out = {"what": "host wall clock of refine_poses_visible and HIP-event time of the three kernels of its last iteration; beside the Cm rows stocs_refine_poses on "
+                   "the same hypotheses (orientation: another algorithm, no bar)",
+           "device": torch.cuda.get_device_name(0), "reps": REPS, "warmup": WARM, "note": "one visit, one GPU; the host column shares the machine with other work",
+           "kernel_resources": "profiles/refine_visible.md (tools/kernel_resources.py refine_visible.hip mesh.hip)", "rows": rows}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
