@@ -1478,11 +1478,11 @@ static int reduce_lists(stocs_ctx* c, CongruentState* S, const PlanDev& plan, Pa
                        (const unsigned long long*)d_bits_p.p, (const uint32_t*)(d_surv.p + o_tp), L.pk_c.p, L.pv_c.p, d_po, 0);
     }
     STOCS_HIP_CHECK(hipGetLastError());
-    c->timing[0].lap("enqueue gather + occupancy + survivor counts");
-    if (S->deferred) { const int rd = S->deferred(); S->deferred = nullptr; if (rd) return rd; c->timing[0].lap("host: cone records of the bases (while the device gathers)"); }
+    c->timing[TIMING_CONGRUENT].lap("enqueue gather + occupancy + survivor counts");
+    if (S->deferred) { const int rd = S->deferred(); S->deferred = nullptr; if (rd) return rd; c->timing[TIMING_CONGRUENT].lap("host: cone records of the bases (while the device gathers)"); }
     STOCS_HIP_CHECK(hipEventSynchronize(c->ev_t[7]));   // the read-back, not the compaction behind it
     AU.host_sync_event(c->ev_t[7]);
-    c->timing[0].lap("wait for the device (survivors)");
+    c->timing[TIMING_CONGRUENT].lap("wait for the device (survivors)");
     if (po_pin) {   // the plan's own totals came with this read-back: were the capacities enough?
         if (po_pin->overflow || po_pin->totP > (unsigned long long)totP0 || po_pin->totQ > (unsigned long long)totQ0) {
             STOCS_HIP_CHECK(hipStreamSynchronize(st));            // the compaction behind the read-back: nothing may still touch the arena
@@ -1533,7 +1533,7 @@ static int count_pass(stocs_ctx* c, CongruentState* S, const PlanDev& plan, cons
     int rc;
     if ((rc = L.pk_raw.alloc(totP0)) || (rc = L.pv_raw.alloc(totP0)) || (rc = L.qk_raw.alloc(totQ0)) || (rc = L.qv_raw.alloc(totQ0))) return rc;
     S->d_jobs.p = plan.jobs;
-    if (S->deferred && !S->reduce) { const int rd = S->deferred(); S->deferred = nullptr; if (rd) return rd; c->timing[0].lap("host: cone records of the bases (no survivors pass to hide them behind)"); }
+    if (S->deferred && !S->reduce) { const int rd = S->deferred(); S->deferred = nullptr; if (rd) return rd; c->timing[TIMING_CONGRUENT].lap("host: cone records of the bases (no survivors pass to hide them behind)"); }
     S->d_qoff.p = plan.q_off;
     S->d_bids.p = plan.bids;
     S->d_err.p = plan.err;
@@ -1646,10 +1646,10 @@ static int count_pass(stocs_ctx* c, CongruentState* S, const PlanDev& plan, cons
     if (own_p) STOCS_HIP_CHECK(hipMemcpyAsync(&sort_err_pin[0], d_tmp.p + sort_own_err_offset(), 4, hipMemcpyDeviceToHost, st));
     if (own_q) STOCS_HIP_CHECK(hipMemcpyAsync(&sort_err_pin[1], d_tmp2.p + sort_own_err_offset(), 4, hipMemcpyDeviceToHost, st));
     if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[5], st));
-    c->timing[0].lap(reduce ? "enqueue compact/sort/records/join/scan" : "enqueue gather/sort/records/join/scan");
+    c->timing[TIMING_CONGRUENT].lap(reduce ? "enqueue compact/sort/records/join/scan" : "enqueue gather/sort/records/join/scan");
     STOCS_HIP_CHECK(hipStreamSynchronize(st));
     AU.host_sync(s0);
-    c->timing[0].lap("wait for the device (counts)");
+    c->timing[TIMING_CONGRUENT].lap("wait for the device (counts)");
     // the device's own account of that wait (every event has completed: the stream is idle, the Q side was joined into it): a group
     // between two events per row, named per form (NULL: not a group of that form)
     static const struct { int from, to; const char *all, *red, *one; } groups[] = {
@@ -1659,7 +1659,7 @@ static int count_pass(stocs_ctx* c, CongruentState* S, const PlanDev& plan, cons
         {2, 3, "device: P records + wait for Q", "device: P records + wait for Q", "device: P records"},
         {3, 4, "device: join count", "device: join count", "device: join count"},
         {4, 5, "device: scan + offsets + read-back", "device: scan + offsets + read-back", "device: scan + offsets + read-back"}};
-    CallTiming& T = c->timing[0];
+    CallTiming& T = c->timing[TIMING_CONGRUENT];
     for (const auto& g : groups) {
         const char* what = one_stream ? g.one : (reduce ? g.red : g.all);
         if (!dev_clock || !what || T.n >= CallTiming::MAX_STEPS) continue;
@@ -1681,7 +1681,7 @@ static int lists_too_long(int* too_big, const char* why) { if (too_big) *too_big
 static int find_congruent(stocs_ctx* c, const CongruentSwitches& sw, int64_t* total_quads, size_t max_bytes, int* too_big) {
     const bool dbg = sw.debug_timing;
     double tprev = now_s();
-    c->timing[0].begin();
+    c->timing[TIMING_CONGRUENT].begin();
     if (!c->index.built) { set_error("stocs_find_congruent_all: PPF index not built"); return STOCS_ERR_STATE; }
     const int nB = (int)c->bases.size();
     if (!c->cong) c->cong = new CongruentState();
@@ -1692,7 +1692,7 @@ static int find_congruent(stocs_ctx* c, const CongruentSwitches& sw, int64_t* to
     c->audit.on = sw.debug_streams;
     c->audit.host_sync(0); if (c->aux_stream) c->audit.host_sync(1);
     c->audit.retire_all("stocs_find_congruent_all: the arena is recycled");
-    c->timing[0].lap("entry synchronisation");
+    c->timing[TIMING_CONGRUENT].lap("entry synchronisation");
     { int rc0 = S->arena_state.reset(); if (rc0) return rc0; }
     tl_arena = &S->arena_state;
     if (!S->d_trig) {   // once per context (synchronous copy from static host memory)
@@ -1701,7 +1701,7 @@ static int find_congruent(stocs_ctx* c, const CongruentSwitches& sw, int64_t* to
     }
     // pinned block for everything this call reads back: plan totals, Q offsets (4 B per base), per-base quad offsets (8 B)
     { int rc0 = ensure_pinned(c, (size_t)PIN_VAR + 12 * ((size_t)nB + 1) + 256); if (rc0) return rc0; }
-    c->timing[0].lap("arena reset + pinned block");
+    c->timing[TIMING_CONGRUENT].lap("arena reset + pinned block");
     if (dbg) { const double t_ = now_s(); fprintf(stderr, "[stocs congruent] %-18s %8.3f ms\n", "sync+reset", (t_ - tprev) * 1e3); tprev = t_; }
     c->quad_off.assign(nB + 1, 0);
     c->quad_id_bits = 16;
@@ -1757,7 +1757,7 @@ static int find_congruent(stocs_ctx* c, const CongruentSwitches& sw, int64_t* to
         STOCS_HIP_CHECK(pinned_malloc(&S->h_stage, 2 * L.stage));   // counted: a regrow inside a trial must show up
         S->stage_bytes = 2 * L.stage;
     }
-    c->timing[0].lap("host: jobs + cone tables + buffers");
+    c->timing[TIMING_CONGRUENT].lap("host: jobs + cone tables + buffers");
     char* h = (char*)S->h_stage;
     char* dpl = S->d_plan;
     PlanDev plan = {(BaseJob*)(dpl + L.jobs), (Segment*)(dpl + L.pseg), (Segment*)(dpl + L.qseg), (uint32_t*)(dpl + L.qoff), (uint32_t*)(dpl + L.poff),
@@ -1788,7 +1788,7 @@ static int find_congruent(stocs_ctx* c, const CongruentSwitches& sw, int64_t* to
     uint32_t* qoff_pin = (uint32_t*)((char*)c->h_pin + PIN_VAR + 8 * ((size_t)nB + 1));
     STOCS_HIP_CHECK(hipMemcpyAsync(po_pin, dpl + L.out, sizeof(PlanOut), hipMemcpyDeviceToHost, c->stream));
     if (!reduce) STOCS_HIP_CHECK(hipMemcpyAsync(qoff_pin, plan.q_off, 4 * ((size_t)nB + 1), hipMemcpyDeviceToHost, c->stream));   // (reduced lists: their own offsets come later)
-    c->timing[0].lap("enqueue plan upload + kernels + read-back");
+    c->timing[TIMING_CONGRUENT].lap("enqueue plan upload + kernels + read-back");
     if (defer_cone) {
         // staged in the pinned block behind the upload, uploaded and patched into the device's jobs on the context's stream -- behind
         // the plan kernels, ahead of the join
@@ -1831,7 +1831,7 @@ static int find_congruent(stocs_ctx* c, const CongruentSwitches& sw, int64_t* to
     }
     if (!optimistic) {
         STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-        c->timing[0].lap("wait for the device (plan)");
+        c->timing[TIMING_CONGRUENT].lap("wait for the device (plan)");
         const PlanOut po = *po_pin;
         if (!reduce) memcpy(q_off.data(), qoff_pin, 4 * ((size_t)nB + 1));
         if (po.overflow) return lists_too_long(too_big, "pair lists exceed 2^32 entries");
@@ -1862,7 +1862,7 @@ static int find_congruent(stocs_ctx* c, const CongruentSwitches& sw, int64_t* to
         if (rc0) return rc0;
         if (over) return lists_too_long(too_big, "pair lists beyond the memory ceiling");   // the caller splits its base set
     }
-    c->timing[0].lap(!use_table ? "arena reserve (no run table, 64-bit keys)" : (wide ? "arena reserve (64-bit keys)" : "arena reserve"));   // (names the form)
+    c->timing[TIMING_CONGRUENT].lap(!use_table ? "arena reserve (no run table, 64-bit keys)" : (wide ? "arena reserve (64-bit keys)" : "arena reserve"));   // (names the form)
     S->nB = nB; S->totP = (uint32_t)totP; S->totQ = (uint32_t)totQ; S->nepsilon = nepsilon;
     S->half_inv_neps = (float)(0.5 / (double)nepsilon);
     S->NC = NC; S->use_table = use_table; S->wide = wide; S->reduce = reduce;
@@ -1886,7 +1886,7 @@ static int find_congruent(stocs_ctx* c, const CongruentSwitches& sw, int64_t* to
         if (outgrown) {
             // the plan outgrew the capacities: once more with the sizes now known.  The base jobs carry the survivors' offsets by now:
             // the layout kernel writes the planned ones again (its inputs are still in the planning buffer)
-            c->timing[0].lap("plan beyond the capacities: redone with exact sizes");
+            c->timing[TIMING_CONGRUENT].lap("plan beyond the capacities: redone with exact sizes");
             launch_plan_offsets(c->stream, nB, dpl, L, plan);
             STOCS_HIP_CHECK(hipGetLastError());
             { int rc0 = S->arena_state.reset(); if (rc0) return rc0; }

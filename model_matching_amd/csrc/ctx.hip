@@ -534,23 +534,10 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
     c->nS = nS; c->nM = nM;
     c->d_scratch = NULL; c->scratch_bytes = 0;
     c->h_pin = NULL; c->pin_bytes = 0;
-    for (int k = 0; k < 9; ++k) c->timing[k].n = 0;
+    for (int k = 0; k < TIMING_COUNT; ++k) c->timing[k].n = 0;
     c->index.built = false;
     c->index.d_bucket_start = NULL; c->index.d_pairs = NULL; c->index.d_exists = NULL;
     c->cong = NULL; c->quad_id_bits = 16;
-    c->refine = NULL;
-    c->track = NULL;
-    c->depth = NULL;
-    c->instances = NULL;
-    c->render = NULL;
-    c->scene = NULL;
-    c->pose_error = NULL;
-    c->pose_error_sym = NULL;
-    c->symmetry = NULL;
-    c->vsd = NULL;
-    c->mesh = NULL;
-    c->render_mesh = NULL;
-    c->refine_visible = NULL;
     c->inst = NULL;
     c->trials = NULL; c->snrmw_trial0 = NULL; c->snrmw_stride = 0; c->snrmw_override = NULL; c->lcp_cand_trial = NULL;
     c->d_cand = NULL; c->cand_bytes = 0; c->n_cands = 0; c->cand_cap = 0; c->cands_stale = false;
@@ -711,19 +698,7 @@ int stocs_ctx_destroy(stocs_ctx* c) {
     stocs_internal_free_congruent(c);
     stocs_internal_free_instance(c);
     stocs_internal_free_trials(c);
-    stocs_internal_free_refine(c);
-    stocs_internal_free_track(c);
-    stocs_internal_free_depth(c);
-    stocs_internal_free_instances(c);
-    stocs_internal_free_render(c);
-    stocs_internal_free_scene(c);
-    stocs_internal_free_pose_error(c);
-    stocs_internal_free_pose_error_sym(c);
-    stocs_internal_free_symmetry(c);
-    stocs_internal_free_vsd(c);
-    stocs_internal_free_mesh(c);
-    stocs_internal_free_render_mesh(c);
-    stocs_internal_free_refine_visible(c);
+    for (StateSlot& s : c->state) if (s.p) { s.del(s.p); s.p = NULL; }   // the features, in the order of StateOwner
     c->grid_mem.destroy(); c->grid_ws.destroy();
     c->order.free(); c->cdf.free(); c->kd.free();
     if (c->h_pin) (void)hipHostFree(c->h_pin);
@@ -830,13 +805,13 @@ static int copy_timing(const CallTiming& t, const char** labels, double* ms, int
 }
 
 int stocs_last_call_timing(const stocs_ctx* c, int which, const char** labels, double* ms, int cap, int* n) {
-    if (!c || which < 0 || which > 7 || !n || cap < 0) return STOCS_ERR_INVALID;
+    if (!c || which < 0 || which >= TIMING_VSD_MESH || !n || cap < 0) return STOCS_ERR_INVALID;
     return copy_timing(c->timing[which], labels, ms, cap, n);
 }
 
 int stocs_mesh_last_call_timing(const stocs_ctx* c, const char** labels, double* ms, int cap, int* n) {
     if (!c || !n || cap < 0) return STOCS_ERR_INVALID;
-    return copy_timing(c->timing[8], labels, ms, cap, n);
+    return copy_timing(c->timing[TIMING_VSD_MESH], labels, ms, cap, n);
 }
 
 // CPU-only self test of the STOCS_DEBUG_STREAMS checker (stream_audit.h) on canned two-stream sequences: 0 = the fork / join

@@ -129,16 +129,6 @@ __global__ __launch_bounds__(256) void depth_check_kernel(const float* __restric
     }
 }
 
-static DepthState* depth_state(stocs_ctx* c) {
-    if (!c->depth) {
-        DepthState* S = new DepthState();
-        S->has_frame = S->has_prob = false; S->npix = 0;
-        memset(&S->cam, 0, sizeof(S->cam));
-        c->depth = S;
-    }
-    return (DepthState*)c->depth;
-}
-
 static int check_params(const stocs_depth_params* p) {
     if (!(p->tolerance > 0.0f) || !isfinite(p->tolerance)) { set_error("stocs_depth_check_poses: tolerance %g must be positive and finite", (double)p->tolerance); return STOCS_ERR_INVALID; }
     if (!isfinite(p->class_threshold)) { set_error("stocs_depth_check_poses: class_threshold is not finite"); return STOCS_ERR_INVALID; }
@@ -155,14 +145,6 @@ static int check_params(const stocs_depth_params* p) {
 
 using namespace stocs;
 
-extern "C" void stocs_internal_free_depth(stocs_ctx* c) {
-    if (!c || !c->depth) return;
-    DepthState* S = (DepthState*)c->depth;
-    S->frame.free(); S->work.free();
-    delete S;
-    c->depth = NULL;
-}
-
 extern "C" void stocs_default_depth_params(stocs_depth_params* p) {
     if (!p) return;
     p->tolerance = 0.01f; p->class_threshold = 0.10f; p->self_occlusion = 1; p->cell_px = 8; p->occlusion_margin = 0.01f;
@@ -172,7 +154,7 @@ extern "C" int stocs_ctx_set_frame(stocs_ctx* c, const stocs_camera* cam, const 
     if (!c || !cam || !depth) { set_error("stocs_ctx_set_frame: NULL context, camera or depth image"); return STOCS_ERR_INVALID; }
     if (cam->width < 1 || cam->height < 1) { set_error("stocs_ctx_set_frame: image of %d x %d pixels", cam->width, cam->height); return STOCS_ERR_INVALID; }
     DeviceGuard dev_guard(c->device);
-    DepthState* S = depth_state(c);
+    DepthState* S = ctx_state<DepthState>(c);
     const size_t npix = (size_t)cam->width * (size_t)cam->height;
     const size_t img = al256(npix * 2);
     S->has_frame = false;

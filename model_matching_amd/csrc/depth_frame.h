@@ -1,5 +1,5 @@
 // depth_frame.h -- what the entry points that work on the frame of stocs_ctx_set_frame share: the frame's state on the context
-// (depth.hip owns it: stocs_ctx_set_frame fills it, stocs_internal_free_depth frees it), the kernel arguments that describe the camera,
+// (depth.hip owns it: stocs_ctx_set_frame fills it, the context's registry deletes it), the kernel arguments that describe the camera,
 // steps 1-3 of the depth-check contract (include/stocs_hip.h), and on the host the checks of the frame, the fill of the arguments and the
 // pointers to its two images.  Included through render_rules.h by depth.hip (stocs_depth_check_poses), render.hip (stocs_render_poses and
 // its kin) and scene.hip (stocs_scene_footprints); all project a model point with the one project_point below.
@@ -11,11 +11,13 @@
 namespace stocs {
 
 struct DepthState {
+    static const StateOwner OWNER = OWN_DEPTH;
     DevBlock frame;   // depth (npix uint16) | class probabilities (npix uint16), grow-only
     DevBlock work;    // poses (n x 16 float) | records (n x stocs_depth_result), grow-only
-    bool has_frame, has_prob;
-    size_t npix;      // pixels uploaded
-    stocs_camera cam;
+    bool has_frame = false, has_prob = false;
+    size_t npix = 0;  // pixels uploaded
+    stocs_camera cam = {};
+    ~DepthState() { frame.free(); work.free(); }
 };
 
 struct DepthArgs {
@@ -47,7 +49,7 @@ __device__ __forceinline__ Projected project_point(const float* P, const float4 
 
 // ---- host side: the frame as every entry point on it requires it, and the kernel arguments from it ----
 static int check_frame(const char* who, stocs_ctx* c, DepthState** frame) {
-    DepthState* S = (DepthState*)c->depth;
+    DepthState* S = ctx_state_if<DepthState>(c);
     if (!S || !S->has_frame) { set_error("%s: no frame (stocs_ctx_set_frame)", who); return STOCS_ERR_STATE; }
     if (S->cam.width < 1 || S->cam.height < 1) { set_error("%s: image of %d x %d pixels", who, S->cam.width, S->cam.height); return STOCS_ERR_INVALID; }
     if ((size_t)S->cam.width * (size_t)S->cam.height != S->npix) {

@@ -29,6 +29,8 @@ namespace stocs {
 enum { INST_MAX_SCENE = 1 << 18, INST_MAX_N = 16384 };
 
 struct InstancesState {
+    static const StateOwner OWNER = OWN_INSTANCES;
+    ~InstancesState() { rows.free(); work.free(); }
     DevBlock rows;   // one chunk of detail rows: lcp | hit | counted
     DevBlock work;   // poses | valid | lcp | own | keys (2) | indices (2) | rank | excl | cover | records + selected + count | sort scratch | E
 };
@@ -103,10 +105,6 @@ __global__ __launch_bounds__(256) void instance_finish_kernel(const uint32_t* __
     }
 }
 
-static InstancesState* instances_state(stocs_ctx* c) {
-    if (!c->instances) c->instances = new InstancesState();
-    return (InstancesState*)c->instances;
-}
 
 static int check_params(const char* who, const stocs_instance_params* p) {
     if (p->max_instances < 1) { set_error("%s: max_instances %d < 1", who, p->max_instances); return STOCS_ERR_INVALID; }
@@ -187,14 +185,6 @@ static int order_select_finish(stocs_ctx* c, const InstancesWork& w, int n, cons
 
 using namespace stocs;
 
-extern "C" void stocs_internal_free_instances(stocs_ctx* c) {
-    if (!c || !c->instances) return;
-    InstancesState* S = (InstancesState*)c->instances;
-    S->rows.free(); S->work.free();
-    delete S;
-    c->instances = NULL;
-}
-
 extern "C" void stocs_default_instance_params(stocs_instance_params* p) {
     if (!p) return;
     p->max_instances = 16; p->min_points = 20; p->min_exclusive_fraction = 0.5f;
@@ -213,7 +203,7 @@ extern "C" int stocs_select_instances(stocs_ctx* c, const float* T16, int n, con
     if (n == 0) return STOCS_OK;
     DeviceGuard dev_guard(c->device);
     begin_scoring_call(c);
-    InstancesState* S = instances_state(c);
+    InstancesState* S = ctx_state<InstancesState>(c);
     const size_t M = (size_t)c->nM;
     size_t chunk = std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)256 << 20) / (5 * M)));
     if (const char* e = getenv("STOCS_INSTANCES_CHUNK")) { const long v = atol(e); if (v >= 1) chunk = std::min<size_t>((size_t)v, (size_t)n); }
@@ -268,7 +258,7 @@ extern "C" int stocs_select_instances_rows(stocs_ctx* c, const int32_t* hit, con
     *n_selected = 0;
     if (n == 0) return STOCS_OK;
     DeviceGuard dev_guard(c->device);
-    InstancesState* S = instances_state(c);
+    InstancesState* S = ctx_state<InstancesState>(c);
     Carve rv;
     const size_t o_l = rv.take((size_t)n * 4), o_h = rv.take(cells * 4), o_c = rv.take(cells);
     { const int rc = S->rows.grow(c->stream, rv.total); if (rc) return rc; }

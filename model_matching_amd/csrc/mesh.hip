@@ -33,7 +33,7 @@
 #include <vector>
 
 #include "mesh_sample.h"
-#include "pose_error_math.h"
+#include "eval_call.h"
 #include "render_shared.h"
 #include "wave_bits.h"
 
@@ -42,6 +42,8 @@ namespace stocs {
 enum { MESH_SMALL_PX = STOCS_MESH_SMALL_PX, MESH_GROUP_PX = 8192, MESH_TRIS = 256, MESH_MAX_V = 1 << 24, MESH_MAX_T = 1 << 22 };
 
 struct MeshState {
+    static const StateOwner OWNER = OWN_MESH;
+    ~MeshState() { verts.free(); tris.free(); }
     DevBlock verts;   // nv float4 (x, y, z, 0), grow-only
     DevBlock tris;    // nt int4 (i0, i1, i2, 0), grow-only
     int nv = 0, nt = 0;
@@ -227,11 +229,6 @@ __global__ __launch_bounds__(256) void mesh_render_kernel(const float* __restric
     }
 }
 
-static MeshState* mesh_state(stocs_ctx* c) {
-    if (!c->mesh) c->mesh = new MeshState();
-    return (MeshState*)c->mesh;
-}
-
 // STOCS_MESH_FORM=<bits> in the environment chooses the kernel's forms, for measurements and for the tests; no bit changes a result.
 // 1: every box up to MESH_GROUP_PX pixels is walked by its own lane; 2: every box is swept by a wavefront or the workgroup, none by its
 // lane; 4: every hit pixel reads the stored depth before its atomicMin, 8: none does (neither: none does);
@@ -259,7 +256,7 @@ static MeshArgs mesh_args(int nt) {
 // the mesh renderer as a VsdRenderer: self is the call's MeshArgs
 static int render_mesh(stocs_ctx* c, const void* self, const float* d_pose, int m, const DepthArgs& a, uint32_t* d_z, int32_t* d_box) {
     const MeshArgs& ma = *(const MeshArgs*)self;
-    const MeshState* S = (const MeshState*)c->mesh;
+    const MeshState* S = ctx_state_if<MeshState>(c);
     const unsigned tri_chunks = (unsigned)((ma.nt + MESH_TRIS - 1) / MESH_TRIS);
     hipLaunchKernelGGL(mesh_render_kernel<DepthSink>, dim3(tri_chunks, (unsigned)m), dim3(256), 0, c->stream, d_pose, (const float4*)S->verts.p, (const int4*)S->tris.p, a, ma, d_z,
                        d_box);
@@ -268,12 +265,12 @@ static int render_mesh(stocs_ctx* c, const void* self, const float* d_pose, int 
 }
 
 int mesh_enqueue_depth(stocs_ctx* c, const float* d_pose, int m, const DepthArgs& a, uint32_t* d_z, int32_t* d_box) {
-    const MeshArgs ma = mesh_args(((const MeshState*)c->mesh)->nt);
+    const MeshArgs ma = mesh_args(ctx_state_if<MeshState>(c)->nt);
     return render_mesh(c, &ma, d_pose, m, a, d_z, d_box);
 }
 
 int mesh_enqueue_keys(stocs_ctx* c, const float* d_pose, int m, const DepthArgs& a, int id_base, unsigned long long* d_zkey, int32_t* d_box) {
-    const MeshState* S = (const MeshState*)c->mesh;
+    const MeshState* S = ctx_state_if<MeshState>(c);
     const MeshArgs ma = mesh_args(S->nt);
     const unsigned tri_chunks = (unsigned)((ma.nt + MESH_TRIS - 1) / MESH_TRIS);
     // the pose is blockIdx.y (at most 65 535 per launch)
@@ -288,7 +285,7 @@ int mesh_enqueue_keys(stocs_ctx* c, const float* d_pose, int m, const DepthArgs&
 }
 
 int mesh_enqueue_tri_keys(stocs_ctx* c, const float* d_pose, int m, const DepthArgs& a, unsigned long long* d_zkey, int32_t* d_box) {
-    const MeshState* S = (const MeshState*)c->mesh;
+    const MeshState* S = ctx_state_if<MeshState>(c);
     const MeshArgs ma = mesh_args(S->nt);
     const unsigned tri_chunks = (unsigned)((ma.nt + MESH_TRIS - 1) / MESH_TRIS);
     // the pose is blockIdx.y: m <= 65 535, the caller's chunks see to that
@@ -300,14 +297,14 @@ int mesh_enqueue_tri_keys(stocs_ctx* c, const float* d_pose, int m, const DepthA
 
 // the mesh on the device for a kernel that reads facets by index (refine_visible.hip): nt int4 triangles, float4 vertices
 void mesh_device_arrays(const stocs_ctx* c, const float4** verts, const int4** tris) {
-    const MeshState* S = (const MeshState*)c->mesh;
+    const MeshState* S = ctx_state_if<MeshState>(c);
     *verts = (const float4*)S->verts.p; *tris = (const int4*)S->tris.p;
 }
 
-int mesh_triangles(const stocs_ctx* c) { return c->mesh ? ((const MeshState*)c->mesh)->nt : 0; }
+int mesh_triangles(const stocs_ctx* c) { const MeshState* S = ctx_state_if<MeshState>(c); return S ? S->nt : 0; }
 
 int mesh_check_present(const char* who, stocs_ctx* c) {
-    const MeshState* S = (const MeshState*)c->mesh;
+    const MeshState* S = ctx_state_if<MeshState>(c);
     if (!S || S->nt < 1) { set_error("%s: the context has no mesh (stocs_ctx_set_mesh)", who); return STOCS_ERR_STATE; }
     return STOCS_OK;
 }
@@ -315,14 +312,6 @@ int mesh_check_present(const char* who, stocs_ctx* c) {
 }  // namespace stocs
 
 using namespace stocs;
-
-extern "C" void stocs_internal_free_mesh(stocs_ctx* c) {
-    if (!c || !c->mesh) return;
-    MeshState* S = (MeshState*)c->mesh;
-    S->verts.free(); S->tris.free();
-    delete S;
-    c->mesh = NULL;
-}
 
 extern "C" int stocs_mesh_small_px(void) { return (int)MESH_SMALL_PX; }
 
@@ -344,13 +333,13 @@ extern "C" int stocs_ctx_set_mesh(stocs_ctx* c, const float* pos3, int nv, const
     if (!c) { set_error("%s: NULL context", who); return STOCS_ERR_INVALID; }
     if (nv < 0 || nt < 0) { set_error("%s: nv %d or nt %d < 0", who, nv, nt); return STOCS_ERR_INVALID; }
     if (nt == 0) {   // drops the mesh; the blocks stay for the next one
-        if (c->mesh) { ((MeshState*)c->mesh)->nv = 0; ((MeshState*)c->mesh)->nt = 0; }
+        if (MeshState* S = ctx_state_if<MeshState>(c)) { S->nv = 0; S->nt = 0; }
         return STOCS_OK;
     }
     if (!pos3 || !tris3) { set_error("%s: NULL vertices or triangles", who); return STOCS_ERR_INVALID; }
     { const int rc = stocs_mesh_check(pos3, nv, tris3, nt); if (rc) return rc; }
     DeviceGuard dev_guard(c->device);
-    MeshState* S = mesh_state(c);
+    MeshState* S = ctx_state<MeshState>(c);
     S->nv = 0; S->nt = 0;   // a failure below leaves no mesh
     { const int rc = S->verts.grow(c->stream, (size_t)nv * 16); if (rc) return rc; }
     { const int rc = S->tris.grow(c->stream, (size_t)nt * 16); if (rc) return rc; }
@@ -370,7 +359,7 @@ extern "C" int stocs_ctx_set_mesh(stocs_ctx* c, const float* pos3, int nv, const
 
 extern "C" int stocs_ctx_mesh_info(const stocs_ctx* c, int* nv, int* nt) {
     if (!c) { set_error("stocs_ctx_mesh_info: NULL context"); return STOCS_ERR_INVALID; }
-    const MeshState* S = (const MeshState*)c->mesh;
+    const MeshState* S = ctx_state_if<MeshState>(c);
     if (nv) *nv = S ? S->nv : 0;
     if (nt) *nt = S ? S->nt : 0;
     return STOCS_OK;
@@ -378,30 +367,26 @@ extern "C" int stocs_ctx_mesh_info(const stocs_ctx* c, int* nv, int* nt) {
 
 extern "C" int stocs_render_depth_mesh(stocs_ctx* c, const float* poses, int n, float* depth) {
     static const char* who = "stocs_render_depth_mesh";
-    if (!c) { set_error("%s: NULL context", who); return STOCS_ERR_INVALID; }
-    if (n < 0) { set_error("%s: n %d < 0", who, n); return STOCS_ERR_INVALID; }
-    if (n == 0) return STOCS_OK;
+    { int rc; if (check_batch(who, c, n, &rc)) return rc; }
     if (!poses || !depth) { set_error("%s: NULL poses or images", who); return STOCS_ERR_INVALID; }
     { const int rc = mesh_check_present(who, c); if (rc) return rc; }
     DepthState* F = NULL;
     { const int rc = check_frame(who, c, &F); if (rc) return rc; }
-    const MeshArgs ma = mesh_args(((const MeshState*)c->mesh)->nt);
+    const MeshArgs ma = mesh_args(ctx_state_if<MeshState>(c)->nt);
     const VsdRenderer rd = {render_mesh, &ma};
     return vsd_render_depth_with(c, F, rd, poses, n, depth);
 }
 
 extern "C" int stocs_pose_errors_vsd_mesh(stocs_ctx* c, const float* est, int n, const float* gt, int n_gt, const stocs_vsd_params* prm, stocs_vsd_record* out) {
     static const char* who = "stocs_pose_errors_vsd_mesh";
-    if (!c) { set_error("%s: NULL context", who); return STOCS_ERR_INVALID; }
-    if (n < 0) { set_error("%s: n %d < 0", who, n); return STOCS_ERR_INVALID; }
-    if (n == 0) return STOCS_OK;
-    if (!est || !gt || !prm || !out) { set_error("%s: NULL estimates, ground truth, parameters or results", who); return STOCS_ERR_INVALID; }
-    if (n_gt != 1 && n_gt != n) { set_error("%s: n_gt %d is neither 1 nor n = %d", who, n_gt, n); return STOCS_ERR_INVALID; }
+    { int rc; if (check_batch(who, c, n, &rc)) return rc; }
+    { const int rc = check_pairs(who, est, n, gt, n_gt, out); if (rc) return rc; }
+    if (!prm) { set_error("%s: NULL parameters", who); return STOCS_ERR_INVALID; }
     { const int rc = vsd_check_compare_params(who, prm); if (rc) return rc; }   // surfel_radius and max_splat_px are not read
     { const int rc = mesh_check_present(who, c); if (rc) return rc; }
     DepthState* F = NULL;
     { const int rc = check_frame(who, c, &F); if (rc) return rc; }
-    const MeshArgs ma = mesh_args(((const MeshState*)c->mesh)->nt);
+    const MeshArgs ma = mesh_args(ctx_state_if<MeshState>(c)->nt);
     const VsdRenderer rd = {render_mesh, &ma};
-    return vsd_pose_errors_with(c, F, 8, rd, est, n, gt, n_gt, prm, out);
+    return vsd_pose_errors_with(c, F, TIMING_VSD_MESH, rd, est, n, gt, n_gt, prm, out);
 }

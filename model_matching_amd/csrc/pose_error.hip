@@ -23,6 +23,7 @@
 // Known limit: a pair is ceil(M / PE_CHUNK) workgroups, so a call of few pairs on a small model is latency-bound.
 #include <string.h>
 
+#include "eval_call.h"
 #include "pose_error_math.h"
 
 namespace stocs {
@@ -32,9 +33,11 @@ static_assert(PE_CHUNK == PE_Q * PE_THREADS, "a chunk is PE_Q rows of PE_THREADS
 static_assert(PE_TILE % PE_THREADS == 0, "a tile is filled in whole rounds of the workgroup");
 
 struct PoseErrorState {
+    static const StateOwner OWNER = OWN_POSE_ERROR;
     DevBlock work;
-    bool have_diameter;
-    float diameter;
+    bool have_diameter = false;
+    float diameter = 0.0f;
+    ~PoseErrorState() { work.free(); }
 };
 
 // the tile loop: jn targets of the LDS tile against NQ queries in registers.  DETAIL also keeps the tile-global index of the winner
@@ -173,39 +176,18 @@ __global__ __launch_bounds__(PE_THREADS) void model_diameter_kernel(const float4
     }
 }
 
-static PoseErrorState* pose_error_state(stocs_ctx* c) {
-    if (!c->pose_error) {
-        PoseErrorState* S = new PoseErrorState();
-        S->have_diameter = false; S->diameter = 0.0f;
-        c->pose_error = S;
-    }
-    return (PoseErrorState*)c->pose_error;
-}
-
 }  // namespace stocs
 
 using namespace stocs;
 
-extern "C" void stocs_internal_free_pose_error(stocs_ctx* c) {
-    if (!c || !c->pose_error) return;
-    PoseErrorState* S = (PoseErrorState*)c->pose_error;
-    S->work.free();
-    delete S;
-    c->pose_error = NULL;
-}
-
 extern "C" int stocs_pose_errors(stocs_ctx* c, const float* est, int n, const float* gt, int n_gt, stocs_pose_error* out) {
-    if (!c) { set_error("stocs_pose_errors: NULL context"); return STOCS_ERR_INVALID; }
-    if (n < 0) { set_error("stocs_pose_errors: n %d < 0", n); return STOCS_ERR_INVALID; }
-    if (n == 0) return STOCS_OK;
-    if (!est || !gt || !out) { set_error("stocs_pose_errors: NULL estimates, ground truth or results"); return STOCS_ERR_INVALID; }
-    if (n_gt != 1 && n_gt != n) { set_error("stocs_pose_errors: n_gt %d is neither 1 nor n = %d", n_gt, n); return STOCS_ERR_INVALID; }
-    if (c->nM < 1) { set_error("stocs_pose_errors: the context has no model"); return STOCS_ERR_STATE; }
+    static const char* who = "stocs_pose_errors";
+    { int rc; if (check_batch(who, c, n, &rc)) return rc; }
+    { const int rc = check_pairs(who, est, n, gt, n_gt, out); if (rc) return rc; }
+    { const int rc = check_model(who, c); if (rc) return rc; }
     DeviceGuard dev_guard(c->device);
-    PoseErrorState* S = pose_error_state(c);
-    CallTiming& tm = c->timing[4];
-    tm.begin();
-    const bool dev_clock = c->device_clock != 0;   // opt-in: an event between two operations of a stream leaves the queue idle for a few microseconds
+    PoseErrorState* S = ctx_state<PoseErrorState>(c);
+    TimedCall tc(c, TIMING_POSE_ERRORS);
     Carve cv;
     const size_t o_est = cv.take((size_t)n * 64), o_gt = cv.take((size_t)n_gt * 64), o_rec = cv.take((size_t)n * sizeof(stocs_pose_error));
     { const int rc = S->work.grow(c->stream, cv.total); if (rc) return rc; }
@@ -215,54 +197,44 @@ extern "C" int stocs_pose_errors(stocs_ctx* c, const float* est, int n, const fl
     float* d_gt = Carve::at<float>(S->work.p, o_gt);
     stocs_pose_error* d_rec = Carve::at<stocs_pose_error>(S->work.p, o_rec);
     stocs_pose_error* h_rec = Carve::at<stocs_pose_error>(hp, o_rec);
+    tc.start();   // (the first step counts the growing of the two blocks)
     memcpy(hp + o_est, est, (size_t)n * 64);
     memcpy(hp + o_gt, gt, (size_t)n_gt * 64);
     STOCS_HIP_CHECK(hipMemcpyAsync(S->work.p, hp, o_gt + (size_t)n_gt * 64, hipMemcpyHostToDevice, c->stream));   // both pose regions in one copy
     STOCS_HIP_CHECK(hipMemsetAsync(d_rec, 0, (size_t)n * sizeof(stocs_pose_error), c->stream));
     const unsigned chunks = (unsigned)((c->nM + PE_CHUNK - 1) / PE_CHUNK);
-    if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev0, c->stream));
+    { const int rc = tc.device_begin(); if (rc) return rc; }
     for (int p0 = 0; p0 < n; p0 += PE_MAX_GRID_Y) {
         const int np = n - p0 < PE_MAX_GRID_Y ? n - p0 : PE_MAX_GRID_Y;
         hipLaunchKernelGGL(pose_error_kernel<false>, dim3(chunks, (unsigned)np), dim3(PE_THREADS), 0, c->stream, (const float*)d_est, (const float*)d_gt,
                            n_gt == 1 ? 0 : 16, p0, (const float4*)c->d_mpos_raw, c->nM, d_rec, (float*)NULL, (float*)NULL, (int32_t*)NULL);
         STOCS_HIP_CHECK(hipGetLastError());
     }
-    if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev1, c->stream));
+    { const int rc = tc.device_end(); if (rc) return rc; }
     STOCS_HIP_CHECK(hipMemcpyAsync(h_rec, d_rec, (size_t)n * sizeof(stocs_pose_error), hipMemcpyDeviceToHost, c->stream));
-    tm.lap("stage and enqueue");
-    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    tm.lap("wait for the device");
-    const double M = (double)c->nM;
+    { const int rc = tc.enqueued_wait(); if (rc) return rc; }
     for (int k = 0; k < n; ++k) {
-        const float* P = est + (size_t)k * 16;
-        const float* G = gt + (size_t)(n_gt == 1 ? 0 : k) * 16;
         stocs_pose_error r = h_rec[k];
-        if (!host_pose_finite(P) || !host_pose_finite(G) || host_pose_zero(P)) {   // step 5 (the kernel left the record zero)
+        if (!pair_valid(est, gt, n_gt, k)) {   // step 5 (the kernel left the record zero)
             r.add_fix = r.adds_fix = 0;
             r.add = r.add_max = r.adds = r.adds_max = INFINITY;
             r.valid = 0;
         } else {
-            r.add = (float)((double)r.add_fix / 4294967296.0 / M);
-            r.adds = (float)((double)r.adds_fix / 4294967296.0 / M);
+            r.add = fix_mean(r.add_fix, c->nM);
+            r.adds = fix_mean(r.adds_fix, c->nM);
             r.valid = 1;
         }
         r.reserved = 0;
         out[k] = r;
     }
-    tm.lap("records");
-    if (dev_clock) {
-        float ms = 0.0f;
-        STOCS_HIP_CHECK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        tm.label[tm.n] = "device: kernel"; tm.ms[tm.n] = (double)ms; ++tm.n;
-    }
-    return STOCS_OK;
+    return tc.finish();
 }
 
 extern "C" int stocs_pose_errors_detail(stocs_ctx* c, const float* est, const float* gt, float* e, float* s, int32_t* nn) {
     if (!c || !est || !gt) { set_error("stocs_pose_errors_detail: NULL context or pose"); return STOCS_ERR_INVALID; }
-    if (c->nM < 1) { set_error("stocs_pose_errors_detail: the context has no model"); return STOCS_ERR_STATE; }
+    { const int rc = check_model("stocs_pose_errors_detail", c); if (rc) return rc; }
     DeviceGuard dev_guard(c->device);
-    PoseErrorState* S = pose_error_state(c);
+    PoseErrorState* S = ctx_state<PoseErrorState>(c);
     const size_t M = (size_t)c->nM;
     Carve cv;
     const size_t o_est = cv.take(64), o_gt = cv.take(64), o_e = cv.take(M * 4), o_s = cv.take(M * 4), o_nn = cv.take(M * 4);
@@ -287,8 +259,8 @@ extern "C" int stocs_pose_errors_detail(stocs_ctx* c, const float* est, const fl
 
 extern "C" int stocs_model_diameter(stocs_ctx* c, float* diameter) {
     if (!c || !diameter) { set_error("stocs_model_diameter: NULL context or result"); return STOCS_ERR_INVALID; }
-    if (c->nM < 1) { set_error("stocs_model_diameter: the context has no model"); return STOCS_ERR_STATE; }
-    PoseErrorState* S = pose_error_state(c);
+    { const int rc = check_model("stocs_model_diameter", c); if (rc) return rc; }
+    PoseErrorState* S = ctx_state<PoseErrorState>(c);
     if (!S->have_diameter) {
         DeviceGuard dev_guard(c->device);
         { const int rc = S->work.grow(c->stream, 256); if (rc) return rc; }

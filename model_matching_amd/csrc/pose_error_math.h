@@ -1,6 +1,6 @@
 // pose_error_math.h -- the arithmetic that the pose-error kernels share (pose_error.hip: ADD / ADD-S; pose_error_sym.hip: MSSD / MSPD /
-// symmetric ADD): steps 1, 2 and 4 of the contract at stocs_pose_errors in include/stocs_hip.h, step 5's validity rule on both sides of
-// the bus, and the wavefront reductions of the integer sums and of the float maxima taken on their bits.  One definition: the
+// symmetric ADD): steps 1, 2 and 4 of the contract at stocs_pose_errors in include/stocs_hip.h, step 5's validity rule on the device
+// (its host twin is eval_call.h's pair_valid), and the wavefront reductions of the integer sums and of the float maxima taken on their bits.  One definition: the
 // symmetry-aware records equal the plain ones bit for bit under the identity because both run these very expressions.
 #ifndef STOCS_POSE_ERROR_MATH_H
 #define STOCS_POSE_ERROR_MATH_H
@@ -56,17 +56,6 @@ __device__ __forceinline__ unsigned wave_max_u32(unsigned v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) { const unsigned w = (unsigned)__shfl_xor((int)v, o, 64); v = w > v ? w : v; }
     return v;
-}
-
-static bool host_pose_finite(const float* P) {
-    for (int i = 0; i < 15; ++i)
-        if ((i & 3) != 3 && !(fabsf(P[i]) <= 3.4028234663852886e38f)) return false;
-    return true;
-}
-static bool host_pose_zero(const float* P) {
-    for (int i = 0; i < 16; ++i)
-        if (!(P[i] == 0.0f)) return false;
-    return true;
 }
 
 }  // namespace stocs

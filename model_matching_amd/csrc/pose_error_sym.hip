@@ -27,6 +27,7 @@
 // of the n records back, ONE synchronisation.  `add`, `valid` and the invalid pairs' records are filled on the host.
 #include <string.h>
 
+#include "eval_call.h"
 #include "pose_error_math.h"
 
 namespace stocs {
@@ -34,7 +35,7 @@ namespace stocs {
 enum { PS_THREADS = STOCS_POSE_SYM_THREADS, PS_KB = STOCS_POSE_SYM_BLOCK, PS_WAVES = PS_THREADS / 64 };
 static_assert(PS_THREADS % 64 == 0 && PS_KB >= 1 && PS_KB <= PS_THREADS, "whole wavefronts; one thread stores one symmetry's values");
 
-struct PoseErrorSymState { DevBlock work; };
+struct PoseErrorSymState { static const StateOwner OWNER = OWN_POSE_ERROR_SYM; DevBlock work; ~PoseErrorSymState() { work.free(); } };
 struct PsPerK { unsigned long long add_fix; float max3, max2; };   // step 3 / 4 of one (pair, k)
 static_assert(sizeof(PsPerK) == 16, "per-k values are 16 bytes");
 struct PsCam { float fx, fy, cx, cy; };
@@ -190,17 +191,10 @@ __global__ __launch_bounds__(PS_THREADS) void pose_sym_min_kernel(const float* _
     }
 }
 
-static PoseErrorSymState* pose_error_sym_state(stocs_ctx* c) {
-    if (!c->pose_error_sym) c->pose_error_sym = new PoseErrorSymState();
-    return (PoseErrorSymState*)c->pose_error_sym;
-}
-
-static bool host_finite(float x) { return fabsf(x) <= 3.4028234663852886e38f; }
-
 // the refusals on the symmetries and the camera, which the two entry points share (K is in range, the pointers are set)
 static int check_sym_values(const char* who, const float* sym, int K, const stocs_camera* cam) {
-    for (int k = 0; k < K; ++k)
-        if (!host_pose_finite(sym + (size_t)k * 16)) { set_error("%s: symmetry %d has a non-finite entry", who, k); return STOCS_ERR_INVALID; }
+    const int bad = first_nonfinite_pose(sym, K);
+    if (bad >= 0) { set_error("%s: symmetry %d has a non-finite entry", who, bad); return STOCS_ERR_INVALID; }
     if (cam && !(host_finite(cam->fx) && host_finite(cam->fy) && host_finite(cam->cx) && host_finite(cam->cy))) {
         set_error("%s: non-finite camera intrinsics", who);
         return STOCS_ERR_INVALID;
@@ -242,26 +236,15 @@ static int ps_enqueue(stocs_ctx* c, char* base, const PsLayout& L, int n, int n_
 
 using namespace stocs;
 
-extern "C" void stocs_internal_free_pose_error_sym(stocs_ctx* c) {
-    if (!c || !c->pose_error_sym) return;
-    PoseErrorSymState* S = (PoseErrorSymState*)c->pose_error_sym;
-    S->work.free();
-    delete S;
-    c->pose_error_sym = NULL;
-}
-
 extern "C" int stocs_pose_errors_sym(stocs_ctx* c, const float* est, int n, const float* gt, int n_gt, const float* sym, int K, const stocs_camera* cam,
                                      stocs_pose_error_sym* out) {
     const char* who = "stocs_pose_errors_sym";
-    if (!c) { set_error("%s: NULL context", who); return STOCS_ERR_INVALID; }
-    if (n < 0) { set_error("%s: n %d < 0", who, n); return STOCS_ERR_INVALID; }
-    if (n == 0) return STOCS_OK;
+    { int rc; if (check_batch(who, c, n, &rc)) return rc; }
     if (K < 1 || K > STOCS_POSE_SYM_MAX) { set_error("%s: K = %d symmetries, not 1 .. %d", who, K, (int)STOCS_POSE_SYM_MAX); return STOCS_ERR_INVALID; }
-    if (!out) { set_error("%s: NULL results", who); return STOCS_ERR_INVALID; }
-    if (!est || !gt || !sym) { set_error("%s: NULL estimates, ground truth or symmetries", who); return STOCS_ERR_INVALID; }
-    if (n_gt != 1 && n_gt != n) { set_error("%s: n_gt %d is neither 1 nor n = %d", who, n_gt, n); return STOCS_ERR_INVALID; }
+    { const int rc = check_pairs(who, est, n, gt, n_gt, out); if (rc) return rc; }
+    if (!sym) { set_error("%s: NULL symmetries", who); return STOCS_ERR_INVALID; }
     { const int rc = check_sym_values(who, sym, K, cam); if (rc) return rc; }
-    if (c->nM < 1) { set_error("%s: the context has no model", who); return STOCS_ERR_STATE; }
+    { const int rc = check_model(who, c); if (rc) return rc; }
     const PsLayout L = ps_layout((size_t)n, (size_t)n_gt, (size_t)K);
     if ((uint64_t)L.cv.total > (uint64_t)STOCS_REFINE_ROBUST_MAX_WORKSPACE_BYTES) {
         set_error("%s: %d pairs x %d symmetries need %llu workspace bytes, the limit is %llu", who, n, K, (unsigned long long)L.cv.total,
@@ -269,56 +252,43 @@ extern "C" int stocs_pose_errors_sym(stocs_ctx* c, const float* est, int n, cons
         return STOCS_ERR_INVALID;
     }
     DeviceGuard dev_guard(c->device);
-    PoseErrorSymState* S = pose_error_sym_state(c);
-    const bool dev_clock = c->device_clock != 0;
-    const double t_call = CallTiming::now_s();
+    PoseErrorSymState* S = ctx_state<PoseErrorSymState>(c);
+    TimedCall tc(c, TIMING_POSE_ERRORS_SYM);
     { const int rc = S->work.grow(c->stream, L.cv.total); if (rc) return rc; }
     const size_t rec_bytes = (size_t)n * sizeof(stocs_pose_error_sym);
     char *hin, *hback;
     { const int rc = pinned_for(c, L.in_bytes, rec_bytes, &hin, &hback); if (rc) return rc; }
-    CallTiming& tm = c->timing[5];   // from here on the call runs: a call refused above leaves the last call's record as it was
-    tm.begin(); tm.t_last = t_call;  // (the first step still counts the growing of the two blocks)
+    tc.start();   // (the first step counts the growing of the two blocks)
     memcpy(hin + L.o_est, est, (size_t)n * 64);
     memcpy(hin + L.o_gt, gt, (size_t)n_gt * 64);
     memcpy(hin + L.o_sym, sym, (size_t)K * 64);
     STOCS_HIP_CHECK(hipMemcpyAsync(S->work.p, hin, L.o_sym + (size_t)K * 64, hipMemcpyHostToDevice, c->stream));   // the three regions in one copy
-    if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev0, c->stream));
+    { const int rc = tc.device_begin(); if (rc) return rc; }
     { const int rc = ps_enqueue(c, S->work.p, L, n, n_gt, K, cam, 1); if (rc) return rc; }
     stocs_pose_error_sym* d_rec = Carve::at<stocs_pose_error_sym>(S->work.p, L.o_rec);
     hipLaunchKernelGGL(pose_sym_min_kernel, dim3((unsigned)((n + PS_WAVES - 1) / PS_WAVES)), dim3(PS_THREADS), 0, c->stream, Carve::at<const float>(S->work.p, L.o_est),
                        Carve::at<const float>(S->work.p, L.o_gt), n_gt == 1 ? 0 : 16, n, K, Carve::at<const PsPerK>(S->work.p, L.o_perk), d_rec);
     STOCS_HIP_CHECK(hipGetLastError());
-    if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev1, c->stream));
+    { const int rc = tc.device_end(); if (rc) return rc; }
     STOCS_HIP_CHECK(hipMemcpyAsync(hback, d_rec, rec_bytes, hipMemcpyDeviceToHost, c->stream));
-    tm.lap("stage and enqueue");
-    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    tm.lap("wait for the device");
-    const double M = (double)c->nM;
+    { const int rc = tc.enqueued_wait(); if (rc) return rc; }
     const stocs_pose_error_sym* h_rec = (const stocs_pose_error_sym*)hback;
     for (int k = 0; k < n; ++k) {
-        const float* P = est + (size_t)k * 16;
-        const float* G = gt + (size_t)(n_gt == 1 ? 0 : k) * 16;
         stocs_pose_error_sym r;
-        if (!host_pose_finite(P) || !host_pose_finite(G) || host_pose_zero(P)) {   // step 6 (the kernels stored nothing for this pair)
+        if (!pair_valid(est, gt, n_gt, k)) {   // step 6 (the kernels stored nothing for this pair)
             r.add_fix = 0;
             r.add = r.mssd = r.mspd = INFINITY;
             r.k_add = r.k_mssd = r.k_mspd = -1;
             r.valid = 0;
         } else {
             r = h_rec[k];
-            r.add = (float)((double)r.add_fix / 4294967296.0 / M);
+            r.add = fix_mean(r.add_fix, c->nM);
             r.valid = 1;
         }
         r.reserved_f = 0.0f;
         out[k] = r;
     }
-    tm.lap("records");
-    if (dev_clock) {
-        float ms = 0.0f;
-        STOCS_HIP_CHECK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        tm.label[tm.n] = "device: kernel"; tm.ms[tm.n] = (double)ms; ++tm.n;
-    }
-    return STOCS_OK;
+    return tc.finish();
 }
 
 extern "C" int stocs_pose_errors_sym_detail(stocs_ctx* c, const float* est, const float* gt, const float* sym, int K, const stocs_camera* cam,
@@ -328,9 +298,9 @@ extern "C" int stocs_pose_errors_sym_detail(stocs_ctx* c, const float* est, cons
     if (K < 1 || K > STOCS_POSE_SYM_MAX) { set_error("%s: K = %d symmetries, not 1 .. %d", who, K, (int)STOCS_POSE_SYM_MAX); return STOCS_ERR_INVALID; }
     if (!est || !gt || !sym) { set_error("%s: NULL pose or symmetries", who); return STOCS_ERR_INVALID; }
     { const int rc = check_sym_values(who, sym, K, cam); if (rc) return rc; }
-    if (c->nM < 1) { set_error("%s: the context has no model", who); return STOCS_ERR_STATE; }
+    { const int rc = check_model(who, c); if (rc) return rc; }
     DeviceGuard dev_guard(c->device);
-    PoseErrorSymState* S = pose_error_sym_state(c);
+    PoseErrorSymState* S = ctx_state<PoseErrorSymState>(c);
     const PsLayout L = ps_layout(1, 1, (size_t)K);
     { const int rc = S->work.grow(c->stream, L.cv.total); if (rc) return rc; }
     const size_t back_bytes = (size_t)K * sizeof(PsPerK);

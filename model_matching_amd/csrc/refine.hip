@@ -61,11 +61,13 @@ struct RefineGrid {
     DevBlock mem;
 };
 
-struct RefineState {
+struct RefineState {   // (value-initialised: no grid, no workspace)
+    static const StateOwner OWNER = OWN_REFINE;
     RefineGrid g;
     DevBlock work;   // hypotheses | T in | source indices | partials | outputs (grow-only)
     DevBlock detail; // stocs_refine_detail: match | counted | sums (grow-only)
     DevBlock robust; // refine_robust.h: rank words | model indices | select results of stocs_refine_poses_robust (grow-only)
+    ~RefineState() { g.mem.free(); work.free(); detail.free(); robust.free(); }
 };
 
 __global__ __launch_bounds__(256) void refine_keys_kernel(const float4* __restrict__ mpos, int nM, float ox, float oy, float oz, float inv_h, int nx, int ny,
@@ -472,10 +474,7 @@ int refine_prepare(stocs_ctx* c, const char* who, int n, int nsrc, const RefineS
         if (const char* e = getenv("STOCS_REFINE_ROBUST_GROUP_BYTES")) { const long long v = atoll(e); if (v > 0 && (uint64_t)v < limit) limit = (uint64_t)v; }
         if (!(flags & REFINE_ONE_GROUP)) group = (int)std::min<uint64_t>(std::max<uint64_t>(limit / per, 1), (uint64_t)group);
     }
-    if (!c->refine) {
-        c->refine = new RefineState();   // (value-initialised: no grid, no workspace)
-    }
-    RefineState* S = (RefineState*)c->refine;
+    RefineState* S = ctx_state<RefineState>(c);
     if (S->g.dist != s.distance) {
         const int rc = build_refine_grid(c, S, s.distance);
         if (rc) { S->g.dist = 0.0f; return rc; }
@@ -511,7 +510,7 @@ int refine_prepare(stocs_ctx* c, const char* who, int n, int nsrc, const RefineS
 // the model in LDS takes
 struct RefEval { RefArgs a; RobustArgs r; size_t lds_bytes; };
 static RefEval refine_eval_args(stocs_ctx* c, const RefineWork& w, bool use_idx) {
-    RefineState* S = (RefineState*)c->refine;
+    RefineState* S = ctx_state_if<RefineState>(c);
     RefEval e;
     RefArgs& a = e.a;
     a.spos = c->d_spos; a.idx = use_idx ? w.d_idx : NULL; a.nsrc = w.nsrc; a.nchunks = w.nchunks; a.nM = c->nM; a.nsub = 8 * S->g.nx * S->g.ny * S->g.nz;
@@ -674,7 +673,7 @@ static int refine_detail_call(stocs_ctx* c, const char* who, const float* T16_in
     DeviceGuard dev_guard(c->device);
     RefineWork w;
     { const int rc = refine_prepare(c, who, 1, nsrc, s, robust ? REFINE_ONE_GROUP | REFINE_ROWS : REFINE_ONE_GROUP, &w); if (rc) return rc; }
-    RefineState* S = (RefineState*)c->refine;
+    RefineState* S = ctx_state_if<RefineState>(c);
     const size_t cells = (size_t)std::max(nsrc, 1);
     Carve cv;
     const size_t o_match = cv.take(cells * 4), o_flag = cv.take(cells), o_sums = cv.take(28 * 8);
@@ -716,14 +715,6 @@ static int refine_detail_call(stocs_ctx* c, const char* who, const float* T16_in
 
 using namespace stocs;
 
-extern "C" void stocs_internal_free_refine(stocs_ctx* c) {
-    if (!c || !c->refine) return;
-    RefineState* S = (RefineState*)c->refine;
-    S->g.mem.free(); S->work.free(); S->detail.free(); S->robust.free();
-    delete S;
-    c->refine = NULL;
-}
-
 extern "C" int stocs_refine_poses(stocs_ctx* c, const float* T16_in, int n, const int32_t* src_idx, int n_src, int max_iterations,
                                   float max_correspondence_distance, float* T16_out, float* pose16_out, float* lcp_out, int32_t* n_corr_out,
                                   int32_t* iterations_out) {
@@ -762,7 +753,7 @@ extern "C" int stocs_refine_robust_detail(stocs_ctx* c, const float* T16_in, con
 
 extern "C" int stocs_refine_robust_workspace(stocs_ctx* c, void** address, uint64_t* bytes) {
     if (!c) { set_error("stocs_refine_robust_workspace: NULL context"); return STOCS_ERR_INVALID; }
-    RefineState* S = (RefineState*)c->refine;
+    RefineState* S = ctx_state_if<RefineState>(c);
     if (address) *address = S ? (void*)S->robust.p : NULL;
     if (bytes) *bytes = S ? (uint64_t)S->robust.bytes : 0;
     return STOCS_OK;

@@ -39,9 +39,11 @@ enum { RV_PRESENT = 0, RV_NO_DEPTH, RV_OFF_CLASS, RV_TOO_FAR, RV_GRAZING };   //
 static const unsigned long long RV_EMPTY = 0xFFFFFFFFFFFFFFFFull;
 
 struct RefineVisibleState {
+    static const StateOwner OWNER = OWN_REFINE_VISIBLE;
+    ~RefineVisibleState() { work.free(); detail.free(); }
     DevBlock work;     // poses | records | frozen flags | rectangles | partial sums | partial counts | one chunk of key buffers, grow-only
     DevBlock detail;   // stocs_refine_visible_detail: state | sums, grow-only
-    float last_ms[3];  // "device_clock": HIP-event time of the last call's last render, accumulation and solve (-1: not taken)
+    float last_ms[3] = {-1.0f, -1.0f, -1.0f};  // "device_clock": HIP-event time of the last call's last render, accumulation and solve (-1: not taken)
 };
 
 struct RvArgs {
@@ -234,15 +236,6 @@ __global__ __launch_bounds__(64) void refine_visible_solve_kernel(float* __restr
     R->iterations += 1;
 }
 
-static RefineVisibleState* refine_visible_state(stocs_ctx* c) {
-    if (!c->refine_visible) {
-        RefineVisibleState* S = new RefineVisibleState();
-        S->last_ms[0] = S->last_ms[1] = S->last_ms[2] = -1.0f;
-        c->refine_visible = S;
-    }
-    return (RefineVisibleState*)c->refine_visible;
-}
-
 static const char* params_error(const stocs_refine_visible_params* p) {
     if (p->max_iterations < 0) return "max_iterations must be >= 0";
     if (!(p->max_distance > 0.0f) || !isfinite(p->max_distance)) return "max_distance must be positive and finite";
@@ -280,7 +273,7 @@ static int visible_work(stocs_ctx* c, int n, size_t chunk, size_t npix, int grou
     w->o_cnt = cv.take(chunk * (size_t)groups * RV_COUNTS * 4);
     w->o_key = cv.take(chunk * npix * 8);
     w->total = cv.total;
-    RefineVisibleState* S = refine_visible_state(c);
+    RefineVisibleState* S = ctx_state<RefineVisibleState>(c);
     { const int rc = S->work.grow(c->stream, cv.total); if (rc) return rc; }
     w->d = S->work.p;
     return STOCS_OK;
@@ -320,14 +313,6 @@ static RvArgs visible_args(const stocs_refine_visible_params* p, int groups) {
 
 using namespace stocs;
 
-extern "C" void stocs_internal_free_refine_visible(stocs_ctx* c) {
-    if (!c || !c->refine_visible) return;
-    RefineVisibleState* S = (RefineVisibleState*)c->refine_visible;
-    S->work.free(); S->detail.free();
-    delete S;
-    c->refine_visible = NULL;
-}
-
 extern "C" void stocs_default_refine_visible_params(stocs_refine_visible_params* p) {
     if (!p) return;
     p->max_iterations = 5; p->max_distance = 0.02f; p->min_view_cos = 0.0f; p->class_threshold = 0.10f;
@@ -346,7 +331,7 @@ extern "C" int stocs_refine_visible_groups(int width, int height) {
 
 extern "C" int stocs_refine_visible_last_device_ms(const stocs_ctx* c, float* render_ms, float* accumulate_ms, float* solve_ms) {
     if (!c) { set_error("stocs_refine_visible_last_device_ms: NULL context"); return STOCS_ERR_INVALID; }
-    const RefineVisibleState* S = (const RefineVisibleState*)c->refine_visible;
+    const RefineVisibleState* S = ctx_state_if<RefineVisibleState>(c);
     if (render_ms) *render_ms = S ? S->last_ms[0] : -1.0f;
     if (accumulate_ms) *accumulate_ms = S ? S->last_ms[1] : -1.0f;
     if (solve_ms) *solve_ms = S ? S->last_ms[2] : -1.0f;
@@ -392,7 +377,7 @@ extern "C" int stocs_refine_poses_visible(stocs_ctx* c, const float* poses, int 
     }
     STOCS_HIP_CHECK(hipMemcpyAsync(hback, w.pose(), back_bytes, hipMemcpyDeviceToHost, c->stream));
     STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    RefineVisibleState* S = refine_visible_state(c);
+    RefineVisibleState* S = ctx_state<RefineVisibleState>(c);
     S->last_ms[0] = S->last_ms[1] = S->last_ms[2] = -1.0f;
     if (dev_clock) {
         float ms = 0.0f;
@@ -417,7 +402,7 @@ extern "C" int stocs_refine_visible_detail(stocs_ctx* c, const float* pose, cons
     const int groups = refine_visible_groups(npix);
     VisibleWork w;
     { const int rc = visible_work(c, 1, 1, npix, groups, &w); if (rc) return rc; }
-    RefineVisibleState* S = refine_visible_state(c);
+    RefineVisibleState* S = ctx_state<RefineVisibleState>(c);
     Carve cv;
     const size_t o_state = cv.take(npix), o_sums = cv.take(RV_SUMS * 8);
     { const int rc = S->detail.grow(c->stream, cv.total); if (rc) return rc; }

@@ -29,6 +29,8 @@ enum { RENDER_CHUNK = 1024, RENDER_MAX_PIXELS = 1 << 19 };
 enum { RC_FOOTPRINT = 0, RC_HIDDEN, RC_NO_DEPTH, RC_AGREE, RC_IN_FRONT, RC_BEHIND, RC_ON_MASK, RC_COUNTS };
 
 struct RenderState {
+    static const StateOwner OWNER = OWN_RENDER;
+    ~RenderState() { work.free(); }
     DevBlock work;   // own key buffer (npix uint64, stocs_explain_poses) | poses (n x 16 float) | records | labels | state, grow-only
 };
 
@@ -135,10 +137,6 @@ __global__ __launch_bounds__(256) void render_labels_kernel(const unsigned long 
     state[px] = empty ? (uint8_t)0 : (uint8_t)classify_pixel(__uint_as_float((uint32_t)(key >> 32)), px, depth, prob, a);
 }
 
-static RenderState* render_state(stocs_ctx* c) {
-    if (!c->render) c->render = new RenderState();
-    return (RenderState*)c->render;
-}
 
 int render_check_ids(const char* who, int n, int id_base) {
     if (id_base < 0 || (long long)id_base + (long long)n > 2147483647ll) {
@@ -169,7 +167,7 @@ int render_layout(stocs_ctx* c, DevBlock* work, size_t own_key, int n, size_t la
     L->d = work->p + L->key_bytes;
     return STOCS_OK;
 }
-static int render_layout(stocs_ctx* c, size_t own_key, int n, size_t label_px, RenderLayout* L) { return render_layout(c, &render_state(c)->work, own_key, n, label_px, 0, L); }
+static int render_layout(stocs_ctx* c, size_t own_key, int n, size_t label_px, RenderLayout* L) { return render_layout(c, &ctx_state<RenderState>(c)->work, own_key, n, label_px, 0, L); }
 
 int render_upload_poses(stocs_ctx* c, const RenderLayout& L, const float* poses, int n) {
     memcpy(L.h + L.o_pose, poses, (size_t)n * 64);
@@ -223,14 +221,6 @@ int render_read_back(stocs_ctx* c, const RenderLayout& L, size_t from, size_t to
 }  // namespace stocs
 
 using namespace stocs;
-
-extern "C" void stocs_internal_free_render(stocs_ctx* c) {
-    if (!c || !c->render) return;
-    RenderState* R = (RenderState*)c->render;
-    R->work.free();
-    delete R;
-    c->render = NULL;
-}
 
 extern "C" void stocs_default_render_params(stocs_render_params* p) {
     if (!p) return;
@@ -317,7 +307,7 @@ extern "C" int stocs_explain_poses(stocs_ctx* c, const float* poses, int n, cons
     DeviceGuard dev_guard(c->device);
     RenderLayout L;
     { const int rc = render_layout(c, S->npix, n, labels ? S->npix : 0, &L); if (rc) return rc; }
-    void* d_zkey = ((RenderState*)c->render)->work.p;
+    void* d_zkey = ctx_state_if<RenderState>(c)->work.p;
     { const int rc = render_upload_poses(c, L, poses, n); if (rc) return rc; }
     { const int rc = render_enqueue_clear(c, S, d_zkey); if (rc) return rc; }
     { const int rc = enqueue_splat(c, S, L, n, prm, 0, d_zkey); if (rc) return rc; }

@@ -30,11 +30,13 @@ enum { RM_RUNS_PER_WAVE = 8 };
 enum { RM_FOOTPRINT = 0, RM_VISIBLE, RM_HIDDEN, RM_NO_DEPTH, RM_AGREE, RM_IN_FRONT, RM_BEHIND, RM_ON_MASK, RM_COUNTS };   // the fields of stocs_render_result in order
 
 struct RenderMeshState {
+    static const StateOwner OWNER = OWN_RENDER_MESH;
+    ~RenderMeshState() { render.free(); resolve.free(); explain.free(); scene.free(); }
     DevBlock render;    // stocs_render_poses_mesh: poses | rectangles, grow-only
     DevBlock resolve;   // stocs_render_resolve_mesh: poses | records | one chunk of rectangles and z-buffers, grow-only
     DevBlock explain;   // stocs_explain_poses_mesh: own key buffer | poses | records | labels | state | rectangles | one chunk of rectangles and z-buffers, grow-only
     DevBlock scene;     // stocs_scene_footprints_mesh: poses | records | one chunk of z-buffers and rectangles, grow-only
-    float last_ms[2];   // "device_clock": HIP-event time of the last call's key render and of its last chunk's resolve kernel (-1: not taken)
+    float last_ms[2] = {-1.0f, -1.0f};   // "device_clock": HIP-event time of the last call's key render and of its last chunk's resolve kernel (-1: not taken)
 };
 
 // pose blockIdx.y of the chunk: its z-buffer at zbuf + blockIdx.y * npix, its rectangle at box + blockIdx.y * VSD_BOX_WORDS, its id
@@ -82,15 +84,6 @@ __global__ __launch_bounds__(256) void render_resolve_mesh_kernel(const uint32_t
     if (tid < RM_COUNTS && cnt[tid]) atomicAdd((int32_t*)(rec + h) + tid, cnt[tid]);   // the record's fields in the order of the RM_ enum
 }
 
-static RenderMeshState* render_mesh_state(stocs_ctx* c) {
-    if (!c->render_mesh) {
-        RenderMeshState* R = new RenderMeshState();
-        R->last_ms[0] = R->last_ms[1] = -1.0f;
-        c->render_mesh = R;
-    }
-    return (RenderMeshState*)c->render_mesh;
-}
-
 // how many poses a chunk of z-buffers holds: 256 MB of them, or what STOCS_RENDER_MESH_CHUNK says; the pose is blockIdx.y
 static size_t resolve_chunk(int n, size_t npix) {
     size_t chunk = std::max<size_t>(1, ((size_t)256 << 20) / (4 * npix));
@@ -135,7 +128,7 @@ static int enqueue_keys(stocs_ctx* c, const float* d_pose, int n, const DepthArg
 
 // after the call's synchronisation: the events of a "device_clock" call into last_ms
 static void read_clock(stocs_ctx* c, bool keys, bool resolve) {
-    RenderMeshState* R = render_mesh_state(c);
+    RenderMeshState* R = ctx_state<RenderMeshState>(c);
     R->last_ms[0] = R->last_ms[1] = -1.0f;
     if (!c->device_clock) return;
     float ms = 0.0f;
@@ -153,17 +146,9 @@ static int fill_mesh(stocs_ctx* c, const void*, const float* d_pose, int m, cons
 
 using namespace stocs;
 
-extern "C" void stocs_internal_free_render_mesh(stocs_ctx* c) {
-    if (!c || !c->render_mesh) return;
-    RenderMeshState* R = (RenderMeshState*)c->render_mesh;
-    R->render.free(); R->resolve.free(); R->explain.free(); R->scene.free();
-    delete R;
-    c->render_mesh = NULL;
-}
-
 extern "C" int stocs_render_mesh_last_device_ms(const stocs_ctx* c, float* key_ms, float* resolve_ms) {
     if (!c) { set_error("stocs_render_mesh_last_device_ms: NULL context"); return STOCS_ERR_INVALID; }
-    const RenderMeshState* R = (const RenderMeshState*)c->render_mesh;
+    const RenderMeshState* R = ctx_state_if<RenderMeshState>(c);
     if (key_ms) *key_ms = R ? R->last_ms[0] : -1.0f;
     if (resolve_ms) *resolve_ms = R ? R->last_ms[1] : -1.0f;
     return STOCS_OK;
@@ -182,7 +167,7 @@ extern "C" int stocs_render_poses_mesh(stocs_ctx* c, const float* poses, int n, 
     DeviceGuard dev_guard(c->device);
     const bool dev_clock = c->device_clock != 0;
     RenderLayout L;
-    { const int rc = render_layout(c, &render_mesh_state(c)->render, 0, n, 0, al256((size_t)n * VSD_BOX_WORDS * 4), &L); if (rc) return rc; }
+    { const int rc = render_layout(c, &ctx_state<RenderMeshState>(c)->render, 0, n, 0, al256((size_t)n * VSD_BOX_WORDS * 4), &L); if (rc) return rc; }
     { const int rc = render_upload_poses(c, L, poses, n); if (rc) return rc; }
     if (clear) { const int rc = render_enqueue_clear(c, S, d_zkey); if (rc) return rc; }
     { const int rc = enqueue_keys(c, (const float*)(L.d + L.o_pose), n, frame_args(S, 1.0f, 0.0f), id_base, d_zkey, (int32_t*)(L.d + L.o_tail), dev_clock); if (rc) return rc; }
@@ -207,7 +192,7 @@ extern "C" int stocs_render_resolve_mesh(stocs_ctx* c, const float* poses, int n
     const bool dev_clock = c->device_clock != 0;
     const size_t chunk = resolve_chunk(n, S->npix);
     RenderLayout L;
-    { const int rc = render_layout(c, &render_mesh_state(c)->resolve, 0, n, 0, resolve_tail(chunk, S->npix), &L); if (rc) return rc; }
+    { const int rc = render_layout(c, &ctx_state<RenderMeshState>(c)->resolve, 0, n, 0, resolve_tail(chunk, S->npix), &L); if (rc) return rc; }
     { const int rc = render_upload_poses(c, L, poses, n); if (rc) return rc; }
     { const int rc = enqueue_resolve_mesh(c, S, L, L.o_tail, chunk, n, frame_args(S, prm), id_base, d_zkey, dev_clock); if (rc) return rc; }
     { const int rc = render_read_back(c, L, L.o_res, L.o_res + (size_t)n * sizeof(stocs_render_result)); if (rc) return rc; }
@@ -237,7 +222,7 @@ extern "C" int stocs_explain_poses_mesh(stocs_ctx* c, const float* poses, int n,
     }
     DeviceGuard dev_guard(c->device);
     const bool dev_clock = c->device_clock != 0;
-    RenderMeshState* R = render_mesh_state(c);
+    RenderMeshState* R = ctx_state<RenderMeshState>(c);
     const size_t chunk = resolve_chunk(n, S->npix);
     const size_t key_boxes = al256((size_t)n * VSD_BOX_WORDS * 4);
     RenderLayout L;
@@ -275,5 +260,5 @@ extern "C" int stocs_scene_footprints_mesh(stocs_ctx* c, const float* poses, int
     { const int rc = check_frame(who, c, &F); if (rc) return rc; }
     { const int rc = scene_check_pixels(who, F->npix); if (rc) return rc; }
     const SceneFill fill = {fill_mesh, NULL, (size_t)VSD_BOX_WORDS * 4};
-    return scene_footprints_with(c, F, &render_mesh_state(c)->scene, fill, poses, n, slot_base, prm->tolerance, prm->class_threshold, claim, d_rows, out);
+    return scene_footprints_with(c, F, &ctx_state<RenderMeshState>(c)->scene, fill, poses, n, slot_base, prm->tolerance, prm->class_threshold, claim, d_rows, out);
 }

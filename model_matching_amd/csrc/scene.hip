@@ -40,6 +40,8 @@ enum { SC_FOOTPRINT = 0, SC_NO_DEPTH, SC_AGREE, SC_IN_FRONT, SC_BEHIND, SC_ON_MA
 #define SCENE_SELECT_MAX_LDS ((SCENE_MAX_PIXELS / 8) + SCENE_MAX_GROUPS * 4 + 4 * COVER_WAVES * 4)
 
 struct SceneState {
+    static const StateOwner OWNER = OWN_SCENE;
+    ~SceneState() { work.free(); sel.free(); }
     DevBlock work;   // footprints: poses (n x 16 float) | records | one chunk of z-buffers, grow-only
     DevBlock sel;    // select: score | group | in_front | footprint | caps | own | eligible | keys (2) | slots (2) | rank | excl | cover | counts | results + selected + count | sort scratch
 };
@@ -181,10 +183,6 @@ __global__ __launch_bounds__(256) void scene_finish_kernel(const uint32_t* __res
     }
 }
 
-static SceneState* scene_state(stocs_ctx* c) {
-    if (!c->scene) c->scene = new SceneState();
-    return (SceneState*)c->scene;
-}
 
 static int check_params(const char* who, const stocs_scene_params* p) {
     if (p->max_selected < 1) { set_error("%s: max_selected %d < 1", who, p->max_selected); return STOCS_ERR_INVALID; }
@@ -211,14 +209,6 @@ int scene_check_pixels(const char* who, size_t npix) {
 }  // namespace stocs
 
 using namespace stocs;
-
-extern "C" void stocs_internal_free_scene(stocs_ctx* c) {
-    if (!c || !c->scene) return;
-    SceneState* S = (SceneState*)c->scene;
-    S->work.free(); S->sel.free();
-    delete S;
-    c->scene = NULL;
-}
 
 extern "C" void stocs_default_scene_params(stocs_scene_params* p) {
     if (!p) return;
@@ -250,7 +240,7 @@ extern "C" int stocs_scene_footprints(stocs_ctx* c, const float* poses, int n, i
     { const int rc = scene_check_pixels(who, F->npix); if (rc) return rc; }
     const RenderArgs ra = render_args(prm, 0);
     const SceneFill fill = {fill_splats, &ra, 0};
-    return scene_footprints_with(c, F, &scene_state(c)->work, fill, poses, n, slot_base, prm->tolerance, prm->class_threshold, claim, d_rows, out);
+    return scene_footprints_with(c, F, &ctx_state<SceneState>(c)->work, fill, poses, n, slot_base, prm->tolerance, prm->class_threshold, claim, d_rows, out);
 }
 
 // the splats as a SceneFill: self is the call's RenderArgs
@@ -329,7 +319,7 @@ extern "C" int stocs_scene_select(stocs_ctx* c, const void* d_rows, int n, int w
     *n_selected = 0;
     if (n == 0) return STOCS_OK;
     DeviceGuard dev_guard(c->device);
-    SceneState* S = scene_state(c);
+    SceneState* S = ctx_state<SceneState>(c);
     const int Wr = row_words(npix);
     SceneArgs a;
     a.max_selected = prm->max_selected < n ? prm->max_selected : n;   // no more can be selected than there are

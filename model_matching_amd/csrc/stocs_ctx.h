@@ -251,6 +251,42 @@ struct Thresholds {
     float ang_dot_lo;
 };
 
+// The records of stocs_ctx::timing: the last call of each of these entry points.  stocs_last_call_timing serves the slots below
+// TIMING_VSD_MESH, stocs_mesh_last_call_timing that one
+enum TimingSlot {
+    TIMING_CONGRUENT,        // stocs_find_congruent_all
+    TIMING_TRANSFORMS,       // stocs_make_transforms
+    TIMING_VERIFY,           // stocs_verify_all
+    TIMING_TRIALS,           // stocs_run_trials
+    TIMING_POSE_ERRORS,      // stocs_pose_errors
+    TIMING_POSE_ERRORS_SYM,  // stocs_pose_errors_sym
+    TIMING_SYMMETRY,         // stocs_symmetry_errors
+    TIMING_VSD,              // stocs_pose_errors_vsd
+    TIMING_VSD_MESH,         // stocs_pose_errors_vsd_mesh
+    TIMING_COUNT
+};
+
+// Per-feature state of a context (stocs_ctx::state): a struct that its owner file defines, made at the feature's first call
+// (ctx_state) and deleted by stocs_ctx_destroy in the order of this enum.  The struct names its slot (`static const StateOwner OWNER`)
+// and frees its device blocks in its destructor.  A new feature adds an enumerator here and a struct in its own file, nothing else
+enum StateOwner {
+    OWN_REFINE,          // refine.hip: the model's correspondence grid of stocs_refine_poses and its grow-only workspace
+    OWN_TRACK,           // track.hip: stocs_track_poses's grow-only workspace and the details of its last call
+    OWN_DEPTH,           // depth_frame.h: the frame of stocs_ctx_set_frame and stocs_depth_check_poses's grow-only workspace
+    OWN_INSTANCES,       // instances.hip: stocs_select_instances's grow-only workspace
+    OWN_RENDER,          // render.hip: the grow-only workspace of stocs_render_poses and its kin
+    OWN_SCENE,           // scene.hip: the grow-only workspaces of stocs_scene_footprints and stocs_scene_select
+    OWN_POSE_ERROR,      // pose_error.hip: the grow-only workspace of stocs_pose_errors and its kin, the cached diameter
+    OWN_POSE_ERROR_SYM,  // pose_error_sym.hip: the grow-only workspace of stocs_pose_errors_sym and its detail form
+    OWN_SYMMETRY,        // symmetry.hip: the model's self-distance grid of stocs_symmetry_errors and its grow-only workspace
+    OWN_VSD,             // vsd.hip: the grow-only workspace of stocs_pose_errors_vsd and stocs_render_depth
+    OWN_MESH,            // mesh.hip: the triangle mesh of stocs_ctx_set_mesh on the device
+    OWN_RENDER_MESH,     // render_mesh.hip: the grow-only workspaces of stocs_render_poses_mesh and its kin
+    OWN_REFINE_VISIBLE,  // refine_visible.hip: the grow-only workspace of stocs_refine_poses_visible and its detail form
+    OWN_COUNT
+};
+struct StateSlot { void* p = NULL; void (*del)(void*) = NULL; };
+
 }  // namespace stocs
 
 struct stocs_ctx {
@@ -352,8 +388,6 @@ struct stocs_ctx {
     // bits per model id below the base id
     void* cong;
     std::vector<unsigned long long> quad_off;
-    void* refine;   // refine.hip (RefineState): the model's correspondence grid of stocs_refine_poses and its grow-only workspace
-    void* track;    // track.hip (TrackState): stocs_track_poses's grow-only workspace and the details of its last call
     int quad_id_bits;
     // candidates of the last stocs_make_transforms: device-resident (compacted, in pick order) as
     // T[n][16] | pose[n][16] | lcp[n] | base[n] inside d_cand; `cands` is the host mirror, filled on demand
@@ -372,7 +406,7 @@ struct stocs_ctx {
     // pageable memory goes through the runtime's own staging and is one more thing that can stall (ensure_pinned grows it)
     void* h_pin;
     size_t pin_bytes;
-    stocs::CallTiming timing[9];   // last stocs_find_congruent_all / stocs_make_transforms / stocs_verify_all / stocs_run_trials / stocs_pose_errors / stocs_pose_errors_sym / stocs_symmetry_errors / stocs_pose_errors_vsd / stocs_pose_errors_vsd_mesh (the last through stocs_mesh_last_call_timing)
+    stocs::CallTiming timing[stocs::TIMING_COUNT];
 
     stocs::StreamAudit audit;   // STOCS_DEBUG_STREAMS=1: happens-before check of the two-stream sections (stream_audit.h); off otherwise
 
@@ -380,34 +414,21 @@ struct stocs_ctx {
     void* d_scratch;
     size_t scratch_bytes;
 
-    void* depth;    // depth.hip (DepthState): the frame of stocs_ctx_set_frame and stocs_depth_check_poses's grow-only workspace (last: no other member moves)
-
     // what the last stocs_sample_bases / stocs_run_trials* call ran, class or instance mode (sample.hip; read by stocs_last_sampling_form): host
     // bookkeeping only.  kernel < 0: no class-mode call yet
     struct { int kernel, threads; size_t lds; int cap, launches, redone; } last_form;
 
-    void* instances;   // instances.hip (InstancesState): stocs_select_instances's grow-only workspace (last: no other member moves)
-
-    void* render;      // render.hip (RenderState): the grow-only workspace of stocs_render_poses and its kin (last: no other member moves)
-
-    void* scene;       // scene.hip (SceneState): the grow-only workspaces of stocs_scene_footprints and stocs_scene_select (last: no other member moves)
-
-    void* pose_error;  // pose_error.hip (PoseErrorState): the grow-only workspace of stocs_pose_errors and its kin, the cached diameter (last: no other member moves)
-
-    void* pose_error_sym;  // pose_error_sym.hip (PoseErrorSymState): the grow-only workspace of stocs_pose_errors_sym and its detail form (last: no other member moves)
-
-    void* symmetry;        // symmetry.hip (SymmetryState): the model's self-distance grid of stocs_symmetry_errors and its grow-only workspace (last: no other member moves)
-
-    void* vsd;             // vsd.hip (VsdState): the grow-only workspace of stocs_pose_errors_vsd and stocs_render_depth (last: no other member moves)
-
-    void* mesh;            // mesh.hip (MeshState): the triangle mesh of stocs_ctx_set_mesh on the device (last: no other member moves)
-
-    void* render_mesh;     // render_mesh.hip (RenderMeshState): the grow-only workspaces of stocs_render_poses_mesh and its kin (last: no other member moves)
-
-    void* refine_visible;  // refine_visible.hip (RefineVisibleState): the grow-only workspace of stocs_refine_poses_visible and its detail form (last: no other member moves)
+    stocs::StateSlot state[stocs::OWN_COUNT];   // per-feature state, see StateOwner
 };
 
 namespace stocs {
+// the state of T's feature on the context, made at first use / as it stands, NULL when the feature has not run (for the readers)
+template <class T> inline T* ctx_state(stocs_ctx* c) {
+    StateSlot& s = c->state[T::OWNER];
+    if (!s.p) { s.p = new T(); s.del = [](void* p) { delete (T*)p; }; }
+    return (T*)s.p;
+}
+template <class T> inline T* ctx_state_if(const stocs_ctx* c) { return (T*)c->state[T::OWNER].p; }
 inline void clear_candidates(stocs_ctx* c) { c->cands.clear(); c->n_cands = 0; c->cands_stale = false; }
 // the base set is (again) one trial's: whoever replaces or extends it outside stocs_run_trials calls this first
 inline void clear_trial_batch(stocs_ctx* c) {
@@ -481,19 +502,6 @@ extern "C" void stocs_internal_free_congruent(stocs_ctx* c);
 extern "C" void stocs_internal_invalidate_congruent(stocs_ctx* c);
 extern "C" void stocs_internal_free_instance(stocs_ctx* c);
 extern "C" void stocs_internal_free_trials(stocs_ctx* c);
-extern "C" void stocs_internal_free_refine(stocs_ctx* c);
-extern "C" void stocs_internal_free_track(stocs_ctx* c);
-extern "C" void stocs_internal_free_depth(stocs_ctx* c);
-extern "C" void stocs_internal_free_instances(stocs_ctx* c);
-extern "C" void stocs_internal_free_render(stocs_ctx* c);
-extern "C" void stocs_internal_free_scene(stocs_ctx* c);
-extern "C" void stocs_internal_free_pose_error(stocs_ctx* c);
-extern "C" void stocs_internal_free_pose_error_sym(stocs_ctx* c);
-extern "C" void stocs_internal_free_symmetry(stocs_ctx* c);
-extern "C" void stocs_internal_free_vsd(stocs_ctx* c);
-extern "C" void stocs_internal_free_mesh(stocs_ctx* c);
-extern "C" void stocs_internal_free_render_mesh(stocs_ctx* c);
-extern "C" void stocs_internal_free_refine_visible(stocs_ctx* c);
 // the congruent phase with a ceiling on its device memory: *too_big != 0 (and STOCS_OK) when the pair lists of the context's base set
 // would need more than max_bytes (0: no ceiling) or exceed 2^32 entries -- a trial batch then splits the base set and tries again
 extern "C" int stocs_internal_find_congruent(stocs_ctx* c, int64_t* total_quads, size_t max_bytes, int* too_big);

@@ -25,6 +25,7 @@
 // waits for that copy).  `mean`, `valid` are filled on the host.  The helpers and the search below the entry points are host code.
 #include <string.h>
 
+#include "eval_call.h"
 #include "pose_error_math.h"
 #include "symmetry.h"
 
@@ -35,7 +36,9 @@ enum { SY_THREADS = STOCS_SYMMETRY_THREADS, SY_WAVES = SY_THREADS / 64, SY_MAX_L
 static_assert(SY_THREADS % 64 == 0, "whole wavefronts");
 
 struct SymmetryState {
+    static const StateOwner OWNER = OWN_SYMMETRY;
     DevBlock grid, work;
+    ~SymmetryState() { grid.free(); work.free(); }
     bool have_grid = false;
     float reach = 0.0f;
     SymGrid g;
@@ -120,12 +123,6 @@ __global__ __launch_bounds__(SY_THREADS) void symmetry_kernel(const float* __res
     }
 }
 
-static SymmetryState* symmetry_state(stocs_ctx* c) {
-    if (!c->symmetry) c->symmetry = new SymmetryState();
-    return (SymmetryState*)c->symmetry;
-}
-
-static bool sy_finite(float x) { return fabsf(x) <= 3.4028234663852886e38f; }
 static bool sy_finite_d(double x) { return fabs(x) <= 1.7976931348623157e308; }
 
 // the grid of the context's model for `reach`: binned on the host with symmetry.h's expression, uploaded, kept until another reach
@@ -139,7 +136,7 @@ static int ensure_sym_grid(stocs_ctx* c, SymmetryState* S, float reach) {
     live.reserve((size_t)M);
     for (int i = 0; i < M; ++i) {
         const float v[3] = {P[i].x, P[i].y, P[i].z};
-        if (!(sy_finite(v[0]) && sy_finite(v[1]) && sy_finite(v[2]))) continue;
+        if (!(host_finite(v[0]) && host_finite(v[1]) && host_finite(v[2]))) continue;
         live.push_back(i);
         for (int a = 0; a < 3; ++a) { mn[a] = v[a] < mn[a] ? v[a] : mn[a]; mx[a] = v[a] > mx[a] ? v[a] : mx[a]; }
     }
@@ -191,9 +188,9 @@ static int ensure_sym_grid(stocs_ctx* c, SymmetryState* S, float reach) {
 }
 
 static int check_sym_args(const char* who, const float* sym, int K, const stocs_symmetry_params* p) {
-    for (int k = 0; k < K; ++k)
-        if (!host_pose_finite(sym + (size_t)k * 16)) { set_error("%s: transform %d has a non-finite entry", who, k); return STOCS_ERR_INVALID; }
-    if (!(p->reach > 0.0f) || !sy_finite(p->reach)) { set_error("%s: reach %g is not a positive finite length", who, (double)p->reach); return STOCS_ERR_INVALID; }
+    const int bad = first_nonfinite_pose(sym, K);
+    if (bad >= 0) { set_error("%s: transform %d has a non-finite entry", who, bad); return STOCS_ERR_INVALID; }
+    if (!(p->reach > 0.0f) || !host_finite(p->reach)) { set_error("%s: reach %g is not a positive finite length", who, (double)p->reach); return STOCS_ERR_INVALID; }
     if (!(p->reach * p->reach >= 1.17549435e-38f)) {   // a square that underflows would match pairs many cells apart (symmetry.h)
         set_error("%s: the square of reach %g is not a normal float", who, (double)p->reach);
         return STOCS_ERR_INVALID;
@@ -265,14 +262,6 @@ static double axis_cos(const float* a, const float* b) {
 
 using namespace stocs;
 
-extern "C" void stocs_internal_free_symmetry(stocs_ctx* c) {
-    if (!c || !c->symmetry) return;
-    SymmetryState* S = (SymmetryState*)c->symmetry;
-    S->grid.free(); S->work.free();
-    delete S;
-    c->symmetry = NULL;
-}
-
 extern "C" int stocs_symmetry_errors(stocs_ctx* c, const float* sym, int K, const stocs_symmetry_params* p, stocs_symmetry_error* out) {
     const char* who = "stocs_symmetry_errors";
     if (!c) { set_error("%s: NULL context", who); return STOCS_ERR_INVALID; }
@@ -287,21 +276,19 @@ extern "C" int stocs_symmetry_errors(stocs_ctx* c, const float* sym, int K, cons
                   (unsigned long long)STOCS_REFINE_ROBUST_MAX_WORKSPACE_BYTES);
         return STOCS_ERR_INVALID;
     }
-    if (c->nM < 1) { set_error("%s: the context has no model", who); return STOCS_ERR_STATE; }
+    { const int rc = check_model(who, c); if (rc) return rc; }
     DeviceGuard dev_guard(c->device);
-    SymmetryState* S = symmetry_state(c);
-    const bool dev_clock = c->device_clock != 0;
-    const double t_call = CallTiming::now_s();
+    SymmetryState* S = ctx_state<SymmetryState>(c);
+    TimedCall tc(c, TIMING_SYMMETRY);
     { const int rc = ensure_sym_grid(c, S, p->reach); if (rc) return rc; }
     { const int rc = S->work.grow(c->stream, cv.total); if (rc) return rc; }
     const size_t rec_bytes = (size_t)K * sizeof(stocs_symmetry_error);
     char *hin, *hback;
     { const int rc = pinned_for(c, (size_t)K * 64, rec_bytes, &hin, &hback); if (rc) return rc; }
-    CallTiming& tm = c->timing[6];   // from here on the call runs: a call refused above leaves the last call's record as it was
-    tm.begin(); tm.t_last = t_call;  // (the first step counts the grid of a new reach and the growing of the blocks)
+    tc.start();   // (the first step counts the grid of a new reach and the growing of the blocks)
     memcpy(hin, sym, (size_t)K * 64);
     STOCS_HIP_CHECK(hipMemcpyAsync(S->work.p + o_sym, hin, (size_t)K * 64, hipMemcpyHostToDevice, c->stream));
-    if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev0, c->stream));
+    { const int rc = tc.device_begin(); if (rc) return rc; }
     stocs_symmetry_error* d_rec = Carve::at<stocs_symmetry_error>(S->work.p, o_rec);
     const float reach2 = p->reach * p->reach;
     for (int k0 = 0; k0 < K; k0 += SY_MAX_LAUNCH) {
@@ -311,35 +298,26 @@ extern "C" int stocs_symmetry_errors(stocs_ctx* c, const float* sym, int K, cons
                            (const float4*)c->d_mnrm, c->nM, p->reach, reach2, p->cos_normal, d_rec + k0, (float*)NULL, (int32_t*)NULL, (float*)NULL);
         STOCS_HIP_CHECK(hipGetLastError());
     }
-    if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev1, c->stream));
+    { const int rc = tc.device_end(); if (rc) return rc; }
     STOCS_HIP_CHECK(hipMemcpyAsync(hback, d_rec, rec_bytes, hipMemcpyDeviceToHost, c->stream));
-    tm.lap("stage and enqueue");
-    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    tm.lap("wait for the device");
-    const double M = (double)c->nM;
+    { const int rc = tc.enqueued_wait(); if (rc) return rc; }
     const stocs_symmetry_error* h_rec = (const stocs_symmetry_error*)hback;
     for (int k = 0; k < K; ++k) {
         stocs_symmetry_error r = h_rec[k];
-        r.mean = (float)((double)r.sum_fix / 4294967296.0 / M);
+        r.mean = fix_mean(r.sum_fix, c->nM);
         r.valid = 1; r.reserved = 0;
         out[k] = r;
     }
-    tm.lap("records");
-    if (dev_clock) {
-        float ms = 0.0f;
-        STOCS_HIP_CHECK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        tm.label[tm.n] = "device: kernel"; tm.ms[tm.n] = (double)ms; ++tm.n;
-    }
-    return STOCS_OK;
+    return tc.finish();
 }
 
 extern "C" int stocs_symmetry_errors_detail(stocs_ctx* c, const float* sym, const stocs_symmetry_params* p, float* s, int32_t* nn, float* dot) {
     const char* who = "stocs_symmetry_errors_detail";
     if (!c || !sym || !p) { set_error("%s: NULL context, transform or parameters", who); return STOCS_ERR_INVALID; }
     { const int rc = check_sym_args(who, sym, 1, p); if (rc) return rc; }
-    if (c->nM < 1) { set_error("%s: the context has no model", who); return STOCS_ERR_STATE; }
+    { const int rc = check_model(who, c); if (rc) return rc; }
     DeviceGuard dev_guard(c->device);
-    SymmetryState* S = symmetry_state(c);
+    SymmetryState* S = ctx_state<SymmetryState>(c);
     { const int rc = ensure_sym_grid(c, S, p->reach); if (rc) return rc; }
     const size_t M = (size_t)c->nM;
     Carve cv;
@@ -394,11 +372,12 @@ extern "C" int stocs_symmetry_close(const float* gen16, int n_gen, float same_de
     *K = 0; *truncated = 0;
     if (n_gen < 0 || (n_gen > 0 && !gen16)) { set_error("%s: %d generators at %p", who, n_gen, (const void*)gen16); return STOCS_ERR_INVALID; }
     if (!out16 || cap < 1 || cap > STOCS_POSE_SYM_MAX) { set_error("%s: room for %d entries, not 1 .. %d", who, out16 ? cap : 0, (int)STOCS_POSE_SYM_MAX); return STOCS_ERR_INVALID; }
-    if (!(same_deg >= 0.0f) || !sy_finite(same_deg)) { set_error("%s: same_deg %g", who, (double)same_deg); return STOCS_ERR_INVALID; }
+    if (!(same_deg >= 0.0f) || !host_finite(same_deg)) { set_error("%s: same_deg %g", who, (double)same_deg); return STOCS_ERR_INVALID; }
     std::vector<M4d> gen((size_t)n_gen);
     double scale = 0.0;
+    const int bad = first_nonfinite_pose(gen16, n_gen);
+    if (bad >= 0) { set_error("%s: generator %d has a non-finite entry", who, bad); return STOCS_ERR_INVALID; }
     for (int k = 0; k < n_gen; ++k) {
-        if (!host_pose_finite(gen16 + (size_t)k * 16)) { set_error("%s: generator %d has a non-finite entry", who, k); return STOCS_ERR_INVALID; }
         gen[k] = m4_identity();
         for (int e = 0; e < 15; ++e)
             if ((e & 3) != 3) gen[k].e[e] = (double)gen16[(size_t)k * 16 + e];
@@ -455,13 +434,13 @@ extern "C" int stocs_find_symmetries(stocs_ctx* c, const stocs_symmetry_search* 
     sym3[0] = sym3[1] = sym3[2] = 0.0f;
     if (cap_axes < 0 || (cap_axes > 0 && !axes) || !set16 || cap_set < 1) { set_error("%s: no room for the axes or the set", who); return STOCS_ERR_INVALID; }
     const stocs_symmetry_search s = *sp;
-    if (s.n_axes < 3 || s.max_order < 2 || s.n_continuous < 1 || s.n_refine < 1 || s.n_local < 1 || s.rounds < 0 || !(s.same_deg > 0.0f) || !sy_finite(s.same_deg) ||
-        !sy_finite(s.tol_max)) {
+    if (s.n_axes < 3 || s.max_order < 2 || s.n_continuous < 1 || s.n_refine < 1 || s.n_local < 1 || s.rounds < 0 || !(s.same_deg > 0.0f) || !host_finite(s.same_deg) ||
+        !host_finite(s.tol_max)) {
         set_error("%s: search parameters out of range", who);
         return STOCS_ERR_INVALID;
     }
-    if (center3 && !(sy_finite(center3[0]) && sy_finite(center3[1]) && sy_finite(center3[2]))) { set_error("%s: non-finite centre", who); return STOCS_ERR_INVALID; }
-    if (c->nM < 1) { set_error("%s: the context has no model", who); return STOCS_ERR_STATE; }
+    if (center3 && !(host_finite(center3[0]) && host_finite(center3[1]) && host_finite(center3[2]))) { set_error("%s: non-finite centre", who); return STOCS_ERR_INVALID; }
+    { const int rc = check_model(who, c); if (rc) return rc; }
     const int M = c->nM, NO = s.max_order - 1;
     float centre[3];
     if (center3) { for (int d = 0; d < 3; ++d) centre[d] = center3[d]; }
@@ -469,14 +448,14 @@ extern "C" int stocs_find_symmetries(stocs_ctx* c, const stocs_symmetry_search* 
         double sum[3] = {0.0, 0.0, 0.0};
         for (int i = 0; i < M; ++i) { sum[0] += (double)c->h_mpos_raw[i].x; sum[1] += (double)c->h_mpos_raw[i].y; sum[2] += (double)c->h_mpos_raw[i].z; }
         for (int d = 0; d < 3; ++d) centre[d] = (float)(sum[d] / (double)M);
-        if (!(sy_finite(centre[0]) && sy_finite(centre[1]) && sy_finite(centre[2]))) { set_error("%s: the model's centroid is not finite", who); return STOCS_ERR_INVALID; }
+        if (!(host_finite(centre[0]) && host_finite(centre[1]) && host_finite(centre[2]))) { set_error("%s: the model's centroid is not finite", who); return STOCS_ERR_INVALID; }
     }
     float tol = s.tol_max;
     if (!(tol > 0.0f)) {
         float d = 0.0f;
         { const int rc = stocs_model_diameter(c, &d); if (rc) return rc; }
         tol = 0.1f * d;
-        if (!(tol > 0.0f) || !sy_finite(tol)) { set_error("%s: a model of diameter %g has no default tolerance", who, (double)d); return STOCS_ERR_INVALID; }
+        if (!(tol > 0.0f) || !host_finite(tol)) { set_error("%s: a model of diameter %g has no default tolerance", who, (double)d); return STOCS_ERR_INVALID; }
     }
     stocs_symmetry_params prm;
     prm.reach = tol; prm.cos_normal = s.cos_normal; prm.reserved[0] = prm.reserved[1] = 0;

@@ -25,10 +25,12 @@
 namespace stocs {
 
 struct TrackState {
+    static const StateOwner OWNER = OWN_TRACK;
     DevBlock mem;   // incumbents | incumbent lcp | prior lcp | results | candidates | scores (grow-only)
-    bool kept;                   // the last call kept its details (hT / hL below)
-    int n, samples, rounds;
+    bool kept = false;           // the last call kept its details (hT / hL below)
+    int n = 0, samples = 0, rounds = 0;
     std::vector<float> hT, hL;   // round-major: round r, prior p, slot j at (r * n + p) * samples + j
+    ~TrackState() { mem.free(); }
 };
 
 // round r's candidates: thread i = p * S + j.  Slot 0 copies the incumbent; slot j >= 1 perturbs it about the model origin with the
@@ -149,14 +151,6 @@ static bool prior_ok(const float* P) {
 
 using namespace stocs;
 
-extern "C" void stocs_internal_free_track(stocs_ctx* c) {
-    if (!c || !c->track) return;
-    TrackState* S = (TrackState*)c->track;
-    S->mem.free();
-    delete S;
-    c->track = NULL;
-}
-
 // stocs_track_poses and stocs_track_poses_robust (who); rs: keep_ratio and min_normal_cos of the refinement, its iterations and distance are prm's
 static int track_poses(stocs_ctx* c, const char* who, const float* priors, int n, const stocs_track_params* prm, RefineSettings rs, stocs_track_result* out) {
     if (!c) { set_error("stocs_track_poses: NULL context"); return STOCS_ERR_INVALID; }
@@ -177,12 +171,7 @@ static int track_poses(stocs_ctx* c, const char* who, const float* priors, int n
     if (c->nS <= 0) { set_error("stocs_track_poses: the context has no scene"); return STOCS_ERR_STATE; }
     DeviceGuard dev_guard(c->device);
     begin_scoring_call(c);
-    if (!c->track) {
-        TrackState* T = new TrackState();
-        T->kept = false; T->n = T->samples = T->rounds = 0;
-        c->track = T;
-    }
-    TrackState* st = (TrackState*)c->track;
+    TrackState* st = ctx_state<TrackState>(c);
     st->kept = false;
     const bool keep = prm->keep_details != 0;
     const int64_t nc = (int64_t)n * S;   // candidates per round
@@ -264,7 +253,7 @@ extern "C" int stocs_track_poses_robust(stocs_ctx* c, const float* priors, int n
 
 extern "C" int stocs_track_get_round(stocs_ctx* c, int prior, int round, float* T16, float* lcp, int cap, int* n) {
     if (!c || !n) { set_error("stocs_track_get_round: NULL context or count"); return STOCS_ERR_INVALID; }
-    const TrackState* st = (const TrackState*)c->track;
+    const TrackState* st = ctx_state_if<TrackState>(c);
     if (!st || !st->kept) { set_error("stocs_track_get_round: the last stocs_track_poses did not keep details"); return STOCS_ERR_STATE; }
     if (prior < 0 || prior >= st->n || round < 0 || round >= st->rounds) {
         set_error("stocs_track_get_round: prior %d / round %d outside [0, %d) x [0, %d)", prior, round, st->n, st->rounds);

@@ -316,7 +316,7 @@ int stocs_make_transforms(stocs_ctx* c, int max_per_base, uint64_t seed, int* n_
     if (!c || max_per_base <= 0) return STOCS_ERR_INVALID;
     DeviceGuard dev_guard(c->device);
     if (c->quad_off.size() != c->bases.size() + 1) { set_error("stocs_make_transforms: call stocs_find_congruent_all first"); return STOCS_ERR_STATE; }
-    c->timing[1].begin();   // (the steps of this call: stocs_last_call_timing(ctx, 1, ...))
+    c->timing[TIMING_TRANSFORMS].begin();   // (the steps of this call: stocs_last_call_timing(ctx, 1, ...))
     // 1. A trial without a single congruent set -- no bases, empty pair lists, or no (base, cell) that both lists occupy -- is a valid,
     // empty result (the reference's loop simply appends nothing, stocs_match_one_object.cpp:111-147): no candidates, "no pose".
     if (c->quad_off.back() == 0) {
@@ -324,7 +324,7 @@ int stocs_make_transforms(stocs_ctx* c, int max_per_base, uint64_t seed, int* n_
         c->best_lcp = 0; c->best_index = -1;
         if (n_candidates) *n_candidates = 0;
         c->trial_cand_off.assign(c->trial_first_base.size(), 0);
-        c->timing[1].lap("no congruent sets");
+        c->timing[TIMING_TRANSFORMS].lap("no congruent sets");
         return STOCS_OK;
     }
     if (max_per_base > (1 << 24)) { set_error("stocs_make_transforms: max_per_base %d exceeds 2^24", max_per_base); return STOCS_ERR_INVALID; }
@@ -348,7 +348,7 @@ int stocs_make_transforms(stocs_ctx* c, int max_per_base, uint64_t seed, int* n_
     std::vector<Pick> picks;
     std::vector<int> job_base;   // per job: the slot of its base in its own trial (what its candidates carry)
     if (!device_picks) draw_picks_host(table, trial, nbases, seed, max_per_base, &picks, &job_base);
-    c->timing[1].lap(device_picks ? "pick table (host)" : "small bases enqueued + host picks");
+    c->timing[TIMING_TRANSFORMS].lap(device_picks ? "pick table (host)" : "small bases enqueued + host picks");
     clear_candidates(c);
     c->best_lcp = 0; c->best_index = -1;
     // 4. buffers.  Candidates stay on the device: jobs -> transforms -> order-preserving compaction of the accepted ones
@@ -363,7 +363,7 @@ int stocs_make_transforms(stocs_ctx* c, int max_per_base, uint64_t seed, int* n_
         c->cand_bytes = (size_t)c->cand_cap * (16 + 16 + 1 + 1) * 4;
         STOCS_HIP_CHECK(dev_malloc((void**)&c->d_cand, c->cand_bytes));
     }
-    c->timing[1].lap("buffers (scratch, pinned, candidate block)");
+    c->timing[TIMING_TRANSFORMS].lap("buffers (scratch, pinned, candidate block)");
     if (!c->d_best) STOCS_HIP_CHECK(dev_malloc((void**)&c->d_best, 8));
     XformJob* dJ = Carve::at<XformJob>(c->d_scratch, L.jobs);
     float *dT = Carve::at<float>(c->d_scratch, L.T), *dP = Carve::at<float>(c->d_scratch, L.P);
@@ -376,11 +376,11 @@ int stocs_make_transforms(stocs_ctx* c, int max_per_base, uint64_t seed, int* n_
         if ((rc = enqueue_device_picks(c, L, batch, seed, max_per_base))) return rc;
         d_picks = Carve::at<Pick>(c->d_scratch, L.picks);
     }
-    c->timing[1].lap("enqueue pick table upload + small bases + draws (auxiliary stream)");
+    c->timing[TIMING_TRANSFORMS].lap("enqueue pick table upload + small bases + draws (auxiliary stream)");
     // 5. resolve: picks -> jobs
     const unsigned int* d_unresolved = NULL;
     if ((rc = stocs_internal_make_jobs(c, picks.data(), d_picks, (int)n, dJ, &d_unresolved))) return rc;
-    c->timing[1].lap("enqueue resolve");
+    c->timing[TIMING_TRANSFORMS].lap("enqueue resolve");
     // 6. transform, scan, compact
     if (!device_picks) STOCS_HIP_CHECK(hipMemcpyAsync(dB, job_base.data(), n * 4, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(rigid_transform_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, c->stream, c->d_spos, c->d_mpos, dJ, (int)n,
@@ -406,7 +406,7 @@ int stocs_make_transforms(stocs_ctx* c, int max_per_base, uint64_t seed, int* n_
     STOCS_HIP_CHECK(hipMemcpyAsync(&rb[0], dPos + n, 4, hipMemcpyDeviceToHost, c->stream));
     if (d_unresolved) STOCS_HIP_CHECK(hipMemcpyAsync(&rb[1], d_unresolved, 4, hipMemcpyDeviceToHost, c->stream));
     c->audit.use(0, d_picks, false, "picks", "resolve picks"); c->audit.use(0, dB, false, "job bases", "compact candidates");
-    c->timing[1].lap("enqueue transform/scan/compact + read-backs");
+    c->timing[TIMING_TRANSFORMS].lap("enqueue transform/scan/compact + read-backs");
     // 8. the one synchronisation point of this call
     STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
     c->audit.host_sync(0);
@@ -415,7 +415,7 @@ int stocs_make_transforms(stocs_ctx* c, int max_per_base, uint64_t seed, int* n_
         c->audit.violations.clear();
         return STOCS_ERR_STATE;
     }
-    c->timing[1].lap("wait for the device");
+    c->timing[TIMING_TRANSFORMS].lap("wait for the device");
     // 9. bookkeeping
     const unsigned int n_unresolved = (unsigned int)rb[1];
     if (n_unresolved) { set_error("stocs_make_transforms: %u picks could not be resolved (internal inconsistency)", n_unresolved); return STOCS_ERR_STATE; }
@@ -472,7 +472,7 @@ int stocs_verify_all(stocs_ctx* c, float* best_lcp, int* best_idx, float* best_p
     c->best_lcp = 0; c->best_index = -1;
     float pose[16];
     memset(pose, 0, sizeof(pose));
-    c->timing[2].begin();
+    c->timing[TIMING_VERIFY].begin();
     if (n > 0) {
         // scores and the arg-max stay on the device: one LCP launch over the resident transforms, then
         // compute_best_transform (stocs.cpp:987-998: strict > from 0 => first maximum wins, Q18) as an integer max
@@ -487,9 +487,9 @@ int stocs_verify_all(stocs_ctx* c, float* best_lcp, int* best_idx, float* best_p
         if ((rc = ensure_pinned(c, PIN_VAR))) return rc;
         float* out18 = (float*)((char*)c->h_pin + PIN_VERIFY);   // pinned read-back slot (18 floats)
         STOCS_HIP_CHECK(hipMemcpyAsync(out18, d_out, 18 * sizeof(float), hipMemcpyDeviceToHost, c->stream));
-        c->timing[2].lap("enqueue score + arg-max + winner");
+        c->timing[TIMING_VERIFY].lap("enqueue score + arg-max + winner");
         STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-        c->timing[2].lap("wait for the device");
+        c->timing[TIMING_VERIFY].lap("wait for the device");
         uint32_t lo, hi;
         memcpy(&lo, &out18[0], 4); memcpy(&hi, &out18[1], 4);
         const uint64_t key = ((uint64_t)hi << 32) | lo;

@@ -384,7 +384,7 @@ static int run_trials_post(stocs_ctx* c, const char* who, int mode, int n_trials
     B->post = post != NULL;
     B->hyps.assign(post ? (size_t)nT : 0, std::vector<stocs_trial_hypothesis>());
     for (int t = 0; t < nT; ++t) { memset(&B->out[(size_t)t], 0, sizeof(stocs_trial_result)); B->out[(size_t)t].best_index = -1; }
-    CallTiming& TM = c->timing[3];
+    CallTiming& TM = c->timing[TIMING_TRIALS];
     TM.begin();
     double ms_cong = 0, ms_xf = 0, ms_ver = 0, ms_asm = 0, ms_res = 0;
     const double ms_setup = now_ms() - t_entry;

@@ -31,6 +31,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "eval_call.h"
 #include "pose_error_math.h"
 #include "render_rules.h"
 #include "vsd_shared.h"
@@ -42,6 +43,8 @@ enum { VSD_POINTS = STOCS_VSD_POINTS, VSD_COUNTS = 6 + STOCS_VSD_MAX_TAU, VSD_RE
 enum { VC_PX_EST = 0, VC_PX_GT, VC_VIS_EST, VC_VIS_GT, VC_INTER, VC_UNI, VC_FAR };
 
 struct VsdState {
+    static const StateOwner OWNER = OWN_VSD;
+    ~VsdState() { work.free(); }
     DevBlock work;   // poses in render order (16 floats each) | counts (VSD_REC_WORDS int32 per pair) | the rectangles and the z-buffers of one chunk, grow-only
 };
 
@@ -192,11 +195,6 @@ __global__ __launch_bounds__(256) void vsd_compare_kernel(const uint32_t* __rest
     if (tid < VSD_COUNTS && cnt[tid]) atomicAdd(cnt_out + (size_t)pair * VSD_REC_WORDS + tid, cnt[tid]);   // the counts in the order of the VC_ enum
 }
 
-static VsdState* vsd_state(stocs_ctx* c) {
-    if (!c->vsd) c->vsd = new VsdState();
-    return (VsdState*)c->vsd;
-}
-
 // surfel_radius and max_splat_px, which both entry points read
 static int check_surfel(const char* who, const stocs_vsd_params* p) {
     if (!(p->surfel_radius > 0.0f) || !isfinite(p->surfel_radius)) { set_error("%s: surfel_radius %g must be positive and finite", who, (double)p->surfel_radius); return STOCS_ERR_INVALID; }
@@ -267,14 +265,6 @@ static int render_surfels(stocs_ctx* c, const void* self, const float* d_pose, i
 
 using namespace stocs;
 
-extern "C" void stocs_internal_free_vsd(stocs_ctx* c) {
-    if (!c || !c->vsd) return;
-    VsdState* S = (VsdState*)c->vsd;
-    S->work.free();
-    delete S;
-    c->vsd = NULL;
-}
-
 extern "C" void stocs_default_vsd_params(stocs_vsd_params* p) {
     if (!p) return;
     p->surfel_radius = 0.006f; p->max_splat_px = 16; p->delta = 0.015f; p->n_tau = 0;
@@ -290,12 +280,10 @@ int stocs::vsd_check_compare_params(const char* who, const stocs_vsd_params* p) 
 
 extern "C" int stocs_render_depth(stocs_ctx* c, const float* poses, int n, const stocs_vsd_params* prm, float* depth) {
     static const char* who = "stocs_render_depth";
-    if (!c) { set_error("%s: NULL context", who); return STOCS_ERR_INVALID; }
-    if (n < 0) { set_error("%s: n %d < 0", who, n); return STOCS_ERR_INVALID; }
-    if (n == 0) return STOCS_OK;
+    { int rc; if (check_batch(who, c, n, &rc)) return rc; }
     if (!poses || !prm || !depth) { set_error("%s: NULL poses, parameters or images", who); return STOCS_ERR_INVALID; }
     { const int rc = check_surfel(who, prm); if (rc) return rc; }
-    if (c->nM < 1) { set_error("%s: the context has no model", who); return STOCS_ERR_STATE; }
+    { const int rc = check_model(who, c); if (rc) return rc; }
     DepthState* F = NULL;
     { const int rc = check_frame(who, c, &F); if (rc) return rc; }
     const VsdSurfelArgs sa = surfel_args(prm, c->nM, (size_t)n);
@@ -305,7 +293,7 @@ extern "C" int stocs_render_depth(stocs_ctx* c, const float* poses, int n, const
 
 int stocs::vsd_render_depth_with(stocs_ctx* c, DepthState* F, const VsdRenderer& rd, const float* poses, int n, float* depth) {
     DeviceGuard dev_guard(c->device);
-    VsdState* S = vsd_state(c);
+    VsdState* S = ctx_state<VsdState>(c);
     const size_t npix = F->npix;
     // pieces of at most 32 MB of images (one at least): what the pinned block has to hold
     const size_t piece = std::min<size_t>(std::min<size_t>((size_t)n, chunk_poses(npix)), std::max<size_t>(1, ((size_t)32 << 20) / (4 * npix)));
@@ -339,27 +327,23 @@ int stocs::vsd_render_depth_with(stocs_ctx* c, DepthState* F, const VsdRenderer&
 
 extern "C" int stocs_pose_errors_vsd(stocs_ctx* c, const float* est, int n, const float* gt, int n_gt, const stocs_vsd_params* prm, stocs_vsd_record* out) {
     static const char* who = "stocs_pose_errors_vsd";
-    if (!c) { set_error("%s: NULL context", who); return STOCS_ERR_INVALID; }
-    if (n < 0) { set_error("%s: n %d < 0", who, n); return STOCS_ERR_INVALID; }
-    if (n == 0) return STOCS_OK;
-    if (!est || !gt || !prm || !out) { set_error("%s: NULL estimates, ground truth, parameters or results", who); return STOCS_ERR_INVALID; }
-    if (n_gt != 1 && n_gt != n) { set_error("%s: n_gt %d is neither 1 nor n = %d", who, n_gt, n); return STOCS_ERR_INVALID; }
+    { int rc; if (check_batch(who, c, n, &rc)) return rc; }
+    { const int rc = check_pairs(who, est, n, gt, n_gt, out); if (rc) return rc; }
+    if (!prm) { set_error("%s: NULL parameters", who); return STOCS_ERR_INVALID; }
     { const int rc = check_vsd(who, prm); if (rc) return rc; }
-    if (c->nM < 1) { set_error("%s: the context has no model", who); return STOCS_ERR_STATE; }
+    { const int rc = check_model(who, c); if (rc) return rc; }
     DepthState* F = NULL;
     { const int rc = check_frame(who, c, &F); if (rc) return rc; }
     const VsdSurfelArgs sa = surfel_args(prm, c->nM, n_gt == 1 ? (size_t)n + 1 : 2 * (size_t)n);
     const VsdRenderer rd = {render_surfels, &sa};
-    return vsd_pose_errors_with(c, F, 7, rd, est, n, gt, n_gt, prm, out);
+    return vsd_pose_errors_with(c, F, TIMING_VSD, rd, est, n, gt, n_gt, prm, out);
 }
 
-int stocs::vsd_pose_errors_with(stocs_ctx* c, DepthState* F, int timing_slot, const VsdRenderer& rd, const float* est, int n, const float* gt, int n_gt,
+int stocs::vsd_pose_errors_with(stocs_ctx* c, DepthState* F, TimingSlot timing_slot, const VsdRenderer& rd, const float* est, int n, const float* gt, int n_gt,
                                 const stocs_vsd_params* prm, stocs_vsd_record* out) {
     DeviceGuard dev_guard(c->device);
-    VsdState* S = vsd_state(c);
-    CallTiming& tm = c->timing[timing_slot];   // from here on the call runs: a call refused above leaves the last call's record as it was
-    tm.begin();
-    const bool dev_clock = c->device_clock != 0;   // opt-in: an event between two operations of a stream leaves the queue idle for a few microseconds
+    VsdState* S = ctx_state<VsdState>(c);
+    TimedCall tc(c, timing_slot);
     const size_t npix = F->npix;
     const bool one_gt = n_gt == 1;
     // render order: one ground truth first and the estimates behind it, or (ground truth k, estimate k) pair by pair
@@ -377,6 +361,7 @@ int stocs::vsd_pose_errors_with(stocs_ctx* c, DepthState* F, int timing_slot, co
     uint32_t* d_z = Carve::at<uint32_t>(S->work.p, o_z);
     int32_t* d_box = Carve::at<int32_t>(S->work.p, o_box);   // a rectangle per z-buffer, in the same order
     const bool rects = !(vsd_form() & VSD_FORM_WHOLE_FRAMES);
+    tc.start();   // (the first step counts the growing of the two blocks)
     if (one_gt) {
         memcpy(h_in, gt, 64);
         memcpy(h_in + 64, est, (size_t)n * 64);
@@ -393,7 +378,7 @@ int stocs::vsd_pose_errors_with(stocs_ctx* c, DepthState* F, int timing_slot, co
     va.delta = prm->delta; va.n_tau = prm->n_tau;
     for (int t = 0; t < STOCS_VSD_MAX_TAU; ++t) va.tau[t] = t < prm->n_tau ? prm->tau[t] : 0.0f;
     const unsigned cmp_blocks = (unsigned)((npix + 256 * VSD_ROUNDS_PER_BLOCK - 1) / (256 * VSD_ROUNDS_PER_BLOCK));
-    if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev0, c->stream));
+    { const int rc = tc.device_begin(); if (rc) return rc; }
     for (int k0 = 0; k0 < n; k0 += per) {
         const int m = std::min(per, n - k0);
         if (one_gt) {
@@ -411,30 +396,20 @@ int stocs::vsd_pose_errors_with(stocs_ctx* c, DepthState* F, int timing_slot, co
         }
         STOCS_HIP_CHECK(hipGetLastError());
     }
-    if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev1, c->stream));
+    { const int rc = tc.device_end(); if (rc) return rc; }
     STOCS_HIP_CHECK(hipMemcpyAsync(h_back, d_cnt, (size_t)n * VSD_REC_WORDS * 4, hipMemcpyDeviceToHost, c->stream));
-    tm.lap("stage and enqueue");
-    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    tm.lap("wait for the device");
+    { const int rc = tc.enqueued_wait(); if (rc) return rc; }
     for (int k = 0; k < n; ++k) {
         const int32_t* w = (const int32_t*)h_back + (size_t)k * VSD_REC_WORDS;
-        const float* P = est + (size_t)k * 16;
-        const float* G = gt + (size_t)(one_gt ? 0 : k) * 16;
         stocs_vsd_record r;
         r.px_est = w[VC_PX_EST]; r.px_gt = w[VC_PX_GT]; r.vis_est = w[VC_VIS_EST]; r.vis_gt = w[VC_VIS_GT]; r.inter = w[VC_INTER]; r.uni = w[VC_UNI];
         for (int t = 0; t < STOCS_VSD_MAX_TAU; ++t) {
             r.far[t] = w[VC_FAR + t];
             r.e[t] = t < prm->n_tau ? (r.uni > 0 ? (float)(r.far[t] + (r.uni - r.inter)) / (float)r.uni : 1.0f) : 0.0f;
         }
-        r.valid = (!host_pose_finite(P) || !host_pose_finite(G) || host_pose_zero(P)) ? 0 : 1;   // step 5 of stocs_pose_errors; the counts stand
+        r.valid = pair_valid(est, gt, n_gt, k) ? 1 : 0;   // step 5 of stocs_pose_errors; the counts stand
         r.reserved = 0;
         out[k] = r;
     }
-    tm.lap("records");
-    if (dev_clock) {
-        float ms = 0.0f;
-        STOCS_HIP_CHECK(hipEventElapsedTime(&ms, c->ev0, c->ev1));
-        tm.label[tm.n] = "device: kernel"; tm.ms[tm.n] = (double)ms; ++tm.n;
-    }
-    return STOCS_OK;
+    return tc.finish();
 }

@@ -26,7 +26,7 @@ struct VsdRenderer {
 // the bodies of stocs_render_depth and stocs_pose_errors_vsd behind their argument checks (F: the checked frame; timing_slot: the
 // CallTiming of the context that the call records into)
 int vsd_render_depth_with(stocs_ctx* c, DepthState* F, const VsdRenderer& rd, const float* poses, int n, float* depth);
-int vsd_pose_errors_with(stocs_ctx* c, DepthState* F, int timing_slot, const VsdRenderer& rd, const float* est, int n, const float* gt, int n_gt,
+int vsd_pose_errors_with(stocs_ctx* c, DepthState* F, TimingSlot timing_slot, const VsdRenderer& rd, const float* est, int n, const float* gt, int n_gt,
                          const stocs_vsd_params* prm, stocs_vsd_record* out);
 // delta, n_tau and the taus of stocs_vsd_params as stocs_check_vsd_params judges them (not the two surfel fields)
 int vsd_check_compare_params(const char* who, const stocs_vsd_params* p);
