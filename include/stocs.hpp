@@ -988,6 +988,35 @@ public:
         return r;
     }
 
+    // Damped refinement on the visible surface (stocs_refine_poses_visible_damped; no reference counterpart): refine_poses_visible with
+    // Levenberg-Marquardt steps that are bounded, turn about a point of the object (prm.pivot_model, in the model frame) and are taken only
+    // when they lower the cost, so a pose never comes back with a higher cost than it came with.  One record per pose in input order,
+    // describing the RETURNED pose; `refined` (when given) receives the poses.  Empty on error (the text goes to the log).
+    static stocs_refine_visible_damped_params default_refine_visible_damped_params() {
+        stocs_refine_visible_damped_params p;
+        stocs_default_refine_visible_damped_params(&p);
+        return p;
+    }
+    std::vector<stocs_refine_visible_damped_result> refine_poses_visible_damped(const std::vector<PoseCandidate*>& poses, std::vector<MatrixType>* refined = NULL,
+                                                                                const stocs_refine_visible_damped_params& prm = default_refine_visible_damped_params(),
+                                                                                std::vector<stocs_refine_visible_trace>* trace = NULL) {
+        const int n = (int)poses.size();
+        std::vector<float> P((size_t)n * 16), Q((size_t)n * 16);
+        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], poses[(size_t)i]->transform.data(), 64);
+        std::vector<stocs_refine_visible_damped_result> r((size_t)n);
+        if (refined) refined->assign((size_t)n, MatrixType());
+        if (trace) trace->assign((size_t)n * (size_t)(prm.base.max_iterations > 0 ? prm.base.max_iterations + 1 : 1), stocs_refine_visible_trace());
+        if (n > 0 && stocs_refine_poses_visible_damped(ctx_, P.data(), n, &prm, Q.data(), r.data(), trace ? trace->data() : NULL) != STOCS_OK) {
+            *log_ << "refine_poses_visible_damped failed: " << stocs_last_error() << std::endl;
+            r.clear();
+            if (refined) refined->clear();
+            if (trace) trace->clear();
+            return r;
+        }
+        for (int i = 0; refined && i < n; ++i) std::memcpy((*refined)[(size_t)i].data(), &Q[(size_t)i * 16], 64);
+        return r;
+    }
+
     // Multi-instance selection (stocs_select_instances; no reference counterpart): which of the camera-frame hypotheses (the
     // hypotheses of run_trials, refined or not) are distinct instances of the object and which are one instance found twice.  Walked
     // best first, a hypothesis is kept only if enough of the scene points it explains are explained by none kept before it.  One record

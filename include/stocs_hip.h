@@ -1266,9 +1266,11 @@ int stocs_render_mesh_last_device_ms(const stocs_ctx* ctx, float* key_ms, float*
  * accumulation and the solve of the last iteration of the last chunk of the last call; -1 otherwise.
  * Known limits: same-pixel association has no pull from frame pixels outside the rendered silhouette, so a pose that is off by more
  * than max_distance along the rays, or by more than the object's width across them, does not come back; the step of 6 is undamped and
- * its rotation is about the camera's origin: where the visible surface constrains a motion weakly (a solid of revolution) it can be large
- * and leave the pose worse than it came (measured: DESIGN.md 7.19); no trimming by rank; the float pose is not re-orthonormalised
- * between iterations; not part of trial batches or the tracker. ---- */
+ * its rotation is about the camera's origin: where the visible surface constrains a motion weakly (a solid of revolution, the Cm solid
+ * of this project's benchmarks) it can be large and leave the pose worse than it came (measured: DESIGN.md 7.19).  For such a solid use
+ * stocs_refine_poses_visible_damped below: the same evaluation, a damped and bounded step about a point of the object that is taken
+ * only when it lowers the cost.  No trimming by rank; the float pose is not re-orthonormalised between iterations;
+ * not part of trial batches or the tracker. ---- */
 typedef struct stocs_refine_visible_params {
     int32_t max_iterations;     /* >= 0 (default 5)                                            */
     float   max_distance;       /* m, > 0 finite (default 0.02)                                */
@@ -1289,6 +1291,69 @@ int stocs_refine_poses_visible(stocs_ctx* ctx, const float* pose16_camera, int n
 int stocs_refine_visible_detail(stocs_ctx* ctx, const float* pose16_camera /* one */, const stocs_refine_visible_params* p,
                                 uint64_t* keys /* H*W or NULL */, uint8_t* state /* H*W or NULL */, double* sums29);
 int stocs_refine_visible_last_device_ms(const stocs_ctx* ctx, float* render_ms, float* accumulate_ms, float* solve_ms);
+
+/* ---- damped refinement on the visible surface: Levenberg-Marquardt steps on the evaluation of stocs_refine_poses_visible, accepted or
+ * rejected on the device, bounded, and applied about a point of the object (no reference counterpart).  csrc/refine_visible.hip, restated
+ * in numpy in tests/refine_visible_damped_ref.py.  The plain form, its kernels and its results are what they were.
+ * An evaluation is exactly one evaluation of the plain contract above: the render, steps 1-5, the 29 sums S and the five counts, by the
+ * same kernels on a float pose.  With K = base.max_iterations a call makes K + 1 evaluations per pose, e = 0 .. K; K = 0 makes one, and
+ * then the pose comes back bit for bit with the plain form's record.  Everything below is in double, from the float pose and the sums.
+ *   Cost.  C = (S[28] + (double)max_d2 too_far) / (counted + too_far), max_d2 the float product max_distance * max_distance of step 2;
+ *     C = +inf when counted < 6.  A truncated quadratic over the silhouette pixels with a measurement: a pose that merely sheds pixels
+ *     past max_distance does not look better for it.
+ *   e = 0.  The start is accepted: the accepted state is the pose Pa, its sums Sa and counts, its cost Ca; lambda = lambda0.  With K > 0,
+ *     counted < 6 freezes the pose as in the plain form (frozen = 1, the pose as it came).
+ *   e > 0, the trial Pt.  Accepted if and only if C < Ca: then the accepted state is the trial's, lambda = max(lambda / lambda_down, 1e-9)
+ *     and iterations grows by 1.  Otherwise lambda = min(lambda lambda_up, 1e9) and rejected grows by 1.  A trial that shows fewer than 6
+ *     counted pixels (or nothing) has C = +inf and is rejected.
+ *   After evaluation e < K, the next trial from (Pa, Sa, lambda):
+ *     1. the pivot c = 0 (pivot 0), or c_r = ((Pa_r0 m_0 + Pa_r1 m_1) + Pa_r2 m_2) + Pa_r3 with m = pivot_model (pivot 1).
+ *     2. the sums about c, without a second accumulation: the row about c is a' = ((q - c) x n, n) = T a with T = [[I, -[c]x], [0, I]],
+ *        so M' = (T M) T^T and v' = T v from the 21 + 6 sums.
+ *     3. M'' = M' with every diagonal entry multiplied by (1 + lambda).
+ *     4. x = the 6x6 elimination of step 6 above on (M'', v'); a pivot below 1e-300 freezes the pose at Pa.
+ *     5. s = min(1, max_step_rotation / |x[0..2]|, max_step_translation / |x[3..5]|), |.| = sqrt(a a + (b b + c c)); a zero norm sets no
+ *        bound; x <- s x.
+ *     6. Delta = (R(x), t) with R = Rz Ry Rx as above and t_r = (x[3 + r] + c_r) - ((R_r0 c_0 + R_r1 c_1) + R_r2 c_2): the rotation is
+ *        about c.
+ *     7. Pt = (float)(Delta Pa), composed and rounded as in step 6 above.
+ *   Returned: Pa; base describes Pa's evaluation (iterations: the accepted updates), evaluations and rejected count what was done, cost
+ *   and lambda are (float) of Ca and of the last lambda.  The cost of the returned pose is never above that of the pose that came in;
+ *   evaluations are deterministic, so two K = 0 calls show it exactly.
+ * As in the plain form: a non-finite or all-zero pose comes back bit for bit with a zero record; the order of the refusals, the new
+ * parameters checked behind the base ones; one grow-only workspace, one read-back and one synchronisation per call; chunks of key
+ * buffers and STOCS_REFINE_VISIBLE_CHUNK; a pose's result is bitwise independent of batch, position and chunk.
+ * trace (n (K + 1) rows, row h (K + 1) + e, or NULL): the pose that was evaluated, its cost, whether it was accepted (1 at e = 0), the
+ * lambda after the decision, state 1: evaluated, 3: evaluated and the pose froze behind it; a row that was not evaluated (an invalid or
+ * frozen pose) is zero.
+ * The kernel: refine_visible_damped_solve_kernel, one wavefront per pose, the fixed-order reduction of the plain solve, then lane 0; the
+ * accepted pose, sums, cost and lambda of a pose live in the workspace between evaluations.
+ * Measured: DESIGN.md 7.21 and profiles/refine_visible_damped.md.  Not here: re-orthonormalising the pose, trimming by rank, use inside
+ * trial batches or the tracker. ---- */
+typedef struct stocs_refine_visible_damped_params {
+    stocs_refine_visible_params base;   /* as above; max_iterations = K                                        */
+    float   lambda0;                    /* >= 0 finite (default 1)                                             */
+    float   lambda_down, lambda_up;     /* >= 1 finite (defaults 4, 16)                                        */
+    float   max_step_rotation;          /* rad, > 0 (default 5 degrees); +inf: no bound                        */
+    float   max_step_translation;       /* m, > 0 (default 0.01); +inf: no bound                               */
+    int32_t pivot;                      /* 0: the camera's origin (the plain form's); 1: pivot_model (default) */
+    float   pivot_model[3];             /* a point in the MODEL frame, finite (default 0, 0, 0)                */
+} stocs_refine_visible_damped_params;   /* 52 bytes */
+typedef struct stocs_refine_visible_damped_result {
+    stocs_refine_visible_result base;   /* the evaluation of the RETURNED pose; iterations = accepted updates  */
+    int32_t evaluations, rejected;
+    float   cost, lambda;               /* (float) of the accepted cost and of the last lambda                 */
+} stocs_refine_visible_damped_result;   /* 56 bytes */
+typedef struct stocs_refine_visible_trace {
+    float   pose[16];
+    double  cost, lambda;
+    int32_t accepted, state;
+} stocs_refine_visible_trace;           /* 88 bytes */
+void stocs_default_refine_visible_damped_params(stocs_refine_visible_damped_params* p);
+int stocs_check_refine_visible_damped_params(const stocs_refine_visible_damped_params* p);   /* host only */
+int stocs_refine_poses_visible_damped(stocs_ctx* ctx, const float* pose16_camera, int n, const stocs_refine_visible_damped_params* p,
+                                      float* pose16_out, stocs_refine_visible_damped_result* out,
+                                      stocs_refine_visible_trace* trace /* n * (K + 1) or NULL */);
 
 /* ---- mesh models: a triangle mesh sampled into the oriented model cloud the search needs (no reference counterpart).  Stand-alone like
  * stocs_preprocess_model: no context; the same cached per-thread workspace and pinned block (stocs_trim gives them back; a second call of

@@ -78,6 +78,10 @@
 // written again from the result; K = 0 scores the pose and leaves the file.  One "refine-visible <object>: iterations=.. frozen=..
 // present=.. no_depth=.. off_class=.. too_far=.. grazing=.. counted=.. rms=.. mesh=<triangles>" line and the refined "pose:" line; with
 // --gt a "refine-visible <object> before: add=.. adds=.." and an "after" line (stocs_pose_errors), and the gt lines score the refined file.
+// --damped [lambda0[,rot_deg[,trans_m]]] (with --refine-visible): the damped form (stocs_refine_poses_visible_damped: K + 1 evaluations, steps
+// bounded by rot_deg degrees and trans_m metres, taken only when they lower the cost, about the mean of the mesh's vertices; the library's
+// defaults unless given); the line then reads "refine-visible <object>: damped iterations=.. rejected=.. evaluations=.. cost=.. lambda=..
+// frozen=.. present=.. .. mesh=<triangles>" and describes the pose that is written.
 // --masks (with --instances M, a scene directory): the selected instances, in rank order, rendered together against the frame's depth image
 // and class-probability map (stocs_explain_poses); one "mask r: footprint .. visible .. hidden .. agree .. in_front .. behind .. no_depth ..
 // on_mask .." line per instance, and the label image to labels_<object>.pgm next to <out>: binary 16-bit PGM (P5, maxval 65535, most
@@ -367,7 +371,7 @@ static bool read_pose_file(const std::string& path, MatrixType& m) {
 // --gt: the pose this run wrote to out_path, read back with the reader the ground truth goes through (what is scored is what a reader of
 // the file gets), against the ground truth: ADD, ADD-S, their maxima, the model's diameter (stocs_pose_errors, stocs_model_diameter); with
 // --trials N also the share of the trials' winners (full precision, a trial without a pose left out) within 0.1 diameter
-struct RefineVisibleOptions { bool on; int iterations; float distance, view_cos; int mesh_triangles; };   // --refine-visible K[,dist[,cos]]; a value < 0 leaves the library's default
+struct RefineVisibleOptions { bool on; int iterations; float distance, view_cos; int mesh_triangles; bool damped; float lambda0, rot_deg, trans_m, pivot[3]; };   // --refine-visible K[,dist[,cos]]; a value < 0 leaves the library's default
 struct VsdOptions { bool on; float delta, surfel_radius; int mesh_triangles; };   // --vsd; a value <= 0 leaves the library's default; mesh_triangles > 0: --mesh
 
 // the ten errors of a VSD record as " e0=... .. e9=..." at b + at; returns the new end
@@ -378,6 +382,19 @@ static int print_vsd_errors(char* b, size_t cap, int at, const stocs_vsd_record&
 
 // --refine-visible: the pose this run wrote to out_path, read back as --gt reads it, refined on the mesh against the frame; out_path is
 // written again in the format the search writes it
+// the parameters of --refine-visible .. --damped ..: the library's defaults unless given
+static stocs_refine_visible_damped_params damped_params_of(const RefineVisibleOptions& rv) {
+    stocs_refine_visible_damped_params prm = stocs::stocs_estimator::default_refine_visible_damped_params();
+    prm.base.max_iterations = rv.iterations;
+    if (rv.distance >= 0.0f) prm.base.max_distance = rv.distance;
+    if (rv.view_cos >= 0.0f) prm.base.min_view_cos = rv.view_cos;
+    if (rv.lambda0 >= 0.0f) prm.lambda0 = rv.lambda0;
+    if (rv.rot_deg >= 0.0f) prm.max_step_rotation = (float)((double)rv.rot_deg * 3.14159265358979323846 / 180.0);
+    if (rv.trans_m >= 0.0f) prm.max_step_translation = rv.trans_m;
+    for (int k = 0; k < 3; ++k) prm.pivot_model[k] = rv.pivot[k];
+    return prm;
+}
+
 static int run_refine_visible(stocs::stocs_estimator& est, const RefineVisibleOptions& rv, const std::string& out_path, const std::string& object, const std::string& gt_path) {
     MatrixType p, g;
     if (!read_pose_file(out_path, p)) { std::cout << "refine-visible " << object << ": no pose" << std::endl; return 0; }
@@ -387,11 +404,21 @@ static int run_refine_visible(stocs::stocs_estimator& est, const RefineVisibleOp
     if (rv.view_cos >= 0.0f) prm.min_view_cos = rv.view_cos;
     PoseCandidate e(p, 0.0f, -1.0f);
     std::vector<MatrixType> refined;
-    const std::vector<stocs_refine_visible_result> r = est.refine_poses_visible(std::vector<PoseCandidate*>(1, &e), &refined, prm);
-    if (r.size() != 1 || refined.size() != 1) { std::cerr << "refine-visible failed: " << stocs_last_error() << std::endl; return 2; }
-    char b[512];
-    snprintf(b, sizeof(b), "refine-visible %s: iterations=%d frozen=%d present=%d no_depth=%d off_class=%d too_far=%d grazing=%d counted=%d rms=%.9g mesh=%d", object.c_str(),
-             r[0].iterations, r[0].frozen, r[0].present, r[0].no_depth, r[0].off_class, r[0].too_far, r[0].grazing, r[0].counted, (double)r[0].rms, rv.mesh_triangles);
+    std::vector<stocs_refine_visible_result> r;
+    char b[640];
+    if (rv.damped) {
+        const std::vector<stocs_refine_visible_damped_result> d = est.refine_poses_visible_damped(std::vector<PoseCandidate*>(1, &e), &refined, damped_params_of(rv));
+        if (d.size() != 1 || refined.size() != 1) { std::cerr << "refine-visible failed: " << stocs_last_error() << std::endl; return 2; }
+        r.push_back(d[0].base);
+        snprintf(b, sizeof(b), "refine-visible %s: damped iterations=%d rejected=%d evaluations=%d cost=%.9g lambda=%.9g frozen=%d present=%d no_depth=%d off_class=%d too_far=%d "
+                 "grazing=%d counted=%d rms=%.9g mesh=%d", object.c_str(), r[0].iterations, d[0].rejected, d[0].evaluations, (double)d[0].cost, (double)d[0].lambda, r[0].frozen,
+                 r[0].present, r[0].no_depth, r[0].off_class, r[0].too_far, r[0].grazing, r[0].counted, (double)r[0].rms, rv.mesh_triangles);
+    } else {
+        r = est.refine_poses_visible(std::vector<PoseCandidate*>(1, &e), &refined, prm);
+        if (r.size() != 1 || refined.size() != 1) { std::cerr << "refine-visible failed: " << stocs_last_error() << std::endl; return 2; }
+        snprintf(b, sizeof(b), "refine-visible %s: iterations=%d frozen=%d present=%d no_depth=%d off_class=%d too_far=%d grazing=%d counted=%d rms=%.9g mesh=%d", object.c_str(),
+                 r[0].iterations, r[0].frozen, r[0].present, r[0].no_depth, r[0].off_class, r[0].too_far, r[0].grazing, r[0].counted, (double)r[0].rms, rv.mesh_triangles);
+    }
     std::cout << b << std::endl;
     if (r[0].iterations > 0) {
         std::ofstream f(out_path, std::ofstream::out);
@@ -720,7 +747,8 @@ int main(int argc, char** argv) {
     bool do_instances = false, do_masks = false, have_trim = false, have_gate = false;
     SceneSelectOptions scene_opt = {false, false, 0};
     VsdOptions vsd_opt = {false, 0.0f, 0.0f, 0};
-    RefineVisibleOptions rv_opt = {false, 0, -1.0f, -1.0f, 0};
+    RefineVisibleOptions rv_opt = {false, 0, -1.0f, -1.0f, 0, false, -1.0f, -1.0f, -1.0f, {0.0f, 0.0f, 0.0f}};
+    bool damped_bad = false;
     std::string mesh_path, surface = "points";
     bool have_vsd_delta = false, have_surfel_radius = false;
     stocs_instance_params inst_prm = stocs::stocs_estimator::default_instance_params();
@@ -730,6 +758,16 @@ int main(int argc, char** argv) {
         if (std::string(argv[i]) == "--masks") { do_masks = true; --i; continue; }
         if (std::string(argv[i]) == "--scene-select") { scene_opt.on = true; --i; continue; }
         if (std::string(argv[i]) == "--vsd") { vsd_opt.on = true; --i; continue; }   // with --gt: the visible-surface discrepancy too
+        if (std::string(argv[i]) == "--damped") {   // [lambda0[,rot_deg[,trans_m]]]: the value may be left out
+            rv_opt.damped = true;
+            if (i + 1 >= argc || std::string(argv[i + 1]).compare(0, 2, "--") == 0) { --i; continue; }
+            const std::string dv = argv[i + 1];
+            char tail = 0;
+            const int got = sscanf(dv.c_str(), "%f,%f,%f%c", &rv_opt.lambda0, &rv_opt.rot_deg, &rv_opt.trans_m, &tail);
+            if (got < 1 || got > 3 || (size_t)std::count(dv.begin(), dv.end(), ',') + 1 != (size_t)got) damped_bad = true;
+            if (!(rv_opt.lambda0 >= 0.0f) || (got >= 2 && !(rv_opt.rot_deg > 0.0f)) || (got == 3 && !(rv_opt.trans_m > 0.0f))) damped_bad = true;
+            continue;
+        }
         if (i + 1 >= argc) break;
         const std::string k = argv[i], v = argv[i + 1];
         if (k == "--edge") edge_path = v;
@@ -821,6 +859,16 @@ int main(int argc, char** argv) {
         if (vsd_opt.on) vsd_opt.mesh_triangles = nt;
         if (surface_mesh) g_mask_mesh_triangles = nt;
         if (rv_opt.on) rv_opt.mesh_triangles = nt;
+        double mean[3] = {0.0, 0.0, 0.0};   // --damped turns about the mean of the vertices
+        for (int i = 0; i < nv; ++i) for (int k = 0; k < 3; ++k) mean[k] += (double)mesh_v[(size_t)i * 3 + (size_t)k];
+        for (int k = 0; k < 3; ++k) rv_opt.pivot[k] = (float)(mean[k] / (double)nv);
+    }
+    if (rv_opt.damped) {   // refused before any search
+        const stocs_refine_visible_damped_params dp = damped_params_of(rv_opt);
+        if (!rv_opt.on || damped_bad || (rv_opt.iterations >= 0 && !mesh_path.empty() && stocs_check_refine_visible_damped_params(&dp) != STOCS_OK)) {
+            std::cerr << "--damped [lambda0[,rot_deg[,trans_m]]] needs --refine-visible, lambda0 >= 0, rot_deg > 0 and trans_m > 0" << std::endl;
+            return -1;
+        }
     }
     if (rv_opt.on) {   // refused before any search
         stocs_refine_visible_params rp = stocs::stocs_estimator::default_refine_visible_params();

@@ -137,6 +137,19 @@ class RefineVisibleResult(C.Structure):
                 ("counted", C.c_int32), ("iterations", C.c_int32), ("frozen", C.c_int32), ("rms", C.c_float), ("reserved", C.c_int32)]
 
 
+class RefineVisibleDampedParams(C.Structure):
+    _fields_ = [("base", RefineVisibleParams), ("lambda0", C.c_float), ("lambda_down", C.c_float), ("lambda_up", C.c_float),
+                ("max_step_rotation", C.c_float), ("max_step_translation", C.c_float), ("pivot", C.c_int32), ("pivot_model", C.c_float * 3)]
+
+
+class RefineVisibleDampedResult(C.Structure):
+    _fields_ = [("base", RefineVisibleResult), ("evaluations", C.c_int32), ("rejected", C.c_int32), ("cost", C.c_float), ("lambda_", C.c_float)]
+
+
+class RefineVisibleTrace(C.Structure):
+    _fields_ = [("pose", C.c_float * 16), ("cost", C.c_double), ("lambda_", C.c_double), ("accepted", C.c_int32), ("state", C.c_int32)]
+
+
 class SceneRecord(C.Structure):
     _fields_ = [("footprint", C.c_int32), ("no_depth", C.c_int32), ("agree", C.c_int32), ("in_front", C.c_int32), ("behind", C.c_int32),
                 ("on_mask", C.c_int32), ("claimed", C.c_int32)]
@@ -278,6 +291,10 @@ SIGNATURES = {
     "stocs_refine_poses_visible": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(RefineVisibleParams), _fp, C.POINTER(RefineVisibleResult)]),
     "stocs_refine_visible_detail": (C.c_int, [_vp, _fp, C.POINTER(RefineVisibleParams), C.POINTER(C.c_uint64), _u8p, C.POINTER(C.c_double)]),
     "stocs_refine_visible_last_device_ms": (C.c_int, [_vp, C.POINTER(C.c_float), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "stocs_default_refine_visible_damped_params": (None, [C.POINTER(RefineVisibleDampedParams)]),
+    "stocs_check_refine_visible_damped_params": (C.c_int, [C.POINTER(RefineVisibleDampedParams)]),
+    "stocs_refine_poses_visible_damped": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(RefineVisibleDampedParams), _fp, C.POINTER(RefineVisibleDampedResult),
+                                                    C.POINTER(RefineVisibleTrace)]),
     "stocs_mesh_sample_counts": (C.c_int, [_fp, C.c_int, _ip, C.c_int, C.c_float, C.c_uint64, C.c_int, _ip, C.POINTER(C.c_double), _i64p, _intp]),
     "stocs_mesh_sample": (C.c_int, [_fp, C.c_int, _ip, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, _fp, _fp, _ip, C.c_int, _intp]),
     "stocs_preprocess_model_mesh": (C.c_int, [_fp, C.c_int, _ip, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_float, C.c_float, C.c_int, _fp, _fp, C.c_int, _intp]),

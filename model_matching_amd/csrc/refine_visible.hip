@@ -21,9 +21,15 @@
 // A hypothesis's walk depends on its rectangle and on G alone, so its result is bitwise independent of the batch, of its position in it
 // and of the chunk.  The detail form (a compile-time argument, as in refine.hip) stops after the sums, writes the per-pixel state and
 // leaves the keys in place for the read-back.
-// Known limits: the step is an undamped Gauss-Newton step whose rotation is about the camera's origin: on a solid whose visible surface
+// The damped form (stocs_refine_poses_visible_damped; tests/refine_visible_damped_ref.py) runs the same render and the same
+// accumulation K + 1 times and puts another kernel in the solve's place:
+//   damped solve  one wavefront per hypothesis: the solve's reduction (rv_reduce_partials), then lane 0 in double: the cost of the
+//               evaluation, accept or reject against the pose's accepted state (pose, 29 sums, cost, lambda, kept in the workspace between
+//               evaluations), and from the accepted state the sums moved to a pivot on the object, the damped 6x6 solve, the bound and the
+//               next trial pose, written into the slot the next render reads; one trace row per evaluation when asked for.
+// Known limits: the plain step is an undamped Gauss-Newton step whose rotation is about the camera's origin: on a solid whose visible surface
 // constrains a motion weakly it can be large and leave the pose worse (measured on the Cm solid; the restatement does the
-// same, bit for bit); a frozen hypothesis is still rendered and walked in the remaining iterations of its chunk (nothing reads the result);
+// same, bit for bit; the damped form is the remedy); a frozen hypothesis is still rendered and walked in the remaining iterations of its chunk (nothing reads the result);
 // the rasteriser's limits (no near-plane clipping; one pose of a 12-triangle model renders on one compute unit) are this file's too.
 #include <math.h>
 #include <stdlib.h>
@@ -40,9 +46,10 @@ static const unsigned long long RV_EMPTY = 0xFFFFFFFFFFFFFFFFull;
 
 struct RefineVisibleState {
     static const StateOwner OWNER = OWN_REFINE_VISIBLE;
-    ~RefineVisibleState() { work.free(); detail.free(); }
+    ~RefineVisibleState() { work.free(); detail.free(); damped.free(); }
     DevBlock work;     // poses | records | frozen flags | rectangles | partial sums | partial counts | one chunk of key buffers, grow-only
     DevBlock detail;   // stocs_refine_visible_detail: state | sums, grow-only
+    DevBlock damped;   // stocs_refine_poses_visible_damped: accepted poses | records | trace | accepted sums, cost, lambda | done flags, grow-only
     float last_ms[3] = {-1.0f, -1.0f, -1.0f};  // "device_clock": HIP-event time of the last call's last render, accumulation and solve (-1: not taken)
 };
 
@@ -170,18 +177,12 @@ __global__ __launch_bounds__(256) void refine_visible_accumulate_kernel(const fl
     if (tid < RV_COUNTS) pcount[slot * RV_COUNTS + tid] = ((cnt[0][tid] + cnt[1][tid]) + cnt[2][tid]) + cnt[3][tid];
 }
 
-// One wavefront per hypothesis of the chunk.  update == 0 (max_iterations == 0): the record alone.  Detail::on: the sums go to
-// det.sums29 and nothing else happens.
-template <class Detail>
-__global__ __launch_bounds__(64) void refine_visible_solve_kernel(float* __restrict__ poses, const double* __restrict__ partial, const int32_t* __restrict__ pcount, int groups,
-                                                                  int update, int32_t* __restrict__ frozen, stocs_refine_visible_result* __restrict__ rec, Detail det) {
-    const int h = (int)blockIdx.x, lane = (int)threadIdx.x;
-    if constexpr (!Detail::on) { if (frozen[h]) return; }   // the same address in every lane: the whole wavefront
-    // lane l sums partials l, l + 64, ... in order, then a butterfly over the wavefront: a fixed order, whatever the batch
+// The fixed-order reduction of a pose's G partials S (sums) and N (counts) by one wavefront: lane l sums partials l, l + 64, ... in order,
+// then a butterfly over the wavefront; every lane ends with the totals.  The order depends on G alone, whatever the batch.
+__device__ __forceinline__ void rv_reduce_partials(const double* __restrict__ partial, const int32_t* __restrict__ pcount, int h, int groups, int lane, double (&acc)[RV_SUMS],
+                                                   int (&n)[RV_COUNTS]) {
     const double* S = partial + (size_t)h * (size_t)groups * RV_SUMS;
     const int32_t* N = pcount + (size_t)h * (size_t)groups * RV_COUNTS;
-    double acc[RV_SUMS];
-    int n[RV_COUNTS];
 #pragma unroll
     for (int k = 0; k < RV_SUMS; ++k) acc[k] = 0.0;
 #pragma unroll
@@ -198,6 +199,18 @@ __global__ __launch_bounds__(64) void refine_visible_solve_kernel(float* __restr
 #pragma unroll
         for (int k = 0; k < RV_COUNTS; ++k) n[k] += __shfl_xor(n[k], o, 64);
     }
+}
+
+// One wavefront per hypothesis of the chunk.  update == 0 (max_iterations == 0): the record alone.  Detail::on: the sums go to
+// det.sums29 and nothing else happens.
+template <class Detail>
+__global__ __launch_bounds__(64) void refine_visible_solve_kernel(float* __restrict__ poses, const double* __restrict__ partial, const int32_t* __restrict__ pcount, int groups,
+                                                                  int update, int32_t* __restrict__ frozen, stocs_refine_visible_result* __restrict__ rec, Detail det) {
+    const int h = (int)blockIdx.x, lane = (int)threadIdx.x;
+    if constexpr (!Detail::on) { if (frozen[h]) return; }   // the same address in every lane: the whole wavefront
+    double acc[RV_SUMS];
+    int n[RV_COUNTS];
+    rv_reduce_partials(partial, pcount, h, groups, lane, acc, n);
     if (lane) return;
     if constexpr (Detail::on) {
 #pragma unroll
@@ -236,11 +249,160 @@ __global__ __launch_bounds__(64) void refine_visible_solve_kernel(float* __restr
     R->iterations += 1;
 }
 
+// ---- the damped form (stocs_refine_poses_visible_damped): the same render and accumulation, another solve step
+struct RvDampedArgs {
+    double max_d2;                 // (double) of the float product the accumulation compares with
+    double lambda0, down, up;
+    double max_rot, max_trans;     // +inf: no bound
+    double pm[3];                  // pivot_model
+    int pivot, K;
+};
+// what a pose keeps between evaluations beside its accepted pose and its record: the accepted sums, the accepted cost, lambda
+struct RvDampedState { double S[RV_SUMS]; double cost, lambda; };
+
+// One wavefront per hypothesis of the chunk, after evaluation e of K + 1: the reduction of refine_visible_solve_kernel, the cost, the
+// decision against the accepted state, and for e < K the next trial from the accepted state (steps 1-7 of the contract), written into the
+// pose slot the next render reads.  Everything behind the reduction is lane 0's, in double.
+__global__ __launch_bounds__(64) void refine_visible_damped_solve_kernel(float* __restrict__ poses, const double* __restrict__ partial, const int32_t* __restrict__ pcount,
+                                                                         int groups, int e, RvDampedArgs da, float* __restrict__ accepted, RvDampedState* __restrict__ state,
+                                                                         int32_t* __restrict__ done, stocs_refine_visible_damped_result* __restrict__ rec,
+                                                                         stocs_refine_visible_trace* __restrict__ trace) {
+    const int h = (int)blockIdx.x, lane = (int)threadIdx.x;
+    if (done[h]) return;   // the same address in every lane: the whole wavefront
+    double acc[RV_SUMS];
+    int n[RV_COUNTS];
+    rv_reduce_partials(partial, pcount, h, groups, lane, acc, n);
+    if (lane) return;
+    float* Ph = poses + (size_t)h * 16;
+    float* Pah = accepted + (size_t)h * 16;
+    float P[16];
+    bool nonzero = false;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { P[i] = Ph[i]; nonzero = nonzero || P[i] != 0.0f; }
+    stocs_refine_visible_damped_result* R = rec + h;   // zeroed in front of the first evaluation
+    RvDampedState* St = state + h;
+    if (e == 0 && (!pose_finite(P) || !nonzero)) { done[h] = 1; return; }   // renders nothing: the zero record, the pose as it came
+    const int count = (int)acc[27];
+    const double C = count < 6 ? (double)INFINITY : (acc[28] + da.max_d2 * (double)n[RV_TOO_FAR]) / (double)(count + n[RV_TOO_FAR]);
+    double lambda = e == 0 ? da.lambda0 : St->lambda;
+    const bool ok = e == 0 || C < St->cost;
+    double Sa[27];   // what the next trial is made from: the 21 + 6 accepted sums
+    if (ok) {
+        R->base.present = n[RV_PRESENT]; R->base.no_depth = n[RV_NO_DEPTH]; R->base.off_class = n[RV_OFF_CLASS]; R->base.too_far = n[RV_TOO_FAR];
+        R->base.grazing = n[RV_GRAZING]; R->base.counted = count;
+        R->base.rms = count > 0 ? sqrtf((float)(acc[28] / (double)count)) : 0.0f;
+        R->cost = (float)C;
+#pragma unroll
+        for (int k = 0; k < RV_SUMS; ++k) St->S[k] = acc[k];
+#pragma unroll
+        for (int k = 0; k < 27; ++k) Sa[k] = acc[k];
+        St->cost = C;
+        if (e > 0) {
+            lambda = fmax(lambda / da.down, 1e-9);
+            R->base.iterations += 1;
+#pragma unroll
+            for (int i = 0; i < 16; ++i) Pah[i] = P[i];
+        }
+    } else {
+        lambda = fmin(lambda * da.up, 1e9);
+        R->rejected += 1;
+#pragma unroll
+        for (int k = 0; k < 27; ++k) Sa[k] = St->S[k];
+#pragma unroll
+        for (int i = 0; i < 16; ++i) P[i] = Pah[i];   // from here on P is the accepted pose
+    }
+    St->lambda = lambda;
+    R->lambda = (float)lambda;
+    R->evaluations += 1;
+    stocs_refine_visible_trace* Tr = trace ? trace + (size_t)h * (size_t)(da.K + 1) + (size_t)e : NULL;
+    if (Tr) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) Tr->pose[i] = Ph[i];
+        Tr->cost = C; Tr->lambda = lambda; Tr->accepted = ok ? 1 : 0; Tr->state = 1;
+    }
+    if (e == da.K) return;
+    bool freeze = e == 0 && count < 6;   // not enough pixels at the start: the pose as it came
+    double x[6];
+    double c0 = 0.0, c1 = 0.0, c2 = 0.0;
+    if (!freeze) {
+        // 1. the pivot in the camera frame
+        if (da.pivot) {
+            c0 = (((double)P[0] * da.pm[0] + (double)P[4] * da.pm[1]) + (double)P[8] * da.pm[2]) + (double)P[12];
+            c1 = (((double)P[1] * da.pm[0] + (double)P[5] * da.pm[1]) + (double)P[9] * da.pm[2]) + (double)P[13];
+            c2 = (((double)P[2] * da.pm[0] + (double)P[6] * da.pm[1]) + (double)P[10] * da.pm[2]) + (double)P[14];
+        }
+        // 2. M' = T M T^T, v' = T v with T = [[I, -[c]x], [0, I]]: rows 0..2 of T M, then columns 0..2 of (T M) T^T
+        const double Cx[3][3] = {{0.0, -c2, c1}, {c2, 0.0, -c0}, {-c1, c0, 0.0}};
+        double M[6][6], A[6][6], b[6];
+        int k = 0;
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int q = r; q < 6; ++q) { M[r][q] = Sa[k]; M[q][r] = Sa[k]; k++; }
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+#pragma unroll
+            for (int q = 0; q < 6; ++q) M[r][q] = M[r][q] - ((Cx[r][0] * M[3][q] + Cx[r][1] * M[4][q]) + Cx[r][2] * M[5][q]);
+            b[r] = Sa[21 + r] - ((Cx[r][0] * Sa[24] + Cx[r][1] * Sa[25]) + Cx[r][2] * Sa[26]);
+            b[3 + r] = Sa[24 + r];
+        }
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+#pragma unroll
+            for (int q = 0; q < 6; ++q)
+                A[r][q] = q < 3 ? M[r][q] - ((M[r][3] * Cx[q][0] + M[r][4] * Cx[q][1]) + M[r][5] * Cx[q][2]) : M[r][q];
+        // 3. damping, 4. the solve
+#pragma unroll
+        for (int r = 0; r < 6; ++r) A[r][r] = A[r][r] * (1.0 + lambda);
+        freeze = !solve6(A, b, x);
+    }
+    if (freeze) {
+        done[h] = 1; R->base.frozen = 1;
+        if (Tr) Tr->state = 3;
+        return;
+    }
+    // 5. the bound
+    double s = 1.0;
+    const double nr = sqrt(x[0] * x[0] + (x[1] * x[1] + x[2] * x[2])), nt = sqrt(x[3] * x[3] + (x[4] * x[4] + x[5] * x[5]));
+    if (nr > 0.0 && da.max_rot / nr < s) s = da.max_rot / nr;
+    if (nt > 0.0 && da.max_trans / nt < s) s = da.max_trans / nt;
+#pragma unroll
+    for (int i = 0; i < 6; ++i) x[i] = s * x[i];
+    // 6. the motion about c, 7. the next trial (float)(Delta Pa)
+    const double ca = cos(x[0]), sa = sin(x[0]), cb = cos(x[1]), sb = sin(x[1]), cg = cos(x[2]), sg = sin(x[2]);
+    const double Rm[3][3] = {{cg * cb, cg * sb * sa - sg * ca, cg * sb * ca + sg * sa},
+                             {sg * cb, sg * sb * sa + cg * ca, sg * sb * ca - cg * sa},
+                             {-sb, cb * sa, cb * ca}};
+    const double cc[3] = {c0, c1, c2};
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double t = (x[3 + r] + cc[r]) - ((Rm[r][0] * c0 + Rm[r][1] * c1) + Rm[r][2] * c2);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            double v = (Rm[r][0] * (double)P[4 * q] + Rm[r][1] * (double)P[4 * q + 1]) + Rm[r][2] * (double)P[4 * q + 2];
+            if (q == 3) v += t;
+            Ph[4 * q + r] = (float)v;   // the slot's last row is the start's, as every accepted pose's is
+        }
+    }
+}
+
 static const char* params_error(const stocs_refine_visible_params* p) {
     if (p->max_iterations < 0) return "max_iterations must be >= 0";
     if (!(p->max_distance > 0.0f) || !isfinite(p->max_distance)) return "max_distance must be positive and finite";
     if (!(p->min_view_cos >= 0.0f && p->min_view_cos < 1.0f)) return "min_view_cos must be in [0, 1)";
     if (!isfinite(p->class_threshold)) return "class_threshold is not finite";
+    return NULL;
+}
+
+static const char* damped_params_error(const stocs_refine_visible_damped_params* p) {
+    if (const char* why = params_error(&p->base)) return why;
+    if (!(p->lambda0 >= 0.0f) || !isfinite(p->lambda0)) return "lambda0 must be >= 0 and finite";
+    if (!(p->lambda_down >= 1.0f) || !isfinite(p->lambda_down)) return "lambda_down must be >= 1 and finite";
+    if (!(p->lambda_up >= 1.0f) || !isfinite(p->lambda_up)) return "lambda_up must be >= 1 and finite";
+    if (!(p->max_step_rotation > 0.0f)) return "max_step_rotation must be positive (+inf: no bound)";
+    if (!(p->max_step_translation > 0.0f)) return "max_step_translation must be positive (+inf: no bound)";
+    if (p->pivot != 0 && p->pivot != 1) return "pivot must be 0 (the camera's origin) or 1 (pivot_model)";
+    if (!isfinite(p->pivot_model[0]) || !isfinite(p->pivot_model[1]) || !isfinite(p->pivot_model[2])) return "pivot_model is not finite";
     return NULL;
 }
 
@@ -386,6 +548,94 @@ extern "C" int stocs_refine_poses_visible(stocs_ctx* c, const float* poses, int 
     }
     memcpy(pose16_out, hback, (size_t)n * 64);
     memcpy(out, hback + (w.o_rec - w.o_pose), (size_t)n * sizeof(stocs_refine_visible_result));
+    return STOCS_OK;
+}
+
+extern "C" void stocs_default_refine_visible_damped_params(stocs_refine_visible_damped_params* p) {
+    if (!p) return;
+    stocs_default_refine_visible_params(&p->base);
+    p->lambda0 = 1.0f; p->lambda_down = 4.0f; p->lambda_up = 16.0f;
+    p->max_step_rotation = 0.0872664626f;   // 5 degrees
+    p->max_step_translation = 0.01f;
+    p->pivot = 1;
+    p->pivot_model[0] = p->pivot_model[1] = p->pivot_model[2] = 0.0f;
+}
+
+extern "C" int stocs_check_refine_visible_damped_params(const stocs_refine_visible_damped_params* p) {
+    if (!p) { set_error("stocs_check_refine_visible_damped_params: NULL parameters"); return STOCS_ERR_INVALID; }
+    if (const char* why = damped_params_error(p)) { set_error("stocs_check_refine_visible_damped_params: %s", why); return STOCS_ERR_INVALID; }
+    return STOCS_OK;
+}
+
+// The plain call's frame with another solve step: K + 1 evaluations per chunk, the accepted pose and the record in the damped block,
+// read back with the trace behind them in one copy.
+extern "C" int stocs_refine_poses_visible_damped(stocs_ctx* c, const float* poses, int n, const stocs_refine_visible_damped_params* prm, float* pose16_out,
+                                                 stocs_refine_visible_damped_result* out, stocs_refine_visible_trace* trace) {
+    static const char* who = "stocs_refine_poses_visible_damped";
+    if (!c) { set_error("%s: NULL context", who); return STOCS_ERR_INVALID; }
+    if (n < 0) { set_error("%s: n %d < 0", who, n); return STOCS_ERR_INVALID; }
+    if (n == 0) return STOCS_OK;
+    if (!poses || !prm || !pose16_out || !out) { set_error("%s: NULL poses, parameters or results", who); return STOCS_ERR_INVALID; }
+    if (const char* why = damped_params_error(prm)) { set_error("%s: %s", who, why); return STOCS_ERR_INVALID; }
+    DepthState* F = NULL;
+    { const int rc = visible_check(who, c, &prm->base, &F); if (rc) return rc; }
+    DeviceGuard dev_guard(c->device);
+    const bool dev_clock = c->device_clock != 0;
+    const size_t npix = F->npix, chunk = visible_chunk(n, npix);
+    const int groups = refine_visible_groups(npix), K = prm->base.max_iterations;
+    VisibleWork w;
+    { const int rc = visible_work(c, n, chunk, npix, groups, &w); if (rc) return rc; }
+    RefineVisibleState* S = ctx_state<RefineVisibleState>(c);
+    const size_t rows = (size_t)n * (size_t)(K + 1);
+    Carve cv;   // what comes back lies in front: accepted poses | records | trace
+    const size_t o_acc = cv.take((size_t)n * 64), o_rec = cv.take((size_t)n * sizeof(stocs_refine_visible_damped_result));
+    const size_t o_trace = cv.take(trace ? rows * sizeof(stocs_refine_visible_trace) : 0), back_all = cv.total;
+    const size_t o_state = cv.take((size_t)n * sizeof(RvDampedState)), o_done = cv.take((size_t)n * 4);
+    { const int rc = S->damped.grow(c->stream, cv.total); if (rc) return rc; }
+    float* d_acc = Carve::at<float>(S->damped.p, o_acc);
+    stocs_refine_visible_damped_result* d_rec = Carve::at<stocs_refine_visible_damped_result>(S->damped.p, o_rec);
+    stocs_refine_visible_trace* d_trace = trace ? Carve::at<stocs_refine_visible_trace>(S->damped.p, o_trace) : NULL;
+    RvDampedState* d_state = Carve::at<RvDampedState>(S->damped.p, o_state);
+    int32_t* d_done = Carve::at<int32_t>(S->damped.p, o_done);
+    const size_t back_bytes = trace ? o_trace + rows * sizeof(stocs_refine_visible_trace) : o_rec + (size_t)n * sizeof(stocs_refine_visible_damped_result);
+    char* hin; char* hback;
+    { const int rc = pinned_for(c, (size_t)n * 64, back_bytes, &hin, &hback); if (rc) return rc; }
+    memcpy(hin, poses, (size_t)n * 64);
+    STOCS_HIP_CHECK(hipMemcpyAsync(w.pose(), hin, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));   // the slot the render reads
+    STOCS_HIP_CHECK(hipMemcpyAsync(d_acc, hin, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));      // the accepted pose: the start
+    STOCS_HIP_CHECK(hipMemsetAsync(S->damped.p + o_rec, 0, back_all - o_rec, c->stream));               // records and trace
+    STOCS_HIP_CHECK(hipMemsetAsync(d_done, 0, (size_t)n * 4, c->stream));
+    const DepthArgs a = frame_args(F, 0.0f, prm->base.class_threshold);
+    const RvArgs ra = visible_args(&prm->base, groups);
+    RvDampedArgs da;
+    da.max_d2 = (double)ra.max_d2; da.lambda0 = (double)prm->lambda0; da.down = (double)prm->lambda_down; da.up = (double)prm->lambda_up;
+    da.max_rot = (double)prm->max_step_rotation; da.max_trans = (double)prm->max_step_translation;
+    for (int k = 0; k < 3; ++k) da.pm[k] = (double)prm->pivot_model[k];
+    da.pivot = prm->pivot; da.K = K;
+    for (int h0 = 0; h0 < n; h0 += (int)chunk) {   // all evaluations of a chunk before the next one starts
+        const int m = std::min((int)chunk, n - h0);
+        STOCS_HIP_CHECK(hipMemsetAsync(w.key(), 0xFF, (size_t)m * npix * 8, c->stream));
+        for (int e = 0; e <= K; ++e) {
+            const bool timed = dev_clock && h0 + m == n && e == K;
+            { const int rc = enqueue_evaluate(c, F, w, h0, m, a, ra, RvNoDetail(), timed); if (rc) return rc; }
+            hipLaunchKernelGGL(refine_visible_damped_solve_kernel, dim3((unsigned)m), dim3(64), 0, c->stream, w.pose() + (size_t)h0 * 16, (const double*)w.part(),
+                               (const int32_t*)w.cnt(), groups, e, da, d_acc + (size_t)h0 * 16, d_state + h0, d_done + h0, d_rec + h0,
+                               d_trace ? d_trace + (size_t)h0 * (size_t)(K + 1) : (stocs_refine_visible_trace*)NULL);
+            STOCS_HIP_CHECK(hipGetLastError());
+            if (timed) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[3], c->stream));
+        }
+    }
+    STOCS_HIP_CHECK(hipMemcpyAsync(hback, S->damped.p, back_bytes, hipMemcpyDeviceToHost, c->stream));
+    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    S->last_ms[0] = S->last_ms[1] = S->last_ms[2] = -1.0f;
+    if (dev_clock) {
+        float ms = 0.0f;
+        for (int k = 0; k < 3; ++k)
+            if (hipEventElapsedTime(&ms, c->ev_t[k], c->ev_t[k + 1]) == hipSuccess) S->last_ms[k] = ms;
+    }
+    memcpy(pose16_out, hback + o_acc, (size_t)n * 64);
+    memcpy(out, hback + o_rec, (size_t)n * sizeof(stocs_refine_visible_damped_result));
+    if (trace) memcpy(trace, hback + o_trace, rows * sizeof(stocs_refine_visible_trace));
     return STOCS_OK;
 }
 

@@ -61,6 +61,10 @@ _INSTANCE_DTYPE = np.dtype([("rank", np.int32), ("own", np.int32), ("exclusive",
 assert _INSTANCE_DTYPE.itemsize == C.sizeof(capi.InstanceResult)
 _REFINE_VISIBLE_DTYPE = np.dtype([(f[0], np.float32 if f[0] == "rms" else np.int32) for f in capi.RefineVisibleResult._fields_])
 assert _REFINE_VISIBLE_DTYPE.itemsize == C.sizeof(capi.RefineVisibleResult)
+_REFINE_VISIBLE_DAMPED_DTYPE = np.dtype(_REFINE_VISIBLE_DTYPE.descr + [("evaluations", np.int32), ("rejected", np.int32), ("cost", np.float32), ("lambda", np.float32)])
+assert _REFINE_VISIBLE_DAMPED_DTYPE.itemsize == C.sizeof(capi.RefineVisibleDampedResult)
+_REFINE_VISIBLE_TRACE_DTYPE = np.dtype([("pose", np.float32, 16), ("cost", np.float64), ("lambda", np.float64), ("accepted", np.int32), ("state", np.int32)])
+assert _REFINE_VISIBLE_TRACE_DTYPE.itemsize == C.sizeof(capi.RefineVisibleTrace)
 _SCENE_RECORD_DTYPE = np.dtype([(f[0], np.int32) for f in capi.SceneRecord._fields_])
 assert _SCENE_RECORD_DTYPE.itemsize == C.sizeof(capi.SceneRecord)
 _SCENE_RESULT_DTYPE = np.dtype([(f[0], np.int32) for f in capi.SceneResult._fields_])
@@ -495,6 +499,8 @@ class StocsEstimator:
         V = np.ascontiguousarray(vertices, np.float32).reshape(-1, 3)
         T = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
         capi.check(self.L.stocs_ctx_set_mesh(self.h, V.ctypes.data_as(capi._fp), len(V), T.ctypes.data_as(capi._ip), len(T)))
+        # refine_poses_visible_damped's default pivot: the mean of the vertices
+        self._mesh_centre = tuple(float(x) for x in V.astype(np.float64).mean(axis=0).astype(np.float32)) if len(V) and len(T) else (0.0, 0.0, 0.0)
 
     def mesh_info(self):
         """(vertices, triangles) of the mesh on the context, (0, 0) without one"""
@@ -804,6 +810,41 @@ class StocsEstimator:
         buf = (capi.RefineVisibleResult * max(n, 1))()
         capi.check(self.L.stocs_refine_poses_visible(self.h, pP, n, C.byref(prm), out.ctypes.data_as(capi._fp), buf))
         return out, np.frombuffer(buf, dtype=_REFINE_VISIBLE_DTYPE, count=n).copy()
+
+    def refine_poses_visible_damped(self, poses16, trace=False, **params):
+        """refine_poses_visible with damped, bounded steps about a point of the object that are taken only when they lower the cost
+        (stocs_refine_poses_visible_damped) -> (poses (n, 16) float32, records), or (poses, records, trace) with trace=True: records a
+        structured array with the fields of stocs_refine_visible_damped_result (the plain record of the RETURNED pose, evaluations,
+        rejected, cost, lambda), trace (n, max_iterations + 1) rows of stocs_refine_visible_trace.  params: the plain form's and lambda0,
+        lambda_down, lambda_up, max_step_rotation (rad), max_step_translation (m), pivot (0: the camera's origin, 1: pivot_model),
+        pivot_model (3 floats in the model frame; default: the mean of the vertices given to set_mesh) over the library's defaults."""
+        P, pP = capi.f32(poses16)
+        if P.size % 16:
+            raise ValueError("refine_poses_visible_damped: poses are 16 floats each")
+        n = P.size // 16
+        prm = capi.RefineVisibleDampedParams()
+        self.L.stocs_default_refine_visible_damped_params(C.byref(prm))
+        params = dict(params)
+        pm = np.asarray(params.pop("pivot_model", getattr(self, "_mesh_centre", (0.0, 0.0, 0.0))), np.float32).reshape(-1)
+        if pm.size != 3:
+            raise ValueError("refine_poses_visible_damped: pivot_model is 3 floats")
+        prm.pivot_model[:] = [float(x) for x in pm]
+        for k, v in params.items():
+            if k in dict(capi.RefineVisibleParams._fields_):
+                setattr(prm.base, k, v)
+            elif k in dict(capi.RefineVisibleDampedParams._fields_) and k != "base":
+                setattr(prm, k, v)
+            else:
+                raise TypeError("refine_poses_visible_damped: unknown parameter %r" % (k,))
+        out = np.zeros((n, 16), np.float32)
+        buf = (capi.RefineVisibleDampedResult * max(n, 1))()
+        rows = max(prm.base.max_iterations, 0) + 1
+        tr = (capi.RefineVisibleTrace * max(n * rows, 1))() if trace else None
+        capi.check(self.L.stocs_refine_poses_visible_damped(self.h, pP, n, C.byref(prm), out.ctypes.data_as(capi._fp), buf, tr))
+        rec = np.frombuffer(buf, dtype=_REFINE_VISIBLE_DAMPED_DTYPE, count=n).copy()
+        if not trace:
+            return out, rec
+        return out, rec, np.frombuffer(tr, dtype=_REFINE_VISIBLE_TRACE_DTYPE, count=n * rows).copy().reshape(n, rows)
 
     def refine_visible_detail(self, pose16, **params):
         """One evaluation of one pose as refine_poses_visible makes it (stocs_refine_visible_detail) -> (keys (height, width) uint64:

@@ -11,6 +11,11 @@ only; nothing is promised.
 
     python tools/refine_visible_quality.py [--out profiles/refine_visible_quality.json] [--samples 16]
 
+--damped: every row also gets stocs_refine_poses_visible_damped on the same hypotheses (the library's defaults about the mean of the mesh's
+vertices, K = 5 and K = 10; add_damped_5/10 or corner_error_damped_5/10, accepted and rejected steps), whether the damped median is at or
+below the row's error before, and for a row where it is not the trace of its worst hypothesis; written to
+profiles/refine_visible_damped_quality.json.
+
 Needs a GPU; no fallback."""
 import argparse
 import json
@@ -53,11 +58,35 @@ def summary(x):
     return {"median_mm": float(np.median(x) * 1e3), "p90_mm": float(np.percentile(x, 90) * 1e3), "max_mm": float(x.max() * 1e3)}
 
 
+def damped_columns(est, poses, error, key, before):
+    """the damped form on the row's hypotheses -> the row's extra columns; error(P) gives one error per pose"""
+    cols = {}
+    for K in (5, 10):
+        P, rec, tr = est.refine_poses_visible_damped(poses, trace=True, max_iterations=K, max_distance=0.02)
+        err = np.asarray(error(P), np.float64)
+        cols["%s_damped_%d" % (key, K)] = summary(err)
+        cols["damped_%d_mean_accepted" % K] = float(rec["iterations"].mean())
+        cols["damped_%d_mean_rejected" % K] = float(rec["rejected"].mean())
+        cols["damped_%d_frozen" % K] = int(rec["frozen"].sum())
+        cols["damped_%d_worse_than_before" % K] = int((err > np.asarray(before, np.float64)).sum())
+        ok = bool(np.median(err) <= np.median(before))
+        cols["damped_%d_median_at_or_below_before" % K] = ok
+        if not ok:
+            w = int(np.argmax(err - np.asarray(before, np.float64)))
+            cols["damped_%d_worst_trace" % K] = {"hypothesis": w, "error_before_mm": float(before[w]) * 1e3, "error_after_mm": float(err[w]) * 1e3,
+                                                "cost": [float(x) for x in tr[w]["cost"]], "lambda": [float(x) for x in tr[w]["lambda"]],
+                                                "accepted": [int(x) for x in tr[w]["accepted"]], "state": [int(x) for x in tr[w]["state"]]}
+    return cols
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "refine_visible_quality.json"))
     ap.add_argument("--samples", type=int, default=16)
+    ap.add_argument("--damped", action="store_true")
     args = ap.parse_args()
+    if args.damped and args.out == ap.get_default("out"):
+        args.out = os.path.join(ROOT, "profiles", "refine_visible_damped_quality.json")
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("refine_visible_quality.py needs a GPU: nothing is measured without one")
@@ -97,6 +126,8 @@ def main():
                    "add_visible_10": summary(est.pose_errors(out10, gt16)["add"]), "add_refine_poses_5": summary(est.pose_errors(plain, gt16)["add"]),
                    "add_refine_poses_robust_5": summary(est.pose_errors(robust, gt16)["add"]), "visible_mean_counted": float(rec["counted"].mean()),
                    "visible_frozen": int(rec["frozen"].sum()), "visible_median_rms_mm": float(np.median(rec["rms"]) * 1e3)}
+            if args.damped:
+                row.update(damped_columns(est, poses, lambda P: est.pose_errors(P, gt16)["add"], "add", before))
             rows.append(row)
             print(json.dumps(row), flush=True)
     # a solid without a near-symmetry: tools/mesh_time.py's box at its pose, the frame its own mesh image in front of the wall; no model
@@ -115,12 +146,15 @@ def main():
             row = {"frame": name, "max_translation_mm": max_t * 1e3, "max_rotation_deg": max_deg, "samples": args.samples, "corner_error_before": summary(corner(poses)),
                    "corner_error_visible_5": summary(corner(out5)), "corner_error_visible_10": summary(corner(out10)), "visible_mean_counted": float(rec["counted"].mean()),
                    "visible_frozen": int(rec["frozen"].sum()), "visible_median_rms_mm": float(np.median(rec["rms"]) * 1e3)}
+            if args.damped:
+                row.update(damped_columns(est, poses, corner, "corner_error", corner(poses)))
             rows.append(row)
             print(json.dumps(row), flush=True)
     est.close()
     out = {"what": "ADD (mean vertex distance of the 5 000-point Cm cloud, stocs_pose_errors) of perturbed ground-truth poses before and after refinement, per frame and "
                    "perturbation level; visible: stocs_refine_poses_visible on the level-5 mesh, max_distance 0.02; refine_poses[_robust]: the scene ingested from "
-                   "the same frame, 3.5 cm, keep 0.7, 30 degrees; box rows: the 12-triangle box on its own mesh image, largest corner distance",
+                   "the same frame, 3.5 cm, keep 0.7, 30 degrees; box rows: the 12-triangle box on its own mesh image, largest corner distance"
+                   + ("; damped: stocs_refine_poses_visible_damped with the library's defaults about the mean of the mesh's vertices" if args.damped else ""),
            "device": torch.cuda.get_device_name(0), "frame": [W, H], "depth_unit_mm": SCALE * 1e3, "triangles": int(len(t)), "rows": rows}
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:

@@ -9,7 +9,13 @@ hypotheses in the centred frames of the Cm workload.  No time is promised.
 
     python tools/refine_visible_time.py [--out profiles/refine_visible_time.json]
 
+--damped: StocsEstimator.refine_poses_visible_damped (K = 5: six evaluations) against the plain call (five iterations) on the same workloads
+at 1, 64 and 256 hypotheses, in one visit and alternating call by call (plain, damped, plain): the host wall clock per evaluation against
+the plain form's per iteration, with the A/A spread of the two plain series as the margin; written to
+profiles/refine_visible_damped_time.json.  Measurement only, no bar.
+
 Needs a GPU; no fallback."""
+import time
 import argparse
 import json
 import os
@@ -59,10 +65,85 @@ def device_medians(est, call):
     return [float(x) for x in np.median(np.asarray(t), axis=0)]
 
 
+DAMPED_SIZES = (1, 64, 256)
+DAMPED_REPS = 30
+
+
+def alternating(calls, reps=DAMPED_REPS, warm=WARM):
+    """the calls in turn, `reps` rounds after `warm` warm-up rounds -> one list of ms per call"""
+    t = [[] for _ in calls]
+    for i in range(warm + reps):
+        for k, fn in enumerate(calls):
+            t0 = time.perf_counter(); fn(); dt = (time.perf_counter() - t0) * 1e3
+            if i >= warm:
+                t[k].append(dt)
+    return t
+
+
+def stats(t):
+    return {"median_ms": float(np.median(t)), "min_ms": float(min(t)), "max_ms": float(max(t))}
+
+
+def damped_rows(est, label, v, t, P0):
+    """plain (A), damped, plain (A') alternating on one workload"""
+    rows = []
+    est.set_mesh(v, t)
+    share = frame_from(est, np.asarray(P0, np.float64))
+    for n in DAMPED_SIZES:
+        poses = np.stack([pose16(T) for T in perturbed(np.asarray(P0, np.float64), n, 100 + n)])
+        plain = lambda: est.refine_poses_visible(poses, max_iterations=ITERATIONS)
+        damped = lambda: est.refine_poses_visible_damped(poses, max_iterations=ITERATIONS)
+        out, rec = damped()
+        a, d, a2 = alternating([plain, damped, plain])
+        per_it = [np.median(a) / ITERATIONS, np.median(a2) / ITERATIONS]
+        per_eval = np.median(d) / (ITERATIONS + 1)
+        solve_plain = device_medians(est, plain)[2]
+        solve_damped = device_medians(est, damped)[2]
+        row = {"workload": label, "triangles": int(len(t)), "frame_share": round(share, 3), "hypotheses": n, "iterations": ITERATIONS, "evaluations": ITERATIONS + 1,
+               "plain_a": stats(a), "damped": stats(d), "plain_a2": stats(a2), "plain_ms_per_iteration": [float(x) for x in per_it],
+               "damped_ms_per_evaluation": float(per_eval), "ratio_per_evaluation_over_per_iteration": float(per_eval / np.mean(per_it)),
+               "aa_spread": float(abs(per_it[0] - per_it[1]) / np.mean(per_it)), "ratio_call_over_call": float(np.median(d) / np.mean([np.median(a), np.median(a2)])),
+               "expected_call_ratio": (ITERATIONS + 1) / ITERATIONS, "solve_kernel_ms_plain": solve_plain, "solve_kernel_ms_damped": solve_damped,
+               "mean_accepted": float(rec["iterations"].mean()), "mean_rejected": float(rec["rejected"].mean()), "frozen": int(rec["frozen"].sum())}
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    return rows
+
+
+def main_damped(args):
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("refine_visible_time.py needs a GPU: no time is taken without one")
+    from model_matching_amd import synth
+    from model_matching_amd.estimator import StocsEstimator
+    mesh_time.K = [float(v) for v in synth.YCB_INTRINSICS]
+    m, s, _ = synth.workload("Cm")
+    est = StocsEstimator(s.pos, s.nrm, s.prob, s.pixel, m.pos, m.nrm, build_index=False)
+    bv, bt, bP = box_mesh_and_pose()
+    rows = []
+    for label, v, t, P0 in (("Cm level 4", *synth.make_model_mesh(4), s.T_gt), ("Cm level 5", *synth.make_model_mesh(5), s.T_gt), ("box 12 triangles", bv, bt, bP)):
+        rows += damped_rows(est, label, v, t, P0)
+    est.close()
+    out = {"what": "host wall clock of refine_poses_visible_damped (K = 5, six evaluations) per evaluation against refine_poses_visible (five iterations) per iteration, "
+                   "alternating plain, damped, plain in one visit; aa_spread is the relative difference of the two plain series, the margin of the ratio; no bar",
+           "device": torch.cuda.get_device_name(0), "reps": DAMPED_REPS, "warmup": WARM, "note": "one visit, one GPU; the host column shares the machine with other work",
+           "kernel_resources": "profiles/refine_visible_damped.md (tools/kernel_resources.py refine_visible.hip)", "rows": rows}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "refine_visible_time.json"))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--damped", action="store_true")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "refine_visible_damped_time.json" if args.damped else "refine_visible_time.json")
+    if args.damped:
+        return main_damped(args)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("refine_visible_time.py needs a GPU: no time is taken without one")
