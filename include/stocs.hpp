@@ -1017,6 +1017,36 @@ public:
         return r;
     }
 
+    // Damped refinement with the contour term (stocs_refine_poses_visible_contour; no reference counterpart): refine_poses_visible_damped
+    // in which the frame's object pixels (the class image of set_frame) that a pose's render leaves uncovered pull the pose towards them,
+    // each paired with the nearest silhouette pixel within prm.pull_radius_px, and a pose that sheds object pixels pays for each.  One
+    // record per pose in input order, describing the RETURNED pose; `refined` (when given) receives the poses.  Empty on error (the text
+    // goes to the log); a frame without a class image is an error.
+    static stocs_refine_visible_contour_params default_refine_visible_contour_params() {
+        stocs_refine_visible_contour_params p;
+        stocs_default_refine_visible_contour_params(&p);
+        return p;
+    }
+    std::vector<stocs_refine_visible_contour_result> refine_poses_visible_contour(const std::vector<PoseCandidate*>& poses, std::vector<MatrixType>* refined = NULL,
+                                                                                  const stocs_refine_visible_contour_params& prm = default_refine_visible_contour_params(),
+                                                                                  std::vector<stocs_refine_visible_trace>* trace = NULL) {
+        const int n = (int)poses.size(), K = prm.damped.base.max_iterations;
+        std::vector<float> P((size_t)n * 16), Q((size_t)n * 16);
+        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], poses[(size_t)i]->transform.data(), 64);
+        std::vector<stocs_refine_visible_contour_result> r((size_t)n);
+        if (refined) refined->assign((size_t)n, MatrixType());
+        if (trace) trace->assign((size_t)n * (size_t)(K > 0 ? K + 1 : 1), stocs_refine_visible_trace());
+        if (n > 0 && stocs_refine_poses_visible_contour(ctx_, P.data(), n, &prm, Q.data(), r.data(), trace ? trace->data() : NULL) != STOCS_OK) {
+            *log_ << "refine_poses_visible_contour failed: " << stocs_last_error() << std::endl;
+            r.clear();
+            if (refined) refined->clear();
+            if (trace) trace->clear();
+            return r;
+        }
+        for (int i = 0; refined && i < n; ++i) std::memcpy((*refined)[(size_t)i].data(), &Q[(size_t)i * 16], 64);
+        return r;
+    }
+
     // Multi-instance selection (stocs_select_instances; no reference counterpart): which of the camera-frame hypotheses (the
     // hypotheses of run_trials, refined or not) are distinct instances of the object and which are one instance found twice.  Walked
     // best first, a hypothesis is kept only if enough of the scene points it explains are explained by none kept before it.  One record

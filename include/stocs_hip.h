@@ -1355,6 +1355,79 @@ int stocs_refine_poses_visible_damped(stocs_ctx* ctx, const float* pose16_camera
                                       float* pose16_out, stocs_refine_visible_damped_result* out,
                                       stocs_refine_visible_trace* trace /* n * (K + 1) or NULL */);
 
+/* ---- contour pull for the damped refinement on the visible surface: the frame's object pixels that the render leaves uncovered pull the
+ * pose towards them (no reference counterpart).  csrc/refine_visible.hip, restated in numpy in tests/refine_visible_contour_ref.py.  The
+ * plain and the damped form, their kernels and their results are what they were.  The frame must carry a class image.
+ *   Object pixels.  O = the pixels with raw != 0 and cp >= class_threshold, cp as in step 1 of the plain contract; N_O = |O| does not
+ *     depend on the pose and is counted once per call.
+ *   Evaluation.  One evaluation of the damped contract (the render, steps 1-5, the 29 sums S, the five counts) plus the contour pass
+ *     below on the same keys.  Let (r0..r1, c0..c1) be the pose's rectangle (the union of its triangles' clamped boxes), grown by
+ *     R = pull_radius_px on every side and clamped to the frame.  For every pixel u = (r, c) of the grown rectangle that is in O and has
+ *     an empty key:
+ *     1. the nearest silhouette pixel: among the pixels s = (r_s, c_s) with a non-empty key, |r_s - r| <= R and |c_s - c| <= R, the one
+ *        with the minimum of (d2 = dr dr + dc dc, r_s W + c_s): the exact Euclidean nearest inside the square window, on equal d2 the
+ *        lowest linear index.  None: u is unreached (state 1).
+ *     2. in float, every operation one IEEE operation, no contraction: z_s the float in the high word of s's key,
+ *        p = (xn_s z_s, yn_s z_s, z_s) on the mesh rule's ray of s; d = (float)raw_u * depth_scale, q = (xn_u d, yn_u d, d) on the ray of
+ *        u; e = q - p; D = e_x e_x + (e_y e_y + e_z e_z).
+ *     3. D > pull_distance * pull_distance (the product in float): u is beyond (state 2) and gives no row; equality is not beyond.  This
+ *        is what drops the table and the neighbours.
+ *     4. otherwise u is pulled (state 3) and gives three point-to-point rows, in double from those floats: for k = 0, 1, 2
+ *        a_k = (p x u_k, u_k) with u_k the k-th unit vector, b_k = e[k]:
+ *        a_0 = (0, p_z, -p_y, 1, 0, 0), a_1 = (-p_z, 0, p_x, 0, 1, 0), a_2 = (p_y, -p_x, 0, 0, 0, 1).
+ *        The rows linearise p' - q for the same left, camera-frame motion as the plain row: p' ~ p + omega x p + t and
+ *        u_k.(omega x p) = omega.(p x u_k).  Each row adds its products to the 29 contour sums Sc as a counted pixel's row does to S, row
+ *        0 first; Sc[27] counts pulled pixels, one per pixel; Sc[28] = the sum of b_k b_k.
+ *   Counts.  uncovered = N_O - (too_far + grazing + counted): the object pixels without a key.  unreached, beyond and pulled are counted
+ *     over the grown rectangle; uncovered pixels outside it are unreached by definition, are not walked and are not in `unreached`.
+ *   System, in double, with w = (double)contour_weight:  M = S[0..20] + w Sc[0..20], v = S[21..26] + w Sc[21..26], entry by entry.
+ *     Everything behind them is the damped contract verbatim on these totals (the sums about the pivot, (1 + lambda) on the diagonal,
+ *     the elimination, the common bound, the composition).
+ *   Cost.  C = ((S[28] + max_d2 too_far) + w (Sc[28] + pull_d2 (uncovered - pulled))) / ((double)(counted + too_far) + w uncovered),
+ *     max_d2 and pull_d2 the (double) of the float products; C = +inf when counted + 3 pulled < 6, and with K > 0 that freezes the pose
+ *     at e = 0 in place of the damped form's counted < 6.  A truncated quadratic over a pixel set that does not depend on the pose: a
+ *     pose that sheds an object pixel pays pull_d2 for it.  An empty render stays rejected or frozen; a silhouette that has slid off the
+ *     object but still reaches it within R is no longer frozen.
+ *   contour_weight == 0: the contour pass is not run; poses, the damped part of the records and the trace are those of
+ *     stocs_refine_poses_visible_damped bit for bit (pulled, unreached, beyond and pull_rms are 0).  N_O == 0 with w > 0: the same,
+ *     every added term is an exact zero.
+ * Returned per pose: the damped record of the RETURNED pose and, of the same evaluation, object_px, uncovered, unreached, beyond, pulled
+ * and pull_rms; an invalid or all-zero pose comes back bit for bit with a zero record.  trace: as in the damped form.
+ * stocs_refine_visible_contour_detail: ONE pose, one evaluation, no update (max_iterations is checked and not used; contour_weight
+ * likewise, the pass runs): per pixel the contour state (H W, or NULL: 0 for a pixel that was not walked, is not in O or has a key, else
+ * 1, 2, 3), the linear index of the nearest silhouette pixel (H W, or NULL; -1 where there is none) and the 29 contour sums.
+ * Checked in the order of the damped form, the new parameters behind the damped ones, and behind "no frame": a frame without a class
+ * image (STOCS_ERR_STATE).  One grow-only workspace, one read-back and one synchronisation per call; chunks of key buffers and
+ * STOCS_REFINE_VISIBLE_CHUNK; a pose's result is bitwise independent of batch, position and chunk.
+ * The kernels: refine_visible_object_count_kernel once per call; per evaluation refine_visible_contour_kernel between
+ * the render and the accumulation (which clears the keys): the accumulation's grid, tiles of 16 rows x 64 columns of the grown
+ * rectangle, "key present" as bit rows in LDS built with __ballot, the nearest set bit of a row by count-leading/trailing-zeros, the
+ * minimum over the window's rows nearest first; one partial per workgroup in a fixed order; refine_visible_contour_solve_kernel in the
+ * damped solve's place.  stocs_refine_visible_contour_last_device_ms: with "device_clock" on, the contour kernel's HIP-event time of the
+ * last evaluation of the last chunk of the last call; -1 otherwise.
+ * Not here: the opposite push (silhouette pixels whose measurement lies far behind), weights per pixel, the term inside trial batches or
+ * the tracker, frames without a class image. ---- */
+typedef struct stocs_refine_visible_contour_params {
+    stocs_refine_visible_damped_params damped;   /* as above                                                   */
+    float   contour_weight;             /* w >= 0 finite (default 1); 0: the damped form, bit for bit          */
+    int32_t pull_radius_px;             /* R, 1 .. 64 (default 16)                                             */
+    float   pull_distance;              /* m, > 0 finite (default 0.03): the 3-D gate of a pull                */
+} stocs_refine_visible_contour_params;  /* 64 bytes */
+typedef struct stocs_refine_visible_contour_result {
+    stocs_refine_visible_damped_result damped;
+    int32_t object_px;                  /* N_O                                                                 */
+    int32_t uncovered, unreached, beyond, pulled;   /* of the returned pose's evaluation                      */
+    float   pull_rms;                   /* sqrtf((float)(Sc[28] / pulled)), 0 when pulled == 0                 */
+} stocs_refine_visible_contour_result;  /* 80 bytes */
+void stocs_default_refine_visible_contour_params(stocs_refine_visible_contour_params* p);
+int stocs_check_refine_visible_contour_params(const stocs_refine_visible_contour_params* p);   /* host only */
+int stocs_refine_poses_visible_contour(stocs_ctx* ctx, const float* pose16_camera, int n, const stocs_refine_visible_contour_params* p,
+                                       float* pose16_out, stocs_refine_visible_contour_result* out,
+                                       stocs_refine_visible_trace* trace /* n * (K + 1) or NULL */);
+int stocs_refine_visible_contour_detail(stocs_ctx* ctx, const float* pose16_camera /* one */, const stocs_refine_visible_contour_params* p,
+                                        uint8_t* state /* H*W or NULL */, int32_t* nearest /* H*W or NULL */, double* sums29);
+int stocs_refine_visible_contour_last_device_ms(const stocs_ctx* ctx, float* contour_ms);
+
 /* ---- mesh models: a triangle mesh sampled into the oriented model cloud the search needs (no reference counterpart).  Stand-alone like
  * stocs_preprocess_model: no context; the same cached per-thread workspace and pinned block (stocs_trim gives them back; a second call of
  * the same or a smaller size allocates nothing).  csrc/mesh_sample.hip, restated in numpy in tests/mesh_sample_ref.py, equal bit for bit.

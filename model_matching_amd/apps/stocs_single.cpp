@@ -78,6 +78,9 @@
 // written again from the result; K = 0 scores the pose and leaves the file.  One "refine-visible <object>: iterations=.. frozen=..
 // present=.. no_depth=.. off_class=.. too_far=.. grazing=.. counted=.. rms=.. mesh=<triangles>" line and the refined "pose:" line; with
 // --gt a "refine-visible <object> before: add=.. adds=.." and an "after" line (stocs_pose_errors), and the gt lines score the refined file.
+// --contour [w[,radius_px[,dist_m]]] (with --refine-visible and --damped; without --damped an error naming it): the damped form with the
+// contour term (stocs_refine_poses_visible_contour: uncovered object pixels of the class image pull the pose); the line then reads
+// "refine-visible <object>: contour iterations=.. .. rms=.. object_px=.. uncovered=.. unreached=.. beyond=.. pulled=.. pull_rms=.. mesh=..".
 // --damped [lambda0[,rot_deg[,trans_m]]] (with --refine-visible): the damped form (stocs_refine_poses_visible_damped: K + 1 evaluations, steps
 // bounded by rot_deg degrees and trans_m metres, taken only when they lower the cost, about the mean of the mesh's vertices; the library's
 // defaults unless given); the line then reads "refine-visible <object>: damped iterations=.. rejected=.. evaluations=.. cost=.. lambda=..
@@ -371,7 +374,7 @@ static bool read_pose_file(const std::string& path, MatrixType& m) {
 // --gt: the pose this run wrote to out_path, read back with the reader the ground truth goes through (what is scored is what a reader of
 // the file gets), against the ground truth: ADD, ADD-S, their maxima, the model's diameter (stocs_pose_errors, stocs_model_diameter); with
 // --trials N also the share of the trials' winners (full precision, a trial without a pose left out) within 0.1 diameter
-struct RefineVisibleOptions { bool on; int iterations; float distance, view_cos; int mesh_triangles; bool damped; float lambda0, rot_deg, trans_m, pivot[3]; };   // --refine-visible K[,dist[,cos]]; a value < 0 leaves the library's default
+struct RefineVisibleOptions { bool on; int iterations; float distance, view_cos; int mesh_triangles; bool damped; float lambda0, rot_deg, trans_m, pivot[3]; bool contour; float weight; int radius_px; float pull_m; };   // --refine-visible K[,dist[,cos]]; a value < 0 leaves the library's default
 struct VsdOptions { bool on; float delta, surfel_radius; int mesh_triangles; };   // --vsd; a value <= 0 leaves the library's default; mesh_triangles > 0: --mesh
 
 // the ten errors of a VSD record as " e0=... .. e9=..." at b + at; returns the new end
@@ -395,6 +398,16 @@ static stocs_refine_visible_damped_params damped_params_of(const RefineVisibleOp
     return prm;
 }
 
+// the parameters of --refine-visible .. --damped .. --contour ..: the library's defaults unless given
+static stocs_refine_visible_contour_params contour_params_of(const RefineVisibleOptions& rv) {
+    stocs_refine_visible_contour_params prm = stocs::stocs_estimator::default_refine_visible_contour_params();
+    prm.damped = damped_params_of(rv);
+    if (rv.weight >= 0.0f) prm.contour_weight = rv.weight;
+    if (rv.radius_px >= 0) prm.pull_radius_px = rv.radius_px;
+    if (rv.pull_m >= 0.0f) prm.pull_distance = rv.pull_m;
+    return prm;
+}
+
 static int run_refine_visible(stocs::stocs_estimator& est, const RefineVisibleOptions& rv, const std::string& out_path, const std::string& object, const std::string& gt_path) {
     MatrixType p, g;
     if (!read_pose_file(out_path, p)) { std::cout << "refine-visible " << object << ": no pose" << std::endl; return 0; }
@@ -405,8 +418,17 @@ static int run_refine_visible(stocs::stocs_estimator& est, const RefineVisibleOp
     PoseCandidate e(p, 0.0f, -1.0f);
     std::vector<MatrixType> refined;
     std::vector<stocs_refine_visible_result> r;
-    char b[640];
-    if (rv.damped) {
+    char b[960];
+    if (rv.contour) {
+        const std::vector<stocs_refine_visible_contour_result> d = est.refine_poses_visible_contour(std::vector<PoseCandidate*>(1, &e), &refined, contour_params_of(rv));
+        if (d.size() != 1 || refined.size() != 1) { std::cerr << "refine-visible failed: " << stocs_last_error() << std::endl; return 2; }
+        r.push_back(d[0].damped.base);
+        snprintf(b, sizeof(b), "refine-visible %s: contour iterations=%d rejected=%d evaluations=%d cost=%.9g lambda=%.9g frozen=%d present=%d no_depth=%d off_class=%d too_far=%d "
+                 "grazing=%d counted=%d rms=%.9g object_px=%d uncovered=%d unreached=%d beyond=%d pulled=%d pull_rms=%.9g mesh=%d", object.c_str(), r[0].iterations,
+                 d[0].damped.rejected, d[0].damped.evaluations, (double)d[0].damped.cost, (double)d[0].damped.lambda, r[0].frozen, r[0].present, r[0].no_depth, r[0].off_class,
+                 r[0].too_far, r[0].grazing, r[0].counted, (double)r[0].rms, d[0].object_px, d[0].uncovered, d[0].unreached, d[0].beyond, d[0].pulled, (double)d[0].pull_rms,
+                 rv.mesh_triangles);
+    } else if (rv.damped) {
         const std::vector<stocs_refine_visible_damped_result> d = est.refine_poses_visible_damped(std::vector<PoseCandidate*>(1, &e), &refined, damped_params_of(rv));
         if (d.size() != 1 || refined.size() != 1) { std::cerr << "refine-visible failed: " << stocs_last_error() << std::endl; return 2; }
         r.push_back(d[0].base);
@@ -747,8 +769,8 @@ int main(int argc, char** argv) {
     bool do_instances = false, do_masks = false, have_trim = false, have_gate = false;
     SceneSelectOptions scene_opt = {false, false, 0};
     VsdOptions vsd_opt = {false, 0.0f, 0.0f, 0};
-    RefineVisibleOptions rv_opt = {false, 0, -1.0f, -1.0f, 0, false, -1.0f, -1.0f, -1.0f, {0.0f, 0.0f, 0.0f}};
-    bool damped_bad = false;
+    RefineVisibleOptions rv_opt = {false, 0, -1.0f, -1.0f, 0, false, -1.0f, -1.0f, -1.0f, {0.0f, 0.0f, 0.0f}, false, -1.0f, -1, -1.0f};
+    bool damped_bad = false, contour_bad = false;
     std::string mesh_path, surface = "points";
     bool have_vsd_delta = false, have_surfel_radius = false;
     stocs_instance_params inst_prm = stocs::stocs_estimator::default_instance_params();
@@ -766,6 +788,16 @@ int main(int argc, char** argv) {
             const int got = sscanf(dv.c_str(), "%f,%f,%f%c", &rv_opt.lambda0, &rv_opt.rot_deg, &rv_opt.trans_m, &tail);
             if (got < 1 || got > 3 || (size_t)std::count(dv.begin(), dv.end(), ',') + 1 != (size_t)got) damped_bad = true;
             if (!(rv_opt.lambda0 >= 0.0f) || (got >= 2 && !(rv_opt.rot_deg > 0.0f)) || (got == 3 && !(rv_opt.trans_m > 0.0f))) damped_bad = true;
+            continue;
+        }
+        if (std::string(argv[i]) == "--contour") {   // [w[,radius_px[,dist_m]]]: the value may be left out
+            rv_opt.contour = true;
+            if (i + 1 >= argc || std::string(argv[i + 1]).compare(0, 2, "--") == 0) { --i; continue; }
+            const std::string cv = argv[i + 1];
+            char tail = 0;
+            const int got = sscanf(cv.c_str(), "%f,%d,%f%c", &rv_opt.weight, &rv_opt.radius_px, &rv_opt.pull_m, &tail);
+            if (got < 1 || got > 3 || (size_t)std::count(cv.begin(), cv.end(), ',') + 1 != (size_t)got) contour_bad = true;
+            if (!(rv_opt.weight >= 0.0f) || (got >= 2 && rv_opt.radius_px < 1) || (got == 3 && !(rv_opt.pull_m > 0.0f))) contour_bad = true;
             continue;
         }
         if (i + 1 >= argc) break;
@@ -867,6 +899,17 @@ int main(int argc, char** argv) {
         const stocs_refine_visible_damped_params dp = damped_params_of(rv_opt);
         if (!rv_opt.on || damped_bad || (rv_opt.iterations >= 0 && !mesh_path.empty() && stocs_check_refine_visible_damped_params(&dp) != STOCS_OK)) {
             std::cerr << "--damped [lambda0[,rot_deg[,trans_m]]] needs --refine-visible, lambda0 >= 0, rot_deg > 0 and trans_m > 0" << std::endl;
+            return -1;
+        }
+    }
+    if (rv_opt.contour) {   // refused before any search
+        const stocs_refine_visible_contour_params cp = contour_params_of(rv_opt);
+        if (!rv_opt.on || !rv_opt.damped) {
+            std::cerr << "--contour [w[,radius_px[,dist_m]]] needs " << (!rv_opt.on ? "--refine-visible" : "--damped") << std::endl;
+            return -1;
+        }
+        if (contour_bad || (rv_opt.iterations >= 0 && !mesh_path.empty() && !damped_bad && stocs_check_refine_visible_contour_params(&cp) != STOCS_OK)) {
+            std::cerr << "--contour [w[,radius_px[,dist_m]]] needs w >= 0, radius_px in 1 .. 64 and dist_m > 0" << std::endl;
             return -1;
         }
     }

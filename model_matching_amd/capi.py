@@ -150,6 +150,15 @@ class RefineVisibleTrace(C.Structure):
     _fields_ = [("pose", C.c_float * 16), ("cost", C.c_double), ("lambda_", C.c_double), ("accepted", C.c_int32), ("state", C.c_int32)]
 
 
+class RefineVisibleContourParams(C.Structure):
+    _fields_ = [("damped", RefineVisibleDampedParams), ("contour_weight", C.c_float), ("pull_radius_px", C.c_int32), ("pull_distance", C.c_float)]
+
+
+class RefineVisibleContourResult(C.Structure):
+    _fields_ = [("damped", RefineVisibleDampedResult), ("object_px", C.c_int32), ("uncovered", C.c_int32), ("unreached", C.c_int32), ("beyond", C.c_int32),
+                ("pulled", C.c_int32), ("pull_rms", C.c_float)]
+
+
 class SceneRecord(C.Structure):
     _fields_ = [("footprint", C.c_int32), ("no_depth", C.c_int32), ("agree", C.c_int32), ("in_front", C.c_int32), ("behind", C.c_int32),
                 ("on_mask", C.c_int32), ("claimed", C.c_int32)]
@@ -295,6 +304,12 @@ SIGNATURES = {
     "stocs_check_refine_visible_damped_params": (C.c_int, [C.POINTER(RefineVisibleDampedParams)]),
     "stocs_refine_poses_visible_damped": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(RefineVisibleDampedParams), _fp, C.POINTER(RefineVisibleDampedResult),
                                                     C.POINTER(RefineVisibleTrace)]),
+    "stocs_default_refine_visible_contour_params": (None, [C.POINTER(RefineVisibleContourParams)]),
+    "stocs_check_refine_visible_contour_params": (C.c_int, [C.POINTER(RefineVisibleContourParams)]),
+    "stocs_refine_poses_visible_contour": (C.c_int, [_vp, _fp, C.c_int, C.POINTER(RefineVisibleContourParams), _fp, C.POINTER(RefineVisibleContourResult),
+                                                     C.POINTER(RefineVisibleTrace)]),
+    "stocs_refine_visible_contour_detail": (C.c_int, [_vp, _fp, C.POINTER(RefineVisibleContourParams), _u8p, _ip, C.POINTER(C.c_double)]),
+    "stocs_refine_visible_contour_last_device_ms": (C.c_int, [_vp, C.POINTER(C.c_float)]),
     "stocs_mesh_sample_counts": (C.c_int, [_fp, C.c_int, _ip, C.c_int, C.c_float, C.c_uint64, C.c_int, _ip, C.POINTER(C.c_double), _i64p, _intp]),
     "stocs_mesh_sample": (C.c_int, [_fp, C.c_int, _ip, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_int, _fp, _fp, _ip, C.c_int, _intp]),
     "stocs_preprocess_model_mesh": (C.c_int, [_fp, C.c_int, _ip, C.c_int, C.c_float, C.c_uint64, C.c_int, C.c_float, C.c_float, C.c_int, _fp, _fp, C.c_int, _intp]),

@@ -27,6 +27,16 @@
 //               evaluation, accept or reject against the pose's accepted state (pose, 29 sums, cost, lambda, kept in the workspace between
 //               evaluations), and from the accepted state the sums moved to a pivot on the object, the damped 6x6 solve, the bound and the
 //               next trial pose, written into the slot the next render reads; one trace row per evaluation when asked for.
+// The contour form (stocs_refine_poses_visible_contour; tests/refine_visible_contour_ref.py) is the damped form with one more
+// kernel per evaluation and another solve:
+//   object count  once per call: N_O, the frame's pixels with a measurement and a class probability at the threshold, by __ballot.
+//   contour     between the render and the accumulation (which clears the keys), on the accumulation's grid: the pose's rectangle grown
+//               by the pull radius in tiles of 16 rows x 64 columns; per tile with an uncovered object pixel, "key present" of the tile and
+//               its halo as bit rows in LDS (one __ballot per 64 keys), per pixel the nearest set bit of each row of the window by
+//               count-leading/trailing-zeros under the minimum of (d2, linear index), one key load for the winner's depth, the 3-D gate,
+//               three point-to-point rows in double; 29 sums and three counts per workgroup in the accumulation's fixed order.
+//   contour solve  both sets of partials reduced, M = S + w Sc, the cost over the object pixels, then rv_damped_decide, the damped solve's
+//               own decision and next trial, on the totals.
 // Known limits: the plain step is an undamped Gauss-Newton step whose rotation is about the camera's origin: on a solid whose visible surface
 // constrains a motion weakly it can be large and leave the pose worse (measured on the Cm solid; the restatement does the
 // same, bit for bit; the damped form is the remedy); a frozen hypothesis is still rendered and walked in the remaining iterations of its chunk (nothing reads the result);
@@ -46,11 +56,13 @@ static const unsigned long long RV_EMPTY = 0xFFFFFFFFFFFFFFFFull;
 
 struct RefineVisibleState {
     static const StateOwner OWNER = OWN_REFINE_VISIBLE;
-    ~RefineVisibleState() { work.free(); detail.free(); damped.free(); }
+    ~RefineVisibleState() { work.free(); detail.free(); damped.free(); contour.free(); }
     DevBlock work;     // poses | records | frozen flags | rectangles | partial sums | partial counts | one chunk of key buffers, grow-only
     DevBlock detail;   // stocs_refine_visible_detail: state | sums, grow-only
     DevBlock damped;   // stocs_refine_poses_visible_damped: accepted poses | records | trace | accepted sums, cost, lambda | done flags, grow-only
+    DevBlock contour;  // the contour form: accepted poses | records | trace | accepted sums, cost, lambda | done flags | contour partials | N_O | detail planes, grow-only
     float last_ms[3] = {-1.0f, -1.0f, -1.0f};  // "device_clock": HIP-event time of the last call's last render, accumulation and solve (-1: not taken)
+    float last_contour_ms = -1.0f;             // the same of the last call's last contour pass
 };
 
 struct RvArgs {
@@ -260,42 +272,25 @@ struct RvDampedArgs {
 // what a pose keeps between evaluations beside its accepted pose and its record: the accepted sums, the accepted cost, lambda
 struct RvDampedState { double S[RV_SUMS]; double cost, lambda; };
 
-// One wavefront per hypothesis of the chunk, after evaluation e of K + 1: the reduction of refine_visible_solve_kernel, the cost, the
-// decision against the accepted state, and for e < K the next trial from the accepted state (steps 1-7 of the contract), written into the
-// pose slot the next render reads.  Everything behind the reduction is lane 0's, in double.
-__global__ __launch_bounds__(64) void refine_visible_damped_solve_kernel(float* __restrict__ poses, const double* __restrict__ partial, const int32_t* __restrict__ pcount,
-                                                                         int groups, int e, RvDampedArgs da, float* __restrict__ accepted, RvDampedState* __restrict__ state,
-                                                                         int32_t* __restrict__ done, stocs_refine_visible_damped_result* __restrict__ rec,
-                                                                         stocs_refine_visible_trace* __restrict__ trace) {
-    const int h = (int)blockIdx.x, lane = (int)threadIdx.x;
-    if (done[h]) return;   // the same address in every lane: the whole wavefront
-    double acc[RV_SUMS];
-    int n[RV_COUNTS];
-    rv_reduce_partials(partial, pcount, h, groups, lane, acc, n);
-    if (lane) return;
-    float* Ph = poses + (size_t)h * 16;
-    float* Pah = accepted + (size_t)h * 16;
-    float P[16];
-    bool nonzero = false;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { P[i] = Ph[i]; nonzero = nonzero || P[i] != 0.0f; }
-    stocs_refine_visible_damped_result* R = rec + h;   // zeroed in front of the first evaluation
-    RvDampedState* St = state + h;
-    if (e == 0 && (!pose_finite(P) || !nonzero)) { done[h] = 1; return; }   // renders nothing: the zero record, the pose as it came
-    const int count = (int)acc[27];
-    const double C = count < 6 ? (double)INFINITY : (acc[28] + da.max_d2 * (double)n[RV_TOO_FAR]) / (double)(count + n[RV_TOO_FAR]);
+// What follows the cost C of evaluation e in the damped contract, lane 0's, in double: the decision against the pose's accepted state, and
+// for e < K the next trial from the accepted state (steps 1-7), written into the slot Ph the next render reads.  sys: the sums the system
+// is made from ([0..26]; [28] is the record's b^T b; kept whole as the accepted sums); n, count: the evaluation's counts; enough: whether
+// the evaluation at e = 0 carries a system at all.  P holds the evaluated pose and, behind a rejection, the accepted one.
+__device__ __forceinline__ void rv_damped_decide(float* Ph, float* Pah, float (&P)[16], stocs_refine_visible_damped_result* R,
+                                                 RvDampedState* St, int32_t* done_h, stocs_refine_visible_trace* trace_h, int e,
+                                                 RvDampedArgs da, const double (&sys)[RV_SUMS], const int (&n)[RV_COUNTS], int count, double C, bool enough) {
     double lambda = e == 0 ? da.lambda0 : St->lambda;
     const bool ok = e == 0 || C < St->cost;
     double Sa[27];   // what the next trial is made from: the 21 + 6 accepted sums
     if (ok) {
         R->base.present = n[RV_PRESENT]; R->base.no_depth = n[RV_NO_DEPTH]; R->base.off_class = n[RV_OFF_CLASS]; R->base.too_far = n[RV_TOO_FAR];
         R->base.grazing = n[RV_GRAZING]; R->base.counted = count;
-        R->base.rms = count > 0 ? sqrtf((float)(acc[28] / (double)count)) : 0.0f;
+        R->base.rms = count > 0 ? sqrtf((float)(sys[28] / (double)count)) : 0.0f;
         R->cost = (float)C;
 #pragma unroll
-        for (int k = 0; k < RV_SUMS; ++k) St->S[k] = acc[k];
+        for (int k = 0; k < RV_SUMS; ++k) St->S[k] = sys[k];
 #pragma unroll
-        for (int k = 0; k < 27; ++k) Sa[k] = acc[k];
+        for (int k = 0; k < 27; ++k) Sa[k] = sys[k];
         St->cost = C;
         if (e > 0) {
             lambda = fmax(lambda / da.down, 1e-9);
@@ -314,14 +309,14 @@ __global__ __launch_bounds__(64) void refine_visible_damped_solve_kernel(float* 
     St->lambda = lambda;
     R->lambda = (float)lambda;
     R->evaluations += 1;
-    stocs_refine_visible_trace* Tr = trace ? trace + (size_t)h * (size_t)(da.K + 1) + (size_t)e : NULL;
+    stocs_refine_visible_trace* Tr = trace_h ? trace_h + (size_t)e : NULL;   // row e of the pose's K + 1
     if (Tr) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) Tr->pose[i] = Ph[i];
         Tr->cost = C; Tr->lambda = lambda; Tr->accepted = ok ? 1 : 0; Tr->state = 1;
     }
     if (e == da.K) return;
-    bool freeze = e == 0 && count < 6;   // not enough pixels at the start: the pose as it came
+    bool freeze = e == 0 && !enough;   // not enough pixels at the start: the pose as it came
     double x[6];
     double c0 = 0.0, c1 = 0.0, c2 = 0.0;
     if (!freeze) {
@@ -357,7 +352,7 @@ __global__ __launch_bounds__(64) void refine_visible_damped_solve_kernel(float* 
         freeze = !solve6(A, b, x);
     }
     if (freeze) {
-        done[h] = 1; R->base.frozen = 1;
+        *done_h = 1; R->base.frozen = 1;
         if (Tr) Tr->state = 3;
         return;
     }
@@ -384,6 +379,255 @@ __global__ __launch_bounds__(64) void refine_visible_damped_solve_kernel(float* 
             Ph[4 * q + r] = (float)v;   // the slot's last row is the start's, as every accepted pose's is
         }
     }
+}
+
+// One wavefront per hypothesis of the chunk, after evaluation e of K + 1: the reduction of refine_visible_solve_kernel, the cost, the
+// decision against the accepted state, and for e < K the next trial from the accepted state (steps 1-7 of the contract), written into the
+// pose slot the next render reads.  Everything behind the reduction is lane 0's, in double.
+__global__ __launch_bounds__(64) void refine_visible_damped_solve_kernel(float* __restrict__ poses, const double* __restrict__ partial, const int32_t* __restrict__ pcount,
+                                                                         int groups, int e, RvDampedArgs da, float* __restrict__ accepted, RvDampedState* __restrict__ state,
+                                                                         int32_t* __restrict__ done, stocs_refine_visible_damped_result* __restrict__ rec,
+                                                                         stocs_refine_visible_trace* __restrict__ trace) {
+    const int h = (int)blockIdx.x, lane = (int)threadIdx.x;
+    if (done[h]) return;   // the same address in every lane: the whole wavefront
+    double acc[RV_SUMS];
+    int n[RV_COUNTS];
+    rv_reduce_partials(partial, pcount, h, groups, lane, acc, n);
+    if (lane) return;
+    float* Ph = poses + (size_t)h * 16;
+    float* Pah = accepted + (size_t)h * 16;
+    float P[16];
+    bool nonzero = false;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { P[i] = Ph[i]; nonzero = nonzero || P[i] != 0.0f; }
+    stocs_refine_visible_damped_result* R = rec + h;   // zeroed in front of the first evaluation
+    RvDampedState* St = state + h;
+    if (e == 0 && (!pose_finite(P) || !nonzero)) { done[h] = 1; return; }   // renders nothing: the zero record, the pose as it came
+    const int count = (int)acc[27];
+    const double C = count < 6 ? (double)INFINITY : (acc[28] + da.max_d2 * (double)n[RV_TOO_FAR]) / (double)(count + n[RV_TOO_FAR]);
+    rv_damped_decide(Ph, Pah, P, R, St, done + h, trace ? trace + (size_t)h * (size_t)(da.K + 1) : (stocs_refine_visible_trace*)NULL, e, da, acc, n, count, C, count >= 6);
+}
+
+// ---- the contour form (stocs_refine_poses_visible_contour): the damped form's evaluation plus a pass over the frame's object
+// pixels that the render left uncovered, each pulled towards the nearest silhouette pixel
+enum { RC_TILE_ROWS = 16, RC_MAX_RADIUS = 64, RC_BIT_ROWS = RC_TILE_ROWS + 2 * RC_MAX_RADIUS };
+enum { RC_UNREACHED = 0, RC_BEYOND, RC_PULLED };   // the integer counts of a contour partial (RV_COUNTS wide: the rest is 0)
+enum { RC_FAR = 999 };                             // "no set bit on this side": above every radius
+
+struct RcArgs {
+    float pull_d2;     // pull_distance * pull_distance, in float
+    int R;             // pull_radius_px
+    int groups;        // G
+};
+struct RcNoDetail { static constexpr bool on = false; };
+struct RcDetailOut {
+    static constexpr bool on = true;
+    uint8_t* state;    // H * W, preset 0
+    int32_t* nearest;  // H * W, preset -1
+};
+
+// N_O of the frame: pixels with a measurement whose class probability reaches the threshold.  Integer counts: any order gives the same.
+__global__ __launch_bounds__(256) void refine_visible_object_count_kernel(const uint16_t* __restrict__ depth, const uint16_t* __restrict__ prob, size_t npix,
+                                                                          float class_threshold, int32_t* __restrict__ n_object) {
+    int mine = 0;
+    const size_t stride = (size_t)gridDim.x * 256;
+    for (size_t base = (size_t)blockIdx.x * 256; base < npix; base += stride) {   // wave-uniform bounds: every __ballot sees the whole wavefront
+        const size_t px = base + threadIdx.x;
+        bool in = false;
+        if (px < npix && depth[px] != 0) in = (float)((double)prob[px] * (1.0 / 10000)) >= class_threshold;
+        mine += __popcll(__ballot(in));
+    }
+    if ((threadIdx.x & 63) == 0 && mine) atomicAdd(n_object, mine);
+}
+
+// the nearest set bit of a 192-bit row (words lo, mid, hi; mid's bit `lane` is the pixel's own column) on either side of the pixel: the
+// distances to the left (dl) and to the right (dr) in columns, 0 .. 64, RC_FAR where there is none within 64
+__device__ __forceinline__ void rc_nearest_in_row(unsigned long long lo, unsigned long long mid, unsigned long long hi, int lane, int& dl, int& dr) {
+    const unsigned long long right = lane ? (mid >> lane) | (hi << (64 - lane)) : mid;           // bit k: column c + k
+    const unsigned long long left = lane == 63 ? mid : (mid << (63 - lane)) | (lo >> (lane + 1));   // bit 63 - k: column c - k
+    dr = right ? (int)__builtin_ctzll(right) : (((hi >> lane) & 1ull) ? 64 : RC_FAR);
+    dl = left ? (int)__builtin_clzll(left) : (((lo >> lane) & 1ull) ? 64 : RC_FAR);
+}
+
+// Pose blockIdx.y of the chunk, the grid of the accumulation.  The pose's rectangle grown by R and clamped to the frame is cut into tiles of
+// RC_TILE_ROWS rows x 64 columns from its upper left corner; workgroup g takes tiles g, g + G, ... in row-major order, its four wavefronts
+// rows w, w + 4, w + 8, w + 12 of a tile, a lane one column.  Per tile: (A) which of its pixels are object pixels with an empty key; a
+// tile without one is done.  (B) "key present" of the tile plus its halo of R rows and 64 columns as bit rows in LDS, one __ballot per 64
+// keys; only the pose's own rectangle is read (nothing is set outside it).  (C) per pixel the exact minimum of (d2, index) over the rows
+// of the window, nearest rows first, until a row's dr dr alone is above the best d2; the winner's key is the only one loaded for its depth.
+// Keys are read and never written.  Sums and counts are reduced as the accumulation's: one partial per workgroup.
+template <class Detail>
+__global__ __launch_bounds__(256) void refine_visible_contour_kernel(const unsigned long long* __restrict__ zkey, const int32_t* __restrict__ box,
+                                                                     const uint16_t* __restrict__ depth, const uint16_t* __restrict__ prob, DepthArgs a, RcArgs ca,
+                                                                     double* __restrict__ partial, int32_t* __restrict__ pcount, Detail det) {
+    __shared__ unsigned long long bits[RC_BIT_ROWS][3];
+    __shared__ double red[4][RV_SUMS];
+    __shared__ int cnt[4][3];
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int h = (int)blockIdx.y, g = (int)blockIdx.x;
+    const int32_t* bx = box + (size_t)h * VSD_BOX_WORDS;
+    const int c0 = -bx[VB_NEG_C0], c1 = bx[VB_C1], r0 = -bx[VB_NEG_R0], r1 = bx[VB_R1];
+    const bool any = c1 >= 0 && c1 >= c0 && r1 >= r0;   // as in the accumulation: a rendered pose has 0 <= c0 <= c1 <= W - 1, 0 <= r0 <= r1 <= H - 1
+    const int R = ca.R;
+    const int ec0 = max(c0 - R, 0), ec1 = min(c1 + R, a.W - 1), er0 = max(r0 - R, 0), er1 = min(r1 + R, a.H - 1);
+    const int n_tcols = any ? (ec1 - ec0 + 64) >> 6 : 0;
+    const int n_trows = any ? (er1 - er0 + RC_TILE_ROWS) / RC_TILE_ROWS : 0;
+    const int n_tiles = n_trows * n_tcols;
+    const unsigned long long* zk = zkey + (size_t)h * ((size_t)a.W * (size_t)a.H);
+    double v[RV_SUMS];
+#pragma unroll
+    for (int k = 0; k < RV_SUMS; ++k) v[k] = 0.0;
+    int n_unreached = 0, n_beyond = 0, n_pulled = 0;
+    for (int tile = g; tile < n_tiles; tile += ca.groups) {
+        const int trow = tile / n_tcols, tcol = tile - trow * n_tcols;
+        const int tr0 = er0 + trow * RC_TILE_ROWS, tr1 = min(tr0 + RC_TILE_ROWS - 1, er1);
+        const int cs = ec0 + tcol * 64, c = cs + lane;
+        // (A) the uncovered object pixels of the tile
+        uint16_t raw[4];
+        bool need[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int r = tr0 + wave + 4 * i;
+            raw[i] = 0; need[i] = false;
+            if (r <= tr1 && c <= ec1) {
+                const size_t px = (size_t)r * (size_t)a.W + (size_t)c;
+                raw[i] = depth[px];
+                if (raw[i] != 0 && (float)((double)prob[px] * (1.0 / 10000)) >= a.class_threshold) need[i] = zk[px] == RV_EMPTY;
+            }
+        }
+        if (!__syncthreads_or((need[0] || need[1]) || (need[2] || need[3]))) continue;   // the barrier also ends the previous tile's reads of bits
+        // (B) the bit rows of rows wr0 .. wr1: at most RC_TILE_ROWS + 2 R of them
+        const int wr0 = max(tr0 - R, r0), wr1 = min(tr1 + R, r1);
+        const int n_words = wr1 >= wr0 ? (wr1 - wr0 + 1) * 3 : 0;
+        for (int it = wave; it < n_words; it += 4) {
+            const int row = it / 3, j = it - row * 3;
+            const int col = cs - 64 + 64 * j + lane;
+            bool set = false;
+            if (col >= c0 && col <= c1) set = zk[(size_t)(wr0 + row) * (size_t)a.W + (size_t)col] != RV_EMPTY;
+            const unsigned long long word = __ballot(set);
+            if (lane == 0) bits[row][j] = word;
+        }
+        __syncthreads();
+        // (C) the search, the gate and the rows
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int r = tr0 + wave + 4 * i;
+            int st = 0;
+            if (need[i]) {
+                unsigned long long best = RV_EMPTY;   // d2 << 32 | linear index: the minimum is the contract's nearest pixel
+                const int lo = max(r - R, wr0), hi = min(r + R, wr1);
+                for (int k = 0; k <= R; ++k) {
+                    if ((unsigned long long)(k * k) > (best >> 32)) break;   // no row further away can hold a nearer or an equal pixel
+                    for (int s = 0; s < (k ? 2 : 1); ++s) {
+                        const int rs = s ? r + k : r - k;
+                        if (rs < lo || rs > hi) continue;
+                        int dl, dr;
+                        rc_nearest_in_row(bits[rs - wr0][0], bits[rs - wr0][1], bits[rs - wr0][2], lane, dl, dr);
+                        if (dl <= R) best = min(best, ((unsigned long long)(k * k + dl * dl) << 32) | (unsigned long long)(uint32_t)(rs * a.W + (c - dl)));
+                        if (dr <= R) best = min(best, ((unsigned long long)(k * k + dr * dr) << 32) | (unsigned long long)(uint32_t)(rs * a.W + (c + dr)));
+                    }
+                }
+                st = 1;
+                if (best != RV_EMPTY) {
+                    const int idx = (int)(uint32_t)best, rs = idx / a.W, cs_ = idx - rs * a.W;
+                    const float z = __uint_as_float((uint32_t)(zk[idx] >> 32));
+                    const float xs = ((float)cs_ - a.cx) / a.fx, ys = ((float)rs - a.cy) / a.fy;
+                    const float xu = ((float)c - a.cx) / a.fx, yu = ((float)r - a.cy) / a.fy;
+                    const float d = (float)raw[i] * a.depth_scale;
+                    const float p0 = xs * z, p1 = ys * z, q0 = xu * d, q1 = yu * d;
+                    const float e0 = q0 - p0, e1 = q1 - p1, e2 = d - z;
+                    const float D = e0 * e0 + (e1 * e1 + e2 * e2);
+                    st = 2;
+                    if (!(D > ca.pull_d2)) {
+                        st = 3;
+                        const double px_ = p0, py_ = p1, pz_ = z;
+                        const double rows[3][6] = {{0.0, pz_, -py_, 1.0, 0.0, 0.0}, {-pz_, 0.0, px_, 0.0, 1.0, 0.0}, {py_, -px_, 0.0, 0.0, 0.0, 1.0}};   // [p x e_k, e_k]
+                        const double bk[3] = {(double)e0, (double)e1, (double)e2};
+#pragma unroll
+                        for (int m = 0; m < 3; ++m) {
+                            int q = 0;
+#pragma unroll
+                            for (int ii = 0; ii < 6; ++ii)
+#pragma unroll
+                                for (int jj = ii; jj < 6; ++jj) { v[q] += rows[m][ii] * rows[m][jj]; ++q; }
+#pragma unroll
+                            for (int ii = 0; ii < 6; ++ii) v[21 + ii] += rows[m][ii] * bk[m];
+                            v[28] += bk[m] * bk[m];
+                        }
+                        v[27] += 1.0;
+                    }
+                    if constexpr (Detail::on) det.nearest[(size_t)r * (size_t)a.W + (size_t)c] = idx;
+                }
+                if constexpr (Detail::on) det.state[(size_t)r * (size_t)a.W + (size_t)c] = (uint8_t)st;
+            }
+            n_unreached += __popcll(__ballot(st == 1)); n_beyond += __popcll(__ballot(st == 2)); n_pulled += __popcll(__ballot(st == 3));
+        }
+    }
+    if (__any(v[27] != 0.0)) {
+        for (int o = 32; o > 0; o >>= 1)
+#pragma unroll
+            for (int k = 0; k < RV_SUMS; ++k) v[k] += __shfl_xor(v[k], o, 64);
+    }   // else: no pulled pixel in the wavefront, every sum is 0
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < RV_SUMS; ++k) red[wave][k] = v[k];
+        cnt[wave][RC_UNREACHED] = n_unreached; cnt[wave][RC_BEYOND] = n_beyond; cnt[wave][RC_PULLED] = n_pulled;
+    }
+    __syncthreads();
+    const size_t slot = (size_t)h * (size_t)ca.groups + (size_t)g;
+    if (tid < RV_SUMS) partial[slot * RV_SUMS + tid] = ((red[0][tid] + red[1][tid]) + red[2][tid]) + red[3][tid];
+    if (tid < RV_COUNTS) pcount[slot * RV_COUNTS + tid] = tid < 3 ? ((cnt[0][tid] + cnt[1][tid]) + cnt[2][tid]) + cnt[3][tid] : 0;
+}
+
+struct RcSolveArgs {
+    double w;          // (double) contour_weight; 0: no contour partials are read
+    double pull_d2;    // (double) of the float product the contour kernel compares with
+};
+
+// The damped solve with the contour term: both sets of partials reduced in the same fixed order, the totals M = S + w Sc, v likewise, the
+// cost over the frame's object pixels, then the damped decision and the next trial (rv_damped_decide) on the totals.
+__global__ __launch_bounds__(64) void refine_visible_contour_solve_kernel(float* __restrict__ poses, const double* __restrict__ partial, const int32_t* __restrict__ pcount,
+                                                                          const double* __restrict__ cpartial, const int32_t* __restrict__ cpcount, int groups, int e,
+                                                                          RvDampedArgs da, RcSolveArgs ca, const int32_t* __restrict__ n_object, float* __restrict__ accepted,
+                                                                          RvDampedState* __restrict__ state, int32_t* __restrict__ done,
+                                                                          stocs_refine_visible_contour_result* __restrict__ rec, stocs_refine_visible_trace* __restrict__ trace) {
+    const int h = (int)blockIdx.x, lane = (int)threadIdx.x;
+    if (done[h]) return;   // the same address in every lane: the whole wavefront
+    double acc[RV_SUMS], con[RV_SUMS];
+    int n[RV_COUNTS], nc[RV_COUNTS];
+    rv_reduce_partials(partial, pcount, h, groups, lane, acc, n);
+    if (ca.w != 0.0) rv_reduce_partials(cpartial, cpcount, h, groups, lane, con, nc);
+    else {
+#pragma unroll
+        for (int k = 0; k < RV_SUMS; ++k) con[k] = 0.0;
+#pragma unroll
+        for (int k = 0; k < RV_COUNTS; ++k) nc[k] = 0;
+    }
+    if (lane) return;
+    float* Ph = poses + (size_t)h * 16;
+    float P[16];
+    bool nonzero = false;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) { P[i] = Ph[i]; nonzero = nonzero || P[i] != 0.0f; }
+    if (e == 0 && (!pose_finite(P) || !nonzero)) { done[h] = 1; return; }   // renders nothing: the zero record, the pose as it came
+    stocs_refine_visible_contour_result* R = rec + h;   // zeroed in front of the first evaluation
+    RvDampedState* St = state + h;
+    const int count = (int)acc[27], pulled = nc[RC_PULLED], n_obj = *n_object;
+    const int uncovered = n_obj - ((n[RV_TOO_FAR] + n[RV_GRAZING]) + count);
+    double sys[RV_SUMS];
+#pragma unroll
+    for (int k = 0; k < 27; ++k) sys[k] = acc[k] + ca.w * con[k];
+    sys[27] = acc[27]; sys[28] = acc[28];
+    const bool enough = count + 3 * pulled >= 6;
+    const double C = !enough ? (double)INFINITY
+                             : ((acc[28] + da.max_d2 * (double)n[RV_TOO_FAR]) + ca.w * (con[28] + ca.pull_d2 * (double)(uncovered - pulled))) /
+                                   ((double)(count + n[RV_TOO_FAR]) + ca.w * (double)uncovered);
+    if (e == 0 || C < St->cost) {   // the decision rv_damped_decide makes: the contour fields of the accepted evaluation
+        R->object_px = n_obj; R->uncovered = uncovered; R->unreached = nc[RC_UNREACHED]; R->beyond = nc[RC_BEYOND]; R->pulled = pulled;
+        R->pull_rms = pulled > 0 ? sqrtf((float)(con[28] / (double)pulled)) : 0.0f;
+    }
+    rv_damped_decide(Ph, accepted + (size_t)h * 16, P, &R->damped, St, done + h, trace ? trace + (size_t)h * (size_t)(da.K + 1) : (stocs_refine_visible_trace*)NULL, e,
+                     da, sys, n, count, C, enough);
 }
 
 static const char* params_error(const stocs_refine_visible_params* p) {
@@ -441,15 +685,25 @@ static int visible_work(stocs_ctx* c, int n, size_t chunk, size_t npix, int grou
     return STOCS_OK;
 }
 
-// one evaluation of poses h0 .. h0 + m of the workspace: rectangles cleared, render, accumulate (their key buffers are clear in front
-// and, in the shipping form, behind)
+// the contour pass of an evaluation: its arguments and where the chunk's contour partials go
+struct RcPass { RcArgs ca; double* part; int32_t* cnt; };
+
+// one evaluation of poses h0 .. h0 + m of the workspace: rectangles cleared, render, with cp the contour pass on the keys, accumulate
+// (their key buffers are clear in front and, in the shipping form, behind)
 template <class Detail>
-static int enqueue_evaluate(stocs_ctx* c, const DepthState* F, const VisibleWork& w, int h0, int m, const DepthArgs& a, const RvArgs& ra, Detail det, bool timed) {
+static int enqueue_evaluate(stocs_ctx* c, const DepthState* F, const VisibleWork& w, int h0, int m, const DepthArgs& a, const RvArgs& ra, Detail det, bool timed,
+                            const RcPass* cp = NULL) {
     const float4* verts; const int4* tris;
     mesh_device_arrays(c, &verts, &tris);
     STOCS_HIP_CHECK(hipMemsetAsync(w.box(), 0x80, (size_t)m * VSD_BOX_WORDS * 4, c->stream));
     if (timed) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[0], c->stream));
     { const int rc = mesh_enqueue_tri_keys(c, w.pose() + (size_t)h0 * 16, m, a, w.key(), w.box()); if (rc) return rc; }
+    if (cp) {
+        if (timed) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[4], c->stream));
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(refine_visible_contour_kernel<RcNoDetail>), dim3((unsigned)ra.groups, (unsigned)m), dim3(256), 0, c->stream,
+                           (const unsigned long long*)w.key(), (const int32_t*)w.box(), frame_depth(F), frame_prob(F), a, cp->ca, cp->part, cp->cnt, RcNoDetail());
+        STOCS_HIP_CHECK(hipGetLastError());
+    }
     if (timed) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[1], c->stream));
     hipLaunchKernelGGL(HIP_KERNEL_NAME(refine_visible_accumulate_kernel<Detail>), dim3((unsigned)ra.groups, (unsigned)m), dim3(256), 0, c->stream,
                        (const float*)(w.pose() + (size_t)h0 * 16), verts, tris, w.key(), (const int32_t*)w.box(), frame_depth(F), frame_prob(F), a, ra, w.part(), w.cnt(), det);
@@ -670,5 +924,181 @@ extern "C" int stocs_refine_visible_detail(stocs_ctx* c, const float* pose, cons
     if (keys) STOCS_HIP_CHECK(hipMemcpy(keys, w.key(), npix * 8, hipMemcpyDeviceToHost));
     if (state) STOCS_HIP_CHECK(hipMemcpy(state, det.state, npix, hipMemcpyDeviceToHost));
     STOCS_HIP_CHECK(hipMemcpy(sums29, det.sums29, RV_SUMS * 8, hipMemcpyDeviceToHost));
+    return STOCS_OK;
+}
+
+// ---- the contour form
+namespace stocs {
+
+static const char* contour_params_error(const stocs_refine_visible_contour_params* p) {
+    if (const char* why = damped_params_error(&p->damped)) return why;
+    if (!(p->contour_weight >= 0.0f) || !isfinite(p->contour_weight)) return "contour_weight must be >= 0 and finite";
+    if (p->pull_radius_px < 1 || p->pull_radius_px > RC_MAX_RADIUS) return "pull_radius_px must be in 1 .. 64";
+    if (!(p->pull_distance > 0.0f) || !isfinite(p->pull_distance)) return "pull_distance must be positive and finite";
+    return NULL;
+}
+
+// the checks of both contour entry points behind their own NULL tests: the damped form's, then the class image
+static int contour_check(const char* who, stocs_ctx* c, const stocs_refine_visible_contour_params* p, DepthState** F) {
+    if (const char* why = contour_params_error(p)) { set_error("%s: %s", who, why); return STOCS_ERR_INVALID; }
+    { const int rc = visible_check(who, c, &p->damped.base, F); if (rc) return rc; }
+    if (!frame_prob(*F)) { set_error("%s: the frame has no class image: the object pixels are not defined (stocs_ctx_set_frame)", who); return STOCS_ERR_STATE; }
+    return STOCS_OK;
+}
+
+static RcArgs contour_args(const stocs_refine_visible_contour_params* p, int groups) {
+    RcArgs ca;
+    ca.pull_d2 = p->pull_distance * p->pull_distance; ca.R = p->pull_radius_px; ca.groups = groups;
+    return ca;
+}
+
+}  // namespace stocs
+
+extern "C" void stocs_default_refine_visible_contour_params(stocs_refine_visible_contour_params* p) {
+    if (!p) return;
+    stocs_default_refine_visible_damped_params(&p->damped);
+    p->contour_weight = 1.0f; p->pull_radius_px = 16; p->pull_distance = 0.03f;
+}
+
+extern "C" int stocs_check_refine_visible_contour_params(const stocs_refine_visible_contour_params* p) {
+    if (!p) { set_error("stocs_check_refine_visible_contour_params: NULL parameters"); return STOCS_ERR_INVALID; }
+    if (const char* why = contour_params_error(p)) { set_error("stocs_check_refine_visible_contour_params: %s", why); return STOCS_ERR_INVALID; }
+    return STOCS_OK;
+}
+
+extern "C" int stocs_refine_visible_contour_last_device_ms(const stocs_ctx* c, float* contour_ms) {
+    if (!c) { set_error("stocs_refine_visible_contour_last_device_ms: NULL context"); return STOCS_ERR_INVALID; }
+    const RefineVisibleState* S = ctx_state_if<RefineVisibleState>(c);
+    if (contour_ms) *contour_ms = S ? S->last_contour_ms : -1.0f;
+    return STOCS_OK;
+}
+
+// The damped call's frame with the object count in front, the contour pass inside every evaluation and the contour solve behind it.
+extern "C" int stocs_refine_poses_visible_contour(stocs_ctx* c, const float* poses, int n, const stocs_refine_visible_contour_params* prm, float* pose16_out,
+                                                  stocs_refine_visible_contour_result* out, stocs_refine_visible_trace* trace) {
+    static const char* who = "stocs_refine_poses_visible_contour";
+    if (!c) { set_error("%s: NULL context", who); return STOCS_ERR_INVALID; }
+    if (n < 0) { set_error("%s: n %d < 0", who, n); return STOCS_ERR_INVALID; }
+    if (n == 0) return STOCS_OK;
+    if (!poses || !prm || !pose16_out || !out) { set_error("%s: NULL poses, parameters or results", who); return STOCS_ERR_INVALID; }
+    DepthState* F = NULL;
+    { const int rc = contour_check(who, c, prm, &F); if (rc) return rc; }
+    DeviceGuard dev_guard(c->device);
+    const stocs_refine_visible_damped_params* dp = &prm->damped;
+    const bool dev_clock = c->device_clock != 0, pass = prm->contour_weight != 0.0f;
+    const size_t npix = F->npix, chunk = visible_chunk(n, npix);
+    const int groups = refine_visible_groups(npix), K = dp->base.max_iterations;
+    VisibleWork w;
+    { const int rc = visible_work(c, n, chunk, npix, groups, &w); if (rc) return rc; }
+    RefineVisibleState* S = ctx_state<RefineVisibleState>(c);
+    const size_t rows = (size_t)n * (size_t)(K + 1);
+    Carve cv;   // what comes back lies in front: accepted poses | records | trace
+    const size_t o_acc = cv.take((size_t)n * 64), o_rec = cv.take((size_t)n * sizeof(stocs_refine_visible_contour_result));
+    const size_t o_trace = cv.take(trace ? rows * sizeof(stocs_refine_visible_trace) : 0), back_all = cv.total;
+    const size_t o_state = cv.take((size_t)n * sizeof(RvDampedState)), o_done = cv.take((size_t)n * 4);
+    const size_t o_cpart = cv.take(chunk * (size_t)groups * RV_SUMS * 8), o_ccnt = cv.take(chunk * (size_t)groups * RV_COUNTS * 4), o_nobj = cv.take(4);
+    { const int rc = S->contour.grow(c->stream, cv.total); if (rc) return rc; }
+    char* base = S->contour.p;
+    float* d_acc = Carve::at<float>(base, o_acc);
+    stocs_refine_visible_contour_result* d_rec = Carve::at<stocs_refine_visible_contour_result>(base, o_rec);
+    stocs_refine_visible_trace* d_trace = trace ? Carve::at<stocs_refine_visible_trace>(base, o_trace) : NULL;
+    RvDampedState* d_state = Carve::at<RvDampedState>(base, o_state);
+    int32_t* d_done = Carve::at<int32_t>(base, o_done);
+    int32_t* d_nobj = Carve::at<int32_t>(base, o_nobj);
+    const size_t back_bytes = trace ? o_trace + rows * sizeof(stocs_refine_visible_trace) : o_rec + (size_t)n * sizeof(stocs_refine_visible_contour_result);
+    char* hin; char* hback;
+    { const int rc = pinned_for(c, (size_t)n * 64, back_bytes, &hin, &hback); if (rc) return rc; }
+    memcpy(hin, poses, (size_t)n * 64);
+    STOCS_HIP_CHECK(hipMemcpyAsync(w.pose(), hin, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));   // the slot the render reads
+    STOCS_HIP_CHECK(hipMemcpyAsync(d_acc, hin, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));      // the accepted pose: the start
+    STOCS_HIP_CHECK(hipMemsetAsync(base + o_rec, 0, back_all - o_rec, c->stream));                      // records and trace
+    STOCS_HIP_CHECK(hipMemsetAsync(d_done, 0, (size_t)n * 4, c->stream));
+    STOCS_HIP_CHECK(hipMemsetAsync(d_nobj, 0, 4, c->stream));
+    const DepthArgs a = frame_args(F, 0.0f, dp->base.class_threshold);
+    const RvArgs ra = visible_args(&dp->base, groups);
+    hipLaunchKernelGGL(refine_visible_object_count_kernel, dim3((unsigned)std::min<size_t>((npix + 255) / 256, 1024)), dim3(256), 0, c->stream, frame_depth(F), frame_prob(F),
+                       npix, a.class_threshold, d_nobj);
+    STOCS_HIP_CHECK(hipGetLastError());
+    RvDampedArgs da;
+    da.max_d2 = (double)ra.max_d2; da.lambda0 = (double)dp->lambda0; da.down = (double)dp->lambda_down; da.up = (double)dp->lambda_up;
+    da.max_rot = (double)dp->max_step_rotation; da.max_trans = (double)dp->max_step_translation;
+    for (int k = 0; k < 3; ++k) da.pm[k] = (double)dp->pivot_model[k];
+    da.pivot = dp->pivot; da.K = K;
+    RcPass cp;
+    cp.ca = contour_args(prm, groups); cp.part = Carve::at<double>(base, o_cpart); cp.cnt = Carve::at<int32_t>(base, o_ccnt);
+    RcSolveArgs sa;
+    sa.w = (double)prm->contour_weight; sa.pull_d2 = (double)cp.ca.pull_d2;
+    for (int h0 = 0; h0 < n; h0 += (int)chunk) {   // all evaluations of a chunk before the next one starts
+        const int m = std::min((int)chunk, n - h0);
+        STOCS_HIP_CHECK(hipMemsetAsync(w.key(), 0xFF, (size_t)m * npix * 8, c->stream));
+        for (int e = 0; e <= K; ++e) {
+            const bool timed = dev_clock && h0 + m == n && e == K;
+            { const int rc = enqueue_evaluate(c, F, w, h0, m, a, ra, RvNoDetail(), timed, pass ? &cp : (const RcPass*)NULL); if (rc) return rc; }
+            hipLaunchKernelGGL(refine_visible_contour_solve_kernel, dim3((unsigned)m), dim3(64), 0, c->stream, w.pose() + (size_t)h0 * 16, (const double*)w.part(),
+                               (const int32_t*)w.cnt(), (const double*)cp.part, (const int32_t*)cp.cnt, groups, e, da, sa, (const int32_t*)d_nobj, d_acc + (size_t)h0 * 16,
+                               d_state + h0, d_done + h0, d_rec + h0, d_trace ? d_trace + (size_t)h0 * (size_t)(K + 1) : (stocs_refine_visible_trace*)NULL);
+            STOCS_HIP_CHECK(hipGetLastError());
+            if (timed) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[3], c->stream));
+        }
+    }
+    STOCS_HIP_CHECK(hipMemcpyAsync(hback, base, back_bytes, hipMemcpyDeviceToHost, c->stream));
+    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    S->last_ms[0] = S->last_ms[1] = S->last_ms[2] = S->last_contour_ms = -1.0f;
+    if (dev_clock) {   // with the pass the render ends where the contour kernel starts
+        float ms = 0.0f;
+        if (hipEventElapsedTime(&ms, c->ev_t[0], c->ev_t[pass ? 4 : 1]) == hipSuccess) S->last_ms[0] = ms;
+        if (pass && hipEventElapsedTime(&ms, c->ev_t[4], c->ev_t[1]) == hipSuccess) S->last_contour_ms = ms;
+        for (int k = 1; k < 3; ++k)
+            if (hipEventElapsedTime(&ms, c->ev_t[k], c->ev_t[k + 1]) == hipSuccess) S->last_ms[k] = ms;
+    }
+    memcpy(pose16_out, hback + o_acc, (size_t)n * 64);
+    memcpy(out, hback + o_rec, (size_t)n * sizeof(stocs_refine_visible_contour_result));
+    if (trace) memcpy(trace, hback + o_trace, rows * sizeof(stocs_refine_visible_trace));
+    return STOCS_OK;
+}
+
+// A plain, synchronous path (a test and diagnosis facility): ONE pose, pageable copies, the render and the contour pass of ONE evaluation;
+// the state and the nearest silhouette pixel per pixel, the 29 contour sums as the solve step forms them.
+extern "C" int stocs_refine_visible_contour_detail(stocs_ctx* c, const float* pose, const stocs_refine_visible_contour_params* prm, uint8_t* state, int32_t* nearest,
+                                                   double* sums29) {
+    static const char* who = "stocs_refine_visible_contour_detail";
+    if (!c) { set_error("%s: NULL context", who); return STOCS_ERR_INVALID; }
+    if (!pose || !prm || !sums29) { set_error("%s: NULL pose, parameters or sums", who); return STOCS_ERR_INVALID; }
+    DepthState* F = NULL;
+    { const int rc = contour_check(who, c, prm, &F); if (rc) return rc; }
+    DeviceGuard dev_guard(c->device);
+    const size_t npix = F->npix;
+    const int groups = refine_visible_groups(npix);
+    VisibleWork w;
+    { const int rc = visible_work(c, 1, 1, npix, groups, &w); if (rc) return rc; }
+    RefineVisibleState* S = ctx_state<RefineVisibleState>(c);
+    Carve cv;
+    const size_t o_near = cv.take(npix * 4), o_state = cv.take(npix), o_sums = cv.take(RV_SUMS * 8);
+    const size_t o_cpart = cv.take((size_t)groups * RV_SUMS * 8), o_ccnt = cv.take((size_t)groups * RV_COUNTS * 4);
+    { const int rc = S->contour.grow(c->stream, cv.total); if (rc) return rc; }
+    char* base = S->contour.p;
+    RcDetailOut det;
+    det.state = Carve::at<uint8_t>(base, o_state); det.nearest = Carve::at<int32_t>(base, o_near);
+    RvDetailOut sums;
+    sums.state = NULL; sums.sums29 = Carve::at<double>(base, o_sums);
+    double* cpart = Carve::at<double>(base, o_cpart);
+    int32_t* ccnt = Carve::at<int32_t>(base, o_ccnt);
+    STOCS_HIP_CHECK(hipMemcpyAsync(w.pose(), pose, 64, hipMemcpyHostToDevice, c->stream));
+    STOCS_HIP_CHECK(hipMemsetAsync(w.key(), 0xFF, npix * 8, c->stream));
+    STOCS_HIP_CHECK(hipMemsetAsync(det.state, 0, npix, c->stream));
+    STOCS_HIP_CHECK(hipMemsetAsync(det.nearest, 0xFF, npix * 4, c->stream));
+    STOCS_HIP_CHECK(hipMemsetAsync(w.box(), 0x80, VSD_BOX_WORDS * 4, c->stream));
+    const DepthArgs a = frame_args(F, 0.0f, prm->damped.base.class_threshold);
+    { const int rc = mesh_enqueue_tri_keys(c, w.pose(), 1, a, w.key(), w.box()); if (rc) return rc; }
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(refine_visible_contour_kernel<RcDetailOut>), dim3((unsigned)groups, 1), dim3(256), 0, c->stream, (const unsigned long long*)w.key(),
+                       (const int32_t*)w.box(), frame_depth(F), frame_prob(F), a, contour_args(prm, groups), cpart, ccnt, det);
+    STOCS_HIP_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(refine_visible_solve_kernel<RvDetailOut>, dim3(1), dim3(64), 0, c->stream, w.pose(), (const double*)cpart, (const int32_t*)ccnt, groups, 0,
+                       w.frozen(), w.rec(), sums);
+    STOCS_HIP_CHECK(hipGetLastError());
+    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (state) STOCS_HIP_CHECK(hipMemcpy(state, det.state, npix, hipMemcpyDeviceToHost));
+    if (nearest) STOCS_HIP_CHECK(hipMemcpy(nearest, det.nearest, npix * 4, hipMemcpyDeviceToHost));
+    STOCS_HIP_CHECK(hipMemcpy(sums29, sums.sums29, RV_SUMS * 8, hipMemcpyDeviceToHost));
     return STOCS_OK;
 }

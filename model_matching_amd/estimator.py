@@ -63,6 +63,9 @@ _REFINE_VISIBLE_DTYPE = np.dtype([(f[0], np.float32 if f[0] == "rms" else np.int
 assert _REFINE_VISIBLE_DTYPE.itemsize == C.sizeof(capi.RefineVisibleResult)
 _REFINE_VISIBLE_DAMPED_DTYPE = np.dtype(_REFINE_VISIBLE_DTYPE.descr + [("evaluations", np.int32), ("rejected", np.int32), ("cost", np.float32), ("lambda", np.float32)])
 assert _REFINE_VISIBLE_DAMPED_DTYPE.itemsize == C.sizeof(capi.RefineVisibleDampedResult)
+_REFINE_VISIBLE_CONTOUR_DTYPE = np.dtype(_REFINE_VISIBLE_DAMPED_DTYPE.descr + [(k, np.int32) for k in ("object_px", "uncovered", "unreached", "beyond", "pulled")] +
+                                         [("pull_rms", np.float32)])
+assert _REFINE_VISIBLE_CONTOUR_DTYPE.itemsize == C.sizeof(capi.RefineVisibleContourResult)
 _REFINE_VISIBLE_TRACE_DTYPE = np.dtype([("pose", np.float32, 16), ("cost", np.float64), ("lambda", np.float64), ("accepted", np.int32), ("state", np.int32)])
 assert _REFINE_VISIBLE_TRACE_DTYPE.itemsize == C.sizeof(capi.RefineVisibleTrace)
 _SCENE_RECORD_DTYPE = np.dtype([(f[0], np.int32) for f in capi.SceneRecord._fields_])
@@ -845,6 +848,67 @@ class StocsEstimator:
         if not trace:
             return out, rec
         return out, rec, np.frombuffer(tr, dtype=_REFINE_VISIBLE_TRACE_DTYPE, count=n * rows).copy().reshape(n, rows)
+
+    def _refine_visible_contour_params(self, who, params):
+        prm = capi.RefineVisibleContourParams()
+        self.L.stocs_default_refine_visible_contour_params(C.byref(prm))
+        params = dict(params)
+        pm = np.asarray(params.pop("pivot_model", getattr(self, "_mesh_centre", (0.0, 0.0, 0.0))), np.float32).reshape(-1)
+        if pm.size != 3:
+            raise ValueError("%s: pivot_model is 3 floats" % who)
+        prm.damped.pivot_model[:] = [float(x) for x in pm]
+        for k, v in params.items():
+            if k in dict(capi.RefineVisibleParams._fields_):
+                setattr(prm.damped.base, k, v)
+            elif k in dict(capi.RefineVisibleDampedParams._fields_) and k != "base":
+                setattr(prm.damped, k, v)
+            elif k in dict(capi.RefineVisibleContourParams._fields_) and k != "damped":
+                setattr(prm, k, v)
+            else:
+                raise TypeError("%s: unknown parameter %r" % (who, k))
+        return prm
+
+    def refine_poses_visible_contour(self, poses16, trace=False, **params):
+        """refine_poses_visible_damped with the contour term: the frame's object pixels (class image) that a pose's render leaves uncovered
+        pull it towards them (stocs_refine_poses_visible_contour) -> (poses (n, 16) float32, records), or (poses, records, trace) with
+        trace=True: records a structured array with the fields of stocs_refine_visible_contour_result (the damped record of the RETURNED
+        pose, object_px, uncovered, unreached, beyond, pulled, pull_rms).  params: the damped form's and contour_weight, pull_radius_px,
+        pull_distance over the library's defaults; the frame of set_frame must carry a class image."""
+        P, pP = capi.f32(poses16)
+        if P.size % 16:
+            raise ValueError("refine_poses_visible_contour: poses are 16 floats each")
+        n = P.size // 16
+        prm = self._refine_visible_contour_params("refine_poses_visible_contour", params)
+        out = np.zeros((n, 16), np.float32)
+        buf = (capi.RefineVisibleContourResult * max(n, 1))()
+        rows = max(prm.damped.base.max_iterations, 0) + 1
+        tr = (capi.RefineVisibleTrace * max(n * rows, 1))() if trace else None
+        capi.check(self.L.stocs_refine_poses_visible_contour(self.h, pP, n, C.byref(prm), out.ctypes.data_as(capi._fp), buf, tr))
+        rec = np.frombuffer(buf, dtype=_REFINE_VISIBLE_CONTOUR_DTYPE, count=n).copy()
+        if not trace:
+            return out, rec
+        return out, rec, np.frombuffer(tr, dtype=_REFINE_VISIBLE_TRACE_DTYPE, count=n * rows).copy().reshape(n, rows)
+
+    def refine_visible_contour_detail(self, pose16, **params):
+        """The contour pass of one evaluation of one pose (stocs_refine_visible_contour_detail) -> (state (height, width) uint8: 1
+        unreached, 2 beyond, 3 pulled, 0 everything else; nearest (height, width) int32: the linear index of the nearest silhouette
+        pixel, -1 where there is none; the 29 contour sums float64)"""
+        P, pP = capi.f32(pose16)
+        if P.size != 16:
+            raise ValueError("refine_visible_contour_detail: one pose of 16 floats")
+        prm = self._refine_visible_contour_params("refine_visible_contour_detail", params)
+        H, W = self._frame_shape("refine_visible_contour_detail")
+        st = np.zeros((H, W), np.uint8); near = np.zeros((H, W), np.int32); sums = np.zeros(29, np.float64)
+        capi.check(self.L.stocs_refine_visible_contour_detail(self.h, pP, C.byref(prm), st.ctypes.data_as(capi._u8p), near.ctypes.data_as(capi._ip),
+                                                              sums.ctypes.data_as(C.POINTER(C.c_double))))
+        return st, near, sums
+
+    def refine_visible_contour_last_device_ms(self):
+        """HIP-event ms of the contour kernel of the last evaluation of the last refine_poses_visible_contour call with the option
+        device_clock on; -1: not taken"""
+        a = C.c_float(-1)
+        capi.check(self.L.stocs_refine_visible_contour_last_device_ms(self.h, C.byref(a)))
+        return a.value
 
     def refine_visible_detail(self, pose16, **params):
         """One evaluation of one pose as refine_poses_visible makes it (stocs_refine_visible_detail) -> (keys (height, width) uint64:

@@ -16,6 +16,12 @@ vertices, K = 5 and K = 10; add_damped_5/10 or corner_error_damped_5/10, accepte
 below the row's error before, and for a row where it is not the trace of its worst hypothesis; written to
 profiles/refine_visible_damped_quality.json.
 
+--contour: the 18 Cm rows and the box rows with the analytic (Cm) or the mesh's own (box) silhouette as the class image, plus lateral-offset
+rows (the start displaced across the rays by 0.5, 1 and 1.5 object widths, in evenly spaced image directions): the error before, after
+stocs_refine_poses_visible_damped and after stocs_refine_poses_visible_contour at contour_weight 0.25, 1 and 4 from the same starts (K = 10,
+max_distance 0.02, otherwise the library's defaults), and for the lateral rows also a wide form (pull_radius_px 64, pull_distance two
+widths); written to profiles/refine_visible_contour_quality.json.
+
 Needs a GPU; no fallback."""
 import argparse
 import json
@@ -79,12 +85,121 @@ def damped_columns(est, poses, error, key, before):
     return cols
 
 
+CONTOUR_WEIGHTS = (0.25, 1.0, 4.0)
+LATERAL = (0.5, 1.0, 1.5)       # object widths across the rays
+
+
+def contour_columns(est, poses, error, key, wide=None):
+    """damped and contour (w = 0.25, 1, 4; with `wide` also pull_radius_px 64 and that pull_distance) from the same starts -> the row's columns"""
+    cols = {key + "_before": summary(error(poses))}
+    P, rec = est.refine_poses_visible_damped(poses, max_iterations=10, max_distance=0.02)
+    cols[key + "_damped"] = summary(error(P))
+    cols["damped_frozen"] = int(rec["frozen"].sum())
+    forms = [("contour_w%g" % w, dict(contour_weight=w)) for w in CONTOUR_WEIGHTS]
+    if wide is not None:
+        forms += [("contour_w%g_R64_wide" % w, dict(contour_weight=w, pull_radius_px=64, pull_distance=wide)) for w in CONTOUR_WEIGHTS]
+    for name, prm in forms:
+        P, rec = est.refine_poses_visible_contour(poses, max_iterations=10, max_distance=0.02, **prm)
+        cols["%s_%s" % (key, name)] = summary(error(P))
+        cols[name + "_frozen"] = int(rec["frozen"].sum())
+        cols[name + "_mean_accepted"] = float(rec["iterations"].mean())
+        cols[name + "_mean_pulled"] = float(rec["pulled"].mean())
+        cols[name + "_mean_uncovered"] = float(rec["uncovered"].mean())
+    return cols
+
+
+def lateral_starts(T, width_m, factor, n):
+    """n starts: T displaced by factor * width_m in the camera's x-y plane, in evenly spaced directions"""
+    out = []
+    for i in range(n):
+        a = 2 * np.pi * (i + 0.5) / n
+        S = np.asarray(T, np.float64).copy()
+        S[:3, 3] += factor * width_m * np.array([np.cos(a), np.sin(a), 0.0])
+        out.append(pose16(S))
+    return np.stack(out)
+
+
+def main_contour(args):
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("refine_visible_quality.py needs a GPU: nothing is measured without one")
+    from model_matching_amd import synth
+    from model_matching_amd.estimator import StocsEstimator, ingest_scene
+    K = [float(v) for v in synth.YCB_INTRINSICS]
+    m = synth.make_model(5000)
+    T = synth.gt_pose()
+    gt16 = pose16(T)
+    za = vc.cm_analytic_depth(T, vc.cm_ellipsoid_centre(m.pos), K, W, H)
+    rng = np.random.default_rng(17)
+    raws, sil = frames(za, rng)
+    prob = np.where(sil, 10000, 0).astype(np.uint16)
+    v, t = synth.make_model_mesh(5)
+    sp, sn, spr, spx = ingest_scene(raws["clean"], prob, K, SCALE)
+    est = StocsEstimator(sp, sn, spr, spx, m.pos, m.nrm, build_index=False)
+    est.set_mesh(v, t)
+    add = lambda P: est.pose_errors(P, gt16)["add"]
+    cols_of = np.flatnonzero(sil.any(axis=0))
+    width = float((cols_of[-1] - cols_of[0] + 1) * T[2, 3] / K[0])
+    rows = []
+    for name, raw in raws.items():
+        est.set_frame(raw, prob, K, SCALE)
+        for li, (max_t, max_deg) in enumerate(LEVELS):
+            poses = np.stack([pose16(x) for x in perturbed(T, args.samples, 1000 + li, max_t=max_t, max_deg=max_deg)])
+            row = {"frame": name, "max_translation_mm": max_t * 1e3, "max_rotation_deg": max_deg, "samples": args.samples}
+            row.update(contour_columns(est, poses, add, "add"))
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    est.set_frame(raws["clean"], prob, K, SCALE)
+    for f in LATERAL:
+        row = {"frame": "clean", "lateral_offset_widths": f, "object_width_mm": width * 1e3, "samples": args.samples}
+        row.update(contour_columns(est, lateral_starts(T, width, f, args.samples), add, "add", wide=2 * width))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    bv, bt, bP = box_mesh_and_pose()
+    est.set_mesh(bv, bt)
+    est.set_frame(np.zeros((H, W), np.uint16), None, K, SCALE)
+    zb = est.render_depth_mesh(pose16(bP))[0].astype(np.float64)
+    bprob = np.where(zb > 0, 10000, 0).astype(np.uint16)
+    corner = lambda P: [rvref.vertex_error(p, pose16(bP), bv) for p in P]
+    bcols = np.flatnonzero((zb > 0).any(axis=0))
+    bwidth = float((bcols[-1] - bcols[0] + 1) * bP[2, 3] / K[0])
+    for name, zimg in (("box clean", np.where(zb > 0, zb, WALL)), ("box noise_1mm", np.where(zb > 0, zb, WALL) + rng.normal(0, 0.001, zb.shape))):
+        est.set_frame(vc.raw_from_depth(zimg, SCALE), bprob, K, SCALE)
+        for li, (max_t, max_deg) in enumerate(LEVELS):
+            poses = np.stack([pose16(x) for x in perturbed(bP, args.samples, 2000 + li, max_t=max_t, max_deg=max_deg)])
+            row = {"frame": name, "max_translation_mm": max_t * 1e3, "max_rotation_deg": max_deg, "samples": args.samples}
+            row.update(contour_columns(est, poses, corner, "corner_error"))
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        if name == "box clean":
+            for f in LATERAL:
+                row = {"frame": name, "lateral_offset_widths": f, "object_width_mm": bwidth * 1e3, "samples": args.samples}
+                row.update(contour_columns(est, lateral_starts(bP, bwidth, f, args.samples), corner, "corner_error", wide=2 * bwidth))
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+    est.close()
+    out = {"what": "ADD (Cm rows) or largest corner distance (box rows) of perturbed and of laterally displaced ground-truth poses before, after "
+                   "stocs_refine_poses_visible_damped and after stocs_refine_poses_visible_contour at three weights from the same starts; K = 10, max_distance 0.02, "
+                   "the class image is the object's true silhouette; synthetic frames only",
+           "device": torch.cuda.get_device_name(0), "frame": [W, H], "depth_unit_mm": SCALE * 1e3, "triangles": int(len(t)), "rows": rows}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "refine_visible_quality.json"))
     ap.add_argument("--samples", type=int, default=16)
     ap.add_argument("--damped", action="store_true")
+    ap.add_argument("--contour", action="store_true")
     args = ap.parse_args()
+    if args.contour:
+        if args.out == ap.get_default("out"):
+            args.out = os.path.join(ROOT, "profiles", "refine_visible_contour_quality.json")
+        return main_contour(args)
     if args.damped and args.out == ap.get_default("out"):
         args.out = os.path.join(ROOT, "profiles", "refine_visible_damped_quality.json")
     import torch

@@ -14,6 +14,11 @@ at 1, 64 and 256 hypotheses, in one visit and alternating call by call (plain, d
 the plain form's per iteration, with the A/A spread of the two plain series as the margin; written to
 profiles/refine_visible_damped_time.json.  Measurement only, no bar.
 
+--contour: StocsEstimator.refine_poses_visible_contour (K = 5) against the damped call on the same workloads, the frame with the mesh's
+own silhouette as its class image, at 1, 64 and 256 hypotheses and pull_radius_px 16 and 64, alternating damped, contour, damped over 30
+rounds: the ratio per evaluation with the A/A spread of the two damped series, and the HIP-event time of the contour kernel next to the
+accumulation's; written to profiles/refine_visible_contour_time.json.  Measurement only, no bar.
+
 Needs a GPU; no fallback."""
 import time
 import argparse
@@ -135,13 +140,79 @@ def main_damped(args):
     print("wrote", args.out)
 
 
+def contour_rows(est, label, v, t, P0, K):
+    """damped (A), contour, damped (A') alternating on one workload, per pull radius"""
+    from mesh_time import SCALE
+    rows = []
+    est.set_mesh(v, t)
+    est.set_frame(np.zeros((480, 640), np.uint16), None, K, SCALE)
+    z = est.render_depth_mesh(pose16(P0))[0]
+    est.set_frame(np.rint(np.where(z > 0, z, 1.5) / SCALE).astype(np.uint16), np.where(z > 0, 10000, 0).astype(np.uint16), K, SCALE)
+    for n in DAMPED_SIZES:
+        poses = np.stack([pose16(T) for T in perturbed(np.asarray(P0, np.float64), n, 100 + n)])
+        damped = lambda: est.refine_poses_visible_damped(poses, max_iterations=ITERATIONS)
+        for R in (16, 64):
+            contour = lambda: est.refine_poses_visible_contour(poses, max_iterations=ITERATIONS, pull_radius_px=R)
+            out, rec = contour()
+            a, c, a2 = alternating([damped, contour, damped])
+            per_a = [np.median(a) / (ITERATIONS + 1), np.median(a2) / (ITERATIONS + 1)]
+            per_c = np.median(c) / (ITERATIONS + 1)
+            est.set_option("device_clock", 1)
+            dev = []
+            for i in range(WARM + REPS):
+                contour()
+                if i >= WARM:
+                    dev.append(est.refine_visible_last_device_ms() + (est.refine_visible_contour_last_device_ms(),))
+            est.set_option("device_clock", 0)
+            render_ms, acc_ms, solve_ms, contour_ms = [float(x) for x in np.median(np.asarray(dev), axis=0)]
+            row = {"workload": label, "triangles": int(len(t)), "frame_share": round(float((z > 0).mean()), 3), "hypotheses": n, "evaluations": ITERATIONS + 1,
+                   "pull_radius_px": R, "damped_a": stats(a), "contour": stats(c), "damped_a2": stats(a2), "damped_ms_per_evaluation": [float(x) for x in per_a],
+                   "contour_ms_per_evaluation": float(per_c), "ratio_contour_over_damped": float(per_c / np.mean(per_a)),
+                   "aa_spread": float(abs(per_a[0] - per_a[1]) / np.mean(per_a)), "render_kernel_ms": render_ms, "contour_kernel_ms": contour_ms,
+                   "accumulate_kernel_ms": acc_ms, "solve_kernel_ms": solve_ms, "mean_uncovered": float(rec["uncovered"].mean()), "mean_pulled": float(rec["pulled"].mean()),
+                   "mean_accepted": float(rec["iterations"].mean()), "mean_rejected": float(rec["rejected"].mean())}
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+    return rows
+
+
+def main_contour(args):
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("refine_visible_time.py needs a GPU: no time is taken without one")
+    from model_matching_amd import synth
+    from model_matching_amd.estimator import StocsEstimator
+    K = [float(v) for v in synth.YCB_INTRINSICS]
+    m, s, _ = synth.workload("Cm")
+    est = StocsEstimator(s.pos, s.nrm, s.prob, s.pixel, m.pos, m.nrm, build_index=False)
+    bv, bt, bP = box_mesh_and_pose()
+    rows = []
+    for label, v, t, P0 in (("Cm level 4", *synth.make_model_mesh(4), s.T_gt), ("Cm level 5", *synth.make_model_mesh(5), s.T_gt), ("box 12 triangles", bv, bt, bP)):
+        rows += contour_rows(est, label, v, t, P0, K)
+    est.close()
+    out = {"what": "host wall clock of refine_poses_visible_contour (K = 5, six evaluations, the library's defaults but the radius) per evaluation against "
+                   "refine_poses_visible_damped, alternating damped, contour, damped in one visit; aa_spread is the relative difference of the two damped series, the "
+                   "margin of the ratio; kernel columns: median HIP-event time of the last evaluation of a contour call; no bar",
+           "device": torch.cuda.get_device_name(0), "reps": DAMPED_REPS, "warmup": WARM, "note": "one visit, one GPU; the host column shares the machine with other work",
+           "kernel_resources": "profiles/refine_visible_contour.md (tools/kernel_resources.py refine_visible.hip)", "rows": rows}
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--damped", action="store_true")
+    ap.add_argument("--contour", action="store_true")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "refine_visible_damped_time.json" if args.damped else "refine_visible_time.json")
+        args.out = os.path.join(ROOT, "profiles", "refine_visible_contour_time.json" if args.contour else "refine_visible_damped_time.json" if args.damped
+                                else "refine_visible_time.json")
+    if args.contour:
+        return main_contour(args)
     if args.damped:
         return main_damped(args)
     import torch
