@@ -961,6 +961,30 @@ public:
         return r;
     }
 
+private:
+    // What the three refine_poses_visible* methods share: the poses marshalled to 16 floats each, call(P, n, Q, records, trace rows or
+    // NULL), on failure the log line and everything empty, else the `refined` copy.  K: max_iterations, for the trace's K + 1 rows a pose.
+    template <class Record, class Call>
+    std::vector<Record> refine_visible_with(const char* name, const std::vector<PoseCandidate*>& poses, std::vector<MatrixType>* refined,
+                                            std::vector<stocs_refine_visible_trace>* trace, int K, Call call) {
+        const int n = (int)poses.size();
+        std::vector<float> P((size_t)n * 16), Q((size_t)n * 16);
+        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], poses[(size_t)i]->transform.data(), 64);
+        std::vector<Record> r((size_t)n);
+        if (refined) refined->assign((size_t)n, MatrixType());
+        if (trace) trace->assign((size_t)n * (size_t)(K > 0 ? K + 1 : 1), stocs_refine_visible_trace());
+        if (n > 0 && call(P.data(), n, Q.data(), r.data(), trace ? trace->data() : NULL) != STOCS_OK) {
+            *log_ << name << " failed: " << stocs_last_error() << std::endl;
+            r.clear();
+            if (refined) refined->clear();
+            if (trace) trace->clear();
+            return r;
+        }
+        for (int i = 0; refined && i < n; ++i) std::memcpy((*refined)[(size_t)i].data(), &Q[(size_t)i * 16], 64);
+        return r;
+    }
+
+public:
     // Refinement on the visible surface (stocs_refine_poses_visible; no reference counterpart): the camera-frame poses refined against the
     // frame of set_frame on the surface of the mesh of set_mesh that each pose shows, projective point-to-plane on every depth pixel under
     // the rendered silhouette.  One record per pose in input order, describing the last evaluation; `refined` (when given) receives the
@@ -973,19 +997,8 @@ public:
     }
     std::vector<stocs_refine_visible_result> refine_poses_visible(const std::vector<PoseCandidate*>& poses, std::vector<MatrixType>* refined = NULL,
                                                                   const stocs_refine_visible_params& prm = default_refine_visible_params()) {
-        const int n = (int)poses.size();
-        std::vector<float> P((size_t)n * 16), Q((size_t)n * 16);
-        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], poses[(size_t)i]->transform.data(), 64);
-        std::vector<stocs_refine_visible_result> r((size_t)n);
-        if (refined) refined->assign((size_t)n, MatrixType());
-        if (n > 0 && stocs_refine_poses_visible(ctx_, P.data(), n, &prm, Q.data(), r.data()) != STOCS_OK) {
-            *log_ << "refine_poses_visible failed: " << stocs_last_error() << std::endl;
-            r.clear();
-            if (refined) refined->clear();
-            return r;
-        }
-        for (int i = 0; refined && i < n; ++i) std::memcpy((*refined)[(size_t)i].data(), &Q[(size_t)i * 16], 64);
-        return r;
+        return refine_visible_with<stocs_refine_visible_result>("refine_poses_visible", poses, refined, NULL, 0,
+            [&](const float* P, int n, float* Q, stocs_refine_visible_result* r, stocs_refine_visible_trace*) { return stocs_refine_poses_visible(ctx_, P, n, &prm, Q, r); });
     }
 
     // Damped refinement on the visible surface (stocs_refine_poses_visible_damped; no reference counterpart): refine_poses_visible with
@@ -1000,21 +1013,8 @@ public:
     std::vector<stocs_refine_visible_damped_result> refine_poses_visible_damped(const std::vector<PoseCandidate*>& poses, std::vector<MatrixType>* refined = NULL,
                                                                                 const stocs_refine_visible_damped_params& prm = default_refine_visible_damped_params(),
                                                                                 std::vector<stocs_refine_visible_trace>* trace = NULL) {
-        const int n = (int)poses.size();
-        std::vector<float> P((size_t)n * 16), Q((size_t)n * 16);
-        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], poses[(size_t)i]->transform.data(), 64);
-        std::vector<stocs_refine_visible_damped_result> r((size_t)n);
-        if (refined) refined->assign((size_t)n, MatrixType());
-        if (trace) trace->assign((size_t)n * (size_t)(prm.base.max_iterations > 0 ? prm.base.max_iterations + 1 : 1), stocs_refine_visible_trace());
-        if (n > 0 && stocs_refine_poses_visible_damped(ctx_, P.data(), n, &prm, Q.data(), r.data(), trace ? trace->data() : NULL) != STOCS_OK) {
-            *log_ << "refine_poses_visible_damped failed: " << stocs_last_error() << std::endl;
-            r.clear();
-            if (refined) refined->clear();
-            if (trace) trace->clear();
-            return r;
-        }
-        for (int i = 0; refined && i < n; ++i) std::memcpy((*refined)[(size_t)i].data(), &Q[(size_t)i * 16], 64);
-        return r;
+        return refine_visible_with<stocs_refine_visible_damped_result>("refine_poses_visible_damped", poses, refined, trace, prm.base.max_iterations,
+            [&](const float* P, int n, float* Q, stocs_refine_visible_damped_result* r, stocs_refine_visible_trace* t) { return stocs_refine_poses_visible_damped(ctx_, P, n, &prm, Q, r, t); });
     }
 
     // Damped refinement with the contour term (stocs_refine_poses_visible_contour; no reference counterpart): refine_poses_visible_damped
@@ -1030,21 +1030,8 @@ public:
     std::vector<stocs_refine_visible_contour_result> refine_poses_visible_contour(const std::vector<PoseCandidate*>& poses, std::vector<MatrixType>* refined = NULL,
                                                                                   const stocs_refine_visible_contour_params& prm = default_refine_visible_contour_params(),
                                                                                   std::vector<stocs_refine_visible_trace>* trace = NULL) {
-        const int n = (int)poses.size(), K = prm.damped.base.max_iterations;
-        std::vector<float> P((size_t)n * 16), Q((size_t)n * 16);
-        for (int i = 0; i < n; ++i) std::memcpy(&P[(size_t)i * 16], poses[(size_t)i]->transform.data(), 64);
-        std::vector<stocs_refine_visible_contour_result> r((size_t)n);
-        if (refined) refined->assign((size_t)n, MatrixType());
-        if (trace) trace->assign((size_t)n * (size_t)(K > 0 ? K + 1 : 1), stocs_refine_visible_trace());
-        if (n > 0 && stocs_refine_poses_visible_contour(ctx_, P.data(), n, &prm, Q.data(), r.data(), trace ? trace->data() : NULL) != STOCS_OK) {
-            *log_ << "refine_poses_visible_contour failed: " << stocs_last_error() << std::endl;
-            r.clear();
-            if (refined) refined->clear();
-            if (trace) trace->clear();
-            return r;
-        }
-        for (int i = 0; refined && i < n; ++i) std::memcpy((*refined)[(size_t)i].data(), &Q[(size_t)i * 16], 64);
-        return r;
+        return refine_visible_with<stocs_refine_visible_contour_result>("refine_poses_visible_contour", poses, refined, trace, prm.damped.base.max_iterations,
+            [&](const float* P, int n, float* Q, stocs_refine_visible_contour_result* r, stocs_refine_visible_trace* t) { return stocs_refine_poses_visible_contour(ctx_, P, n, &prm, Q, r, t); });
     }
 
     // Multi-instance selection (stocs_select_instances; no reference counterpart): which of the camera-frame hypotheses (the

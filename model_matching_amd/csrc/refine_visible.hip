@@ -22,21 +22,21 @@
 // and of the chunk.  The detail form (a compile-time argument, as in refine.hip) stops after the sums, writes the per-pixel state and
 // leaves the keys in place for the read-back.
 // The damped form (stocs_refine_poses_visible_damped; tests/refine_visible_damped_ref.py) runs the same render and the same
-// accumulation K + 1 times and puts another kernel in the solve's place:
-//   damped solve  one wavefront per hypothesis: the solve's reduction (rv_reduce_partials), then lane 0 in double: the cost of the
-//               evaluation, accept or reject against the pose's accepted state (pose, 29 sums, cost, lambda, kept in the workspace between
-//               evaluations), and from the accepted state the sums moved to a pivot on the object, the damped 6x6 solve, the bound and the
-//               next trial pose, written into the slot the next render reads; one trace row per evaluation when asked for.
-// The contour form (stocs_refine_poses_visible_contour; tests/refine_visible_contour_ref.py) is the damped form with one more
-// kernel per evaluation and another solve:
+// accumulation K + 1 times and puts another kernel in the solve's place; the contour form (stocs_refine_poses_visible_contour, DESIGN
+// 7.22; tests/refine_visible_contour_ref.py) is the damped form with one more kernel per evaluation.  One solve kernel serves both:
+//   damped solve  one wavefront per hypothesis: the solve's reduction, then lane 0 in double: the cost, accept or reject against the pose's
+//               accepted state (pose, 29 sums, cost, lambda, kept in the workspace), and from it the sums moved to a pivot on the object, the
+//               damped 6x6 solve, the bound and the next trial pose in the slot the next render reads (rv_damped_decide); a trace row when
+//               asked for.  As the contour form (a compile-time argument) it reduces both sets of partials, decides on M = S + w Sc with the
+//               cost over the object pixels, and fills the record's contour fields from that decision.
 //   object count  once per call: N_O, the frame's pixels with a measurement and a class probability at the threshold, by __ballot.
 //   contour     between the render and the accumulation (which clears the keys), on the accumulation's grid: the pose's rectangle grown
 //               by the pull radius in tiles of 16 rows x 64 columns; per tile with an uncovered object pixel, "key present" of the tile and
 //               its halo as bit rows in LDS (one __ballot per 64 keys), per pixel the nearest set bit of each row of the window by
 //               count-leading/trailing-zeros under the minimum of (d2, linear index), one key load for the winner's depth, the 3-D gate,
 //               three point-to-point rows in double; 29 sums and three counts per workgroup in the accumulation's fixed order.
-//   contour solve  both sets of partials reduced, M = S + w Sc, the cost over the object pixels, then rv_damped_decide, the damped solve's
-//               own decision and next trial, on the totals.
+// Host: the batch entry points are their checks and one frame (VisibleCall): workspace, staging, per chunk and evaluation
+// render, contour pass, accumulation, the form's solve; one read-back, one event read-out.  Blocks: workspace, DampedWork, DetailWork.
 // Known limits: the plain step is an undamped Gauss-Newton step whose rotation is about the camera's origin: on a solid whose visible surface
 // constrains a motion weakly it can be large and leave the pose worse (measured on the Cm solid; the restatement does the
 // same, bit for bit; the damped form is the remedy); a frozen hypothesis is still rendered and walked in the remaining iterations of its chunk (nothing reads the result);
@@ -56,11 +56,10 @@ static const unsigned long long RV_EMPTY = 0xFFFFFFFFFFFFFFFFull;
 
 struct RefineVisibleState {
     static const StateOwner OWNER = OWN_REFINE_VISIBLE;
-    ~RefineVisibleState() { work.free(); detail.free(); damped.free(); contour.free(); }
+    ~RefineVisibleState() { work.free(); detail.free(); damped.free(); }
     DevBlock work;     // poses | records | frozen flags | rectangles | partial sums | partial counts | one chunk of key buffers, grow-only
-    DevBlock detail;   // stocs_refine_visible_detail: state | sums, grow-only
-    DevBlock damped;   // stocs_refine_poses_visible_damped: accepted poses | records | trace | accepted sums, cost, lambda | done flags, grow-only
-    DevBlock contour;  // the contour form: accepted poses | records | trace | accepted sums, cost, lambda | done flags | contour partials | N_O | detail planes, grow-only
+    DevBlock detail;   // both detail entry points (DetailWork): nearest | state | sums | contour partials, grow-only
+    DevBlock damped;   // the damped and the contour form (DampedWork): accepted poses | records | trace | accepted sums, cost, lambda | done flags | contour partials | N_O, grow-only
     float last_ms[3] = {-1.0f, -1.0f, -1.0f};  // "device_clock": HIP-event time of the last call's last render, accumulation and solve (-1: not taken)
     float last_contour_ms = -1.0f;             // the same of the last call's last contour pass
 };
@@ -276,7 +275,7 @@ struct RvDampedState { double S[RV_SUMS]; double cost, lambda; };
 // for e < K the next trial from the accepted state (steps 1-7), written into the slot Ph the next render reads.  sys: the sums the system
 // is made from ([0..26]; [28] is the record's b^T b; kept whole as the accepted sums); n, count: the evaluation's counts; enough: whether
 // the evaluation at e = 0 carries a system at all.  P holds the evaluated pose and, behind a rejection, the accepted one.
-__device__ __forceinline__ void rv_damped_decide(float* Ph, float* Pah, float (&P)[16], stocs_refine_visible_damped_result* R,
+__device__ __forceinline__ bool rv_damped_decide(float* Ph, float* Pah, float (&P)[16], stocs_refine_visible_damped_result* R,
                                                  RvDampedState* St, int32_t* done_h, stocs_refine_visible_trace* trace_h, int e,
                                                  RvDampedArgs da, const double (&sys)[RV_SUMS], const int (&n)[RV_COUNTS], int count, double C, bool enough) {
     double lambda = e == 0 ? da.lambda0 : St->lambda;
@@ -315,7 +314,7 @@ __device__ __forceinline__ void rv_damped_decide(float* Ph, float* Pah, float (&
         for (int i = 0; i < 16; ++i) Tr->pose[i] = Ph[i];
         Tr->cost = C; Tr->lambda = lambda; Tr->accepted = ok ? 1 : 0; Tr->state = 1;
     }
-    if (e == da.K) return;
+    if (e == da.K) return ok;
     bool freeze = e == 0 && !enough;   // not enough pixels at the start: the pose as it came
     double x[6];
     double c0 = 0.0, c1 = 0.0, c2 = 0.0;
@@ -354,7 +353,7 @@ __device__ __forceinline__ void rv_damped_decide(float* Ph, float* Pah, float (&
     if (freeze) {
         *done_h = 1; R->base.frozen = 1;
         if (Tr) Tr->state = 3;
-        return;
+        return ok;
     }
     // 5. the bound
     double s = 1.0;
@@ -379,33 +378,7 @@ __device__ __forceinline__ void rv_damped_decide(float* Ph, float* Pah, float (&
             Ph[4 * q + r] = (float)v;   // the slot's last row is the start's, as every accepted pose's is
         }
     }
-}
-
-// One wavefront per hypothesis of the chunk, after evaluation e of K + 1: the reduction of refine_visible_solve_kernel, the cost, the
-// decision against the accepted state, and for e < K the next trial from the accepted state (steps 1-7 of the contract), written into the
-// pose slot the next render reads.  Everything behind the reduction is lane 0's, in double.
-__global__ __launch_bounds__(64) void refine_visible_damped_solve_kernel(float* __restrict__ poses, const double* __restrict__ partial, const int32_t* __restrict__ pcount,
-                                                                         int groups, int e, RvDampedArgs da, float* __restrict__ accepted, RvDampedState* __restrict__ state,
-                                                                         int32_t* __restrict__ done, stocs_refine_visible_damped_result* __restrict__ rec,
-                                                                         stocs_refine_visible_trace* __restrict__ trace) {
-    const int h = (int)blockIdx.x, lane = (int)threadIdx.x;
-    if (done[h]) return;   // the same address in every lane: the whole wavefront
-    double acc[RV_SUMS];
-    int n[RV_COUNTS];
-    rv_reduce_partials(partial, pcount, h, groups, lane, acc, n);
-    if (lane) return;
-    float* Ph = poses + (size_t)h * 16;
-    float* Pah = accepted + (size_t)h * 16;
-    float P[16];
-    bool nonzero = false;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) { P[i] = Ph[i]; nonzero = nonzero || P[i] != 0.0f; }
-    stocs_refine_visible_damped_result* R = rec + h;   // zeroed in front of the first evaluation
-    RvDampedState* St = state + h;
-    if (e == 0 && (!pose_finite(P) || !nonzero)) { done[h] = 1; return; }   // renders nothing: the zero record, the pose as it came
-    const int count = (int)acc[27];
-    const double C = count < 6 ? (double)INFINITY : (acc[28] + da.max_d2 * (double)n[RV_TOO_FAR]) / (double)(count + n[RV_TOO_FAR]);
-    rv_damped_decide(Ph, Pah, P, R, St, done + h, trace ? trace + (size_t)h * (size_t)(da.K + 1) : (stocs_refine_visible_trace*)NULL, e, da, acc, n, count, C, count >= 6);
+    return ok;
 }
 
 // ---- the contour form (stocs_refine_poses_visible_contour): the damped form's evaluation plus a pass over the frame's object
@@ -579,55 +552,74 @@ __global__ __launch_bounds__(256) void refine_visible_contour_kernel(const unsig
     if (tid < RV_COUNTS) pcount[slot * RV_COUNTS + tid] = tid < 3 ? ((cnt[0][tid] + cnt[1][tid]) + cnt[2][tid]) + cnt[3][tid] : 0;
 }
 
-struct RcSolveArgs {
-    double w;          // (double) contour_weight; 0: no contour partials are read
-    double pull_d2;    // (double) of the float product the contour kernel compares with
+// ---- the damped solve of both forms.  A form names its record and says whether contour partials exist
+struct RvDampedForm {
+    typedef stocs_refine_visible_damped_result Record;
+    static constexpr bool contour = false;
+};
+struct RvContourForm {
+    typedef stocs_refine_visible_contour_result Record;
+    static constexpr bool contour = true;
+    const double* part; const int32_t* cnt;   // the chunk's contour partials
+    const int32_t* n_object;                  // N_O
+    double w;                                 // (double) contour_weight; 0: no contour partials are read
+    double pull_d2;                           // (double) of the float product the contour kernel compares with
 };
 
-// The damped solve with the contour term: both sets of partials reduced in the same fixed order, the totals M = S + w Sc, v likewise, the
-// cost over the frame's object pixels, then the damped decision and the next trial (rv_damped_decide) on the totals.
-__global__ __launch_bounds__(64) void refine_visible_contour_solve_kernel(float* __restrict__ poses, const double* __restrict__ partial, const int32_t* __restrict__ pcount,
-                                                                          const double* __restrict__ cpartial, const int32_t* __restrict__ cpcount, int groups, int e,
-                                                                          RvDampedArgs da, RcSolveArgs ca, const int32_t* __restrict__ n_object, float* __restrict__ accepted,
-                                                                          RvDampedState* __restrict__ state, int32_t* __restrict__ done,
-                                                                          stocs_refine_visible_contour_result* __restrict__ rec, stocs_refine_visible_trace* __restrict__ trace) {
+// One wavefront per hypothesis of the chunk, after evaluation e of K + 1: the reduction of refine_visible_solve_kernel, the cost, the
+// decision against the accepted state, and for e < K the next trial from the accepted state (rv_damped_decide), written into the pose
+// slot the next render reads.  Everything behind the reduction is lane 0's, in double.  The contour form reduces both sets of partials in
+// the same fixed order, decides on the totals M = S + w Sc, v likewise, with the cost over the frame's object pixels, and fills its own
+// fields of the record from the decision.
+template <class Form>
+__global__ __launch_bounds__(64) void refine_visible_damped_solve_kernel(float* __restrict__ poses, const double* __restrict__ partial, const int32_t* __restrict__ pcount,
+                                                                         int groups, int e, RvDampedArgs da, float* __restrict__ accepted, RvDampedState* __restrict__ state,
+                                                                         int32_t* __restrict__ done, typename Form::Record* __restrict__ rec,
+                                                                         stocs_refine_visible_trace* __restrict__ trace, Form f) {
     const int h = (int)blockIdx.x, lane = (int)threadIdx.x;
     if (done[h]) return;   // the same address in every lane: the whole wavefront
-    double acc[RV_SUMS], con[RV_SUMS];
-    int n[RV_COUNTS], nc[RV_COUNTS];
+    double acc[RV_SUMS], con[Form::contour ? RV_SUMS : 1];
+    int n[RV_COUNTS], nc[Form::contour ? RV_COUNTS : 1];
     rv_reduce_partials(partial, pcount, h, groups, lane, acc, n);
-    if (ca.w != 0.0) rv_reduce_partials(cpartial, cpcount, h, groups, lane, con, nc);
-    else {
+    if constexpr (Form::contour) {
+        if (f.w != 0.0) rv_reduce_partials(f.part, f.cnt, h, groups, lane, con, nc);
+        else {
 #pragma unroll
-        for (int k = 0; k < RV_SUMS; ++k) con[k] = 0.0;
+            for (int k = 0; k < RV_SUMS; ++k) con[k] = 0.0;
 #pragma unroll
-        for (int k = 0; k < RV_COUNTS; ++k) nc[k] = 0;
+            for (int k = 0; k < RV_COUNTS; ++k) nc[k] = 0;
+        }
     }
     if (lane) return;
     float* Ph = poses + (size_t)h * 16;
+    float* Pah = accepted + (size_t)h * 16;
     float P[16];
     bool nonzero = false;
 #pragma unroll
     for (int i = 0; i < 16; ++i) { P[i] = Ph[i]; nonzero = nonzero || P[i] != 0.0f; }
     if (e == 0 && (!pose_finite(P) || !nonzero)) { done[h] = 1; return; }   // renders nothing: the zero record, the pose as it came
-    stocs_refine_visible_contour_result* R = rec + h;   // zeroed in front of the first evaluation
-    RvDampedState* St = state + h;
-    const int count = (int)acc[27], pulled = nc[RC_PULLED], n_obj = *n_object;
-    const int uncovered = n_obj - ((n[RV_TOO_FAR] + n[RV_GRAZING]) + count);
-    double sys[RV_SUMS];
+    typename Form::Record* R = rec + h;   // zeroed in front of the first evaluation
+    stocs_refine_visible_trace* trace_h = trace ? trace + (size_t)h * (size_t)(da.K + 1) : (stocs_refine_visible_trace*)NULL;
+    const int count = (int)acc[27];
+    if constexpr (!Form::contour) {
+        const double C = count < 6 ? (double)INFINITY : (acc[28] + da.max_d2 * (double)n[RV_TOO_FAR]) / (double)(count + n[RV_TOO_FAR]);
+        rv_damped_decide(Ph, Pah, P, R, state + h, done + h, trace_h, e, da, acc, n, count, C, count >= 6);
+    } else {
+        const int pulled = nc[RC_PULLED], n_obj = *f.n_object;
+        const int uncovered = n_obj - ((n[RV_TOO_FAR] + n[RV_GRAZING]) + count);
+        double sys[RV_SUMS];
 #pragma unroll
-    for (int k = 0; k < 27; ++k) sys[k] = acc[k] + ca.w * con[k];
-    sys[27] = acc[27]; sys[28] = acc[28];
-    const bool enough = count + 3 * pulled >= 6;
-    const double C = !enough ? (double)INFINITY
-                             : ((acc[28] + da.max_d2 * (double)n[RV_TOO_FAR]) + ca.w * (con[28] + ca.pull_d2 * (double)(uncovered - pulled))) /
-                                   ((double)(count + n[RV_TOO_FAR]) + ca.w * (double)uncovered);
-    if (e == 0 || C < St->cost) {   // the decision rv_damped_decide makes: the contour fields of the accepted evaluation
-        R->object_px = n_obj; R->uncovered = uncovered; R->unreached = nc[RC_UNREACHED]; R->beyond = nc[RC_BEYOND]; R->pulled = pulled;
-        R->pull_rms = pulled > 0 ? sqrtf((float)(con[28] / (double)pulled)) : 0.0f;
+        for (int k = 0; k < 27; ++k) sys[k] = acc[k] + f.w * con[k];
+        sys[27] = acc[27]; sys[28] = acc[28];
+        const bool enough = count + 3 * pulled >= 6;
+        const double C = !enough ? (double)INFINITY
+                                 : ((acc[28] + da.max_d2 * (double)n[RV_TOO_FAR]) + f.w * (con[28] + f.pull_d2 * (double)(uncovered - pulled))) /
+                                       ((double)(count + n[RV_TOO_FAR]) + f.w * (double)uncovered);
+        if (rv_damped_decide(Ph, Pah, P, &R->damped, state + h, done + h, trace_h, e, da, sys, n, count, C, enough)) {   // accepted: its contour fields
+            R->object_px = n_obj; R->uncovered = uncovered; R->unreached = nc[RC_UNREACHED]; R->beyond = nc[RC_BEYOND]; R->pulled = pulled;
+            R->pull_rms = pulled > 0 ? sqrtf((float)(con[28] / (double)pulled)) : 0.0f;
+        }
     }
-    rv_damped_decide(Ph, accepted + (size_t)h * 16, P, &R->damped, St, done + h, trace ? trace + (size_t)h * (size_t)(da.K + 1) : (stocs_refine_visible_trace*)NULL, e,
-                     da, sys, n, count, C, enough);
 }
 
 static const char* params_error(const stocs_refine_visible_params* p) {
@@ -647,6 +639,14 @@ static const char* damped_params_error(const stocs_refine_visible_damped_params*
     if (!(p->max_step_translation > 0.0f)) return "max_step_translation must be positive (+inf: no bound)";
     if (p->pivot != 0 && p->pivot != 1) return "pivot must be 0 (the camera's origin) or 1 (pivot_model)";
     if (!isfinite(p->pivot_model[0]) || !isfinite(p->pivot_model[1]) || !isfinite(p->pivot_model[2])) return "pivot_model is not finite";
+    return NULL;
+}
+
+static const char* contour_params_error(const stocs_refine_visible_contour_params* p) {
+    if (const char* why = damped_params_error(&p->damped)) return why;
+    if (!(p->contour_weight >= 0.0f) || !isfinite(p->contour_weight)) return "contour_weight must be >= 0 and finite";
+    if (p->pull_radius_px < 1 || p->pull_radius_px > RC_MAX_RADIUS) return "pull_radius_px must be in 1 .. 64";
+    if (!(p->pull_distance > 0.0f) || !isfinite(p->pull_distance)) return "pull_distance must be positive and finite";
     return NULL;
 }
 
@@ -685,25 +685,70 @@ static int visible_work(stocs_ctx* c, int n, size_t chunk, size_t npix, int grou
     return STOCS_OK;
 }
 
-// the contour pass of an evaluation: its arguments and where the chunk's contour partials go
-struct RcPass { RcArgs ca; double* part; int32_t* cnt; };
+// The workspace of n poses of the damped and the contour form, in RefineVisibleState::damped.  What comes back lies in front, so one copy
+// reads it: accepted poses | records (rec_size each) | trace (K + 1 rows per pose, when asked for).  contour_slots: the chunk's contour
+// partials (chunk * G), 0 for the damped form, which has no N_O either.
+struct DampedWork {
+    size_t o_acc, o_rec, o_trace, o_state, o_done, o_cpart, o_ccnt, o_nobj, trace_bytes, back_all, back_bytes;
+    char* d;
+    float* acc() const { return (float*)(d + o_acc); }
+    stocs_refine_visible_trace* trace() const { return trace_bytes ? (stocs_refine_visible_trace*)(d + o_trace) : NULL; }
+    RvDampedState* state() const { return (RvDampedState*)(d + o_state); }
+    int32_t* done() const { return (int32_t*)(d + o_done); }
+    double* cpart() const { return (double*)(d + o_cpart); }
+    int32_t* ccnt() const { return (int32_t*)(d + o_ccnt); }
+    int32_t* nobj() const { return (int32_t*)(d + o_nobj); }
+};
+static int damped_work(stocs_ctx* c, int n, int K, size_t rec_size, bool traced, size_t contour_slots, DampedWork* w) {
+    Carve cv;
+    w->trace_bytes = traced ? (size_t)n * (size_t)(K + 1) * sizeof(stocs_refine_visible_trace) : 0;
+    w->o_acc = cv.take((size_t)n * 64);
+    w->o_rec = cv.take((size_t)n * rec_size);
+    w->o_trace = cv.take(w->trace_bytes);
+    w->back_all = cv.total;
+    w->back_bytes = traced ? w->o_trace + w->trace_bytes : w->o_rec + (size_t)n * rec_size;
+    w->o_state = cv.take((size_t)n * sizeof(RvDampedState));
+    w->o_done = cv.take((size_t)n * 4);
+    w->o_cpart = cv.take(contour_slots * RV_SUMS * 8);
+    w->o_ccnt = cv.take(contour_slots * RV_COUNTS * 4);
+    w->o_nobj = cv.take(contour_slots ? 4 : 0);
+    RefineVisibleState* S = ctx_state<RefineVisibleState>(c);
+    { const int rc = S->damped.grow(c->stream, cv.total); if (rc) return rc; }
+    w->d = S->damped.p;
+    return STOCS_OK;
+}
 
-// one evaluation of poses h0 .. h0 + m of the workspace: rectangles cleared, render, with cp the contour pass on the keys, accumulate
-// (their key buffers are clear in front and, in the shipping form, behind)
-template <class Detail>
-static int enqueue_evaluate(stocs_ctx* c, const DepthState* F, const VisibleWork& w, int h0, int m, const DepthArgs& a, const RvArgs& ra, Detail det, bool timed,
-                            const RcPass* cp = NULL) {
-    const float4* verts; const int4* tris;
-    mesh_device_arrays(c, &verts, &tris);
+static RvDampedArgs damped_args(const stocs_refine_visible_damped_params* p, const RvArgs& ra) {
+    RvDampedArgs da;
+    da.max_d2 = (double)ra.max_d2; da.lambda0 = (double)p->lambda0; da.down = (double)p->lambda_down; da.up = (double)p->lambda_up;
+    da.max_rot = (double)p->max_step_rotation; da.max_trans = (double)p->max_step_translation;
+    for (int k = 0; k < 3; ++k) da.pm[k] = (double)p->pivot_model[k];
+    da.pivot = p->pivot; da.K = p->base.max_iterations;
+    return da;
+}
+
+// ---- one evaluation of poses h0 .. h0 + m of the workspace, in three parts (their key buffers are clear in front and, behind the shipping
+// accumulation, clear again)
+// rectangles cleared, render
+static int enqueue_render(stocs_ctx* c, const VisibleWork& w, int h0, int m, const DepthArgs& a, bool timed) {
     STOCS_HIP_CHECK(hipMemsetAsync(w.box(), 0x80, (size_t)m * VSD_BOX_WORDS * 4, c->stream));
     if (timed) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[0], c->stream));
-    { const int rc = mesh_enqueue_tri_keys(c, w.pose() + (size_t)h0 * 16, m, a, w.key(), w.box()); if (rc) return rc; }
-    if (cp) {
-        if (timed) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[4], c->stream));
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(refine_visible_contour_kernel<RcNoDetail>), dim3((unsigned)ra.groups, (unsigned)m), dim3(256), 0, c->stream,
-                           (const unsigned long long*)w.key(), (const int32_t*)w.box(), frame_depth(F), frame_prob(F), a, cp->ca, cp->part, cp->cnt, RcNoDetail());
-        STOCS_HIP_CHECK(hipGetLastError());
-    }
+    return mesh_enqueue_tri_keys(c, w.pose() + (size_t)h0 * 16, m, a, w.key(), w.box());
+}
+// the contour pass on the keys: its arguments and where the chunk's contour partials go; run: whether the form's weight asks for it
+struct RcPass { RcArgs ca; double* part; int32_t* cnt; bool run; };
+template <class Detail>
+static int enqueue_contour(stocs_ctx* c, const DepthState* F, const VisibleWork& w, int m, const DepthArgs& a, const RcPass& cp, Detail det, bool timed) {
+    if (timed) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[4], c->stream));
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(refine_visible_contour_kernel<Detail>), dim3((unsigned)cp.ca.groups, (unsigned)m), dim3(256), 0, c->stream,
+                       (const unsigned long long*)w.key(), (const int32_t*)w.box(), frame_depth(F), frame_prob(F), a, cp.ca, cp.part, cp.cnt, det);
+    STOCS_HIP_CHECK(hipGetLastError());
+    return STOCS_OK;
+}
+template <class Detail>
+static int enqueue_accumulate(stocs_ctx* c, const DepthState* F, const VisibleWork& w, int h0, int m, const DepthArgs& a, const RvArgs& ra, Detail det, bool timed) {
+    const float4* verts; const int4* tris;
+    mesh_device_arrays(c, &verts, &tris);
     if (timed) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[1], c->stream));
     hipLaunchKernelGGL(HIP_KERNEL_NAME(refine_visible_accumulate_kernel<Detail>), dim3((unsigned)ra.groups, (unsigned)m), dim3(256), 0, c->stream,
                        (const float*)(w.pose() + (size_t)h0 * 16), verts, tris, w.key(), (const int32_t*)w.box(), frame_depth(F), frame_prob(F), a, ra, w.part(), w.cnt(), det);
@@ -712,17 +757,172 @@ static int enqueue_evaluate(stocs_ctx* c, const DepthState* F, const VisibleWork
     return STOCS_OK;
 }
 
-// the checks both entry points make behind their own NULL tests, in the documented order
+// ---- the checks, in the documented orders
+// the refusals every batch entry point starts with.  True: the call ends here with *rc (n == 0: STOCS_OK)
+static bool visible_refuse(const char* who, const stocs_ctx* c, const void* poses, int n, const void* prm, const void* pose16_out, const void* out, int* rc) {
+    *rc = STOCS_ERR_INVALID;
+    if (!c) { set_error("%s: NULL context", who); return true; }
+    if (n < 0) { set_error("%s: n %d < 0", who, n); return true; }
+    if (n == 0) { *rc = STOCS_OK; return true; }
+    if (!poses || !prm || !pose16_out || !out) { set_error("%s: NULL poses, parameters or results", who); return true; }
+    return false;
+}
+// a stocs_check_*_params entry point
+template <class P>
+static int params_check(const char* who, const P* p, const char* (*error)(const P*)) {
+    if (!p) { set_error("%s: NULL parameters", who); return STOCS_ERR_INVALID; }
+    if (const char* why = error(p)) { set_error("%s: %s", who, why); return STOCS_ERR_INVALID; }
+    return STOCS_OK;
+}
+// behind an entry point's own NULL tests: the plain parameters, the mesh, the frame
 static int visible_check(const char* who, stocs_ctx* c, const stocs_refine_visible_params* p, DepthState** F) {
     if (const char* why = params_error(p)) { set_error("%s: %s", who, why); return STOCS_ERR_INVALID; }
     { const int rc = mesh_check_present(who, c); if (rc) return rc; }
     return check_frame(who, c, F);
+}
+// ... of both contour entry points: the contour parameters, the damped order, then the class image
+static int contour_check(const char* who, stocs_ctx* c, const stocs_refine_visible_contour_params* p, DepthState** F) {
+    if (const char* why = contour_params_error(p)) { set_error("%s: %s", who, why); return STOCS_ERR_INVALID; }
+    { const int rc = visible_check(who, c, &p->damped.base, F); if (rc) return rc; }
+    if (!frame_prob(*F)) { set_error("%s: the frame has no class image: the object pixels are not defined (stocs_ctx_set_frame)", who); return STOCS_ERR_STATE; }
+    return STOCS_OK;
 }
 
 static RvArgs visible_args(const stocs_refine_visible_params* p, int groups) {
     RvArgs ra;
     ra.max_d2 = p->max_distance * p->max_distance; ra.min_cos2 = p->min_view_cos * p->min_view_cos; ra.groups = groups;
     return ra;
+}
+static RcArgs contour_args(const stocs_refine_visible_contour_params* p, int groups) {
+    RcArgs ca;
+    ca.pull_d2 = p->pull_distance * p->pull_distance; ca.R = p->pull_radius_px; ca.groups = groups;
+    return ca;
+}
+
+// ---- The call frame of the three batch entry points.  Made behind the last refusal, it holds the device, the chunk size, G, the
+// arguments of render and accumulation and the workspace of n poses (rc: whether that could be had).  run() stages the poses through the
+// pinned block, runs all evaluations of a chunk before the next chunk starts -- render, the contour pass if there is one to run,
+// accumulation, the form's solve step -- and reads back_bytes at d_back back in one copy behind the call's one synchronisation.
+struct VisibleCall {
+    DeviceGuard guard;
+    stocs_ctx* c; const DepthState* F;
+    int n, groups, rc;
+    size_t npix, chunk;
+    DepthArgs a; RvArgs ra; VisibleWork w;
+    VisibleCall(stocs_ctx* c_, const DepthState* F_, int n_, const stocs_refine_visible_params* p)
+        : guard(c_->device), c(c_), F(F_), n(n_), groups(refine_visible_groups(F_->npix)), npix(F_->npix), chunk(visible_chunk(n_, F_->npix)),
+          a(frame_args(F_, 0.0f, p->class_threshold)), ra(visible_args(p, groups)) {
+        rc = visible_work(c, n, chunk, npix, groups, &w);
+    }
+    // evaluations: per chunk; cp: the contour form's pass (NULL: another form); d_accepted: where the start goes beside the slot the render
+    // reads (NULL: nowhere); step(h0, m, e) launches the form's solve behind evaluation e of poses h0 .. h0 + m; *hback: what came back
+    template <class Step>
+    int run(const float* poses, int evaluations, const RcPass* cp, float* d_accepted, Step step, const void* d_back, size_t back_bytes, char** hback) {
+        const bool dev_clock = c->device_clock != 0, pass = cp && cp->run;
+        char* hin;
+        { const int r = pinned_for(c, (size_t)n * 64, back_bytes, &hin, hback); if (r) return r; }
+        memcpy(hin, poses, (size_t)n * 64);
+        STOCS_HIP_CHECK(hipMemcpyAsync(w.pose(), hin, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));   // the slot the render reads
+        if (d_accepted) STOCS_HIP_CHECK(hipMemcpyAsync(d_accepted, hin, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));
+        for (int h0 = 0; h0 < n; h0 += (int)chunk) {
+            const int m = std::min((int)chunk, n - h0);
+            STOCS_HIP_CHECK(hipMemsetAsync(w.key(), 0xFF, (size_t)m * npix * 8, c->stream));
+            for (int e = 0; e < evaluations; ++e) {
+                const bool timed = dev_clock && h0 + m == n && e + 1 == evaluations;   // the call's last evaluation
+                { const int r = enqueue_render(c, w, h0, m, a, timed); if (r) return r; }
+                if (pass) { const int r = enqueue_contour(c, F, w, m, a, *cp, RcNoDetail(), timed); if (r) return r; }
+                { const int r = enqueue_accumulate(c, F, w, h0, m, a, ra, RvNoDetail(), timed); if (r) return r; }
+                { const int r = step(h0, m, e); if (r) return r; }
+                if (timed) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[3], c->stream));
+            }
+        }
+        STOCS_HIP_CHECK(hipMemcpyAsync(*hback, d_back, back_bytes, hipMemcpyDeviceToHost, c->stream));
+        STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
+        // the event read-out: render, the contour pass if run (with it the render ends where the contour kernel starts), accumulation, solve
+        RefineVisibleState* S = ctx_state<RefineVisibleState>(c);
+        S->last_ms[0] = S->last_ms[1] = S->last_ms[2] = -1.0f;
+        if (cp) S->last_contour_ms = -1.0f;
+        const int mark[5] = {0, pass ? 4 : 1, 1, 2, 3};
+        float* const slot[4] = {&S->last_ms[0], pass ? &S->last_contour_ms : (float*)NULL, &S->last_ms[1], &S->last_ms[2]};
+        float ms = 0.0f;
+        for (int k = 0; dev_clock && k < 4; ++k)
+            if (slot[k] && hipEventElapsedTime(&ms, c->ev_t[mark[k]], c->ev_t[mark[k + 1]]) == hipSuccess) *slot[k] = ms;
+        return STOCS_OK;
+    }
+};
+
+// The damped and the contour entry point behind their checks (cprm: the contour form's parameters): K + 1 evaluations per chunk with the
+// damped solve of the form, the accepted pose and the record in the damped block, read back with the trace behind them.  The contour form
+// counts N_O in front and has the contour pass inside every evaluation.
+template <class Form>
+static int damped_call(stocs_ctx* c, const DepthState* F, const float* poses, int n, const stocs_refine_visible_damped_params* dp,
+                       const stocs_refine_visible_contour_params* cprm, float* pose16_out, typename Form::Record* out, stocs_refine_visible_trace* trace) {
+    typedef typename Form::Record Record;
+    VisibleCall vc(c, F, n, &dp->base);
+    if (vc.rc) return vc.rc;
+    const int K = dp->base.max_iterations;
+    DampedWork dw;
+    { const int rc = damped_work(c, n, K, sizeof(Record), trace != NULL, Form::contour ? vc.chunk * (size_t)vc.groups : 0, &dw); if (rc) return rc; }
+    STOCS_HIP_CHECK(hipMemsetAsync(dw.d + dw.o_rec, 0, dw.back_all - dw.o_rec, c->stream));   // records and trace
+    STOCS_HIP_CHECK(hipMemsetAsync(dw.done(), 0, (size_t)n * 4, c->stream));
+    const RvDampedArgs da = damped_args(dp, vc.ra);
+    Form f;
+    RcPass cp;
+    if constexpr (Form::contour) {
+        STOCS_HIP_CHECK(hipMemsetAsync(dw.nobj(), 0, 4, c->stream));
+        hipLaunchKernelGGL(refine_visible_object_count_kernel, dim3((unsigned)std::min<size_t>((vc.npix + 255) / 256, 1024)), dim3(256), 0, c->stream, frame_depth(F),
+                           frame_prob(F), vc.npix, vc.a.class_threshold, dw.nobj());
+        STOCS_HIP_CHECK(hipGetLastError());
+        cp.ca = contour_args(cprm, vc.groups); cp.part = dw.cpart(); cp.cnt = dw.ccnt(); cp.run = cprm->contour_weight != 0.0f;
+        f.part = cp.part; f.cnt = cp.cnt; f.n_object = dw.nobj(); f.w = (double)cprm->contour_weight; f.pull_d2 = (double)cp.ca.pull_d2;
+    }
+    Record* d_rec = (Record*)(dw.d + dw.o_rec);
+    char* hback;
+    const int rc = vc.run(poses, K + 1, Form::contour ? &cp : (const RcPass*)NULL, dw.acc(), [&](int h0, int m, int e) -> int {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(refine_visible_damped_solve_kernel<Form>), dim3((unsigned)m), dim3(64), 0, c->stream, vc.w.pose() + (size_t)h0 * 16,
+                           (const double*)vc.w.part(), (const int32_t*)vc.w.cnt(), vc.groups, e, da, dw.acc() + (size_t)h0 * 16, dw.state() + h0, dw.done() + h0, d_rec + h0,
+                           dw.trace() ? dw.trace() + (size_t)h0 * (size_t)(K + 1) : (stocs_refine_visible_trace*)NULL, f);
+        STOCS_HIP_CHECK(hipGetLastError());
+        return STOCS_OK;
+    }, dw.d, dw.back_bytes, &hback);
+    if (rc) return rc;
+    memcpy(pose16_out, hback + dw.o_acc, (size_t)n * 64);
+    memcpy(out, hback + dw.o_rec, (size_t)n * sizeof(Record));
+    if (trace) memcpy(trace, hback + dw.o_trace, dw.trace_bytes);
+    return STOCS_OK;
+}
+
+// The front of both detail entry points, synchronous paths for tests and diagnosis: ONE pose, pageable copies, ONE evaluation.  The
+// workspace of one pose and the planes in RefineVisibleState::detail (nearest and the contour partials only for the contour detail), the
+// pose up, the keys and the planes cleared.
+struct DetailWork { VisibleWork w; int groups; DepthArgs a; uint8_t* state; int32_t* nearest; double* sums29; double* cpart; int32_t* ccnt; };
+static int detail_begin(stocs_ctx* c, const DepthState* F, const float* pose, float class_threshold, bool contour, DetailWork* d) {
+    const size_t npix = F->npix;
+    d->groups = refine_visible_groups(npix);
+    d->a = frame_args(F, 0.0f, class_threshold);
+    { const int rc = visible_work(c, 1, 1, npix, d->groups, &d->w); if (rc) return rc; }
+    RefineVisibleState* S = ctx_state<RefineVisibleState>(c);
+    Carve cv;
+    const size_t o_near = cv.take(contour ? npix * 4 : 0), o_state = cv.take(npix), o_sums = cv.take(RV_SUMS * 8);
+    const size_t o_cpart = cv.take(contour ? (size_t)d->groups * RV_SUMS * 8 : 0), o_ccnt = cv.take(contour ? (size_t)d->groups * RV_COUNTS * 4 : 0);
+    { const int rc = S->detail.grow(c->stream, cv.total); if (rc) return rc; }
+    char* base = S->detail.p;
+    d->nearest = Carve::at<int32_t>(base, o_near); d->state = Carve::at<uint8_t>(base, o_state); d->sums29 = Carve::at<double>(base, o_sums);
+    d->cpart = Carve::at<double>(base, o_cpart); d->ccnt = Carve::at<int32_t>(base, o_ccnt);
+    STOCS_HIP_CHECK(hipMemcpyAsync(d->w.pose(), pose, 64, hipMemcpyHostToDevice, c->stream));
+    STOCS_HIP_CHECK(hipMemsetAsync(d->w.key(), 0xFF, npix * 8, c->stream));
+    STOCS_HIP_CHECK(hipMemsetAsync(d->state, 0, npix, c->stream));
+    if (contour) STOCS_HIP_CHECK(hipMemsetAsync(d->nearest, 0xFF, npix * 4, c->stream));
+    return STOCS_OK;
+}
+// ... and their end: the 29 sums of the partials (part, cnt) as the solve step forms them, the one synchronisation
+static int detail_sums(stocs_ctx* c, const DetailWork& d, const double* part, const int32_t* cnt) {
+    RvDetailOut det;
+    det.state = NULL; det.sums29 = d.sums29;
+    hipLaunchKernelGGL(refine_visible_solve_kernel<RvDetailOut>, dim3(1), dim3(64), 0, c->stream, d.w.pose(), part, cnt, d.groups, 0, d.w.frozen(), d.w.rec(), det);
+    STOCS_HIP_CHECK(hipGetLastError());
+    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return STOCS_OK;
 }
 
 }  // namespace stocs
@@ -734,10 +934,28 @@ extern "C" void stocs_default_refine_visible_params(stocs_refine_visible_params*
     p->max_iterations = 5; p->max_distance = 0.02f; p->min_view_cos = 0.0f; p->class_threshold = 0.10f;
 }
 
-extern "C" int stocs_check_refine_visible_params(const stocs_refine_visible_params* p) {
-    if (!p) { set_error("stocs_check_refine_visible_params: NULL parameters"); return STOCS_ERR_INVALID; }
-    if (const char* why = params_error(p)) { set_error("stocs_check_refine_visible_params: %s", why); return STOCS_ERR_INVALID; }
-    return STOCS_OK;
+extern "C" void stocs_default_refine_visible_damped_params(stocs_refine_visible_damped_params* p) {
+    if (!p) return;
+    stocs_default_refine_visible_params(&p->base);
+    p->lambda0 = 1.0f; p->lambda_down = 4.0f; p->lambda_up = 16.0f;
+    p->max_step_rotation = 0.0872664626f;   // 5 degrees
+    p->max_step_translation = 0.01f;
+    p->pivot = 1;
+    p->pivot_model[0] = p->pivot_model[1] = p->pivot_model[2] = 0.0f;
+}
+
+extern "C" void stocs_default_refine_visible_contour_params(stocs_refine_visible_contour_params* p) {
+    if (!p) return;
+    stocs_default_refine_visible_damped_params(&p->damped);
+    p->contour_weight = 1.0f; p->pull_radius_px = 16; p->pull_distance = 0.03f;
+}
+
+extern "C" int stocs_check_refine_visible_params(const stocs_refine_visible_params* p) { return params_check("stocs_check_refine_visible_params", p, params_error); }
+extern "C" int stocs_check_refine_visible_damped_params(const stocs_refine_visible_damped_params* p) {
+    return params_check("stocs_check_refine_visible_damped_params", p, damped_params_error);
+}
+extern "C" int stocs_check_refine_visible_contour_params(const stocs_refine_visible_contour_params* p) {
+    return params_check("stocs_check_refine_visible_contour_params", p, contour_params_error);
 }
 
 extern "C" int stocs_refine_visible_groups(int width, int height) {
@@ -754,218 +972,6 @@ extern "C" int stocs_refine_visible_last_device_ms(const stocs_ctx* c, float* re
     return STOCS_OK;
 }
 
-extern "C" int stocs_refine_poses_visible(stocs_ctx* c, const float* poses, int n, const stocs_refine_visible_params* prm, float* pose16_out,
-                                          stocs_refine_visible_result* out) {
-    static const char* who = "stocs_refine_poses_visible";
-    if (!c) { set_error("%s: NULL context", who); return STOCS_ERR_INVALID; }
-    if (n < 0) { set_error("%s: n %d < 0", who, n); return STOCS_ERR_INVALID; }
-    if (n == 0) return STOCS_OK;
-    if (!poses || !prm || !pose16_out || !out) { set_error("%s: NULL poses, parameters or results", who); return STOCS_ERR_INVALID; }
-    DepthState* F = NULL;
-    { const int rc = visible_check(who, c, prm, &F); if (rc) return rc; }
-    DeviceGuard dev_guard(c->device);
-    const bool dev_clock = c->device_clock != 0;
-    const size_t npix = F->npix, chunk = visible_chunk(n, npix);
-    const int groups = refine_visible_groups(npix);
-    VisibleWork w;
-    { const int rc = visible_work(c, n, chunk, npix, groups, &w); if (rc) return rc; }
-    const size_t back_bytes = w.o_rec - w.o_pose + (size_t)n * sizeof(stocs_refine_visible_result);
-    char* hin; char* hback;
-    { const int rc = pinned_for(c, (size_t)n * 64, back_bytes, &hin, &hback); if (rc) return rc; }
-    memcpy(hin, poses, (size_t)n * 64);
-    STOCS_HIP_CHECK(hipMemcpyAsync(w.pose(), hin, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));
-    STOCS_HIP_CHECK(hipMemsetAsync(w.rec(), 0, (size_t)n * sizeof(stocs_refine_visible_result), c->stream));
-    STOCS_HIP_CHECK(hipMemsetAsync(w.frozen(), 0, (size_t)n * 4, c->stream));
-    const DepthArgs a = frame_args(F, 0.0f, prm->class_threshold);
-    const RvArgs ra = visible_args(prm, groups);
-    const int evaluations = std::max(prm->max_iterations, 1), update = prm->max_iterations > 0 ? 1 : 0;
-    for (int h0 = 0; h0 < n; h0 += (int)chunk) {   // all iterations of a chunk before the next one starts
-        const int m = std::min((int)chunk, n - h0);
-        STOCS_HIP_CHECK(hipMemsetAsync(w.key(), 0xFF, (size_t)m * npix * 8, c->stream));
-        for (int it = 0; it < evaluations; ++it) {
-            const bool timed = dev_clock && h0 + m == n && it + 1 == evaluations;
-            { const int rc = enqueue_evaluate(c, F, w, h0, m, a, ra, RvNoDetail(), timed); if (rc) return rc; }
-            hipLaunchKernelGGL(refine_visible_solve_kernel<RvNoDetail>, dim3((unsigned)m), dim3(64), 0, c->stream, w.pose() + (size_t)h0 * 16, (const double*)w.part(),
-                               (const int32_t*)w.cnt(), groups, update, w.frozen() + h0, w.rec() + h0, RvNoDetail());
-            STOCS_HIP_CHECK(hipGetLastError());
-            if (timed) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[3], c->stream));
-        }
-    }
-    STOCS_HIP_CHECK(hipMemcpyAsync(hback, w.pose(), back_bytes, hipMemcpyDeviceToHost, c->stream));
-    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    RefineVisibleState* S = ctx_state<RefineVisibleState>(c);
-    S->last_ms[0] = S->last_ms[1] = S->last_ms[2] = -1.0f;
-    if (dev_clock) {
-        float ms = 0.0f;
-        for (int k = 0; k < 3; ++k)
-            if (hipEventElapsedTime(&ms, c->ev_t[k], c->ev_t[k + 1]) == hipSuccess) S->last_ms[k] = ms;
-    }
-    memcpy(pose16_out, hback, (size_t)n * 64);
-    memcpy(out, hback + (w.o_rec - w.o_pose), (size_t)n * sizeof(stocs_refine_visible_result));
-    return STOCS_OK;
-}
-
-extern "C" void stocs_default_refine_visible_damped_params(stocs_refine_visible_damped_params* p) {
-    if (!p) return;
-    stocs_default_refine_visible_params(&p->base);
-    p->lambda0 = 1.0f; p->lambda_down = 4.0f; p->lambda_up = 16.0f;
-    p->max_step_rotation = 0.0872664626f;   // 5 degrees
-    p->max_step_translation = 0.01f;
-    p->pivot = 1;
-    p->pivot_model[0] = p->pivot_model[1] = p->pivot_model[2] = 0.0f;
-}
-
-extern "C" int stocs_check_refine_visible_damped_params(const stocs_refine_visible_damped_params* p) {
-    if (!p) { set_error("stocs_check_refine_visible_damped_params: NULL parameters"); return STOCS_ERR_INVALID; }
-    if (const char* why = damped_params_error(p)) { set_error("stocs_check_refine_visible_damped_params: %s", why); return STOCS_ERR_INVALID; }
-    return STOCS_OK;
-}
-
-// The plain call's frame with another solve step: K + 1 evaluations per chunk, the accepted pose and the record in the damped block,
-// read back with the trace behind them in one copy.
-extern "C" int stocs_refine_poses_visible_damped(stocs_ctx* c, const float* poses, int n, const stocs_refine_visible_damped_params* prm, float* pose16_out,
-                                                 stocs_refine_visible_damped_result* out, stocs_refine_visible_trace* trace) {
-    static const char* who = "stocs_refine_poses_visible_damped";
-    if (!c) { set_error("%s: NULL context", who); return STOCS_ERR_INVALID; }
-    if (n < 0) { set_error("%s: n %d < 0", who, n); return STOCS_ERR_INVALID; }
-    if (n == 0) return STOCS_OK;
-    if (!poses || !prm || !pose16_out || !out) { set_error("%s: NULL poses, parameters or results", who); return STOCS_ERR_INVALID; }
-    if (const char* why = damped_params_error(prm)) { set_error("%s: %s", who, why); return STOCS_ERR_INVALID; }
-    DepthState* F = NULL;
-    { const int rc = visible_check(who, c, &prm->base, &F); if (rc) return rc; }
-    DeviceGuard dev_guard(c->device);
-    const bool dev_clock = c->device_clock != 0;
-    const size_t npix = F->npix, chunk = visible_chunk(n, npix);
-    const int groups = refine_visible_groups(npix), K = prm->base.max_iterations;
-    VisibleWork w;
-    { const int rc = visible_work(c, n, chunk, npix, groups, &w); if (rc) return rc; }
-    RefineVisibleState* S = ctx_state<RefineVisibleState>(c);
-    const size_t rows = (size_t)n * (size_t)(K + 1);
-    Carve cv;   // what comes back lies in front: accepted poses | records | trace
-    const size_t o_acc = cv.take((size_t)n * 64), o_rec = cv.take((size_t)n * sizeof(stocs_refine_visible_damped_result));
-    const size_t o_trace = cv.take(trace ? rows * sizeof(stocs_refine_visible_trace) : 0), back_all = cv.total;
-    const size_t o_state = cv.take((size_t)n * sizeof(RvDampedState)), o_done = cv.take((size_t)n * 4);
-    { const int rc = S->damped.grow(c->stream, cv.total); if (rc) return rc; }
-    float* d_acc = Carve::at<float>(S->damped.p, o_acc);
-    stocs_refine_visible_damped_result* d_rec = Carve::at<stocs_refine_visible_damped_result>(S->damped.p, o_rec);
-    stocs_refine_visible_trace* d_trace = trace ? Carve::at<stocs_refine_visible_trace>(S->damped.p, o_trace) : NULL;
-    RvDampedState* d_state = Carve::at<RvDampedState>(S->damped.p, o_state);
-    int32_t* d_done = Carve::at<int32_t>(S->damped.p, o_done);
-    const size_t back_bytes = trace ? o_trace + rows * sizeof(stocs_refine_visible_trace) : o_rec + (size_t)n * sizeof(stocs_refine_visible_damped_result);
-    char* hin; char* hback;
-    { const int rc = pinned_for(c, (size_t)n * 64, back_bytes, &hin, &hback); if (rc) return rc; }
-    memcpy(hin, poses, (size_t)n * 64);
-    STOCS_HIP_CHECK(hipMemcpyAsync(w.pose(), hin, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));   // the slot the render reads
-    STOCS_HIP_CHECK(hipMemcpyAsync(d_acc, hin, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));      // the accepted pose: the start
-    STOCS_HIP_CHECK(hipMemsetAsync(S->damped.p + o_rec, 0, back_all - o_rec, c->stream));               // records and trace
-    STOCS_HIP_CHECK(hipMemsetAsync(d_done, 0, (size_t)n * 4, c->stream));
-    const DepthArgs a = frame_args(F, 0.0f, prm->base.class_threshold);
-    const RvArgs ra = visible_args(&prm->base, groups);
-    RvDampedArgs da;
-    da.max_d2 = (double)ra.max_d2; da.lambda0 = (double)prm->lambda0; da.down = (double)prm->lambda_down; da.up = (double)prm->lambda_up;
-    da.max_rot = (double)prm->max_step_rotation; da.max_trans = (double)prm->max_step_translation;
-    for (int k = 0; k < 3; ++k) da.pm[k] = (double)prm->pivot_model[k];
-    da.pivot = prm->pivot; da.K = K;
-    for (int h0 = 0; h0 < n; h0 += (int)chunk) {   // all evaluations of a chunk before the next one starts
-        const int m = std::min((int)chunk, n - h0);
-        STOCS_HIP_CHECK(hipMemsetAsync(w.key(), 0xFF, (size_t)m * npix * 8, c->stream));
-        for (int e = 0; e <= K; ++e) {
-            const bool timed = dev_clock && h0 + m == n && e == K;
-            { const int rc = enqueue_evaluate(c, F, w, h0, m, a, ra, RvNoDetail(), timed); if (rc) return rc; }
-            hipLaunchKernelGGL(refine_visible_damped_solve_kernel, dim3((unsigned)m), dim3(64), 0, c->stream, w.pose() + (size_t)h0 * 16, (const double*)w.part(),
-                               (const int32_t*)w.cnt(), groups, e, da, d_acc + (size_t)h0 * 16, d_state + h0, d_done + h0, d_rec + h0,
-                               d_trace ? d_trace + (size_t)h0 * (size_t)(K + 1) : (stocs_refine_visible_trace*)NULL);
-            STOCS_HIP_CHECK(hipGetLastError());
-            if (timed) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[3], c->stream));
-        }
-    }
-    STOCS_HIP_CHECK(hipMemcpyAsync(hback, S->damped.p, back_bytes, hipMemcpyDeviceToHost, c->stream));
-    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    S->last_ms[0] = S->last_ms[1] = S->last_ms[2] = -1.0f;
-    if (dev_clock) {
-        float ms = 0.0f;
-        for (int k = 0; k < 3; ++k)
-            if (hipEventElapsedTime(&ms, c->ev_t[k], c->ev_t[k + 1]) == hipSuccess) S->last_ms[k] = ms;
-    }
-    memcpy(pose16_out, hback + o_acc, (size_t)n * 64);
-    memcpy(out, hback + o_rec, (size_t)n * sizeof(stocs_refine_visible_damped_result));
-    if (trace) memcpy(trace, hback + o_trace, rows * sizeof(stocs_refine_visible_trace));
-    return STOCS_OK;
-}
-
-// A plain, synchronous path (a test and diagnosis facility): ONE pose, pageable copies, ONE evaluation; the keys as the render left
-// them, the state per pixel, the 29 sums as the solve step forms them.
-extern "C" int stocs_refine_visible_detail(stocs_ctx* c, const float* pose, const stocs_refine_visible_params* prm, uint64_t* keys, uint8_t* state, double* sums29) {
-    static const char* who = "stocs_refine_visible_detail";
-    if (!c) { set_error("%s: NULL context", who); return STOCS_ERR_INVALID; }
-    if (!pose || !prm || !sums29) { set_error("%s: NULL pose, parameters or sums", who); return STOCS_ERR_INVALID; }
-    DepthState* F = NULL;
-    { const int rc = visible_check(who, c, prm, &F); if (rc) return rc; }
-    DeviceGuard dev_guard(c->device);
-    const size_t npix = F->npix;
-    const int groups = refine_visible_groups(npix);
-    VisibleWork w;
-    { const int rc = visible_work(c, 1, 1, npix, groups, &w); if (rc) return rc; }
-    RefineVisibleState* S = ctx_state<RefineVisibleState>(c);
-    Carve cv;
-    const size_t o_state = cv.take(npix), o_sums = cv.take(RV_SUMS * 8);
-    { const int rc = S->detail.grow(c->stream, cv.total); if (rc) return rc; }
-    RvDetailOut det;
-    det.state = Carve::at<uint8_t>(S->detail.p, o_state); det.sums29 = Carve::at<double>(S->detail.p, o_sums);
-    STOCS_HIP_CHECK(hipMemcpyAsync(w.pose(), pose, 64, hipMemcpyHostToDevice, c->stream));
-    STOCS_HIP_CHECK(hipMemsetAsync(w.key(), 0xFF, npix * 8, c->stream));
-    STOCS_HIP_CHECK(hipMemsetAsync(det.state, 0, npix, c->stream));
-    const DepthArgs a = frame_args(F, 0.0f, prm->class_threshold);
-    { const int rc = enqueue_evaluate(c, F, w, 0, 1, a, visible_args(prm, groups), det, false); if (rc) return rc; }
-    hipLaunchKernelGGL(refine_visible_solve_kernel<RvDetailOut>, dim3(1), dim3(64), 0, c->stream, w.pose(), (const double*)w.part(), (const int32_t*)w.cnt(), groups, 0,
-                       w.frozen(), w.rec(), det);
-    STOCS_HIP_CHECK(hipGetLastError());
-    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (keys) STOCS_HIP_CHECK(hipMemcpy(keys, w.key(), npix * 8, hipMemcpyDeviceToHost));
-    if (state) STOCS_HIP_CHECK(hipMemcpy(state, det.state, npix, hipMemcpyDeviceToHost));
-    STOCS_HIP_CHECK(hipMemcpy(sums29, det.sums29, RV_SUMS * 8, hipMemcpyDeviceToHost));
-    return STOCS_OK;
-}
-
-// ---- the contour form
-namespace stocs {
-
-static const char* contour_params_error(const stocs_refine_visible_contour_params* p) {
-    if (const char* why = damped_params_error(&p->damped)) return why;
-    if (!(p->contour_weight >= 0.0f) || !isfinite(p->contour_weight)) return "contour_weight must be >= 0 and finite";
-    if (p->pull_radius_px < 1 || p->pull_radius_px > RC_MAX_RADIUS) return "pull_radius_px must be in 1 .. 64";
-    if (!(p->pull_distance > 0.0f) || !isfinite(p->pull_distance)) return "pull_distance must be positive and finite";
-    return NULL;
-}
-
-// the checks of both contour entry points behind their own NULL tests: the damped form's, then the class image
-static int contour_check(const char* who, stocs_ctx* c, const stocs_refine_visible_contour_params* p, DepthState** F) {
-    if (const char* why = contour_params_error(p)) { set_error("%s: %s", who, why); return STOCS_ERR_INVALID; }
-    { const int rc = visible_check(who, c, &p->damped.base, F); if (rc) return rc; }
-    if (!frame_prob(*F)) { set_error("%s: the frame has no class image: the object pixels are not defined (stocs_ctx_set_frame)", who); return STOCS_ERR_STATE; }
-    return STOCS_OK;
-}
-
-static RcArgs contour_args(const stocs_refine_visible_contour_params* p, int groups) {
-    RcArgs ca;
-    ca.pull_d2 = p->pull_distance * p->pull_distance; ca.R = p->pull_radius_px; ca.groups = groups;
-    return ca;
-}
-
-}  // namespace stocs
-
-extern "C" void stocs_default_refine_visible_contour_params(stocs_refine_visible_contour_params* p) {
-    if (!p) return;
-    stocs_default_refine_visible_damped_params(&p->damped);
-    p->contour_weight = 1.0f; p->pull_radius_px = 16; p->pull_distance = 0.03f;
-}
-
-extern "C" int stocs_check_refine_visible_contour_params(const stocs_refine_visible_contour_params* p) {
-    if (!p) { set_error("stocs_check_refine_visible_contour_params: NULL parameters"); return STOCS_ERR_INVALID; }
-    if (const char* why = contour_params_error(p)) { set_error("stocs_check_refine_visible_contour_params: %s", why); return STOCS_ERR_INVALID; }
-    return STOCS_OK;
-}
-
 extern "C" int stocs_refine_visible_contour_last_device_ms(const stocs_ctx* c, float* contour_ms) {
     if (!c) { set_error("stocs_refine_visible_contour_last_device_ms: NULL context"); return STOCS_ERR_INVALID; }
     const RefineVisibleState* S = ctx_state_if<RefineVisibleState>(c);
@@ -973,92 +979,77 @@ extern "C" int stocs_refine_visible_contour_last_device_ms(const stocs_ctx* c, f
     return STOCS_OK;
 }
 
-// The damped call's frame with the object count in front, the contour pass inside every evaluation and the contour solve behind it.
-extern "C" int stocs_refine_poses_visible_contour(stocs_ctx* c, const float* poses, int n, const stocs_refine_visible_contour_params* prm, float* pose16_out,
-                                                  stocs_refine_visible_contour_result* out, stocs_refine_visible_trace* trace) {
-    static const char* who = "stocs_refine_poses_visible_contour";
-    if (!c) { set_error("%s: NULL context", who); return STOCS_ERR_INVALID; }
-    if (n < 0) { set_error("%s: n %d < 0", who, n); return STOCS_ERR_INVALID; }
-    if (n == 0) return STOCS_OK;
-    if (!poses || !prm || !pose16_out || !out) { set_error("%s: NULL poses, parameters or results", who); return STOCS_ERR_INVALID; }
+// The plain form: max(max_iterations, 1) evaluations per chunk, each followed by the plain solve; poses and records come back from the
+// workspace, where the records lie behind the poses.
+extern "C" int stocs_refine_poses_visible(stocs_ctx* c, const float* poses, int n, const stocs_refine_visible_params* prm, float* pose16_out,
+                                          stocs_refine_visible_result* out) {
+    static const char* who = "stocs_refine_poses_visible";
+    int rc;
+    if (visible_refuse(who, c, poses, n, prm, pose16_out, out, &rc)) return rc;
     DepthState* F = NULL;
-    { const int rc = contour_check(who, c, prm, &F); if (rc) return rc; }
-    DeviceGuard dev_guard(c->device);
-    const stocs_refine_visible_damped_params* dp = &prm->damped;
-    const bool dev_clock = c->device_clock != 0, pass = prm->contour_weight != 0.0f;
-    const size_t npix = F->npix, chunk = visible_chunk(n, npix);
-    const int groups = refine_visible_groups(npix), K = dp->base.max_iterations;
-    VisibleWork w;
-    { const int rc = visible_work(c, n, chunk, npix, groups, &w); if (rc) return rc; }
-    RefineVisibleState* S = ctx_state<RefineVisibleState>(c);
-    const size_t rows = (size_t)n * (size_t)(K + 1);
-    Carve cv;   // what comes back lies in front: accepted poses | records | trace
-    const size_t o_acc = cv.take((size_t)n * 64), o_rec = cv.take((size_t)n * sizeof(stocs_refine_visible_contour_result));
-    const size_t o_trace = cv.take(trace ? rows * sizeof(stocs_refine_visible_trace) : 0), back_all = cv.total;
-    const size_t o_state = cv.take((size_t)n * sizeof(RvDampedState)), o_done = cv.take((size_t)n * 4);
-    const size_t o_cpart = cv.take(chunk * (size_t)groups * RV_SUMS * 8), o_ccnt = cv.take(chunk * (size_t)groups * RV_COUNTS * 4), o_nobj = cv.take(4);
-    { const int rc = S->contour.grow(c->stream, cv.total); if (rc) return rc; }
-    char* base = S->contour.p;
-    float* d_acc = Carve::at<float>(base, o_acc);
-    stocs_refine_visible_contour_result* d_rec = Carve::at<stocs_refine_visible_contour_result>(base, o_rec);
-    stocs_refine_visible_trace* d_trace = trace ? Carve::at<stocs_refine_visible_trace>(base, o_trace) : NULL;
-    RvDampedState* d_state = Carve::at<RvDampedState>(base, o_state);
-    int32_t* d_done = Carve::at<int32_t>(base, o_done);
-    int32_t* d_nobj = Carve::at<int32_t>(base, o_nobj);
-    const size_t back_bytes = trace ? o_trace + rows * sizeof(stocs_refine_visible_trace) : o_rec + (size_t)n * sizeof(stocs_refine_visible_contour_result);
-    char* hin; char* hback;
-    { const int rc = pinned_for(c, (size_t)n * 64, back_bytes, &hin, &hback); if (rc) return rc; }
-    memcpy(hin, poses, (size_t)n * 64);
-    STOCS_HIP_CHECK(hipMemcpyAsync(w.pose(), hin, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));   // the slot the render reads
-    STOCS_HIP_CHECK(hipMemcpyAsync(d_acc, hin, (size_t)n * 64, hipMemcpyHostToDevice, c->stream));      // the accepted pose: the start
-    STOCS_HIP_CHECK(hipMemsetAsync(base + o_rec, 0, back_all - o_rec, c->stream));                      // records and trace
-    STOCS_HIP_CHECK(hipMemsetAsync(d_done, 0, (size_t)n * 4, c->stream));
-    STOCS_HIP_CHECK(hipMemsetAsync(d_nobj, 0, 4, c->stream));
-    const DepthArgs a = frame_args(F, 0.0f, dp->base.class_threshold);
-    const RvArgs ra = visible_args(&dp->base, groups);
-    hipLaunchKernelGGL(refine_visible_object_count_kernel, dim3((unsigned)std::min<size_t>((npix + 255) / 256, 1024)), dim3(256), 0, c->stream, frame_depth(F), frame_prob(F),
-                       npix, a.class_threshold, d_nobj);
-    STOCS_HIP_CHECK(hipGetLastError());
-    RvDampedArgs da;
-    da.max_d2 = (double)ra.max_d2; da.lambda0 = (double)dp->lambda0; da.down = (double)dp->lambda_down; da.up = (double)dp->lambda_up;
-    da.max_rot = (double)dp->max_step_rotation; da.max_trans = (double)dp->max_step_translation;
-    for (int k = 0; k < 3; ++k) da.pm[k] = (double)dp->pivot_model[k];
-    da.pivot = dp->pivot; da.K = K;
-    RcPass cp;
-    cp.ca = contour_args(prm, groups); cp.part = Carve::at<double>(base, o_cpart); cp.cnt = Carve::at<int32_t>(base, o_ccnt);
-    RcSolveArgs sa;
-    sa.w = (double)prm->contour_weight; sa.pull_d2 = (double)cp.ca.pull_d2;
-    for (int h0 = 0; h0 < n; h0 += (int)chunk) {   // all evaluations of a chunk before the next one starts
-        const int m = std::min((int)chunk, n - h0);
-        STOCS_HIP_CHECK(hipMemsetAsync(w.key(), 0xFF, (size_t)m * npix * 8, c->stream));
-        for (int e = 0; e <= K; ++e) {
-            const bool timed = dev_clock && h0 + m == n && e == K;
-            { const int rc = enqueue_evaluate(c, F, w, h0, m, a, ra, RvNoDetail(), timed, pass ? &cp : (const RcPass*)NULL); if (rc) return rc; }
-            hipLaunchKernelGGL(refine_visible_contour_solve_kernel, dim3((unsigned)m), dim3(64), 0, c->stream, w.pose() + (size_t)h0 * 16, (const double*)w.part(),
-                               (const int32_t*)w.cnt(), (const double*)cp.part, (const int32_t*)cp.cnt, groups, e, da, sa, (const int32_t*)d_nobj, d_acc + (size_t)h0 * 16,
-                               d_state + h0, d_done + h0, d_rec + h0, d_trace ? d_trace + (size_t)h0 * (size_t)(K + 1) : (stocs_refine_visible_trace*)NULL);
-            STOCS_HIP_CHECK(hipGetLastError());
-            if (timed) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[3], c->stream));
-        }
-    }
-    STOCS_HIP_CHECK(hipMemcpyAsync(hback, base, back_bytes, hipMemcpyDeviceToHost, c->stream));
-    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    S->last_ms[0] = S->last_ms[1] = S->last_ms[2] = S->last_contour_ms = -1.0f;
-    if (dev_clock) {   // with the pass the render ends where the contour kernel starts
-        float ms = 0.0f;
-        if (hipEventElapsedTime(&ms, c->ev_t[0], c->ev_t[pass ? 4 : 1]) == hipSuccess) S->last_ms[0] = ms;
-        if (pass && hipEventElapsedTime(&ms, c->ev_t[4], c->ev_t[1]) == hipSuccess) S->last_contour_ms = ms;
-        for (int k = 1; k < 3; ++k)
-            if (hipEventElapsedTime(&ms, c->ev_t[k], c->ev_t[k + 1]) == hipSuccess) S->last_ms[k] = ms;
-    }
-    memcpy(pose16_out, hback + o_acc, (size_t)n * 64);
-    memcpy(out, hback + o_rec, (size_t)n * sizeof(stocs_refine_visible_contour_result));
-    if (trace) memcpy(trace, hback + o_trace, rows * sizeof(stocs_refine_visible_trace));
+    if ((rc = visible_check(who, c, prm, &F))) return rc;
+    VisibleCall vc(c, F, n, prm);
+    if (vc.rc) return vc.rc;
+    const VisibleWork& w = vc.w;
+    STOCS_HIP_CHECK(hipMemsetAsync(w.rec(), 0, (size_t)n * sizeof(stocs_refine_visible_result), c->stream));
+    STOCS_HIP_CHECK(hipMemsetAsync(w.frozen(), 0, (size_t)n * 4, c->stream));
+    const int update = prm->max_iterations > 0 ? 1 : 0;
+    char* hback;
+    rc = vc.run(poses, std::max(prm->max_iterations, 1), NULL, NULL, [&](int h0, int m, int) -> int {
+        hipLaunchKernelGGL(refine_visible_solve_kernel<RvNoDetail>, dim3((unsigned)m), dim3(64), 0, c->stream, w.pose() + (size_t)h0 * 16, (const double*)w.part(),
+                           (const int32_t*)w.cnt(), vc.groups, update, w.frozen() + h0, w.rec() + h0, RvNoDetail());
+        STOCS_HIP_CHECK(hipGetLastError());
+        return STOCS_OK;
+    }, w.pose(), w.o_rec - w.o_pose + (size_t)n * sizeof(stocs_refine_visible_result), &hback);
+    if (rc) return rc;
+    memcpy(pose16_out, hback, (size_t)n * 64);
+    memcpy(out, hback + (w.o_rec - w.o_pose), (size_t)n * sizeof(stocs_refine_visible_result));
     return STOCS_OK;
 }
 
-// A plain, synchronous path (a test and diagnosis facility): ONE pose, pageable copies, the render and the contour pass of ONE evaluation;
-// the state and the nearest silhouette pixel per pixel, the 29 contour sums as the solve step forms them.
+extern "C" int stocs_refine_poses_visible_damped(stocs_ctx* c, const float* poses, int n, const stocs_refine_visible_damped_params* prm, float* pose16_out,
+                                                 stocs_refine_visible_damped_result* out, stocs_refine_visible_trace* trace) {
+    static const char* who = "stocs_refine_poses_visible_damped";
+    int rc;
+    if (visible_refuse(who, c, poses, n, prm, pose16_out, out, &rc)) return rc;
+    DepthState* F = NULL;
+    if (const char* why = damped_params_error(prm)) { set_error("%s: %s", who, why); return STOCS_ERR_INVALID; }   // its own parameters in front
+    if ((rc = visible_check(who, c, &prm->base, &F))) return rc;
+    return damped_call<RvDampedForm>(c, F, poses, n, prm, NULL, pose16_out, out, trace);
+}
+
+extern "C" int stocs_refine_poses_visible_contour(stocs_ctx* c, const float* poses, int n, const stocs_refine_visible_contour_params* prm, float* pose16_out,
+                                                  stocs_refine_visible_contour_result* out, stocs_refine_visible_trace* trace) {
+    static const char* who = "stocs_refine_poses_visible_contour";
+    int rc;
+    if (visible_refuse(who, c, poses, n, prm, pose16_out, out, &rc)) return rc;
+    DepthState* F = NULL;
+    if ((rc = contour_check(who, c, prm, &F))) return rc;
+    return damped_call<RvContourForm>(c, F, poses, n, &prm->damped, prm, pose16_out, out, trace);
+}
+
+// The keys as the render left them, the state per pixel, the 29 sums of one evaluation of one pose.
+extern "C" int stocs_refine_visible_detail(stocs_ctx* c, const float* pose, const stocs_refine_visible_params* prm, uint64_t* keys, uint8_t* state, double* sums29) {
+    static const char* who = "stocs_refine_visible_detail";
+    if (!c) { set_error("%s: NULL context", who); return STOCS_ERR_INVALID; }
+    if (!pose || !prm || !sums29) { set_error("%s: NULL pose, parameters or sums", who); return STOCS_ERR_INVALID; }
+    DepthState* F = NULL;
+    { const int rc = visible_check(who, c, prm, &F); if (rc) return rc; }
+    DeviceGuard dev_guard(c->device);
+    DetailWork d;
+    { const int rc = detail_begin(c, F, pose, prm->class_threshold, false, &d); if (rc) return rc; }
+    RvDetailOut det;
+    det.state = d.state; det.sums29 = d.sums29;
+    { const int rc = enqueue_render(c, d.w, 0, 1, d.a, false); if (rc) return rc; }
+    { const int rc = enqueue_accumulate(c, F, d.w, 0, 1, d.a, visible_args(prm, d.groups), det, false); if (rc) return rc; }
+    { const int rc = detail_sums(c, d, d.w.part(), d.w.cnt()); if (rc) return rc; }
+    if (keys) STOCS_HIP_CHECK(hipMemcpy(keys, d.w.key(), F->npix * 8, hipMemcpyDeviceToHost));
+    if (state) STOCS_HIP_CHECK(hipMemcpy(state, d.state, F->npix, hipMemcpyDeviceToHost));
+    STOCS_HIP_CHECK(hipMemcpy(sums29, d.sums29, RV_SUMS * 8, hipMemcpyDeviceToHost));
+    return STOCS_OK;
+}
+
+// The render and the contour pass of one evaluation of one pose: the state and the nearest silhouette pixel per pixel, the 29 contour sums.
 extern "C" int stocs_refine_visible_contour_detail(stocs_ctx* c, const float* pose, const stocs_refine_visible_contour_params* prm, uint8_t* state, int32_t* nearest,
                                                    double* sums29) {
     static const char* who = "stocs_refine_visible_contour_detail";
@@ -1067,38 +1058,16 @@ extern "C" int stocs_refine_visible_contour_detail(stocs_ctx* c, const float* po
     DepthState* F = NULL;
     { const int rc = contour_check(who, c, prm, &F); if (rc) return rc; }
     DeviceGuard dev_guard(c->device);
-    const size_t npix = F->npix;
-    const int groups = refine_visible_groups(npix);
-    VisibleWork w;
-    { const int rc = visible_work(c, 1, 1, npix, groups, &w); if (rc) return rc; }
-    RefineVisibleState* S = ctx_state<RefineVisibleState>(c);
-    Carve cv;
-    const size_t o_near = cv.take(npix * 4), o_state = cv.take(npix), o_sums = cv.take(RV_SUMS * 8);
-    const size_t o_cpart = cv.take((size_t)groups * RV_SUMS * 8), o_ccnt = cv.take((size_t)groups * RV_COUNTS * 4);
-    { const int rc = S->contour.grow(c->stream, cv.total); if (rc) return rc; }
-    char* base = S->contour.p;
+    DetailWork d;
+    { const int rc = detail_begin(c, F, pose, prm->damped.base.class_threshold, true, &d); if (rc) return rc; }
     RcDetailOut det;
-    det.state = Carve::at<uint8_t>(base, o_state); det.nearest = Carve::at<int32_t>(base, o_near);
-    RvDetailOut sums;
-    sums.state = NULL; sums.sums29 = Carve::at<double>(base, o_sums);
-    double* cpart = Carve::at<double>(base, o_cpart);
-    int32_t* ccnt = Carve::at<int32_t>(base, o_ccnt);
-    STOCS_HIP_CHECK(hipMemcpyAsync(w.pose(), pose, 64, hipMemcpyHostToDevice, c->stream));
-    STOCS_HIP_CHECK(hipMemsetAsync(w.key(), 0xFF, npix * 8, c->stream));
-    STOCS_HIP_CHECK(hipMemsetAsync(det.state, 0, npix, c->stream));
-    STOCS_HIP_CHECK(hipMemsetAsync(det.nearest, 0xFF, npix * 4, c->stream));
-    STOCS_HIP_CHECK(hipMemsetAsync(w.box(), 0x80, VSD_BOX_WORDS * 4, c->stream));
-    const DepthArgs a = frame_args(F, 0.0f, prm->damped.base.class_threshold);
-    { const int rc = mesh_enqueue_tri_keys(c, w.pose(), 1, a, w.key(), w.box()); if (rc) return rc; }
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(refine_visible_contour_kernel<RcDetailOut>), dim3((unsigned)groups, 1), dim3(256), 0, c->stream, (const unsigned long long*)w.key(),
-                       (const int32_t*)w.box(), frame_depth(F), frame_prob(F), a, contour_args(prm, groups), cpart, ccnt, det);
-    STOCS_HIP_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(refine_visible_solve_kernel<RvDetailOut>, dim3(1), dim3(64), 0, c->stream, w.pose(), (const double*)cpart, (const int32_t*)ccnt, groups, 0,
-                       w.frozen(), w.rec(), sums);
-    STOCS_HIP_CHECK(hipGetLastError());
-    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (state) STOCS_HIP_CHECK(hipMemcpy(state, det.state, npix, hipMemcpyDeviceToHost));
-    if (nearest) STOCS_HIP_CHECK(hipMemcpy(nearest, det.nearest, npix * 4, hipMemcpyDeviceToHost));
-    STOCS_HIP_CHECK(hipMemcpy(sums29, sums.sums29, RV_SUMS * 8, hipMemcpyDeviceToHost));
+    det.state = d.state; det.nearest = d.nearest;
+    const RcPass cp = {contour_args(prm, d.groups), d.cpart, d.ccnt, true};
+    { const int rc = enqueue_render(c, d.w, 0, 1, d.a, false); if (rc) return rc; }
+    { const int rc = enqueue_contour(c, F, d.w, 1, d.a, cp, det, false); if (rc) return rc; }
+    { const int rc = detail_sums(c, d, cp.part, cp.cnt); if (rc) return rc; }
+    if (state) STOCS_HIP_CHECK(hipMemcpy(state, d.state, F->npix, hipMemcpyDeviceToHost));
+    if (nearest) STOCS_HIP_CHECK(hipMemcpy(nearest, d.nearest, F->npix * 4, hipMemcpyDeviceToHost));
+    STOCS_HIP_CHECK(hipMemcpy(sums29, d.sums29, RV_SUMS * 8, hipMemcpyDeviceToHost));
     return STOCS_OK;
 }

@@ -68,6 +68,10 @@ _REFINE_VISIBLE_CONTOUR_DTYPE = np.dtype(_REFINE_VISIBLE_DAMPED_DTYPE.descr + [(
 assert _REFINE_VISIBLE_CONTOUR_DTYPE.itemsize == C.sizeof(capi.RefineVisibleContourResult)
 _REFINE_VISIBLE_TRACE_DTYPE = np.dtype([("pose", np.float32, 16), ("cost", np.float64), ("lambda", np.float64), ("accepted", np.int32), ("state", np.int32)])
 assert _REFINE_VISIBLE_TRACE_DTYPE.itemsize == C.sizeof(capi.RefineVisibleTrace)
+# the forms of the visible-surface refinement by the suffix of their entry points: parameter struct, record struct, record dtype
+_REFINE_VISIBLE_FORMS = {"": (capi.RefineVisibleParams, capi.RefineVisibleResult, _REFINE_VISIBLE_DTYPE),
+                         "_damped": (capi.RefineVisibleDampedParams, capi.RefineVisibleDampedResult, _REFINE_VISIBLE_DAMPED_DTYPE),
+                         "_contour": (capi.RefineVisibleContourParams, capi.RefineVisibleContourResult, _REFINE_VISIBLE_CONTOUR_DTYPE)}
 _SCENE_RECORD_DTYPE = np.dtype([(f[0], np.int32) for f in capi.SceneRecord._fields_])
 assert _SCENE_RECORD_DTYPE.itemsize == C.sizeof(capi.SceneRecord)
 _SCENE_RESULT_DTYPE = np.dtype([(f[0], np.int32) for f in capi.SceneResult._fields_])
@@ -789,14 +793,54 @@ class StocsEstimator:
         capi.check(self.L.stocs_render_mesh_last_device_ms(self.h, C.byref(a), C.byref(b)))
         return a.value, b.value
 
-    def _refine_visible_params(self, who, params):
-        prm = capi.RefineVisibleParams()
-        self.L.stocs_default_refine_visible_params(C.byref(prm))
+    @staticmethod
+    def _fill_params(who, prm, params):
+        """keyword arguments into a ctypes parameter struct.  A struct that extends another holds it in its first member, `base` or
+        `damped`: a name is set in the struct that has it, a name that none has is a TypeError -> the innermost struct"""
+        levels = [prm]
+        while levels[-1]._fields_[0][0] in ("base", "damped"):
+            levels.append(getattr(levels[-1], levels[-1]._fields_[0][0]))
         for k, v in params.items():
-            if k not in dict(capi.RefineVisibleParams._fields_):
+            s = next((s for s in levels if k in dict(s._fields_) and k not in ("base", "damped")), None)
+            if s is None:
                 raise TypeError("%s: unknown parameter %r" % (who, k))
-            setattr(prm, k, v)
-        return prm
+            setattr(s, k, v)
+        return levels[-1]
+
+    def _take_pivot_model(self, who, params, damped):
+        """params without pivot_model, which goes into the damped parameters: 3 floats, by default the mean of the vertices of set_mesh"""
+        params = dict(params)
+        pm = np.asarray(params.pop("pivot_model", getattr(self, "_mesh_centre", (0.0, 0.0, 0.0))), np.float32).reshape(-1)
+        if pm.size != 3:
+            raise ValueError("%s: pivot_model is 3 floats" % who)
+        damped.pivot_model[:] = [float(x) for x in pm]
+        return params
+
+    def _refine_visible_params(self, who, params, form=""):
+        """the parameter struct of a form ("", "_damped", "_contour"): params over the library's defaults -> (struct, its plain part)"""
+        prm = _REFINE_VISIBLE_FORMS[form][0]()
+        getattr(self.L, "stocs_default_refine_visible%s_params" % form)(C.byref(prm))
+        if form:
+            params = self._take_pivot_model(who, params, prm if form == "_damped" else prm.damped)
+        return prm, self._fill_params(who, prm, params)
+
+    def _refine_poses_visible(self, form, poses16, params, trace=None):
+        """poses in, (n, 16) out, the form's records and, for a form that has one (trace is not None) and when asked for, the trace"""
+        who = "refine_poses_visible" + form
+        P, pP = capi.f32(poses16)
+        if P.size % 16:
+            raise ValueError("%s: poses are 16 floats each" % who)
+        n = P.size // 16
+        prm, base = self._refine_visible_params(who, params, form)
+        out = np.zeros((n, 16), np.float32)
+        buf = (_REFINE_VISIBLE_FORMS[form][1] * max(n, 1))()
+        rows = max(base.max_iterations, 0) + 1
+        tr = (capi.RefineVisibleTrace * max(n * rows, 1))() if trace else None
+        capi.check(getattr(self.L, "stocs_" + who)(self.h, pP, n, C.byref(prm), out.ctypes.data_as(capi._fp), buf, *(() if trace is None else (tr,))))
+        rec = np.frombuffer(buf, dtype=_REFINE_VISIBLE_FORMS[form][2], count=n).copy()
+        if not trace:
+            return out, rec
+        return out, rec, np.frombuffer(tr, dtype=_REFINE_VISIBLE_TRACE_DTYPE, count=n * rows).copy().reshape(n, rows)
 
     def refine_poses_visible(self, poses16, **params):
         """n camera-frame poses of the mesh of set_mesh refined against the frame of set_frame on the surface each pose shows
@@ -804,15 +848,7 @@ class StocsEstimator:
         float32, records): a structured array with the fields of stocs_refine_visible_result, one per pose, describing the last
         evaluation.  params: max_iterations, max_distance, min_view_cos, class_threshold over the library's defaults;
         max_iterations=0 scores the poses and changes nothing."""
-        P, pP = capi.f32(poses16)
-        if P.size % 16:
-            raise ValueError("refine_poses_visible: poses are 16 floats each")
-        n = P.size // 16
-        prm = self._refine_visible_params("refine_poses_visible", params)
-        out = np.zeros((n, 16), np.float32)
-        buf = (capi.RefineVisibleResult * max(n, 1))()
-        capi.check(self.L.stocs_refine_poses_visible(self.h, pP, n, C.byref(prm), out.ctypes.data_as(capi._fp), buf))
-        return out, np.frombuffer(buf, dtype=_REFINE_VISIBLE_DTYPE, count=n).copy()
+        return self._refine_poses_visible("", poses16, params)
 
     def refine_poses_visible_damped(self, poses16, trace=False, **params):
         """refine_poses_visible with damped, bounded steps about a point of the object that are taken only when they lower the cost
@@ -821,52 +857,7 @@ class StocsEstimator:
         rejected, cost, lambda), trace (n, max_iterations + 1) rows of stocs_refine_visible_trace.  params: the plain form's and lambda0,
         lambda_down, lambda_up, max_step_rotation (rad), max_step_translation (m), pivot (0: the camera's origin, 1: pivot_model),
         pivot_model (3 floats in the model frame; default: the mean of the vertices given to set_mesh) over the library's defaults."""
-        P, pP = capi.f32(poses16)
-        if P.size % 16:
-            raise ValueError("refine_poses_visible_damped: poses are 16 floats each")
-        n = P.size // 16
-        prm = capi.RefineVisibleDampedParams()
-        self.L.stocs_default_refine_visible_damped_params(C.byref(prm))
-        params = dict(params)
-        pm = np.asarray(params.pop("pivot_model", getattr(self, "_mesh_centre", (0.0, 0.0, 0.0))), np.float32).reshape(-1)
-        if pm.size != 3:
-            raise ValueError("refine_poses_visible_damped: pivot_model is 3 floats")
-        prm.pivot_model[:] = [float(x) for x in pm]
-        for k, v in params.items():
-            if k in dict(capi.RefineVisibleParams._fields_):
-                setattr(prm.base, k, v)
-            elif k in dict(capi.RefineVisibleDampedParams._fields_) and k != "base":
-                setattr(prm, k, v)
-            else:
-                raise TypeError("refine_poses_visible_damped: unknown parameter %r" % (k,))
-        out = np.zeros((n, 16), np.float32)
-        buf = (capi.RefineVisibleDampedResult * max(n, 1))()
-        rows = max(prm.base.max_iterations, 0) + 1
-        tr = (capi.RefineVisibleTrace * max(n * rows, 1))() if trace else None
-        capi.check(self.L.stocs_refine_poses_visible_damped(self.h, pP, n, C.byref(prm), out.ctypes.data_as(capi._fp), buf, tr))
-        rec = np.frombuffer(buf, dtype=_REFINE_VISIBLE_DAMPED_DTYPE, count=n).copy()
-        if not trace:
-            return out, rec
-        return out, rec, np.frombuffer(tr, dtype=_REFINE_VISIBLE_TRACE_DTYPE, count=n * rows).copy().reshape(n, rows)
-
-    def _refine_visible_contour_params(self, who, params):
-        prm = capi.RefineVisibleContourParams()
-        self.L.stocs_default_refine_visible_contour_params(C.byref(prm))
-        params = dict(params)
-        pm = np.asarray(params.pop("pivot_model", getattr(self, "_mesh_centre", (0.0, 0.0, 0.0))), np.float32).reshape(-1)
-        if pm.size != 3:
-            raise ValueError("%s: pivot_model is 3 floats" % who)
-        prm.damped.pivot_model[:] = [float(x) for x in pm]
-        for k, v in params.items():
-            if k in dict(capi.RefineVisibleParams._fields_):
-                setattr(prm.damped.base, k, v)
-            elif k in dict(capi.RefineVisibleDampedParams._fields_) and k != "base":
-                setattr(prm.damped, k, v)
-            elif k in dict(capi.RefineVisibleContourParams._fields_) and k != "damped":
-                setattr(prm, k, v)
-            else:
-                raise TypeError("%s: unknown parameter %r" % (who, k))
-        return prm
+        return self._refine_poses_visible("_damped", poses16, params, bool(trace))
 
     def refine_poses_visible_contour(self, poses16, trace=False, **params):
         """refine_poses_visible_damped with the contour term: the frame's object pixels (class image) that a pose's render leaves uncovered
@@ -874,20 +865,7 @@ class StocsEstimator:
         trace=True: records a structured array with the fields of stocs_refine_visible_contour_result (the damped record of the RETURNED
         pose, object_px, uncovered, unreached, beyond, pulled, pull_rms).  params: the damped form's and contour_weight, pull_radius_px,
         pull_distance over the library's defaults; the frame of set_frame must carry a class image."""
-        P, pP = capi.f32(poses16)
-        if P.size % 16:
-            raise ValueError("refine_poses_visible_contour: poses are 16 floats each")
-        n = P.size // 16
-        prm = self._refine_visible_contour_params("refine_poses_visible_contour", params)
-        out = np.zeros((n, 16), np.float32)
-        buf = (capi.RefineVisibleContourResult * max(n, 1))()
-        rows = max(prm.damped.base.max_iterations, 0) + 1
-        tr = (capi.RefineVisibleTrace * max(n * rows, 1))() if trace else None
-        capi.check(self.L.stocs_refine_poses_visible_contour(self.h, pP, n, C.byref(prm), out.ctypes.data_as(capi._fp), buf, tr))
-        rec = np.frombuffer(buf, dtype=_REFINE_VISIBLE_CONTOUR_DTYPE, count=n).copy()
-        if not trace:
-            return out, rec
-        return out, rec, np.frombuffer(tr, dtype=_REFINE_VISIBLE_TRACE_DTYPE, count=n * rows).copy().reshape(n, rows)
+        return self._refine_poses_visible("_contour", poses16, params, bool(trace))
 
     def refine_visible_contour_detail(self, pose16, **params):
         """The contour pass of one evaluation of one pose (stocs_refine_visible_contour_detail) -> (state (height, width) uint8: 1
@@ -896,7 +874,7 @@ class StocsEstimator:
         P, pP = capi.f32(pose16)
         if P.size != 16:
             raise ValueError("refine_visible_contour_detail: one pose of 16 floats")
-        prm = self._refine_visible_contour_params("refine_visible_contour_detail", params)
+        prm, _ = self._refine_visible_params("refine_visible_contour_detail", params, "_contour")
         H, W = self._frame_shape("refine_visible_contour_detail")
         st = np.zeros((H, W), np.uint8); near = np.zeros((H, W), np.int32); sums = np.zeros(29, np.float64)
         capi.check(self.L.stocs_refine_visible_contour_detail(self.h, pP, C.byref(prm), st.ctypes.data_as(capi._u8p), near.ctypes.data_as(capi._ip),
@@ -917,7 +895,7 @@ class StocsEstimator:
         P, pP = capi.f32(pose16)
         if P.size != 16:
             raise ValueError("refine_visible_detail: one pose of 16 floats")
-        prm = self._refine_visible_params("refine_visible_detail", params)
+        prm, _ = self._refine_visible_params("refine_visible_detail", params)
         H, W = self._frame_shape("refine_visible_detail")
         keys = np.zeros((H, W), np.uint64); st = np.zeros((H, W), np.uint8); sums = np.zeros(29, np.float64)
         capi.check(self.L.stocs_refine_visible_detail(self.h, pP, C.byref(prm), keys.ctypes.data_as(C.POINTER(C.c_uint64)), st.ctypes.data_as(capi._u8p),

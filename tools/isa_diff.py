@@ -7,8 +7,8 @@ usage: isa_diff.py OLD.s NEW.s
 A kernel's body is the text between its label and its .Lfunc_end; mangled names and basic-block numbers are replaced by
 placeholders before the comparison.  Prints one markdown table row per kernel of NEW: identical or the number of differing lines,
 and VGPRs / SGPRs / LDS bytes / scratch bytes of both listings.  Kernels are paired by their demangled names (any file); for the
-queue and per-step kernels of lcp.hip and the accumulation of refine.hip pair_name() also knows how their template arguments were
-renamed."""
+queue and per-step kernels of lcp.hip, the accumulation of refine.hip and the damped solve of refine_visible.hip pair_name() also knows
+how their template arguments were renamed."""
 import difflib
 import re
 import subprocess
@@ -58,6 +58,9 @@ def pair_name(old):
     # form is what an older listing calls robust_fused_kernel<L>
     d = d.replace(", RefNoGate>", ">").replace(", RefGate>", ", gate>")
     d = re.sub(r"robust_fused_kernel<(\w+)>", r"refine_accumulate_kernel<\1, gate>", d)
+    # refine_visible.hip: the two forms of the one damped solve are what an older listing calls ..._damped_solve_kernel and ..._contour_solve_kernel
+    d = d.replace("refine_visible_damped_solve_kernel<RvDampedForm>", "refine_visible_damped_solve_kernel")
+    d = d.replace("refine_visible_damped_solve_kernel<RvContourForm>", "refine_visible_contour_solve_kernel")
     return d.replace(", RefNoDetail", "").replace("<RefNoDetail>", "")
 
 
