@@ -1432,6 +1432,35 @@ inline SceneSelection select_scene(const std::vector<stocs_estimator*>& estimato
     return select_scene(estimators, poses, std::vector<SceneSurface>(), max_per_object, with_labels, prm, render, claim);
 }
 
+// Not in the reference (its class and edge images come from a network): both from the depth image alone (stocs_segment_frame) -- the
+// support plane removed, what stands on it split into depth-connected segments.  class_prob is what the estimator's image constructor
+// and set_frame take, edge what they take as the edge map (255 = interior), labels the segment numbers 1 .. records.size().
+struct SegmentedFrame {
+    stocs_segment_result result;
+    std::vector<stocs_segment_record> records;
+    std::vector<uint16_t> class_prob;
+    std::vector<int32_t> labels;
+    std::vector<uint8_t> edge;
+};
+inline stocs_segment_params default_segment_params() { stocs_segment_params p; stocs_default_segment_params(&p); return p; }
+inline SegmentedFrame segment_frame(const uint16_t* depth, const std::vector<float>& camera_intrinsics, int image_width, int image_height, float read_depth_scale,
+                                    const stocs_segment_params& prm = default_segment_params(), int device = -1) {
+    if (camera_intrinsics.size() < 4) throw std::runtime_error("camera_intrinsics must hold {fx, cx, fy, cy}");
+    if (image_width < 1 || image_height < 1 || prm.min_pixels < 1) throw std::runtime_error("segment_frame: an empty frame or min_pixels < 1");
+    stocs_camera cam;
+    cam.fx = camera_intrinsics[0]; cam.cx = camera_intrinsics[1]; cam.fy = camera_intrinsics[2]; cam.cy = camera_intrinsics[3];
+    cam.depth_scale = read_depth_scale; cam.width = image_width; cam.height = image_height;
+    cam.normal_method = STOCS_NORMALS_DEPTH_GRADIENT;   // (not looked at)
+    SegmentedFrame out;
+    const size_t npix = (size_t)image_width * image_height, cap = npix / (size_t)prm.min_pixels;   // no more segments than this fit the frame
+    out.records.resize(cap ? cap : 1);
+    out.class_prob.resize(npix); out.labels.resize(npix); out.edge.resize(npix);
+    if (stocs_segment_frame(&cam, depth, &prm, device, out.class_prob.data(), out.labels.data(), out.edge.data(), out.records.data(), (int)cap, &out.result) != STOCS_OK)
+        throw std::runtime_error(std::string("stocs_segment_frame: ") + stocs_last_error());
+    out.records.resize((size_t)out.result.n_segments);
+    return out;
+}
+
 // Not in the reference (its driver runs once per object): every object of one frame from one ingest (stocs_ingest_scene_multi).
 // class_probability_maps holds class_thresholds.size() images of image_height x image_width, object after object; edge (may be NULL)
 // is shared by all of them.  Scene k is what the estimator's own ingest makes of (depth, map k, class_thresholds[k]), bit for bit.

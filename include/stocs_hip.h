@@ -416,6 +416,79 @@ int stocs_preprocess_model(const float* raw_pos3, int n_raw, float normal_radius
  * pageable memory at no cost); this gives the calling thread's cache and block back. */
 int stocs_trim(void);
 
+/* ---- depth-only frames: support-plane removal and depth-connected segments (no reference counterpart; csrc/segment.hip, restated in
+ * float32 numpy in tests/segment_ref.py, equal bit for bit).  In the reference the class-probability image and the edge image come from
+ * a network; a caller with a depth camera and no network gets both from the frame's geometry here, in the formats the existing entry
+ * points take: a uint16 class image (stocs_ingest_scene, stocs_ctx_set_frame), a uint8 edge image (stocs_set_edge_map), a label image
+ * and one record per segment.  Stand-alone like stocs_ingest_scene: `device` (-1: the current one), no context; a per-thread cached
+ * workspace and pinned block of its own that stocs_trim gives back; one read-back and one synchronisation per call; a second call of
+ * the same size allocates nothing (stocs_device_alloc_count).  Every step is float, one IEEE operation at a time, no contraction;
+ * 3-term sums are e0 + (e1 + e2); a comparison with NaN is false.  Pixel (row i, col j) has linear index i * width + j.
+ *
+ *   1. Points.  z = (float)raw * depth_scale; x = (float)(((double)j - (double)cx) * (double)z / (double)fx), y likewise with i, cy,
+ *      fy (as the ingest forms them).  A pixel is VALID when raw != 0 and z <= max_depth.  cam->normal_method is ignored.
+ *   2. Hypotheses.  Hypothesis h (0 .. plane_hypotheses - 1) draws the pixels i_k = ((rng64(seed, h, k) >> 32) * npix) >> 32, k = 0, 1, 2
+ *      (rng64 of csrc/stocs_math.h, npix = width * height, 64-bit unsigned arithmetic), with points A, B, C.  e1 = B - A, e2 = C - A,
+ *      m = e1 x e2 (each component a * b - c * d), mm = m0 m0 + (m1 m1 + m2 m2).  It is DEAD when one of the pixels is not valid, two
+ *      indices are equal, or mm is not > 0 and finite.  The SCORED pixels are the valid ones with i % score_stride == 0 and
+ *      j % score_stride == 0 (n_scored of them).  A pixel X is an inlier of h when, with d = X - A, s = m0 dx + (m1 dy + m2 dz),
+ *      s * s <= (tol * tol) * mm.  count(h) = the inliers among the scored pixels.  The winner is the live h of count > 0 with the
+ *      largest (count << 32) | ~h: the largest count, the lowest h on a tie; `winner` and `winner_count` report it (-1 and 0 without
+ *      one).  plane_found = 0 when plane_hypotheses == 0, when there is no winner, or when (double)count < (double)plane_min_share *
+ *      (double)n_scored -- then plane is zero, n_refit, n_on_plane, n_above and n_below are 0.
+ *   3. Refit.  Over EVERY valid pixel (unstrided) that is an inlier of the winner and has |x|, |y|, |z| < 16: q = llrint((double)v *
+ *      65536) per coordinate (exact: the product is a double, rounded to nearest even), and the int64 sums n_refit = sum 1, Sx, Sy, Sz,
+ *      Sxx, Sxy, Sxz, Syy, Syz, Szz of q and their products (stocs_segment_last_moments gives the ten).  |q| < 2^20, a product < 2^40,
+ *      and a frame holds at most 2^22 pixels (more: STOCS_ERR_CAPACITY), so every sum stays below 2^62: exact, whatever the order.
+ *      In double: c = S / n / 65536, cov_ab = Sab / n / 2^32 - c_a c_b; the eigenvector of the smallest eigenvalue by cyclic Jacobi
+ *      (pairs (0,1), (0,2), (1,2), 12 sweeps), normalised; d = -(n . c); n and d negated when d < 0; one cast to float each.  With
+ *      n_refit < 3 or a non-finite result the winner's own plane is used the same way: n = m / |m|, d = -(n . A).  plane is
+ *      (n0, n1, n2, d): n . X + d = 0, d >= 0 (the normal faces the camera).
+ *   4. Heights.  h = (n0 x + (n1 y + n2 z)) + d on the float plane of `out`.  Among the valid pixels: on the plane when
+ *      fabsf(h) <= tol (n_on_plane), above when h > tol (n_above), below when h < -tol (n_below).  FOREGROUND: valid, h > tol and
+ *      h <= max_height.  Without a plane every valid pixel is foreground.
+ *   5. Components.  4-neighbourhood; two foreground neighbours a, b join when fabsf(za - zb) <= jump_abs + jump_rel * fminf(za, zb).
+ *      A component's root is the lowest linear index among its pixels.  n_components counts all of them; those of fewer than
+ *      min_pixels pixels are dropped; the others are the segments, numbered 1 .. n_segments in the order of their roots.
+ *      n_segments > cap_records: STOCS_ERR_CAPACITY with `out` filled, no record and no image written.
+ *   6. Images (each height * width, or NULL).  labels: the segment's number, 0 elsewhere.  class_prob: 10000 in a segment, 0 elsewhere.
+ *      edge: 255 where the pixel has a label and every 4-neighbour inside the image has the same label, 0 elsewhere (the png
+ *      convention of stocs_set_edge_map: 255 = not an edge).
+ *   7. Records.  root, pixels, the box c0 <= col <= c1, r0 <= row <= r1, and zmin / zmax, the extremes of the float z.
+ *   8. Checked in this order: NULL cam / depth / p / out; width or height < 1; a parameter outside its range
+ *      (stocs_check_segment_params; plane_hypotheses at most 2^20); cap_records < 0 or records == NULL with cap_records > 0: all
+ *      STOCS_ERR_INVALID.  Then more than 2^22 pixels: STOCS_ERR_CAPACITY; a STOCS_SEGMENT_FORM other than 0, 1, 2: STOCS_ERR_INVALID.
+ *      A frame with no valid pixel is not an error: zero result, empty images.
+ * STOCS_SEGMENT_FORM in the environment forces the label kernel's form (1: union-find in device memory; 2: tiles of
+ * stocs_segment_tile in LDS, then the tile borders; 0 or unset: the default); both end at the same roots.  With STOCS_SEGMENT_CLOCK=1
+ * stocs_segment_last_device_ms gives the HIP-event times of the calling thread's last call: hypotheses + scoring + winner, and the
+ * label kernels up to the flattened roots (STOCS_ERR_STATE without such a call). ---- */
+typedef struct stocs_segment_params {
+    float    max_depth;         /* m, > 0 finite: farther pixels are not valid (default 2.0, the ingest's cut)       */
+    int32_t  plane_hypotheses;  /* >= 0; 0: no plane search, every valid pixel is foreground (default 1024)          */
+    int32_t  score_stride;      /* >= 1: hypotheses are scored on pixels with row % s == 0 and col % s == 0 (4)      */
+    float    plane_tolerance;   /* m, > 0 finite (0.01)                                                               */
+    float    plane_min_share;   /* [0, 1]: least share of the scored pixels on the winning plane (0.15)              */
+    float    max_height;        /* m, > 0 finite: foreground stands at most this far off the plane (0.5)             */
+    float    jump_abs, jump_rel;/* >= 0 finite: neighbours join when |za - zb| <= jump_abs + jump_rel * min(za, zb) (0.005, 0.01) */
+    int32_t  min_pixels;        /* >= 1: smaller components are dropped (200)                                         */
+    uint64_t seed;              /* (1)                                                                                */
+} stocs_segment_params;
+typedef struct stocs_segment_result {
+    float   plane[4];           /* unit normal facing the camera and offset: n.X + d = 0, d > 0; zeros without one   */
+    int32_t plane_found, winner, winner_count, n_valid, n_scored, n_refit, n_on_plane, n_above, n_below,
+            n_components, n_segments, reserved;
+} stocs_segment_result;
+typedef struct stocs_segment_record { int32_t root, pixels, c0, r0, c1, r1; float zmin, zmax; } stocs_segment_record; /* 32 bytes */
+void stocs_default_segment_params(stocs_segment_params*);
+int  stocs_check_segment_params(const stocs_segment_params*);                 /* host only */
+int  stocs_segment_frame(const stocs_camera* cam, const uint16_t* depth, const stocs_segment_params* p, int device,
+                         uint16_t* class_prob /* H W or NULL */, int32_t* labels /* H W or NULL */, uint8_t* edge /* H W or NULL */,
+                         stocs_segment_record* records, int cap_records, stocs_segment_result* out);
+int  stocs_segment_tile(int* width, int* height);                             /* host only: the label kernel's tile */
+int  stocs_segment_last_device_ms(float* score_ms, float* label_ms);          /* with STOCS_SEGMENT_CLOCK=1         */
+int  stocs_segment_last_moments(int64_t* moments10);                          /* n_refit, Sx, Sy, Sz, Sxx, Sxy, Sxz, Syy, Syz, Szz of the thread's last call */
+
 /* ---- files either side of the path (host code; zlib only): what the reference's constructor and driver read and
  * write through OpenCV / PCL.  stocs_png_read: 8/16-bit grey / RGB (+alpha), non-interlaced; pixels = height rows of
  * width*channels samples of bit_depth/8 bytes, 16-bit in host byte order; pixels == NULL queries the sizes.

@@ -89,6 +89,11 @@
 // and class-probability map (stocs_explain_poses); one "mask r: footprint .. visible .. hidden .. agree .. in_front .. behind .. no_depth ..
 // on_mask .." line per instance, and the label image to labels_<object>.pgm next to <out>: binary 16-bit PGM (P5, maxval 65535, most
 // significant byte first), value = rank + 1, 0 = no instance.  Every other line and file is what the run writes without the flag.
+// --segment [tol[,min_pixels]] (a scene directory, a single object): a depth-only frame.  probability_maps is not read: the class image is made
+// from depth.png (stocs_segment_frame: the support plane within tol metres removed, what stands on it split into depth-connected segments of
+// min_pixels or more; the library's defaults unless given) and goes to the ingest and, where a frame is set, to set_frame; one "segment: plane
+// found (n0 n1 n2 d), .. pixels on it, .. components, .. segments kept" line.  --segment-edges (with --segment, refused without it): the edge
+// image of the same call goes to stocs_set_edge_map, so sampling runs in instance mode.
 // The reference edits its per-data-set constants in the source (README.md:42-66); here they are options with the
 // reference's YCB values as defaults.
 #include <algorithm>
@@ -771,6 +776,8 @@ int main(int argc, char** argv) {
     VsdOptions vsd_opt = {false, 0.0f, 0.0f, 0};
     RefineVisibleOptions rv_opt = {false, 0, -1.0f, -1.0f, 0, false, -1.0f, -1.0f, -1.0f, {0.0f, 0.0f, 0.0f}, false, -1.0f, -1, -1.0f};
     bool damped_bad = false, contour_bad = false;
+    bool do_segment = false, segment_edges = false, segment_bad = false;   // --segment [tol[,min_pixels]] [--segment-edges]
+    stocs_segment_params seg_prm = stocs::default_segment_params();
     std::string mesh_path, surface = "points";
     bool have_vsd_delta = false, have_surfel_radius = false;
     stocs_instance_params inst_prm = stocs::stocs_estimator::default_instance_params();
@@ -779,6 +786,16 @@ int main(int argc, char** argv) {
         if (std::string(argv[i]) == "--depth-check") { depth_check = 1; --i; continue; }   // the options without a value
         if (std::string(argv[i]) == "--masks") { do_masks = true; --i; continue; }
         if (std::string(argv[i]) == "--scene-select") { scene_opt.on = true; --i; continue; }
+        if (std::string(argv[i]) == "--segment-edges") { segment_edges = true; --i; continue; }
+        if (std::string(argv[i]) == "--segment") {   // [tol[,min_pixels]]: the class image from the depth image; the value may be left out
+            do_segment = true;
+            if (i + 1 >= argc || std::string(argv[i + 1]).compare(0, 2, "--") == 0) { --i; continue; }
+            const std::string sv = argv[i + 1];
+            char tail = 0;
+            const int got = sscanf(sv.c_str(), "%f,%d%c", &seg_prm.plane_tolerance, &seg_prm.min_pixels, &tail);
+            if (got < 1 || got > 2 || (size_t)std::count(sv.begin(), sv.end(), ',') + 1 != (size_t)got || stocs_check_segment_params(&seg_prm) != STOCS_OK) segment_bad = true;
+            continue;
+        }
         if (std::string(argv[i]) == "--vsd") { vsd_opt.on = true; --i; continue; }   // with --gt: the visible-surface discrepancy too
         if (std::string(argv[i]) == "--damped") {   // [lambda0[,rot_deg[,trans_m]]]: the value may be left out
             rv_opt.damped = true;
@@ -870,6 +887,10 @@ int main(int argc, char** argv) {
         }
     }
 
+    if (segment_bad || (segment_edges && !do_segment) || (do_segment && (clouds || a2.find(',') != std::string::npos))) {   // refused before any search
+        std::cerr << "--segment [tol[,min_pixels]] needs a scene directory, a single object, tol > 0 and min_pixels >= 1; --segment-edges needs --segment" << std::endl;
+        return -1;
+    }
     std::vector<float> mesh_v;
     std::vector<int32_t> mesh_t;
     if (surface != "points" && surface != "mesh") { std::cerr << "--surface takes points or mesh" << std::endl; return -1; }
@@ -1021,10 +1042,25 @@ int main(int argc, char** argv) {
             // :207-208 (only the reference's own <scene>/dbg is wiped; a directory named with --dbg is merely created)
             if (system(((own_dbg ? "rm -rf '" + dbg_dir + "' && " : std::string()) + "mkdir -p '" + dbg_dir + "'").c_str()) != 0) std::cerr << "cannot create " << dbg_dir << std::endl;
             std::cout << "############# RUNNING STOCS for Scene: " << scene_path << ", Object: " << object_name << " ##############" << std::endl;
+            if (do_segment) {   // no probability_maps: the class image (and with --segment-edges the edge image) comes from the depth image
+                std::vector<uint16_t> depth;
+                stocs::read_image(depth_path, 1, 16, image_width, image_height, &depth);
+                const stocs::SegmentedFrame seg = stocs::segment_frame(depth.data(), cam_intrinsics, image_width, image_height, depth_scale, seg_prm);
+                const stocs_segment_result& sr = seg.result;
+                std::cout << "segment: plane " << (sr.plane_found ? "found" : "not found") << " (" << sr.plane[0] << " " << sr.plane[1] << " " << sr.plane[2] << " " << sr.plane[3]
+                          << "), " << sr.n_on_plane << " pixels on it, " << sr.n_components << " components, " << sr.n_segments << " segments kept" << std::endl;
+                stocs::ModelCloud model;
+                stocs::read_ply(model_path, &model, true);
+                est.reset(new stocs::stocs_estimator(model, model_map, depth.data(), seg.class_prob.data(), segment_edges ? seg.edge.data() : NULL, dbg_dir, cam_intrinsics,
+                                                     image_width, image_height, depth_scale, 1.0f, voxel_size, distance_threshold, ppf_tr_discretization,
+                                                     ppf_rot_discretization, edge_threshold, class_threshold));
+                if (depth_check || do_masks || vsd_opt.on || rv_opt.on) est->set_frame(depth.data(), seg.class_prob.data(), cam_intrinsics, depth_scale);
+            } else {
             est.reset(new stocs::stocs_estimator(model_path, model_map, rgb_path, depth_path, class_probability_path, edge_probability_path, dbg_dir, cam_intrinsics,
                                                  image_width, image_height, depth_scale, 1.0f, voxel_size, distance_threshold, ppf_tr_discretization,
                                                  ppf_rot_discretization, edge_threshold, class_threshold));
-            if (depth_check || do_masks || vsd_opt.on || rv_opt.on) {   // the frame the scene was ingested from, for stocs_depth_check_poses / stocs_explain_poses / stocs_pose_errors_vsd
+            }
+            if (!do_segment && (depth_check || do_masks || vsd_opt.on || rv_opt.on)) {   // the frame the scene was ingested from, for stocs_depth_check_poses / stocs_explain_poses / stocs_pose_errors_vsd
                 std::vector<uint16_t> depth, prob;
                 stocs::read_image(depth_path, 1, 16, image_width, image_height, &depth);
                 stocs::read_image(class_probability_path, 1, 16, image_width, image_height, &prob);

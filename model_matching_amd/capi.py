@@ -159,6 +159,23 @@ class RefineVisibleContourResult(C.Structure):
                 ("pulled", C.c_int32), ("pull_rms", C.c_float)]
 
 
+class SegmentParams(C.Structure):
+    _fields_ = [("max_depth", C.c_float), ("plane_hypotheses", C.c_int32), ("score_stride", C.c_int32), ("plane_tolerance", C.c_float),
+                ("plane_min_share", C.c_float), ("max_height", C.c_float), ("jump_abs", C.c_float), ("jump_rel", C.c_float), ("min_pixels", C.c_int32),
+                ("seed", C.c_uint64)]
+
+
+class SegmentResult(C.Structure):
+    _fields_ = [("plane", C.c_float * 4), ("plane_found", C.c_int32), ("winner", C.c_int32), ("winner_count", C.c_int32), ("n_valid", C.c_int32),
+                ("n_scored", C.c_int32), ("n_refit", C.c_int32), ("n_on_plane", C.c_int32), ("n_above", C.c_int32), ("n_below", C.c_int32),
+                ("n_components", C.c_int32), ("n_segments", C.c_int32), ("reserved", C.c_int32)]
+
+
+class SegmentRecord(C.Structure):
+    _fields_ = [("root", C.c_int32), ("pixels", C.c_int32), ("c0", C.c_int32), ("r0", C.c_int32), ("c1", C.c_int32), ("r1", C.c_int32),
+                ("zmin", C.c_float), ("zmax", C.c_float)]
+
+
 class SceneRecord(C.Structure):
     _fields_ = [("footprint", C.c_int32), ("no_depth", C.c_int32), ("agree", C.c_int32), ("in_front", C.c_int32), ("behind", C.c_int32),
                 ("on_mask", C.c_int32), ("claimed", C.c_int32)]
@@ -265,6 +282,13 @@ SIGNATURES = {
                                            C.c_int, _ip]),
     "stocs_preprocess_model": (C.c_int, [_fp, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, _fp, _fp, C.c_int, _intp]),
     "stocs_trim": (C.c_int, []),
+    "stocs_default_segment_params": (None, [C.POINTER(SegmentParams)]),
+    "stocs_check_segment_params": (C.c_int, [C.POINTER(SegmentParams)]),
+    "stocs_segment_frame": (C.c_int, [C.POINTER(Camera), C.POINTER(C.c_uint16), C.POINTER(SegmentParams), C.c_int, C.POINTER(C.c_uint16), _ip, _u8p,
+                                      C.POINTER(SegmentRecord), C.c_int, C.POINTER(SegmentResult)]),
+    "stocs_segment_tile": (C.c_int, [_intp, _intp]),
+    "stocs_segment_last_device_ms": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "stocs_segment_last_moments": (C.c_int, [_i64p]),
     "stocs_icp_point_to_plane": (C.c_int, [_fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_float, C.c_int, _fp, _intp]),
     "stocs_refine_poses": (C.c_int, [_vp, _fp, C.c_int, _ip, C.c_int, C.c_int, C.c_float, _fp, _fp, _fp, _ip, _ip]),
     "stocs_refine_detail": (C.c_int, [_vp, _fp, _ip, C.c_int, C.c_float, _ip, _u8p, C.POINTER(C.c_double)]),

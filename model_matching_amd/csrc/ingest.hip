@@ -27,6 +27,7 @@
 
 #include "mesh_sample.h"
 #include "prims.h"
+#include "segment.h"
 #include "stocs_ctx.h"
 
 namespace stocs {
@@ -815,6 +816,7 @@ int stocs_trim(void) {
         tl_cur = NULL;
     }
     if (tl_pin) { (void)hipHostFree(tl_pin); tl_pin = NULL; tl_pin_bytes = 0; }
+    segment_trim();
     return STOCS_OK;
 }
 

@@ -1470,6 +1470,68 @@ def ingest_scene_multi(depth_u16, probs_u16, K, depth_scale, voxel_size=0.005, c
     return [(pos[a:b].copy(), nrm[a:b].copy(), pr[a:b].copy(), px[a:b].copy()) for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
 
 
+def segment_params(**kw):
+    """stocs_segment_params with the library's defaults and kw on top; a value outside its range raises (stocs_check_segment_params)."""
+    p = capi.SegmentParams()
+    capi.load().stocs_default_segment_params(C.byref(p))
+    for k, v in kw.items():
+        if not hasattr(p, k):
+            raise TypeError("segment_frame: no parameter %r" % k)
+        setattr(p, k, v)
+    capi.check(capi.load().stocs_check_segment_params(C.byref(p)))
+    return p
+
+
+def segment_frame(depth_u16, K, depth_scale, device=-1, cap_records=None, images=("class_prob", "labels", "edge"), **params):
+    """A depth-only frame's class image from its geometry (stocs_segment_frame): the support plane is found and removed, what stands on it
+    is split into depth-connected segments.  Returns (result dict, records, images dict): the records as a structured array (root, pixels,
+    c0, r0, c1, r1, zmin, zmax), images["class_prob"] (uint16: 10000 in a kept segment, what ingest_scene and set_frame take),
+    images["labels"] (int32, 1 .. n_segments) and images["edge"] (uint8, 255 = interior, what set_edge_map takes).  params: the fields of
+    stocs_segment_params.  cap_records None: as many as the frame can hold (pixels // min_pixels)."""
+    L = capi.load()
+    d = np.ascontiguousarray(depth_u16, np.uint16)
+    H, W = d.shape
+    p = segment_params(**params)
+    cam = capi.Camera(K[0], K[1], K[2], K[3], depth_scale, W, H, 0)
+    cap = (W * H) // p.min_pixels if cap_records is None else int(cap_records)
+    rec = (capi.SegmentRecord * max(cap, 1))()
+    out = capi.SegmentResult()
+    img = {"class_prob": np.zeros((H, W), np.uint16) if "class_prob" in images else None, "labels": np.zeros((H, W), np.int32) if "labels" in images else None,
+           "edge": np.zeros((H, W), np.uint8) if "edge" in images else None}
+    ptr = lambda a, t: a.ctypes.data_as(t) if a is not None else None
+    capi.check(L.stocs_segment_frame(C.byref(cam), d.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(p), device, ptr(img["class_prob"], C.POINTER(C.c_uint16)),
+                                     ptr(img["labels"], capi._ip), ptr(img["edge"], capi._u8p), rec if cap > 0 else None, cap, C.byref(out)))
+    res = {f: getattr(out, f) for f, _ in capi.SegmentResult._fields_ if f not in ("plane", "reserved")}
+    res["plane"] = np.array(list(out.plane), np.float32)
+    records = np.frombuffer(rec, dtype=np.dtype([(f, np.float32 if f in ("zmin", "zmax") else np.int32) for f, _ in capi.SegmentRecord._fields_]))[:out.n_segments].copy()
+    return res, records, {k: v for k, v in img.items() if v is not None}
+
+
+def segment_class_images(labels, ids=None):
+    """The object-major uint16 stack ingest_scene_multi takes, from a label image: image k is 10000 where labels == ids[k] (ids None: every
+    segment 1 .. labels.max(), one image each; an entry of ids may be a list of segment numbers that make up one object)."""
+    lab = np.asarray(labels)
+    ids = list(range(1, int(lab.max()) + 1)) if ids is None else list(ids)
+    out = np.zeros((len(ids),) + lab.shape, np.uint16)
+    for k, i in enumerate(ids):
+        out[k][np.isin(lab, np.atleast_1d(np.asarray(i)))] = 10000
+    return out
+
+
+def segment_last_device_ms():
+    """(score_ms, label_ms) of the calling thread's last segment_frame under STOCS_SEGMENT_CLOCK=1."""
+    a, b = C.c_float(0), C.c_float(0)
+    capi.check(capi.load().stocs_segment_last_device_ms(C.byref(a), C.byref(b)))
+    return a.value, b.value
+
+
+def segment_last_moments():
+    """The refit's count and nine int64 moments of the calling thread's last segment_frame."""
+    m = np.zeros(10, np.int64)
+    capi.check(capi.load().stocs_segment_last_moments(m.ctypes.data_as(capi._i64p)))
+    return m
+
+
 def estimate_objects(scenes, models, seeds, n_attempts=100, mode=0, dispersion=0.9, max_per_base=200, edge_map=None, options=None,
                      params=None, max_workers=4, device=-1, post=None, robust=None):
     """One estimator per object of a frame, run concurrently on a pool of at most max_workers host threads (each context owns its

@@ -1,0 +1,81 @@
+#!/usr/bin/env python3
+"""Times of stocs_segment_frame on the GPU -> profiles/segment_time.json: per frame and label form (1: union-find in device memory, 2: tiles
+in LDS) the host time of the whole call and, under STOCS_SEGMENT_CLOCK=1, the HIP-event times of the scoring group and of the label group,
+each the median of REPS calls after WARM warm-up calls; beside them the numpy restatement's host time on the same frame, for scale.  Frames:
+640 x 480 (a table scene, the three example frames of tests/golden, blobs, a checkerboard, one component) and the sizes the tests use.  The
+default form (SEG_DEFAULT_FORM in csrc/segment.hip) is chosen on the 640 x 480 rows.
+
+    python tools/segment_time.py [--out profiles/segment_time.json]"""
+import glob
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import segment_cases as sc  # noqa: E402
+import segment_ref as sr  # noqa: E402
+from model_matching_amd import estimator as E  # noqa: E402
+
+WARM, REPS = 3, 20
+
+
+def frames():
+    out = []
+    d, K, _, _ = sc.table_frame(W=640, H=480, seed=0, noise_mm=1.0, boxes=((150, 200, 140, 120, 0.08), (400, 250, 150, 100, 0.12)))
+    out.append(("table 640x480", d, K, sc.SCALE, {}))
+    for f in sorted(glob.glob(os.path.join(ROOT, "tests", "golden", "example_*_raw.npz"))):
+        raw = np.load(f)
+        out.append((os.path.basename(f)[len("example_"):-len("_raw.npz")] + " 640x480", raw["depth"].astype(np.uint16), [float(x) for x in raw["K"]], float(raw["depth_scale"]), {}))
+    out.append(("blobs 640x480, no plane search", sc.blobs(640, 480, 0), sc.camera(640, 480), sc.SCALE, dict(sc.LABEL, min_pixels=20)))
+    out.append(("checkerboard 640x480, no plane search", sc.checkerboard(640, 480), sc.camera(640, 480), sc.SCALE, dict(sc.LABEL, min_pixels=200)))
+    out.append(("one component 640x480, no plane search", sc.blank(640, 480, 1000), sc.camera(640, 480), sc.SCALE, dict(sc.LABEL)))
+    out.append(("serpentine 640x480, no plane search", sc.serpentine(640, 480), sc.camera(640, 480), sc.SCALE, dict(sc.LABEL)))
+    d, K, _, _ = sc.table_frame(seed=1, noise_mm=1.5)
+    out.append(("table 128x96", d, K, sc.SCALE, {}))
+    out.append(("blobs 129x33, no plane search", sc.blobs(129, 33, 162), sc.camera(129, 33), sc.SCALE, dict(sc.LABEL, min_pixels=3)))
+    return out
+
+
+def main():
+    out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "segment_time.json")
+    os.environ["STOCS_SEGMENT_CLOCK"] = "1"
+    rows = []
+    for name, d, K, scale, kw in frames():
+        t0 = time.perf_counter()
+        ref = sr.segment_frame(d, K, scale, **kw)
+        row = {"frame": name, "restatement_host_ms": (time.perf_counter() - t0) * 1e3, "n_valid": ref["n_valid"], "plane_found": ref["plane_found"],
+               "n_components": ref["n_components"], "n_segments": ref["n_segments"]}
+        for form in ("1", "2"):
+            os.environ["STOCS_SEGMENT_FORM"] = form
+            call, score, label = [], [], []
+            for i in range(WARM + REPS):
+                t0 = time.perf_counter()
+                res, _, _ = E.segment_frame(d, K, scale, **kw)
+                dt = (time.perf_counter() - t0) * 1e3
+                s, l = E.segment_last_device_ms()
+                if i >= WARM:
+                    call.append(dt); score.append(s); label.append(l)
+            assert res["n_components"] == ref["n_components"] and res["n_segments"] == ref["n_segments"], (name, form)
+            row["form_%s" % form] = {"call_host_ms_median": float(np.median(call)), "call_host_ms_min": float(np.min(call)), "score_device_ms_median": float(np.median(score)),
+                                     "label_device_ms_median": float(np.median(label)), "label_device_ms_min": float(np.min(label)), "label_device_ms_max": float(np.max(label))}
+        row["faster_label_form"] = 1 if row["form_1"]["label_device_ms_median"] < row["form_2"]["label_device_ms_median"] else 2
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    del os.environ["STOCS_SEGMENT_FORM"]
+    out = {"what": "stocs_segment_frame on an MI355X: host time of the whole call (through the Python wrapper, which allocates the output arrays), HIP-event time of the "
+                   "scoring group (hypotheses, scoring, winner) and of the label group (union or tiles + borders, flatten), per label form; medians of %d calls after %d; "
+                   "the numpy restatement's host time beside them for scale" % (REPS, WARM),
+           "default_form": 2, "rows": rows,
+           "unmeasured": "frame sizes other than those listed; real frames beyond the three examples"}
+    with open(out_path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
+if __name__ == "__main__":
+    main()
