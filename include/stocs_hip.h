@@ -489,6 +489,51 @@ int  stocs_segment_tile(int* width, int* height);                             /*
 int  stocs_segment_last_device_ms(float* score_ms, float* label_ms);          /* with STOCS_SEGMENT_CLOCK=1         */
 int  stocs_segment_last_moments(int64_t* moments10);                          /* n_refit, Sx, Sy, Sz, Sxx, Sxy, Sxz, Syy, Syz, Szz of the thread's last call */
 
+/* ---- the concavity cut in front of the labelling (opt-in; no reference counterpart; restated in tests/segment_convex_ref.py, equal bit
+ * for bit).  Two touching objects have no depth jump between them, so step 5 joins them; they have a concave crease.  This entry point is
+ * stocs_segment_frame with two more steps between its steps 4 and 5, under step 1's conventions (float, one IEEE operation at a time, no
+ * contraction, 3-term sums e0 + (e1 + e2), a comparison with NaN false).  It follows the local-convexity idea of LCCP (Stein et al. 2014)
+ * on the image grid: three smoothed points a fixed pixel distance apart stand in for the two normals, and the angle test is on squared
+ * quantities, so there is no normal and no square root.
+ *
+ *   4a. Smoothed depth.  For a FOREGROUND pixel c (raw depth q_c, float depth z_c), over the (2s+1)^2 window around it (s =
+ *       smooth_radius) clipped to the image, a window pixel w COUNTS when it is foreground and fabsf(z_c - z_w) <= jump_abs + jump_rel *
+ *       fminf(z_c, z_w) (step 5's rule between the centre and w directly; the centre always counts).  S = the integer sum of the raw
+ *       depths that count, N their number; zs = ((float)S / (float)N) * depth_scale; xs, ys from zs as step 1 forms x, y from z, through
+ *       double.  S <= 81 * 65535 < 2^24: exact as a float, whatever the order.  With s = 0 zs is step 1's z.  Off the foreground zs is NaN.
+ *   4b. Bend test, per axis, r = bend_radius.  The horizontal triple at (i, j) is L = (i, j - r), C = (i, j), R = (i, j + r); the
+ *       vertical one uses rows.  A triple is TESTED when all three pixels are inside the image and foreground and, for X in {L, R},
+ *       fabsf(zs_X - zs_C) <= (float)r * (jump_abs + jump_rel * fminf(zs_C, zs_X)).  On the smoothed points, component-wise: a = C - L,
+ *       b = R - C, m = (L + R) - (C + C); ab = a.b, aa = a.a, bb = b.b; toward = m.C < 0 (the chord's midpoint lies nearer the camera
+ *       than C: the bend opens towards the viewer); bend = ab <= 0 || ab * ab < (bend_cos * bend_cos) * (aa * bb).  The pixel is CUT on
+ *       that axis when the triple is tested and toward and bend hold.  A pixel cut on either axis leaves the foreground for step 5 only:
+ *       it joins nothing, has label 0 and class 0 and is no component; n_on_plane, n_above and n_below stay step 4's.  Steps 5 - 7 run
+ *       on what is left, unchanged, so the edge image marks the neighbours of a cut pixel as edges.
+ *
+ * cut (uint8 H W or NULL): bit 0 the horizontal cut, bit 1 the vertical.  smoothed (float H W or NULL): zs, NaN off the foreground;
+ * copied back only when asked for.  cout: the triples tested and the pixels cut per axis, and the pixels cut on either.  Everything else
+ * is stocs_segment_frame's, checked in its order: NULL cp / cout with the other NULLs, cp (stocs_check_segment_convex_params) right
+ * after p; a STOCS_SEGMENT_BEND_FORM other than 0, 1, 2 after STOCS_SEGMENT_FORM.  On STOCS_ERR_CAPACITY `out` and `cout` are filled
+ * and nothing else is written.  With bend_radius == 0 every output is stocs_segment_frame's bit for bit, cut is zero and so are the
+ * counts (smoothed is still 4a's).  STOCS_SEGMENT_BEND_FORM forces the step's form (1: a lane per pixel, every read from device memory;
+ * 2: a workgroup per stocs_segment_tile, depths and smoothed points in LDS; 0 or unset: the default); both end at the same bits.  With
+ * STOCS_SEGMENT_CLOCK=1 stocs_segment_last_bend_ms gives the HIP-event time of steps 4a + 4b of the thread's last call
+ * (STOCS_ERR_STATE when that was not a stocs_segment_frame_convex under the clock); stocs_segment_last_device_ms keeps its two values. ---- */
+typedef struct stocs_segment_convex_params {
+    int32_t bend_radius;        /* 0 .. 8 pixels between the points of a triple; 0: no cut (default 4)               */
+    int32_t smooth_radius;      /* 0 .. 4: the window of 4a is (2s+1)^2 pixels (2)                                    */
+    float   bend_cos;           /* [0, 1]: a bend of more than acos(bend_cos) is cut (0.90630779f, cos 25 degrees)   */
+    int32_t reserved;           /* 0                                                                                  */
+} stocs_segment_convex_params;
+typedef struct stocs_segment_convex_result { int32_t n_tested_h, n_tested_v, n_cut_h, n_cut_v, n_cut, reserved[3]; } stocs_segment_convex_result; /* 32 bytes */
+void stocs_default_segment_convex_params(stocs_segment_convex_params*);
+int  stocs_check_segment_convex_params(const stocs_segment_convex_params*);   /* host only */
+int  stocs_segment_frame_convex(const stocs_camera* cam, const uint16_t* depth, const stocs_segment_params* p, const stocs_segment_convex_params* cp,
+                                int device, uint16_t* class_prob /* H W or NULL */, int32_t* labels /* H W or NULL */, uint8_t* edge /* H W or NULL */,
+                                uint8_t* cut /* H W or NULL */, float* smoothed /* H W or NULL */, stocs_segment_record* records, int cap_records,
+                                stocs_segment_result* out, stocs_segment_convex_result* cout);
+int  stocs_segment_last_bend_ms(float* bend_ms);                              /* with STOCS_SEGMENT_CLOCK=1         */
+
 /* ---- files either side of the path (host code; zlib only): what the reference's constructor and driver read and
  * write through OpenCV / PCL.  stocs_png_read: 8/16-bit grey / RGB (+alpha), non-interlaced; pixels = height rows of
  * width*channels samples of bit_depth/8 bytes, 16-bit in host byte order; pixels == NULL queries the sizes.

@@ -93,7 +93,10 @@
 // from depth.png (stocs_segment_frame: the support plane within tol metres removed, what stands on it split into depth-connected segments of
 // min_pixels or more; the library's defaults unless given) and goes to the ingest and, where a frame is set, to set_frame; one "segment: plane
 // found (n0 n1 n2 d), .. pixels on it, .. components, .. segments kept" line.  --segment-edges (with --segment, refused without it): the edge
-// image of the same call goes to stocs_set_edge_map, so sampling runs in instance mode.
+// image of the same call goes to stocs_set_edge_map, so sampling runs in instance mode.  --segment-convex [r[,s[,deg]]] (with --segment,
+// refused without it): touching objects are cut apart at concave creases before the labelling (stocs_segment_frame_convex: bend radius and
+// smoothing radius in pixels, the bend angle in degrees, which becomes bend_cos here; the library's defaults unless given), and a
+// "segment convex: .. triples tested, .. cut, .. pixels cut" line follows.
 // The reference edits its per-data-set constants in the source (README.md:42-66); here they are options with the
 // reference's YCB values as defaults.
 #include <algorithm>
@@ -778,6 +781,8 @@ int main(int argc, char** argv) {
     bool damped_bad = false, contour_bad = false;
     bool do_segment = false, segment_edges = false, segment_bad = false;   // --segment [tol[,min_pixels]] [--segment-edges]
     stocs_segment_params seg_prm = stocs::default_segment_params();
+    bool segment_convex = false;                                            // --segment-convex [r[,s[,deg]]]
+    stocs_segment_convex_params seg_cvx = stocs::default_segment_convex_params();
     std::string mesh_path, surface = "points";
     bool have_vsd_delta = false, have_surfel_radius = false;
     stocs_instance_params inst_prm = stocs::stocs_estimator::default_instance_params();
@@ -794,6 +799,18 @@ int main(int argc, char** argv) {
             char tail = 0;
             const int got = sscanf(sv.c_str(), "%f,%d%c", &seg_prm.plane_tolerance, &seg_prm.min_pixels, &tail);
             if (got < 1 || got > 2 || (size_t)std::count(sv.begin(), sv.end(), ',') + 1 != (size_t)got || stocs_check_segment_params(&seg_prm) != STOCS_OK) segment_bad = true;
+            continue;
+        }
+        if (std::string(argv[i]) == "--segment-convex") {   // [r[,s[,deg]]]: the concavity cut in front of the labelling; the value may be left out
+            segment_convex = true;
+            if (i + 1 >= argc || std::string(argv[i + 1]).compare(0, 2, "--") == 0) { --i; continue; }
+            const std::string sv = argv[i + 1];
+            char tail = 0;
+            float deg = 25.0f;
+            const int got = sscanf(sv.c_str(), "%d,%d,%f%c", &seg_cvx.bend_radius, &seg_cvx.smooth_radius, &deg, &tail);
+            if (got < 1 || got > 3 || (size_t)std::count(sv.begin(), sv.end(), ',') + 1 != (size_t)got || !(deg >= 0.0f && deg <= 90.0f)) segment_bad = true;
+            if (got == 3) seg_cvx.bend_cos = std::min(1.0f, std::max(0.0f, (float)std::cos((double)deg * 3.14159265358979323846 / 180.0)));   // degrees become bend_cos here
+            if (stocs_check_segment_convex_params(&seg_cvx) != STOCS_OK) segment_bad = true;
             continue;
         }
         if (std::string(argv[i]) == "--vsd") { vsd_opt.on = true; --i; continue; }   // with --gt: the visible-surface discrepancy too
@@ -887,8 +904,9 @@ int main(int argc, char** argv) {
         }
     }
 
-    if (segment_bad || (segment_edges && !do_segment) || (do_segment && (clouds || a2.find(',') != std::string::npos))) {   // refused before any search
-        std::cerr << "--segment [tol[,min_pixels]] needs a scene directory, a single object, tol > 0 and min_pixels >= 1; --segment-edges needs --segment" << std::endl;
+    if (segment_bad || ((segment_edges || segment_convex) && !do_segment) || (do_segment && (clouds || a2.find(',') != std::string::npos))) {   // refused before any search
+        std::cerr << "--segment [tol[,min_pixels]] needs a scene directory, a single object, tol > 0 and min_pixels >= 1; --segment-edges needs --segment; "
+                     "--segment-convex [r[,s[,deg]]] needs --segment, r in 0..8, s in 0..4 and 0 <= deg <= 90" << std::endl;
         return -1;
     }
     std::vector<float> mesh_v;
@@ -1045,8 +1063,13 @@ int main(int argc, char** argv) {
             if (do_segment) {   // no probability_maps: the class image (and with --segment-edges the edge image) comes from the depth image
                 std::vector<uint16_t> depth;
                 stocs::read_image(depth_path, 1, 16, image_width, image_height, &depth);
-                const stocs::SegmentedFrame seg = stocs::segment_frame(depth.data(), cam_intrinsics, image_width, image_height, depth_scale, seg_prm);
+                const stocs::SegmentedFrame seg = segment_convex ? stocs::segment_frame(depth.data(), cam_intrinsics, image_width, image_height, depth_scale, seg_prm, seg_cvx)
+                                                                 : stocs::segment_frame(depth.data(), cam_intrinsics, image_width, image_height, depth_scale, seg_prm);
                 const stocs_segment_result& sr = seg.result;
+                if (segment_convex)
+                    std::cout << "segment convex: radius " << seg_cvx.bend_radius << ", smoothing " << seg_cvx.smooth_radius << ", cos " << seg_cvx.bend_cos << ": " << seg.convex.n_tested_h
+                              << " + " << seg.convex.n_tested_v << " triples tested, " << seg.convex.n_cut_h << " + " << seg.convex.n_cut_v << " cut, " << seg.convex.n_cut
+                              << " pixels cut" << std::endl;
                 std::cout << "segment: plane " << (sr.plane_found ? "found" : "not found") << " (" << sr.plane[0] << " " << sr.plane[1] << " " << sr.plane[2] << " " << sr.plane[3]
                           << "), " << sr.n_on_plane << " pixels on it, " << sr.n_components << " components, " << sr.n_segments << " segments kept" << std::endl;
                 stocs::ModelCloud model;

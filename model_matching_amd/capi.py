@@ -176,6 +176,15 @@ class SegmentRecord(C.Structure):
                 ("zmin", C.c_float), ("zmax", C.c_float)]
 
 
+class SegmentConvexParams(C.Structure):
+    _fields_ = [("bend_radius", C.c_int32), ("smooth_radius", C.c_int32), ("bend_cos", C.c_float), ("reserved", C.c_int32)]
+
+
+class SegmentConvexResult(C.Structure):
+    _fields_ = [("n_tested_h", C.c_int32), ("n_tested_v", C.c_int32), ("n_cut_h", C.c_int32), ("n_cut_v", C.c_int32), ("n_cut", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
 class SceneRecord(C.Structure):
     _fields_ = [("footprint", C.c_int32), ("no_depth", C.c_int32), ("agree", C.c_int32), ("in_front", C.c_int32), ("behind", C.c_int32),
                 ("on_mask", C.c_int32), ("claimed", C.c_int32)]
@@ -289,6 +298,12 @@ SIGNATURES = {
     "stocs_segment_tile": (C.c_int, [_intp, _intp]),
     "stocs_segment_last_device_ms": (C.c_int, [C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "stocs_segment_last_moments": (C.c_int, [_i64p]),
+    "stocs_default_segment_convex_params": (None, [C.POINTER(SegmentConvexParams)]),
+    "stocs_check_segment_convex_params": (C.c_int, [C.POINTER(SegmentConvexParams)]),
+    "stocs_segment_frame_convex": (C.c_int, [C.POINTER(Camera), C.POINTER(C.c_uint16), C.POINTER(SegmentParams), C.POINTER(SegmentConvexParams), C.c_int,
+                                             C.POINTER(C.c_uint16), _ip, _u8p, _u8p, _fp, C.POINTER(SegmentRecord), C.c_int, C.POINTER(SegmentResult),
+                                             C.POINTER(SegmentConvexResult)]),
+    "stocs_segment_last_bend_ms": (C.c_int, [C.POINTER(C.c_float)]),
     "stocs_icp_point_to_plane": (C.c_int, [_fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_float, C.c_int, _fp, _intp]),
     "stocs_refine_poses": (C.c_int, [_vp, _fp, C.c_int, _ip, C.c_int, C.c_int, C.c_float, _fp, _fp, _fp, _ip, _ip]),
     "stocs_refine_detail": (C.c_int, [_vp, _fp, _ip, C.c_int, C.c_float, _ip, _u8p, C.POINTER(C.c_double)]),

@@ -14,6 +14,11 @@
 //   seg_refit         int64 moments of the winner's inliers over every valid pixel: lane accumulators, butterfly, one atomic per workgroup
 //                     and moment; seg_plane: one lane forms the plane from them in double (Jacobi, SEG_SWEEPS sweeps)
 //   seg_heights       pixel classes against the float plane, the foreground depth image (NaN elsewhere), labels = own index
+//   bend (stocs_segment_frame_convex only; steps 4a and 4b)  form 1 seg_smooth (a lane per pixel, the window from device memory) +
+//                     seg_bend (the four far smoothed points from device memory); form 2 seg_bend_tiles (a workgroup per tile: raw depths of
+//                     the foreground with a halo of r + s in LDS, the smoothed points of the tile and a halo of r in LDS, both tests from
+//                     LDS).  Either writes the second depth image (NaN at cut pixels) that the kernels below then read, L = -1 at cut
+//                     pixels, the cut image and five counts (ballots, one atomic per workgroup and counter).
 //   label             form 1 seg_union_global + seg_flatten; form 2 seg_tiles (runs by ballot, union-find on run heads in LDS) +
 //                     seg_borders (tile borders only, device memory) + seg_flatten.  Every link points from a larger index to a smaller
 //                     one, so both forms end at the component's lowest index whatever the order.
@@ -32,13 +37,14 @@
 
 namespace stocs {
 
-enum { SEG_TILE_W = 64, SEG_TILE_H = 16, SEG_SCORE_PTS = 1024, SEG_SCORE_HYP = 64, SEG_SWEEPS = 12, SEG_MAX_HYP = 1 << 20, SEG_MAX_PIX = 1 << 22 };
+enum { SEG_MAX_BEND = 8, SEG_MAX_SMOOTH = 4, SEG_TILE_W = 64, SEG_TILE_H = 16, SEG_SCORE_PTS = 1024, SEG_SCORE_HYP = 64, SEG_SWEEPS = 12, SEG_MAX_HYP = 1 << 20, SEG_MAX_PIX = 1 << 22 };
 
 // what the kernels leave for the host: the result, the refit's count and nine moments, the winner's hypothesis
 struct SegHeader {
     stocs_segment_result r;
     long long mom[10];     // n, Sx, Sy, Sz, Sxx, Sxy, Sxz, Syy, Syz, Szz of q = llrint(v * 65536)
     float win[8];          // A, m, tol^2 |m|^2, alive
+    stocs_segment_convex_result c;   // the bend step's counts (behind everything the older kernels address)
 };
 
 __device__ __forceinline__ bool seg_join(float za, float zb, float jump_abs, float jump_rel) {
@@ -253,6 +259,155 @@ __global__ __launch_bounds__(256) void seg_heights_kernel(const float4* __restri
     }
 }
 
+// ---- steps 4a and 4b: the concavity cut in front of the labelling (stocs_segment_frame_convex).  A smoothed point is (xs, ys, zs); off the
+// foreground and outside the image all three are NaN, so every test on it is false.
+__device__ __forceinline__ V3 seg_nan3() { const float n = __int_as_float(0x7fc00000); return mk3(n, n, n); }
+// zs of the integer window sum, and x, y from it as seg_points forms them from z
+__device__ __forceinline__ V3 seg_smoothed_point(uint32_t S, uint32_t N, int i, int j, float fx, float cx, float fy, float cy, float depth_scale) {
+    const float zs = ((float)S / (float)N) * depth_scale;
+    return mk3((float)(((double)j - (double)cx) * (double)zs / (double)fx), (float)(((double)i - (double)cy) * (double)zs / (double)fy), zs);
+}
+// one triple: bit 0 tested, bit 1 cut
+__device__ __forceinline__ int seg_bend_triple(V3 l, V3 c, V3 r, float rf, float jump_abs, float jump_rel, float cos2) {
+    if (!(fabsf(l.z - c.z) <= rf * (jump_abs + jump_rel * fminf(c.z, l.z)) && fabsf(r.z - c.z) <= rf * (jump_abs + jump_rel * fminf(c.z, r.z)))) return 0;
+    const V3 a = c - l, b = r - c;
+    const V3 m = mk3((l.x + r.x) - (c.x + c.x), (l.y + r.y) - (c.y + c.y), (l.z + r.z) - (c.z + c.z));
+    const float ab = a.x * b.x + (a.y * b.y + a.z * b.z), aa = a.x * a.x + (a.y * a.y + a.z * a.z), bb = b.x * b.x + (b.y * b.y + b.z * b.z);
+    const bool toward = m.x * c.x + (m.y * c.y + m.z * c.z) < 0.0f;
+    const bool bend = ab <= 0.0f || ab * ab < cos2 * (aa * bb);
+    return (toward && bend) ? 3 : 1;
+}
+// what a lane leaves of its pixel (th, tv: the two triples' bits) and the five counts of its wavefront into s_n[wave]
+__device__ __forceinline__ void seg_bend_store(bool inside, int idx, float z, int th, int tv, float* __restrict__ fz2, int* __restrict__ L, uint8_t* __restrict__ cut, int* acc) {
+    const int bits = ((th >> 1) & 1) | (tv & 2);
+    if (inside) {
+        cut[idx] = (uint8_t)bits;
+        fz2[idx] = bits ? __int_as_float(0x7fc00000) : z;
+        if (bits) L[idx] = -1;
+    }
+    acc[0] += __popcll(__ballot(th & 1)); acc[1] += __popcll(__ballot(tv & 1)); acc[2] += __popcll(__ballot(th & 2)); acc[3] += __popcll(__ballot(tv & 2));
+    acc[4] += __popcll(__ballot(bits != 0));
+}
+__device__ __forceinline__ void seg_bend_counts(const int* acc, int (*s_n)[5], SegHeader* __restrict__ hdr) {
+    if ((threadIdx.x & 63) == 0)
+        for (int k = 0; k < 5; ++k) s_n[threadIdx.x >> 6][k] = acc[k];
+    __syncthreads();
+    if (threadIdx.x < 5) {
+        const int t = (s_n[0][threadIdx.x] + s_n[1][threadIdx.x]) + (s_n[2][threadIdx.x] + s_n[3][threadIdx.x]);
+        if (t) atomicAdd(&hdr->c.n_tested_h + threadIdx.x, t);
+    }
+}
+
+// form 1, step 4a: a lane per pixel, the window read from device memory
+__global__ __launch_bounds__(256) void seg_smooth_kernel(const uint16_t* __restrict__ depth, const float* __restrict__ fz, int W, int H, float fx, float cx, float fy, float cy,
+                                                         float depth_scale, float jump_abs, float jump_rel, int s, float4* __restrict__ PS, float* __restrict__ zs_out) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= W * H) return;
+    const int i = idx / W, j = idx % W;
+    const float zc = fz[idx];
+    V3 q = seg_nan3();
+    if (zc == zc) {
+        uint32_t S = 0, N = 0;
+        for (int y = max(i - s, 0); y <= min(i + s, H - 1); ++y)
+            for (int x = max(j - s, 0); x <= min(j + s, W - 1); ++x)
+                if (seg_join(zc, fz[y * W + x], jump_abs, jump_rel)) { S += depth[y * W + x]; ++N; }
+        q = seg_smoothed_point(S, N, i, j, fx, cx, fy, cy, depth_scale);
+    }
+    PS[idx] = make_float4(q.x, q.y, q.z, 0.0f);
+    if (zs_out) zs_out[idx] = q.z;
+}
+// form 1, step 4b: the centre's and the four far smoothed points from device memory
+__global__ __launch_bounds__(256) void seg_bend_kernel(const float4* __restrict__ PS, const float* __restrict__ fz, int W, int H, int r, float jump_abs, float jump_rel, float cos2,
+                                                       float* __restrict__ fz2, int* __restrict__ L, uint8_t* __restrict__ cut, SegHeader* __restrict__ hdr) {
+    __shared__ int s_n[4][5];
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    const bool inside = idx < W * H;
+    int th = 0, tv = 0;
+    if (inside && r > 0) {
+        const int i = idx / W, j = idx % W;
+        const float4 c4 = PS[idx];
+        const V3 c = mk3(c4.x, c4.y, c4.z);
+        if (c.z == c.z) {
+            const float rf = (float)r;
+            if (j - r >= 0 && j + r < W) { const float4 a = PS[idx - r], b = PS[idx + r]; th = seg_bend_triple(mk3(a.x, a.y, a.z), c, mk3(b.x, b.y, b.z), rf, jump_abs, jump_rel, cos2); }
+            if (i - r >= 0 && i + r < H) { const float4 a = PS[idx - r * W], b = PS[idx + r * W]; tv = seg_bend_triple(mk3(a.x, a.y, a.z), c, mk3(b.x, b.y, b.z), rf, jump_abs, jump_rel, cos2); }
+        }
+    }
+    int acc[5] = {0, 0, 0, 0, 0};
+    seg_bend_store(inside, idx, inside ? fz[idx] : 0.0f, th, tv, fz2, L, cut, acc);
+    seg_bend_counts(acc, s_n, hdr);
+}
+
+// form 2: a workgroup per tile of SEG_TILE_W x SEG_TILE_H pixels.  Stage: the raw depth of every foreground pixel of the tile and a halo of
+// r + s (0: not foreground or outside the image; a foreground pixel's raw depth is never 0); a tile that holds no foreground ends there.  Then the smoothed point of every pixel of the
+// tile and a halo of r, once, the window read from the staged depths (the window is gated on the centre's depth, so it is not a separable
+// sum; it is an integer sum, so its order is free).  Then both tests from LDS: a wavefront holds a tile row, so its lanes read consecutive words.
+enum { SEG_BEND_SW = SEG_TILE_W + 2 * (SEG_MAX_BEND + SEG_MAX_SMOOTH), SEG_BEND_SH = SEG_TILE_H + 2 * (SEG_MAX_BEND + SEG_MAX_SMOOTH),
+       SEG_BEND_ZW = SEG_TILE_W + 2 * SEG_MAX_BEND, SEG_BEND_ZH = SEG_TILE_H + 2 * SEG_MAX_BEND };
+__global__ __launch_bounds__(256) void seg_bend_tiles_kernel(const uint16_t* __restrict__ depth, const float* __restrict__ fz, int W, int H, float fx, float cx, float fy, float cy,
+                                                             float depth_scale, float jump_abs, float jump_rel, int s, int r, float cos2, float* __restrict__ fz2,
+                                                             int* __restrict__ L, uint8_t* __restrict__ cut, float* __restrict__ zs_out, SegHeader* __restrict__ hdr) {
+    __shared__ uint16_t s_raw[SEG_BEND_SW * SEG_BEND_SH];
+    __shared__ float s_x[SEG_BEND_ZW * SEG_BEND_ZH], s_y[SEG_BEND_ZW * SEG_BEND_ZH], s_z[SEG_BEND_ZW * SEG_BEND_ZH];
+    __shared__ int s_n[4][5];
+    const int x0 = blockIdx.x * SEG_TILE_W, y0 = blockIdx.y * SEG_TILE_H;
+    const int hs = r + s, SW = SEG_TILE_W + 2 * hs, SH = SEG_TILE_H + 2 * hs, ZW = SEG_TILE_W + 2 * r, ZH = SEG_TILE_H + 2 * r;
+    int own = 0;                                                          // foreground in the tile itself (not its halo)
+    for (int t = threadIdx.x; t < SW * SH; t += 256) {
+        const int x = x0 - hs + t % SW, y = y0 - hs + t / SW;
+        uint16_t v = 0;
+        if (x >= 0 && x < W && y >= 0 && y < H) { const float z = fz[y * W + x]; if (z == z) v = depth[y * W + x]; }
+        s_raw[t] = v;
+        own |= (v != 0 && x >= x0 && x < x0 + SEG_TILE_W && y >= y0 && y < y0 + SEG_TILE_H) ? 1 : 0;
+    }
+    if (!__syncthreads_or(own)) {                                         // a tile without foreground (the support plane, the background): nothing to smooth, test or count
+        for (int k = 0; k < 4; ++k) {
+            const int x = x0 + (threadIdx.x & 63), y = y0 + (threadIdx.x >> 6) * 4 + k;
+            if (x < W && y < H) { cut[y * W + x] = 0; fz2[y * W + x] = __int_as_float(0x7fc00000); if (zs_out) zs_out[y * W + x] = __int_as_float(0x7fc00000); }
+        }
+        return;
+    }
+    for (int t = threadIdx.x; t < ZW * ZH; t += 256) {
+        const int lx = t % ZW, ly = t / ZW, x = x0 - r + lx, y = y0 - r + ly;
+        const uint16_t* row = s_raw + (ly + s) * SW + (lx + s);          // the centre in the staged block; the window around it lies inside the block
+        const uint32_t rc = row[0];
+        V3 q = seg_nan3();
+        if (rc) {
+            const float zc = (float)rc * depth_scale;
+            uint32_t S = 0, N = 0;
+            for (int dy = -s; dy <= s; ++dy)
+                for (int dx = -s; dx <= s; ++dx) {
+                    const uint32_t rw = row[dy * SW + dx];
+                    if (rw && seg_join(zc, (float)rw * depth_scale, jump_abs, jump_rel)) { S += rw; ++N; }
+                }
+            q = seg_smoothed_point(S, N, y, x, fx, cx, fy, cy, depth_scale);
+            if (zs_out && lx >= r && lx < r + SEG_TILE_W && ly >= r && ly < r + SEG_TILE_H) zs_out[y * W + x] = q.z;     // rc != 0: inside the image
+        } else if (zs_out && lx >= r && lx < r + SEG_TILE_W && ly >= r && ly < r + SEG_TILE_H && x < W && y < H) {
+            zs_out[y * W + x] = q.z;
+        }
+        s_x[t] = q.x; s_y[t] = q.y; s_z[t] = q.z;
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const float rf = (float)r;
+    int acc[5] = {0, 0, 0, 0, 0};
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const int ty = wave * 4 + k, x = x0 + lane, y = y0 + ty;
+        const bool inside = x < W && y < H;
+        const int at = (ty + r) * ZW + (lane + r);
+        const uint32_t rc = s_raw[(ty + hs) * SW + (lane + hs)];
+        int th = 0, tv = 0;
+        if (r > 0 && rc) {
+            const V3 c = mk3(s_x[at], s_y[at], s_z[at]);
+            th = seg_bend_triple(mk3(s_x[at - r], s_y[at - r], s_z[at - r]), c, mk3(s_x[at + r], s_y[at + r], s_z[at + r]), rf, jump_abs, jump_rel, cos2);
+            tv = seg_bend_triple(mk3(s_x[at - r * ZW], s_y[at - r * ZW], s_z[at - r * ZW]), c, mk3(s_x[at + r * ZW], s_y[at + r * ZW], s_z[at + r * ZW]), rf, jump_abs, jump_rel, cos2);
+        }
+        seg_bend_store(inside, y * W + x, rc ? (float)rc * depth_scale : __int_as_float(0x7fc00000), th, tv, fz2, L, cut, acc);
+    }
+    seg_bend_counts(acc, s_n, hdr);
+}
+
 // ---- union-find.  L[x] <= x always, L[x] is in x's component, and only a root (L[x] == x) is ever given a new parent by the link below, or
 // a node a smaller one: values only fall.  A read may be stale (another compute unit's L1 is not refreshed): it then names an earlier parent,
 // still an ancestor, so a find only walks further; the link itself is an atomic at the L2.  No lane ever waits for another.
@@ -436,11 +591,13 @@ __global__ __launch_bounds__(256) void seg_edges_kernel(const int32_t* __restric
 static thread_local std::map<int, Arena>* tl_seg_ws = NULL;
 static thread_local void* tl_seg_pin = NULL;
 static thread_local size_t tl_seg_pin_bytes = 0;
-static thread_local hipEvent_t tl_seg_ev[4];
+static thread_local hipEvent_t tl_seg_ev[6];           // 4, 5: around the bend step
 static thread_local bool tl_seg_ev_made = false;
 static thread_local int tl_seg_ev_dev = -1;          // events belong to the device they were made on
 static thread_local float tl_seg_ms[2] = {0.f, 0.f};
 static thread_local bool tl_seg_ms_valid = false;
+static thread_local float tl_seg_bend_ms = 0.f;
+static thread_local bool tl_seg_bend_ms_valid = false;
 static thread_local long long tl_seg_mom[10];
 static thread_local bool tl_seg_mom_valid = false;
 
@@ -451,7 +608,7 @@ void segment_trim() {
         tl_seg_ws = NULL;
     }
     if (tl_seg_pin) { (void)hipHostFree(tl_seg_pin); tl_seg_pin = NULL; tl_seg_pin_bytes = 0; }
-    if (tl_seg_ev_made) { for (int k = 0; k < 4; ++k) (void)hipEventDestroy(tl_seg_ev[k]); tl_seg_ev_made = false; }
+    if (tl_seg_ev_made) { for (int k = 0; k < 6; ++k) (void)hipEventDestroy(tl_seg_ev[k]); tl_seg_ev_made = false; }
 }
 
 static int segment_form(int* form) {
@@ -464,6 +621,18 @@ static int segment_form(int* form) {
 }
 // the default label form: the one that was faster in every row of profiles/segment_time.json
 enum { SEG_DEFAULT_FORM = 2 };
+
+static int segment_bend_form(int* form) {
+    const char* e = getenv("STOCS_SEGMENT_BEND_FORM");
+    *form = 0;
+    if (!e || !*e) return STOCS_OK;
+    if ((e[0] == '0' || e[0] == '1' || e[0] == '2') && e[1] == 0) { *form = e[0] - '0'; return STOCS_OK; }
+    set_error("STOCS_SEGMENT_BEND_FORM=%s: 0 (default), 1 (a lane per pixel, device memory) or 2 (tiles in LDS)", e);
+    return STOCS_ERR_INVALID;
+}
+// the default bend form: the one that was faster on the camera frames of profiles/segment_convex_time.json: 20 - 29 us
+// against 30 - 35 us at 640 x 480; the tiled form is ahead only where the whole frame is foreground
+enum { SEG_DEFAULT_BEND_FORM = 1 };
 
 }  // namespace stocs
 
@@ -492,6 +661,27 @@ int stocs_check_segment_params(const stocs_segment_params* p) {
     return STOCS_OK;
 }
 
+void stocs_default_segment_convex_params(stocs_segment_convex_params* cp) {
+    if (!cp) return;
+    memset(cp, 0, sizeof(*cp));
+    cp->bend_radius = 4; cp->smooth_radius = 2; cp->bend_cos = 0.90630779f;
+}
+
+int stocs_check_segment_convex_params(const stocs_segment_convex_params* cp) {
+    if (!cp) { set_error("stocs_check_segment_convex_params: NULL params"); return STOCS_ERR_INVALID; }
+    if (cp->bend_radius < 0 || cp->bend_radius > SEG_MAX_BEND) { set_error("segment convex params: bend_radius %d outside 0..%d", cp->bend_radius, (int)SEG_MAX_BEND); return STOCS_ERR_INVALID; }
+    if (cp->smooth_radius < 0 || cp->smooth_radius > SEG_MAX_SMOOTH) { set_error("segment convex params: smooth_radius %d outside 0..%d", cp->smooth_radius, (int)SEG_MAX_SMOOTH); return STOCS_ERR_INVALID; }
+    if (!(cp->bend_cos >= 0 && cp->bend_cos <= 1)) { set_error("segment convex params: bend_cos %g outside [0, 1]", (double)cp->bend_cos); return STOCS_ERR_INVALID; }
+    if (cp->reserved != 0) { set_error("segment convex params: reserved %d is not 0", cp->reserved); return STOCS_ERR_INVALID; }
+    return STOCS_OK;
+}
+
+int stocs_segment_last_bend_ms(float* bend_ms) {
+    if (!tl_seg_bend_ms_valid) { set_error("stocs_segment_last_bend_ms: no stocs_segment_frame_convex of this thread ran with STOCS_SEGMENT_CLOCK=1"); return STOCS_ERR_STATE; }
+    if (bend_ms) *bend_ms = tl_seg_bend_ms;
+    return STOCS_OK;
+}
+
 int stocs_segment_tile(int* width, int* height) {
     if (width) *width = SEG_TILE_W;
     if (height) *height = SEG_TILE_H;
@@ -512,21 +702,31 @@ int stocs_segment_last_moments(int64_t* moments10) {
     return STOCS_OK;
 }
 
-int stocs_segment_frame(const stocs_camera* cam, const uint16_t* depth, const stocs_segment_params* p, int device, uint16_t* class_prob, int32_t* labels,
-                        uint8_t* edge, stocs_segment_record* records, int cap_records, stocs_segment_result* out) {
-    if (!cam || !depth || !p || !out) { set_error("stocs_segment_frame: NULL camera, depth image, params or result"); return STOCS_ERR_INVALID; }
-    if (cam->width < 1 || cam->height < 1) { set_error("stocs_segment_frame: frame of %d x %d pixels", cam->width, cam->height); return STOCS_ERR_INVALID; }
+}  // extern "C"
+
+namespace stocs {
+// Both entry points: one launch sequence.  cp == NULL is stocs_segment_frame: no bend step, the label kernels read the foreground depth image
+// itself.  `who` names the entry point in messages; all_given: none of its required pointers is NULL.
+static int segment_run(const char* who, const stocs_camera* cam, const uint16_t* depth, const stocs_segment_params* p, const stocs_segment_convex_params* cp, int device,
+                       uint16_t* class_prob, int32_t* labels, uint8_t* edge, uint8_t* cut, float* smoothed, stocs_segment_record* records, int cap_records,
+                       stocs_segment_result* out, stocs_segment_convex_result* cout, bool all_given) {
+    if (!all_given) { set_error("%s: NULL camera, depth image, params or result", who); return STOCS_ERR_INVALID; }
+    if (cam->width < 1 || cam->height < 1) { set_error("%s: frame of %d x %d pixels", who, cam->width, cam->height); return STOCS_ERR_INVALID; }
     int rc = stocs_check_segment_params(p);
     if (rc) return rc;
-    if (cap_records < 0 || (!records && cap_records > 0)) { set_error("stocs_segment_frame: cap_records %d with %s records", cap_records, records ? "given" : "NULL"); return STOCS_ERR_INVALID; }
-    if ((long long)cam->width * cam->height > (long long)SEG_MAX_PIX) { set_error("stocs_segment_frame: %d x %d pixels, above 2^22 (the refit's moments are 64-bit sums)", cam->width, cam->height); return STOCS_ERR_CAPACITY; }
+    if (cp && (rc = stocs_check_segment_convex_params(cp))) return rc;
+    if (cap_records < 0 || (!records && cap_records > 0)) { set_error("%s: cap_records %d with %s records", who, cap_records, records ? "given" : "NULL"); return STOCS_ERR_INVALID; }
+    if ((long long)cam->width * cam->height > (long long)SEG_MAX_PIX) { set_error("%s: %d x %d pixels, above 2^22 (the refit's moments are 64-bit sums)", who, cam->width, cam->height); return STOCS_ERR_CAPACITY; }
     int form = 0;
     if ((rc = segment_form(&form))) return rc;
     if (form == 0) form = SEG_DEFAULT_FORM;
+    int bform = 0;
+    if (cp && (rc = segment_bend_form(&bform))) return rc;
+    if (bform == 0) bform = SEG_DEFAULT_BEND_FORM;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: this library has no CPU fallback"); return STOCS_ERR_NO_DEVICE; }
     if (device >= 0) STOCS_HIP_CHECK(hipSetDevice(device));
-    tl_seg_ms_valid = false; tl_seg_mom_valid = false;
+    tl_seg_ms_valid = false; tl_seg_mom_valid = false; tl_seg_bend_ms_valid = false;
 
     const int W = cam->width, H = cam->height, npix = W * H, s = p->score_stride, Hn = p->plane_hypotheses;
     const int LW = (W + s - 1) / s, LH = (H + s - 1) / s, nl = LW * LH;
@@ -543,6 +743,7 @@ int stocs_segment_frame(const stocs_camera* cam, const uint16_t* depth, const st
     // the block that comes back in one copy: header | labels | class image | edge image | records
     Carve oc;
     const size_t o_hdr = oc.take(sizeof(SegHeader)), o_lab = oc.take(4 * (size_t)npix), o_cls = oc.take(2 * (size_t)npix), o_edge = oc.take((size_t)npix);
+    const size_t o_cut = cp ? oc.take((size_t)npix) : 0, o_zs = (cp && smoothed) ? oc.take(4 * (size_t)npix) : 0;       // in front of the records: they come back too
     const size_t o_rec = oc.take(32 * std::max<size_t>(nrec_dev, 1));
     const size_t back_bytes = o_rec + 32 * nrec_copy;
     const size_t pin_need = al256(back_bytes) + 2 * (size_t)npix;
@@ -556,7 +757,7 @@ int stocs_segment_frame(const stocs_camera* cam, const uint16_t* depth, const st
     char* pin_depth = pin + al256(back_bytes);
 
     char* d_out = NULL; uint16_t* dD = NULL; float4 *P = NULL, *SP = NULL; uint32_t *lat_flag = NULL, *lat_pos = NULL, *cnt = NULL, *size = NULL, *keep = NULL, *kpos = NULL;
-    float *hyp = NULL, *fz = NULL; int* L = NULL; char* tmp = NULL;
+    float *hyp = NULL, *fz = NULL, *fz2 = NULL; float4* PS = NULL; int* L = NULL; char* tmp = NULL;
     size_t tb_lat = 0, tb_keep = 0;
     STOCS_HIP_CHECK(exclusive_scan(NULL, tb_lat, lat_flag, lat_pos, (size_t)nl + 1, st));
     STOCS_HIP_CHECK(exclusive_scan(NULL, tb_keep, keep, kpos, (size_t)npix + 1, st));
@@ -566,13 +767,14 @@ int stocs_segment_frame(const stocs_camera* cam, const uint16_t* depth, const st
         (rc = ws.take(4 * (size_t)npix, (void**)&L)) || (rc = ws.take(4 * (size_t)npix, (void**)&size)) || (rc = ws.take(4 * ((size_t)npix + 1), (void**)&keep)) ||
         (rc = ws.take(4 * ((size_t)npix + 1), (void**)&kpos)) || (rc = ws.take(std::max(tb_lat, tb_keep), (void**)&tmp)))
         return rc;
+    if (cp && ((rc = ws.take(4 * (size_t)npix, (void**)&fz2)) || (bform == 1 && (rc = ws.take(16 * (size_t)npix, (void**)&PS))))) return rc;
     SegHeader* hdr = (SegHeader*)(d_out + o_hdr);
     int32_t* d_lab = (int32_t*)(d_out + o_lab); uint16_t* d_cls = (uint16_t*)(d_out + o_cls); uint8_t* d_edge = (uint8_t*)(d_out + o_edge);
     stocs_segment_record* d_rec = (stocs_segment_record*)(d_out + o_rec);
 
     const bool clock = getenv("STOCS_SEGMENT_CLOCK") != NULL && atoi(getenv("STOCS_SEGMENT_CLOCK")) == 1;
-    if (clock && tl_seg_ev_made && tl_seg_ev_dev != dev) { for (int k = 0; k < 4; ++k) (void)hipEventDestroy(tl_seg_ev[k]); tl_seg_ev_made = false; }
-    if (clock && !tl_seg_ev_made) { for (int k = 0; k < 4; ++k) STOCS_HIP_CHECK(hipEventCreate(&tl_seg_ev[k])); tl_seg_ev_made = true; tl_seg_ev_dev = dev; }
+    if (clock && tl_seg_ev_made && tl_seg_ev_dev != dev) { for (int k = 0; k < 6; ++k) (void)hipEventDestroy(tl_seg_ev[k]); tl_seg_ev_made = false; }
+    if (clock && !tl_seg_ev_made) { for (int k = 0; k < 6; ++k) STOCS_HIP_CHECK(hipEventCreate(&tl_seg_ev[k])); tl_seg_ev_made = true; tl_seg_ev_dev = dev; }
 
     memcpy(pin_depth, depth, 2 * (size_t)npix);
     STOCS_HIP_CHECK(hipMemcpyAsync(dD, pin_depth, 2 * (size_t)npix, hipMemcpyHostToDevice, st));
@@ -595,14 +797,29 @@ int stocs_segment_frame(const stocs_camera* cam, const uint16_t* depth, const st
         hipLaunchKernelGGL(seg_plane_kernel, dim3(1), dim3(64), 0, st, hdr);
     }
     hipLaunchKernelGGL(seg_heights_kernel, gp, B, 0, st, P, npix, p->plane_tolerance, p->max_height, hdr, fz, L, size);
+    const float* lz = fz;                                                               // the depth image the label kernels and the relabelling read
+    if (cp) {
+        uint8_t* d_cut = (uint8_t*)(d_out + o_cut); float* d_zs = smoothed ? (float*)(d_out + o_zs) : NULL;
+        const float cos2 = cp->bend_cos * cp->bend_cos;
+        if (clock) STOCS_HIP_CHECK(hipEventRecord(tl_seg_ev[4], st));
+        if (bform == 1) {
+            hipLaunchKernelGGL(seg_smooth_kernel, gp, B, 0, st, dD, fz, W, H, cam->fx, cam->cx, cam->fy, cam->cy, cam->depth_scale, p->jump_abs, p->jump_rel, cp->smooth_radius, PS, d_zs);
+            hipLaunchKernelGGL(seg_bend_kernel, gp, B, 0, st, PS, fz, W, H, cp->bend_radius, p->jump_abs, p->jump_rel, cos2, fz2, L, d_cut, hdr);
+        } else {
+            hipLaunchKernelGGL(seg_bend_tiles_kernel, dim3((unsigned)((W + SEG_TILE_W - 1) / SEG_TILE_W), (unsigned)((H + SEG_TILE_H - 1) / SEG_TILE_H)), B, 0, st, dD, fz, W, H, cam->fx,
+                               cam->cx, cam->fy, cam->cy, cam->depth_scale, p->jump_abs, p->jump_rel, cp->smooth_radius, cp->bend_radius, cos2, fz2, L, d_cut, d_zs, hdr);
+        }
+        if (clock) STOCS_HIP_CHECK(hipEventRecord(tl_seg_ev[5], st));
+        lz = fz2;
+    }
     if (clock) STOCS_HIP_CHECK(hipEventRecord(tl_seg_ev[2], st));
     if (form == 1) {
-        hipLaunchKernelGGL(seg_union_global_kernel, gp, B, 0, st, fz, W, H, p->jump_abs, p->jump_rel, L);
+        hipLaunchKernelGGL(seg_union_global_kernel, gp, B, 0, st, lz, W, H, p->jump_abs, p->jump_rel, L);
     } else {
         const int ntx = (W + SEG_TILE_W - 1) / SEG_TILE_W, nty = (H + SEG_TILE_H - 1) / SEG_TILE_H;
-        hipLaunchKernelGGL(seg_tiles_kernel, dim3((unsigned)ntx, (unsigned)nty), B, 0, st, fz, W, H, p->jump_abs, p->jump_rel, L);
+        hipLaunchKernelGGL(seg_tiles_kernel, dim3((unsigned)ntx, (unsigned)nty), B, 0, st, lz, W, H, p->jump_abs, p->jump_rel, L);
         const int n_col = (ntx - 1) * H, n_all = n_col + (nty - 1) * W;
-        if (n_all > 0) hipLaunchKernelGGL(seg_borders_kernel, dim3((unsigned)((n_all + 255) / 256)), B, 0, st, fz, W, H, n_col, n_all, p->jump_abs, p->jump_rel, L);
+        if (n_all > 0) hipLaunchKernelGGL(seg_borders_kernel, dim3((unsigned)((n_all + 255) / 256)), B, 0, st, lz, W, H, n_col, n_all, p->jump_abs, p->jump_rel, L);
     }
     hipLaunchKernelGGL(seg_flatten_kernel, gp, B, 0, st, npix, L);
     if (clock) STOCS_HIP_CHECK(hipEventRecord(tl_seg_ev[3], st));
@@ -610,7 +827,7 @@ int stocs_segment_frame(const stocs_camera* cam, const uint16_t* depth, const st
     hipLaunchKernelGGL(seg_keep_kernel, gp1, B, 0, st, L, size, npix, (uint32_t)p->min_pixels, keep, hdr);
     STOCS_HIP_CHECK(exclusive_scan(tmp, tb_keep, keep, kpos, (size_t)npix + 1, st));
     hipLaunchKernelGGL(seg_records_init_kernel, gp, B, 0, st, keep, kpos, size, npix, d_rec, hdr);
-    hipLaunchKernelGGL(seg_relabel_kernel, gp, B, 0, st, L, fz, keep, kpos, W, npix, d_lab, d_cls, d_rec);
+    hipLaunchKernelGGL(seg_relabel_kernel, gp, B, 0, st, L, lz, keep, kpos, W, npix, d_lab, d_cls, d_rec);
     hipLaunchKernelGGL(seg_edges_kernel, gp, B, 0, st, d_lab, W, H, d_edge);
     STOCS_HIP_CHECK(hipGetLastError());
     STOCS_HIP_CHECK(hipMemcpyAsync(pin, d_out, back_bytes, hipMemcpyDeviceToHost, st));
@@ -618,6 +835,7 @@ int stocs_segment_frame(const stocs_camera* cam, const uint16_t* depth, const st
 
     const SegHeader* h = (const SegHeader*)(pin + o_hdr);
     *out = h->r;
+    if (cout) *cout = h->c;
     if (!out->plane_found) { out->plane[0] = out->plane[1] = out->plane[2] = out->plane[3] = 0.0f; out->n_refit = 0; }
     for (int k = 0; k < 10; ++k) tl_seg_mom[k] = h->mom[k];
     tl_seg_mom_valid = true;
@@ -625,13 +843,31 @@ int stocs_segment_frame(const stocs_camera* cam, const uint16_t* depth, const st
         STOCS_HIP_CHECK(hipEventElapsedTime(&tl_seg_ms[0], tl_seg_ev[0], tl_seg_ev[1]));
         STOCS_HIP_CHECK(hipEventElapsedTime(&tl_seg_ms[1], tl_seg_ev[2], tl_seg_ev[3]));
         tl_seg_ms_valid = true;
+        if (cp) { STOCS_HIP_CHECK(hipEventElapsedTime(&tl_seg_bend_ms, tl_seg_ev[4], tl_seg_ev[5])); tl_seg_bend_ms_valid = true; }
     }
-    if (out->n_segments > cap_records) { set_error("stocs_segment_frame: %d segments, cap_records %d", out->n_segments, cap_records); return STOCS_ERR_CAPACITY; }
+    if (out->n_segments > cap_records) { set_error("%s: %d segments, cap_records %d", who, out->n_segments, cap_records); return STOCS_ERR_CAPACITY; }
     if (labels) memcpy(labels, pin + o_lab, 4 * (size_t)npix);
     if (class_prob) memcpy(class_prob, pin + o_cls, 2 * (size_t)npix);
     if (edge) memcpy(edge, pin + o_edge, (size_t)npix);
+    if (cut) memcpy(cut, pin + o_cut, (size_t)npix);
+    if (smoothed) memcpy(smoothed, pin + o_zs, 4 * (size_t)npix);
     if (out->n_segments > 0) memcpy(records, pin + o_rec, 32 * (size_t)out->n_segments);
     return STOCS_OK;
+}
+}  // namespace stocs
+
+extern "C" {
+
+int stocs_segment_frame(const stocs_camera* cam, const uint16_t* depth, const stocs_segment_params* p, int device, uint16_t* class_prob, int32_t* labels,
+                        uint8_t* edge, stocs_segment_record* records, int cap_records, stocs_segment_result* out) {
+    return segment_run("stocs_segment_frame", cam, depth, p, NULL, device, class_prob, labels, edge, NULL, NULL, records, cap_records, out, NULL, cam && depth && p && out);
+}
+
+int stocs_segment_frame_convex(const stocs_camera* cam, const uint16_t* depth, const stocs_segment_params* p, const stocs_segment_convex_params* cp, int device,
+                               uint16_t* class_prob, int32_t* labels, uint8_t* edge, uint8_t* cut, float* smoothed, stocs_segment_record* records, int cap_records,
+                               stocs_segment_result* out, stocs_segment_convex_result* cout) {
+    return segment_run("stocs_segment_frame_convex", cam, depth, p, cp, device, class_prob, labels, edge, cut, smoothed, records, cap_records, out, cout,
+                       cam && depth && p && cp && out && cout);
 }
 
 }  // extern "C"

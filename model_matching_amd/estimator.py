@@ -1482,12 +1482,27 @@ def segment_params(**kw):
     return p
 
 
-def segment_frame(depth_u16, K, depth_scale, device=-1, cap_records=None, images=("class_prob", "labels", "edge"), **params):
+def segment_convex_params(**kw):
+    """stocs_segment_convex_params with the library's defaults and kw on top; a value outside its range raises."""
+    cp = capi.SegmentConvexParams()
+    capi.load().stocs_default_segment_convex_params(C.byref(cp))
+    for k, v in kw.items():
+        if not hasattr(cp, k):
+            raise TypeError("segment_frame: no convex parameter %r" % k)
+        setattr(cp, k, v)
+    capi.check(capi.load().stocs_check_segment_convex_params(C.byref(cp)))
+    return cp
+
+
+def segment_frame(depth_u16, K, depth_scale, device=-1, cap_records=None, images=("class_prob", "labels", "edge"), convex=None, **params):
     """A depth-only frame's class image from its geometry (stocs_segment_frame): the support plane is found and removed, what stands on it
     is split into depth-connected segments.  Returns (result dict, records, images dict): the records as a structured array (root, pixels,
     c0, r0, c1, r1, zmin, zmax), images["class_prob"] (uint16: 10000 in a kept segment, what ingest_scene and set_frame take),
     images["labels"] (int32, 1 .. n_segments) and images["edge"] (uint8, 255 = interior, what set_edge_map takes).  params: the fields of
-    stocs_segment_params.  cap_records None: as many as the frame can hold (pixels // min_pixels)."""
+    stocs_segment_params.  cap_records None: as many as the frame can hold (pixels // min_pixels).  convex: None, or True (the defaults) or a
+    dict of the fields of stocs_segment_convex_params: touching objects are cut apart at concave creases before the labelling
+    (stocs_segment_frame_convex); the result dict then holds n_tested_h, n_tested_v, n_cut_h, n_cut_v and n_cut too, and `images` may name
+    "cut" (uint8: bit 0 horizontal, bit 1 vertical) and "smoothed" (float32, NaN off the foreground)."""
     L = capi.load()
     d = np.ascontiguousarray(depth_u16, np.uint16)
     H, W = d.shape
@@ -1499,6 +1514,19 @@ def segment_frame(depth_u16, K, depth_scale, device=-1, cap_records=None, images
     img = {"class_prob": np.zeros((H, W), np.uint16) if "class_prob" in images else None, "labels": np.zeros((H, W), np.int32) if "labels" in images else None,
            "edge": np.zeros((H, W), np.uint8) if "edge" in images else None}
     ptr = lambda a, t: a.ctypes.data_as(t) if a is not None else None
+    if convex is not None and convex is not False:
+        cp = segment_convex_params(**({} if convex is True else dict(convex)))
+        cout = capi.SegmentConvexResult()
+        img["cut"] = np.zeros((H, W), np.uint8) if "cut" in images else None
+        img["smoothed"] = np.zeros((H, W), np.float32) if "smoothed" in images else None
+        capi.check(L.stocs_segment_frame_convex(C.byref(cam), d.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(p), C.byref(cp), device,
+                                                ptr(img["class_prob"], C.POINTER(C.c_uint16)), ptr(img["labels"], capi._ip), ptr(img["edge"], capi._u8p),
+                                                ptr(img["cut"], capi._u8p), ptr(img["smoothed"], capi._fp), rec if cap > 0 else None, cap, C.byref(out), C.byref(cout)))
+        res = {f: getattr(out, f) for f, _ in capi.SegmentResult._fields_ if f not in ("plane", "reserved")}
+        res.update({f: getattr(cout, f) for f, _ in capi.SegmentConvexResult._fields_ if f != "reserved"})
+        res["plane"] = np.array(list(out.plane), np.float32)
+        records = np.frombuffer(rec, dtype=np.dtype([(f, np.float32 if f in ("zmin", "zmax") else np.int32) for f, _ in capi.SegmentRecord._fields_]))[:out.n_segments].copy()
+        return res, records, {k: v for k, v in img.items() if v is not None}
     capi.check(L.stocs_segment_frame(C.byref(cam), d.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(p), device, ptr(img["class_prob"], C.POINTER(C.c_uint16)),
                                      ptr(img["labels"], capi._ip), ptr(img["edge"], capi._u8p), rec if cap > 0 else None, cap, C.byref(out)))
     res = {f: getattr(out, f) for f, _ in capi.SegmentResult._fields_ if f not in ("plane", "reserved")}
@@ -1523,6 +1551,13 @@ def segment_last_device_ms():
     a, b = C.c_float(0), C.c_float(0)
     capi.check(capi.load().stocs_segment_last_device_ms(C.byref(a), C.byref(b)))
     return a.value, b.value
+
+
+def segment_last_bend_ms():
+    """The bend step's time in the calling thread's last segment_frame(convex=...) under STOCS_SEGMENT_CLOCK=1."""
+    a = C.c_float(0)
+    capi.check(capi.load().stocs_segment_last_bend_ms(C.byref(a)))
+    return a.value
 
 
 def segment_last_moments():

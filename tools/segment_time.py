@@ -5,7 +5,15 @@ each the median of REPS calls after WARM warm-up calls; beside them the numpy re
 640 x 480 (a table scene, the three example frames of tests/golden, blobs, a checkerboard, one component) and the sizes the tests use.  The
 default form (SEG_DEFAULT_FORM in csrc/segment.hip) is chosen on the 640 x 480 rows.
 
-    python tools/segment_time.py [--out profiles/segment_time.json]"""
+    python tools/segment_time.py [--out profiles/segment_time.json]
+
+With --convex: the concavity cut (stocs_segment_frame_convex) on the same frames -> profiles/segment_convex_time.json.  Per frame, at the cut's
+defaults and the default label form: the HIP-event time of the bend step under both bend forms (1: a lane per pixel, device memory; 2: tiles in
+LDS) beside the label group's, the host time of the whole call with and without the cut, and, with --parent-lib PATH (a libstocs_hip.so built
+from the parent commit), the plain call through that library in alternation with the plain call through this one: A/A evidence that nothing
+existing moved.
+
+    python tools/segment_time.py --convex [--parent-lib PATH] [--out profiles/segment_convex_time.json]"""
 import glob
 import json
 import os
@@ -41,7 +49,78 @@ def frames():
     return out
 
 
+def timed(fn, clock):
+    """medians over REPS calls after WARM: host ms of fn() and of each value clock() returns"""
+    host, dev = [], []
+    for i in range(WARM + REPS):
+        t0 = time.perf_counter()
+        res = fn()
+        dt = (time.perf_counter() - t0) * 1e3
+        c = clock()
+        if i >= WARM:
+            host.append(dt); dev.append(c)
+    return res, float(np.median(host)), float(np.min(host)), [float(x) for x in np.median(np.array(dev, np.float64).reshape(len(host), -1), axis=0)]
+
+
+def plain_through(lib_path, frames_):
+    """host ms (median, min) of the plain stocs_segment_frame per frame through another build of the library, in a child process so that the two
+    libraries never share a process; prints one JSON list"""
+    import subprocess
+    code = ("import json, sys, time, numpy as np\n"
+            "sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
+            "from model_matching_amd import capi\n"
+            "capi.LIB_PATH = %r\n"
+            "import ctypes\n"
+            "capi.SIGNATURES = {k: v for k, v in capi.SIGNATURES.items() if hasattr(ctypes.CDLL(capi.LIB_PATH), k)}   # an older build lacks the newer entry points\n"
+            "import tools.segment_time as st\n"
+            "rows = []\n"
+            "for name, d, K, scale, kw in st.frames():\n"
+            "    _, med, mn, _ = st.timed(lambda: st.E.segment_frame(d, K, scale, **kw), lambda: 0.0)\n"
+            "    rows.append([name, med, mn])\n"
+            "print('ROWS ' + json.dumps(rows))\n") % (ROOT, os.path.join(ROOT, "tests"), lib_path)
+    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=ROOT, timeout=600)
+    assert r.returncode == 0, r.stdout + r.stderr
+    return {n: (a, b) for n, a, b in json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("ROWS ")][0][5:])}
+
+
+def main_convex():
+    out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "segment_convex_time.json")
+    parent = sys.argv[sys.argv.index("--parent-lib") + 1] if "--parent-lib" in sys.argv else None
+    os.environ["STOCS_SEGMENT_CLOCK"] = "1"
+    os.environ.pop("STOCS_SEGMENT_FORM", None)
+    fr = frames()
+    this_lib = os.path.join(ROOT, "model_matching_amd", "libstocs_hip.so")
+    order = ("this", "parent", "this", "parent", "parent", "this")
+    aa = [plain_through(parent if w == "parent" else this_lib, fr) for w in order] if parent else None
+    rows = []
+    for name, d, K, scale, kw in fr:
+        res0, plain_med, plain_min, (score0, label0) = timed(lambda: E.segment_frame(d, K, scale, **kw)[0], E.segment_last_device_ms)
+        row = {"frame": name, "plain": {"call_host_ms_median": plain_med, "call_host_ms_min": plain_min, "label_device_ms_median": label0, "n_segments": res0["n_segments"]}}
+        for form in ("1", "2"):
+            os.environ["STOCS_SEGMENT_BEND_FORM"] = form
+            res, med, mn, (bend, label) = timed(lambda: E.segment_frame(d, K, scale, convex=True, **kw)[0], lambda: (E.segment_last_bend_ms(), E.segment_last_device_ms()[1]))
+            row["bend_form_%s" % form] = {"call_host_ms_median": med, "call_host_ms_min": mn, "bend_device_ms_median": bend, "label_device_ms_median": label,
+                                           "n_segments": res["n_segments"], "n_cut": res["n_cut"], "n_tested": res["n_tested_h"] + res["n_tested_v"]}
+        del os.environ["STOCS_SEGMENT_BEND_FORM"]
+        assert row["bend_form_1"]["n_cut"] == row["bend_form_2"]["n_cut"] and row["bend_form_1"]["n_segments"] == row["bend_form_2"]["n_segments"], name
+        row["faster_bend_form"] = 1 if row["bend_form_1"]["bend_device_ms_median"] < row["bend_form_2"]["bend_device_ms_median"] else 2
+        if aa:
+            row["plain_call_host_ms_median_aa"] = [[w, a[name][0]] for w, a in zip(order, aa)]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    out = {"what": "stocs_segment_frame_convex on an MI355X at the cut's defaults (radius 4, smoothing 2, 25 degrees) and the default label form: HIP-event time of the bend "
+                   "step per bend form beside the label group's, host time of the whole call (through the Python wrapper) with and without the cut; medians of %d calls "
+                   "after %d.  plain_call_host_ms_median_aa: the plain call through a library built from the parent commit and through this one, "
+                   "each run in a process of its own, in the order listed" % (REPS, WARM),
+           "default_bend_form": 1, "rows": rows, "unmeasured": "frame sizes other than those listed; real frames beyond the three examples; radii and smoothing off the defaults"}
+    with open(out_path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
 def main():
+    if "--convex" in sys.argv:
+        return main_convex()
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "segment_time.json")
     os.environ["STOCS_SEGMENT_CLOCK"] = "1"
     rows = []
