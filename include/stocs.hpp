@@ -1445,8 +1445,10 @@ struct SegmentedFrame {
     std::vector<uint8_t> cut;             // from the overload with the cut: bit 0 horizontal, bit 1 vertical
 };
 inline stocs_segment_params default_segment_params() { stocs_segment_params p; stocs_default_segment_params(&p); return p; }
-inline SegmentedFrame segment_frame(const uint16_t* depth, const std::vector<float>& camera_intrinsics, int image_width, int image_height, float read_depth_scale,
-                                    const stocs_segment_params& prm = default_segment_params(), int device = -1) {
+inline stocs_segment_convex_params default_segment_convex_params() { stocs_segment_convex_params p; stocs_default_segment_convex_params(&p); return p; }
+// both overloads below: the camera, the vectors sized, the call (convex NULL: stocs_segment_frame, and out.convex stays zero), the throw
+inline SegmentedFrame segment_frame_impl(const uint16_t* depth, const std::vector<float>& camera_intrinsics, int image_width, int image_height, float read_depth_scale,
+                                         const stocs_segment_params& prm, const stocs_segment_convex_params* convex, int device) {
     if (camera_intrinsics.size() < 4) throw std::runtime_error("camera_intrinsics must hold {fx, cx, fy, cy}");
     if (image_width < 1 || image_height < 1 || prm.min_pixels < 1) throw std::runtime_error("segment_frame: an empty frame or min_pixels < 1");
     stocs_camera cam;
@@ -1458,30 +1460,22 @@ inline SegmentedFrame segment_frame(const uint16_t* depth, const std::vector<flo
     const size_t npix = (size_t)image_width * image_height, cap = npix / (size_t)prm.min_pixels;   // no more segments than this fit the frame
     out.records.resize(cap ? cap : 1);
     out.class_prob.resize(npix); out.labels.resize(npix); out.edge.resize(npix);
-    if (stocs_segment_frame(&cam, depth, &prm, device, out.class_prob.data(), out.labels.data(), out.edge.data(), out.records.data(), (int)cap, &out.result) != STOCS_OK)
-        throw std::runtime_error(std::string("stocs_segment_frame: ") + stocs_last_error());
+    if (convex) out.cut.resize(npix);
+    const int rc = convex ? stocs_segment_frame_convex(&cam, depth, &prm, convex, device, out.class_prob.data(), out.labels.data(), out.edge.data(), out.cut.data(), NULL, out.records.data(),
+                                                       (int)cap, &out.result, &out.convex)
+                          : stocs_segment_frame(&cam, depth, &prm, device, out.class_prob.data(), out.labels.data(), out.edge.data(), out.records.data(), (int)cap, &out.result);
+    if (rc != STOCS_OK) throw std::runtime_error(std::string(convex ? "stocs_segment_frame_convex: " : "stocs_segment_frame: ") + stocs_last_error());
     out.records.resize((size_t)out.result.n_segments);
     return out;
 }
+inline SegmentedFrame segment_frame(const uint16_t* depth, const std::vector<float>& camera_intrinsics, int image_width, int image_height, float read_depth_scale,
+                                    const stocs_segment_params& prm = default_segment_params(), int device = -1) {
+    return segment_frame_impl(depth, camera_intrinsics, image_width, image_height, read_depth_scale, prm, NULL, device);
+}
 // The same with the concavity cut in front of the labelling (stocs_segment_frame_convex): touching objects come apart at concave creases.
-inline stocs_segment_convex_params default_segment_convex_params() { stocs_segment_convex_params p; stocs_default_segment_convex_params(&p); return p; }
 inline SegmentedFrame segment_frame(const uint16_t* depth, const std::vector<float>& camera_intrinsics, int image_width, int image_height, float read_depth_scale,
                                     const stocs_segment_params& prm, const stocs_segment_convex_params& convex, int device = -1) {
-    if (camera_intrinsics.size() < 4) throw std::runtime_error("camera_intrinsics must hold {fx, cx, fy, cy}");
-    if (image_width < 1 || image_height < 1 || prm.min_pixels < 1) throw std::runtime_error("segment_frame: an empty frame or min_pixels < 1");
-    stocs_camera cam;
-    cam.fx = camera_intrinsics[0]; cam.cx = camera_intrinsics[1]; cam.fy = camera_intrinsics[2]; cam.cy = camera_intrinsics[3];
-    cam.depth_scale = read_depth_scale; cam.width = image_width; cam.height = image_height;
-    cam.normal_method = STOCS_NORMALS_DEPTH_GRADIENT;   // (not looked at)
-    SegmentedFrame out;
-    const size_t npix = (size_t)image_width * image_height, cap = npix / (size_t)prm.min_pixels;
-    out.records.resize(cap ? cap : 1);
-    out.class_prob.resize(npix); out.labels.resize(npix); out.edge.resize(npix); out.cut.resize(npix);
-    if (stocs_segment_frame_convex(&cam, depth, &prm, &convex, device, out.class_prob.data(), out.labels.data(), out.edge.data(), out.cut.data(), NULL, out.records.data(), (int)cap,
-                                   &out.result, &out.convex) != STOCS_OK)
-        throw std::runtime_error(std::string("stocs_segment_frame_convex: ") + stocs_last_error());
-    out.records.resize((size_t)out.result.n_segments);
-    return out;
+    return segment_frame_impl(depth, camera_intrinsics, image_width, image_height, read_depth_scale, prm, &convex, device);
 }
 
 // Not in the reference (its driver runs once per object): every object of one frame from one ingest (stocs_ingest_scene_multi).

@@ -22,13 +22,13 @@
 #include <limits.h>
 
 #include <algorithm>
-#include <map>
 #include <vector>
 
 #include "mesh_sample.h"
 #include "prims.h"
 #include "segment.h"
 #include "stocs_ctx.h"
+#include "thread_cache.h"
 
 namespace stocs {
 
@@ -392,38 +392,16 @@ __global__ __launch_bounds__(256) void model_normals_kernel(const float4* __rest
 // ---- workspace: every temporary of a call comes out of a grow-only arena cached per host thread and device, so a
 // caller that ingests one frame after the other does no hipMalloc / hipFree after the first frame.
 // stocs_trim() gives the calling thread's cached memory back.
-static thread_local std::map<int, Arena>* tl_ws = NULL;
-static thread_local Arena* tl_cur = NULL;
-
-// Pinned staging of a frame's images (in) and cloud (out), per calling thread: a copy between device memory and the caller's PAGEABLE arrays
+// Its pinned block stages a frame's images (in) and cloud (out): a copy between device memory and the caller's PAGEABLE arrays
 // goes through the runtime's own staging path -- the four output copies of a frame stalled the calling thread for 240-280 us (kernel trace of
 // tools/frame_latency.py, round 5b); through this block they are device -> pinned copies and host memcpy's of half a megabyte.
-static thread_local void* tl_pin = NULL;
-static thread_local size_t tl_pin_bytes = 0;
-static int staging(size_t bytes, char** out) {
-    if (tl_pin_bytes < bytes) {
-        if (tl_pin) { (void)hipHostFree(tl_pin); tl_pin = NULL; tl_pin_bytes = 0; }
-        const size_t want = bytes + bytes / 4 + ((size_t)1 << 20);
-        STOCS_HIP_CHECK(pinned_malloc(&tl_pin, want));
-        tl_pin_bytes = want;
-    }
-    *out = (char*)tl_pin;
-    return STOCS_OK;
-}
-
-static int workspace_begin(int device) {
-    if (!tl_ws) tl_ws = new std::map<int, Arena>();
-    int dev = device;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-    tl_cur = &(*tl_ws)[dev];
-    return tl_cur->reset();   // the previous call synchronised before it returned
-}
+static thread_local ThreadCache tl_cache;
 
 template <class T>
 struct Buf {   // typed view of workspace memory
     T* p;
     Buf() : p(NULL) {}
-    int alloc(size_t n) { return tl_cur->take(n * sizeof(T), (void**)&p); }
+    int alloc(size_t n) { return tl_cache.cur->take(n * sizeof(T), (void**)&p); }
 };
 
 // out[0..2] = min, out[3..5] = max of the leaf coordinates; out[6..7] = min, out[8..9] = max of the x and y leaf coordinates of the
@@ -742,7 +720,7 @@ static int mesh_sample_count_run(const char* who, const float* pos3, int nv, con
         return rc;
     char* pin = NULL;
     const size_t o_v = 4096, o_t = o_v + al256((size_t)nv * 16);
-    if ((rc = staging(o_t + (size_t)nt * 16, &pin))) return rc;
+    if ((rc = tl_cache.staging(o_t + (size_t)nt * 16, &pin))) return rc;
     float* hv = (float*)(pin + o_v);
     int32_t* ht = (int32_t*)(pin + o_t);
     for (int i = 0; i < nv; ++i) { hv[4 * i] = pos3[3 * i]; hv[4 * i + 1] = pos3[3 * i + 1]; hv[4 * i + 2] = pos3[3 * i + 2]; hv[4 * i + 3] = 0.0f; }
@@ -808,14 +786,8 @@ using namespace stocs;
 extern "C" {
 
 int stocs_trim(void) {
-    if (tl_ws) {
-        (void)hipDeviceSynchronize();
-        for (std::map<int, Arena>::iterator it = tl_ws->begin(); it != tl_ws->end(); ++it) it->second.destroy();
-        delete tl_ws;
-        tl_ws = NULL;
-        tl_cur = NULL;
-    }
-    if (tl_pin) { (void)hipHostFree(tl_pin); tl_pin = NULL; tl_pin_bytes = 0; }
+    if (tl_cache.ws) (void)hipDeviceSynchronize();
+    tl_cache.trim();
     segment_trim();
     return STOCS_OK;
 }
@@ -827,14 +799,14 @@ int stocs_ingest_scene(const stocs_camera* cam, const uint16_t* depth, const uin
     if (rc) return rc;
     if (device >= 0) STOCS_HIP_CHECK(hipSetDevice(device));
     IngestTick tick("stocs ingest");
-    if ((rc = workspace_begin(device))) return rc;
+    if ((rc = tl_cache.begin(device))) return rc;
     tick("workspace");
     hipStream_t st = NULL;
     const int W = cam->width, H = cam->height, npx = W * H;
     Buf<uint16_t> dD, dC;
     if ((rc = dD.alloc(npx)) || (rc = dC.alloc(npx))) return rc;
     char* pin = NULL;
-    if ((rc = staging((size_t)npx * 40 + 4096, &pin))) return rc;     // in: two u16 images (4 B per pixel); out: at most one point per pixel, 36 B each
+    if ((rc = tl_cache.staging((size_t)npx * 40 + 4096, &pin))) return rc;     // in: two u16 images (4 B per pixel); out: at most one point per pixel, 36 B each
     memcpy(pin, depth, 2 * (size_t)npx); memcpy(pin + 2 * (size_t)npx, class_prob, 2 * (size_t)npx);
     STOCS_HIP_CHECK(hipMemcpyAsync(dD.p, pin, 2 * (size_t)npx, hipMemcpyHostToDevice, st));
     STOCS_HIP_CHECK(hipMemcpyAsync(dC.p, pin + 2 * (size_t)npx, 2 * (size_t)npx, hipMemcpyHostToDevice, st));
@@ -902,7 +874,7 @@ int stocs_ingest_scene_multi(const stocs_camera* cam, const uint16_t* depth, int
     if (rc) return rc;
     if (device >= 0) STOCS_HIP_CHECK(hipSetDevice(device));
     IngestTick tick("stocs ingest multi");
-    if ((rc = workspace_begin(device))) return rc;
+    if ((rc = tl_cache.begin(device))) return rc;
     tick("workspace");
     hipStream_t st = NULL;
     const int W = cam->width, H = cam->height, npx = W * H, K = n_objects;
@@ -911,7 +883,7 @@ int stocs_ingest_scene_multi(const stocs_camera* cam, const uint16_t* depth, int
     // staging: 4 KB of small read-backs, then the depth image and the K class images (the cloud comes down through the block later)
     char* pin = NULL;
     const size_t in_bytes = (size_t)(2 + 2 * K) * npx;
-    if ((rc = staging(4096 + in_bytes, &pin))) return rc;
+    if ((rc = tl_cache.staging(4096 + in_bytes, &pin))) return rc;
     int* pin_small = (int*)pin;
     memcpy(pin + 4096, depth, 2 * (size_t)npx); memcpy(pin + 4096 + 2 * (size_t)npx, class_probs, 2 * (size_t)K * npx);
     STOCS_HIP_CHECK(hipMemcpyAsync(dD.p, pin + 4096, 2 * (size_t)npx, hipMemcpyHostToDevice, st));
@@ -953,7 +925,7 @@ int stocs_ingest_scene_multi(const stocs_camera* cam, const uint16_t* depth, int
     if (m > (size_t)std::max(cap, 0)) { set_error("stocs_ingest_scene_multi: %zu points over all objects, cap %d", m, cap); return STOCS_ERR_CAPACITY; }
     if (m == 0) return STOCS_OK;
     // (the images in the staging block were consumed before the offsets came back: the block is free for the clouds)
-    if ((rc = staging(36 * m, &pin))) return rc;
+    if ((rc = tl_cache.staging(36 * m, &pin))) return rc;
     char* h_pos = pin; char* h_nrm = pin + 12 * m; char* h_prob = pin + 24 * m; char* h_px = pin + 28 * m;
     if (pos3) STOCS_HIP_CHECK(hipMemcpyAsync(h_pos, o_pos.p, 12 * m, hipMemcpyDeviceToHost, st));
     if (nrm3) STOCS_HIP_CHECK(hipMemcpyAsync(h_nrm, o_nrm.p, 12 * m, hipMemcpyDeviceToHost, st));
@@ -974,7 +946,7 @@ int stocs_preprocess_model(const float* raw_pos3, int n_raw, float normal_radius
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: this library has no CPU fallback"); return STOCS_ERR_NO_DEVICE; }
     if (device >= 0) STOCS_HIP_CHECK(hipSetDevice(device));
-    { int rc0 = workspace_begin(device); if (rc0) return rc0; }
+    { int rc0 = tl_cache.begin(device); if (rc0) return rc0; }
     hipStream_t st = NULL;
     std::vector<float4> hp((size_t)n_raw);
     for (int i = 0; i < n_raw; ++i) hp[i] = make_float4(raw_pos3[3 * i], raw_pos3[3 * i + 1], raw_pos3[3 * i + 2], 0.f);
@@ -1014,7 +986,7 @@ int stocs_mesh_sample_counts(const float* pos3, int nv, const int32_t* tris3, in
     if (nt == 0) return STOCS_OK;
     if ((rc = ingest_require_device())) return rc;
     if (device >= 0) STOCS_HIP_CHECK(hipSetDevice(device));
-    if ((rc = workspace_begin(device))) return rc;
+    if ((rc = tl_cache.begin(device))) return rc;
     hipStream_t st = NULL;
     MeshSampleRun R;
     if ((rc = mesh_sample_count_run(who, pos3, nv, tris3, nt, spacing, seed, false, area_total != NULL, R, st))) return rc;
@@ -1022,7 +994,7 @@ int stocs_mesh_sample_counts(const float* pos3, int nv, const int32_t* tris3, in
     if (n_skipped) *n_skipped = R.skipped;
     if (!counts && !area_total) return STOCS_OK;
     char* pin = NULL;
-    if ((rc = staging((size_t)nt * 12, &pin))) return rc;   // (the mesh in the block was consumed before the total came back)
+    if ((rc = tl_cache.staging((size_t)nt * 12, &pin))) return rc;   // (the mesh in the block was consumed before the total came back)
     double* h_area = (double*)pin;
     int32_t* h_counts = (int32_t*)(pin + (size_t)nt * 8);
     if (area_total) STOCS_HIP_CHECK(hipMemcpyAsync(h_area, R.area.p, (size_t)nt * 8, hipMemcpyDeviceToHost, st));
@@ -1045,7 +1017,7 @@ int stocs_mesh_sample(const float* pos3, int nv, const int32_t* tris3, int nt, f
     if (nt == 0) return STOCS_OK;
     if ((rc = ingest_require_device())) return rc;
     if (device >= 0) STOCS_HIP_CHECK(hipSetDevice(device));
-    if ((rc = workspace_begin(device))) return rc;
+    if ((rc = tl_cache.begin(device))) return rc;
     hipStream_t st = NULL;
     MeshSampleRun R;
     if ((rc = mesh_sample_count_run(who, pos3, nv, tris3, nt, spacing, seed, true, false, R, st))) return rc;
@@ -1056,7 +1028,7 @@ int stocs_mesh_sample(const float* pos3, int nv, const int32_t* tris3, int nt, f
     Buf<float4> pos, nrm; Buf<int32_t> tri;
     if ((rc = mesh_sample_run(R, nt, seed, orient, out_tri != NULL, pos, nrm, tri, st))) return rc;
     char* pin = NULL;
-    if ((rc = staging(36 * n, &pin))) return rc;   // (the mesh in the block was consumed before the total came back)
+    if ((rc = tl_cache.staging(36 * n, &pin))) return rc;   // (the mesh in the block was consumed before the total came back)
     const float4* h_pos = (const float4*)pin; const float4* h_nrm = (const float4*)(pin + 16 * n); const int32_t* h_tri = (const int32_t*)(pin + 32 * n);
     if (out_pos3) STOCS_HIP_CHECK(hipMemcpyAsync(pin, pos.p, 16 * n, hipMemcpyDeviceToHost, st));
     if (out_nrm3) STOCS_HIP_CHECK(hipMemcpyAsync(pin + 16 * n, nrm.p, 16 * n, hipMemcpyDeviceToHost, st));
@@ -1082,7 +1054,7 @@ int stocs_preprocess_model_mesh(const float* pos3, int nv, const int32_t* tris3,
     if (nt == 0) return STOCS_OK;
     if ((rc = ingest_require_device())) return rc;
     if (device >= 0) STOCS_HIP_CHECK(hipSetDevice(device));
-    if ((rc = workspace_begin(device))) return rc;
+    if ((rc = tl_cache.begin(device))) return rc;
     hipStream_t st = NULL;
     const float h = spacing == 0.0f ? voxel_size / 4.0f : spacing;
     MeshSampleRun R;

@@ -1,5 +1,5 @@
-// segment.h -- what segment.hip shares with the rest of the library: stocs_trim (ingest.hip) gives the calling thread's cached
-// segmentation workspace, pinned block and clock events back through this.
+// segment.h -- what segment.hip shares with the rest of the library: stocs_trim (ingest.hip) trims its own thread cache and gives the
+// calling thread's segmentation cache (thread_cache.h: arenas and pinned block) and the clock's events back through this.
 #ifndef STOCS_SEGMENT_H
 #define STOCS_SEGMENT_H
 namespace stocs {

@@ -23,16 +23,21 @@
 //                     seg_borders (tile borders only, device memory) + seg_flatten.  Every link points from a larger index to a smaller
 //                     one, so both forms end at the component's lowest index whatever the order.
 //   seg_sizes, seg_keep, (library scan), seg_records_init, seg_relabel, seg_edges
+//
+// Host: both entry points refuse their NULL pointers and hand a SegCall to segment_run, the one launch sequence; the thread's arena per device
+// and pinned block are a ThreadCache (thread_cache.h) of this file's own, beside ingest.hip's; SegLast is the clock and what the three
+// stocs_segment_last_* entry points return.  What a third cut rule or label form adds: DESIGN 7.26.
 #include <math.h>
+#include <stddef.h>
 #include <stdlib.h>
 #include <string.h>
 
 #include <cmath>
-#include <map>
 
 #include "prims.h"
 #include "segment.h"
 #include "stocs_ctx.h"
+#include "thread_cache.h"
 #include "wave_bits.h"
 
 namespace stocs {
@@ -56,10 +61,21 @@ __device__ __forceinline__ bool seg_inlier(float4 p, const float* __restrict__ q
     return s * s <= q[6];
 }
 
+// the counting tails (wg_add_counts) address these counters as arrays: n_on_plane, n_above, n_below and n_tested_h .. n_cut are adjacent
+static_assert(offsetof(stocs_segment_result, n_above) == offsetof(stocs_segment_result, n_on_plane) + 4 && offsetof(stocs_segment_result, n_below) == offsetof(stocs_segment_result, n_on_plane) + 8, "seg_heights");
+static_assert(offsetof(stocs_segment_convex_result, n_tested_h) == 0 && offsetof(stocs_segment_convex_result, n_cut) == 16, "seg_bend_store");
+
+__device__ __forceinline__ float seg_nan() { return __int_as_float(0x7fc00000); }   // the quiet NaN of "not foreground", "cut" and "outside the image"
+// pixel (row i, column j) at depth z -> x, y: in double, one cast each.  The smoothed points are formed by the same expression
+// (tests/segment_convex_ref.py relies on the two being equal bit for bit)
+__device__ __forceinline__ V3 seg_unproject(int i, int j, float z, float fx, float cx, float fy, float cy) {
+    return mk3((float)(((double)j - (double)cx) * (double)z / (double)fx), (float)(((double)i - (double)cy) * (double)z / (double)fy), z);
+}
+
 __global__ __launch_bounds__(256) void seg_points_kernel(const uint16_t* __restrict__ depth, int W, int H, float fx, float cx, float fy, float cy, float depth_scale,
                                                          float max_depth, int stride, int LW, float4* __restrict__ P, uint32_t* __restrict__ lat_flag,
                                                          SegHeader* __restrict__ hdr) {
-    __shared__ int s_n[4];
+    __shared__ int s_n[4][1];
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     bool valid = false;
     if (idx < W * H) {
@@ -67,13 +83,12 @@ __global__ __launch_bounds__(256) void seg_points_kernel(const uint16_t* __restr
         const uint16_t raw = depth[idx];
         const float z = (float)raw * depth_scale;
         valid = raw != 0 && z <= max_depth;
-        P[idx] = make_float4((float)(((double)j - (double)cx) * (double)z / (double)fx), (float)(((double)i - (double)cy) * (double)z / (double)fy), z, valid ? 1.0f : 0.0f);
+        const V3 q = seg_unproject(i, j, z, fx, cx, fy, cy);
+        P[idx] = make_float4(q.x, q.y, q.z, valid ? 1.0f : 0.0f);
         if (i % stride == 0 && j % stride == 0) lat_flag[(i / stride) * LW + j / stride] = valid ? 1u : 0u;
     }
     const int c = __popcll(__ballot(valid));
-    if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) { const int t = s_n[0] + s_n[1] + s_n[2] + s_n[3]; if (t) atomicAdd(&hdr->r.n_valid, t); }
+    wg_add_counts<1>(&c, s_n, &hdr->r.n_valid);
 }
 
 __global__ __launch_bounds__(256) void seg_compact_kernel(const float4* __restrict__ P, int W, int stride, int LW, int nl, const uint32_t* __restrict__ lat_flag,
@@ -246,26 +261,20 @@ __global__ __launch_bounds__(256) void seg_heights_kernel(const float4* __restri
             on = valid && fabsf(h) <= tol; above = valid && h > tol; below = valid && h < -tol;
             fg = above && h <= max_height;
         }
-        fz[idx] = fg ? p.z : __int_as_float(0x7fc00000);
+        fz[idx] = fg ? p.z : seg_nan();
         L[idx] = fg ? idx : -1;
         size[idx] = 0;
     }
-    const int c0 = __popcll(__ballot(on)), c1 = __popcll(__ballot(above)), c2 = __popcll(__ballot(below));
-    if ((threadIdx.x & 63) == 0) { s_n[threadIdx.x >> 6][0] = c0; s_n[threadIdx.x >> 6][1] = c1; s_n[threadIdx.x >> 6][2] = c2; }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        const int t = s_n[0][threadIdx.x] + s_n[1][threadIdx.x] + s_n[2][threadIdx.x] + s_n[3][threadIdx.x];
-        if (t) atomicAdd(threadIdx.x == 0 ? &hdr->r.n_on_plane : threadIdx.x == 1 ? &hdr->r.n_above : &hdr->r.n_below, t);
-    }
+    const int c[3] = {(int)__popcll(__ballot(on)), (int)__popcll(__ballot(above)), (int)__popcll(__ballot(below))};
+    wg_add_counts<3>(c, s_n, &hdr->r.n_on_plane);
 }
 
 // ---- steps 4a and 4b: the concavity cut in front of the labelling (stocs_segment_frame_convex).  A smoothed point is (xs, ys, zs); off the
 // foreground and outside the image all three are NaN, so every test on it is false.
-__device__ __forceinline__ V3 seg_nan3() { const float n = __int_as_float(0x7fc00000); return mk3(n, n, n); }
+__device__ __forceinline__ V3 seg_nan3() { const float n = seg_nan(); return mk3(n, n, n); }
 // zs of the integer window sum, and x, y from it as seg_points forms them from z
 __device__ __forceinline__ V3 seg_smoothed_point(uint32_t S, uint32_t N, int i, int j, float fx, float cx, float fy, float cy, float depth_scale) {
-    const float zs = ((float)S / (float)N) * depth_scale;
-    return mk3((float)(((double)j - (double)cx) * (double)zs / (double)fx), (float)(((double)i - (double)cy) * (double)zs / (double)fy), zs);
+    return seg_unproject(i, j, ((float)S / (float)N) * depth_scale, fx, cx, fy, cy);
 }
 // one triple: bit 0 tested, bit 1 cut
 __device__ __forceinline__ int seg_bend_triple(V3 l, V3 c, V3 r, float rf, float jump_abs, float jump_rel, float cos2) {
@@ -277,25 +286,17 @@ __device__ __forceinline__ int seg_bend_triple(V3 l, V3 c, V3 r, float rf, float
     const bool bend = ab <= 0.0f || ab * ab < cos2 * (aa * bb);
     return (toward && bend) ? 3 : 1;
 }
-// what a lane leaves of its pixel (th, tv: the two triples' bits) and the five counts of its wavefront into s_n[wave]
+// what a lane leaves of its pixel (th, tv: the two triples' bits); its wavefront's five counts are added to acc, in the order of
+// stocs_segment_convex_result's counters (wg_add_counts<5> on &hdr->c.n_tested_h ends either kernel)
 __device__ __forceinline__ void seg_bend_store(bool inside, int idx, float z, int th, int tv, float* __restrict__ fz2, int* __restrict__ L, uint8_t* __restrict__ cut, int* acc) {
     const int bits = ((th >> 1) & 1) | (tv & 2);
     if (inside) {
         cut[idx] = (uint8_t)bits;
-        fz2[idx] = bits ? __int_as_float(0x7fc00000) : z;
+        fz2[idx] = bits ? seg_nan() : z;
         if (bits) L[idx] = -1;
     }
     acc[0] += __popcll(__ballot(th & 1)); acc[1] += __popcll(__ballot(tv & 1)); acc[2] += __popcll(__ballot(th & 2)); acc[3] += __popcll(__ballot(tv & 2));
     acc[4] += __popcll(__ballot(bits != 0));
-}
-__device__ __forceinline__ void seg_bend_counts(const int* acc, int (*s_n)[5], SegHeader* __restrict__ hdr) {
-    if ((threadIdx.x & 63) == 0)
-        for (int k = 0; k < 5; ++k) s_n[threadIdx.x >> 6][k] = acc[k];
-    __syncthreads();
-    if (threadIdx.x < 5) {
-        const int t = (s_n[0][threadIdx.x] + s_n[1][threadIdx.x]) + (s_n[2][threadIdx.x] + s_n[3][threadIdx.x]);
-        if (t) atomicAdd(&hdr->c.n_tested_h + threadIdx.x, t);
-    }
 }
 
 // form 1, step 4a: a lane per pixel, the window read from device memory
@@ -335,7 +336,7 @@ __global__ __launch_bounds__(256) void seg_bend_kernel(const float4* __restrict_
     }
     int acc[5] = {0, 0, 0, 0, 0};
     seg_bend_store(inside, idx, inside ? fz[idx] : 0.0f, th, tv, fz2, L, cut, acc);
-    seg_bend_counts(acc, s_n, hdr);
+    wg_add_counts<5>(acc, s_n, &hdr->c.n_tested_h);
 }
 
 // form 2: a workgroup per tile of SEG_TILE_W x SEG_TILE_H pixels.  Stage: the raw depth of every foreground pixel of the tile and a halo of
@@ -363,7 +364,7 @@ __global__ __launch_bounds__(256) void seg_bend_tiles_kernel(const uint16_t* __r
     if (!__syncthreads_or(own)) {                                         // a tile without foreground (the support plane, the background): nothing to smooth, test or count
         for (int k = 0; k < 4; ++k) {
             const int x = x0 + (threadIdx.x & 63), y = y0 + (threadIdx.x >> 6) * 4 + k;
-            if (x < W && y < H) { cut[y * W + x] = 0; fz2[y * W + x] = __int_as_float(0x7fc00000); if (zs_out) zs_out[y * W + x] = __int_as_float(0x7fc00000); }
+            if (x < W && y < H) { cut[y * W + x] = 0; fz2[y * W + x] = seg_nan(); if (zs_out) zs_out[y * W + x] = seg_nan(); }
         }
         return;
     }
@@ -403,38 +404,28 @@ __global__ __launch_bounds__(256) void seg_bend_tiles_kernel(const uint16_t* __r
             th = seg_bend_triple(mk3(s_x[at - r], s_y[at - r], s_z[at - r]), c, mk3(s_x[at + r], s_y[at + r], s_z[at + r]), rf, jump_abs, jump_rel, cos2);
             tv = seg_bend_triple(mk3(s_x[at - r * ZW], s_y[at - r * ZW], s_z[at - r * ZW]), c, mk3(s_x[at + r * ZW], s_y[at + r * ZW], s_z[at + r * ZW]), rf, jump_abs, jump_rel, cos2);
         }
-        seg_bend_store(inside, y * W + x, rc ? (float)rc * depth_scale : __int_as_float(0x7fc00000), th, tv, fz2, L, cut, acc);
+        seg_bend_store(inside, y * W + x, rc ? (float)rc * depth_scale : seg_nan(), th, tv, fz2, L, cut, acc);
     }
-    seg_bend_counts(acc, s_n, hdr);
+    wg_add_counts<5>(acc, s_n, &hdr->c.n_tested_h);
 }
 
 // ---- union-find.  L[x] <= x always, L[x] is in x's component, and only a root (L[x] == x) is ever given a new parent by the link below, or
 // a node a smaller one: values only fall.  A read may be stale (another compute unit's L1 is not refreshed): it then names an earlier parent,
 // still an ancestor, so a find only walks further; the link itself is an atomic at the L2.  No lane ever waits for another.
-__device__ __forceinline__ int seg_find_global(int* L, int x) {
-    for (;;) { const int p = __hip_atomic_load(&L[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); if (p == x) return x; x = p; }
+// SCOPE: the memory scope of the plain reads, __HIP_MEMORY_SCOPE_AGENT for labels in device memory, __HIP_MEMORY_SCOPE_WORKGROUP for a tile's in LDS.
+template <int SCOPE>
+__device__ __forceinline__ int seg_find(int* L, int x) {
+    for (;;) { const int p = __hip_atomic_load(&L[x], __ATOMIC_RELAXED, SCOPE); if (p == x) return x; x = p; }
 }
-__device__ __forceinline__ void seg_union_global(int* L, int a, int b) {
+template <int SCOPE>
+__device__ __forceinline__ void seg_union(int* L, int a, int b) {
     for (;;) {
-        a = seg_find_global(L, a); b = seg_find_global(L, b);
+        a = seg_find<SCOPE>(L, a); b = seg_find<SCOPE>(L, b);
         if (a == b) return;
         if (a < b) { const int t = a; a = b; b = t; }
         const int old = atomicMin(&L[a], b);       // a > b: a's parent becomes b unless somebody gave it a smaller one
         if (old == a) return;
         a = old;                                   // a had a parent `old` < a by now: its tree still has to meet b's
-    }
-}
-__device__ __forceinline__ int seg_find_lds(int* L, int x) {
-    for (;;) { const int p = __hip_atomic_load(&L[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); if (p == x) return x; x = p; }
-}
-__device__ __forceinline__ void seg_union_lds(int* L, int a, int b) {
-    for (;;) {
-        a = seg_find_lds(L, a); b = seg_find_lds(L, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }
-        const int old = atomicMin(&L[a], b);
-        if (old == a) return;
-        a = old;
     }
 }
 
@@ -445,8 +436,8 @@ __global__ __launch_bounds__(256) void seg_union_global_kernel(const float* __re
     const float z = fz[idx];
     if (!(z == z)) return;
     const int i = idx / W, j = idx % W;
-    if (j > 0 && seg_join(z, fz[idx - 1], jump_abs, jump_rel)) seg_union_global(L, idx, idx - 1);
-    if (i > 0 && seg_join(z, fz[idx - W], jump_abs, jump_rel)) seg_union_global(L, idx, idx - W);
+    if (j > 0 && seg_join(z, fz[idx - 1], jump_abs, jump_rel)) seg_union<__HIP_MEMORY_SCOPE_AGENT>(L, idx, idx - 1);
+    if (i > 0 && seg_join(z, fz[idx - W], jump_abs, jump_rel)) seg_union<__HIP_MEMORY_SCOPE_AGENT>(L, idx, idx - W);
 }
 
 // form 2: a workgroup labels one tile of SEG_TILE_W x SEG_TILE_H pixels in LDS.  A wavefront holds a tile row: one ballot of "joins its left
@@ -458,7 +449,7 @@ __global__ __launch_bounds__(256) void seg_tiles_kernel(const float* __restrict_
     __shared__ unsigned long long s_jl[SEG_TILE_H];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int x = blockIdx.x * SEG_TILE_W + lane, y0 = blockIdx.y * SEG_TILE_H;
-    const float nanf_ = __int_as_float(0x7fc00000);
+    const float nanf_ = seg_nan();
     float z[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -480,14 +471,14 @@ __global__ __launch_bounds__(256) void seg_tiles_kernel(const float* __restrict_
         const bool ju = seg_join(z[k], zu, jump_abs, jump_rel);
         const unsigned long long ub = __ballot(ju);
         const unsigned long long same = s_jl[r] & (ub << 1) & s_jl[r - 1];     // my left neighbour is in my run, joins upward, and its upper one is in my upper one's run
-        if (ju && !((same >> lane) & 1ull)) seg_union_lds(s_lab, r * SEG_TILE_W + lane, (r - 1) * SEG_TILE_W + lane);
+        if (ju && !((same >> lane) & 1ull)) seg_union<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, r * SEG_TILE_W + lane, (r - 1) * SEG_TILE_W + lane);
     }
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int r = wave * 4 + k, y = y0 + r;
         if (!(z[k] == z[k])) continue;
-        const int root = seg_find_lds(s_lab, r * SEG_TILE_W + lane);
+        const int root = seg_find<__HIP_MEMORY_SCOPE_WORKGROUP>(s_lab, r * SEG_TILE_W + lane);
         L[(size_t)y * W + x] = (y0 + root / SEG_TILE_W) * W + blockIdx.x * SEG_TILE_W + root % SEG_TILE_W;
     }
 }
@@ -498,14 +489,14 @@ __global__ __launch_bounds__(256) void seg_borders_kernel(const float* __restric
     int idx, nb;
     if (t < n_col) { const int y = t % H, x = (t / H + 1) * SEG_TILE_W; idx = y * W + x; nb = idx - 1; }
     else { const int u = t - n_col, x = u % W, y = (u / W + 1) * SEG_TILE_H; idx = y * W + x; nb = idx - W; }
-    if (seg_join(fz[idx], fz[nb], jump_abs, jump_rel)) seg_union_global(L, idx, nb);
+    if (seg_join(fz[idx], fz[nb], jump_abs, jump_rel)) seg_union<__HIP_MEMORY_SCOPE_AGENT>(L, idx, nb);
 }
 __global__ __launch_bounds__(256) void seg_flatten_kernel(int npix, int* L) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= npix) return;
     const int p = __hip_atomic_load(&L[idx], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (p < 0 || p == idx) return;
-    const int r = seg_find_global(L, p);
+    const int r = seg_find<__HIP_MEMORY_SCOPE_AGENT>(L, p);
     if (r != p) __hip_atomic_store(&L[idx], r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // a root's own entry is never written here
 }
 
@@ -522,14 +513,12 @@ __global__ __launch_bounds__(256) void seg_sizes_kernel(const int* __restrict__ 
 }
 __global__ __launch_bounds__(256) void seg_keep_kernel(const int* __restrict__ L, const uint32_t* __restrict__ size, int npix, uint32_t min_pixels, uint32_t* __restrict__ keep,
                                                        SegHeader* __restrict__ hdr) {
-    __shared__ int s_n[4];
+    __shared__ int s_n[4][1];
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const bool root = idx < npix && L[idx] == idx;
     if (idx <= npix) keep[idx] = (root && size[idx] >= min_pixels) ? 1u : 0u;     // entry npix: the scan's total
     const int c = __popcll(__ballot(root));
-    if ((threadIdx.x & 63) == 0) s_n[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) { const int t = s_n[0] + s_n[1] + s_n[2] + s_n[3]; if (t) atomicAdd(&hdr->r.n_components, t); }
+    wg_add_counts<1>(&c, s_n, &hdr->r.n_components);
 }
 __global__ __launch_bounds__(256) void seg_records_init_kernel(const uint32_t* __restrict__ keep, const uint32_t* __restrict__ kpos, const uint32_t* __restrict__ size, int npix,
                                                                stocs_segment_record* __restrict__ rec, SegHeader* __restrict__ hdr) {
@@ -586,50 +575,59 @@ __global__ __launch_bounds__(256) void seg_edges_kernel(const int32_t* __restric
     edge[idx] = in ? 255 : 0;
 }
 
-// ---- the calling thread's cached memory (stocs_trim gives it back through segment_trim): a grow-only arena per device, a pinned block,
-// the clock's events and what the last call left for the two "last" entry points
-static thread_local std::map<int, Arena>* tl_seg_ws = NULL;
-static thread_local void* tl_seg_pin = NULL;
-static thread_local size_t tl_seg_pin_bytes = 0;
-static thread_local hipEvent_t tl_seg_ev[6];           // 4, 5: around the bend step
-static thread_local bool tl_seg_ev_made = false;
-static thread_local int tl_seg_ev_dev = -1;          // events belong to the device they were made on
-static thread_local float tl_seg_ms[2] = {0.f, 0.f};
-static thread_local bool tl_seg_ms_valid = false;
-static thread_local float tl_seg_bend_ms = 0.f;
-static thread_local bool tl_seg_bend_ms_valid = false;
-static thread_local long long tl_seg_mom[10];
-static thread_local bool tl_seg_mom_valid = false;
+// ---- the calling thread's cached memory (stocs_trim gives it back through segment_trim): the arena per device and the pinned block
+// (an instance of its own: a thread that also ingests keeps both), and what its last call left
+static thread_local ThreadCache tl_seg_cache;
+
+// What the thread's last call left for the three stocs_segment_last_* entry points, one validity state each, and the clock behind two of
+// them (STOCS_SEGMENT_CLOCK=1): HIP events at named marks of the launch sequence, owned with the device they were made on.  Plain data,
+// all zero at first, so that it can be thread_local.
+struct SegLast {
+    enum Mark { SCORE_BEGIN, SCORE_END, BEND_BEGIN, BEND_END, LABEL_BEGIN, LABEL_END, N_MARKS };
+    hipEvent_t ev[N_MARKS];
+    bool ev_made; int ev_dev;
+    float score_ms, label_ms, bend_ms;
+    long long mom[10];
+    bool ms_valid, bend_valid, mom_valid;     // stocs_segment_last_device_ms, _bend_ms, _moments
+
+    void invalidate() { ms_valid = bend_valid = mom_valid = false; }
+    // the events, on `dev`: made by the thread's first clocked call, and anew when it has moved to another device
+    int arm(int dev) {
+        if (ev_made && ev_dev != dev) drop_events();
+        if (!ev_made) { for (int k = 0; k < N_MARKS; ++k) STOCS_HIP_CHECK(hipEventCreate(&ev[k])); ev_made = true; ev_dev = dev; }
+        return STOCS_OK;
+    }
+    // behind the call's synchronisation: the moments always, the times of a clocked call, the bend step's of a clocked convex call
+    int read(const long long* moments, bool clocked, bool bend) {
+        for (int k = 0; k < 10; ++k) mom[k] = moments[k];
+        mom_valid = true;
+        if (!clocked) return STOCS_OK;
+        STOCS_HIP_CHECK(hipEventElapsedTime(&score_ms, ev[SCORE_BEGIN], ev[SCORE_END]));
+        STOCS_HIP_CHECK(hipEventElapsedTime(&label_ms, ev[LABEL_BEGIN], ev[LABEL_END]));
+        ms_valid = true;
+        if (bend) { STOCS_HIP_CHECK(hipEventElapsedTime(&bend_ms, ev[BEND_BEGIN], ev[BEND_END])); bend_valid = true; }
+        return STOCS_OK;
+    }
+    void drop_events() { if (ev_made) { for (int k = 0; k < N_MARKS; ++k) (void)hipEventDestroy(ev[k]); ev_made = false; } }
+};
+static thread_local SegLast tl_seg_last;
 
 void segment_trim() {
-    if (tl_seg_ws) {
-        for (std::map<int, Arena>::iterator it = tl_seg_ws->begin(); it != tl_seg_ws->end(); ++it) it->second.destroy();
-        delete tl_seg_ws;
-        tl_seg_ws = NULL;
-    }
-    if (tl_seg_pin) { (void)hipHostFree(tl_seg_pin); tl_seg_pin = NULL; tl_seg_pin_bytes = 0; }
-    if (tl_seg_ev_made) { for (int k = 0; k < 6; ++k) (void)hipEventDestroy(tl_seg_ev[k]); tl_seg_ev_made = false; }
+    tl_seg_cache.trim();
+    tl_seg_last.drop_events();
 }
 
-static int segment_form(int* form) {
-    const char* e = getenv("STOCS_SEGMENT_FORM");
+// STOCS_SEGMENT_FORM, STOCS_SEGMENT_BEND_FORM: unset, empty or 0 (the default), 1 or 2; what_1, what_2 name the two forms in the refusal
+static int env_form(const char* name, const char* what_1, const char* what_2, int* form) {
+    const char* e = getenv(name);
     *form = 0;
     if (!e || !*e) return STOCS_OK;
     if ((e[0] == '0' || e[0] == '1' || e[0] == '2') && e[1] == 0) { *form = e[0] - '0'; return STOCS_OK; }
-    set_error("STOCS_SEGMENT_FORM=%s: 0 (default), 1 (device-memory union-find) or 2 (tiles in LDS)", e);
+    set_error("%s=%s: 0 (default), 1 (%s) or 2 (%s)", name, e, what_1, what_2);
     return STOCS_ERR_INVALID;
 }
 // the default label form: the one that was faster in every row of profiles/segment_time.json
 enum { SEG_DEFAULT_FORM = 2 };
-
-static int segment_bend_form(int* form) {
-    const char* e = getenv("STOCS_SEGMENT_BEND_FORM");
-    *form = 0;
-    if (!e || !*e) return STOCS_OK;
-    if ((e[0] == '0' || e[0] == '1' || e[0] == '2') && e[1] == 0) { *form = e[0] - '0'; return STOCS_OK; }
-    set_error("STOCS_SEGMENT_BEND_FORM=%s: 0 (default), 1 (a lane per pixel, device memory) or 2 (tiles in LDS)", e);
-    return STOCS_ERR_INVALID;
-}
 // the default bend form: the one that was faster on the camera frames of profiles/segment_convex_time.json: 20 - 29 us
 // against 30 - 35 us at 640 x 480; the tiled form is ahead only where the whole frame is foreground
 enum { SEG_DEFAULT_BEND_FORM = 1 };
@@ -677,8 +675,8 @@ int stocs_check_segment_convex_params(const stocs_segment_convex_params* cp) {
 }
 
 int stocs_segment_last_bend_ms(float* bend_ms) {
-    if (!tl_seg_bend_ms_valid) { set_error("stocs_segment_last_bend_ms: no stocs_segment_frame_convex of this thread ran with STOCS_SEGMENT_CLOCK=1"); return STOCS_ERR_STATE; }
-    if (bend_ms) *bend_ms = tl_seg_bend_ms;
+    if (!tl_seg_last.bend_valid) { set_error("stocs_segment_last_bend_ms: no stocs_segment_frame_convex of this thread ran with STOCS_SEGMENT_CLOCK=1"); return STOCS_ERR_STATE; }
+    if (bend_ms) *bend_ms = tl_seg_last.bend_ms;
     return STOCS_OK;
 }
 
@@ -689,71 +687,70 @@ int stocs_segment_tile(int* width, int* height) {
 }
 
 int stocs_segment_last_device_ms(float* score_ms, float* label_ms) {
-    if (!tl_seg_ms_valid) { set_error("stocs_segment_last_device_ms: no stocs_segment_frame of this thread ran with STOCS_SEGMENT_CLOCK=1"); return STOCS_ERR_STATE; }
-    if (score_ms) *score_ms = tl_seg_ms[0];
-    if (label_ms) *label_ms = tl_seg_ms[1];
+    if (!tl_seg_last.ms_valid) { set_error("stocs_segment_last_device_ms: no stocs_segment_frame of this thread ran with STOCS_SEGMENT_CLOCK=1"); return STOCS_ERR_STATE; }
+    if (score_ms) *score_ms = tl_seg_last.score_ms;
+    if (label_ms) *label_ms = tl_seg_last.label_ms;
     return STOCS_OK;
 }
 
 int stocs_segment_last_moments(int64_t* moments10) {
     if (!moments10) { set_error("stocs_segment_last_moments: NULL output"); return STOCS_ERR_INVALID; }
-    if (!tl_seg_mom_valid) { set_error("stocs_segment_last_moments: no stocs_segment_frame of this thread has run"); return STOCS_ERR_STATE; }
-    for (int k = 0; k < 10; ++k) moments10[k] = (int64_t)tl_seg_mom[k];
+    if (!tl_seg_last.mom_valid) { set_error("stocs_segment_last_moments: no stocs_segment_frame of this thread has run"); return STOCS_ERR_STATE; }
+    for (int k = 0; k < 10; ++k) moments10[k] = (int64_t)tl_seg_last.mom[k];
     return STOCS_OK;
 }
 
 }  // extern "C"
 
 namespace stocs {
+// what an entry point hands to the one launch sequence: its name for messages, and where the results go (each image may be NULL)
+struct SegCall {
+    const char* who;
+    uint16_t* class_prob; int32_t* labels; uint8_t* edge; uint8_t* cut; float* smoothed;
+    stocs_segment_record* records; int cap_records;
+    stocs_segment_result* out; stocs_segment_convex_result* cout;
+};
+static int seg_refuse_null(const char* who) { set_error("%s: NULL camera, depth image, params or result", who); return STOCS_ERR_INVALID; }
+
 // Both entry points: one launch sequence.  cp == NULL is stocs_segment_frame: no bend step, the label kernels read the foreground depth image
-// itself.  `who` names the entry point in messages; all_given: none of its required pointers is NULL.
-static int segment_run(const char* who, const stocs_camera* cam, const uint16_t* depth, const stocs_segment_params* p, const stocs_segment_convex_params* cp, int device,
-                       uint16_t* class_prob, int32_t* labels, uint8_t* edge, uint8_t* cut, float* smoothed, stocs_segment_record* records, int cap_records,
-                       stocs_segment_result* out, stocs_segment_convex_result* cout, bool all_given) {
-    if (!all_given) { set_error("%s: NULL camera, depth image, params or result", who); return STOCS_ERR_INVALID; }
+// itself.  The entry point has refused its NULL pointers.
+static int segment_run(const stocs_camera* cam, const uint16_t* depth, const stocs_segment_params* p, const stocs_segment_convex_params* cp, int device, const SegCall& o) {
+    const char* who = o.who;
     if (cam->width < 1 || cam->height < 1) { set_error("%s: frame of %d x %d pixels", who, cam->width, cam->height); return STOCS_ERR_INVALID; }
     int rc = stocs_check_segment_params(p);
     if (rc) return rc;
     if (cp && (rc = stocs_check_segment_convex_params(cp))) return rc;
-    if (cap_records < 0 || (!records && cap_records > 0)) { set_error("%s: cap_records %d with %s records", who, cap_records, records ? "given" : "NULL"); return STOCS_ERR_INVALID; }
+    if (o.cap_records < 0 || (!o.records && o.cap_records > 0)) { set_error("%s: cap_records %d with %s records", who, o.cap_records, o.records ? "given" : "NULL"); return STOCS_ERR_INVALID; }
     if ((long long)cam->width * cam->height > (long long)SEG_MAX_PIX) { set_error("%s: %d x %d pixels, above 2^22 (the refit's moments are 64-bit sums)", who, cam->width, cam->height); return STOCS_ERR_CAPACITY; }
-    int form = 0;
-    if ((rc = segment_form(&form))) return rc;
+    int form = 0, bform = 0;
+    if ((rc = env_form("STOCS_SEGMENT_FORM", "device-memory union-find", "tiles in LDS", &form))) return rc;
+    if (cp && (rc = env_form("STOCS_SEGMENT_BEND_FORM", "a lane per pixel, device memory", "tiles in LDS", &bform))) return rc;
     if (form == 0) form = SEG_DEFAULT_FORM;
-    int bform = 0;
-    if (cp && (rc = segment_bend_form(&bform))) return rc;
     if (bform == 0) bform = SEG_DEFAULT_BEND_FORM;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_error("no HIP device available: this library has no CPU fallback"); return STOCS_ERR_NO_DEVICE; }
     if (device >= 0) STOCS_HIP_CHECK(hipSetDevice(device));
-    tl_seg_ms_valid = false; tl_seg_mom_valid = false; tl_seg_bend_ms_valid = false;
+    SegLast& last = tl_seg_last;
+    last.invalidate();                                                                  // a call refused above leaves the last call's record as it was
 
     const int W = cam->width, H = cam->height, npix = W * H, s = p->score_stride, Hn = p->plane_hypotheses;
     const int LW = (W + s - 1) / s, LH = (H + s - 1) / s, nl = LW * LH;
+    const int ntx = (W + SEG_TILE_W - 1) / SEG_TILE_W, nty = (H + SEG_TILE_H - 1) / SEG_TILE_H;   // the tiles of seg_bend_tiles and seg_tiles
     const size_t nrec_dev = (size_t)npix / (size_t)p->min_pixels;                       // no more segments than this fit the frame
-    const size_t nrec_copy = std::min<size_t>(nrec_dev, (size_t)cap_records);
+    const size_t nrec_copy = std::min<size_t>(nrec_dev, (size_t)o.cap_records);
     hipStream_t st = NULL;
 
-    if (!tl_seg_ws) tl_seg_ws = new std::map<int, Arena>();
-    int dev = device;
-    if (dev < 0 && hipGetDevice(&dev) != hipSuccess) dev = 0;
-    Arena& ws = (*tl_seg_ws)[dev];
-    if ((rc = ws.reset())) return rc;                                                   // the previous call synchronised before it returned
+    Arena* ws = NULL;
+    if ((rc = tl_seg_cache.begin(device, &ws))) return rc;
 
     // the block that comes back in one copy: header | labels | class image | edge image | records
     Carve oc;
     const size_t o_hdr = oc.take(sizeof(SegHeader)), o_lab = oc.take(4 * (size_t)npix), o_cls = oc.take(2 * (size_t)npix), o_edge = oc.take((size_t)npix);
-    const size_t o_cut = cp ? oc.take((size_t)npix) : 0, o_zs = (cp && smoothed) ? oc.take(4 * (size_t)npix) : 0;       // in front of the records: they come back too
+    const size_t o_cut = cp ? oc.take((size_t)npix) : 0, o_zs = (cp && o.smoothed) ? oc.take(4 * (size_t)npix) : 0;       // in front of the records: they come back too
     const size_t o_rec = oc.take(32 * std::max<size_t>(nrec_dev, 1));
     const size_t back_bytes = o_rec + 32 * nrec_copy;
-    const size_t pin_need = al256(back_bytes) + 2 * (size_t)npix;
-    if (tl_seg_pin_bytes < pin_need) {
-        if (tl_seg_pin) { (void)hipHostFree(tl_seg_pin); tl_seg_pin = NULL; tl_seg_pin_bytes = 0; }
-        const size_t want = pin_need + pin_need / 4 + ((size_t)1 << 20);
-        STOCS_HIP_CHECK(pinned_malloc(&tl_seg_pin, want));
-        tl_seg_pin_bytes = want;
-    }
-    char* pin = (char*)tl_seg_pin;
+    char* pin = NULL;
+    if ((rc = tl_seg_cache.staging(al256(back_bytes) + 2 * (size_t)npix, &pin))) return rc;
     char* pin_depth = pin + al256(back_bytes);
 
     char* d_out = NULL; uint16_t* dD = NULL; float4 *P = NULL, *SP = NULL; uint32_t *lat_flag = NULL, *lat_pos = NULL, *cnt = NULL, *size = NULL, *keep = NULL, *kpos = NULL;
@@ -761,37 +758,39 @@ static int segment_run(const char* who, const stocs_camera* cam, const uint16_t*
     size_t tb_lat = 0, tb_keep = 0;
     STOCS_HIP_CHECK(exclusive_scan(NULL, tb_lat, lat_flag, lat_pos, (size_t)nl + 1, st));
     STOCS_HIP_CHECK(exclusive_scan(NULL, tb_keep, keep, kpos, (size_t)npix + 1, st));
-    if ((rc = ws.take(oc.total, (void**)&d_out)) || (rc = ws.take(2 * (size_t)npix, (void**)&dD)) || (rc = ws.take(16 * (size_t)npix, (void**)&P)) ||
-        (rc = ws.take(16 * (size_t)nl, (void**)&SP)) || (rc = ws.take(4 * ((size_t)nl + 1), (void**)&lat_flag)) || (rc = ws.take(4 * ((size_t)nl + 1), (void**)&lat_pos)) ||
-        (rc = ws.take(4 * (size_t)std::max(Hn, 1), (void**)&cnt)) || (rc = ws.take(32 * (size_t)std::max(Hn, 1), (void**)&hyp)) || (rc = ws.take(4 * (size_t)npix, (void**)&fz)) ||
-        (rc = ws.take(4 * (size_t)npix, (void**)&L)) || (rc = ws.take(4 * (size_t)npix, (void**)&size)) || (rc = ws.take(4 * ((size_t)npix + 1), (void**)&keep)) ||
-        (rc = ws.take(4 * ((size_t)npix + 1), (void**)&kpos)) || (rc = ws.take(std::max(tb_lat, tb_keep), (void**)&tmp)))
+    if ((rc = ws->take(oc.total, (void**)&d_out)) || (rc = ws->take(2 * (size_t)npix, (void**)&dD)) || (rc = ws->take(16 * (size_t)npix, (void**)&P)) ||
+        (rc = ws->take(16 * (size_t)nl, (void**)&SP)) || (rc = ws->take(4 * ((size_t)nl + 1), (void**)&lat_flag)) || (rc = ws->take(4 * ((size_t)nl + 1), (void**)&lat_pos)) ||
+        (rc = ws->take(4 * (size_t)std::max(Hn, 1), (void**)&cnt)) || (rc = ws->take(32 * (size_t)std::max(Hn, 1), (void**)&hyp)) || (rc = ws->take(4 * (size_t)npix, (void**)&fz)) ||
+        (rc = ws->take(4 * (size_t)npix, (void**)&L)) || (rc = ws->take(4 * (size_t)npix, (void**)&size)) || (rc = ws->take(4 * ((size_t)npix + 1), (void**)&keep)) ||
+        (rc = ws->take(4 * ((size_t)npix + 1), (void**)&kpos)) || (rc = ws->take(std::max(tb_lat, tb_keep), (void**)&tmp)))
         return rc;
-    if (cp && ((rc = ws.take(4 * (size_t)npix, (void**)&fz2)) || (bform == 1 && (rc = ws.take(16 * (size_t)npix, (void**)&PS))))) return rc;
-    SegHeader* hdr = (SegHeader*)(d_out + o_hdr);
-    int32_t* d_lab = (int32_t*)(d_out + o_lab); uint16_t* d_cls = (uint16_t*)(d_out + o_cls); uint8_t* d_edge = (uint8_t*)(d_out + o_edge);
-    stocs_segment_record* d_rec = (stocs_segment_record*)(d_out + o_rec);
+    if (cp && ((rc = ws->take(4 * (size_t)npix, (void**)&fz2)) || (bform == 1 && (rc = ws->take(16 * (size_t)npix, (void**)&PS))))) return rc;
+    SegHeader* hdr = Carve::at<SegHeader>(d_out, o_hdr);
+    int32_t* d_lab = Carve::at<int32_t>(d_out, o_lab); uint16_t* d_cls = Carve::at<uint16_t>(d_out, o_cls); uint8_t* d_edge = Carve::at<uint8_t>(d_out, o_edge);
+    uint8_t* d_cut = cp ? Carve::at<uint8_t>(d_out, o_cut) : NULL; float* d_zs = (cp && o.smoothed) ? Carve::at<float>(d_out, o_zs) : NULL;
+    stocs_segment_record* d_rec = Carve::at<stocs_segment_record>(d_out, o_rec);
 
-    const bool clock = getenv("STOCS_SEGMENT_CLOCK") != NULL && atoi(getenv("STOCS_SEGMENT_CLOCK")) == 1;
-    if (clock && tl_seg_ev_made && tl_seg_ev_dev != dev) { for (int k = 0; k < 6; ++k) (void)hipEventDestroy(tl_seg_ev[k]); tl_seg_ev_made = false; }
-    if (clock && !tl_seg_ev_made) { for (int k = 0; k < 6; ++k) STOCS_HIP_CHECK(hipEventCreate(&tl_seg_ev[k])); tl_seg_ev_made = true; tl_seg_ev_dev = dev; }
+    const char* ce = getenv("STOCS_SEGMENT_CLOCK");
+    const bool clock = ce != NULL && atoi(ce) == 1;
+    if (clock && (rc = last.arm(tl_seg_cache.dev))) return rc;
+    const auto mark = [&](SegLast::Mark m) { return clock ? hipEventRecord(last.ev[m], st) : hipSuccess; };
 
     memcpy(pin_depth, depth, 2 * (size_t)npix);
     STOCS_HIP_CHECK(hipMemcpyAsync(dD, pin_depth, 2 * (size_t)npix, hipMemcpyHostToDevice, st));
     STOCS_HIP_CHECK(hipMemsetAsync(hdr, 0, sizeof(SegHeader), st));
     STOCS_HIP_CHECK(hipMemsetAsync(lat_flag, 0, 4 * ((size_t)nl + 1), st));
     STOCS_HIP_CHECK(hipMemsetAsync(cnt, 0, 4 * (size_t)std::max(Hn, 1), st));
-    const dim3 B(256), gp((unsigned)((npix + 255) / 256)), gp1((unsigned)((npix + 256) / 256)), gl((unsigned)((nl + 255) / 256));
+    const dim3 B(256), gp((unsigned)((npix + 255) / 256)), gp1((unsigned)((npix + 256) / 256)), gl((unsigned)((nl + 255) / 256)), gt((unsigned)ntx, (unsigned)nty);
     hipLaunchKernelGGL(seg_points_kernel, gp, B, 0, st, dD, W, H, cam->fx, cam->cx, cam->fy, cam->cy, cam->depth_scale, p->max_depth, s, LW, P, lat_flag, hdr);
     STOCS_HIP_CHECK(exclusive_scan(tmp, tb_lat, lat_flag, lat_pos, (size_t)nl + 1, st));
     hipLaunchKernelGGL(seg_compact_kernel, gl, B, 0, st, P, W, s, LW, nl, lat_flag, lat_pos, SP);
-    if (clock) STOCS_HIP_CHECK(hipEventRecord(tl_seg_ev[0], st));
+    STOCS_HIP_CHECK(mark(SegLast::SCORE_BEGIN));
     if (Hn > 0) {
         hipLaunchKernelGGL(seg_hypotheses_kernel, dim3((unsigned)((Hn + 255) / 256)), B, 0, st, P, (uint32_t)npix, Hn, p->seed, p->plane_tolerance, hyp);
         hipLaunchKernelGGL(seg_score_kernel, dim3((unsigned)((nl + SEG_SCORE_PTS - 1) / SEG_SCORE_PTS), (unsigned)((Hn + SEG_SCORE_HYP - 1) / SEG_SCORE_HYP)), B, 0, st, SP, lat_pos + nl, hyp, Hn, cnt);
     }
     hipLaunchKernelGGL(seg_winner_kernel, dim3(1), B, 0, st, hyp, cnt, Hn, lat_pos + nl, p->plane_min_share, hdr);
-    if (clock) STOCS_HIP_CHECK(hipEventRecord(tl_seg_ev[1], st));
+    STOCS_HIP_CHECK(mark(SegLast::SCORE_END));
     if (Hn > 0) {
         hipLaunchKernelGGL(seg_refit_kernel, dim3(std::min(gp.x, 256u)), B, 0, st, P, npix, hdr);
         hipLaunchKernelGGL(seg_plane_kernel, dim3(1), dim3(64), 0, st, hdr);
@@ -799,30 +798,28 @@ static int segment_run(const char* who, const stocs_camera* cam, const uint16_t*
     hipLaunchKernelGGL(seg_heights_kernel, gp, B, 0, st, P, npix, p->plane_tolerance, p->max_height, hdr, fz, L, size);
     const float* lz = fz;                                                               // the depth image the label kernels and the relabelling read
     if (cp) {
-        uint8_t* d_cut = (uint8_t*)(d_out + o_cut); float* d_zs = smoothed ? (float*)(d_out + o_zs) : NULL;
         const float cos2 = cp->bend_cos * cp->bend_cos;
-        if (clock) STOCS_HIP_CHECK(hipEventRecord(tl_seg_ev[4], st));
+        STOCS_HIP_CHECK(mark(SegLast::BEND_BEGIN));
         if (bform == 1) {
             hipLaunchKernelGGL(seg_smooth_kernel, gp, B, 0, st, dD, fz, W, H, cam->fx, cam->cx, cam->fy, cam->cy, cam->depth_scale, p->jump_abs, p->jump_rel, cp->smooth_radius, PS, d_zs);
             hipLaunchKernelGGL(seg_bend_kernel, gp, B, 0, st, PS, fz, W, H, cp->bend_radius, p->jump_abs, p->jump_rel, cos2, fz2, L, d_cut, hdr);
         } else {
-            hipLaunchKernelGGL(seg_bend_tiles_kernel, dim3((unsigned)((W + SEG_TILE_W - 1) / SEG_TILE_W), (unsigned)((H + SEG_TILE_H - 1) / SEG_TILE_H)), B, 0, st, dD, fz, W, H, cam->fx,
-                               cam->cx, cam->fy, cam->cy, cam->depth_scale, p->jump_abs, p->jump_rel, cp->smooth_radius, cp->bend_radius, cos2, fz2, L, d_cut, d_zs, hdr);
+            hipLaunchKernelGGL(seg_bend_tiles_kernel, gt, B, 0, st, dD, fz, W, H, cam->fx, cam->cx, cam->fy, cam->cy, cam->depth_scale, p->jump_abs, p->jump_rel, cp->smooth_radius,
+                               cp->bend_radius, cos2, fz2, L, d_cut, d_zs, hdr);
         }
-        if (clock) STOCS_HIP_CHECK(hipEventRecord(tl_seg_ev[5], st));
+        STOCS_HIP_CHECK(mark(SegLast::BEND_END));
         lz = fz2;
     }
-    if (clock) STOCS_HIP_CHECK(hipEventRecord(tl_seg_ev[2], st));
+    STOCS_HIP_CHECK(mark(SegLast::LABEL_BEGIN));
     if (form == 1) {
         hipLaunchKernelGGL(seg_union_global_kernel, gp, B, 0, st, lz, W, H, p->jump_abs, p->jump_rel, L);
     } else {
-        const int ntx = (W + SEG_TILE_W - 1) / SEG_TILE_W, nty = (H + SEG_TILE_H - 1) / SEG_TILE_H;
-        hipLaunchKernelGGL(seg_tiles_kernel, dim3((unsigned)ntx, (unsigned)nty), B, 0, st, lz, W, H, p->jump_abs, p->jump_rel, L);
+        hipLaunchKernelGGL(seg_tiles_kernel, gt, B, 0, st, lz, W, H, p->jump_abs, p->jump_rel, L);
         const int n_col = (ntx - 1) * H, n_all = n_col + (nty - 1) * W;
         if (n_all > 0) hipLaunchKernelGGL(seg_borders_kernel, dim3((unsigned)((n_all + 255) / 256)), B, 0, st, lz, W, H, n_col, n_all, p->jump_abs, p->jump_rel, L);
     }
     hipLaunchKernelGGL(seg_flatten_kernel, gp, B, 0, st, npix, L);
-    if (clock) STOCS_HIP_CHECK(hipEventRecord(tl_seg_ev[3], st));
+    STOCS_HIP_CHECK(mark(SegLast::LABEL_END));
     hipLaunchKernelGGL(seg_sizes_kernel, gp, B, 0, st, L, npix, size);
     hipLaunchKernelGGL(seg_keep_kernel, gp1, B, 0, st, L, size, npix, (uint32_t)p->min_pixels, keep, hdr);
     STOCS_HIP_CHECK(exclusive_scan(tmp, tb_keep, keep, kpos, (size_t)npix + 1, st));
@@ -833,25 +830,19 @@ static int segment_run(const char* who, const stocs_camera* cam, const uint16_t*
     STOCS_HIP_CHECK(hipMemcpyAsync(pin, d_out, back_bytes, hipMemcpyDeviceToHost, st));
     STOCS_HIP_CHECK(hipStreamSynchronize(st));
 
-    const SegHeader* h = (const SegHeader*)(pin + o_hdr);
+    const SegHeader* h = Carve::at<const SegHeader>(pin, o_hdr);
+    stocs_segment_result* out = o.out;
     *out = h->r;
-    if (cout) *cout = h->c;
+    if (o.cout) *o.cout = h->c;
     if (!out->plane_found) { out->plane[0] = out->plane[1] = out->plane[2] = out->plane[3] = 0.0f; out->n_refit = 0; }
-    for (int k = 0; k < 10; ++k) tl_seg_mom[k] = h->mom[k];
-    tl_seg_mom_valid = true;
-    if (clock) {
-        STOCS_HIP_CHECK(hipEventElapsedTime(&tl_seg_ms[0], tl_seg_ev[0], tl_seg_ev[1]));
-        STOCS_HIP_CHECK(hipEventElapsedTime(&tl_seg_ms[1], tl_seg_ev[2], tl_seg_ev[3]));
-        tl_seg_ms_valid = true;
-        if (cp) { STOCS_HIP_CHECK(hipEventElapsedTime(&tl_seg_bend_ms, tl_seg_ev[4], tl_seg_ev[5])); tl_seg_bend_ms_valid = true; }
-    }
-    if (out->n_segments > cap_records) { set_error("%s: %d segments, cap_records %d", who, out->n_segments, cap_records); return STOCS_ERR_CAPACITY; }
-    if (labels) memcpy(labels, pin + o_lab, 4 * (size_t)npix);
-    if (class_prob) memcpy(class_prob, pin + o_cls, 2 * (size_t)npix);
-    if (edge) memcpy(edge, pin + o_edge, (size_t)npix);
-    if (cut) memcpy(cut, pin + o_cut, (size_t)npix);
-    if (smoothed) memcpy(smoothed, pin + o_zs, 4 * (size_t)npix);
-    if (out->n_segments > 0) memcpy(records, pin + o_rec, 32 * (size_t)out->n_segments);
+    if ((rc = last.read(h->mom, clock, cp != NULL))) return rc;
+    if (out->n_segments > o.cap_records) { set_error("%s: %d segments, cap_records %d", who, out->n_segments, o.cap_records); return STOCS_ERR_CAPACITY; }
+    if (o.labels) memcpy(o.labels, pin + o_lab, 4 * (size_t)npix);
+    if (o.class_prob) memcpy(o.class_prob, pin + o_cls, 2 * (size_t)npix);
+    if (o.edge) memcpy(o.edge, pin + o_edge, (size_t)npix);
+    if (o.cut) memcpy(o.cut, pin + o_cut, (size_t)npix);
+    if (o.smoothed) memcpy(o.smoothed, pin + o_zs, 4 * (size_t)npix);
+    if (out->n_segments > 0) memcpy(o.records, pin + o_rec, 32 * (size_t)out->n_segments);
     return STOCS_OK;
 }
 }  // namespace stocs
@@ -860,14 +851,17 @@ extern "C" {
 
 int stocs_segment_frame(const stocs_camera* cam, const uint16_t* depth, const stocs_segment_params* p, int device, uint16_t* class_prob, int32_t* labels,
                         uint8_t* edge, stocs_segment_record* records, int cap_records, stocs_segment_result* out) {
-    return segment_run("stocs_segment_frame", cam, depth, p, NULL, device, class_prob, labels, edge, NULL, NULL, records, cap_records, out, NULL, cam && depth && p && out);
+    const SegCall o = {"stocs_segment_frame", class_prob, labels, edge, NULL, NULL, records, cap_records, out, NULL};
+    if (!(cam && depth && p && out)) return seg_refuse_null(o.who);
+    return segment_run(cam, depth, p, NULL, device, o);
 }
 
 int stocs_segment_frame_convex(const stocs_camera* cam, const uint16_t* depth, const stocs_segment_params* p, const stocs_segment_convex_params* cp, int device,
                                uint16_t* class_prob, int32_t* labels, uint8_t* edge, uint8_t* cut, float* smoothed, stocs_segment_record* records, int cap_records,
                                stocs_segment_result* out, stocs_segment_convex_result* cout) {
-    return segment_run("stocs_segment_frame_convex", cam, depth, p, cp, device, class_prob, labels, edge, cut, smoothed, records, cap_records, out, cout,
-                       cam && depth && p && cp && out && cout);
+    const SegCall o = {"stocs_segment_frame_convex", class_prob, labels, edge, cut, smoothed, records, cap_records, out, cout};
+    if (!(cam && depth && p && cp && out && cout)) return seg_refuse_null(o.who);
+    return segment_run(cam, depth, p, cp, device, o);
 }
 
 }  // extern "C"

@@ -1470,28 +1470,28 @@ def ingest_scene_multi(depth_u16, probs_u16, K, depth_scale, voxel_size=0.005, c
     return [(pos[a:b].copy(), nrm[a:b].copy(), pr[a:b].copy(), px[a:b].copy()) for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
 
 
-def segment_params(**kw):
-    """stocs_segment_params with the library's defaults and kw on top; a value outside its range raises (stocs_check_segment_params)."""
-    p = capi.SegmentParams()
-    capi.load().stocs_default_segment_params(C.byref(p))
+def _params(struct, default_fn, check_fn, kw, what):
+    """A parameter struct with the library's defaults and kw on top; `what` names the kind of parameter in the TypeError."""
+    p = struct()
+    default_fn(C.byref(p))
     for k, v in kw.items():
         if not hasattr(p, k):
-            raise TypeError("segment_frame: no parameter %r" % k)
+            raise TypeError("segment_frame: no %s %r" % (what, k))
         setattr(p, k, v)
-    capi.check(capi.load().stocs_check_segment_params(C.byref(p)))
+    capi.check(check_fn(C.byref(p)))
     return p
+
+
+def segment_params(**kw):
+    """stocs_segment_params with the library's defaults and kw on top; a value outside its range raises (stocs_check_segment_params)."""
+    L = capi.load()
+    return _params(capi.SegmentParams, L.stocs_default_segment_params, L.stocs_check_segment_params, kw, "parameter")
 
 
 def segment_convex_params(**kw):
     """stocs_segment_convex_params with the library's defaults and kw on top; a value outside its range raises."""
-    cp = capi.SegmentConvexParams()
-    capi.load().stocs_default_segment_convex_params(C.byref(cp))
-    for k, v in kw.items():
-        if not hasattr(cp, k):
-            raise TypeError("segment_frame: no convex parameter %r" % k)
-        setattr(cp, k, v)
-    capi.check(capi.load().stocs_check_segment_convex_params(C.byref(cp)))
-    return cp
+    L = capi.load()
+    return _params(capi.SegmentConvexParams, L.stocs_default_segment_convex_params, L.stocs_check_segment_convex_params, kw, "convex parameter")
 
 
 def segment_frame(depth_u16, K, depth_scale, device=-1, cap_records=None, images=("class_prob", "labels", "edge"), convex=None, **params):
@@ -1511,28 +1511,26 @@ def segment_frame(depth_u16, K, depth_scale, device=-1, cap_records=None, images
     cap = (W * H) // p.min_pixels if cap_records is None else int(cap_records)
     rec = (capi.SegmentRecord * max(cap, 1))()
     out = capi.SegmentResult()
-    img = {"class_prob": np.zeros((H, W), np.uint16) if "class_prob" in images else None, "labels": np.zeros((H, W), np.int32) if "labels" in images else None,
-           "edge": np.zeros((H, W), np.uint8) if "edge" in images else None}
-    ptr = lambda a, t: a.ctypes.data_as(t) if a is not None else None
-    if convex is not None and convex is not False:
+    with_cut = convex is not None and convex is not False
+    kinds = {"class_prob": (np.uint16, C.POINTER(C.c_uint16)), "labels": (np.int32, capi._ip), "edge": (np.uint8, capi._u8p)}
+    if with_cut:
+        kinds.update({"cut": (np.uint8, capi._u8p), "smoothed": (np.float32, capi._fp)})
+    img = {k: np.zeros((H, W), t) for k, (t, _) in kinds.items() if k in images}
+    ptr = {k: img[k].ctypes.data_as(t) if k in img else None for k, (_, t) in kinds.items()}
+    front = (C.byref(cam), d.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(p))
+    back = (rec if cap > 0 else None, cap, C.byref(out))
+    res = {}
+    if with_cut:
         cp = segment_convex_params(**({} if convex is True else dict(convex)))
         cout = capi.SegmentConvexResult()
-        img["cut"] = np.zeros((H, W), np.uint8) if "cut" in images else None
-        img["smoothed"] = np.zeros((H, W), np.float32) if "smoothed" in images else None
-        capi.check(L.stocs_segment_frame_convex(C.byref(cam), d.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(p), C.byref(cp), device,
-                                                ptr(img["class_prob"], C.POINTER(C.c_uint16)), ptr(img["labels"], capi._ip), ptr(img["edge"], capi._u8p),
-                                                ptr(img["cut"], capi._u8p), ptr(img["smoothed"], capi._fp), rec if cap > 0 else None, cap, C.byref(out), C.byref(cout)))
-        res = {f: getattr(out, f) for f, _ in capi.SegmentResult._fields_ if f not in ("plane", "reserved")}
-        res.update({f: getattr(cout, f) for f, _ in capi.SegmentConvexResult._fields_ if f != "reserved"})
-        res["plane"] = np.array(list(out.plane), np.float32)
-        records = np.frombuffer(rec, dtype=np.dtype([(f, np.float32 if f in ("zmin", "zmax") else np.int32) for f, _ in capi.SegmentRecord._fields_]))[:out.n_segments].copy()
-        return res, records, {k: v for k, v in img.items() if v is not None}
-    capi.check(L.stocs_segment_frame(C.byref(cam), d.ctypes.data_as(C.POINTER(C.c_uint16)), C.byref(p), device, ptr(img["class_prob"], C.POINTER(C.c_uint16)),
-                                     ptr(img["labels"], capi._ip), ptr(img["edge"], capi._u8p), rec if cap > 0 else None, cap, C.byref(out)))
-    res = {f: getattr(out, f) for f, _ in capi.SegmentResult._fields_ if f not in ("plane", "reserved")}
+        capi.check(L.stocs_segment_frame_convex(*front, C.byref(cp), device, ptr["class_prob"], ptr["labels"], ptr["edge"], ptr["cut"], ptr["smoothed"], *back, C.byref(cout)))
+        res = {f: getattr(cout, f) for f, _ in capi.SegmentConvexResult._fields_ if f != "reserved"}
+    else:
+        capi.check(L.stocs_segment_frame(*front, device, ptr["class_prob"], ptr["labels"], ptr["edge"], *back))
+    res = dict({f: getattr(out, f) for f, _ in capi.SegmentResult._fields_ if f not in ("plane", "reserved")}, **res)
     res["plane"] = np.array(list(out.plane), np.float32)
     records = np.frombuffer(rec, dtype=np.dtype([(f, np.float32 if f in ("zmin", "zmax") else np.int32) for f, _ in capi.SegmentRecord._fields_]))[:out.n_segments].copy()
-    return res, records, {k: v for k, v in img.items() if v is not None}
+    return res, records, img
 
 
 def segment_class_images(labels, ids=None):

@@ -10,8 +10,8 @@ default form (SEG_DEFAULT_FORM in csrc/segment.hip) is chosen on the 640 x 480 r
 With --convex: the concavity cut (stocs_segment_frame_convex) on the same frames -> profiles/segment_convex_time.json.  Per frame, at the cut's
 defaults and the default label form: the HIP-event time of the bend step under both bend forms (1: a lane per pixel, device memory; 2: tiles in
 LDS) beside the label group's, the host time of the whole call with and without the cut, and, with --parent-lib PATH (a libstocs_hip.so built
-from the parent commit), the plain call through that library in alternation with the plain call through this one: A/A evidence that nothing
-existing moved.
+from the parent commit), the plain and the convex call through that library in alternation with the same through this one, their HIP-event
+group times beside them: A/B evidence that nothing existing moved.
 
     python tools/segment_time.py --convex [--parent-lib PATH] [--out profiles/segment_convex_time.json]"""
 import glob
@@ -63,8 +63,9 @@ def timed(fn, clock):
 
 
 def plain_through(lib_path, frames_):
-    """host ms (median, min) of the plain stocs_segment_frame per frame through another build of the library, in a child process so that the two
-    libraries never share a process; prints one JSON list"""
+    """host ms (median, min) of the plain stocs_segment_frame per frame through another build of the library, then the same of
+    stocs_segment_frame_convex at the default forms, then the medians of their HIP-event times ([score, label] and [bend, score, label]); in a
+    child process so that the two libraries never share a process; prints one JSON list"""
     import subprocess
     code = ("import json, sys, time, numpy as np\n"
             "sys.path.insert(0, %r); sys.path.insert(0, %r)\n"
@@ -75,12 +76,13 @@ def plain_through(lib_path, frames_):
             "import tools.segment_time as st\n"
             "rows = []\n"
             "for name, d, K, scale, kw in st.frames():\n"
-            "    _, med, mn, _ = st.timed(lambda: st.E.segment_frame(d, K, scale, **kw), lambda: 0.0)\n"
-            "    rows.append([name, med, mn])\n"
+            "    _, med, mn, dev = st.timed(lambda: st.E.segment_frame(d, K, scale, **kw), st.E.segment_last_device_ms)\n"
+            "    _, cmed, cmn, cdev = st.timed(lambda: st.E.segment_frame(d, K, scale, convex=True, **kw), lambda: (st.E.segment_last_bend_ms(),) + tuple(st.E.segment_last_device_ms()))\n"
+            "    rows.append([name, med, mn, cmed, cmn, dev, cdev])\n"
             "print('ROWS ' + json.dumps(rows))\n") % (ROOT, os.path.join(ROOT, "tests"), lib_path)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, cwd=ROOT, timeout=600)
     assert r.returncode == 0, r.stdout + r.stderr
-    return {n: (a, b) for n, a, b in json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("ROWS ")][0][5:])}
+    return {row[0]: tuple(row[1:]) for row in json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("ROWS ")][0][5:])}
 
 
 def main_convex():
@@ -106,12 +108,14 @@ def main_convex():
         row["faster_bend_form"] = 1 if row["bend_form_1"]["bend_device_ms_median"] < row["bend_form_2"]["bend_device_ms_median"] else 2
         if aa:
             row["plain_call_host_ms_median_aa"] = [[w, a[name][0]] for w, a in zip(order, aa)]
+            row["convex_call_host_ms_median_aa"] = [[w, a[name][2]] for w, a in zip(order, aa)]
+            row["device_ms_median_aa"] = [[w, a[name][4], a[name][5]] for w, a in zip(order, aa)]     # plain [score, label], convex [bend, score, label]
         rows.append(row)
         print(json.dumps(row), flush=True)
     out = {"what": "stocs_segment_frame_convex on an MI355X at the cut's defaults (radius 4, smoothing 2, 25 degrees) and the default label form: HIP-event time of the bend "
                    "step per bend form beside the label group's, host time of the whole call (through the Python wrapper) with and without the cut; medians of %d calls "
-                   "after %d.  plain_call_host_ms_median_aa: the plain call through a library built from the parent commit and through this one, "
-                   "each run in a process of its own, in the order listed" % (REPS, WARM),
+                   "after %d.  plain_call_host_ms_median_aa, convex_call_host_ms_median_aa: the plain and the convex call through a library built from the parent "
+                   "commit and through this one, each run in a process of its own, in the order listed" % (REPS, WARM),
            "default_bend_form": 1, "rows": rows, "unmeasured": "frame sizes other than those listed; real frames beyond the three examples; radii and smoothing off the defaults"}
     with open(out_path, "w") as f:
         json.dump(out, f, indent=1)
