@@ -103,6 +103,10 @@ def lib():
         L.orc_cone_samples.restype = C.c_int
         L.orc_index_normal.argtypes = [fp]
         L.orc_index_normal.restype = C.c_int
+        L.orc_index_pos.argtypes = [C.c_float, fp]
+        L.orc_index_pos.restype = C.c_int
+        L.orc_nset_cell.argtypes = [C.c_float, fp, fp, C.c_int, fp, fp, C.POINTER(C.c_uint32), C.c_int]
+        L.orc_nset_cell.restype = C.c_int
         L.orc_model_ratio.argtypes = [vp, fp]
         L.orc_model_ratio.restype = C.c_float
         L.orc_rigid_transform.argtypes = [vp, ip, ip, fp, fp]
@@ -418,6 +422,36 @@ def pose_diff(test16, base16, sym):
     r = C.c_float(0); t = C.c_float(0)
     lib().orc_pose_diff(pa, pb, ps, C.byref(r), C.byref(t))
     return r.value, t.value
+
+
+def normalset_params(eps_unit):
+    """(gridDepth, egSize, corrected epsilon) of the oracle's NormalSet(eps_unit)"""
+    d = C.c_int(0); g = C.c_int(0); c = C.c_float(0)
+    lib().orc_normalset_params(eps_unit, C.byref(d), C.byref(g), C.byref(c))
+    return d.value, g.value, c.value
+
+
+def index_normal(n3):
+    n, pn = _f(n3)
+    return lib().orc_index_normal(pn)
+
+
+def index_pos(eps_unit, p3):
+    p, pp = _f(p3)
+    return lib().orc_index_pos(eps_unit, pp)
+
+
+def nset_cell(eps_unit, pos, nrm, p3, n3=None):
+    """ids of one cell of a NormalSet(eps_unit) filled with (pos[i], nrm[i], i) in index order: the cell of (p3, n3), or p3's whole
+    position cell when n3 is None; in stored order"""
+    pos, ppos = _f(pos); nrm, pnrm = _f(nrm); p, pp = _f(p3)
+    pn = None
+    if n3 is not None:
+        n, pn = _f(n3)
+    out = np.zeros(max(len(pos), 1), np.uint32)
+    k = lib().orc_nset_cell(eps_unit, ppos, pnrm, len(pos), pp, pn, out.ctypes.data_as(C.POINTER(C.c_uint32)), len(out))
+    assert 0 <= k <= len(out), k
+    return out[:k]
 
 
 def set_index_build_threads(n):

@@ -1,6 +1,7 @@
 /*
  * stocs_oracle.cpp -- TEST INFRASTRUCTURE, NOT PRODUCT.  See stocs_oracle.h.
- * PARITY STATUS: "parity unpinned" (no reference tests / golden vectors exist; reference not buildable).
+ * PARITY STATUS: kd-tree and normal-set cells pinned to the reference's headers (ref_accel.cpp), the rest "parity unpinned"
+ * (no reference tests / golden vectors exist; no reference .cpp is buildable).
  *
  * Conventions for arithmetic that lives in the (absent) Eigen dependency -- stated once, used
  * everywhere, also documented in DESIGN.md "numerics":
@@ -1344,6 +1345,23 @@ int orc_normalset_params(float eps_unit, int* gridDepth, int* egSize, float* cel
 }
 int orc_cone_samples(float cos_alpha) { return NormalSet::nbSample(cos_alpha, NULL, NULL); }
 int orc_index_normal(const float* n3) { NormalSet ns(0.03f); return ns.indexNormal(ld(n3)); }
+int orc_index_pos(float eps_unit, const float* p3) { NormalSet ns(eps_unit); return ns.indexPos(ld(p3)); }
+int orc_nset_cell(float eps_unit, const float* pos3, const float* nrm3, int n, const float* p3, const float* n3, uint32_t* out, int cap) {
+    NormalSet ns(eps_unit);
+    for (int i = 0; i < n; ++i) ns.addElement(ld(pos3 + 3 * (size_t)i), ld(nrm3 + 3 * (size_t)i), (unsigned)i);
+    auto git = ns.grid.find(ns.indexPos(ld(p3)));
+    if (git == ns.grid.end()) return 0;
+    std::vector<unsigned> nei;
+    if (n3) {                                     // getNeighbors(p, n), normalset.hpp:151-163
+        const int nId = ns.indexNormal(ld(n3));
+        if (nId < 0 || nId >= 343) return -1;
+        nei = git->second[nId];
+    } else {                                      // getNeighbors(p), :134-148: the normal cells in index order
+        for (const std::vector<unsigned>& l : git->second) nei.insert(nei.end(), l.begin(), l.end());
+    }
+    for (size_t i = 0; i < nei.size() && (int)i < cap; ++i) out[i] = nei[i];
+    return (int)nei.size();
+}
 float orc_model_ratio(orc_ctx* c, float* g) { if (g) { g[0] = c->gcenter.x; g[1] = c->gcenter.y; g[2] = c->gcenter.z; } return c->ratio; }
 
 int orc_rigid_transform(orc_ctx* c, const int32_t* ids4, const int32_t* quad4, float* T, float* pose) {

@@ -6,11 +6,14 @@
  * {kdtree.h,normalset.h,normalset.hpp,bbox.h,utils.h}, include/super4pcs/pairCreationFunctor.h,
  * src/pose_clustering.cpp.  Every function cites the reference file:line it follows.
  *
- * PARITY STATUS: "parity unpinned".  The reference holds no tests, golden vectors or expected
- * outputs for this path and cannot be built here (needs Eigen, PCL,
- * OpenCV, Boost -- all absent).  This restatement is pinned only by hand-derived known-answer
- * tests (tests/test_oracle_*.py) and by internal cross-checks (kd-tree vs brute force, literal
- * 128-key std::map index vs the query-side form).
+ * PARITY STATUS: pinned to the reference's own code for the kd-tree and the normal set's cells
+ * (their headers compile unchanged into oracle/_ref/libref_accel.so, ref_accel.cpp;
+ * tests/test_ref_accel_cpu.py), "parity unpinned" for the rest.  The reference holds no tests,
+ * golden vectors or expected outputs for this path and none of its
+ * .cpp files can be built here (Eigen, PCL, OpenCV, Boost -- all absent).  The rest of this
+ * restatement is pinned only by hand-derived known-answer tests (tests/test_oracle_*.py) and by
+ * internal cross-checks (kd-tree vs brute force, literal 128-key std::map index vs the
+ * query-side form).
  *
  * Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may load this library.
  * The product (model_matching_amd/) never links, imports or calls it.
@@ -107,6 +110,11 @@ int64_t orc_find_congruent_seq(orc_ctx*, const int32_t* ids4, float inv1, float 
 int  orc_normalset_params(float eps_unit, int* gridDepth, int* egSize, float* cell);
 int  orc_cone_samples(float cos_alpha);
 int  orc_index_normal(const float* n3);
+int  orc_index_pos(float eps_unit, const float* p3);   /* position cell of NormalSet(eps_unit); p in the unit cube */
+/* a NormalSet(eps_unit) filled with addElement(pos[i], nrm[i], i), i = 0..n-1: the list of (p, n)'s cell, or with n3 == NULL of p's
+ * whole position cell, in stored order; returns its length, writes <= cap ids */
+int  orc_nset_cell(float eps_unit, const float* pos3, const float* nrm3, int n, const float* p3, const float* n3,
+                   uint32_t* out, int cap);
 float orc_model_ratio(orc_ctx*, float* gcenter3);
 
 /* ---- rows 11-12: rigid transform ---- */

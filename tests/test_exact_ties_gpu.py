@@ -99,16 +99,21 @@ def test_fixture_exercises_q11_in_default_mode(lattice):
     assert est.last_tie_counts() == (0, 0)
 
 
+# the kernel forms of test_per_point_parity_every_form (tests/test_ref_accel_gpu.py walks the same list), and the settings that undo one
+FORMS = ({"lcp_variant": 0}, {"lcp_variant": 31}, {"lcp_variant": 39}, {"lcp_variant": 24},
+         {"lcp_split": 0, "lcp_flat": 0}, {"lcp_split": 1, "lcp_flat": 1, "lcp_cull": 2}, {"lcp_cull": 0, "lcp_order": 2})
+FORM_DEFAULTS = (("lcp_variant", 99), ("lcp_split", 1), ("lcp_flat", 1), ("lcp_cull", 1), ("lcp_order", 1))
+
+
 def test_per_point_parity_every_form(lattice):
     est, orc, T = lattice
     est.set_option("exact_ties", 1)
     _parity(est, orc, T[:64])
-    for opts in ({"lcp_variant": 0}, {"lcp_variant": 31}, {"lcp_variant": 39}, {"lcp_variant": 24},
-                 {"lcp_split": 0, "lcp_flat": 0}, {"lcp_split": 1, "lcp_flat": 1, "lcp_cull": 2}, {"lcp_cull": 0, "lcp_order": 2}):
+    for opts in FORMS:
         for k, v in opts.items():
             est.set_option(k, v)
         _parity(est, orc, T[:16])
-        for k, v in (("lcp_variant", 99), ("lcp_split", 1), ("lcp_flat", 1), ("lcp_cull", 1), ("lcp_order", 1)):
+        for k, v in FORM_DEFAULTS:
             est.set_option(k, v)
 
 

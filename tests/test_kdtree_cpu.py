@@ -3,7 +3,7 @@ the reference's KdTree (orc_nn): the same scene index for every query, exact dis
 
 Both trees see identical floats: the product's tree is built over Oracle.scene_centred(), the positions the oracle's own tree
 holds.  Lattices with spacing 2^-9, symmetric about the origin, have an exactly zero sequential float centroid, so centring keeps
-their ties exact.  No device is needed."""
+their ties exact.  No device is needed.  tests/test_ref_accel_cpu.py holds both trees to the reference's own kdtree.h."""
 import numpy as np
 import pytest
 
