@@ -13,6 +13,7 @@
 #include <numeric>
 
 #include "normal_cone.h"
+#include "prims.h"
 #include "stocs_ctx.h"
 
 namespace stocs {
@@ -174,29 +175,48 @@ static int upload(T** dptr, const T* h, size_t n) {
     return STOCS_OK;
 }
 
-static void free_grid(stocs_ctx* c) {   // the grid lives in c->grid_mem, which the next build resets
-    c->grid.d_top = NULL; c->grid.d_cells = NULL; c->grid.d_list = NULL; c->grid.d_chunk_r = NULL; c->grid.d_flat = NULL;
-    c->grid.d_dist = NULL; c->grid.dist_ready = false; c->grid.oct_pending = false;
+static void free_grid(stocs_ctx* c) { reset_grid(c->grid); }   // the grid lives in c->grid_mem, which the next build resets
+
+// Which grid a build at cell edge eps / div makes: the context's settings and every environment switch of the build, read here, per
+// build (tests and A/B tools set them around one construction).  What still depends on a count of the build is decided where the count
+// becomes known, by the predicates next to build_grid_gpu (grid.hip).
+//   layout   dominance-pruned lists ("grid_prune" / STOCS_GRID_PRUNE, round 5: index-ordered at every cell edge, no early exit needed)
+//            unless STOCS_GRID_DENSE is set, which forces an unpruned layout (measurement switch, tools/layout_sweep.py): 0 =
+//            index-ordered lists whatever their length, 1 = centre-sorted always.  Unpruned and not forced -- the layouts of rounds 2-4,
+//            same scores bit for bit: at eps the index-ordered lists with the flat cell table and the sub-cell masks (the sparse
+//            layout); finer grids have neither, and the centre-sorted lists with early exit (the dense layout) win there whatever
+//            the list length (65 000-point scene at eps/2: 1.53 ms against 1.99 for index-ordered lists of 13 entries).
+//            long_lists: eps is final although its unpruned lists turned out long: centre-sorted there too
+//   prune_k  STOCS_GRID_PRUNE_K (measurement switch: 4, 8, 16; anything else is 8)
+//   cones, octants, own_sort   on unless STOCS_GRID_CONES=0, STOCS_GRID_OCTANTS=0, STOCS_SORT=rocprim (A/B runs, cross-checks)
+static GridForm grid_form(const stocs_ctx* c, int div, bool long_lists) {
+    auto env_int = [](const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; };
+    const char* force = getenv("STOCS_GRID_DENSE");
+    GridForm f;
+    if (force) f.layout = atoi(force) == 1 ? GRID_CENTRE_SORTED : GRID_INDEX_ORDERED;
+    else if (env_int("STOCS_GRID_PRUNE", c->grid_prune)) f.layout = GRID_PRUNED;
+    else f.layout = (div > 1 || long_lists) ? GRID_CENTRE_SORTED : GRID_INDEX_ORDERED;
+    f.div = (div < 1 || div > 4) ? 1 : div;
+    f.qbits = f.layout == GRID_CENTRE_SORTED ? 16 : 0;
+    const int pk = env_int("STOCS_GRID_PRUNE_K", 8);
+    f.prune_k = f.layout != GRID_PRUNED ? 0 : (pk == 4 || pk == 16) ? pk : 8;
+    f.cones = env_int("STOCS_GRID_CONES", 1) != 0;
+    f.flat = f.layout != GRID_CENTRE_SORTED && f.div == 1 && c->lcp_flat;
+    f.octants = f.layout == GRID_PRUNED && f.flat && env_int("STOCS_GRID_OCTANTS", 1) != 0;
+    f.own_sort = sort_own_allowed();
+    return f;
 }
 
-// One build at cell edge eps / div.  At eps the index-ordered lists with the flat cell table and the sub-cell masks (the sparse
-// layout); finer grids have neither, and the centre-sorted lists with early exit (the dense layout) win there whatever the list
-// length (65 000-point scene at eps/2: 1.53 ms against 1.99 for index-ordered lists of 13 entries; tools/layout_sweep.py).
-// last_resort: eps is final although its lists are long (the finer grid does not fit): centre-sorted there too.
+// One build at cell edge eps / div.  last_resort: eps is final (the finer grid does not fit), so lists that came out long are built
+// again in the layout for long lists, where the form has one
 static int build_grid_once(stocs_ctx* c, int div, bool last_resort = false) {
-    // STOCS_GRID_DENSE (measurement switch, tools/layout_sweep.py): 0 = index-ordered lists whatever their length, 1 = centre-sorted always
-    const char* force = getenv("STOCS_GRID_DENSE");
-    // round 5: dominance-pruned lists (grid.hip) -- index-ordered at every cell edge, no early exit needed; "grid_prune" 0 / STOCS_GRID_PRUNE=0
-    // keeps the layouts of rounds 2-4 (A/B and cross-check: same scores bit for bit)
-    const char* pe = getenv("STOCS_GRID_PRUNE");
-    const int prune = pe ? atoi(pe) : c->grid_prune;
-    if (prune && !force) return build_grid_gpu(c, div, 0, 1);
-    if (force) return build_grid_gpu(c, div, atoi(force) == 1 ? 1 : 0, 0);
-    if (div > 1) return build_grid_gpu(c, div, 1, 0);
-    int rc = build_grid_gpu(c, div, 0, 0);
+    const GridForm form = grid_form(c, div, false);
+    const int rc = build_grid_gpu(c, form);
     if (rc || !last_resort || c->grid.avg_list_len <= 16.0) return rc;
+    const GridForm again = grid_form(c, div, true);
+    if (again.layout == form.layout) return rc;
     free_grid(c);
-    return build_grid_gpu(c, div, 1, 0);
+    return build_grid_gpu(c, again);
 }
 
 static int build_grid_levels(stocs_ctx* c) {

@@ -3,26 +3,24 @@
 // kdtree.h:191-330, built by stocs_estimator::kdtree_initialize, stocs.cpp:966-980) as the spatial index of the
 // verification pass; the restricted-radius query it has to answer is kdtree.h:387-442.
 //
-// A new scene arrives with every camera frame, so the build is part of the per-frame latency: every step is
-// a kernel or a rocPRIM primitive on the context's stream (the host only sizes buffers):
-//   1. count / fill the (cell, point) incidences: a point belongs to every cell whose box is within
-//      r = 1.001 eps of it -- more on scenes wider than ~2 100 eps, see build_grid_gpu (double arithmetic, the same predicate for count and fill);
-//   2. one stable radix sort by cell key (brick << 9 | local cell) -- incidences are generated in ascending
-//      point order, so a cell's list comes out in ascending scene index (the tie rule of the scan kernels
-//      relies on it); dense scenes append a 16-bit quantised distance to the cell centre to the key;
-//   3. run boundaries -> non-empty cells -> bricks (prefix sums), padded list offsets (multiples of 8
-//      entries = whole 128-byte lines, sentinel-filled);
-//   4. cell words (offset, count, 64-bit sub-cell mask), the top-level brick table, the lists;
-//   5. dense scenes: per 8-entry chunk a lower bound of the distance to the cell centre (suffix minimum of
-//      the exact distances, so the quantised order only affects how early the scan stops, never the result).
+// A new scene arrives with every camera frame, so the build is part of the per-frame latency: every stage is
+// kernels and rocPRIM primitives on the context's stream (the host computes the geometry, grid_geometry.h, and sizes buffers).
+// build_grid_gpu runs them in this order (the stages of its Build), for the GridForm it is given:
+//   1. count: per point the cells whose box is within r of it -- r = 1.001 eps, more on scenes wider than ~2 100 eps, see
+//      grid_geometry.h (double arithmetic, the same predicate for count and fill) -- and the prefix sums of those counts;
+//   2. sort: the (cell key, point) incidences, one stable radix sort by cell key (brick << 9 | local cell) -- incidences are
+//      generated in ascending point order, so a cell's list comes out in ascending scene index (the tie rule of the scan kernels
+//      relies on it); centre-sorted lists append a 16-bit quantised distance to the cell centre to the key;
+//   3. cells: run boundaries -> non-empty cells -> bricks (prefix sums);
+//   4. layout: per cell its first incidence, key and brick; pruned lists: the entries that can win somewhere in the cell;
+//      padded list offsets (multiples of 8 entries = whole 128-byte lines, sentinel-filled);
+//   5. lists: cell words (offset, count, 64-bit sub-cell mask), the top-level brick table, the flat table, the lists;
+//   6. chunk_bounds (centre-sorted lists): per 8-entry chunk a lower bound of the distance to the cell centre (suffix minimum
+//      of the exact distances, so the quantised order only affects how early the scan stops, never the result).
 // HBM-bound integer/byte work; no MFMA.
 #include <math.h>
-#include <string.h>
-#include <cstring>
-
 
 #include <algorithm>
-#include <vector>
 
 #include "normal_cone.h"
 #include "octant_lists.h"
@@ -487,262 +485,263 @@ __global__ __launch_bounds__(256) void cell_nearest_store_kernel(const uint64_t*
     cells[(size_t)cell_brick[c] * 512 + (uint32_t)(cell_key[c] & 511)].z = __float_as_uint(nearest[c]);
 }
 
-struct Tmp {   // temporaries of one build: the context's workspace arena (no hipMalloc / hipFree in steady state)
-    Arena* ws;
-    template <class T>
-    int get(T** p, size_t n) { return ws->take(std::max<size_t>(n, 1) * sizeof(T), (void**)p); }
-};
-
+// ---------------------------------------------------------------------------------------------
+// The build, host side.  Which grid comes out is the GridForm (grid_form, ctx.hip) plus the four predicates here, which need a count
+// of the build; build_grid_gpu runs the stages of `Build` in order, with a read-back wherever the next one sizes its buffers by a count.
+// ---------------------------------------------------------------------------------------------
 static inline unsigned grid_of(size_t n) { return (unsigned)((n + 255) / 256); }
 
-// Builds c->grid for cell edge eps / div from c->d_spos (device) and c->h_spos (bounding box only).
-// dense != 0: lists ordered by distance to the cell centre + chunk bounds (scan kernels with early exit).
-int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
-    if (prune) dense = 0;      // pruned lists stay in index order (the `<=` tie rule of the index-ordered scan) and need no early exit
+// keys of at most 32 bits (every sparse scene: ~21 bits of cell) and a frame's worth of incidences: the library's own onesweep (sort32.hip,
+// one launch per 8-bit pass) where rocPRIM's 64-bit radix_sort_pairs runs ~17 small launches (150 us of a frame's stocs_ctx_set_scene in
+// round 5a); both stable
+static bool own_sort_pays(const GridForm& f, size_t n_inc, unsigned end_bit) { return sort_own_wanted(n_inc, f.own_sort) && end_bit <= 32 && n_inc < ((size_t)1 << 30); }
+// a handful of points per cell: 16 lanes per cell, four cells per wavefront; else a wavefront per cell
+static int prune_group(size_t n_inc, uint32_t n_cells) { return (double)n_inc <= 12.0 * (double)n_cells ? 16 : 64; }
+// the flat copy of the cell words (one look-up per query instead of two dependent ones) while the table stays within 512 MB
+static bool flat_fits(const GridForm& f, const GridBox& B) { return f.flat && (size_t)B.n[0] * B.n[1] * B.n[2] * sizeof(uint4) <= ((size_t)512 << 20); }
+// octant lines behind the long lists of a pruned grid with a flat table (octant_lists.h).  On by default although the step's drop at Cm
+// (2 to 2.9 %, the faster build in all 30 alternations) cleared three times the run-to-run range in one visit of three only: the line
+// select in the FLAT forms costs a grid WITHOUT lines 1.4 % against the parent (five alternations, slower in each), so off is the
+// slower default, not the neutral one.  At most n_inc / 9 cells are long: below 2^24 incidences their blocks stay far
+// below the 2^31 entries an offset can address
+static bool octants_fit(const GridForm& f, bool flat, size_t n_inc) { return f.octants && flat && n_inc < ((size_t)1 << 24); }
+
+typedef void (*PruneKernel)(GridGeom, double, double, const uint32_t*, const uint64_t*, uint32_t, uint32_t, const uint32_t*, const float4*, uint32_t*, uint32_t*, float*);
+static PruneKernel prune_kernel_for(int k, int group) {
+    if (group == 16) return k == 4 ? prune_kernel<4, 16> : k == 16 ? prune_kernel<16, 16> : prune_kernel<8, 16>;
+    return k == 4 ? prune_kernel<4, 64> : k == 16 ? prune_kernel<16, 64> : prune_kernel<8, 64>;
+}
+
+static GridGeom device_geom(const GridBox& B, bool centre_sorted) {
+    GridGeom G;
+    for (int k = 0; k < 3; ++k) { G.of[k] = B.of[k]; G.n[k] = B.n[k]; }   // the FLOAT origin of the scan kernels' floor((q - o_f) * inv_h), widened
+    G.h = B.h; G.r = B.r; G.nbx = B.nb[0]; G.nby = B.nb[1];
+    G.dense = centre_sorted ? 1 : 0; G.qscale = B.qscale;
+    return G;
+}
+
+static PinGrid* pin_grid(stocs_ctx* c) { return (PinGrid*)((char*)c->h_pin + PIN_GRID); }
+
+struct Build {   // one build in flight
+    stocs_ctx* c;
+    const GridForm& form;
+    SceneGrid& g;
+    GridStages& S;        // = g.stages
+    PinGrid* pin;         // the read-backs (a copy into a pageable stack word would take the runtime's staging path)
+    GridGeom G;
+    hipStream_t st;
+    bool flat, octants;   // decided once the incidences are counted
+
+    // temporaries: the context's workspace arena (no hipMalloc / hipFree in steady state)
+    template <class T> int tmp(T** p, size_t n) { return c->grid_ws.take(std::max<size_t>(n, 1) * sizeof(T), (void**)p); }
+    template <class K, class... A> void run(K kernel, size_t threads, A... a) { hipLaunchKernelGGL(kernel, dim3(grid_of(threads)), dim3(256), 0, st, a...); }
+    template <class T> int read_back(T* pinned, const T* dev, int n = 1) { STOCS_HIP_CHECK(hipMemcpyAsync(pinned, dev, n * sizeof(T), hipMemcpyDeviceToHost, st)); return STOCS_OK; }
+
+    // out[0 .. n] = the exclusive prefix sums of in[0 .. n): out[n] is the total.  The scan runs over n + 1 words, and in[n] -- read, but
+    // part of no output -- needs no value.  *t == NULL: the temporary is sized for this call and taken; later calls of at most this size reuse it
+    template <class In, class Out> int scan_total(char** t, size_t* bytes, const In* in, Out* out, size_t n) {
+        if (!*t) {
+            STOCS_HIP_CHECK(exclusive_scan(NULL, *bytes, in, out, n + 1, st));
+            if (int rc = tmp(t, *bytes)) return rc;
+        }
+        STOCS_HIP_CHECK(exclusive_scan(*t, *bytes, in, out, n + 1, st));
+        return STOCS_OK;
+    }
+
+    // Stable sort of the S.n_inc (key, point) pairs by the low end_bit bits into S.keys / S.vals.  own: the keys lie as 32-bit words in the
+    // first half of `keys` (the unsorted 64-bit array is not needed), are sorted into its second half and widened into S.keys for the
+    // kernels behind, and S.sort_err points at the sort's error word
+    int sort_pairs_take(bool own, uint64_t* keys, const uint32_t* vals, unsigned end_bit) {
+        const size_t n = S.n_inc;
+        size_t bytes = 0;
+        char* t;
+        int rc;
+        if (!own) {
+            STOCS_HIP_CHECK(sort_pairs(NULL, bytes, keys, S.keys, vals, S.vals, n, 0, end_bit, st));
+            if ((rc = tmp(&t, bytes))) return rc;
+            STOCS_HIP_CHECK(sort_pairs(t, bytes, keys, S.keys, vals, S.vals, n, 0, end_bit, st));
+            return STOCS_OK;
+        }
+        uint32_t *k32 = (uint32_t*)keys, *k32s = k32 + n;
+        STOCS_HIP_CHECK(sort_pairs_own(NULL, bytes, k32, k32s, vals, S.vals, n, 0, end_bit, NULL, 1, st));
+        if ((rc = tmp(&t, bytes))) return rc;
+        STOCS_HIP_CHECK(sort_pairs_own(t, bytes, k32, k32s, vals, S.vals, n, 0, end_bit, NULL, 1, st));
+        run(widen_keys_kernel, n, k32s, n, S.keys);
+        S.sort_err = (const uint32_t*)(t + sort_own_err_offset());
+        return STOCS_OK;
+    }
+
+    // 1. incidences: per scene point the number of cells within r of it and, by prefix sums, its first incidence; the total is read back
+    int count() {
+        const int nS = c->nS;
+        uint32_t* d_cnt;
+        char* t = NULL;
+        size_t bytes = 0;
+        int rc;
+        if ((rc = tmp(&d_cnt, (size_t)nS + 1)) || (rc = tmp(&S.off, (size_t)nS + 1))) return rc;
+        run(incidence_kernel<false>, nS, G, c->d_spos, nS, d_cnt, (const unsigned long long*)NULL, (uint64_t*)NULL, (uint32_t*)NULL, (uint32_t*)NULL);
+        if ((rc = scan_total(&t, &bytes, d_cnt, S.off, (size_t)nS))) return rc;
+        return read_back(&pin->n_inc, S.off + nS);
+    }
+
+    // 2. sort: the (key, point) records of every point, sorted stably by cell (and quantised centre distance)
+    int sort() {
+        const int nS = c->nS;
+        uint64_t* d_keys;
+        uint32_t* d_vals;
+        int rc;
+        if ((rc = tmp(&d_keys, S.n_inc)) || (rc = tmp(&S.keys, S.n_inc)) || (rc = tmp(&d_vals, S.n_inc)) || (rc = tmp(&S.vals, S.n_inc))) return rc;
+        const unsigned end_bit = (unsigned)std::min(64, S.box.cell_bits + form.qbits);
+        const bool own = own_sort_pays(form, S.n_inc, end_bit);
+        g.sort_kind = own ? STOCS_GRID_SORT_OWN : STOCS_GRID_SORT_ROCPRIM;
+        run(incidence_kernel<true>, nS, G, c->d_spos, nS, (uint32_t*)NULL, S.off, own ? (uint64_t*)NULL : d_keys, d_vals, own ? (uint32_t*)d_keys : (uint32_t*)NULL);
+        STOCS_HIP_CHECK(hipGetLastError());
+        return sort_pairs_take(own, d_keys, d_vals, end_bit);
+    }
+
+    // 3. cells and bricks: the incidences that open a cell / a brick, their ordinals by prefix sums; both totals and the sort's error
+    // word are read back
+    int cells() {
+        const size_t n = S.n_inc;
+        int rc;
+        if ((rc = tmp(&S.cflag, n + 1)) || (rc = tmp(&S.bflag, n + 1)) || (rc = tmp(&S.cidx, n + 1)) || (rc = tmp(&S.bidx, n + 1))) return rc;
+        run(cell_flags_kernel, n, S.keys, n, form.qbits, S.cflag, S.bflag);
+        if ((rc = scan_total(&S.scan_tmp, &S.scan_bytes, S.cflag, S.cidx, n)) || (rc = scan_total(&S.scan_tmp, &S.scan_bytes, S.bflag, S.bidx, n))) return rc;
+        if ((rc = read_back(&pin->n_cells, S.cidx + n)) || (rc = read_back(&pin->n_bricks, S.bidx + n))) return rc;
+        return S.sort_err ? read_back(&pin->sort_err, S.sort_err) : STOCS_OK;
+    }
+
+    // 4. list layout: per non-empty cell its first incidence, key and brick; pruned lists: every entry's place among its cell's survivors;
+    // then the padded list lengths (whole 128-byte lines; behind a long pruned list its octant block) and, by prefix sums, the list
+    // offsets.  The list entries, the longest list and the kept entries are read back
+    int layout() {
+        const uint32_t n_cells = S.n_cells, n_inc = (uint32_t)S.n_inc;
+        const size_t nc1 = (size_t)n_cells + 1;
+        int rc;
+        if ((rc = tmp(&S.cell_first, nc1)) || (rc = tmp(&S.cell_brick, nc1)) || (rc = tmp(&S.padded, nc1)) || (rc = tmp(&S.list_off, nc1)) || (rc = tmp(&S.cell_key, nc1)) ||
+            (rc = tmp(&S.counters, GridStages::COUNTER_WORDS)))
+            return rc;
+        run(cell_records_kernel, n_inc, S.keys, S.n_inc, form.qbits, S.cflag, S.cidx, S.bflag, S.bidx, S.cell_first, S.cell_key, S.cell_brick);
+        run(fill_i32_kernel, GridStages::COUNTER_WORDS, (int32_t*)S.counters, (size_t)GridStages::COUNTER_WORDS, 0);
+        if (form.layout == GRID_PRUNED) {
+            if ((rc = tmp(&S.rank, S.n_inc + 1)) || (rc = tmp(&S.kept, nc1)) || (rc = tmp(&S.nearest, nc1))) return rc;
+            g.prune_group = prune_group(S.n_inc, n_cells);
+            g.prune_k = form.prune_k;
+            run(prune_kernel_for(g.prune_k, g.prune_group), (size_t)n_cells * g.prune_group, G, S.box.hh, S.box.margin, S.cell_first, S.cell_key, n_cells, n_inc, S.vals,
+                c->d_spos, S.rank, S.kept, S.nearest);
+            run(cell_padded_kept_kernel, n_cells, S.kept, n_cells, 8u, S.padded, S.longest(), S.total(), octants ? STOCS_OCTANT_BLOCK : 0u, S.oct());
+        } else
+            run(cell_padded_kernel, n_cells, S.cell_first, n_cells, n_inc, 8u, S.padded, S.longest());
+        if ((rc = scan_total(&S.scan_tmp, &S.scan_bytes, S.padded, S.list_off, (size_t)n_cells))) return rc;
+        if ((rc = read_back(&pin->n_list, S.list_off + n_cells)) || (rc = read_back(&pin->longest, S.longest()))) return rc;
+        return form.layout == GRID_PRUNED ? read_back(&pin->n_kept, S.total()) : STOCS_OK;
+    }
+
+    // 5. cell words and lists: the grid itself, in c->grid_mem -- cell words (offset, count | cone, sub-cell mask) in their bricks and in
+    // the flat table, the top-level brick table, the sentinel-filled lists
+    int lists() {
+        const uint32_t n_cells = S.n_cells;
+        const size_t n_words = (size_t)S.n_bricks * 512, n_list = std::max<size_t>(S.n_list, 8), n_flat = (size_t)S.box.n[0] * S.box.n[1] * S.box.n[2];
+        int rc;
+        g.has_cones = form.cones;
+        if ((rc = c->grid_mem.take(std::max<size_t>(n_words, 1) * sizeof(uint4), (void**)&g.d_cells)) || (rc = c->grid_mem.take(n_list * sizeof(float4), (void**)&g.d_list))) return rc;
+        run(zero_cells_kernel, n_words, g.d_cells, n_words);
+        if (flat) {
+            if ((rc = c->grid_mem.take(n_flat * sizeof(uint4), (void**)&g.d_flat))) return rc;
+            run(zero_cells_kernel, n_flat, g.d_flat, n_flat);
+        }
+        run(fill_list_kernel, n_list, g.d_list, n_list);
+        run(cell_words_kernel, (size_t)n_cells * 64, G, form.div, S.cell_first, S.cell_key, S.cell_brick, S.list_off, n_cells, (uint32_t)S.n_inc, S.vals, c->d_spos, g.d_top,
+            g.d_cells, g.d_flat, S.kept, S.rank, c->d_snrmw, g.has_cones ? 1 : 0);
+        run(list_fill_kernel, S.n_inc, S.cflag, S.cidx, S.cell_first, S.list_off, S.vals, S.n_inc, c->d_spos, g.d_list, S.rank);
+        STOCS_HIP_CHECK(hipGetLastError());
+        if (octants) {
+            // The lines themselves are written later, by build_octant_lines, once the scene has been scored often enough for them to pay
+            // (lcp.hip; the threshold of the distance field): the build only reserved their blocks and counts the long cells.  What that
+            // call needs stays in g.stages until the next build resets the workspace
+            if ((rc = read_back(&pin->n_long_cells, S.oct()))) return rc;   // lands with the build's last synchronisation
+            g.oct_pending = true;
+        }
+        if (form.layout == GRID_PRUNED && form.div > 1) {   // no sub-cell masks on grids finer than epsilon: the z word takes the distance bound (has_nearest)
+            run(cell_nearest_store_kernel, n_cells, S.cell_key, S.cell_brick, n_cells, S.nearest, g.d_cells);
+            g.has_nearest = true;
+        }
+        return STOCS_OK;
+    }
+
+    // 6. dense chunk bounds (centre-sorted lists): per 8-entry chunk a lower bound of the distance to the cell centre; on grids finer
+    // than epsilon the z word of a cell takes the bound of its first chunk
+    int chunk_bounds() {
+        const size_t n_chunks = S.n_list / 8;
+        if (int rc = c->grid_mem.take(std::max<size_t>(n_chunks, 1) * sizeof(float), (void**)&g.d_chunk_r)) return rc;
+        run(fill_i32_kernel, n_chunks, (int32_t*)g.d_chunk_r, n_chunks, 0);
+        run(chunk_bounds_kernel, S.n_cells, G, S.cell_first, S.cell_key, S.list_off, S.n_cells, (uint32_t)S.n_inc, g.d_list, g.d_chunk_r);
+        g.has_nearest = form.div > 1;
+        if (g.has_nearest) run(cell_nearest_kernel, S.n_cells, S.cell_key, S.cell_brick, S.list_off, S.n_cells, g.d_chunk_r, g.d_cells);
+        STOCS_HIP_CHECK(hipGetLastError());
+        return STOCS_OK;
+    }
+};
+
+int build_grid_gpu(stocs_ctx* c, const GridForm& form) {
     SceneGrid& g = c->grid;
     const int nS = c->nS;
-    const double eps = (double)c->prm.distance_threshold;
-    if (div < 1 || div > 4) div = 1;
-    const double h = eps / div;
-    const double r0 = eps * 1.001;  // safety margin >> float rounding of the device cell computation -- on scenes of ordinary extent
+    hipStream_t st = c->stream;
+    int rc;
+    reset_grid(g);
     double mn[3] = {1e30, 1e30, 1e30}, mx[3] = {-1e30, -1e30, -1e30};
     for (int i = 0; i < nS; ++i) {
         const V3 p = c->h_spos[i];
         const double v[3] = {p.x, p.y, p.z};
         for (int k = 0; k < 3; ++k) { mn[k] = std::min(mn[k], v[k]); mx[k] = std::max(mx[k], v[k]); }
     }
-    if (nS == 0) { for (int k = 0; k < 3; ++k) { mn[k] = 0; mx[k] = 0; } }
-    for (int k = 0; k < 3; ++k) { g.bb_mn[k] = mn[k]; g.bb_mx[k] = mx[k]; }
-    g.d_dist = NULL; g.dist_ready = false;
-    // The scan kernels compute floor((q - o_f) * inv_h) in float: the subtraction, the float inv_h and the product each contribute up to
-    // 2^-24 of the offset from the origin, so the face they see can lie 3 * 2^-24 * span from the box face used here (measured: up to
-    // 1.5e-3 eps at an extent of 31 000 eps, 1.1e-2 eps at 262 000).  The margin grows with the extent once 2^-21 of it exceeds the
-    // thousandth of epsilon -- from about 2 100 epsilons on; below that r is what it always was
-    double ext = 0;
-    for (int k = 0; k < 3; ++k) ext = std::max(ext, mx[k] - mn[k]);
-    const double span = ext + 2.0 * (r0 + 2 * h) + h;   // the largest offset from the origin inside the grid
-    const double r = std::max(r0, eps + span * (1.0 / 2097152.0));
-    const double pad = r + 2 * h;  // a query outside the grid is farther than epsilon from every point
-    const double o[3] = {mn[0] - pad, mn[1] - pad, mn[2] - pad};
-    int n[3];
-    for (int k = 0; k < 3; ++k) n[k] = (int)floor((mx[k] + pad - o[k]) / h) + 1;
-    g.ox = (float)o[0]; g.oy = (float)o[1]; g.oz = (float)o[2];
-    g.inv_h = (float)(1.0 / h);
-    g.nx = n[0]; g.ny = n[1]; g.nz = n[2];
-    g.nbx = (n[0] + 7) / 8; g.nby = (n[1] + 7) / 8; g.nbz = (n[2] + 7) / 8;
-    g.h = (float)h;
-    g.n_bricks = 0; g.n_entries = 0; g.avg_list_len = 0; g.has_nearest = false; g.has_cones = false;
-    g.div = div; g.sort_kind = 0; g.prune_group = 0; g.prune_k = 0; g.n_inc = 0; g.n_cells = 0; g.longest_list = 0;
-    g.n_long_cells = 0; g.n_octant_cells = 0; g.n_octant_entries = 0; g.oct_pending = false;
-    g.d_top = NULL; g.d_cells = NULL; g.d_list = NULL; g.d_chunk_r = NULL; g.d_flat = NULL;
-    const int64_t n_top = (int64_t)g.nbx * g.nby * g.nbz;
-    if (n_top > (int64_t)400 * 1000 * 1000) { set_error("scene extent too large for the brick grid"); return STOCS_ERR_INVALID; }
-    int cell_bits = 1;
-    while (((int64_t)1 << cell_bits) < n_top * 512) cell_bits++;
+    for (int k = 0; k < 3; ++k) { g.bb_mn[k] = nS ? mn[k] : 0.0; g.bb_mx[k] = nS ? mx[k] : 0.0; }
+    GridStages& S = g.stages;
+    const GridBox& B = S.box = grid_geometry(g.bb_mn, g.bb_mx, (double)c->prm.distance_threshold, form.div);
+    g.ox = B.of[0]; g.oy = B.of[1]; g.oz = B.of[2];
+    g.h = B.hf; g.inv_h = B.inv_h; g.div = form.div;
+    g.nx = B.n[0]; g.ny = B.n[1]; g.nz = B.n[2];
+    g.nbx = B.nb[0]; g.nby = B.nb[1]; g.nbz = B.nb[2];
+    if (B.n_top > (int64_t)STOCS_GRID_MAX_BRICKS) { set_error("scene extent too large for the brick grid"); return STOCS_ERR_INVALID; }
 
-    GridGeom G;
-    // the scan kernels compute the cell as floor((q - o_f) * inv_h) with the FLOAT origin: use exactly that origin
-    G.of[0] = g.ox; G.of[1] = g.oy; G.of[2] = g.oz;
-    G.h = h; G.r = r;
-    G.n[0] = n[0]; G.n[1] = n[1]; G.n[2] = n[2];
-    G.nbx = g.nbx; G.nby = g.nby;
-    G.dense = dense ? 1 : 0;
-    G.qscale = 65535.0 / (r + h * 0.8660254037844387 + 1e-9);   // a listed point is at most r + half a cell diagonal from the centre
-    const int qbits = dense ? 16 : 0;
-
-    hipStream_t st = c->stream;
-    Tmp T;
-    T.ws = &c->grid_ws;
-    int rc;
     STOCS_HIP_CHECK(hipStreamSynchronize(st));   // the previous grid and the previous build's temporaries are recycled
-    if ((rc = c->grid_ws.reset()) || (rc = c->grid_mem.reset())) return rc;
-    if ((rc = c->grid_mem.take((size_t)std::max<int64_t>(n_top, 1) * 4, (void**)&g.d_top))) return rc;
-    hipLaunchKernelGGL(fill_i32_kernel, dim3(grid_of((size_t)n_top)), dim3(256), 0, st, g.d_top, (size_t)n_top, -1);
+    if ((rc = c->grid_ws.reset()) || (rc = c->grid_mem.reset()) || (rc = ensure_pinned(c, PIN_VAR))) return rc;
+    Build b = {c, form, g, S, pin_grid(c), device_geom(B, form.layout == GRID_CENTRE_SORTED), st, false, false};
+    PinGrid& pin = *b.pin = PinGrid();
+    if ((rc = c->grid_mem.take((size_t)std::max<int64_t>(B.n_top, 1) * 4, (void**)&g.d_top))) return rc;
+    b.run(fill_i32_kernel, (size_t)B.n_top, g.d_top, (size_t)B.n_top, -1);
     if (nS == 0) {
         if ((rc = c->grid_mem.take(16, (void**)&g.d_cells)) || (rc = c->grid_mem.take(8 * 16, (void**)&g.d_list))) return rc;
         STOCS_HIP_CHECK(hipStreamSynchronize(st));
         return STOCS_OK;
     }
-    // ---- 1. incidences ----
-    uint32_t* d_cnt; unsigned long long* d_off;
-    if ((rc = T.get(&d_cnt, (size_t)nS + 1)) || (rc = T.get(&d_off, (size_t)nS + 1))) return rc;
-    hipLaunchKernelGGL(incidence_kernel<false>, dim3(grid_of(nS)), dim3(256), 0, st, G, c->d_spos, nS, d_cnt, (const unsigned long long*)NULL,
-                       (uint64_t*)NULL, (uint32_t*)NULL);
-    hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(256), 0, st, (int32_t*)(d_cnt + nS), (size_t)1, 0);
-    size_t tb = 0;
-    STOCS_HIP_CHECK(exclusive_scan(NULL, tb, d_cnt, d_off, (size_t)nS + 1, st));
-    char* d_tmp;
-    if ((rc = T.get(&d_tmp, tb))) return rc;
-    STOCS_HIP_CHECK(exclusive_scan(d_tmp, tb, d_cnt, d_off, (size_t)nS + 1, st));
-    // the build's small read-backs land in a pinned slot of the context (a copy into a pageable stack word takes the runtime's staging path)
-    if ((rc = ensure_pinned(c, PIN_VAR))) return rc;
-    unsigned long long* rb64 = (unsigned long long*)((char*)c->h_pin + PIN_BEST + 128);   // [0] incidences, [1] kept entries
-    uint32_t* rb32 = (uint32_t*)((char*)c->h_pin + PIN_BEST + 160);                     // [0..1] cells, bricks, [2] sort error, [3..4] list entries, longest list
-    rb64[0] = 0; rb64[1] = 0; for (int k = 0; k < 5; ++k) rb32[k] = 0;
-    STOCS_HIP_CHECK(hipMemcpyAsync(&rb64[0], d_off + nS, 8, hipMemcpyDeviceToHost, st));
+    if ((rc = b.count())) return rc;
     STOCS_HIP_CHECK(hipStreamSynchronize(st));
-    const unsigned long long n_inc64 = rb64[0];
     // padded lists stay below 2^31 entries (32-bit offsets in the cell words)
-    if (n_inc64 >= (1ull << 28)) { set_error("scene grid lists too large (%llu incidences)", n_inc64); return STOCS_ERR_INVALID; }
-    const size_t n_inc = (size_t)n_inc64;
-    g.n_inc = (int64_t)n_inc64;
-    uint64_t *d_keys, *d_keys_s; uint32_t *d_vals, *d_vals_s;
-    if ((rc = T.get(&d_keys, n_inc)) || (rc = T.get(&d_keys_s, n_inc)) || (rc = T.get(&d_vals, n_inc)) || (rc = T.get(&d_vals_s, n_inc))) return rc;
-    // ---- 2. stable sort by cell (and quantised centre distance) ----
-    size_t ts = 0;
-    const unsigned end_bit = (unsigned)std::min(64, cell_bits + qbits);
-    // keys of at most 32 bits (every sparse scene: ~21 bits of cell) and a frame's worth of incidences: the library's own onesweep (sort32.hip,
-    // one launch per 8-bit pass) where rocPRIM's 64-bit radix_sort_pairs runs ~17 small launches (150 us of a frame's stocs_ctx_set_scene in
-    // round 5a); both stable, the sorted keys are widened back for the kernels behind
-    const bool own_sort = end_bit <= 32 && n_inc >= 65536 && n_inc < ((size_t)1 << 30) && !(getenv("STOCS_SORT") && !strcmp(getenv("STOCS_SORT"), "rocprim"));
-    g.sort_kind = own_sort ? STOCS_GRID_SORT_OWN : STOCS_GRID_SORT_ROCPRIM;
-    char* d_ts;
-    const uint32_t* d_sort_err = NULL;
-    if (own_sort) {
-        uint32_t* k32 = (uint32_t*)d_keys;                         // (the unsorted 64-bit array is not needed: its first half holds the 32-bit keys)
-        uint32_t* k32s = k32 + n_inc;
-        hipLaunchKernelGGL(incidence_kernel<true>, dim3(grid_of(nS)), dim3(256), 0, st, G, c->d_spos, nS, (uint32_t*)NULL, d_off, (uint64_t*)NULL, d_vals, k32);
-        STOCS_HIP_CHECK(hipGetLastError());
-        STOCS_HIP_CHECK(sort_pairs_own(NULL, ts, k32, k32s, d_vals, d_vals_s, n_inc, 0, end_bit, NULL, 1, st));
-        if ((rc = T.get(&d_ts, ts))) return rc;
-        STOCS_HIP_CHECK(sort_pairs_own(d_ts, ts, k32, k32s, d_vals, d_vals_s, n_inc, 0, end_bit, NULL, 1, st));
-        hipLaunchKernelGGL(widen_keys_kernel, dim3(grid_of(n_inc)), dim3(256), 0, st, (const uint32_t*)k32s, n_inc, d_keys_s);
-        d_sort_err = (const uint32_t*)(d_ts + sort_own_err_offset());
-    } else {
-    hipLaunchKernelGGL(incidence_kernel<true>, dim3(grid_of(nS)), dim3(256), 0, st, G, c->d_spos, nS, (uint32_t*)NULL, d_off, d_keys, d_vals);
-    STOCS_HIP_CHECK(hipGetLastError());
-    STOCS_HIP_CHECK(sort_pairs(NULL, ts, d_keys, d_keys_s, d_vals, d_vals_s, n_inc, 0, end_bit, st));
-    if ((rc = T.get(&d_ts, ts))) return rc;
-    STOCS_HIP_CHECK(sort_pairs(d_ts, ts, d_keys, d_keys_s, d_vals, d_vals_s, n_inc, 0, end_bit, st));
-    }
-    // ---- 3. cells and bricks ----
-    uint32_t *d_cflag, *d_bflag, *d_cidx, *d_bidx;
-    if ((rc = T.get(&d_cflag, n_inc + 1)) || (rc = T.get(&d_bflag, n_inc + 1)) || (rc = T.get(&d_cidx, n_inc + 1)) || (rc = T.get(&d_bidx, n_inc + 1))) return rc;
-    hipLaunchKernelGGL(cell_flags_kernel, dim3(grid_of(n_inc)), dim3(256), 0, st, d_keys_s, n_inc, qbits, d_cflag, d_bflag);
-    hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(256), 0, st, (int32_t*)(d_cflag + n_inc), (size_t)1, 0);
-    hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(256), 0, st, (int32_t*)(d_bflag + n_inc), (size_t)1, 0);
-    size_t t32 = 0;
-    STOCS_HIP_CHECK(exclusive_scan(NULL, t32, d_cflag, d_cidx, (size_t)n_inc + 1, st));
-    char* d_t32;
-    if ((rc = T.get(&d_t32, t32))) return rc;
-    STOCS_HIP_CHECK(exclusive_scan(d_t32, t32, d_cflag, d_cidx, (size_t)n_inc + 1, st));
-    STOCS_HIP_CHECK(exclusive_scan(d_t32, t32, d_bflag, d_bidx, (size_t)n_inc + 1, st));
-    uint32_t* counts = rb32;
-    STOCS_HIP_CHECK(hipMemcpyAsync(&counts[0], d_cidx + n_inc, 4, hipMemcpyDeviceToHost, st));
-    STOCS_HIP_CHECK(hipMemcpyAsync(&counts[1], d_bidx + n_inc, 4, hipMemcpyDeviceToHost, st));
-    if (d_sort_err) STOCS_HIP_CHECK(hipMemcpyAsync(&rb32[2], d_sort_err, 4, hipMemcpyDeviceToHost, st));
+    if (pin.n_inc >= (1ull << 28)) { set_error("scene grid lists too large (%llu incidences)", pin.n_inc); return STOCS_ERR_INVALID; }
+    S.n_inc = (size_t)pin.n_inc;
+    g.n_inc = (int64_t)pin.n_inc;
+    b.flat = flat_fits(form, B);
+    b.octants = octants_fit(form, b.flat, S.n_inc);
+    if ((rc = b.sort()) || (rc = b.cells())) return rc;
     STOCS_HIP_CHECK(hipStreamSynchronize(st));
-    const uint32_t sort_err = rb32[2];
-    if (sort_err) { set_error("scene grid: the incidence sort gave up waiting for a tile (sort32.hip)"); return STOCS_ERR_HIP; }
-    const uint32_t n_cells = counts[0], n_bricks = counts[1];
-    g.n_cells = (int64_t)n_cells;
-    uint32_t *d_cell_first, *d_cell_brick, *d_padded, *d_list_off, *d_max;
-    uint64_t* d_cell_key;
-    if ((rc = T.get(&d_cell_first, (size_t)n_cells + 1)) || (rc = T.get(&d_cell_brick, (size_t)n_cells + 1)) || (rc = T.get(&d_padded, (size_t)n_cells + 1)) ||
-        (rc = T.get(&d_list_off, (size_t)n_cells + 1)) || (rc = T.get(&d_cell_key, (size_t)n_cells + 1)) || (rc = T.get(&d_max, 1)))
-        return rc;
-    hipLaunchKernelGGL(cell_records_kernel, dim3(grid_of(n_inc)), dim3(256), 0, st, d_keys_s, n_inc, qbits, d_cflag, d_cidx, d_bflag, d_bidx, d_cell_first,
-                       d_cell_key, d_cell_brick);
-    hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(256), 0, st, (int32_t*)d_max, (size_t)1, 0);
-    uint32_t *d_rank = NULL, *d_kept = NULL; float* d_near = NULL; unsigned long long* d_total = NULL;
-    // the flat copy of the cell words (sparse scenes, cell edge epsilon): decided here, built in step 4
-    const size_t n_flat = (size_t)n[0] * n[1] * n[2];
-    const bool want_flat = !dense && div == 1 && c->lcp_flat && n_flat * sizeof(uint4) <= ((size_t)512 << 20);
-    // octant lines behind the long lists of such a grid (octant_lists.h); STOCS_GRID_OCTANTS=0, read per build: a grid without them (A/B
-    // runs, cross-checks).  On by default although the step's drop at Cm (2 to 2.9 %, the faster build in all 30 alternations) cleared
-    // three times the run-to-run range in one visit of three only: the line select in the FLAT forms costs a grid WITHOUT lines 1.4 % against
-    // the parent (five alternations, slower in each), so off is the slower default, not the neutral one.
-    // At most n_inc / 9 cells are long: below 2^24 incidences their blocks stay far below the 2^31 entries an offset can address
-    const bool octants = prune && want_flat && n_inc < ((size_t)1 << 24) && !(getenv("STOCS_GRID_OCTANTS") && atoi(getenv("STOCS_GRID_OCTANTS")) == 0);
-    uint32_t* d_oct = NULL;   // [0] long cells, [1] cells with octant lines, [2] entries of those lines
-    double oct_hw = 0, oct_margin = 0;
-    if (prune) {
-        if ((rc = T.get(&d_rank, n_inc + 1)) || (rc = T.get(&d_kept, (size_t)n_cells + 1)) || (rc = T.get(&d_near, (size_t)n_cells + 1)) || (rc = T.get(&d_total, 1))) return rc;
-        // positions the kernels assign to a cell lie inside its box up to the float rounding of floor((q - o) * inv_h): 3 ulp of the
-        // offset from the origin; squared distances are evaluated in float with a relative error below 4e-7 each
-        double ext = 0; for (int k = 0; k < 3; ++k) ext = std::max(ext, (double)n[k] * h);
-        const double hh = 0.5 * h + 2.0e-6 * (ext + 1.0) * 0.5 + 1.0e-7, reach = r + 2.0 * h;
-        const double margin = 4.0e-6 * reach * reach;
-        hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(256), 0, st, (int32_t*)d_total, (size_t)2, 0);
-        const int pk = getenv("STOCS_GRID_PRUNE_K") ? atoi(getenv("STOCS_GRID_PRUNE_K")) : 8;   // dominators tried per entry (measurement switch: 4, 8, 16)
-#define STOCS_PRUNE_LAUNCH(KV) do { if (short_lists) hipLaunchKernelGGL((prune_kernel<KV, 16>), dim3((unsigned)((n_cells + 15) / 16)), dim3(256), 0, st, G, hh, margin, d_cell_first, d_cell_key, n_cells, (uint32_t)n_inc, d_vals_s, c->d_spos, d_rank, d_kept, d_near); \
-                                    else hipLaunchKernelGGL((prune_kernel<KV, 64>), dim3((unsigned)((n_cells + 3) / 4)), dim3(256), 0, st, G, hh, margin, d_cell_first, d_cell_key, n_cells, (uint32_t)n_inc, d_vals_s, c->d_spos, d_rank, d_kept, d_near); } while (0)
-        const bool short_lists = (double)n_inc <= 12.0 * (double)n_cells;     // a handful of points per cell: 16 lanes per cell, four cells per wavefront
-        if (pk == 4) STOCS_PRUNE_LAUNCH(4); else if (pk == 16) STOCS_PRUNE_LAUNCH(16); else STOCS_PRUNE_LAUNCH(8);
-#undef STOCS_PRUNE_LAUNCH
-        g.prune_group = short_lists ? 16 : 64;
-        g.prune_k = (pk == 4 || pk == 16) ? pk : 8;
-        if ((rc = T.get(&d_oct, 4))) return rc;
-        hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(256), 0, st, (int32_t*)d_oct, (size_t)4, 0);
-        oct_hw = 0.25 * h + (hh - 0.5 * h); oct_margin = margin;   // the octant box, widened by the slack of the cell box
-        hipLaunchKernelGGL(cell_padded_kept_kernel, dim3(grid_of(n_cells)), dim3(256), 0, st, d_kept, n_cells, 8u, d_padded, d_max, d_total,
-                           octants ? STOCS_OCTANT_BLOCK : 0u, d_oct);
-    } else
-    hipLaunchKernelGGL(cell_padded_kernel, dim3(grid_of(n_cells)), dim3(256), 0, st, d_cell_first, n_cells, (uint32_t)n_inc, 8u, d_padded, d_max);
-    hipLaunchKernelGGL(fill_i32_kernel, dim3(1), dim3(256), 0, st, (int32_t*)(d_padded + n_cells), (size_t)1, 0);
-    STOCS_HIP_CHECK(exclusive_scan(d_t32, t32, d_padded, d_list_off, (size_t)n_cells + 1, st));
-    uint32_t* tail = rb32 + 3;
-    STOCS_HIP_CHECK(hipMemcpyAsync(&tail[0], d_list_off + n_cells, 4, hipMemcpyDeviceToHost, st));
-    STOCS_HIP_CHECK(hipMemcpyAsync(&tail[1], d_max, 4, hipMemcpyDeviceToHost, st));
-    if (prune) STOCS_HIP_CHECK(hipMemcpyAsync(&rb64[1], d_total, 8, hipMemcpyDeviceToHost, st));
+    if (pin.sort_err) { set_error("scene grid: the incidence sort gave up waiting for a tile (sort32.hip)"); return STOCS_ERR_HIP; }
+    S.n_cells = pin.n_cells; S.n_bricks = pin.n_bricks;
+    g.n_cells = (int64_t)S.n_cells;
+    if ((rc = b.layout())) return rc;
     STOCS_HIP_CHECK(hipStreamSynchronize(st));
-    const unsigned long long n_kept = prune ? rb64[1] : (unsigned long long)n_inc;
-    const size_t n_list = tail[0];
-    g.longest_list = (int)tail[1];
-    if (tail[1] > 65535u) { set_error("more than 65535 scene points within epsilon of one grid cell"); return STOCS_ERR_INVALID; }
-    // normal cones above the 16-bit counts (normal_cone.h); STOCS_GRID_CONES=0: a grid without them (A/B runs, cross-checks)
-    g.has_cones = !(getenv("STOCS_GRID_CONES") && atoi(getenv("STOCS_GRID_CONES")) == 0);
-    // ---- 4. cell words, top table, lists ----
-    if ((rc = c->grid_mem.take(std::max<size_t>((size_t)n_bricks * 512, 1) * sizeof(uint4), (void**)&g.d_cells)) ||
-        (rc = c->grid_mem.take(std::max<size_t>(n_list, 8) * sizeof(float4), (void**)&g.d_list)))
-        return rc;
-    hipLaunchKernelGGL(zero_cells_kernel, dim3(grid_of((size_t)n_bricks * 512)), dim3(256), 0, st, g.d_cells, (size_t)n_bricks * 512);
-    {   // flat copy of the cell words for the sparse-scene kernel: one look-up per query instead of two dependent ones
-        if (want_flat) {
-            if ((rc = c->grid_mem.take(n_flat * sizeof(uint4), (void**)&g.d_flat))) return rc;
-            hipLaunchKernelGGL(zero_cells_kernel, dim3(grid_of(n_flat)), dim3(256), 0, st, g.d_flat, n_flat);
-        }
-    }
-    hipLaunchKernelGGL(fill_list_kernel, dim3(grid_of(std::max<size_t>(n_list, 8))), dim3(256), 0, st, g.d_list, std::max<size_t>(n_list, 8));
-    hipLaunchKernelGGL(cell_words_kernel, dim3((unsigned)((n_cells + 3) / 4)), dim3(256), 0, st, G, div, d_cell_first, d_cell_key, d_cell_brick, d_list_off, n_cells,
-                       (uint32_t)n_inc, d_vals_s, c->d_spos, g.d_top, g.d_cells, g.d_flat, (const uint32_t*)d_kept,
-                       (const uint32_t*)d_rank, (const float4*)c->d_snrmw, g.has_cones ? 1 : 0);
-    hipLaunchKernelGGL(list_fill_kernel, dim3(grid_of(n_inc)), dim3(256), 0, st, d_cflag, d_cidx, d_cell_first, d_list_off, d_vals_s, n_inc, c->d_spos, g.d_list, (const uint32_t*)d_rank);
-    STOCS_HIP_CHECK(hipGetLastError());
-    uint32_t* oct_counts = rb32 + 5;   // [5..7] long cells, cells with octant lines, their entries
-    for (int k = 0; k < 3; ++k) oct_counts[k] = 0;
-    if (octants) {
-        // The lines themselves are written later, by build_octant_lines, once the scene has been scored often enough for them to pay
-        // (lcp.hip; the threshold of the distance field): the build only reserved their blocks and counts the long cells.  What that
-        // call needs stays where it is until the next build resets the workspace
-        STOCS_HIP_CHECK(hipMemcpyAsync(oct_counts, d_oct, 4, hipMemcpyDeviceToHost, st));   // lands with the build's last synchronisation
-        g.oct_pending = true;
-        g.oct_cell_key = d_cell_key; g.oct_list_off = d_list_off; g.oct_kept = d_kept; g.oct_counts = d_oct; g.oct_n_cells = n_cells;
-        g.oct_h = h; g.oct_r = r; g.oct_hw = oct_hw; g.oct_margin = oct_margin;
-    }
-    if (prune && div > 1) {   // no sub-cell masks on grids finer than epsilon: the z word takes the distance bound (has_nearest)
-        hipLaunchKernelGGL(cell_nearest_store_kernel, dim3(grid_of(n_cells)), dim3(256), 0, st, d_cell_key, d_cell_brick, n_cells, (const float*)d_near, g.d_cells);
-        g.has_nearest = true;
-    }
-    // ---- 5. dense scenes: chunk bounds ----
-    if (dense) {
-        if ((rc = c->grid_mem.take(std::max<size_t>(n_list / 8, 1) * sizeof(float), (void**)&g.d_chunk_r))) return rc;
-        hipLaunchKernelGGL(fill_i32_kernel, dim3(grid_of(n_list / 8)), dim3(256), 0, st, (int32_t*)g.d_chunk_r, n_list / 8, 0);
-        hipLaunchKernelGGL(chunk_bounds_kernel, dim3(grid_of(n_cells)), dim3(256), 0, st, G, d_cell_first, d_cell_key, d_list_off, n_cells, (uint32_t)n_inc,
-                           g.d_list, g.d_chunk_r);
-        g.has_nearest = div > 1;
-        if (g.has_nearest)
-            hipLaunchKernelGGL(cell_nearest_kernel, dim3(grid_of(n_cells)), dim3(256), 0, st, d_cell_key, d_cell_brick, d_list_off, n_cells, g.d_chunk_r, g.d_cells);
-        STOCS_HIP_CHECK(hipGetLastError());
-    }
+    S.n_list = pin.n_list;
+    g.longest_list = (int)pin.longest;
+    if (pin.longest > 65535u) { set_error("more than 65535 scene points within epsilon of one grid cell"); return STOCS_ERR_INVALID; }
+    if ((rc = b.lists()) || (form.layout == GRID_CENTRE_SORTED && (rc = b.chunk_bounds()))) return rc;
     STOCS_HIP_CHECK(hipStreamSynchronize(st));
-    g.n_bricks = (int)n_bricks;
+    g.n_bricks = (int)S.n_bricks;
     // the plain lists only: the octant blocks are not part of what the launch layer weighs (lcp.hip: lists_spill, lists_huge)
-    g.n_long_cells = (int64_t)oct_counts[0]; g.n_octant_cells = (int64_t)oct_counts[1]; g.n_octant_entries = (int64_t)oct_counts[2];
-    g.n_entries = (int64_t)n_list - (int64_t)STOCS_OCTANT_BLOCK * g.n_long_cells;
-    g.avg_list_len = n_cells ? (double)n_kept / (double)n_cells : 0.0;
-    g.avg_dilated_len = n_cells ? (double)n_inc / (double)n_cells : 0.0;
-    g.pruned = prune != 0;
+    g.n_long_cells = (int64_t)pin.n_long_cells;
+    g.n_entries = (int64_t)S.n_list - (int64_t)STOCS_OCTANT_BLOCK * g.n_long_cells;
+    g.pruned = form.layout == GRID_PRUNED;
+    g.avg_list_len = S.n_cells ? (double)(g.pruned ? pin.n_kept : pin.n_inc) / (double)S.n_cells : 0.0;
+    g.avg_dilated_len = S.n_cells ? (double)S.n_inc / (double)S.n_cells : 0.0;
     return STOCS_OK;
 }
 
@@ -752,26 +751,20 @@ int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune) {
 // one synchronisation for the two counts of stocs_get_grid_octants.
 int build_octant_lines(stocs_ctx* c) {
     SceneGrid& g = c->grid;
+    const GridStages& S = g.stages;
     if (!g.oct_pending) return STOCS_OK;
     g.oct_pending = false;
     if (!g.d_flat || !g.d_list || g.n_long_cells == 0) return STOCS_OK;
-    GridGeom G;
-    G.of[0] = g.ox; G.of[1] = g.oy; G.of[2] = g.oz;
-    G.h = g.oct_h; G.r = g.oct_r;
-    G.n[0] = g.nx; G.n[1] = g.ny; G.n[2] = g.nz;
-    G.nbx = g.nbx; G.nby = g.nby;
-    G.dense = 0; G.qscale = 0.0;
-    int rc;
-    if ((rc = ensure_pinned(c, PIN_VAR))) return rc;
-    uint32_t* counts = (uint32_t*)((char*)c->h_pin + PIN_BEST + 160) + 5;   // (the build's slots)
-    counts[1] = 0; counts[2] = 0;
+    if (int rc = ensure_pinned(c, PIN_VAR)) return rc;
+    PinGrid* pin = pin_grid(c);
+    pin->n_octant_cells = 0; pin->n_octant_entries = 0;
     // eight lanes per cell; cells with one line of entries leave at once
-    hipLaunchKernelGGL(octant_lines_kernel, dim3(grid_of((size_t)g.oct_n_cells * 8)), dim3(256), 0, c->stream, G, g.oct_hw, g.oct_margin, g.oct_cell_key,
-                       g.oct_list_off, g.oct_kept, g.oct_n_cells, g.d_list, g.d_flat, g.oct_counts);
+    hipLaunchKernelGGL(octant_lines_kernel, dim3(grid_of((size_t)S.n_cells * 8)), dim3(256), 0, c->stream, device_geom(S.box, false), S.box.oct_hw, S.box.margin, S.cell_key,
+                       S.list_off, S.kept, S.n_cells, g.d_list, g.d_flat, S.oct());
     STOCS_HIP_CHECK(hipGetLastError());
-    STOCS_HIP_CHECK(hipMemcpyAsync(counts + 1, g.oct_counts + 1, 8, hipMemcpyDeviceToHost, c->stream));
+    STOCS_HIP_CHECK(hipMemcpyAsync(&pin->n_octant_cells, S.oct() + 1, 8, hipMemcpyDeviceToHost, c->stream));   // (and n_octant_entries behind it)
     STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-    g.n_octant_cells = (int64_t)counts[1]; g.n_octant_entries = (int64_t)counts[2];
+    g.n_octant_cells = (int64_t)pin->n_octant_cells; g.n_octant_entries = (int64_t)pin->n_octant_entries;
     return STOCS_OK;
 }
 

@@ -555,7 +555,7 @@ static int voxel_grid_device(const float4* dP, const float4* dExtra, int n, doub
         hipLaunchKernelGGL(leaf_keys_kernel<uint32_t>, g, dim3(256), 0, st, ijk.p, n, mn, dims, k32, ids.p);
         // a frame's 300 000 leaf keys: the library's own onesweep (sort32.hip, one launch per 8-bit pass) where rocPRIM's radix_sort_pairs runs
         // ~20 small launches (190 us of a frame's ingest in round 5a); small clouds stay with rocPRIM (a block / merge sort there).  Both stable.
-        own_sort = n >= 65536 && !(getenv("STOCS_SORT") && !strcmp(getenv("STOCS_SORT"), "rocprim"));
+        own_sort = sort_own_wanted((size_t)n);
         Buf<char> tmp_scan;
         if (own_sort) {
             STOCS_HIP_CHECK(sort_pairs_own(NULL, tb, k32, k32s, ids.p, ids_s.p, (size_t)n, 0, (unsigned)key_bits, NULL, 1, st));

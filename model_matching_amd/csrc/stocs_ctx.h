@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "../../include/stocs_hip.h"
+#include "grid_geometry.h"
 #include "kdtree.h"
 #include "stocs_math.h"
 #include "stream_audit.h"
@@ -152,6 +153,43 @@ struct Arena {
     void destroy() { for (size_t i = 0; i < slabs.size(); ++i) (void)hipFree(slabs[i].p); slabs.clear(); }
 };
 
+// Which grid a build makes (grid.hip).  grid_form (ctx.hip) fills it from the context and the environment switches, once per build; the
+// parts that depend on counts known only mid-build are the predicates next to build_grid_gpu, which take the form and the count.
+enum GridLayout { GRID_PRUNED, GRID_INDEX_ORDERED, GRID_CENTRE_SORTED };
+struct GridForm {
+    int div;             // cell edge = epsilon / div, 1 .. 4
+    GridLayout layout;   // dominance-pruned lists in index order | every point within r, in index order | ... ordered by distance to the
+                         // cell centre, with chunk bounds for the early exit
+    int qbits;           // bits of quantised centre distance below the cell in the sort key: 16 centre-sorted, else 0
+    int prune_k;         // dominators tried per entry (4, 8, 16); 0 when the lists are not pruned
+    bool cones;          // normal cones in the count words (normal_cone.h)
+    bool flat;           // asked for: the flat cell table (cell edge epsilon, index order; built if it fits)
+    bool octants;        // asked for: octant lines behind long pruned lists (needs the flat table)
+    bool own_sort;       // asked for: the library's own sort (sort32.hip) where the incidences are many and the key is short
+};
+
+// What one build hands from stage to stage (grid.hip): the geometry, the counts as they become known, and the device arrays in the
+// build's workspace (c->grid_ws), where they stay until the next build.
+struct GridStages {
+    GridBox box;
+    size_t n_inc, n_list;           // (cell, point) incidences; padded list entries
+    uint32_t n_cells, n_bricks;     // non-empty cells, bricks
+    unsigned long long* off;        // per scene point: its first incidence
+    uint64_t* keys; uint32_t* vals; // the incidences sorted by key: key, scene point
+    const uint32_t* sort_err;       // the own sort's error word, NULL after rocPRIM's
+    uint32_t *cflag, *cidx, *bflag, *bidx;   // per incidence: opens a cell / a brick, and the exclusive scans of those flags
+    char* scan_tmp; size_t scan_bytes;       // temporary of the 32-bit scans over up to n_inc + 1 words
+    uint32_t *cell_first, *cell_brick, *padded, *list_off; uint64_t* cell_key;   // per non-empty cell
+    uint32_t *rank, *kept; float* nearest;   // pruned lists: per incidence its place in the stored list (~0: dropped); per cell
+    // one zeroed block; its three parts lie 256 bytes apart, as separate workspace takes would, so that the kernels' atomics on them
+    // stay apart: [0] longest list; [64..65] kept entries (64 bits); [128..130] long cells, cells with octant lines, entries of those lines
+    uint32_t* counters;
+    enum { COUNTER_WORDS = 192 };
+    uint32_t* longest() const { return counters; }
+    unsigned long long* total() const { return (unsigned long long*)(counters + 64); }
+    uint32_t* oct() const { return counters + 128; }
+};
+
 // Brick grid over the centred scene (replaces the kd-tree of kdtree.h for the restricted-radius
 // nearest-neighbour query).  Cell edge h = epsilon.  A cell's candidate list holds every scene
 // point whose distance to the cell's box is <= epsilon (+ a 0.1% safety margin), so ONE list scan
@@ -175,11 +213,10 @@ struct SceneGrid {
     // octant lines (octant_lists.h): cells whose stored list is longer than a line, those of them whose flat-table word names an octant
     // block, and the entries of their octant lines before padding; all 0 on a grid without them.  n_entries counts the plain lists only
     int64_t n_long_cells, n_octant_cells, n_octant_entries;
-    // the lines are written by build_octant_lines once the scene's scoring work makes them pay (lcp.hip); until then: what that call needs
-    // of the build (its temporaries stay in the build's workspace until the next build)
+    // the lines are written by build_octant_lines once the scene's scoring work makes them pay (lcp.hip); until then `stages` keeps what
+    // that call needs of the build (its temporaries stay in the build's workspace until the next build)
     bool oct_pending;
-    const uint64_t* oct_cell_key; const uint32_t* oct_list_off; const uint32_t* oct_kept; uint32_t* oct_counts; uint32_t oct_n_cells;
-    double oct_h, oct_r, oct_hw, oct_margin;
+    GridStages stages;
     int32_t* d_top;     // nbx*nby*nbz -> brick id or -1
     uint4* d_flat;       // the same cell words addressed directly, (cz*ny + cy)*nx + cx, when the box is small enough (sparse
                          // scenes, cell edge eps): saves the LCP kernel the dependent `top` look-up; else NULL
@@ -203,6 +240,8 @@ struct SceneGrid {
     int cg_nx, cg_ny, cg_nz, cg_w;   // cg_w: cells a point reaches on either side (ceil(cap / g))
     double bb_mn[3], bb_mx[3];       // bounding box of the centred scene
 };
+// No grid: every pointer NULL, every count and record zero.  The memory is the arenas' (c->grid_mem, c->grid_ws), which the next build resets
+inline void reset_grid(SceneGrid& g) { g = SceneGrid(); }
 
 // Model PPF index on the device: every ordered pair stored once under its own quantised key F
 // (CSR over the dense key space), plus the dilated existence bitmap ("is K a key of the
@@ -443,7 +482,14 @@ inline float* cand_lcp(stocs_ctx* c) { return (float*)c->d_cand + (size_t)c->can
 inline int32_t* cand_base(stocs_ctx* c) { return (int32_t*)((float*)c->d_cand + (size_t)c->cand_cap * 33); }
 int ensure_scratch(stocs_ctx* c, size_t bytes);
 int ensure_pinned(stocs_ctx* c, size_t bytes);   // c->h_pin of at least `bytes` (nothing may still be copying into the old block)
-enum { PIN_CONGRUENT = 0, PIN_TRANSFORMS = 256, PIN_VERIFY = 512, PIN_BEST = 768, PIN_VAR = 1024 };   // fixed slots, then the per-call variable part
+enum { PIN_CONGRUENT = 0, PIN_TRANSFORMS = 256, PIN_VERIFY = 512, PIN_BEST = 768, PIN_GRID = 1024, PIN_VAR = 1280 };   // fixed slots, then the per-call variable part
+struct PinGrid {   // PIN_GRID: the read-backs of a grid build and of build_octant_lines (grid.hip)
+    unsigned long long n_inc, n_kept;      // incidences, entries kept by the pruning
+    uint32_t n_cells, n_bricks, sort_err;  // non-empty cells, bricks, the own sort's error word
+    uint32_t n_list, longest;              // padded list entries, entries of the longest stored list
+    uint32_t n_long_cells, n_octant_cells, n_octant_entries;   // (the last two are one 8-byte copy)
+};
+static_assert(sizeof(PinGrid) <= PIN_VAR - PIN_GRID, "PinGrid outgrew its pinned slot");
 // The per-call staging: *h = the variable part of the pinned block, holding at least `bytes`.  The one place where the block grows under a
 // call: the stream is synchronised first if it has to move (nothing may still be copying into the old block).
 int pinned_var(stocs_ctx* c, size_t bytes, char** h);
@@ -491,7 +537,7 @@ int enqueue_trial_cluster(stocs_ctx* c, int n_trials, const float* d_P, const fl
 int ensure_kdtree(stocs_ctx* c);   // kdtree.hip: the kd-tree of the current scene on the device (exact_ties); synchronises
 int sample_trials(stocs_ctx* c, int mode, int nT, const uint64_t* seeds, int nA, float dispersion, BaseOut* res_host, const float4** snrmw0, size_t* snrmw_stride);   // sample.hip
 int build_ppf_index(stocs_ctx* c);
-int build_grid_gpu(stocs_ctx* c, int div, int dense, int prune);
+int build_grid_gpu(stocs_ctx* c, const GridForm& form);   // c->grid from c->d_spos (device) and c->h_spos (bounding box only)
 int prepare_cull_field(stocs_ctx* c);   // geometry + memory of SceneGrid::d_dist for the current grid and model (end of a grid build)
 int build_octant_lines(stocs_ctx* c);                          // the octant lines of the current grid, on c->stream, once per scene (grid.hip)
 int fill_cull_field(stocs_ctx* c, hipStream_t st = NULL);      // the values, on st (NULL: c->stream); no synchronisation
