@@ -124,6 +124,9 @@ __device__ __forceinline__ const float4* lcp_weights_of(const LcpArgs& a, int ca
 // >= 2^-9 (class probabilities are >= the 0.10 threshold), hence independent of the order -- of the lane a point lands on,
 // of how a candidate's model points are split over wavefronts, of the batch it is scored in.  The score is the correctly
 // rounded float of the exact mean; the reference's running float sum differs from it by ~1e-7 (tests: <= 1e-5).
+__device__ __forceinline__ unsigned long long lcp_addend(float w) {
+    return w > 0.0f ? (unsigned long long)(w * 4294967296.0f) : 0ull;   // exact product (power of two), truncating conversion
+}
 __device__ __forceinline__ void lcp_add(unsigned long long& acc, float w) {
     if (w > 0.0f) acc += (unsigned long long)(w * 4294967296.0f);   // exact product (power of two), truncating conversion
 }
@@ -404,6 +407,40 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT)) void lcp_c
 // score (stocs.cpp:1019-1024) and is skipped: one look-up per step instead of 64.  Margins cover the float rounding of the
 // transform, of the field and of the cell centre; positions that are not finite are never ruled out here.
 // ---------------------------------------------------------------------------------------------
+//
+// The test comes in two halves with the field look-up between them, and neither half branches around a load: the whole 16-byte record
+// is used whatever the centre is (a record whose radius word is wanted only behind the magnitude test arrives as a 12-byte load and
+// a dependent 4-byte one), and a centre that is not finite or lies outside the table looks up cell 0, whose value it does not use.  A
+// caller with two records can so have both record loads, then both look-ups, in flight together.
+struct LcpPatchProbe {
+    float cx, cy, cz, fx, fy, fz;
+    uint32_t cell;   // of a.dist; 0 when !inside
+    bool inside;     // finite, and one cell inside the border: the float cell of a position next to the box never names a cell outside the table
+};
+__device__ __forceinline__ LcpPatchProbe lcp_patch_probe(const LcpArgs& a, const float4 sp, float t0, float t1, float t2, float t4, float t5, float t6,
+                                                         float t8, float t9, float t10, float t12, float t13, float t14) {
+    LcpPatchProbe p;
+    p.cx = ((t0 * sp.x + t4 * sp.y) + t8 * sp.z) + t12;
+    p.cy = ((t1 * sp.x + t5 * sp.y) + t9 * sp.z) + t13;
+    p.cz = ((t2 * sp.x + t6 * sp.y) + t10 * sp.z) + t14;
+    const float mag = fabsf(p.cx) + (fabsf(p.cy) + fabsf(p.cz));
+    const float ux = (p.cx - a.gox) * a.inv_g, uy = (p.cy - a.goy) * a.inv_g, uz = (p.cz - a.goz) * a.inv_g;
+    p.fx = floorf(ux); p.fy = floorf(uy); p.fz = floorf(uz);
+    p.inside = (mag < 1.0e18f) && p.fx >= 1.0f && p.fy >= 1.0f && p.fz >= 1.0f && p.fx < (float)(a.gnx - 1) && p.fy < (float)(a.gny - 1) && p.fz < (float)(a.gnz - 1);
+    p.cell = p.inside ? ((uint32_t)(int)p.fz * (uint32_t)a.gny + (uint32_t)(int)p.fy) * (uint32_t)a.gnx + (uint32_t)(int)p.fx : 0u;   // <= 16 M cells
+    return p;
+}
+// v = a.dist[p.cell]
+__device__ __forceinline__ bool lcp_patch_verdict(const LcpArgs& a, const LcpPatchProbe& p, float radius, float sn, float v) {
+    const float mag = fabsf(p.cx) + (fabsf(p.cy) + fabsf(p.cz));
+    const float need = (sn * radius + a.eps * 1.002f) + (4.0e-6f + 4.0e-6f * mag);
+    const float ex = p.cx - (a.gox + (p.fx + 0.5f) * a.g), ey = p.cy - (a.goy + (p.fy + 0.5f) * a.g), ez = p.cz - (a.goz + (p.fz + 0.5f) * a.g);
+    // outside (or in the border cells of) the table: at least cap from every scene point
+    const float room = p.inside ? v - sqrtf(ex * ex + (ey * ey + ez * ez)) : a.cap;
+    return (mag < 1.0e18f) && room > need;
+}
+// the test in one piece, branching: for the forms that have no registers to spare for the halves (the ring and whole-step forms of the
+// queue kernel: up to 28 bytes of scratch with them)
 __device__ __forceinline__ bool lcp_patch_dead(const LcpArgs& a, const float4 sp, float sn, float t0, float t1, float t2, float t4, float t5, float t6,
                                                float t8, float t9, float t10, float t12, float t13, float t14) {
     const float cx = ((t0 * sp.x + t4 * sp.y) + t8 * sp.z) + t12;
@@ -495,13 +532,20 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
     constexpr bool NOSENT = !DENSE;
     constexpr int UNR = 1;           // list lines per trip after the first (two: +3 %)
     constexpr int PIPE = 1;          // trips in flight (two: 1.18 -> 1.185 ms at Cm; three and four spill)
+    // CHAIN: fewer dependent memory round trips per wavefront -- whole-record loads, both windows of the patch test in flight together,
+    // a sorted record per query in place of three dependent LDS reads in front of every verify trip (Cm 0.805 -> 0.785 ms, 8 192
+    // candidates 0.1328 -> 0.1269; profiles/lcp_chain_ab.json, _isa.md).  For the shared-list forms, which have 5 to 13 VGPRs to spare;
+    // the others sit at 55 to 64, two of the gated ones spill 8 bytes with the whole-record normal test alone, and every one keeps
+    // exactly the code it had
+    constexpr bool CHAIN = SHARED;
     static_assert(!EARLY || (FIRST == 1 && !NOSENT), "early exit decides line by line");
     __shared__ float4 qt[WPB][128];     // qx, qy, qz, bits(list offset)
     __shared__ float qcd[EARLY ? WPB : 1][EARLY ? 128 : 1];   // |query - cell centre| (EARLY)
     __shared__ uint32_t qn[WPB][128];   // list length
     __shared__ uint32_t qs[WPB][128];   // model slot (patch order)
     __shared__ int ri[WPB][128];        // best scene index
-    __shared__ uint8_t ord[WPB][64];    // batch order sorted by list length
+    __shared__ uint8_t ord[WPB][64];    // batch order sorted by list length (!CHAIN)
+    __shared__ uint2 srec[CHAIN ? WPB : 1][CHAIN ? 64 : 1];   // CHAIN: the batch sorted by list length: (list offset, list length | ring slot << 16)
     __shared__ unsigned long long part[WPB];
     const int lane = threadIdx.x & 63;
     // (the wavefront index stays in a VGPR: forced into an SGPR the kernel is 12 % slower, profiles/r04_lcp_w_uniform_isa.md)
@@ -509,6 +553,17 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
     const int cand = SPLIT ? lcp_candidate(a, n, 0, 1) : lcp_candidate(a, n, w, WPB);
     if (cand < 0) return;   // SPLIT: the whole workgroup leaves together
     const float4* __restrict__ snrmw = lcp_weights_of(a, cand);
+    // SHARED: the sphere records of this wavefront's two windows of the patch test (below) do not depend on the candidate: both are
+    // requested here, back to back and ahead of the wait for the transform.  A window beyond the model reads the last record (no branch
+    // around the load); its result is discarded.  (A shared-list form runs only with the test on -- CU = 16 is chosen by a.patch,
+    // choose_lcp_form -- so a.sub is there)
+    const bool patch_on = SHARED && !STOCS_ABLATE(a, 64);
+    float4 wsp[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+    if (SHARED) {
+        const int last_sub = max(((a.M + 15) >> 4) - 1, 0);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) wsp[j] = a.sub[min((int)(((threadIdx.x >> 6) + 4 * j) << 6) + lane, last_sub)];
+    }
     const float* T = T16 + (size_t)cand * 16;
     const float t0 = T[0], t1 = T[1], t2 = T[2], t4 = T[4], t5 = T[5], t6 = T[6], t8 = T[8], t9 = T[9], t10 = T[10],
                 t12 = T[12], t13 = T[13], t14 = T[14];
@@ -525,21 +580,36 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
         // three classes -- one trip, two, more -- do it at a third of the instructions of a sort over all lengths
         {
             uint32_t cls = 4;   // no query
+            uint2 rec = make_uint2(0u, 0u);
             if (lane < nq) {
-                const uint32_t nch = (qn[w][(head + lane) & 127] + 7u) >> 3;
+                const int idx = (head + lane) & 127;
+                const uint32_t len = qn[w][idx];
+                const uint32_t nch = (len + 7u) >> 3;
                 cls = nch <= (uint32_t)FIRST ? 1u : (nch <= (uint32_t)(FIRST + UNR) ? 2u : 3u);
+                if (CHAIN) rec = make_uint2((uint32_t)__float_as_int(qt[w][idx].w), len | ((uint32_t)idx << 16));   // (len <= STOCS_CONE_COUNT_MASK: 16 bits)
             }
             const unsigned long long below = (1ull << lane) - 1ull;
             const unsigned long long m1 = __ballot(cls == 1u), m2 = __ballot(cls == 2u), m3 = __ballot(cls == 3u);
             const int n1 = __popcll(m1), n2 = __popcll(m2);
             const int pos = cls == 1u ? __popcll(m1 & below) : (cls == 2u ? n1 + __popcll(m2 & below) : n1 + n2 + __popcll(m3 & below));
-            if (lane < nq) ord[w][pos] = (uint8_t)lane;
+            if (CHAIN) { if (lane < nq) srec[w][pos] = rec; }
+            else if (lane < nq) ord[w][pos] = (uint8_t)lane;
             __builtin_amdgcn_wave_barrier();
         }
         // a trip: NG queries, GL lanes each.  The first FIRST lines of the lists of PIPE trips are requested back to back, then
         // compared: one memory round trip serves most of the queries
+        // CHAIN: a trip finds offset, length and ring slot of its query in ONE record at a static address, not behind the chain
+        // order -> length -> offset of three dependent LDS reads; and the record of the next trip is requested behind this trip's list
+        // loads, so that it arrives under them (the last trip reads its own again; records behind the call's queries are stale and
+        // replaced below).  Two VGPRs: all four records ahead of the first trip cost eight, and the gated forms then reach 64 and one spills
+        static_assert(!CHAIN || PIPE == 1, "one record per trip");
+        uint2 rec_next = make_uint2(0u, 0u);
+        if (CHAIN) rec_next = srec[w][lane / GL];
         for (int s0 = 0; s0 < nq; s0 += NG * PIPE) {
             const int sub = lane & (GL - 1), grp = lane / GL;
+            // a group without a query takes the ring slot of the call's first one, with no entries: the later lines of a trip are read by
+            // every group through the offset that sits in that slot (a stale record may name a slot that was never written)
+            const uint2 rec = s0 + grp < nq ? rec_next : make_uint2(0u, (uint32_t)(head & 127) << 16);
             float4 e0[PIPE][E0];
             bool wide[PIPE];
             int idxs[PIPE];
@@ -548,8 +618,8 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
             for (int u = 0; u < PIPE; ++u) {
                 const int slot = s0 + NG * u + grp;
                 const bool gact = slot < nq;
-                idxs[u] = (head + (int)ord[w][gact ? slot : 0]) & 127;
-                cs[u] = gact ? qn[w][idxs[u]] : 0u;
+                idxs[u] = CHAIN ? (int)((rec.y >> 16) & 127u) : (head + (int)ord[w][gact ? slot : 0]) & 127;
+                cs[u] = gact ? (CHAIN ? (rec.y & 0xFFFFu) : qn[w][idxs[u]]) : 0u;
                 wide[u] = true;
                 if (!NOSENT) {
 #pragma unroll
@@ -562,7 +632,7 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
                 else if (NOSENT) {
                     // no sentinels, no predication: a group without a query reads list line 0 (its result is never stored), a list
                     // shorter than the trip reads its last line again -- the same entries, the same winner
-                    const float4* l0 = a.list + (cs[u] ? (uint32_t)__float_as_int(qt[w][idxs[u]].w) : 0u) + sub;
+                    const float4* l0 = a.list + (cs[u] ? (CHAIN ? rec.x : (uint32_t)__float_as_int(qt[w][idxs[u]].w)) : 0u) + sub;
                     const uint32_t last = cs[u] ? ((cs[u] - 1u) & ~7u) : 0u;
 #pragma unroll
                     for (int e = 0; e < EPL; ++e) e0[u][e] = l0[GL * e];
@@ -575,11 +645,12 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
                     }
                 }
                 else if (cs[u]) {
-                    const float4* l0 = a.list + (uint32_t)__float_as_int(qt[w][idxs[u]].w) + sub;
+                    const float4* l0 = a.list + (CHAIN ? rec.x : (uint32_t)__float_as_int(qt[w][idxs[u]].w)) + sub;
 #pragma unroll
                     for (int e = 0; e < E0; ++e) e0[u][e] = l0[GL * e];   // (E0 = EPL: one line)
                 }
             }
+            if (CHAIN) rec_next = srec[w][min(s0 + NG * PIPE, 64 - NG * PIPE) + grp];
 #pragma unroll
             for (int u = 0; u < PIPE; ++u) {
                 const float4 qq = qt[w][idxs[u]];
@@ -658,9 +729,14 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
                 const float ny = t1 * nm.x + (t5 * nm.y + t9 * nm.z);
                 const float nz = t2 * nm.x + (t6 * nm.y + t10 * nm.z);
                 const float4 sn = STOCS_ABLATE(a, 32) ? make_float4(nx, ny, nz, 0.5f) : snrmw[best];         // 32: no scene-normal gather
+                // the addend is formed from the record's fourth word ahead of the test and selected behind it: all four words are used
+                // whatever the test says, so the record arrives as ONE 16-byte load (a weight wanted only by the counted lanes arrives as a
+                // dependent 4-byte load behind a 12-byte one)
+                const unsigned long long add = CHAIN ? lcp_addend(sn.w) : 0ull;
                 const float d = sn.x * nx + (sn.y * ny + sn.z * nz);
                 counted = (d >= a.dot_lo) && (d <= 1.0f);
-                if (counted) lcp_add(acc, sn.w);
+                if (CHAIN) acc += counted ? add : 0ull;
+                else if (counted) lcp_add(acc, sn.w);
             }
             if (DETAIL) {
                 const int orig = a.mperm[slot_i];
@@ -772,14 +848,25 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
     if (threadIdx.x == 0) live_n = 0;
     const int nsubs = (a.M + 15) >> 4;   // <= LCP_SHARED_LIVE: at most two windows per wavefront
     const float snorm = GATE ? gnorm : (a.patch ? linear_norm_bound(t0, t1, t2, t4, t5, t6, t8, t9, t10) : 0.0f);
+    // windows w and w + 4: both centres, then both look-ups of the distance field back to back, then the two verdicts -- two memory
+    // round trips in front of the barrier, not four
     unsigned long long lm[2];
+    {
+        bool live[2];
+        LcpPatchProbe pp[2];
+        float fv[2] = {0.f, 0.f};
 #pragma unroll
-    for (int j = 0; j < 2; ++j) {   // windows w and w + 4
-        const int q = ((w + 4 * j) << 6) + lane;
-        bool live = q < nsubs;
-        if (a.patch && live && !STOCS_ABLATE(a, 64))
-            live = !lcp_patch_dead(a, a.sub[q], snorm, t0, t1, t2, t4, t5, t6, t8, t9, t10, t12, t13, t14);
-        lm[j] = __ballot(live);
+        for (int j = 0; j < 2; ++j) live[j] = ((w + 4 * j) << 6) + lane < nsubs;
+        if (patch_on) {
+#pragma unroll
+            for (int j = 0; j < 2; ++j) pp[j] = lcp_patch_probe(a, wsp[j], t0, t1, t2, t4, t5, t6, t8, t9, t10, t12, t13, t14);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) fv[j] = a.dist[pp[j].cell];
+#pragma unroll
+            for (int j = 0; j < 2; ++j) live[j] = live[j] && !lcp_patch_verdict(a, pp[j], wsp[j].w, snorm, fv[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) lm[j] = __ballot(live[j]);
     }
     __syncthreads();   // live_n is zero for everyone (the tests above needed no LDS: nobody waits here for long)
 #pragma unroll
