@@ -44,32 +44,15 @@
 #include <algorithm>
 
 #include "cone_cells.h"
+#include "congruent_lists.h"
 #include "prims.h"
 #include "stocs_ctx.h"
 
 namespace stocs {
 
-struct BaseJob {
-    float inv1, inv2, cos_alpha;
-    float cell;       // _epsilon of the normal set (unit-cube cell edge)
-    int egSize;
-    int nb;           // cone samples
-    uint32_t p_off, p_len, q_off, q_len;   // runs in the gathered P / Q arrays
-    float sin_alpha;  // the cone samples of the base are (sin_alpha * cos theta_a, sin_alpha * sin theta_a, cos_alpha), a < nb, with cos / sin of
-                      // theta_a = a * angleStep(nb) from ONE table shared by all bases (cone_trig: they depend on nb alone).  Round 3 carried the
-                      // 56 products per base in the job record: 808 bytes per base to fill and upload -- 0.7 ms of host time for the 6 000
-                      // bases of a 64-trial batch; the one float product per sample is the same IEEE operation on the device.
-    float pad;
-};
-
-struct Segment { uint32_t src, len, dst, base; };
-
 __device__ __forceinline__ V3 ld3c(const float4* a, int i) { const float4 v = a[i]; return mk3(v.x, v.y, v.z); }
 
 // ---- planning of the lookups on the device (what plan_lookup of ppf_index.hip does per key on the host) ----
-// Totals and array sizes of a trial's pair lists, read back by the host (the only thing it needs before it can size the sorts)
-struct PlanOut { unsigned long long totP, totQ; uint32_t n_pseg, n_qseg, overflow, pad; };
-
 // One 64-lane workgroup per (base, list): the PPF key of the base's point pair (stocs.cpp:771-772, the reference's double
 // arithmetic), its 128 probes of the bucket table in ASCENDING key order -- F = K - o with o0 in {-tr, 0}, ok in
 // {-2 rot, -rot, 0, rot}, rgbd.cpp:130-137 read from the query side -- two per lane, then lane 0 merges adjacent buckets
@@ -114,26 +97,6 @@ __global__ __launch_bounds__(64) void plan_ranges_kernel(const uint32_t* __restr
         n_ranges[(size_t)list * nB + b] = n;
         totals[(size_t)list * nB + b] = total;
     }
-}
-
-// exclusive scan of a[0 .. n) by one workgroup of 1024, in place; emit(i, offset, value) sees every element
-template <class F>
-__device__ __forceinline__ void block_scan_1024(uint32_t* __restrict__ a, uint32_t n, uint32_t* s_part, F emit) {
-    const uint32_t tid = threadIdx.x, chunk = (n + 1023u) / 1024u;
-    const uint32_t lo = min(tid * chunk, n), hi = min(lo + chunk, n);
-    uint32_t sum = 0;
-    for (uint32_t i = lo; i < hi; ++i) sum += a[i];
-    __syncthreads();
-    s_part[tid] = sum;
-    __syncthreads();
-    for (uint32_t d = 1; d < 1024u; d <<= 1) {
-        const uint32_t v = tid >= d ? s_part[tid - d] : 0u;
-        __syncthreads();
-        s_part[tid] += v;
-        __syncthreads();
-    }
-    uint32_t run = s_part[tid] - sum;
-    for (uint32_t i = lo; i < hi; ++i) { const uint32_t v = a[i]; a[i] = run; emit(i, run, v); run += v; }
 }
 
 // One workgroup of 1024: offsets of every base in the gathered lists (a base without P pairs or without Q pairs gets neither,
@@ -199,412 +162,6 @@ __global__ __launch_bounds__(256) void plan_segments_kernel(int nB, const uint2*
         if (k < n) { Segment o = {v.x, len, d0 + carry + (inc - len), (uint32_t)b}; sg[k] = o; }
         carry += __shfl(inc, 63, 64);
     }
-}
-
-// normalset.h:97-104 + utils.h:139-148: int truncation of coord/epsilon, x fastest
-// (cell = 1 / eg with eg a power of two, normalset.h:117-119: dividing by it and multiplying by eg are the same float)
-__device__ __forceinline__ int64_t index_pos(V3 p, float cell, int eg) {
-    (void)cell;
-    const V3 cp = p * (float)eg;
-    return (int64_t)(int)cp.z * eg * eg + ((int64_t)(int)cp.y * eg + (int64_t)(int)cp.x);
-}
-
-// Pair lists of all bases out of the device index (a lookup is the union of <= 128 buckets, ppf_index.hip), each entry
-// with its sort key (base << cell_bits | position cell).  P entries sit at p1 + inv1 (p2 - p1) (nset.addElement,
-// stocs.cpp:810-818), Q entries query at p1 + inv2 (p2 - p1) (stocs.cpp:827-836).  A cell the table cannot hold -- it
-// cannot occur for points of the unit cube -- gets the all-ones cell: never queried, never matched.
-#define GATHER_EPT 4
-#define GATHER_TILE (256u * GATHER_EPT)
-// (8 192 since round 5b: with 2 048 -- one round of resident workgroups, each with an eighth of a per cent of the list -- the last of them ran on a
-//  half-empty chip: 4.4 wavefronts per SIMD on average over a 42-trial piece; four times as many, shorter workgroups level that: congruent phase -2 %)
-static inline unsigned gather_max_wgs() { static const unsigned v = getenv("STOCS_GATHER_WGS") ? (unsigned)std::max(1, atoi(getenv("STOCS_GATHER_WGS"))) : 8192u; return v; }
-#define GATHER_MAX_WGS gather_max_wgs()
-static inline unsigned gather_grid(unsigned long long total) { const unsigned long long t = (total + GATHER_TILE - 1) / GATHER_TILE; return (unsigned)std::max<unsigned long long>(1, std::min<unsigned long long>(t, GATHER_MAX_WGS)); }
-// po != NULL: the launch was sized by a CAPACITY (the host has not read the plan yet, see stocs_internal_find_congruent): the
-// list's length and segment count are the planned ones, read here, and the workgroups beyond them leave at once.
-template <class KeyT>
-__device__ __forceinline__ void gather_key_body(const uint32_t* __restrict__ pairs, const Segment* __restrict__ segs, int nseg, uint32_t total,
-                                                const BaseJob* __restrict__ jobs, const float4* __restrict__ munit, int is_q, int cell_bits,
-                                                long long cell_limit, KeyT* __restrict__ keys, uint32_t* __restrict__ vals,
-                                                uint32_t* __restrict__ occ, const PlanOut* __restrict__ po, uint32_t lds_words, uint32_t n_bases) {
-    // occ: ONE BIT per (base, cell) value of the key -- which (base, cell) this list occupies.  lds_words > 0 (= 2^cell_bits / 32, the
-    // words of one base): the bits of the base the workgroup's current tile starts in are collected in LDS and OR-ed into the table
-    // when the workgroup moves on to the next base or ends (a base's stretch is ~88 tiles at Cm: one atomic per word and workgroup
-    // instead of one scattered store per entry); entries of another base in the same tile (a boundary tile) go to the table directly.
-    extern __shared__ uint32_t s_occ[];
-    if (po) {
-        if (po->overflow) return;          // >= 2^32 planned entries: the segments' 32-bit destinations have wrapped; the host reports STOCS_ERR_CAPACITY
-        const unsigned long long t = is_q ? po->totQ : po->totP;
-        total = t < (unsigned long long)total ? (uint32_t)t : total;      // never beyond the buffers (a plan beyond the capacity is redone by the host)
-        nseg = (int)(is_q ? po->n_qseg : po->n_pseg);
-    }
-    // A workgroup takes a contiguous run of tiles (GATHER_EPT * 256 entries each; a thread GATHER_EPT of them 256 apart, coalesced),
-    // the launch at most GATHER_MAX_WGS workgroups: the binary search over the segments (12 scalar loads one after the other) runs once
-    // per workgroup, the segment of a wavefront's entries is wave-uniform STATE carried from tile to tile (a segment holds thousands
-    // of entries: the next boundary is compared, not loaded), and the workgroup owns the LDS bits of "its" base across its tiles.  The
-    // steady state is pair load -> two model points -> stores: three dependent round trips per tile, ~10 us per tile with eight
-    // workgroups on a CU (device clock of one workgroup, round 4).  The kernel is bound by the bytes its waves keep in flight (1.5 TB/s
-    // over both lists, waves waiting 53 %, no unit above 0.65 busy); by ablation (one list, 9.5 M entries, 103 us): without the
-    // occupancy marks 83, without the (key, pair) stores 83, with nothing but the pair load 62.  Prefetching the next tile's pairs,
-    // the model in LDS and 64-bit products as shifts were measured and not kept.
-    const uint32_t n_tiles = (total + GATHER_TILE - 1u) / GATHER_TILE;
-    const uint32_t per_wg = (n_tiles + gridDim.x - 1u) / gridDim.x;
-    const uint32_t t_begin = blockIdx.x * per_wg, t_end = min(n_tiles, t_begin + per_wg);
-    if (t_begin >= t_end) return;
-    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63u;
-    const uint32_t w0 = t_begin * GATHER_TILE + wave * 64u;      // the wavefront's first entry
-    const bool mark_lds = occ != NULL && lds_words != 0u;
-    if (mark_lds) { for (uint32_t w = threadIdx.x; w < lds_words; w += blockDim.x) s_occ[w] = 0u; __syncthreads(); }
-    // the base the current TILE starts in, followed through the base jobs (uniform over the workgroup: it depends on the tile alone)
-    uint32_t cur_b = 0, cur_end = 0;
-    if (mark_lds) {
-        const uint32_t ts = t_begin * GATHER_TILE;
-        int blo = 0, bhi = (int)n_bases - 1;       // last base whose stretch begins at or before ts
-        while (blo < bhi) {
-            const int mid = (blo + bhi + 1) >> 1;
-            const uint32_t off = is_q ? jobs[mid].q_off : jobs[mid].p_off;
-            if (off <= ts) blo = mid; else bhi = mid - 1;
-        }
-        cur_b = (uint32_t)blo;
-        cur_end = blo + 1 < (int)n_bases ? (is_q ? jobs[blo + 1].q_off : jobs[blo + 1].p_off) : 0xFFFFFFFFu;
-    }
-    auto flush = [&](uint32_t b) {
-        __syncthreads();
-        for (uint32_t w = threadIdx.x; w < lds_words; w += blockDim.x) {
-            const uint32_t v = s_occ[w];
-            if (v) { atomicOr(&occ[(size_t)b * lds_words + w], v); s_occ[w] = 0u; }
-        }
-        __syncthreads();
-    };
-    int lo = 0, hi = nseg - 1;                                    // last segment with dst <= w0 (uniform binary search, scalar loads)
-    if (w0 < total) {
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if (segs[mid].dst <= w0) lo = mid; else hi = mid - 1;
-        }
-    }
-    // wave-uniform segment state
-    int sgu = lo;
-    uint32_t sg_src = 0, sg_dst = 0, sg_base = 0, next_dst = 0xFFFFFFFFu, gu = 1;
-    float ju = 0.0f;
-    auto load_segment = [&](int i) {
-        const Segment sg = segs[i];
-        sg_src = __builtin_amdgcn_readfirstlane(sg.src); sg_dst = __builtin_amdgcn_readfirstlane(sg.dst); sg_base = __builtin_amdgcn_readfirstlane(sg.base);
-        next_dst = i + 1 < nseg ? __builtin_amdgcn_readfirstlane(segs[i + 1].dst) : 0xFFFFFFFFu;
-        const BaseJob& J = jobs[sg_base];
-        ju = is_q ? J.inv2 : J.inv1; gu = (uint32_t)J.egSize;
-    };
-    if (nseg > 0) load_segment(sgu);
-    const KeyT cmask = ((KeyT)1 << cell_bits) - (KeyT)1;
-    for (uint32_t tile = t_begin; tile < t_end; ++tile) {
-        if (mark_lds && tile * GATHER_TILE >= cur_end) {            // (uniform over the workgroup)
-            flush(cur_b);
-            while (tile * GATHER_TILE >= cur_end) { ++cur_b; cur_end = cur_b + 1 < n_bases ? (is_q ? jobs[cur_b + 1].q_off : jobs[cur_b + 1].p_off) : 0xFFFFFFFFu; }
-        }
-        uint32_t e[GATHER_EPT], pr[GATHER_EPT], base[GATHER_EPT];
-        bool live[GATHER_EPT];
-        float inv[GATHER_EPT]; int eg[GATHER_EPT];
-#pragma unroll
-        for (int k = 0; k < GATHER_EPT; ++k) {
-            const uint32_t ef = tile * GATHER_TILE + (uint32_t)k * 256u + wave * 64u;   // (uniform)
-            e[k] = ef + lane;
-            live[k] = e[k] < total;
-            pr[k] = 0; base[k] = 0; inv[k] = 0.0f; eg[k] = 1;
-            if (ef >= total) continue;
-            const uint32_t el = min(ef + 63u, total - 1u);
-            while (next_dst <= ef) load_segment(++sgu);
-            if (el < next_dst) {                    // the 64 entries lie in one segment: nothing but the pair load
-                if (live[k]) { pr[k] = pairs[sg_src + (e[k] - sg_dst)]; base[k] = sg_base; inv[k] = ju; eg[k] = (int)gu; }
-            } else if (live[k]) {                   // a wavefront across a boundary: per-lane walk from the uniform segment
-                int sgi = sgu;
-                while (sgi + 1 < nseg && segs[sgi + 1].dst <= e[k]) ++sgi;
-                const Segment sg = segs[sgi];
-                pr[k] = pairs[sg.src + (e[k] - sg.dst)];
-                base[k] = sg.base;
-                const BaseJob& J = jobs[sg.base];
-                inv[k] = is_q ? J.inv2 : J.inv1; eg[k] = J.egSize;
-            }
-        }
-        float4 a1[GATHER_EPT], a2[GATHER_EPT];
-#pragma unroll
-        for (int k = 0; k < GATHER_EPT; ++k) { a1[k] = munit[pr[k] >> 16]; a2[k] = munit[pr[k] & 0xFFFF]; }
-#pragma unroll
-        for (int k = 0; k < GATHER_EPT; ++k) {
-            if (!live[k]) continue;
-            const V3 p1 = mk3(a1[k].x, a1[k].y, a1[k].z), p2 = mk3(a2[k].x, a2[k].y, a2[k].z);
-            const int64_t pc = index_pos(p1 + inv[k] * (p2 - p1), 0.0f, eg[k]);
-            const bool no_cell = pc < 0 || pc >= cell_limit;
-            const KeyT key = ((KeyT)base[k] << cell_bits) | (no_cell ? cmask : (KeyT)pc);
-            keys[e[k]] = key;
-            vals[e[k]] = pr[k];
-            if (occ && !no_cell) {
-                if (mark_lds && base[k] == cur_b) atomicOr(&s_occ[(uint32_t)pc >> 5], 1u << ((uint32_t)pc & 31u));
-                else atomicOr(&occ[(size_t)(key >> 5)], 1u << ((uint32_t)key & 31u));
-            }
-        }
-    }
-    if (mark_lds) flush(cur_b);
-}
-template <class KeyT>
-__global__ __launch_bounds__(256) void gather_key_kernel(const uint32_t* __restrict__ pairs, const Segment* __restrict__ segs, int nseg, uint32_t total,
-                                                         const BaseJob* __restrict__ jobs, const float4* __restrict__ munit, int is_q, int cell_bits,
-                                                         long long cell_limit, KeyT* __restrict__ keys, uint32_t* __restrict__ vals,
-                                                         uint32_t* __restrict__ occ, const PlanOut* __restrict__ po, uint32_t lds_words, uint32_t n_bases) {
-    gather_key_body<KeyT>(pairs, segs, nseg, total, jobs, munit, is_q, cell_bits, cell_limit, keys, vals, occ, po, lds_words, n_bases);
-}
-// Both lists in ONE launch (blockIdx.y: 0 = P, 1 = Q): the one-stream form of count_pass -- P and Q still share the chip, and no event edge
-// between two streams (~11 us each on this runtime, five of them in a trial) stands between the steps.
-template <class KeyT>
-struct GatherSide { const Segment* segs; int nseg; uint32_t total; KeyT* keys; uint32_t* vals; uint32_t* occ; };
-template <class KeyT>
-__global__ __launch_bounds__(256) void gather_key_dual_kernel(const uint32_t* __restrict__ pairs, GatherSide<KeyT> P, GatherSide<KeyT> Q, const BaseJob* __restrict__ jobs,
-                                                              const float4* __restrict__ munit, int cell_bits, long long cell_limit, const PlanOut* __restrict__ po,
-                                                              uint32_t lds_words, uint32_t n_bases) {
-    const bool q = blockIdx.y == 1;
-    gather_key_body<KeyT>(pairs, q ? Q.segs : P.segs, q ? Q.nseg : P.nseg, q ? Q.total : P.total, jobs, munit, q ? 1 : 0, cell_bits, cell_limit, q ? Q.keys : P.keys,
-                          q ? Q.vals : P.vals, q ? Q.occ : P.occ, po, lds_words, n_bases);
-}
-
-// ---- survivors ----
-// A P entry can only ever be matched by a Q entry of the same (base, position cell) and the other way round (Q9: only the
-// query's own cell is inspected), and on the metric workload three entries out of four have no partner cell at all (CPU census
-// of a Cm trial: 23 % of 7.9 M Q entries and 27 % of 10 M P entries do).  So each gather also marks the cells its list occupies,
-// and both lists are reduced to the entries whose cell the OTHER list occupies -- in gather order, so the stable sorts that
-// follow see the same relative order -- before anything is sorted: the sorts, the records and the join work on a quarter of
-// the entries.  Entries dropped here have an empty partner run: they contribute no quad and no rank of the walk order.
-#define SURV_TILE 1024
-template <class KeyT>
-__device__ __forceinline__ bool occ_test(const uint32_t* __restrict__ occ, KeyT key) { return (occ[(size_t)(key >> 5)] >> ((uint32_t)key & 31u)) & 1u; }
-
-// per tile of SURV_TILE entries: how many survive.  A workgroup takes a run of consecutive GROUPS of four tiles, wavefront w of it the w-th
-// tile of the group: its 16 rows of 64 keys are requested together (the round-4 form took one tile per trip of the whole workgroup -- four
-// loads per thread in flight between two barriers, ~10 us per trip: 0.4 TB/s over a 40-trial piece), its count is its own (no reduction
-// across wavefronts), its 16 ballots leave as one 128-byte store.  lds_words > 0: the OTHER list's bits of the base that holds the group's
-// middle entry sit in LDS (2^cell_bits / 8 bytes, loaded when that base changes -- one barrier per group, two more on a change), so the
-// test of an entry of that base is an LDS read -- the byte table of rounds 3-4a was gathered from device memory per entry and missed the
-// L2 half of the time (3.2 MB per list and trial against a 4 MB L2 that the lists stream through).  Entries of another base read the
-// table directly.
-#define SURV_ROWS (SURV_TILE / 64)
-template <class KeyT>
-__device__ __forceinline__ void survivors_count_body(const KeyT* __restrict__ keys, uint32_t n, const uint32_t* __restrict__ other,
-                                                     uint32_t* __restrict__ tile_cnt, const PlanOut* __restrict__ po, int is_q,
-                                                     unsigned long long* __restrict__ alive_bits, uint32_t lds_words, int cell_bits) {
-    extern __shared__ uint32_t s_occ[];
-    __shared__ KeyT s_mid[2];
-    if (po) { if (po->overflow) return; const unsigned long long t = is_q ? po->totQ : po->totP; n = t < (unsigned long long)n ? (uint32_t)t : n; }   // (overflow: the gather wrote nothing)
-    const uint32_t n_tiles = (n + SURV_TILE - 1u) / SURV_TILE, n_groups = (n_tiles + 3u) / 4u;
-    const uint32_t per_wg = (n_groups + gridDim.x - 1u) / gridDim.x;
-    const uint32_t g_begin = blockIdx.x * per_wg, g_end = min(n_groups, g_begin + per_wg);
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const KeyT cmask = ((KeyT)1 << cell_bits) - (KeyT)1;
-    KeyT cur = ~(KeyT)0;                 // base whose bits are in LDS
-    for (uint32_t g = g_begin; g < g_end; ++g) {
-        const uint32_t tile = g * 4u + w, e0 = tile * SURV_TILE + lane;       // (n < 2^32 - 2^16: no wrap; a tile beyond the list loads nothing)
-        KeyT key[SURV_ROWS];
-#pragma unroll
-        for (int k = 0; k < SURV_ROWS; ++k) { const uint32_t e = e0 + (uint32_t)k * 64u; key[k] = (tile < n_tiles && e < n) ? keys[e] : ~(KeyT)0; }
-        if (lds_words) {
-            // the group's middle entry is row 0, lane 0 of wavefront 2; a group that ends before it takes its first entry (wavefront 0)
-            const bool has_mid = g * 4u * SURV_TILE + 2u * SURV_TILE < n;
-            if (lane == 0u && w == (has_mid ? 2u : 0u)) s_mid[g & 1u] = key[0] >> cell_bits;
-            __syncthreads();                                       // (also: every wavefront is done with the bits of the group before)
-            const KeyT tb = s_mid[g & 1u];
-            if (tb != cur) {                                       // (uniform)
-                cur = tb;
-                for (uint32_t i = threadIdx.x; i < lds_words; i += blockDim.x) s_occ[i] = other[(size_t)cur * lds_words + i];
-                __syncthreads();
-            }
-        }
-        if (tile >= n_tiles) continue;                             // (wave-uniform; the barriers above are behind it)
-        uint32_t cnt = 0;
-        unsigned long long mine = 0ull;
-#pragma unroll
-        for (int k = 0; k < SURV_ROWS; ++k) {
-            const uint32_t e = e0 + (uint32_t)k * 64u;
-            bool ob;
-            if (e >= n) ob = false;
-            else if (lds_words && (key[k] >> cell_bits) == cur) { const uint32_t cl = (uint32_t)(key[k] & cmask); ob = (s_occ[cl >> 5] >> (cl & 31u)) & 1u; }
-            else ob = occ_test(other, key[k]);
-            const unsigned long long am = __ballot(ob);            // (the all-ones cell is never marked)
-            // one bit per entry, kept for the compaction: it then reads 8 bytes per row instead of testing again,
-            // and loads the keys and pairs of the survivors only (a quarter of the entries)
-            if (lane == (uint32_t)k) mine = am;
-            cnt += (uint32_t)__popcll(am);
-        }
-        if (lane < (uint32_t)SURV_ROWS) alive_bits[(size_t)tile * SURV_ROWS + lane] = mine;
-        if (lane == 0u) tile_cnt[tile] = cnt;
-    }
-}
-template <class KeyT>
-__global__ __launch_bounds__(256) void survivors_count_kernel(const KeyT* __restrict__ keys, uint32_t n, const uint32_t* __restrict__ other,
-                                                              uint32_t* __restrict__ tile_cnt, const PlanOut* __restrict__ po, int is_q,
-                                                              unsigned long long* __restrict__ alive_bits, uint32_t lds_words, int cell_bits) {
-    survivors_count_body<KeyT>(keys, n, other, tile_cnt, po, is_q, alive_bits, lds_words, cell_bits);
-}
-template <class KeyT>
-struct SurvSide { const KeyT* keys; const uint32_t* vals; uint32_t n; const uint32_t* other; uint32_t* tiles; unsigned long long* alive; KeyT* okeys; uint32_t* ovals; };
-template <class KeyT>
-__global__ __launch_bounds__(256) void survivors_count_dual_kernel(SurvSide<KeyT> P, SurvSide<KeyT> Q, const PlanOut* __restrict__ po, uint32_t lds_words, int cell_bits) {
-    const bool q = blockIdx.y == 1;
-    survivors_count_body<KeyT>(q ? Q.keys : P.keys, q ? Q.n : P.n, q ? Q.other : P.other, q ? Q.tiles : P.tiles, po, q ? 1 : 0, q ? Q.alive : P.alive, lds_words, cell_bits);
-}
-
-// workgroup 0: P list, workgroup 1: Q list.  Tile counts -> tile offsets (element n_tiles receives the total)
-__global__ __launch_bounds__(1024) void survivors_scan_kernel(uint32_t* __restrict__ tiles_p, uint32_t ntp, uint32_t* __restrict__ tiles_q, uint32_t ntq) {
-    __shared__ uint32_t s_part[1024];
-    const bool q = blockIdx.x == 1;
-    block_scan_1024(q ? tiles_q : tiles_p, (q ? ntq : ntp) + 1u, s_part, [](uint32_t, uint32_t, uint32_t) {});
-}
-
-// The same scan for long lists (a trial batch: 10^5 tiles), on as many workgroups as it takes -- the single workgroup above walks 137 counts
-// per thread, one at a time, for a 16-trial piece (137 us on one CU, 1.4 % of the batch).  Two launches: every workgroup scans its 4 096
-// counts (coalesced loads into LDS, 16 per thread there) and writes their sum; then every workgroup adds the sums of the workgroups in
-// front of it (a few dozen words, reduced by the workgroup itself) to its counts.  blockIdx.y: 0 = P list, 1 = Q list.
-#define TSCAN 4096
-__global__ __launch_bounds__(256) void tile_scan_local_kernel(uint32_t* __restrict__ tiles_p, uint32_t np, uint32_t* __restrict__ tiles_q, uint32_t nq, uint32_t* __restrict__ part,
-                                                              uint32_t parts_p) {
-    __shared__ uint32_t s_v[TSCAN + 16];
-    __shared__ uint32_t s_w[4];
-    const bool q = blockIdx.y == 1;
-    uint32_t* a = q ? tiles_q : tiles_p;
-    const uint32_t n = q ? nq : np;
-    const uint32_t base = blockIdx.x * TSCAN;
-    if (base >= n) return;
-    const uint32_t t = threadIdx.x, lane = t & 63u, w = t >> 6;
-#pragma unroll
-    for (int j = 0; j < TSCAN / 256; ++j) { const uint32_t i = base + (uint32_t)j * 256u + t; s_v[(uint32_t)j * 256u + t] = i < n ? a[i] : 0u; }
-    __syncthreads();
-    uint32_t v[16], sum = 0;
-#pragma unroll
-    for (int j = 0; j < 16; ++j) { v[j] = s_v[t * 16u + (uint32_t)j]; sum += v[j]; }
-    uint32_t inc = sum;
-    for (int o = 1; o < 64; o <<= 1) { const uint32_t x = __shfl_up(inc, o, 64); if (lane >= (uint32_t)o) inc += x; }
-    if (lane == 63u) s_w[w] = inc;
-    __syncthreads();
-    uint32_t run = inc - sum;
-    for (uint32_t x = 0; x < w; ++x) run += s_w[x];
-#pragma unroll
-    for (int j = 0; j < 16; ++j) { s_v[t * 16u + (uint32_t)j] = run; run += v[j]; }
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < TSCAN / 256; ++j) { const uint32_t i = base + (uint32_t)j * 256u + t; if (i < n) a[i] = s_v[(uint32_t)j * 256u + t]; }
-    if (t == 255u) part[(q ? parts_p : 0u) + blockIdx.x] = run;
-}
-__global__ __launch_bounds__(256) void tile_scan_add_kernel(uint32_t* __restrict__ tiles_p, uint32_t np, uint32_t* __restrict__ tiles_q, uint32_t nq, const uint32_t* __restrict__ part,
-                                                            uint32_t parts_p) {
-    __shared__ uint32_t s_w[4];
-    const bool q = blockIdx.y == 1;
-    uint32_t* a = q ? tiles_q : tiles_p;
-    const uint32_t n = q ? nq : np;
-    const uint32_t base = blockIdx.x * TSCAN;
-    if (base >= n || blockIdx.x == 0) return;
-    const uint32_t* mine = part + (q ? parts_p : 0u);
-    uint32_t acc = 0;
-    for (uint32_t j = threadIdx.x; j < blockIdx.x; j += 256u) acc += mine[j];
-    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
-    if ((threadIdx.x & 63u) == 0u) s_w[threadIdx.x >> 6] = acc;
-    __syncthreads();
-    const uint32_t off = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-#pragma unroll
-    for (int j = 0; j < TSCAN / 256; ++j) { const uint32_t i = base + (uint32_t)j * 256u + threadIdx.x; if (i < n) a[i] += off; }
-}
-
-// Where every base's stretch begins and ends in the reduced lists (the lists are base-major, so that is the number of
-// survivors in front of the stretch's old bounds: the offset of the tile a bound falls into plus the survivors of that
-// tile in front of it), patched into the base jobs and the offset arrays the join reads.  Workgroup (b, list).
-template <class KeyT>
-__global__ __launch_bounds__(256) void survivors_base_offsets_kernel(const KeyT* __restrict__ pkeys, uint32_t nP, const uint32_t* __restrict__ occ_q,
-                                                                     const uint32_t* __restrict__ tiles_p, const KeyT* __restrict__ qkeys, uint32_t nQ,
-                                                                     const uint32_t* __restrict__ occ_p, const uint32_t* __restrict__ tiles_q, int nB,
-                                                                     BaseJob* __restrict__ jobs, uint32_t* __restrict__ p_off, uint32_t* __restrict__ q_off,
-                                                                     const PlanOut* __restrict__ po) {
-    __shared__ uint32_t s_w[2][4];
-    const int b = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const bool q = blockIdx.y == 1;
-    // po != NULL: nP / nQ are the CAPACITIES the key buffers and the tile arrays were sized by, the base jobs carry the PLANNED
-    // stretches.  A plan beyond a capacity is redone by the host with exact sizes (count_pass returns 1 at its read-back), so this
-    // launch has nothing to deliver -- and must not follow planned offsets past the gathered keys and the scanned tiles (the
-    // unguarded form of round 4 read keys[e] beyond d_pk_raw / d_qk_raw and used what it found there as an occupancy index, up to
-    // 512 MB past the table).  The test is uniform over the grid: either every workgroup works or none does.
-    if (po && (po->overflow || po->totP > (unsigned long long)nP || po->totQ > (unsigned long long)nQ)) return;
-    const KeyT* keys = q ? qkeys : pkeys;
-    const uint32_t* other = q ? occ_p : occ_q;
-    const uint32_t* tiles = q ? tiles_q : tiles_p;
-    const uint32_t cap = q ? nQ : nP;
-    uint32_t r0 = q ? jobs[b].q_off : jobs[b].p_off, r1 = r0 + (q ? jobs[b].q_len : jobs[b].p_len);
-    r0 = min(r0, cap); r1 = min(max(r1, r0), cap);      // (belt and braces: tiles[] holds cap / SURV_TILE + 1 entries, keys[] cap)
-    uint32_t got[2];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const uint32_t r = h ? r1 : r0, t0 = (r / SURV_TILE) * SURV_TILE;
-        uint32_t cnt = 0;
-        for (uint32_t e = t0 + threadIdx.x; e < r; e += 256) cnt += occ_test(other, keys[e]) ? 1u : 0u;
-        for (int d = 32; d; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
-        if (lane == 0) s_w[h][w] = cnt;
-        got[h] = tiles[r / SURV_TILE];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const uint32_t n0 = got[0] + s_w[0][0] + s_w[0][1] + s_w[0][2] + s_w[0][3], n1 = got[1] + s_w[1][0] + s_w[1][1] + s_w[1][2] + s_w[1][3];
-        if (q) { jobs[b].q_off = n0; jobs[b].q_len = n1 - n0; q_off[b] = n0; if (b == nB - 1) q_off[nB] = n1; }
-        else   { jobs[b].p_off = n0; jobs[b].p_len = n1 - n0; p_off[b] = n0; if (b == nB - 1) { p_off[nB] = n1; q_off[nB + 1] = n1; } }   // q_off[nB + 1]: P's total rides along with the Q offsets
-    }
-}
-
-// the survivors of a tile, in order, behind the tile's offset: one WAVEFRONT per tile (four tiles per workgroup), no LDS, no barrier -- the
-// tile's 16 ballots arrive as one 128-byte load and are handed out through scalar registers, the 16 rows of the survivors' keys and pairs
-// are requested together (the round-4 form: one workgroup per tile, four rows per thread, 75 000 workgroups for a 40-trial piece)
-template <class KeyT>
-__device__ __forceinline__ void survivors_compact_body(const KeyT* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t n,
-                                                       const unsigned long long* __restrict__ alive_bits, const uint32_t* __restrict__ tile_off,
-                                                       KeyT* __restrict__ okeys, uint32_t* __restrict__ ovals, const PlanOut* __restrict__ po, int is_q) {
-    if (po) { if (po->overflow) return; const unsigned long long t = is_q ? po->totQ : po->totP; n = t < (unsigned long long)n ? (uint32_t)t : n; }
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const uint32_t tile = blockIdx.x * 4u + w;
-    if ((unsigned long long)tile * SURV_TILE >= (unsigned long long)n) return;      // (wave-uniform)
-    const unsigned long long mine = lane < (uint32_t)SURV_ROWS ? alive_bits[(size_t)tile * SURV_ROWS + lane] : 0ull;   // the count pass's ballots
-    uint32_t base = tile_off[tile];
-    const uint32_t e0 = tile * SURV_TILE + lane;
-    KeyT key[SURV_ROWS];
-    uint32_t val[SURV_ROWS];
-    unsigned long long bm[SURV_ROWS];
-#pragma unroll
-    for (int k = 0; k < SURV_ROWS; ++k) {
-        const uint32_t lo = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)mine, k), hi = (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)(mine >> 32), k);
-        bm[k] = ((unsigned long long)hi << 32) | lo;
-        key[k] = (KeyT)0; val[k] = 0u;
-        if ((bm[k] >> lane) & 1ull) { key[k] = keys[e0 + (uint32_t)k * 64u]; val[k] = vals[e0 + (uint32_t)k * 64u]; }       // survivors only (a set bit is an entry below n)
-    }
-#pragma unroll
-    for (int k = 0; k < SURV_ROWS; ++k) {
-        const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(bm[k] >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bm[k], 0u));
-        if ((bm[k] >> lane) & 1ull) { okeys[base + rank] = key[k]; ovals[base + rank] = val[k]; }
-        base += (uint32_t)__popcll(bm[k]);
-    }
-}
-template <class KeyT>
-__global__ __launch_bounds__(256) void survivors_compact_kernel(const KeyT* __restrict__ keys, const uint32_t* __restrict__ vals, uint32_t n,
-                                                                const unsigned long long* __restrict__ alive_bits, const uint32_t* __restrict__ tile_off,
-                                                                KeyT* __restrict__ okeys, uint32_t* __restrict__ ovals, const PlanOut* __restrict__ po, int is_q) {
-    survivors_compact_body<KeyT>(keys, vals, n, alive_bits, tile_off, okeys, ovals, po, is_q);
-}
-// Both lists in one launch, into ONE list: P's survivors, then Q's right behind them (q_off[nB + 1] = P's total, written by
-// survivors_base_offsets_kernel) -- so that ONE segmented sort over 2 nB segments sorts both (blockIdx.y == 2: its segment offsets, P's bases then
-// Q's shifted by P's total).
-template <class KeyT>
-__global__ __launch_bounds__(256) void survivors_compact_dual_kernel(SurvSide<KeyT> P, SurvSide<KeyT> Q, const PlanOut* __restrict__ po, const uint32_t* __restrict__ p_off,
-                                                                     const uint32_t* __restrict__ q_off, int nB, uint32_t* __restrict__ comb_off) {
-    // (a plan beyond the capacities is redone by the host: survivors_base_offsets_kernel wrote nothing then, q_off[nB + 1] is not P's total)
-    if (po && (po->overflow || po->totP > (unsigned long long)P.n || po->totQ > (unsigned long long)Q.n)) return;
-    if (blockIdx.y == 2) {
-        const uint32_t totP = q_off[nB + 1];
-        for (uint32_t i = blockIdx.x * 256u + threadIdx.x; i <= 2u * (uint32_t)nB; i += gridDim.x * 256u) comb_off[i] = i < (uint32_t)nB ? p_off[i] : totP + q_off[i - (uint32_t)nB];
-        return;
-    }
-    const bool q = blockIdx.y == 1;                                // (ONE inlined body: two of them under an if / else took 248 VGPRs)
-    const uint32_t shift = q ? q_off[nB + 1] : 0u;
-    survivors_compact_body<KeyT>(q ? Q.keys : P.keys, q ? Q.vals : P.vals, q ? Q.n : P.n, q ? Q.alive : P.alive, q ? Q.tiles : P.tiles, (q ? Q.okeys : P.okeys) + shift,
-                                 (q ? Q.ovals : P.ovals) + shift, po, q ? 1 : 0);
 }
 
 // Zero fill as an ordinary kernel on the context's stream
@@ -1097,7 +654,7 @@ struct CongruentState {
     Arena arena_tmp;     // temporaries of the calls that produce quads afterwards; reset by each of them
     bool valid = false;  // a count pass has completed and its buffers are intact
     // host work of the current call that only the join needs (the cone records of a batch's thousands of bases: three libm calls each,
-    // 0.2 ms for 6 400 bases), done by count_pass while the device gathers instead of before anything is enqueued
+    // 0.2 ms for 6 400 bases), done by the count pass while the device gathers instead of before anything is enqueued
     std::function<int()> deferred;
     // quads of the small bases, materialised ahead of the picks that refer to them (stocs_internal_prepare_small)
     bool small_ready = false, small_any = false;
@@ -1267,13 +824,9 @@ static void fill_cone_table(BaseJob* J) {
     J->nb = (nb > STOCS_MAX_CONE || !(alpha == alpha)) ? 0 : (int)nb;  // nb <= 56 for any alpha in [0, pi]; NaN alpha -> no samples
 }
 
-static double now_s() {
-    struct timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec + 1e-9 * ts.tv_nsec;
-}
+// STOCS_DEBUG_TIMING: synchronised steps on stderr (tools read them)
 #define STOCS_TICK(label)                                                                          \
-    if (dbg) { (void)hipStreamSynchronize(c->stream); const double t_ = now_s(); fprintf(stderr, "[stocs congruent] %-18s %8.3f ms\n", label, (t_ - tprev) * 1e3); tprev = t_; }
+    if (dbg) { (void)hipStreamSynchronize(c->stream); const double t_ = CallTiming::now_s(); fprintf(stderr, "[stocs congruent] %-18s %8.3f ms\n", label, (t_ - tprev) * 1e3); tprev = t_; }
 
 // device part of stocs_find_congruent_all for one key width
 // The stable sort of a pair list by (base, cell).  The lists are base-major already (the gather, and the compaction of the survivors, emit
@@ -1360,560 +913,743 @@ struct CongruentSwitches {
     }
 };
 
-// the pair lists of one count pass as gathered and, when they are reduced, their survivors (one buffer for both lists in the one-stream form)
-template <class KeyT>
-struct PassLists { DevBuf<KeyT> pk_raw, qk_raw, pk_c, qk_c; DevBuf<uint32_t> pv_raw, qv_raw, pv_c, qv_c, comb_off; };
-
-// The reduced form's first stage: gather -> occupancy -> survivor counts -> tile scan -> compaction of both lists, and the read-back of
-// the survivors' offsets and totals (S->totP, S->totQ, S->h_qoff).  S->no_quads when no cell is shared; *outgrown when the plan turned
-// out larger than the capacities (d_po != NULL): the streams are idle then.
-template <class KeyT>
-static int reduce_lists(stocs_ctx* c, CongruentState* S, const PlanDev& plan, PassLists<KeyT>& L, hipStream_t sq, bool one_stream, uint32_t lds_words, bool dbg,
-                        const PlanOut* d_po, const PlanOut* po_pin, bool* outgrown) {
-    const int nB = S->nB;
-    const size_t totP0 = S->totP, totQ0 = S->totQ;
-    hipStream_t st = c->stream;
-    const int s0 = 0, s1 = sq != st ? 1 : 0;
-    const bool dev_clock = c->device_clock != 0;
-    const long long cell_limit = S->use_table ? S->NC : ((long long)1 << 31);
-    const PpfIndex& ix = c->index;
-    StreamAudit& AU = c->audit;
-    int rc;
-    // one zeroed block: occupancy of P | occupancy of Q | P tile counts (+ total) | Q tile counts (+ total)
-    const size_t W = (size_t)((((unsigned long long)nB << S->cell_bits) + 31) >> 5) + 1;   // words of one occupancy table: one bit per (base, cell) value
-    const uint32_t ntp = (uint32_t)((totP0 + SURV_TILE - 1) / SURV_TILE), ntq = (uint32_t)((totQ0 + SURV_TILE - 1) / SURV_TILE);
-    const size_t o_tp = 2 * W, o_tq = o_tp + ntp + 1, n_words = o_tq + ntq + 1;
-    DevBuf<uint32_t> d_surv;
-    if ((rc = d_surv.alloc(n_words))) return rc;
-    DevBuf<unsigned long long> d_bits_p, d_bits_q;   // one bit per gathered entry: survives (written by the count pass, read by the compaction)
-    if ((rc = d_bits_p.alloc((size_t)std::max(ntp, 1u) * (SURV_TILE / 64))) || (rc = d_bits_q.alloc((size_t)std::max(ntq, 1u) * (SURV_TILE / 64)))) return rc;
-    uint32_t* occ_p = d_surv.p;
-    uint32_t* occ_q = d_surv.p + W;
-    hipLaunchKernelGGL(zero_u32_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, st, d_surv.p, n_words, (uint32_t*)NULL);
-    const uint32_t* tiles_p = d_surv.p + o_tp; const uint32_t* tiles_q = d_surv.p + o_tq;
-    AU.use(s0, occ_p, true, "occupancy of P", "zero fill"); AU.use(s0, occ_q, true, "occupancy of Q", "zero fill");
-    AU.use(s0, tiles_p, true, "tile counts of P", "zero fill"); AU.use(s0, tiles_q, true, "tile counts of Q", "zero fill");
-    AU.use(s0, plan.jobs, true, "base jobs", "plan kernels"); AU.use(s0, plan.psegs, true, "P segments", "plan kernels"); AU.use(s0, plan.qsegs, true, "Q segments", "plan kernels");
-    AU.use(s0, plan.q_off, true, "Q offsets per base", "plan kernels");
-    if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[6], st));
-    if (sq != st) {
-        STOCS_HIP_CHECK(hipEventRecord(c->ev_fork, st));          // the plan upload and the zero fill are on st
-        STOCS_HIP_CHECK(hipStreamWaitEvent(sq, c->ev_fork, 0));
-        AU.record(c->ev_fork, s0); AU.wait(s1, c->ev_fork);
+// ---- the form of a pass ----
+// The key layout of a call: a pure function of the number of bases, the model size, the position grid and the switches.
+struct KeyLayout { long long NC; bool use_table; int base_bits, id_bits, cell_bits; bool wide, reduce; };
+static KeyLayout key_layout(int nB, int nM, int egSize, const CongruentSwitches& sw) {
+    KeyLayout K;
+    K.NC = (long long)egSize * egSize * egSize;
+    // (8 bytes of run table + 2 of occupancy per (base, cell): up to 2.7 GB -- a trial batch brings thousands of bases, and 288 GB are there for it)
+    K.use_table = K.NC > 0 && K.NC * (long long)nB <= (long long)256 * 1024 * 1024;
+    K.base_bits = 1; K.id_bits = 1; K.cell_bits = 1;
+    while ((1 << K.base_bits) < nB) K.base_bits++;
+    while ((1 << K.id_bits) < nM) K.id_bits++;
+    K.id_bits = std::max(K.id_bits, sw.min_id_bits);
+    {   // cells 0 .. limit-1 plus the all-ones "no cell" value
+        const unsigned long long lim = K.use_table ? (unsigned long long)K.NC : ((unsigned long long)1 << 31);
+        while (K.cell_bits < 40 && (((unsigned long long)1 << K.cell_bits) - 1ull) < lim) K.cell_bits++;
     }
-    if (one_stream) {
-        const GatherSide<KeyT> gp = {plan.psegs, plan.n_pseg, (uint32_t)totP0, L.pk_raw.p, L.pv_raw.p, occ_p}, gq = {plan.qsegs, plan.n_qseg, (uint32_t)totQ0, L.qk_raw.p, L.qv_raw.p, occ_q};
-        hipLaunchKernelGGL(gather_key_dual_kernel<KeyT>, dim3(std::max(gather_grid(totP0), gather_grid(totQ0)), 2), dim3(256), lds_words * 4, st, ix.d_pairs, gp, gq,
-                           (const BaseJob*)S->d_jobs.p, (const float4*)c->d_munit, S->cell_bits, cell_limit, d_po, lds_words, (uint32_t)nB);
-    } else
-    hipLaunchKernelGGL(gather_key_kernel<KeyT>, dim3(gather_grid(totQ0)), dim3(256), lds_words * 4, sq, ix.d_pairs, plan.qsegs, plan.n_qseg, (uint32_t)totQ0,
-                       S->d_jobs.p, c->d_munit, 1, S->cell_bits, cell_limit, L.qk_raw.p, L.qv_raw.p, occ_q, d_po, lds_words, (uint32_t)nB);
-    AU.use(s1, plan.qsegs, false, "Q segments", "gather Q"); AU.use(s1, plan.jobs, false, "base jobs", "gather Q");
-    AU.use(s1, L.qk_raw.p, true, "gathered Q keys", "gather Q"); AU.use(s1, L.qv_raw.p, true, "gathered Q pairs", "gather Q"); AU.use(s1, occ_q, true, "occupancy of Q", "gather Q");
-    if (sq != st || dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[8], sq));             // Q's cells are marked
-    AU.record(c->ev_t[8], s1);
-    if (!one_stream)
-    hipLaunchKernelGGL(gather_key_kernel<KeyT>, dim3(gather_grid(totP0)), dim3(256), lds_words * 4, st, ix.d_pairs, plan.psegs, plan.n_pseg, (uint32_t)totP0,
-                       S->d_jobs.p, c->d_munit, 0, S->cell_bits, cell_limit, L.pk_raw.p, L.pv_raw.p, occ_p, d_po, lds_words, (uint32_t)nB);
-    AU.use(s0, plan.psegs, false, "P segments", "gather P"); AU.use(s0, plan.jobs, false, "base jobs", "gather P");
-    AU.use(s0, L.pk_raw.p, true, "gathered P keys", "gather P"); AU.use(s0, L.pv_raw.p, true, "gathered P pairs", "gather P"); AU.use(s0, occ_p, true, "occupancy of P", "gather P");
-    if (sq != st || dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[9], st));             // P's cells are marked
-    AU.record(c->ev_t[9], s0);
-    if (sq != st) { STOCS_HIP_CHECK(hipStreamWaitEvent(sq, c->ev_t[9], 0)); STOCS_HIP_CHECK(hipStreamWaitEvent(st, c->ev_t[8], 0)); AU.wait(s1, c->ev_t[9]); AU.wait(s0, c->ev_t[8]); }
-    // (one stream: the compacted lists are ONE buffer, allocated here so that the launch below can name it)
-    if (one_stream) { if ((rc = L.pk_c.alloc(totP0 + totQ0)) || (rc = L.pv_c.alloc(totP0 + totQ0)) || (rc = L.comb_off.alloc(2 * (size_t)nB + 1))) return rc; }
-    const SurvSide<KeyT> sp = {(const KeyT*)L.pk_raw.p, (const uint32_t*)L.pv_raw.p, (uint32_t)totP0, (const uint32_t*)occ_q, d_surv.p + o_tp, d_bits_p.p, L.pk_c.p, L.pv_c.p},
-                         sqd = {(const KeyT*)L.qk_raw.p, (const uint32_t*)L.qv_raw.p, (uint32_t)totQ0, (const uint32_t*)occ_p, d_surv.p + o_tq, d_bits_q.p, L.pk_c.p, L.pv_c.p};
-    if (one_stream)
-        hipLaunchKernelGGL(survivors_count_dual_kernel<KeyT>, dim3(std::max(1u, std::min((std::max(ntp, ntq) + 3u) / 4u, GATHER_MAX_WGS)), 2), dim3(256), lds_words * 4, st, sp, sqd, d_po,
-                           lds_words, S->cell_bits);
-    else
-    hipLaunchKernelGGL(survivors_count_kernel<KeyT>, dim3(std::max(1u, std::min((ntq + 3u) / 4u, GATHER_MAX_WGS))), dim3(256), lds_words * 4, sq, (const KeyT*)L.qk_raw.p, (uint32_t)totQ0, (const uint32_t*)occ_p, d_surv.p + o_tq, d_po, 1, d_bits_q.p, lds_words, S->cell_bits);
-    AU.use(s1, L.qk_raw.p, false, "gathered Q keys", "survivors count Q"); AU.use(s1, occ_p, false, "occupancy of P", "survivors count Q"); AU.use(s1, tiles_q, true, "tile counts of Q", "survivors count Q"); AU.use(s1, d_bits_q.p, true, "alive bits of Q", "survivors count Q");
-    if (sq != st) { STOCS_HIP_CHECK(hipEventRecord(c->ev_join, sq)); AU.record(c->ev_join, s1); }
-    if (!one_stream)
-    hipLaunchKernelGGL(survivors_count_kernel<KeyT>, dim3(std::max(1u, std::min((ntp + 3u) / 4u, GATHER_MAX_WGS))), dim3(256), lds_words * 4, st, (const KeyT*)L.pk_raw.p, (uint32_t)totP0, (const uint32_t*)occ_q, d_surv.p + o_tp, d_po, 0, d_bits_p.p, lds_words, S->cell_bits);
-    AU.use(s0, L.pk_raw.p, false, "gathered P keys", "survivors count P"); AU.use(s0, occ_q, false, "occupancy of Q", "survivors count P"); AU.use(s0, tiles_p, true, "tile counts of P", "survivors count P"); AU.use(s0, d_bits_p.p, true, "alive bits of P", "survivors count P");
-    if (sq != st) { STOCS_HIP_CHECK(hipStreamWaitEvent(st, c->ev_join, 0)); AU.wait(s0, c->ev_join); }
-    AU.use(s0, tiles_p, true, "tile counts of P", "tile scan"); AU.use(s0, tiles_q, true, "tile counts of Q", "tile scan");
-    AU.use(s0, L.qk_raw.p, false, "gathered Q keys", "base offsets"); AU.use(s0, occ_p, false, "occupancy of P", "base offsets"); AU.use(s0, plan.jobs, true, "base jobs", "base offsets");
-    AU.use(s0, plan.q_off, true, "Q offsets per base", "base offsets");
-    if (std::max(ntp, ntq) + 1u <= 2u * TSCAN) {
-        hipLaunchKernelGGL(survivors_scan_kernel, dim3(2), dim3(1024), 0, st, d_surv.p + o_tp, ntp, d_surv.p + o_tq, ntq);
-    } else {      // long lists (trial batches): the scan on many workgroups
-        const uint32_t pp = (ntp + 1u + TSCAN - 1u) / TSCAN, pq = (ntq + 1u + TSCAN - 1u) / TSCAN;
-        DevBuf<uint32_t> d_part;
-        if ((rc = d_part.alloc((size_t)pp + pq))) return rc;
-        hipLaunchKernelGGL(tile_scan_local_kernel, dim3(std::max(pp, pq), 2), dim3(256), 0, st, d_surv.p + o_tp, ntp + 1u, d_surv.p + o_tq, ntq + 1u, d_part.p, pp);
-        hipLaunchKernelGGL(tile_scan_add_kernel, dim3(std::max(pp, pq), 2), dim3(256), 0, st, d_surv.p + o_tp, ntp + 1u, d_surv.p + o_tq, ntq + 1u, (const uint32_t*)d_part.p, pp);
-    }
-    hipLaunchKernelGGL(survivors_base_offsets_kernel<KeyT>, dim3((unsigned)nB, 2), dim3(256), 0, st, (const KeyT*)L.pk_raw.p, (uint32_t)totP0, (const uint32_t*)occ_q,
-                       (const uint32_t*)(d_surv.p + o_tp), (const KeyT*)L.qk_raw.p, (uint32_t)totQ0, (const uint32_t*)occ_p, (const uint32_t*)(d_surv.p + o_tq), nB,
-                       S->d_jobs.p, plan.p_off, plan.q_off, d_po);
-    STOCS_HIP_CHECK(hipGetLastError());
-    // the host sizes the sorts and the join with the survivors' totals and lays the materialise blocks out with their Q offsets
-    uint32_t* qoff_pin = (uint32_t*)((char*)c->h_pin + PIN_VAR + 8 * ((size_t)nB + 1));
-    STOCS_HIP_CHECK(hipMemcpyAsync(qoff_pin, plan.q_off, 4 * ((size_t)nB + 2), hipMemcpyDeviceToHost, st));   // Q offsets, Q total, P total
-    STOCS_HIP_CHECK(hipEventRecord(c->ev_t[7], st));
-    AU.record(c->ev_t[7], s0);
-    // the survivors move behind their tiles' offsets while the host waits for the totals: the compacted lists are sized by
-    // the gathered ones here (the totals are what the wait is for)
-    if (!one_stream) { if ((rc = L.pk_c.alloc(totP0)) || (rc = L.pv_c.alloc(totP0)) || (rc = L.qk_c.alloc(totQ0)) || (rc = L.qv_c.alloc(totQ0))) return rc; }
-    if (sq != st) {
-        STOCS_HIP_CHECK(hipEventRecord(c->ev_fork, st));          // tile offsets are scanned on st
-        STOCS_HIP_CHECK(hipStreamWaitEvent(sq, c->ev_fork, 0));
-        AU.record(c->ev_fork, s0); AU.wait(s1, c->ev_fork);
-    }
-    AU.use(s1, L.qk_raw.p, false, "gathered Q keys", "compact Q"); AU.use(s1, L.qv_raw.p, false, "gathered Q pairs", "compact Q"); AU.use(s1, d_bits_q.p, false, "alive bits of Q", "compact Q");
-    AU.use(s1, tiles_q, false, "tile counts of Q", "compact Q"); AU.use(s1, L.qk_c.p, true, "surviving Q keys", "compact Q"); AU.use(s1, L.qv_c.p, true, "surviving Q pairs", "compact Q");
-    AU.use(s0, L.pk_raw.p, false, "gathered P keys", "compact P"); AU.use(s0, L.pv_raw.p, false, "gathered P pairs", "compact P"); AU.use(s0, d_bits_p.p, false, "alive bits of P", "compact P");
-    AU.use(s0, tiles_p, false, "tile counts of P", "compact P"); AU.use(s0, L.pk_c.p, true, "surviving P keys", "compact P"); AU.use(s0, L.pv_c.p, true, "surviving P pairs", "compact P");
-    if (one_stream)
-        hipLaunchKernelGGL(survivors_compact_dual_kernel<KeyT>, dim3(std::max(1u, (std::max(ntp, ntq) + 3u) / 4u), 3), dim3(256), 0, st, sp, sqd, d_po, (const uint32_t*)plan.p_off,
-                           (const uint32_t*)plan.q_off, nB, L.comb_off.p);
-    else {
-    hipLaunchKernelGGL(survivors_compact_kernel<KeyT>, dim3((ntq + 3u) / 4u), dim3(256), 0, sq, (const KeyT*)L.qk_raw.p, (const uint32_t*)L.qv_raw.p, (uint32_t)totQ0,
-                       (const unsigned long long*)d_bits_q.p, (const uint32_t*)(d_surv.p + o_tq), L.qk_c.p, L.qv_c.p, d_po, 1);
-    hipLaunchKernelGGL(survivors_compact_kernel<KeyT>, dim3((ntp + 3u) / 4u), dim3(256), 0, st, (const KeyT*)L.pk_raw.p, (const uint32_t*)L.pv_raw.p, (uint32_t)totP0,
-                       (const unsigned long long*)d_bits_p.p, (const uint32_t*)(d_surv.p + o_tp), L.pk_c.p, L.pv_c.p, d_po, 0);
-    }
-    STOCS_HIP_CHECK(hipGetLastError());
-    c->timing[TIMING_CONGRUENT].lap("enqueue gather + occupancy + survivor counts");
-    if (S->deferred) { const int rd = S->deferred(); S->deferred = nullptr; if (rd) return rd; c->timing[TIMING_CONGRUENT].lap("host: cone records of the bases (while the device gathers)"); }
-    STOCS_HIP_CHECK(hipEventSynchronize(c->ev_t[7]));   // the read-back, not the compaction behind it
-    AU.host_sync_event(c->ev_t[7]);
-    c->timing[TIMING_CONGRUENT].lap("wait for the device (survivors)");
-    if (po_pin) {   // the plan's own totals came with this read-back: were the capacities enough?
-        if (po_pin->overflow || po_pin->totP > (unsigned long long)totP0 || po_pin->totQ > (unsigned long long)totQ0) {
-            STOCS_HIP_CHECK(hipStreamSynchronize(st));            // the compaction behind the read-back: nothing may still touch the arena
-            if (sq != st) STOCS_HIP_CHECK(hipStreamSynchronize(sq));
-            AU.host_sync(s0); AU.host_sync(s1);
-            *outgrown = true;
-            return STOCS_OK;
-        }
-    }
-    const size_t totP = qoff_pin[nB + 1], totQ = qoff_pin[nB];
-    memcpy(S->h_qoff.data(), qoff_pin, 4 * ((size_t)nB + 1));
-    if (dbg) fprintf(stderr, "[stocs congruent] survivors: P %zu of %zu, Q %zu of %zu\n", totP, totP0, totQ, totQ0);
-    S->totP = (uint32_t)totP; S->totQ = (uint32_t)totQ;
-    if (totP == 0 || totQ == 0) S->no_quads = true;   // no cell is shared: no quads (quad_off is all zero already)
-    return STOCS_OK;
+    K.wide = K.base_bits + K.cell_bits > 32 || sw.wide_keys;
+    // both pair lists are reduced to the entries with a partner cell when one byte per (base, cell) is a small table (CountPass::reduce_lists)
+    K.reduce = K.use_table && ((unsigned long long)nB << K.cell_bits) <= (1ull << 29) && !sw.keep_all;
+    return K;
 }
 
-// The count pass over the planned lists: (reduce_lists,) sorts, P records and run table, join count, scan, per-base quad offsets.
-// d_po != NULL ("optimistic"): the host has NOT read the plan -- S->totP / S->totQ are capacities the buffers and launches are
-// sized by, the kernels read the planned totals from *d_po, and the plan's totals arrive with the survivors' in ONE read-back
-// (po_pin).  *outgrown (not an error) when the plan turned out larger than the capacities: the caller redoes the pass with the
-// exact sizes it now knows.
-template <class KeyT>
-static int count_pass(stocs_ctx* c, CongruentState* S, const PlanDev& plan, const CongruentSwitches& sw, double& tprev, const PlanOut* d_po, const PlanOut* po_pin,
-                      bool* outgrown) {
-    *outgrown = false;
-    const bool dbg = sw.debug_timing;
-    const int nB = S->nB;
-    const size_t totP0 = S->totP, totQ0 = S->totQ;   // the gathered lists as planned (d_po: their capacities)
-    size_t totP = totP0, totQ = totQ0;               // the lists that are sorted and joined (the survivors, when the lists are reduced)
-    hipStream_t st = c->stream;
-    // The device's own clock of the kernel groups (HIP events between them, reported by stocs_last_call_timing as "device: ..." steps) is
-    // OPT-IN since round 5b (stocs_set_option "device_clock" / STOCS_DEVICE_CLOCK=1): on this runtime every event recorded between two kernels
-    // of a stream leaves the queue idle for ~5 us, and the nine of a call were 45 us of a Cm trial's 600.  The host's steps between the call's
-    // own synchronisation points are always recorded.
-    const bool dev_clock = c->device_clock != 0;
+// The form ONE count pass takes, decided here and nowhere else: from the key layout, the switches and the list sizes of THIS pass (nP, nQ:
+// capacities when the pass is optimistic, exact sizes otherwise -- so the first pass and the redo of an outgrown plan may differ in
+// one_stream).  It also owns the strings that name the form in the call's timing record.
+struct PassForm {
+    bool wide, use_table, reduce, one_stream;
+    bool optimistic;              // sized by capacities: the kernels read the planned totals from the device (d_po)
+    uint32_t lds_words;           // one base's occupancy bits in LDS (gather: collected there; count: the other list's, tested there) while they fit 32 KB
+    unsigned end_bit, end_bit_p;  // bits the Q sort and the P sort look at
+    hipStream_t st, sq;           // P's stream (the context's) and Q's (the auxiliary one when the pass has two streams)
+    int s0, s1;                   // their indices in the stream audit
+    bool two_streams() const { return sq != st; }
+    int audit_stream(int side) const { return side ? s1 : s0; }
+    const char* reserve_label() const { return !use_table ? "arena reserve (no run table, 64-bit keys)" : (wide ? "arena reserve (64-bit keys)" : "arena reserve"); }
+    const char* enqueue_label() const { return reduce ? "enqueue compact/sort/records/join/scan" : "enqueue gather/sort/records/join/scan"; }
+    const char* clock_label(const char* all, const char* red, const char* one) const { return one_stream ? one : (reduce ? red : all); }   // (NULL: not a group of this form)
+};
+static PassForm pass_form(const stocs_ctx* c, const KeyLayout& K, const CongruentSwitches& sw, int nB, size_t nP, size_t nQ, bool optimistic) {
+    PassForm F;
+    F.wide = K.wide; F.use_table = K.use_table; F.reduce = K.reduce; F.optimistic = optimistic;
     // ONE stream (round 5b) for the reduced 32-bit form: P and Q go through every step in the SAME launch (blockIdx.y), the survivors of both
     // land in one list and ONE segmented sort over 2 nB segments sorts it.  The two-stream form of rounds 3-5a (P on the context's stream, Q on
     // the auxiliary one) paid ~11 us per event edge between the streams, five of them in a trial -- a tenth of a Cm trial's congruent phase;
     // it stays for 64-bit keys, unreduced lists and rocPRIM's sort, and under STOCS_CONGRUENT_TWO_STREAMS for A/B.
     // Lists beyond 10^8 entries -- the pieces of a trial batch at the metric size -- keep the two streams: there the edges are nothing and the
     // overlap of unlike kernels (P's records next to Q's sort) is worth 2 % (64 Cm trials: 2 040 against 1 985 trials/s).
-    const bool one_stream = S->reduce && sizeof(KeyT) == 4 && cong_sort_own() && (totP0 + totQ0) < ((size_t)1 << 30) && nB < (1 << 22) && sw.force_streams != 2 &&
-                            (sw.force_streams == 1 || totP0 + totQ0 < (size_t)100000000);
-    hipStream_t sq = (c->aux_stream && !one_stream) ? c->aux_stream : st;
-    PassLists<KeyT> L;
-    DevBuf<char> d_tmp;
-    int rc;
-    if ((rc = L.pk_raw.alloc(totP0)) || (rc = L.pv_raw.alloc(totP0)) || (rc = L.qk_raw.alloc(totQ0)) || (rc = L.qv_raw.alloc(totQ0))) return rc;
-    S->d_jobs.p = plan.jobs;
-    if (S->deferred && !S->reduce) { const int rd = S->deferred(); S->deferred = nullptr; if (rd) return rd; c->timing[TIMING_CONGRUENT].lap("host: cone records of the bases (no survivors pass to hide them behind)"); }
-    S->d_qoff.p = plan.q_off;
-    S->d_bids.p = plan.bids;
-    S->d_err.p = plan.err;
-    const PpfIndex& ix = c->index;
-    StreamAudit& AU = c->audit;                       // STOCS_DEBUG_STREAMS: every two-stream step below says what it reads and writes
-    const int s0 = 0, s1 = sq != st ? 1 : 0;
-    const long long cell_limit = S->use_table ? S->NC : ((long long)1 << 31);
-    const unsigned end_bit = (unsigned)(S->cell_bits + S->base_bits);
-    // one base's bits in LDS (gather: collected there; count: the other list's, tested there) while they fit 32 KB
-    const uint32_t lds_words = (S->cell_bits >= 5 && S->cell_bits <= 18 && !sw.no_lds_bits) ? (1u << (S->cell_bits - 5)) : 0u;
-    const bool reduce = S->reduce;
-    const KeyT* pk_in = L.pk_raw.p; const uint32_t* pv_in = L.pv_raw.p;   // what the sorts read
-    const KeyT* qk_in = L.qk_raw.p; const uint32_t* qv_in = L.qv_raw.p;
-    if (reduce) {
-        if ((rc = reduce_lists<KeyT>(c, S, plan, L, sq, one_stream, lds_words, dbg, d_po, po_pin, outgrown)) || *outgrown || S->no_quads) return rc;
-        totP = S->totP; totQ = S->totQ;
-        pk_in = L.pk_c.p; pv_in = L.pv_c.p; qk_in = L.qk_c.p; qv_in = L.qv_c.p;
-        if (one_stream) { qk_in = L.pk_c.p + totP; qv_in = L.pv_c.p + totP; }   // (Q's survivors sit behind P's)
-    }
-    if (one_stream) {   // one sorted list: P's part, then Q's
-        if ((rc = S->d_pkeys.alloc((totP + totQ) * sizeof(KeyT))) || (rc = S->d_pvals.alloc(totP + totQ))) return rc;
-        S->d_qkeys.p = S->d_pkeys.p + totP * sizeof(KeyT); S->d_qvals.p = S->d_pvals.p + totP;
-    } else if ((rc = S->d_pkeys.alloc(totP * sizeof(KeyT))) || (rc = S->d_pvals.alloc(totP)) || (rc = S->d_qkeys.alloc(totQ * sizeof(KeyT))) || (rc = S->d_qvals.alloc(totQ)))
-        return rc;
-    if ((rc = S->d_prec.alloc(S->close_cells ? 1 : totP)) || (rc = S->d_pdc.alloc(((size_t)totP + 15) & ~(size_t)7)))
-        return rc;
-    // The P side (sort, records) and the Q side (sort) are independent until the join: the Q side runs on
-    // the context's auxiliary stream next to the P side (a radix pass of 7 M pairs moves ~1.8 TB/s: two of them share the chip)
-    size_t tb1 = 0, tb2 = 0;
+    F.one_stream = K.reduce && !K.wide && cong_sort_own() && (nP + nQ) < ((size_t)1 << 30) && nB < (1 << 22) && sw.force_streams != 2 &&
+                   (sw.force_streams == 1 || nP + nQ < (size_t)100000000);
+    F.st = c->stream;
+    F.sq = (c->aux_stream && !F.one_stream) ? c->aux_stream : c->stream;
+    F.s0 = 0; F.s1 = F.sq != F.st ? 1 : 0;
+    F.lds_words = (K.cell_bits >= 5 && K.cell_bits <= 18 && !sw.no_lds_bits) ? (1u << (K.cell_bits - 5)) : 0u;
+    F.end_bit = (unsigned)(K.cell_bits + K.base_bits);
     // P side with the run table: sorted by position cell ALONE.  The gather emits base after base and the sort is stable, so
     // inside a cell the entries stay grouped by base, in index order inside a base: the runs of (base, cell) are contiguous
     // all the same, the table finds them wherever they are, and 15 bits are two radix passes where 22 are three.
-    const unsigned end_bit_p = (S->use_table && !sw.p_fullsort) ? (unsigned)S->cell_bits : end_bit;
-    bool own_p = false, own_q = false;      // (decided per list: by its length per base)
-    if (one_stream) STOCS_HIP_CHECK(cong_sort(NULL, tb1, pk_in, (KeyT*)S->d_pkeys.p, pv_in, S->d_pvals.p, totP + totQ, (unsigned)S->cell_bits, end_bit_p, L.comb_off.p, 2 * nB, st, &own_p));
-    else {
-    STOCS_HIP_CHECK(cong_sort(NULL, tb1, pk_in, (KeyT*)S->d_pkeys.p, pv_in, S->d_pvals.p, totP, (unsigned)S->cell_bits, end_bit_p, plan.p_off, nB, st, &own_p));
-    STOCS_HIP_CHECK(cong_sort(NULL, tb2, qk_in, (KeyT*)S->d_qkeys.p, qv_in, S->d_qvals.p, totQ, (unsigned)S->cell_bits, end_bit, plan.q_off, nB, st, &own_q));
+    F.end_bit_p = (K.use_table && !sw.p_fullsort) ? (unsigned)K.cell_bits : F.end_bit;
+    return F;
+}
+
+// ---- the list kernels of a pass: one launch helper, one declaration ----
+enum ListKernel { LIST_GATHER, LIST_COUNT, LIST_COMPACT };
+// what the list kernels of one pass are given: the two records and the pass's constants
+template <class KeyT>
+struct ListPass {
+    ListSide<KeyT> side[2];
+    const uint32_t* pairs; const BaseJob* jobs; const float4* munit; int cell_bits; long long cell_limit; const PlanOut* d_po; uint32_t lds_words; int nB;
+    const uint32_t* p_off; const uint32_t* q_off; uint32_t* comb_off;   // the combined compaction: the lists' offsets per base, the segment offsets of the one sort
+};
+// the buffers of a list and its steps as the stream audit names them
+struct ListNames { const char *segs, *keys, *vals, *occ, *tiles, *alive, *okeys, *ovals, *gather, *count, *compact; };
+static const ListNames LIST_NAMES[2] = {
+    {"P segments", "gathered P keys", "gathered P pairs", "occupancy of P", "tile counts of P", "alive bits of P", "surviving P keys", "surviving P pairs",
+     "gather P", "survivors count P", "compact P"},
+    {"Q segments", "gathered Q keys", "gathered Q pairs", "occupancy of Q", "tile counts of Q", "alive bits of Q", "surviving Q keys", "surviving Q pairs",
+     "gather Q", "survivors count Q", "compact Q"}};
+
+// ONE launch of a list kernel for the lists side0 .. side0 + ny - 1 on the stream with audit index s, and what it reads and writes declared to
+// the stream audit from the records the kernel was given.  The grid is the largest any of its lists asks for (a workgroup beyond a list's
+// end leaves at once); both lists compacted in one launch go into ONE list (the third plane writes its segment offsets).
+template <class KeyT>
+static void launch_list_kernel(stocs_ctx* c, ListKernel k, const ListPass<KeyT>& A, int side0, int ny, int s) {
+    const ListSide<KeyT>&P = A.side[0], &Q = A.side[1];
+    hipStream_t stream = ctx_stream(c, s);
+    unsigned gx = 1u;
+    for (int y = side0; y < side0 + ny; ++y) {
+        const uint32_t groups = (uint32_t)((((size_t)A.side[y].n + SURV_TILE - 1) / SURV_TILE + 3) / 4);     // four tiles of survivors per workgroup and trip
+        gx = std::max(gx, k == LIST_GATHER ? gather_grid(A.side[y].n) : (k == LIST_COUNT ? std::min(groups, GATHER_MAX_WGS) : groups));
     }
-    DevBuf<char> d_tmp2;
-    if ((rc = d_tmp.alloc(tb1)) || (rc = d_tmp2.alloc(tb2))) return rc;
-    // device-side clock of the groups below (HIP events on the streams they run on; read after the call's closing
-    // synchronisation): a call that takes 70 ms instead of 1 then says which group of kernels it spent them in
-    if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[0], st));
-    if (sq != st) {
-        STOCS_HIP_CHECK(hipEventRecord(c->ev_fork, st));          // the upload above is on st
-        STOCS_HIP_CHECK(hipStreamWaitEvent(sq, c->ev_fork, 0));
-        AU.record(c->ev_fork, s0); AU.wait(s1, c->ev_fork);
+    const int combined = (k == LIST_COMPACT && ny == 2) ? 1 : 0;
+    switch (k) {
+    case LIST_GATHER:
+        hipLaunchKernelGGL(gather_key_kernel<KeyT>, dim3(gx, (unsigned)ny), dim3(256), A.lds_words * 4, stream, A.pairs, P, Q, side0, A.jobs, A.munit, A.cell_bits, A.cell_limit, A.d_po,
+                           A.lds_words, (uint32_t)A.nB);
+        break;
+    case LIST_COUNT:
+        hipLaunchKernelGGL(survivors_count_kernel<KeyT>, dim3(gx, (unsigned)ny), dim3(256), A.lds_words * 4, stream, P, Q, side0, A.d_po, A.lds_words, A.cell_bits);
+        break;
+    case LIST_COMPACT:
+        hipLaunchKernelGGL(survivors_compact_kernel<KeyT>, dim3(gx, (unsigned)(ny + combined)), dim3(256), 0, stream, P, Q, side0, combined, A.d_po, A.p_off, A.q_off, A.nB, A.comb_off);
+        break;
     }
-    // The P side first: it is the longer chain (sort + records: ~100 us at Cm against ~70 us of the Q sort), and whichever side is enqueued second
-    // starts ~25 us later -- the host needs that long for the first side's five launches (kernel trace of a trial, round 5)
-    if (!reduce)
-        hipLaunchKernelGGL(gather_key_kernel<KeyT>, dim3(gather_grid(totP)), dim3(256), 0, st, ix.d_pairs, plan.psegs, plan.n_pseg, (uint32_t)totP,
-                           S->d_jobs.p, c->d_munit, 0, S->cell_bits, cell_limit, L.pk_raw.p, L.pv_raw.p, (uint32_t*)NULL, (const PlanOut*)NULL, 0u, (uint32_t)nB);
-    STOCS_HIP_CHECK(hipGetLastError());
-    // one stable sort per list: (base, position cell); inside a cell the entries keep the index order of the gather
-    if (one_stream) STOCS_HIP_CHECK(cong_sort(d_tmp.p, tb1, pk_in, (KeyT*)S->d_pkeys.p, pv_in, S->d_pvals.p, totP + totQ, (unsigned)S->cell_bits, end_bit_p, L.comb_off.p, 2 * nB, st, &own_p));
-    else
-    STOCS_HIP_CHECK(cong_sort(d_tmp.p, tb1, pk_in, (KeyT*)S->d_pkeys.p, pv_in, S->d_pvals.p, totP, (unsigned)S->cell_bits, end_bit_p, plan.p_off, nB, st, &own_p));
-    if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[2], st));
-    if (S->use_table) {
-        const size_t ncell = (size_t)(S->NC * nB);
-        if ((rc = S->d_cfirst.alloc(ncell)) || (rc = S->d_cend.alloc(ncell))) return rc;
-        // the table is read at the cells of the Q entries only: in the reduced lists every such cell holds P entries, so the
-        // records kernel writes every slot that is read and the 8 bytes per (base, cell) need no zero fill
-        if (!reduce) hipLaunchKernelGGL(zero_u32_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, st, S->d_cfirst.p, ncell, S->d_cend.p);
+    for (int y = side0; y < side0 + ny; ++y) {
+        const ListSide<KeyT>& X = A.side[y];
+        const ListNames& N = LIST_NAMES[y];
+        switch (k) {
+        case LIST_GATHER: c->audit.step(s, N.gather, {{X.segs, N.segs}, {A.jobs, "base jobs"}}, {{X.keys, N.keys}, {X.vals, N.vals}, {X.occ, N.occ}}); break;
+        case LIST_COUNT: c->audit.step(s, N.count, {{X.keys, N.keys}, {X.other, LIST_NAMES[1 - y].occ}}, {{X.tiles, N.tiles}, {X.alive, N.alive}}); break;
+        case LIST_COMPACT: c->audit.step(s, N.compact, {{X.keys, N.keys}, {X.vals, N.vals}, {X.alive, N.alive}, {X.tiles, N.tiles}}, {{X.okeys, N.okeys}, {X.ovals, N.ovals}}); break;
+        }
     }
-    hipLaunchKernelGGL(p_records_kernel<KeyT>, dim3((unsigned)((totP + 1023) / 1024)), dim3(256), 0, st, (const KeyT*)S->d_pkeys.p, S->d_pvals.p, (uint32_t)totP,
-                       S->cell_bits, S->NC, S->d_jobs.p, c->d_munit, c->d_mpos, S->nepsilon, S->close_cells ? (float4*)NULL : S->d_prec.p, S->close_cells ? S->d_pdc.p : (uint16_t*)NULL,
-                       S->use_table ? S->d_cfirst.p : (uint32_t*)NULL,
-                       S->use_table ? S->d_cend.p : (uint32_t*)NULL);
-    STOCS_HIP_CHECK(hipGetLastError());
-    AU.use(s0, pk_in, false, "P keys to sort", "sort P"); AU.use(s0, pv_in, false, "P pairs to sort", "sort P");
-    AU.use(s0, S->d_pkeys.p, true, "sorted P keys", "sort P + records"); AU.use(s0, S->d_pvals.p, true, "sorted P pairs", "sort P + records"); AU.use(s0, plan.jobs, false, "base jobs", "P records");
-    if (!reduce)
-        hipLaunchKernelGGL(gather_key_kernel<KeyT>, dim3(gather_grid(totQ)), dim3(256), 0, sq, ix.d_pairs, plan.qsegs, plan.n_qseg, (uint32_t)totQ,
-                           S->d_jobs.p, c->d_munit, 1, S->cell_bits, cell_limit, L.qk_raw.p, L.qv_raw.p, (uint32_t*)NULL, (const PlanOut*)NULL, 0u, (uint32_t)nB);
-    if (!one_stream)
-    STOCS_HIP_CHECK(cong_sort(d_tmp2.p, tb2, qk_in, (KeyT*)S->d_qkeys.p, qv_in, S->d_qvals.p, totQ, (unsigned)S->cell_bits, end_bit, plan.q_off, nB, sq, &own_q));
-    AU.use(s1, plan.q_off, false, "Q offsets per base", "sort Q");
-    AU.use(s1, qk_in, false, "Q keys to sort", "sort Q"); AU.use(s1, qv_in, false, "Q pairs to sort", "sort Q");
-    AU.use(s1, S->d_qkeys.p, true, "sorted Q keys", "sort Q"); AU.use(s1, S->d_qvals.p, true, "sorted Q pairs", "sort Q"); AU.use(s1, d_tmp2.p, true, "sort scratch Q", "sort Q");
-    if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[1], sq));
-    if (sq != st) { STOCS_HIP_CHECK(hipEventRecord(c->ev_join, sq)); AU.record(c->ev_join, s1); }
-    if (sq != st) { STOCS_HIP_CHECK(hipStreamWaitEvent(st, c->ev_join, 0)); AU.wait(s0, c->ev_join); }   // the join needs both sides
-    AU.use(s0, S->d_qkeys.p, false, "sorted Q keys", "join count"); AU.use(s0, S->d_qvals.p, false, "sorted Q pairs", "join count"); AU.use(s0, plan.jobs, false, "base jobs", "join count");
-    if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[3], st));
-    STOCS_TICK("gather+sort+records")
-    // join: count pass + exclusive scan.  The quads themselves are produced on demand (materialise / resolve_picks_kernel)
-    DevBuf<unsigned long long> d_qcnt;   // 64-bit: the total can exceed 2^32
-    if ((rc = d_qcnt.alloc(totQ + 1)) || (rc = S->d_qoffe.alloc(totQ + 1))) return rc;
-    hipLaunchKernelGGL(join_count_kernel<KeyT>, dim3((unsigned)((totQ + 255) / 256)), dim3(256), 0, st, S->args<KeyT>(c), d_qcnt.p);
-    STOCS_HIP_CHECK(hipGetLastError());
-    if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[4], st));
-    size_t tmp_scan = 0;
-    STOCS_HIP_CHECK(exclusive_scan(NULL, tmp_scan, d_qcnt.p, S->d_qoffe.p, totQ + 1, st));
-    DevBuf<char> d_tmp_scan;
-    if ((rc = d_tmp_scan.alloc(tmp_scan))) return rc;
-    STOCS_HIP_CHECK(exclusive_scan(d_tmp_scan.p, tmp_scan, d_qcnt.p, S->d_qoffe.p, totQ + 1, st));
-    // per-base offsets = scan value at the first Q entry of each base
-    unsigned long long* qoff_at = (unsigned long long*)((char*)c->h_pin + PIN_VAR);   // pinned (sized by the caller)
-    DevBuf<unsigned long long> d_boff;
-    if ((rc = d_boff.alloc(nB + 1))) return rc;
-    hipLaunchKernelGGL(base_offsets_kernel, dim3((unsigned)((nB + 1 + 255) / 256)), dim3(256), 0, st, S->d_qoffe.p, S->d_qoff.p, nB + 1, d_boff.p);
-    STOCS_HIP_CHECK(hipGetLastError());
-    STOCS_HIP_CHECK(hipMemcpyAsync(qoff_at, d_boff.p, 8 * (size_t)(nB + 1), hipMemcpyDeviceToHost, st));
-    uint32_t* sort_err_pin = (uint32_t*)((char*)c->h_pin + PIN_CONGRUENT + 128);   // the own sort's error words (a look-back wait that ran into its bound)
-    sort_err_pin[0] = sort_err_pin[1] = 0u;
-    // (both sorts are joined into st by now)
-    if (own_p) STOCS_HIP_CHECK(hipMemcpyAsync(&sort_err_pin[0], d_tmp.p + sort_own_err_offset(), 4, hipMemcpyDeviceToHost, st));
-    if (own_q) STOCS_HIP_CHECK(hipMemcpyAsync(&sort_err_pin[1], d_tmp2.p + sort_own_err_offset(), 4, hipMemcpyDeviceToHost, st));
-    if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[5], st));
-    c->timing[TIMING_CONGRUENT].lap(reduce ? "enqueue compact/sort/records/join/scan" : "enqueue gather/sort/records/join/scan");
-    STOCS_HIP_CHECK(hipStreamSynchronize(st));
-    AU.host_sync(s0);
-    c->timing[TIMING_CONGRUENT].lap("wait for the device (counts)");
-    // the device's own account of that wait (every event has completed: the stream is idle, the Q side was joined into it): a group
-    // between two events per row, named per form (NULL: not a group of that form)
-    static const struct { int from, to; const char *all, *red, *one; } groups[] = {
-        {6, 7, NULL, "device: gathers + occupancy + survivor counts (both lists)", "device: gathers + occupancy + survivor counts (both lists in every launch)"},
-        {0, 1, "device: Q gather + sort (aux stream, from the fork)", "device: Q sort (aux stream, from the fork; its compaction ran during the wait)", NULL},
-        {0, 2, "device: P gather + sort", "device: P sort", "device: sort (P and Q as one list of 2 nB segments)"},
-        {2, 3, "device: P records + wait for Q", "device: P records + wait for Q", "device: P records"},
-        {3, 4, "device: join count", "device: join count", "device: join count"},
-        {4, 5, "device: scan + offsets + read-back", "device: scan + offsets + read-back", "device: scan + offsets + read-back"}};
-    CallTiming& T = c->timing[TIMING_CONGRUENT];
-    for (const auto& g : groups) {
-        const char* what = one_stream ? g.one : (reduce ? g.red : g.all);
-        if (!dev_clock || !what || T.n >= CallTiming::MAX_STEPS) continue;
-        float ms = -1.0f;
-        if (hipEventElapsedTime(&ms, c->ev_t[g.from], c->ev_t[g.to]) != hipSuccess) ms = -1.0f;
-        T.label[T.n] = what; T.ms[T.n] = (double)ms; ++T.n;
+}
+
+// One step for BOTH lists, in the form of the pass.  One stream: ONE launch with gridDim.y == 2 on the context's stream.  Otherwise one launch
+// per list, `first`'s list first, P on the context's stream and Q on the pass's second one -- the order of the two enqueues is the caller's
+// and matters (the side enqueued second starts later).  after(side) follows each list's launch (the one launch for both: both calls behind it,
+// in the same order): the events a list's step is followed by.
+template <class KeyT, class After>
+static int issue_lists(stocs_ctx* c, const PassForm& F, ListKernel k, const ListPass<KeyT>& A, int first, After after) {
+    int rc;
+    if (F.one_stream) {
+        launch_list_kernel(c, k, A, 0, 2, F.s0);
+        if ((rc = after(first)) || (rc = after(1 - first))) return rc;
+        return STOCS_OK;
     }
-    T.t_last = CallTiming::now_s();
-    STOCS_TICK("join count+scan")
-    if (sort_err_pin[0] || sort_err_pin[1]) { set_error("stocs_find_congruent_all: the pair-list sort gave up waiting for a tile (sort32.hip)"); return STOCS_ERR_HIP; }
-    for (int b = 0; b <= nB; ++b) c->quad_off[b] = qoff_at[b];
+    for (int i = 0; i < 2; ++i) {
+        const int side = i ? 1 - first : first;
+        launch_list_kernel(c, k, A, side, 1, F.audit_stream(side));
+        if ((rc = after(side))) return rc;
+    }
     return STOCS_OK;
 }
+
+// One cong_sort call, described once: the size query and the run take it from here.  An inactive descriptor (the Q sort of the one-stream
+// form, whose list is sorted as the second half of P's) does nothing and needs no bytes.
+struct SortNames { const char *what, *kin, *vin, *seg, *kout, *vout, *tmp; };
+static const SortNames SORT_NAMES[2] = {
+    {"sort P", "P keys to sort", "P pairs to sort", "P offsets per base", "sorted P keys", "sorted P pairs", "sort scratch P"},
+    {"sort Q", "Q keys to sort", "Q pairs to sort", "Q offsets per base", "sorted Q keys", "sorted Q pairs", "sort scratch Q"}};
+template <class KeyT>
+struct SortCall {
+    bool active;
+    const KeyT* kin; KeyT* kout; const uint32_t* vin; uint32_t* vout; size_t n; unsigned cell_bits, end_bit; const uint32_t* seg_off; int n_seg;
+    int s;               // audit index of its stream
+    size_t bytes;        // of temporary storage (bytes_needed)
+    bool own;            // the library's own sort runs (decided per list: by its length per base): its error word is read back
+    char* tmp;
+    hipError_t bytes_needed(stocs_ctx* c) { bytes = 0; own = false; return active ? cong_sort(NULL, bytes, kin, kout, vin, vout, n, cell_bits, end_bit, seg_off, n_seg, ctx_stream(c, s), &own) : hipSuccess; }
+    hipError_t run(stocs_ctx* c, int side, char* t) {
+        tmp = t;
+        if (!active) return hipSuccess;
+        const hipError_t e = cong_sort(tmp, bytes, kin, kout, vin, vout, n, cell_bits, end_bit, seg_off, n_seg, ctx_stream(c, s), &own);
+        const SortNames& N = SORT_NAMES[side];
+        c->audit.step(s, N.what, {{kin, N.kin}, {vin, N.vin}, {seg_off, N.seg}}, {{kout, N.kout}, {vout, N.vout}, {tmp, N.tmp}});
+        return e;
+    }
+    // the own sort keeps an error word at the start of its temporary block (a look-back wait that ran into its bound)
+    hipError_t read_error(uint32_t* pinned, hipStream_t st) const { return (active && own) ? hipMemcpyAsync(pinned, tmp + sort_own_err_offset(), 4, hipMemcpyDeviceToHost, st) : hipSuccess; }
+};
+
+// ---- one count pass ----
+// The count pass over the planned lists: (reduce_lists,) sorts, P records and run table, join count, scan, per-base quad offsets -- a short
+// list of stages (run) over the state they share.
+// F.optimistic: the host has NOT read the plan -- S->totP / S->totQ are capacities the buffers and launches are sized by, the kernels read
+// the planned totals from *d_po, and the plan's totals arrive with the survivors' in ONE read-back (po_pin).  *outgrown (not an error) when
+// the plan turned out larger than the capacities: the caller redoes the pass with the exact sizes it now knows.
+template <class KeyT>
+struct CountPass {
+    stocs_ctx* const c; CongruentState* const S; const PlanDev& plan; const PassForm& F; double& tprev;
+    const PlanOut* const d_po; const PlanOut* const po_pin;   // the plan's totals on the device and in the pinned block (NULL unless F.optimistic)
+    const bool dbg;
+    // The device's own clock of the kernel groups (HIP events between them, reported by stocs_last_call_timing as "device: ..." steps) is
+    // OPT-IN since round 5b (stocs_set_option "device_clock" / STOCS_DEVICE_CLOCK=1): on this runtime every event recorded between two kernels
+    // of a stream leaves the queue idle for ~5 us, and the nine of a call were 45 us of a Cm trial's 600.  The host's steps between the call's
+    // own synchronisation points are always recorded.
+    const bool dev_clock;
+    const int nB;
+    const size_t nP0, nQ0;   // the gathered lists as planned (F.optimistic: their capacities)
+    size_t nP, nQ;           // the lists that are sorted and joined (the survivors, when the lists are reduced)
+    hipStream_t const st;
+    StreamAudit& AU;         // STOCS_DEBUG_STREAMS: every step below says what it reads and writes
+    ListPass<KeyT> A;
+    // the pair lists as gathered and, when they are reduced, their survivors (ONE buffer for both lists in the one-stream form: Q's behind P's)
+    DevBuf<KeyT> pk_raw, qk_raw, pk_c, qk_c;
+    DevBuf<uint32_t> pv_raw, qv_raw, pv_c, qv_c, comb_off;
+    DevBuf<uint32_t> d_surv;                             // one zeroed block: occupancy of P | occupancy of Q | P tile counts (+ total) | Q tile counts (+ total)
+    DevBuf<unsigned long long> d_bits_p, d_bits_q;       // one bit per gathered entry: survives (written by the count, read by the compaction)
+    size_t n_surv_words = 0;
+    uint32_t ntp = 0, ntq = 0;                           // tiles of the gathered lists
+    SortCall<KeyT> sort_p, sort_q;
+    DevBuf<char> d_tmp_p, d_tmp_q;
+    uint32_t* sort_err_pin = NULL;
+
+    CountPass(stocs_ctx* c_, CongruentState* S_, const PlanDev& plan_, const PassForm& F_, bool dbg_, double& tprev_, const PlanOut* d_po_, const PlanOut* po_pin_)
+        : c(c_), S(S_), plan(plan_), F(F_), tprev(tprev_), d_po(d_po_), po_pin(po_pin_), dbg(dbg_), dev_clock(c_->device_clock != 0), nB(S_->nB), nP0(S_->totP), nQ0(S_->totQ),
+          nP(S_->totP), nQ(S_->totQ), st(c_->stream), AU(c_->audit) {}
+
+    int clock_stamp(CongEvent e, hipStream_t s) { if (dev_clock) STOCS_HIP_CHECK(hipEventRecord(c->ev_t[e], s)); return STOCS_OK; }
+    // main -> aux: what the context's stream holds now comes before whatever the second stream is given next (nothing to do with one stream)
+    int fork() { return F.two_streams() ? stream_edge(c, c->ev_fork, F.s0, F.s1) : STOCS_OK; }
+    int run_deferred(const char* label) {
+        if (!S->deferred) return STOCS_OK;
+        const int rd = S->deferred();
+        S->deferred = nullptr;
+        if (rd) return rd;
+        c->timing[TIMING_CONGRUENT].lap(label);
+        return STOCS_OK;
+    }
+
+    // -- stage: the pass's lists and the records its kernels are given (every buffer the records name is allocated here) --
+    int allocate_lists() {
+        int rc;
+        if ((rc = pk_raw.alloc(nP0)) || (rc = pv_raw.alloc(nP0)) || (rc = qk_raw.alloc(nQ0)) || (rc = qv_raw.alloc(nQ0))) return rc;
+        S->d_jobs.p = plan.jobs; S->d_qoff.p = plan.q_off; S->d_bids.p = plan.bids; S->d_err.p = plan.err;
+        memset(&A, 0, sizeof A);
+        A.pairs = c->index.d_pairs; A.jobs = plan.jobs; A.munit = c->d_munit; A.cell_bits = S->cell_bits; A.cell_limit = S->use_table ? S->NC : ((long long)1 << 31);
+        A.nB = nB; A.p_off = plan.p_off; A.q_off = plan.q_off;
+        ListSide<KeyT>&P = A.side[0], &Q = A.side[1];
+        P.segs = plan.psegs; P.nseg = plan.n_pseg; P.n = (uint32_t)nP0; P.keys = pk_raw.p; P.vals = pv_raw.p;
+        Q.segs = plan.qsegs; Q.nseg = plan.n_qseg; Q.n = (uint32_t)nQ0; Q.keys = qk_raw.p; Q.vals = qv_raw.p;
+        if (!F.reduce) return STOCS_OK;       // (the unreduced gather: no occupancy, no plan on the device, no LDS words)
+        A.d_po = d_po; A.lds_words = F.lds_words;
+        const size_t W = (size_t)((((unsigned long long)nB << S->cell_bits) + 31) >> 5) + 1;   // words of one occupancy table: one bit per (base, cell) value
+        ntp = (uint32_t)((nP0 + SURV_TILE - 1) / SURV_TILE); ntq = (uint32_t)((nQ0 + SURV_TILE - 1) / SURV_TILE);
+        const size_t o_tp = 2 * W, o_tq = o_tp + ntp + 1;
+        n_surv_words = o_tq + ntq + 1;
+        if ((rc = d_surv.alloc(n_surv_words))) return rc;
+        if ((rc = d_bits_p.alloc((size_t)std::max(ntp, 1u) * (SURV_TILE / 64))) || (rc = d_bits_q.alloc((size_t)std::max(ntq, 1u) * (SURV_TILE / 64)))) return rc;
+        // the compacted lists are sized by the gathered ones (the survivors' totals are what the host waits for while they are written)
+        if (F.one_stream) { if ((rc = pk_c.alloc(nP0 + nQ0)) || (rc = pv_c.alloc(nP0 + nQ0)) || (rc = comb_off.alloc(2 * (size_t)nB + 1))) return rc; }
+        else if ((rc = pk_c.alloc(nP0)) || (rc = pv_c.alloc(nP0)) || (rc = qk_c.alloc(nQ0)) || (rc = qv_c.alloc(nQ0))) return rc;
+        A.comb_off = comb_off.p;
+        P.occ = d_surv.p; Q.occ = d_surv.p + W; P.other = Q.occ; Q.other = P.occ;
+        P.tiles = d_surv.p + o_tp; Q.tiles = d_surv.p + o_tq; P.alive = d_bits_p.p; Q.alive = d_bits_q.p;
+        P.okeys = pk_c.p; P.ovals = pv_c.p;
+        Q.okeys = F.one_stream ? pk_c.p : qk_c.p; Q.ovals = F.one_stream ? pv_c.p : qv_c.p;      // (one list: the kernel puts Q's survivors behind P's)
+        return STOCS_OK;
+    }
+
+    // -- stages of the reduced form: gather -> occupancy -> survivor counts -> tile scan -> compaction of both lists, and the read-back of the
+    //    survivors' offsets and totals.  In every two-list step Q is enqueued first. --
+    int zero_fill_and_fork() {
+        const ListSide<KeyT>&P = A.side[0], &Q = A.side[1];
+        hipLaunchKernelGGL(zero_u32_kernel, dim3((unsigned)((n_surv_words + 255) / 256)), dim3(256), 0, st, d_surv.p, n_surv_words, (uint32_t*)NULL);
+        AU.step(F.s0, "zero fill", {}, {{P.occ, LIST_NAMES[0].occ}, {Q.occ, LIST_NAMES[1].occ}, {P.tiles, LIST_NAMES[0].tiles}, {Q.tiles, LIST_NAMES[1].tiles}});
+        int rc = clock_stamp(EV_REDUCE_BEGIN, st);
+        return rc ? rc : fork();          // the plan upload, the plan kernels and the zero fill are on st
+    }
+    int gather() {
+        // each list's cells are marked behind its gather: the OTHER list's count waits for that (two streams: the cross edges below)
+        int rc = issue_lists(c, F, LIST_GATHER, A, 1, [&](int side) -> int {
+            return (F.two_streams() || dev_clock) ? stream_edge_record(c, c->ev_t[side ? EV_Q_MARKED : EV_P_MARKED], F.audit_stream(side)) : STOCS_OK;
+        });
+        if (rc || !F.two_streams()) return rc;
+        if ((rc = stream_edge_wait(c, c->ev_t[EV_P_MARKED], F.s1))) return rc;
+        return stream_edge_wait(c, c->ev_t[EV_Q_MARKED], F.s0);
+    }
+    int count() {
+        const int rc = issue_lists(c, F, LIST_COUNT, A, 1, [&](int side) -> int { return (side == 1 && F.two_streams()) ? stream_edge_record(c, c->ev_join, F.s1) : STOCS_OK; });
+        if (rc || !F.two_streams()) return rc;
+        return stream_edge_wait(c, c->ev_join, F.s0);       // the scan below reads both lists' counts
+    }
+    int tile_scan() {
+        const ListSide<KeyT>&P = A.side[0], &Q = A.side[1];
+        AU.step(F.s0, "tile scan", {}, {{P.tiles, LIST_NAMES[0].tiles}, {Q.tiles, LIST_NAMES[1].tiles}});
+        if (std::max(ntp, ntq) + 1u <= 2u * TSCAN) {
+            hipLaunchKernelGGL(survivors_scan_kernel, dim3(2), dim3(1024), 0, st, P.tiles, ntp, Q.tiles, ntq);
+            return STOCS_OK;
+        }
+        // long lists (trial batches): the scan on many workgroups
+        const uint32_t pp = (ntp + 1u + TSCAN - 1u) / TSCAN, pq = (ntq + 1u + TSCAN - 1u) / TSCAN;
+        DevBuf<uint32_t> d_part;
+        const int rc = d_part.alloc((size_t)pp + pq);
+        if (rc) return rc;
+        hipLaunchKernelGGL(tile_scan_local_kernel, dim3(std::max(pp, pq), 2), dim3(256), 0, st, P.tiles, ntp + 1u, Q.tiles, ntq + 1u, d_part.p, pp);
+        hipLaunchKernelGGL(tile_scan_add_kernel, dim3(std::max(pp, pq), 2), dim3(256), 0, st, P.tiles, ntp + 1u, Q.tiles, ntq + 1u, (const uint32_t*)d_part.p, pp);
+        return STOCS_OK;
+    }
+    uint32_t* qoff_pin() const { return (uint32_t*)((char*)c->h_pin + PIN_VAR + 8 * ((size_t)nB + 1)); }
+    int base_offsets_and_read_back() {
+        const ListSide<KeyT>&P = A.side[0], &Q = A.side[1];
+        AU.step(F.s0, "base offsets", {{P.keys, LIST_NAMES[0].keys}, {Q.keys, LIST_NAMES[1].keys}, {P.occ, LIST_NAMES[0].occ}, {Q.occ, LIST_NAMES[1].occ}},
+                {{plan.jobs, "base jobs"}, {plan.q_off, "Q offsets per base"}});
+        hipLaunchKernelGGL(survivors_base_offsets_kernel<KeyT>, dim3((unsigned)nB, 2), dim3(256), 0, st, (const KeyT*)P.keys, P.n, (const uint32_t*)Q.occ, (const uint32_t*)P.tiles,
+                           (const KeyT*)Q.keys, Q.n, (const uint32_t*)P.occ, (const uint32_t*)Q.tiles, nB, S->d_jobs.p, plan.p_off, plan.q_off, d_po);
+        STOCS_HIP_CHECK(hipGetLastError());
+        // the host sizes the sorts and the join with the survivors' totals and lays the materialise blocks out with their Q offsets
+        STOCS_HIP_CHECK(hipMemcpyAsync(qoff_pin(), plan.q_off, 4 * ((size_t)nB + 2), hipMemcpyDeviceToHost, st));   // Q offsets, Q total, P total
+        return stream_edge_record(c, c->ev_t[EV_SURVIVORS_READ], F.s0);
+    }
+    int compact() {
+        // the survivors move behind their tiles' offsets while the host waits for the totals
+        int rc = fork();                  // tile offsets are scanned on st
+        if (rc || (rc = issue_lists(c, F, LIST_COMPACT, A, 1, [](int) -> int { return STOCS_OK; }))) return rc;
+        STOCS_HIP_CHECK(hipGetLastError());
+        c->timing[TIMING_CONGRUENT].lap("enqueue gather + occupancy + survivor counts");
+        return STOCS_OK;
+    }
+    int deferred_records_and_wait() {
+        const int rc = run_deferred("host: cone records of the bases (while the device gathers)");
+        if (rc) return rc;
+        STOCS_HIP_CHECK(hipEventSynchronize(c->ev_t[EV_SURVIVORS_READ]));   // the read-back, not the compaction behind it
+        AU.host_sync_event(c->ev_t[EV_SURVIVORS_READ]);
+        c->timing[TIMING_CONGRUENT].lap("wait for the device (survivors)");
+        return STOCS_OK;
+    }
+    // the plan's own totals came with the read-back: were the capacities enough?  If not the streams are idle on return.
+    int capacity_check(bool* outgrown) {
+        if (!po_pin || !(po_pin->overflow || po_pin->totP > (unsigned long long)nP0 || po_pin->totQ > (unsigned long long)nQ0)) return STOCS_OK;
+        STOCS_HIP_CHECK(hipStreamSynchronize(st));            // the compaction behind the read-back: nothing may still touch the arena
+        if (F.two_streams()) STOCS_HIP_CHECK(hipStreamSynchronize(F.sq));
+        AU.host_sync(F.s0); AU.host_sync(F.s1);
+        *outgrown = true;
+        return STOCS_OK;
+    }
+    // S->totP, S->totQ, S->h_qoff of the survivors; S->no_quads when no cell is shared
+    int reduce_lists(bool* outgrown) {
+        int rc;
+        if ((rc = zero_fill_and_fork()) || (rc = gather()) || (rc = count()) || (rc = tile_scan()) || (rc = base_offsets_and_read_back()) || (rc = compact()) ||
+            (rc = deferred_records_and_wait()) || (rc = capacity_check(outgrown)) || *outgrown)
+            return rc;
+        const uint32_t* pin = qoff_pin();
+        nP = pin[nB + 1]; nQ = pin[nB];
+        memcpy(S->h_qoff.data(), pin, 4 * ((size_t)nB + 1));
+        if (dbg) fprintf(stderr, "[stocs congruent] survivors: P %zu of %zu, Q %zu of %zu\n", nP, nP0, nQ, nQ0);
+        S->totP = (uint32_t)nP; S->totQ = (uint32_t)nQ;
+        if (nP == 0 || nQ == 0) S->no_quads = true;   // no cell is shared: no quads (quad_off is all zero already)
+        return STOCS_OK;
+    }
+
+    // -- stage: the sorted lists and the sorts that fill them --
+    int prepare_sorts() {
+        int rc;
+        const ListSide<KeyT>&P = A.side[0], &Q = A.side[1];
+        const KeyT* pk_in = F.reduce ? P.okeys : P.keys; const uint32_t* pv_in = F.reduce ? P.ovals : P.vals;    // what the sorts read
+        const KeyT* qk_in = F.reduce ? Q.okeys : Q.keys; const uint32_t* qv_in = F.reduce ? Q.ovals : Q.vals;
+        if (F.one_stream) {   // one sorted list: P's part, then Q's
+            if ((rc = S->d_pkeys.alloc((nP + nQ) * sizeof(KeyT))) || (rc = S->d_pvals.alloc(nP + nQ))) return rc;
+            S->d_qkeys.p = S->d_pkeys.p + nP * sizeof(KeyT); S->d_qvals.p = S->d_pvals.p + nP;
+        } else if ((rc = S->d_pkeys.alloc(nP * sizeof(KeyT))) || (rc = S->d_pvals.alloc(nP)) || (rc = S->d_qkeys.alloc(nQ * sizeof(KeyT))) || (rc = S->d_qvals.alloc(nQ)))
+            return rc;
+        if ((rc = S->d_prec.alloc(S->close_cells ? 1 : nP)) || (rc = S->d_pdc.alloc(((size_t)nP + 15) & ~(size_t)7))) return rc;
+        // one stable sort per list: (base, position cell); inside a cell the entries keep the index order of the gather.  One stream: ONE
+        // sort of the combined list, its 2 nB segments P's bases and then Q's.
+        const unsigned cb = (unsigned)S->cell_bits;
+        if (F.one_stream) sort_p = {true, pk_in, (KeyT*)S->d_pkeys.p, pv_in, S->d_pvals.p, nP + nQ, cb, F.end_bit_p, comb_off.p, 2 * nB, F.s0, 0, false, NULL};
+        else sort_p = {true, pk_in, (KeyT*)S->d_pkeys.p, pv_in, S->d_pvals.p, nP, cb, F.end_bit_p, plan.p_off, nB, F.s0, 0, false, NULL};
+        sort_q = {!F.one_stream, qk_in, (KeyT*)S->d_qkeys.p, qv_in, S->d_qvals.p, nQ, cb, F.end_bit, plan.q_off, nB, F.s1, 0, false, NULL};
+        STOCS_HIP_CHECK(sort_p.bytes_needed(c));
+        STOCS_HIP_CHECK(sort_q.bytes_needed(c));
+        if ((rc = d_tmp_p.alloc(sort_p.bytes)) || (rc = d_tmp_q.alloc(sort_q.bytes))) return rc;
+        return STOCS_OK;
+    }
+    // The P side (sort, records) and the Q side (sort) are independent until the join: the Q side runs on the pass's second stream next to
+    // the P side (a radix pass of 7 M pairs moves ~1.8 TB/s: two of them share the chip).
+    // The P side first: it is the longer chain (sort + records: ~100 us at Cm against ~70 us of the Q sort), and whichever side is enqueued second
+    // starts ~25 us later -- the host needs that long for the first side's five launches (kernel trace of a trial, round 5)
+    int p_side() {
+        int rc;
+        if (!F.reduce) launch_list_kernel(c, LIST_GATHER, A, 0, 1, F.s0);
+        STOCS_HIP_CHECK(hipGetLastError());
+        STOCS_HIP_CHECK(sort_p.run(c, 0, d_tmp_p.p));
+        if ((rc = clock_stamp(EV_P_SORTED, st))) return rc;
+        if (S->use_table) {
+            const size_t ncell = (size_t)(S->NC * nB);
+            if ((rc = S->d_cfirst.alloc(ncell)) || (rc = S->d_cend.alloc(ncell))) return rc;
+            // the table is read at the cells of the Q entries only: in the reduced lists every such cell holds P entries, so the
+            // records kernel writes every slot that is read and the 8 bytes per (base, cell) need no zero fill
+            if (!F.reduce) hipLaunchKernelGGL(zero_u32_kernel, dim3((unsigned)((ncell + 255) / 256)), dim3(256), 0, st, S->d_cfirst.p, ncell, S->d_cend.p);
+        }
+        hipLaunchKernelGGL(p_records_kernel<KeyT>, dim3((unsigned)((nP + 1023) / 1024)), dim3(256), 0, st, (const KeyT*)S->d_pkeys.p, S->d_pvals.p, (uint32_t)nP,
+                           S->cell_bits, S->NC, S->d_jobs.p, c->d_munit, c->d_mpos, S->nepsilon, S->close_cells ? (float4*)NULL : S->d_prec.p, S->close_cells ? S->d_pdc.p : (uint16_t*)NULL,
+                           S->use_table ? S->d_cfirst.p : (uint32_t*)NULL,
+                           S->use_table ? S->d_cend.p : (uint32_t*)NULL);
+        STOCS_HIP_CHECK(hipGetLastError());
+        AU.step(F.s0, "P records", {{S->d_pkeys.p, SORT_NAMES[0].kout}, {S->d_pvals.p, SORT_NAMES[0].vout}, {plan.jobs, "base jobs"}}, {{S->d_prec.p, "P records"}, {S->d_pdc.p, "P direction cells"}});
+        return STOCS_OK;
+    }
+    int q_side_and_join_streams() {
+        int rc;
+        if (!F.reduce) launch_list_kernel(c, LIST_GATHER, A, 1, 1, F.s1);
+        STOCS_HIP_CHECK(sort_q.run(c, 1, d_tmp_q.p));
+        if ((rc = clock_stamp(EV_Q_SORTED, F.sq))) return rc;
+        if (F.two_streams() && (rc = stream_edge(c, c->ev_join, F.s1, F.s0))) return rc;   // the join needs both sides
+        return clock_stamp(EV_SIDES_JOINED, st);
+    }
+    // join: count pass + exclusive scan.  The quads themselves are produced on demand (materialise / resolve_picks_kernel)
+    int join_count_and_scan() {
+        int rc;
+        AU.step(F.s0, "join count", {{S->d_qkeys.p, SORT_NAMES[1].kout}, {S->d_qvals.p, SORT_NAMES[1].vout}, {plan.jobs, "base jobs"}}, {});
+        DevBuf<unsigned long long> d_qcnt;   // 64-bit: the total can exceed 2^32
+        if ((rc = d_qcnt.alloc(nQ + 1)) || (rc = S->d_qoffe.alloc(nQ + 1))) return rc;
+        hipLaunchKernelGGL(join_count_kernel<KeyT>, dim3((unsigned)((nQ + 255) / 256)), dim3(256), 0, st, S->template args<KeyT>(c), d_qcnt.p);
+        STOCS_HIP_CHECK(hipGetLastError());
+        if ((rc = clock_stamp(EV_JOIN_COUNTED, st))) return rc;
+        size_t tmp_scan = 0;
+        STOCS_HIP_CHECK(exclusive_scan(NULL, tmp_scan, d_qcnt.p, S->d_qoffe.p, nQ + 1, st));
+        DevBuf<char> d_tmp_scan;
+        if ((rc = d_tmp_scan.alloc(tmp_scan))) return rc;
+        STOCS_HIP_CHECK(exclusive_scan(d_tmp_scan.p, tmp_scan, d_qcnt.p, S->d_qoffe.p, nQ + 1, st));
+        return STOCS_OK;
+    }
+    unsigned long long* quad_off_pin() const { return (unsigned long long*)((char*)c->h_pin + PIN_VAR); }   // pinned (sized by the caller)
+    int enqueue_read_back() {
+        int rc;
+        // per-base offsets = scan value at the first Q entry of each base
+        DevBuf<unsigned long long> d_boff;
+        if ((rc = d_boff.alloc(nB + 1))) return rc;
+        hipLaunchKernelGGL(base_offsets_kernel, dim3((unsigned)((nB + 1 + 255) / 256)), dim3(256), 0, st, S->d_qoffe.p, S->d_qoff.p, nB + 1, d_boff.p);
+        STOCS_HIP_CHECK(hipGetLastError());
+        STOCS_HIP_CHECK(hipMemcpyAsync(quad_off_pin(), d_boff.p, 8 * (size_t)(nB + 1), hipMemcpyDeviceToHost, st));
+        sort_err_pin = (uint32_t*)((char*)c->h_pin + PIN_CONGRUENT + 128);   // the own sort's error words
+        sort_err_pin[0] = sort_err_pin[1] = 0u;
+        // (both sorts are joined into st by now)
+        STOCS_HIP_CHECK(sort_p.read_error(&sort_err_pin[0], st));
+        STOCS_HIP_CHECK(sort_q.read_error(&sort_err_pin[1], st));
+        if ((rc = clock_stamp(EV_PASS_END, st))) return rc;
+        c->timing[TIMING_CONGRUENT].lap(F.enqueue_label());
+        return STOCS_OK;
+    }
+    int wait_and_clock_rows() {
+        STOCS_HIP_CHECK(hipStreamSynchronize(st));
+        AU.host_sync(F.s0);
+        c->timing[TIMING_CONGRUENT].lap("wait for the device (counts)");
+        // the device's own account of that wait (every event has completed: the stream is idle, the Q side was joined into it): a group
+        // between two clock stamps per row, named per form (PassForm::clock_label)
+        static const struct { CongEvent from, to; const char *all, *red, *one; } groups[] = {
+            {EV_REDUCE_BEGIN, EV_SURVIVORS_READ, NULL, "device: gathers + occupancy + survivor counts (both lists)", "device: gathers + occupancy + survivor counts (both lists in every launch)"},
+            {EV_SORT_BEGIN, EV_Q_SORTED, "device: Q gather + sort (aux stream, from the fork)", "device: Q sort (aux stream, from the fork; its compaction ran during the wait)", NULL},
+            {EV_SORT_BEGIN, EV_P_SORTED, "device: P gather + sort", "device: P sort", "device: sort (P and Q as one list of 2 nB segments)"},
+            {EV_P_SORTED, EV_SIDES_JOINED, "device: P records + wait for Q", "device: P records + wait for Q", "device: P records"},
+            {EV_SIDES_JOINED, EV_JOIN_COUNTED, "device: join count", "device: join count", "device: join count"},
+            {EV_JOIN_COUNTED, EV_PASS_END, "device: scan + offsets + read-back", "device: scan + offsets + read-back", "device: scan + offsets + read-back"}};
+        CallTiming& T = c->timing[TIMING_CONGRUENT];
+        for (const auto& g : groups) {
+            const char* what = F.clock_label(g.all, g.red, g.one);
+            if (!dev_clock || !what || T.n >= CallTiming::MAX_STEPS) continue;
+            float ms = -1.0f;
+            if (hipEventElapsedTime(&ms, c->ev_t[g.from], c->ev_t[g.to]) != hipSuccess) ms = -1.0f;
+            T.label[T.n] = what; T.ms[T.n] = (double)ms; ++T.n;
+        }
+        T.t_last = CallTiming::now_s();
+        return STOCS_OK;
+    }
+
+    int run(bool* outgrown) {
+        *outgrown = false;
+        int rc;
+        if ((rc = allocate_lists())) return rc;
+        if (!F.reduce && (rc = run_deferred("host: cone records of the bases (no survivors pass to hide them behind)"))) return rc;
+        if (F.reduce && ((rc = reduce_lists(outgrown)) || *outgrown || S->no_quads)) return rc;
+        if ((rc = prepare_sorts())) return rc;
+        // device-side clock of the groups below (HIP events on the streams they run on; read after the call's closing
+        // synchronisation): a call that takes 70 ms instead of 1 then says which group of kernels it spent them in
+        if ((rc = clock_stamp(EV_SORT_BEGIN, st)) || (rc = fork())) return rc;       // (the fork: the upload and the plan are on st)
+        if ((rc = p_side()) || (rc = q_side_and_join_streams())) return rc;
+        STOCS_TICK("gather+sort+records")
+        if ((rc = join_count_and_scan()) || (rc = enqueue_read_back()) || (rc = wait_and_clock_rows())) return rc;
+        STOCS_TICK("join count+scan")
+        if (sort_err_pin[0] || sort_err_pin[1]) { set_error("stocs_find_congruent_all: the pair-list sort gave up waiting for a tile (sort32.hip)"); return STOCS_ERR_HIP; }
+        const unsigned long long* qoff_at = quad_off_pin();
+        for (int b = 0; b <= nB; ++b) c->quad_off[b] = qoff_at[b];
+        return STOCS_OK;
+    }
+};
 
 // the pair lists are too long for this call: a piece of a trial batch (too_big != NULL) hears it and splits its base set, any other caller gets an error
 static int lists_too_long(int* too_big, const char* why) { if (too_big) *too_big = 1; else set_error("%s", why); return too_big ? STOCS_OK : STOCS_ERR_CAPACITY; }
 
-// stocs_internal_find_congruent without its exit (below): every return of this body, error or not, goes through there
-static int find_congruent(stocs_ctx* c, const CongruentSwitches& sw, int64_t* total_quads, size_t max_bytes, int* too_big) {
-    const bool dbg = sw.debug_timing;
-    double tprev = now_s();
-    c->timing[TIMING_CONGRUENT].begin();
-    if (!c->index.built) { set_error("stocs_find_congruent_all: PPF index not built"); return STOCS_ERR_STATE; }
-    const int nB = (int)c->bases.size();
-    if (!c->cong) c->cong = new CongruentState();
-    CongruentState* S = (CongruentState*)c->cong;
-    S->valid = false;
-    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));   // the previous trial's buffers are about to be reused
-    if (c->aux_stream) STOCS_HIP_CHECK(hipStreamSynchronize(c->aux_stream));   // (idle unless an earlier call failed half way)
-    c->audit.on = sw.debug_streams;
-    c->audit.host_sync(0); if (c->aux_stream) c->audit.host_sync(1);
-    c->audit.retire_all("stocs_find_congruent_all: the arena is recycled");
-    c->timing[TIMING_CONGRUENT].lap("entry synchronisation");
-    { int rc0 = S->arena_state.reset(); if (rc0) return rc0; }
-    tl_arena = &S->arena_state;
-    if (!S->d_trig) {   // once per context (synchronous copy from static host memory)
-        STOCS_HIP_CHECK(dev_malloc((void**)&S->d_trig, sizeof(float2) * (STOCS_MAX_CONE + 1) * STOCS_MAX_CONE));
-        STOCS_HIP_CHECK(hipMemcpy(S->d_trig, cone_trig(), sizeof(float2) * (STOCS_MAX_CONE + 1) * STOCS_MAX_CONE, hipMemcpyHostToDevice));
-    }
-    // pinned block for everything this call reads back: plan totals, Q offsets (4 B per base), per-base quad offsets (8 B)
-    { int rc0 = ensure_pinned(c, (size_t)PIN_VAR + 12 * ((size_t)nB + 1) + 256); if (rc0) return rc0; }
-    c->timing[TIMING_CONGRUENT].lap("arena reset + pinned block");
-    if (dbg) { const double t_ = now_s(); fprintf(stderr, "[stocs congruent] %-18s %8.3f ms\n", "sync+reset", (t_ - tprev) * 1e3); tprev = t_; }
-    c->quad_off.assign(nB + 1, 0);
-    c->quad_id_bits = 16;
-    if (total_quads) *total_quads = 0;
-    if (nB == 0) return STOCS_OK;
-    if (nB >= (1 << 20)) { set_error("too many bases"); return STOCS_ERR_INVALID; }
-    const PpfIndex& ix = c->index;
+// One call of stocs_internal_find_congruent without its exit (below): every return of run(), error or not, goes through there.  The body is
+// a short list of stages over the state they share.
+struct CongruentCall {
+    stocs_ctx* const c; const CongruentSwitches& sw; const size_t max_bytes; int* const too_big;
+    const bool dbg;
+    double tprev;
+    CongruentState* S = NULL;
+    int nB = 0, egSize = 0;
+    float cell = 0, nepsilon = 0;
+    KeyLayout K;
+    PlanLayout L;
+    PlanDev plan;
+    char* dpl = NULL;                 // the planning buffer on the device
+    PlanOut* po_pin = NULL;           // the plan's totals in the pinned block
+    uint64_t totP = 0, totQ = 0;      // the first pass's list sizes: capacities (optimistic) or the plan's own
+    bool optimistic = false;
 
-    // ---- per base: the job record (invariants, cone table), then the plan of its two lookups ----
-    std::vector<BaseJob> jobs(nB);
-    const float eps_unit = c->prm.distance_threshold / c->ratio;  // getNormalizedEpsilon, pairCreationFunctor.h:141-143
-    const int gridDepth = (int)(-log2f(eps_unit));                // normalset.h:117
-    const int egSize = (int)pow(2.0, (double)gridDepth);          // :118
-    const float cell = 1.f / egSize;                               // :119
-    const float nepsilon = (float)((double)(1.0f / 7.0f) + 0.00001);  // normalset.h:86
-    // ---- key layout ----
-    const long long NC = (long long)egSize * egSize * egSize;
-    // (8 bytes of run table + 2 of occupancy per (base, cell): up to 2.7 GB -- a trial batch brings thousands of bases, and 288 GB are there for it)
-    const bool use_table = NC > 0 && NC * (long long)nB <= (long long)256 * 1024 * 1024;
-    int base_bits = 1, id_bits = 1, cell_bits = 1;
-    while ((1 << base_bits) < nB) base_bits++;
-    while ((1 << id_bits) < c->nM) id_bits++;
-    id_bits = std::max(id_bits, sw.min_id_bits);
-    {   // cells 0 .. limit-1 plus the all-ones "no cell" value
-        const unsigned long long lim = use_table ? (unsigned long long)NC : ((unsigned long long)1 << 31);
-        while (cell_bits < 40 && (((unsigned long long)1 << cell_bits) - 1ull) < lim) cell_bits++;
-    }
-    const bool wide = base_bits + cell_bits > 32 || sw.wide_keys;
-    // both pair lists are reduced to the entries with a partner cell when one byte per (base, cell) is a small table (count_pass)
-    const bool reduce = use_table && ((unsigned long long)nB << cell_bits) <= (1ull << 29) && !sw.keep_all;
-    // a batch's bases: the cone records wait until the device is busy (S->deferred, below)
-    const bool defer_cone = nB >= 512;
-    for (int b = 0; b < nB; ++b) {
-        const BaseRec& B = c->bases[b];
-        BaseJob& J = jobs[b];
-        memset(&J, 0, sizeof(J));
-        J.inv1 = B.inv1; J.inv2 = B.inv2;
-        J.cell = cell; J.egSize = egSize;
-        if (defer_cone) continue;
-        J.cos_alpha = dot3(normalized3(c->h_spos[B.ids[1]] - c->h_spos[B.ids[0]]), normalized3(c->h_spos[B.ids[3]] - c->h_spos[B.ids[2]]));  // stocs.cpp:801-803
-        fill_cone_table(&J);
-    }
-    const PlanLayout L(nB);
-    if (S->plan_bytes < L.bytes) {
-        if (S->d_plan) (void)hipFree(S->d_plan);
-        S->d_plan = NULL; S->plan_bytes = 0;
-        STOCS_HIP_CHECK(dev_malloc((void**)&S->d_plan, 2 * L.bytes));
-        S->plan_bytes = 2 * L.bytes;
-    }
-    if (S->stage_bytes < L.stage) {
-        if (S->h_stage) (void)hipHostFree(S->h_stage);
-        S->h_stage = NULL; S->stage_bytes = 0;
-        STOCS_HIP_CHECK(pinned_malloc(&S->h_stage, 2 * L.stage));   // counted: a regrow inside a trial must show up
-        S->stage_bytes = 2 * L.stage;
-    }
-    c->timing[TIMING_CONGRUENT].lap("host: jobs + cone tables + buffers");
-    char* h = (char*)S->h_stage;
-    char* dpl = S->d_plan;
-    PlanDev plan = {(BaseJob*)(dpl + L.jobs), (Segment*)(dpl + L.pseg), (Segment*)(dpl + L.qseg), (uint32_t*)(dpl + L.qoff), (uint32_t*)(dpl + L.poff),
-                    (int32_t*)(dpl + L.bids), (unsigned int*)(dpl + L.err), 0, 0};
-    uint64_t totP = 0, totQ = 0;
-    std::vector<uint32_t>& q_off = S->h_qoff;
-    q_off.assign(nB + 1, 0);
-    {
-        int32_t* bids = (int32_t*)(h + L.bids);
-        for (int b = 0; b < nB; ++b) for (int k = 0; k < 4; ++k) bids[4 * b + k] = c->bases[b].ids[k];
-        memset(h + L.err, 0, 256);
-    }
-    // the plan, on the device: 2 x nB small workgroups probe the bucket table, one workgroup lays the lists out; the host reads
-    // back four totals and the Q offsets (it sizes the sorts with them) -- 0.2 ms of host work per trial otherwise
-    memcpy(h + L.jobs, jobs.data(), sizeof(BaseJob) * (size_t)nB);
-    STOCS_HIP_CHECK(hipMemcpyAsync(dpl, h, L.up, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(plan_ranges_kernel, dim3((unsigned)nB, 2), dim3(64), 0, c->stream, ix.d_bucket_start, ix.tr, ix.rot, ix.NA, ix.nD, plan.bids,
-                       (const float4*)c->d_spos, (const float4*)c->d_snrmw, nB, (uint2*)(dpl + L.rng), (uint32_t*)(dpl + L.nr), (uint32_t*)(dpl + L.tot));
-    launch_plan_offsets(c->stream, nB, dpl, L, plan);
-    hipLaunchKernelGGL(plan_segments_kernel, dim3((unsigned)((2 * nB + 3) / 4)), dim3(256), 0, c->stream, nB, (const uint2*)(dpl + L.rng), (const uint32_t*)(dpl + L.nr),
-                       (const uint32_t*)(dpl + L.tot), plan.psegs, plan.qsegs, (const uint32_t*)plan.p_off, (const uint32_t*)plan.q_off, (const uint32_t*)(dpl + L.spo),
-                       (const uint32_t*)(dpl + L.sqo));
-    STOCS_HIP_CHECK(hipGetLastError());
-    // read-backs land in the pinned block (a copy into pageable memory -- a stack variable, a std::vector -- takes the
-    // runtime's staging path): totals in the fixed slot, the Q offsets behind the per-base quad offsets of count_pass
-    static_assert(sizeof(PlanOut) <= 256, "PlanOut must fit its pinned slot");
-    PlanOut* po_pin = (PlanOut*)((char*)c->h_pin + PIN_CONGRUENT);
-    uint32_t* qoff_pin = (uint32_t*)((char*)c->h_pin + PIN_VAR + 8 * ((size_t)nB + 1));
-    STOCS_HIP_CHECK(hipMemcpyAsync(po_pin, dpl + L.out, sizeof(PlanOut), hipMemcpyDeviceToHost, c->stream));
-    if (!reduce) STOCS_HIP_CHECK(hipMemcpyAsync(qoff_pin, plan.q_off, 4 * ((size_t)nB + 1), hipMemcpyDeviceToHost, c->stream));   // (reduced lists: their own offsets come later)
-    c->timing[TIMING_CONGRUENT].lap("enqueue plan upload + kernels + read-back");
-    if (defer_cone) {
-        // staged in the pinned block behind the upload, uploaded and patched into the device's jobs on the context's stream -- behind
-        // the plan kernels, ahead of the join
-        float4* hc = (float4*)(h + L.cone);
-        BaseJob* dj = plan.jobs;
-        S->deferred = [c, hc, dj, nB]() -> int {
-            for (int b = 0; b < nB; ++b) {
-                const BaseRec& B = c->bases[b];
-                BaseJob J;
-                J.cos_alpha = dot3(normalized3(c->h_spos[B.ids[1]] - c->h_spos[B.ids[0]]), normalized3(c->h_spos[B.ids[3]] - c->h_spos[B.ids[2]]));  // stocs.cpp:801-803
-                fill_cone_table(&J);
-                float nb_bits; memcpy(&nb_bits, &J.nb, 4);
-                hc[b] = make_float4(J.cos_alpha, J.sin_alpha, nb_bits, 0.f);
-            }
-            DevBuf<float4> d_cone;
-            int rc1 = d_cone.alloc((size_t)nB);
-            if (rc1) return rc1;
-            STOCS_HIP_CHECK(hipMemcpyAsync(d_cone.p, hc, sizeof(float4) * (size_t)nB, hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(patch_cone_kernel, dim3((unsigned)((nB + 255) / 256)), dim3(256), 0, c->stream, dj, (const float4*)d_cone.p, nB);
-            STOCS_HIP_CHECK(hipGetLastError());
-            return STOCS_OK;
-        };
-    }
-    // ONE sizing synchronisation point instead of two (plan totals, then survivors' totals): when an earlier trial of this scene
-    // has shown how long the lists get, buffers and launches are sized by a capacity (1.6 x that, per base), the kernels read the
-    // planned totals from the device, and the plan's totals come back together with the survivors' (count_pass).  A plan beyond
-    // the capacity is detected there and redone with exact sizes.  Not for a trial batch under a memory ceiling (its caller
-    // needs the totals first) and not for the first trial of a scene.
-    bool optimistic = reduce && S->hist_nB > 0 && !sw.exact_sizes;
-    if (optimistic) {
-        const double scale = sw.capacity * (double)nB / (double)S->hist_nB;
-        totP = (uint64_t)std::min(4.0e9, (double)S->hist_P * scale + sw.slack);
-        totQ = (uint64_t)std::min(4.0e9, (double)S->hist_Q * scale + sw.slack);
-        // a piece of a trial batch (too_big: its caller wants to hear when the lists do not fit the ceiling) goes this way only when the
-        // capacities are far below the ceiling -- small frames, where the plan's round trip is a tenth of the piece; near the ceiling the
-        // totals are read first, as in round 4
-        if (too_big && max_bytes && (double)(totP + totQ) * 64.0 + (use_table ? (double)(NC * nB) * 8.0 : 0.0) + (double)((size_t)nB << cell_bits) / 4.0 > 0.25 * (double)max_bytes) {
-            optimistic = false; totP = 0; totQ = 0;
+    CongruentCall(stocs_ctx* c_, const CongruentSwitches& sw_, size_t max_bytes_, int* too_big_)
+        : c(c_), sw(sw_), max_bytes(max_bytes_), too_big(too_big_), dbg(sw_.debug_timing), tprev(CallTiming::now_s()), L(0) {}
+
+    // -- stage: both streams idle, the audit started, the arena recycled, the pinned block large enough --
+    int enter() {
+        c->timing[TIMING_CONGRUENT].begin();
+        if (!c->index.built) { set_error("stocs_find_congruent_all: PPF index not built"); return STOCS_ERR_STATE; }
+        nB = (int)c->bases.size();
+        if (!c->cong) c->cong = new CongruentState();
+        S = (CongruentState*)c->cong;
+        S->valid = false;
+        STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));   // the previous trial's buffers are about to be reused
+        if (c->aux_stream) STOCS_HIP_CHECK(hipStreamSynchronize(c->aux_stream));   // (idle unless an earlier call failed half way)
+        c->audit.on = sw.debug_streams;
+        c->audit.host_sync(0); if (c->aux_stream) c->audit.host_sync(1);
+        c->audit.retire_all("stocs_find_congruent_all: the arena is recycled");
+        c->timing[TIMING_CONGRUENT].lap("entry synchronisation");
+        { int rc0 = S->arena_state.reset(); if (rc0) return rc0; }
+        tl_arena = &S->arena_state;
+        if (!S->d_trig) {   // once per context (synchronous copy from static host memory)
+            STOCS_HIP_CHECK(dev_malloc((void**)&S->d_trig, sizeof(float2) * (STOCS_MAX_CONE + 1) * STOCS_MAX_CONE));
+            STOCS_HIP_CHECK(hipMemcpy(S->d_trig, cone_trig(), sizeof(float2) * (STOCS_MAX_CONE + 1) * STOCS_MAX_CONE, hipMemcpyHostToDevice));
         }
+        // pinned block for everything this call reads back: plan totals, Q offsets (4 B per base), per-base quad offsets (8 B)
+        { int rc0 = ensure_pinned(c, (size_t)PIN_VAR + 12 * ((size_t)nB + 1) + 256); if (rc0) return rc0; }
+        c->timing[TIMING_CONGRUENT].lap("arena reset + pinned block");
+        if (dbg) { const double t_ = CallTiming::now_s(); fprintf(stderr, "[stocs congruent] %-18s %8.3f ms\n", "sync+reset", (t_ - tprev) * 1e3); tprev = t_; }
+        return STOCS_OK;
     }
-    if (!optimistic) {
-        STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
-        c->timing[TIMING_CONGRUENT].lap("wait for the device (plan)");
-        const PlanOut po = *po_pin;
-        if (!reduce) memcpy(q_off.data(), qoff_pin, 4 * ((size_t)nB + 1));
-        if (po.overflow) return lists_too_long(too_big, "pair lists exceed 2^32 entries");
-        totP = po.totP; totQ = po.totQ; plan.n_pseg = (int)po.n_pseg; plan.n_qseg = (int)po.n_qseg;
-        S->hist_P = po.totP; S->hist_Q = po.totQ; S->hist_nB = nB;
-    }
-    STOCS_TICK("plan (device)")
-    if (dbg) fprintf(stderr, "[stocs congruent] %s totP %llu totQ %llu segs %d %d\n", optimistic ? "capacities" : "planned", (unsigned long long)totP, (unsigned long long)totQ, plan.n_pseg, plan.n_qseg);
-    if (totP == 0 || totQ == 0) return STOCS_OK;
-    if (id_bits > 16) { set_error("|M| = %d: model ids beyond 16 bits do not fit the packed pairs and quads", c->nM); return STOCS_ERR_CAPACITY; }
 
-    auto reserve_arena = [&](uint64_t nP, uint64_t nQ, bool* over) -> int {
-        // everything this call allocates, estimated up front: one slab, one hipMalloc in a context's lifetime (if sizes stay put)
-        const size_t kb = wide ? 8 : 4;
-        const size_t tables = use_table ? (size_t)(NC * nB) * 8 : 0;
-        const size_t per_entry = 3 * kb + 8 + 16 + 8 + (reduce ? kb + 4 : 0);   // (the compacted copies of the reduced form)
-        const size_t occ = reduce ? 2 * (((size_t)nB << cell_bits) / 8 + 8) : 0;
+    // the cone record of a base: stocs.cpp:801-803
+    void cone_of(int b, BaseJob* J) const {
+        const BaseRec& B = c->bases[b];
+        J->cos_alpha = dot3(normalized3(c->h_spos[B.ids[1]] - c->h_spos[B.ids[0]]), normalized3(c->h_spos[B.ids[3]] - c->h_spos[B.ids[2]]));
+        fill_cone_table(J);
+    }
+
+    // -- stage: per base the job record (invariants, cone table), uploaded; then the plan of its two lookups, on the device: 2 x nB small
+    //    workgroups probe the bucket table, one workgroup lays the lists out; the host reads back four totals and the Q offsets (it sizes
+    //    the sorts with them) -- 0.2 ms of host work per trial otherwise --
+    int jobs_and_plan() {
+        const PpfIndex& ix = c->index;
+        // a batch's bases: the cone records wait until the device is busy (S->deferred, below)
+        const bool defer_cone = nB >= 512;
+        std::vector<BaseJob> jobs(nB);
+        for (int b = 0; b < nB; ++b) {
+            const BaseRec& B = c->bases[b];
+            BaseJob& J = jobs[b];
+            memset(&J, 0, sizeof(J));
+            J.inv1 = B.inv1; J.inv2 = B.inv2;
+            J.cell = cell; J.egSize = egSize;
+            if (!defer_cone) cone_of(b, &J);
+        }
+        L = PlanLayout(nB);
+        if (S->plan_bytes < L.bytes) {
+            if (S->d_plan) (void)hipFree(S->d_plan);
+            S->d_plan = NULL; S->plan_bytes = 0;
+            STOCS_HIP_CHECK(dev_malloc((void**)&S->d_plan, 2 * L.bytes));
+            S->plan_bytes = 2 * L.bytes;
+        }
+        if (S->stage_bytes < L.stage) {
+            if (S->h_stage) (void)hipHostFree(S->h_stage);
+            S->h_stage = NULL; S->stage_bytes = 0;
+            STOCS_HIP_CHECK(pinned_malloc(&S->h_stage, 2 * L.stage));   // counted: a regrow inside a trial must show up
+            S->stage_bytes = 2 * L.stage;
+        }
+        c->timing[TIMING_CONGRUENT].lap("host: jobs + cone tables + buffers");
+        char* h = (char*)S->h_stage;
+        dpl = S->d_plan;
+        plan = {(BaseJob*)(dpl + L.jobs), (Segment*)(dpl + L.pseg), (Segment*)(dpl + L.qseg), (uint32_t*)(dpl + L.qoff), (uint32_t*)(dpl + L.poff),
+                (int32_t*)(dpl + L.bids), (unsigned int*)(dpl + L.err), 0, 0};
+        S->h_qoff.assign(nB + 1, 0);
+        {
+            int32_t* bids = (int32_t*)(h + L.bids);
+            for (int b = 0; b < nB; ++b) for (int k = 0; k < 4; ++k) bids[4 * b + k] = c->bases[b].ids[k];
+            memset(h + L.err, 0, 256);
+        }
+        memcpy(h + L.jobs, jobs.data(), sizeof(BaseJob) * (size_t)nB);
+        STOCS_HIP_CHECK(hipMemcpyAsync(dpl, h, L.up, hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(plan_ranges_kernel, dim3((unsigned)nB, 2), dim3(64), 0, c->stream, ix.d_bucket_start, ix.tr, ix.rot, ix.NA, ix.nD, plan.bids,
+                           (const float4*)c->d_spos, (const float4*)c->d_snrmw, nB, (uint2*)(dpl + L.rng), (uint32_t*)(dpl + L.nr), (uint32_t*)(dpl + L.tot));
+        plan_offsets();
+        hipLaunchKernelGGL(plan_segments_kernel, dim3((unsigned)((2 * nB + 3) / 4)), dim3(256), 0, c->stream, nB, (const uint2*)(dpl + L.rng), (const uint32_t*)(dpl + L.nr),
+                           (const uint32_t*)(dpl + L.tot), plan.psegs, plan.qsegs, (const uint32_t*)plan.p_off, (const uint32_t*)plan.q_off, (const uint32_t*)(dpl + L.spo),
+                           (const uint32_t*)(dpl + L.sqo));
+        STOCS_HIP_CHECK(hipGetLastError());
+        // read-backs land in the pinned block (a copy into pageable memory -- a stack variable, a std::vector -- takes the
+        // runtime's staging path): totals in the fixed slot, the Q offsets behind the per-base quad offsets of the count pass
+        static_assert(sizeof(PlanOut) <= 256, "PlanOut must fit its pinned slot");
+        po_pin = (PlanOut*)((char*)c->h_pin + PIN_CONGRUENT);
+        STOCS_HIP_CHECK(hipMemcpyAsync(po_pin, dpl + L.out, sizeof(PlanOut), hipMemcpyDeviceToHost, c->stream));
+        if (!K.reduce) STOCS_HIP_CHECK(hipMemcpyAsync(qoff_pin(), plan.q_off, 4 * ((size_t)nB + 1), hipMemcpyDeviceToHost, c->stream));   // (reduced lists: their own offsets come later)
+        c->timing[TIMING_CONGRUENT].lap("enqueue plan upload + kernels + read-back");
+        if (defer_cone) {
+            // staged in the pinned block behind the upload, uploaded and patched into the device's jobs on the context's stream -- behind
+            // the plan kernels, ahead of the join
+            float4* hc = (float4*)(h + L.cone);
+            BaseJob* dj = plan.jobs;
+            S->deferred = [this, hc, dj]() -> int {
+                for (int b = 0; b < nB; ++b) {
+                    BaseJob J;
+                    cone_of(b, &J);
+                    float nb_bits; memcpy(&nb_bits, &J.nb, 4);
+                    hc[b] = make_float4(J.cos_alpha, J.sin_alpha, nb_bits, 0.f);
+                }
+                DevBuf<float4> d_cone;
+                int rc1 = d_cone.alloc((size_t)nB);
+                if (rc1) return rc1;
+                STOCS_HIP_CHECK(hipMemcpyAsync(d_cone.p, hc, sizeof(float4) * (size_t)nB, hipMemcpyHostToDevice, c->stream));
+                hipLaunchKernelGGL(patch_cone_kernel, dim3((unsigned)((nB + 255) / 256)), dim3(256), 0, c->stream, dj, (const float4*)d_cone.p, nB);
+                STOCS_HIP_CHECK(hipGetLastError());
+                return STOCS_OK;
+            };
+        }
+        return STOCS_OK;
+    }
+    uint32_t* qoff_pin() const { return (uint32_t*)((char*)c->h_pin + PIN_VAR + 8 * ((size_t)nB + 1)); }
+    // the layout kernel of the plan (again before the redo: the base jobs carry the survivors' offsets by then, its inputs are still in the
+    // planning buffer), and what it leaves behind for the passes declared to the stream audit
+    void plan_offsets() {
+        launch_plan_offsets(c->stream, nB, dpl, L, plan);
+        c->audit.step(0, "plan kernels", {}, {{plan.jobs, "base jobs"}, {plan.psegs, "P segments"}, {plan.qsegs, "Q segments"}, {plan.q_off, "Q offsets per base"}});
+    }
+
+    // -- stage: the sizes of the first pass.  ONE sizing synchronisation point instead of two (plan totals, then survivors' totals): when an
+    //    earlier trial of this scene has shown how long the lists get, buffers and launches are sized by a capacity (1.6 x that, per base),
+    //    the kernels read the planned totals from the device, and the plan's totals come back together with the survivors' (the count pass).
+    //    A plan beyond the capacity is detected there and redone with exact sizes.  Not for a trial batch under a memory ceiling (its
+    //    caller needs the totals first) and not for the first trial of a scene.  *done: the lists are empty or too long. --
+    int size_lists(bool* done, int* rc_done) {
+        *done = false;
+        optimistic = K.reduce && S->hist_nB > 0 && !sw.exact_sizes;
+        if (optimistic) {
+            const double scale = sw.capacity * (double)nB / (double)S->hist_nB;
+            totP = (uint64_t)std::min(4.0e9, (double)S->hist_P * scale + sw.slack);
+            totQ = (uint64_t)std::min(4.0e9, (double)S->hist_Q * scale + sw.slack);
+            // a piece of a trial batch (too_big: its caller wants to hear when the lists do not fit the ceiling) goes this way only when the
+            // capacities are far below the ceiling -- small frames, where the plan's round trip is a tenth of the piece; near the ceiling the
+            // totals are read first, as in round 4
+            if (too_big && max_bytes && (double)(totP + totQ) * 64.0 + (K.use_table ? (double)(K.NC * nB) * 8.0 : 0.0) + (double)((size_t)nB << K.cell_bits) / 4.0 > 0.25 * (double)max_bytes) {
+                optimistic = false; totP = 0; totQ = 0;
+            }
+        }
+        if (!optimistic) {
+            STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
+            c->timing[TIMING_CONGRUENT].lap("wait for the device (plan)");
+            const PlanOut po = *po_pin;
+            if (!K.reduce) memcpy(S->h_qoff.data(), qoff_pin(), 4 * ((size_t)nB + 1));
+            if (po.overflow) { *done = true; *rc_done = lists_too_long(too_big, "pair lists exceed 2^32 entries"); return STOCS_OK; }
+            totP = po.totP; totQ = po.totQ; plan.n_pseg = (int)po.n_pseg; plan.n_qseg = (int)po.n_qseg;
+            S->hist_P = po.totP; S->hist_Q = po.totQ; S->hist_nB = nB;
+        }
+        STOCS_TICK("plan (device)")
+        if (dbg) fprintf(stderr, "[stocs congruent] %s totP %llu totQ %llu segs %d %d\n", optimistic ? "capacities" : "planned", (unsigned long long)totP, (unsigned long long)totQ, plan.n_pseg, plan.n_qseg);
+        if (totP == 0 || totQ == 0) { *done = true; *rc_done = STOCS_OK; return STOCS_OK; }
+        if (K.id_bits > 16) { set_error("|M| = %d: model ids beyond 16 bits do not fit the packed pairs and quads", c->nM); return STOCS_ERR_CAPACITY; }
+        return STOCS_OK;
+    }
+
+    // everything a pass allocates, estimated up front: one slab, one hipMalloc in a context's lifetime (if sizes stay put)
+    int reserve_arena(uint64_t nP, uint64_t nQ, bool* over) {
+        const size_t kb = K.wide ? 8 : 4;
+        const size_t tables = K.use_table ? (size_t)(K.NC * nB) * 8 : 0;
+        const size_t per_entry = 3 * kb + 8 + 16 + 8 + (K.reduce ? kb + 4 : 0);   // (the compacted copies of the reduced form)
+        const size_t occ = K.reduce ? 2 * (((size_t)nB << K.cell_bits) / 8 + 8) : 0;
         const size_t need = (size_t)nP * per_entry + (size_t)nQ * per_entry + tables + occ + ((size_t)48 << 20);
         if (max_bytes && need > max_bytes && nB > 1) { *over = true; return STOCS_OK; }
         // (under a ceiling -- a piece of a trial batch -- the slab is 1.5 x the need, not twice it: 40 Cm trials need 36 GB)
         const int rc_r = S->arena_state.reserve(need, (max_bytes && need > ((size_t)4 << 30)) ? 1.5 : 2.0);   // (small pieces: room for the next call's capacities, which follow THIS call's totals)
         if (rc_r == STOCS_ERR_NOMEM && max_bytes && nB > 1) { *over = true; return STOCS_OK; }   // the device is fuller than the ceiling assumes: the caller halves the piece
         return rc_r;
-    };
-    {
-        bool over = false;
-        int rc0 = reserve_arena(totP, totQ, &over);
-        if (rc0) return rc0;
-        if (over) return lists_too_long(too_big, "pair lists beyond the memory ceiling");   // the caller splits its base set
     }
-    c->timing[TIMING_CONGRUENT].lap(!use_table ? "arena reserve (no run table, 64-bit keys)" : (wide ? "arena reserve (64-bit keys)" : "arena reserve"));   // (names the form)
-    S->nB = nB; S->totP = (uint32_t)totP; S->totQ = (uint32_t)totQ; S->nepsilon = nepsilon;
-    S->half_inv_neps = (float)(0.5 / (double)nepsilon);
-    S->NC = NC; S->use_table = use_table; S->wide = wide; S->reduce = reduce;
-    {   // two points of one position cell are at most a cell diagonal apart (cell edge = ratio / egSize < 2 epsilon); the
-        // float roundings of the two world-space points and of the unit-cube coordinates are far below the 1e-5 m allowed for
-        const double cell_world = (double)c->ratio / (double)egSize, diag2 = 3.0 * (cell_world * 1.001 + 1e-5) * (cell_world * 1.001 + 1e-5);
-        S->close_cells = diag2 < 0.999 * (double)c->prm.distance_threshold && !sw.distance_gate;
-    }
-    S->id_bits = id_bits; S->base_bits = base_bits; S->cell_bits = cell_bits;
-    S->base_in_key = 4 * id_bits + base_bits <= 64;
-    S->no_quads = false;
-    const PlanOut* d_po = optimistic ? (const PlanOut*)(dpl + L.out) : NULL;
-    bool outgrown = false;
-    int rc = wide ? count_pass<uint64_t>(c, S, plan, sw, tprev, d_po, optimistic ? po_pin : NULL, &outgrown)
-                  : count_pass<uint32_t>(c, S, plan, sw, tprev, d_po, optimistic ? po_pin : NULL, &outgrown);
-    if (rc) return rc;   // (on an error the read-back may not have landed: the capacity history stays as it was)
-    if (optimistic) {    // the read-back of count_pass brought the plan's totals
-        const PlanOut po = *po_pin;
-        if (po.overflow) return lists_too_long(too_big, "pair lists exceed 2^32 entries");
-        S->hist_P = po.totP; S->hist_Q = po.totQ; S->hist_nB = nB;
-        if (outgrown) {
-            // the plan outgrew the capacities: once more with the sizes now known.  The base jobs carry the survivors' offsets by now:
-            // the layout kernel writes the planned ones again (its inputs are still in the planning buffer)
-            c->timing[TIMING_CONGRUENT].lap("plan beyond the capacities: redone with exact sizes");
-            launch_plan_offsets(c->stream, nB, dpl, L, plan);
-            STOCS_HIP_CHECK(hipGetLastError());
-            { int rc0 = S->arena_state.reset(); if (rc0) return rc0; }
-            tl_arena = &S->arena_state;
-            bool over = false;
-            int rc0 = reserve_arena(po.totP, po.totQ, &over);
+
+    // -- stage: one count pass over lists of nP and nQ entries (capacities when `with_capacities`): the arena reserved, the state the pass and
+    //    the later calls read set, the form decided, the pass run.  The first pass and the redo of an outgrown plan both come through here;
+    //    the redo recycles the arena first.  *done: the lists do not fit the ceiling (the caller of a batch's piece splits its base set). --
+    int pass(uint64_t nP, uint64_t nQ, bool with_capacities, bool redo, bool* outgrown, bool* done, int* rc_done) {
+        *done = false; *outgrown = false;
+        if (redo) {
+            int rc0 = S->arena_state.reset();
             if (rc0) return rc0;
-            if (over) return lists_too_long(too_big, "pair lists beyond the memory ceiling");   // (a batch's piece: the caller splits its base set)
-            plan.n_pseg = (int)po.n_pseg; plan.n_qseg = (int)po.n_qseg;
-            S->totP = (uint32_t)po.totP; S->totQ = (uint32_t)po.totQ;
-            S->no_quads = false;
-            if (po.totP == 0 || po.totQ == 0) return STOCS_OK;
-            rc = wide ? count_pass<uint64_t>(c, S, plan, sw, tprev, NULL, NULL, &outgrown) : count_pass<uint32_t>(c, S, plan, sw, tprev, NULL, NULL, &outgrown);
-            if (rc) return rc;
+            tl_arena = &S->arena_state;
         }
+        bool over = false;
+        int rc = reserve_arena(nP, nQ, &over);
+        if (rc) return rc;
+        if (over) { *done = true; *rc_done = lists_too_long(too_big, "pair lists beyond the memory ceiling"); return STOCS_OK; }
+        const PassForm F = pass_form(c, K, sw, nB, (size_t)(uint32_t)nP, (size_t)(uint32_t)nQ, with_capacities);
+        if (!redo) c->timing[TIMING_CONGRUENT].lap(F.reserve_label());   // (names the form)
+        S->nB = nB; S->totP = (uint32_t)nP; S->totQ = (uint32_t)nQ; S->nepsilon = nepsilon;
+        S->half_inv_neps = (float)(0.5 / (double)nepsilon);
+        S->NC = K.NC; S->use_table = K.use_table; S->wide = K.wide; S->reduce = K.reduce;
+        {   // two points of one position cell are at most a cell diagonal apart (cell edge = ratio / egSize < 2 epsilon); the
+            // float roundings of the two world-space points and of the unit-cube coordinates are far below the 1e-5 m allowed for
+            const double cell_world = (double)c->ratio / (double)egSize, diag2 = 3.0 * (cell_world * 1.001 + 1e-5) * (cell_world * 1.001 + 1e-5);
+            S->close_cells = diag2 < 0.999 * (double)c->prm.distance_threshold && !sw.distance_gate;
+        }
+        S->id_bits = K.id_bits; S->base_bits = K.base_bits; S->cell_bits = K.cell_bits;
+        S->base_in_key = 4 * K.id_bits + K.base_bits <= 64;
+        S->no_quads = false;
+        const PlanOut* d_po = F.optimistic ? (const PlanOut*)(dpl + L.out) : NULL;
+        const PlanOut* pin = F.optimistic ? po_pin : NULL;
+        return K.wide ? CountPass<uint64_t>(c, S, plan, F, dbg, tprev, d_po, pin).run(outgrown) : CountPass<uint32_t>(c, S, plan, F, dbg, tprev, d_po, pin).run(outgrown);
     }
-    if (!c->audit.violations.empty()) {   // STOCS_DEBUG_STREAMS: a use without an event edge between the two streams
-        set_error("stocs_find_congruent_all: %zu stream-ordering violation(s); first: %s", c->audit.violations.size(), c->audit.violations[0].c_str());
-        c->audit.violations.clear();
-        return STOCS_ERR_STATE;
+
+    int run(int64_t* total_quads) {
+        int rc = enter();
+        if (rc) return rc;
+        c->quad_off.assign(nB + 1, 0);
+        c->quad_id_bits = 16;
+        if (total_quads) *total_quads = 0;
+        if (nB == 0) return STOCS_OK;
+        if (nB >= (1 << 20)) { set_error("too many bases"); return STOCS_ERR_INVALID; }
+        const float eps_unit = c->prm.distance_threshold / c->ratio;  // getNormalizedEpsilon, pairCreationFunctor.h:141-143
+        const int gridDepth = (int)(-log2f(eps_unit));                // normalset.h:117
+        egSize = (int)pow(2.0, (double)gridDepth);                    // :118
+        cell = 1.f / egSize;                                          // :119
+        nepsilon = (float)((double)(1.0f / 7.0f) + 0.00001);          // normalset.h:86
+        K = key_layout(nB, c->nM, egSize, sw);
+        if ((rc = jobs_and_plan())) return rc;
+        bool done = false, outgrown = false;
+        int rc_done = STOCS_OK;
+        if ((rc = size_lists(&done, &rc_done)) || done) return rc ? rc : rc_done;
+        if ((rc = pass(totP, totQ, optimistic, false, &outgrown, &done, &rc_done)) || done) return rc ? rc : rc_done;   // (on an error the read-back may not have landed: the capacity history stays as it was)
+        if (optimistic) {    // the read-back of the count pass brought the plan's totals
+            const PlanOut po = *po_pin;
+            if (po.overflow) return lists_too_long(too_big, "pair lists exceed 2^32 entries");
+            S->hist_P = po.totP; S->hist_Q = po.totQ; S->hist_nB = nB;
+            if (outgrown) {
+                // the plan outgrew the capacities: once more with the sizes now known, the planned offsets written into the base jobs again
+                c->timing[TIMING_CONGRUENT].lap("plan beyond the capacities: redone with exact sizes");
+                plan_offsets();
+                STOCS_HIP_CHECK(hipGetLastError());
+                plan.n_pseg = (int)po.n_pseg; plan.n_qseg = (int)po.n_qseg;
+                if (po.totP == 0 || po.totQ == 0) return STOCS_OK;
+                if ((rc = pass(po.totP, po.totQ, false, true, &outgrown, &done, &rc_done)) || done) return rc ? rc : rc_done;
+            }
+        }
+        if (!c->audit.violations.empty()) {   // STOCS_DEBUG_STREAMS: a use without an event edge between the two streams
+            set_error("stocs_find_congruent_all: %zu stream-ordering violation(s); first: %s", c->audit.violations.size(), c->audit.violations[0].c_str());
+            c->audit.violations.clear();
+            return STOCS_ERR_STATE;
+        }
+        if (S->no_quads) return STOCS_OK;   // as with empty lists: nothing to materialise, every base has zero quads
+        S->valid = true;
+        c->quad_id_bits = K.id_bits;
+        if (total_quads) *total_quads = (int64_t)c->quad_off[nB];
+        return STOCS_OK;
     }
-    if (S->no_quads) return STOCS_OK;   // as with empty lists: nothing to materialise, every base has zero quads
-    S->valid = true;
-    c->quad_id_bits = id_bits;
-    if (total_quads) *total_quads = (int64_t)c->quad_off[nB];
-    return STOCS_OK;
-}
+};
 
 }  // namespace stocs
 
@@ -1973,7 +1709,8 @@ int stocs_internal_find_congruent(stocs_ctx* c, int64_t* total_quads, size_t max
     if (!c) return STOCS_ERR_INVALID;
     if (too_big) *too_big = 0;
     DeviceGuard dev_guard(c->device);
-    const int rc = find_congruent(c, CongruentSwitches::read(), total_quads, max_bytes, too_big);
+    const CongruentSwitches sw = CongruentSwitches::read();
+    const int rc = CongruentCall(c, sw, max_bytes, too_big).run(total_quads);
     // The one exit.  The deferred host work never outlives the call, and a failed call leaves nothing in flight: no read-back still
     // landing in the pinned block (ensure_pinned may free it), nothing still running on the auxiliary stream.  The synchronisation's
     // own status is ignored (the first error message stands); a successful call is synchronised at the next one's entry.

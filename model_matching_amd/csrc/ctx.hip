@@ -853,8 +853,7 @@ int stocs_debug_stream_audit_selftest(int scenario, char* first_msg, int cap) {
     int buf_a = 0, buf_b = 0, ev_fork = 0, ev_join = 0;
     A.use(0, &buf_a, true, "a", "produce a (main)");
     if (scenario != 1) { A.record(&ev_fork, 0); A.wait(1, &ev_fork); }
-    A.use(1, &buf_a, false, "a", "consume a (aux)");
-    A.use(1, &buf_b, true, "b", "produce b (aux)");
+    A.step(1, "consume a, produce b (aux)", {{&buf_a, "a"}}, {{&buf_b, "b"}});   // (a whole step in one declaration, as the library makes them)
     if (scenario == 4) A.use(0, &buf_a, true, "a", "overwrite a (main)");
     if (scenario != 2 && scenario != 3) { A.record(&ev_join, 1); A.wait(0, &ev_join); }
     if (scenario != 3) A.use(0, &buf_b, false, "b", "consume b (main)");

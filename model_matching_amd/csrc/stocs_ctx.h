@@ -335,7 +335,7 @@ struct stocs_ctx {
     hipStream_t own_stream;   // created with the context; `stream` may point to a caller's stream instead
     hipStream_t aux_stream;   // second stream of the context for work that is independent of `stream` until an event joins it
     hipEvent_t ev0, ev1, ev_fork, ev_join;
-    hipEvent_t ev_t[10];   // timing events around the device groups of stocs_find_congruent_all (always recorded; read after the call's own sync)
+    hipEvent_t ev_t[10];   // stocs_find_congruent_all: clock stamps around its device groups (opt-in) and three ordering events, named by CongEvent below; other calls borrow slots as plain clock stamps
     int nS, nM;
     stocs::Thresholds thr;
 
@@ -475,6 +475,32 @@ inline void clear_trial_batch(stocs_ctx* c) {
     c->base_seed.clear(); c->base_local.clear(); c->trial_first_base.clear(); c->trial_cand_off.clear();
     c->snrmw_trial0 = NULL; c->snrmw_stride = 0;
     c->bases.clear(); c->quad_off.clear(); clear_candidates(c);   // what is left of the batch's last piece means nothing to a single trial
+}
+// The ev_t slots as stocs_find_congruent_all uses them.  The first seven are CLOCK STAMPS only: recorded when the device clock is on
+// (c->device_clock; an event between two kernels costs ~5 us on this runtime) and read after the call's closing synchronisation.
+// The last three also ORDER work: the host waits on EV_SURVIVORS_READ in every reduced pass, and EV_Q_MARKED / EV_P_MARKED are the
+// cross edges of the two-stream form (each list's counts test the OTHER list's occupancy); those two are recorded when the pass has
+// two streams or the device clock is on.
+enum CongEvent {
+    EV_SORT_BEGIN = 0, EV_Q_SORTED = 1, EV_P_SORTED = 2, EV_SIDES_JOINED = 3, EV_JOIN_COUNTED = 4, EV_PASS_END = 5, EV_REDUCE_BEGIN = 6,
+    EV_SURVIVORS_READ = 7, EV_Q_MARKED = 8, EV_P_MARKED = 9
+};
+// An event edge between the context's two streams and its mirror in the stream audit, as one call: `record` stamps what `from` holds
+// now, `wait` puts whatever `to` is given from now on behind it.  Streams by their audit index: 0 = c->stream, 1 = c->aux_stream.
+inline hipStream_t ctx_stream(const stocs_ctx* c, int s) { return s ? c->aux_stream : c->stream; }
+inline int stream_edge_record(stocs_ctx* c, hipEvent_t ev, int from) {
+    STOCS_HIP_CHECK(hipEventRecord(ev, ctx_stream(c, from)));
+    c->audit.record(ev, from);
+    return STOCS_OK;
+}
+inline int stream_edge_wait(stocs_ctx* c, hipEvent_t ev, int to) {
+    STOCS_HIP_CHECK(hipStreamWaitEvent(ctx_stream(c, to), ev, 0));
+    c->audit.wait(to, ev);
+    return STOCS_OK;
+}
+inline int stream_edge(stocs_ctx* c, hipEvent_t ev, int from, int to) {
+    const int rc = stream_edge_record(c, ev, from);
+    return rc ? rc : stream_edge_wait(c, ev, to);
 }
 inline float* cand_T(stocs_ctx* c) { return (float*)c->d_cand; }
 inline float* cand_P(stocs_ctx* c) { return (float*)c->d_cand + (size_t)c->cand_cap * 16; }

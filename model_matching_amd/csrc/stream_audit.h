@@ -3,8 +3,9 @@
 // stocs_find_congruent_all and stocs_make_transforms run part of their work on the context's auxiliary stream.  Every buffer such a
 // section touches must be ordered between the streams by an event edge: main -> aux before the first use on the auxiliary stream,
 // aux -> main before the next use on the main stream (or before the arena is recycled).  A missing edge does not fail -- it reads
-// stale data once in a while.  With STOCS_DEBUG_STREAMS=1 the entry points describe what they enqueue -- use(stream, buffer,
-// read / write), record(event, stream), wait(stream, event), host_sync(stream) -- and this checker keeps a vector clock per stream,
+// stale data once in a while.  With STOCS_DEBUG_STREAMS=1 the entry points describe what they enqueue -- step(stream, name, buffers
+// read, buffers written) (or use(stream, buffer, read / write) for a single buffer), record(event, stream), wait(stream, event) (both
+// made by stream_edge of stocs_ctx.h together with the edge itself), host_sync(stream) -- and this checker keeps a vector clock per stream,
 // a clock snapshot per event and the last write / last reads of every buffer: a use that is not ordered behind the conflicting
 // use of the other stream is reported (the call then returns STOCS_ERR_STATE naming buffer and kernel).  Nothing of this touches
 // the device; the launches are the same with and without it (DESIGN.md 3 holds the audited table).
@@ -14,6 +15,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
+#include <initializer_list>
 #include <map>
 #include <string>
 #include <vector>
@@ -58,6 +60,13 @@ struct StreamAudit {
         } else {
             b.has_read[t] = true; b.reads[t].stream = t; b.reads[t].tick = vc[t].c[t]; b.reads[t].what = what;
         }
+    }
+    // one enqueued step as a whole, declared where it is launched: what it reads, then what it writes (a NULL buffer is not part of the step)
+    struct Buf { const void* p; const char* name; };
+    void step(int t, const char* what, std::initializer_list<Buf> reads, std::initializer_list<Buf> writes) {
+        if (!on) return;
+        for (const Buf& b : reads) use(t, b.p, false, b.name, what);
+        for (const Buf& b : writes) use(t, b.p, true, b.name, what);
     }
     void record(const void* ev, int s) { if (on) events[ev] = vc[s]; }
     void wait(int t, const void* ev) {

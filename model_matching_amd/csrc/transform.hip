@@ -276,19 +276,16 @@ static int enqueue_device_picks(stocs_ctx* c, const CandLayout& L, bool batch, u
     const uint32_t hmask = pick_table_mask(max_per_base);
     const size_t lds = (size_t)(2 * (hmask + 1) + ((max_per_base + 1) & ~1)) * 4 + (size_t)max_per_base * 8;
     STOCS_HIP_CHECK(hipMemcpyAsync(d_var, (char*)c->h_pin + PIN_VAR, (batch ? L.trial : L.table) + 16 * nbases, hipMemcpyHostToDevice, c->stream));
-    STOCS_HIP_CHECK(hipEventRecord(c->ev_fork, c->stream));
-    STOCS_HIP_CHECK(hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
-    c->audit.use(0, d_table, true, "pick table", "table upload"); c->audit.record(c->ev_fork, 0); c->audit.wait(1, c->ev_fork);
-    const int rc = stocs_internal_prepare_small(c, max_per_base);
+    c->audit.step(0, "table upload", {}, {{d_table, "pick table"}});
+    int rc = stream_edge(c, c->ev_fork, 0, 1);
+    if (rc) return rc;
+    rc = stocs_internal_prepare_small(c, max_per_base);
     if (rc) return rc;
     hipLaunchKernelGGL(draw_picks_kernel, dim3((unsigned)nbases), dim3(256), lds, c->aux_stream, (const uint4*)d_table,
                        batch ? Carve::at<const uint4>(d_var, L.trial) : (const uint4*)NULL, seed, max_per_base, hmask, d_picks, dB);
     STOCS_HIP_CHECK(hipGetLastError());
-    STOCS_HIP_CHECK(hipEventRecord(c->ev_join, c->aux_stream));
-    STOCS_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
-    c->audit.use(1, d_table, false, "pick table", "draw picks"); c->audit.use(1, d_picks, true, "picks", "draw picks"); c->audit.use(1, dB, true, "job bases", "draw picks");
-    c->audit.record(c->ev_join, 1); c->audit.wait(0, c->ev_join);
-    return STOCS_OK;
+    c->audit.step(1, "draw picks", {{d_table, "pick table"}}, {{d_picks, "picks"}, {dB, "job bases"}});
+    return stream_edge(c, c->ev_join, 1, 0);
 }
 
 }  // namespace stocs

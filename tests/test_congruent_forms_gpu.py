@@ -1,4 +1,4 @@
-"""Every form of the congruent-set phase against the CPU oracle (stocs_internal_find_congruent / count_pass, csrc/congruent.hip).
+"""Every form of the congruent-set phase against the CPU oracle (stocs_internal_find_congruent / CountPass, csrc/congruent.hip).
 
 The phase picks its form per call: pair lists reduced to the entries with a partner cell or kept whole, 32- or 64-bit list keys, one
 stream or two, the library's own sort or rocPRIM's, sizes from a capacity or exact -- and per batch size: cone records computed late from
@@ -258,7 +258,8 @@ def test_switches_read_once_per_process_equal_the_oracle(forms, tmp_path):
     np.savez(path, ids=bi, inv=bv)
     refs = [cache.get(bi[k], bv[k]) for k in range(len(bi))]
     cells = [{"STOCS_SORT": "rocprim"}, {"STOCS_SORT": "rocprim", "STOCS_CONGRUENT_KEEP_ALL": "1"},
-             {"STOCS_GATHER_WGS": "1"}, {"STOCS_GATHER_WGS": "3"}, {"STOCS_GATHER_WGS": "7"}]
+             {"STOCS_GATHER_WGS": "1"}, {"STOCS_GATHER_WGS": "3"}, {"STOCS_GATHER_WGS": "7"},
+             {"STOCS_GATHER_WGS": "3", "STOCS_CONGRUENT_TWO_STREAMS": "1"}]   # (one list per launch, first side 0 and 1, many tiles per workgroup)
     for cell in cells:
         env = {k: v for k, v in os.environ.items() if k not in SWITCHES and k not in ("STOCS_SORT", "STOCS_GATHER_WGS")}
         env.update(cell)
