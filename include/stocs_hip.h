@@ -1604,6 +1604,15 @@ int stocs_preprocess_model_mesh(const float* pos3, int nv, const int32_t* tris3,
  *   inside the cell's cone can pass the 30-degree test against the rotated model normal; 0 = the forms without the gate; any
  *   other value is STOCS_ERR_INVALID.  A dropped query is one the ungated kernel would not count: same scores, bitwise.  The
  *   per-point detail forms and the cross-check kernels (lcp_variant 0, 31, exact_ties) never gate.
+ * "lcp_patch_normals": 1 (default; STOCS_LCP_PATCH_NORMALS=0 in the environment turns it off at context creation) = the patch test
+ *   of the shared-list forms ("lcp_split" 1, "lcp_cull_unit" 16, models of 512 to 8 192 points -- from 64 points on dense grids, which
+ *   split every model) also drops a 16-point sub-patch when no scene normal within reach of it can pass the 30-degree test against
+ *   any of its rotated normals: a cone of the scene normals per cell of the distance field against a cone per sub-patch
+ *   (csrc/patch_normals.h); 0 = the sphere test alone; any other value is STOCS_ERR_INVALID.  A dropped sub-patch holds no point the
+ *   kernel would count: same scores, bitwise.  Every other kernel form never runs the test, and a context that runs none of those
+ *   forms never fills the field: the first launch of a shared-list form with the option on does (once per scene).  Its memory is
+ *   taken with the scene's grid, when the option is on and the model's size allows such a form; turned on later, the option takes
+ *   effect from the next scene.
  * "lcp_split": 1 (default) = four wavefronts share a candidate's model points, 0 = one wavefront per candidate.  Scores are
  *   accumulated as integers, so neither option changes a single bit of them.
  * "lcp_order": 0 = candidates in batch order, 1 (default) = big batches against scenes whose lists do not stay in the caches
@@ -1689,6 +1698,27 @@ int stocs_model_patch_order(const float* model_pos3, int nM, int32_t* perm, floa
  * 16-slot runs) and the bounding sphere of every run of 16 consecutive slots (centre x, y, z in the centred frame, radius),
  * ceil(nM / 16) of them. */
 int stocs_model_subpatches(const float* model_pos3, int nM, int32_t* perm, float* spheres4);
+/* The normal cone of each of those runs ("lcp_patch_normals"), on the host likewise: the same perm, and per run of 16 slots the unit
+ * axis of its normals (x, y, z) and sb >= sin(beta), beta the largest angle of a member normal (model_nrm3 normalised in float, as
+ * stocs_ctx_create does) against that axis, rounded outwards; sb < 0: the run takes no part in the test (beta above 45 degrees, a
+ * normal that is not finite or has no direction).  ceil(nM / 16) records. */
+int stocs_model_subpatch_normals(const float* model_pos3, const float* model_nrm3, int nM, int32_t* perm, float* records4);
+/* The left-hand side of that test on the host (csrc/patch_normals.h, the function the kernel runs): for the field word `cone_word`
+ * (octahedral axis of 2 x 12 bits, class k in bits 24..31), the rotated model axis v3, the model record's sb and the norm bound s of the
+ * matrix.  *outside = 1 when v3 lies outside the scene cone (only then is a sub-patch ruled out).  axis3 (may be NULL) receives the axis
+ * of the word as the kernel decodes it, not normalised. */
+float stocs_patch_normal_bound_host(uint32_t cone_word, const float* v3, float sb, float s, int* outside, float* axis3);
+/* Test aid for "lcp_patch_normals" (no reference counterpart): over n candidate transforms (device, column-major 4x4) and every
+ * sub-patch of the model, out[0] = the sub-patches the sphere test leaves alive, out[1] = those of them that the normal-cone test rules
+ * out, out[2] = those of out[1] that hold a point which the per-point detail form counts (must be 0).  Fills the distance field and
+ * the cone field of the scene if need be.  All zero when the scene has no cone field (a model no shared-list form can
+ * score: more than 8 192 points, or fewer than 512 on a sparse grid; the option off when the scene was set; an empty scene). */
+int stocs_lcp_patch_normal_count(stocs_ctx* ctx, const void* d_T16, int n, int64_t out[3]);
+/* What the context holds for "lcp_patch_normals" (host records, no device work): out[0] = the reach of the current scene's cone field
+ * as the kernels are given it, in the units of the clouds (at most 5.9 cells of the distance field: csrc/patch_normals.h), 0 without
+ * a field; out[1] = cells a scene point reaches on either side when the field is filled; out[2] = 1 when the field has been filled;
+ * out[3] = the scoring launches of this context so far that ran a shared-list form WITH the cone test (counted over all scenes). */
+int stocs_patch_normal_info(stocs_ctx* ctx, double out[4]);
 /* The reference-order kd-tree of the "exact_ties" option on the host, for tests: builds the tree over n points pos3 as the reference
  * builds it (64 points per leaf, depth 32, widest axis split at the box midpoint, the same in-place partition) and answers nq
  * radius queries q3 with the query function the device runs: idx[i] = the reference's doQueryRestrictedClosestIndex(q3[i], sqdist),

@@ -389,6 +389,10 @@ SIGNATURES = {
     "stocs_get_grid_octants": (C.c_int, [_vp, _i64p]),
     "stocs_model_patch_order": (C.c_int, [_fp, C.c_int, _ip, _fp]),
     "stocs_model_subpatches": (C.c_int, [_fp, C.c_int, _ip, _fp]),
+    "stocs_model_subpatch_normals": (C.c_int, [_fp, _fp, C.c_int, _ip, _fp]),
+    "stocs_patch_normal_bound_host": (C.c_float, [C.c_uint32, _fp, C.c_float, C.c_float, _intp, _fp]),
+    "stocs_lcp_patch_normal_count": (C.c_int, [_vp, _vp, C.c_int, _i64p]),
+    "stocs_patch_normal_info": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     "stocs_kdtree_nn_host": (C.c_int, [_fp, C.c_int, _fp, C.c_int, C.c_float, _ip]),
     "stocs_last_tie_counts": (C.c_int, [_vp, _i64p, _i64p]),
     "stocs_set_stream": (C.c_int, [_vp, _vp]),

@@ -13,6 +13,7 @@
 #include <numeric>
 
 #include "normal_cone.h"
+#include "patch_normals.h"
 #include "prims.h"
 #include "stocs_ctx.h"
 
@@ -338,7 +339,7 @@ static int load_scene_impl(stocs_ctx* c, const float* sp, const float* sn, const
     if (!rc && c->exact_ties) { rc = ensure_kdtree(c); lap("kd-tree (exact_ties)"); }
     if (!rc && c->prev_scene_warm && c->lcp_cull == 1 && c->grid.d_dist && c->d_mpatch && c->aux_stream) {
         // (the grid build has synchronised c->stream: the scene arrays the fill reads are in place)
-        rc = fill_cull_field(c, c->aux_stream);
+        rc = fill_cull_field(c, c->aux_stream, false);   // (the cone field waits for the first launch that wants it)
         if (!rc) { STOCS_HIP_CHECK(hipEventRecord(c->ev_cull, c->aux_stream)); c->cull_pending = true; }
     }
     // per-trial state belongs to the old scene
@@ -476,6 +477,41 @@ static void model_patch_order(const std::vector<V3>& mpos, const std::vector<V3>
     for (int q = 0; q < (nM + 15) / 16; ++q) sub[q] = sphere(16 * q, std::min(nM, 16 * q + 16));
 }
 
+// The normal cone of every 16-point sub-patch (patch_normals.h): the axis is the normalised mean of the member normals as a float triple,
+// sb >= sin(beta) with beta the largest angle of a member against THAT triple, in double, rounded outwards.  No test (w < 0) for a
+// sub-patch with beta above 45 degrees, with a normal that is not finite or not of unit length within 1e-6, without an axis, and for the
+// padding.  mnrm: the normals as the context keeps them (normalised in float), original order; n_rec >= the sub-patches of the model.
+static void model_subpatch_normals(const std::vector<V3>& mnrm, const std::vector<int32_t>& perm, size_t n_rec, std::vector<float4>& rec) {
+    const int nM = (int)mnrm.size();
+    rec.assign(n_rec, make_float4(0.f, 0.f, 0.f, STOCS_PN_NO_TEST));
+    for (int q = 0; q < (nM + 15) / 16; ++q) {
+        const int lo = 16 * q, hi = std::min(nM, lo + 16);
+        double sx = 0, sy = 0, sz = 0;
+        bool bad = false;
+        for (int k = lo; k < hi; ++k) {
+            const V3 n = mnrm[perm[k]];
+            const double n2 = (double)n.x * n.x + (double)n.y * n.y + (double)n.z * n.z;
+            if (!(n2 >= (1.0 - 1.0e-6) * (1.0 - 1.0e-6) && n2 <= (1.0 + 1.0e-6) * (1.0 + 1.0e-6))) bad = true;   // (NaN included)
+            sx += n.x; sy += n.y; sz += n.z;
+        }
+        const double l = sqrt(sx * sx + sy * sy + sz * sz);
+        if (bad || !(l > 1.0e-6)) continue;
+        const float a[3] = {(float)(sx / l), (float)(sy / l), (float)(sz / l)};
+        const double a2 = (double)a[0] * a[0] + (double)a[1] * a[1] + (double)a[2] * a[2];
+        double cmin = 1.0;
+        for (int k = lo; k < hi; ++k) {
+            const V3 n = mnrm[perm[k]];
+            const double n2 = (double)n.x * n.x + (double)n.y * n.y + (double)n.z * n.z;
+            cmin = std::min(cmin, ((double)n.x * a[0] + (double)n.y * a[1] + (double)n.z * a[2]) / sqrt(n2 * a2));
+        }
+        if (!(cmin > 0.0)) continue;
+        const double sb = sqrt(std::max((1.0 - cmin) * (1.0 + cmin), 0.0)) * (1.0 + 1.0e-6) + 1.0e-7;   // (outwards: double rounding, then the float's)
+        const float sbf = nextafterf((float)sb, 2.0f);
+        if (!(sbf <= STOCS_PN_MAX_SIN_BETA)) continue;
+        rec[q] = make_float4(a[0], a[1], a[2], sbf);
+    }
+}
+
 // the model order and spheres of a model as stocs_ctx_create computes them, without a context (CPU tests)
 static void model_patch_order_host(const float* model_pos3, int nM, std::vector<int32_t>& perm, std::vector<float4>& patch, std::vector<float4>& sub) {
     // centroid_shift and the unit cube exactly as stocs_ctx_create does them (stocs.cpp:943-964, pairCreationFunctor.h:96-132)
@@ -571,6 +607,7 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
     c->lcp_split = 1;
     c->lcp_flat = getenv("STOCS_LCP_FLAT") ? atoi(getenv("STOCS_LCP_FLAT")) : 1;
     c->lcp_normal_gate = 1;
+    c->lcp_patch_normals = getenv("STOCS_LCP_PATCH_NORMALS") ? (atoi(getenv("STOCS_LCP_PATCH_NORMALS")) != 0 ? 1 : 0) : 1;
     c->lcp_order = getenv("STOCS_LCP_ORDER") ? atoi(getenv("STOCS_LCP_ORDER")) : 1;
     c->exact_ties = 0; c->kd_ready = false; c->d_kd_nodes = NULL; c->d_kd_pts = NULL; c->d_ties = NULL; c->ties_started = false;
     c->cdf_n = 0; c->prior_epoch = 1; c->cdf_epoch = 0;
@@ -578,7 +615,7 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
     memset(&c->grid, 0, sizeof(c->grid));
     c->d_spos = c->d_snrmw = c->d_mpos = c->d_mnrm = c->d_munit = c->d_mpos_raw = c->d_mpos_s = c->d_mnrm_s = NULL;
     c->d_spix = NULL; c->d_mperm = NULL; c->d_mpatch = NULL; c->d_msub = NULL; c->d_scene_mem = NULL; c->scene_cap = 0;
-    c->patch_r_ref = 0.0f; c->scene_scored = 0; c->scene_work = 0.0;
+    c->patch_r_ref = 0.0f; c->sub_r_ref = 0.0f; c->pn_launches = 0; c->scene_scored = 0; c->scene_work = 0.0;
     c->lcp_cull = getenv("STOCS_LCP_CULL") ? atoi(getenv("STOCS_LCP_CULL")) : 1;
     c->lcp_cull_unit = 16;
     c->lcp_cull_after = 1.0e9; c->prev_scene_warm = false; c->cull_pending = false; c->ev_cull = NULL;
@@ -681,6 +718,16 @@ int stocs_ctx_create(const stocs_params* prm, const float* sp, const float* sn, 
         if (!rc) rc = upload(&c->d_mnrm_s, bs.data(), bs.size());
         if (!rc) rc = upload(&c->d_mperm, c->h_mperm.data(), c->h_mperm.size());
         if (!rc) rc = upload(&c->d_mpatch, patch.data(), patch.size());
+        // the sub-patch normal cones lie behind the spheres, in the same block: a kernel finds them from the sphere pointer and the model size
+        {
+            std::vector<float> radii;
+            for (int q = 0; q < (nM + 15) / 16; ++q) radii.push_back(sub[q].w);
+            std::sort(radii.begin(), radii.end());
+            c->sub_r_ref = radii[(size_t)((double)(radii.size() - 1) * STOCS_PN_REACH_QUANTILE)];
+        }
+        std::vector<float4> subn;
+        model_subpatch_normals(c->h_mnrm, c->h_mperm, sub.size(), subn);
+        sub.insert(sub.end(), subn.begin(), subn.end());
         if (!rc) rc = upload(&c->d_msub, sub.data(), sub.size());
     }
     if (!rc) rc = load_scene(c, sp, sn, sprob, spix, nS);
@@ -705,6 +752,18 @@ int stocs_model_subpatches(const float* model_pos3, int nM, int32_t* perm, float
     model_patch_order_host(model_pos3, nM, pm, patch, sub);
     for (int i = 0; i < nM; ++i) perm[i] = pm[i];
     for (int q = 0; q < (nM + 15) / 16; ++q) { spheres4[4 * q] = sub[q].x; spheres4[4 * q + 1] = sub[q].y; spheres4[4 * q + 2] = sub[q].z; spheres4[4 * q + 3] = sub[q].w; }
+    return STOCS_OK;
+}
+
+int stocs_model_subpatch_normals(const float* model_pos3, const float* model_nrm3, int nM, int32_t* perm, float* records4) {
+    if (!model_pos3 || !model_nrm3 || nM <= 0 || !perm || !records4) return STOCS_ERR_INVALID;
+    std::vector<int32_t> pm; std::vector<float4> patch, sub, rec;
+    model_patch_order_host(model_pos3, nM, pm, patch, sub);
+    std::vector<V3> mnrm(nM);
+    for (int i = 0; i < nM; ++i) mnrm[i] = normalized3(mk3(model_nrm3[3 * i], model_nrm3[3 * i + 1], model_nrm3[3 * i + 2]));   // as stocs_ctx_create
+    model_subpatch_normals(mnrm, pm, (size_t)(nM + 15) / 16, rec);
+    for (int i = 0; i < nM; ++i) perm[i] = pm[i];
+    for (int q = 0; q < (nM + 15) / 16; ++q) { records4[4 * q] = rec[q].x; records4[4 * q + 1] = rec[q].y; records4[4 * q + 2] = rec[q].z; records4[4 * q + 3] = rec[q].w; }
     return STOCS_OK;
 }
 

@@ -23,6 +23,7 @@
 #include <algorithm>
 
 #include "normal_cone.h"
+#include "patch_normals.h"
 #include "octant_lists.h"
 #include "prims.h"
 #include "stocs_ctx.h"
@@ -828,6 +829,7 @@ __global__ __launch_bounds__(256) void dist_splat_kernel(CullGeom G, float ox, f
 int prepare_cull_field(stocs_ctx* c) {
     SceneGrid& g = c->grid;
     g.d_dist = NULL; g.dist_ready = false;
+    g.d_ncone = NULL; g.d_nsum = NULL; g.ncone_ready = false; g.pn_rb = g.pn_reach = 0.0f; g.pn_w = 0;
     if (c->nS <= 0 || c->nM < 64 || !c->d_mpatch) return STOCS_OK;
     const double eps = (double)c->prm.distance_threshold;
     if (!(eps > 0)) return STOCS_OK;
@@ -849,23 +851,127 @@ int prepare_cull_field(stocs_ctx* c) {
     for (int k = 0; k < 3; ++k) n[k] = (int)floor((g.bb_mx[k] + cap + cg - of[k]) / (double)g.cg_g) + 1;
     g.cg_nx = n[0]; g.cg_ny = n[1]; g.cg_nz = n[2];
     g.cg_w = (int)ceil(cap / (double)g.cg_g);
-    return c->grid_mem.take((size_t)n[0] * n[1] * n[2] * sizeof(float), (void**)&g.d_dist);
+    // the cone field of the sub-patch normal test (patch_normals.h) over the same cells, for models the shared-list forms of the queue
+    // kernel score: one more word per cell right behind the distances, three words per cell of sums for its build.  The reach follows the
+    // model's sub-patch radii as the cap follows its patch radii: a sub-patch of radius r at e from a cell's centre needs r + epsilon + e
+    const size_t n_cells = (size_t)n[0] * n[1] * n[2];
+    // Only where a shared-list form can run at all: the option on as the grid is built, a model of up to 8 192 points that the queue
+    // kernel splits (512 points on; dense grids split every model).  lcp_split and lcp_cull_unit can change later: whether a launch
+    // runs such a form, and so whether the cones are ever filled, is decided launch by launch (lcp.hip)
+    const bool shared_possible = c->lcp_patch_normals && c->nM <= STOCS_PN_MAX_MODEL && (c->nM >= 512 || g.d_chunk_r != NULL);
+    if (!shared_possible) return c->grid_mem.take(n_cells * sizeof(float), (void**)&g.d_dist);
+    // The radius term is clamped as the cap's is: the fill visits (2 pn_w + 1)^3 cells per scene point, twice, so its cost grows with
+    // the cube of the reach, and the cones of a wide reach rule nothing out anyway.  At most STOCS_PN_MAX_REACH_EPS + 1 epsilon + half
+    // a cell diagonal: 5.9 cells, four times the visits of Cm's 3.7.  A sub-patch beyond it is "not testable", as the kernel has it
+    g.pn_rb = (float)(std::min((double)c->sub_r_ref, STOCS_PN_MAX_REACH_EPS * eps) + eps + 0.5 * sqrt(3.0) * (double)g.cg_g);
+    g.pn_reach = pn_reach_for_kernel(g.pn_rb);
+    g.pn_w = (int)ceil((double)g.pn_rb / (double)g.cg_g);
+    if (int rc = c->grid_mem.take(2 * n_cells * sizeof(float), (void**)&g.d_dist)) return rc;
+    g.d_ncone = (uint32_t*)(g.d_dist + n_cells);
+    return c->grid_mem.take(3 * n_cells * sizeof(int32_t), (void**)&g.d_nsum);
 }
 
-int fill_cull_field(stocs_ctx* c, hipStream_t st) {
+// ---- the cone field (patch_normals.h) ----
+// One wavefront per scene point, its window walked as dist_splat_kernel walks it (the cell centres computed as the scan kernel
+// computes them); a cell takes part when the point's float distance from its centre is below rb.  Integer atomics only, so the field
+// is the same from run to run:
+//   PASS 0   the axis sums, fixed point: round(1024 n) per component (a point whose normal is not of unit length within 1e-4 adds nothing)
+//   (cone_axis_kernel: per cell, the sums -> the octahedral axis, class 0)
+//   PASS 1   the class of the point's normal against the axis AS DECODED (double, rounded outwards), atomic maximum on the word: the
+//            low 24 bits of every operand of a cell are the same axis, so the maximum is the maximum of the classes
+template <int PASS>
+__global__ __launch_bounds__(256) void cone_splat_kernel(CullGeom G, float ox, float oy, float oz, float g, float rb, const float4* __restrict__ spos,
+                                                         const float4* __restrict__ snrmw, int nS, int32_t* __restrict__ nsum, uint32_t* __restrict__ ncone) {
+    const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= nS) return;
+    const int lane = threadIdx.x & 63, xo0 = lane & 15, rsub = lane >> 4;
+    const int side = 2 * G.w + 1;
+    const float4 p = spos[i];
+    const float4 nf = snrmw[i];
+    const double n2 = (double)nf.x * nf.x + (double)nf.y * nf.y + (double)nf.z * nf.z;
+    const bool unit = n2 >= 0.99980001 && n2 <= 1.00020001;   // within 1e-4 of unit length (false for a NaN)
+    if (PASS == 0 && !unit) return;
+    const int kx = unit ? (int)rintf(nf.x * 1024.0f) : 0, ky = unit ? (int)rintf(nf.y * 1024.0f) : 0, kz = unit ? (int)rintf(nf.z * 1024.0f) : 0;
+    const float inv_g = 1.0f / g, rb2 = rb * rb;
+    if (!(fabsf(p.x) + (fabsf(p.y) + fabsf(p.z)) < 1.0e18f)) return;   // (a position that is not finite is within reach of nothing)
+    const int ix = (int)floorf((p.x - ox) * inv_g), iy0 = (int)floorf((p.y - oy) * inv_g) - G.w, iz0 = (int)floorf((p.z - oz) * inv_g) - G.w;
+    for (int r = rsub; r < side * side; r += 4) {
+        const int iz = iz0 + r / side, iy = iy0 + r % side;
+        if (iy < 0 || iy >= G.n[1] || iz < 0 || iz >= G.n[2]) continue;
+        const float dy = p.y - (oy + ((float)iy + 0.5f) * g), dz = p.z - (oz + ((float)iz + 0.5f) * g);
+        const float dyz = dy * dy + dz * dz;
+        if (dyz >= rb2) continue;
+        const size_t row = ((size_t)iz * G.n[1] + iy) * G.n[0];
+        for (int xo = xo0; xo < side; xo += 16) {
+            const int cx = ix - G.w + xo;
+            if (cx < 0 || cx >= G.n[0]) continue;
+            const float dx = p.x - (ox + ((float)cx + 0.5f) * g);
+            if (dx * dx + dyz >= rb2) continue;
+            const size_t cell = row + cx;
+            if (PASS == 0) {
+                atomicAdd(&nsum[3 * cell], kx); atomicAdd(&nsum[3 * cell + 1], ky); atomicAdd(&nsum[3 * cell + 2], kz);
+            } else {
+                const uint32_t w0 = __hip_atomic_load(&ncone[cell], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                uint32_t cls = STOCS_PN_BAD_CLASS;
+                if (unit) {
+                    float fx, fy, fz;
+                    pn_axis(w0, fx, fy, fz);
+                    const double o2 = (double)fx * fx + (double)fy * fy + (double)fz * fz;
+                    const double cs = ((double)nf.x * fx + (double)nf.y * fy + (double)nf.z * fz) / sqrt(n2 * o2);
+                    if (cs > 0.0) {   // below 90 degrees
+                        const double sd = sqrt(fmax((1.0 - cs) * (1.0 + cs), 0.0));
+                        cls = (uint32_t)fmin(floor(sd * (double)STOCS_PN_SIN_STEPS + 1.0e-4) + 1.0, (double)STOCS_PN_BAD_CLASS);   // sin(angle) < cls / 256, the double rounding included
+                    }
+                }
+                const uint32_t w1 = (w0 & 0xFFFFFFu) | (cls << 24);
+                if (w1 > w0) atomicMax(&ncone[cell], w1);
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void cone_axis_kernel(const int32_t* __restrict__ nsum, uint32_t* __restrict__ ncone, size_t n) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double sx = (double)nsum[3 * i], sy = (double)nsum[3 * i + 1], sz = (double)nsum[3 * i + 2];
+    const double l1 = fabs(sx) + fabs(sy) + fabs(sz);
+    uint32_t w = 0u;   // (no sum: the axis of word 0 is as good as any, the classes are measured against it)
+    if (l1 > 0.0) {
+        double px = sx / l1, py = sy / l1;
+        if (sz < 0) { const double qx = (1.0 - fabs(py)) * (px >= 0 ? 1.0 : -1.0), qy = (1.0 - fabs(px)) * (py >= 0 ? 1.0 : -1.0); px = qx; py = qy; }
+        const double amax = (double)STOCS_PN_AXIS_MAX;
+        w = pn_pack((uint32_t)fmin(fmax(floor((px * 0.5 + 0.5) * amax + 0.5), 0.0), amax), (uint32_t)fmin(fmax(floor((py * 0.5 + 0.5) * amax + 0.5), 0.0), amax), 0u);
+    }
+    ncone[i] = w;
+}
+
+int fill_cull_field(stocs_ctx* c, hipStream_t st, bool cones) {
     SceneGrid& g = c->grid;
-    if (!g.d_dist || g.dist_ready) return STOCS_OK;
+    cones = cones && g.d_ncone && !g.ncone_ready && c->lcp_patch_normals;
+    if (!g.d_dist || (g.dist_ready && !cones)) return STOCS_OK;
     if (!st) st = c->stream;
     CullGeom G;
     G.o[0] = g.cg_ox; G.o[1] = g.cg_oy; G.o[2] = g.cg_oz;   // the float origin and edge the scan kernels use, widened
     G.g = g.cg_g; G.cap = g.cg_cap;
     G.n[0] = g.cg_nx; G.n[1] = g.cg_ny; G.n[2] = g.cg_nz; G.w = g.cg_w;
     const size_t n = (size_t)g.cg_nx * g.cg_ny * g.cg_nz;
-    hipLaunchKernelGGL(dist_fill_kernel, dim3(grid_of(n)), dim3(256), 0, st, g.d_dist, n, g.cg_cap);
-    hipLaunchKernelGGL(dist_splat_kernel, dim3((unsigned)((c->nS + 3) / 4)), dim3(256), 0, st, G, g.cg_ox, g.cg_oy, g.cg_oz, g.cg_g, g.cg_cap,
-                       c->d_spos, c->nS, (uint32_t*)g.d_dist);
-    STOCS_HIP_CHECK(hipGetLastError());
-    g.dist_ready = true;
+    if (!g.dist_ready) {
+        hipLaunchKernelGGL(dist_fill_kernel, dim3(grid_of(n)), dim3(256), 0, st, g.d_dist, n, g.cg_cap);
+        hipLaunchKernelGGL(dist_splat_kernel, dim3((unsigned)((c->nS + 3) / 4)), dim3(256), 0, st, G, g.cg_ox, g.cg_oy, g.cg_oz, g.cg_g, g.cg_cap,
+                           c->d_spos, c->nS, (uint32_t*)g.d_dist);
+        STOCS_HIP_CHECK(hipGetLastError());
+        g.dist_ready = true;
+    }
+    if (cones) {
+        G.w = g.pn_w;
+        const dim3 per_point((unsigned)((c->nS + 3) / 4));
+        STOCS_HIP_CHECK(hipMemsetAsync(g.d_nsum, 0, 3 * n * sizeof(int32_t), st));
+        hipLaunchKernelGGL(cone_splat_kernel<0>, per_point, dim3(256), 0, st, G, g.cg_ox, g.cg_oy, g.cg_oz, g.cg_g, g.pn_rb, c->d_spos, c->d_snrmw, c->nS, g.d_nsum, g.d_ncone);
+        hipLaunchKernelGGL(cone_axis_kernel, dim3(grid_of(n)), dim3(256), 0, st, g.d_nsum, g.d_ncone, n);
+        hipLaunchKernelGGL(cone_splat_kernel<1>, per_point, dim3(256), 0, st, G, g.cg_ox, g.cg_oy, g.cg_oz, g.cg_g, g.pn_rb, c->d_spos, c->d_snrmw, c->nS, g.d_nsum, g.d_ncone);
+        STOCS_HIP_CHECK(hipGetLastError());
+        g.ncone_ready = true;
+    }
     return STOCS_OK;
 }
 

@@ -40,6 +40,7 @@
 #include "kdtree.h"
 #include "normal_cone.h"
 #include "octant_lists.h"
+#include "patch_normals.h"
 #include "prims.h"
 #include "stocs_ctx.h"
 
@@ -71,6 +72,11 @@ struct LcpArgs {
     int xcd_blocks;         // != 0: workgroups of one XCD take a contiguous run of slots (each XCD has its own L2)
     unsigned long long* best;   // != NULL: compute_best_transform in the kernel's epilogue -- every candidate's packed (score, ~id) key joins an
     uint32_t id_offset;         // atomic max on this word (integer max: order independent), id = id_offset + candidate
+    // > 0: the shared-list forms also test the sub-patches' normal cones (patch_normals.h) against the cone field, whose reach this is;
+    // 0: off (the option, no field, not yet filled).  The records need no pointers of their own: the sub-patch cones lie behind the
+    // spheres (sub + 4 * steps), the field's cones behind the distances (dist + cells).  The word fills the gap in front of the next
+    // pointer, so the record keeps its size and every other member its place: no other kernel's argument loads move
+    float nreach;
     // patch test (lcp_coopq_kernel): bounding sphere per 64-point step + the scene's distance field (SceneGrid::d_dist); patch == NULL: off
     const float4* patch;
     const float4* sub;    // bounding sphere per 16-point sub-patch (ctx.hip), the unit of that test in the CU = 16 kernels
@@ -439,6 +445,20 @@ __device__ __forceinline__ bool lcp_patch_verdict(const LcpArgs& a, const LcpPat
     const float room = p.inside ? v - sqrtf(ex * ex + (ey * ey + ez * ez)) : a.cap;
     return (mag < 1.0e18f) && room > need;
 }
+// The normal-cone half of the test for a sub-patch the sphere test leaves alive (patch_normals.h): rec = the sub-patch's cone, cw = the
+// cone of the probe's cell.  The cell's reach must hold every scene point the sub-patch can be counted with: the sphere test's `need`
+// plus the distance of the centre from the cell's centre, against a.nreach.  Outside the table, in its border, for a centre that is not
+// finite: no test (cell 0 was read, its word is not used)
+__device__ __forceinline__ bool lcp_patch_normals_dead(const LcpArgs& a, const LcpPatchProbe& p, float radius, float sn, const float4 rec, uint32_t cw,
+                                                       float t0, float t1, float t2, float t4, float t5, float t6, float t8, float t9, float t10) {
+    const float mag = fabsf(p.cx) + (fabsf(p.cy) + fabsf(p.cz));
+    const float need = (sn * radius + a.eps * 1.002f) + (4.0e-6f + 4.0e-6f * mag);
+    const float ex = p.cx - (a.gox + (p.fx + 0.5f) * a.g), ey = p.cy - (a.goy + (p.fy + 0.5f) * a.g), ez = p.cz - (a.goz + (p.fz + 0.5f) * a.g);
+    const bool within = p.inside && need + sqrtf(ex * ex + (ey * ey + ez * ez)) < a.nreach;
+    return within && pn_rules_out(cw, rec.x, rec.y, rec.z, rec.w, sn, t0, t1, t2, t4, t5, t6, t8, t9, t10, a.dot_lo);
+}
+static_assert(STOCS_PN_MAX_MODEL == 16 * 512, "the cone field is built for the models the shared-list forms score (LCP_SHARED_LIVE)");
+
 // the test in one piece, branching: for the forms that have no registers to spare for the halves (the ring and whole-step forms of the
 // queue kernel: up to 28 bytes of scratch with them)
 __device__ __forceinline__ bool lcp_patch_dead(const LcpArgs& a, const float4 sp, float sn, float t0, float t1, float t2, float t4, float t5, float t6,
@@ -554,15 +574,28 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
     if (cand < 0) return;   // SPLIT: the whole workgroup leaves together
     const float4* __restrict__ snrmw = lcp_weights_of(a, cand);
     // SHARED: the sphere records of this wavefront's two windows of the patch test (below) do not depend on the candidate: both are
-    // requested here, back to back and ahead of the wait for the transform.  A window beyond the model reads the last record (no branch
-    // around the load); its result is discarded.  (A shared-list form runs only with the test on -- CU = 16 is chosen by a.patch,
+    // requested here, back to back and ahead of the wait for the transform.  The lanes of a window that reach beyond the model read the
+    // last record (a clamped index, no branch around the load); their result is discarded.  (A shared-list form runs only with the test on -- CU = 16 is chosen by a.patch,
     // choose_lcp_form -- so a.sub is there)
     const bool patch_on = SHARED && !STOCS_ABLATE(a, 64);
+    // The second window of a wavefront lies wholly beyond the model for models of up to 64 * (4 + w) sub-patches (three of the eight
+    // windows at 313 sub-patches): its loads and its tests are skipped, on a wave-uniform branch.  With a.nreach > 0 (wave-uniform) the
+    // sub-patches' normal cones are requested with the spheres: they lie behind them (patch_normals.h)
+    const bool two = SHARED && __builtin_amdgcn_readfirstlane((int)(((threadIdx.x >> 6) + 4) << 6)) < ((a.M + 15) >> 4);
+    const bool pn_on = SHARED && a.nreach > 0.0f;
     float4 wsp[2] = {make_float4(0.f, 0.f, 0.f, 0.f), make_float4(0.f, 0.f, 0.f, 0.f)};
+    float4 wsn[2] = {make_float4(0.f, 0.f, 0.f, STOCS_PN_NO_TEST), make_float4(0.f, 0.f, 0.f, STOCS_PN_NO_TEST)};
     if (SHARED) {
         const int last_sub = max(((a.M + 15) >> 4) - 1, 0);
+        const float4* const subn = a.sub + (((a.M + 63) >> 6) << 2);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) wsp[j] = a.sub[min((int)(((threadIdx.x >> 6) + 4 * j) << 6) + lane, last_sub)];
+        for (int j = 0; j < 2; ++j) {
+            if (j == 0 || two) {
+                const int q = min((int)(((threadIdx.x >> 6) + 4 * j) << 6) + lane, last_sub);
+                wsp[j] = a.sub[q];
+                if (pn_on) wsn[j] = subn[q];
+            }
+        }
     }
     const float* T = T16 + (size_t)cand * 16;
     const float t0 = T[0], t1 = T[1], t2 = T[2], t4 = T[4], t5 = T[5], t6 = T[6], t8 = T[8], t9 = T[9], t10 = T[10],
@@ -858,12 +891,24 @@ __global__ __launch_bounds__(64 * lcp_waves_per_block(DETAIL, SPLIT), 8) void lc
 #pragma unroll
         for (int j = 0; j < 2; ++j) live[j] = ((w + 4 * j) << 6) + lane < nsubs;
         if (patch_on) {
+            // (the cone of a cell is requested with its distance: one round trip for both)
+            const uint32_t* const ncone = (const uint32_t*)a.dist + (size_t)a.gnx * (size_t)a.gny * (size_t)a.gnz;
+            uint32_t cw[2] = {0u, 0u};
 #pragma unroll
-            for (int j = 0; j < 2; ++j) pp[j] = lcp_patch_probe(a, wsp[j], t0, t1, t2, t4, t5, t6, t8, t9, t10, t12, t13, t14);
+            for (int j = 0; j < 2; ++j)
+                if (j == 0 || two) pp[j] = lcp_patch_probe(a, wsp[j], t0, t1, t2, t4, t5, t6, t8, t9, t10, t12, t13, t14);
 #pragma unroll
-            for (int j = 0; j < 2; ++j) fv[j] = a.dist[pp[j].cell];
+            for (int j = 0; j < 2; ++j)
+                if (j == 0 || two) {
+                    fv[j] = a.dist[pp[j].cell];
+                    if (pn_on) cw[j] = ncone[pp[j].cell];
+                }
 #pragma unroll
-            for (int j = 0; j < 2; ++j) live[j] = live[j] && !lcp_patch_verdict(a, pp[j], wsp[j].w, snorm, fv[j]);
+            for (int j = 0; j < 2; ++j)
+                if (j == 0 || two) {
+                    live[j] = live[j] && !lcp_patch_verdict(a, pp[j], wsp[j].w, snorm, fv[j]);
+                    if (pn_on) live[j] = live[j] && !lcp_patch_normals_dead(a, pp[j], wsp[j].w, snorm, wsn[j], cw[j], t0, t1, t2, t4, t5, t6, t8, t9, t10);
+                }
         }
 #pragma unroll
         for (int j = 0; j < 2; ++j) lm[j] = __ballot(live[j]);
@@ -1245,6 +1290,21 @@ static int launch_lcp_form(stocs_ctx* c, const LcpForm& f, const LcpArgs& a, con
     return STOCS_OK;
 }
 
+// The form of this launch, and with it whether the launch tests the sub-patches' normal cones: only a shared-list form reads the cone
+// field, so only a launch that runs one fills it (once per scene, behind the distances) and is given its reach.  A model that is never
+// split, lcp_split = 0, lcp_cull_unit = 64 and the detail forms never pay for the field.
+static int launch_chosen_form(stocs_ctx* c, LcpArgs& a, const float* d_T16, int n, float* d_lcp, int32_t* d_hit, uint8_t* d_counted) {
+    const LcpForm f = choose_lcp_form(c, a, d_hit != NULL);
+    a.nreach = 0.0f;
+    if (f.kernel == LCP_QUEUE && f.shared && c->lcp_patch_normals && c->grid.d_ncone && c->grid.dist_ready) {
+        int rc = fill_cull_field(c);
+        if (rc) return rc;
+        a.nreach = c->grid.pn_reach;
+        c->pn_launches++;
+    }
+    return launch_lcp_form(c, f, a, d_T16, n, d_lcp, d_hit, d_counted);
+}
+
 int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d_hit, uint8_t* d_counted, unsigned long long* d_best8, uint32_t id_offset) {
     if (n <= 0) { if (d_best8) STOCS_HIP_CHECK(hipMemsetAsync(d_best8, 0, 8, c->stream)); return STOCS_OK; }
     bool best_zeroed = false;
@@ -1270,7 +1330,7 @@ int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d
     // patch test: its distance field costs one pass over the scene points (0.24 ms at Cm) and takes ~6 % off a launch, so it is filled
     // once the scene has seen 1e9 point queries (three steps of the metric batch; ~25 trials of one frame) -- a caller that scores one
     // trial per frame never pays for it.  The scores do not depend on it
-    a.patch = NULL; a.sub = NULL; a.dist = NULL;
+    a.patch = NULL; a.sub = NULL; a.dist = NULL; a.nreach = 0.0f;
     a.gox = a.goy = a.goz = 0.f; a.g = a.inv_g = a.cap = 0.f; a.gnx = a.gny = a.gnz = 0;
     c->scene_scored++;
     c->scene_work += (double)n * (double)c->nM;
@@ -1282,10 +1342,10 @@ int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d
         a.order = NULL; a.xcd_blocks = 0;
         if (d_best8 && !(d_best8 == c->d_best && c->best_is_zero)) STOCS_HIP_CHECK(hipMemsetAsync(d_best8, 0, 8, c->stream));
         if (d_best8 == c->d_best) c->best_is_zero = false;
-        return launch_lcp_form(c, choose_lcp_form(c, a, d_hit != NULL), a, d_T16, n, d_lcp, d_hit, d_counted);
+        return launch_chosen_form(c, a, d_T16, n, d_lcp, d_hit, d_counted);
     }
     if (c->lcp_cull && c->grid.d_dist && c->d_mpatch && (c->grid.dist_ready || c->lcp_cull >= 2 || c->scene_work >= c->lcp_cull_after)) {
-        int rc = fill_cull_field(c);
+        int rc = fill_cull_field(c, NULL, false);   // the distances; the cones when the form of this launch reads them (launch_chosen_form)
         if (rc) return rc;
         if (c->cull_pending) { STOCS_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_cull, 0)); c->cull_pending = false; }   // filled at stocs_ctx_set_scene, on the auxiliary stream
         a.patch = c->d_mpatch; a.sub = c->d_msub; a.dist = c->grid.d_dist;
@@ -1330,7 +1390,7 @@ int launch_lcp(stocs_ctx* c, const float* d_T16, int n, float* d_lcp, int32_t* d
     if (d_best8 && d_best8 == c->d_best && c->best_is_zero) best_zeroed = true;   // stocs_make_transforms left the word zeroed for this launch
     if (d_best8 == c->d_best) c->best_is_zero = false;
     if (d_best8 && !best_zeroed) STOCS_HIP_CHECK(hipMemsetAsync(d_best8, 0, 8, c->stream));
-    return launch_lcp_form(c, choose_lcp_form(c, a, d_hit != NULL), a, d_T16, n, d_lcp, d_hit, d_counted);
+    return launch_chosen_form(c, a, d_T16, n, d_lcp, d_hit, d_counted);
 }
 
 // the arg-max key of n scores (n > 0) into *d_key8, on the context's stream: one workgroup up to 2^18 scores, else zero fill + atomic max
@@ -1534,6 +1594,99 @@ int stocs_lcp_gate_count(stocs_ctx* c, const void* d_T16, int n, int64_t out[3])
     return STOCS_OK;
 }
 
+// stocs_lcp_patch_normal_count: one lane per (candidate, sub-patch), the two halves of the patch test as the shared-list forms' prologue
+// runs them (the same device functions, the same records), and the detail form's counted flags of the sub-patch's 16 points
+__global__ __launch_bounds__(256) void patch_normal_count_kernel(LcpArgs a, const float* __restrict__ T16, size_t total, const uint8_t* __restrict__ counted,
+                                                                 unsigned long long* __restrict__ out3) {
+    const size_t g = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int nsubs = (a.M + 15) >> 4;
+    unsigned long long nl = 0, nr = 0, nb = 0;
+    if (g < total) {
+        const size_t cand = g / (size_t)nsubs;
+        const int q = (int)(g % (size_t)nsubs);
+        const float* T = T16 + cand * 16;
+        const float t0 = T[0], t1 = T[1], t2 = T[2], t4 = T[4], t5 = T[5], t6 = T[6], t8 = T[8], t9 = T[9], t10 = T[10], t12 = T[12], t13 = T[13], t14 = T[14];
+        const float sn = linear_norm_bound(t0, t1, t2, t4, t5, t6, t8, t9, t10);
+        const float4 sp = a.sub[q], rec = a.sub[(((a.M + 63) >> 6) << 2) + q];
+        const LcpPatchProbe pp = lcp_patch_probe(a, sp, t0, t1, t2, t4, t5, t6, t8, t9, t10, t12, t13, t14);
+        const uint32_t* const ncone = (const uint32_t*)a.dist + (size_t)a.gnx * (size_t)a.gny * (size_t)a.gnz;
+        if (!lcp_patch_verdict(a, pp, sp.w, sn, a.dist[pp.cell])) {
+            nl = 1;
+            if (lcp_patch_normals_dead(a, pp, sp.w, sn, rec, ncone[pp.cell], t0, t1, t2, t4, t5, t6, t8, t9, t10)) {
+                nr = 1;
+                for (int i = 16 * q; i < min(16 * q + 16, a.M); ++i) nb |= counted[cand * (size_t)a.M + (size_t)a.mperm[i]] ? 1ull : 0ull;
+            }
+        }
+    }
+    nl = lcp_wave_sum(nl); nr = lcp_wave_sum(nr); nb = lcp_wave_sum(nb);
+    if ((threadIdx.x & 63) == 0) { if (nl) atomicAdd(&out3[0], nl); if (nr) atomicAdd(&out3[1], nr); if (nb) atomicAdd(&out3[2], nb); }
+}
+
+int stocs_lcp_patch_normal_count(stocs_ctx* c, const void* d_T16, int n, int64_t out[3]) {
+    if (!c || n < 0 || (n && !d_T16) || !out) return STOCS_ERR_INVALID;
+    DeviceGuard dev_guard(c->device);
+    begin_scoring_call(c);
+    out[0] = out[1] = out[2] = 0;
+    if (n == 0 || c->nM == 0 || c->nS == 0 || !c->grid.d_dist || !c->grid.d_ncone || !c->d_msub) return STOCS_OK;
+    const size_t M = (size_t)c->nM, nsubs = (M + 15) / 16;
+    const int chunk = (int)std::max<size_t>(1, std::min<size_t>((size_t)n, ((size_t)256 << 20) / (5 * M)));
+    const size_t hb = al256((size_t)chunk * M * 4), cb = al256((size_t)chunk * M), lb = al256((size_t)chunk * 4);
+    int rc = ensure_scratch(c, 256 + lb + hb + cb);
+    if (rc) return rc;
+    char* base = (char*)c->d_scratch;
+    unsigned long long* d_out = (unsigned long long*)base;
+    float* dL = (float*)(base + 256);
+    int32_t* dH = (int32_t*)(base + 256 + lb);
+    uint8_t* dC = (uint8_t*)(base + 256 + lb + hb);
+    // both fields, whatever the options and the scene's scoring work say
+    const int keep = c->lcp_patch_normals;
+    c->lcp_patch_normals = 1;
+    rc = fill_cull_field(c);
+    c->lcp_patch_normals = keep;
+    if (rc) return rc;
+    if (c->cull_pending) { STOCS_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_cull, 0)); c->cull_pending = false; }
+    LcpArgs a;
+    memset(&a, 0, sizeof(a));
+    a.M = c->nM; a.mperm = c->d_mperm; a.sub = c->d_msub; a.dist = c->grid.d_dist;
+    a.eps = c->prm.distance_threshold; a.dot_lo = c->thr.lcp_dot_lo; a.nreach = c->grid.pn_reach;
+    a.gox = c->grid.cg_ox; a.goy = c->grid.cg_oy; a.goz = c->grid.cg_oz; a.g = c->grid.cg_g; a.inv_g = c->grid.cg_inv_g; a.cap = c->grid.cg_cap;
+    a.gnx = c->grid.cg_nx; a.gny = c->grid.cg_ny; a.gnz = c->grid.cg_nz;
+    STOCS_HIP_CHECK(hipMemsetAsync(d_out, 0, 24, c->stream));
+    for (int i0 = 0; i0 < n; i0 += chunk) {
+        const int m = std::min(chunk, n - i0);
+        const float* dT = (const float*)d_T16 + (size_t)i0 * 16;
+        rc = launch_lcp(c, dT, m, dL, dH, dC, NULL, 0);   // the detail form: counted flags per (candidate, model point)
+        if (rc) return rc;
+        const size_t total = (size_t)m * nsubs;
+        hipLaunchKernelGGL(patch_normal_count_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, c->stream, a, dT, total, (const uint8_t*)dC, d_out);
+        STOCS_HIP_CHECK(hipGetLastError());
+    }
+    if ((rc = ensure_pinned(c, PIN_VAR))) return rc;
+    unsigned long long* pin = (unsigned long long*)((char*)c->h_pin + PIN_BEST);
+    STOCS_HIP_CHECK(hipMemcpyAsync(pin, d_out, 24, hipMemcpyDeviceToHost, c->stream));
+    STOCS_HIP_CHECK(hipStreamSynchronize(c->stream));
+    for (int k = 0; k < 3; ++k) out[k] = (int64_t)pin[k];
+    return STOCS_OK;
+}
+
+int stocs_patch_normal_info(stocs_ctx* c, double out[4]) {
+    if (!c || !out) return STOCS_ERR_INVALID;
+    const SceneGrid& g = c->grid;
+    out[0] = g.d_ncone ? (double)g.pn_reach : 0.0;
+    out[1] = g.d_ncone ? (double)g.pn_w : 0.0;
+    out[2] = g.d_ncone && g.ncone_ready ? 1.0 : 0.0;
+    out[3] = (double)c->pn_launches;
+    return STOCS_OK;
+}
+
+float stocs_patch_normal_bound_host(uint32_t cone_word, const float* v3, float sb, float s, int* outside, float* axis3) {
+    bool o = false;
+    const float b = pn_bound(cone_word, v3[0], v3[1], v3[2], sb, s, &o);
+    if (outside) *outside = o ? 1 : 0;
+    if (axis3) pn_axis(cone_word, axis3[0], axis3[1], axis3[2]);
+    return b;
+}
+
 int stocs_best_device(stocs_ctx* c, const void* d_lcp, int n, uint32_t id_offset, uint64_t* key) {
     if (!c || !key || n < 0 || (n && !d_lcp)) return STOCS_ERR_INVALID;
     DeviceGuard dev_guard(c->device);
@@ -1594,6 +1747,12 @@ int stocs_set_option(stocs_ctx* c, const char* key, int value) {
     if (!strcmp(key, "exact_ties")) {
         if (value != 0 && value != 1) { set_error("stocs_set_option: exact_ties takes 0 or 1, not %d", value); return STOCS_ERR_INVALID; }
         c->exact_ties = value;
+        return STOCS_OK;
+    }
+    // 1 (default): the shared-list forms' patch test also rules sub-patches out by their normal cones (patch_normals.h; same scores); 0: spheres alone
+    if (!strcmp(key, "lcp_patch_normals")) {
+        if (value != 0 && value != 1) { set_error("stocs_set_option: lcp_patch_normals takes 0 or 1, not %d", value); return STOCS_ERR_INVALID; }
+        c->lcp_patch_normals = value;
         return STOCS_OK;
     }
     // 0: one wavefront per candidate, 1 (default): four wavefronts share a candidate's model points (same scores)

@@ -236,6 +236,15 @@ struct SceneGrid {
     // The memory is taken with the grid (no allocation later); the values are filled on first use (fill_cull_field).
     float* d_dist;
     bool dist_ready;
+    // Normal cones over the same cells (patch_normals.h), for models the shared-list forms score: d_ncone lies right behind d_dist in
+    // one block of cg cells each (a kernel finds it from d_dist and the cell counts), one 32-bit cone per cell of the normals of every
+    // scene point within pn_rb of the cell's centre; d_nsum: the build's fixed-point axis sums, three words per cell.  Filled with
+    // d_dist (fill_cull_field); NULL: no cone field.  pn_reach: what a kernel may rely on (pn_reach_for_kernel); pn_w: cells a point reaches
+    uint32_t* d_ncone;
+    int32_t* d_nsum;
+    bool ncone_ready;
+    float pn_rb, pn_reach;
+    int pn_w;
     float cg_ox, cg_oy, cg_oz, cg_g, cg_inv_g, cg_cap;
     int cg_nx, cg_ny, cg_nz, cg_w;   // cg_w: cells a point reaches on either side (ceil(cap / g))
     double bb_mn[3], bb_mx[3];       // bounding box of the centred scene
@@ -363,6 +372,7 @@ struct stocs_ctx {
     float4* d_mpatch;  // per 64-point step of the sorted model: bounding sphere (centre xyz, radius) of its points (patch test, lcp.hip)
     float4* d_msub;    // per 16-point sub-patch (four per step, NaN spheres behind the model): the unit of the patch test at lcp_cull_unit = 16
     float patch_r_ref; // the radius most patches stay below (sizes the cap of the scene's distance field)
+    float sub_r_ref;   // ... most 16-point sub-patches stay below (sizes the reach of the scene's cone field, patch_normals.h)
     int lcp_cull;      // 1: the scan kernels skip the 64-point steps whose bounding sphere is farther than epsilon from every scene point
     int lcp_cull_unit; // points per sphere of that test: 16 (default; live sub-patches are packed four to a step) or 64 (whole steps)
     double lcp_cull_after;   // lcp_cull == 1: the distance field is filled once this many point queries were scored against the scene (default 1e9)
@@ -382,6 +392,8 @@ struct stocs_ctx {
     int device_clock;  // 1: stocs_find_congruent_all records HIP events between its kernel groups ("device: ..." steps of stocs_last_call_timing); default 0 (STOCS_DEVICE_CLOCK=1 turns it on)
     int lcp_split;     // 1: four wavefronts share one candidate (default), 0: one wavefront per candidate
     int lcp_flat;      // 1: build and use the flat cell table when it fits (default), 0: brick look-ups only
+    unsigned long long pn_launches;   // scoring launches so far that ran a shared-list form with the cone test on (stocs_patch_normal_info)
+    int lcp_patch_normals; // 1 (default): the shared-list forms' patch test also rules sub-patches out by normal cones (patch_normals.h; same scores)
     int lcp_normal_gate;   // 1 (default): the queue kernel drops queries whose cell's normal cone cannot pass the normal test (same scores)
     int lcp_order;     // 0: candidates in batch order; 1: spatially ordered processing of big batches; 2: + XCD-contiguous blocks
     stocs::DevBlock order;   // keys / permutation / sort scratch of the ordering
@@ -566,7 +578,8 @@ int build_ppf_index(stocs_ctx* c);
 int build_grid_gpu(stocs_ctx* c, const GridForm& form);   // c->grid from c->d_spos (device) and c->h_spos (bounding box only)
 int prepare_cull_field(stocs_ctx* c);   // geometry + memory of SceneGrid::d_dist for the current grid and model (end of a grid build)
 int build_octant_lines(stocs_ctx* c);                          // the octant lines of the current grid, on c->stream, once per scene (grid.hip)
-int fill_cull_field(stocs_ctx* c, hipStream_t st = NULL);      // the values, on st (NULL: c->stream); no synchronisation
+int fill_cull_field(stocs_ctx* c, hipStream_t st = NULL, bool cones = true);   // the values, on st (NULL: c->stream); no synchronisation.  cones: also
+                                                                               // the cone field, when the grid has one, it is not yet filled and lcp_patch_normals is on
 // congruent.hip, the device side of stocs_make_transforms: the bases used whole materialised and sorted, then picks -> jobs (see there)
 extern "C" int stocs_internal_prepare_small(stocs_ctx* c, int max_per_base);
 extern "C" int stocs_internal_make_jobs(stocs_ctx* c, const Pick* picks_host, const Pick* picks_dev, int n, XformJob* d_jobs_out, const unsigned int** d_unresolved_out);

@@ -999,6 +999,19 @@ class StocsEstimator:
         capi.check(self.L.stocs_lcp_gate_count(self.h, dT, n, out))
         return int(out[0]), int(out[1]), int(out[2])
 
+    def lcp_patch_normal_count(self, dT, n):
+        """(sub-patches the sphere test leaves alive; those the normal-cone test rules out; ruled-out ones that hold a point the detail
+        form counts -- 0) over n device-resident transforms (stocs_lcp_patch_normal_count)."""
+        out = (C.c_int64 * 3)(0, 0, 0)
+        capi.check(self.L.stocs_lcp_patch_normal_count(self.h, dT, n, out))
+        return int(out[0]), int(out[1]), int(out[2])
+
+    def patch_normal_info(self):
+        """{"reach", "window", "filled", "launches"} of the sub-patch normal-cone test (stocs_patch_normal_info)"""
+        out = (C.c_double * 4)()
+        capi.check(self.L.stocs_patch_normal_info(self.h, out))
+        return {"reach": out[0], "window": int(out[1]), "filled": bool(out[2]), "launches": int(out[3])}
+
     def compute_best_transform(self):
         s = C.c_float(0); i = C.c_int(-1)
         P = np.zeros(16, np.float32)
