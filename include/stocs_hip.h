@@ -198,6 +198,20 @@ int stocs_get_quads_at(stocs_ctx* ctx, int base_slot, const int64_t* ranks, int 
  * reference's arithmetic where the filter cannot decide; cone_cells.h); the two must be equal.  n3 = query direction. */
 int stocs_cone_cells_host(const float* n3, float cos_alpha, uint32_t* exact_bits11, uint32_t* kernel_bits11, int* n_samples,
                           int* n_undecided);
+/* n such queries on the device, for tests: what the join kernels compute for a sample.  The cone fields of every query (number of
+ * samples, sin alpha, the shared (cos, sin) table) are filled on the host exactly as stocs_cone_cells_host and the count pass fill
+ * them; ONE kernel, one lane per query, then evaluates the shared functions of cone_cells.h in the order of the join: the
+ * quaternion, the filter's constants, and per sample (sin_alpha * table entry) the filtered cell and the exact cell.
+ * n3 = n x 3 query directions, cos_alpha = n values; device < 0: the current device.  Per query:
+ *   exact_bits11 [11 n]  the direction-cell set from the reference's arithmetic alone;
+ *   kernel_bits11[11 n]  the set the join builds (filter first, exact where the filter is undecided);
+ *   n_samples[n], n_undecided[n] (samples whose filtered cell was -1);  q4[4 n] the quaternion (x, y, z, w).
+ * Per sample a of query i, at i * 64 + a (64 = the most samples a cone can have; slots beyond n_samples[i] hold -1, -1, 0):
+ *   filtered_id  the filter's cell, or -1 when it cannot decide;  exact_id  the exact cell, or -1 for a direction that is not finite;
+ *   t3[3 ..]     the filter's cell coordinates (tx, ty, tz) before truncation.
+ * Synchronous; allocates and frees its own device memory. */
+int stocs_cone_cells_device(int device, const float* n3, const float* cos_alpha, int n, uint32_t* exact_bits11, uint32_t* kernel_bits11,
+                            int32_t* n_samples, int32_t* n_undecided, float* q4, int32_t* filtered_id, int32_t* exact_id, float* t3);
 
 /* ---- candidate transforms: the loop stocs_match_one_object.cpp:120-147 over
  * get_rigid_transform_from_congruent_pair (stocs.cpp:871-941 -> ComputeRigidTransformation :270-361):

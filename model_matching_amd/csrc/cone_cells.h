@@ -3,7 +3,8 @@
 // include/super4pcs/accelerators/normalset.hpp:166-214) up to the point where the set of direction cells is known:
 //   q = Quaternion::setFromTwoVectors(z, n);  for every sample a:  dir = (q * d_a).normalized();
 //   id = indexNormal(dir) = int((dir/2 + 0.5) / _nepsilon) per axis, base 7 (normalset.h:100-104)
-// Shared by host and device (and exercised on the host by tests/test_abi_cpu.py through stocs_cone_cells_host).
+// Shared by host and device (exercised on the host by tests/test_abi_cpu.py through stocs_cone_cells_host, on the device by
+// tests/test_cone_cells_gpu.py through stocs_cone_cells_device).
 //
 // Two evaluations of the same cell:
 //   * exact  -- the reference's float operations in the reference's order (IEEE divide / sqrt, no contraction):
@@ -13,8 +14,13 @@
 //               below 1e-5 cell units (float32, |t| < 7, a dozen operations each), so when the filtered value is more
 //               than CONE_MARGIN = 5e-5 away from every integer the two truncations agree and the cheap one is used; in
 //               the remaining ~3e-4 of the samples (and for anything non-finite) the exact evaluation decides.
-// The result is therefore bit-identical to the exact evaluation alone (asserted over 10^7 random samples on the host,
-// and implicitly by every GPU-vs-oracle quad comparison).
+//               The 1e-5 is a bound from counting operations; MEASURED on the device (gfx950: __frsqrt_rn, __fmaf_rn) against a
+//               float64 evaluation of the same coordinate, over 4 096 random queries and 4 096 built to sit on cell boundaries
+//               (tests/test_cone_cells_gpu.py, profiles/cone_filter_device.md): filter 7.1e-7, exact arithmetic 9.6e-7 cell units,
+//               their sum 1.7e-6 -- a thirtieth of the margin; undecided 3.9e-4 of the random samples.
+// The result is therefore bit-identical to the exact evaluation alone (asserted over 10^7 random samples on the host, on
+// the device by tests/test_cone_cells_gpu.py through stocs_cone_cells_device, and implicitly by every GPU-vs-oracle quad
+// comparison).
 #ifndef STOCS_CONE_CELLS_H
 #define STOCS_CONE_CELLS_H
 
@@ -29,6 +35,9 @@ namespace stocs {
 STOCS_HD int index_normal(V3 n, float nepsilon) {
     const V3 half = mk3(0.5f, 0.5f, 0.5f);
     const V3 cn = (n / 2.0f + half) / nepsilon;
+    // (int) of a NaN is undefined: the host's conversion gives INT_MIN (an index .at() throws on, which is what the callers' range
+    // tests stand for), the device's gives 0 -- cell 0.  A direction that is not a number has no cell on either side.
+    if (!(cn.x == cn.x && cn.y == cn.y && cn.z == cn.z)) return -1;
     return (int)cn.z * 49 + ((int)cn.y * 7 + (int)cn.x);
 }
 
@@ -98,13 +107,18 @@ STOCS_HD ConeFilter cone_filter_setup(const float q[4], float dz, float half_inv
 #else
 #define STOCS_RSQRTF(a) (1.0f / sqrtf(a))
 #endif
-// cell of the sample with (x, y) components (dx, dy), or -1 when the filter cannot decide (use cone_cell_exact then)
-STOCS_HD int cone_cell_filtered(const ConeFilter& f, float dx, float dy) {
+// the filter's cell coordinates t = s (v / |v| + 1) of the sample with (x, y) components (dx, dy), before truncation
+STOCS_HD void cone_filter_coords(const ConeFilter& f, float dx, float dy, float* tx, float* ty, float* tz) {
     const float vx = STOCS_FMAF(dx, f.ax, STOCS_FMAF(dy, f.bx, f.cx));
     const float vy = STOCS_FMAF(dx, f.ay, STOCS_FMAF(dy, f.by, f.cy));
     const float vz = STOCS_FMAF(dx, f.az, STOCS_FMAF(dy, f.bz, f.cz));
     const float k = STOCS_RSQRTF(STOCS_FMAF(vx, vx, STOCS_FMAF(vy, vy, vz * vz))) * f.s;
-    const float tx = STOCS_FMAF(vx, k, f.s), ty = STOCS_FMAF(vy, k, f.s), tz = STOCS_FMAF(vz, k, f.s);
+    *tx = STOCS_FMAF(vx, k, f.s); *ty = STOCS_FMAF(vy, k, f.s); *tz = STOCS_FMAF(vz, k, f.s);
+}
+// cell of the sample with (x, y) components (dx, dy), or -1 when the filter cannot decide (use cone_cell_exact then)
+STOCS_HD int cone_cell_filtered(const ConeFilter& f, float dx, float dy) {
+    float tx, ty, tz;
+    cone_filter_coords(f, dx, dy, &tx, &ty, &tz);
     const float fx = floorf(tx), fy = floorf(ty), fz = floorf(tz);
     const float rx = tx - fx, ry = ty - fy, rz = tz - fz;
     const float lo = fminf(rx, fminf(ry, rz)), hi = fmaxf(rx, fmaxf(ry, rz));

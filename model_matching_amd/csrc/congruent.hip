@@ -1703,6 +1703,97 @@ int stocs_cone_cells_host(const float* n3, float cos_alpha, uint32_t* exact_bits
     return STOCS_OK;
 }
 
+}  // extern "C"
+
+namespace stocs {
+
+// One cone query as the device sees it: the query direction and the cone fields of its base job (fill_cone_table on the host).
+struct ConeQuery { float nx, ny, nz, cos_alpha, sin_alpha; int nb; };
+
+// The colouring of join_one on its own, one lane per query (stocs_cone_cells_device): the same shared functions in the same order --
+// quat_from_z, cone_filter_setup, per sample (sin_alpha * trig) cone_cell_filtered and, here for EVERY sample, cone_cell_exact.
+// Every lane writes its own rows of the outputs (zeroed by the host) and nothing else.
+__global__ __launch_bounds__(256) void cone_cells_kernel(const ConeQuery* __restrict__ qs, int n, const float2* __restrict__ trig, float nepsilon, float half_inv_neps,
+                                                         uint32_t* __restrict__ exact_bits, uint32_t* __restrict__ kernel_bits, int32_t* __restrict__ n_undecided,
+                                                         float4* __restrict__ quat, int32_t* __restrict__ filt_id, int32_t* __restrict__ exact_id, float* __restrict__ t3) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const ConeQuery Q = qs[i];
+    float q[4];
+    quat_from_z(mk3(Q.nx, Q.ny, Q.nz), q);
+    const float dz = Q.cos_alpha;
+    const ConeFilter cf = cone_filter_setup(q, dz, half_inv_neps);
+    quat[i] = make_float4(q[0], q[1], q[2], q[3]);
+    uint32_t* eb = exact_bits + (size_t)i * 11;
+    uint32_t* kb = kernel_bits + (size_t)i * 11;
+    const float2* tr = trig + (size_t)Q.nb * STOCS_MAX_CONE;
+    const float sa = Q.sin_alpha;
+    int undecided = 0;
+    for (int a = 0; a < Q.nb; ++a) {
+        const float2 t = tr[a];
+        const float dx = sa * t.x, dy = sa * t.y;
+        const size_t o = (size_t)i * STOCS_MAX_CONE + (size_t)a;
+        float tx, ty, tz;
+        cone_filter_coords(cf, dx, dy, &tx, &ty, &tz);
+        t3[3 * o] = tx; t3[3 * o + 1] = ty; t3[3 * o + 2] = tz;
+        const int ik = cone_cell_filtered(cf, dx, dy);
+        const int ie = cone_cell_exact(q, mk3(dx, dy, dz), nepsilon);
+        filt_id[o] = ik; exact_id[o] = ie;
+        if (ie >= 0) eb[ie >> 5] |= 1u << (ie & 31);
+        int id = ik;
+        if (id < 0) { undecided++; id = ie; }   // what `colour` of join_one does
+        if (id >= 0) kb[id >> 5] |= 1u << (id & 31);
+    }
+    n_undecided[i] = undecided;
+}
+
+}  // namespace stocs
+
+extern "C" {
+
+// The same query on the device, n at a time: what the join kernels compute for a sample (contract in stocs_hip.h)
+int stocs_cone_cells_device(int device, const float* n3, const float* cos_alpha, int n, uint32_t* exact_bits11, uint32_t* kernel_bits11, int32_t* n_samples,
+                            int32_t* n_undecided, float* q4, int32_t* filtered_id, int32_t* exact_id, float* t3) {
+    if (n < 0 || (n && (!n3 || !cos_alpha || !exact_bits11 || !kernel_bits11 || !n_samples || !n_undecided || !q4 || !filtered_id || !exact_id || !t3))) return STOCS_ERR_INVALID;
+    if (n == 0) return STOCS_OK;
+    if (device < 0) { if (hipGetDevice(&device) != hipSuccess) device = 0; }
+    DeviceGuard dev_guard(device);
+    const float nepsilon = (float)((double)(1.0f / 7.0f) + 0.00001);
+    const float half_inv_neps = (float)(0.5 / (double)nepsilon);
+    std::vector<ConeQuery> hq((size_t)n);
+    for (int i = 0; i < n; ++i) {
+        BaseJob J;
+        memset(&J, 0, sizeof(J));
+        J.cos_alpha = cos_alpha[i];
+        fill_cone_table(&J);
+        const ConeQuery Q = {n3[3 * i], n3[3 * i + 1], n3[3 * i + 2], J.cos_alpha, J.sin_alpha, J.nb};
+        hq[i] = Q;
+        n_samples[i] = J.nb;
+    }
+    const size_t nn = (size_t)n, ns = nn * STOCS_MAX_CONE;
+    const size_t trig_bytes = sizeof(float2) * (STOCS_MAX_CONE + 1) * STOCS_MAX_CONE;
+    ConeQuery* d_q = NULL; float2* d_trig = NULL; uint32_t *d_eb = NULL, *d_kb = NULL; int32_t *d_nu = NULL, *d_fi = NULL, *d_ei = NULL; float4* d_quat = NULL; float* d_t = NULL;
+    int rc = STOCS_OK;
+#define CC_TRY(x) do { if ((x) != hipSuccess) { set_error("stocs_cone_cells_device: %s", #x); rc = STOCS_ERR_HIP; goto done; } } while (0)
+    CC_TRY(hipMalloc((void**)&d_q, nn * sizeof(ConeQuery))); CC_TRY(hipMalloc((void**)&d_trig, trig_bytes));
+    CC_TRY(hipMalloc((void**)&d_eb, nn * 44)); CC_TRY(hipMalloc((void**)&d_kb, nn * 44)); CC_TRY(hipMalloc((void**)&d_nu, nn * 4)); CC_TRY(hipMalloc((void**)&d_quat, nn * 16));
+    CC_TRY(hipMalloc((void**)&d_fi, ns * 4)); CC_TRY(hipMalloc((void**)&d_ei, ns * 4)); CC_TRY(hipMalloc((void**)&d_t, ns * 12));
+    CC_TRY(hipMemcpy(d_q, hq.data(), nn * sizeof(ConeQuery), hipMemcpyHostToDevice)); CC_TRY(hipMemcpy(d_trig, cone_trig(), trig_bytes, hipMemcpyHostToDevice));
+    CC_TRY(hipMemset(d_eb, 0, nn * 44)); CC_TRY(hipMemset(d_kb, 0, nn * 44)); CC_TRY(hipMemset(d_t, 0, ns * 12));
+    CC_TRY(hipMemset(d_fi, 0xFF, ns * 4)); CC_TRY(hipMemset(d_ei, 0xFF, ns * 4));      // slots beyond a query's samples: -1, t = 0
+    cone_cells_kernel<<<(unsigned)((nn + 255) / 256), 256, 0, 0>>>(d_q, n, d_trig, nepsilon, half_inv_neps, d_eb, d_kb, d_nu, d_quat, d_fi, d_ei, d_t);
+    CC_TRY(hipGetLastError());
+    CC_TRY(hipDeviceSynchronize());
+    CC_TRY(hipMemcpy(exact_bits11, d_eb, nn * 44, hipMemcpyDeviceToHost)); CC_TRY(hipMemcpy(kernel_bits11, d_kb, nn * 44, hipMemcpyDeviceToHost));
+    CC_TRY(hipMemcpy(n_undecided, d_nu, nn * 4, hipMemcpyDeviceToHost)); CC_TRY(hipMemcpy(q4, d_quat, nn * 16, hipMemcpyDeviceToHost));
+    CC_TRY(hipMemcpy(filtered_id, d_fi, ns * 4, hipMemcpyDeviceToHost)); CC_TRY(hipMemcpy(exact_id, d_ei, ns * 4, hipMemcpyDeviceToHost));
+    CC_TRY(hipMemcpy(t3, d_t, ns * 12, hipMemcpyDeviceToHost));
+done:
+#undef CC_TRY
+    (void)hipFree(d_q); (void)hipFree(d_trig); (void)hipFree(d_eb); (void)hipFree(d_kb); (void)hipFree(d_nu); (void)hipFree(d_quat); (void)hipFree(d_fi); (void)hipFree(d_ei); (void)hipFree(d_t);
+    return rc;
+}
+
 int stocs_find_congruent_all(stocs_ctx* c, int64_t* total_quads) { return stocs_internal_find_congruent(c, total_quads, 0, NULL); }
 
 int stocs_internal_find_congruent(stocs_ctx* c, int64_t* total_quads, size_t max_bytes, int* too_big) {
