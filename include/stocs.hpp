@@ -1478,6 +1478,60 @@ inline SegmentedFrame segment_frame(const uint16_t* depth, const std::vector<flo
     return segment_frame_impl(depth, camera_intrinsics, image_width, image_height, read_depth_scale, prm, &convex, device);
 }
 
+// Not in the reference: the join between the segments of a frame and the objects with models (stocs_segment_shapes, stocs_segment_assign).
+// A label image (segment_frame's or anybody's, 1 .. n_labels) -> one 3-D shape per label; with objects, the size gate's reason bits
+// (reasons[k * n_labels + l]: object k, label l + 1; 0 = compatible) and the object-major class stack load_frame_scenes takes.  The
+// gate is not exclusive: objects of like size keep the same segments, and choosing among them is select_scene's job.
+struct SegmentAssignment {
+    stocs_segment_shapes_result result;
+    std::vector<stocs_segment_shape> shapes;   // n_labels
+    std::vector<uint8_t> reasons;              // n_objects x n_labels, STOCS_GATE_* bits
+    std::vector<uint16_t> class_stack;         // n_objects x image_height x image_width: 10000 where the pixel's label is compatible
+    int n_labels, n_objects;
+    int compatible(int object) const {         // the segments the gate leaves the object
+        int c = 0;
+        for (int l = 0; l < n_labels; ++l) c += reasons[(size_t)object * n_labels + l] == 0 ? 1 : 0;
+        return c;
+    }
+};
+inline stocs_segment_gate_params default_segment_gate_params() { stocs_segment_gate_params g; stocs_default_segment_gate_params(&g); return g; }
+// an object's size from its (preprocessed) model cloud: the extents of stocs_points_shape; the diameter is the caller's exact one or,
+// with diameter <= 0, the diagonal of the extents formed in double and cast once: an upper bound, so TOO_LARGE stays sound
+inline stocs_object_size object_size(const std::vector<float>& model_pos, float diameter = 0.0f, int device = -1) {
+    stocs_segment_shape s;
+    if (stocs_points_shape(model_pos.data(), (int)(model_pos.size() / 3), device, &s, NULL) != STOCS_OK) throw std::runtime_error(std::string("stocs_points_shape: ") + stocs_last_error());
+    stocs_object_size o;
+    for (int k = 0; k < 3; ++k) o.extent[k] = s.extent[k];
+    o.diameter = diameter > 0.0f ? diameter
+                                 : (float)std::sqrt((double)s.extent[0] * (double)s.extent[0] + ((double)s.extent[1] * (double)s.extent[1] + (double)s.extent[2] * (double)s.extent[2]));
+    return o;
+}
+inline SegmentAssignment segment_assign(const uint16_t* depth, const int32_t* labels, int n_labels, const std::vector<stocs_object_size>& objects,
+                                        const std::vector<float>& camera_intrinsics, int image_width, int image_height, float read_depth_scale, float max_depth = 2.0f,
+                                        const stocs_segment_gate_params& gate = default_segment_gate_params(), int device = -1) {
+    if (camera_intrinsics.size() < 4) throw std::runtime_error("camera_intrinsics must hold {fx, cx, fy, cy}");
+    if (image_width < 1 || image_height < 1 || n_labels < 0) throw std::runtime_error("segment_assign: an empty frame or n_labels < 0");
+    stocs_camera cam;
+    cam.fx = camera_intrinsics[0]; cam.cx = camera_intrinsics[1]; cam.fy = camera_intrinsics[2]; cam.cy = camera_intrinsics[3];
+    cam.depth_scale = read_depth_scale; cam.width = image_width; cam.height = image_height;
+    cam.normal_method = STOCS_NORMALS_DEPTH_GRADIENT;   // (not looked at)
+    SegmentAssignment out;
+    out.n_labels = n_labels; out.n_objects = (int)objects.size();
+    out.shapes.resize((size_t)n_labels);
+    out.reasons.resize(objects.size() * (size_t)n_labels);
+    out.class_stack.resize(objects.size() * (size_t)image_width * image_height);
+    const int rc = stocs_segment_assign(&cam, depth, labels, n_labels, max_depth, objects.empty() ? NULL : objects.data(), out.n_objects, &gate, device,
+                                        n_labels ? out.shapes.data() : NULL, NULL, out.reasons.empty() ? NULL : out.reasons.data(),
+                                        objects.empty() ? NULL : out.class_stack.data(), &out.result);
+    if (rc != STOCS_OK) throw std::runtime_error(std::string("stocs_segment_assign: ") + stocs_last_error());
+    return out;
+}
+inline SegmentAssignment segment_shapes(const uint16_t* depth, const int32_t* labels, int n_labels, const std::vector<float>& camera_intrinsics, int image_width,
+                                        int image_height, float read_depth_scale, float max_depth = 2.0f, int device = -1) {
+    return segment_assign(depth, labels, n_labels, std::vector<stocs_object_size>(), camera_intrinsics, image_width, image_height, read_depth_scale, max_depth,
+                          default_segment_gate_params(), device);
+}
+
 // Not in the reference (its driver runs once per object): every object of one frame from one ingest (stocs_ingest_scene_multi).
 // class_probability_maps holds class_thresholds.size() images of image_height x image_width, object after object; edge (may be NULL)
 // is shared by all of them.  Scene k is what the estimator's own ingest makes of (depth, map k, class_thresholds[k]), bit for bit.

@@ -548,6 +548,81 @@ int  stocs_segment_frame_convex(const stocs_camera* cam, const uint16_t* depth, 
                                 stocs_segment_result* out, stocs_segment_convex_result* cout);
 int  stocs_segment_last_bend_ms(float* bend_ms);                              /* with STOCS_SEGMENT_CLOCK=1         */
 
+/* ---- 3-D shape of every labelled region of a depth frame, and a size gate between segments and objects (no reference counterpart;
+ * csrc/segment_shapes.hip and csrc/segment_gate.h, restated in numpy in tests/segment_shapes_ref.py).  The label image (int32, 0 = none,
+ * 1 .. n_labels) may be stocs_segment_frame's, stocs_segment_frame_convex's or anybody's (a network's instance mask): nothing here depends
+ * on how it was made.  Stand-alone like stocs_segment_frame: `device` (-1: the current one), no context, one stream, one pinned read-back
+ * and one synchronisation per call, a per-thread cached workspace of its own that stocs_trim gives back; a second call of the same or a
+ * smaller size allocates nothing (stocs_device_alloc_count).  Conventions of stocs_segment_frame: float, one IEEE operation at a time, no
+ * contraction, 3-term sums e0 + (e1 + e2).
+ *
+ *   1. Used pixels.  A label outside [0, n_labels] is counted (n_out_of_range) and treated as 0.  A LABELLED pixel (label 1 .. n_labels,
+ *      n_labelled) is USED (n_used) when raw != 0 and z = (float)raw * depth_scale <= max_depth (else n_invalid) and its point, step 1 of
+ *      stocs_segment_frame, has |x|, |y|, |z| < 16 (else n_far).  n_labelled = n_used + n_invalid + n_far.
+ *   2. Moments, per label: n, Sx, Sy, Sz, Sxx, Sxy, Sxz, Syy, Syz, Szz of q = llrint((double)v * 65536) in int64, over the used pixels,
+ *      under the refit's overflow argument (|q| < 2^20, at most 2^22 pixels, every sum below 2^62): exact whatever the order.  `moments`
+ *      (n_labels x 10, or NULL) returns them.
+ *   3. Centroid, covariance, axes, per label in double from the moments as step 3 of stocs_segment_frame forms them (c = S / n / 65536,
+ *      cov_ab = Sab / n / 2^32 - c_a c_b), all three eigenpairs by the same cyclic Jacobi (pairs (0,1), (0,2), (1,2), 12 sweeps).
+ *      Eigenvalues descending, on equal values the lower column first; each axis normalised and signed so that its component of largest
+ *      magnitude is positive (the lowest index on equal magnitudes); one cast to float each.  axis[k] is the k-th axis.  A non-finite
+ *      value: identity axes, zero eigenvalues, flag STOCS_SHAPE_NONFINITE.  n_used == 0: a zero record, flag STOCS_SHAPE_EMPTY.
+ *   4. Extents, a second pass over the used pixels, in float on the record's float centroid and axes: d = p - c,
+ *      t_k = a_k0 * d.x + (a_k1 * d.y + a_k2 * d.z); lo[k], hi[k] the minimum and maximum of t_k under the order of the bits (as signed
+ *      integers, negative floats with their low 31 bits inverted: -0 < +0), extent[k] = hi[k] - lo[k].
+ * stocs_points_shape: the same kernels on n points (pos3, n x 3 float) as one label, every point "labelled" and used when all three of
+ * |x|, |y|, |z| < 16: a model cloud's descriptor.  n == 0 is the EMPTY record; NULL pos3 (with n > 0) or shape, n < 0: STOCS_ERR_INVALID;
+ * n > 2^22: STOCS_ERR_CAPACITY.
+ *
+ * The gate (csrc/segment_gate.h, one rule for host and device).  e1 >= e2 >= e3 the shape's extents sorted by value, m1 >= m2 >= m3 the
+ * object's.  Reason bits, float, one operation each: TOO_LARGE e1 > (1 + slack) * diameter (no view of a body is wider than its diameter);
+ * TOO_SMALL e1 < min_ratio * m2 (an unoccluded view of a box shows at least its middle extent; min_ratio is the room left for
+ * occlusion); NO_SHAPE n_used < min_used or flags != 0.  A segment is compatible with an object when no bit is set.  The gate is not
+ * exclusive: two objects of like size keep the same segments.  Defaults slack 0.25, min_ratio 0.5, min_used 3: chosen from the geometry
+ * argument above, not fitted to data.  stocs_check_segment_gate_params: slack finite and >= 0, min_ratio in [0, 1], min_used >= 1,
+ * reserved 0.  stocs_segment_gate is host only: reasons[k * n_labels + l] for object k and label l + 1.
+ *
+ * stocs_segment_assign: shapes, the gate (on the device, one lane per (object, label) pair) and the class stack in one launch sequence.
+ * class_stack: n_objects images of height * width uint16, object-major, what stocs_ingest_scene_multi takes: image k holds 10000 where
+ * the pixel's label is compatible with object k (used or not), else 0.  Checked in this order: (1) NULL cam, depth, labels or result:
+ * STOCS_ERR_INVALID; (2) n_labels < 0 or above 2^22, width or height < 1: STOCS_ERR_INVALID; more than 2^22 pixels: STOCS_ERR_CAPACITY;
+ * (3) n_objects outside 0 .. STOCS_MAX_FRAME_OBJECTS: STOCS_ERR_INVALID; (4) NULL shapes with n_labels > 0; with n_objects > 0 NULL objects,
+ * class_stack, or reasons with n_labels > 0: STOCS_ERR_INVALID; (5) max_depth not finite or not above 0, gate parameters outside their range
+ * (NULL with n_objects > 0: the defaults), an object's diameter or extent negative or not finite: STOCS_ERR_INVALID.  n_labels == 0 is not an
+ * error: the stack comes back zero.  n_objects == 0 (objects, gate, reasons, class_stack ignored) is the shapes call alone, and
+ * stocs_segment_shapes is that. ---- */
+#define STOCS_SHAPE_EMPTY     1
+#define STOCS_SHAPE_NONFINITE 2
+#define STOCS_GATE_TOO_LARGE  1
+#define STOCS_GATE_TOO_SMALL  2
+#define STOCS_GATE_NO_SHAPE   4
+typedef struct stocs_segment_shape {
+    int32_t n_used, flags;      /* STOCS_SHAPE_*                                                                      */
+    float   centroid[3];
+    float   eigenvalue[3];      /* of the covariance, m^2, descending                                                 */
+    float   axis[3][3];         /* axis[k]: the unit eigenvector of eigenvalue[k]                                     */
+    float   lo[3], hi[3];       /* the range of (p - centroid) . axis[k] over the used pixels                         */
+    float   extent[3];          /* hi - lo                                                                            */
+    int32_t reserved[6];
+} stocs_segment_shape;          /* 128 bytes */
+typedef struct stocs_segment_shapes_result { int32_t n_labelled, n_used, n_invalid, n_far, n_out_of_range, reserved[3]; } stocs_segment_shapes_result; /* 32 bytes */
+typedef struct stocs_object_size { float diameter; float extent[3]; } stocs_object_size;                    /* 16 bytes */
+typedef struct stocs_segment_gate_params { float slack, min_ratio; int32_t min_used, reserved; } stocs_segment_gate_params; /* 16 bytes */
+void stocs_default_segment_gate_params(stocs_segment_gate_params*);
+int  stocs_check_segment_gate_params(const stocs_segment_gate_params*);       /* host only */
+int  stocs_segment_gate(const stocs_segment_shape* shapes, int n_labels, const stocs_object_size* objects, int n_objects,
+                        const stocs_segment_gate_params* params /* NULL: the defaults */, uint8_t* reasons /* n_objects x n_labels */);   /* host only */
+int  stocs_segment_shapes(const stocs_camera* cam, const uint16_t* depth, const int32_t* labels, int n_labels, float max_depth, int device,
+                          stocs_segment_shape* shapes /* n_labels */, int64_t* moments /* n_labels x 10 or NULL */, stocs_segment_shapes_result* result);
+int  stocs_points_shape(const float* pos3, int n, int device, stocs_segment_shape* shape, int64_t* moments10 /* or NULL */);
+int  stocs_segment_assign(const stocs_camera* cam, const uint16_t* depth, const int32_t* labels, int n_labels, float max_depth,
+                          const stocs_object_size* objects, int n_objects, const stocs_segment_gate_params* gate_params, int device,
+                          stocs_segment_shape* shapes, int64_t* moments, uint8_t* reasons, uint16_t* class_stack, stocs_segment_shapes_result* result);
+int  stocs_segment_shapes_table(int* slots);                                  /* host only: labels a tile's LDS table holds */
+/* with STOCS_SEGMENT_CLOCK=1: the HIP-event time of the calling thread's last shapes / points / assign call, every kernel of it, without
+ * the copies up and down (STOCS_ERR_STATE without such a call) */
+int  stocs_segment_shapes_last_device_ms(float* shapes_ms);
+
 /* ---- files either side of the path (host code; zlib only): what the reference's constructor and driver read and
  * write through OpenCV / PCL.  stocs_png_read: 8/16-bit grey / RGB (+alpha), non-interlaced; pixels = height rows of
  * width*channels samples of bit_depth/8 bytes, 16-bit in host byte order; pixels == NULL queries the sizes.

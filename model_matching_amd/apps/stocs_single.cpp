@@ -97,6 +97,11 @@
 // refused without it): touching objects are cut apart at concave creases before the labelling (stocs_segment_frame_convex: bend radius and
 // smoothing radius in pixels, the bend angle in degrees, which becomes bend_cos here; the library's defaults unless given), and a
 // "segment convex: .. triples tested, .. cut, .. pixels cut" line follows.
+// <scene> a,b,c --segment [...] [--segment-gate slack[,min_ratio]]: several objects of a depth-only frame.  One stocs_segment_frame, one
+// stocs_segment_assign (each segment's 3-D shape against each object's size, from its model cloud: the extents of stocs_points_shape and
+// their diagonal as the diameter; the library's gate defaults unless given), the per-object class stack into the multi-object ingest; one
+// "segment assign: <object>: k of n segments" line per object.  The gate is not exclusive: objects of like size keep the same segments
+// (--scene-select chooses among them).  --segment-gate without --segment is refused; with a single object it takes the same path.
 // The reference edits its per-data-set constants in the source (README.md:42-66); here they are options with the
 // reference's YCB values as defaults.
 #include <algorithm>
@@ -677,8 +682,25 @@ static int run_scene_select(const std::string& scene_path, const std::vector<std
     return 0;
 }
 
+// --segment with several objects (or --segment-gate): the class images come from the depth image and the size gate, not from probability_maps
+struct SegmentAssignOptions {
+    bool on, convex;
+    stocs_segment_params prm;
+    stocs_segment_convex_params cvx;
+    stocs_segment_gate_params gate;
+};
+static void print_segment_lines(std::ostream& os, const stocs::SegmentedFrame& seg, bool convex, const stocs_segment_convex_params& cvx) {
+    const stocs_segment_result& sr = seg.result;
+    if (convex)
+        os << "segment convex: radius " << cvx.bend_radius << ", smoothing " << cvx.smooth_radius << ", cos " << cvx.bend_cos << ": " << seg.convex.n_tested_h
+           << " + " << seg.convex.n_tested_v << " triples tested, " << seg.convex.n_cut_h << " + " << seg.convex.n_cut_v << " cut, " << seg.convex.n_cut
+           << " pixels cut" << std::endl;
+    os << "segment: plane " << (sr.plane_found ? "found" : "not found") << " (" << sr.plane[0] << " " << sr.plane[1] << " " << sr.plane[2] << " " << sr.plane[3]
+       << "), " << sr.n_on_plane << " pixels on it, " << sr.n_components << " components, " << sr.n_segments << " segments kept" << std::endl;
+}
+
 static int run_frame_objects(const std::string& scene_path, const std::vector<std::string>& objects, uint64_t seed, int n_trials, int exact_ties,
-                             const SceneSelectOptions& scene_opt) {
+                             const SceneSelectOptions& scene_opt, const SegmentAssignOptions& seg_opt) {
     const size_t n = objects.size();
     std::vector<stocs::ModelCloud> models(n);
     std::vector<PPFMapType> maps(n);
@@ -688,7 +710,7 @@ static int run_frame_objects(const std::string& scene_path, const std::vector<st
         const std::string& obj = objects[k];
         const std::string model_path = repo_path + "/models/" + obj + "/model_search.ply", map_path = repo_path + "/models/" + obj + "/ppf_map";
         prob_paths[k] = scene_path + "/probability_maps/" + obj + ".png";
-        if (!stocs::file_exists(prob_paths[k])) { std::cerr << "object " << obj << ": no class probability map " << prob_paths[k] << std::endl; return 1; }
+        if (!seg_opt.on && !stocs::file_exists(prob_paths[k])) { std::cerr << "object " << obj << ": no class probability map " << prob_paths[k] << std::endl; return 1; }
         if (!stocs::file_exists(model_path)) { std::cerr << "object " << obj << ": no model " << model_path << std::endl; return 1; }
         rgbd::load_ppf_map(map_path, maps[k]);
         if (maps[k].location.empty()) { std::cerr << "object " << obj << ": no readable ppf_map " << map_path << std::endl; return 1; }
@@ -702,7 +724,23 @@ static int run_frame_objects(const std::string& scene_path, const std::vector<st
     }
     std::cout << "############# LOADING OBJECT COMPLETE ################" << std::endl;
     std::vector<stocs::SceneCloud> scenes;
+    std::vector<uint16_t> seg_depth, seg_stack;   // --segment: the frame and the gate's class stack (object-major), kept for --scene-select
     try {
+        if (seg_opt.on) {
+            stocs::read_image(scene_path + "/depth.png", 1, 16, image_width, image_height, &seg_depth);
+            const stocs::SegmentedFrame seg = seg_opt.convex ? stocs::segment_frame(seg_depth.data(), cam_intrinsics, image_width, image_height, depth_scale, seg_opt.prm, seg_opt.cvx)
+                                                             : stocs::segment_frame(seg_depth.data(), cam_intrinsics, image_width, image_height, depth_scale, seg_opt.prm);
+            print_segment_lines(std::cout, seg, seg_opt.convex, seg_opt.cvx);
+            std::vector<stocs_object_size> sizes(n);
+            for (size_t k = 0; k < n; ++k) sizes[k] = stocs::object_size(models[k].pos);
+            stocs::SegmentAssignment as = stocs::segment_assign(seg_depth.data(), seg.labels.data(), seg.result.n_segments, sizes, cam_intrinsics, image_width, image_height,
+                                                                depth_scale, seg_opt.prm.max_depth, seg_opt.gate);
+            for (size_t k = 0; k < n; ++k)
+                std::cout << "segment assign: " << objects[k] << ": " << as.compatible((int)k) << " of " << as.n_labels << " segments" << std::endl;
+            seg_stack.swap(as.class_stack);
+            scenes = stocs::load_frame_scenes(seg_depth.data(), seg_stack.data(), std::vector<float>(n, class_threshold), NULL, cam_intrinsics, image_width, image_height,
+                                              depth_scale, voxel_size);
+        } else
         scenes = stocs::load_frame_scenes(scene_path + "/depth.png", prob_paths, std::vector<float>(n, class_threshold), scene_path + "/probability_maps/edge.png",
                                           cam_intrinsics, image_width, image_height, depth_scale, voxel_size);
     } catch (const std::exception& e) {
@@ -736,7 +774,8 @@ static int run_frame_objects(const std::string& scene_path, const std::vector<st
                                     std::string(), scene_opt.on ? &trial_results[k] : NULL);
                 if (scene_opt.on) {
                     std::vector<uint16_t> prob;
-                    stocs::read_image(prob_paths[k], 1, 16, image_width, image_height, &prob);
+                    if (seg_opt.on) prob.assign(seg_stack.begin() + (std::ptrdiff_t)(k * (size_t)image_width * image_height), seg_stack.begin() + (std::ptrdiff_t)((k + 1) * (size_t)image_width * image_height));
+                    else stocs::read_image(prob_paths[k], 1, 16, image_width, image_height, &prob);
                     est->set_frame(frame_depth.data(), prob.data(), cam_intrinsics, depth_scale);
                     kept[k] = std::move(est);
                 }
@@ -783,6 +822,8 @@ int main(int argc, char** argv) {
     stocs_segment_params seg_prm = stocs::default_segment_params();
     bool segment_convex = false;                                            // --segment-convex [r[,s[,deg]]]
     stocs_segment_convex_params seg_cvx = stocs::default_segment_convex_params();
+    bool segment_gate = false, segment_gate_bad = false;                    // --segment-gate slack[,min_ratio]
+    stocs_segment_gate_params seg_gate = stocs::default_segment_gate_params();
     std::string mesh_path, surface = "points";
     bool have_vsd_delta = false, have_surfel_radius = false;
     stocs_instance_params inst_prm = stocs::stocs_estimator::default_instance_params();
@@ -811,6 +852,14 @@ int main(int argc, char** argv) {
             if (got < 1 || got > 3 || (size_t)std::count(sv.begin(), sv.end(), ',') + 1 != (size_t)got || !(deg >= 0.0f && deg <= 90.0f)) segment_bad = true;
             if (got == 3) seg_cvx.bend_cos = std::min(1.0f, std::max(0.0f, (float)std::cos((double)deg * 3.14159265358979323846 / 180.0)));   // degrees become bend_cos here
             if (stocs_check_segment_convex_params(&seg_cvx) != STOCS_OK) segment_bad = true;
+            continue;
+        }
+        if (std::string(argv[i]) == "--segment-gate") {   // slack[,min_ratio]: the size gate between segments and objects
+            segment_gate = true;
+            const std::string sv = i + 1 < argc ? argv[i + 1] : "";
+            char tail = 0;
+            const int got = sscanf(sv.c_str(), "%f,%f%c", &seg_gate.slack, &seg_gate.min_ratio, &tail);
+            if (got < 1 || got > 2 || (size_t)std::count(sv.begin(), sv.end(), ',') + 1 != (size_t)got || stocs_check_segment_gate_params(&seg_gate) != STOCS_OK) segment_gate_bad = true;
             continue;
         }
         if (std::string(argv[i]) == "--vsd") { vsd_opt.on = true; --i; continue; }   // with --gt: the visible-surface discrepancy too
@@ -904,8 +953,13 @@ int main(int argc, char** argv) {
         }
     }
 
-    if (segment_bad || ((segment_edges || segment_convex) && !do_segment) || (do_segment && (clouds || a2.find(',') != std::string::npos))) {   // refused before any search
-        std::cerr << "--segment [tol[,min_pixels]] needs a scene directory, a single object, tol > 0 and min_pixels >= 1; --segment-edges needs --segment; "
+    const bool segment_assign = do_segment && !clouds && (segment_gate || a2.find(',') != std::string::npos);   // the multi-object path of --segment
+    if (segment_gate && (!do_segment || segment_gate_bad || clouds)) {   // refused before any search
+        std::cerr << "--segment-gate slack[,min_ratio] needs --segment, a scene directory, slack >= 0 and min_ratio in [0, 1]" << std::endl;
+        return -1;
+    }
+    if (segment_bad || ((segment_edges || segment_convex) && !do_segment) || (do_segment && clouds) || (segment_assign && segment_edges)) {   // refused before any search
+        std::cerr << "--segment [tol[,min_pixels]] needs a scene directory, tol > 0 and min_pixels >= 1; --segment-edges needs --segment and a single object without --segment-gate; "
                      "--segment-convex [r[,s[,deg]]] needs --segment, r in 0..8, s in 0..4 and 0 <= deg <= 90" << std::endl;
         return -1;
     }
@@ -1012,7 +1066,7 @@ int main(int argc, char** argv) {
         return -1;
     }
 
-    if (!clouds && a2.find(',') != std::string::npos) {
+    if (!clouds && (a2.find(',') != std::string::npos || segment_assign)) {
         std::vector<std::string> objects;
         std::stringstream names(a2);
         for (std::string o; std::getline(names, o, ',');) objects.push_back(o);
@@ -1021,10 +1075,12 @@ int main(int argc, char** argv) {
             if (objects[k].empty() || std::count(objects.begin(), objects.end(), objects[k]) > 1) { std::cerr << "object list " << a2 << ": empty or repeated name" << std::endl; return -1; }
         }
         if (do_cluster || n_refine || !out_path.empty() || !dbg_dir.empty() || !edge_path.empty() || !track_path.empty() || !gt_path.empty()) {
-            std::cerr << "several objects: --cluster, --refine, --out, --dbg, --edge, --track and --gt take a single object" << std::endl;
+            std::cerr << (objects.size() > 1 ? "several objects" : "--segment-gate (the path of several objects, also with one)")
+                      << ": --cluster, --refine, --out, --dbg, --edge, --track and --gt take a single object" << (objects.size() > 1 ? "" : " without --segment-gate") << std::endl;
             return -1;
         }
-        return run_frame_objects(a1, objects, seed, n_trials, exact_ties, scene_opt);
+        const SegmentAssignOptions seg_opt = {segment_assign, segment_convex, seg_prm, seg_cvx, seg_gate};
+        return run_frame_objects(a1, objects, seed, n_trials, exact_ties, scene_opt, seg_opt);
     }
 
     std::unique_ptr<stocs::stocs_estimator> est;

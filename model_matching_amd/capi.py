@@ -185,6 +185,36 @@ class SegmentConvexResult(C.Structure):
                 ("reserved", C.c_int32 * 3)]
 
 
+SHAPE_EMPTY, SHAPE_NONFINITE = 1, 2
+GATE_TOO_LARGE, GATE_TOO_SMALL, GATE_NO_SHAPE = 1, 2, 4
+MAX_FRAME_OBJECTS = 64
+
+
+class SegmentShape(C.Structure):
+    _fields_ = [("n_used", C.c_int32), ("flags", C.c_int32), ("centroid", C.c_float * 3), ("eigenvalue", C.c_float * 3), ("axis", (C.c_float * 3) * 3),
+                ("lo", C.c_float * 3), ("hi", C.c_float * 3), ("extent", C.c_float * 3), ("reserved", C.c_int32 * 6)]
+
+
+SHAPE_DTYPE = np.dtype([("n_used", np.int32), ("flags", np.int32), ("centroid", np.float32, (3,)), ("eigenvalue", np.float32, (3,)), ("axis", np.float32, (3, 3)),
+                        ("lo", np.float32, (3,)), ("hi", np.float32, (3,)), ("extent", np.float32, (3,)), ("reserved", np.int32, (6,))])
+
+
+class SegmentShapesResult(C.Structure):
+    _fields_ = [("n_labelled", C.c_int32), ("n_used", C.c_int32), ("n_invalid", C.c_int32), ("n_far", C.c_int32), ("n_out_of_range", C.c_int32),
+                ("reserved", C.c_int32 * 3)]
+
+
+class ObjectSize(C.Structure):
+    _fields_ = [("diameter", C.c_float), ("extent", C.c_float * 3)]
+
+
+OBJECT_DTYPE = np.dtype([("diameter", np.float32), ("extent", np.float32, (3,))])
+
+
+class SegmentGateParams(C.Structure):
+    _fields_ = [("slack", C.c_float), ("min_ratio", C.c_float), ("min_used", C.c_int32), ("reserved", C.c_int32)]
+
+
 class SceneRecord(C.Structure):
     _fields_ = [("footprint", C.c_int32), ("no_depth", C.c_int32), ("agree", C.c_int32), ("in_front", C.c_int32), ("behind", C.c_int32),
                 ("on_mask", C.c_int32), ("claimed", C.c_int32)]
@@ -305,6 +335,16 @@ SIGNATURES = {
                                              C.POINTER(C.c_uint16), _ip, _u8p, _u8p, _fp, C.POINTER(SegmentRecord), C.c_int, C.POINTER(SegmentResult),
                                              C.POINTER(SegmentConvexResult)]),
     "stocs_segment_last_bend_ms": (C.c_int, [C.POINTER(C.c_float)]),
+    "stocs_default_segment_gate_params": (None, [C.POINTER(SegmentGateParams)]),
+    "stocs_check_segment_gate_params": (C.c_int, [C.POINTER(SegmentGateParams)]),
+    "stocs_segment_gate": (C.c_int, [C.POINTER(SegmentShape), C.c_int, C.POINTER(ObjectSize), C.c_int, C.POINTER(SegmentGateParams), _u8p]),
+    "stocs_segment_shapes": (C.c_int, [C.POINTER(Camera), C.POINTER(C.c_uint16), _ip, C.c_int, C.c_float, C.c_int, C.POINTER(SegmentShape), _i64p,
+                                       C.POINTER(SegmentShapesResult)]),
+    "stocs_points_shape": (C.c_int, [_fp, C.c_int, C.c_int, C.POINTER(SegmentShape), _i64p]),
+    "stocs_segment_assign": (C.c_int, [C.POINTER(Camera), C.POINTER(C.c_uint16), _ip, C.c_int, C.c_float, C.POINTER(ObjectSize), C.c_int, C.POINTER(SegmentGateParams),
+                                       C.c_int, C.POINTER(SegmentShape), _i64p, _u8p, C.POINTER(C.c_uint16), C.POINTER(SegmentShapesResult)]),
+    "stocs_segment_shapes_table": (C.c_int, [_intp]),
+    "stocs_segment_shapes_last_device_ms": (C.c_int, [C.POINTER(C.c_float)]),
     "stocs_icp_point_to_plane": (C.c_int, [_fp, C.c_int, _fp, _fp, C.c_int, C.c_int, C.c_float, C.c_int, _fp, _intp]),
     "stocs_refine_poses": (C.c_int, [_vp, _fp, C.c_int, _ip, C.c_int, C.c_int, C.c_float, _fp, _fp, _fp, _ip, _ip]),
     "stocs_refine_detail": (C.c_int, [_vp, _fp, _ip, C.c_int, C.c_float, _ip, _u8p, C.POINTER(C.c_double)]),

@@ -4,5 +4,6 @@
 #define STOCS_SEGMENT_H
 namespace stocs {
 void segment_trim();   // nothing of the thread's last stocs_segment_frame is in flight (the call synchronises before it returns)
+void segment_shapes_trim();   // segment_shapes.hip's cache, the same way (segment_trim calls it: stocs_trim gives both back)
 }
 #endif

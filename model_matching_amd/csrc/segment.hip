@@ -36,13 +36,12 @@
 
 #include "prims.h"
 #include "segment.h"
+#include "segment_rules.h"
 #include "stocs_ctx.h"
 #include "thread_cache.h"
 #include "wave_bits.h"
 
 namespace stocs {
-
-enum { SEG_MAX_BEND = 8, SEG_MAX_SMOOTH = 4, SEG_TILE_W = 64, SEG_TILE_H = 16, SEG_SCORE_PTS = 1024, SEG_SCORE_HYP = 64, SEG_SWEEPS = 12, SEG_MAX_HYP = 1 << 20, SEG_MAX_PIX = 1 << 22 };
 
 // what the kernels leave for the host: the result, the refit's count and nine moments, the winner's hypothesis
 struct SegHeader {
@@ -66,11 +65,7 @@ static_assert(offsetof(stocs_segment_result, n_above) == offsetof(stocs_segment_
 static_assert(offsetof(stocs_segment_convex_result, n_tested_h) == 0 && offsetof(stocs_segment_convex_result, n_cut) == 16, "seg_bend_store");
 
 __device__ __forceinline__ float seg_nan() { return __int_as_float(0x7fc00000); }   // the quiet NaN of "not foreground", "cut" and "outside the image"
-// pixel (row i, column j) at depth z -> x, y: in double, one cast each.  The smoothed points are formed by the same expression
-// (tests/segment_convex_ref.py relies on the two being equal bit for bit)
-__device__ __forceinline__ V3 seg_unproject(int i, int j, float z, float fx, float cx, float fy, float cy) {
-    return mk3((float)(((double)j - (double)cx) * (double)z / (double)fx), (float)(((double)i - (double)cy) * (double)z / (double)fy), z);
-}
+// seg_unproject, pixel -> point, is in segment_rules.h: the shapes of labelled regions (segment_shapes.hip) form their points by it too
 
 __global__ __launch_bounds__(256) void seg_points_kernel(const uint16_t* __restrict__ depth, int W, int H, float fx, float cx, float fy, float cy, float depth_scale,
                                                          float max_depth, int stride, int LW, float4* __restrict__ P, uint32_t* __restrict__ lat_flag,
@@ -161,12 +156,6 @@ __global__ __launch_bounds__(256) void seg_winner_kernel(const float* __restrict
             hdr->r.plane_found = ((double)c < (double)min_share * (double)ns) ? 0 : 1;
         }
     }
-}
-
-__device__ __forceinline__ long long wave_sum_ll(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 __global__ __launch_bounds__(256) void seg_refit_kernel(const float4* __restrict__ P, int npix, SegHeader* __restrict__ hdr) {
@@ -615,6 +604,7 @@ static thread_local SegLast tl_seg_last;
 void segment_trim() {
     tl_seg_cache.trim();
     tl_seg_last.drop_events();
+    segment_shapes_trim();
 }
 
 // STOCS_SEGMENT_FORM, STOCS_SEGMENT_BEND_FORM: unset, empty or 0 (the default), 1 or 2; what_1, what_2 name the two forms in the refusal

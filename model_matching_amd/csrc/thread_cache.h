@@ -1,7 +1,7 @@
 // thread_cache.h -- the memory that the entry points without a context keep for the calling thread: a grow-only arena per device, so a
 // caller that runs one frame after the other does no hipMalloc / hipFree after the first, and one grow-only pinned block for the staging of
-// what a call sends up and reads back.  ingest.hip and segment.hip each keep a thread_local instance of their own (two arenas, two pinned
-// blocks: a thread that does both evicts nothing of either); stocs_trim() gives both back.
+// what a call sends up and reads back.  ingest.hip, segment.hip and segment_shapes.hip each keep a thread_local instance of their own
+// (three arenas, three pinned blocks: a thread that ingests, segments and takes shapes evicts nothing of any); stocs_trim() gives all back.
 #ifndef STOCS_THREAD_CACHE_H
 #define STOCS_THREAD_CACHE_H
 

@@ -1557,6 +1557,106 @@ def segment_class_images(labels, ids=None):
     return out
 
 
+def segment_gate_params(**kw):
+    """stocs_segment_gate_params with the library's defaults (slack 0.25, min_ratio 0.5, min_used 3: from the geometry of a view, not fitted
+    to data) and kw on top; a value outside its range raises."""
+    L = capi.load()
+    return _params(capi.SegmentGateParams, L.stocs_default_segment_gate_params, L.stocs_check_segment_gate_params, kw, "gate parameter")
+
+
+def _shape_call(depth_u16, labels, K, depth_scale, n_labels):
+    d = np.ascontiguousarray(depth_u16, np.uint16)
+    lab = np.ascontiguousarray(labels, np.int32)
+    if lab.shape != d.shape or d.ndim != 2:
+        raise ValueError("label image %s, depth image %s" % (lab.shape, d.shape))
+    n = int(max(int(lab.max()), 0)) if n_labels is None else int(n_labels)
+    cam = capi.Camera(K[0], K[1], K[2], K[3], depth_scale, d.shape[1], d.shape[0], 0)
+    return d, lab, n, cam
+
+
+def _shape_counts(res):
+    return {f: getattr(res, f) for f, _ in capi.SegmentShapesResult._fields_ if f != "reserved"}
+
+
+def segment_shapes(depth_u16, labels, K, depth_scale, n_labels=None, max_depth=2.0, device=-1, moments=False):
+    """The 3-D shape of every labelled region of a depth frame (stocs_segment_shapes): labels is an int32 image, 0 = none, 1 .. n_labels
+    (None: labels.max()), from segment_frame or from anywhere else.  Returns (shapes, counts): shapes a structured array (capi.SHAPE_DTYPE:
+    n_used, flags, centroid, eigenvalue, axis, lo, hi, extent), counts the dict of n_labelled, n_used, n_invalid, n_far, n_out_of_range;
+    with moments=True the (n_labels, 10) int64 moments as a third value."""
+    L = capi.load()
+    d, lab, n, cam = _shape_call(depth_u16, labels, K, depth_scale, n_labels)
+    shapes = np.zeros(n, capi.SHAPE_DTYPE)
+    mom = np.zeros((n, 10), np.int64) if moments else None
+    res = capi.SegmentShapesResult()
+    capi.check(L.stocs_segment_shapes(C.byref(cam), d.ctypes.data_as(C.POINTER(C.c_uint16)), lab.ctypes.data_as(capi._ip), n, max_depth, device,
+                                      shapes.ctypes.data_as(C.POINTER(capi.SegmentShape)) if n else None, mom.ctypes.data_as(capi._i64p) if moments and n else None, C.byref(res)))
+    return (shapes, _shape_counts(res), mom) if moments else (shapes, _shape_counts(res))
+
+
+def points_shape(pos, device=-1, moments=False):
+    """The same descriptor for a point cloud (stocs_points_shape), e.g. a preprocessed model: one record of capi.SHAPE_DTYPE."""
+    L = capi.load()
+    p = np.ascontiguousarray(pos, np.float32).reshape(-1, 3)
+    shape = np.zeros(1, capi.SHAPE_DTYPE)
+    mom = np.zeros(10, np.int64)
+    capi.check(L.stocs_points_shape(p.ctypes.data_as(capi._fp) if len(p) else None, len(p), device, shape.ctypes.data_as(C.POINTER(capi.SegmentShape)), mom.ctypes.data_as(capi._i64p)))
+    return (shape[0], mom) if moments else shape[0]
+
+
+def object_size(model_pos, diameter=None, device=-1):
+    """An object's size for the gate, a record of capi.OBJECT_DTYPE: the extents are points_shape's of the model cloud; the diameter is the
+    caller's exact one (StocsEstimator.model_diameter()) or, with None, the diagonal sqrt(m1^2 + m2^2 + m3^2) of the extents, formed in
+    double and cast once: an upper bound of the diameter, so the gate's TOO_LARGE stays sound."""
+    ext = points_shape(model_pos, device=device)["extent"]
+    out = np.zeros((), capi.OBJECT_DTYPE)
+    out["extent"] = ext
+    out["diameter"] = np.float32(np.sqrt(np.sum(ext.astype(np.float64) ** 2))) if diameter is None else np.float32(diameter)
+    return out
+
+
+def _objects(objects):
+    o = np.ascontiguousarray(np.atleast_1d(np.asarray(objects, capi.OBJECT_DTYPE)))
+    return o, o.ctypes.data_as(C.POINTER(capi.ObjectSize)) if len(o) else None
+
+
+def segment_gate(shapes, objects, **gate):
+    """The size gate on the host (stocs_segment_gate): the (n_objects, n_labels) uint8 reason bits (capi.GATE_TOO_LARGE, GATE_TOO_SMALL,
+    GATE_NO_SHAPE); 0: the segment is compatible with the object.  The gate is not exclusive.  gate: the fields of stocs_segment_gate_params."""
+    L = capi.load()
+    s = np.ascontiguousarray(np.atleast_1d(np.asarray(shapes, capi.SHAPE_DTYPE)))
+    o, op = _objects(objects)
+    g = segment_gate_params(**gate)
+    reasons = np.zeros((len(o), len(s)), np.uint8)
+    capi.check(L.stocs_segment_gate(s.ctypes.data_as(C.POINTER(capi.SegmentShape)) if len(s) else None, len(s), op, len(o), C.byref(g),
+                                    reasons.ctypes.data_as(capi._u8p) if reasons.size else None))
+    return reasons
+
+
+def segment_assign(depth_u16, labels, K, depth_scale, objects, n_labels=None, max_depth=2.0, device=-1, **gate):
+    """Shapes, the gate and the per-object class images of a labelled depth frame in one call (stocs_segment_assign).  objects: records of
+    capi.OBJECT_DTYPE (object_size).  Returns (shapes, reasons, stack, counts): reasons (n_objects, n_labels) uint8, stack the
+    (n_objects, H, W) uint16 images that ingest_scene_multi takes, 10000 where the pixel's label is compatible with the object."""
+    L = capi.load()
+    d, lab, n, cam = _shape_call(depth_u16, labels, K, depth_scale, n_labels)
+    o, op = _objects(objects)
+    g = segment_gate_params(**gate)
+    shapes = np.zeros(n, capi.SHAPE_DTYPE)
+    reasons = np.zeros((len(o), n), np.uint8)
+    stack = np.zeros((len(o),) + d.shape, np.uint16)
+    res = capi.SegmentShapesResult()
+    capi.check(L.stocs_segment_assign(C.byref(cam), d.ctypes.data_as(C.POINTER(C.c_uint16)), lab.ctypes.data_as(capi._ip), n, max_depth, op, len(o), C.byref(g), device,
+                                      shapes.ctypes.data_as(C.POINTER(capi.SegmentShape)) if n else None, None,
+                                      reasons.ctypes.data_as(capi._u8p) if reasons.size else None, stack.ctypes.data_as(C.POINTER(C.c_uint16)) if len(o) else None, C.byref(res)))
+    return shapes, reasons, stack, _shape_counts(res)
+
+
+def segment_shapes_last_device_ms():
+    """The kernels' HIP-event time of the calling thread's last segment_shapes / points_shape / segment_assign under STOCS_SEGMENT_CLOCK=1."""
+    a = C.c_float(0)
+    capi.check(capi.load().stocs_segment_shapes_last_device_ms(C.byref(a)))
+    return a.value
+
+
 def segment_last_device_ms():
     """(score_ms, label_ms) of the calling thread's last segment_frame under STOCS_SEGMENT_CLOCK=1."""
     a, b = C.c_float(0), C.c_float(0)

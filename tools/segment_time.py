@@ -13,7 +13,12 @@ LDS) beside the label group's, the host time of the whole call with and without 
 from the parent commit), the plain and the convex call through that library in alternation with the same through this one, their HIP-event
 group times beside them: A/B evidence that nothing existing moved.
 
-    python tools/segment_time.py --convex [--parent-lib PATH] [--out profiles/segment_convex_time.json]"""
+    python tools/segment_time.py --convex [--parent-lib PATH] [--out profiles/segment_convex_time.json]
+
+With --shapes: the shapes step (stocs_segment_shapes, and stocs_segment_assign with two objects) on the labels of the 640 x 480 frames, its
+HIP-event time beside the label group's of the same frame -> profiles/segment_shapes_time.json; --parent-lib as above.
+
+    python tools/segment_time.py --shapes [--parent-lib PATH] [--out profiles/segment_shapes_time.json]"""
 import glob
 import json
 import os
@@ -122,7 +127,44 @@ def main_convex():
         f.write("\n")
 
 
+def main_shapes():
+    out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "segment_shapes_time.json")
+    parent = sys.argv[sys.argv.index("--parent-lib") + 1] if "--parent-lib" in sys.argv else None
+    os.environ["STOCS_SEGMENT_CLOCK"] = "1"
+    os.environ.pop("STOCS_SEGMENT_FORM", None)
+    fr = [f for f in frames() if "640x480" in f[0]]
+    this_lib = os.path.join(ROOT, "model_matching_amd", "libstocs_hip.so")
+    order = ("this", "parent", "this", "parent", "parent", "this")
+    aa = [plain_through(parent if w == "parent" else this_lib, fr) for w in order] if parent else None
+    objects = np.zeros(2, E.capi.OBJECT_DTYPE)
+    objects["diameter"] = (0.12, 0.25); objects["extent"] = ((0.10, 0.06, 0.04), (0.16, 0.16, 0.06))
+    rows = []
+    for name, d, K, scale, kw in fr:
+        (res, _, img), seg_med, _, (score, label) = timed(lambda: E.segment_frame(d, K, scale, **kw), E.segment_last_device_ms)
+        lab, n = img["labels"], res["n_segments"]
+        (_, counts), sh_med, sh_min, (sh_dev,) = timed(lambda: E.segment_shapes(d, lab, K, scale, n_labels=n, max_depth=kw.get("max_depth", 2.0)), lambda: (E.segment_shapes_last_device_ms(),))
+        out4, as_med, as_min, (as_dev,) = timed(lambda: E.segment_assign(d, lab, K, scale, objects, n_labels=n, max_depth=kw.get("max_depth", 2.0)), lambda: (E.segment_shapes_last_device_ms(),))
+        row = {"frame": name, "n_segments": n, "n_used": counts["n_used"], "segment_frame": {"call_host_ms_median": seg_med, "score_device_ms_median": score, "label_device_ms_median": label},
+               "segment_shapes": {"call_host_ms_median": sh_med, "call_host_ms_min": sh_min, "device_ms_median": sh_dev},
+               "segment_assign_2_objects": {"call_host_ms_median": as_med, "call_host_ms_min": as_min, "device_ms_median": as_dev, "compatible": (out4[1] == 0).sum(axis=1).tolist()}}
+        if aa:
+            row["plain_call_host_ms_median_aa"] = [[w, a[name][0]] for w, a in zip(order, aa)]
+            row["plain_device_ms_median_aa"] = [[w, a[name][4]] for w, a in zip(order, aa)]      # [score, label]
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+    out = {"what": "stocs_segment_shapes and stocs_segment_assign (two objects) on an MI355X on the labels of stocs_segment_frame, 640 x 480 frames: HIP-event time of every "
+                   "kernel of the call (moments, shape, extents, finish; gate and stack with objects) beside the label group's of the same frame, host time of the whole call "
+                   "through the Python wrapper; medians of %d calls after %d.  plain_call_host_ms_median_aa: the plain stocs_segment_frame through a library built from the "
+                   "parent commit and through this one, each in a process of its own, in the order listed" % (REPS, WARM),
+           "rows": rows, "unmeasured": "frame sizes other than 640 x 480; real frames beyond the three examples; more than two objects; labels not made by stocs_segment_frame"}
+    with open(out_path, "w") as f:
+        json.dump(out, f, indent=1)
+        f.write("\n")
+
+
 def main():
+    if "--shapes" in sys.argv:
+        return main_shapes()
     if "--convex" in sys.argv:
         return main_convex()
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else os.path.join(ROOT, "profiles", "segment_time.json")
